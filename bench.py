@@ -59,6 +59,39 @@ def profile_stale(stored_sha):
         return True
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, prefix=""):
+    """--dump-outputs: write what the timed block returned, one row per timed step (row -1 = the last step), as <out_dir>/<prefix><name>.npy in
+    float32 / float64.  Past DUMP_MAX_BYTES in all, a fixed, seeded sample of the rows is kept (the last step always among them); `step_index` names the rows."""
+    arrays = {k: np.ascontiguousarray(v) for k, v in arrays.items()}
+    n = len(next(iter(arrays.values())))
+    row_bytes = sum(v.nbytes // max(n, 1) for v in arrays.values()) + 8
+    keep = np.arange(n)
+    if n * row_bytes > DUMP_MAX_BYTES:
+        m = max(1, DUMP_MAX_BYTES // row_bytes)
+        keep = np.union1d(np.random.default_rng(0).choice(n - 1, size=m - 1, replace=False), [n - 1])
+    arrays = {k: v[keep] for k, v in arrays.items()}
+    arrays["step_index"] = keep.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in arrays.items():
+        assert v.dtype in (np.float32, np.float64), (k, v.dtype)
+        np.save(os.path.join(out_dir, prefix + k + ".npy"), v)
+
+
+def gicp_result_arrays(results, valid, status):
+    """the GicpResult records of engine.icp_alignment_batch as arrays (integers as float64)"""
+    return {"T": np.array([list(r.T) for r in results], dtype=np.float32).reshape(-1, 4, 4),
+            "T64": np.array([list(r.T64) for r in results], dtype=np.float64).reshape(-1, 4, 4),
+            "H": np.array([list(r.H) for r in results], dtype=np.float64).reshape(-1, 6, 6),
+            "fitness": np.array([r.fitness for r in results], dtype=np.float64),
+            "iterations": np.array([r.iterations for r in results], dtype=np.float64),
+            "converged": np.array([r.converged for r in results], dtype=np.float64),
+            "lm_failed": np.array([r.lm_failed for r in results], dtype=np.float64),
+            "valid": np.array(valid, dtype=np.float64), "status": np.array(status, dtype=np.float64)}
+
+
 def pct(xs):
     xs = np.sort(np.asarray(xs, dtype=np.float64))
     return {"median": round(float(np.median(xs)), 4), "p10": round(float(np.percentile(xs, 10)), 4), "p90": round(float(np.percentile(xs, 90)), 4), "n": int(len(xs))}
@@ -455,6 +488,10 @@ def single_process(args, engine, synth, json_fd):
     assert all(r.status == 0 for r in recs), [r.status for r in recs]
     per_gpu_ms, gather_ms = mg.timing()
     winner = best if best is not None else min(recs, key=lambda r: (r.fitness, r.pair_id))     # forced iterations never "converge": rank by score
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"T": np.array([list(r.T) for r in recs], dtype=np.float32).reshape(-1, 4, 4),
+                                         **{f: np.array([getattr(r, f) for r in recs], dtype=np.float64) for f in ("fitness", "pair_id", "status", "valid", "converged", "iterations")}})
+        np.save(os.path.join(args.dump_outputs, "winner.npy"), np.array([winner.pair_id, winner.converged, winner.fitness] + list(winner.T), dtype=np.float64))
     # roofline leg on GPU 0 with a context of its own (the same kernels the qn_multi contexts run)
     torch.cuda.set_device(0)
     ctx = engine.Context(N_PTS + 1024, device=0)
@@ -501,8 +538,11 @@ def main():
     ap.add_argument("--repeats", type=int, default=5, help="extra timed repeats of the --steps block for the spread of `value` (reported in config.value_repeats)")
     ap.add_argument("--shift", type=float, default=None, help="developer: scene-window shift of the synthetic pairs in metres (default: the generator's 5 m = ~96 %% overlap; 24 = 80 %%)")
     ap.add_argument("--batch-pairs", type=int, default=64, help="BASELINE configs[3]: candidate pairs of one query, sharded over the ranks")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what they computed (one row per step) as DIR/<name>.npy (rank r > 0: DIR/rank<r>_<name>.npy)")
     ap.add_argument("--single-process", action="store_true", help="ONE process drives all --gpus N devices through qn_multi_init(N) / qn_multi_align_best (ncclCommInitAll + grouped ncclAllGather inside the C-ABI): the path a C++ host like the reference's single process would call")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1 (the timed block is exactly --steps registrations per rank)")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1 and not args.single_process:
         return spawn_ranks(args)
@@ -625,6 +665,11 @@ def main():
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=cdev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {**gicp_result_arrays(results, valid, status), "pair_id": np.array([rank + world * (j % len(pairs)) for j in range(args.steps)], dtype=np.float64)},
+                     prefix="" if rank == 0 else "rank%d_" % rank)
+        if rank == 0:
+            np.save(os.path.join(args.dump_outputs, "winner.npy"), np.array(winner, dtype=np.float64))
     # ---- spread of `value`: the same --steps block, `repeats` more times (a 60 ms timed region cannot resolve a few per cent on its own)
     rep_vals = []
     for _ in range(max(0, args.repeats)):

@@ -109,3 +109,20 @@ def test_single_process_bench_mode_runs_qn_multi_over_every_visible_gpu():
     c = line["config"]
     assert line["n_gpus"] == n and c["rccl_ranks"] == n and len(c["per_gpu_pairs_per_s"]) == n and line["value"] > 0
     assert line["roofline"]["frac"] > 0 and c["gather_ms"] >= 0
+
+
+def test_bench_dump_outputs_holds_the_timed_steps(tmp_path):
+    """`--dump-outputs DIR`: the records the timed block returned, one row per step (exactly --steps of them), float32 / float64 only; a pair met twice
+    in the block gives the same record both times."""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "1", "--pairs", "2", "--repeats", "0",
+                          "--no-extras", "--no-cpu-baseline", "--no-quatro", "--dump-outputs", str(tmp_path)], capture_output=True, timeout=600)
+    assert out.returncode == 0, out.stderr.decode()[-2000:]
+    line = json.loads(out.stdout.decode().strip().splitlines()[-1])
+    assert line["steps"] == 5 and line["ms_per_step"] > 0
+    d = {f[:-4]: np.load(tmp_path / f) for f in os.listdir(tmp_path)}
+    assert all(v.dtype in (np.float32, np.float64) for v in d.values())
+    assert d["T"].shape == (5, 4, 4) and d["T64"].shape == (5, 4, 4) and d["fitness"].shape == (5,)
+    assert np.array_equal(d["step_index"], np.arange(5)) and np.array_equal(d["pair_id"], [0, 1, 0, 1, 0]) and not d["status"].any()
+    assert np.isfinite(d["T64"]).all() and d["winner"].shape == (19,)
+    for j in (2, 3, 4):
+        assert np.array_equal(d["T64"][j], d["T64"][j - 2]) and d["fitness"][j] == d["fitness"][j - 2]
