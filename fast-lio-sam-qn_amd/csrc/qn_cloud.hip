@@ -9,6 +9,8 @@
 // sort (8-bit digits, only as many passes as the leaf grid has bits; the input is in ascending point order and stability
 // keeps it so inside every leaf), leaf heads are compacted with the engine's own scan kernels and one thread per leaf sums
 // its points in ascending point order in f32 - the order the oracle fixes (PCL's own order inside a leaf is unspecified).
+// The corrected global map (qn_kf_build_map, fast_lio_sam_qn.cpp:302-316, 398-411, 435-448) reuses the store: every keyframe in one
+// transform launch, intensity carried in .w, a radix sort with 4096-key tiles, its own output slot.
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include <string>
@@ -103,17 +105,184 @@ __global__ void k_leaf_centroids(const float4* __restrict__ pts, const unsigned 
   out[m] = make_float4(sx / cnt, sy / cnt, sz / cnt, 1.0f);
 }
 
+// ---- corrected global map (fast_lio_sam_qn.cpp:302-316, 398-411, 435-448): transformPcd of EVERY keyframe with its corrected
+// pose, concatenation, voxelizePcd at save_voxel_resolution - xyz AND intensity (PointXYZI; VoxelGrid averages all fields).
+// Sized for 10^3 keyframes / 3e7 points: one transform launch for all keyframes, radix tiles of QN_MAP_TILE keys per block.
+#define QN_MAP_TILE 4096
+#define QN_MAP_ITEMS (QN_MAP_TILE / QN_BLOCK)
+__device__ __forceinline__ int wave_sum_i(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+struct MapKf { const float4* src; uint32_t off, n, blk0, has_i; };     // one listed keyframe: its concatenation offset, first tile, pose = its list position
+// transformPcd of every listed keyframe in ONE launch: tile b belongs to keyframe blk_kf[b] (the same f64 arithmetic and order as
+// k_kf_transform, so xyz is bit-identical to qn_kf_assemble's); intensity = the resident .w for qn_kf_add_xyzi keyframes, 0 for
+// qn_kf_add ones.  Fused: the tile's bounding box of the finite points and its count of non-finite ones -> part[b].
+__global__ void __launch_bounds__(QN_BLOCK) k_map_transform(const MapKf* __restrict__ kfs, const uint32_t* __restrict__ blk_kf, const double* __restrict__ poses,
+                                                            float4* __restrict__ out, BBoxOut* __restrict__ part) {
+  __shared__ int smn[QN_BLOCK / 64][3], smx[QN_BLOCK / 64][3], sbad[QN_BLOCK / 64];
+  const uint32_t k = blk_kf[blockIdx.x];
+  const MapKf f = kfs[k];
+  const double* T = poses + 16 * (size_t)k;
+  const uint32_t base = (blockIdx.x - f.blk0) * QN_MAP_TILE;
+  int mn[3] = {0x7fffffff, 0x7fffffff, 0x7fffffff}, mx[3] = {(int)0x80000000, (int)0x80000000, (int)0x80000000};
+  int bad = 0;
+#pragma unroll 4
+  for (int j = 0; j < QN_MAP_ITEMS; j++) {
+    const uint32_t i = base + j * QN_BLOCK + threadIdx.x;
+    if (i >= f.n) break;
+    const float4 p = f.src[i]; const double x = p.x, y = p.y, z = p.z;
+    const float4 q = make_float4((float)(((T[0] * x + T[1] * y) + T[2] * z) + T[3]), (float)(((T[4] * x + T[5] * y) + T[6] * z) + T[7]),
+                                 (float)(((T[8] * x + T[9] * y) + T[10] * z) + T[11]), f.has_i ? p.w : 0.0f);
+    out[f.off + i] = q;
+    if (!(isfinite(q.x) && isfinite(q.y) && isfinite(q.z))) { bad++; continue; }
+    const int ox = f2ord(q.x), oy = f2ord(q.y), oz = f2ord(q.z);
+    mn[0] = min(mn[0], ox); mn[1] = min(mn[1], oy); mn[2] = min(mn[2], oz);
+    mx[0] = max(mx[0], ox); mx[1] = max(mx[1], oy); mx[2] = max(mx[2], oz);
+  }
+#pragma unroll
+  for (int d = 0; d < 3; d++) { mn[d] = wave_min_i(mn[d]); mx[d] = wave_max_i(mx[d]); }
+  bad = wave_sum_i(bad);
+  const int wid = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) { for (int d = 0; d < 3; d++) { smn[wid][d] = mn[d]; smx[wid][d] = mx[d]; } sbad[wid] = bad; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < QN_BLOCK / 64; w++) { for (int d = 0; d < 3; d++) { mn[d] = min(mn[d], smn[w][d]); mx[d] = max(mx[d], smx[w][d]); } bad += sbad[w]; }
+    BBoxOut r; for (int d = 0; d < 3; d++) { r.mn[d] = mn[d]; r.mx[d] = mx[d]; } r.nonfinite = (uint32_t)bad;
+    part[blockIdx.x] = r;
+  }
+}
+// the per-tile partials -> one box and the total number of non-finite points (one block; deterministic, no atomics)
+__global__ void __launch_bounds__(QN_BLOCK) k_map_bbox_reduce(const BBoxOut* __restrict__ part, uint32_t nb, BBoxOut* __restrict__ out) {
+  __shared__ int smn[QN_BLOCK / 64][3], smx[QN_BLOCK / 64][3], sbad[QN_BLOCK / 64];
+  int mn[3] = {0x7fffffff, 0x7fffffff, 0x7fffffff}, mx[3] = {(int)0x80000000, (int)0x80000000, (int)0x80000000};
+  int bad = 0;
+  for (uint32_t b = threadIdx.x; b < nb; b += QN_BLOCK) {
+    const BBoxOut r = part[b];
+    for (int d = 0; d < 3; d++) { mn[d] = min(mn[d], r.mn[d]); mx[d] = max(mx[d], r.mx[d]); }
+    bad += (int)r.nonfinite;
+  }
+#pragma unroll
+  for (int d = 0; d < 3; d++) { mn[d] = wave_min_i(mn[d]); mx[d] = wave_max_i(mx[d]); }
+  bad = wave_sum_i(bad);
+  const int wid = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) { for (int d = 0; d < 3; d++) { smn[wid][d] = mn[d]; smx[wid][d] = mx[d]; } sbad[wid] = bad; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < QN_BLOCK / 64; w++) { for (int d = 0; d < 3; d++) { mn[d] = min(mn[d], smn[w][d]); mx[d] = max(mx[d], smx[w][d]); } bad += sbad[w]; }
+    BBoxOut r; for (int d = 0; d < 3; d++) { r.mn[d] = mn[d]; r.mx[d] = mx[d]; } r.nonfinite = (uint32_t)bad;
+    *out = r;
+  }
+}
+// leaf keys as k_voxel_keys computes them; a non-finite point gets the leaf `sentinel` (= number of cells, past every real leaf), so the
+// stable sort moves it behind all finite points in its original order and the leaf pass simply stops before it (no compaction pass)
+__global__ void k_map_keys(const float4* __restrict__ pts, uint32_t n, VoxelDims d, uint32_t sentinel, unsigned long long* __restrict__ keys) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float4 p = pts[i];
+  uint32_t leaf = sentinel;
+  if (isfinite(p.x) && isfinite(p.y) && isfinite(p.z)) {
+    const int i0 = (int)(floorf(p.x * d.inv) - (float)d.minb[0]);
+    const int i1 = (int)(floorf(p.y * d.inv) - (float)d.minb[1]);
+    const int i2 = (int)(floorf(p.z * d.inv) - (float)d.minb[2]);
+    leaf = (uint32_t)(i0 + i1 * d.div0 + i2 * d.div01);
+  }
+  keys[i] = ((unsigned long long)leaf << 32) | i;
+}
+// lanes of this wave whose digit equals mine (8 ballots), restricted to `valid` lanes
+__device__ __forceinline__ unsigned long long match_digit8(uint32_t d, bool valid) {
+  unsigned long long same = __ballot(valid);
+#pragma unroll
+  for (int b = 0; b < 8; b++) { const unsigned long long m = __ballot((d >> b) & 1u); same &= ((d >> b) & 1u) ? m : ~m; }
+  return same;
+}
+// ---- stable LSD radix pass over bits [shift, shift + 8), QN_MAP_TILE keys per block: digit histogram in LDS (one LDS add per distinct
+// digit of a wave, so a tile whose keys share their high digits does not serialise on one bank) ...
+__global__ void __launch_bounds__(QN_BLOCK) k_map_radix_hist(const unsigned long long* __restrict__ keys, uint32_t n, int shift, uint32_t nblocks, uint32_t* __restrict__ hist) {
+  __shared__ uint32_t h[256];
+  h[threadIdx.x] = 0;
+  __syncthreads();
+  const uint32_t base = blockIdx.x * QN_MAP_TILE + threadIdx.x;
+  const int lane = threadIdx.x & 63;
+#pragma unroll 4
+  for (int j = 0; j < QN_MAP_ITEMS; j++) {
+    const uint32_t i = base + j * QN_BLOCK;
+    const bool valid = i < n;
+    const uint32_t d = valid ? (uint32_t)(keys[i] >> shift) & 255u : 0u;
+    const unsigned long long same = match_digit8(d, valid);
+    if (valid && (uint32_t)__popcll(same & ((1ull << lane) - 1ull)) == 0) atomicAdd(&h[d], (uint32_t)__popcll(same));
+  }
+  __syncthreads();
+  hist[threadIdx.x * nblocks + blockIdx.x] = h[threadIdx.x];             // digit-major: the scan yields global offsets directly
+}
+// ... and the scatter: the tile is ranked in QN_MAP_ITEMS rounds of QN_BLOCK consecutive keys (round order = key order, wave order
+// inside a round, lane order inside a wave: stable), each digit's running output position kept in LDS across the rounds.
+__global__ void __launch_bounds__(QN_BLOCK) k_map_radix_scatter(const unsigned long long* __restrict__ keys, uint32_t n, int shift, uint32_t nblocks,
+                                                                const uint32_t* __restrict__ offs, unsigned long long* __restrict__ out) {
+  __shared__ uint32_t wcount[QN_BLOCK / 64][256];
+  __shared__ uint32_t run[256];
+  for (int w = 0; w < QN_BLOCK / 64; w++) wcount[w][threadIdx.x] = 0;
+  run[threadIdx.x] = offs[threadIdx.x * nblocks + blockIdx.x];
+  const uint32_t base = blockIdx.x * QN_MAP_TILE + threadIdx.x;
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  unsigned long long kv[QN_MAP_ITEMS];
+#pragma unroll
+  for (int j = 0; j < QN_MAP_ITEMS; j++) { const uint32_t i = base + j * QN_BLOCK; kv[j] = i < n ? keys[i] : 0ull; }
+  __syncthreads();
+#pragma unroll
+  for (int j = 0; j < QN_MAP_ITEMS; j++) {
+    const bool valid = base + j * QN_BLOCK < n;
+    const uint32_t d = (uint32_t)(kv[j] >> shift) & 255u;
+    const unsigned long long same = match_digit8(d, valid);
+    const uint32_t rank = (uint32_t)__popcll(same & ((1ull << lane) - 1ull));
+    if (valid && rank == 0) wcount[wid][d] = (uint32_t)__popcll(same);
+    __syncthreads();
+    if (valid) {
+      uint32_t before = run[d];
+      for (int w = 0; w < wid; w++) before += wcount[w][d];
+      out[before + rank] = kv[j];
+    }
+    __syncthreads();
+    uint32_t t = 0;
+    for (int w = 0; w < QN_BLOCK / 64; w++) { t += wcount[w][threadIdx.x]; wcount[w][threadIdx.x] = 0; }
+    run[threadIdx.x] += t;
+    __syncthreads();
+  }
+}
+// one thread per leaf: f32 sums of x, y, z, intensity in ascending concatenation order, each / (float)count (a NaN intensity poisons its leaf's)
+__global__ void k_map_centroids(const float4* __restrict__ pts, const unsigned long long* __restrict__ keys, const uint32_t* __restrict__ heads,
+                                const uint32_t* __restrict__ nleaf_ptr, float4* __restrict__ out) {
+  const uint32_t m = blockIdx.x * blockDim.x + threadIdx.x;
+  if (m >= *nleaf_ptr) return;
+  const uint32_t a = heads[m], b = heads[m + 1];
+  float sx = 0.f, sy = 0.f, sz = 0.f, si = 0.f;
+  for (uint32_t t = a; t < b; t++) { const float4 p = pts[(uint32_t)keys[t]]; sx = sx + p.x; sy = sy + p.y; sz = sz + p.z; si = si + p.w; }
+  const float cnt = (float)(b - a);
+  out[m] = make_float4(sx / cnt, sy / cnt, sz / cnt, si / cnt);
+}
+// pack a strided PointXYZI-like host layout into float4 (x, y, z, intensity)
+__global__ void k_pack_xyzi(const char* __restrict__ in, uint32_t stride, uint32_t ioff, uint32_t n, float4* __restrict__ out) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const char* r = in + (size_t)i * stride;
+  const float* p = (const float*)r;
+  out[i] = make_float4(p[0], p[1], p[2], *(const float*)(r + ioff));
+}
+
 }  // namespace qn
 
 struct qn_kf_store {
   int device = 0; hipStream_t stream = nullptr;
-  std::vector<float4*> clouds; std::vector<uint32_t> sizes;
+  std::vector<float4*> clouds; std::vector<uint32_t> sizes; std::vector<uint8_t> has_i;   // has_i: added by qn_kf_add_xyzi (.w = intensity)
   float4* concat = nullptr; unsigned long long* keys = nullptr; unsigned long long* keys_alt = nullptr;
   uint32_t* flag = nullptr; uint32_t* pos = nullptr; uint32_t* heads = nullptr; uint32_t* sums = nullptr; size_t cap = 0;
   uint32_t* hist = nullptr; uint32_t* hist_sums = nullptr;
   float4* out[2] = {nullptr, nullptr}; size_t out_cap[2] = {0, 0}; uint32_t out_n[2] = {0, 0};
   double* poses = nullptr; size_t poses_cap = 0;
   qn::BBoxOut* bbox = nullptr; qn::BBoxOut* bbox_host = nullptr; uint32_t* count_host = nullptr; char* staging = nullptr; size_t staging_cap = 0;
+  float4* map = nullptr; size_t map_cap = 0; uint32_t map_n = 0;                          // the corrected global map: its own slot
+  qn::MapKf* map_kfs = nullptr; size_t map_kfs_cap = 0; uint32_t* map_blk = nullptr; size_t map_blk_cap = 0; qn::BBoxOut* map_part = nullptr; size_t map_part_cap = 0;
   std::string last_error;
 };
 #define KFCHK(s, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { (s)->last_error = std::string(#call) + " -> " + hipGetErrorString(e_); return QN_ERR_HIP; } } while (0)
@@ -136,28 +305,40 @@ extern "C" void qn_kf_store_destroy(qn_kf_store* s) {
   for (float4* p : s->clouds) (void)hipFree(p);
   (void)hipFree(s->concat); (void)hipFree(s->keys); (void)hipFree(s->keys_alt); (void)hipFree(s->flag); (void)hipFree(s->pos); (void)hipFree(s->heads); (void)hipFree(s->sums);
   (void)hipFree(s->hist); (void)hipFree(s->hist_sums); (void)hipFree(s->out[0]); (void)hipFree(s->out[1]); (void)hipFree(s->poses); (void)hipFree(s->bbox); (void)hipFree(s->staging);
+  (void)hipFree(s->map); (void)hipFree(s->map_kfs); (void)hipFree(s->map_blk); (void)hipFree(s->map_part);
   if (s->bbox_host) (void)hipHostFree(s->bbox_host); if (s->count_host) (void)hipHostFree(s->count_host);
   if (s->stream) (void)hipStreamDestroy(s->stream);
   delete s;
 }
 extern "C" const char* qn_kf_last_error(const qn_kf_store* s) { return s ? s->last_error.c_str() : "null store"; }
 
-// upload one keyframe cloud (sensor frame) - PosePcd::pcd_ - and keep it resident
-extern "C" int qn_kf_add(qn_kf_store* s, const float* xyz, uint32_t n, uint32_t stride, int32_t* id_out) {
-  if (!s || !id_out || (n && !xyz) || stride < 12 || (stride & 3)) return QN_ERR_INVALID_ARG;
+// upload one keyframe cloud (sensor frame) - PosePcd::pcd_ - and keep it resident; ioff < 0: xyz only (.w = 1), else the intensity's byte offset
+static int kf_add(qn_kf_store* s, const float* xyz, uint32_t n, uint32_t stride, int ioff, int32_t* id_out) {
   KFCHK(s, hipSetDevice(s->device));
   float4* d = nullptr;
   if (n) {
-    const size_t bytes = (size_t)(n - 1) * stride + 12;
+    const size_t bytes = (size_t)(n - 1) * stride + (ioff < 0 ? 12 : std::max(12, ioff + 4));
     if (bytes > s->staging_cap) { (void)hipFree(s->staging); s->staging = nullptr; s->staging_cap = 0; KFCHK(s, hipMalloc(&s->staging, bytes + bytes / 2)); s->staging_cap = bytes + bytes / 2; }
     KFCHK(s, hipMalloc(&d, sizeof(float4) * n));
     KFCHK(s, hipMemcpyAsync(s->staging, xyz, bytes, hipMemcpyHostToDevice, s->stream));
-    hipLaunchKernelGGL(qn::k_pack_points, dim3((n + 255) / 256), dim3(256), 0, s->stream, s->staging, stride, n, d);
-    KFCHK(s, hipStreamSynchronize(s->stream));
+    if (ioff < 0) hipLaunchKernelGGL(qn::k_pack_points, dim3((n + 255) / 256), dim3(256), 0, s->stream, s->staging, stride, n, d);
+    else hipLaunchKernelGGL(qn::k_pack_xyzi, dim3((n + 255) / 256), dim3(256), 0, s->stream, (const char*)s->staging, stride, (uint32_t)ioff, n, d);
+    const hipError_t e = hipStreamSynchronize(s->stream);
+    if (e != hipSuccess) { (void)hipFree(d); s->last_error = std::string("kf_add -> ") + hipGetErrorString(e); return QN_ERR_HIP; }
   }
-  s->clouds.push_back(d); s->sizes.push_back(n);
+  s->clouds.push_back(d); s->sizes.push_back(n); s->has_i.push_back(ioff >= 0);
   *id_out = (int32_t)s->clouds.size() - 1;
   return QN_OK;
+}
+extern "C" int qn_kf_add(qn_kf_store* s, const float* xyz, uint32_t n, uint32_t stride, int32_t* id_out) {
+  if (!s || !id_out || (n && !xyz) || stride < 12 || (stride & 3)) return QN_ERR_INVALID_ARG;
+  return kf_add(s, xyz, n, stride, -1, id_out);
+}
+// PointXYZI records: xyz at 0, intensity at `ioff` (pcl::PointXYZI: stride 32, offset 16)
+static bool xyzi_layout_ok(uint32_t stride, uint32_t ioff) { return !(stride & 3) && ioff >= 12 && !(ioff & 3) && (size_t)ioff + 4 <= stride; }
+extern "C" int qn_kf_add_xyzi(qn_kf_store* s, const float* pts, uint32_t n, uint32_t stride, uint32_t ioff, int32_t* id_out) {
+  if (!s || !id_out || (n && !pts) || !xyzi_layout_ok(stride, ioff)) return QN_ERR_INVALID_ARG;
+  return kf_add(s, pts, n, stride, (int)ioff, id_out);
 }
 
 static int kf_reserve(qn_kf_store* s, size_t n) {
@@ -173,6 +354,25 @@ static int kf_reserve(qn_kf_store* s, size_t n) {
   s->cap = c;
   return QN_OK;
 }
+
+// pcl::VoxelGrid::applyFilter's grid from the bounding box of the finite points: leaf-index origin and divisions, number of cells;
+// returns false when PCL's overflow guard trips (its own arithmetic: f32 product, int64 cast; it warns and sets output = *input_)
+static bool voxel_dims(const qn::BBoxOut& bb, double leaf, qn::VoxelDims* vd, long long* cells_out) {
+  vd->inv = 1.0f / (float)leaf;
+  long long cells = 1; int divb[3];
+  for (int d = 0; d < 3; d++) {
+    const float mn = qn::ord2f(bb.mn[d]), mx = qn::ord2f(bb.mx[d]);
+    vd->minb[d] = (int)std::floor(mn * vd->inv); const int maxb = (int)std::floor(mx * vd->inv);
+    divb[d] = maxb - vd->minb[d] + 1; cells *= divb[d];
+  }
+  long long pd = 1;
+  for (int d = 0; d < 3; d++) { const float mn = qn::ord2f(bb.mn[d]), mx = qn::ord2f(bb.mx[d]); pd *= (long long)((mx - mn) * vd->inv) + 1; }
+  *cells_out = cells;
+  if (pd > (long long)INT32_MAX || cells > (long long)INT32_MAX) return false;
+  vd->div0 = divb[0]; vd->div01 = divb[0] * divb[1];
+  return true;
+}
+static const char* kOverflowWarning = "warning: leaf size is too small for the input dataset, integer indices would overflow: cloud passed through unfiltered (as pcl::VoxelGrid does)";
 
 // transform + concatenate `count` resident keyframes with their poses (row-major 4x4 f64) and voxel-grid them into
 // output slot 0 (source) or 1 (target); returns the device pointer (float4, stride 16) and the point count.
@@ -219,26 +419,15 @@ extern "C" int qn_kf_assemble(qn_kf_store* s, const int32_t* ids, const double* 
     n = kept;
     s->last_error = "note: non-finite points dropped (pcl::VoxelGrid on a non-dense cloud)";
   }
-  qn::VoxelDims vd; vd.inv = 1.0f / (float)leaf;
-  long long cells = 1; int divb[3];
-  for (int d = 0; d < 3; d++) {
-    const float mn = qn::ord2f(s->bbox_host->mn[d]), mx = qn::ord2f(s->bbox_host->mx[d]);
-    vd.minb[d] = (int)std::floor(mn * vd.inv); const int maxb = (int)std::floor(mx * vd.inv);
-    divb[d] = maxb - vd.minb[d] + 1; cells *= divb[d];
+  qn::VoxelDims vd; long long cells = 1;
+  if (!voxel_dims(*s->bbox_host, leaf, &vd, &cells)) {
+    s->last_error = kOverflowWarning;
+    if (n > s->out_cap[slot]) { (void)hipFree(s->out[slot]); s->out[slot] = nullptr; s->out_cap[slot] = 0; KFCHK(s, hipMalloc(&s->out[slot], sizeof(float4) * (n + n / 2))); s->out_cap[slot] = n + n / 2; }
+    KFCHK(s, hipMemcpyAsync(s->out[slot], s->concat, sizeof(float4) * n, hipMemcpyDeviceToDevice, st));
+    KFCHK(s, hipStreamSynchronize(st));
+    s->out_n[slot] = n; *d_xyz_out = (const float*)s->out[slot]; *n_out = n;
+    return QN_OK;
   }
-  {  // pcl::VoxelGrid::applyFilter's overflow guard in PCL's own arithmetic (f32 product, int64 cast): it warns and sets output = *input_
-    long long pd = 1;
-    for (int d = 0; d < 3; d++) { const float mn = qn::ord2f(s->bbox_host->mn[d]), mx = qn::ord2f(s->bbox_host->mx[d]); pd *= (long long)((mx - mn) * vd.inv) + 1; }
-    if (pd > (long long)INT32_MAX || cells > (long long)INT32_MAX) {
-      s->last_error = "warning: leaf size is too small for the input dataset, integer indices would overflow: cloud passed through unfiltered (as pcl::VoxelGrid does)";
-      if (n > s->out_cap[slot]) { (void)hipFree(s->out[slot]); s->out[slot] = nullptr; s->out_cap[slot] = 0; KFCHK(s, hipMalloc(&s->out[slot], sizeof(float4) * (n + n / 2))); s->out_cap[slot] = n + n / 2; }
-      KFCHK(s, hipMemcpyAsync(s->out[slot], s->concat, sizeof(float4) * n, hipMemcpyDeviceToDevice, st));
-      KFCHK(s, hipStreamSynchronize(st));
-      s->out_n[slot] = n; *d_xyz_out = (const float*)s->out[slot]; *n_out = n;
-      return QN_OK;
-    }
-  }
-  vd.div0 = divb[0]; vd.div01 = divb[0] * divb[1];
   const uint32_t nb = (n + 255) / 256;
   hipLaunchKernelGGL(qn::k_voxel_keys, dim3(nb), dim3(256), 0, st, s->concat, n, vd, s->keys);
   unsigned long long* sorted = s->keys; unsigned long long* other = s->keys_alt;
@@ -274,6 +463,106 @@ extern "C" int qn_kf_download(qn_kf_store* s, int slot, float* xyz_out) {       
   if (!n) return QN_OK;
   KFCHK(s, hipSetDevice(s->device));
   KFCHK(s, hipMemcpy2D(xyz_out, 12, s->out[slot], 16, 12, n, hipMemcpyDeviceToHost));
+  return QN_OK;
+}
+
+// the corrected global map (fast_lio_sam_qn.cpp:302-316, 398-411, 435-448): every listed keyframe transformed with its corrected pose,
+// concatenated in list order, voxel-grid at `leaf` with intensity; into the store's own map slot (never assemble slots 0 / 1).
+// Unlike qn_kf_assemble, a tripped overflow guard passes the WHOLE concatenation through, non-finite points included (output = *input_).
+static int map_grow(qn_kf_store* s, void** p, size_t* cap, size_t need, size_t elem) {
+  if (need <= *cap) return QN_OK;
+  (void)hipFree(*p); *p = nullptr; *cap = 0;
+  KFCHK(s, hipMalloc(p, elem * (need + need / 2)));
+  *cap = need + need / 2;
+  return QN_OK;
+}
+extern "C" int qn_kf_build_map(qn_kf_store* s, const int32_t* ids, const double* poses, uint32_t count, double leaf,
+                               const float** d_xyzi_out, uint32_t* n_out) {
+  if (!s || (count && (!ids || !poses)) || !d_xyzi_out || !n_out || !(leaf > 0)) return QN_ERR_INVALID_ARG;
+  *d_xyzi_out = nullptr; *n_out = 0;
+  s->map_n = 0; s->last_error.clear();
+  if (count == 0) return QN_ERR_EMPTY_CLOUD;
+  size_t total = 0, tiles = 0;
+  for (uint32_t k = 0; k < count; k++) {
+    if (ids[k] < 0 || (size_t)ids[k] >= s->clouds.size()) return QN_ERR_INVALID_ARG;
+    total += s->sizes[ids[k]]; tiles += (s->sizes[ids[k]] + QN_MAP_TILE - 1) / QN_MAP_TILE;
+  }
+  if (total == 0) return QN_ERR_EMPTY_CLOUD;
+  if (total >= 0xffffffffull) return QN_ERR_CAPACITY;
+  KFCHK(s, hipSetDevice(s->device));
+  int rc = kf_reserve(s, total); if (rc != QN_OK) return rc;
+  if ((rc = map_grow(s, (void**)&s->map_kfs, &s->map_kfs_cap, count, sizeof(qn::MapKf))) != QN_OK) return rc;
+  if ((rc = map_grow(s, (void**)&s->map_blk, &s->map_blk_cap, tiles, sizeof(uint32_t))) != QN_OK) return rc;
+  if ((rc = map_grow(s, (void**)&s->map_part, &s->map_part_cap, tiles, sizeof(qn::BBoxOut))) != QN_OK) return rc;
+  if ((size_t)count * 16 > s->poses_cap) { (void)hipFree(s->poses); s->poses = nullptr; s->poses_cap = 0; KFCHK(s, hipMalloc(&s->poses, sizeof(double) * 16 * (count + 8))); s->poses_cap = (size_t)16 * (count + 8); }
+  if ((rc = map_grow(s, (void**)&s->map, &s->map_cap, total, sizeof(float4))) != QN_OK) return rc;
+  // the keyframe table and the tile -> keyframe table (host, O(count + tiles))
+  std::vector<qn::MapKf> kfs(count); std::vector<uint32_t> blk(tiles);
+  uint32_t off = 0, b0 = 0;
+  for (uint32_t k = 0; k < count; k++) {
+    const uint32_t n = s->sizes[ids[k]], nt = (n + QN_MAP_TILE - 1) / QN_MAP_TILE;
+    kfs[k] = qn::MapKf{s->clouds[ids[k]], off, n, b0, s->has_i[ids[k]]};
+    for (uint32_t t = 0; t < nt; t++) blk[b0 + t] = k;
+    off += n; b0 += nt;
+  }
+  hipStream_t st = s->stream;
+  const uint32_t n = (uint32_t)total, nt = (uint32_t)tiles;
+  KFCHK(s, hipMemcpyAsync(s->poses, poses, sizeof(double) * 16 * count, hipMemcpyHostToDevice, st));
+  KFCHK(s, hipMemcpyAsync(s->map_kfs, kfs.data(), sizeof(qn::MapKf) * count, hipMemcpyHostToDevice, st));
+  KFCHK(s, hipMemcpyAsync(s->map_blk, blk.data(), sizeof(uint32_t) * tiles, hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(qn::k_map_transform, dim3(nt), dim3(QN_BLOCK), 0, st, (const qn::MapKf*)s->map_kfs, (const uint32_t*)s->map_blk, (const double*)s->poses, s->concat, s->map_part);
+  hipLaunchKernelGGL(qn::k_map_bbox_reduce, dim3(1), dim3(QN_BLOCK), 0, st, (const qn::BBoxOut*)s->map_part, nt, s->bbox);
+  KFCHK(s, hipMemcpyAsync(s->bbox_host, s->bbox, sizeof(qn::BBoxOut), hipMemcpyDeviceToHost, st));
+  KFCHK(s, hipStreamSynchronize(st));                               // sync 1 of 2: the bounding box sizes the grid
+  const qn::BBoxOut bb = *s->bbox_host;
+  const uint32_t n_fin = n - bb.nonfinite;
+  if (n_fin == 0) return QN_ERR_EMPTY_CLOUD;
+  qn::VoxelDims vd; long long cells = 1;
+  if (!voxel_dims(bb, leaf, &vd, &cells)) {
+    s->last_error = kOverflowWarning;
+    KFCHK(s, hipMemcpyAsync(s->map, s->concat, sizeof(float4) * n, hipMemcpyDeviceToDevice, st));
+    KFCHK(s, hipStreamSynchronize(st));
+    s->map_n = n; *d_xyzi_out = (const float*)s->map; *n_out = n;
+    return QN_OK;
+  }
+  const uint32_t nb = (n + 255) / 256;
+  hipLaunchKernelGGL(qn::k_map_keys, dim3(nb), dim3(256), 0, st, (const float4*)s->concat, n, vd, (uint32_t)cells, s->keys);
+  unsigned long long* sorted = s->keys; unsigned long long* other = s->keys_alt;
+  const long long maxleaf = bb.nonfinite ? cells : cells - 1;        // the sentinel leaf of the non-finite points is `cells`
+  int bits = 1; while ((1ll << bits) <= maxleaf) bits++;
+  const uint32_t rb = (n + QN_MAP_TILE - 1) / QN_MAP_TILE, hn = rb * 256, hsb = (hn + QN_BLOCK * QN_SCAN_ITEMS - 1) / (QN_BLOCK * QN_SCAN_ITEMS);
+  for (int shift = 32; shift < 32 + bits; shift += 8) {                  // stable LSD passes over the leaf-index bits only
+    hipLaunchKernelGGL(qn::k_map_radix_hist, dim3(rb), dim3(QN_BLOCK), 0, st, (const unsigned long long*)sorted, n, shift, rb, s->hist);
+    hipLaunchKernelGGL(qn::k_scan_block, dim3(hsb), dim3(QN_BLOCK), 0, st, s->hist, hn, s->hist, s->hist_sums);
+    hipLaunchKernelGGL(qn::k_scan_top, dim3(1), dim3(QN_BLOCK), 0, st, s->hist_sums, hsb);
+    hipLaunchKernelGGL(qn::k_scan_add, dim3(hsb), dim3(QN_BLOCK), 0, st, s->hist, hn, s->hist_sums, n);
+    hipLaunchKernelGGL(qn::k_map_radix_scatter, dim3(rb), dim3(QN_BLOCK), 0, st, (const unsigned long long*)sorted, n, shift, rb, (const uint32_t*)s->hist, other);
+    std::swap(sorted, other);
+  }
+  // leaf heads over the finite prefix of the sorted keys (the engine's scans), then one thread per leaf
+  const uint32_t nbf = (n_fin + 255) / 256, sb = (n_fin + QN_BLOCK * QN_SCAN_ITEMS - 1) / (QN_BLOCK * QN_SCAN_ITEMS);
+  hipLaunchKernelGGL(qn::k_leaf_flags, dim3(nbf), dim3(256), 0, st, sorted, n_fin, s->flag);
+  hipLaunchKernelGGL(qn::k_scan_block, dim3(sb), dim3(QN_BLOCK), 0, st, s->flag, n_fin, s->pos, s->sums);
+  hipLaunchKernelGGL(qn::k_scan_top, dim3(1), dim3(QN_BLOCK), 0, st, s->sums, sb);
+  hipLaunchKernelGGL(qn::k_scan_add_total, dim3(sb), dim3(QN_BLOCK), 0, st, s->pos, n_fin, s->sums, s->flag);
+  hipLaunchKernelGGL(qn::k_leaf_heads, dim3(nbf), dim3(256), 0, st, s->flag, s->pos, n_fin, s->heads);
+  hipLaunchKernelGGL(qn::k_map_centroids, dim3(nbf), dim3(256), 0, st, (const float4*)s->concat, (const unsigned long long*)sorted, (const uint32_t*)s->heads, (const uint32_t*)(s->pos + n_fin), s->map);
+  KFCHK(s, hipMemcpyAsync(s->count_host, s->pos + n_fin, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  KFCHK(s, hipGetLastError());
+  KFCHK(s, hipStreamSynchronize(st));                               // sync 2 of 2: the leaf count
+  s->map_n = *s->count_host;
+  *d_xyzi_out = (const float*)s->map; *n_out = s->map_n;
+  return QN_OK;
+}
+
+// the map into host records: only the 12 xyz bytes (offset 0) and the 4 intensity bytes (offset ioff) of each are written
+extern "C" int qn_kf_download_map(qn_kf_store* s, void* out, uint32_t stride, uint32_t ioff) {
+  if (!s || !out || !xyzi_layout_ok(stride, ioff)) return QN_ERR_INVALID_ARG;
+  const uint32_t n = s->map_n;
+  if (!n) return QN_OK;
+  KFCHK(s, hipSetDevice(s->device));
+  KFCHK(s, hipMemcpy2D(out, stride, s->map, 16, 12, n, hipMemcpyDeviceToHost));
+  KFCHK(s, hipMemcpy2D((char*)out + ioff, stride, (const char*)s->map + 12, 16, 4, n, hipMemcpyDeviceToHost));
   return QN_OK;
 }
 

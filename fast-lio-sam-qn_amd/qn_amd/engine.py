@@ -630,9 +630,18 @@ class KeyframeStore:
         if st != QN_OK:
             raise EngineError(st, self._l.qn_status_str(st).decode() + ": " + self._l.qn_kf_last_error(self.h).decode())
 
-    def add(self, xyz):
-        a, n, stride = _cloud_arg(xyz); kid = C.c_int32()
-        self._check(self._l.qn_kf_add(self.h, _p(a), C.c_uint32(n), C.c_uint32(stride), C.byref(kid)))
+    def add(self, xyz, intensity=None):
+        """intensity (n,) given: qn_kf_add_xyzi, the keyframe carries it into build_map; otherwise qn_kf_add (intensity 0 in the map)."""
+        kid = C.c_int32()
+        if intensity is None:
+            a, n, stride = _cloud_arg(xyz)
+            self._check(self._l.qn_kf_add(self.h, _p(a), C.c_uint32(n), C.c_uint32(stride), C.byref(kid)))
+            return kid.value
+        xyz = np.asarray(xyz, dtype=np.float32); intensity = np.asarray(intensity, dtype=np.float32).reshape(-1)
+        if xyz.ndim != 2 or xyz.shape[1] < 3 or len(intensity) != len(xyz):
+            raise ValueError("cloud must be (n, >=3) float32 with n intensities")
+        a = np.empty((len(xyz), 4), np.float32); a[:, :3] = xyz[:, :3]; a[:, 3] = intensity
+        self._check(self._l.qn_kf_add_xyzi(self.h, _p(a), C.c_uint32(len(a)), C.c_uint32(16), C.c_uint32(12), C.byref(kid)))
         return kid.value
 
     def assemble(self, ids, poses, leaf, slot):
@@ -645,6 +654,23 @@ class KeyframeStore:
     def download(self, slot, n):
         out = np.zeros((n, 3), np.float32)
         self._check(self._l.qn_kf_download(self.h, C.c_int(slot), _p(out)))
+        return out
+
+    def build_map(self, ids, poses, leaf):
+        """qn_kf_build_map: the corrected global map (transform every listed keyframe, concatenate in `ids` order, voxel grid with
+        intensity) into the store's own map slot -> number of map points."""
+        ids = np.ascontiguousarray(ids, dtype=np.int32); poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(len(ids), 16)
+        ptr = C.c_void_p(); n = C.c_uint32(); self._map_n = 0
+        self._check(self._l.qn_kf_build_map(self.h, _p(ids), _p(poses), C.c_uint32(len(ids)), C.c_double(leaf), C.byref(ptr), C.byref(n)))
+        self._map_n = n.value
+        return n.value
+
+    def download_map(self, n):
+        """-> (n, 4) float32: x y z intensity of the latest build_map"""
+        if n != getattr(self, "_map_n", 0):
+            raise ValueError("download_map(%d): the map holds %d points" % (n, getattr(self, "_map_n", 0)))
+        out = np.zeros((n, 4), np.float32)
+        self._check(self._l.qn_kf_download_map(self.h, _p(out), C.c_uint32(16), C.c_uint32(12)))
         return out
 
 

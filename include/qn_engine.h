@@ -276,6 +276,18 @@ int  qn_kf_add(qn_kf_store*, const float* xyz, uint32_t n, uint32_t stride_bytes
 int  qn_kf_assemble(qn_kf_store*, const int32_t* ids, const double* poses16, uint32_t count, double leaf, int slot,
                     const float** d_xyz_out, uint32_t* n_out);
 int  qn_kf_download(qn_kf_store*, int slot, float* xyz_out /* n x 3 packed */);
+/* the corrected global map = the three loops of FastLioSamQn that rebuild it from every keyframe with its corrected pose
+ * (fast_lio_sam_qn.cpp:302-316 visTimerFunc, :398-411 saveFlagCallback, :435-448 the destructor's result.pcd): transformPcd of each
+ * listed keyframe, concatenation in `ids` order (ids may repeat), voxelizePcd at save_voxel_resolution (pcl::VoxelGrid,
+ * include/utilities.hpp:38-51) averaging xyz AND intensity.  PointXYZI keyframes come in through qn_kf_add_xyzi (stride 32, intensity
+ * at offset 16); keyframes added by qn_kf_add count as intensity 0.  The map has its own slot: building it never touches the
+ * qn_kf_assemble slots and assembling never touches it.  When PCL's overflow guard trips (qn_kf_last_error says so) the map is the
+ * unfiltered concatenation, non-finite points included, as VoxelGrid::applyFilter's `output = *input_` (qn_kf_assemble drops them first).
+ * qn_kf_download_map writes only the 12 xyz bytes and the 4 intensity bytes of each record; the rest of each record is left as it was. */
+int  qn_kf_add_xyzi(qn_kf_store*, const float* pts, uint32_t n, uint32_t stride_bytes, uint32_t intensity_offset_bytes, int32_t* id_out);
+int  qn_kf_build_map(qn_kf_store*, const int32_t* ids, const double* poses16, uint32_t count, double leaf,
+                     const float** d_xyzi_out /* float4: x y z intensity */, uint32_t* n_out);
+int  qn_kf_download_map(qn_kf_store*, void* out, uint32_t stride_bytes, uint32_t intensity_offset_bytes);
 /* LoopClosure::fetchClosestKeyframeIdx (loop_closure.cpp:34-56) generalised to the max_k nearest admissible keyframes,
  * ascending distance; out[0] is the reference's single choice.  Host code (O(#keyframes)).                        */
 int  qn_loop_candidates(const double* pos_xyz, const double* stamps, uint32_t n, uint32_t query, double radius, double tdiff,

@@ -15,7 +15,9 @@ The registration engine is the product under test: keyframe clouds resident in H
 on the device, Nano-GICP and (--quatro) Quatro + Nano-GICP on the device through the `_device` entry points: a loop attempt moves no
 point cloud across PCIe.  `backend="oracle"` runs the same loop with the CPU oracle's assembly and registrations instead (test
 infrastructure: tests/test_replay.py compares the two); `save_dir` writes the corrected trajectory the way saveFlagCallback does
-(FQ:344-373): poses_kitti.txt (3x4 row-major, default stream precision) and poses_tum.txt ("#timestamp x y z qx qy qz qw", 8 decimals).
+(FQ:344-373): poses_kitti.txt (3x4 row-major, default stream precision) and poses_tum.txt ("#timestamp x y z qx qy qz qw", 8 decimals);
+with `save_map_leaf` the GPU backend also writes the corrected global map there as map.pcd (FQ:398-411: every keyframe with its corrected
+pose, voxel grid at save_voxel_resolution, on the device through qn_kf_build_map).
 The reference's extra iSAM2::update() calls after a loop (FQ:160-165) are iSAM2 relinearisation sweeps; the batch Gauss-Newton stand-in
 iterates to convergence instead.
 """
@@ -170,11 +172,21 @@ def write_kitti_tum(save_dir, poses, stamps):
             ft.write("%.8f %.8f %.8f %.8f %.8f %.8f %.8f %.8f\n" % (st, T[0, 3], T[1, 3], T[2, 3], q[0], q[1], q[2], q[3]))
 
 
+def write_pcd_xyzi(path, pts):
+    """PCD v0.7 ASCII, FIELDS x y z intensity (what pcl::io::savePCDFileASCII writes for a PointXYZI cloud)."""
+    with open(path, "w") as f:
+        f.write("# .PCD v0.7 - Point Cloud Data file format\nVERSION 0.7\nFIELDS x y z intensity\nSIZE 4 4 4 4\nTYPE F F F F\nCOUNT 1 1 1 1\n"
+                "WIDTH %d\nHEIGHT 1\nVIEWPOINT 0 0 0 1 0 0 0\nPOINTS %d\nDATA ascii\n" % (len(pts), len(pts)))
+        for p in pts:
+            f.write("%.9g %.9g %.9g %.9g\n" % (p[0], p[1], p[2], p[3]))
+
+
 def ate(poses, gt):
     return float(np.sqrt(np.mean([np.sum((a[:3, 3] - b[:3, 3]) ** 2) for a, b in zip(poses, gt)])))
 
 
-def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, submap_range=5, score_thr=1.5, verbose=True, backend="gpu", save_dir=None):
+def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, submap_range=5, score_thr=1.5, verbose=True, backend="gpu", save_dir=None,
+        save_map_leaf=None):
     scans, gt, odom, stamps = make_stream(n_kf, seed)
     if backend == "gpu":
         from qn_amd import engine
@@ -241,6 +253,9 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
                ms_per_attempt=1e3 * float(np.mean(t_reg)) if t_reg else None, quatro=use_quatro, loop_list=loops, poses=corrected)
     if save_dir:
         write_kitti_tum(save_dir, corrected, stamps)
+        if save_map_leaf is not None and backend == "gpu":
+            n = store.build_map(ids, corrected, save_map_leaf)
+            write_pcd_xyzi(os.path.join(save_dir, "map.pcd"), store.download_map(n))
     if verbose:
         print({k: v for k, v in out.items() if k not in ("poses", "loop_list")})
     if backend == "gpu":
@@ -254,5 +269,6 @@ if __name__ == "__main__":
     ap.add_argument("--quatro", action="store_true")
     ap.add_argument("--seed", type=int, default=7)
     ap.add_argument("--save-dir", default=None, help="write poses_kitti.txt / poses_tum.txt (FQ:344-373) here")
+    ap.add_argument("--save-map-leaf", type=float, default=None, help="with --save-dir: also write map.pcd, the corrected map at this leaf (0.3 = save_voxel_resolution)")
     a = ap.parse_args()
-    run(a.keyframes, a.seed, a.quatro, save_dir=a.save_dir)
+    run(a.keyframes, a.seed, a.quatro, save_dir=a.save_dir, save_map_leaf=a.save_map_leaf)
