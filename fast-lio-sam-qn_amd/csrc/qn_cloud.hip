@@ -270,6 +270,119 @@ __global__ void k_pack_xyzi(const char* __restrict__ in, uint32_t stride, uint32
   out[i] = make_float4(p[0], p[1], p[2], *(const float*)(r + ioff));
 }
 
+// ---- many loop-closure submaps in one pass (qn_kf_assemble_batch): the qn_kf_build_map structure with the submap as one more key field.
+// The listed keyframes of all submaps are transformed by k_map_transform (one launch; tiles never straddle keyframes, so a submap owns
+// a contiguous tile range and a contiguous point range [p0, p1)).  Keys are ((seg << L | leaf) << 32 | point index): one stable sort
+// orders every submap's points by leaf, finite points of a submap first (its non-finite ones carry the sentinel leaf).
+struct BatchSeg { VoxelDims vd; uint32_t p0, p1, nvox, sentinel, prefix, tripped; };  // nvox: finite points that are voxelized (0 if tripped / empty)
+// one block per submap over its tile range: the box of its finite points and its non-finite count, in a fixed order (no atomics)
+__global__ void __launch_bounds__(QN_BLOCK) k_seg_bbox_reduce(const BBoxOut* __restrict__ part, const uint32_t* __restrict__ tile_off, BBoxOut* __restrict__ out) {
+  __shared__ int smn[QN_BLOCK / 64][3], smx[QN_BLOCK / 64][3], sbad[QN_BLOCK / 64];
+  int mn[3] = {0x7fffffff, 0x7fffffff, 0x7fffffff}, mx[3] = {(int)0x80000000, (int)0x80000000, (int)0x80000000};
+  int bad = 0;
+  const uint32_t b1 = tile_off[blockIdx.x + 1];
+  for (uint32_t b = tile_off[blockIdx.x] + threadIdx.x; b < b1; b += QN_BLOCK) {
+    const BBoxOut r = part[b];
+    for (int d = 0; d < 3; d++) { mn[d] = min(mn[d], r.mn[d]); mx[d] = max(mx[d], r.mx[d]); }
+    bad += (int)r.nonfinite;
+  }
+#pragma unroll
+  for (int d = 0; d < 3; d++) { mn[d] = wave_min_i(mn[d]); mx[d] = wave_max_i(mx[d]); }
+  bad = wave_sum_i(bad);
+  const int wid = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) { for (int d = 0; d < 3; d++) { smn[wid][d] = mn[d]; smx[wid][d] = mx[d]; } sbad[wid] = bad; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < QN_BLOCK / 64; w++) { for (int d = 0; d < 3; d++) { mn[d] = min(mn[d], smn[w][d]); mx[d] = max(mx[d], smx[w][d]); } bad += sbad[w]; }
+    BBoxOut r; for (int d = 0; d < 3; d++) { r.mn[d] = mn[d]; r.mx[d] = mx[d]; } r.nonfinite = (uint32_t)bad;
+    out[blockIdx.x] = r;
+  }
+}
+// keys, one block per tile: leaf as k_voxel_keys computes it; the submap's sentinel for a non-finite point; leaf 0 for every finite point of a
+// submap whose guard tripped (the stable sort then keeps them in concatenation order for the pass-through gather)
+__global__ void __launch_bounds__(QN_BLOCK) k_batch_keys(const MapKf* __restrict__ kfs, const uint32_t* __restrict__ blk_kf, const uint32_t* __restrict__ kf_seg,
+                                                         const BatchSeg* __restrict__ segs, const float4* __restrict__ pts, unsigned long long* __restrict__ keys) {
+  const uint32_t k = blk_kf[blockIdx.x];
+  const MapKf f = kfs[k];
+  const BatchSeg sg = segs[kf_seg[k]];
+  const uint32_t base = (blockIdx.x - f.blk0) * QN_MAP_TILE;
+  for (int j = 0; j < QN_MAP_ITEMS; j++) {
+    const uint32_t i = base + j * QN_BLOCK + threadIdx.x;
+    if (i >= f.n) break;
+    const uint32_t g = f.off + i;
+    const float4 p = pts[g];
+    uint32_t leaf = sg.sentinel;
+    if (isfinite(p.x) && isfinite(p.y) && isfinite(p.z)) {
+      leaf = 0;
+      if (!sg.tripped) {
+        const int i0 = (int)(floorf(p.x * sg.vd.inv) - (float)sg.vd.minb[0]);
+        const int i1 = (int)(floorf(p.y * sg.vd.inv) - (float)sg.vd.minb[1]);
+        const int i2 = (int)(floorf(p.z * sg.vd.inv) - (float)sg.vd.minb[2]);
+        leaf = (uint32_t)(i0 + i1 * sg.vd.div0 + i2 * sg.vd.div01);
+      }
+    }
+    keys[g] = ((unsigned long long)(sg.prefix | leaf) << 32) | g;
+  }
+}
+// leaf heads over the sorted keys, one block per tile of positions: a head is a voxelized position whose leaf differs from its predecessor's
+// or that opens its submap (the submap field alone would not separate two submaps of different sort groups)
+__global__ void __launch_bounds__(QN_BLOCK) k_batch_leaf_flags(const MapKf* __restrict__ kfs, const uint32_t* __restrict__ blk_kf, const uint32_t* __restrict__ kf_seg,
+                                                               const BatchSeg* __restrict__ segs, const unsigned long long* __restrict__ keys, uint32_t* __restrict__ flag) {
+  const uint32_t k = blk_kf[blockIdx.x];
+  const MapKf f = kfs[k];
+  const BatchSeg sg = segs[kf_seg[k]];
+  const uint32_t base = (blockIdx.x - f.blk0) * QN_MAP_TILE, fe = sg.p0 + sg.nvox;
+  for (int j = 0; j < QN_MAP_ITEMS; j++) {
+    const uint32_t i = base + j * QN_BLOCK + threadIdx.x;
+    if (i >= f.n) break;
+    const uint32_t g = f.off + i;
+    flag[g] = (g < fe && (g == sg.p0 || (keys[g] >> 32) != (keys[g - 1] >> 32))) ? 1u : 0u;
+  }
+}
+// after the exclusive scan pos of the flags: leaf m = [heads[m], ends[m]) (its position in the output = its rank over all submaps)
+__global__ void __launch_bounds__(QN_BLOCK) k_batch_leaf_bounds(const MapKf* __restrict__ kfs, const uint32_t* __restrict__ blk_kf, const uint32_t* __restrict__ kf_seg,
+                                                                const BatchSeg* __restrict__ segs, const uint32_t* __restrict__ flag, const uint32_t* __restrict__ pos,
+                                                                uint32_t* __restrict__ heads, uint32_t* __restrict__ ends) {
+  const uint32_t k = blk_kf[blockIdx.x];
+  const MapKf f = kfs[k];
+  const BatchSeg sg = segs[kf_seg[k]];
+  const uint32_t base = (blockIdx.x - f.blk0) * QN_MAP_TILE, fe = sg.p0 + sg.nvox;
+  for (int j = 0; j < QN_MAP_ITEMS; j++) {
+    const uint32_t i = base + j * QN_BLOCK + threadIdx.x;
+    if (i >= f.n) break;
+    const uint32_t g = f.off + i;
+    if (g >= fe) continue;
+    const uint32_t fl = flag[g], m = pos[g] + fl - 1;
+    if (fl) heads[m] = g;
+    if (g + 1 == fe || flag[g + 1]) ends[m] = g + 1;
+  }
+}
+// one thread per leaf: k_leaf_centroids' arithmetic (f32 sums in ascending concatenation order, / (float)count, w = 1)
+__global__ void k_batch_centroids(const float4* __restrict__ pts, const unsigned long long* __restrict__ keys, const uint32_t* __restrict__ heads,
+                                  const uint32_t* __restrict__ ends, const uint32_t* __restrict__ nleaf_ptr, float4* __restrict__ out) {
+  const uint32_t m = blockIdx.x * blockDim.x + threadIdx.x;
+  if (m >= *nleaf_ptr) return;
+  const uint32_t a = heads[m], b = ends[m];
+  float sx = 0.f, sy = 0.f, sz = 0.f;
+  for (uint32_t t = a; t < b; t++) { const float4 p = pts[(uint32_t)keys[t]]; sx = sx + p.x; sy = sy + p.y; sz = sz + p.z; }
+  const float cnt = (float)(b - a);
+  out[m] = make_float4(sx / cnt, sy / cnt, sz / cnt, 1.0f);
+}
+// each submap's first leaf and leaf count: res[2 s] = first, res[2 s + 1] = count
+__global__ void k_batch_counts(const BatchSeg* __restrict__ segs, uint32_t nseg, const uint32_t* __restrict__ pos, uint32_t* __restrict__ res) {
+  const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= nseg) return;
+  const uint32_t a = pos[segs[s].p0];
+  res[2 * s] = a; res[2 * s + 1] = pos[segs[s].p1] - a;
+}
+// a tripped submap: its finite points (the first n of its sorted range, in concatenation order), unfiltered, w = 1 as qn_kf_assemble copies them
+__global__ void k_batch_gather(const unsigned long long* __restrict__ keys, uint32_t n, const float4* __restrict__ pts, float4* __restrict__ out) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float4 p = pts[(uint32_t)keys[i]];
+  out[i] = make_float4(p.x, p.y, p.z, 1.0f);
+}
+
 }  // namespace qn
 
 struct qn_kf_store {
@@ -283,6 +396,11 @@ struct qn_kf_store {
   qn::BBoxOut* bbox = nullptr; qn::BBoxOut* bbox_host = nullptr; uint32_t* count_host = nullptr; char* staging = nullptr; size_t staging_cap = 0;
   float4* map = nullptr; size_t map_cap = 0; uint32_t map_n = 0;                          // the corrected global map: its own slot
   qn::MapKf* map_kfs = nullptr; size_t map_kfs_cap = 0; uint32_t* map_blk = nullptr; size_t map_blk_cap = 0; qn::BBoxOut* map_part = nullptr; size_t map_part_cap = 0;
+  // qn_kf_assemble_batch: its own output slot (all submaps in one buffer) and tables
+  float4* bt_out = nullptr; size_t bt_out_cap = 0; std::vector<const float4*> bt_ptr; std::vector<uint32_t> bt_n;
+  uint32_t* bt_ends = nullptr; size_t bt_ends_cap = 0; uint32_t* bt_kf_seg = nullptr; size_t bt_kf_seg_cap = 0; uint32_t* bt_tile_off = nullptr; size_t bt_tile_off_cap = 0;
+  qn::BatchSeg* bt_segs = nullptr; size_t bt_segs_cap = 0; qn::BBoxOut* bt_bbox = nullptr; size_t bt_bbox_cap = 0; uint32_t* bt_res = nullptr; size_t bt_res_cap = 0;
+  qn::BBoxOut* bt_bbox_host = nullptr; size_t bt_bbox_host_cap = 0; uint32_t* bt_res_host = nullptr; size_t bt_res_host_cap = 0;
   std::string last_error;
 };
 #define KFCHK(s, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { (s)->last_error = std::string(#call) + " -> " + hipGetErrorString(e_); return QN_ERR_HIP; } } while (0)
@@ -306,6 +424,8 @@ extern "C" void qn_kf_store_destroy(qn_kf_store* s) {
   (void)hipFree(s->concat); (void)hipFree(s->keys); (void)hipFree(s->keys_alt); (void)hipFree(s->flag); (void)hipFree(s->pos); (void)hipFree(s->heads); (void)hipFree(s->sums);
   (void)hipFree(s->hist); (void)hipFree(s->hist_sums); (void)hipFree(s->out[0]); (void)hipFree(s->out[1]); (void)hipFree(s->poses); (void)hipFree(s->bbox); (void)hipFree(s->staging);
   (void)hipFree(s->map); (void)hipFree(s->map_kfs); (void)hipFree(s->map_blk); (void)hipFree(s->map_part);
+  (void)hipFree(s->bt_out); (void)hipFree(s->bt_ends); (void)hipFree(s->bt_kf_seg); (void)hipFree(s->bt_tile_off); (void)hipFree(s->bt_segs); (void)hipFree(s->bt_bbox); (void)hipFree(s->bt_res);
+  if (s->bt_bbox_host) (void)hipHostFree(s->bt_bbox_host); if (s->bt_res_host) (void)hipHostFree(s->bt_res_host);
   if (s->bbox_host) (void)hipHostFree(s->bbox_host); if (s->count_host) (void)hipHostFree(s->count_host);
   if (s->stream) (void)hipStreamDestroy(s->stream);
   delete s;
@@ -563,6 +683,164 @@ extern "C" int qn_kf_download_map(qn_kf_store* s, void* out, uint32_t stride, ui
   KFCHK(s, hipSetDevice(s->device));
   KFCHK(s, hipMemcpy2D(out, stride, s->map, 16, 12, n, hipMemcpyDeviceToHost));
   KFCHK(s, hipMemcpy2D((char*)out + ioff, stride, (const char*)s->map + 12, 16, 4, n, hipMemcpyDeviceToHost));
+  return QN_OK;
+}
+
+// S loop-closure submaps in one pass (LoopClosure::setSrcAndDstCloud for one query and its candidates, loop_closure.cpp:58-108): submap t =
+// ids[seg_off[t] .. seg_off[t + 1]) with the poses of the same entries; each equals qn_kf_assemble of its list in all 16 bytes of every record.
+// Into the store's batch slot (never slots 0 / 1 or the map slot).  Two host synchronisations: the per-submap boxes (grid sizes, sort
+// bits), then the per-submap leaf counts.  Submaps are sorted in groups whose keys fit 32 bits - normally one group.
+static int pin_grow(qn_kf_store* s, void** p, size_t* cap, size_t need, size_t elem) {
+  if (need <= *cap) return QN_OK;
+  if (*p) (void)hipHostFree(*p);
+  *p = nullptr; *cap = 0;
+  KFCHK(s, hipHostMalloc(p, elem * (need + need / 2), hipHostMallocDefault));
+  *cap = need + need / 2;
+  return QN_OK;
+}
+static int bits_for(unsigned long long v) { int b = 0; while (b < 64 && (1ull << b) <= v) b++; return b; }      // smallest b with v < 2^b
+extern "C" int qn_kf_assemble_batch(qn_kf_store* s, const int32_t* ids, const double* poses, const uint32_t* seg_off, uint32_t n_seg, double leaf,
+                                    const float** d_xyz_out, uint32_t* n_out, int* status) {
+  if (!s || !seg_off || n_seg == 0 || !d_xyz_out || !n_out || !status || !(leaf > 0)) return QN_ERR_INVALID_ARG;
+  for (uint32_t t = 0; t < n_seg; t++) if (seg_off[t + 1] < seg_off[t]) return QN_ERR_INVALID_ARG;
+  const uint32_t e0 = seg_off[0], count = seg_off[n_seg] - e0;
+  if (count && (!ids || !poses)) return QN_ERR_INVALID_ARG;
+  size_t total = 0, tiles = 0;
+  for (uint32_t j = e0; j < e0 + count; j++) {
+    if (ids[j] < 0 || (size_t)ids[j] >= s->clouds.size()) return QN_ERR_INVALID_ARG;
+    total += s->sizes[ids[j]]; tiles += (s->sizes[ids[j]] + QN_MAP_TILE - 1) / QN_MAP_TILE;
+  }
+  for (uint32_t t = 0; t < n_seg; t++) { d_xyz_out[t] = nullptr; n_out[t] = 0; status[t] = QN_ERR_EMPTY_CLOUD; }
+  s->bt_ptr.assign(n_seg, nullptr); s->bt_n.assign(n_seg, 0); s->last_error.clear();
+  if (total >= 0xffffffffull) return QN_ERR_CAPACITY;
+  if (total == 0) return QN_OK;
+  KFCHK(s, hipSetDevice(s->device));
+  int rc = kf_reserve(s, total); if (rc != QN_OK) return rc;
+  if ((rc = map_grow(s, (void**)&s->map_kfs, &s->map_kfs_cap, count, sizeof(qn::MapKf))) != QN_OK) return rc;     // (the map's scratch tables, not its slot)
+  if ((rc = map_grow(s, (void**)&s->map_blk, &s->map_blk_cap, tiles, sizeof(uint32_t))) != QN_OK) return rc;
+  if ((rc = map_grow(s, (void**)&s->map_part, &s->map_part_cap, tiles, sizeof(qn::BBoxOut))) != QN_OK) return rc;
+  if ((rc = map_grow(s, (void**)&s->bt_kf_seg, &s->bt_kf_seg_cap, count, sizeof(uint32_t))) != QN_OK) return rc;
+  if ((rc = map_grow(s, (void**)&s->bt_tile_off, &s->bt_tile_off_cap, n_seg + 1, sizeof(uint32_t))) != QN_OK) return rc;
+  if ((rc = map_grow(s, (void**)&s->bt_segs, &s->bt_segs_cap, n_seg, sizeof(qn::BatchSeg))) != QN_OK) return rc;
+  if ((rc = map_grow(s, (void**)&s->bt_bbox, &s->bt_bbox_cap, n_seg, sizeof(qn::BBoxOut))) != QN_OK) return rc;
+  if ((rc = map_grow(s, (void**)&s->bt_res, &s->bt_res_cap, 2 * (size_t)n_seg, sizeof(uint32_t))) != QN_OK) return rc;
+  if ((rc = map_grow(s, (void**)&s->bt_ends, &s->bt_ends_cap, total, sizeof(uint32_t))) != QN_OK) return rc;
+  if ((rc = pin_grow(s, (void**)&s->bt_bbox_host, &s->bt_bbox_host_cap, n_seg, sizeof(qn::BBoxOut))) != QN_OK) return rc;
+  if ((rc = pin_grow(s, (void**)&s->bt_res_host, &s->bt_res_host_cap, 2 * (size_t)n_seg, sizeof(uint32_t))) != QN_OK) return rc;
+  if ((size_t)count * 16 > s->poses_cap) { (void)hipFree(s->poses); s->poses = nullptr; s->poses_cap = 0; KFCHK(s, hipMalloc(&s->poses, sizeof(double) * 16 * (count + 8))); s->poses_cap = (size_t)16 * (count + 8); }
+  // keyframe table, tile -> keyframe, keyframe -> submap, each submap's tile range and point range (host, O(count + tiles))
+  std::vector<qn::MapKf> kfs(count); std::vector<uint32_t> blk(tiles), kseg(count), toff(n_seg + 1), p0(n_seg + 1);
+  uint32_t off = 0, b0 = 0;
+  for (uint32_t t = 0; t < n_seg; t++) {
+    toff[t] = b0; p0[t] = off;
+    for (uint32_t j = seg_off[t]; j < seg_off[t + 1]; j++) {
+      const uint32_t k = j - e0, n = s->sizes[ids[j]], nt = (n + QN_MAP_TILE - 1) / QN_MAP_TILE;
+      kfs[k] = qn::MapKf{s->clouds[ids[j]], off, n, b0, s->has_i[ids[j]]}; kseg[k] = t;
+      for (uint32_t b = 0; b < nt; b++) blk[b0 + b] = k;
+      off += n; b0 += nt;
+    }
+  }
+  toff[n_seg] = b0; p0[n_seg] = off;
+  hipStream_t st = s->stream;
+  const uint32_t n = (uint32_t)total, nt = (uint32_t)tiles;
+  KFCHK(s, hipMemcpyAsync(s->poses, poses + 16 * (size_t)e0, sizeof(double) * 16 * count, hipMemcpyHostToDevice, st));
+  KFCHK(s, hipMemcpyAsync(s->map_kfs, kfs.data(), sizeof(qn::MapKf) * count, hipMemcpyHostToDevice, st));
+  KFCHK(s, hipMemcpyAsync(s->map_blk, blk.data(), sizeof(uint32_t) * tiles, hipMemcpyHostToDevice, st));
+  KFCHK(s, hipMemcpyAsync(s->bt_kf_seg, kseg.data(), sizeof(uint32_t) * count, hipMemcpyHostToDevice, st));
+  KFCHK(s, hipMemcpyAsync(s->bt_tile_off, toff.data(), sizeof(uint32_t) * (n_seg + 1), hipMemcpyHostToDevice, st));
+  // transformPcd of every listed keyframe of every submap (k_map_transform: k_kf_transform's f64 order), per-tile boxes, per-submap reduce
+  hipLaunchKernelGGL(qn::k_map_transform, dim3(nt), dim3(QN_BLOCK), 0, st, (const qn::MapKf*)s->map_kfs, (const uint32_t*)s->map_blk, (const double*)s->poses, s->concat, s->map_part);
+  hipLaunchKernelGGL(qn::k_seg_bbox_reduce, dim3(n_seg), dim3(QN_BLOCK), 0, st, (const qn::BBoxOut*)s->map_part, (const uint32_t*)s->bt_tile_off, s->bt_bbox);
+  KFCHK(s, hipMemcpyAsync(s->bt_bbox_host, s->bt_bbox, sizeof(qn::BBoxOut) * n_seg, hipMemcpyDeviceToHost, st));
+  KFCHK(s, hipStreamSynchronize(st));                               // sync 1 of 2: each submap's box sizes its grid
+  // per submap: pcl::VoxelGrid's grid and overflow guard (voxel_dims), its sentinel leaf and the key bits it needs
+  std::vector<qn::BatchSeg> sg(n_seg); std::vector<int> lbits(n_seg); std::vector<uint32_t> nfin(n_seg), trip_off(n_seg, 0);
+  std::vector<uint8_t> live(n_seg, 0);
+  size_t sum_vox = 0, sum_trip = 0; bool any_nonfinite = false, any_trip = false;
+  for (uint32_t t = 0; t < n_seg; t++) {
+    qn::BatchSeg& g = sg[t];
+    g = qn::BatchSeg{}; g.p0 = p0[t]; g.p1 = p0[t + 1]; g.sentinel = 1; g.tripped = 1; g.nvox = 0;
+    const qn::BBoxOut bb = s->bt_bbox_host[t];
+    nfin[t] = (g.p1 - g.p0) - bb.nonfinite;
+    if (nfin[t]) {
+      live[t] = 1; any_nonfinite |= bb.nonfinite != 0;
+      long long cells = 1;
+      if (voxel_dims(bb, leaf, &g.vd, &cells)) { g.tripped = 0; g.sentinel = (uint32_t)cells; g.nvox = nfin[t]; sum_vox += nfin[t]; }
+      else { any_trip = true; trip_off[t] = (uint32_t)sum_trip; sum_trip += nfin[t]; }
+    }
+    lbits[t] = bits_for(g.sentinel);
+  }
+  if (any_nonfinite) s->last_error = "note: non-finite points dropped (pcl::VoxelGrid on a non-dense cloud)";
+  if (any_trip) s->last_error = kOverflowWarning;
+  if (sum_vox + sum_trip == 0) return QN_OK;                        // every submap empty
+  // sort groups: consecutive submaps whose (submap, leaf) fields fit the 32 key bits above the point index
+  struct Group { uint32_t s0, s1; int L, sb; };
+  std::vector<Group> groups;
+  { uint32_t g0 = 0; int L = 0;
+    for (uint32_t t = 0; t < n_seg; t++) {
+      const int L2 = std::max(L, lbits[t]);
+      if (t > g0 && L2 + bits_for(t - g0) > 32) { groups.push_back(Group{g0, t, L, bits_for(t - 1 - g0)}); g0 = t; L = lbits[t]; }
+      else L = L2;
+    }
+    groups.push_back(Group{g0, n_seg, L, bits_for(n_seg - 1 - g0)}); }
+  for (const Group& gr : groups) for (uint32_t t = gr.s0; t < gr.s1; t++) sg[t].prefix = (t - gr.s0) << gr.L;
+  if ((rc = map_grow(s, (void**)&s->bt_out, &s->bt_out_cap, sum_vox + sum_trip, sizeof(float4))) != QN_OK) return rc;
+  KFCHK(s, hipMemcpyAsync(s->bt_segs, sg.data(), sizeof(qn::BatchSeg) * n_seg, hipMemcpyHostToDevice, st));
+  const qn::MapKf* dkf = s->map_kfs; const uint32_t* dblk = s->map_blk; const uint32_t* dks = s->bt_kf_seg; const qn::BatchSeg* dsg = s->bt_segs;
+  hipLaunchKernelGGL(qn::k_batch_keys, dim3(nt), dim3(QN_BLOCK), 0, st, dkf, dblk, dks, dsg, (const float4*)s->concat, s->keys);
+  // stable LSD passes over each group's (submap, leaf) bits only, on its own point range; every group's result ends in one buffer
+  unsigned long long* fin = nullptr;
+  for (const Group& gr : groups) {
+    const uint32_t gp0 = p0[gr.s0], gn = p0[gr.s1] - gp0;
+    if (!gn) continue;
+    unsigned long long* sorted = s->keys + gp0; unsigned long long* other = s->keys_alt + gp0;
+    const uint32_t rb = (gn + QN_MAP_TILE - 1) / QN_MAP_TILE, hn = rb * 256, hsb = (hn + QN_BLOCK * QN_SCAN_ITEMS - 1) / (QN_BLOCK * QN_SCAN_ITEMS);
+    for (int shift = 32; shift < 32 + gr.L + gr.sb; shift += 8) {
+      hipLaunchKernelGGL(qn::k_map_radix_hist, dim3(rb), dim3(QN_BLOCK), 0, st, (const unsigned long long*)sorted, gn, shift, rb, s->hist);
+      hipLaunchKernelGGL(qn::k_scan_block, dim3(hsb), dim3(QN_BLOCK), 0, st, s->hist, hn, s->hist, s->hist_sums);
+      hipLaunchKernelGGL(qn::k_scan_top, dim3(1), dim3(QN_BLOCK), 0, st, s->hist_sums, hsb);
+      hipLaunchKernelGGL(qn::k_scan_add, dim3(hsb), dim3(QN_BLOCK), 0, st, s->hist, hn, s->hist_sums, gn);
+      hipLaunchKernelGGL(qn::k_map_radix_scatter, dim3(rb), dim3(QN_BLOCK), 0, st, (const unsigned long long*)sorted, gn, shift, rb, (const uint32_t*)s->hist, other);
+      std::swap(sorted, other);
+    }
+    unsigned long long* base = sorted - gp0;
+    if (!fin) fin = base;
+    else if (base != fin) KFCHK(s, hipMemcpyAsync(fin + gp0, sorted, sizeof(unsigned long long) * gn, hipMemcpyDeviceToDevice, st));
+  }
+  // leaves of all submaps at once: heads, exclusive scan, bounds, one thread per leaf
+  const uint32_t sb = (n + QN_BLOCK * QN_SCAN_ITEMS - 1) / (QN_BLOCK * QN_SCAN_ITEMS);
+  hipLaunchKernelGGL(qn::k_batch_leaf_flags, dim3(nt), dim3(QN_BLOCK), 0, st, dkf, dblk, dks, dsg, (const unsigned long long*)fin, s->flag);
+  hipLaunchKernelGGL(qn::k_scan_block, dim3(sb), dim3(QN_BLOCK), 0, st, s->flag, n, s->pos, s->sums);
+  hipLaunchKernelGGL(qn::k_scan_top, dim3(1), dim3(QN_BLOCK), 0, st, s->sums, sb);
+  hipLaunchKernelGGL(qn::k_scan_add_total, dim3(sb), dim3(QN_BLOCK), 0, st, s->pos, n, s->sums, s->flag);
+  if (sum_vox) {
+    hipLaunchKernelGGL(qn::k_batch_leaf_bounds, dim3(nt), dim3(QN_BLOCK), 0, st, dkf, dblk, dks, dsg, (const uint32_t*)s->flag, (const uint32_t*)s->pos, s->heads, s->bt_ends);
+    hipLaunchKernelGGL(qn::k_batch_centroids, dim3((uint32_t)((sum_vox + 255) / 256)), dim3(256), 0, st, (const float4*)s->concat, (const unsigned long long*)fin,
+                       (const uint32_t*)s->heads, (const uint32_t*)s->bt_ends, (const uint32_t*)(s->pos + n), s->bt_out);
+  }
+  for (uint32_t t = 0; t < n_seg; t++)                              // rare: tripped guards, their finite points unfiltered behind the leaves
+    if (live[t] && sg[t].tripped)
+      hipLaunchKernelGGL(qn::k_batch_gather, dim3((nfin[t] + 255) / 256), dim3(256), 0, st, (const unsigned long long*)fin + p0[t], nfin[t], (const float4*)s->concat, s->bt_out + sum_vox + trip_off[t]);
+  hipLaunchKernelGGL(qn::k_batch_counts, dim3((n_seg + 255) / 256), dim3(256), 0, st, dsg, n_seg, (const uint32_t*)s->pos, s->bt_res);
+  KFCHK(s, hipMemcpyAsync(s->bt_res_host, s->bt_res, sizeof(uint32_t) * 2 * n_seg, hipMemcpyDeviceToHost, st));
+  KFCHK(s, hipGetLastError());
+  KFCHK(s, hipStreamSynchronize(st));                               // sync 2 of 2: each submap's first leaf and leaf count
+  for (uint32_t t = 0; t < n_seg; t++) {
+    if (!live[t]) continue;
+    const bool tr = sg[t].tripped != 0;
+    s->bt_ptr[t] = s->bt_out + (tr ? sum_vox + trip_off[t] : s->bt_res_host[2 * t]);
+    s->bt_n[t] = tr ? nfin[t] : s->bt_res_host[2 * t + 1];
+    d_xyz_out[t] = (const float*)s->bt_ptr[t]; n_out[t] = s->bt_n[t]; status[t] = QN_OK;
+  }
+  return QN_OK;
+}
+
+extern "C" int qn_kf_download_batch(qn_kf_store* s, uint32_t seg, float* xyz_out) {     // packed n x 3, for tests / visualisation
+  if (!s || !xyz_out || seg >= s->bt_n.size()) return QN_ERR_INVALID_ARG;
+  const uint32_t n = s->bt_n[seg];
+  if (!n) return QN_OK;
+  KFCHK(s, hipSetDevice(s->device));
+  KFCHK(s, hipMemcpy2D(xyz_out, 12, s->bt_ptr[seg], 16, 12, n, hipMemcpyDeviceToHost));
   return QN_OK;
 }
 

@@ -673,6 +673,46 @@ class KeyframeStore:
         self._check(self._l.qn_kf_download_map(self.h, _p(out), C.c_uint32(16), C.c_uint32(12)))
         return out
 
+    def assemble_batch(self, lists, poses, leaf):
+        """qn_kf_assemble_batch: submap s = lists[s] transformed with poses[s] (one 4x4 per entry), concatenated, voxel grid at `leaf`, all
+        submaps in one pass into the store's batch slot -> [(device pointer of float4 points, count, status)] per submap.  Each equals
+        assemble() of the same list; a submap with no finite point has status QN_ERR_EMPTY_CLOUD.  Valid until the next assemble_batch."""
+        lists = [np.asarray(l, dtype=np.int32).reshape(-1) for l in lists]
+        if len(poses) != len(lists):
+            raise ValueError("assemble_batch: %d lists but %d pose lists" % (len(lists), len(poses)))
+        seg = np.zeros(len(lists) + 1, np.uint32); seg[1:] = np.cumsum([len(l) for l in lists])
+        ids = np.ascontiguousarray(np.concatenate(lists) if lists else np.zeros(0, np.int32), dtype=np.int32)
+        T = np.zeros((max(len(ids), 1), 16), np.float64)
+        for l, P, a in zip(lists, poses, seg[:-1]):
+            T[a:a + len(l)] = np.asarray(P, dtype=np.float64).reshape(len(l), 16)
+        S = len(lists)
+        ptrs = (C.c_void_p * max(S, 1))(); n = np.zeros(max(S, 1), np.uint32); st = np.zeros(max(S, 1), np.int32)
+        self._batch_n = []
+        self._check(self._l.qn_kf_assemble_batch(self.h, _p(ids), _p(T), _p(seg), C.c_uint32(S), C.c_double(leaf), ptrs, _p(n), _p(st)))
+        self._batch_n = [int(v) for v in n[:S]]
+        return [(ptrs[s], int(n[s]), int(st[s])) for s in range(S)]
+
+    def download_batch(self, seg, n):
+        """-> (n, 3) float32: submap `seg` of the latest assemble_batch"""
+        have = self._batch_n[seg] if seg < len(getattr(self, "_batch_n", [])) else None
+        if n != have:
+            raise ValueError("download_batch(%d, %d): the submap holds %s points" % (seg, n, have))
+        out = np.zeros((n, 3), np.float32)
+        self._check(self._l.qn_kf_download_batch(self.h, C.c_uint32(seg), _p(out)))
+        return out
+
+    def loop_submap_pairs(self, poses, query, candidates, submap_range, leaf, enable_quatro=True, enable_submap_matching=False):
+        """LoopClosure::setSrcAndDstCloud for one query and K candidates in ONE assemble_batch: the query's submap once, one submap per candidate.
+        Store ids are keyframe indices; poses[i] = keyframe i's corrected pose, len(poses) keyframes exist.  -> (pairs, status): pairs[k] =
+        (src_ptr, ns, dst_ptr, nt, 16, 1) for gicp_align_batch / coarse_to_fine_align_batch, every pair naming the same source buffer (the batch
+        prepares it once); status = [query submap's] + [each candidate submap's]."""
+        n_kf = len(poses)
+        src = loop_submap_ids(query, query, submap_range, enable_quatro, enable_submap_matching, n_kf)[0]
+        lists = [src] + [loop_submap_ids(query, c, submap_range, enable_quatro, enable_submap_matching, n_kf)[1] for c in candidates]
+        out = self.assemble_batch(lists, [[poses[i] for i in l] for l in lists], leaf)
+        (sp, ns, _), rest = out[0], out[1:]
+        return [(sp, ns, dp, nt, 16, 1) for dp, nt, _ in rest], [o[2] for o in out]
+
 
 def loop_candidates(pos, stamps, query, radius, tdiff, max_k=64):
     pos = np.ascontiguousarray(pos, dtype=np.float64); stamps = np.ascontiguousarray(stamps, dtype=np.float64)
@@ -681,3 +721,14 @@ def loop_candidates(pos, stamps, query, radius, tdiff, max_k=64):
     if st != QN_OK:
         raise EngineError(st, lib().qn_status_str(st).decode())
     return out[:n.value].copy()
+
+
+def loop_submap_ids(src_idx, dst_idx, submap_range, enable_quatro, enable_submap_matching, n_keyframes):
+    """LoopClosure::setSrcAndDstCloud's keyframe lists (loop_closure.cpp:58-108) -> (src_ids, dst_ids).  A submap takes the keyframes within
+    submap_range of its centre except the newest one (`i < keyframes.size() - 1`); without submap matching the source is src_idx alone, and
+    with Quatro so is the destination (dst_idx)."""
+    def around(c):
+        return [i for i in range(c - submap_range, c + submap_range + 1) if 0 <= i < n_keyframes - 1]
+    if enable_submap_matching:
+        return around(src_idx), around(dst_idx)
+    return [src_idx], ([dst_idx] if enable_quatro else around(dst_idx))

@@ -276,6 +276,17 @@ int  qn_kf_add(qn_kf_store*, const float* xyz, uint32_t n, uint32_t stride_bytes
 int  qn_kf_assemble(qn_kf_store*, const int32_t* ids, const double* poses16, uint32_t count, double leaf, int slot,
                     const float** d_xyz_out, uint32_t* n_out);
 int  qn_kf_download(qn_kf_store*, int slot, float* xyz_out /* n x 3 packed */);
+/* S submaps in one pass (setSrcAndDstCloud for one query and its K candidates, loop_closure.cpp:58-108): submap s = transformPcd +
+ * concatenation of ids[seg_off[s] .. seg_off[s+1]) with poses16 of the same entries, voxelizePcd at `leaf` - in all 16 bytes of every record
+ * what qn_kf_assemble builds for that list (ids may repeat, within and across submaps).  d_xyz_out[s] / n_out[s] / status[s] per submap
+ * (float4, stride 16).  Storage is the store's own batch slot: slots 0/1 and the map slot are never touched.  Valid until the next
+ * qn_kf_assemble_batch on this store or its destruction.  Returns QN_OK when the call ran; a submap that is empty after dropping non-finite
+ * points gets status QN_ERR_EMPTY_CLOUD and n 0 without failing the others.  PCL's overflow guard is applied per submap from its own box:
+ * a tripped submap is its finite points, unfiltered, in concatenation order (qn_kf_last_error carries the warning).  Bad id, non-monotone
+ * seg_off, leaf <= 0 or n_seg == 0: QN_ERR_INVALID_ARG before anything runs.  Two host synchronisations per call.                          */
+int  qn_kf_assemble_batch(qn_kf_store*, const int32_t* ids, const double* poses16, const uint32_t* seg_off, uint32_t n_seg, double leaf,
+                          const float** d_xyz_out, uint32_t* n_out, int* status);
+int  qn_kf_download_batch(qn_kf_store*, uint32_t seg, float* xyz_out /* n x 3 packed */);
 /* the corrected global map = the three loops of FastLioSamQn that rebuild it from every keyframe with its corrected pose
  * (fast_lio_sam_qn.cpp:302-316 visTimerFunc, :398-411 saveFlagCallback, :435-448 the destructor's result.pcd): transformPcd of each
  * listed keyframe, concatenation in `ids` order (ids may repeat), voxelizePcd at save_voxel_resolution (pcl::VoxelGrid,
