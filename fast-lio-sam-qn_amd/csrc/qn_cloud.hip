@@ -18,6 +18,7 @@
 #include <algorithm>
 #include "../../include/qn_engine.h"
 #include "qn_util_kernels.cuh"
+#include "qn_kf_internal.h"
 
 namespace qn {
 
@@ -401,6 +402,8 @@ struct qn_kf_store {
   uint32_t* bt_ends = nullptr; size_t bt_ends_cap = 0; uint32_t* bt_kf_seg = nullptr; size_t bt_kf_seg_cap = 0; uint32_t* bt_tile_off = nullptr; size_t bt_tile_off_cap = 0;
   qn::BatchSeg* bt_segs = nullptr; size_t bt_segs_cap = 0; qn::BBoxOut* bt_bbox = nullptr; size_t bt_bbox_cap = 0; uint32_t* bt_res = nullptr; size_t bt_res_cap = 0;
   qn::BBoxOut* bt_bbox_host = nullptr; size_t bt_bbox_host_cap = 0; uint32_t* bt_res_host = nullptr; size_t bt_res_host_cap = 0;
+  // scratch of other translation units (the ray-caster, qn_sim.hip): see qn_kf_internal.h
+  void* int_scratch[QN_KF_INT_SCRATCH] = {}; size_t int_scratch_cap[QN_KF_INT_SCRATCH] = {}; void* int_pinned = nullptr; size_t int_pinned_cap = 0;
   std::string last_error;
 };
 #define KFCHK(s, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { (s)->last_error = std::string(#call) + " -> " + hipGetErrorString(e_); return QN_ERR_HIP; } } while (0)
@@ -425,6 +428,8 @@ extern "C" void qn_kf_store_destroy(qn_kf_store* s) {
   (void)hipFree(s->hist); (void)hipFree(s->hist_sums); (void)hipFree(s->out[0]); (void)hipFree(s->out[1]); (void)hipFree(s->poses); (void)hipFree(s->bbox); (void)hipFree(s->staging);
   (void)hipFree(s->map); (void)hipFree(s->map_kfs); (void)hipFree(s->map_blk); (void)hipFree(s->map_part);
   (void)hipFree(s->bt_out); (void)hipFree(s->bt_ends); (void)hipFree(s->bt_kf_seg); (void)hipFree(s->bt_tile_off); (void)hipFree(s->bt_segs); (void)hipFree(s->bt_bbox); (void)hipFree(s->bt_res);
+  for (void* p : s->int_scratch) (void)hipFree(p);
+  if (s->int_pinned) (void)hipHostFree(s->int_pinned);
   if (s->bt_bbox_host) (void)hipHostFree(s->bt_bbox_host); if (s->bt_res_host) (void)hipHostFree(s->bt_res_host);
   if (s->bbox_host) (void)hipHostFree(s->bbox_host); if (s->count_host) (void)hipHostFree(s->count_host);
   if (s->stream) (void)hipStreamDestroy(s->stream);
@@ -459,6 +464,80 @@ static bool xyzi_layout_ok(uint32_t stride, uint32_t ioff) { return !(stride & 3
 extern "C" int qn_kf_add_xyzi(qn_kf_store* s, const float* pts, uint32_t n, uint32_t stride, uint32_t ioff, int32_t* id_out) {
   if (!s || !id_out || (n && !pts) || !xyzi_layout_ok(stride, ioff)) return QN_ERR_INVALID_ARG;
   return kf_add(s, pts, n, stride, (int)ioff, id_out);
+}
+
+// ---- keyframes from device memory (qn_kf_add_device) and read-back of one keyframe (qn_kf_download_keyframe)
+// The record layout rules of qn_kf_add / qn_kf_add_xyzi, and the same pack kernels: the resident bytes are identical for the same input bytes.
+static bool device_layout_ok(uint32_t stride, int32_t ioff) { return ioff < 0 ? (stride >= 12 && !(stride & 3)) : xyzi_layout_ok(stride, (uint32_t)ioff); }
+int qn_kf_int_copy_async(qn_kf_store* s, const void* d_pts, uint32_t n, uint32_t stride, int32_t ioff, float4** out) {
+  *out = nullptr;
+  if (!n) return QN_OK;
+  KFCHK(s, hipSetDevice(s->device));
+  float4* d = nullptr;
+  KFCHK(s, hipMalloc(&d, sizeof(float4) * n));
+  if (ioff < 0) hipLaunchKernelGGL(qn::k_pack_points, dim3((n + 255) / 256), dim3(256), 0, s->stream, (const char*)d_pts, stride, n, d);
+  else hipLaunchKernelGGL(qn::k_pack_xyzi, dim3((n + 255) / 256), dim3(256), 0, s->stream, (const char*)d_pts, stride, (uint32_t)ioff, n, d);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) { (void)hipFree(d); s->last_error = std::string("kf_add_device -> ") + hipGetErrorString(e); return QN_ERR_HIP; }
+  *out = d;
+  return QN_OK;
+}
+void qn_kf_int_append(qn_kf_store* s, float4* const* bufs, const uint32_t* n, uint32_t count, bool has_i, int32_t* ids_out) {
+  for (uint32_t k = 0; k < count; k++) {
+    s->clouds.push_back(bufs[k]); s->sizes.push_back(n[k]); s->has_i.push_back(has_i);
+    ids_out[k] = (int32_t)s->clouds.size() - 1;
+  }
+}
+int qn_kf_int_device(const qn_kf_store* s) { return s->device; }
+hipStream_t qn_kf_int_stream(const qn_kf_store* s) { return s->stream; }
+size_t qn_kf_int_count(const qn_kf_store* s) { return s->clouds.size(); }
+void qn_kf_int_set_error(qn_kf_store* s, const char* msg) { s->last_error = msg; }
+void* qn_kf_int_scratch(qn_kf_store* s, int which, size_t bytes) {
+  if (which < 0 || which >= QN_KF_INT_SCRATCH) return nullptr;
+  if (bytes > s->int_scratch_cap[which]) {
+    (void)hipFree(s->int_scratch[which]); s->int_scratch[which] = nullptr; s->int_scratch_cap[which] = 0;
+    if (hipMalloc(&s->int_scratch[which], bytes) != hipSuccess) { s->int_scratch[which] = nullptr; return nullptr; }
+    s->int_scratch_cap[which] = bytes;
+  }
+  return s->int_scratch[which];
+}
+void* qn_kf_int_pinned(qn_kf_store* s, size_t bytes) {
+  if (bytes > s->int_pinned_cap) {
+    if (s->int_pinned) (void)hipHostFree(s->int_pinned);
+    s->int_pinned = nullptr; s->int_pinned_cap = 0;
+    if (hipHostMalloc(&s->int_pinned, bytes, hipHostMallocDefault) != hipSuccess) { s->int_pinned = nullptr; return nullptr; }
+    s->int_pinned_cap = bytes;
+  }
+  return s->int_pinned;
+}
+extern "C" int qn_kf_add_device(qn_kf_store* s, const float* d_pts, uint32_t n, uint32_t stride, int32_t ioff, int32_t* id_out) {
+  if (!s || !id_out || (n && !d_pts) || !device_layout_ok(stride, ioff) || ((uintptr_t)d_pts & 3)) return QN_ERR_INVALID_ARG;
+  if (n) {        // the records must lie inside one device allocation of this store's device: a host pointer here would fault the GPU
+    KFCHK(s, hipSetDevice(s->device));
+    hipPointerAttribute_t a{};
+    if (hipPointerGetAttributes(&a, d_pts) != hipSuccess || a.type != hipMemoryTypeDevice || a.device != s->device) { (void)hipGetLastError(); return QN_ERR_INVALID_ARG; }
+    hipDeviceptr_t base = nullptr; size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)d_pts) != hipSuccess) { (void)hipGetLastError(); return QN_ERR_INVALID_ARG; }
+    const size_t need = (size_t)(n - 1) * stride + (ioff < 0 ? 12 : std::max<size_t>(12, (size_t)ioff + 4));
+    if ((const char*)d_pts < (const char*)base || (size_t)((const char*)d_pts - (const char*)base) + need > size) return QN_ERR_INVALID_ARG;
+  }
+  float4* d = nullptr;
+  const int st = qn_kf_int_copy_async(s, d_pts, n, stride, ioff, &d);
+  if (st != QN_OK) return st;
+  if (n) {
+    const hipError_t e = hipStreamSynchronize(s->stream);      // the caller may reuse its buffer when this returns
+    if (e != hipSuccess) { (void)hipFree(d); s->last_error = std::string("kf_add_device -> ") + hipGetErrorString(e); return QN_ERR_HIP; }
+  }
+  qn_kf_int_append(s, &d, &n, 1, ioff >= 0, id_out);
+  return QN_OK;
+}
+extern "C" int qn_kf_download_keyframe(qn_kf_store* s, int32_t id, float* xyzi_out) {
+  if (!s || id < 0 || (size_t)id >= s->clouds.size() || (s->sizes[id] && !xyzi_out)) return QN_ERR_INVALID_ARG;
+  const uint32_t n = s->sizes[id];
+  if (!n) return QN_OK;
+  KFCHK(s, hipSetDevice(s->device));
+  KFCHK(s, hipMemcpy(xyzi_out, s->clouds[id], sizeof(float4) * n, hipMemcpyDeviceToHost));
+  return QN_OK;
 }
 
 static int kf_reserve(qn_kf_store* s, size_t n) {

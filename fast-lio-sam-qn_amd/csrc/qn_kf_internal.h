@@ -1,0 +1,21 @@
+// qn_kf_internal.h - what another translation unit may do with a qn_kf_store (its struct lives in qn_cloud.hip).
+// Used by the ray-caster (qn_sim.hip), which writes keyframes straight into the store without host staging.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <cstdint>
+#include <cstddef>
+#include "../../include/qn_engine.h"
+
+int  qn_kf_int_device(const qn_kf_store* s);
+hipStream_t qn_kf_int_stream(const qn_kf_store* s);
+size_t qn_kf_int_count(const qn_kf_store* s);                                    // keyframes stored so far
+void qn_kf_int_set_error(qn_kf_store* s, const char* msg);
+// per-store scratch buffer `which` (0 .. QN_KF_INT_SCRATCH - 1) of at least `bytes`; grown only, freed with the store.  nullptr on failure.
+#define QN_KF_INT_SCRATCH 8
+void* qn_kf_int_scratch(qn_kf_store* s, int which, size_t bytes);
+void* qn_kf_int_pinned(qn_kf_store* s, size_t bytes);                           // one pinned host buffer, same rules
+// the adopt path of qn_kf_add_device without its final synchronisation: allocates the keyframe's float4 buffer and enqueues the copy of
+// n records (xyz at 0, intensity at ioff, ioff < 0: none) on the store's stream; *out = the new buffer (nullptr when n == 0).
+int  qn_kf_int_copy_async(qn_kf_store* s, const void* d_pts, uint32_t n, uint32_t stride, int32_t ioff, float4** out);
+// append keyframes whose buffers were made by qn_kf_int_copy_async (after the stream has been synchronised); ids are consecutive.
+void qn_kf_int_append(qn_kf_store* s, float4* const* bufs, const uint32_t* n, uint32_t count, bool has_i, int32_t* ids_out);

@@ -604,6 +604,12 @@ class MultiGpu:
 
 
 # ---------------------------------------------------------------------------------------- keyframe store / cloud assembly
+class SimSensor(C.Structure):
+    """qn_sim_sensor"""
+    _fields_ = [("n_beams", C.c_uint32), ("n_cols", C.c_uint32), ("cos_el", C.c_void_p), ("sin_el", C.c_void_p), ("cos_az", C.c_void_p),
+                ("sin_az", C.c_void_p), ("min_range", C.c_double), ("max_range", C.c_double), ("sigma", C.c_double)]
+
+
 class KeyframeStore:
     """Device-resident keyframe clouds + LoopClosure::setSrcAndDstCloud on the GPU (loop_closure.cpp:58-108)."""
 
@@ -615,6 +621,7 @@ class KeyframeStore:
         self.h = h
         self._l.qn_kf_last_error.restype = C.c_char_p; self._l.qn_kf_last_error.argtypes = [C.c_void_p]
         self._l.qn_kf_store_destroy.argtypes = [C.c_void_p]
+        self._sizes = {}                                             # keyframe id -> number of points (for keyframe())
 
     def close(self):
         if getattr(self, "h", None):
@@ -636,13 +643,52 @@ class KeyframeStore:
         if intensity is None:
             a, n, stride = _cloud_arg(xyz)
             self._check(self._l.qn_kf_add(self.h, _p(a), C.c_uint32(n), C.c_uint32(stride), C.byref(kid)))
+            self._sizes[kid.value] = n
             return kid.value
         xyz = np.asarray(xyz, dtype=np.float32); intensity = np.asarray(intensity, dtype=np.float32).reshape(-1)
         if xyz.ndim != 2 or xyz.shape[1] < 3 or len(intensity) != len(xyz):
             raise ValueError("cloud must be (n, >=3) float32 with n intensities")
         a = np.empty((len(xyz), 4), np.float32); a[:, :3] = xyz[:, :3]; a[:, 3] = intensity
         self._check(self._l.qn_kf_add_xyzi(self.h, _p(a), C.c_uint32(len(a)), C.c_uint32(16), C.c_uint32(12), C.byref(kid)))
+        self._sizes[kid.value] = len(a)
         return kid.value
+
+    def add_device(self, ptr, n, stride, intensity_offset=None):
+        """qn_kf_add_device: a keyframe from n records in device memory at `ptr` (an int address, e.g. tensor.data_ptr(); the producer's
+        stream must be synchronised): xyz at byte 0 of each `stride`-byte record, intensity at `intensity_offset` (None: xyz only, as add)."""
+        kid = C.c_int32()
+        ioff = -1 if intensity_offset is None else int(intensity_offset)
+        self._check(self._l.qn_kf_add_device(self.h, C.c_void_p(ptr), C.c_uint32(n), C.c_uint32(stride), C.c_int32(ioff), C.byref(kid)))
+        self._sizes[kid.value] = int(n)
+        return kid.value
+
+    def add_lidar_scans(self, prims, sensor, poses, seeds):
+        """qn_sim_lidar_to_store: ray-cast one spinning-LiDAR scan (synth.SpinningLidar) of the primitives (synth.PRIM_DTYPE) per pose
+        (sensor -> world 4x4) and seed, on the GPU, each straight into the store as an intensity keyframe -> ids (consecutive).
+        Each keyframe equals synth.lidar_scan(prims, sensor, pose, seed) bit for bit."""
+        from . import synth
+        prims = np.ascontiguousarray(prims, dtype=synth.PRIM_DTYPE).reshape(-1)
+        poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 16)
+        seeds = np.ascontiguousarray(seeds, dtype=np.uint32).reshape(-1)
+        if len(seeds) != len(poses):
+            raise ValueError("add_lidar_scans: %d poses but %d seeds" % (len(poses), len(seeds)))
+        tabs = [np.ascontiguousarray(t, dtype=np.float64) for t in sensor.tables()]
+        sen = SimSensor(sensor.n_beams, sensor.n_cols, *[t.ctypes.data for t in tabs], sensor.min_range, sensor.max_range, sensor.sigma)
+        S = len(poses)
+        ids = np.zeros(max(S, 1), np.int32); n = np.zeros(max(S, 1), np.uint32)
+        self._check(self._l.qn_sim_lidar_to_store(self.h, _p(prims) if len(prims) else None, C.c_uint32(len(prims)), C.byref(sen), _p(poses),
+                                                  _p(seeds), C.c_uint32(S), _p(ids), _p(n)))
+        self._sizes.update(zip(ids[:S].tolist(), n[:S].tolist()))
+        return ids[:S].copy()
+
+    def keyframe(self, kid):
+        """-> (n, 4) float32: the resident records of keyframe `kid` (x y z, intensity or 1), qn_kf_download_keyframe"""
+        n = self._sizes.get(int(kid))
+        if n is None:
+            raise ValueError("keyframe(%d): no such keyframe in this store" % kid)
+        out = np.zeros((n, 4), np.float32)
+        self._check(self._l.qn_kf_download_keyframe(self.h, C.c_int32(kid), _p(out)))
+        return out
 
     def assemble(self, ids, poses, leaf, slot):
         """-> (device pointer of float4 points, count)"""

@@ -304,6 +304,54 @@ int  qn_kf_download_map(qn_kf_store*, void* out, uint32_t stride_bytes, uint32_t
 int  qn_loop_candidates(const double* pos_xyz, const double* stamps, uint32_t n, uint32_t query, double radius, double tdiff,
                         uint32_t max_k, int32_t* out, uint32_t* n_out);
 
+/* ---- keyframes from device memory, and back ----------------------------------------------------------------------------------
+ * qn_kf_add_device: a keyframe from a DEVICE buffer (a GPU front end, a torch tensor) with no host staging.  Record i is at
+ * d_pts + i * stride_bytes: xyz at byte 0, intensity at intensity_offset_bytes (< 0: none, as qn_kf_add; else the qn_kf_add_xyzi layout
+ * rules).  The resident keyframe is byte-identical to qn_kf_add / qn_kf_add_xyzi of the same bytes.  The records must lie inside one
+ * device allocation on the store's device (checked: QN_ERR_INVALID_ARG otherwise) and be complete when the call is made (synchronise their
+ * producer's stream first); the call returns once they have been copied, so the caller may reuse the buffer.
+ * qn_kf_download_keyframe: the resident float4 records of keyframe `id` (n x 4 floats: x y z and .w = intensity for qn_kf_add_xyzi /
+ * qn_kf_add_device with intensity / simulated keyframes, 1 for xyz-only ones), for tests and visualisation.                        */
+int  qn_kf_add_device(qn_kf_store*, const float* d_pts, uint32_t n, uint32_t stride_bytes, int32_t intensity_offset_bytes, int32_t* id_out);
+int  qn_kf_download_keyframe(qn_kf_store*, int32_t id, float* xyzi_out /* n x 4 */);
+
+/* ---- spinning-LiDAR scans ray-cast into the keyframe store (csrc/qn_sim.hip; numpy twin: qn_amd/synth.lidar_scan) -----------
+ * The scene is a flat array of analytic primitives:
+ *   QN_SIM_GROUND p = (x0, y0, x1, y1, -, -)   plane z = 0 over [x0, x1] x [y0, y1]
+ *   QN_SIM_WALL   p = (x0, y0, dx, dy, H, -)   vertical rectangle: dy == 0 -> plane y = y0, x in [x0, x0 + dx]; else plane x = x0,
+ *                                              y in [y0, y0 + dy]; z in [0, H]
+ *   QN_SIM_POLE   p = (cx, cy, r, H, -, -)     side surface of a vertical cylinder, z in [0, H]
+ *   QN_SIM_BOX    p = (cx, cy, sx, sy, H, -)   four sides and the top of an axis-aligned box standing on z = 0
+ * The sensor casts n_beams x n_cols rays; the host computes every transcendental (cos / sin of each elevation and azimuth).  Ray (beam,
+ * col) of scan s starts at the translation of poses16[s] (sensor -> world, row-major) along R u, u = (cos el cos az, cos el sin az,
+ * sin el); primitives are tested in index order and a hit is kept only when strictly nearer (ties go to the lowest index).  The range
+ * noise is sigma * sqrt(3) * (u0 + u1 + u2 + u3 - 2), u_i from a counter-based hash of (seeds[s], beam, col, i); the noisy range t' is
+ * kept when min_range <= t' <= max_range, and the record is (t' u, intensity) in the SENSOR frame, intensity = a function of the kind and
+ * |n . d|.  All arithmetic is f64 (no fused multiply-add), rounded to f32 once: the records equal the numpy twin's bit for bit.
+ * Each scan becomes one keyframe (float4 x y z intensity, counted as a qn_kf_add_xyzi keyframe by qn_kf_build_map), hits in (beam, col)
+ * order; ids_out[s] are consecutive and n_out[s] is the scan's count (0 allowed).  Every argument is checked before anything runs
+ * (QN_ERR_INVALID_ARG, store unchanged): kinds, finite parameters and poses, tables in [-1, 1], 0 <= min_range < max_range,
+ * sigma >= 0, and the caps below.  Device scratch is about 40 bytes per ray of the call, kept by the store.  Two host synchronisations
+ * per call, whatever n_scans is.                                                                                                     */
+enum { QN_SIM_GROUND = 0, QN_SIM_WALL = 1, QN_SIM_POLE = 2, QN_SIM_BOX = 3 };
+#define QN_SIM_MAX_PRIMS 4096u                     /* primitives per scene (each ray tests all of them)              */
+#define QN_SIM_MAX_RAYS (1u << 20)                 /* n_beams x n_cols per scan                                      */
+#define QN_SIM_MAX_SCANS 65535u                    /* scans per call (grid dimension y)                              */
+#define QN_SIM_MAX_TOTAL_RAYS (1ull << 27)         /* n_beams x n_cols x n_scans per call (~1160 default 64 x 1800 scans) */
+typedef struct {
+  uint32_t kind;                                   /* QN_SIM_GROUND / WALL / POLE / BOX */
+  uint32_t pad_;
+  double p[6];
+} qn_sim_prim;
+typedef struct {
+  uint32_t n_beams, n_cols;
+  const double *cos_el, *sin_el;                   /* [n_beams] */
+  const double *cos_az, *sin_az;                   /* [n_cols]  */
+  double min_range, max_range, sigma;              /* blind radius, detection range, range noise [m] */
+} qn_sim_sensor;
+int  qn_sim_lidar_to_store(qn_kf_store*, const qn_sim_prim* prims, uint32_t n_prims, const qn_sim_sensor* sensor, const double* poses16,
+                           const uint32_t* seeds, uint32_t n_scans, int32_t* ids_out, uint32_t* n_out);
+
 /* ---- per-stage read-backs used by the parity tests (not needed by the shims) ------------ */
 int  qn_gicp_get_covariances(qn_ctx*, int which, double* cov9_out);   /* n x 9 f64, original point order */
 int  qn_gicp_knn(qn_ctx*, int which, int k, int32_t* idx_out, float* d2_out);   /* self k-NN of a cloud, n x k */

@@ -146,6 +146,30 @@ def make_stream(n_kf, seed, scan_range=28.0, drift_yaw=0.004, drift_xy=0.03, pts
     return scans, gt, odom, np.arange(n_kf) * 1.0
 
 
+def make_lidar_stream(n_kf, seed, lidar=None, drift_yaw=0.004, drift_xy=0.03, yaw_bias=0.006):
+    """The figure-8 of make_stream seen by a spinning LiDAR: the scene's primitives, the sensor, one noise seed per keyframe and the
+    ground-truth / odometry poses.  The keyframe clouds are ray-cast from the ground-truth poses (sensor frame): on the GPU straight into
+    the keyframe store (KeyframeStore.add_lidar_scans), for the oracle by the numpy twin synth.lidar_scan - the same bits."""
+    from qn_amd import synth
+    lidar = synth.SpinningLidar(n_beams=32, n_cols=360) if lidar is None else lidar      # few columns: the oracle casts with numpy
+    rng = np.random.default_rng(seed)
+    scene = synth.Scene(rng, 120.0)
+    s = np.linspace(0, 2 * np.pi, n_kf, endpoint=False)
+    xy = np.c_[30 * np.sin(s), 22 * np.sin(2 * s)]
+    head = np.arctan2(np.gradient(xy[:, 1]), np.gradient(xy[:, 0]))
+    gt = []
+    for k in range(n_kf):
+        T = np.eye(4); T[:3, :3] = synth._rot_zyx(head[k], 0, 0); T[:3, 3] = [xy[k, 0], xy[k, 1], 1.8]
+        gt.append(T)
+    seeds = rng.integers(0, 2 ** 32, n_kf).astype(np.uint32)
+    odom = [gt[0].copy()]
+    for k in range(1, n_kf):
+        rel = inv(gt[k - 1]) @ gt[k]
+        noise = exp_se3(np.r_[0, 0, rng.normal(0, drift_yaw) + yaw_bias, rng.normal(0, drift_xy, 2), 0])
+        odom.append(odom[-1] @ rel @ noise)
+    return scene.primitives(), lidar, seeds, gt, odom, np.arange(n_kf) * 1.0
+
+
 def rot_to_quat(R):
     """(qx, qy, qz, qw) of a rotation matrix (what tf::Matrix3x3::getRotation yields in poseEigToPoseStamped, utilities.hpp)"""
     t = np.trace(R)
@@ -186,8 +210,16 @@ def ate(poses, gt):
 
 
 def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, submap_range=5, score_thr=1.5, verbose=True, backend="gpu", save_dir=None,
-        save_map_leaf=None):
-    scans, gt, odom, stamps = make_stream(n_kf, seed)
+        save_map_leaf=None, sensor="uniform"):
+    """sensor = "uniform": keyframe clouds sampled uniformly by area inside a disc (make_stream); "spinning": ray-cast spinning-LiDAR
+    scans from the ground-truth poses of the same figure-8 (make_lidar_stream)."""
+    if sensor == "uniform":
+        scans, gt, odom, stamps = make_stream(n_kf, seed)
+    elif sensor == "spinning":
+        prims, lidar, seeds, gt, odom, stamps = make_lidar_stream(n_kf, seed)
+        scans = None
+    else:
+        raise ValueError("sensor must be 'uniform' or 'spinning', not %r" % (sensor,))
     if backend == "gpu":
         from qn_amd import engine
         store = engine.KeyframeStore()
@@ -196,15 +228,20 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
         g.setCorrespondenceRandomness(15); g.setMaximumIterations(32); g.setMaxCorrespondenceDistance(1.5 * radius); g.setTransformationEpsilon(0.01)
         quatro = engine.Quatro(ctx) if use_quatro else None
         loop_candidates = engine.loop_candidates
+        if scans is None:                                           # one call casts every keyframe into the store
+            cast_ids = list(store.add_lidar_scans(prims, lidar, gt, seeds))
     else:
         from oracle import oracle as orc                           # the checker's side of the comparison (tests only)
         loop_candidates = orc.loop_candidates
+        if scans is None:
+            from qn_amd import synth
+            scans = [synth.lidar_scan(prims, lidar, T, int(sd))[:, :3] for T, sd in zip(gt, seeds)]
     pg = PoseGraph(); ids = []; corrected = []
     prior_var = np.array([1e-4, 1e-4, 1e-4, 1e-2, 1e-2, 1e-2]); odom_var = prior_var.copy()   # FQ:112-114, 132-133 (rot, then trans)
     loops = []; t_reg = []
     for k in range(n_kf):
         if backend == "gpu":
-            ids.append(store.add(scans[k]))
+            ids.append(store.add(scans[k]) if scans is not None else cast_ids[k])
         pose = odom[k] if k == 0 else corrected[-1] @ (inv(odom[k - 1]) @ odom[k])           # realtime pose = last corrected * delta odom (FQ:93-103)
         pg.add_pose(pose); corrected.append(pose)
         if k == 0:
@@ -249,7 +286,7 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
         loops.append((k, c, score))
         pg.optimize()
         corrected = [p.copy() for p in pg.poses]                                             # FQ:180-188
-    out = dict(n_keyframes=n_kf, loops=len(loops), attempts=len(t_reg), ate_odometry=ate(odom, gt), ate_corrected=ate(corrected, gt),
+    out = dict(sensor=sensor, n_keyframes=n_kf, loops=len(loops), attempts=len(t_reg), ate_odometry=ate(odom, gt), ate_corrected=ate(corrected, gt),
                ms_per_attempt=1e3 * float(np.mean(t_reg)) if t_reg else None, quatro=use_quatro, loop_list=loops, poses=corrected)
     if save_dir:
         write_kitti_tum(save_dir, corrected, stamps)
@@ -268,7 +305,8 @@ if __name__ == "__main__":
     ap.add_argument("--keyframes", type=int, default=70)
     ap.add_argument("--quatro", action="store_true")
     ap.add_argument("--seed", type=int, default=7)
+    ap.add_argument("--sensor", choices=["uniform", "spinning"], default="uniform", help="keyframe clouds: uniform surface samples, or ray-cast spinning-LiDAR scans")
     ap.add_argument("--save-dir", default=None, help="write poses_kitti.txt / poses_tum.txt (FQ:344-373) here")
     ap.add_argument("--save-map-leaf", type=float, default=None, help="with --save-dir: also write map.pcd, the corrected map at this leaf (0.3 = save_voxel_resolution)")
     a = ap.parse_args()
-    run(a.keyframes, a.seed, a.quatro, save_dir=a.save_dir, save_map_leaf=a.save_map_leaf)
+    run(a.keyframes, a.seed, a.quatro, save_dir=a.save_dir, save_map_leaf=a.save_map_leaf, sensor=a.sensor)
