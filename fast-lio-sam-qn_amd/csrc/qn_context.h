@@ -135,4 +135,7 @@ struct qn_ctx {
 
   void set_error(const char* what, hipError_t e, int line);
   void prof_begin(int family, int count = 1); void prof_end(); void prof_collect();
+  // lanes per query of the FPFH kernels quatro_fpfh launches (knobs normals_fg / fpfh_fg; 0 = 8): k_normals_group<16> / <8> or k_normals (1); k_spfh + k_fpfh <16> / <8>
+  int quatro_normals_width() const { const int g = normals_fg > 0 ? normals_fg : 8; return g >= 16 ? 16 : (g >= 8 ? 8 : 1); }
+  int quatro_fpfh_width() const { const int g = fpfh_fg > 0 ? fpfh_fg : 8; return g >= 16 ? 16 : 8; }
 };

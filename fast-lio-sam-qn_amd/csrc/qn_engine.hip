@@ -1313,6 +1313,8 @@ extern "C" int qn_debug_get(qn_ctx* c, const char* key, double* value) {
   if (k == "quatro_wall_match_ms") { *value = c->q_wall_ms[1]; return QN_OK; }
   if (k == "quatro_wall_solve_ms") { *value = c->q_wall_ms[2]; return QN_OK; }
   if (k == "extra_unseeded") { *value = c->last_extra_unseeded; return QN_OK; }          // the adaptive hand-over's decision in the latest align (ticks)
+  if (k == "normals_width") { *value = c->quatro_normals_width(); return QN_OK; }      // lanes per query of the next FPFH normals / SPFH + FPFH launches (knobs normals_fg / fpfh_fg)
+  if (k == "fpfh_width") { *value = c->quatro_fpfh_width(); return QN_OK; }
   if (k == "persist_launches") { *value = c->persist_launches; return QN_OK; }
   if (k == "persist_gave_up") { *value = c->persist_gave_up; return QN_OK; }      // persistent launches that gave up and were re-run on the k_tick chain
   if (k == "persist_fits") { *value = c->persist_fits ? 1 : 0; return QN_OK; }

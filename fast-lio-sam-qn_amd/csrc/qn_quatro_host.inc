@@ -128,6 +128,15 @@ static std::vector<int> max_clique_lex(const std::vector<uint8_t>& a, int n) {  
 }
 
 static double tls_estimate(std::vector<double> X, double alpha) {      // TEASER++ TLSEstimator, one axis
+  if (!(alpha > 0)) {
+    // noise_bound = 0: the sweep below would weigh by 1 / 0 and every estimate would be NaN (the translation came out 0 whatever the data).  Defined as the
+    // estimate's limit for a bound going to 0: the value the most measurements share exactly, the smallest one on a tie (the first the sweep meets)
+    X.erase(std::remove_if(X.begin(), X.end(), [](double v) { return v != v; }), X.end());
+    std::sort(X.begin(), X.end());
+    double best = 0; int run = 0, best_run = 0;
+    for (size_t i = 0; i < X.size(); i++) { run = (i > 0 && X[i] == X[i - 1]) ? run + 1 : 1; if (run > best_run) { best_run = run; best = X[i]; } }
+    return best;
+  }
   const int N = (int)X.size();
   std::vector<std::pair<double, int>> h; h.reserve(2 * N);
   for (int i = 0; i < N; i++) { h.emplace_back(X[i] - alpha, i + 1); h.emplace_back(X[i] + alpha, -i - 1); }
@@ -346,8 +355,8 @@ static int quatro_fpfh(qn_ctx* c, int w) {                                  // K
   // lanes per query: a cloud is a small grid for this chip - the fewer its points, the more lanes share a query's neighbourhood walk (knobs normals_fg / fpfh_fg; 0 = by cloud size)
   // measured (tools/gpu_quatro_ab.py, profiles/r5_*_quatro_ab.txt): normals 1 -> 8 lanes: 0.103 -> 0.066 ms at 30k (both clouds), 0.200 -> 0.125 at 100k, 16 lanes slower again;
   // SPFH / FPFH 8 -> 16 lanes: slower at both sizes (the 33 group sums double)
-  const int nfg = c->normals_fg > 0 ? c->normals_fg : 8;
-  const int ffg = c->fpfh_fg > 0 ? c->fpfh_fg : 8;
+  const int nfg = c->quatro_normals_width();
+  const int ffg = c->quatro_fpfh_width();
   { ProfScope ps(c, QN_K_FPFH_NORMALS);
     if (nfg >= 16) hipLaunchKernelGGL((k_normals_group<16>), dim3(nb * 16), dim3(QN_BLOCK), 0, s, b.grid, rn, rn2, c->q_normals[w]);
     else if (nfg >= 8) hipLaunchKernelGGL((k_normals_group<8>), dim3(nb * 8), dim3(QN_BLOCK), 0, s, b.grid, rn, rn2, c->q_normals[w]);
@@ -728,12 +737,17 @@ extern "C" int qn_quatro_solve(const float* src, const float* dst, uint32_t stri
 
 extern "C" int qn_quatro_solve_scaled(const float* src, const float* dst, uint32_t stride, const int32_t* corres_pairs, uint32_t n_corres, const qn_quatro_params* p,
                                       double T[16], int* valid, int32_t* clique, uint32_t* n_clique, double* scale) {
-  if (!src || !dst || !p || !T || !valid || !scale || (n_corres && !corres_pairs)) return QN_ERR_INVALID_ARG;
+  int32_t it;
+  return qn_quatro_solve_iter(src, dst, stride, corres_pairs, n_corres, p, T, valid, clique, n_clique, scale, &it);
+}
+extern "C" int qn_quatro_solve_iter(const float* src, const float* dst, uint32_t stride, const int32_t* corres_pairs, uint32_t n_corres, const qn_quatro_params* p,
+                                    double T[16], int* valid, int32_t* clique, uint32_t* n_clique, double* scale, int32_t* rot_iterations) {
+  if (!src || !dst || !p || !T || !valid || !scale || !rot_iterations || (n_corres && !corres_pairs)) return QN_ERR_INVALID_ARG;
   auto at = [](const float* base, uint32_t st, int i) { return (const float*)((const char*)base + (size_t)i * st); };
   std::vector<qnq::P3> S(n_corres), D(n_corres);
   for (uint32_t k = 0; k < n_corres; k++) for (int d = 0; d < 3; d++) { S[k][d] = at(src, stride, corres_pairs[2 * k])[d]; D[k][d] = at(dst, stride, corres_pairs[2 * k + 1])[d]; }
   qnq::SolveOut so; qnq::solve(S, D, *p, &so);
-  memcpy(T, so.T, sizeof(so.T)); *valid = so.valid; *scale = so.scale;
+  memcpy(T, so.T, sizeof(so.T)); *valid = so.valid; *scale = so.scale; *rot_iterations = so.rot_iterations;
   if (n_clique) { *n_clique = (uint32_t)so.clique.size(); if (clique) for (size_t i = 0; i < so.clique.size(); i++) clique[i] = so.clique[i]; }
   return QN_OK;
 }

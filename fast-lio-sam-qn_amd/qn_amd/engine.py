@@ -423,11 +423,11 @@ def quatro_solve(src, dst, corres, params=None):
     a, _, stride = _cloud_arg(src); b, _, _ = _cloud_arg(dst)
     corres = np.ascontiguousarray(corres, dtype=np.int32)
     T = np.zeros((4, 4)); valid = C.c_int(); clique = np.zeros(max(len(corres), 1), np.int32); nq = C.c_uint32()
-    scale = C.c_double(1.0)
-    st = lib().qn_quatro_solve_scaled(_p(a), _p(b), C.c_uint32(stride), _p(corres), C.c_uint32(len(corres)), C.byref(p), _p(T), C.byref(valid), _p(clique), C.byref(nq), C.byref(scale))
+    scale = C.c_double(1.0); it = C.c_int32()
+    st = lib().qn_quatro_solve_iter(_p(a), _p(b), C.c_uint32(stride), _p(corres), C.c_uint32(len(corres)), C.byref(p), _p(T), C.byref(valid), _p(clique), C.byref(nq), C.byref(scale), C.byref(it))
     if st != QN_OK:
         raise EngineError(st, lib().qn_status_str(st).decode())
-    return dict(T=T, valid=bool(valid.value), clique=clique[:nq.value].copy(), scale=scale.value)
+    return dict(T=T, valid=bool(valid.value), clique=clique[:nq.value].copy(), scale=scale.value, rot_iterations=it.value)
 
 
 def coarse_to_fine_alignment(ctx, src, dst, *, quatro=None, k=15, max_iter=32, max_corr_dist=52.5, trans_eps=0.01, score_thr=1.5):

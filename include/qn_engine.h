@@ -201,7 +201,9 @@ int  qn_multi_align_best(qn_multi*, const qn_pair_desc* pairs, uint32_t n_pairs,
 typedef struct {
   double  fpfh_normal_radius;      /* loop_closure.cpp:18 */
   double  fpfh_radius;             /* :19 */
-  double  noise_bound;             /* :20 */
+  double  noise_bound;             /* :20  >= 0.  0 = no measurement may deviate: the consistency graph keeps only TIMs of exactly equal length, the rotation's GNC
+                                      takes TEASER++'s fallback bound (0.1^2), and each translation axis is the limit of the TLS estimate for a bound going to 0 -
+                                      the residual value the most clique members share exactly, the smallest one on a tie (never the NaN the 1 / 0 weights would give) */
   double  rot_gnc_factor;          /* :21 */
   double  rot_cost_diff_thr;       /* :22 */
   int32_t rot_max_iter;            /* :23 */
@@ -216,7 +218,9 @@ typedef struct {
 } qn_quatro_params;
 
 void qn_quatro_default_params(qn_quatro_params* p);                  /* the reference's effective values */
-int  qn_quatro_set_params(qn_ctx*, const qn_quatro_params*);         /* quatro<PointType> ctor, loop_closure.cpp:18-27 */
+/* quatro<PointType> ctor, loop_closure.cpp:18-27.  QN_ERR_INVALID_ARG, and the context keeps its previous parameters, unless both radii are > 0 (not NaN),
+ * noise_bound >= 0, rot_max_iter >= 1, max_num_corres >= 3 and tuple_scale > 0 */
+int  qn_quatro_set_params(qn_ctx*, const qn_quatro_params*);
 /* quatro<PointType>::align(src, dst, is_converged), loop_closure.cpp:144: T = 4x4 f64 row-major, *valid = is_converged */
 int  qn_quatro_align(qn_ctx*, const float* src, uint32_t ns, const float* dst, uint32_t nt, uint32_t stride_bytes, double T[16], int* valid);
 int  qn_quatro_align_device(qn_ctx*, const float* d_src, uint32_t ns, const float* d_dst, uint32_t nt, uint32_t stride_bytes, double T[16], int* valid);
@@ -262,6 +266,9 @@ int  qn_quatro_solve(const float* src, const float* dst, uint32_t stride_bytes, 
 int  qn_quatro_get_scale(qn_ctx*, double* scale);
 int  qn_quatro_solve_scaled(const float* src, const float* dst, uint32_t stride_bytes, const int32_t* corres_pairs, uint32_t n_corres,
                             const qn_quatro_params* p, double T[16], int* valid, int32_t* clique, uint32_t* n_clique, double* scale);
+/* the same, plus the number of GNC iterations the rotation stage ran (0 when no clique of two or more was found) */
+int  qn_quatro_solve_iter(const float* src, const float* dst, uint32_t stride_bytes, const int32_t* corres_pairs, uint32_t n_corres,
+                          const qn_quatro_params* p, double T[16], int* valid, int32_t* clique, uint32_t* n_clique, double* scale, int32_t* rot_iterations);
 
 /* ---- feeder of the path, kept on the device -------------------------------
  * Keyframe clouds (PosePcd::pcd_, sensor frame, include/pose_pcd.hpp:7-19) are uploaded once and stay resident;

@@ -158,7 +158,8 @@ class QuatroParams:
                  max_num_corres=200, rng_seed=1, tuple_scale=0.95):
         self.dp = np.array([fpfh_normal_radius, fpfh_radius, noise_bound, rot_gnc_factor, rot_cost_diff_thr,
                             distance_threshold, tuple_scale], dtype=np.float64)
-        self.ip = np.array([rot_max_iter, int(estimate_scale), int(use_optimized_matching), max_num_corres, rng_seed], dtype=np.int32)
+        # (the seed is a uint32 on the C side: its bit pattern travels in the int32 slot)
+        self.ip = np.array([rot_max_iter, int(estimate_scale), int(use_optimized_matching), max_num_corres, int(rng_seed) & 0xFFFFFFFF], dtype=np.int64).astype(np.int32)
         self.fpfh_normal_radius, self.fpfh_radius = fpfh_normal_radius, fpfh_radius
 
 

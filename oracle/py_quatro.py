@@ -244,6 +244,9 @@ def max_clique_lex(adj):
 def _tls_1d(X, alpha):
     """TEASER++ scalar TLS: over the consensus sets swept by the sorted interval ends, minimise
     sum_in (x - mean_in)^2 + alpha * #out; first minimum in sweep order."""
+    if not alpha > 0:      # noise_bound = 0: the limit for a bound going to 0 - the value most measurements share exactly, the smallest on a tie (as the C++ solvers)
+        x = np.asarray(X, np.float64); vals, counts = np.unique(x[~np.isnan(x)], return_counts=True)
+        return float(vals[np.argmax(counts)]) if len(vals) else 0.0
     N = len(X)
     # ties: an interval that starts at a value enters before one that ends there leaves
     ev = sorted([(X[i] - alpha, 0, i) for i in range(N)] + [(X[i] + alpha, 1, i) for i in range(N)], key=lambda e: (e[0], e[1]))

@@ -280,6 +280,18 @@ std::vector<int> max_clique_lex(const std::vector<uint8_t>& adj, int n) {
 
 // ------------------------------------------------------------------ TEASER++ solve with Quatro rotation
 static double tls_estimate(const std::vector<double>& X, double alpha) {
+  if (!(alpha > 0)) {      // noise_bound = 0: the limit of the estimate for a bound going to 0 - the value most measurements share exactly, the smallest on a tie
+    std::vector<double> v;
+    for (double x : X) if (x == x) v.push_back(x);
+    std::sort(v.begin(), v.end());
+    double best = 0; int best_run = 0;
+    for (size_t i = 0; i < v.size();) {
+      size_t j = i; while (j < v.size() && v[j] == v[i]) j++;
+      if ((int)(j - i) > best_run) { best_run = (int)(j - i); best = v[i]; }
+      i = j;
+    }
+    return best;
+  }
   const int N = (int)X.size();
   struct H { double v; int tag; };
   std::vector<H> h; h.reserve(2 * N);

@@ -148,3 +148,74 @@ def test_product_clique_search_matches_oracle_on_hard_graphs(oracle, n, inlier_f
     b = oracle.quatro_solve(src, dst, corres)
     assert a["valid"] == b["valid"] and a["clique"].tolist() == b["clique"].tolist()
     assert np.abs(a["T"] - b["T"]).max() < 1e-9
+
+
+# ---- solver parameters away from the reference's operating point (noise_bound 0.3, gnc factor 1.4, cost threshold 1e-4, 50 iterations): the PRODUCT's host
+# solver against the oracle on fixed correspondence sets - the golden fixtures' and one with half outliers.  Same valid, clique and GNC iteration count, T <= 1e-9.
+def _solver_sets():
+    import os
+    G = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+    out = {}
+    for name in ("quatro_a", "quatro_b"):
+        d = np.load(os.path.join(G, name + ".npz"))
+        out[name] = (d["src"], d["tgt"], d["corres"])
+    rng = np.random.default_rng(4242)
+    n = 84
+    src = rng.uniform(-25, 25, size=(n, 3)).astype(np.float32); src[:, 2] = rng.uniform(0, 4, n)
+    T = yaw_T(1.1, [4.0, -3.0, 0.2])
+    dst = (src.astype(np.float64) @ T[:3, :3].T + T[:3, 3] + rng.normal(0, 0.03, (n, 3))).astype(np.float32)
+    bad = rng.choice(n, n // 2, replace=False); dst[bad] = rng.uniform(-25, 25, size=(len(bad), 3))
+    out["outliers50"] = (src, dst, np.c_[np.arange(n), np.arange(n)].astype(np.int32))
+    return out
+
+
+@pytest.mark.parametrize("noise_bound", [0.0, 0.05, 1.0])
+@pytest.mark.parametrize("which", ["quatro_a", "quatro_b", "outliers50"])
+def test_product_solver_parameter_sweep_matches_oracle(oracle, which, noise_bound):
+    from qn_amd import engine
+    src, dst, corres = _solver_sets()[which]
+    for gnc, cost_thr, max_iter in itertools.product([1.05, 4.0], [0.0, 1e-2], [1, 2, 200]):
+        ep = engine.quatro_default_params()
+        ep.noise_bound, ep.rot_gnc_factor, ep.rot_cost_diff_thr, ep.rot_max_iter = noise_bound, gnc, cost_thr, max_iter
+        a = engine.quatro_solve(src, dst, corres, ep)
+        b = oracle.quatro_solve(src, dst, corres, oracle.QuatroParams(noise_bound=noise_bound, rot_gnc_factor=gnc, rot_cost_diff_thr=cost_thr, rot_max_iter=max_iter))
+        case = (which, noise_bound, gnc, cost_thr, max_iter)
+        assert a["valid"] == b["valid"] and a["clique"].tolist() == b["clique"].tolist(), case
+        assert a["rot_iterations"] == b["rot_iterations"] and 0 <= a["rot_iterations"] <= max_iter, (case, a["rot_iterations"], b["rot_iterations"])
+        assert np.abs(a["T"] - b["T"]).max() <= 1e-9, case
+        assert np.isfinite(a["T"]).all() and np.isfinite(b["T"]).all(), case
+        if a["valid"]:
+            assert len(a["clique"]) >= 2 and a["rot_iterations"] >= 1, case
+    if which == "outliers50" and noise_bound == 0.05:                 # the sweep is not vacuous: the set registers
+        assert a["valid"] and len(a["clique"]) >= 30
+
+
+def test_zero_noise_bound_is_the_limit_of_the_tls_estimate(oracle):
+    """noise_bound = 0 (accepted by qn_quatro_set_params): the TLS translation's 1 / bound^2 weights are infinite, and both implementations used to return
+    t = 0 whatever the data, with valid = 1 as soon as two TIMs had exactly equal lengths.  Defined now (include/qn_engine.h): per axis, the value the most
+    clique members share exactly (the estimate's limit for a bound going to 0), the smallest on a tie.  Exactly representable points under an exact shift:
+    every TIM matches, the yaw is exactly 0, and the shift is recovered bit for bit - by the product and the oracle alike."""
+    from qn_amd import engine
+    g = np.stack(np.meshgrid(np.arange(6), np.arange(5), np.arange(3), indexing="ij"), -1).reshape(-1, 3).astype(np.float64)
+    src = (g * [1.25, 0.75, 0.5] + [3.5, -8.25, 0.125]).astype(np.float32)
+    shift = np.array([7.25, -2.5, 0.375])
+    dst = (src.astype(np.float64) + shift).astype(np.float32)
+    n = len(src)
+    rng = np.random.default_rng(9)
+    out = rng.choice(n, 12, replace=False); dst[out] += rng.uniform(-5, 5, size=(12, 3)).astype(np.float32)      # outliers: their TIMs do not match exactly
+    corres = np.c_[np.arange(n), np.arange(n)].astype(np.int32)
+    ep = engine.quatro_default_params(); ep.noise_bound = 0.0
+    a = engine.quatro_solve(src, dst, corres, ep)
+    b = oracle.quatro_solve(src, dst, corres, oracle.QuatroParams(noise_bound=0.0))
+    assert a["valid"] and b["valid"] and a["clique"].tolist() == b["clique"].tolist() == sorted(set(range(n)) - set(out.tolist()))
+    assert a["rot_iterations"] == b["rot_iterations"]
+    assert np.array_equal(a["T"], b["T"])
+    expect = np.eye(4); expect[:3, 3] = shift
+    assert np.array_equal(a["T"], expect), a["T"]
+    from oracle import py_quatro as pq                                                   # and the numpy restatement
+    c = pq.solve(src, dst, corres, pq.Params(noise_bound=0.0))
+    assert c["valid"] and list(c["clique"]) == a["clique"].tolist() and np.array_equal(c["T"], expect)
+    # no exactly matching TIM at all: no clique of two, not a registration (and the identity, finite)
+    dst2 = dst.copy(); dst2 += rng.normal(0, 1e-3, dst2.shape).astype(np.float32)
+    a = engine.quatro_solve(src, dst2, corres, ep); b = oracle.quatro_solve(src, dst2, corres, oracle.QuatroParams(noise_bound=0.0))
+    assert a["valid"] == b["valid"] and a["clique"].tolist() == b["clique"].tolist() and np.array_equal(a["T"], b["T"]) and np.isfinite(a["T"]).all()
