@@ -240,7 +240,7 @@ extern "C" int qn_ctx_synchronize(qn_ctx* c) {
 extern "C" int qn_gicp_set_params(qn_ctx* c, const qn_gicp_params* p) {
   if (!c || !p) return QN_ERR_INVALID_ARG;
   if (p->k_correspondences < 1 || p->k_correspondences > 32 || p->max_iterations < 0 || p->lm_max_iterations < 1 ||
-      (p->optimizer != QN_OPT_LM && p->optimizer != QN_OPT_GN) || !(p->max_corr_dist > 0)) return QN_ERR_INVALID_ARG;
+      (p->optimizer != QN_OPT_LM && p->optimizer != QN_OPT_GN) || !(p->max_corr_dist > 0) || !(p->lm_init_lambda_factor >= 0)) return QN_ERR_INVALID_ARG;
   if (p->k_correspondences != c->params.k_correspondences) { c->cloud[0].has_cov = c->cloud[1].has_cov = false; }
   c->params = *p;
   return QN_OK;

@@ -1138,7 +1138,10 @@ __device__ inline bool d_is_converged(const double delta[16], const GicpConfig& 
   double mr = 0, mt = 0;
   for (int a = 0; a < 3; a++) { for (int b = 0; b < 3; b++) mr = fmax(mr, fabs(delta[4 * a + b] - (a == b ? 1.0 : 0.0))); mt = fmax(mt, fabs(delta[4 * a + 3])); }
   if (mr_out) { *mr_out = mr; *mt_out = mt; }
-  return fmax(mr / cfg.rotation_epsilon, mt / cfg.transformation_epsilon) < 1.0;
+  // std::max(a, b) as the reference writes it, (a < b) ? b : a - NOT fmax: a NaN ratio of the rotation (rotation_epsilon NaN, or 0 with an exact-identity
+  // rotation step) must never converge, while fmax would drop it and stop on the translation alone
+  const double qr = mr / cfg.rotation_epsilon, qt = mt / cfg.transformation_epsilon;
+  return (qr < qt ? qt : qr) < 1.0;
 }
 
 __device__ __forceinline__ void d_propose(GicpState* st, double lambda, SolveWork* A) {      // d = LDLT(H + lambda I).solve(-b); delta; xi = delta * x0

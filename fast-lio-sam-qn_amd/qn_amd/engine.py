@@ -196,6 +196,12 @@ class NanoGICP:
     def setRotationEpsilon(self, e):
         self.p.rotation_epsilon = e; self._push()
 
+    def setLMMaxIterations(self, n):                 # LM trial steps per outer iteration before "lm not converged!!" (>= 1; default 10)
+        self.p.lm_max_iterations = n; self._push()
+
+    def setLMInitLambdaFactor(self, f):              # lambda = f * max |diag H| at the first linearisation (default 1e-9)
+        self.p.lm_init_lambda_factor = f; self._push()
+
     def setOptimizer(self, name):
         self.p.optimizer = 0 if name == "lm" else 1; self._push()
 

@@ -105,7 +105,13 @@ int  qn_ctx_synchronize(qn_ctx* ctx);
 
 /* ---- Nano-GICP ------------------------------------------------------------------------ */
 void qn_gicp_default_params(qn_gicp_params* p);                       /* NanoGICP()/LsqRegistration() ctor defaults */
-int  qn_gicp_set_params(qn_ctx*, const qn_gicp_params*);              /* loop_closure.cpp:9-16  */
+/* loop_closure.cpp:9-16.  QN_ERR_INVALID_ARG, and the context keeps its previous parameters, unless 1 <= k_correspondences <= 32, max_iterations >= 0,
+ * lm_max_iterations >= 1, max_corr_dist > 0 and lm_init_lambda_factor >= 0 (a negative factor makes H + lambda I indefinite: no defined step).
+ * Both epsilons are taken as they are, NaN and 0 included, with the reference's stopping rule max(mr / rotation_epsilon, mt / transformation_epsilon) < 1
+ * and std::max's (a < b) ? b : a: a NaN rotation ratio (epsilon NaN, or 0 with an exact-identity rotation step) never converges, a NaN translation
+ * ratio leaves the decision to the rotation's, and an epsilon of 0 never converges on a non-zero step.  max_iterations = 0: T = the guess, iterations 0,
+ * not converged, H = identity, fitness at the guess. */
+int  qn_gicp_set_params(qn_ctx*, const qn_gicp_params*);
 int  qn_gicp_get_params(const qn_ctx*, qn_gicp_params* out);          /* what the setters above last stored (the getters of pcl::Registration / NanoGICP) */
 /* setInputSource / setInputTarget do not wait for the GPU: upload, packing and the grid build (its numbers are derived from the bounding box ON the
  * device) are enqueued and the call returns.  Consequences at this boundary: (1) a cloud with non-finite coordinates is refused by the first call that

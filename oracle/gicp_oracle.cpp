@@ -281,7 +281,7 @@ bool NanoGicpOracle::step_lm(double x0[16], double delta[16], IterTrace& tr) {
 // LsqRegistration::computeTransformation behind pcl::Registration::align (A.1.6)
 void NanoGicpOracle::align(const double guess[16], GicpResult* out) {
   double x0[16]; std::memcpy(x0, guess, sizeof(x0));
-  lm_lambda_ = -1.0; bool converged = false; int iters = 0;
+  lm_lambda_ = -1.0; bool converged = false, failed = false; int iters = 0;
   for (int i = 0; i < 36; i++) final_H_[i] = (i % 7 == 0) ? 1.0 : 0.0;
   out->trace.clear();
   const int maxit = params.force_iterations > 0 ? params.force_iterations : params.max_iterations;
@@ -289,7 +289,7 @@ void NanoGicpOracle::align(const double guess[16], GicpResult* out) {
     iters = i + 1;
     double delta[16]; IterTrace tr{};
     bool ok = (params.optimizer == 0) ? step_lm(x0, delta, tr) : step_gn(x0, delta, tr);
-    if (!ok) { out->trace.push_back(tr); break; }            // "lm not converged!!"
+    if (!ok) { out->trace.push_back(tr); failed = true; break; }            // "lm not converged!!"
     converged = is_converged(delta, &tr);
     if (params.force_iterations > 0) converged = false;
     out->trace.push_back(tr);
@@ -297,7 +297,7 @@ void NanoGicpOracle::align(const double guess[16], GicpResult* out) {
   std::memcpy(out->T, x0, sizeof(x0));
   for (int i = 0; i < 16; i++) out->Tf[i] = (float)x0[i];
   std::memcpy(out->H, final_H_, sizeof(final_H_));
-  out->iterations = iters; out->converged = converged ? 1 : 0;
+  out->iterations = iters; out->converged = converged ? 1 : 0; out->lm_failed = failed ? 1 : 0;
   out->fitness = getFitnessScore(out->Tf, DBL_MAX);
 }
 

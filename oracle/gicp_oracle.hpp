@@ -52,6 +52,7 @@ struct GicpResult {
   double H[36];            // final_hessian_
   int iterations;          // outer iterations executed
   int converged;
+  int lm_failed;           // the LM inner loop ran out of tries ("lm not converged!!"): the outer loop broke there
   double fitness;          // pcl getFitnessScore(): mean squared NN distance over ALL source points
   std::vector<IterTrace> trace;
 };

@@ -103,12 +103,12 @@ class GicpOracle:
 
     def align(self, guess=None):
         guess = np.eye(4) if guess is None else _f64(guess)
-        od = np.zeros(53); of = np.zeros(16, dtype=np.float32); oi = np.zeros(3, dtype=np.int32)
+        od = np.zeros(53); of = np.zeros(16, dtype=np.float32); oi = np.zeros(4, dtype=np.int32)
         cap = max(self.max_iter, 512)
         tr = np.zeros((cap, 7))
         self._l.orc_gicp_align(self._h, _p(guess), _p(od), _p(of), _p(oi), _p(tr), C.c_int(cap))
         return dict(T=od[:16].reshape(4, 4).copy(), H=od[16:52].reshape(6, 6).copy(), fitness=float(od[52]),
-                    Tf=of.reshape(4, 4).copy(), iterations=int(oi[0]), converged=bool(oi[1]),
+                    Tf=of.reshape(4, 4).copy(), iterations=int(oi[0]), converged=bool(oi[1]), lm_failed=bool(oi[3]),
                     trace=tr[:oi[2]].copy())
 
     def fitness(self, Tf, max_range=1.7976931348623157e308):

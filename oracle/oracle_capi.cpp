@@ -50,7 +50,7 @@ void orc_gicp_align(void* h, const double* guess, double* out_d, float* out_f, i
   GicpResult r; ((NanoGicpOracle*)h)->align(guess, &r);
   std::memcpy(out_d, r.T, 16 * sizeof(double)); std::memcpy(out_d + 16, r.H, 36 * sizeof(double)); out_d[52] = r.fitness;
   std::memcpy(out_f, r.Tf, 16 * sizeof(float));
-  out_i[0] = r.iterations; out_i[1] = r.converged; out_i[2] = (int)r.trace.size();
+  out_i[0] = r.iterations; out_i[1] = r.converged; out_i[2] = (int)r.trace.size(); out_i[3] = r.lm_failed;
   for (int i = 0; i < (int)r.trace.size() && i < trace_cap; i++) {
     const auto& t = r.trace[i]; double* o = trace + 7 * i;
     o[0] = t.y0; o[1] = t.lambda; o[2] = t.rho; o[3] = t.max_dR; o[4] = t.max_dt; o[5] = t.inner; o[6] = t.accepted;

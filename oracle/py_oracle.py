@@ -88,17 +88,24 @@ class PyGicp:
         v = self.valid
         return float(np.einsum("ni,nij,nj->", e[v], self.M[v], e[v]))
 
-    def is_converged(self, d):
-        return max(np.abs(d[:3, :3] - np.eye(3)).max() / self.rot_eps, np.abs(d[:3, 3]).max() / self.trans_eps) < 1
+    def is_converged(self, d, row=None):
+        mr, mt = np.abs(d[:3, :3] - np.eye(3)).max(), np.abs(d[:3, 3]).max()
+        if row is not None:
+            row[3], row[4] = mr, mt
+        with np.errstate(divide="ignore", invalid="ignore"):
+            # Python's max(a, b) keeps a unless b > a, as std::max does: a NaN rotation ratio never converges, a NaN translation ratio defers to the rotation's
+            return max(np.float64(mr) / self.rot_eps, np.float64(mt) / self.trans_eps) < 1
 
     def align(self, guess=None):
+        """-> dict(T, Tf, iterations, converged, lm_failed, fitness, trace): trace rows (y0, lambda, rho, max_dR, max_dt, inner, accepted), one per outer iteration"""
         x0 = np.eye(4) if guess is None else guess.astype(np.float64).copy()
-        lam = -1.0; converged = False; iters = 0
+        lam = -1.0; converged = False; failed = False; iters = 0; trace = []
         for i in range(self.max_iter):
             if converged:
                 break
             iters = i + 1
             H, b, y0 = self.linearize(x0)
+            row = [y0, 0.0, 0.0, 0.0, 0.0, 1, 1]
             ok = False
             if self.optimizer == "gn":
                 d = np.linalg.solve(H, -b)
@@ -108,22 +115,26 @@ class PyGicp:
                 if lam < 0:
                     lam = self.lm_f * np.abs(np.diag(H)).max()
                 nu = 2.0
-                for _ in range(self.lm_max_iter):
+                for it in range(self.lm_max_iter):
                     d = np.linalg.solve(H + lam * np.eye(6), -b)
                     delta = np.eye(4); delta[:3, :3] = so3_exp(d[:3]); delta[:3, 3] = d[3:]
                     xi = delta @ x0
                     yi = self.compute_error(xi)
-                    rho = (y0 - yi) / (d @ (lam * d - b))
+                    with np.errstate(divide="ignore", invalid="ignore"):
+                        rho = np.float64(y0 - yi) / (d @ (lam * d - b))
+                    row[1], row[2], row[5], row[6] = lam, rho, it + 1, 0
                     if rho < 0:
                         if self.is_converged(delta):
                             ok = True; break
                         lam *= nu; nu *= 2; continue
-                    x0 = xi; lam *= max(1.0 / 3.0, 1 - (2 * rho - 1) ** 3); ok = True
+                    x0 = xi; lam *= max(1.0 / 3.0, 1 - (2 * rho - 1) ** 3); ok = True; row[6] = 1
                     break
             if not ok:
+                trace.append(row); failed = True
                 break
-            converged = self.is_converged(delta)
+            converged = self.is_converged(delta, row)
+            trace.append(row)
         Tf = x0.astype(np.float32)
         q = Tf[:3, 0] * self.src[:, :1] + (Tf[:3, 1] * self.src[:, 1:2] + (Tf[:3, 2] * self.src[:, 2:3] + Tf[:3, 3]))
         d, _ = self.tree.query(q.astype(np.float64), k=1)
-        return dict(T=x0, Tf=Tf, iterations=iters, converged=converged, fitness=float(np.mean((d * d).astype(np.float32).astype(np.float64))))
+        return dict(T=x0, Tf=Tf, iterations=iters, converged=converged, lm_failed=failed, trace=np.array(trace, dtype=np.float64).reshape(-1, 7), fitness=float(np.mean((d * d).astype(np.float32).astype(np.float64))))
