@@ -404,6 +404,7 @@ struct qn_kf_store {
   qn::BBoxOut* bt_bbox_host = nullptr; size_t bt_bbox_host_cap = 0; uint32_t* bt_res_host = nullptr; size_t bt_res_host_cap = 0;
   // scratch of other translation units (the ray-caster, qn_sim.hip): see qn_kf_internal.h
   void* int_scratch[QN_KF_INT_SCRATCH] = {}; size_t int_scratch_cap[QN_KF_INT_SCRATCH] = {}; void* int_pinned = nullptr; size_t int_pinned_cap = 0;
+  void* ext[QN_KF_INT_EXT] = {}; qn_kf_int_release_fn ext_release[QN_KF_INT_EXT] = {};      // state of other translation units (qn_sc.hip)
   std::string last_error;
 };
 #define KFCHK(s, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { (s)->last_error = std::string(#call) + " -> " + hipGetErrorString(e_); return QN_ERR_HIP; } } while (0)
@@ -428,6 +429,7 @@ extern "C" void qn_kf_store_destroy(qn_kf_store* s) {
   (void)hipFree(s->hist); (void)hipFree(s->hist_sums); (void)hipFree(s->out[0]); (void)hipFree(s->out[1]); (void)hipFree(s->poses); (void)hipFree(s->bbox); (void)hipFree(s->staging);
   (void)hipFree(s->map); (void)hipFree(s->map_kfs); (void)hipFree(s->map_blk); (void)hipFree(s->map_part);
   (void)hipFree(s->bt_out); (void)hipFree(s->bt_ends); (void)hipFree(s->bt_kf_seg); (void)hipFree(s->bt_tile_off); (void)hipFree(s->bt_segs); (void)hipFree(s->bt_bbox); (void)hipFree(s->bt_res);
+  for (int k = 0; k < QN_KF_INT_EXT; k++) if (s->ext[k] && s->ext_release[k]) s->ext_release[k](s->ext[k]);
   for (void* p : s->int_scratch) (void)hipFree(p);
   if (s->int_pinned) (void)hipHostFree(s->int_pinned);
   if (s->bt_bbox_host) (void)hipHostFree(s->bt_bbox_host); if (s->bt_res_host) (void)hipHostFree(s->bt_res_host);
@@ -500,6 +502,13 @@ void* qn_kf_int_scratch(qn_kf_store* s, int which, size_t bytes) {
     s->int_scratch_cap[which] = bytes;
   }
   return s->int_scratch[which];
+}
+const float4* qn_kf_int_keyframe(const qn_kf_store* s, int32_t id, uint32_t* n) { *n = s->sizes[id]; return s->clouds[id]; }
+void* qn_kf_int_ext(const qn_kf_store* s, int which) { return which >= 0 && which < QN_KF_INT_EXT ? s->ext[which] : nullptr; }
+void qn_kf_int_set_ext(qn_kf_store* s, int which, void* p, qn_kf_int_release_fn release) {
+  if (which < 0 || which >= QN_KF_INT_EXT) return;
+  if (s->ext[which] && s->ext_release[which] && s->ext[which] != p) s->ext_release[which](s->ext[which]);
+  s->ext[which] = p; s->ext_release[which] = release;
 }
 void* qn_kf_int_pinned(qn_kf_store* s, size_t bytes) {
   if (bytes > s->int_pinned_cap) {

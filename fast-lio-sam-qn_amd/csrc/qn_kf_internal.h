@@ -1,5 +1,6 @@
 // qn_kf_internal.h - what another translation unit may do with a qn_kf_store (its struct lives in qn_cloud.hip).
-// Used by the ray-caster (qn_sim.hip), which writes keyframes straight into the store without host staging.
+// Used by the ray-caster (qn_sim.hip), which writes keyframes straight into the store without host staging, and by the Scan Context
+// descriptors (qn_sc.hip), which read the resident keyframes and keep per-store state.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -19,3 +20,12 @@ void* qn_kf_int_pinned(qn_kf_store* s, size_t bytes);                           
 int  qn_kf_int_copy_async(qn_kf_store* s, const void* d_pts, uint32_t n, uint32_t stride, int32_t ioff, float4** out);
 // append keyframes whose buffers were made by qn_kf_int_copy_async (after the stream has been synchronised); ids are consecutive.
 void qn_kf_int_append(qn_kf_store* s, float4* const* bufs, const uint32_t* n, uint32_t count, bool has_i, int32_t* ids_out);
+// the resident float4 records of keyframe `id` (0 <= id < qn_kf_int_count; not checked) and their number (nullptr when n == 0)
+const float4* qn_kf_int_keyframe(const qn_kf_store* s, int32_t id, uint32_t* n);
+// per-store state of another translation unit (slot QN_KF_INT_EXT_SC: qn_sc.hip's descriptors): nullptr until set; the store owns it from
+// qn_kf_int_set_ext on and calls `release` from qn_kf_store_destroy once its stream has drained.
+#define QN_KF_INT_EXT 2
+#define QN_KF_INT_EXT_SC 0
+typedef void (*qn_kf_int_release_fn)(void*);
+void* qn_kf_int_ext(const qn_kf_store* s, int which);
+void qn_kf_int_set_ext(qn_kf_store* s, int which, void* p, qn_kf_int_release_fn release);

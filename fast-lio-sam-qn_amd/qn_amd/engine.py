@@ -616,6 +616,15 @@ class SimSensor(C.Structure):
                 ("sin_az", C.c_void_p), ("min_range", C.c_double), ("max_range", C.c_double), ("sigma", C.c_double)]
 
 
+class ScParams(C.Structure):
+    """qn_sc_params: Scan Context descriptor shape and the ring-key prefilter (defaults = the original's, exhaustive search)"""
+    _fields_ = [("n_rings", C.c_uint32), ("n_sectors", C.c_uint32), ("max_radius", C.c_double), ("lidar_height", C.c_double),
+                ("ringkey_prefilter", C.c_uint32), ("pad_", C.c_uint32)]
+
+    def __init__(self, n_rings=20, n_sectors=60, max_radius=80.0, lidar_height=2.0, ringkey_prefilter=0):
+        super().__init__(n_rings, n_sectors, max_radius, lidar_height, ringkey_prefilter, 0)
+
+
 class KeyframeStore:
     """Device-resident keyframe clouds + LoopClosure::setSrcAndDstCloud on the GPU (loop_closure.cpp:58-108)."""
 
@@ -764,6 +773,42 @@ class KeyframeStore:
         out = self.assemble_batch(lists, [[poses[i] for i in l] for l in lists], leaf)
         (sp, ns, _), rest = out[0], out[1:]
         return [(sp, ns, dp, nt, 16, 1) for dp, nt, _ in rest], [o[2] for o in out]
+
+
+    # ---- Scan Context loop candidates (qn_kf_sc_*; numpy twin: qn_amd/scancontext.py)
+    def sc_set_params(self, params=None, **kw):
+        """qn_kf_sc_set_params: a ScParams, or its fields as keywords (the rest default).  A shape change discards every descriptor."""
+        p = params if params is not None else ScParams(**kw)
+        self._check(self._l.qn_kf_sc_set_params(self.h, C.byref(p)))
+
+    def sc_params(self):
+        p = ScParams()
+        self._check(self._l.qn_kf_sc_get_params(self.h, C.byref(p)))
+        return p
+
+    def sc_describe(self, ids):
+        """qn_kf_sc_describe: the descriptors of these keyframes, on the GPU from their resident records (already described ones are kept)"""
+        ids = np.ascontiguousarray(np.atleast_1d(ids), dtype=np.int32)
+        self._check(self._l.qn_kf_sc_describe(self.h, _p(ids) if len(ids) else None, C.c_uint32(len(ids))))
+
+    def sc_descriptor(self, kid):
+        """-> (desc (n_rings, n_sectors) f32, ring key (n_rings,) f64, column norms (n_sectors,) f64) of a described keyframe"""
+        p = self.sc_params()
+        d = np.zeros((p.n_rings, p.n_sectors), np.float32); rk = np.zeros(p.n_rings); cn = np.zeros(p.n_sectors)
+        self._check(self._l.qn_kf_sc_get(self.h, C.c_int32(kid), _p(d), _p(rk), _p(cn)))
+        return d, rk, cn
+
+    def sc_query(self, query_ids, stamps, tdiff, top_k=10):
+        """qn_kf_sc_query: for each query id, the top_k described keyframes older than it by more than tdiff (stamps[q] - stamps[c] > tdiff)
+        nearest by Scan Context distance -> list (one per query) of (ids int32, D f64, shift int32) arrays, ascending D, ties to the lower id.
+        scancontext.yaw_of_shift(shift, n_sectors) is the candidate's heading minus the query's."""
+        q = np.ascontiguousarray(np.atleast_1d(query_ids), dtype=np.int32)
+        st = np.ascontiguousarray(stamps, dtype=np.float64)
+        nq, k = len(q), int(top_k)
+        ids = np.zeros(max(nq * k, 1), np.int32); D = np.zeros(max(nq * k, 1)); sh = np.zeros(max(nq * k, 1), np.int32); n = np.zeros(max(nq, 1), np.uint32)
+        self._check(self._l.qn_kf_sc_query(self.h, _p(q) if nq else None, C.c_uint32(nq), _p(st), C.c_uint32(len(st)), C.c_double(tdiff), C.c_uint32(k),
+                                           _p(ids), _p(D), _p(sh), _p(n)))
+        return [(ids[r * k:r * k + n[r]].copy(), D[r * k:r * k + n[r]].copy(), sh[r * k:r * k + n[r]].copy()) for r in range(nq)]
 
 
 def loop_candidates(pos, stamps, query, radius, tdiff, max_k=64):

@@ -365,6 +365,62 @@ typedef struct {
 int  qn_sim_lidar_to_store(qn_kf_store*, const qn_sim_prim* prims, uint32_t n_prims, const qn_sim_sensor* sensor, const double* poses16,
                            const uint32_t* seeds, uint32_t n_scans, int32_t* ids_out, uint32_t* n_out);
 
+/* ---- loop candidates by Scan Context on the resident keyframes (csrc/qn_sc.hip; numpy twin: qn_amd/scancontext.py) ------------
+ * LoopClosure::fetchClosestKeyframeIdx (loop_closure.cpp:34-56, qn_loop_candidates) keeps keyframes within loop_detection_radius of the
+ * query's drifted, corrected position; these calls produce the candidate list from a place descriptor instead (Scan Context, Kim & Kim 2018,
+ * as in the reference's sibling projects SC-A-LOAM / FAST_LIO_SLAM), independent of the pose estimate.  Opt-in: nothing else uses them.
+ * Descriptor of keyframe id: Nr x Ns (n_rings x n_sectors) f32, row-major by ring, from its resident float4 records in the SENSOR frame
+ * (PosePcd::pcd_, include/pose_pcd.hpp:7-19), no pose applied.  A point is dropped when x, y or z is not finite, x == y == 0, or
+ * r2 = x*x + y*y >= max_radius^2 (f64 from the f32 inputs).  Ring i holds r in [i R / Nr, (i + 1) R / Nr): ring = #{i in 1..Nr-1 : r2 >=
+ * (i R / Nr)^2}, edges squared in f64 on the host.  Sector j holds the azimuth [2 pi j / Ns, 2 pi (j + 1) / Ns), counter-clockwise from +x
+ * in [0, 2 pi): sector = #{j in 1..Ns-1 : p at or past b_j}, b_j = (cos, sin)(2 pi j / Ns) from the C library on the host; "at or past"
+ * = p in the lower half plane [pi, 2 pi) and b_j in the upper, or both in the same half and b_j.x * y - b_j.y * x >= 0 (f64, no fused
+ * multiply-add): no transcendental on the device, and a point exactly on an edge goes to the upper bin.  A bin's value is the max over its
+ * points of (float)((double)z + lidar_height); a bin with no point is 0 (the original's NO_POINT).
+ * Ring key rk[i] = (sum over j in order of d[i][j]) / Ns; column sums of squares ss[j] = sum over i in order of d[i][j]^2; column norm
+ * cn[j] = sqrt(ss[j]) (all f64).  Distance of query q to candidate c: for each shift s in [0, Ns), over the columns j in order whose ss_q[j]
+ * and ss_c[k] (k = (j + s) mod Ns) are both non-zero, D_s = mean of 1 - (sum over i in order of q[i][j] c[i][k]) / sqrt(ss_q[j] ss_c[k]),
+ * D_s = 1 when there is no such column; D = min over s, shift = the lowest s reaching it.  (sqrt of the product rather than the product of
+ * the norms: a scan against itself, or turned by whole sectors, is at exactly 0.)  Candidate column j + shift matches query column j: the
+ * candidate's heading minus the query's is -shift * 2 pi / Ns.  f64 throughout with IEEE division and the correctly rounded sqrt, in the
+ * stated orders, so the engine equals the twin bit for bit.
+ * qn_kf_sc_set_params: QN_ERR_INVALID_ARG, previous parameters kept, unless 1 <= n_rings <= QN_SC_MAX_RINGS, 1 <= n_sectors <=
+ *   QN_SC_MAX_SECTORS, n_rings * n_sectors <= QN_SC_MAX_BINS, 0 < max_radius <= 1e6, |lidar_height| <= 1e4 (finite; every bin value is
+ *   then finite) and ringkey_prefilter <= QN_SC_MAX_PREFILTER.  Changing n_rings, n_sectors, max_radius or lidar_height discards every
+ *   descriptor; the prefilter alone does not.  A store starts with n_rings 20, n_sectors 60, max_radius 80, lidar_height 2, no prefilter (qn_kf_sc_get_params).
+ * qn_kf_sc_describe: computes the descriptors of `ids` (repeats allowed; an id already described under the current parameters is left as it
+ *   is - describing again gives the same bits).  A bad id or count == 0: QN_ERR_INVALID_ARG, nothing described.  One synchronisation (plus
+ *   one when the descriptor storage grows).
+ * qn_kf_sc_get: desc (Nr x Ns), ringkey (Nr), colnorm (Ns); NULL outputs are skipped.  QN_ERR_NOT_READY when id is not described.
+ * qn_kf_sc_query: for each of the nq queries, the candidates c with c != q, stamps[q] - stamps[c] > tdiff (the strict time test of
+ *   loop_closure.cpp:45) and c described - an undescribed keyframe is not a candidate.  With ringkey_prefilter = P > 0 only the P of them with
+ *   the smallest sum over i in order of (rk_q[i] - rk_c[i])^2 (ties: the lower id) get the full distance (the original's KD-tree search,
+ *   made exact).  Row k of the outputs (top_k entries from k * top_k) holds the n_out[k] <= top_k candidates with the smallest D, ties to
+ *   the lower id: ids_out, dist_out = D, shift_out = shift; entries past n_out[k] are -1, NaN, -1.  QN_ERR_INVALID_ARG before anything runs,
+ *   store unchanged: a null pointer, nq == 0, a query id outside the store, n_stamps < the number of keyframes, NaN tdiff, top_k == 0 or
+ *   > QN_SC_MAX_TOP_K, nq * top_k > QN_SC_MAX_RESULTS.  QN_ERR_NOT_READY when a query is not described.  Queries run in chunks whose device
+ *   scratch stays under 256 MB; one host synchronisation per call, whatever nq is.                                                 */
+#define QN_SC_MAX_RINGS 64u
+#define QN_SC_MAX_SECTORS 360u
+#define QN_SC_MAX_BINS 8192u                       /* n_rings x n_sectors                              */
+#define QN_SC_MAX_PREFILTER 1024u
+#define QN_SC_MAX_TOP_K 1024u
+#define QN_SC_MAX_RESULTS (1u << 26)               /* nq x top_k per call                               */
+typedef struct {
+  uint32_t n_rings;                                /* PC_NUM_RING, default 20                           */
+  uint32_t n_sectors;                              /* PC_NUM_SECTOR, default 60                         */
+  double max_radius;                               /* PC_MAX_RADIUS [m], default 80                     */
+  double lidar_height;                             /* LIDAR_HEIGHT [m], added to z, default 2           */
+  uint32_t ringkey_prefilter;                      /* 0 = exhaustive (default); P = only the P nearest by ring key */
+  uint32_t pad_;
+} qn_sc_params;
+int  qn_kf_sc_set_params(qn_kf_store*, const qn_sc_params* p);
+int  qn_kf_sc_get_params(qn_kf_store*, qn_sc_params* p);
+int  qn_kf_sc_describe(qn_kf_store*, const int32_t* ids, uint32_t count);
+int  qn_kf_sc_get(qn_kf_store*, int32_t id, float* desc /* Nr x Ns */, double* ringkey /* Nr */, double* colnorm /* Ns */);
+int  qn_kf_sc_query(qn_kf_store*, const int32_t* query_ids, uint32_t nq, const double* stamps, uint32_t n_stamps, double tdiff, uint32_t top_k,
+                    int32_t* ids_out, double* dist_out, int32_t* shift_out, uint32_t* n_out);
+
 /* ---- per-stage read-backs used by the parity tests (not needed by the shims) ------------ */
 int  qn_gicp_get_covariances(qn_ctx*, int which, double* cov9_out);   /* n x 9 f64, original point order */
 int  qn_gicp_knn(qn_ctx*, int which, int k, int32_t* idx_out, float* d2_out);   /* self k-NN of a cloud, n x k */

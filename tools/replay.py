@@ -210,13 +210,18 @@ def ate(poses, gt):
 
 
 def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, submap_range=5, score_thr=1.5, verbose=True, backend="gpu", save_dir=None,
-        save_map_leaf=None, sensor="uniform"):
+        save_map_leaf=None, sensor="uniform", detector="radius", sc_max_dist=0.3, yaw_bias=0.006):
     """sensor = "uniform": keyframe clouds sampled uniformly by area inside a disc (make_stream); "spinning": ray-cast spinning-LiDAR
-    scans from the ground-truth poses of the same figure-8 (make_lidar_stream)."""
+    scans from the ground-truth poses of the same figure-8 (make_lidar_stream).  detector = "radius": the candidate is the closest older
+    keyframe within `radius` of the corrected position (LC:34-56); "scancontext": the older keyframe nearest by Scan Context distance, kept
+    when that is below sc_max_dist - on the GPU from the resident keyframes (KeyframeStore.sc_describe / sc_query), for the oracle backend by
+    the numpy twin qn_amd.scancontext.  yaw_bias: the odometry's heading drift per keyframe [rad]."""
+    if detector not in ("radius", "scancontext"):
+        raise ValueError("detector must be 'radius' or 'scancontext', not %r" % (detector,))
     if sensor == "uniform":
-        scans, gt, odom, stamps = make_stream(n_kf, seed)
+        scans, gt, odom, stamps = make_stream(n_kf, seed, yaw_bias=yaw_bias)
     elif sensor == "spinning":
-        prims, lidar, seeds, gt, odom, stamps = make_lidar_stream(n_kf, seed)
+        prims, lidar, seeds, gt, odom, stamps = make_lidar_stream(n_kf, seed, yaw_bias=yaw_bias)
         scans = None
     else:
         raise ValueError("sensor must be 'uniform' or 'spinning', not %r" % (sensor,))
@@ -236,7 +241,7 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
         if scans is None:
             from qn_amd import synth
             scans = [synth.lidar_scan(prims, lidar, T, int(sd))[:, :3] for T, sd in zip(gt, seeds)]
-    pg = PoseGraph(); ids = []; corrected = []
+    pg = PoseGraph(); ids = []; corrected = []; sc_descs = {}
     prior_var = np.array([1e-4, 1e-4, 1e-4, 1e-2, 1e-2, 1e-2]); odom_var = prior_var.copy()   # FQ:112-114, 132-133 (rot, then trans)
     loops = []; t_reg = []
     for k in range(n_kf):
@@ -249,8 +254,18 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
         else:
             pg.add_between(k - 1, k, inv(odom[k - 1]) @ odom[k], odom_var)
         # ---- loopTimerFunc
-        pos = np.array([c[:3, 3] for c in corrected])
-        cand = loop_candidates(pos, stamps[:k + 1], k, radius, tdiff, max_k=1)
+        if detector == "radius":
+            pos = np.array([c[:3, 3] for c in corrected])
+            cand = loop_candidates(pos, stamps[:k + 1], k, radius, tdiff, max_k=1)
+        elif backend == "gpu":                                                               # store ids are keyframe indices here
+            store.sc_describe([ids[k]])
+            c_ids, c_d, _ = store.sc_query([ids[k]], stamps, tdiff, 1)[0]
+            cand = c_ids[c_d < sc_max_dist]
+        else:
+            from qn_amd import scancontext
+            sc_descs[k] = scancontext.descriptor(scans[k])
+            best = scancontext.query(sc_descs, k, stamps, tdiff, 1)
+            cand = [b[0] for b in best if b[1] < sc_max_dist]
         if len(cand) == 0:
             continue
         c = int(cand[0])
@@ -286,7 +301,7 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
         loops.append((k, c, score))
         pg.optimize()
         corrected = [p.copy() for p in pg.poses]                                             # FQ:180-188
-    out = dict(sensor=sensor, n_keyframes=n_kf, loops=len(loops), attempts=len(t_reg), ate_odometry=ate(odom, gt), ate_corrected=ate(corrected, gt),
+    out = dict(sensor=sensor, detector=detector, n_keyframes=n_kf, loops=len(loops), attempts=len(t_reg), ate_odometry=ate(odom, gt), ate_corrected=ate(corrected, gt),
                ms_per_attempt=1e3 * float(np.mean(t_reg)) if t_reg else None, quatro=use_quatro, loop_list=loops, poses=corrected)
     if save_dir:
         write_kitti_tum(save_dir, corrected, stamps)
@@ -308,5 +323,7 @@ if __name__ == "__main__":
     ap.add_argument("--sensor", choices=["uniform", "spinning"], default="uniform", help="keyframe clouds: uniform surface samples, or ray-cast spinning-LiDAR scans")
     ap.add_argument("--save-dir", default=None, help="write poses_kitti.txt / poses_tum.txt (FQ:344-373) here")
     ap.add_argument("--save-map-leaf", type=float, default=None, help="with --save-dir: also write map.pcd, the corrected map at this leaf (0.3 = save_voxel_resolution)")
+    ap.add_argument("--detector", choices=["radius", "scancontext"], default="radius", help="loop candidates: radius search on corrected poses, or Scan Context")
+    ap.add_argument("--yaw-bias", type=float, default=0.006, help="odometry heading drift per keyframe [rad]")
     a = ap.parse_args()
-    run(a.keyframes, a.seed, a.quatro, save_dir=a.save_dir, save_map_leaf=a.save_map_leaf, sensor=a.sensor)
+    run(a.keyframes, a.seed, a.quatro, save_dir=a.save_dir, save_map_leaf=a.save_map_leaf, sensor=a.sensor, detector=a.detector, yaw_bias=a.yaw_bias)
