@@ -29,21 +29,42 @@ struct LanePlan {                        // the launches of one segment and thei
   explicit LanePlan(qn_ctx* c_) : c(c_) {}
   template <class F> void add(const std::vector<LaneEntry<typename F::Args>>& e, int family, uint32_t shmem = 0) {      // shmem: dynamic LDS the launch asks for on top of the kernel's own (an occupancy limiter: knob tick_lds_pad)      // family: the profiling family of qn_prof_get (hipEvents around the launch when profiling is on)
     if (e.empty()) return;
-    size_t a = (off + 255) & ~(size_t)255; const size_t bytes = sizeof(LaneEntry<typename F::Args>) * e.size();
-    if (a + bytes > c->args_cap) {
-      // the segment's tables outgrow the arena (forced runs of hundreds of iterations x many lanes): launch what is planned, wait until the device has consumed the
-      // pinned staging copy, and carry on from the start of the arena - stream order keeps the chain's meaning, the host merely looks in once more (ADVICE r4)
-      if (items.empty() || bytes > c->args_cap || flush_rc != QN_OK) { overflow = true; return; }
-      flush_rc = run();
-      if (flush_rc == QN_OK && hipStreamSynchronize(c->stream) != hipSuccess) { c->last_error = "batch: stream synchronisation failed while flushing the argument arena"; flush_rc = QN_ERR_HIP; }
-      if (flush_rc != QN_OK) { overflow = true; return; }
-      a = 0;
-    }
+    const size_t bytes = sizeof(LaneEntry<typename F::Args>) * e.size();
+    const size_t a = reserve(bytes);
+    if (a == SIZE_MAX) return;
+    put<F>(e, a, family, shmem);
+  }
+  // the same with `blob_bytes` bytes of data the entries point to (per-lane initial guesses) in front of the table, in ONE reservation: a flush of the arena can
+  // never fall between the data and its launch.  fix(entries, device address of the blob) sets the entries' pointers once the place is known.
+  template <class F, class Fix> void add(std::vector<LaneEntry<typename F::Args>>& e, int family, const void* blob, size_t blob_bytes, Fix fix) {
+    if (e.empty()) return;
+    const size_t head = (blob_bytes + 255) & ~(size_t)255, bytes = head + sizeof(LaneEntry<typename F::Args>) * e.size();
+    const size_t a = reserve(bytes);
+    if (a == SIZE_MAX) return;
+    memcpy(c->args_h + a, blob, blob_bytes);
+    fix(e, (const char*)(c->args_d + a));
+    put<F>(e, a + head, family, 0);
+  }
+  template <class F> void put(const std::vector<LaneEntry<typename F::Args>>& e, size_t a, int family, uint32_t shmem) {
+    const size_t bytes = sizeof(LaneEntry<typename F::Args>) * e.size();
     memcpy(c->args_h + a, e.data(), bytes);
     uint32_t gx = 0; for (const auto& x : e) gx = std::max(gx, x.nbx);
     gx = (gx + 7u) & ~7u;                                              // a multiple of 8: (linear workgroup id) mod 8 - the XCD - stays blockIdx.x mod 8 in every lane (xcd_block)
     items.push_back(Item{&lanes_launch<F>, a, dim3(gx, (uint32_t)e.size()), family, shmem});
     off = a + bytes;
+  }
+  size_t reserve(size_t bytes) {                                       // the arena offset of `bytes` more (SIZE_MAX: overflow, reported by run())
+    size_t a = (off + 255) & ~(size_t)255;
+    if (a + bytes > c->args_cap) {
+      // the segment's tables outgrow the arena (forced runs of hundreds of iterations x many lanes): launch what is planned, wait until the device has consumed the
+      // pinned staging copy, and carry on from the start of the arena - stream order keeps the chain's meaning, the host merely looks in once more (ADVICE r4)
+      if (items.empty() || bytes > c->args_cap || flush_rc != QN_OK) { overflow = true; return SIZE_MAX; }
+      flush_rc = run();
+      if (flush_rc == QN_OK && hipStreamSynchronize(c->stream) != hipSuccess) { c->last_error = "batch: stream synchronisation failed while flushing the argument arena"; flush_rc = QN_ERR_HIP; }
+      if (flush_rc != QN_OK) { overflow = true; return SIZE_MAX; }
+      a = 0;
+    }
+    return a;
   }
   int run() {                                                          // one upload, then the launches in order; the arena is free again after the caller's next synchronisation
     if (overflow) { if (flush_rc == QN_OK) c->last_error = "batch: argument arena too small for one launch's table"; return QN_ERR_HIP; }
@@ -133,9 +154,9 @@ int batch_ensure_lanes(qn_ctx* c) {
   return QN_OK;
 }
 
-// m <= B pairs through the chain in lockstep.  idx[l] = the pair lane l registers.
+// m <= B pairs through the chain in lockstep.  idx[l] = the pair lane l registers; guesses16 (or null: identity) = 16 floats per PAIR, align(output, guess).
 int batch_register(qn_ctx* owner, const qn_pair_desc* pairs, const uint32_t* idx, uint32_t m, double thr, qn_gicp_result* results, int* valid, int* status,
-                   std::vector<const float*>& last_src, std::vector<uint64_t>& last_key) {
+                   std::vector<const float*>& last_src, std::vector<uint64_t>& last_key, const float* guesses16) {
   hipStream_t s = owner->stream;
   const auto t_call = std::chrono::steady_clock::now();
   const qn_gicp_params& p = owner->params;
@@ -207,7 +228,7 @@ int batch_register(qn_ctx* owner, const qn_pair_desc* pairs, const uint32_t* idx
   const int fixed_unseeded = std::max(1, std::min(owner->track_from_tick, owner->fused_from_tick)) * per_outer;
   const bool exact_ticks = p.force_iterations > 0 && p.optimizer == QN_OPT_GN;
   {
-    std::vector<LaneEntry<InitStateK::Args>> v_init;
+    std::vector<LaneEntry<InitStateK::Args>> v_init; std::vector<float> g16;
     for (LaneRun& R : L) {
       if (!R.active) continue;
       qn_ctx* c = R.c;
@@ -216,9 +237,14 @@ int batch_register(qn_ctx* owner, const qn_pair_desc* pairs, const uint32_t* idx
       R.ticks_left = exact_ticks ? maxit : 1 << 30;
       R.chunk = std::min(fixed_unseeded, R.ticks_left); R.chunk_start = 0; R.next = R.chunk; R.first_chunk = true;
       R.budget = (long)maxit * (p.optimizer == QN_OPT_LM ? (p.lm_max_iterations + 1) : 1) + 2;
-      lane_push(v_init, InitStateK::Args{st_cur(c), c->guess_tmp, 0, 0, c->far_stats}, 1u);
+      lane_push(v_init, InitStateK::Args{st_cur(c), c->guess_tmp, guesses16 ? 1 : 0, 0, c->far_stats}, 1u);
+      if (guesses16) g16.insert(g16.end(), guesses16 + 16 * (size_t)R.pair, guesses16 + 16 * (size_t)R.pair + 16);
     }
-    plan.add<InitStateK>(v_init, QN_K_SOLVE);
+    if (!guesses16) plan.add<InitStateK>(v_init, QN_K_SOLVE);
+    else                   // the lanes' guesses ride in the segment's one arena upload, in front of the table that points at them (k_init_state's `guess` of gicp_align)
+      plan.add<InitStateK>(v_init, QN_K_SOLVE, g16.data(), sizeof(float) * g16.size(), [](std::vector<LaneEntry<InitStateK::Args>>& e, const char* d) {
+        for (size_t j = 0; j < e.size(); j++) e[j].a.guess = (const float*)(d + sizeof(float) * 16 * j);
+      });
   }
   auto finish_lane = [&](LaneRun& R, int rc) {
     qn_ctx* c = R.c;
@@ -322,8 +348,15 @@ int batch_register(qn_ctx* owner, const qn_pair_desc* pairs, const uint32_t* idx
 
 // SURVEY.md 8b: n_pairs independent LoopClosure::icpAlignment calls (loop_closure.cpp:110-136) on ONE context, `batch_lanes` of them per kernel launch.
 // Parameters are the context's (qn_gicp_set_params).  status[i] = the pair's own status; the return value is QN_OK unless the batch machinery itself failed.
-extern "C" int qn_gicp_align_batch(qn_ctx* c, const qn_pair_desc* pairs, uint32_t n_pairs, double score_thr, qn_gicp_result* results, int* valid, int* status) {
+// guesses16 (n_pairs x 16 floats, row-major; null = identity): pair i is align(output, guess i) - NanoGICP::align with a guess, what qn_gicp_align(guess) runs.
+extern "C" int qn_gicp_align_batch_guess(qn_ctx* c, const qn_pair_desc* pairs, const float* guesses16, uint32_t n_pairs, double score_thr, qn_gicp_result* results, int* valid, int* status) {
   if (!c || (n_pairs && (!pairs || !results || !valid || !status))) return QN_ERR_INVALID_ARG;
+  if (guesses16)
+    for (uint32_t i = 0; i < n_pairs; i++) {
+      const float* g = guesses16 + 16 * (size_t)i;
+      for (int j = 0; j < 16; j++) if (!std::isfinite(g[j])) { c->last_error = "align_batch_guess: non-finite guess entry"; return QN_ERR_INVALID_ARG; }
+      if (g[12] != 0.f || g[13] != 0.f || g[14] != 0.f || g[15] != 1.f) { c->last_error = "align_batch_guess: a guess's last row is not 0 0 0 1"; return QN_ERR_INVALID_ARG; }
+    }
   if (n_pairs == 0) return QN_OK;
   HIPCHK(c, hipSetDevice(c->device));
   if (join_target(c) != QN_OK) return QN_ERR_HIP;
@@ -333,7 +366,8 @@ extern "C" int qn_gicp_align_batch(qn_ctx* c, const qn_pair_desc* pairs, uint32_
     for (uint32_t i = 0; i < n_pairs; i++) {
       const qn_pair_desc& p = pairs[i];
       const bool same = c->batch_share_source && i > 0 && status[i - 1] == QN_OK && pairs[i - 1].src == p.src && pairs[i - 1].ns == p.ns && pairs[i - 1].stride_bytes == p.stride_bytes && pairs[i - 1].on_device == p.on_device;
-      status[i] = icp_alignment(c, p.src, p.ns, p.dst, p.nt, p.stride_bytes, score_thr, &results[i], &valid[i], p.on_device ? 1 : 0, same);
+      status[i] = icp_alignment(c, p.src, p.ns, p.dst, p.nt, p.stride_bytes, score_thr, &results[i], &valid[i], p.on_device ? 1 : 0, same, false,
+                                guesses16 ? guesses16 + 16 * (size_t)i : nullptr);
     }
     c->pair_pipeline = sp; c->persist_batch_off = sb;
     return QN_OK;
@@ -345,9 +379,12 @@ extern "C" int qn_gicp_align_batch(qn_ctx* c, const qn_pair_desc* pairs, uint32_
   for (uint32_t base = 0; base < n_pairs && rc == QN_OK; base += B) {
     const uint32_t m = std::min(B, n_pairs - base);
     for (uint32_t l = 0; l < m; l++) idx[l] = base + l;
-    rc = batch_register(c, pairs, idx.data(), m, score_thr, results, valid, status, last_src, last_key);
+    rc = batch_register(c, pairs, idx.data(), m, score_thr, results, valid, status, last_src, last_key, guesses16);
   }
   c->pair_pipeline = sp; c->persist_batch_off = sb;
   if (rc != QN_OK) (void)hipStreamSynchronize(c->stream);
   return rc;
+}
+extern "C" int qn_gicp_align_batch(qn_ctx* c, const qn_pair_desc* pairs, uint32_t n_pairs, double score_thr, qn_gicp_result* results, int* valid, int* status) {
+  return qn_gicp_align_batch_guess(c, pairs, nullptr, n_pairs, score_thr, results, valid, status);
 }

@@ -923,6 +923,11 @@ extern "C" int qn_kf_assemble_batch(qn_kf_store* s, const int32_t* ids, const do
   return QN_OK;
 }
 
+extern "C" int qn_kf_batch_count(const qn_kf_store* s, uint32_t seg, uint32_t* n) {
+  if (!s || !n || seg >= s->bt_n.size()) return QN_ERR_INVALID_ARG;
+  *n = s->bt_n[seg];
+  return QN_OK;
+}
 extern "C" int qn_kf_download_batch(qn_kf_store* s, uint32_t seg, float* xyz_out) {     // packed n x 3, for tests / visualisation
   if (!s || !xyz_out || seg >= s->bt_n.size()) return QN_ERR_INVALID_ARG;
   const uint32_t n = s->bt_n[seg];

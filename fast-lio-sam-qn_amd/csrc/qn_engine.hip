@@ -229,6 +229,7 @@ extern "C" void qn_ctx_destroy(qn_ctx* c) {
 
 static int clouds_valid(qn_ctx* c);
 extern "C" void* qn_ctx_stream(qn_ctx* c) { return c ? (void*)c->stream : nullptr; }
+int qn_ctx_int_device(const qn_ctx* c) { return c->device; }      // (for other translation units: qn_verify.hip)
 extern "C" int qn_ctx_synchronize(qn_ctx* c) {
   if (!c) return QN_ERR_INVALID_ARG;
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -966,7 +967,7 @@ extern "C" int qn_gicp_get_lane_trace(qn_ctx* c, uint32_t lane, qn_iter_trace* o
 // 2 = source on the device as packed float4 (the coarse-aligned cloud of coarseToFineAlignment), target on the host,
 // 3 = like 2 with the target on the device too.
 static int icp_alignment(qn_ctx* c, const float* src, uint32_t ns, const float* dst, uint32_t nt, uint32_t stride, double thr,
-                         qn_gicp_result* out, int* valid, int where, bool reuse_source = false, bool target_ready = false) {
+                         qn_gicp_result* out, int* valid, int where, bool reuse_source = false, bool target_ready = false, const float* guess = nullptr) {
   if (!c || !out || !valid) return QN_ERR_INVALID_ARG;
   *valid = 0;
   memset(out, 0, sizeof(*out)); out->fitness = DBL_MAX;
@@ -989,7 +990,7 @@ static int icp_alignment(qn_ctx* c, const float* src, uint32_t ns, const float* 
     if (!early && (rc = set_cloud(c, QN_TARGET, dst, nt, stride, where == 1 || where == 3)) != QN_OK) return rc;     // :122 (on the second stream: see TargetScope)
     if ((rc = qn_gicp_compute_covariances(c, QN_TARGET)) != QN_OK) return rc;         // :123
   }
-  if ((rc = qn_gicp_align(c, nullptr, out)) != QN_OK) return rc;                    // :124, :127
+  if ((rc = qn_gicp_align(c, guess, out)) != QN_OK) return rc;                      // :124 (align(output, guess) when a guess is given), :127
   *valid = (out->converged && out->fitness < thr) ? 1 : 0;                          // :129
   return QN_OK;
 }
@@ -1014,7 +1015,7 @@ extern "C" int qn_icp_alignment_device(qn_ctx* c, const float* src, uint32_t ns,
 // (qn_ctx::batch_min_share of the FIRST context of the call, default 4; knob batch_min_share)
 namespace { bool batch_supported(const qn_ctx* c); int batch_ensure_lanes(qn_ctx* c);
             int batch_register(qn_ctx* owner, const qn_pair_desc* pairs, const uint32_t* idx, uint32_t m, double thr, qn_gicp_result* results, int* valid, int* status,
-                               std::vector<const float*>& last_src, std::vector<uint64_t>& last_key); }
+                               std::vector<const float*>& last_src, std::vector<uint64_t>& last_key, const float* guesses16); }
 extern "C" int qn_icp_alignment_batch(qn_ctx* const* ctxs, uint32_t n_ctx, const qn_pair_desc* pairs, uint32_t n_pairs, double thr,
                                       qn_gicp_result* results, int* valid, int* status) {
   if (!ctxs || n_ctx == 0 || (n_pairs && (!pairs || !results || !valid || !status))) return QN_ERR_INVALID_ARG;
@@ -1055,7 +1056,7 @@ extern "C" int qn_icp_alignment_batch(qn_ctx* const* ctxs, uint32_t n_ctx, const
         }
         if (base >= n_pairs) break;
         for (uint32_t l = 0; l < m; l++) idx[l] = base + l;
-        const int rc = batch_register(c, pairs, idx.data(), m, thr, results, valid, status, last_src, last_key);
+        const int rc = batch_register(c, pairs, idx.data(), m, thr, results, valid, status, last_src, last_key, nullptr);
         if (rc != QN_OK) { (void)hipStreamSynchronize(c->stream); for (uint32_t l = 0; l < m; l++) status[base + l] = rc; std::fill(last_src.begin(), last_src.end(), nullptr); }
       }
       return;

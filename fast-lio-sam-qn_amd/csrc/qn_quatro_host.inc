@@ -973,7 +973,7 @@ int c2f_run(qn_ctx* owner, const qn_pair_desc* pairs, const uint32_t* idx, uint3
   // ---- the fine stage (:153): the accepted pairs through the GICP lanes (lane j of the GICP run = the j-th accepted pair; its clouds live in the Quatro lane's c2f buffers)
   std::vector<qn_gicp_result> gres(m); std::vector<int> gval(m, 0), gst(m, QN_ERR_HIP);
   std::vector<const float*> last_src(owner->lanes.size(), nullptr); std::vector<uint64_t> last_key(owner->lanes.size(), 0);
-  const int rc = batch_register(owner, gp.data(), gidx.data(), (uint32_t)gidx.size(), thr, gres.data(), gval.data(), gst.data(), last_src, last_key);
+  const int rc = batch_register(owner, gp.data(), gidx.data(), (uint32_t)gidx.size(), thr, gres.data(), gval.data(), gst.data(), last_src, last_key, nullptr);
   if (rc != QN_OK) return rc;
   // ---- 4. compose (:156) and accept (:129)
   for (uint32_t l : gidx) {

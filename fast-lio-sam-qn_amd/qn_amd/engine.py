@@ -489,9 +489,9 @@ def icp_alignment_batch(contexts, pairs, score_thr=1.5):
     return results, list(valid), list(status)
 
 
-def gicp_align_batch(ctx, pairs, score_thr=1.5):
+def gicp_align_batch(ctx, pairs, score_thr=1.5, guesses=None):
     """qn_gicp_align_batch: the same batch on ONE context, the pair as a grid dimension of every kernel launch (`batch_lanes` pairs in lockstep).
-    pairs / return value as icp_alignment_batch."""
+    pairs / return value as icp_alignment_batch.  guesses (n x 4 x 4, rounded to f32) given: qn_gicp_align_batch_guess, pair i starts from guesses[i]."""
     n = len(pairs)
     descs = (PairDesc * n)(); keep = []
     for i, (s, ns, d, nt, stride, dev) in enumerate(pairs):
@@ -501,7 +501,13 @@ def gicp_align_batch(ctx, pairs, score_thr=1.5):
         else:
             descs[i] = PairDesc(s, ns, d, nt, stride, 1)
     results = (GicpResult * n)(); valid = (C.c_int * n)(); status = (C.c_int * n)()
-    st = lib().qn_gicp_align_batch(ctx.h, descs, C.c_uint32(n), C.c_double(score_thr), results, valid, status)
+    if guesses is None:
+        st = lib().qn_gicp_align_batch(ctx.h, descs, C.c_uint32(n), C.c_double(score_thr), results, valid, status)
+    else:
+        g = np.ascontiguousarray(np.asarray(guesses, dtype=np.float64).astype(np.float32).reshape(-1, 16))
+        if len(g) != n:
+            raise ValueError("gicp_align_batch: %d pairs but %d guesses" % (n, len(g)))
+        st = lib().qn_gicp_align_batch_guess(ctx.h, descs, _p(g), C.c_uint32(n), C.c_double(score_thr), results, valid, status)
     if st != QN_OK:
         raise EngineError(st, lib().qn_status_str(st).decode() + ": " + lib().qn_last_error(ctx.h).decode())
     return results, list(valid), list(status)
@@ -774,6 +780,33 @@ class KeyframeStore:
         (sp, ns, _), rest = out[0], out[1:]
         return [(sp, ns, dp, nt, 16, 1) for dp, nt, _ in rest], [o[2] for o in out]
 
+
+    def verify_loop_candidates(self, ctx, query, candidates, yaw, poses, submap_range, leaf, score_thr=1.5):
+        """qn_kf_verify_loop_candidates: the query scan in its own sensor frame against each candidate's scan-to-submap window in the candidate's sensor
+        frame (keyframe i with scancontext.relative_pose(P_c, P_i)), every pair seeded with scancontext.seed_from_yaw(yaw[j]), all K in ONE batched
+        registration on ctx (its NanoGICP parameters).  yaw: per candidate, the candidate's heading minus the query's (scancontext.yaw_of_shift of
+        sc_query's shift), or None for 0.  poses[i] = keyframe i's corrected pose.  The store's batch slot holds the clouds afterwards (download_batch:
+        segment 0 the source, 1 + j candidate j).  -> one dict per candidate: valid, converged, score, T (inv(P_c) P_query estimate, the f32 record
+        as f64), status (QN_ERR_EMPTY_CLOUD for an empty candidate submap)."""
+        cand = np.ascontiguousarray(np.atleast_1d(candidates), dtype=np.int32)
+        K = len(cand)
+        y = None if yaw is None else np.ascontiguousarray(np.atleast_1d(yaw), dtype=np.float64)
+        if y is not None and len(y) != K:
+            raise ValueError("verify_loop_candidates: %d candidates but %d yaw values" % (K, len(y)))
+        P = np.ascontiguousarray(np.asarray(poses, dtype=np.float64).reshape(-1, 16))
+        results = (GicpResult * max(K, 1))(); valid = np.zeros(max(K, 1), np.int32); status = np.zeros(max(K, 1), np.int32)
+        st = self._l.qn_kf_verify_loop_candidates(self.h, ctx.h, C.c_int32(query), _p(cand) if K else None, _p(y) if y is not None else None, C.c_uint32(K),
+                                                  _p(P), C.c_uint32(len(P)), C.c_uint32(submap_range), C.c_double(leaf), C.c_double(score_thr),
+                                                  results, _p(valid), _p(status))
+        if st != QN_OK:
+            raise EngineError(st, self._l.qn_status_str(st).decode() + ": " + self._l.qn_kf_last_error(self.h).decode() + " / " + lib().qn_last_error(ctx.h).decode())
+        self._batch_n = []
+        for seg in range(K + 1):
+            n = C.c_uint32()
+            self._check(self._l.qn_kf_batch_count(self.h, C.c_uint32(seg), C.byref(n)))
+            self._batch_n.append(n.value)
+        return [dict(valid=bool(valid[j]), converged=bool(results[j].converged), score=results[j].fitness, iterations=results[j].iterations,
+                     T=np.array(results[j].T, dtype=np.float32).reshape(4, 4).astype(np.float64), status=int(status[j]), record=results[j]) for j in range(K)]
 
     # ---- Scan Context loop candidates (qn_kf_sc_*; numpy twin: qn_amd/scancontext.py)
     def sc_set_params(self, params=None, **kw):

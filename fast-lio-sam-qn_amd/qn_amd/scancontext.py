@@ -196,3 +196,34 @@ def query(descs, q, stamps, tdiff, top_k, prefilter=0):
     D, sh = distances(descs[q], [descs[c] for c in cand])
     order = sorted(range(len(cand)), key=lambda m: (D[m], cand[m]))[:top_k]
     return [(cand[m], float(D[m]), int(sh[m])) for m in order]
+
+
+# ---- drift-free verification of a candidate (qn_kf_verify_loop_candidates, csrc/qn_verify.hip): the engine's target poses and seeds, bit for bit
+def relative_pose(P_c, P_i):
+    """inv(P_c) P_i in f64: inv(P) = [R^T | -R^T t] (each -R^T t entry summed over k = 0..2 in order), every entry of the product summed over
+    k = 0..3 in order, no fused multiply-add.  Keyframe i of candidate c's window enters the target with this pose (the candidate's sensor frame)."""
+    Pc = [[float(v) for v in row] for row in np.asarray(P_c, np.float64).reshape(4, 4)]
+    Pi = [[float(v) for v in row] for row in np.asarray(P_i, np.float64).reshape(4, 4)]
+    A = [[0.0] * 4 for _ in range(4)]
+    for r in range(3):
+        acc = 0.0
+        for k in range(3):
+            A[r][k] = Pc[k][r]
+            acc = acc + Pc[k][r] * Pc[k][3]
+        A[r][3] = -acc
+    A[3] = [0.0, 0.0, 0.0, 1.0]
+    Q = np.zeros((4, 4))
+    for r in range(4):
+        for c in range(4):
+            acc = 0.0
+            for k in range(4):
+                acc = acc + A[r][k] * Pi[k][c]
+            Q[r, c] = acc
+    return Q
+
+
+def seed_from_yaw(yaw):
+    """the initial guess of a candidate whose heading minus the query's is yaw: Rz(-yaw) as f32 (4x4), from the C library's cos / sin in f64.
+    R(inv(P_c) P_q) = Rz(h_q - h_c) = Rz(-yaw)."""
+    c, s = math.cos(-float(yaw)), math.sin(-float(yaw))
+    return np.array([[c, -s, 0.0, 0.0], [s, c, 0.0, 0.0], [0.0, 0.0, 1.0, 0.0], [0.0, 0.0, 0.0, 1.0]]).astype(np.float32)

@@ -3,7 +3,7 @@
 // descriptor is made on the GPU from its resident keyframe (qn_kf_sc_describe, a no-op when it exists), the older keyframes' descriptors
 // must already exist (describe each keyframe once, when it is added), and qn_kf_sc_query ranks them.  The indices feed
 // qn_map::loopSubmapPairs (loop_submaps.hpp) and the batched registrations; yaw is the candidate's heading minus the query's, from the
-// best column shift, for callers that want an initial rotation.
+// best column shift: verifyScanContextCandidates seeds each candidate's registration with it.
 // Header-only; forwards to the C-ABI in include/qn_engine.h.  Link with -lqn_engine.  Uses nothing from Eigen or PCL.
 #pragma once
 #include <cmath>
@@ -42,6 +42,39 @@ inline ScCandidates scanContextCandidates(qn_kf_store* store, const std::vector<
     double yaw = std::fmod(-2.0 * pi * shift[r] / p.n_sectors + pi, 2.0 * pi);
     if (yaw < 0) yaw += 2.0 * pi;
     out.idx.push_back(ids[r]); out.dist.push_back(d[r]); out.yaw.push_back(yaw - pi);
+  }
+  return out;
+}
+
+struct ScVerified {
+  int idx;                                         // the candidate's keyframe index
+  bool valid;                                      // loop_closure.cpp:129: converged and score < score_thr
+  double score;                                    // fitness
+  double T[16];                                    // row-major, query sensor frame -> candidate sensor frame: an estimate of inv(P_c) P_query
+  int status;                                      // QN_OK, or QN_ERR_EMPTY_CLOUD for an empty candidate submap
+};
+
+// Drift-free verification of the candidates (qn_kf_verify_loop_candidates): the query scan in its own sensor frame against each candidate's
+// scan-to-submap window in the candidate's sensor frame, seeded with ScCandidates::yaw, all in one batched registration on ctx (its NanoGICP
+// parameters).  poses16 = the corrected poses (row-major 4x4 each), one per keyframe.  In loopTimerFunc the loop factor is then
+// BetweenFactor(latest, c, inv(T), score) from T itself, in place of pose_between_eig_ * pose_corrected (fast_lio_sam_qn.cpp:224-233).
+inline std::vector<ScVerified> verifyScanContextCandidates(qn_kf_store* store, qn_ctx* ctx, int query, const ScCandidates& c, const std::vector<double>& poses16,
+                                                           int submap_range, double leaf, double score_thr) {
+  std::vector<ScVerified> out;
+  if (c.idx.empty()) return out;
+  if (submap_range < 0 || poses16.size() % 16 != 0 || c.yaw.size() != c.idx.size())
+    throw std::invalid_argument("[qn_map] verifyScanContextCandidates: bad submap_range, poses or candidates");
+  const size_t K = c.idx.size();
+  std::vector<int32_t> ids(c.idx.begin(), c.idx.end());
+  std::vector<qn_gicp_result> r(K);
+  std::vector<int> valid(K), status(K);
+  const int rc = qn_kf_verify_loop_candidates(store, ctx, query, ids.data(), c.yaw.data(), (uint32_t)K, poses16.data(), (uint32_t)(poses16.size() / 16),
+                                              (uint32_t)submap_range, leaf, score_thr, r.data(), valid.data(), status.data());
+  if (rc != QN_OK) throw std::runtime_error(std::string("[qn_map] qn_kf_verify_loop_candidates: ") + qn_status_str(rc) + " " + qn_kf_last_error(store));
+  for (size_t k = 0; k < K; k++) {
+    ScVerified v{c.idx[k], valid[k] != 0, r[k].fitness, {}, status[k]};
+    for (int i = 0; i < 16; i++) v.T[i] = (double)r[k].T[i];
+    out.push_back(v);
   }
   return out;
 }

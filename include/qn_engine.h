@@ -164,6 +164,11 @@ int  qn_icp_alignment_batch(qn_ctx* const* ctxs, uint32_t n_ctx, const qn_pair_d
  * first batch call: batch_lanes x in_flight x slab in total (8 x 3 x 119 MB = 2.9 GB at the bench's setting; batch_lanes = 64 at 100k is 7.6 GB per context).  If the lanes cannot be
  * allocated, the ones created so far are freed again and both entry points register the pairs one at a time on the context itself (same records).                        */
 int  qn_gicp_align_batch(qn_ctx*, const qn_pair_desc* pairs, uint32_t n_pairs, double score_thr, qn_gicp_result* results, int* valid, int* status);
+/* The same batch with an initial guess per pair: pair i is align(output, guesses16[16 i .. 16 i + 15]) (NanoGICP::align with a guess, what qn_gicp_align(guess)
+ * runs), row-major 4x4 f32, through the same lanes; guesses16 = NULL is qn_gicp_align_batch itself (identity).  Any non-finite guess entry, or a last row other
+ * than 0 0 0 1: QN_ERR_INVALID_ARG before anything runs.  The guesses reach the device inside each segment's one argument upload.                        */
+int  qn_gicp_align_batch_guess(qn_ctx*, const qn_pair_desc* pairs, const float* guesses16, uint32_t n_pairs, double score_thr,
+                               qn_gicp_result* results, int* valid, int* status);
 
 /* ---- candidate pairs sharded over the GPUs of one node (BASELINE "batch of 64 candidate keyframe pairs sharded
  * across 8 MI355X, RCCL gather of best loop").  The reference registers ONE candidate per timer tick
@@ -300,6 +305,23 @@ int  qn_kf_download(qn_kf_store*, int slot, float* xyz_out /* n x 3 packed */);
 int  qn_kf_assemble_batch(qn_kf_store*, const int32_t* ids, const double* poses16, const uint32_t* seg_off, uint32_t n_seg, double leaf,
                           const float** d_xyz_out, uint32_t* n_out, int* status);
 int  qn_kf_download_batch(qn_kf_store*, uint32_t seg, float* xyz_out /* n x 3 packed */);
+int  qn_kf_batch_count(const qn_kf_store*, uint32_t seg, uint32_t* n);      /* points of segment `seg` of the batch slot (as n_out of the call that filled it) */
+/* Drift-free verification of loop candidates (Scan Context's, typically) of one query: no cloud depends on the accumulated drift of the corrected poses.
+ * Store ids are keyframe indices; poses16[i] = keyframe i's corrected pose, n_poses of them.  One qn_kf_assemble_batch into the store's batch slot:
+ *   segment 0     = keyframe `query` alone with the exact identity pose (its sensor frame), voxel grid at `leaf` - the one source of every pair;
+ *   segment 1 + j = the scan-to-submap window of cand[j] (loop_submap_ids(query, c, submap_range, no Quatro, no submap matching, n_poses)[1]: keyframes
+ *                   c - submap_range .. c + submap_range with 0 <= i < n_poses - 1), keyframe i with Q_i = inv(P_c) P_i (inv(P) = [R^T | -R^T t]; every
+ *                   entry of each product summed over k = 0..3 in order in f64, no fused multiply-add), voxel grid at `leaf`;
+ * then ONE qn_gicp_align_batch_guess on ctx (its parameters) with pair j seeded by Rz(-yaw[j]): c = cos(-yaw), s = sin(-yaw) in f64 (C library), each entry
+ * rounded to f32, [c -s 0 0; s c 0 0; 0 0 1 0; 0 0 0 1].  yaw[j] (NULL: all 0) = the candidate's heading minus the query's (qn_kf_sc_query's shift as
+ * scancontext.yaw_of_shift).  results[j].T maps query-sensor points into the candidate's sensor frame: an estimate of inv(P_c) P_query; valid[j] follows
+ * loop_closure.cpp:129.  status[j]: the candidate submap's assembly status (QN_ERR_EMPTY_CLOUD: valid 0, the others still run), else the registration's.
+ * QN_ERR_INVALID_ARG before anything runs (store and context unchanged): a bad or repeated id, a candidate equal to the query, n_cand == 0, n_poses <= the
+ * largest id used, a non-finite pose or yaw, leaf <= 0, or store and context on different devices.  Host synchronisations: the assembly's two and the
+ * registration's own.                                                                                                                                  */
+int  qn_kf_verify_loop_candidates(qn_kf_store*, qn_ctx*, int32_t query, const int32_t* cand, const double* yaw /* per candidate; NULL = 0 */,
+                                  uint32_t n_cand, const double* poses16 /* n_poses x 16 */, uint32_t n_poses, uint32_t submap_range, double leaf,
+                                  double score_thr, qn_gicp_result* results, int* valid, int* status);
 /* the corrected global map = the three loops of FastLioSamQn that rebuild it from every keyframe with its corrected pose
  * (fast_lio_sam_qn.cpp:302-316 visTimerFunc, :398-411 saveFlagCallback, :435-448 the destructor's result.pcd): transformPcd of each
  * listed keyframe, concatenation in `ids` order (ids may repeat), voxelizePcd at save_voxel_resolution (pcl::VoxelGrid,

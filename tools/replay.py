@@ -209,15 +209,38 @@ def ate(poses, gt):
     return float(np.sqrt(np.mean([np.sum((a[:3, 3] - b[:3, 3]) ** 2) for a, b in zip(poses, gt)])))
 
 
+def _oracle_relative(orc, scans, poses, k, c, yaw, submap_range, voxel, max_corr_dist, score_thr):
+    """verify_loop_candidates for one candidate on the CPU oracle: the same clouds and guess from the twins"""
+    from qn_amd import scancontext, engine
+    sub = engine.loop_submap_ids(k, c, submap_range, False, False, len(poses))[1]
+    src = orc.assemble_submap(scans, {k: np.eye(4)}, [k], voxel)
+    dst = orc.assemble_submap(scans, {i: scancontext.relative_pose(poses[c], poses[i]) for i in sub}, sub, voxel)
+    g = orc.GicpOracle(k=15, max_iter=32, max_corr_dist=max_corr_dist, trans_eps=0.01)
+    g.set_source(src); g.compute_covariances(0); g.set_target(dst); g.compute_covariances(1)
+    r = g.align(scancontext.seed_from_yaw(yaw).astype(np.float64))
+    return dict(valid=bool(r["converged"] and r["fitness"] < score_thr), converged=r["converged"], score=r["fitness"], T=r["Tf"].astype(np.float64))
+
+
 def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, submap_range=5, score_thr=1.5, verbose=True, backend="gpu", save_dir=None,
-        save_map_leaf=None, sensor="uniform", detector="radius", sc_max_dist=0.3, yaw_bias=0.006):
+        save_map_leaf=None, sensor="uniform", detector="radius", sc_max_dist=0.3, yaw_bias=0.006, verify="reference", sc_top_k=1):
     """sensor = "uniform": keyframe clouds sampled uniformly by area inside a disc (make_stream); "spinning": ray-cast spinning-LiDAR
     scans from the ground-truth poses of the same figure-8 (make_lidar_stream).  detector = "radius": the candidate is the closest older
     keyframe within `radius` of the corrected position (LC:34-56); "scancontext": the older keyframe nearest by Scan Context distance, kept
     when that is below sc_max_dist - on the GPU from the resident keyframes (KeyframeStore.sc_describe / sc_query), for the oracle backend by
-    the numpy twin qn_amd.scancontext.  yaw_bias: the odometry's heading drift per keyframe [rad]."""
+    the numpy twin qn_amd.scancontext.  yaw_bias: the odometry's heading drift per keyframe [rad].
+    verify = "reference": the candidate's registration as loop_closure.cpp does it (both clouds in the world frame of the corrected poses, GICP from
+    identity).  "relative" (with detector="scancontext"): the query's top sc_top_k candidates with D < sc_max_dist in ONE drift-free verification
+    (KeyframeStore.verify_loop_candidates: the query scan in its sensor frame against each candidate's window in the candidate's sensor frame, seeded
+    with its Scan Context heading); the valid one with the lowest score gives the loop factor Z = inv(T), variance = score.  The oracle backend
+    rebuilds the same clouds and guesses from the twins (scancontext.relative_pose / seed_from_yaw) and registers them with the CPU oracle."""
     if detector not in ("radius", "scancontext"):
         raise ValueError("detector must be 'radius' or 'scancontext', not %r" % (detector,))
+    if verify not in ("reference", "relative"):
+        raise ValueError("verify must be 'reference' or 'relative', not %r" % (verify,))
+    if verify == "relative" and detector != "scancontext":
+        raise ValueError("verify='relative' needs detector='scancontext' (it is seeded with the Scan Context heading)")
+    if verify == "relative" and use_quatro:
+        raise ValueError("verify='relative' registers with Nano-GICP alone (the seed replaces Quatro's coarse alignment)")
     if sensor == "uniform":
         scans, gt, odom, stamps = make_stream(n_kf, seed, yaw_bias=yaw_bias)
     elif sensor == "spinning":
@@ -243,7 +266,7 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
             scans = [synth.lidar_scan(prims, lidar, T, int(sd))[:, :3] for T, sd in zip(gt, seeds)]
     pg = PoseGraph(); ids = []; corrected = []; sc_descs = {}
     prior_var = np.array([1e-4, 1e-4, 1e-4, 1e-2, 1e-2, 1e-2]); odom_var = prior_var.copy()   # FQ:112-114, 132-133 (rot, then trans)
-    loops = []; t_reg = []
+    loops = []; t_reg = []; loop_T = []
     for k in range(n_kf):
         if backend == "gpu":
             ids.append(store.add(scans[k]) if scans is not None else cast_ids[k])
@@ -259,14 +282,33 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
             cand = loop_candidates(pos, stamps[:k + 1], k, radius, tdiff, max_k=1)
         elif backend == "gpu":                                                               # store ids are keyframe indices here
             store.sc_describe([ids[k]])
-            c_ids, c_d, _ = store.sc_query([ids[k]], stamps, tdiff, 1)[0]
-            cand = c_ids[c_d < sc_max_dist]
+            c_ids, c_d, c_sh = store.sc_query([ids[k]], stamps, tdiff, sc_top_k if verify == "relative" else 1)[0]
+            cand, shifts = c_ids[c_d < sc_max_dist], c_sh[c_d < sc_max_dist]
         else:
             from qn_amd import scancontext
             sc_descs[k] = scancontext.descriptor(scans[k])
-            best = scancontext.query(sc_descs, k, stamps, tdiff, 1)
-            cand = [b[0] for b in best if b[1] < sc_max_dist]
+            best = scancontext.query(sc_descs, k, stamps, tdiff, sc_top_k if verify == "relative" else 1)
+            cand = [b[0] for b in best if b[1] < sc_max_dist]; shifts = [b[2] for b in best if b[1] < sc_max_dist]
         if len(cand) == 0:
+            continue
+        if verify == "relative":
+            from qn_amd import scancontext
+            cand = [int(x) for x in cand]; yaws = [scancontext.yaw_of_shift(int(x), scancontext.Params().n_sectors) for x in shifts]
+            t0 = time.perf_counter()
+            if backend == "gpu":
+                rs = store.verify_loop_candidates(ctx, ids[k], [ids[x] for x in cand], yaws, corrected[:k + 1], submap_range, voxel, score_thr)
+            else:
+                rs = [_oracle_relative(orc, scans, corrected[:k + 1], k, x, y, submap_range, voxel, 1.5 * radius, score_thr) for x, y in zip(cand, yaws)]
+            t_reg.append(time.perf_counter() - t0)
+            ok = [(r["score"], j) for j, r in enumerate(rs) if r["valid"]]
+            if not ok:
+                continue
+            score, j = min(ok)
+            c = cand[j]
+            pg.add_between(k, c, inv(rs[j]["T"]), np.full(6, max(score, 1e-6)))               # T ~ inv(P_c) P_k: the between factor (k -> c) is its inverse
+            loops.append((k, c, score)); loop_T.append(rs[j]["T"])
+            pg.optimize()
+            corrected = [p.copy() for p in pg.poses]
             continue
         c = int(cand[0])
         t0 = time.perf_counter()
@@ -298,18 +340,19 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
             continue
         pose_from = Treg @ corrected[k]; pose_to = corrected[c]                              # FQ:224-225
         pg.add_between(k, c, inv(pose_from) @ pose_to, np.full(6, max(score, 1e-6)))        # FQ:226-233
-        loops.append((k, c, score))
+        loops.append((k, c, score)); loop_T.append(Treg)
         pg.optimize()
         corrected = [p.copy() for p in pg.poses]                                             # FQ:180-188
     out = dict(sensor=sensor, detector=detector, n_keyframes=n_kf, loops=len(loops), attempts=len(t_reg), ate_odometry=ate(odom, gt), ate_corrected=ate(corrected, gt),
-               ms_per_attempt=1e3 * float(np.mean(t_reg)) if t_reg else None, quatro=use_quatro, loop_list=loops, poses=corrected)
+               ms_per_attempt=1e3 * float(np.mean(t_reg)) if t_reg else None, quatro=use_quatro, verify=verify, loop_list=loops, poses=corrected,
+               loop_T=loop_T, gt=gt)
     if save_dir:
         write_kitti_tum(save_dir, corrected, stamps)
         if save_map_leaf is not None and backend == "gpu":
             n = store.build_map(ids, corrected, save_map_leaf)
             write_pcd_xyzi(os.path.join(save_dir, "map.pcd"), store.download_map(n))
     if verbose:
-        print({k: v for k, v in out.items() if k not in ("poses", "loop_list")})
+        print({k: v for k, v in out.items() if k not in ("poses", "loop_list", "loop_T", "gt")})
     if backend == "gpu":
         ctx.close(); store.close()
     return out
@@ -325,5 +368,10 @@ if __name__ == "__main__":
     ap.add_argument("--save-map-leaf", type=float, default=None, help="with --save-dir: also write map.pcd, the corrected map at this leaf (0.3 = save_voxel_resolution)")
     ap.add_argument("--detector", choices=["radius", "scancontext"], default="radius", help="loop candidates: radius search on corrected poses, or Scan Context")
     ap.add_argument("--yaw-bias", type=float, default=0.006, help="odometry heading drift per keyframe [rad]")
+    ap.add_argument("--verify", choices=["reference", "relative"], default="reference",
+                    help="candidate registration: the reference's world-frame submaps from identity, or (with --detector scancontext) drift-free relative submaps seeded with the Scan Context heading")
+    ap.add_argument("--sc-top-k", type=int, default=1, help="with --verify relative: Scan Context candidates verified per query, in one batched registration")
+    ap.add_argument("--backend", choices=["gpu", "oracle"], default="gpu", help="the engine on the GPU, or the CPU oracle")
     a = ap.parse_args()
-    run(a.keyframes, a.seed, a.quatro, save_dir=a.save_dir, save_map_leaf=a.save_map_leaf, sensor=a.sensor, detector=a.detector, yaw_bias=a.yaw_bias)
+    run(a.keyframes, a.seed, a.quatro, save_dir=a.save_dir, save_map_leaf=a.save_map_leaf, sensor=a.sensor, detector=a.detector, yaw_bias=a.yaw_bias,
+        verify=a.verify, sc_top_k=a.sc_top_k, backend=a.backend)
