@@ -168,7 +168,7 @@ int batch_register(qn_ctx* owner, const qn_pair_desc* pairs, const uint32_t* idx
     std::vector<LaneRun>& L; std::vector<CloudBuf> saved; std::vector<double*> saved_nrm; std::vector<const float*>& last_src;
     AliasGuard(std::vector<LaneRun>& L_, std::vector<const float*>& ls) : L(L_), saved(L_.size()), saved_nrm(L_.size(), nullptr), last_src(ls) {}
     void borrow(size_t l, qn_ctx* from) { qn_ctx* c = L[l].c; saved[l] = c->cloud[0]; saved_nrm[l] = c->nrm_s_sorted; c->cloud[0] = from->cloud[0]; c->nrm_s_sorted = from->nrm_s_sorted; }
-    ~AliasGuard() { for (size_t l = 0; l < L.size(); l++) if (L[l].alias >= 0 && saved_nrm[l]) { qn_ctx* c = L[l].c; c->cloud[0] = saved[l]; c->nrm_s_sorted = saved_nrm[l]; c->cloud[0].has_grid = c->cloud[0].has_cov = false; c->cloud[0].n = 0; last_src[l] = nullptr; } }
+    ~AliasGuard() { for (size_t l = 0; l < L.size(); l++) if (L[l].alias >= 0 && saved_nrm[l]) { qn_ctx* c = L[l].c; c->cloud[0] = saved[l]; c->nrm_s_sorted = saved_nrm[l]; c->cloud[0].has_grid = c->cloud[0].has_cov = false; c->cloud[0].n = 0; c->cloud[0].knn_tab = nullptr; last_src[l] = nullptr; } }
   } alias_guard(L, last_src);
   // a failure of the batch machinery itself (a HIP error: the function returns it) must not leave a pair that was still under way reported as QN_OK
   struct FailGuard { std::vector<LaneRun>& L; int* status; bool armed = true; ~FailGuard() { if (armed) for (const LaneRun& R : L) if (R.active) status[R.pair] = QN_ERR_HIP; } } fail_guard{L, status};
@@ -211,13 +211,20 @@ int batch_register(qn_ctx* owner, const qn_pair_desc* pairs, const uint32_t* idx
       c->cloud[1].has_grid = c->cloud[1].has_cov = false; c->cloud[1].n = 0;
       continue;
     }
-    if (R.build_source) { push_grid(gs); push_knn(prep_knn(c, c->cloud[0], k, c->knn_idx, nullptr, true)); c->cloud[0].has_cov = true; }                        // :121
-    { ScratchSwap sw(c); push_grid(gt); push_knn(prep_knn(c, c->cloud[1], k, c->knn_idx, nullptr, true)); c->cloud[1].has_cov = true; }                           // :123
+    if (R.build_source) { push_grid(gs); push_knn(prep_knn(c, c->cloud[0], k, c->knn_idx, nullptr, true)); c->cloud[0].has_cov = true; note_knn_table(c, c->cloud[0], c->knn_idx, k); }      // :121
+    { ScratchSwap sw(c); push_grid(gt); push_knn(prep_knn(c, c->cloud[1], k, c->knn_idx, nullptr, true)); c->cloud[1].has_cov = true; note_knn_table(c, c->cloud[1], c->knn_idx, k); }         // :123
     last_src[l] = R.alias >= 0 ? nullptr : pd.src; last_key[l] = key;
     R.active = true;
   }
   plan.add<PackBBoxK>(v_pack, QN_K_GRID_BUILD); plan.add<CellCountK>(v_count, QN_K_GRID_BUILD); plan.add<ScanLookbackK>(v_scan, QN_K_GRID_BUILD); plan.add<ScatterK>(v_scat, QN_K_GRID_BUILD); plan.add<StableCellsK>(v_stab, QN_K_GRID_BUILD);
-  if (k <= 24) { if (owner->knn_mm) plan.add<KnnHistK<false, 32>>(v_sel, QN_K_KNN_SELECT, (uint32_t)owner->knn_lds_pad); else plan.add<KnnHistK<false, 32, false>>(v_sel, QN_K_KNN_SELECT, (uint32_t)owner->knn_lds_pad); plan.add<KnnHistK<true, 32>>(v_lst, QN_K_KNN_COV); } else { plan.add<KnnHistK<false, 48>>(v_sel, QN_K_KNN_SELECT); plan.add<KnnHistK<true, 48>>(v_lst, QN_K_KNN_COV); }
+  // (knn_mm 0: the VALU-scoring forms of both histogram passes)
+  if (k <= 24) {
+    if (owner->knn_mm) { plan.add<KnnHistK<false, 32>>(v_sel, QN_K_KNN_SELECT, (uint32_t)owner->knn_lds_pad); plan.add<KnnHistK<true, 32>>(v_lst, QN_K_KNN_COV); }
+    else { plan.add<KnnHistK<false, 32, false>>(v_sel, QN_K_KNN_SELECT, (uint32_t)owner->knn_lds_pad); plan.add<KnnHistK<true, 32, false>>(v_lst, QN_K_KNN_COV); }
+  } else {
+    if (owner->knn_mm) { plan.add<KnnHistK<false, 48>>(v_sel, QN_K_KNN_SELECT); plan.add<KnnHistK<true, 48>>(v_lst, QN_K_KNN_COV); }
+    else { plan.add<KnnHistK<false, 48, false>>(v_sel, QN_K_KNN_SELECT); plan.add<KnnHistK<true, 48, false>>(v_lst, QN_K_KNN_COV); }
+  }
   plan.add<KnnSingleK>(v_single, QN_K_KNN_COV);
   if (k <= 16) plan.add<KnnCovK<16, true, 4>>(v_tail, QN_K_KNN_COV); else if (k <= 20) plan.add<KnnCovK<20, true, 4>>(v_tail, QN_K_KNN_COV); else if (k <= 24) plan.add<KnnCovK<24, true, 4>>(v_tail, QN_K_KNN_COV); else plan.add<KnnCovK<32, true, 4>>(v_tail, QN_K_KNN_COV);
   plan.add<CovFromIdxK>(v_cov, QN_K_KNN_COV);

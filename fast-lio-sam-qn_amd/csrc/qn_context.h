@@ -18,6 +18,9 @@ struct CloudBuf {                       // one point cloud, resident in HBM
   qn::GridView grid{};                  // pointers + the pointer to the device-side numbers (`dims`); the numeric fields are NOT valid on the host
   qn::GridDims* dims = nullptr;         // device: the grid's numbers (k_grid_dims)
   qn::GridDims* dims_host = nullptr;    // pinned mirror, copied behind every grid build: valid after the next synchronisation of the stream that built the grid
+  // the k-NN index table the covariances were formed from (read-back: qn_gicp_get_lane_knn): the context buffer that holds it - knn_idx or knn_idx2, which the pair pipeline
+  // (TargetScope) and the batched target (ScratchSwap) swap - and its k.  Null once the cloud changed or another table went into that buffer (note_knn_table)
+  const int32_t* knn_tab = nullptr; int knn_k = 0;
 };
 
 struct ProfSpan { int family; hipEvent_t a, b; int count; };      // count: registrations a batched launch (k_lanes) carried - the family's `launches` are counted per registration
@@ -102,7 +105,9 @@ struct qn_ctx {
                                         // kernel for the large early steps, but it saves four launches and the persistent kernel starts sooner (align 0.506 -> 0.477 ms; batches: 2268 -> 2031 /s)
   bool fused_final = true;              // closing pass (last controller step + fitness sweep + output cloud) in one launch
   int knn_rounds = 2;                   // rounds of the first k-NN pass before a query goes to the list pass
-  int knn_mm = 1;                       // k-NN selection: squared distances of the two passes on the matrix cores (v_mfma_f32_16x16x4_f32 screen + exact re-evaluation of the listed candidates); 0 = VALU scoring (k <= 24 only)
+  int knn_mm = 1;                       // k-NN selection: squared distances of both histogram passes on the matrix cores (v_mfma_f32_16x16x4_f32 screen + exact re-evaluation of the listed candidates) in
+                                        // every k_knn_hist / KnnHistK launch - selection and list pass, HCAP 32 and 48, classic and batched; 0 = VALU scoring in all of them (the one-query-per-wave and
+                                        // sorted-list passes behind them always score on the VALU)
   int knn_trips = 3;                    // batched launches: groups of 16 queries a wave of the k-NN selection pass serves (grid = n / 64 / knn_trips blocks)
   int knn_hist = 1;                     // 1: k-NN by histogram selection (wave_knn_hist), 0: sorted-list sink (wave_search + BestK)
   int big_blocks0 = 4096, fb_blocks0 = 512;   // grid of the list pass behind the first (unseeded) ticks: one-far-query-per-wave blocks, wave-stride leftover blocks

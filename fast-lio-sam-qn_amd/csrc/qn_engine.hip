@@ -103,6 +103,7 @@ extern "C" int qn_ctx_create(int device, uint32_t max_points, qn_ctx** out) { re
 static int ctx_create(int device, uint32_t max_points, hipStream_t shared_stream, qn_ctx** out) {
   if (!out || max_points == 0) return QN_ERR_INVALID_ARG;
   *out = nullptr;
+  if (max_points > QN_CTX_MAX_POINTS) return QN_ERR_CAPACITY;        // (the k-NN screen's 26-bit position field, qn_knn_hist.cuh)
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) return QN_ERR_NO_DEVICE;
   qn_ctx* c = new qn_ctx();
@@ -321,7 +322,7 @@ static GridLaunch prep_grid(qn_ctx* c, CloudBuf& b, const char* dsrc, uint32_t s
   L.stable = c->stable_cells;
   L.scat = ScatterK::Args{b.raw, n, b.cell_of_pt, b.cell_start, b.counts, L.stable ? b.sorted_tmp : b.sorted};
   L.stab = StableCellsK::Args{b.sorted_tmp, n, b.cell_of_pt, b.cell_start, b.sorted};
-  b.has_grid = true; b.has_cov = false;
+  b.has_grid = true; b.has_cov = false; b.knn_tab = nullptr;
   return L;
 }
 static int build_grid(qn_ctx* c, CloudBuf& b, const char* dsrc, uint32_t stride) {
@@ -433,10 +434,11 @@ static void launch_knn_cov(qn_ctx* c, CloudBuf& b, int k, int32_t* kidx, float* 
     const KnnLaunch L = prep_knn(c, b, k, kidx, kd2);
     constexpr int HCAP = KMAX <= 24 ? 32 : 48;      // pass-2 list capacity: 32 keeps the selection kernel at 4 waves/SIMD
     { ProfScope sel(c, QN_K_KNN_SELECT);
-      if (HCAP == 32 && !c->knn_mm) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_knn_hist<false, 32, false>), dim3(L.sel_nb), dim3(QN_KNN_BLOCK), 0, s, L.sel.g, L.sel.k, L.sel.r0, L.sel.max_rounds, L.sel.knn_idx, L.sel.knn_d2, L.sel.fb_list, L.sel.fb_count, L.sel.gen_list, L.sel.gen_count);
+      if (!c->knn_mm) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_knn_hist<false, HCAP, false>), dim3(L.sel_nb), dim3(QN_KNN_BLOCK), 0, s, L.sel.g, L.sel.k, L.sel.r0, L.sel.max_rounds, L.sel.knn_idx, L.sel.knn_d2, L.sel.fb_list, L.sel.fb_count, L.sel.gen_list, L.sel.gen_count);
       else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_knn_hist<false, HCAP>), dim3(L.sel_nb), dim3(QN_KNN_BLOCK), 0, s, L.sel.g, L.sel.k, L.sel.r0, L.sel.max_rounds, L.sel.knn_idx, L.sel.knn_d2, L.sel.fb_list, L.sel.fb_count, L.sel.gen_list, L.sel.gen_count); }
     ProfScope ps(c, QN_K_KNN_COV);
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_knn_hist<true, HCAP>), dim3(L.lst_nb), dim3(QN_KNN_BLOCK), 0, s, L.lst.g, L.lst.k, L.lst.r0, L.lst.max_rounds, L.lst.knn_idx, L.lst.knn_d2, L.lst.fb_list, L.lst.fb_count, L.lst.gen_list, L.lst.gen_count);
+    if (!c->knn_mm) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_knn_hist<true, HCAP, false>), dim3(L.lst_nb), dim3(QN_KNN_BLOCK), 0, s, L.lst.g, L.lst.k, L.lst.r0, L.lst.max_rounds, L.lst.knn_idx, L.lst.knn_d2, L.lst.fb_list, L.lst.fb_count, L.lst.gen_list, L.lst.gen_count);
+    else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_knn_hist<true, HCAP>), dim3(L.lst_nb), dim3(QN_KNN_BLOCK), 0, s, L.lst.g, L.lst.k, L.lst.r0, L.lst.max_rounds, L.lst.knn_idx, L.lst.knn_d2, L.lst.fb_list, L.lst.fb_count, L.lst.gen_list, L.lst.gen_count);
     hipLaunchKernelGGL(k_knn_single, dim3(L.single_nb), dim3(QN_BLOCK), 0, s, L.single.g, L.single.k, L.single.knn_idx, L.single.knn_d2, L.single.list, L.single.count, L.single.gen_list, L.single.gen_count);
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_knn_cov<KMAX, true, 4>), dim3(L.tail_nb), dim3(QN_BLOCK), 0, s, L.tail.g, L.tail.raw, L.tail.k, L.tail.r0, L.tail.max_rounds, L.tail.cov, L.tail.knn_idx, L.tail.knn_d2, L.tail.fb_list, L.tail.fb_count);
     hipLaunchKernelGGL(k_cov_from_idx, dim3(L.cov_nb), dim3(QN_BLOCK), 0, s, L.cov.raw, L.cov.sorted, L.cov.n, L.cov.k, L.cov.knn_idx, L.cov.nrm, L.cov.nrm_sorted, L.cov.rec, L.cov.list_counts);
@@ -452,6 +454,11 @@ static void launch_knn_cov(qn_ctx* c, CloudBuf& b, int k, int32_t* kidx, float* 
   const uint32_t nbp = (b.n + QN_BLOCK - 1) / QN_BLOCK;
   hipLaunchKernelGGL(k_cov_from_idx, dim3(nbp), dim3(QN_BLOCK), 0, s, b.raw, b.sorted, b.n, k, kidx, b.nrm,
                      &b == &c->cloud[0] ? c->nrm_s_sorted : (double*)nullptr, &b == &c->cloud[0] ? (TargetRec*)nullptr : c->tgt_rec, c->fb_count2);   // + the optimiser ticks' layouts
+}
+// cloud b's k-NN table now lives in the context buffer kidx (knn_idx or knn_idx2): the other cloud's table, if that buffer held it, is gone (qn_gicp_get_lane_knn)
+static void note_knn_table(qn_ctx* c, CloudBuf& b, const int32_t* kidx, int k) {
+  for (CloudBuf& o : c->cloud) if (&o != &b && o.knn_tab == kidx) o.knn_tab = nullptr;
+  b.knn_tab = kidx; b.knn_k = k;
 }
 static int compute_cov(qn_ctx* c, int which, int32_t* kidx, float* kd2) {
   if (!c || (which != 0 && which != 1)) return QN_ERR_INVALID_ARG;
@@ -469,6 +476,7 @@ static int compute_cov(qn_ctx* c, int which, int32_t* kidx, float* kd2) {
   else launch_knn_cov<32>(c, b, k, kidx, kd2);
   HIPCHK(c, hipGetLastError());
   b.has_cov = true;
+  if (kidx == c->knn_idx || kidx == c->knn_idx2) note_knn_table(c, b, kidx, k);     // (not the developer read-back's private table, qn_gicp_knn)
   return QN_OK;
 }
 extern "C" int qn_gicp_compute_covariances(qn_ctx* c, int which) { return compute_cov(c, which, c->knn_idx, nullptr); }
@@ -1097,6 +1105,37 @@ extern "C" int qn_gicp_get_covariances(qn_ctx* c, int which, double* out9) {
     o[0] = s[0]; o[1] = s[1]; o[2] = s[2]; o[3] = s[1]; o[4] = s[3]; o[5] = s[4]; o[6] = s[2]; o[7] = s[4]; o[8] = s[5];
   }
   return QN_OK;
+}
+
+// the k-NN table / covariances a registration lane actually used (lane convention of qn_gicp_get_lane_trace: lane 0 of a context without lanes is the context)
+static int lane_ctx(qn_ctx* c, uint32_t lane, qn_ctx** out) {
+  if (c->lanes.empty()) { if (lane != 0) return QN_ERR_NOT_READY; *out = c; return QN_OK; }
+  if (lane >= c->lanes.size()) return QN_ERR_INVALID_ARG;
+  *out = c->lanes[lane];
+  return QN_OK;
+}
+extern "C" int qn_gicp_get_lane_knn(qn_ctx* c, uint32_t lane, int which, int32_t* idx_out, uint32_t* n, int* k) {
+  if (c && join_target(c) != QN_OK) return QN_ERR_HIP;
+  if (!c || !n || !k || (which != 0 && which != 1)) return QN_ERR_INVALID_ARG;
+  *n = 0; *k = 0;
+  qn_ctx* l = nullptr;
+  { const int rc = lane_ctx(c, lane, &l); if (rc != QN_OK) return rc; }
+  const CloudBuf& b = l->cloud[which];
+  // (a lane's k is synchronised with its owner's at the next batch call: a table of another k than the owner's current one is not handed out)
+  if (!b.has_grid || !b.has_cov || !b.knn_tab || b.knn_k != c->params.k_correspondences) return QN_ERR_NOT_READY;
+  *n = b.n; *k = b.knn_k;
+  if (!idx_out) return QN_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipMemcpyAsync(idx_out, b.knn_tab, sizeof(int32_t) * (size_t)b.n * b.knn_k, hipMemcpyDeviceToHost, l->stream));
+  HIPCHK(c, hipStreamSynchronize(l->stream));
+  return clouds_valid(l);
+}
+extern "C" int qn_gicp_get_lane_covariances(qn_ctx* c, uint32_t lane, int which, double* cov9_out) {
+  if (!c) return QN_ERR_INVALID_ARG;
+  qn_ctx* l = nullptr;
+  { const int rc = lane_ctx(c, lane, &l); if (rc != QN_OK) return rc; }
+  if (l != c && join_target(c) != QN_OK) return QN_ERR_HIP;
+  return qn_gicp_get_covariances(l, which, cov9_out);
 }
 
 extern "C" int qn_gicp_knn(qn_ctx* c, int which, int k, int32_t* idx_out, float* d2_out) {

@@ -541,6 +541,23 @@ def lane_trace(ctx, lane):
     return np.array([[t.y0, t.lambda_, t.rho, t.max_dR, t.max_dt, t.inner, t.accepted] for t in buf[:n.value]]).reshape(-1, 7)
 
 
+def lane_knn(ctx, lane, which):
+    """qn_gicp_get_lane_knn: the k-NN index table (n x k int32, original point order, -1 = missing) cloud `which` of lane `lane` was last given its covariances from -
+    the table the registration used.  EngineError QN_ERR_NOT_READY once it is gone (cloud set anew, k changed, buffer reused for the other cloud, a borrowed source)"""
+    n = C.c_uint32(); k = C.c_int()
+    ctx.check(lib().qn_gicp_get_lane_knn(ctx.h, C.c_uint32(lane), C.c_int(which), None, C.byref(n), C.byref(k)))
+    idx = np.zeros((n.value, k.value), dtype=np.int32)
+    ctx.check(lib().qn_gicp_get_lane_knn(ctx.h, C.c_uint32(lane), C.c_int(which), _p(idx), C.byref(n), C.byref(k)))
+    return idx
+
+
+def lane_covariances(ctx, lane, which, n):
+    """qn_gicp_get_lane_covariances: the covariances cloud `which` (n points) of lane `lane` holds, n x 3 x 3"""
+    out = np.zeros((ctx.max_points, 3, 3))
+    ctx.check(lib().qn_gicp_get_lane_covariances(ctx.h, C.c_uint32(lane), C.c_int(which), _p(out)))
+    return out[:n].copy()
+
+
 class PairRecord(C.Structure):
     _fields_ = [("pair_id", C.c_int32), ("status", C.c_int32), ("valid", C.c_int32), ("converged", C.c_int32), ("iterations", C.c_int32),
                 ("reserved", C.c_int32), ("fitness", C.c_double), ("T", C.c_float * 16)]

@@ -93,6 +93,9 @@ enum {                     /* kernel families for qn_prof_get */
 };
 
 /* ---- lifetime ------------------------------------------------------------------------- */
+/* max_points: the largest cloud the context takes, at most QN_CTX_MAX_POINTS; a larger value returns QN_ERR_CAPACITY before anything is allocated
+ * (qn_multi_init inherits the limit).  The k-NN screen packs a point's position in the cell-sorted cloud into a 26-bit field (qn_knn_hist.cuh). */
+#define QN_CTX_MAX_POINTS (1u << 26)
 int  qn_ctx_create(int device, uint32_t max_points, qn_ctx** out);
 void qn_ctx_destroy(qn_ctx* ctx);
 const char* qn_status_str(int status);
@@ -129,6 +132,15 @@ int  qn_gicp_transformed_source(qn_ctx*, float* xyz_out, uint32_t stride_bytes);
 int  qn_gicp_get_trace(qn_ctx*, qn_iter_trace* out, uint32_t cap, uint32_t* n);
 /* the same for lane `lane` of the latest qn_gicp_align_batch run on this context (lane l of a run carries the l-th pair of that run) */
 int  qn_gicp_get_lane_trace(qn_ctx*, uint32_t lane, qn_iter_trace* out, uint32_t cap, uint32_t* n);
+/* The k-NN index table cloud `which` (QN_SOURCE / QN_TARGET) of lane `lane` was last given its covariances from - the table the registration used, not a
+ * fresh search: n x k int32 in the cloud's original point order, row i = the k nearest of point i in ascending (squared distance, index) order, -1 for a
+ * missing neighbour (a cloud of fewer than k points).  idx_out NULL: only *n and *k.  Indices only (the batched path keeps no distances).  Same lane
+ * convention as qn_gicp_get_lane_trace.  QN_ERR_NOT_READY when the table is gone: the cloud was set anew, k changed, or the buffer now holds the other
+ * cloud's table (the target's covariances overwrite the source's table unless the target was prepared on the second stream); also for a lane that borrowed
+ * its source from another lane of the run (the lending lane's table is the one to read). */
+int  qn_gicp_get_lane_knn(qn_ctx*, uint32_t lane, int which, int32_t* idx_out, uint32_t* n, int* k);
+/* qn_gicp_get_covariances of lane `lane` (n x 9 row-major 3x3, rebuilt from the normals the lane holds) */
+int  qn_gicp_get_lane_covariances(qn_ctx*, uint32_t lane, int which, double* cov9_out);
 
 /* LoopClosure::icpAlignment in one call (loop_closure.cpp:110-136): set x2, cov x2, align, score,
  * accept test `converged && score < score_thr` (loop_closure.cpp:129).  *valid receives is_valid_. */

@@ -22,6 +22,27 @@ def test_header_declares_the_reference_surface():
         assert s in syms
 
 
+def test_header_declares_the_lane_read_backs():
+    """the developer read-backs of what a registration lane used: iteration trace, k-NN tables, covariances (qn_gicp_get_lane_*), and their Python wrappers"""
+    syms = declared_symbols()
+    for s in ["qn_gicp_get_lane_trace", "qn_gicp_get_lane_knn", "qn_gicp_get_lane_covariances"]:
+        assert s in syms, s
+    from qn_amd import engine
+    for f in ["lane_trace", "lane_knn", "lane_covariances"]:
+        assert callable(getattr(engine, f, None)), f
+
+
+def test_context_capacity_is_refused_before_the_device_is_touched():
+    """max_points beyond QN_CTX_MAX_POINTS (= 2^26: the k-NN screen's 26-bit position field) is QN_ERR_CAPACITY - on a machine without a GPU too, so before any device call"""
+    txt = open(os.path.join(ROOT, "include", "qn_engine.h")).read()
+    assert re.search(r"#define\s+QN_CTX_MAX_POINTS\s+\(1u\s*<<\s*26\)", txt)
+    from qn_amd import engine
+    for n in ((1 << 26) + 1, 0xffffffff):
+        with pytest.raises(engine.EngineError) as ei:
+            engine.Context(n)
+        assert ei.value.status == engine.QN_ERR_CAPACITY
+
+
 def test_library_exports_every_declared_symbol():
     from qn_amd import build, engine
     build.build()

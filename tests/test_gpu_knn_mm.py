@@ -86,20 +86,22 @@ def test_coarse_and_fine_cells(oracle, cell):
 
 
 def test_matches_valu_scoring_at_full_size(eng):
-    """100k-point street scene: the matrix-core path and the VALU path (knn_mm 0) write the same tables."""
+    """100k-point street scene at k = 20 and 27: the matrix-core path and the VALU path (knn_mm 0: every histogram pass, selection and list, HCAP 32 and 48) write the
+    same tables."""
     engine, ctx = eng
     src, _, _ = synth.make_pair(2, 100000)
-    out = []
-    for mm in (1, 0):
-        ctx.debug_set("knn_mm", mm)
-        g = engine.NanoGICP(ctx); g.setInputSource(src)
-        out.append(g.knn(0, 20))
-    ctx.debug_set("knn_mm", 1)
-    assert np.array_equal(out[0][0], out[1][0]) and np.array_equal(out[0][1], out[1][1])
-    # brute-force spot check of 64 rows
-    rng = np.random.default_rng(0)
-    for i in rng.choice(len(src), 64, replace=False):
-        d = ((src.astype(np.float32) - src[i]) ** 2)
-        d2 = (d[:, 0] + d[:, 1]) + d[:, 2]
-        order = np.lexsort((np.arange(len(src)), d2))[:20]
-        assert np.array_equal(out[0][0][i], order.astype(np.int32)), i
+    for k in (20, 27):
+        out = []
+        for mm in (1, 0):
+            ctx.debug_set("knn_mm", mm)
+            g = engine.NanoGICP(ctx); g.setInputSource(src)
+            out.append(g.knn(0, k))
+        ctx.debug_set("knn_mm", 1)
+        assert np.array_equal(out[0][0], out[1][0]) and np.array_equal(out[0][1], out[1][1]), k
+        # brute-force spot check of 64 rows
+        rng = np.random.default_rng(0)
+        for i in rng.choice(len(src), 64, replace=False):
+            d = ((src.astype(np.float32) - src[i]) ** 2)
+            d2 = (d[:, 0] + d[:, 1]) + d[:, 2]
+            order = np.lexsort((np.arange(len(src)), d2))[:k]
+            assert np.array_equal(out[0][0][i], order.astype(np.int32)), (k, i)
