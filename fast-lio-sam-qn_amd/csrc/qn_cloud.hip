@@ -5,12 +5,13 @@
 // Keyframe clouds (PosePcd::pcd_, sensor frame, immutable: include/pose_pcd.hpp:7-19) are uploaded ONCE into a store
 // and stay resident in HBM; a loop attempt then assembles its source / target clouds on the device and hands the
 // device pointers to qn_icp_alignment_device / the batch API - no point cloud crosses PCIe per attempt.
-// VoxelGrid: 64-bit keys (leaf index << 32 | point index) are sorted by leaf index with a hand-written STABLE LSD radix
-// sort (8-bit digits, only as many passes as the leaf grid has bits; the input is in ascending point order and stability
-// keeps it so inside every leaf), leaf heads are compacted with the engine's own scan kernels and one thread per leaf sums
-// its points in ascending point order in f32 - the order the oracle fixes (PCL's own order inside a leaf is unspecified).
-// The corrected global map (qn_kf_build_map, fast_lio_sam_qn.cpp:302-316, 398-411, 435-448) reuses the store: every keyframe in one
-// transform launch, intensity carried in .w, a radix sort with 4096-key tiles, its own output slot.
+// ONE voxel-grid pipeline (voxel_submaps) serves all three entry points, each with its own output slot: qn_kf_assemble (one submap, slot
+// 0 / 1), qn_kf_build_map (the corrected global map, fast_lio_sam_qn.cpp:302-316, 398-411, 435-448: one submap, intensity averaged) and
+// qn_kf_assemble_batch (S submaps).  Every listed keyframe is transformed in one launch; one host sync brings each submap's bounding box
+// back to size its grid.  VoxelGrid: 64-bit keys ((submap, leaf) << 32 | point index) are sorted with a hand-written STABLE LSD radix
+// sort (8-bit digits, only as many passes as the keys have bits; the input is in ascending point order and stability keeps it so inside
+// every leaf), leaf heads are compacted with the engine's own scan kernels and one thread per leaf sums its points in ascending point
+// order in f32 - the order the oracle fixes (PCL's own order inside a leaf is unspecified).  A second sync brings the leaf counts back.
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include <string>
@@ -22,92 +23,7 @@
 
 namespace qn {
 
-__global__ void k_kf_transform(const float4* __restrict__ in, uint32_t n, const double* __restrict__ T, float4* __restrict__ out) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const float4 p = in[i]; const double x = p.x, y = p.y, z = p.z;
-  out[i] = make_float4((float)(((T[0] * x + T[1] * y) + T[2] * z) + T[3]), (float)(((T[4] * x + T[5] * y) + T[6] * z) + T[7]),
-                       (float)(((T[8] * x + T[9] * y) + T[10] * z) + T[11]), 1.0f);
-}
-// pcl::VoxelGrid on a cloud that is not dense (utilities.hpp:38-51 -> pcl::VoxelGrid::applyFilter: `if (!input_->is_dense) if (!isXYZFinite(p)) continue;`,
-// getMinMax3D skips them as well): non-finite points take no part - they are dropped by a stable compaction (flag, exclusive scan, scatter).
-__global__ void k_finite_flags(const float4* __restrict__ pts, uint32_t n, uint32_t* __restrict__ flag) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const float4 p = pts[i];
-  flag[i] = (isfinite(p.x) && isfinite(p.y) && isfinite(p.z)) ? 1u : 0u;
-}
-__global__ void k_compact_finite(const float4* __restrict__ pts, uint32_t n, const uint32_t* __restrict__ flag, const uint32_t* __restrict__ pos, float4* __restrict__ out) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  if (flag[i]) out[pos[i]] = pts[i];
-}
 struct VoxelDims { float inv; int minb[3]; int div0, div01; };
-__global__ void k_voxel_keys(const float4* __restrict__ pts, uint32_t n, VoxelDims d, unsigned long long* __restrict__ keys) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const float4 p = pts[i];
-  const int i0 = (int)(floorf(p.x * d.inv) - (float)d.minb[0]);
-  const int i1 = (int)(floorf(p.y * d.inv) - (float)d.minb[1]);
-  const int i2 = (int)(floorf(p.z * d.inv) - (float)d.minb[2]);
-  keys[i] = ((unsigned long long)(uint32_t)(i0 + i1 * d.div0 + i2 * d.div01) << 32) | i;
-}
-// ---- stable LSD radix sort pass over bits [shift, shift + 8) of the 64-bit key; tile = one 256-thread block, one key per thread
-__global__ void __launch_bounds__(QN_BLOCK) k_radix_hist(const unsigned long long* __restrict__ keys, uint32_t n, int shift, uint32_t nblocks, uint32_t* __restrict__ hist) {
-  __shared__ uint32_t h[256];
-  h[threadIdx.x] = 0;
-  __syncthreads();
-  const uint32_t i = blockIdx.x * QN_BLOCK + threadIdx.x;
-  if (i < n) atomicAdd(&h[(uint32_t)(keys[i] >> shift) & 255u], 1u);
-  __syncthreads();
-  hist[threadIdx.x * nblocks + blockIdx.x] = h[threadIdx.x];             // digit-major: the scan yields global offsets directly
-}
-__global__ void __launch_bounds__(QN_BLOCK) k_radix_scatter(const unsigned long long* __restrict__ keys, uint32_t n, int shift, uint32_t nblocks,
-                                                            const uint32_t* __restrict__ offs, unsigned long long* __restrict__ out) {
-  __shared__ uint32_t wcount[QN_BLOCK / 64][256];
-  for (int t = threadIdx.x; t < (QN_BLOCK / 64) * 256; t += QN_BLOCK) (&wcount[0][0])[t] = 0;
-  __syncthreads();
-  const uint32_t i = blockIdx.x * QN_BLOCK + threadIdx.x;
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const bool valid = i < n;
-  const unsigned long long key = valid ? keys[i] : 0ull;
-  const uint32_t d = (uint32_t)(key >> shift) & 255u;
-  unsigned long long same = __ballot(valid);                            // lanes of this wave holding the same digit
-#pragma unroll
-  for (int b = 0; b < 8; b++) { const unsigned long long m = __ballot((d >> b) & 1u); same &= ((d >> b) & 1u) ? m : ~m; }
-  const uint32_t rank = (uint32_t)__popcll(same & ((1ull << lane) - 1ull));
-  if (valid && rank == 0) wcount[wid][d] = (uint32_t)__popcll(same);
-  __syncthreads();
-  if (!valid) return;
-  uint32_t before = 0;
-  for (int w = 0; w < wid; w++) before += wcount[w][d];
-  out[offs[d * nblocks + blockIdx.x] + before + rank] = key;
-}
-
-__global__ void k_leaf_flags(const unsigned long long* __restrict__ keys, uint32_t n, uint32_t* __restrict__ flag) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  flag[i] = (i == 0 || (keys[i] >> 32) != (keys[i - 1] >> 32)) ? 1u : 0u;
-}
-__global__ void k_leaf_heads(const uint32_t* __restrict__ flag, const uint32_t* __restrict__ pos, uint32_t n, uint32_t* __restrict__ heads) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  if (flag[i]) heads[pos[i]] = i;
-  if (i == n - 1) heads[pos[n]] = n;          // pos[n] = number of leaves (exclusive scan total)
-}
-__global__ void k_leaf_centroids(const float4* __restrict__ pts, const unsigned long long* __restrict__ keys, const uint32_t* __restrict__ heads,
-                                 const uint32_t* __restrict__ nleaf_ptr, float4* __restrict__ out) {
-  const uint32_t m = blockIdx.x * blockDim.x + threadIdx.x;
-  if (m >= *nleaf_ptr) return;
-  const uint32_t a = heads[m], b = heads[m + 1];
-  float sx = 0.f, sy = 0.f, sz = 0.f;
-  for (uint32_t t = a; t < b; t++) { const float4 p = pts[(uint32_t)keys[t]]; sx = sx + p.x; sy = sy + p.y; sz = sz + p.z; }
-  const float cnt = (float)(b - a);
-  out[m] = make_float4(sx / cnt, sy / cnt, sz / cnt, 1.0f);
-}
-
-// ---- corrected global map (fast_lio_sam_qn.cpp:302-316, 398-411, 435-448): transformPcd of EVERY keyframe with its corrected
-// pose, concatenation, voxelizePcd at save_voxel_resolution - xyz AND intensity (PointXYZI; VoxelGrid averages all fields).
 // Sized for 10^3 keyframes / 3e7 points: one transform launch for all keyframes, radix tiles of QN_MAP_TILE keys per block.
 #define QN_MAP_TILE 4096
 #define QN_MAP_ITEMS (QN_MAP_TILE / QN_BLOCK)
@@ -116,13 +32,28 @@ __device__ __forceinline__ int wave_sum_i(int v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
   return v;
 }
+// the block's box (ordered ints) of its finite points and its non-finite count -> *dst, written by thread 0 (wave reductions, then one
+// LDS row per wave in a fixed order: deterministic, no atomics).  Every thread of the block must call it.
+__device__ __forceinline__ void block_bbox(int (&mn)[3], int (&mx)[3], int bad, BBoxOut* dst) {
+  __shared__ int smn[QN_BLOCK / 64][3], smx[QN_BLOCK / 64][3], sbad[QN_BLOCK / 64];
+#pragma unroll
+  for (int d = 0; d < 3; d++) { mn[d] = wave_min_i(mn[d]); mx[d] = wave_max_i(mx[d]); }
+  bad = wave_sum_i(bad);
+  const int wid = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) { for (int d = 0; d < 3; d++) { smn[wid][d] = mn[d]; smx[wid][d] = mx[d]; } sbad[wid] = bad; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < QN_BLOCK / 64; w++) { for (int d = 0; d < 3; d++) { mn[d] = min(mn[d], smn[w][d]); mx[d] = max(mx[d], smx[w][d]); } bad += sbad[w]; }
+    BBoxOut r; for (int d = 0; d < 3; d++) { r.mn[d] = mn[d]; r.mx[d] = mx[d]; } r.nonfinite = (uint32_t)bad;
+    *dst = r;
+  }
+}
 struct MapKf { const float4* src; uint32_t off, n, blk0, has_i; };     // one listed keyframe: its concatenation offset, first tile, pose = its list position
-// transformPcd of every listed keyframe in ONE launch: tile b belongs to keyframe blk_kf[b] (the same f64 arithmetic and order as
-// k_kf_transform, so xyz is bit-identical to qn_kf_assemble's); intensity = the resident .w for qn_kf_add_xyzi keyframes, 0 for
-// qn_kf_add ones.  Fused: the tile's bounding box of the finite points and its count of non-finite ones -> part[b].
+// transformPcd of every listed keyframe in ONE launch: tile b belongs to keyframe blk_kf[b] (f64 arithmetic, row by row in the order
+// ((T0 x + T1 y) + T2 z) + T3); intensity = the resident .w for qn_kf_add_xyzi keyframes, 0 for qn_kf_add ones.  Fused: the tile's
+// bounding box of the finite points and its count of non-finite ones -> part[b].
 __global__ void __launch_bounds__(QN_BLOCK) k_map_transform(const MapKf* __restrict__ kfs, const uint32_t* __restrict__ blk_kf, const double* __restrict__ poses,
                                                             float4* __restrict__ out, BBoxOut* __restrict__ part) {
-  __shared__ int smn[QN_BLOCK / 64][3], smx[QN_BLOCK / 64][3], sbad[QN_BLOCK / 64];
   const uint32_t k = blk_kf[blockIdx.x];
   const MapKf f = kfs[k];
   const double* T = poses + 16 * (size_t)k;
@@ -142,54 +73,7 @@ __global__ void __launch_bounds__(QN_BLOCK) k_map_transform(const MapKf* __restr
     mn[0] = min(mn[0], ox); mn[1] = min(mn[1], oy); mn[2] = min(mn[2], oz);
     mx[0] = max(mx[0], ox); mx[1] = max(mx[1], oy); mx[2] = max(mx[2], oz);
   }
-#pragma unroll
-  for (int d = 0; d < 3; d++) { mn[d] = wave_min_i(mn[d]); mx[d] = wave_max_i(mx[d]); }
-  bad = wave_sum_i(bad);
-  const int wid = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) { for (int d = 0; d < 3; d++) { smn[wid][d] = mn[d]; smx[wid][d] = mx[d]; } sbad[wid] = bad; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int w = 1; w < QN_BLOCK / 64; w++) { for (int d = 0; d < 3; d++) { mn[d] = min(mn[d], smn[w][d]); mx[d] = max(mx[d], smx[w][d]); } bad += sbad[w]; }
-    BBoxOut r; for (int d = 0; d < 3; d++) { r.mn[d] = mn[d]; r.mx[d] = mx[d]; } r.nonfinite = (uint32_t)bad;
-    part[blockIdx.x] = r;
-  }
-}
-// the per-tile partials -> one box and the total number of non-finite points (one block; deterministic, no atomics)
-__global__ void __launch_bounds__(QN_BLOCK) k_map_bbox_reduce(const BBoxOut* __restrict__ part, uint32_t nb, BBoxOut* __restrict__ out) {
-  __shared__ int smn[QN_BLOCK / 64][3], smx[QN_BLOCK / 64][3], sbad[QN_BLOCK / 64];
-  int mn[3] = {0x7fffffff, 0x7fffffff, 0x7fffffff}, mx[3] = {(int)0x80000000, (int)0x80000000, (int)0x80000000};
-  int bad = 0;
-  for (uint32_t b = threadIdx.x; b < nb; b += QN_BLOCK) {
-    const BBoxOut r = part[b];
-    for (int d = 0; d < 3; d++) { mn[d] = min(mn[d], r.mn[d]); mx[d] = max(mx[d], r.mx[d]); }
-    bad += (int)r.nonfinite;
-  }
-#pragma unroll
-  for (int d = 0; d < 3; d++) { mn[d] = wave_min_i(mn[d]); mx[d] = wave_max_i(mx[d]); }
-  bad = wave_sum_i(bad);
-  const int wid = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) { for (int d = 0; d < 3; d++) { smn[wid][d] = mn[d]; smx[wid][d] = mx[d]; } sbad[wid] = bad; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int w = 1; w < QN_BLOCK / 64; w++) { for (int d = 0; d < 3; d++) { mn[d] = min(mn[d], smn[w][d]); mx[d] = max(mx[d], smx[w][d]); } bad += sbad[w]; }
-    BBoxOut r; for (int d = 0; d < 3; d++) { r.mn[d] = mn[d]; r.mx[d] = mx[d]; } r.nonfinite = (uint32_t)bad;
-    *out = r;
-  }
-}
-// leaf keys as k_voxel_keys computes them; a non-finite point gets the leaf `sentinel` (= number of cells, past every real leaf), so the
-// stable sort moves it behind all finite points in its original order and the leaf pass simply stops before it (no compaction pass)
-__global__ void k_map_keys(const float4* __restrict__ pts, uint32_t n, VoxelDims d, uint32_t sentinel, unsigned long long* __restrict__ keys) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const float4 p = pts[i];
-  uint32_t leaf = sentinel;
-  if (isfinite(p.x) && isfinite(p.y) && isfinite(p.z)) {
-    const int i0 = (int)(floorf(p.x * d.inv) - (float)d.minb[0]);
-    const int i1 = (int)(floorf(p.y * d.inv) - (float)d.minb[1]);
-    const int i2 = (int)(floorf(p.z * d.inv) - (float)d.minb[2]);
-    leaf = (uint32_t)(i0 + i1 * d.div0 + i2 * d.div01);
-  }
-  keys[i] = ((unsigned long long)leaf << 32) | i;
+  block_bbox(mn, mx, bad, part + blockIdx.x);
 }
 // lanes of this wave whose digit equals mine (8 ballots), restricted to `valid` lanes
 __device__ __forceinline__ unsigned long long match_digit8(uint32_t d, bool valid) {
@@ -198,16 +82,18 @@ __device__ __forceinline__ unsigned long long match_digit8(uint32_t d, bool vali
   for (int b = 0; b < 8; b++) { const unsigned long long m = __ballot((d >> b) & 1u); same &= ((d >> b) & 1u) ? m : ~m; }
   return same;
 }
-// ---- stable LSD radix pass over bits [shift, shift + 8), QN_MAP_TILE keys per block: digit histogram in LDS (one LDS add per distinct
-// digit of a wave, so a tile whose keys share their high digits does not serialise on one bank) ...
+// ---- stable LSD radix pass over bits [shift, shift + 8), kItems * QN_BLOCK keys per block (kItems = QN_MAP_ITEMS, or 1 for a small sort
+// that would otherwise run on a handful of blocks): digit histogram in LDS (one LDS add per distinct digit of a wave, so a tile whose keys
+// share their high digits does not serialise on one bank) ...
+template <int kItems>
 __global__ void __launch_bounds__(QN_BLOCK) k_map_radix_hist(const unsigned long long* __restrict__ keys, uint32_t n, int shift, uint32_t nblocks, uint32_t* __restrict__ hist) {
   __shared__ uint32_t h[256];
   h[threadIdx.x] = 0;
   __syncthreads();
-  const uint32_t base = blockIdx.x * QN_MAP_TILE + threadIdx.x;
+  const uint32_t base = blockIdx.x * (kItems * QN_BLOCK) + threadIdx.x;
   const int lane = threadIdx.x & 63;
 #pragma unroll 4
-  for (int j = 0; j < QN_MAP_ITEMS; j++) {
+  for (int j = 0; j < kItems; j++) {
     const uint32_t i = base + j * QN_BLOCK;
     const bool valid = i < n;
     const uint32_t d = valid ? (uint32_t)(keys[i] >> shift) & 255u : 0u;
@@ -217,22 +103,23 @@ __global__ void __launch_bounds__(QN_BLOCK) k_map_radix_hist(const unsigned long
   __syncthreads();
   hist[threadIdx.x * nblocks + blockIdx.x] = h[threadIdx.x];             // digit-major: the scan yields global offsets directly
 }
-// ... and the scatter: the tile is ranked in QN_MAP_ITEMS rounds of QN_BLOCK consecutive keys (round order = key order, wave order
-// inside a round, lane order inside a wave: stable), each digit's running output position kept in LDS across the rounds.
+// ... and the scatter: the tile is ranked in kItems rounds of QN_BLOCK consecutive keys (round order = key order, wave order inside a
+// round, lane order inside a wave: stable), each digit's running output position kept in LDS across the rounds.
+template <int kItems>
 __global__ void __launch_bounds__(QN_BLOCK) k_map_radix_scatter(const unsigned long long* __restrict__ keys, uint32_t n, int shift, uint32_t nblocks,
                                                                 const uint32_t* __restrict__ offs, unsigned long long* __restrict__ out) {
   __shared__ uint32_t wcount[QN_BLOCK / 64][256];
   __shared__ uint32_t run[256];
   for (int w = 0; w < QN_BLOCK / 64; w++) wcount[w][threadIdx.x] = 0;
   run[threadIdx.x] = offs[threadIdx.x * nblocks + blockIdx.x];
-  const uint32_t base = blockIdx.x * QN_MAP_TILE + threadIdx.x;
+  const uint32_t base = blockIdx.x * (kItems * QN_BLOCK) + threadIdx.x;
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  unsigned long long kv[QN_MAP_ITEMS];
+  unsigned long long kv[kItems];
 #pragma unroll
-  for (int j = 0; j < QN_MAP_ITEMS; j++) { const uint32_t i = base + j * QN_BLOCK; kv[j] = i < n ? keys[i] : 0ull; }
+  for (int j = 0; j < kItems; j++) { const uint32_t i = base + j * QN_BLOCK; kv[j] = i < n ? keys[i] : 0ull; }
   __syncthreads();
 #pragma unroll
-  for (int j = 0; j < QN_MAP_ITEMS; j++) {
+  for (int j = 0; j < kItems; j++) {
     const bool valid = base + j * QN_BLOCK < n;
     const uint32_t d = (uint32_t)(kv[j] >> shift) & 255u;
     const unsigned long long same = match_digit8(d, valid);
@@ -251,17 +138,6 @@ __global__ void __launch_bounds__(QN_BLOCK) k_map_radix_scatter(const unsigned l
     __syncthreads();
   }
 }
-// one thread per leaf: f32 sums of x, y, z, intensity in ascending concatenation order, each / (float)count (a NaN intensity poisons its leaf's)
-__global__ void k_map_centroids(const float4* __restrict__ pts, const unsigned long long* __restrict__ keys, const uint32_t* __restrict__ heads,
-                                const uint32_t* __restrict__ nleaf_ptr, float4* __restrict__ out) {
-  const uint32_t m = blockIdx.x * blockDim.x + threadIdx.x;
-  if (m >= *nleaf_ptr) return;
-  const uint32_t a = heads[m], b = heads[m + 1];
-  float sx = 0.f, sy = 0.f, sz = 0.f, si = 0.f;
-  for (uint32_t t = a; t < b; t++) { const float4 p = pts[(uint32_t)keys[t]]; sx = sx + p.x; sy = sy + p.y; sz = sz + p.z; si = si + p.w; }
-  const float cnt = (float)(b - a);
-  out[m] = make_float4(sx / cnt, sy / cnt, sz / cnt, si / cnt);
-}
 // pack a strided PointXYZI-like host layout into float4 (x, y, z, intensity)
 __global__ void k_pack_xyzi(const char* __restrict__ in, uint32_t stride, uint32_t ioff, uint32_t n, float4* __restrict__ out) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -271,14 +147,12 @@ __global__ void k_pack_xyzi(const char* __restrict__ in, uint32_t stride, uint32
   out[i] = make_float4(p[0], p[1], p[2], *(const float*)(r + ioff));
 }
 
-// ---- many loop-closure submaps in one pass (qn_kf_assemble_batch): the qn_kf_build_map structure with the submap as one more key field.
-// The listed keyframes of all submaps are transformed by k_map_transform (one launch; tiles never straddle keyframes, so a submap owns
-// a contiguous tile range and a contiguous point range [p0, p1)).  Keys are ((seg << L | leaf) << 32 | point index): one stable sort
-// orders every submap's points by leaf, finite points of a submap first (its non-finite ones carry the sentinel leaf).
+// ---- the submaps of one call.  The listed keyframes of all submaps are transformed by k_map_transform (one launch; tiles never straddle
+// keyframes, so a submap owns a contiguous tile range and a contiguous point range [p0, p1)).  Keys are ((seg << L | leaf) << 32 | point
+// index): one stable sort orders every submap's points by leaf, finite points of a submap first (its non-finite ones carry the sentinel leaf).
 struct BatchSeg { VoxelDims vd; uint32_t p0, p1, nvox, sentinel, prefix, tripped; };  // nvox: finite points that are voxelized (0 if tripped / empty)
 // one block per submap over its tile range: the box of its finite points and its non-finite count, in a fixed order (no atomics)
 __global__ void __launch_bounds__(QN_BLOCK) k_seg_bbox_reduce(const BBoxOut* __restrict__ part, const uint32_t* __restrict__ tile_off, BBoxOut* __restrict__ out) {
-  __shared__ int smn[QN_BLOCK / 64][3], smx[QN_BLOCK / 64][3], sbad[QN_BLOCK / 64];
   int mn[3] = {0x7fffffff, 0x7fffffff, 0x7fffffff}, mx[3] = {(int)0x80000000, (int)0x80000000, (int)0x80000000};
   int bad = 0;
   const uint32_t b1 = tile_off[blockIdx.x + 1];
@@ -287,87 +161,79 @@ __global__ void __launch_bounds__(QN_BLOCK) k_seg_bbox_reduce(const BBoxOut* __r
     for (int d = 0; d < 3; d++) { mn[d] = min(mn[d], r.mn[d]); mx[d] = max(mx[d], r.mx[d]); }
     bad += (int)r.nonfinite;
   }
-#pragma unroll
-  for (int d = 0; d < 3; d++) { mn[d] = wave_min_i(mn[d]); mx[d] = wave_max_i(mx[d]); }
-  bad = wave_sum_i(bad);
-  const int wid = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) { for (int d = 0; d < 3; d++) { smn[wid][d] = mn[d]; smx[wid][d] = mx[d]; } sbad[wid] = bad; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int w = 1; w < QN_BLOCK / 64; w++) { for (int d = 0; d < 3; d++) { mn[d] = min(mn[d], smn[w][d]); mx[d] = max(mx[d], smx[w][d]); } bad += sbad[w]; }
-    BBoxOut r; for (int d = 0; d < 3; d++) { r.mn[d] = mn[d]; r.mx[d] = mx[d]; } r.nonfinite = (uint32_t)bad;
-    out[blockIdx.x] = r;
-  }
+  block_bbox(mn, mx, bad, out + blockIdx.x);
 }
-// keys, one block per tile: leaf as k_voxel_keys computes it; the submap's sentinel for a non-finite point; leaf 0 for every finite point of a
-// submap whose guard tripped (the stable sort then keeps them in concatenation order for the pass-through gather)
+// the per-position kernels below run QN_MAP_ITEMS blocks per tile, one position per thread (one block per tile would walk 16 positions per
+// thread: latency-bound on a small cloud); block b covers positions [(b % QN_MAP_ITEMS) * QN_BLOCK, + QN_BLOCK) of tile b / QN_MAP_ITEMS
+__device__ __forceinline__ uint32_t tile_pos(const MapKf& f) {
+  return (blockIdx.x / QN_MAP_ITEMS - f.blk0) * QN_MAP_TILE + (blockIdx.x % QN_MAP_ITEMS) * QN_BLOCK + threadIdx.x;
+}
+// keys, one position per thread: pcl::VoxelGrid's leaf index of a finite point from the submap's grid; the submap's sentinel for a non-finite
+// point (the stable sort moves it behind all finite points, in its original order, and the leaf pass stops before it: no compaction pass);
+// leaf 0 for every finite point of a submap whose guard tripped (the stable sort then keeps them in concatenation order for the gather)
 __global__ void __launch_bounds__(QN_BLOCK) k_batch_keys(const MapKf* __restrict__ kfs, const uint32_t* __restrict__ blk_kf, const uint32_t* __restrict__ kf_seg,
                                                          const BatchSeg* __restrict__ segs, const float4* __restrict__ pts, unsigned long long* __restrict__ keys) {
-  const uint32_t k = blk_kf[blockIdx.x];
+  const uint32_t k = blk_kf[blockIdx.x / QN_MAP_ITEMS];
   const MapKf f = kfs[k];
+  const uint32_t i = tile_pos(f);
+  if (i >= f.n) return;
   const BatchSeg sg = segs[kf_seg[k]];
-  const uint32_t base = (blockIdx.x - f.blk0) * QN_MAP_TILE;
-  for (int j = 0; j < QN_MAP_ITEMS; j++) {
-    const uint32_t i = base + j * QN_BLOCK + threadIdx.x;
-    if (i >= f.n) break;
-    const uint32_t g = f.off + i;
-    const float4 p = pts[g];
-    uint32_t leaf = sg.sentinel;
-    if (isfinite(p.x) && isfinite(p.y) && isfinite(p.z)) {
-      leaf = 0;
-      if (!sg.tripped) {
-        const int i0 = (int)(floorf(p.x * sg.vd.inv) - (float)sg.vd.minb[0]);
-        const int i1 = (int)(floorf(p.y * sg.vd.inv) - (float)sg.vd.minb[1]);
-        const int i2 = (int)(floorf(p.z * sg.vd.inv) - (float)sg.vd.minb[2]);
-        leaf = (uint32_t)(i0 + i1 * sg.vd.div0 + i2 * sg.vd.div01);
-      }
+  const uint32_t g = f.off + i;
+  const float4 p = pts[g];
+  uint32_t leaf = sg.sentinel;
+  if (isfinite(p.x) && isfinite(p.y) && isfinite(p.z)) {
+    leaf = 0;
+    if (!sg.tripped) {
+      const int i0 = (int)(floorf(p.x * sg.vd.inv) - (float)sg.vd.minb[0]);
+      const int i1 = (int)(floorf(p.y * sg.vd.inv) - (float)sg.vd.minb[1]);
+      const int i2 = (int)(floorf(p.z * sg.vd.inv) - (float)sg.vd.minb[2]);
+      leaf = (uint32_t)(i0 + i1 * sg.vd.div0 + i2 * sg.vd.div01);
     }
-    keys[g] = ((unsigned long long)(sg.prefix | leaf) << 32) | g;
   }
+  keys[g] = ((unsigned long long)(sg.prefix | leaf) << 32) | g;
 }
-// leaf heads over the sorted keys, one block per tile of positions: a head is a voxelized position whose leaf differs from its predecessor's
+// leaf heads over the sorted keys: a head is a voxelized position whose leaf differs from its predecessor's
 // or that opens its submap (the submap field alone would not separate two submaps of different sort groups)
 __global__ void __launch_bounds__(QN_BLOCK) k_batch_leaf_flags(const MapKf* __restrict__ kfs, const uint32_t* __restrict__ blk_kf, const uint32_t* __restrict__ kf_seg,
                                                                const BatchSeg* __restrict__ segs, const unsigned long long* __restrict__ keys, uint32_t* __restrict__ flag) {
-  const uint32_t k = blk_kf[blockIdx.x];
+  const uint32_t k = blk_kf[blockIdx.x / QN_MAP_ITEMS];
   const MapKf f = kfs[k];
+  const uint32_t i = tile_pos(f);
+  if (i >= f.n) return;
   const BatchSeg sg = segs[kf_seg[k]];
-  const uint32_t base = (blockIdx.x - f.blk0) * QN_MAP_TILE, fe = sg.p0 + sg.nvox;
-  for (int j = 0; j < QN_MAP_ITEMS; j++) {
-    const uint32_t i = base + j * QN_BLOCK + threadIdx.x;
-    if (i >= f.n) break;
-    const uint32_t g = f.off + i;
-    flag[g] = (g < fe && (g == sg.p0 || (keys[g] >> 32) != (keys[g - 1] >> 32))) ? 1u : 0u;
-  }
+  const uint32_t g = f.off + i, fe = sg.p0 + sg.nvox;
+  flag[g] = (g < fe && (g == sg.p0 || (keys[g] >> 32) != (keys[g - 1] >> 32))) ? 1u : 0u;
 }
 // after the exclusive scan pos of the flags: leaf m = [heads[m], ends[m]) (its position in the output = its rank over all submaps)
 __global__ void __launch_bounds__(QN_BLOCK) k_batch_leaf_bounds(const MapKf* __restrict__ kfs, const uint32_t* __restrict__ blk_kf, const uint32_t* __restrict__ kf_seg,
                                                                 const BatchSeg* __restrict__ segs, const uint32_t* __restrict__ flag, const uint32_t* __restrict__ pos,
                                                                 uint32_t* __restrict__ heads, uint32_t* __restrict__ ends) {
-  const uint32_t k = blk_kf[blockIdx.x];
+  const uint32_t k = blk_kf[blockIdx.x / QN_MAP_ITEMS];
   const MapKf f = kfs[k];
+  const uint32_t i = tile_pos(f);
+  if (i >= f.n) return;
   const BatchSeg sg = segs[kf_seg[k]];
-  const uint32_t base = (blockIdx.x - f.blk0) * QN_MAP_TILE, fe = sg.p0 + sg.nvox;
-  for (int j = 0; j < QN_MAP_ITEMS; j++) {
-    const uint32_t i = base + j * QN_BLOCK + threadIdx.x;
-    if (i >= f.n) break;
-    const uint32_t g = f.off + i;
-    if (g >= fe) continue;
-    const uint32_t fl = flag[g], m = pos[g] + fl - 1;
-    if (fl) heads[m] = g;
-    if (g + 1 == fe || flag[g + 1]) ends[m] = g + 1;
-  }
+  const uint32_t g = f.off + i, fe = sg.p0 + sg.nvox;
+  if (g >= fe) return;
+  const uint32_t fl = flag[g], m = pos[g] + fl - 1;
+  if (fl) heads[m] = g;
+  if (g + 1 == fe || flag[g + 1]) ends[m] = g + 1;
 }
-// one thread per leaf: k_leaf_centroids' arithmetic (f32 sums in ascending concatenation order, / (float)count, w = 1)
+// one thread per leaf: f32 sums of x, y, z (and intensity when kIntensity) in ascending concatenation order, each / (float)count; w = the
+// mean intensity (a NaN intensity poisons its leaf's) or 1
+template <bool kIntensity>
 __global__ void k_batch_centroids(const float4* __restrict__ pts, const unsigned long long* __restrict__ keys, const uint32_t* __restrict__ heads,
                                   const uint32_t* __restrict__ ends, const uint32_t* __restrict__ nleaf_ptr, float4* __restrict__ out) {
   const uint32_t m = blockIdx.x * blockDim.x + threadIdx.x;
   if (m >= *nleaf_ptr) return;
   const uint32_t a = heads[m], b = ends[m];
-  float sx = 0.f, sy = 0.f, sz = 0.f;
-  for (uint32_t t = a; t < b; t++) { const float4 p = pts[(uint32_t)keys[t]]; sx = sx + p.x; sy = sy + p.y; sz = sz + p.z; }
+  float sx = 0.f, sy = 0.f, sz = 0.f, si = 0.f;
+  for (uint32_t t = a; t < b; t++) {
+    const float4 p = pts[(uint32_t)keys[t]]; sx = sx + p.x; sy = sy + p.y; sz = sz + p.z;
+    if (kIntensity) si = si + p.w;
+  }
   const float cnt = (float)(b - a);
-  out[m] = make_float4(sx / cnt, sy / cnt, sz / cnt, 1.0f);
+  out[m] = make_float4(sx / cnt, sy / cnt, sz / cnt, kIntensity ? si / cnt : 1.0f);
 }
 // each submap's first leaf and leaf count: res[2 s] = first, res[2 s + 1] = count
 __global__ void k_batch_counts(const BatchSeg* __restrict__ segs, uint32_t nseg, const uint32_t* __restrict__ pos, uint32_t* __restrict__ res) {
@@ -376,7 +242,7 @@ __global__ void k_batch_counts(const BatchSeg* __restrict__ segs, uint32_t nseg,
   const uint32_t a = pos[segs[s].p0];
   res[2 * s] = a; res[2 * s + 1] = pos[segs[s].p1] - a;
 }
-// a tripped submap: its finite points (the first n of its sorted range, in concatenation order), unfiltered, w = 1 as qn_kf_assemble copies them
+// a tripped submap under the finite-points rule: its finite points (the first n of its sorted range, in concatenation order), unfiltered, w = 1
 __global__ void k_batch_gather(const unsigned long long* __restrict__ keys, uint32_t n, const float4* __restrict__ pts, float4* __restrict__ out) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -386,22 +252,22 @@ __global__ void k_batch_gather(const unsigned long long* __restrict__ keys, uint
 
 }  // namespace qn
 
+// a device (or pinned host) buffer of `cap` elements, grown only by dev_grow / pin_grow (contents not kept), freed with the store
+template <typename T> struct Buf { T* p = nullptr; size_t cap = 0; };
+
 struct qn_kf_store {
   int device = 0; hipStream_t stream = nullptr;
   std::vector<float4*> clouds; std::vector<uint32_t> sizes; std::vector<uint8_t> has_i;   // has_i: added by qn_kf_add_xyzi (.w = intensity)
-  float4* concat = nullptr; unsigned long long* keys = nullptr; unsigned long long* keys_alt = nullptr;
-  uint32_t* flag = nullptr; uint32_t* pos = nullptr; uint32_t* heads = nullptr; uint32_t* sums = nullptr; size_t cap = 0;
-  uint32_t* hist = nullptr; uint32_t* hist_sums = nullptr;
-  float4* out[2] = {nullptr, nullptr}; size_t out_cap[2] = {0, 0}; uint32_t out_n[2] = {0, 0};
-  double* poses = nullptr; size_t poses_cap = 0;
-  qn::BBoxOut* bbox = nullptr; qn::BBoxOut* bbox_host = nullptr; uint32_t* count_host = nullptr; char* staging = nullptr; size_t staging_cap = 0;
-  float4* map = nullptr; size_t map_cap = 0; uint32_t map_n = 0;                          // the corrected global map: its own slot
-  qn::MapKf* map_kfs = nullptr; size_t map_kfs_cap = 0; uint32_t* map_blk = nullptr; size_t map_blk_cap = 0; qn::BBoxOut* map_part = nullptr; size_t map_part_cap = 0;
-  // qn_kf_assemble_batch: its own output slot (all submaps in one buffer) and tables
-  float4* bt_out = nullptr; size_t bt_out_cap = 0; std::vector<const float4*> bt_ptr; std::vector<uint32_t> bt_n;
-  uint32_t* bt_ends = nullptr; size_t bt_ends_cap = 0; uint32_t* bt_kf_seg = nullptr; size_t bt_kf_seg_cap = 0; uint32_t* bt_tile_off = nullptr; size_t bt_tile_off_cap = 0;
-  qn::BatchSeg* bt_segs = nullptr; size_t bt_segs_cap = 0; qn::BBoxOut* bt_bbox = nullptr; size_t bt_bbox_cap = 0; uint32_t* bt_res = nullptr; size_t bt_res_cap = 0;
-  qn::BBoxOut* bt_bbox_host = nullptr; size_t bt_bbox_host_cap = 0; uint32_t* bt_res_host = nullptr; size_t bt_res_host_cap = 0;
+  Buf<char> staging;                                                                         // qn_kf_add's upload
+  // scratch of the voxel-grid pipeline (voxel_submaps), shared by every entry point: per point, per scan block / radix histogram entry,
+  // per tile (its box), per submap (box, leaf range); the call's tables (Tables) in one device buffer, uploaded from one pinned buffer
+  Buf<float4> concat; Buf<unsigned long long> keys, keys_alt; Buf<uint32_t> flag, pos, heads, ends;
+  Buf<uint32_t> sums, hist, hist_sums; Buf<qn::BBoxOut> tile_box, seg_box; Buf<uint32_t> seg_res;
+  Buf<char> tab, tab_host; Buf<qn::BBoxOut> seg_box_host; Buf<uint32_t> seg_res_host;        // *_host: pinned
+  // the output slots: qn_kf_assemble's 0 / 1, the corrected global map, qn_kf_assemble_batch's (all submaps in one buffer)
+  Buf<float4> out[2]; uint32_t out_n[2] = {0, 0};
+  Buf<float4> map; uint32_t map_n = 0;
+  Buf<float4> bt_out; std::vector<const float4*> bt_ptr; std::vector<uint32_t> bt_n;
   // scratch of other translation units (the ray-caster, qn_sim.hip): see qn_kf_internal.h
   void* int_scratch[QN_KF_INT_SCRATCH] = {}; size_t int_scratch_cap[QN_KF_INT_SCRATCH] = {}; void* int_pinned = nullptr; size_t int_pinned_cap = 0;
   void* ext[QN_KF_INT_EXT] = {}; qn_kf_int_release_fn ext_release[QN_KF_INT_EXT] = {};      // state of other translation units (qn_sc.hip)
@@ -409,15 +275,33 @@ struct qn_kf_store {
 };
 #define KFCHK(s, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { (s)->last_error = std::string(#call) + " -> " + hipGetErrorString(e_); return QN_ERR_HIP; } } while (0)
 
+// b grown to at least `need` elements (by half again); false when the allocation failed (last_error says why, the caller returns QN_ERR_HIP)
+template <typename T> static bool dev_grow(qn_kf_store* s, Buf<T>& b, size_t need) {
+  if (need <= b.cap) return true;
+  (void)hipFree(b.p); b.p = nullptr; b.cap = 0;
+  const hipError_t e = hipMalloc((void**)&b.p, sizeof(T) * (need + need / 2));
+  if (e != hipSuccess) { b.p = nullptr; s->last_error = std::string("hipMalloc -> ") + hipGetErrorString(e); return false; }
+  b.cap = need + need / 2;
+  return true;
+}
+template <typename T> static bool pin_grow(qn_kf_store* s, Buf<T>& b, size_t need) {
+  if (need <= b.cap) return true;
+  if (b.p) (void)hipHostFree(b.p);
+  b.p = nullptr; b.cap = 0;
+  const hipError_t e = hipHostMalloc((void**)&b.p, sizeof(T) * (need + need / 2), hipHostMallocDefault);
+  if (e != hipSuccess) { b.p = nullptr; s->last_error = std::string("hipHostMalloc -> ") + hipGetErrorString(e); return false; }
+  b.cap = need + need / 2;
+  return true;
+}
+template <typename T> static void dev_free(Buf<T>& b) { (void)hipFree(b.p); b = Buf<T>{}; }
+
 extern "C" int qn_kf_store_create(int device, qn_kf_store** out) {
   if (!out) return QN_ERR_INVALID_ARG;
   *out = nullptr;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) return QN_ERR_NO_DEVICE;
   qn_kf_store* s = new qn_kf_store(); s->device = device;
-  if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess ||
-      hipMalloc(&s->bbox, sizeof(qn::BBoxOut)) != hipSuccess || hipHostMalloc(&s->bbox_host, sizeof(qn::BBoxOut), hipHostMallocDefault) != hipSuccess ||
-      hipHostMalloc(&s->count_host, sizeof(uint32_t), hipHostMallocDefault) != hipSuccess) { delete s; return QN_ERR_HIP; }
+  if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess) { delete s; return QN_ERR_HIP; }
   *out = s;
   return QN_OK;
 }
@@ -425,15 +309,13 @@ extern "C" void qn_kf_store_destroy(qn_kf_store* s) {
   if (!s) return;
   (void)hipSetDevice(s->device); if (s->stream) (void)hipStreamSynchronize(s->stream);
   for (float4* p : s->clouds) (void)hipFree(p);
-  (void)hipFree(s->concat); (void)hipFree(s->keys); (void)hipFree(s->keys_alt); (void)hipFree(s->flag); (void)hipFree(s->pos); (void)hipFree(s->heads); (void)hipFree(s->sums);
-  (void)hipFree(s->hist); (void)hipFree(s->hist_sums); (void)hipFree(s->out[0]); (void)hipFree(s->out[1]); (void)hipFree(s->poses); (void)hipFree(s->bbox); (void)hipFree(s->staging);
-  (void)hipFree(s->map); (void)hipFree(s->map_kfs); (void)hipFree(s->map_blk); (void)hipFree(s->map_part);
-  (void)hipFree(s->bt_out); (void)hipFree(s->bt_ends); (void)hipFree(s->bt_kf_seg); (void)hipFree(s->bt_tile_off); (void)hipFree(s->bt_segs); (void)hipFree(s->bt_bbox); (void)hipFree(s->bt_res);
+  dev_free(s->staging); dev_free(s->concat); dev_free(s->keys); dev_free(s->keys_alt); dev_free(s->flag); dev_free(s->pos); dev_free(s->heads); dev_free(s->ends);
+  dev_free(s->sums); dev_free(s->hist); dev_free(s->hist_sums); dev_free(s->tile_box); dev_free(s->seg_box); dev_free(s->seg_res); dev_free(s->tab);
+  dev_free(s->out[0]); dev_free(s->out[1]); dev_free(s->map); dev_free(s->bt_out);
   for (int k = 0; k < QN_KF_INT_EXT; k++) if (s->ext[k] && s->ext_release[k]) s->ext_release[k](s->ext[k]);
   for (void* p : s->int_scratch) (void)hipFree(p);
   if (s->int_pinned) (void)hipHostFree(s->int_pinned);
-  if (s->bt_bbox_host) (void)hipHostFree(s->bt_bbox_host); if (s->bt_res_host) (void)hipHostFree(s->bt_res_host);
-  if (s->bbox_host) (void)hipHostFree(s->bbox_host); if (s->count_host) (void)hipHostFree(s->count_host);
+  if (s->tab_host.p) (void)hipHostFree(s->tab_host.p); if (s->seg_box_host.p) (void)hipHostFree(s->seg_box_host.p); if (s->seg_res_host.p) (void)hipHostFree(s->seg_res_host.p);
   if (s->stream) (void)hipStreamDestroy(s->stream);
   delete s;
 }
@@ -445,11 +327,11 @@ static int kf_add(qn_kf_store* s, const float* xyz, uint32_t n, uint32_t stride,
   float4* d = nullptr;
   if (n) {
     const size_t bytes = (size_t)(n - 1) * stride + (ioff < 0 ? 12 : std::max(12, ioff + 4));
-    if (bytes > s->staging_cap) { (void)hipFree(s->staging); s->staging = nullptr; s->staging_cap = 0; KFCHK(s, hipMalloc(&s->staging, bytes + bytes / 2)); s->staging_cap = bytes + bytes / 2; }
+    if (!dev_grow(s, s->staging, bytes)) return QN_ERR_HIP;
     KFCHK(s, hipMalloc(&d, sizeof(float4) * n));
-    KFCHK(s, hipMemcpyAsync(s->staging, xyz, bytes, hipMemcpyHostToDevice, s->stream));
-    if (ioff < 0) hipLaunchKernelGGL(qn::k_pack_points, dim3((n + 255) / 256), dim3(256), 0, s->stream, s->staging, stride, n, d);
-    else hipLaunchKernelGGL(qn::k_pack_xyzi, dim3((n + 255) / 256), dim3(256), 0, s->stream, (const char*)s->staging, stride, (uint32_t)ioff, n, d);
+    KFCHK(s, hipMemcpyAsync(s->staging.p, xyz, bytes, hipMemcpyHostToDevice, s->stream));
+    if (ioff < 0) hipLaunchKernelGGL(qn::k_pack_points, dim3((n + 255) / 256), dim3(256), 0, s->stream, s->staging.p, stride, n, d);
+    else hipLaunchKernelGGL(qn::k_pack_xyzi, dim3((n + 255) / 256), dim3(256), 0, s->stream, (const char*)s->staging.p, stride, (uint32_t)ioff, n, d);
     const hipError_t e = hipStreamSynchronize(s->stream);
     if (e != hipSuccess) { (void)hipFree(d); s->last_error = std::string("kf_add -> ") + hipGetErrorString(e); return QN_ERR_HIP; }
   }
@@ -549,20 +431,6 @@ extern "C" int qn_kf_download_keyframe(qn_kf_store* s, int32_t id, float* xyzi_o
   return QN_OK;
 }
 
-static int kf_reserve(qn_kf_store* s, size_t n) {
-  if (n <= s->cap) return QN_OK;
-  (void)hipFree(s->concat); (void)hipFree(s->keys); (void)hipFree(s->keys_alt); (void)hipFree(s->flag); (void)hipFree(s->pos); (void)hipFree(s->heads); (void)hipFree(s->sums); (void)hipFree(s->hist); (void)hipFree(s->hist_sums);
-  s->concat = nullptr; s->keys = s->keys_alt = nullptr; s->flag = s->pos = s->heads = s->sums = nullptr; s->hist = s->hist_sums = nullptr; s->cap = 0;
-  const size_t c = n + n / 2 + 1024;
-  KFCHK(s, hipMalloc(&s->concat, sizeof(float4) * c)); KFCHK(s, hipMalloc(&s->keys, 8 * c)); KFCHK(s, hipMalloc(&s->keys_alt, 8 * c));
-  KFCHK(s, hipMalloc(&s->flag, 4 * (c + 1))); KFCHK(s, hipMalloc(&s->pos, 4 * (c + 1))); KFCHK(s, hipMalloc(&s->heads, 4 * (c + 2)));
-  KFCHK(s, hipMalloc(&s->sums, 4 * (c / (QN_BLOCK * QN_SCAN_ITEMS) + 2)));
-  const size_t hb = (c + QN_BLOCK - 1) / QN_BLOCK * 256;                   // digit-major block histograms of one radix pass
-  KFCHK(s, hipMalloc(&s->hist, 4 * (hb + 1))); KFCHK(s, hipMalloc(&s->hist_sums, 4 * (hb / (QN_BLOCK * QN_SCAN_ITEMS) + 2)));
-  s->cap = c;
-  return QN_OK;
-}
-
 // pcl::VoxelGrid::applyFilter's grid from the bounding box of the finite points: leaf-index origin and divisions, number of cells;
 // returns false when PCL's overflow guard trips (its own arithmetic: f32 product, int64 cast; it warns and sets output = *input_)
 static bool voxel_dims(const qn::BBoxOut& bb, double leaf, qn::VoxelDims* vd, long long* cells_out) {
@@ -581,285 +449,98 @@ static bool voxel_dims(const qn::BBoxOut& bb, double leaf, qn::VoxelDims* vd, lo
   return true;
 }
 static const char* kOverflowWarning = "warning: leaf size is too small for the input dataset, integer indices would overflow: cloud passed through unfiltered (as pcl::VoxelGrid does)";
+static const char* kNonFiniteNote = "note: non-finite points dropped (pcl::VoxelGrid on a non-dense cloud)";
 
-// transform + concatenate `count` resident keyframes with their poses (row-major 4x4 f64) and voxel-grid them into
-// output slot 0 (source) or 1 (target); returns the device pointer (float4, stride 16) and the point count.
-extern "C" int qn_kf_assemble(qn_kf_store* s, const int32_t* ids, const double* poses, uint32_t count, double leaf, int slot,
-                              const float** d_xyz_out, uint32_t* n_out) {
-  if (!s || !ids || !poses || !d_xyz_out || !n_out || (slot != 0 && slot != 1) || !(leaf > 0)) return QN_ERR_INVALID_ARG;
-  *d_xyz_out = nullptr; *n_out = 0;
-  KFCHK(s, hipSetDevice(s->device));
-  size_t total = 0;
-  for (uint32_t k = 0; k < count; k++) { if (ids[k] < 0 || (size_t)ids[k] >= s->clouds.size()) return QN_ERR_INVALID_ARG; total += s->sizes[ids[k]]; }
-  if (total == 0) return QN_ERR_EMPTY_CLOUD;
-  if (total >= 0xffffffffull) return QN_ERR_CAPACITY;
-  int rc = kf_reserve(s, total); if (rc != QN_OK) return rc;
-  if ((size_t)count * 16 > s->poses_cap) { (void)hipFree(s->poses); s->poses = nullptr; s->poses_cap = 0; KFCHK(s, hipMalloc(&s->poses, sizeof(double) * 16 * (count + 8))); s->poses_cap = (size_t)16 * (count + 8); }
-  hipStream_t st = s->stream;
-  KFCHK(s, hipMemcpyAsync(s->poses, poses, sizeof(double) * 16 * count, hipMemcpyHostToDevice, st));
-  size_t off = 0;
-  for (uint32_t k = 0; k < count; k++) {                       // transformPcd + operator+= (loop_closure.cpp:76,83,89,92,102)
-    const uint32_t n = s->sizes[ids[k]];
-    if (n) hipLaunchKernelGGL(qn::k_kf_transform, dim3((n + 255) / 256), dim3(256), 0, st, s->clouds[ids[k]], n, s->poses + 16 * k, s->concat + off);
-    off += n;
-  }
-  uint32_t n = (uint32_t)total;
-  // pcl::VoxelGrid::applyFilter: bounds, leaf indices
-  qn::BBoxOut init; for (int d = 0; d < 3; d++) { init.mn[d] = 0x7fffffff; init.mx[d] = (int)0x80000000; } init.nonfinite = 0;
-  *s->bbox_host = init;
-  KFCHK(s, hipMemcpyAsync(s->bbox, s->bbox_host, sizeof(qn::BBoxOut), hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(qn::k_bbox, dim3(std::min<uint32_t>((n + QN_BLOCK - 1) / QN_BLOCK, 128)), dim3(QN_BLOCK), 0, st, s->concat, n, s->bbox);
-  KFCHK(s, hipMemcpyAsync(s->bbox_host, s->bbox, sizeof(qn::BBoxOut), hipMemcpyDeviceToHost, st));
-  KFCHK(s, hipStreamSynchronize(st));
-  if (s->bbox_host->nonfinite) {                                  // rare path: drop the non-finite points like pcl::VoxelGrid does for a non-dense cloud (order of the others kept)
-    const uint32_t nbf = (n + 255) / 256, sbf = (n + QN_BLOCK * QN_SCAN_ITEMS - 1) / (QN_BLOCK * QN_SCAN_ITEMS);
-    hipLaunchKernelGGL(qn::k_finite_flags, dim3(nbf), dim3(256), 0, st, s->concat, n, s->flag);
-    hipLaunchKernelGGL(qn::k_scan_block, dim3(sbf), dim3(QN_BLOCK), 0, st, s->flag, n, s->pos, s->sums);
-    hipLaunchKernelGGL(qn::k_scan_top, dim3(1), dim3(QN_BLOCK), 0, st, s->sums, sbf);
-    hipLaunchKernelGGL(qn::k_scan_add_total, dim3(sbf), dim3(QN_BLOCK), 0, st, s->pos, n, s->sums, s->flag);
-    if (n > s->out_cap[slot]) { (void)hipFree(s->out[slot]); s->out[slot] = nullptr; s->out_cap[slot] = 0; KFCHK(s, hipMalloc(&s->out[slot], sizeof(float4) * (n + n / 2))); s->out_cap[slot] = n + n / 2; }
-    hipLaunchKernelGGL(qn::k_compact_finite, dim3(nbf), dim3(256), 0, st, (const float4*)s->concat, n, (const uint32_t*)s->flag, (const uint32_t*)s->pos, s->out[slot]);      // (the output slot as scratch)
-    uint32_t kept = 0;
-    KFCHK(s, hipMemcpyAsync(&kept, s->pos + n, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    KFCHK(s, hipStreamSynchronize(st));
-    if (kept == 0) return QN_ERR_EMPTY_CLOUD;
-    KFCHK(s, hipMemcpyAsync(s->concat, s->out[slot], sizeof(float4) * kept, hipMemcpyDeviceToDevice, st));
-    n = kept;
-    s->last_error = "note: non-finite points dropped (pcl::VoxelGrid on a non-dense cloud)";
-  }
-  qn::VoxelDims vd; long long cells = 1;
-  if (!voxel_dims(*s->bbox_host, leaf, &vd, &cells)) {
-    s->last_error = kOverflowWarning;
-    if (n > s->out_cap[slot]) { (void)hipFree(s->out[slot]); s->out[slot] = nullptr; s->out_cap[slot] = 0; KFCHK(s, hipMalloc(&s->out[slot], sizeof(float4) * (n + n / 2))); s->out_cap[slot] = n + n / 2; }
-    KFCHK(s, hipMemcpyAsync(s->out[slot], s->concat, sizeof(float4) * n, hipMemcpyDeviceToDevice, st));
-    KFCHK(s, hipStreamSynchronize(st));
-    s->out_n[slot] = n; *d_xyz_out = (const float*)s->out[slot]; *n_out = n;
-    return QN_OK;
-  }
-  const uint32_t nb = (n + 255) / 256;
-  hipLaunchKernelGGL(qn::k_voxel_keys, dim3(nb), dim3(256), 0, st, s->concat, n, vd, s->keys);
-  unsigned long long* sorted = s->keys; unsigned long long* other = s->keys_alt;
-  int bits = 1; while ((1ll << bits) < cells) bits++;
-  const uint32_t rb = (n + QN_BLOCK - 1) / QN_BLOCK, hn = rb * 256, hsb = (hn + QN_BLOCK * QN_SCAN_ITEMS - 1) / (QN_BLOCK * QN_SCAN_ITEMS);
-  for (int shift = 32; shift < 32 + bits; shift += 8) {                  // stable LSD passes over the leaf-index bits only
-    hipLaunchKernelGGL(qn::k_radix_hist, dim3(rb), dim3(QN_BLOCK), 0, st, sorted, n, shift, rb, s->hist);
-    hipLaunchKernelGGL(qn::k_scan_block, dim3(hsb), dim3(QN_BLOCK), 0, st, s->hist, hn, s->hist, s->hist_sums);
-    hipLaunchKernelGGL(qn::k_scan_top, dim3(1), dim3(QN_BLOCK), 0, st, s->hist_sums, hsb);
-    hipLaunchKernelGGL(qn::k_scan_add, dim3(hsb), dim3(QN_BLOCK), 0, st, s->hist, hn, s->hist_sums, n);
-    hipLaunchKernelGGL(qn::k_radix_scatter, dim3(rb), dim3(QN_BLOCK), 0, st, sorted, n, shift, rb, s->hist, other);
-    std::swap(sorted, other);
-  }
-  hipLaunchKernelGGL(qn::k_leaf_flags, dim3(nb), dim3(256), 0, st, sorted, n, s->flag);
-  const uint32_t sb = (n + QN_BLOCK * QN_SCAN_ITEMS - 1) / (QN_BLOCK * QN_SCAN_ITEMS);
-  hipLaunchKernelGGL(qn::k_scan_block, dim3(sb), dim3(QN_BLOCK), 0, st, s->flag, n, s->pos, s->sums);
-  hipLaunchKernelGGL(qn::k_scan_top, dim3(1), dim3(QN_BLOCK), 0, st, s->sums, sb);
-  hipLaunchKernelGGL(qn::k_scan_add_total, dim3(sb), dim3(QN_BLOCK), 0, st, s->pos, n, s->sums, s->flag);
-  hipLaunchKernelGGL(qn::k_leaf_heads, dim3(nb), dim3(256), 0, st, s->flag, s->pos, n, s->heads);
-  if (n > s->out_cap[slot]) { (void)hipFree(s->out[slot]); s->out[slot] = nullptr; s->out_cap[slot] = 0; KFCHK(s, hipMalloc(&s->out[slot], sizeof(float4) * (n + n / 2))); s->out_cap[slot] = n + n / 2; }
-  hipLaunchKernelGGL(qn::k_leaf_centroids, dim3(nb), dim3(256), 0, st, s->concat, sorted, s->heads, s->pos + n, s->out[slot]);
-  KFCHK(s, hipMemcpyAsync(s->count_host, s->pos + n, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-  KFCHK(s, hipGetLastError());
-  KFCHK(s, hipStreamSynchronize(st));
-  s->out_n[slot] = *s->count_host;
-  *d_xyz_out = (const float*)s->out[slot]; *n_out = s->out_n[slot];
-  return QN_OK;
-}
-
-extern "C" int qn_kf_download(qn_kf_store* s, int slot, float* xyz_out) {        // packed n x 3, for tests / visualisation
-  if (!s || !xyz_out || (slot != 0 && slot != 1)) return QN_ERR_INVALID_ARG;
-  const uint32_t n = s->out_n[slot];
-  if (!n) return QN_OK;
-  KFCHK(s, hipSetDevice(s->device));
-  KFCHK(s, hipMemcpy2D(xyz_out, 12, s->out[slot], 16, 12, n, hipMemcpyDeviceToHost));
-  return QN_OK;
-}
-
-// the corrected global map (fast_lio_sam_qn.cpp:302-316, 398-411, 435-448): every listed keyframe transformed with its corrected pose,
-// concatenated in list order, voxel-grid at `leaf` with intensity; into the store's own map slot (never assemble slots 0 / 1).
-// Unlike qn_kf_assemble, a tripped overflow guard passes the WHOLE concatenation through, non-finite points included (output = *input_).
-static int map_grow(qn_kf_store* s, void** p, size_t* cap, size_t need, size_t elem) {
-  if (need <= *cap) return QN_OK;
-  (void)hipFree(*p); *p = nullptr; *cap = 0;
-  KFCHK(s, hipMalloc(p, elem * (need + need / 2)));
-  *cap = need + need / 2;
-  return QN_OK;
-}
-extern "C" int qn_kf_build_map(qn_kf_store* s, const int32_t* ids, const double* poses, uint32_t count, double leaf,
-                               const float** d_xyzi_out, uint32_t* n_out) {
-  if (!s || (count && (!ids || !poses)) || !d_xyzi_out || !n_out || !(leaf > 0)) return QN_ERR_INVALID_ARG;
-  *d_xyzi_out = nullptr; *n_out = 0;
-  s->map_n = 0; s->last_error.clear();
-  if (count == 0) return QN_ERR_EMPTY_CLOUD;
-  size_t total = 0, tiles = 0;
-  for (uint32_t k = 0; k < count; k++) {
-    if (ids[k] < 0 || (size_t)ids[k] >= s->clouds.size()) return QN_ERR_INVALID_ARG;
-    total += s->sizes[ids[k]]; tiles += (s->sizes[ids[k]] + QN_MAP_TILE - 1) / QN_MAP_TILE;
-  }
-  if (total == 0) return QN_ERR_EMPTY_CLOUD;
-  if (total >= 0xffffffffull) return QN_ERR_CAPACITY;
-  KFCHK(s, hipSetDevice(s->device));
-  int rc = kf_reserve(s, total); if (rc != QN_OK) return rc;
-  if ((rc = map_grow(s, (void**)&s->map_kfs, &s->map_kfs_cap, count, sizeof(qn::MapKf))) != QN_OK) return rc;
-  if ((rc = map_grow(s, (void**)&s->map_blk, &s->map_blk_cap, tiles, sizeof(uint32_t))) != QN_OK) return rc;
-  if ((rc = map_grow(s, (void**)&s->map_part, &s->map_part_cap, tiles, sizeof(qn::BBoxOut))) != QN_OK) return rc;
-  if ((size_t)count * 16 > s->poses_cap) { (void)hipFree(s->poses); s->poses = nullptr; s->poses_cap = 0; KFCHK(s, hipMalloc(&s->poses, sizeof(double) * 16 * (count + 8))); s->poses_cap = (size_t)16 * (count + 8); }
-  if ((rc = map_grow(s, (void**)&s->map, &s->map_cap, total, sizeof(float4))) != QN_OK) return rc;
-  // the keyframe table and the tile -> keyframe table (host, O(count + tiles))
-  std::vector<qn::MapKf> kfs(count); std::vector<uint32_t> blk(tiles);
-  uint32_t off = 0, b0 = 0;
-  for (uint32_t k = 0; k < count; k++) {
-    const uint32_t n = s->sizes[ids[k]], nt = (n + QN_MAP_TILE - 1) / QN_MAP_TILE;
-    kfs[k] = qn::MapKf{s->clouds[ids[k]], off, n, b0, s->has_i[ids[k]]};
-    for (uint32_t t = 0; t < nt; t++) blk[b0 + t] = k;
-    off += n; b0 += nt;
-  }
-  hipStream_t st = s->stream;
-  const uint32_t n = (uint32_t)total, nt = (uint32_t)tiles;
-  KFCHK(s, hipMemcpyAsync(s->poses, poses, sizeof(double) * 16 * count, hipMemcpyHostToDevice, st));
-  KFCHK(s, hipMemcpyAsync(s->map_kfs, kfs.data(), sizeof(qn::MapKf) * count, hipMemcpyHostToDevice, st));
-  KFCHK(s, hipMemcpyAsync(s->map_blk, blk.data(), sizeof(uint32_t) * tiles, hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(qn::k_map_transform, dim3(nt), dim3(QN_BLOCK), 0, st, (const qn::MapKf*)s->map_kfs, (const uint32_t*)s->map_blk, (const double*)s->poses, s->concat, s->map_part);
-  hipLaunchKernelGGL(qn::k_map_bbox_reduce, dim3(1), dim3(QN_BLOCK), 0, st, (const qn::BBoxOut*)s->map_part, nt, s->bbox);
-  KFCHK(s, hipMemcpyAsync(s->bbox_host, s->bbox, sizeof(qn::BBoxOut), hipMemcpyDeviceToHost, st));
-  KFCHK(s, hipStreamSynchronize(st));                               // sync 1 of 2: the bounding box sizes the grid
-  const qn::BBoxOut bb = *s->bbox_host;
-  const uint32_t n_fin = n - bb.nonfinite;
-  if (n_fin == 0) return QN_ERR_EMPTY_CLOUD;
-  qn::VoxelDims vd; long long cells = 1;
-  if (!voxel_dims(bb, leaf, &vd, &cells)) {
-    s->last_error = kOverflowWarning;
-    KFCHK(s, hipMemcpyAsync(s->map, s->concat, sizeof(float4) * n, hipMemcpyDeviceToDevice, st));
-    KFCHK(s, hipStreamSynchronize(st));
-    s->map_n = n; *d_xyzi_out = (const float*)s->map; *n_out = n;
-    return QN_OK;
-  }
-  const uint32_t nb = (n + 255) / 256;
-  hipLaunchKernelGGL(qn::k_map_keys, dim3(nb), dim3(256), 0, st, (const float4*)s->concat, n, vd, (uint32_t)cells, s->keys);
-  unsigned long long* sorted = s->keys; unsigned long long* other = s->keys_alt;
-  const long long maxleaf = bb.nonfinite ? cells : cells - 1;        // the sentinel leaf of the non-finite points is `cells`
-  int bits = 1; while ((1ll << bits) <= maxleaf) bits++;
-  const uint32_t rb = (n + QN_MAP_TILE - 1) / QN_MAP_TILE, hn = rb * 256, hsb = (hn + QN_BLOCK * QN_SCAN_ITEMS - 1) / (QN_BLOCK * QN_SCAN_ITEMS);
-  for (int shift = 32; shift < 32 + bits; shift += 8) {                  // stable LSD passes over the leaf-index bits only
-    hipLaunchKernelGGL(qn::k_map_radix_hist, dim3(rb), dim3(QN_BLOCK), 0, st, (const unsigned long long*)sorted, n, shift, rb, s->hist);
-    hipLaunchKernelGGL(qn::k_scan_block, dim3(hsb), dim3(QN_BLOCK), 0, st, s->hist, hn, s->hist, s->hist_sums);
-    hipLaunchKernelGGL(qn::k_scan_top, dim3(1), dim3(QN_BLOCK), 0, st, s->hist_sums, hsb);
-    hipLaunchKernelGGL(qn::k_scan_add, dim3(hsb), dim3(QN_BLOCK), 0, st, s->hist, hn, s->hist_sums, n);
-    hipLaunchKernelGGL(qn::k_map_radix_scatter, dim3(rb), dim3(QN_BLOCK), 0, st, (const unsigned long long*)sorted, n, shift, rb, (const uint32_t*)s->hist, other);
-    std::swap(sorted, other);
-  }
-  // leaf heads over the finite prefix of the sorted keys (the engine's scans), then one thread per leaf
-  const uint32_t nbf = (n_fin + 255) / 256, sb = (n_fin + QN_BLOCK * QN_SCAN_ITEMS - 1) / (QN_BLOCK * QN_SCAN_ITEMS);
-  hipLaunchKernelGGL(qn::k_leaf_flags, dim3(nbf), dim3(256), 0, st, sorted, n_fin, s->flag);
-  hipLaunchKernelGGL(qn::k_scan_block, dim3(sb), dim3(QN_BLOCK), 0, st, s->flag, n_fin, s->pos, s->sums);
-  hipLaunchKernelGGL(qn::k_scan_top, dim3(1), dim3(QN_BLOCK), 0, st, s->sums, sb);
-  hipLaunchKernelGGL(qn::k_scan_add_total, dim3(sb), dim3(QN_BLOCK), 0, st, s->pos, n_fin, s->sums, s->flag);
-  hipLaunchKernelGGL(qn::k_leaf_heads, dim3(nbf), dim3(256), 0, st, s->flag, s->pos, n_fin, s->heads);
-  hipLaunchKernelGGL(qn::k_map_centroids, dim3(nbf), dim3(256), 0, st, (const float4*)s->concat, (const unsigned long long*)sorted, (const uint32_t*)s->heads, (const uint32_t*)(s->pos + n_fin), s->map);
-  KFCHK(s, hipMemcpyAsync(s->count_host, s->pos + n_fin, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-  KFCHK(s, hipGetLastError());
-  KFCHK(s, hipStreamSynchronize(st));                               // sync 2 of 2: the leaf count
-  s->map_n = *s->count_host;
-  *d_xyzi_out = (const float*)s->map; *n_out = s->map_n;
-  return QN_OK;
-}
-
-// the map into host records: only the 12 xyz bytes (offset 0) and the 4 intensity bytes (offset ioff) of each are written
-extern "C" int qn_kf_download_map(qn_kf_store* s, void* out, uint32_t stride, uint32_t ioff) {
-  if (!s || !out || !xyzi_layout_ok(stride, ioff)) return QN_ERR_INVALID_ARG;
-  const uint32_t n = s->map_n;
-  if (!n) return QN_OK;
-  KFCHK(s, hipSetDevice(s->device));
-  KFCHK(s, hipMemcpy2D(out, stride, s->map, 16, 12, n, hipMemcpyDeviceToHost));
-  KFCHK(s, hipMemcpy2D((char*)out + ioff, stride, (const char*)s->map + 12, 16, 4, n, hipMemcpyDeviceToHost));
-  return QN_OK;
-}
-
-// S loop-closure submaps in one pass (LoopClosure::setSrcAndDstCloud for one query and its candidates, loop_closure.cpp:58-108): submap t =
-// ids[seg_off[t] .. seg_off[t + 1]) with the poses of the same entries; each equals qn_kf_assemble of its list in all 16 bytes of every record.
-// Into the store's batch slot (never slots 0 / 1 or the map slot).  Two host synchronisations: the per-submap boxes (grid sizes, sort
-// bits), then the per-submap leaf counts.  Submaps are sorted in groups whose keys fit 32 bits - normally one group.
-static int pin_grow(qn_kf_store* s, void** p, size_t* cap, size_t need, size_t elem) {
-  if (need <= *cap) return QN_OK;
-  if (*p) (void)hipHostFree(*p);
-  *p = nullptr; *cap = 0;
-  KFCHK(s, hipHostMalloc(p, elem * (need + need / 2), hipHostMallocDefault));
-  *cap = need + need / 2;
-  return QN_OK;
-}
 static int bits_for(unsigned long long v) { int b = 0; while (b < 64 && (1ull << b) <= v) b++; return b; }      // smallest b with v < 2^b
-extern "C" int qn_kf_assemble_batch(qn_kf_store* s, const int32_t* ids, const double* poses, const uint32_t* seg_off, uint32_t n_seg, double leaf,
-                                    const float** d_xyz_out, uint32_t* n_out, int* status) {
-  if (!s || !seg_off || n_seg == 0 || !d_xyz_out || !n_out || !status || !(leaf > 0)) return QN_ERR_INVALID_ARG;
-  for (uint32_t t = 0; t < n_seg; t++) if (seg_off[t + 1] < seg_off[t]) return QN_ERR_INVALID_ARG;
-  const uint32_t e0 = seg_off[0], count = seg_off[n_seg] - e0;
-  if (count && (!ids || !poses)) return QN_ERR_INVALID_ARG;
-  size_t total = 0, tiles = 0;
-  for (uint32_t j = e0; j < e0 + count; j++) {
-    if (ids[j] < 0 || (size_t)ids[j] >= s->clouds.size()) return QN_ERR_INVALID_ARG;
-    total += s->sizes[ids[j]]; tiles += (s->sizes[ids[j]] + QN_MAP_TILE - 1) / QN_MAP_TILE;
+static uint32_t tiles_of(size_t n) { return (uint32_t)((n + QN_MAP_TILE - 1) / QN_MAP_TILE); }
+static uint32_t scan_blocks(size_t n) { return (uint32_t)((n + QN_BLOCK * QN_SCAN_ITEMS - 1) / (QN_BLOCK * QN_SCAN_ITEMS)); }
+// keys per thread of the radix passes over n keys: QN_MAP_TILE-key tiles fill the chip's 256 CUs from 2^20 keys on; below that (one
+// keyframe, a small submap) one key per thread, or the passes would run on a handful of blocks
+static int radix_items(uint32_t n) { return n < 256u * QN_MAP_TILE ? 1 : QN_MAP_ITEMS; }
+static uint32_t radix_blocks(uint32_t n) { const uint32_t tile = radix_items(n) * QN_BLOCK; return (n + tile - 1) / tile; }
+static bool ids_valid(const qn_kf_store* s, const int32_t* ids, uint32_t a, uint32_t b) {
+  for (uint32_t j = a; j < b; j++) if (ids[j] < 0 || (size_t)ids[j] >= s->clouds.size()) return false;
+  return true;
+}
+
+// ---- the one voxel-grid pipeline.  Submap t = the keyframes ids[seg_off[t] .. seg_off[t + 1]) (ids already checked) with the poses of the
+// same entries, transformed, concatenated in list order and voxel-grid at `leaf`, every submap into `out` (the caller's slot).
+// carry_intensity: the centroids average .w (the map), else w = 1.  A submap that trips PCL's overflow guard is passed through behind the
+// leaves: trip_whole = its whole concatenation, non-finite points and intensity included (the map: output = *input_), else its finite points
+// in concatenation order with w = 1 (assemble, batch).  res[t] = its records, their count and QN_OK, or QN_ERR_EMPTY_CLOUD when it has no
+// finite point; notes = what the callers may put in last_error.  Two host synchronisations: the per-submap boxes (grid sizes, sort bits),
+// then the per-submap leaf counts.  Submaps are sorted in groups whose keys fit 32 bits - normally one group.
+struct SubmapOut { const float4* ptr; uint32_t n; int status; };
+// byte offsets of the call's tables in s->tab / s->tab_host: the poses, one row per listed keyframe, tile -> keyframe, keyframe -> submap,
+// each submap's first tile (n_seg + 1), then the submap grids (uploaded after sync 1); every table 16-byte aligned
+struct Tables {
+  size_t pose, kf, blk, kseg, toff, seg, end;
+  Tables(uint32_t count, size_t tiles, uint32_t n_seg) {
+    const auto up = [](size_t b) { return (b + 15) & ~(size_t)15; };
+    pose = 0; kf = up(sizeof(double) * 16 * count); blk = up(kf + sizeof(qn::MapKf) * count); kseg = up(blk + 4 * tiles);
+    toff = up(kseg + 4 * (size_t)count); seg = up(toff + 4 * ((size_t)n_seg + 1)); end = seg + sizeof(qn::BatchSeg) * n_seg;
   }
-  for (uint32_t t = 0; t < n_seg; t++) { d_xyz_out[t] = nullptr; n_out[t] = 0; status[t] = QN_ERR_EMPTY_CLOUD; }
-  s->bt_ptr.assign(n_seg, nullptr); s->bt_n.assign(n_seg, 0); s->last_error.clear();
+};
+struct VoxelNotes { bool nonfinite, tripped; };      // a voxelized or tripped submap had non-finite points / some submap tripped the guard
+static int voxel_submaps(qn_kf_store* s, const int32_t* ids, const double* poses, const uint32_t* seg_off, uint32_t n_seg, double leaf,
+                         bool carry_intensity, bool trip_whole, Buf<float4>& out, SubmapOut* res, VoxelNotes* notes) {
+  const uint32_t e0 = seg_off[0], count = seg_off[n_seg] - e0;
+  size_t total = 0, tiles = 0;
+  for (uint32_t j = e0; j < e0 + count; j++) { total += s->sizes[ids[j]]; tiles += tiles_of(s->sizes[ids[j]]); }
+  for (uint32_t t = 0; t < n_seg; t++) res[t] = SubmapOut{nullptr, 0, QN_ERR_EMPTY_CLOUD};
+  *notes = VoxelNotes{false, false};
   if (total >= 0xffffffffull) return QN_ERR_CAPACITY;
   if (total == 0) return QN_OK;
   KFCHK(s, hipSetDevice(s->device));
-  int rc = kf_reserve(s, total); if (rc != QN_OK) return rc;
-  if ((rc = map_grow(s, (void**)&s->map_kfs, &s->map_kfs_cap, count, sizeof(qn::MapKf))) != QN_OK) return rc;     // (the map's scratch tables, not its slot)
-  if ((rc = map_grow(s, (void**)&s->map_blk, &s->map_blk_cap, tiles, sizeof(uint32_t))) != QN_OK) return rc;
-  if ((rc = map_grow(s, (void**)&s->map_part, &s->map_part_cap, tiles, sizeof(qn::BBoxOut))) != QN_OK) return rc;
-  if ((rc = map_grow(s, (void**)&s->bt_kf_seg, &s->bt_kf_seg_cap, count, sizeof(uint32_t))) != QN_OK) return rc;
-  if ((rc = map_grow(s, (void**)&s->bt_tile_off, &s->bt_tile_off_cap, n_seg + 1, sizeof(uint32_t))) != QN_OK) return rc;
-  if ((rc = map_grow(s, (void**)&s->bt_segs, &s->bt_segs_cap, n_seg, sizeof(qn::BatchSeg))) != QN_OK) return rc;
-  if ((rc = map_grow(s, (void**)&s->bt_bbox, &s->bt_bbox_cap, n_seg, sizeof(qn::BBoxOut))) != QN_OK) return rc;
-  if ((rc = map_grow(s, (void**)&s->bt_res, &s->bt_res_cap, 2 * (size_t)n_seg, sizeof(uint32_t))) != QN_OK) return rc;
-  if ((rc = map_grow(s, (void**)&s->bt_ends, &s->bt_ends_cap, total, sizeof(uint32_t))) != QN_OK) return rc;
-  if ((rc = pin_grow(s, (void**)&s->bt_bbox_host, &s->bt_bbox_host_cap, n_seg, sizeof(qn::BBoxOut))) != QN_OK) return rc;
-  if ((rc = pin_grow(s, (void**)&s->bt_res_host, &s->bt_res_host_cap, 2 * (size_t)n_seg, sizeof(uint32_t))) != QN_OK) return rc;
-  if ((size_t)count * 16 > s->poses_cap) { (void)hipFree(s->poses); s->poses = nullptr; s->poses_cap = 0; KFCHK(s, hipMalloc(&s->poses, sizeof(double) * 16 * (count + 8))); s->poses_cap = (size_t)16 * (count + 8); }
-  // keyframe table, tile -> keyframe, keyframe -> submap, each submap's tile range and point range (host, O(count + tiles))
-  std::vector<qn::MapKf> kfs(count); std::vector<uint32_t> blk(tiles), kseg(count), toff(n_seg + 1), p0(n_seg + 1);
+  const uint32_t n = (uint32_t)total, nt = (uint32_t)tiles;
+  const Tables tb(count, tiles, n_seg);
+  if (!dev_grow(s, s->concat, n) || !dev_grow(s, s->keys, n) || !dev_grow(s, s->keys_alt, n) || !dev_grow(s, s->flag, n) || !dev_grow(s, s->pos, n + 1) ||
+      !dev_grow(s, s->heads, n) || !dev_grow(s, s->ends, n) || !dev_grow(s, s->sums, scan_blocks(n)) || !dev_grow(s, s->tile_box, nt) ||
+      !dev_grow(s, s->seg_box, n_seg) || !dev_grow(s, s->seg_res, 2 * (size_t)n_seg) || !dev_grow(s, s->tab, tb.end) || !pin_grow(s, s->tab_host, tb.end) ||
+      !pin_grow(s, s->seg_box_host, n_seg) || !pin_grow(s, s->seg_res_host, 2 * (size_t)n_seg)) return QN_ERR_HIP;
+  // the tables in pinned memory (host, O(count + tiles)): poses, keyframe rows, tile -> keyframe, keyframe -> submap, each submap's tile range
+  char* h = s->tab_host.p;
+  qn::MapKf* kfs = (qn::MapKf*)(h + tb.kf); uint32_t* blk = (uint32_t*)(h + tb.blk); uint32_t* kseg = (uint32_t*)(h + tb.kseg); uint32_t* toff = (uint32_t*)(h + tb.toff);
+  std::copy(poses + 16 * (size_t)e0, poses + 16 * ((size_t)e0 + count), (double*)(h + tb.pose));
+  std::vector<uint32_t> p0(n_seg + 1);                              // each submap's point range
   uint32_t off = 0, b0 = 0;
   for (uint32_t t = 0; t < n_seg; t++) {
     toff[t] = b0; p0[t] = off;
     for (uint32_t j = seg_off[t]; j < seg_off[t + 1]; j++) {
-      const uint32_t k = j - e0, n = s->sizes[ids[j]], nt = (n + QN_MAP_TILE - 1) / QN_MAP_TILE;
-      kfs[k] = qn::MapKf{s->clouds[ids[j]], off, n, b0, s->has_i[ids[j]]}; kseg[k] = t;
-      for (uint32_t b = 0; b < nt; b++) blk[b0 + b] = k;
-      off += n; b0 += nt;
+      const uint32_t k = j - e0, nk = s->sizes[ids[j]], ntk = tiles_of(nk);
+      kfs[k] = qn::MapKf{s->clouds[ids[j]], off, nk, b0, s->has_i[ids[j]]}; kseg[k] = t;
+      for (uint32_t b = 0; b < ntk; b++) blk[b0 + b] = k;
+      off += nk; b0 += ntk;
     }
   }
   toff[n_seg] = b0; p0[n_seg] = off;
   hipStream_t st = s->stream;
-  const uint32_t n = (uint32_t)total, nt = (uint32_t)tiles;
-  KFCHK(s, hipMemcpyAsync(s->poses, poses + 16 * (size_t)e0, sizeof(double) * 16 * count, hipMemcpyHostToDevice, st));
-  KFCHK(s, hipMemcpyAsync(s->map_kfs, kfs.data(), sizeof(qn::MapKf) * count, hipMemcpyHostToDevice, st));
-  KFCHK(s, hipMemcpyAsync(s->map_blk, blk.data(), sizeof(uint32_t) * tiles, hipMemcpyHostToDevice, st));
-  KFCHK(s, hipMemcpyAsync(s->bt_kf_seg, kseg.data(), sizeof(uint32_t) * count, hipMemcpyHostToDevice, st));
-  KFCHK(s, hipMemcpyAsync(s->bt_tile_off, toff.data(), sizeof(uint32_t) * (n_seg + 1), hipMemcpyHostToDevice, st));
-  // transformPcd of every listed keyframe of every submap (k_map_transform: k_kf_transform's f64 order), per-tile boxes, per-submap reduce
-  hipLaunchKernelGGL(qn::k_map_transform, dim3(nt), dim3(QN_BLOCK), 0, st, (const qn::MapKf*)s->map_kfs, (const uint32_t*)s->map_blk, (const double*)s->poses, s->concat, s->map_part);
-  hipLaunchKernelGGL(qn::k_seg_bbox_reduce, dim3(n_seg), dim3(QN_BLOCK), 0, st, (const qn::BBoxOut*)s->map_part, (const uint32_t*)s->bt_tile_off, s->bt_bbox);
-  KFCHK(s, hipMemcpyAsync(s->bt_bbox_host, s->bt_bbox, sizeof(qn::BBoxOut) * n_seg, hipMemcpyDeviceToHost, st));
+  KFCHK(s, hipMemcpyAsync(s->tab.p, h, tb.seg, hipMemcpyHostToDevice, st));
+  // transformPcd + operator+= of every listed keyframe of every submap (loop_closure.cpp:76,83,89,92,102), per-tile boxes, per-submap reduce
+  const char* d = s->tab.p;
+  const qn::MapKf* dkf = (const qn::MapKf*)(d + tb.kf); const uint32_t* dblk = (const uint32_t*)(d + tb.blk); const uint32_t* dks = (const uint32_t*)(d + tb.kseg);
+  const qn::BatchSeg* dsg = (const qn::BatchSeg*)(d + tb.seg);
+  hipLaunchKernelGGL(qn::k_map_transform, dim3(nt), dim3(QN_BLOCK), 0, st, dkf, dblk, (const double*)(d + tb.pose), s->concat.p, s->tile_box.p);
+  hipLaunchKernelGGL(qn::k_seg_bbox_reduce, dim3(n_seg), dim3(QN_BLOCK), 0, st, (const qn::BBoxOut*)s->tile_box.p, (const uint32_t*)(d + tb.toff), s->seg_box.p);
+  KFCHK(s, hipMemcpyAsync(s->seg_box_host.p, s->seg_box.p, sizeof(qn::BBoxOut) * n_seg, hipMemcpyDeviceToHost, st));
   KFCHK(s, hipStreamSynchronize(st));                               // sync 1 of 2: each submap's box sizes its grid
   // per submap: pcl::VoxelGrid's grid and overflow guard (voxel_dims), its sentinel leaf and the key bits it needs
-  std::vector<qn::BatchSeg> sg(n_seg); std::vector<int> lbits(n_seg); std::vector<uint32_t> nfin(n_seg), trip_off(n_seg, 0);
+  qn::BatchSeg* sg = (qn::BatchSeg*)(h + tb.seg); std::vector<int> lbits(n_seg); std::vector<uint32_t> nfin(n_seg), ntrip(n_seg, 0), trip_off(n_seg, 0);
   std::vector<uint8_t> live(n_seg, 0);
-  size_t sum_vox = 0, sum_trip = 0; bool any_nonfinite = false, any_trip = false;
+  size_t sum_vox = 0, sum_trip = 0;
   for (uint32_t t = 0; t < n_seg; t++) {
     qn::BatchSeg& g = sg[t];
     g = qn::BatchSeg{}; g.p0 = p0[t]; g.p1 = p0[t + 1]; g.sentinel = 1; g.tripped = 1; g.nvox = 0;
-    const qn::BBoxOut bb = s->bt_bbox_host[t];
+    const qn::BBoxOut bb = s->seg_box_host.p[t];
     nfin[t] = (g.p1 - g.p0) - bb.nonfinite;
     if (nfin[t]) {
-      live[t] = 1; any_nonfinite |= bb.nonfinite != 0;
+      live[t] = 1; notes->nonfinite |= bb.nonfinite != 0;
       long long cells = 1;
       if (voxel_dims(bb, leaf, &g.vd, &cells)) { g.tripped = 0; g.sentinel = (uint32_t)cells; g.nvox = nfin[t]; sum_vox += nfin[t]; }
-      else { any_trip = true; trip_off[t] = (uint32_t)sum_trip; sum_trip += nfin[t]; }
+      else { notes->tripped = true; ntrip[t] = trip_whole ? g.p1 - g.p0 : nfin[t]; trip_off[t] = (uint32_t)sum_trip; sum_trip += ntrip[t]; }
     }
-    lbits[t] = bits_for(g.sentinel);
+    lbits[t] = bits_for(bb.nonfinite ? g.sentinel : g.sentinel - 1);  // the sentinel leaf needs key bits only when some point carries it
   }
-  if (any_nonfinite) s->last_error = "note: non-finite points dropped (pcl::VoxelGrid on a non-dense cloud)";
-  if (any_trip) s->last_error = kOverflowWarning;
   if (sum_vox + sum_trip == 0) return QN_OK;                        // every submap empty
   // sort groups: consecutive submaps whose (submap, leaf) fields fit the 32 key bits above the point index
   struct Group { uint32_t s0, s1; int L, sb; };
@@ -871,24 +552,29 @@ extern "C" int qn_kf_assemble_batch(qn_kf_store* s, const int32_t* ids, const do
       else L = L2;
     }
     groups.push_back(Group{g0, n_seg, L, bits_for(n_seg - 1 - g0)}); }
-  for (const Group& gr : groups) for (uint32_t t = gr.s0; t < gr.s1; t++) sg[t].prefix = (t - gr.s0) << gr.L;
-  if ((rc = map_grow(s, (void**)&s->bt_out, &s->bt_out_cap, sum_vox + sum_trip, sizeof(float4))) != QN_OK) return rc;
-  KFCHK(s, hipMemcpyAsync(s->bt_segs, sg.data(), sizeof(qn::BatchSeg) * n_seg, hipMemcpyHostToDevice, st));
-  const qn::MapKf* dkf = s->map_kfs; const uint32_t* dblk = s->map_blk; const uint32_t* dks = s->bt_kf_seg; const qn::BatchSeg* dsg = s->bt_segs;
-  hipLaunchKernelGGL(qn::k_batch_keys, dim3(nt), dim3(QN_BLOCK), 0, st, dkf, dblk, dks, dsg, (const float4*)s->concat, s->keys);
+  size_t hn = 0;                                                    // the digit-major block histograms of the largest radix pass
+  for (const Group& gr : groups) {
+    for (uint32_t t = gr.s0; t < gr.s1; t++) sg[t].prefix = (t - gr.s0) << gr.L;
+    hn = std::max<size_t>(hn, 256 * (size_t)radix_blocks(p0[gr.s1] - p0[gr.s0]));
+  }
+  if (!dev_grow(s, out, sum_vox + sum_trip) || !dev_grow(s, s->hist, hn + 1) || !dev_grow(s, s->hist_sums, scan_blocks(hn))) return QN_ERR_HIP;
+  KFCHK(s, hipMemcpyAsync(s->tab.p + tb.seg, sg, tb.end - tb.seg, hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(qn::k_batch_keys, dim3(nt * QN_MAP_ITEMS), dim3(QN_BLOCK), 0, st, dkf, dblk, dks, dsg, (const float4*)s->concat.p, s->keys.p);
   // stable LSD passes over each group's (submap, leaf) bits only, on its own point range; every group's result ends in one buffer
   unsigned long long* fin = nullptr;
   for (const Group& gr : groups) {
     const uint32_t gp0 = p0[gr.s0], gn = p0[gr.s1] - gp0;
     if (!gn) continue;
-    unsigned long long* sorted = s->keys + gp0; unsigned long long* other = s->keys_alt + gp0;
-    const uint32_t rb = (gn + QN_MAP_TILE - 1) / QN_MAP_TILE, hn = rb * 256, hsb = (hn + QN_BLOCK * QN_SCAN_ITEMS - 1) / (QN_BLOCK * QN_SCAN_ITEMS);
+    unsigned long long* sorted = s->keys.p + gp0; unsigned long long* other = s->keys_alt.p + gp0;
+    const bool small = radix_items(gn) == 1;
+    const uint32_t rb = radix_blocks(gn), ghn = rb * 256, hsb = scan_blocks(ghn);
     for (int shift = 32; shift < 32 + gr.L + gr.sb; shift += 8) {
-      hipLaunchKernelGGL(qn::k_map_radix_hist, dim3(rb), dim3(QN_BLOCK), 0, st, (const unsigned long long*)sorted, gn, shift, rb, s->hist);
-      hipLaunchKernelGGL(qn::k_scan_block, dim3(hsb), dim3(QN_BLOCK), 0, st, s->hist, hn, s->hist, s->hist_sums);
-      hipLaunchKernelGGL(qn::k_scan_top, dim3(1), dim3(QN_BLOCK), 0, st, s->hist_sums, hsb);
-      hipLaunchKernelGGL(qn::k_scan_add, dim3(hsb), dim3(QN_BLOCK), 0, st, s->hist, hn, s->hist_sums, gn);
-      hipLaunchKernelGGL(qn::k_map_radix_scatter, dim3(rb), dim3(QN_BLOCK), 0, st, (const unsigned long long*)sorted, gn, shift, rb, (const uint32_t*)s->hist, other);
+      hipLaunchKernelGGL(small ? qn::k_map_radix_hist<1> : qn::k_map_radix_hist<QN_MAP_ITEMS>, dim3(rb), dim3(QN_BLOCK), 0, st, (const unsigned long long*)sorted, gn, shift, rb, s->hist.p);
+      hipLaunchKernelGGL(qn::k_scan_block, dim3(hsb), dim3(QN_BLOCK), 0, st, s->hist.p, ghn, s->hist.p, s->hist_sums.p);
+      hipLaunchKernelGGL(qn::k_scan_top, dim3(1), dim3(QN_BLOCK), 0, st, s->hist_sums.p, hsb);
+      hipLaunchKernelGGL(qn::k_scan_add, dim3(hsb), dim3(QN_BLOCK), 0, st, s->hist.p, ghn, s->hist_sums.p, gn);
+      hipLaunchKernelGGL(small ? qn::k_map_radix_scatter<1> : qn::k_map_radix_scatter<QN_MAP_ITEMS>, dim3(rb), dim3(QN_BLOCK), 0, st, (const unsigned long long*)sorted, gn, shift, rb,
+                         (const uint32_t*)s->hist.p, other);
       std::swap(sorted, other);
     }
     unsigned long long* base = sorted - gp0;
@@ -896,29 +582,116 @@ extern "C" int qn_kf_assemble_batch(qn_kf_store* s, const int32_t* ids, const do
     else if (base != fin) KFCHK(s, hipMemcpyAsync(fin + gp0, sorted, sizeof(unsigned long long) * gn, hipMemcpyDeviceToDevice, st));
   }
   // leaves of all submaps at once: heads, exclusive scan, bounds, one thread per leaf
-  const uint32_t sb = (n + QN_BLOCK * QN_SCAN_ITEMS - 1) / (QN_BLOCK * QN_SCAN_ITEMS);
-  hipLaunchKernelGGL(qn::k_batch_leaf_flags, dim3(nt), dim3(QN_BLOCK), 0, st, dkf, dblk, dks, dsg, (const unsigned long long*)fin, s->flag);
-  hipLaunchKernelGGL(qn::k_scan_block, dim3(sb), dim3(QN_BLOCK), 0, st, s->flag, n, s->pos, s->sums);
-  hipLaunchKernelGGL(qn::k_scan_top, dim3(1), dim3(QN_BLOCK), 0, st, s->sums, sb);
-  hipLaunchKernelGGL(qn::k_scan_add_total, dim3(sb), dim3(QN_BLOCK), 0, st, s->pos, n, s->sums, s->flag);
+  const uint32_t sb = scan_blocks(n);
+  hipLaunchKernelGGL(qn::k_batch_leaf_flags, dim3(nt * QN_MAP_ITEMS), dim3(QN_BLOCK), 0, st, dkf, dblk, dks, dsg, (const unsigned long long*)fin, s->flag.p);
+  hipLaunchKernelGGL(qn::k_scan_block, dim3(sb), dim3(QN_BLOCK), 0, st, s->flag.p, n, s->pos.p, s->sums.p);
+  hipLaunchKernelGGL(qn::k_scan_top, dim3(1), dim3(QN_BLOCK), 0, st, s->sums.p, sb);
+  hipLaunchKernelGGL(qn::k_scan_add_total, dim3(sb), dim3(QN_BLOCK), 0, st, s->pos.p, n, s->sums.p, s->flag.p);
   if (sum_vox) {
-    hipLaunchKernelGGL(qn::k_batch_leaf_bounds, dim3(nt), dim3(QN_BLOCK), 0, st, dkf, dblk, dks, dsg, (const uint32_t*)s->flag, (const uint32_t*)s->pos, s->heads, s->bt_ends);
-    hipLaunchKernelGGL(qn::k_batch_centroids, dim3((uint32_t)((sum_vox + 255) / 256)), dim3(256), 0, st, (const float4*)s->concat, (const unsigned long long*)fin,
-                       (const uint32_t*)s->heads, (const uint32_t*)s->bt_ends, (const uint32_t*)(s->pos + n), s->bt_out);
+    hipLaunchKernelGGL(qn::k_batch_leaf_bounds, dim3(nt * QN_MAP_ITEMS), dim3(QN_BLOCK), 0, st, dkf, dblk, dks, dsg, (const uint32_t*)s->flag.p, (const uint32_t*)s->pos.p, s->heads.p, s->ends.p);
+    const dim3 cg((uint32_t)((sum_vox + 255) / 256));
+    if (carry_intensity) hipLaunchKernelGGL(qn::k_batch_centroids<true>, cg, dim3(256), 0, st, (const float4*)s->concat.p, (const unsigned long long*)fin,
+                                            (const uint32_t*)s->heads.p, (const uint32_t*)s->ends.p, (const uint32_t*)(s->pos.p + n), out.p);
+    else hipLaunchKernelGGL(qn::k_batch_centroids<false>, cg, dim3(256), 0, st, (const float4*)s->concat.p, (const unsigned long long*)fin,
+                            (const uint32_t*)s->heads.p, (const uint32_t*)s->ends.p, (const uint32_t*)(s->pos.p + n), out.p);
   }
-  for (uint32_t t = 0; t < n_seg; t++)                              // rare: tripped guards, their finite points unfiltered behind the leaves
-    if (live[t] && sg[t].tripped)
-      hipLaunchKernelGGL(qn::k_batch_gather, dim3((nfin[t] + 255) / 256), dim3(256), 0, st, (const unsigned long long*)fin + p0[t], nfin[t], (const float4*)s->concat, s->bt_out + sum_vox + trip_off[t]);
-  hipLaunchKernelGGL(qn::k_batch_counts, dim3((n_seg + 255) / 256), dim3(256), 0, st, dsg, n_seg, (const uint32_t*)s->pos, s->bt_res);
-  KFCHK(s, hipMemcpyAsync(s->bt_res_host, s->bt_res, sizeof(uint32_t) * 2 * n_seg, hipMemcpyDeviceToHost, st));
+  for (uint32_t t = 0; t < n_seg; t++) {                            // rare: tripped guards, passed through behind the leaves
+    if (!live[t] || !sg[t].tripped) continue;
+    float4* dst = out.p + sum_vox + trip_off[t];
+    if (trip_whole) KFCHK(s, hipMemcpyAsync(dst, s->concat.p + p0[t], sizeof(float4) * ntrip[t], hipMemcpyDeviceToDevice, st));
+    else hipLaunchKernelGGL(qn::k_batch_gather, dim3((ntrip[t] + 255) / 256), dim3(256), 0, st, (const unsigned long long*)fin + p0[t], ntrip[t], (const float4*)s->concat.p, dst);
+  }
+  hipLaunchKernelGGL(qn::k_batch_counts, dim3((n_seg + 255) / 256), dim3(256), 0, st, dsg, n_seg, (const uint32_t*)s->pos.p, s->seg_res.p);
+  KFCHK(s, hipMemcpyAsync(s->seg_res_host.p, s->seg_res.p, sizeof(uint32_t) * 2 * n_seg, hipMemcpyDeviceToHost, st));
   KFCHK(s, hipGetLastError());
   KFCHK(s, hipStreamSynchronize(st));                               // sync 2 of 2: each submap's first leaf and leaf count
   for (uint32_t t = 0; t < n_seg; t++) {
     if (!live[t]) continue;
     const bool tr = sg[t].tripped != 0;
-    s->bt_ptr[t] = s->bt_out + (tr ? sum_vox + trip_off[t] : s->bt_res_host[2 * t]);
-    s->bt_n[t] = tr ? nfin[t] : s->bt_res_host[2 * t + 1];
-    d_xyz_out[t] = (const float*)s->bt_ptr[t]; n_out[t] = s->bt_n[t]; status[t] = QN_OK;
+    res[t] = SubmapOut{out.p + (tr ? sum_vox + trip_off[t] : s->seg_res_host.p[2 * t]), tr ? ntrip[t] : s->seg_res_host.p[2 * t + 1], QN_OK};
+  }
+  return QN_OK;
+}
+
+// transform + concatenate `count` resident keyframes with their poses (row-major 4x4 f64) and voxel-grid them into output slot 0 (source)
+// or 1 (target); returns the device pointer (float4, stride 16, w = 1) and the point count.  Non-finite points are dropped (a note in
+// last_error); a tripped guard returns the finite points unfiltered (the warning replaces the note).  last_error is not cleared on entry.
+extern "C" int qn_kf_assemble(qn_kf_store* s, const int32_t* ids, const double* poses, uint32_t count, double leaf, int slot,
+                              const float** d_xyz_out, uint32_t* n_out) {
+  if (!s || !ids || !poses || !d_xyz_out || !n_out || (slot != 0 && slot != 1) || !(leaf > 0)) return QN_ERR_INVALID_ARG;
+  *d_xyz_out = nullptr; *n_out = 0;
+  if (!ids_valid(s, ids, 0, count)) return QN_ERR_INVALID_ARG;
+  const uint32_t seg[2] = {0, count};
+  SubmapOut r; VoxelNotes nt;
+  const int rc = voxel_submaps(s, ids, poses, seg, 1, leaf, false, false, s->out[slot], &r, &nt);
+  if (rc != QN_OK) return rc;
+  if (r.status != QN_OK) return r.status;
+  if (nt.nonfinite) s->last_error = kNonFiniteNote;
+  if (nt.tripped) s->last_error = kOverflowWarning;
+  s->out_n[slot] = r.n; *d_xyz_out = (const float*)r.ptr; *n_out = r.n;
+  return QN_OK;
+}
+
+extern "C" int qn_kf_download(qn_kf_store* s, int slot, float* xyz_out) {        // packed n x 3, for tests / visualisation
+  if (!s || !xyz_out || (slot != 0 && slot != 1)) return QN_ERR_INVALID_ARG;
+  const uint32_t n = s->out_n[slot];
+  if (!n) return QN_OK;
+  KFCHK(s, hipSetDevice(s->device));
+  KFCHK(s, hipMemcpy2D(xyz_out, 12, s->out[slot].p, 16, 12, n, hipMemcpyDeviceToHost));
+  return QN_OK;
+}
+
+// the corrected global map (fast_lio_sam_qn.cpp:302-316, 398-411, 435-448): every listed keyframe transformed with its corrected pose,
+// concatenated in list order, voxel-grid at `leaf` with intensity; into the store's own map slot (never assemble slots 0 / 1).
+// Unlike qn_kf_assemble, a tripped overflow guard passes the WHOLE concatenation through, non-finite points included (output = *input_).
+extern "C" int qn_kf_build_map(qn_kf_store* s, const int32_t* ids, const double* poses, uint32_t count, double leaf,
+                               const float** d_xyzi_out, uint32_t* n_out) {
+  if (!s || (count && (!ids || !poses)) || !d_xyzi_out || !n_out || !(leaf > 0)) return QN_ERR_INVALID_ARG;
+  *d_xyzi_out = nullptr; *n_out = 0;
+  s->map_n = 0; s->last_error.clear();
+  if (count == 0) return QN_ERR_EMPTY_CLOUD;
+  if (!ids_valid(s, ids, 0, count)) return QN_ERR_INVALID_ARG;
+  const uint32_t seg[2] = {0, count};
+  SubmapOut r; VoxelNotes nt;
+  const int rc = voxel_submaps(s, ids, poses, seg, 1, leaf, true, true, s->map, &r, &nt);
+  if (rc != QN_OK) return rc;
+  if (r.status != QN_OK) return r.status;
+  if (nt.tripped) s->last_error = kOverflowWarning;
+  s->map_n = r.n; *d_xyzi_out = (const float*)r.ptr; *n_out = r.n;
+  return QN_OK;
+}
+
+// the map into host records: only the 12 xyz bytes (offset 0) and the 4 intensity bytes (offset ioff) of each are written
+extern "C" int qn_kf_download_map(qn_kf_store* s, void* out, uint32_t stride, uint32_t ioff) {
+  if (!s || !out || !xyzi_layout_ok(stride, ioff)) return QN_ERR_INVALID_ARG;
+  const uint32_t n = s->map_n;
+  if (!n) return QN_OK;
+  KFCHK(s, hipSetDevice(s->device));
+  KFCHK(s, hipMemcpy2D(out, stride, s->map.p, 16, 12, n, hipMemcpyDeviceToHost));
+  KFCHK(s, hipMemcpy2D((char*)out + ioff, stride, (const char*)s->map.p + 12, 16, 4, n, hipMemcpyDeviceToHost));
+  return QN_OK;
+}
+
+// S loop-closure submaps in one pass (LoopClosure::setSrcAndDstCloud for one query and its candidates, loop_closure.cpp:58-108): submap t =
+// ids[seg_off[t] .. seg_off[t + 1]) with the poses of the same entries, each what qn_kf_assemble builds for its list (the same pipeline),
+// into the store's batch slot (never slots 0 / 1 or the map slot).  A submap with no finite point has status QN_ERR_EMPTY_CLOUD.
+extern "C" int qn_kf_assemble_batch(qn_kf_store* s, const int32_t* ids, const double* poses, const uint32_t* seg_off, uint32_t n_seg, double leaf,
+                                    const float** d_xyz_out, uint32_t* n_out, int* status) {
+  if (!s || !seg_off || n_seg == 0 || !d_xyz_out || !n_out || !status || !(leaf > 0)) return QN_ERR_INVALID_ARG;
+  for (uint32_t t = 0; t < n_seg; t++) if (seg_off[t + 1] < seg_off[t]) return QN_ERR_INVALID_ARG;
+  if (seg_off[n_seg] != seg_off[0] && (!ids || !poses)) return QN_ERR_INVALID_ARG;
+  if (!ids_valid(s, ids, seg_off[0], seg_off[n_seg])) return QN_ERR_INVALID_ARG;
+  for (uint32_t t = 0; t < n_seg; t++) { d_xyz_out[t] = nullptr; n_out[t] = 0; status[t] = QN_ERR_EMPTY_CLOUD; }
+  s->bt_ptr.assign(n_seg, nullptr); s->bt_n.assign(n_seg, 0); s->last_error.clear();
+  std::vector<SubmapOut> res(n_seg); VoxelNotes nt;
+  const int rc = voxel_submaps(s, ids, poses, seg_off, n_seg, leaf, false, false, s->bt_out, res.data(), &nt);
+  if (rc != QN_OK) return rc;
+  if (nt.nonfinite) s->last_error = kNonFiniteNote;
+  if (nt.tripped) s->last_error = kOverflowWarning;
+  for (uint32_t t = 0; t < n_seg; t++) {
+    if (res[t].status != QN_OK) continue;
+    s->bt_ptr[t] = res[t].ptr; s->bt_n[t] = res[t].n;
+    d_xyz_out[t] = (const float*)res[t].ptr; n_out[t] = res[t].n; status[t] = QN_OK;
   }
   return QN_OK;
 }

@@ -1,5 +1,5 @@
 // qn_util_kernels.cuh - small utility kernels shared by the translation units of the library (point packing,
-// bounding box with ordered-int atomics, 3-kernel exclusive scan).  `static __global__`: every TU gets its own copy.
+// ordered-int float keys for bounding boxes, 3-kernel exclusive scan).  `static __global__`: every TU gets its own copy.
 #pragma once
 #include "qn_device.cuh"
 
@@ -20,30 +20,6 @@ static __global__ void k_pack_points(const char* __restrict__ in, uint32_t strid
   if (i >= n) return;
   const float* p = (const float*)(in + (size_t)i * stride);
   out[i] = make_float4(p[0], p[1], p[2], 1.0f);
-}
-
-static __global__ void __launch_bounds__(QN_BLOCK) k_bbox(const float4* __restrict__ pts, uint32_t n, BBoxOut* out) {
-  __shared__ int smn[QN_BLOCK / 64][3], smx[QN_BLOCK / 64][3], sbad[QN_BLOCK / 64];
-  int mn[3] = {0x7fffffff, 0x7fffffff, 0x7fffffff}, mx[3] = {(int)0x80000000, (int)0x80000000, (int)0x80000000};
-  int bad = 0;
-  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-    float4 p = pts[i];
-    if (!(isfinite(p.x) && isfinite(p.y) && isfinite(p.z))) { bad = 1; continue; }
-    int ox = f2ord(p.x), oy = f2ord(p.y), oz = f2ord(p.z);
-    mn[0] = min(mn[0], ox); mn[1] = min(mn[1], oy); mn[2] = min(mn[2], oz);
-    mx[0] = max(mx[0], ox); mx[1] = max(mx[1], oy); mx[2] = max(mx[2], oz);
-  }
-#pragma unroll
-  for (int d = 0; d < 3; d++) { mn[d] = wave_min_i(mn[d]); mx[d] = wave_max_i(mx[d]); }
-  bad = wave_max_i(bad);
-  const int wid = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) { for (int d = 0; d < 3; d++) { smn[wid][d] = mn[d]; smx[wid][d] = mx[d]; } sbad[wid] = bad; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int w = 1; w < QN_BLOCK / 64; w++) { for (int d = 0; d < 3; d++) { mn[d] = min(mn[d], smn[w][d]); mx[d] = max(mx[d], smx[w][d]); } bad |= sbad[w]; }
-    for (int d = 0; d < 3; d++) { atomicMin(&out->mn[d], mn[d]); atomicMax(&out->mx[d], mx[d]); }
-    if (bad) atomicAdd(&out->nonfinite, 1u);
-  }
 }
 
 // exclusive scan of counts[0..m) -> out[0..m], out[m] = total.  3 kernels, 4096 items per block.

@@ -87,6 +87,34 @@ def test_assemble_drops_non_finite_points_like_pcl_voxelgrid(oracle):
 
 
 @pytest.mark.gpu
+def test_assemble_tripped_guard_passes_finite_points_through(oracle):
+    """PCL's overflow guard (VoxelGrid::applyFilter warns and copies its input): a tripped qn_kf_assemble returns the finite points of the
+    concatenation unfiltered, in concatenation order, w = 1, with the warning in last_error; normal calls on the same store beside it are unaffected."""
+    from qn_amd import engine
+    from test_gpu_kf_batch import _records
+    kfs, poses = _keyframes()
+    rng = np.random.default_rng(5)
+    huge = rng.uniform(-2e4, 2e4, (3000, 3)).astype(np.float32); huge[::9, 1] = np.nan; huge[4::13, 2] = np.inf
+    store = engine.KeyframeStore()
+    ids = [store.add(k) for k in kfs]
+    hid = store.add(huge)
+    exp = oracle.assemble_submap(kfs, poses, [1, 2], 0.3)
+    ptr0, n0 = store.assemble([ids[1], ids[2]], poses[1:3], 0.3, 0)
+    assert n0 == len(exp) and np.array_equal(store.download(0, n0), exp)
+    ptr1, n1 = store.assemble([ids[0], hid, ids[3]], [poses[0], np.eye(4), poses[3]], 0.3, 1)
+    assert "too small" in store._l.qn_kf_last_error(store.h).decode()
+    cat = np.concatenate([oracle.transform_pcd(kfs[0], poses[0]), oracle.transform_pcd(huge, np.eye(4)), oracle.transform_pcd(kfs[3], poses[3])])
+    fin = cat[np.isfinite(cat).all(1)]
+    assert 0 < len(fin) < len(cat)
+    got = _records(ptr1, n1)
+    assert n1 == len(fin) and np.array_equal(got[:, :3].view(np.uint32), fin.view(np.uint32)) and (got[:, 3] == 1.0).all()
+    assert np.array_equal(store.download(0, n0), exp)                  # slot 0 untouched by the tripped call
+    ptr0, n0 = store.assemble([ids[1], ids[2]], poses[1:3], 0.3, 0)    # and a normal call after it
+    assert n0 == len(exp) and np.array_equal(store.download(0, n0), exp)
+    store.close()
+
+
+@pytest.mark.gpu
 def test_loop_attempt_on_device_matches_oracle_pipeline(oracle):
     """setSrcAndDstCloud (scan-to-submap branch, loop_closure.cpp:94-105) + icpAlignment with nothing leaving the GPU."""
     from qn_amd import engine

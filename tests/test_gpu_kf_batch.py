@@ -1,5 +1,5 @@
 """Many loop-closure submaps in one pass (qn_kf_assemble_batch, loop_closure.cpp:58-108 for one query and its candidates): every submap
-equals qn_kf_assemble of the same list in all 16 bytes of every record, a subset also equals the oracle's assemble_submap, the batch slot
+equals qn_kf_assemble of the same list in all 16 bytes of every record and the oracle's assemble_submap, the batch slot
 is isolated from slots 0/1 and the map slot, and the batch outputs registered through gicp_align_batch / coarse_to_fine_align_batch give
 the records of the one-pair device entry points on the same clouds assembled through slots 0/1."""
 import ctypes as C
@@ -84,7 +84,7 @@ def test_query_and_sixteen_candidates_with_overlaps_and_repeats(store, oracle):
     lists[8] = [4]                                                     # a single-keyframe submap
     out, got, _ = _check_batch(store, lists, [[poses[i] for i in l] for l in lists], 0.3)
     assert all(st == 0 for _, _, st in out) and len(out) == 17
-    for s in (0, 3, 8, 16):                                            # the oracle's setSrcAndDstCloud
+    for s in range(len(lists)):                                        # the oracle's setSrcAndDstCloud, every submap
         ref = oracle.assemble_submap(kfs, poses, lists[s], 0.3)
         assert np.array_equal(got[s][:, :3].view(np.uint32), ref.view(np.uint32)) and (got[s][:, 3] == 1.0).all()
 
