@@ -696,6 +696,26 @@ extern "C" int qn_kf_assemble_batch(qn_kf_store* s, const int32_t* ids, const do
   return QN_OK;
 }
 
+int qn_kf_int_voxel_each(qn_kf_store* s, const int32_t* ids, uint32_t count, double leaf, float4** block, const float4** ptr, uint32_t* n, int* status) {
+  *block = nullptr;
+  for (uint32_t t = 0; t < count; t++) { ptr[t] = nullptr; n[t] = 0; status[t] = QN_ERR_EMPTY_CLOUD; }
+  if (count == 0) return QN_OK;
+  std::vector<uint32_t> seg(count + 1);
+  for (uint32_t t = 0; t <= count; t++) seg[t] = t;
+  std::vector<double> eye(16 * (size_t)count, 0.0);
+  for (uint32_t t = 0; t < count; t++) for (int i = 0; i < 4; i++) eye[16 * (size_t)t + 5 * i] = 1.0;
+  std::vector<SubmapOut> res(count); VoxelNotes nt;
+  Buf<float4> out;
+  s->last_error.clear();
+  const int rc = voxel_submaps(s, ids, eye.data(), seg.data(), count, leaf, false, false, out, res.data(), &nt);
+  if (rc != QN_OK) { dev_free(out); return rc; }
+  if (nt.nonfinite) s->last_error = kNonFiniteNote;
+  if (nt.tripped) s->last_error = kOverflowWarning;
+  for (uint32_t t = 0; t < count; t++) { ptr[t] = res[t].ptr; n[t] = res[t].n; status[t] = res[t].status; }
+  *block = out.p;
+  return QN_OK;
+}
+
 extern "C" int qn_kf_batch_count(const qn_kf_store* s, uint32_t seg, uint32_t* n) {
   if (!s || !n || seg >= s->bt_n.size()) return QN_ERR_INVALID_ARG;
   *n = s->bt_n[seg];

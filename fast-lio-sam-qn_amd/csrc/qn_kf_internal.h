@@ -22,10 +22,16 @@ int  qn_kf_int_copy_async(qn_kf_store* s, const void* d_pts, uint32_t n, uint32_
 void qn_kf_int_append(qn_kf_store* s, float4* const* bufs, const uint32_t* n, uint32_t count, bool has_i, int32_t* ids_out);
 // the resident float4 records of keyframe `id` (0 <= id < qn_kf_int_count; not checked) and their number (nullptr when n == 0)
 const float4* qn_kf_int_keyframe(const qn_kf_store* s, int32_t id, uint32_t* n);
-// per-store state of another translation unit (slot QN_KF_INT_EXT_SC: qn_sc.hip's descriptors): nullptr until set; the store owns it from
-// qn_kf_int_set_ext on and calls `release` from qn_kf_store_destroy once its stream has drained.
+// per-store state of another translation unit (slot QN_KF_INT_EXT_SC: qn_sc.hip's descriptors, QN_KF_INT_EXT_QUATRO: the resident Quatro features of
+// qn_kf_quatro.inc): nullptr until set; the store owns it from qn_kf_int_set_ext on and calls `release` from qn_kf_store_destroy once its stream has drained.
 #define QN_KF_INT_EXT 2
 #define QN_KF_INT_EXT_SC 0
+#define QN_KF_INT_EXT_QUATRO 1
 typedef void (*qn_kf_int_release_fn)(void*);
 void* qn_kf_int_ext(const qn_kf_store* s, int which);
 void qn_kf_int_set_ext(qn_kf_store* s, int which, void* p, qn_kf_int_release_fn release);
+// keyframes ids[0 .. count) each alone in its sensor frame (the identity pose), voxel grid at `leaf`: what qn_kf_assemble({id}, {identity}, leaf) builds,
+// through the one voxel-grid pipeline as a batch of `count` submaps.  Every cloud lands in ONE new device allocation (*block, nullptr when all are empty)
+// that the caller owns from here on (hipFree); ptr / n / status per keyframe as qn_kf_assemble_batch's.  The store's assemble, map and batch slots are
+// not touched.  Two host synchronisations.  ids are not checked.
+int qn_kf_int_voxel_each(qn_kf_store* s, const int32_t* ids, uint32_t count, double leaf, float4** block, const float4** ptr, uint32_t* n, int* status);

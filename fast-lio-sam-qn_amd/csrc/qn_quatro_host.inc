@@ -846,6 +846,26 @@ struct C2fBorrow {
   }
 };
 
+// a pair whose clouds and FPFH rows are resident already (qn_kf_verify_loop_candidates_c2f: the store's described keyframes): the lane borrows both sides - points and
+// descriptor rows, which is all the matching reads - and builds no grid and no feature (the rows are the ones quatro_fpfh makes of the same cloud: qn_kf_quatro_describe)
+struct C2fCached { float4* src_pts; float* src_rows; float4* dst_pts; float* dst_rows; };
+struct C2fCacheBorrow {
+  qn_ctx* c = nullptr; CloudBuf cloud[2]; float* fpfh[2];
+  void take(qn_ctx* lane, const C2fCached& k, uint32_t ns, uint32_t nt) {
+    c = lane;
+    for (int w = 0; w < 2; w++) { cloud[w] = lane->cloud[w]; fpfh[w] = lane->q_fpfh[w]; }
+    CloudBuf& s = lane->cloud[0]; CloudBuf& d = lane->cloud[1];
+    s.raw = k.src_pts; s.n = ns; d.raw = k.dst_pts; d.n = nt;
+    for (int w = 0; w < 2; w++) { lane->cloud[w].has_grid = lane->cloud[w].has_cov = false; lane->cloud[w].knn_tab = nullptr; }
+    lane->q_fpfh[0] = k.src_rows; lane->q_fpfh[1] = k.dst_rows;
+  }
+  void give_back() {
+    if (!c) return;
+    for (int w = 0; w < 2; w++) { c->cloud[w] = cloud[w]; c->q_fpfh[w] = fpfh[w]; c->cloud[w].has_grid = c->cloud[w].has_cov = false; c->cloud[w].n = 0; c->cloud[w].knn_tab = nullptr; }
+    c = nullptr;
+  }
+};
+
 int c2f_alloc(qn_ctx* owner, qn_ctx* l) {
   if (l->c2f_src) return QN_OK;
   HIPCHK(owner, hipMalloc(&l->c2f_src, sizeof(float4) * l->max_points));
@@ -853,12 +873,14 @@ int c2f_alloc(qn_ctx* owner, qn_ctx* l) {
   return QN_OK;
 }
 
-// one run of m <= B pairs on `owner`'s lanes.  idx[l] = the pair lane l carries.
-int c2f_run(qn_ctx* owner, const qn_pair_desc* pairs, const uint32_t* idx, uint32_t m, double thr, qn_gicp_result* results, double* T_total, double* T_quatro, int* valid, int* status) {
+// one run of m <= B pairs on `owner`'s lanes.  idx[l] = the pair lane l carries.  cached (or null) = per pair, its resident points and rows (C2fCached)
+int c2f_run(qn_ctx* owner, const qn_pair_desc* pairs, const uint32_t* idx, uint32_t m, double thr, qn_gicp_result* results, double* T_total, double* T_quatro, int* valid, int* status,
+            const C2fCached* cached) {
   hipStream_t s = owner->stream;
   std::vector<C2fSlot> S(m);
   std::vector<C2fBorrow> borrowed(m);
-  struct GiveBack { std::vector<C2fBorrow>& b; ~GiveBack() { for (auto& x : b) x.give_back(); } } give_back{borrowed};      // (every exit path: the lanes get their own buffers back)
+  std::vector<C2fCacheBorrow> borrowed_cache(m);
+  struct GiveBack { std::vector<C2fBorrow>& b; std::vector<C2fCacheBorrow>& k; ~GiveBack() { for (auto& x : b) x.give_back(); for (auto& x : k) x.give_back(); } } give_back{borrowed, borrowed_cache};      // (every exit path: the lanes get their own buffers back)
   // ---- 1. enqueue the Quatro device stages of every pair (loop_closure.cpp:144 up to the hand-over).  Grid builds and K9-K11 of ALL lanes' clouds ride in NINE launches
   // (k_lanes<F>: blockIdx.y = one cloud of one pair, the machinery of qn_batch.inc) - per-lane launches were 18 per pair, most of them ~5 us of work, 140 per run of eight
   // pairs on a stream that serialises them; the matching stage (K12 / K13) follows per lane.  MEASURED NEUTRAL TO SLIGHTLY SLOWER (qn_context.h, EXPERIMENTS.md round 5): with 3-8 contexts in
@@ -896,6 +918,14 @@ int c2f_run(qn_ctx* owner, const qn_pair_desc* pairs, const uint32_t* idx, uint3
     if (pd.ns == 0 || pd.nt == 0) { q.rc = QN_ERR_EMPTY_CLOUD; continue; }
     if ((q.rc = c2f_alloc(owner, c)) != QN_OK) return q.rc;
     if ((q.rc = quatro_alloc(c)) != QN_OK) { owner->last_error = c->last_error; return q.rc; }      // (the lane's own buffers exist before any of them is swapped out)
+    if (cached) {                                                                 // resident features: the matching stage straight away, on borrowed points and rows
+      if (pd.ns > c->max_points || pd.nt > c->max_points) { q.rc = QN_ERR_CAPACITY; continue; }      // (what set_cloud says of such a cloud)
+      borrowed_cache[l].take(c, cached[q.pair], pd.ns, pd.nt);
+      q.rc = quatro_match_enqueue(c, pd.ns, pd.nt, c->qparams);
+      if (q.rc == QN_ERR_HIP) { owner->last_error = c->last_error; return q.rc; }
+      q.enq = q.rc == QN_OK;
+      continue;
+    }
     // the candidates of ONE query name the same source buffer: the first lane of the run that carries it prepares it (grid, normals, SPFH, FPFH), the others borrow
     // the result (read-only from here on: the matching reads raw points and descriptor rows, the row hashes written into the rows are the same for every borrower)
     if (owner->batch_share_source && pd.src != nullptr) {
@@ -968,6 +998,7 @@ int c2f_run(qn_ctx* owner, const qn_pair_desc* pairs, const uint32_t* idx, uint3
     gidx.push_back(l);
   }
   HIPCHK(owner, hipGetLastError());
+  for (auto& x : borrowed_cache) x.give_back();
   for (auto& x : borrowed) x.give_back();      // the transforms above are enqueued: from here on every lane works on its own source buffers again (the GICP lanes pack into them)
   if (gidx.empty()) return QN_OK;
   // ---- the fine stage (:153): the accepted pairs through the GICP lanes (lane j of the GICP run = the j-th accepted pair; its clouds live in the Quatro lane's c2f buffers)
@@ -988,8 +1019,9 @@ int c2f_run(qn_ctx* owner, const qn_pair_desc* pairs, const uint32_t* idx, uint3
 }
 }  // namespace
 
-extern "C" int qn_coarse_to_fine_align_batch(qn_ctx* const* ctxs, uint32_t n_ctx, const qn_pair_desc* pairs, uint32_t n_pairs, double score_thr,
-                                             qn_gicp_result* results, double* T_total, double* T_quatro, int* valid, int* status) {
+// the driver of qn_coarse_to_fine_align_batch; cached (or null): per pair, resident points and FPFH rows the lanes borrow (qn_kf_verify_loop_candidates_c2f)
+static int c2f_batch(qn_ctx* const* ctxs, uint32_t n_ctx, const qn_pair_desc* pairs, uint32_t n_pairs, double score_thr,
+                     qn_gicp_result* results, double* T_total, double* T_quatro, int* valid, int* status, const C2fCached* cached) {
   if (!ctxs || n_ctx == 0 || (n_pairs && (!pairs || !results || !T_total || !valid || !status))) return QN_ERR_INVALID_ARG;
   for (uint32_t i = 0; i < n_ctx; i++) if (!ctxs[i]) return QN_ERR_INVALID_ARG;
   if (n_pairs == 0) return QN_OK;
@@ -1029,11 +1061,15 @@ extern "C" int qn_coarse_to_fine_align_batch(qn_ctx* const* ctxs, uint32_t n_ctx
       }
       if (base >= n_pairs) break;
       for (uint32_t l = 0; l < m; l++) idx[l] = base + l;
-      const int rc = c2f_run(c, pairs, idx.data(), m, score_thr, results, T_total, T_quatro, valid, status);
+      const int rc = c2f_run(c, pairs, idx.data(), m, score_thr, results, T_total, T_quatro, valid, status, cached);
       if (rc != QN_OK) { (void)hipStreamSynchronize(c->stream); for (uint32_t l = 0; l < m; l++) { status[base + l] = rc; valid[base + l] = 0; } wrc[w] = rc; }
     }
     c->pair_pipeline = sp; c->persist_batch_off = sb;
   };
   qn::WorkerPool::instance().run(n_ctx, worker);
   return QN_OK;
+}
+extern "C" int qn_coarse_to_fine_align_batch(qn_ctx* const* ctxs, uint32_t n_ctx, const qn_pair_desc* pairs, uint32_t n_pairs, double score_thr,
+                                             qn_gicp_result* results, double* T_total, double* T_quatro, int* valid, int* status) {
+  return c2f_batch(ctxs, n_ctx, pairs, n_pairs, score_thr, results, T_total, T_quatro, valid, status, nullptr);
 }

@@ -825,6 +825,44 @@ class KeyframeStore:
         return [dict(valid=bool(valid[j]), converged=bool(results[j].converged), score=results[j].fitness, iterations=results[j].iterations,
                      T=np.array(results[j].T, dtype=np.float32).reshape(4, 4).astype(np.float64), status=int(status[j]), record=results[j]) for j in range(K)]
 
+    # ---- resident Quatro descriptors and the drift-free coarse-to-fine check (qn_kf_quatro_*, qn_kf_verify_loop_candidates_c2f)
+    def quatro_describe(self, ctx, ids, leaf):
+        """qn_kf_quatro_describe: each keyframe alone in its sensor frame, voxel grid at `leaf` (= assemble([id], [eye(4)], leaf)), and its FPFH rows with
+        ctx's Quatro radii, kept resident in the store (describing again replaces) -> per id its status (QN_ERR_EMPTY_CLOUD: nothing left after the voxel grid)."""
+        ids = np.ascontiguousarray(np.atleast_1d(ids), dtype=np.int32)
+        st = np.zeros(max(len(ids), 1), np.int32)
+        self._check(self._l.qn_kf_quatro_describe(self.h, ctx.h, _p(ids) if len(ids) else None, C.c_uint32(len(ids)), C.c_double(leaf), _p(st)))
+        return [int(v) for v in st[:len(ids)]]
+
+    def quatro_cloud(self, kid):
+        """-> (device pointer of the described float4 cloud (None when empty), count)"""
+        ptr = C.c_void_p(); n = C.c_uint32()
+        self._check(self._l.qn_kf_quatro_cloud(self.h, C.c_int32(kid), C.byref(ptr), C.byref(n)))
+        return ptr.value, n.value
+
+    def quatro_features(self, kid):
+        """-> (n, 33) float32: the described FPFH rows of keyframe `kid` (original point order; NaN rows where PCL has none)"""
+        _, n = self.quatro_cloud(kid)
+        out = np.zeros((n, 33), np.float32)
+        self._check(self._l.qn_kf_quatro_features(self.h, C.c_int32(kid), _p(out) if n else None))
+        return out
+
+    def verify_loop_candidates_c2f(self, ctx, query, candidates, score_thr=1.5):
+        """qn_kf_verify_loop_candidates_c2f: the query's described cloud against each candidate's, coarse to fine (Quatro -> transformPcd -> Nano-GICP,
+        loop_closure.cpp:138-159) on ctx's lanes, the features borrowed from the store.  No pose is involved.  -> one dict per candidate as
+        coarse_to_fine_align_batch's: valid, converged, score, iterations, T (T_gicp * T_quatro: estimates inv(P_c) P_query), T_quatro, T_gicp, status."""
+        cand = np.ascontiguousarray(np.atleast_1d(candidates), dtype=np.int32)
+        K = len(cand)
+        results = (GicpResult * max(K, 1))(); valid = np.zeros(max(K, 1), np.int32); status = np.zeros(max(K, 1), np.int32)
+        Tt = np.zeros((max(K, 1), 4, 4)); Tq = np.zeros((max(K, 1), 4, 4))
+        st = self._l.qn_kf_verify_loop_candidates_c2f(self.h, ctx.h, C.c_int32(query), _p(cand) if K else None, C.c_uint32(K), C.c_double(score_thr),
+                                                      results, _p(Tt), _p(Tq), _p(valid), _p(status))
+        if st != QN_OK:
+            raise EngineError(st, self._l.qn_status_str(st).decode() + ": " + self._l.qn_kf_last_error(self.h).decode() + " / " + lib().qn_last_error(ctx.h).decode())
+        return [dict(valid=bool(valid[j]), converged=bool(results[j].converged), score=results[j].fitness, iterations=results[j].iterations, T=Tt[j].copy(),
+                     T_quatro=Tq[j].copy(), T_gicp=np.array(results[j].T, dtype=np.float32).reshape(4, 4).astype(np.float64), status=int(status[j]),
+                     record=results[j]) for j in range(K)]
+
     # ---- Scan Context loop candidates (qn_kf_sc_*; numpy twin: qn_amd/scancontext.py)
     def sc_set_params(self, params=None, **kw):
         """qn_kf_sc_set_params: a ScParams, or its fields as keywords (the rest default).  A shape change discards every descriptor."""

@@ -79,4 +79,41 @@ inline std::vector<ScVerified> verifyScanContextCandidates(qn_kf_store* store, q
   return out;
 }
 
+struct ScVerifiedC2f {
+  int idx;                                         // the candidate's keyframe index
+  bool valid;                                      // Quatro converged, GICP converged and score < score_thr (loop_closure.cpp:129, 145-148)
+  double score;                                    // the fine stage's fitness
+  double T[16];                                    // row-major T_gicp * T_quatro, query sensor frame -> candidate sensor frame: an estimate of inv(P_c) P_query
+  double T_quatro[16];                             // the coarse estimate
+  int status;                                      // QN_OK, or QN_ERR_EMPTY_CLOUD for an empty side
+};
+
+// The reference's default check (quatro/enable true, enable_submap_matching false: Quatro -> transformPcd -> Nano-GICP scan to scan, loop_closure.cpp:138-159)
+// made drift-free: the query and each candidate are keyframes in their own sensor frames, described once (qn_kf_quatro_describe: voxel grid at `leaf` and FPFH
+// with ctx's Quatro radii, kept resident) and registered in one qn_kf_verify_loop_candidates_c2f on ctx (its NanoGICP and Quatro parameters).  Keyframes not yet
+// described under ctx's radii are described here first, in one call.  In loopTimerFunc the loop factor is then BetweenFactor(latest, c, inv(T), score).
+inline std::vector<ScVerifiedC2f> verifyScanContextCandidatesCoarseToFine(qn_kf_store* store, qn_ctx* ctx, int query, const ScCandidates& c, double leaf, double score_thr) {
+  std::vector<ScVerifiedC2f> out;
+  if (c.idx.empty()) return out;
+  const size_t K = c.idx.size();
+  std::vector<int32_t> ids(c.idx.begin(), c.idx.end());
+  std::vector<qn_gicp_result> r(K);
+  std::vector<double> Tt(16 * K), Tq(16 * K);
+  std::vector<int> valid(K), status(K);
+  int rc = qn_kf_verify_loop_candidates_c2f(store, ctx, query, ids.data(), (uint32_t)K, score_thr, r.data(), Tt.data(), Tq.data(), valid.data(), status.data());
+  if (rc == QN_ERR_INVALID_ARG) {                  // (a keyframe not described yet, or under other radii: describe the query and every candidate, then once more)
+    std::vector<int32_t> all(ids); all.push_back(query);
+    std::vector<int> st(all.size());
+    rc = qn_kf_quatro_describe(store, ctx, all.data(), (uint32_t)all.size(), leaf, st.data());
+    if (rc == QN_OK) rc = qn_kf_verify_loop_candidates_c2f(store, ctx, query, ids.data(), (uint32_t)K, score_thr, r.data(), Tt.data(), Tq.data(), valid.data(), status.data());
+  }
+  if (rc != QN_OK) throw std::runtime_error(std::string("[qn_map] qn_kf_verify_loop_candidates_c2f: ") + qn_status_str(rc) + " " + qn_kf_last_error(store));
+  for (size_t k = 0; k < K; k++) {
+    ScVerifiedC2f v{c.idx[k], valid[k] != 0, r[k].fitness, {}, {}, status[k]};
+    for (int i = 0; i < 16; i++) { v.T[i] = Tt[16 * k + i]; v.T_quatro[i] = Tq[16 * k + i]; }
+    out.push_back(v);
+  }
+  return out;
+}
+
 }  // namespace qn_map

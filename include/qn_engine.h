@@ -334,6 +334,36 @@ int  qn_kf_batch_count(const qn_kf_store*, uint32_t seg, uint32_t* n);      /* p
 int  qn_kf_verify_loop_candidates(qn_kf_store*, qn_ctx*, int32_t query, const int32_t* cand, const double* yaw /* per candidate; NULL = 0 */,
                                   uint32_t n_cand, const double* poses16 /* n_poses x 16 */, uint32_t n_poses, uint32_t submap_range, double leaf,
                                   double score_thr, qn_gicp_result* results, int* valid, int* status);
+/* Resident Quatro descriptors per keyframe, for the reference's default scan-to-scan check (quatro/enable true, enable_submap_matching false:
+ * loop_closure.cpp:85-92, 138-159, 188-192), where each cloud of a pair is one keyframe in its own sensor frame and depends on no pose.
+ * qn_kf_quatro_describe: for each listed keyframe, its cloud = qn_kf_assemble({id}, {identity}, leaf) in all 16 bytes of every record (the store's voxel
+ *   pipeline as one batch of identity-pose submaps; the assemble, map and batch slots are not touched), and its FPFH rows with ctx's Quatro radii
+ *   (fpfh_normal_radius / fpfh_radius): K9 normals, K10 SPFH, K11 FPFH on the grid qn_fpfh builds for that cloud on ctx - the rows equal qn_fpfh's bit for bit.
+ *   Both stay resident in a store-owned arena (float4 points; QN_FROW floats per row, original point order); the entry records (leaf, radii, ctx's grid
+ *   capacity).  Describing again replaces the entry (an id listed twice: the later one).  status[i] = QN_ERR_EMPTY_CLOUD for a keyframe with no point after
+ *   the voxel grid (an entry with no points); the others are still described.  QN_ERR_INVALID_ARG before anything runs: a null pointer, count == 0, a bad id,
+ *   leaf <= 0, store and context on different devices.  An allocation failure (QN_ERR_HIP) leaves every earlier entry as it was.  Launches: the voxel
+ *   pipeline's, then nine for the grids and K9-K11 of all S keyframes (the keyframe is a grid dimension) - more only when the S grids' scratch (two tables
+ *   of max_cells + 1 words per keyframe, ~100 B per point) exceeds 1 GiB.  Host synchronisations: the voxel pipeline's two and one.  Memory per point
+ *   resident: 16 B of cloud (x 1.5 growth slack of the voxel output) + 144 B of rows.
+ * qn_kf_quatro_cloud: the described cloud of `id` (device pointer, float4, stride 16; NULL and n = 0 for an empty one), valid until `id` is described again
+ *   or the store is destroyed.  qn_kf_quatro_features: its n x 33 FPFH rows (one synchronous copy).  Both: QN_ERR_INVALID_ARG for a bad id,
+ *   QN_ERR_NOT_READY for a keyframe that was never described.                                                                                       */
+int  qn_kf_quatro_describe(qn_kf_store*, qn_ctx*, const int32_t* ids, uint32_t count, double leaf, int* status);
+int  qn_kf_quatro_cloud(qn_kf_store*, int32_t id, const float** d_xyz, uint32_t* n);
+int  qn_kf_quatro_features(qn_kf_store*, int32_t id, float* fpfh33_out /* n x 33 */);
+/* Drift-free coarse-to-fine verification from the described keyframes: pair j = the query's described cloud (source) against cand[j]'s (target), no pose
+ * involved.  The Quatro stage of every lane borrows both sides' resident points and rows - no grid, no feature is built - then runs
+ * qn_coarse_to_fine_align_batch's own machinery on ctx: matching (K12 / K13), one synchronisation per run of lanes, the host solver, transformPcd on the
+ * device, the GICP lanes.  Every record (results, T_total, T_quatro (optional), valid, status) equals qn_coarse_to_fine_align_batch({ctx}) given the two
+ * described device clouds bit for bit.  T_total[16 j ..] = T_gicp * T_quatro estimates inv(P_c) P_query; valid[j] = Quatro converged && GICP converged &&
+ * score < score_thr (loop_closure.cpp:129, 145-148).  A pair with an empty side: QN_ERR_EMPTY_CLOUD, valid 0, the other pairs still run.
+ * QN_ERR_INVALID_ARG before anything runs (store and context unchanged): a null pointer, n_cand == 0, a bad or repeated id, a candidate equal to the query,
+ * a keyframe never described, or described with radii other than ctx's current Quatro radii or on a context of another grid capacity (max_points), store
+ * and context on different devices.  Memory: the lanes' own, as qn_coarse_to_fine_align_batch; nothing per point beyond it.                        */
+int  qn_kf_verify_loop_candidates_c2f(qn_kf_store*, qn_ctx*, int32_t query, const int32_t* cand, uint32_t n_cand, double score_thr,
+                                      qn_gicp_result* results, double* T_total /* n_cand x 16 */, double* T_quatro /* n_cand x 16 or NULL */,
+                                      int* valid, int* status);
 /* the corrected global map = the three loops of FastLioSamQn that rebuild it from every keyframe with its corrected pose
  * (fast_lio_sam_qn.cpp:302-316 visTimerFunc, :398-411 saveFlagCallback, :435-448 the destructor's result.pcd): transformPcd of each
  * listed keyframe, concatenation in `ids` order (ids may repeat), voxelizePcd at save_voxel_resolution (pcl::VoxelGrid,

@@ -232,15 +232,17 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
     identity).  "relative" (with detector="scancontext"): the query's top sc_top_k candidates with D < sc_max_dist in ONE drift-free verification
     (KeyframeStore.verify_loop_candidates: the query scan in its sensor frame against each candidate's window in the candidate's sensor frame, seeded
     with its Scan Context heading); the valid one with the lowest score gives the loop factor Z = inv(T), variance = score.  The oracle backend
-    rebuilds the same clouds and guesses from the twins (scancontext.relative_pose / seed_from_yaw) and registers them with the CPU oracle."""
+    rebuilds the same clouds and guesses from the twins (scancontext.relative_pose / seed_from_yaw) and registers them with the CPU oracle.
+    "relative" with use_quatro (the reference's default check, scan to scan): every keyframe is described on arrival (KeyframeStore.quatro_describe:
+    its voxel grid in its sensor frame and its FPFH, kept resident) and the candidates go through ONE verify_loop_candidates_c2f (Quatro -> transformPcd
+    -> Nano-GICP from the resident features, no pose involved); the oracle backend runs oracle.coarse_to_fine_alignment on oracle.voxel_grid of the
+    sensor-frame scans."""
     if detector not in ("radius", "scancontext"):
         raise ValueError("detector must be 'radius' or 'scancontext', not %r" % (detector,))
     if verify not in ("reference", "relative"):
         raise ValueError("verify must be 'reference' or 'relative', not %r" % (verify,))
     if verify == "relative" and detector != "scancontext":
         raise ValueError("verify='relative' needs detector='scancontext' (it is seeded with the Scan Context heading)")
-    if verify == "relative" and use_quatro:
-        raise ValueError("verify='relative' registers with Nano-GICP alone (the seed replaces Quatro's coarse alignment)")
     if sensor == "uniform":
         scans, gt, odom, stamps = make_stream(n_kf, seed, yaw_bias=yaw_bias)
     elif sensor == "spinning":
@@ -282,6 +284,8 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
             cand = loop_candidates(pos, stamps[:k + 1], k, radius, tdiff, max_k=1)
         elif backend == "gpu":                                                               # store ids are keyframe indices here
             store.sc_describe([ids[k]])
+            if verify == "relative" and use_quatro:                                          # the keyframe's Quatro features, once, on arrival
+                store.quatro_describe(ctx, [ids[k]], voxel)
             c_ids, c_d, c_sh = store.sc_query([ids[k]], stamps, tdiff, sc_top_k if verify == "relative" else 1)[0]
             cand, shifts = c_ids[c_d < sc_max_dist], c_sh[c_d < sc_max_dist]
         else:
@@ -295,7 +299,12 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
             from qn_amd import scancontext
             cand = [int(x) for x in cand]; yaws = [scancontext.yaw_of_shift(int(x), scancontext.Params().n_sectors) for x in shifts]
             t0 = time.perf_counter()
-            if backend == "gpu":
+            if use_quatro and backend == "gpu":
+                rs = store.verify_loop_candidates_c2f(ctx, ids[k], [ids[x] for x in cand], score_thr)
+            elif use_quatro:
+                rs = [orc.coarse_to_fine_alignment(orc.voxel_grid(scans[k], voxel), orc.voxel_grid(scans[x], voxel), max_corr_dist=1.5 * radius, score_thr=score_thr)
+                      for x in cand]
+            elif backend == "gpu":
                 rs = store.verify_loop_candidates(ctx, ids[k], [ids[x] for x in cand], yaws, corrected[:k + 1], submap_range, voxel, score_thr)
             else:
                 rs = [_oracle_relative(orc, scans, corrected[:k + 1], k, x, y, submap_range, voxel, 1.5 * radius, score_thr) for x, y in zip(cand, yaws)]
@@ -369,7 +378,8 @@ if __name__ == "__main__":
     ap.add_argument("--detector", choices=["radius", "scancontext"], default="radius", help="loop candidates: radius search on corrected poses, or Scan Context")
     ap.add_argument("--yaw-bias", type=float, default=0.006, help="odometry heading drift per keyframe [rad]")
     ap.add_argument("--verify", choices=["reference", "relative"], default="reference",
-                    help="candidate registration: the reference's world-frame submaps from identity, or (with --detector scancontext) drift-free relative submaps seeded with the Scan Context heading")
+                    help="candidate registration: the reference's world-frame submaps from identity, or (with --detector scancontext) drift-free relative submaps seeded with the Scan Context heading "
+                         "(with --quatro: the keyframes' resident Quatro features, scan to scan)")
     ap.add_argument("--sc-top-k", type=int, default=1, help="with --verify relative: Scan Context candidates verified per query, in one batched registration")
     ap.add_argument("--backend", choices=["gpu", "oracle"], default="gpu", help="the engine on the GPU, or the CPU oracle")
     a = ap.parse_args()
