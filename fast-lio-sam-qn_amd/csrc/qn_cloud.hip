@@ -681,6 +681,7 @@ extern "C" int qn_kf_assemble_batch(qn_kf_store* s, const int32_t* ids, const do
   for (uint32_t t = 0; t < n_seg; t++) if (seg_off[t + 1] < seg_off[t]) return QN_ERR_INVALID_ARG;
   if (seg_off[n_seg] != seg_off[0] && (!ids || !poses)) return QN_ERR_INVALID_ARG;
   if (!ids_valid(s, ids, seg_off[0], seg_off[n_seg])) return QN_ERR_INVALID_ARG;
+  qn_kf_int_verify_stale(s, 0, nullptr, 0);                                  // (a multi-pair GICP verification's segments are about to be replaced)
   for (uint32_t t = 0; t < n_seg; t++) { d_xyz_out[t] = nullptr; n_out[t] = 0; status[t] = QN_ERR_EMPTY_CLOUD; }
   s->bt_ptr.assign(n_seg, nullptr); s->bt_n.assign(n_seg, 0); s->last_error.clear();
   std::vector<SubmapOut> res(n_seg); VoxelNotes nt;

@@ -1,5 +1,5 @@
 // qn_kf_quatro.inc - Quatro features of resident keyframes, described once and kept next to their points (qn_kf_quatro_describe), and the drift-free
-// coarse-to-fine verification of loop candidates that borrows them (qn_kf_verify_loop_candidates_c2f).  Included by qn_engine.hip behind qn_quatro_host.inc:
+// coarse-to-fine verification of loop candidates that borrows them (qn_kf_verify_loop_candidates_c2f, and for many queries at once qn_kf_verify_loop_pairs_c2f).  Included by qn_engine.hip behind qn_quatro_host.inc:
 // it drives that file's batched coarse-to-fine machinery (c2f_batch) and qn_batch.inc's lane launches.
 //
 // Scan to scan (config.yaml: quatro/enable true, enable_submap_matching false; loop_closure.cpp:85-92) both clouds of a pair are functions of ONE keyframe each
@@ -187,6 +187,7 @@ extern "C" int qn_kf_quatro_describe(qn_kf_store* s, qn_ctx* ctx, const int32_t*
     c->prof_collect();
   }
   // ---- the entries: describing again replaces (the block of a replaced entry goes when no entry names it)
+  qn_kf_int_verify_stale(s, 1, ids, count);                                         // (a multi-pair coarse-to-fine record that names one of them goes)
   if (st->e.size() < n_kf) st->e.resize(n_kf);
   for (uint32_t i = 0; i < count; i++) {
     KfqEntry& e = st->e[ids[i]];
@@ -252,4 +253,57 @@ extern "C" int qn_kf_verify_loop_candidates_c2f(qn_kf_store* s, qn_ctx* ctx, int
   }
   qn_ctx* const one[1] = {ctx};
   return c2f_batch(one, 1, pairs.data(), n_cand, score_thr, results, T_total, T_quatro, valid, status, cached.data());
+}
+
+extern "C" int qn_kf_verify_loop_pairs_c2f(qn_kf_store* s, qn_ctx* ctx, const int32_t* query, const int32_t* cand, uint32_t n_pairs, double score_thr,
+                                           qn_gicp_result* results, double* T_total, double* T_quatro, int* valid, int* status) {
+  // ---- every argument before anything runs, per pair as qn_kf_verify_loop_candidates_c2f: the store's entries, its verify record and the context stay as they were
+  if (!s || !ctx || !query || !cand || n_pairs == 0 || !results || !T_total || !valid || !status) return QN_ERR_INVALID_ARG;
+  if (qn_kf_int_device(s) != ctx->device) return QN_ERR_INVALID_ARG;
+  qn_quatro_params qp;
+  if (ctx->qparams_set) qp = ctx->qparams; else qn_quatro_default_params(&qp);
+  auto usable = [&](int32_t id) -> const KfqEntry* {
+    if (id < 0 || (size_t)id >= qn_kf_int_count(s)) return nullptr;
+    const KfqEntry* e = kfq_entry(s, id);
+    if (!e || e->rn != qp.fpfh_normal_radius || e->rf != qp.fpfh_radius || e->max_cells != ctx->max_cells) return nullptr;
+    return e;
+  };
+  std::vector<int32_t> uq; std::vector<uint32_t> qi(n_pairs);                    // distinct queries in order of first appearance; pair j -> its place
+  for (uint32_t j = 0; j < n_pairs; j++) {
+    if (cand[j] == query[j] || !usable(query[j]) || !usable(cand[j])) return QN_ERR_INVALID_ARG;
+    for (uint32_t i = 0; i < j; i++) if (query[i] == query[j] && cand[i] == cand[j]) return QN_ERR_INVALID_ARG;
+    uint32_t k = 0;
+    while (k < uq.size() && uq[k] != query[j]) k++;
+    if (k == uq.size()) uq.push_back(query[j]);
+    qi[j] = k;
+  }
+  // ---- the pairs grouped by query (stable), so that the candidates of one query run in consecutive lanes and share the source side; one c2f_batch for all
+  std::vector<uint32_t> order(n_pairs);
+  for (uint32_t j = 0; j < n_pairs; j++) order[j] = j;
+  std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return qi[a] < qi[b]; });
+  std::vector<qn_pair_desc> pairs(n_pairs); std::vector<C2fCached> cached(n_pairs);
+  for (uint32_t k = 0; k < n_pairs; k++) {
+    const KfqEntry* q = usable(query[order[k]]); const KfqEntry* e = usable(cand[order[k]]);
+    pairs[k] = qn_pair_desc{(const float*)q->pts, q->n, (const float*)e->pts, e->n, 16u, 1};
+    cached[k] = C2fCached{q->pts, q->rows, e->pts, e->rows};
+  }
+  std::vector<qn_gicp_result> res(n_pairs); std::vector<double> Tt(16 * (size_t)n_pairs), Tq(16 * (size_t)n_pairs);
+  std::vector<int> val(n_pairs, 0), st(n_pairs, QN_OK), stage(n_pairs, 0);
+  qn_ctx* const one[1] = {ctx};
+  const int rc = c2f_batch(one, 1, pairs.data(), n_pairs, score_thr, res.data(), Tt.data(), Tq.data(), val.data(), st.data(), cached.data(), stage.data());
+  if (rc != QN_OK) return rc;
+  // ---- back into caller order, and the verify record qn_kf_verify_cloud serves
+  std::vector<qn_kf_int_verify_pair> rec(n_pairs);
+  for (uint32_t k = 0; k < n_pairs; k++) {
+    const uint32_t j = order[k];
+    results[j] = res[k]; valid[j] = val[k]; status[j] = st[k];
+    memcpy(T_total + 16 * (size_t)j, Tt.data() + 16 * (size_t)k, 16 * sizeof(double));
+    if (T_quatro) memcpy(T_quatro + 16 * (size_t)j, Tq.data() + 16 * (size_t)k, 16 * sizeof(double));
+    qn_kf_int_verify_pair& r = rec[j];
+    r = qn_kf_int_verify_pair{(const float4*)pairs[k].src, pairs[k].ns, (const float4*)pairs[k].dst, pairs[k].nt, query[j], cand[j],
+                              st[k] == QN_ERR_HIP ? 0 : stage[k], {}, {}};
+    memcpy(r.Tq, Tq.data() + 16 * (size_t)k, sizeof(r.Tq));
+    memcpy(r.Tg, res[k].T, sizeof(r.Tg));
+  }
+  return qn_kf_int_verify_record(s, 1, rec.data(), n_pairs);
 }

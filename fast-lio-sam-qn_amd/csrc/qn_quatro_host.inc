@@ -757,9 +757,10 @@ extern "C" int qn_quatro_get_scale(qn_ctx* c, double* scale) { if (!c || !scale)
 // on_device: both clouds are HIP device pointers (e.g. the voxelised submaps qn_kf_assemble left on the GPU, loop_closure.cpp:177-192):
 // nothing but the <= ~6 KB of selected correspondences and the result record crosses PCIe.
 static int coarse_to_fine(qn_ctx* c, const float* src, uint32_t ns, const float* dst, uint32_t nt, uint32_t stride, bool on_device, double score_thr,
-                          qn_gicp_result* out, double T_total[16], double T_quatro[16], int* valid) {
+                          qn_gicp_result* out, double T_total[16], double T_quatro[16], int* valid, int* stage = nullptr) {
   if (!c || !out || !T_total || !valid) return QN_ERR_INVALID_ARG;
   *valid = 0;
+  if (stage) *stage = 0;                                                          // (stage: 1 = Quatro solved, 2 = the fine stage ran too)
   memset(out, 0, sizeof(*out)); out->fitness = DBL_MAX;
   for (int i = 0; i < 4; i++) { out->T[5 * i] = 1.f; out->T64[5 * i] = 1.0; }      // (a pair Quatro cannot register reports the identity, like the batched entry point - ADVICE r5: the two paths' records are the same bytes)
   for (int i = 0; i < 16; i++) T_total[i] = (i % 5 == 0) ? 1.0 : 0.0;
@@ -791,6 +792,7 @@ static int coarse_to_fine(qn_ctx* c, const float* src, uint32_t ns, const float*
   else rc = quatro_align_impl(c, src, ns, dst, nt, stride, on_device, Tq, &qvalid, nullptr, nullptr);   // :144
   if (T_quatro) memcpy(T_quatro, Tq, sizeof(Tq));
   if (rc != QN_OK) return rc;
+  if (stage) *stage = 1;
   if (!qvalid) return QN_OK;                                                      // :145-148
   // :152 coarse_aligned_ = transformPcd(src, T_q) - done on the device from the source cloud already resident (slot 0, caller order)
   hipStream_t s = c->stream;
@@ -799,6 +801,7 @@ static int coarse_to_fine(qn_ctx* c, const float* src, uint32_t ns, const float*
   int gvalid = 0;
   rc = icp_alignment(c, (const float*)c->aligned, ns, dst, nt, stride, score_thr, out, &gvalid, on_device ? 3 : 2, false, target_ready);   // :153 (the coarse-aligned source stays on the device)
   if (rc != QN_OK) return rc;
+  if (stage) *stage = 2;
   *valid = gvalid;
   for (int a = 0; a < 4; a++) for (int b = 0; b < 4; b++) {                        // :156 pose_between = T_gicp * T_quatro (the f32 GICP result cast to double, :133)
     double v = 0; for (int k = 0; k < 4; k++) v += (double)out->T[4 * a + k] * Tq[4 * k + b];
@@ -875,7 +878,7 @@ int c2f_alloc(qn_ctx* owner, qn_ctx* l) {
 
 // one run of m <= B pairs on `owner`'s lanes.  idx[l] = the pair lane l carries.  cached (or null) = per pair, its resident points and rows (C2fCached)
 int c2f_run(qn_ctx* owner, const qn_pair_desc* pairs, const uint32_t* idx, uint32_t m, double thr, qn_gicp_result* results, double* T_total, double* T_quatro, int* valid, int* status,
-            const C2fCached* cached) {
+            const C2fCached* cached, int* stage) {
   hipStream_t s = owner->stream;
   std::vector<C2fSlot> S(m);
   std::vector<C2fBorrow> borrowed(m);
@@ -986,6 +989,7 @@ int c2f_run(qn_ctx* owner, const qn_pair_desc* pairs, const uint32_t* idx, uint3
         qnq::solve(tr.S, tr.D, c->qparams, &so);
         memcpy(q.Tq, so.T, sizeof(so.T)); q.qvalid = so.valid;
         if (T_quatro) memcpy(T_quatro + 16 * (size_t)q.pair, q.Tq, sizeof(q.Tq));
+        if (stage) stage[q.pair] = 1;
       }
     }
     status[q.pair] = q.rc;
@@ -1011,6 +1015,7 @@ int c2f_run(qn_ctx* owner, const qn_pair_desc* pairs, const uint32_t* idx, uint3
     const C2fSlot& q = S[l];
     status[q.pair] = gst[l];
     if (gst[l] != QN_OK) continue;
+    if (stage) stage[q.pair] = 2;
     results[q.pair] = gres[l]; valid[q.pair] = gval[l];
     double* Tt = T_total + 16 * (size_t)q.pair;
     for (int a = 0; a < 4; a++) for (int b = 0; b < 4; b++) { double v = 0; for (int k = 0; k < 4; k++) v += (double)gres[l].T[4 * a + k] * q.Tq[4 * k + b]; Tt[4 * a + b] = v; }
@@ -1019,12 +1024,14 @@ int c2f_run(qn_ctx* owner, const qn_pair_desc* pairs, const uint32_t* idx, uint3
 }
 }  // namespace
 
-// the driver of qn_coarse_to_fine_align_batch; cached (or null): per pair, resident points and FPFH rows the lanes borrow (qn_kf_verify_loop_candidates_c2f)
+// the driver of qn_coarse_to_fine_align_batch; cached (or null): per pair, resident points and FPFH rows the lanes borrow (qn_kf_verify_loop_candidates_c2f);
+// stage (or null): per pair 0, 1 when T_quatro was solved, 2 when the fine stage ran as well (qn_kf_verify_cloud)
 static int c2f_batch(qn_ctx* const* ctxs, uint32_t n_ctx, const qn_pair_desc* pairs, uint32_t n_pairs, double score_thr,
-                     qn_gicp_result* results, double* T_total, double* T_quatro, int* valid, int* status, const C2fCached* cached) {
+                     qn_gicp_result* results, double* T_total, double* T_quatro, int* valid, int* status, const C2fCached* cached, int* stage = nullptr) {
   if (!ctxs || n_ctx == 0 || (n_pairs && (!pairs || !results || !T_total || !valid || !status))) return QN_ERR_INVALID_ARG;
   for (uint32_t i = 0; i < n_ctx; i++) if (!ctxs[i]) return QN_ERR_INVALID_ARG;
   if (n_pairs == 0) return QN_OK;
+  if (stage) for (uint32_t i = 0; i < n_pairs; i++) stage[i] = 0;
   std::atomic<uint32_t> next{0}, final_share{0};
   std::vector<int> wrc(n_ctx, QN_OK);
   auto worker = [&](uint32_t w) {
@@ -1039,7 +1046,8 @@ static int c2f_batch(qn_ctx* const* ctxs, uint32_t n_ctx, const qn_pair_desc* pa
         const uint32_t i = next.fetch_add(1);
         if (i >= n_pairs) break;
         const qn_pair_desc& p = pairs[i];
-        status[i] = coarse_to_fine(c, p.src, p.ns, p.dst, p.nt, p.stride_bytes, p.on_device != 0, score_thr, &results[i], T_total + 16 * (size_t)i, T_quatro ? T_quatro + 16 * (size_t)i : nullptr, &valid[i]);
+        status[i] = coarse_to_fine(c, p.src, p.ns, p.dst, p.nt, p.stride_bytes, p.on_device != 0, score_thr, &results[i], T_total + 16 * (size_t)i, T_quatro ? T_quatro + 16 * (size_t)i : nullptr, &valid[i],
+                                   stage ? &stage[i] : nullptr);
       }
       return;
     }
@@ -1061,7 +1069,7 @@ static int c2f_batch(qn_ctx* const* ctxs, uint32_t n_ctx, const qn_pair_desc* pa
       }
       if (base >= n_pairs) break;
       for (uint32_t l = 0; l < m; l++) idx[l] = base + l;
-      const int rc = c2f_run(c, pairs, idx.data(), m, score_thr, results, T_total, T_quatro, valid, status, cached);
+      const int rc = c2f_run(c, pairs, idx.data(), m, score_thr, results, T_total, T_quatro, valid, status, cached, stage);
       if (rc != QN_OK) { (void)hipStreamSynchronize(c->stream); for (uint32_t l = 0; l < m; l++) { status[base + l] = rc; valid[base + l] = 0; } wrc[w] = rc; }
     }
     c->pair_pipeline = sp; c->persist_batch_off = sb;

@@ -7,10 +7,14 @@
 // Host code only: the clouds are assembled by qn_kf_assemble_batch and registered by qn_gicp_align_batch_guess, both on the device.
 // The numpy twins (qn_amd/scancontext.py: relative_pose, seed_from_yaw) restate the poses and guesses bit for bit; the build's
 // -ffp-contract=off keeps every product a rounded multiply and a rounded add.
+// qn_kf_verify_loop_pairs runs the same step for many queries at once (one assembly, one registration), and qn_kf_verify_cloud serves the debug clouds
+// loopTimerFunc publishes after each attempt (fast_lio_sam_qn.cpp:245-248) for any pair of the latest multi-pair call, GICP or coarse-to-fine.
 #include <hip/hip_runtime.h>
 #include <cfloat>
 #include <cmath>
+#include <algorithm>
 #include <cstring>
+#include <memory>
 #include <vector>
 #include "../../include/qn_engine.h"
 #include "qn_kf_internal.h"
@@ -105,5 +109,177 @@ extern "C" int qn_kf_verify_loop_candidates(qn_kf_store* s, qn_ctx* ctx, int32_t
   rc = qn_gicp_align_batch_guess(ctx, pairs.data(), g.data(), m, score_thr, res.data(), val.data(), st.data());
   if (rc != QN_OK) return rc;
   for (uint32_t k = 0; k < m; k++) { results[which[k]] = res[k]; valid[which[k]] = val[k]; status[which[k]] = st[k]; }
+  return QN_OK;
+}
+
+// ------------------------------------------------------------------ many queries in one call
+namespace {
+
+// the record of the latest qn_kf_verify_loop_pairs[_c2f] call (store slot QN_KF_INT_EXT_VERIFY) and the arena qn_kf_verify_cloud computes into:
+// COARSE and FINAL of pair j at fixed places (2 * (sum of ns before j), then + ns), so every pointer handed out stays valid until the record is replaced
+struct VerifyState {
+  bool live = false; int c2f = 0;
+  std::vector<qn_kf_int_verify_pair> p; std::vector<size_t> off;
+  float4* arena = nullptr; size_t arena_cap = 0;
+  ~VerifyState() { if (arena) (void)hipFree(arena); }
+};
+void verify_release(void* p) { delete (VerifyState*)p; }
+
+// the two clouds qn_kf_verify_cloud computes: COARSE = transformPcd(src, T_quatro) (k_transform_cloud_f64's f64 order, rounded to f32); FINAL = that (or src on
+// the GICP path) through the GICP T as align() fills aligned_ (k_transform_cloud: xform_query<1> with the f32 entries).  One point per thread.
+struct VerifyXf { double Tq[12]; float Tg[12]; int coarse, fine; };
+__global__ void k_verify_cloud(const float4* __restrict__ in, uint32_t n, VerifyXf m, float4* __restrict__ out) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float4 p = in[i];
+  float x = p.x, y = p.y, z = p.z;
+  if (m.coarse) {
+    const double dx = x, dy = y, dz = z;
+    x = (float)(((m.Tq[0] * dx + m.Tq[1] * dy) + m.Tq[2] * dz) + m.Tq[3]);
+    y = (float)(((m.Tq[4] * dx + m.Tq[5] * dy) + m.Tq[6] * dz) + m.Tq[7]);
+    z = (float)(((m.Tq[8] * dx + m.Tq[9] * dy) + m.Tq[10] * dz) + m.Tq[11]);
+  }
+  if (m.fine) {
+    const float qx = m.Tg[0] * x + (m.Tg[1] * y + (m.Tg[2] * z + m.Tg[3]));
+    const float qy = m.Tg[4] * x + (m.Tg[5] * y + (m.Tg[6] * z + m.Tg[7]));
+    const float qz = m.Tg[8] * x + (m.Tg[9] * y + (m.Tg[10] * z + m.Tg[11]));
+    x = qx; y = qy; z = qz;
+  }
+  out[i] = make_float4(x, y, z, 1.0f);
+}
+
+}  // namespace
+
+int qn_kf_int_verify_record(qn_kf_store* s, int c2f, const qn_kf_int_verify_pair* p, uint32_t n) {
+  VerifyState* st = (VerifyState*)qn_kf_int_ext(s, QN_KF_INT_EXT_VERIFY);
+  if (!st) {
+    st = new (std::nothrow) VerifyState();
+    if (!st) return QN_ERR_HIP;
+    qn_kf_int_set_ext(s, QN_KF_INT_EXT_VERIFY, st, verify_release);
+  }
+  st->c2f = c2f; st->p.assign(p, p + n); st->off.assign(n + 1, 0);
+  for (uint32_t j = 0; j < n; j++) st->off[j + 1] = st->off[j] + 2 * (size_t)p[j].ns;
+  st->live = true;
+  return QN_OK;
+}
+
+void qn_kf_int_verify_stale(qn_kf_store* s, int c2f, const int32_t* ids, uint32_t count) {
+  VerifyState* st = (VerifyState*)qn_kf_int_ext(s, QN_KF_INT_EXT_VERIFY);
+  if (!st || !st->live || st->c2f != c2f) return;
+  if (!c2f) { st->live = false; return; }
+  for (uint32_t i = 0; i < count; i++)
+    for (const qn_kf_int_verify_pair& q : st->p)
+      if (q.query == ids[i] || q.cand == ids[i]) { st->live = false; return; }
+}
+
+extern "C" int qn_kf_verify_loop_pairs(qn_kf_store* s, qn_ctx* ctx, const int32_t* query, const int32_t* cand, const double* yaw, uint32_t n_pairs,
+                                       const double* poses, uint32_t n_poses, uint32_t submap_range, double leaf, double score_thr,
+                                       qn_gicp_result* results, int* valid, int* status) {
+  // ---- every argument before anything runs: the store's batch slot, its verify record and the context stay as they were
+  if (!s || !ctx || !query || !cand || n_pairs == 0 || !poses || !results || !valid || !status || !(leaf > 0)) return QN_ERR_INVALID_ARG;
+  if (qn_kf_int_device(s) != qn_ctx_int_device(ctx)) return QN_ERR_INVALID_ARG;
+  const size_t n_kf = qn_kf_int_count(s);
+  auto bad_id = [&](int32_t id) { return id < 0 || (size_t)id >= n_kf || (uint32_t)id >= n_poses; };
+  std::vector<int32_t> uq, uc;                                                    // distinct queries, distinct candidates, in order of first appearance
+  std::vector<uint32_t> qi(n_pairs), ci(n_pairs);                                 // pair j -> its place in uq / uc
+  auto place = [](std::vector<int32_t>& u, int32_t id) -> uint32_t {
+    for (size_t i = 0; i < u.size(); i++) if (u[i] == id) return (uint32_t)i;
+    u.push_back(id); return (uint32_t)(u.size() - 1);
+  };
+  for (uint32_t j = 0; j < n_pairs; j++) {
+    if (bad_id(query[j]) || bad_id(cand[j]) || cand[j] == query[j]) return QN_ERR_INVALID_ARG;
+    for (uint32_t i = 0; i < j; i++) if (query[i] == query[j] && cand[i] == cand[j]) return QN_ERR_INVALID_ARG;
+    if (yaw && !std::isfinite(yaw[j])) return QN_ERR_INVALID_ARG;
+    qi[j] = place(uq, query[j]); ci[j] = place(uc, cand[j]);
+  }
+  for (size_t i = 0; i < (size_t)n_poses * 16; i++) if (!std::isfinite(poses[i])) return QN_ERR_INVALID_ARG;
+  // ---- the lists: each distinct query alone with the identity, then each distinct candidate's window relative to it - the lists of
+  //      qn_kf_verify_loop_candidates, one segment per distinct keyframe (a window depends on c, the poses and submap_range, never on the query)
+  const uint32_t nq = (uint32_t)uq.size(), S = nq + (uint32_t)uc.size();
+  std::vector<int32_t> ids; std::vector<double> rel; std::vector<uint32_t> seg(S + 1, 0);
+  const double eye[16] = {1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0};
+  for (uint32_t k = 0; k < nq; k++) { ids.push_back(uq[k]); rel.insert(rel.end(), eye, eye + 16); seg[k + 1] = (uint32_t)ids.size(); }
+  for (size_t k = 0; k < uc.size(); k++) {
+    const long long c = uc[k];
+    for (long long i = c - (long long)submap_range; i <= c + (long long)submap_range; i++) {
+      if (i < 0 || i >= (long long)n_poses - 1) continue;                // the reference's `i < keyframes.size() - 1` (loop_closure.cpp:98-104)
+      if ((size_t)i >= n_kf) return QN_ERR_INVALID_ARG;
+      double Q[16];
+      relative_pose(poses + 16 * (size_t)c, poses + 16 * (size_t)i, Q);
+      ids.push_back((int32_t)i); rel.insert(rel.end(), Q, Q + 16);
+    }
+    seg[nq + k + 1] = (uint32_t)ids.size();
+  }
+  // ---- one assembly (two host synchronisations)
+  std::vector<const float*> d_xyz(S, nullptr); std::vector<uint32_t> n(S, 0); std::vector<int> ast(S, QN_OK);
+  int rc = qn_kf_assemble_batch(s, ids.data(), rel.data(), seg.data(), S, leaf, d_xyz.data(), n.data(), ast.data());
+  if (rc != QN_OK) return rc;
+  // ---- one batched registration: the pairs whose clouds exist, grouped by query (stable: caller order within a query) so that the candidates of one
+  //      query sit in consecutive lanes and share the source's preparation
+  std::vector<uint32_t> order(n_pairs);
+  for (uint32_t j = 0; j < n_pairs; j++) order[j] = j;
+  std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return qi[a] < qi[b]; });
+  std::vector<qn_pair_desc> pairs; std::vector<float> g; std::vector<uint32_t> which;
+  for (uint32_t j = 0; j < n_pairs; j++) {
+    unset_record(&results[j]); valid[j] = 0;
+    const int sq = ast[qi[j]], sc = ast[nq + ci[j]];
+    status[j] = sq != QN_OK ? sq : sc;
+  }
+  for (uint32_t j : order) {
+    if (status[j] != QN_OK) continue;
+    const uint32_t a = qi[j], b = nq + ci[j];
+    pairs.push_back(qn_pair_desc{d_xyz[a], n[a], d_xyz[b], n[b], 16, 1});
+    float gj[16];
+    seed_from_yaw(yaw ? yaw[j] : 0.0, gj);
+    g.insert(g.end(), gj, gj + 16);
+    which.push_back(j);
+  }
+  std::vector<qn_kf_int_verify_pair> rec(n_pairs);
+  for (uint32_t j = 0; j < n_pairs; j++) {
+    const uint32_t a = qi[j], b = nq + ci[j];
+    rec[j] = qn_kf_int_verify_pair{(const float4*)d_xyz[a], n[a], (const float4*)d_xyz[b], n[b], query[j], cand[j], 0, {}, {}};
+  }
+  if (!pairs.empty()) {
+    const uint32_t m = (uint32_t)pairs.size();
+    std::vector<qn_gicp_result> res(m); std::vector<int> val(m, 0), st(m, QN_OK);
+    rc = qn_gicp_align_batch_guess(ctx, pairs.data(), g.data(), m, score_thr, res.data(), val.data(), st.data());
+    if (rc != QN_OK) return rc;
+    for (uint32_t k = 0; k < m; k++) {
+      const uint32_t j = which[k];
+      results[j] = res[k]; valid[j] = val[k]; status[j] = st[k];
+      if (st[k] == QN_OK) { rec[j].stage = 2; memcpy(rec[j].Tg, res[k].T, sizeof(rec[j].Tg)); }
+    }
+  }
+  return qn_kf_int_verify_record(s, 0, rec.data(), n_pairs);
+}
+
+extern "C" int qn_kf_verify_cloud(qn_kf_store* s, uint32_t pair, int which, const float** d_xyz, uint32_t* n) {
+  if (!s || !d_xyz || !n || which < QN_VERIFY_SRC || which > QN_VERIFY_FINAL) return QN_ERR_INVALID_ARG;
+  *d_xyz = nullptr; *n = 0;
+  VerifyState* st = (VerifyState*)qn_kf_int_ext(s, QN_KF_INT_EXT_VERIFY);
+  if (!st || !st->live) return QN_ERR_NOT_READY;
+  if (pair >= st->p.size()) return QN_ERR_INVALID_ARG;
+  const qn_kf_int_verify_pair& q = st->p[pair];
+  if (which == QN_VERIFY_SRC) { *d_xyz = (const float*)q.src; *n = q.ns; return QN_OK; }
+  if (which == QN_VERIFY_DST) { *d_xyz = (const float*)q.dst; *n = q.nt; return QN_OK; }
+  // COARSE needs the solved Quatro stage (coarse-to-fine only), FINAL the registration
+  if (which == QN_VERIFY_COARSE ? (!st->c2f || q.stage < 1) : q.stage < 2) return QN_ERR_NOT_READY;
+  if (q.ns == 0 || !q.src) return QN_ERR_NOT_READY;
+  const int dev = qn_kf_int_device(s);
+  hipStream_t stream = qn_kf_int_stream(s);
+  if (hipSetDevice(dev) != hipSuccess) { qn_kf_int_set_error(s, "qn_kf_verify_cloud: hipSetDevice failed"); return QN_ERR_HIP; }
+  const size_t need = st->off.back();
+  if (need > st->arena_cap) {
+    if (st->arena) { (void)hipStreamSynchronize(stream); (void)hipFree(st->arena); st->arena = nullptr; st->arena_cap = 0; }
+    if (hipMalloc(&st->arena, sizeof(float4) * need) != hipSuccess) { (void)hipGetLastError(); st->arena = nullptr; qn_kf_int_set_error(s, "qn_kf_verify_cloud: hipMalloc failed"); return QN_ERR_HIP; }
+    st->arena_cap = need;
+  }
+  float4* out = st->arena + st->off[pair] + (which == QN_VERIFY_FINAL ? q.ns : 0);
+  VerifyXf m{};
+  m.coarse = st->c2f ? 1 : 0; m.fine = which == QN_VERIFY_FINAL ? 1 : 0;
+  for (int i = 0; i < 12; i++) { m.Tq[i] = q.Tq[i]; m.Tg[i] = q.Tg[i]; }
+  hipLaunchKernelGGL(k_verify_cloud, dim3((q.ns + 255) / 256), dim3(256), 0, stream, q.src, q.ns, m, out);
+  if (hipGetLastError() != hipSuccess || hipStreamSynchronize(stream) != hipSuccess) { qn_kf_int_set_error(s, "qn_kf_verify_cloud: the transform failed"); return QN_ERR_HIP; }
+  *d_xyz = (const float*)out; *n = q.ns;
   return QN_OK;
 }

@@ -9,6 +9,7 @@ from . import build as _build
 
 QN_OK, QN_ERR_INVALID_ARG, QN_ERR_EMPTY_CLOUD, QN_ERR_CAPACITY, QN_ERR_NOT_READY, QN_ERR_HIP, QN_ERR_NO_DEVICE = range(7)
 QN_SOURCE, QN_TARGET = 0, 1
+QN_VERIFY_SRC, QN_VERIFY_DST, QN_VERIFY_COARSE, QN_VERIFY_FINAL = 0, 1, 2, 3
 FLOAT_MAX = 3.4028234663852886e38
 KERNEL_FAMILIES = ["grid_build", "knn_cov", "nn_search", "nn_fallback", "accumulate", "solve", "fitness", "transform",
                    "fpfh_normals", "fpfh_spfh", "fpfh_fpfh", "feat_match", "gn_tick_fused", "knn_select", "match_tail", "far_refresh", "align_persist"]
@@ -862,6 +863,63 @@ class KeyframeStore:
         return [dict(valid=bool(valid[j]), converged=bool(results[j].converged), score=results[j].fitness, iterations=results[j].iterations, T=Tt[j].copy(),
                      T_quatro=Tq[j].copy(), T_gicp=np.array(results[j].T, dtype=np.float32).reshape(4, 4).astype(np.float64), status=int(status[j]),
                      record=results[j]) for j in range(K)]
+
+    # ---- many queries in one verification (qn_kf_verify_loop_pairs[_c2f]) and the debug clouds of a verified pair (qn_kf_verify_cloud)
+    @staticmethod
+    def _pairs(query, cand):
+        q = np.ascontiguousarray(np.atleast_1d(query), dtype=np.int32); c = np.ascontiguousarray(np.atleast_1d(cand), dtype=np.int32)
+        if len(q) != len(c):
+            raise ValueError("%d queries but %d candidates" % (len(q), len(c)))
+        return q, c, len(q)
+
+    def verify_loop_pairs(self, ctx, query, cand, yaw, poses, submap_range, leaf, score_thr=1.5):
+        """qn_kf_verify_loop_pairs: pair j = (query[j], cand[j], yaw[j]) checked as verify_loop_candidates(ctx, query[j], [cand[j]], [yaw[j]], ...) would,
+        record for record, but every pair in ONE assembly (each distinct query scan and each distinct candidate window once) and ONE batched registration.
+        yaw None: all 0.  The store's batch slot holds the distinct queries (order of first appearance), then the distinct candidates' windows
+        (download_batch).  -> one dict per pair, as verify_loop_candidates'."""
+        q, c, n = self._pairs(query, cand)
+        y = None if yaw is None else np.ascontiguousarray(np.atleast_1d(yaw), dtype=np.float64)
+        if y is not None and len(y) != n:
+            raise ValueError("verify_loop_pairs: %d pairs but %d yaw values" % (n, len(y)))
+        P = np.ascontiguousarray(np.asarray(poses, dtype=np.float64).reshape(-1, 16))
+        results = (GicpResult * max(n, 1))(); valid = np.zeros(max(n, 1), np.int32); status = np.zeros(max(n, 1), np.int32)
+        st = self._l.qn_kf_verify_loop_pairs(self.h, ctx.h, _p(q) if n else None, _p(c) if n else None, _p(y) if y is not None else None, C.c_uint32(n),
+                                             _p(P), C.c_uint32(len(P)), C.c_uint32(submap_range), C.c_double(leaf), C.c_double(score_thr),
+                                             results, _p(valid), _p(status))
+        if st != QN_OK:
+            raise EngineError(st, self._l.qn_status_str(st).decode() + ": " + self._l.qn_kf_last_error(self.h).decode() + " / " + lib().qn_last_error(ctx.h).decode())
+        self._batch_n = []
+        for seg in range(len(dict.fromkeys(q.tolist())) + len(dict.fromkeys(c.tolist()))):
+            m = C.c_uint32()
+            self._check(self._l.qn_kf_batch_count(self.h, C.c_uint32(seg), C.byref(m)))
+            self._batch_n.append(m.value)
+        return [dict(valid=bool(valid[j]), converged=bool(results[j].converged), score=results[j].fitness, iterations=results[j].iterations,
+                     T=np.array(results[j].T, dtype=np.float32).reshape(4, 4).astype(np.float64), status=int(status[j]), record=results[j]) for j in range(n)]
+
+    def verify_loop_pairs_c2f(self, ctx, query, cand, score_thr=1.5):
+        """qn_kf_verify_loop_pairs_c2f: pair j checked as verify_loop_candidates_c2f(ctx, query[j], [cand[j]]) would, record for record, all pairs in one run
+        of the batched coarse-to-fine lanes on ctx (both sides borrowed from the described keyframes).  -> one dict per pair, as verify_loop_candidates_c2f's."""
+        q, c, n = self._pairs(query, cand)
+        results = (GicpResult * max(n, 1))(); valid = np.zeros(max(n, 1), np.int32); status = np.zeros(max(n, 1), np.int32)
+        Tt = np.zeros((max(n, 1), 4, 4)); Tq = np.zeros((max(n, 1), 4, 4))
+        st = self._l.qn_kf_verify_loop_pairs_c2f(self.h, ctx.h, _p(q) if n else None, _p(c) if n else None, C.c_uint32(n), C.c_double(score_thr),
+                                                 results, _p(Tt), _p(Tq), _p(valid), _p(status))
+        if st != QN_OK:
+            raise EngineError(st, self._l.qn_status_str(st).decode() + ": " + self._l.qn_kf_last_error(self.h).decode() + " / " + lib().qn_last_error(ctx.h).decode())
+        return [dict(valid=bool(valid[j]), converged=bool(results[j].converged), score=results[j].fitness, iterations=results[j].iterations, T=Tt[j].copy(),
+                     T_quatro=Tq[j].copy(), T_gicp=np.array(results[j].T, dtype=np.float32).reshape(4, 4).astype(np.float64), status=int(status[j]),
+                     record=results[j]) for j in range(n)]
+
+    def verify_cloud(self, pair, which):
+        """qn_kf_verify_cloud: cloud `which` (QN_VERIFY_SRC / _DST / _COARSE / _FINAL) of pair `pair` of the latest verify_loop_pairs[_c2f] -> (n, 3) float32"""
+        ptr = C.c_void_p(); n = C.c_uint32()
+        self._check(self._l.qn_kf_verify_cloud(self.h, C.c_uint32(pair), C.c_int(which), C.byref(ptr), C.byref(n)))
+        out = np.zeros((n.value, 4), np.float32)
+        if n.value:
+            l = self._l; l.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]; l.hipMemcpy.restype = C.c_int
+            if l.hipMemcpy(out.ctypes.data, ptr, 16 * n.value, 2) != 0:
+                raise EngineError(QN_ERR_HIP, "verify_cloud: read-back failed")
+        return np.ascontiguousarray(out[:, :3])
 
     # ---- Scan Context loop candidates (qn_kf_sc_*; numpy twin: qn_amd/scancontext.py)
     def sc_set_params(self, params=None, **kw):

@@ -3,7 +3,8 @@
 // descriptor is made on the GPU from its resident keyframe (qn_kf_sc_describe, a no-op when it exists), the older keyframes' descriptors
 // must already exist (describe each keyframe once, when it is added), and qn_kf_sc_query ranks them.  The indices feed
 // qn_map::loopSubmapPairs (loop_submaps.hpp) and the batched registrations; yaw is the candidate's heading minus the query's, from the
-// best column shift: verifyScanContextCandidates seeds each candidate's registration with it.
+// best column shift: verifyScanContextCandidates seeds each candidate's registration with it.  For the keyframes that arrived between two loop-timer
+// ticks, scanContextCandidatesMany ranks them all in one query and verifyLoopPairs / verifyLoopPairsCoarseToFine check every (query, candidate) pair at once.
 // Header-only; forwards to the C-ABI in include/qn_engine.h.  Link with -lqn_engine.  Uses nothing from Eigen or PCL.
 #pragma once
 #include <cmath>
@@ -110,6 +111,102 @@ inline std::vector<ScVerifiedC2f> verifyScanContextCandidatesCoarseToFine(qn_kf_
   if (rc != QN_OK) throw std::runtime_error(std::string("[qn_map] qn_kf_verify_loop_candidates_c2f: ") + qn_status_str(rc) + " " + qn_kf_last_error(store));
   for (size_t k = 0; k < K; k++) {
     ScVerifiedC2f v{c.idx[k], valid[k] != 0, r[k].fitness, {}, {}, status[k]};
+    for (int i = 0; i < 16; i++) { v.T[i] = Tt[16 * k + i]; v.T_quatro[i] = Tq[16 * k + i]; }
+    out.push_back(v);
+  }
+  return out;
+}
+
+struct ScPairs {                                   // flat (query, candidate) pairs, every query's candidates together, nearest first
+  std::vector<int> query;                          // the query's keyframe index
+  std::vector<int> cand;                           // the candidate's keyframe index
+  std::vector<double> dist;                        // Scan Context distance D in [0, 2]
+  std::vector<double> yaw;                         // candidate heading minus query heading [rad], in [-pi, pi)
+};
+
+// scanContextCandidates for many queries (the keyframes added since the last loop-timer tick) in ONE qn_kf_sc_query: each query is described (a no-op when
+// its descriptor exists) and ranked against the keyframes older than it by more than tdiff; the kept candidates (D < max_dist) come back as flat pairs.
+inline ScPairs scanContextCandidatesMany(qn_kf_store* store, const std::vector<double>& stamps, const std::vector<int>& queries, double tdiff, int top_k, double max_dist) {
+  if (top_k <= 0) throw std::invalid_argument("[qn_map] scanContextCandidatesMany: top_k must be positive");
+  ScPairs out;
+  if (queries.empty()) return out;
+  qn_sc_params p{};
+  int rc = qn_kf_sc_get_params(store, &p);
+  const std::vector<int32_t> q(queries.begin(), queries.end());
+  const size_t nq = q.size(), k = (size_t)top_k;
+  if (rc == QN_OK) rc = qn_kf_sc_describe(store, q.data(), (uint32_t)nq);
+  std::vector<int32_t> ids(nq * k), shift(nq * k);
+  std::vector<double> d(nq * k);
+  std::vector<uint32_t> n(nq);
+  if (rc == QN_OK) rc = qn_kf_sc_query(store, q.data(), (uint32_t)nq, stamps.data(), (uint32_t)stamps.size(), tdiff, (uint32_t)top_k, ids.data(), d.data(), shift.data(), n.data());
+  if (rc != QN_OK) throw std::runtime_error(std::string("[qn_map] qn_kf_sc_query: ") + qn_status_str(rc) + " " + qn_kf_last_error(store));
+  const double pi = 3.14159265358979323846;
+  for (size_t i = 0; i < nq; i++)
+    for (uint32_t r = 0; r < n[i]; r++) {
+      const size_t e = i * k + r;
+      if (!(d[e] < max_dist)) continue;
+      double yaw = std::fmod(-2.0 * pi * shift[e] / p.n_sectors + pi, 2.0 * pi);
+      if (yaw < 0) yaw += 2.0 * pi;
+      out.query.push_back(queries[i]); out.cand.push_back(ids[e]); out.dist.push_back(d[e]); out.yaw.push_back(yaw - pi);
+    }
+  return out;
+}
+
+struct ScVerifiedPair {
+  int query;                                       // the query's keyframe index
+  int idx;                                         // the candidate's keyframe index
+  bool valid;                                      // loop_closure.cpp:129 (coarse to fine: and Quatro converged, :145-148)
+  double score;                                    // fitness (of the fine stage)
+  double T[16];                                    // row-major, query sensor frame -> candidate sensor frame: an estimate of inv(P_c) P_query
+  double T_quatro[16];                             // the coarse estimate (coarse to fine only; identity otherwise)
+  int status;                                      // QN_OK, or QN_ERR_EMPTY_CLOUD for an empty side
+};
+
+// verifyScanContextCandidates for every pair at once (qn_kf_verify_loop_pairs): one assembly of each distinct query scan and candidate window, one batched
+// registration on ctx.  Pair j's result equals verifyScanContextCandidates of that pair alone.  In loopTimerFunc each query's best valid pair then gives
+// BetweenFactor(query, c, inv(T), score).
+inline std::vector<ScVerifiedPair> verifyLoopPairs(qn_kf_store* store, qn_ctx* ctx, const ScPairs& c, const std::vector<double>& poses16, int submap_range,
+                                                   double leaf, double score_thr) {
+  std::vector<ScVerifiedPair> out;
+  if (c.cand.empty()) return out;
+  if (submap_range < 0 || poses16.size() % 16 != 0 || c.query.size() != c.cand.size() || c.yaw.size() != c.cand.size())
+    throw std::invalid_argument("[qn_map] verifyLoopPairs: bad submap_range, poses or pairs");
+  const size_t K = c.cand.size();
+  const std::vector<int32_t> q(c.query.begin(), c.query.end()), ids(c.cand.begin(), c.cand.end());
+  std::vector<qn_gicp_result> r(K);
+  std::vector<int> valid(K), status(K);
+  const int rc = qn_kf_verify_loop_pairs(store, ctx, q.data(), ids.data(), c.yaw.data(), (uint32_t)K, poses16.data(), (uint32_t)(poses16.size() / 16),
+                                         (uint32_t)submap_range, leaf, score_thr, r.data(), valid.data(), status.data());
+  if (rc != QN_OK) throw std::runtime_error(std::string("[qn_map] qn_kf_verify_loop_pairs: ") + qn_status_str(rc) + " " + qn_kf_last_error(store));
+  for (size_t k = 0; k < K; k++) {
+    ScVerifiedPair v{c.query[k], c.cand[k], valid[k] != 0, r[k].fitness, {}, {}, status[k]};
+    for (int i = 0; i < 16; i++) { v.T[i] = (double)r[k].T[i]; v.T_quatro[i] = i % 5 == 0 ? 1.0 : 0.0; }
+    out.push_back(v);
+  }
+  return out;
+}
+
+// verifyScanContextCandidatesCoarseToFine for every pair at once (qn_kf_verify_loop_pairs_c2f): one run of the coarse-to-fine lanes from the resident
+// features.  Keyframes not yet described under ctx's radii are described here first, in one call.
+inline std::vector<ScVerifiedPair> verifyLoopPairsCoarseToFine(qn_kf_store* store, qn_ctx* ctx, const ScPairs& c, double leaf, double score_thr) {
+  std::vector<ScVerifiedPair> out;
+  if (c.cand.empty()) return out;
+  if (c.query.size() != c.cand.size()) throw std::invalid_argument("[qn_map] verifyLoopPairsCoarseToFine: bad pairs");
+  const size_t K = c.cand.size();
+  const std::vector<int32_t> q(c.query.begin(), c.query.end()), ids(c.cand.begin(), c.cand.end());
+  std::vector<qn_gicp_result> r(K);
+  std::vector<double> Tt(16 * K), Tq(16 * K);
+  std::vector<int> valid(K), status(K);
+  int rc = qn_kf_verify_loop_pairs_c2f(store, ctx, q.data(), ids.data(), (uint32_t)K, score_thr, r.data(), Tt.data(), Tq.data(), valid.data(), status.data());
+  if (rc == QN_ERR_INVALID_ARG) {                  // (a keyframe not described yet, or under other radii: describe every query and candidate, then once more)
+    std::vector<int32_t> all(ids); all.insert(all.end(), q.begin(), q.end());
+    std::vector<int> st(all.size());
+    rc = qn_kf_quatro_describe(store, ctx, all.data(), (uint32_t)all.size(), leaf, st.data());
+    if (rc == QN_OK) rc = qn_kf_verify_loop_pairs_c2f(store, ctx, q.data(), ids.data(), (uint32_t)K, score_thr, r.data(), Tt.data(), Tq.data(), valid.data(), status.data());
+  }
+  if (rc != QN_OK) throw std::runtime_error(std::string("[qn_map] qn_kf_verify_loop_pairs_c2f: ") + qn_status_str(rc) + " " + qn_kf_last_error(store));
+  for (size_t k = 0; k < K; k++) {
+    ScVerifiedPair v{c.query[k], c.cand[k], valid[k] != 0, r[k].fitness, {}, {}, status[k]};
     for (int i = 0; i < 16; i++) { v.T[i] = Tt[16 * k + i]; v.T_quatro[i] = Tq[16 * k + i]; }
     out.push_back(v);
   }

@@ -334,6 +334,22 @@ int  qn_kf_batch_count(const qn_kf_store*, uint32_t seg, uint32_t* n);      /* p
 int  qn_kf_verify_loop_candidates(qn_kf_store*, qn_ctx*, int32_t query, const int32_t* cand, const double* yaw /* per candidate; NULL = 0 */,
                                   uint32_t n_cand, const double* poses16 /* n_poses x 16 */, uint32_t n_poses, uint32_t submap_range, double leaf,
                                   double score_thr, qn_gicp_result* results, int* valid, int* status);
+/* The same check for arbitrary (query, candidate) pairs of MANY queries in one call - the keyframes that arrived between two loop-timer ticks
+ * (fast_lio_sam_qn.cpp:203-252 checks only keyframes_.back()).  Pair j = (query[j], cand[j], yaw[j]); its record (results[j], valid[j], status[j]) equals
+ * qn_kf_verify_loop_candidates(store, ctx, query[j], &cand[j], &yaw[j], 1, poses16, n_poses, submap_range, leaf, score_thr, ...) bit for bit.  Pairs may
+ * come in any order; queries and candidates may repeat across pairs.  ONE qn_kf_assemble_batch into the store's batch slot, segments in this order:
+ *   segments 0 .. Q - 1     = the distinct queries in order of first appearance, each alone with the identity (the single-query call's segment 0);
+ *   segments Q .. Q + C - 1 = the distinct candidates in order of first appearance, each candidate's window relative to it (a window depends on c, the
+ *                             poses and submap_range only, so each is built once however many queries name it);
+ * then ONE qn_gicp_align_batch_guess over every pair whose two clouds exist, seeded as the single-query call, grouped by query (stable) so that a query's
+ * pairs share the source preparation; the records are scattered back into caller order.  status[j]: the assembly status of the pair's query or candidate
+ * segment (QN_ERR_EMPTY_CLOUD: valid 0, the other pairs still run), else the registration's.  QN_ERR_INVALID_ARG before anything runs (batch slot, verify
+ * record and context unchanged): a null pointer, n_pairs == 0, a bad id, cand[j] == query[j], a repeated (query, cand) pair, an id >= n_poses, a
+ * non-finite pose or yaw, leaf <= 0, or store and context on different devices.  Host synchronisations: the assembly's two and the registration's own,
+ * whatever n_pairs is.                                                                                                                                */
+int  qn_kf_verify_loop_pairs(qn_kf_store*, qn_ctx*, const int32_t* query, const int32_t* cand, const double* yaw /* per pair; NULL = 0 */, uint32_t n_pairs,
+                             const double* poses16 /* n_poses x 16 */, uint32_t n_poses, uint32_t submap_range, double leaf,
+                             double score_thr, qn_gicp_result* results, int* valid, int* status);
 /* Resident Quatro descriptors per keyframe, for the reference's default scan-to-scan check (quatro/enable true, enable_submap_matching false:
  * loop_closure.cpp:85-92, 138-159, 188-192), where each cloud of a pair is one keyframe in its own sensor frame and depends on no pose.
  * qn_kf_quatro_describe: for each listed keyframe, its cloud = qn_kf_assemble({id}, {identity}, leaf) in all 16 bytes of every record (the store's voxel
@@ -364,6 +380,31 @@ int  qn_kf_quatro_features(qn_kf_store*, int32_t id, float* fpfh33_out /* n x 33
 int  qn_kf_verify_loop_candidates_c2f(qn_kf_store*, qn_ctx*, int32_t query, const int32_t* cand, uint32_t n_cand, double score_thr,
                                       qn_gicp_result* results, double* T_total /* n_cand x 16 */, double* T_quatro /* n_cand x 16 or NULL */,
                                       int* valid, int* status);
+/* The coarse-to-fine check for arbitrary (query, candidate) pairs of many queries: pair j's record (results[j], T_total[16 j ..], T_quatro[16 j ..], valid[j],
+ * status[j]) equals qn_kf_verify_loop_candidates_c2f(store, ctx, query[j], &cand[j], 1, ...) bit for bit.  All pairs go through ONE run of the batched
+ * coarse-to-fine machinery on ctx, each lane borrowing the described clouds and FPFH rows; the pairs are grouped by query (stable) so that a query's pairs
+ * share the source side, and the records come back in caller order.  QN_ERR_INVALID_ARG before anything runs: the single-query call's checks applied
+ * to every pair, n_pairs == 0, or a repeated (query, cand) pair.                                                                                     */
+int  qn_kf_verify_loop_pairs_c2f(qn_kf_store*, qn_ctx*, const int32_t* query, const int32_t* cand, uint32_t n_pairs, double score_thr,
+                                 qn_gicp_result* results, double* T_total /* n_pairs x 16 */, double* T_quatro /* n_pairs x 16 or NULL */,
+                                 int* valid, int* status);
+/* The debug clouds loopTimerFunc publishes after an attempt (/src, /dst, /coarse_aligned_quatro, /fine_aligned_nano_gicp: fast_lio_sam_qn.cpp:245-248,
+ * loop_closure.cpp:207-231) for pair `pair` of the store's latest qn_kf_verify_loop_pairs[_c2f] call, as a device pointer (float4, stride 16) and count:
+ *   QN_VERIFY_SRC    the query's segment (GICP path) / the query's described cloud (coarse-to-fine path);
+ *   QN_VERIFY_DST    the candidate's segment / the candidate's described cloud;
+ *   QN_VERIFY_COARSE coarse-to-fine only: transformPcd(src, T_quatro) in k_transform_cloud_f64's arithmetic (((T0 x + T1 y) + T2 z) + T3 in f64, rounded to f32);
+ *   QN_VERIFY_FINAL  the GICP stage's source (src, or COARSE) through the pair's f32 GICP T as align() fills aligned_ (T0 x + (T1 y + (T2 z + T3)) in f32):
+ *                    what qn_gicp_transformed_source gives after the equivalent one-pair registration.
+ * COARSE and FINAL are computed on demand (one launch, one synchronisation on the store's stream) into a store-owned buffer, one place per pair and cloud.
+ * QN_ERR_NOT_READY: no such call yet, its clouds are gone (see below), COARSE on the GICP path, or a pair whose stage did not run (no solved Quatro for
+ * COARSE, no registration for FINAL).  QN_ERR_INVALID_ARG: a null pointer, pair >= that call's n_pairs, or a bad `which`.  The pointers stay valid until
+ * the next qn_kf_verify_loop_pairs[_c2f] call, the next qn_kf_assemble_batch on the store (any caller: the GICP path's clouds live in its batch slot), a
+ * qn_kf_quatro_describe of a keyframe the latest coarse-to-fine call involved, or the store's destruction.                                             */
+#define QN_VERIFY_SRC 0
+#define QN_VERIFY_DST 1
+#define QN_VERIFY_COARSE 2
+#define QN_VERIFY_FINAL 3
+int  qn_kf_verify_cloud(qn_kf_store*, uint32_t pair, int which, const float** d_xyz /* float4, stride 16 */, uint32_t* n);
 /* the corrected global map = the three loops of FastLioSamQn that rebuild it from every keyframe with its corrected pose
  * (fast_lio_sam_qn.cpp:302-316 visTimerFunc, :398-411 saveFlagCallback, :435-448 the destructor's result.pcd): transformPcd of each
  * listed keyframe, concatenation in `ids` order (ids may repeat), voxelizePcd at save_voxel_resolution (pcl::VoxelGrid,

@@ -222,7 +222,7 @@ def _oracle_relative(orc, scans, poses, k, c, yaw, submap_range, voxel, max_corr
 
 
 def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, submap_range=5, score_thr=1.5, verbose=True, backend="gpu", save_dir=None,
-        save_map_leaf=None, sensor="uniform", detector="radius", sc_max_dist=0.3, yaw_bias=0.006, verify="reference", sc_top_k=1):
+        save_map_leaf=None, sensor="uniform", detector="radius", sc_max_dist=0.3, yaw_bias=0.006, verify="reference", sc_top_k=1, loop_every=1, catch_up=False):
     """sensor = "uniform": keyframe clouds sampled uniformly by area inside a disc (make_stream); "spinning": ray-cast spinning-LiDAR
     scans from the ground-truth poses of the same figure-8 (make_lidar_stream).  detector = "radius": the candidate is the closest older
     keyframe within `radius` of the corrected position (LC:34-56); "scancontext": the older keyframe nearest by Scan Context distance, kept
@@ -236,13 +236,22 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
     "relative" with use_quatro (the reference's default check, scan to scan): every keyframe is described on arrival (KeyframeStore.quatro_describe:
     its voxel grid in its sensor frame and its FPFH, kept resident) and the candidates go through ONE verify_loop_candidates_c2f (Quatro -> transformPcd
     -> Nano-GICP from the resident features, no pose involved); the oracle backend runs oracle.coarse_to_fine_alignment on oracle.voxel_grid of the
-    sensor-frame scans."""
+    sensor-frame scans.
+    loop_every = N > 1 (verify="relative", detector="scancontext"): the loop timer fires after every N-th keyframe instead of after each one (loop_update_hz,
+    fast_lio_sam_qn.cpp:203-252); every keyframe is described on arrival.  Without catch_up a tick checks only the newest keyframe, as the reference's
+    timer does (keyframes_.back()); with catch_up it checks every keyframe added since the last tick: one sc_query for all of them, then ONE
+    verify_loop_pairs (verify_loop_pairs_c2f with use_quatro) for all their pairs; each query's best valid candidate becomes a factor (Z = inv(T),
+    variance = score), then one optimisation.  The oracle backend runs the same pairs through the twins and the CPU oracle.  loop_every = 1 is the loop above."""
     if detector not in ("radius", "scancontext"):
         raise ValueError("detector must be 'radius' or 'scancontext', not %r" % (detector,))
     if verify not in ("reference", "relative"):
         raise ValueError("verify must be 'reference' or 'relative', not %r" % (verify,))
     if verify == "relative" and detector != "scancontext":
         raise ValueError("verify='relative' needs detector='scancontext' (it is seeded with the Scan Context heading)")
+    if int(loop_every) < 1:
+        raise ValueError("loop_every must be >= 1, not %r" % (loop_every,))
+    if (loop_every > 1 or catch_up) and (verify != "relative" or detector != "scancontext"):
+        raise ValueError("loop_every > 1 / catch_up need verify='relative' and detector='scancontext'")
     if sensor == "uniform":
         scans, gt, odom, stamps = make_stream(n_kf, seed, yaw_bias=yaw_bias)
     elif sensor == "spinning":
@@ -268,7 +277,7 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
             scans = [synth.lidar_scan(prims, lidar, T, int(sd))[:, :3] for T, sd in zip(gt, seeds)]
     pg = PoseGraph(); ids = []; corrected = []; sc_descs = {}
     prior_var = np.array([1e-4, 1e-4, 1e-4, 1e-2, 1e-2, 1e-2]); odom_var = prior_var.copy()   # FQ:112-114, 132-133 (rot, then trans)
-    loops = []; t_reg = []; loop_T = []
+    loops = []; t_reg = []; loop_T = []; last_tick = -1
     for k in range(n_kf):
         if backend == "gpu":
             ids.append(store.add(scans[k]) if scans is not None else cast_ids[k])
@@ -278,6 +287,54 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
             pg.add_prior(0, pose, prior_var)
         else:
             pg.add_between(k - 1, k, inv(odom[k - 1]) @ odom[k], odom_var)
+        if loop_every > 1 or catch_up:                                                      # ---- a timer that fires every loop_every keyframes
+            from qn_amd import scancontext
+            if backend == "gpu":                                                             # every keyframe is described on arrival
+                store.sc_describe([ids[k]])
+                if use_quatro:
+                    store.quatro_describe(ctx, [ids[k]], voxel)
+            else:
+                sc_descs[k] = scancontext.descriptor(scans[k])
+            if (k + 1) % loop_every:
+                continue
+            queries = list(range(last_tick + 1, k + 1)) if catch_up else [k]
+            last_tick = k
+            if backend == "gpu":
+                found = [(c_ids[c_d < sc_max_dist], c_sh[c_d < sc_max_dist]) for c_ids, c_d, c_sh in store.sc_query([ids[q] for q in queries], stamps, tdiff, sc_top_k)]
+            else:
+                found = []
+                for q in queries:
+                    best = scancontext.query(sc_descs, q, stamps, tdiff, sc_top_k)
+                    found.append(([b[0] for b in best if b[1] < sc_max_dist], [b[2] for b in best if b[1] < sc_max_dist]))
+            pq, pc, py = [], [], []
+            for q, (cs, shs) in zip(queries, found):
+                for x, sh in zip(cs, shs):
+                    pq.append(q); pc.append(int(x)); py.append(scancontext.yaw_of_shift(int(sh), scancontext.Params().n_sectors))
+            if not pq:
+                continue
+            t0 = time.perf_counter()
+            if use_quatro and backend == "gpu":
+                rs = store.verify_loop_pairs_c2f(ctx, [ids[q] for q in pq], [ids[x] for x in pc], score_thr)
+            elif use_quatro:
+                rs = [orc.coarse_to_fine_alignment(orc.voxel_grid(scans[q], voxel), orc.voxel_grid(scans[x], voxel), max_corr_dist=1.5 * radius, score_thr=score_thr)
+                      for q, x in zip(pq, pc)]
+            elif backend == "gpu":
+                rs = store.verify_loop_pairs(ctx, [ids[q] for q in pq], [ids[x] for x in pc], py, corrected[:k + 1], submap_range, voxel, score_thr)
+            else:
+                rs = [_oracle_relative(orc, scans, corrected[:k + 1], q, x, y, submap_range, voxel, 1.5 * radius, score_thr) for q, x, y in zip(pq, pc, py)]
+            t_reg.append(time.perf_counter() - t0)
+            added = False
+            for q in queries:
+                ok = [(rs[j]["score"], j) for j in range(len(pq)) if pq[j] == q and rs[j]["valid"]]
+                if not ok:
+                    continue
+                score, j = min(ok)
+                pg.add_between(q, pc[j], inv(rs[j]["T"]), np.full(6, max(score, 1e-6)))      # T ~ inv(P_c) P_q
+                loops.append((q, pc[j], score)); loop_T.append(rs[j]["T"]); added = True
+            if added:
+                pg.optimize()
+                corrected = [p.copy() for p in pg.poses]
+            continue
         # ---- loopTimerFunc
         if detector == "radius":
             pos = np.array([c[:3, 3] for c in corrected])
@@ -354,7 +411,7 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
         corrected = [p.copy() for p in pg.poses]                                             # FQ:180-188
     out = dict(sensor=sensor, detector=detector, n_keyframes=n_kf, loops=len(loops), attempts=len(t_reg), ate_odometry=ate(odom, gt), ate_corrected=ate(corrected, gt),
                ms_per_attempt=1e3 * float(np.mean(t_reg)) if t_reg else None, quatro=use_quatro, verify=verify, loop_list=loops, poses=corrected,
-               loop_T=loop_T, gt=gt)
+               loop_T=loop_T, gt=gt, loop_every=loop_every, catch_up=catch_up)
     if save_dir:
         write_kitti_tum(save_dir, corrected, stamps)
         if save_map_leaf is not None and backend == "gpu":
@@ -381,7 +438,9 @@ if __name__ == "__main__":
                     help="candidate registration: the reference's world-frame submaps from identity, or (with --detector scancontext) drift-free relative submaps seeded with the Scan Context heading "
                          "(with --quatro: the keyframes' resident Quatro features, scan to scan)")
     ap.add_argument("--sc-top-k", type=int, default=1, help="with --verify relative: Scan Context candidates verified per query, in one batched registration")
+    ap.add_argument("--loop-every", type=int, default=1, help="with --verify relative: the loop timer fires after every N-th keyframe (loop_update_hz)")
+    ap.add_argument("--catch-up", action="store_true", help="with --loop-every: a tick checks every keyframe added since the last one, in one batched verification")
     ap.add_argument("--backend", choices=["gpu", "oracle"], default="gpu", help="the engine on the GPU, or the CPU oracle")
     a = ap.parse_args()
     run(a.keyframes, a.seed, a.quatro, save_dir=a.save_dir, save_map_leaf=a.save_map_leaf, sensor=a.sensor, detector=a.detector, yaw_bias=a.yaw_bias,
-        verify=a.verify, sc_top_k=a.sc_top_k, backend=a.backend)
+        verify=a.verify, sc_top_k=a.sc_top_k, backend=a.backend, loop_every=a.loop_every, catch_up=a.catch_up)
