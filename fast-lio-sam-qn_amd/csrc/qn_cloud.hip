@@ -681,7 +681,7 @@ extern "C" int qn_kf_assemble_batch(qn_kf_store* s, const int32_t* ids, const do
   for (uint32_t t = 0; t < n_seg; t++) if (seg_off[t + 1] < seg_off[t]) return QN_ERR_INVALID_ARG;
   if (seg_off[n_seg] != seg_off[0] && (!ids || !poses)) return QN_ERR_INVALID_ARG;
   if (!ids_valid(s, ids, seg_off[0], seg_off[n_seg])) return QN_ERR_INVALID_ARG;
-  qn_kf_int_verify_stale(s, 0, nullptr, 0);                                  // (a multi-pair GICP verification's segments are about to be replaced)
+  qn_kf_int_verify_stale(s, QN_KF_VERIFY_FROM_BATCH, nullptr, 0);                                  // (a multi-pair GICP verification's segments are about to be replaced)
   for (uint32_t t = 0; t < n_seg; t++) { d_xyz_out[t] = nullptr; n_out[t] = 0; status[t] = QN_ERR_EMPTY_CLOUD; }
   s->bt_ptr.assign(n_seg, nullptr); s->bt_n.assign(n_seg, 0); s->last_error.clear();
   std::vector<SubmapOut> res(n_seg); VoxelNotes nt;
@@ -697,24 +697,29 @@ extern "C" int qn_kf_assemble_batch(qn_kf_store* s, const int32_t* ids, const do
   return QN_OK;
 }
 
-int qn_kf_int_voxel_each(qn_kf_store* s, const int32_t* ids, uint32_t count, double leaf, float4** block, const float4** ptr, uint32_t* n, int* status) {
+int qn_kf_int_voxel_windows(qn_kf_store* s, const int32_t* ids, const double* poses, const uint32_t* seg_off, uint32_t n_seg, double leaf,
+                            float4** block, const float4** ptr, uint32_t* n, int* status) {
   *block = nullptr;
-  for (uint32_t t = 0; t < count; t++) { ptr[t] = nullptr; n[t] = 0; status[t] = QN_ERR_EMPTY_CLOUD; }
-  if (count == 0) return QN_OK;
+  for (uint32_t t = 0; t < n_seg; t++) { ptr[t] = nullptr; n[t] = 0; status[t] = QN_ERR_EMPTY_CLOUD; }
+  if (n_seg == 0) return QN_OK;
+  std::vector<SubmapOut> res(n_seg); VoxelNotes nt;
+  Buf<float4> out;
+  s->last_error.clear();
+  const int rc = voxel_submaps(s, ids, poses, seg_off, n_seg, leaf, false, false, out, res.data(), &nt);
+  if (rc != QN_OK) { dev_free(out); return rc; }
+  if (nt.nonfinite) s->last_error = kNonFiniteNote;
+  if (nt.tripped) s->last_error = kOverflowWarning;
+  for (uint32_t t = 0; t < n_seg; t++) { ptr[t] = res[t].ptr; n[t] = res[t].n; status[t] = res[t].status; }
+  *block = out.p;
+  return QN_OK;
+}
+
+int qn_kf_int_voxel_each(qn_kf_store* s, const int32_t* ids, uint32_t count, double leaf, float4** block, const float4** ptr, uint32_t* n, int* status) {
   std::vector<uint32_t> seg(count + 1);
   for (uint32_t t = 0; t <= count; t++) seg[t] = t;
   std::vector<double> eye(16 * (size_t)count, 0.0);
   for (uint32_t t = 0; t < count; t++) for (int i = 0; i < 4; i++) eye[16 * (size_t)t + 5 * i] = 1.0;
-  std::vector<SubmapOut> res(count); VoxelNotes nt;
-  Buf<float4> out;
-  s->last_error.clear();
-  const int rc = voxel_submaps(s, ids, eye.data(), seg.data(), count, leaf, false, false, out, res.data(), &nt);
-  if (rc != QN_OK) { dev_free(out); return rc; }
-  if (nt.nonfinite) s->last_error = kNonFiniteNote;
-  if (nt.tripped) s->last_error = kOverflowWarning;
-  for (uint32_t t = 0; t < count; t++) { ptr[t] = res[t].ptr; n[t] = res[t].n; status[t] = res[t].status; }
-  *block = out.p;
-  return QN_OK;
+  return qn_kf_int_voxel_windows(s, ids, eye.data(), seg.data(), count, leaf, block, ptr, n, status);
 }
 
 extern "C" int qn_kf_batch_count(const qn_kf_store* s, uint32_t seg, uint32_t* n) {

@@ -1400,3 +1400,4 @@ extern "C" int qn_debug_get_grid(qn_ctx* c, int which, double out[8]) {
 #include "qn_batch.inc"
 #include "qn_quatro_host.inc"
 #include "qn_kf_quatro.inc"
+#include "qn_kf_submap.inc"

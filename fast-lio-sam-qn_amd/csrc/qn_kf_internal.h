@@ -23,12 +23,13 @@ void qn_kf_int_append(qn_kf_store* s, float4* const* bufs, const uint32_t* n, ui
 // the resident float4 records of keyframe `id` (0 <= id < qn_kf_int_count; not checked) and their number (nullptr when n == 0)
 const float4* qn_kf_int_keyframe(const qn_kf_store* s, int32_t id, uint32_t* n);
 // per-store state of another translation unit (slot QN_KF_INT_EXT_SC: qn_sc.hip's descriptors, QN_KF_INT_EXT_QUATRO: the resident Quatro features of
-// qn_kf_quatro.inc, QN_KF_INT_EXT_VERIFY: qn_verify.hip's record of the latest multi-pair verification): nullptr until set; the store owns it from
-// qn_kf_int_set_ext on and calls `release` from qn_kf_store_destroy once its stream has drained.
-#define QN_KF_INT_EXT 3
+// qn_kf_quatro.inc, QN_KF_INT_EXT_VERIFY: qn_verify.hip's record of the latest multi-pair verification, QN_KF_INT_EXT_SUBMAP: the resident local submaps of
+// qn_kf_submap.inc): nullptr until set; the store owns it from qn_kf_int_set_ext on and calls `release` from qn_kf_store_destroy once its stream has drained.
+#define QN_KF_INT_EXT 4
 #define QN_KF_INT_EXT_SC 0
 #define QN_KF_INT_EXT_QUATRO 1
 #define QN_KF_INT_EXT_VERIFY 2
+#define QN_KF_INT_EXT_SUBMAP 3
 typedef void (*qn_kf_int_release_fn)(void*);
 void* qn_kf_int_ext(const qn_kf_store* s, int which);
 void qn_kf_int_set_ext(qn_kf_store* s, int which, void* p, qn_kf_int_release_fn release);
@@ -37,10 +38,26 @@ void qn_kf_int_set_ext(qn_kf_store* s, int which, void* p, qn_kf_int_release_fn 
 // that the caller owns from here on (hipFree); ptr / n / status per keyframe as qn_kf_assemble_batch's.  The store's assemble, map and batch slots are
 // not touched.  Two host synchronisations.  ids are not checked.
 int qn_kf_int_voxel_each(qn_kf_store* s, const int32_t* ids, uint32_t count, double leaf, float4** block, const float4** ptr, uint32_t* n, int* status);
-// qn_verify.hip: what qn_kf_verify_cloud serves for pair j of the latest qn_kf_verify_loop_pairs[_c2f] call.  src / dst: the pair's two clouds (batch segments
-// on the GICP path, described clouds on the coarse-to-fine path); stage: 0 nothing registered, 1 T_quatro solved (coarse-to-fine only), 2 the GICP stage ran
-// (Tg = its f32 T).  qn_kf_int_verify_record replaces the store's record; qn_kf_int_verify_stale drops it when the clouds it names go away: c2f = 0, the batch
-// slot is rebuilt (ids ignored); c2f = 1, keyframes ids[0 .. count) are described again.
+// the general form: submap t = keyframes ids[seg_off[t] .. seg_off[t + 1]) with the poses of the same entries (row-major 4x4 f64), what qn_kf_assemble_batch builds
+// for those lists - the same pipeline, the same bytes - but into ONE new allocation the caller owns (as above) instead of the store's batch slot.
+int qn_kf_int_voxel_windows(qn_kf_store* s, const int32_t* ids, const double* poses, const uint32_t* seg_off, uint32_t n_seg, double leaf,
+                            float4** block, const float4** ptr, uint32_t* n, int* status);
+// qn_verify.hip: what qn_kf_verify_cloud serves for pair j of the latest multi-pair verification.  src / dst: the pair's two clouds (batch segments on the
+// GICP path, described clouds on the coarse-to-fine path, resident local submaps on the two submap paths); stage: 0 nothing registered, 1 T_quatro solved
+// (coarse-to-fine only), 2 the GICP stage ran (Tg = its f32 T).  qn_kf_int_verify_record replaces the store's record; `kind` says which call made it.
+// qn_kf_int_verify_stale drops it when the clouds it names go away.  from = where those clouds live: QN_KF_VERIFY_FROM_BATCH, the batch slot is rebuilt (ids
+// ignored); _FROM_SCANS / _FROM_SUBMAPS, the scan / local-submap entries of keyframes ids[0 .. count) are replaced or released (ids == nullptr: all of them).
+#define QN_KF_VERIFY_GICP 0
+#define QN_KF_VERIFY_C2F 1
+#define QN_KF_VERIFY_SUBMAP 2
+#define QN_KF_VERIFY_SUBMAP_C2F 3
+#define QN_KF_VERIFY_FROM_BATCH 0
+#define QN_KF_VERIFY_FROM_SCANS 1
+#define QN_KF_VERIFY_FROM_SUBMAPS 2
 struct qn_kf_int_verify_pair { const float4* src; uint32_t ns; const float4* dst; uint32_t nt; int32_t query, cand; int stage; double Tq[16]; float Tg[16]; };
-int  qn_kf_int_verify_record(qn_kf_store* s, int c2f, const qn_kf_int_verify_pair* p, uint32_t n);
-void qn_kf_int_verify_stale(qn_kf_store* s, int c2f, const int32_t* ids, uint32_t count);
+int  qn_kf_int_verify_record(qn_kf_store* s, int kind, const qn_kf_int_verify_pair* p, uint32_t n);
+void qn_kf_int_verify_stale(qn_kf_store* s, int from, const int32_t* ids, uint32_t count);
+// the pose and seed arithmetic qn_kf_verify_loop_candidates documents (include/qn_engine.h): Q = inv(Pc) Pi with inv(P) = [R^T | -R^T t], every entry summed
+// in order in f64; g = Rz(-yaw) from the C library's cos / sin in f64, each entry rounded to f32.  Twins: scancontext.relative_pose / seed_from_yaw.
+void qn_kf_int_relative_pose(const double* Pc, const double* Pi, double* Q);
+void qn_kf_int_seed_from_yaw(double yaw, float* g);

@@ -79,31 +79,12 @@ int kfq_fixed(qn_ctx* c, KfqState* st, uint32_t slots) {
   return QN_OK;
 }
 
-}  // namespace
-
-extern "C" int qn_kf_quatro_describe(qn_kf_store* s, qn_ctx* ctx, const int32_t* ids, uint32_t count, double leaf, int* status) {
-  // ---- every argument before anything runs
-  if (!s || !ctx || !ids || count == 0 || !status || !(leaf > 0)) return QN_ERR_INVALID_ARG;
-  if (qn_kf_int_device(s) != ctx->device) return QN_ERR_INVALID_ARG;
-  const size_t n_kf = qn_kf_int_count(s);
-  for (uint32_t i = 0; i < count; i++) if (ids[i] < 0 || (size_t)ids[i] >= n_kf) return QN_ERR_INVALID_ARG;
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  qn_ctx* c = ctx;
-  if (!c->qparams_set) { qn_quatro_default_params(&c->qparams); c->qparams_set = true; }
-  KfqState* st = (KfqState*)qn_kf_int_ext(s, QN_KF_INT_EXT_QUATRO);
-  if (!st) { st = new KfqState(); qn_kf_int_set_ext(s, QN_KF_INT_EXT_QUATRO, st, kfq_release); }
-  // ---- the clouds: one batch of `count` identity-pose submaps through the store's voxel pipeline (two host synchronisations), into a new block
-  std::vector<const float4*> vp(count, nullptr); std::vector<uint32_t> vn(count, 0); std::vector<int> vs(count, QN_ERR_EMPTY_CLOUD);
-  float4* vblock = nullptr;
-  int rc = qn_kf_int_voxel_each(s, ids, count, leaf, &vblock, vp.data(), vn.data(), vs.data());
-  if (rc != QN_OK) return rc;                                                       // (an allocation failure: no entry changed)
-  auto blk = std::make_shared<KfqBlock>(); blk->pts = vblock;
-  size_t total = 0; std::vector<size_t> roff(count, 0);
-  for (uint32_t i = 0; i < count; i++) if (vs[i] == QN_OK) { roff[i] = total; total += vn[i]; }
-  if (total) {
-    if (hipMalloc(&blk->rows, sizeof(float) * QN_FROW * total) != hipSuccess) { (void)hipGetLastError(); blk->rows = nullptr; c->last_error = "qn_kf_quatro_describe: hipMalloc of the FPFH rows failed"; qn_kf_int_set_error(s, c->last_error.c_str()); return QN_ERR_HIP; }
-  }
+// K9-K11 of `count` resident clouds (vp / vn / vs: pointer, points, status; only the QN_OK ones are described) with c's Quatro radii, cloud i's rows at
+// rows + QN_FROW * roff[i] in original point order: the grids and the three feature stages of a chunk of clouds ride in nine k_lanes launches, the cloud as
+// blockIdx.y.  Shared by qn_kf_quatro_describe (single scans) and qn_kf_submap_describe (windows of scans); st = the scratch both use.  Ends synchronised.
+int kfq_rows(qn_kf_store* s, qn_ctx* c, KfqState* st, const float4* const* vp, const uint32_t* vn, const int* vs, uint32_t count, float* rows, const size_t* roff) {
   // ---- K9-K11 of every non-empty keyframe, a chunk of keyframes per nine k_lanes launches
+  int rc = QN_OK;
   const double rn_d = c->qparams.fpfh_normal_radius, rf_d = c->qparams.fpfh_radius;
   const float rn = (float)rn_d, rf = (float)rf_d, rn2 = (float)(rn_d * rn_d), rf2 = (float)(rf_d * rf_d);
   std::vector<uint32_t> live;
@@ -175,7 +156,7 @@ extern "C" int qn_kf_quatro_describe(qn_kf_store* s, qn_ctx* ctx, const int32_t*
       lane_push(v_nrm, NormalsK<8>::Args{b.grid, rn, rn2, nrm}, nb * 8u);
       lane_push(v_spfh, SpfhK<8>::Args{b.grid, rf, rf2, nrm, spfh}, nb * 8u);
       lane_push(v_fpfh, FpfhK<8>::Args{b.grid, rf, rf2, nrm, spfh, fpfh_s}, nb * 8u);
-      lane_push(v_rows, RowsToOriginalK::Args{b.sorted, n, fpfh_s, blk->rows + QN_FROW * roff[i], QN_FROW, QN_FROW}, nb);
+      lane_push(v_rows, RowsToOriginalK::Args{b.sorted, n, fpfh_s, rows + QN_FROW * roff[i], QN_FROW, QN_FROW}, nb);
     }
     c->bbox_acc = save_acc; c->scan_status = save_status; c->build_epoch = save_epoch; c->cell_override = save_cell;
     plan.add<PackBBoxK>(v_pack, QN_K_GRID_BUILD); plan.add<CellCountK>(v_count, QN_K_GRID_BUILD); plan.add<ScanLookbackK>(v_scan, QN_K_GRID_BUILD); plan.add<ScatterK>(v_scat, QN_K_GRID_BUILD); plan.add<StableCellsK>(v_stab, QN_K_GRID_BUILD);
@@ -186,8 +167,38 @@ extern "C" int qn_kf_quatro_describe(qn_kf_store* s, qn_ctx* ctx, const int32_t*
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->prof_collect();
   }
+  return QN_OK;
+}
+
+}  // namespace
+
+extern "C" int qn_kf_quatro_describe(qn_kf_store* s, qn_ctx* ctx, const int32_t* ids, uint32_t count, double leaf, int* status) {
+  // ---- every argument before anything runs
+  if (!s || !ctx || !ids || count == 0 || !status || !(leaf > 0)) return QN_ERR_INVALID_ARG;
+  if (qn_kf_int_device(s) != ctx->device) return QN_ERR_INVALID_ARG;
+  const size_t n_kf = qn_kf_int_count(s);
+  for (uint32_t i = 0; i < count; i++) if (ids[i] < 0 || (size_t)ids[i] >= n_kf) return QN_ERR_INVALID_ARG;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  qn_ctx* c = ctx;
+  if (!c->qparams_set) { qn_quatro_default_params(&c->qparams); c->qparams_set = true; }
+  KfqState* st = (KfqState*)qn_kf_int_ext(s, QN_KF_INT_EXT_QUATRO);
+  if (!st) { st = new KfqState(); qn_kf_int_set_ext(s, QN_KF_INT_EXT_QUATRO, st, kfq_release); }
+  // ---- the clouds: one batch of `count` identity-pose submaps through the store's voxel pipeline (two host synchronisations), into a new block
+  std::vector<const float4*> vp(count, nullptr); std::vector<uint32_t> vn(count, 0); std::vector<int> vs(count, QN_ERR_EMPTY_CLOUD);
+  float4* vblock = nullptr;
+  int rc = qn_kf_int_voxel_each(s, ids, count, leaf, &vblock, vp.data(), vn.data(), vs.data());
+  if (rc != QN_OK) return rc;                                                       // (an allocation failure: no entry changed)
+  auto blk = std::make_shared<KfqBlock>(); blk->pts = vblock;
+  size_t total = 0; std::vector<size_t> roff(count, 0);
+  for (uint32_t i = 0; i < count; i++) if (vs[i] == QN_OK) { roff[i] = total; total += vn[i]; }
+  if (total) {
+    if (hipMalloc(&blk->rows, sizeof(float) * QN_FROW * total) != hipSuccess) { (void)hipGetLastError(); blk->rows = nullptr; c->last_error = "qn_kf_quatro_describe: hipMalloc of the FPFH rows failed"; qn_kf_int_set_error(s, c->last_error.c_str()); return QN_ERR_HIP; }
+  }
+  // ---- K9-K11 of every non-empty keyframe, a chunk of keyframes per nine k_lanes launches
+  const double rn_d = c->qparams.fpfh_normal_radius, rf_d = c->qparams.fpfh_radius;
+  if ((rc = kfq_rows(s, c, st, vp.data(), vn.data(), vs.data(), count, blk->rows, roff.data())) != QN_OK) return rc;
   // ---- the entries: describing again replaces (the block of a replaced entry goes when no entry names it)
-  qn_kf_int_verify_stale(s, 1, ids, count);                                         // (a multi-pair coarse-to-fine record that names one of them goes)
+  qn_kf_int_verify_stale(s, QN_KF_VERIFY_FROM_SCANS, ids, count);                                         // (a multi-pair coarse-to-fine record that names one of them goes)
   if (st->e.size() < n_kf) st->e.resize(n_kf);
   for (uint32_t i = 0; i < count; i++) {
     KfqEntry& e = st->e[ids[i]];
@@ -255,19 +266,15 @@ extern "C" int qn_kf_verify_loop_candidates_c2f(qn_kf_store* s, qn_ctx* ctx, int
   return c2f_batch(one, 1, pairs.data(), n_cand, score_thr, results, T_total, T_quatro, valid, status, cached.data());
 }
 
-extern "C" int qn_kf_verify_loop_pairs_c2f(qn_kf_store* s, qn_ctx* ctx, const int32_t* query, const int32_t* cand, uint32_t n_pairs, double score_thr,
-                                           qn_gicp_result* results, double* T_total, double* T_quatro, int* valid, int* status) {
-  // ---- every argument before anything runs, per pair as qn_kf_verify_loop_candidates_c2f: the store's entries, its verify record and the context stay as they were
+// the pairs of a multi-pair coarse-to-fine call on resident entries: `usable(id)` = the entry of keyframe id when the call may use it (described, rows made with
+// the context's radii and grid capacity), else nullptr; kind = the verify record the call leaves (qn_kf_internal.h).  Every argument is checked before anything
+// runs; then the pairs grouped by query (stable), ONE c2f_batch, records back in caller order.  qn_kf_verify_loop_pairs_c2f (scan entries) and
+// qn_kf_verify_loop_pairs_submap_c2f (local submaps, qn_kf_submap.inc) are this with their own entries.
+template <class Usable>
+static int kfq_pairs_c2f(qn_kf_store* s, qn_ctx* ctx, const Usable& usable, int kind, const int32_t* query, const int32_t* cand, uint32_t n_pairs, double score_thr,
+                         qn_gicp_result* results, double* T_total, double* T_quatro, int* valid, int* status) {
   if (!s || !ctx || !query || !cand || n_pairs == 0 || !results || !T_total || !valid || !status) return QN_ERR_INVALID_ARG;
   if (qn_kf_int_device(s) != ctx->device) return QN_ERR_INVALID_ARG;
-  qn_quatro_params qp;
-  if (ctx->qparams_set) qp = ctx->qparams; else qn_quatro_default_params(&qp);
-  auto usable = [&](int32_t id) -> const KfqEntry* {
-    if (id < 0 || (size_t)id >= qn_kf_int_count(s)) return nullptr;
-    const KfqEntry* e = kfq_entry(s, id);
-    if (!e || e->rn != qp.fpfh_normal_radius || e->rf != qp.fpfh_radius || e->max_cells != ctx->max_cells) return nullptr;
-    return e;
-  };
   std::vector<int32_t> uq; std::vector<uint32_t> qi(n_pairs);                    // distinct queries in order of first appearance; pair j -> its place
   for (uint32_t j = 0; j < n_pairs; j++) {
     if (cand[j] == query[j] || !usable(query[j]) || !usable(cand[j])) return QN_ERR_INVALID_ARG;
@@ -305,5 +312,20 @@ extern "C" int qn_kf_verify_loop_pairs_c2f(qn_kf_store* s, qn_ctx* ctx, const in
     memcpy(r.Tq, Tq.data() + 16 * (size_t)k, sizeof(r.Tq));
     memcpy(r.Tg, res[k].T, sizeof(r.Tg));
   }
-  return qn_kf_int_verify_record(s, 1, rec.data(), n_pairs);
+  return qn_kf_int_verify_record(s, kind, rec.data(), n_pairs);
+}
+
+extern "C" int qn_kf_verify_loop_pairs_c2f(qn_kf_store* s, qn_ctx* ctx, const int32_t* query, const int32_t* cand, uint32_t n_pairs, double score_thr,
+                                           qn_gicp_result* results, double* T_total, double* T_quatro, int* valid, int* status) {
+  // ---- every argument before anything runs, per pair as qn_kf_verify_loop_candidates_c2f: the store's entries, its verify record and the context stay as they were
+  if (!s || !ctx) return QN_ERR_INVALID_ARG;
+  qn_quatro_params qp;
+  if (ctx->qparams_set) qp = ctx->qparams; else qn_quatro_default_params(&qp);
+  auto usable = [&](int32_t id) -> const KfqEntry* {
+    if (id < 0 || (size_t)id >= qn_kf_int_count(s)) return nullptr;
+    const KfqEntry* e = kfq_entry(s, id);
+    if (!e || e->rn != qp.fpfh_normal_radius || e->rf != qp.fpfh_radius || e->max_cells != ctx->max_cells) return nullptr;
+    return e;
+  };
+  return kfq_pairs_c2f(s, ctx, usable, QN_KF_VERIFY_C2F, query, cand, n_pairs, score_thr, results, T_total, T_quatro, valid, status);
 }

@@ -1,0 +1,191 @@
+// qn_kf_submap.inc - a keyframe's local submap, in that keyframe's own frame, built once and kept resident (qn_kf_submap_describe), and the drift-free
+// submap-to-submap verification of loop candidates that borrows it on both sides (qn_kf_verify_loop_pairs_submap, and coarse to fine from resident FPFH rows
+// qn_kf_verify_loop_pairs_submap_c2f).  Included by qn_engine.hip behind qn_kf_quatro.inc, whose describe machinery (kfq_rows) and pair driver (kfq_pairs_c2f)
+// it shares.
+//
+// The reference's third mode (config.yaml: enable_submap_matching true; loop_closure.cpp:70-84, 98-107) registers the submap around the query against the
+// submap around the candidate, both placed with the corrected poses - the whole trajectory's drift.  Here the submap around keyframe c is
+//   voxel_grid( concat_i transformPcd(kf_i, inv(P_c) P_i) ),  i in local_submap_ids(c, r, n) = [c - r .. c + r] clipped to [0, n),
+// in c's sensor frame: it depends on the relative poses inside its window only.  It is the candidate window of qn_kf_verify_loop_candidates (the same pose
+// arithmetic, qn_kf_int_relative_pose, keyframe c itself included) except that the window keeps the newest keyframe: the reference drops it because its only
+// query is keyframes_.back(); with many queries per call there is no such keyframe, and a submap without its own centre is not what anyone wants.
+// An entry serves as the source when c is a query and as the target when c is a candidate; a pair's result estimates inv(P_c) P_q.
+//
+// describe: every listed window goes through the store's ONE voxel-grid pipeline as one batch (qn_kf_int_voxel_windows: what qn_kf_assemble_batch builds for
+// the same lists, into a block of its own, no store slot touched); with features, kfq_rows gives every window its FPFH rows in the nine keyframe-as-grid-
+// dimension launches per chunk.  Windows are several times a scan, so the 1 GiB chunking of the grids' scratch does run here.  No kernel of its own: the
+// relative poses are a few dozen 4x4 products on the host and reach the device inside the pipeline's one table upload.
+namespace {
+
+struct KfsEntry : KfqEntry { uint32_t range = 0; bool has_rows = false; };
+struct KfsState { std::vector<KfsEntry> e; };
+void kfs_release(void* p) { delete (KfsState*)p; }
+
+const KfsEntry* kfs_entry(const qn_kf_store* s, int32_t id) {
+  const KfsState* st = (const KfsState*)qn_kf_int_ext(s, QN_KF_INT_EXT_SUBMAP);
+  if (!st || id < 0 || (size_t)id >= st->e.size() || !st->e[id].described) return nullptr;
+  return &st->e[id];
+}
+
+}  // namespace
+
+extern "C" int qn_kf_submap_describe(qn_kf_store* s, qn_ctx* ctx, const int32_t* ids, uint32_t count, const double* poses, uint32_t n_poses, uint32_t submap_range,
+                                     double leaf, int with_features, int* status) {
+  // ---- every argument before anything runs
+  if (!s || !ctx || !ids || count == 0 || !poses || !status || !(leaf > 0)) return QN_ERR_INVALID_ARG;
+  if (qn_kf_int_device(s) != ctx->device) return QN_ERR_INVALID_ARG;
+  const size_t n_kf = qn_kf_int_count(s);
+  for (uint32_t i = 0; i < count; i++) if (ids[i] < 0 || (size_t)ids[i] >= n_kf || (uint32_t)ids[i] >= n_poses) return QN_ERR_INVALID_ARG;
+  for (size_t i = 0; i < (size_t)n_poses * 16; i++) if (!std::isfinite(poses[i])) return QN_ERR_INVALID_ARG;
+  // ---- the lists: window t = local_submap_ids(ids[t], submap_range, n_poses), keyframe i with inv(P_c) P_i
+  std::vector<int32_t> wid; std::vector<double> rel; std::vector<uint32_t> seg(count + 1, 0);
+  for (uint32_t t = 0; t < count; t++) {
+    const long long c = ids[t];
+    for (long long i = c - (long long)submap_range; i <= c + (long long)submap_range; i++) {
+      if (i < 0 || i >= (long long)n_poses) continue;
+      if ((size_t)i >= n_kf) return QN_ERR_INVALID_ARG;                             // (a pose without a keyframe inside a window)
+      double Q[16];
+      qn_kf_int_relative_pose(poses + 16 * (size_t)c, poses + 16 * (size_t)i, Q);
+      wid.push_back((int32_t)i); rel.insert(rel.end(), Q, Q + 16);
+    }
+    seg[t + 1] = (uint32_t)wid.size();
+  }
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  qn_ctx* c = ctx;
+  if (!c->qparams_set) { qn_quatro_default_params(&c->qparams); c->qparams_set = true; }
+  KfsState* st = (KfsState*)qn_kf_int_ext(s, QN_KF_INT_EXT_SUBMAP);
+  if (!st) { st = new KfsState(); qn_kf_int_set_ext(s, QN_KF_INT_EXT_SUBMAP, st, kfs_release); }
+  KfqState* scratch = (KfqState*)qn_kf_int_ext(s, QN_KF_INT_EXT_QUATRO);             // (the grids' scratch is the scan entries' too: one arena per store)
+  if (with_features && !scratch) { scratch = new KfqState(); qn_kf_int_set_ext(s, QN_KF_INT_EXT_QUATRO, scratch, kfq_release); }
+  // ---- the clouds: one batch of `count` windows through the store's voxel pipeline (two host synchronisations), into a new block
+  std::vector<const float4*> vp(count, nullptr); std::vector<uint32_t> vn(count, 0); std::vector<int> vs(count, QN_ERR_EMPTY_CLOUD);
+  float4* vblock = nullptr;
+  int rc = qn_kf_int_voxel_windows(s, wid.data(), rel.data(), seg.data(), count, leaf, &vblock, vp.data(), vn.data(), vs.data());
+  if (rc != QN_OK) return rc;                                                       // (an allocation failure: no entry changed)
+  auto blk = std::make_shared<KfqBlock>(); blk->pts = vblock;
+  size_t total = 0; std::vector<size_t> roff(count, 0);
+  for (uint32_t i = 0; i < count; i++) {
+    if (vs[i] == QN_OK && vn[i] > c->max_points) vs[i] = QN_ERR_CAPACITY;           // (no lane of this context could take it)
+    if (vs[i] == QN_OK) { roff[i] = total; total += vn[i]; }
+  }
+  if (with_features && total) {
+    if (hipMalloc(&blk->rows, sizeof(float) * QN_FROW * total) != hipSuccess) { (void)hipGetLastError(); blk->rows = nullptr; c->last_error = "qn_kf_submap_describe: hipMalloc of the FPFH rows failed"; qn_kf_int_set_error(s, c->last_error.c_str()); return QN_ERR_HIP; }
+    if ((rc = kfq_rows(s, c, scratch, vp.data(), vn.data(), vs.data(), count, blk->rows, roff.data())) != QN_OK) return rc;
+  }
+  // ---- the entries: describing again replaces (the block of a replaced entry goes when no entry names it); a window over capacity leaves no entry
+  qn_kf_int_verify_stale(s, QN_KF_VERIFY_FROM_SUBMAPS, ids, count);
+  if (st->e.size() < n_kf) st->e.resize(n_kf);
+  for (uint32_t i = 0; i < count; i++) {
+    KfsEntry& e = st->e[ids[i]];
+    e = KfsEntry{};
+    status[i] = vs[i];
+    if (vs[i] == QN_ERR_CAPACITY) continue;
+    e.described = true; e.leaf = leaf; e.rn = c->qparams.fpfh_normal_radius; e.rf = c->qparams.fpfh_radius; e.max_cells = c->max_cells; e.status = vs[i];
+    e.range = submap_range; e.has_rows = with_features != 0;
+    if (vs[i] == QN_OK) { e.blk = blk; e.pts = const_cast<float4*>(vp[i]); e.rows = with_features ? blk->rows + QN_FROW * roff[i] : nullptr; e.n = vn[i]; }
+  }
+  return QN_OK;
+}
+
+extern "C" int qn_kf_submap_cloud(qn_kf_store* s, int32_t id, const float** d_xyz, uint32_t* n) {
+  if (!s || !d_xyz || !n || id < 0 || (size_t)id >= qn_kf_int_count(s)) return QN_ERR_INVALID_ARG;
+  *d_xyz = nullptr; *n = 0;
+  const KfsEntry* e = kfs_entry(s, id);
+  if (!e) return QN_ERR_NOT_READY;
+  *d_xyz = (const float*)e->pts; *n = e->n;
+  return QN_OK;
+}
+
+extern "C" int qn_kf_submap_features(qn_kf_store* s, int32_t id, float* fpfh33_out) {
+  if (!s || id < 0 || (size_t)id >= qn_kf_int_count(s)) return QN_ERR_INVALID_ARG;
+  const KfsEntry* e = kfs_entry(s, id);
+  if (!e || !e->has_rows) return QN_ERR_NOT_READY;
+  if (!e->n) return QN_OK;
+  if (!fpfh33_out) return QN_ERR_INVALID_ARG;
+  if (hipSetDevice(qn_kf_int_device(s)) != hipSuccess ||
+      hipMemcpy2D(fpfh33_out, 33 * sizeof(float), e->rows, QN_FROW * sizeof(float), 33 * sizeof(float), e->n, hipMemcpyDeviceToHost) != hipSuccess) {
+    qn_kf_int_set_error(s, "qn_kf_submap_features: read-back failed"); return QN_ERR_HIP;
+  }
+  return QN_OK;
+}
+
+extern "C" int qn_kf_submap_release(qn_kf_store* s, const int32_t* ids, uint32_t count) {
+  if (!s || (ids == nullptr) != (count == 0)) return QN_ERR_INVALID_ARG;
+  const size_t n_kf = qn_kf_int_count(s);
+  for (uint32_t i = 0; i < count; i++) if (ids[i] < 0 || (size_t)ids[i] >= n_kf) return QN_ERR_INVALID_ARG;
+  KfsState* st = (KfsState*)qn_kf_int_ext(s, QN_KF_INT_EXT_SUBMAP);
+  if (!st) return QN_OK;
+  // (the entries' blocks are device memory nothing in flight reads: every call that borrows them ends synchronised)
+  qn_kf_int_verify_stale(s, QN_KF_VERIFY_FROM_SUBMAPS, ids, count);
+  if (!ids) { st->e.clear(); return QN_OK; }
+  for (uint32_t i = 0; i < count; i++) if ((size_t)ids[i] < st->e.size()) st->e[ids[i]] = KfsEntry{};
+  return QN_OK;
+}
+
+extern "C" int qn_kf_verify_loop_pairs_submap(qn_kf_store* s, qn_ctx* ctx, const int32_t* query, const int32_t* cand, const double* yaw, uint32_t n_pairs,
+                                              double score_thr, qn_gicp_result* results, int* valid, int* status) {
+  // ---- every argument before anything runs: the entries, the verify record and the context stay as they were
+  if (!s || !ctx || !query || !cand || n_pairs == 0 || !results || !valid || !status) return QN_ERR_INVALID_ARG;
+  if (qn_kf_int_device(s) != ctx->device) return QN_ERR_INVALID_ARG;
+  const size_t n_kf = qn_kf_int_count(s);
+  auto usable = [&](int32_t id) -> const KfsEntry* { return id < 0 || (size_t)id >= n_kf ? nullptr : kfs_entry(s, id); };
+  std::vector<int32_t> uq; std::vector<uint32_t> qi(n_pairs);                    // distinct queries in order of first appearance; pair j -> its place
+  for (uint32_t j = 0; j < n_pairs; j++) {
+    if (cand[j] == query[j] || !usable(query[j]) || !usable(cand[j])) return QN_ERR_INVALID_ARG;
+    for (uint32_t i = 0; i < j; i++) if (query[i] == query[j] && cand[i] == cand[j]) return QN_ERR_INVALID_ARG;
+    if (yaw && !std::isfinite(yaw[j])) return QN_ERR_INVALID_ARG;
+    uint32_t k = 0;
+    while (k < uq.size() && uq[k] != query[j]) k++;
+    if (k == uq.size()) uq.push_back(query[j]);
+    qi[j] = k;
+  }
+  // ---- one batched registration: the pairs whose clouds exist, grouped by query (stable) so that a query's pairs share the source's preparation
+  std::vector<uint32_t> order(n_pairs);
+  for (uint32_t j = 0; j < n_pairs; j++) order[j] = j;
+  std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return qi[a] < qi[b]; });
+  std::vector<qn_pair_desc> pairs; std::vector<float> g; std::vector<uint32_t> which;
+  std::vector<qn_kf_int_verify_pair> rec(n_pairs);
+  std::vector<qn_gicp_result> r0(n_pairs); std::vector<int> st0(n_pairs, QN_OK);
+  for (uint32_t j = 0; j < n_pairs; j++) {
+    const KfsEntry* q = usable(query[j]); const KfsEntry* e = usable(cand[j]);
+    memset(&r0[j], 0, sizeof(r0[j])); r0[j].fitness = DBL_MAX;                   // (what a registration that did not run reports: the batch's defaults)
+    for (int i = 0; i < 4; i++) { r0[j].T[5 * i] = 1.f; r0[j].T64[5 * i] = 1.0; }
+    st0[j] = q->n == 0 || e->n == 0 ? QN_ERR_EMPTY_CLOUD : QN_OK;
+    rec[j] = qn_kf_int_verify_pair{q->pts, q->n, e->pts, e->n, query[j], cand[j], 0, {}, {}};
+  }
+  for (uint32_t j : order) {
+    if (st0[j] != QN_OK) continue;
+    pairs.push_back(qn_pair_desc{(const float*)rec[j].src, rec[j].ns, (const float*)rec[j].dst, rec[j].nt, 16, 1});
+    float gj[16];
+    qn_kf_int_seed_from_yaw(yaw ? yaw[j] : 0.0, gj);
+    g.insert(g.end(), gj, gj + 16);
+    which.push_back(j);
+  }
+  const uint32_t m = (uint32_t)pairs.size();
+  std::vector<qn_gicp_result> res(m); std::vector<int> val(m, 0), st(m, QN_OK);
+  if (m) {
+    const int rc = qn_gicp_align_batch_guess(ctx, pairs.data(), g.data(), m, score_thr, res.data(), val.data(), st.data());
+    if (rc != QN_OK) return rc;                                                    // (nothing written: the caller's arrays and the record are the previous call's)
+  }
+  for (uint32_t j = 0; j < n_pairs; j++) { results[j] = r0[j]; valid[j] = 0; status[j] = st0[j]; }
+  for (uint32_t k = 0; k < m; k++) {
+    const uint32_t j = which[k];
+    results[j] = res[k]; valid[j] = val[k]; status[j] = st[k];
+    if (st[k] == QN_OK) { rec[j].stage = 2; memcpy(rec[j].Tg, res[k].T, sizeof(rec[j].Tg)); }
+  }
+  return qn_kf_int_verify_record(s, QN_KF_VERIFY_SUBMAP, rec.data(), n_pairs);
+}
+
+extern "C" int qn_kf_verify_loop_pairs_submap_c2f(qn_kf_store* s, qn_ctx* ctx, const int32_t* query, const int32_t* cand, uint32_t n_pairs, double score_thr,
+                                                  qn_gicp_result* results, double* T_total, double* T_quatro, int* valid, int* status) {
+  if (!s || !ctx) return QN_ERR_INVALID_ARG;
+  qn_quatro_params qp;
+  if (ctx->qparams_set) qp = ctx->qparams; else qn_quatro_default_params(&qp);
+  auto usable = [&](int32_t id) -> const KfqEntry* {      // described with rows, under the context's current radii and grid capacity
+    if (id < 0 || (size_t)id >= qn_kf_int_count(s)) return nullptr;
+    const KfsEntry* e = kfs_entry(s, id);
+    if (!e || !e->has_rows || e->rn != qp.fpfh_normal_radius || e->rf != qp.fpfh_radius || e->max_cells != ctx->max_cells) return nullptr;
+    return e;
+  };
+  return kfq_pairs_c2f(s, ctx, usable, QN_KF_VERIFY_SUBMAP_C2F, query, cand, n_pairs, score_thr, results, T_total, T_quatro, valid, status);
+}

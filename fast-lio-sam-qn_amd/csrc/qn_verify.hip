@@ -47,6 +47,11 @@ void seed_from_yaw(double yaw, float* g) {
   for (int i = 0; i < 16; i++) g[i] = (float)m[i];
 }
 
+}  // namespace
+void qn_kf_int_relative_pose(const double* Pc, const double* Pi, double* Q) { relative_pose(Pc, Pi, Q); }
+void qn_kf_int_seed_from_yaw(double yaw, float* g) { seed_from_yaw(yaw, g); }
+namespace {
+
 void unset_record(qn_gicp_result* r) {       // what a registration that did not run reports (the batch's defaults)
   memset(r, 0, sizeof(*r)); r->fitness = DBL_MAX;
   for (int i = 0; i < 4; i++) { r->T[5 * i] = 1.f; r->T64[5 * i] = 1.0; }
@@ -118,7 +123,9 @@ namespace {
 // the record of the latest qn_kf_verify_loop_pairs[_c2f] call (store slot QN_KF_INT_EXT_VERIFY) and the arena qn_kf_verify_cloud computes into:
 // COARSE and FINAL of pair j at fixed places (2 * (sum of ns before j), then + ns), so every pointer handed out stays valid until the record is replaced
 struct VerifyState {
-  bool live = false; int c2f = 0;
+  bool live = false; int kind = QN_KF_VERIFY_GICP;
+  bool c2f() const { return kind == QN_KF_VERIFY_C2F || kind == QN_KF_VERIFY_SUBMAP_C2F; }
+  int from() const { return kind >= QN_KF_VERIFY_SUBMAP ? QN_KF_VERIFY_FROM_SUBMAPS : kind; }
   std::vector<qn_kf_int_verify_pair> p; std::vector<size_t> off;
   float4* arena = nullptr; size_t arena_cap = 0;
   ~VerifyState() { if (arena) (void)hipFree(arena); }
@@ -150,23 +157,23 @@ __global__ void k_verify_cloud(const float4* __restrict__ in, uint32_t n, Verify
 
 }  // namespace
 
-int qn_kf_int_verify_record(qn_kf_store* s, int c2f, const qn_kf_int_verify_pair* p, uint32_t n) {
+int qn_kf_int_verify_record(qn_kf_store* s, int kind, const qn_kf_int_verify_pair* p, uint32_t n) {
   VerifyState* st = (VerifyState*)qn_kf_int_ext(s, QN_KF_INT_EXT_VERIFY);
   if (!st) {
     st = new (std::nothrow) VerifyState();
     if (!st) return QN_ERR_HIP;
     qn_kf_int_set_ext(s, QN_KF_INT_EXT_VERIFY, st, verify_release);
   }
-  st->c2f = c2f; st->p.assign(p, p + n); st->off.assign(n + 1, 0);
+  st->kind = kind; st->p.assign(p, p + n); st->off.assign(n + 1, 0);
   for (uint32_t j = 0; j < n; j++) st->off[j + 1] = st->off[j] + 2 * (size_t)p[j].ns;
   st->live = true;
   return QN_OK;
 }
 
-void qn_kf_int_verify_stale(qn_kf_store* s, int c2f, const int32_t* ids, uint32_t count) {
+void qn_kf_int_verify_stale(qn_kf_store* s, int from, const int32_t* ids, uint32_t count) {
   VerifyState* st = (VerifyState*)qn_kf_int_ext(s, QN_KF_INT_EXT_VERIFY);
-  if (!st || !st->live || st->c2f != c2f) return;
-  if (!c2f) { st->live = false; return; }
+  if (!st || !st->live || st->from() != from) return;
+  if (from == QN_KF_VERIFY_FROM_BATCH || !ids) { st->live = false; return; }
   for (uint32_t i = 0; i < count; i++)
     for (const qn_kf_int_verify_pair& q : st->p)
       if (q.query == ids[i] || q.cand == ids[i]) { st->live = false; return; }
@@ -250,7 +257,7 @@ extern "C" int qn_kf_verify_loop_pairs(qn_kf_store* s, qn_ctx* ctx, const int32_
       if (st[k] == QN_OK) { rec[j].stage = 2; memcpy(rec[j].Tg, res[k].T, sizeof(rec[j].Tg)); }
     }
   }
-  return qn_kf_int_verify_record(s, 0, rec.data(), n_pairs);
+  return qn_kf_int_verify_record(s, QN_KF_VERIFY_GICP, rec.data(), n_pairs);
 }
 
 extern "C" int qn_kf_verify_cloud(qn_kf_store* s, uint32_t pair, int which, const float** d_xyz, uint32_t* n) {
@@ -263,7 +270,7 @@ extern "C" int qn_kf_verify_cloud(qn_kf_store* s, uint32_t pair, int which, cons
   if (which == QN_VERIFY_SRC) { *d_xyz = (const float*)q.src; *n = q.ns; return QN_OK; }
   if (which == QN_VERIFY_DST) { *d_xyz = (const float*)q.dst; *n = q.nt; return QN_OK; }
   // COARSE needs the solved Quatro stage (coarse-to-fine only), FINAL the registration
-  if (which == QN_VERIFY_COARSE ? (!st->c2f || q.stage < 1) : q.stage < 2) return QN_ERR_NOT_READY;
+  if (which == QN_VERIFY_COARSE ? (!st->c2f() || q.stage < 1) : q.stage < 2) return QN_ERR_NOT_READY;
   if (q.ns == 0 || !q.src) return QN_ERR_NOT_READY;
   const int dev = qn_kf_int_device(s);
   hipStream_t stream = qn_kf_int_stream(s);
@@ -276,7 +283,7 @@ extern "C" int qn_kf_verify_cloud(qn_kf_store* s, uint32_t pair, int which, cons
   }
   float4* out = st->arena + st->off[pair] + (which == QN_VERIFY_FINAL ? q.ns : 0);
   VerifyXf m{};
-  m.coarse = st->c2f ? 1 : 0; m.fine = which == QN_VERIFY_FINAL ? 1 : 0;
+  m.coarse = st->c2f() ? 1 : 0; m.fine = which == QN_VERIFY_FINAL ? 1 : 0;
   for (int i = 0; i < 12; i++) { m.Tq[i] = q.Tq[i]; m.Tg[i] = q.Tg[i]; }
   hipLaunchKernelGGL(k_verify_cloud, dim3((q.ns + 255) / 256), dim3(256), 0, stream, q.src, q.ns, m, out);
   if (hipGetLastError() != hipSuccess || hipStreamSynchronize(stream) != hipSuccess) { qn_kf_int_set_error(s, "qn_kf_verify_cloud: the transform failed"); return QN_ERR_HIP; }

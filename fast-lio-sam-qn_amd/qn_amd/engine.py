@@ -910,6 +910,83 @@ class KeyframeStore:
                      T_quatro=Tq[j].copy(), T_gicp=np.array(results[j].T, dtype=np.float32).reshape(4, 4).astype(np.float64), status=int(status[j]),
                      record=results[j]) for j in range(n)]
 
+    # ---- resident local submaps and the submap-to-submap check (qn_kf_submap_*, qn_kf_verify_loop_pairs_submap[_c2f])
+    def submap_describe(self, ctx, ids, poses, submap_range, leaf, with_features=True):
+        """qn_kf_submap_describe: for each listed keyframe c its local submap in c's own sensor frame - the keyframes local_submap_ids(c, submap_range,
+        len(poses)), keyframe i with scancontext.relative_pose(poses[c], poses[i]), voxel grid at `leaf` (= assemble_batch of that list) - and, with_features,
+        its FPFH rows with ctx's Quatro radii; both stay resident in the store (describing again replaces).  -> per id its status (QN_ERR_EMPTY_CLOUD: nothing
+        left after the voxel grid; QN_ERR_CAPACITY: more points than ctx takes, no entry)."""
+        ids = np.ascontiguousarray(np.atleast_1d(ids), dtype=np.int32)
+        P = np.ascontiguousarray(np.asarray(poses, dtype=np.float64).reshape(-1, 16))
+        st = np.zeros(max(len(ids), 1), np.int32)
+        rc = self._l.qn_kf_submap_describe(self.h, ctx.h, _p(ids) if len(ids) else None, C.c_uint32(len(ids)), _p(P) if len(P) else None, C.c_uint32(len(P)),
+                                           C.c_uint32(submap_range), C.c_double(leaf), C.c_int(1 if with_features else 0), _p(st))
+        if rc != QN_OK:
+            raise EngineError(rc, self._l.qn_status_str(rc).decode() + ": " + self._l.qn_kf_last_error(self.h).decode() + " / " + lib().qn_last_error(ctx.h).decode())
+        return [int(v) for v in st[:len(ids)]]
+
+    def submap_cloud(self, kid):
+        """-> (device pointer of keyframe `kid`'s resident local submap, float4 records (None when empty), count)"""
+        ptr = C.c_void_p(); n = C.c_uint32()
+        self._check(self._l.qn_kf_submap_cloud(self.h, C.c_int32(kid), C.byref(ptr), C.byref(n)))
+        return ptr.value, n.value
+
+    def submap_features(self, kid):
+        """-> (n, 33) float32: the FPFH rows of keyframe `kid`'s local submap (original point order; NaN rows where PCL has none)"""
+        _, n = self.submap_cloud(kid)
+        out = np.zeros((n, 33), np.float32)
+        self._check(self._l.qn_kf_submap_features(self.h, C.c_int32(kid), _p(out) if n else None))
+        return out
+
+    def submap_release(self, ids=None):
+        """qn_kf_submap_release: free the local submaps of these keyframes (None: of all)"""
+        if ids is None:
+            self._check(self._l.qn_kf_submap_release(self.h, None, C.c_uint32(0)))
+            return
+        ids = np.ascontiguousarray(np.atleast_1d(ids), dtype=np.int32)
+        self._check(self._l.qn_kf_submap_release(self.h, _p(ids) if len(ids) else None, C.c_uint32(len(ids))))
+
+    def verify_loop_pairs_submap(self, ctx, query, cand, yaw=None, score_thr=1.5):
+        """qn_kf_verify_loop_pairs_submap: pair j = query[j]'s resident local submap (source) against cand[j]'s (target), seeded with
+        scancontext.seed_from_yaw(yaw[j]) (None: 0), every pair in ONE batched registration on ctx = gicp_align_batch(..., guesses=) on the entry clouds,
+        record for record.  -> one dict per pair, as verify_loop_pairs'."""
+        q, c, n = self._pairs(query, cand)
+        y = None if yaw is None else np.ascontiguousarray(np.atleast_1d(yaw), dtype=np.float64)
+        if y is not None and len(y) != n:
+            raise ValueError("verify_loop_pairs_submap: %d pairs but %d yaw values" % (n, len(y)))
+        results = (GicpResult * max(n, 1))(); valid = np.zeros(max(n, 1), np.int32); status = np.zeros(max(n, 1), np.int32)
+        st = self._l.qn_kf_verify_loop_pairs_submap(self.h, ctx.h, _p(q) if n else None, _p(c) if n else None, _p(y) if y is not None else None, C.c_uint32(n),
+                                                    C.c_double(score_thr), results, _p(valid), _p(status))
+        if st != QN_OK:
+            raise EngineError(st, self._l.qn_status_str(st).decode() + ": " + self._l.qn_kf_last_error(self.h).decode() + " / " + lib().qn_last_error(ctx.h).decode())
+        return [dict(valid=bool(valid[j]), converged=bool(results[j].converged), score=results[j].fitness, iterations=results[j].iterations,
+                     T=np.array(results[j].T, dtype=np.float32).reshape(4, 4).astype(np.float64), status=int(status[j]), record=results[j]) for j in range(n)]
+
+    def verify_loop_pairs_submap_c2f(self, ctx, query, cand, score_thr=1.5):
+        """qn_kf_verify_loop_pairs_submap_c2f: pair j coarse to fine (Quatro -> transformPcd -> Nano-GICP) between the two resident local submaps, the lanes
+        borrowing their points and FPFH rows = coarse_to_fine_align_batch([ctx]) on the entry clouds, record for record.  -> one dict per pair, as
+        verify_loop_pairs_c2f's."""
+        q, c, n = self._pairs(query, cand)
+        results = (GicpResult * max(n, 1))(); valid = np.zeros(max(n, 1), np.int32); status = np.zeros(max(n, 1), np.int32)
+        Tt = np.zeros((max(n, 1), 4, 4)); Tq = np.zeros((max(n, 1), 4, 4))
+        st = self._l.qn_kf_verify_loop_pairs_submap_c2f(self.h, ctx.h, _p(q) if n else None, _p(c) if n else None, C.c_uint32(n), C.c_double(score_thr),
+                                                        results, _p(Tt), _p(Tq), _p(valid), _p(status))
+        if st != QN_OK:
+            raise EngineError(st, self._l.qn_status_str(st).decode() + ": " + self._l.qn_kf_last_error(self.h).decode() + " / " + lib().qn_last_error(ctx.h).decode())
+        return [dict(valid=bool(valid[j]), converged=bool(results[j].converged), score=results[j].fitness, iterations=results[j].iterations, T=Tt[j].copy(),
+                     T_quatro=Tq[j].copy(), T_gicp=np.array(results[j].T, dtype=np.float32).reshape(4, 4).astype(np.float64), status=int(status[j]),
+                     record=results[j]) for j in range(n)]
+
+    def verify_loop_candidates_submap(self, ctx, query, candidates, yaw=None, score_thr=1.5):
+        """one query's candidates, submap against submap: verify_loop_pairs_submap with the query repeated"""
+        cand = np.atleast_1d(candidates)
+        return self.verify_loop_pairs_submap(ctx, [query] * len(cand), cand, yaw, score_thr)
+
+    def verify_loop_candidates_submap_c2f(self, ctx, query, candidates, score_thr=1.5):
+        """one query's candidates, submap against submap, coarse to fine: verify_loop_pairs_submap_c2f with the query repeated"""
+        cand = np.atleast_1d(candidates)
+        return self.verify_loop_pairs_submap_c2f(ctx, [query] * len(cand), cand, score_thr)
+
     def verify_cloud(self, pair, which):
         """qn_kf_verify_cloud: cloud `which` (QN_VERIFY_SRC / _DST / _COARSE / _FINAL) of pair `pair` of the latest verify_loop_pairs[_c2f] -> (n, 3) float32"""
         ptr = C.c_void_p(); n = C.c_uint32()
@@ -964,6 +1041,12 @@ def loop_candidates(pos, stamps, query, radius, tdiff, max_k=64):
     if st != QN_OK:
         raise EngineError(st, lib().qn_status_str(st).decode())
     return out[:n.value].copy()
+
+
+def local_submap_ids(c, submap_range, n_keyframes):
+    """the window of keyframe c's resident local submap (KeyframeStore.submap_describe): the keyframes within submap_range of c that exist.  Unlike
+    loop_submap_ids it keeps the newest keyframe: the reference drops it because its only query is the newest keyframe itself."""
+    return [i for i in range(c - submap_range, c + submap_range + 1) if 0 <= i < n_keyframes]
 
 
 def loop_submap_ids(src_idx, dst_idx, submap_range, enable_quatro, enable_submap_matching, n_keyframes):

@@ -213,4 +213,60 @@ inline std::vector<ScVerifiedPair> verifyLoopPairsCoarseToFine(qn_kf_store* stor
   return out;
 }
 
+// The reference's third mode (enable_submap_matching: the submap around the query against the submap around the candidate, loop_closure.cpp:70-84, 98-107) made
+// drift-free: every keyframe's local submap is built once in that keyframe's own sensor frame (qn_kf_submap_describe: the keyframes within submap_range of it,
+// each with inv(P_c) P_i, voxel grid at `leaf`; with_features also its FPFH rows under ctx's Quatro radii) and stays resident.  poses16 = 16 doubles per
+// keyframe, raw odometry or corrected: only the relative poses inside a window matter.  Returns each id's status (QN_OK, QN_ERR_EMPTY_CLOUD, QN_ERR_CAPACITY).
+inline std::vector<int> describeLocalSubmaps(qn_kf_store* store, qn_ctx* ctx, const std::vector<int>& ids, const std::vector<double>& poses16, int submap_range,
+                                             double leaf, bool with_features) {
+  std::vector<int> st(ids.size());
+  if (ids.empty()) return st;
+  if (submap_range < 0 || poses16.size() % 16 != 0) throw std::invalid_argument("[qn_map] describeLocalSubmaps: bad submap_range or poses");
+  const std::vector<int32_t> id32(ids.begin(), ids.end());
+  const int rc = qn_kf_submap_describe(store, ctx, id32.data(), (uint32_t)id32.size(), poses16.data(), (uint32_t)(poses16.size() / 16), (uint32_t)submap_range, leaf,
+                                       with_features ? 1 : 0, st.data());
+  if (rc != QN_OK) throw std::runtime_error(std::string("[qn_map] qn_kf_submap_describe: ") + qn_status_str(rc) + " " + qn_kf_last_error(store));
+  return st;
+}
+
+// every pair's described local submaps registered against each other in one batched Nano-GICP on ctx, seeded with the pair's Scan Context heading
+// (qn_kf_verify_loop_pairs_submap).  The queries and candidates must have been described (describeLocalSubmaps).  T estimates inv(P_c) P_query.
+inline std::vector<ScVerifiedPair> verifyLoopPairsSubmap(qn_kf_store* store, qn_ctx* ctx, const ScPairs& c, double score_thr) {
+  std::vector<ScVerifiedPair> out;
+  if (c.cand.empty()) return out;
+  if (c.query.size() != c.cand.size() || c.yaw.size() != c.cand.size()) throw std::invalid_argument("[qn_map] verifyLoopPairsSubmap: bad pairs");
+  const size_t K = c.cand.size();
+  const std::vector<int32_t> q(c.query.begin(), c.query.end()), ids(c.cand.begin(), c.cand.end());
+  std::vector<qn_gicp_result> r(K);
+  std::vector<int> valid(K), status(K);
+  const int rc = qn_kf_verify_loop_pairs_submap(store, ctx, q.data(), ids.data(), c.yaw.data(), (uint32_t)K, score_thr, r.data(), valid.data(), status.data());
+  if (rc != QN_OK) throw std::runtime_error(std::string("[qn_map] qn_kf_verify_loop_pairs_submap: ") + qn_status_str(rc) + " " + qn_kf_last_error(store));
+  for (size_t k = 0; k < K; k++) {
+    ScVerifiedPair v{c.query[k], c.cand[k], valid[k] != 0, r[k].fitness, {}, {}, status[k]};
+    for (int i = 0; i < 16; i++) { v.T[i] = (double)r[k].T[i]; v.T_quatro[i] = i % 5 == 0 ? 1.0 : 0.0; }
+    out.push_back(v);
+  }
+  return out;
+}
+
+// the same pairs coarse to fine from the submaps' resident FPFH rows (qn_kf_verify_loop_pairs_submap_c2f); they must have been described with features
+inline std::vector<ScVerifiedPair> verifyLoopPairsSubmapCoarseToFine(qn_kf_store* store, qn_ctx* ctx, const ScPairs& c, double score_thr) {
+  std::vector<ScVerifiedPair> out;
+  if (c.cand.empty()) return out;
+  if (c.query.size() != c.cand.size()) throw std::invalid_argument("[qn_map] verifyLoopPairsSubmapCoarseToFine: bad pairs");
+  const size_t K = c.cand.size();
+  const std::vector<int32_t> q(c.query.begin(), c.query.end()), ids(c.cand.begin(), c.cand.end());
+  std::vector<qn_gicp_result> r(K);
+  std::vector<double> Tt(16 * K), Tq(16 * K);
+  std::vector<int> valid(K), status(K);
+  const int rc = qn_kf_verify_loop_pairs_submap_c2f(store, ctx, q.data(), ids.data(), (uint32_t)K, score_thr, r.data(), Tt.data(), Tq.data(), valid.data(), status.data());
+  if (rc != QN_OK) throw std::runtime_error(std::string("[qn_map] qn_kf_verify_loop_pairs_submap_c2f: ") + qn_status_str(rc) + " " + qn_kf_last_error(store));
+  for (size_t k = 0; k < K; k++) {
+    ScVerifiedPair v{c.query[k], c.cand[k], valid[k] != 0, r[k].fitness, {}, {}, status[k]};
+    for (int i = 0; i < 16; i++) { v.T[i] = Tt[16 * k + i]; v.T_quatro[i] = Tq[16 * k + i]; }
+    out.push_back(v);
+  }
+  return out;
+}
+
 }  // namespace qn_map

@@ -399,12 +399,64 @@ int  qn_kf_verify_loop_pairs_c2f(qn_kf_store*, qn_ctx*, const int32_t* query, co
  * QN_ERR_NOT_READY: no such call yet, its clouds are gone (see below), COARSE on the GICP path, or a pair whose stage did not run (no solved Quatro for
  * COARSE, no registration for FINAL).  QN_ERR_INVALID_ARG: a null pointer, pair >= that call's n_pairs, or a bad `which`.  The pointers stay valid until
  * the next qn_kf_verify_loop_pairs[_c2f] call, the next qn_kf_assemble_batch on the store (any caller: the GICP path's clouds live in its batch slot), a
- * qn_kf_quatro_describe of a keyframe the latest coarse-to-fine call involved, or the store's destruction.                                             */
+ * qn_kf_quatro_describe of a keyframe the latest coarse-to-fine call involved, or the store's destruction.  The latest call may also be
+ * qn_kf_verify_loop_pairs_submap[_c2f] (below): SRC / DST are then the two resident local submaps, valid until one of them is described again or released.  */
 #define QN_VERIFY_SRC 0
 #define QN_VERIFY_DST 1
 #define QN_VERIFY_COARSE 2
 #define QN_VERIFY_FINAL 3
 int  qn_kf_verify_cloud(qn_kf_store*, uint32_t pair, int which, const float** d_xyz /* float4, stride 16 */, uint32_t* n);
+/* ---- resident local submaps and the drift-free submap-to-submap check (csrc/qn_kf_submap.inc) ---------------------------------------------------------
+ * The reference's third mode (enable_submap_matching true: loop_closure.cpp:70-84, 98-107) registers the submap around the query against the submap around
+ * the candidate.  Here the submap around keyframe c lives in c's OWN sensor frame,
+ *   voxel_grid( concat_i transformPcd(kf_i, inv(P_c) P_i) ),  i in local_submap_ids(c, r, n) = [i for i in c - r .. c + r if 0 <= i < n],
+ * so it depends on the relative poses inside its window only: described from raw odometry it is never invalidated by a pose-graph update; described from
+ * corrected poses the caller describes again when it wants to.  NOTE the window rule: it keeps the newest keyframe, unlike loop_submap_ids' `i < n - 1`
+ * (qn_kf_verify_loop_candidates, loop_closure.cpp:98-104).  The reference drops the newest keyframe because its only query is keyframes_.back(); with many
+ * queries per call there is no such keyframe, and a submap that leaves out its own centre is not what anyone wants.  For c + r < n - 1 both rules give the
+ * same list.  An entry is the source when c is a query and the target when c is a candidate; a verified pair (q, c) estimates inv(P_c) P_q.
+ * qn_kf_submap_describe: for every listed id c, the cloud = what qn_kf_assemble_batch builds for the list local_submap_ids(c, submap_range, n_poses) with the
+ *   poses Q_i = inv(P_c) P_i, in all 16 bytes of every record, Q_i in the arithmetic qn_kf_verify_loop_candidates documents for its candidate segments
+ *   (inv(P) = [R^T | -R^T t]; every entry summed over k = 0..3 in order in f64, no fused multiply-add; scancontext.relative_pose) for every i of the window,
+ *   i = c included - which is what keeps the entry equal to that call's candidate segment bit for bit wherever the two window rules agree.  All listed windows go
+ *   through the store's one voxel-grid pipeline as ONE batch; the assemble, map and batch slots are not touched.  with_features != 0: the FPFH rows of each
+ *   cloud with ctx's Quatro radii, equal to qn_fpfh's on that cloud bit for bit, through the launches of qn_kf_quatro_describe (nine for the grids and K9-K11 of
+ *   all windows, the window a grid dimension; windows are taken in chunks whose grid scratch - two tables of max_cells + 1 words per window, ~360 B per point -
+ *   stays under 1 GiB, one synchronisation per further chunk; the scratch is shared with qn_kf_quatro_describe).  Entries are separate from the scan entries of
+ *   qn_kf_quatro_describe: a keyframe may have both.  Each entry records (submap_range, leaf, radii, ctx's grid capacity, whether it has rows).  Describing
+ *   again replaces (an id listed twice: the later one).  status[i]: QN_ERR_EMPTY_CLOUD for a window with no point left (an entry with no points),
+ *   QN_ERR_CAPACITY for a window whose cloud exceeds ctx's max_points (NO entry, an earlier one of that id is dropped); the others are still described.
+ *   QN_ERR_INVALID_ARG before anything runs, store unchanged: a null pointer, count == 0, a bad id, an id >= n_poses, a window member that is no keyframe of the
+ *   store (n_poses > the number of keyframes), a non-finite pose, leaf <= 0, store and context on different devices.  An allocation failure (QN_ERR_HIP) leaves
+ *   every earlier entry as it was.  Host synchronisations: the voxel pipeline's two and one per chunk.  Memory per point of a window's cloud, resident: 16 B of
+ *   cloud (x 1.5 growth slack of the voxel output) + 144 B of rows (with_features); a window holds roughly the points of its 2 r + 1 scans less their overlap.
+ * qn_kf_submap_cloud: the entry's cloud (device pointer, float4, stride 16; NULL and n = 0 for an empty one), valid until `id` is described again or released or
+ *   the store is destroyed.  qn_kf_submap_features: its n x 33 FPFH rows (one synchronous copy).  Both: QN_ERR_INVALID_ARG for a bad id, QN_ERR_NOT_READY for a
+ *   keyframe without an entry (features: or an entry described without rows).
+ * qn_kf_submap_release: frees the entries of ids[0 .. count) (never-described ones are skipped), or of every keyframe with ids = NULL and count = 0; device
+ *   memory goes back when the last entry of a describe call's block is released.  QN_ERR_INVALID_ARG, nothing released: a bad id, NULL with count > 0 or the reverse. */
+int  qn_kf_submap_describe(qn_kf_store*, qn_ctx*, const int32_t* ids, uint32_t count, const double* poses16 /* n_poses x 16 */, uint32_t n_poses,
+                           uint32_t submap_range, double leaf, int with_features, int* status);
+int  qn_kf_submap_cloud(qn_kf_store*, int32_t id, const float** d_xyz /* float4, stride 16 */, uint32_t* n);
+int  qn_kf_submap_features(qn_kf_store*, int32_t id, float* fpfh33_out /* n x 33 */);
+int  qn_kf_submap_release(qn_kf_store*, const int32_t* ids, uint32_t count);   /* NULL, 0: all */
+/* Submap against submap with Nano-GICP: pair j = query[j]'s entry (source) against cand[j]'s entry (target) through ONE qn_gicp_align_batch_guess on ctx, pair j
+ * seeded with Rz(-yaw[j]) built as qn_kf_verify_loop_candidates builds it (yaw NULL: all 0), the pairs grouped by query (stable) so that a query's pairs share
+ * the source preparation, the records scattered back to caller order.  Record j (results[j], valid[j], status[j]) equals qn_gicp_align_batch_guess on the two
+ * entry clouds with that seed bit for bit.  Rows are not needed.  A pair with an empty side: QN_ERR_EMPTY_CLOUD, valid 0, the other pairs still run.
+ * QN_ERR_INVALID_ARG before anything runs (entries, verify record and context unchanged): a null pointer, n_pairs == 0, a bad id, cand[j] == query[j], a
+ * repeated (query, cand) pair, a keyframe without an entry, a non-finite yaw, store and context on different devices.  Host synchronisations: the
+ * registration's own, whatever n_pairs is.                                                                                                              */
+int  qn_kf_verify_loop_pairs_submap(qn_kf_store*, qn_ctx*, const int32_t* query, const int32_t* cand, const double* yaw /* per pair; NULL = 0 */, uint32_t n_pairs,
+                                    double score_thr, qn_gicp_result* results, int* valid, int* status);
+/* Submap against submap coarse to fine, as qn_kf_verify_loop_pairs_c2f with the lanes borrowing the entries' points and rows: record j equals
+ * qn_coarse_to_fine_align_batch({ctx}) on the two entry clouds bit for bit.  QN_ERR_INVALID_ARG before anything runs: that call's checks, with "never
+ * described" = no entry, an entry without rows, or rows made with radii or a grid capacity (max_points) other than ctx's; a repeated (query, cand) pair.
+ * After either call qn_kf_verify_cloud serves the pair's clouds (SRC / DST = the two entries, COARSE only after this form) until an involved entry is
+ * described again or released.                                                                                                                          */
+int  qn_kf_verify_loop_pairs_submap_c2f(qn_kf_store*, qn_ctx*, const int32_t* query, const int32_t* cand, uint32_t n_pairs, double score_thr,
+                                        qn_gicp_result* results, double* T_total /* n_pairs x 16 */, double* T_quatro /* n_pairs x 16 or NULL */,
+                                        int* valid, int* status);
 /* the corrected global map = the three loops of FastLioSamQn that rebuild it from every keyframe with its corrected pose
  * (fast_lio_sam_qn.cpp:302-316 visTimerFunc, :398-411 saveFlagCallback, :435-448 the destructor's result.pcd): transformPcd of each
  * listed keyframe, concatenation in `ids` order (ids may repeat), voxelizePcd at save_voxel_resolution (pcl::VoxelGrid,

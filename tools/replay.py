@@ -221,8 +221,24 @@ def _oracle_relative(orc, scans, poses, k, c, yaw, submap_range, voxel, max_corr
     return dict(valid=bool(r["converged"] and r["fitness"] < score_thr), converged=r["converged"], score=r["fitness"], T=r["Tf"].astype(np.float64))
 
 
+def _oracle_submap_relative(orc, scans, poses, q, c, yaw, submap_range, voxel, max_corr_dist, score_thr, use_quatro):
+    """verify_loop_pairs_submap[_c2f] for one pair on the CPU oracle: both local submaps assembled from the twins, each in its centre's sensor frame"""
+    from qn_amd import scancontext, engine
+    def local(x):
+        sub = engine.local_submap_ids(x, submap_range, len(poses))
+        return orc.assemble_submap(scans, {i: scancontext.relative_pose(poses[x], poses[i]) for i in sub}, sub, voxel)
+    src, dst = local(q), local(c)
+    if use_quatro:
+        return orc.coarse_to_fine_alignment(src, dst, max_corr_dist=max_corr_dist, score_thr=score_thr)
+    g = orc.GicpOracle(k=15, max_iter=32, max_corr_dist=max_corr_dist, trans_eps=0.01)
+    g.set_source(src); g.compute_covariances(0); g.set_target(dst); g.compute_covariances(1)
+    r = g.align(scancontext.seed_from_yaw(yaw).astype(np.float64))
+    return dict(valid=bool(r["converged"] and r["fitness"] < score_thr), converged=r["converged"], score=r["fitness"], T=r["Tf"].astype(np.float64))
+
+
 def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, submap_range=5, score_thr=1.5, verbose=True, backend="gpu", save_dir=None,
-        save_map_leaf=None, sensor="uniform", detector="radius", sc_max_dist=0.3, yaw_bias=0.006, verify="reference", sc_top_k=1, loop_every=1, catch_up=False):
+        save_map_leaf=None, sensor="uniform", detector="radius", sc_max_dist=0.3, yaw_bias=0.006, verify="reference", sc_top_k=1, loop_every=1, catch_up=False,
+        submap_matching=False):
     """sensor = "uniform": keyframe clouds sampled uniformly by area inside a disc (make_stream); "spinning": ray-cast spinning-LiDAR
     scans from the ground-truth poses of the same figure-8 (make_lidar_stream).  detector = "radius": the candidate is the closest older
     keyframe within `radius` of the corrected position (LC:34-56); "scancontext": the older keyframe nearest by Scan Context distance, kept
@@ -241,7 +257,12 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
     fast_lio_sam_qn.cpp:203-252); every keyframe is described on arrival.  Without catch_up a tick checks only the newest keyframe, as the reference's
     timer does (keyframes_.back()); with catch_up it checks every keyframe added since the last tick: one sc_query for all of them, then ONE
     verify_loop_pairs (verify_loop_pairs_c2f with use_quatro) for all their pairs; each query's best valid candidate becomes a factor (Z = inv(T),
-    variance = score), then one optimisation.  The oracle backend runs the same pairs through the twins and the CPU oracle.  loop_every = 1 is the loop above."""
+    variance = score), then one optimisation.  The oracle backend runs the same pairs through the twins and the CPU oracle.  loop_every = 1 is the loop above.
+    submap_matching (verify="relative"; the reference's enable_submap_matching, made drift-free): both sides of a pair are local submaps, the keyframes within
+    submap_range of the query / the candidate, each submap in its centre's own sensor frame and placed with the RAW ODOMETRY poses, so no pose-graph update
+    ever invalidates one.  At a tick the keyframes involved are described (KeyframeStore.submap_describe, with FPFH rows when use_quatro) unless their entry
+    is still current - a window is final once submap_range later keyframes exist - and the pairs go through ONE verify_loop_pairs_submap
+    (verify_loop_pairs_submap_c2f with use_quatro).  The oracle backend assembles the same windows (orc.assemble_submap, scancontext.relative_pose)."""
     if detector not in ("radius", "scancontext"):
         raise ValueError("detector must be 'radius' or 'scancontext', not %r" % (detector,))
     if verify not in ("reference", "relative"):
@@ -252,6 +273,8 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
         raise ValueError("loop_every must be >= 1, not %r" % (loop_every,))
     if (loop_every > 1 or catch_up) and (verify != "relative" or detector != "scancontext"):
         raise ValueError("loop_every > 1 / catch_up need verify='relative' and detector='scancontext'")
+    if submap_matching and verify != "relative":
+        raise ValueError("submap_matching needs verify='relative' (the reference's world-frame submap matching is verify='reference' without it)")
     if sensor == "uniform":
         scans, gt, odom, stamps = make_stream(n_kf, seed, yaw_bias=yaw_bias)
     elif sensor == "spinning":
@@ -278,6 +301,14 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
     pg = PoseGraph(); ids = []; corrected = []; sc_descs = {}
     prior_var = np.array([1e-4, 1e-4, 1e-4, 1e-2, 1e-2, 1e-2]); odom_var = prior_var.copy()   # FQ:112-114, 132-133 (rot, then trans)
     loops = []; t_reg = []; loop_T = []; last_tick = -1
+    sub_hi = {}                                                                             # keyframe -> the last keyframe of its described window
+
+    def describe_submaps(kfs, k):
+        """the local submaps of `kfs` with the k + 1 keyframes that exist, from raw odometry; entries whose window has not grown are kept"""
+        todo = [x for x in dict.fromkeys(kfs) if sub_hi.get(x) != min(x + submap_range, k)]
+        if todo:
+            st = store.submap_describe(ctx, [ids[x] for x in todo], odom[:k + 1], submap_range, voxel, with_features=use_quatro)
+            sub_hi.update({x: min(x + submap_range, k) for x, v in zip(todo, st) if v != engine.QN_ERR_CAPACITY})
     for k in range(n_kf):
         if backend == "gpu":
             ids.append(store.add(scans[k]) if scans is not None else cast_ids[k])
@@ -291,7 +322,7 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
             from qn_amd import scancontext
             if backend == "gpu":                                                             # every keyframe is described on arrival
                 store.sc_describe([ids[k]])
-                if use_quatro:
+                if use_quatro and not submap_matching:
                     store.quatro_describe(ctx, [ids[k]], voxel)
             else:
                 sc_descs[k] = scancontext.descriptor(scans[k])
@@ -313,7 +344,13 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
             if not pq:
                 continue
             t0 = time.perf_counter()
-            if use_quatro and backend == "gpu":
+            if submap_matching and backend == "gpu":
+                describe_submaps(pq + pc, k)
+                rs = (store.verify_loop_pairs_submap_c2f(ctx, [ids[q] for q in pq], [ids[x] for x in pc], score_thr) if use_quatro else
+                      store.verify_loop_pairs_submap(ctx, [ids[q] for q in pq], [ids[x] for x in pc], py, score_thr))
+            elif submap_matching:
+                rs = [_oracle_submap_relative(orc, scans, odom[:k + 1], q, x, y, submap_range, voxel, 1.5 * radius, score_thr, use_quatro) for q, x, y in zip(pq, pc, py)]
+            elif use_quatro and backend == "gpu":
                 rs = store.verify_loop_pairs_c2f(ctx, [ids[q] for q in pq], [ids[x] for x in pc], score_thr)
             elif use_quatro:
                 rs = [orc.coarse_to_fine_alignment(orc.voxel_grid(scans[q], voxel), orc.voxel_grid(scans[x], voxel), max_corr_dist=1.5 * radius, score_thr=score_thr)
@@ -341,7 +378,7 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
             cand = loop_candidates(pos, stamps[:k + 1], k, radius, tdiff, max_k=1)
         elif backend == "gpu":                                                               # store ids are keyframe indices here
             store.sc_describe([ids[k]])
-            if verify == "relative" and use_quatro:                                          # the keyframe's Quatro features, once, on arrival
+            if verify == "relative" and use_quatro and not submap_matching:                  # the keyframe's Quatro features, once, on arrival
                 store.quatro_describe(ctx, [ids[k]], voxel)
             c_ids, c_d, c_sh = store.sc_query([ids[k]], stamps, tdiff, sc_top_k if verify == "relative" else 1)[0]
             cand, shifts = c_ids[c_d < sc_max_dist], c_sh[c_d < sc_max_dist]
@@ -356,7 +393,13 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
             from qn_amd import scancontext
             cand = [int(x) for x in cand]; yaws = [scancontext.yaw_of_shift(int(x), scancontext.Params().n_sectors) for x in shifts]
             t0 = time.perf_counter()
-            if use_quatro and backend == "gpu":
+            if submap_matching and backend == "gpu":
+                describe_submaps([k] + cand, k)
+                rs = (store.verify_loop_candidates_submap_c2f(ctx, ids[k], [ids[x] for x in cand], score_thr) if use_quatro else
+                      store.verify_loop_candidates_submap(ctx, ids[k], [ids[x] for x in cand], yaws, score_thr))
+            elif submap_matching:
+                rs = [_oracle_submap_relative(orc, scans, odom[:k + 1], k, x, y, submap_range, voxel, 1.5 * radius, score_thr, use_quatro) for x, y in zip(cand, yaws)]
+            elif use_quatro and backend == "gpu":
                 rs = store.verify_loop_candidates_c2f(ctx, ids[k], [ids[x] for x in cand], score_thr)
             elif use_quatro:
                 rs = [orc.coarse_to_fine_alignment(orc.voxel_grid(scans[k], voxel), orc.voxel_grid(scans[x], voxel), max_corr_dist=1.5 * radius, score_thr=score_thr)
@@ -411,7 +454,7 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
         corrected = [p.copy() for p in pg.poses]                                             # FQ:180-188
     out = dict(sensor=sensor, detector=detector, n_keyframes=n_kf, loops=len(loops), attempts=len(t_reg), ate_odometry=ate(odom, gt), ate_corrected=ate(corrected, gt),
                ms_per_attempt=1e3 * float(np.mean(t_reg)) if t_reg else None, quatro=use_quatro, verify=verify, loop_list=loops, poses=corrected,
-               loop_T=loop_T, gt=gt, loop_every=loop_every, catch_up=catch_up)
+               loop_T=loop_T, gt=gt, loop_every=loop_every, catch_up=catch_up, submap_matching=submap_matching)
     if save_dir:
         write_kitti_tum(save_dir, corrected, stamps)
         if save_map_leaf is not None and backend == "gpu":
@@ -440,7 +483,9 @@ if __name__ == "__main__":
     ap.add_argument("--sc-top-k", type=int, default=1, help="with --verify relative: Scan Context candidates verified per query, in one batched registration")
     ap.add_argument("--loop-every", type=int, default=1, help="with --verify relative: the loop timer fires after every N-th keyframe (loop_update_hz)")
     ap.add_argument("--catch-up", action="store_true", help="with --loop-every: a tick checks every keyframe added since the last one, in one batched verification")
+    ap.add_argument("--submap-matching", action="store_true",
+                    help="with --verify relative: submap against submap from resident local submaps (the reference's enable_submap_matching, drift-free); with --quatro coarse to fine")
     ap.add_argument("--backend", choices=["gpu", "oracle"], default="gpu", help="the engine on the GPU, or the CPU oracle")
     a = ap.parse_args()
     run(a.keyframes, a.seed, a.quatro, save_dir=a.save_dir, save_map_leaf=a.save_map_leaf, sensor=a.sensor, detector=a.detector, yaw_bias=a.yaw_bias,
-        verify=a.verify, sc_top_k=a.sc_top_k, backend=a.backend, loop_every=a.loop_every, catch_up=a.catch_up)
+        verify=a.verify, sc_top_k=a.sc_top_k, backend=a.backend, loop_every=a.loop_every, catch_up=a.catch_up, submap_matching=a.submap_matching)
