@@ -463,6 +463,56 @@ static bool ids_valid(const qn_kf_store* s, const int32_t* ids, uint32_t a, uint
   return true;
 }
 
+// ---- the segment-tagged stable sort of the voxel-grid pipeline, as functions (voxel_submaps and the cell index of qn_kf_int_cell_index use them).
+// sort groups: consecutive segments whose (segment, leaf) fields fit the 32 key bits above the point index; lbits[t] = the leaf bits segment t needs,
+// p0[t] its first point.  Sets every segment's key prefix.
+struct SortGroup { uint32_t s0, s1; int L, sb; };
+static std::vector<SortGroup> sort_groups(const std::vector<int>& lbits, uint32_t n_seg, qn::BatchSeg* sg, const std::vector<uint32_t>& p0) {
+  std::vector<SortGroup> groups;
+  { uint32_t g0 = 0; int L = 0;
+    for (uint32_t t = 0; t < n_seg; t++) {
+      const int L2 = std::max(L, lbits[t]);
+      if (t > g0 && L2 + bits_for(t - g0) > 32) { groups.push_back(SortGroup{g0, t, L, bits_for(t - 1 - g0)}); g0 = t; L = lbits[t]; }
+      else L = L2;
+    }
+    groups.push_back(SortGroup{g0, n_seg, L, bits_for(n_seg - 1 - g0)}); }
+  for (const SortGroup& gr : groups)
+    for (uint32_t t = gr.s0; t < gr.s1; t++) sg[t].prefix = (t - gr.s0) << gr.L;
+  return groups;
+}
+// the digit-major block histograms of the largest radix pass
+static bool sort_scratch(qn_kf_store* s, const std::vector<SortGroup>& groups, const std::vector<uint32_t>& p0) {
+  size_t hn = 0;
+  for (const SortGroup& gr : groups) hn = std::max<size_t>(hn, 256 * (size_t)radix_blocks(p0[gr.s1] - p0[gr.s0]));
+  return dev_grow(s, s->hist, hn + 1) && dev_grow(s, s->hist_sums, scan_blocks(hn));
+}
+// stable LSD passes over each group's (segment, leaf) bits only, on its own point range of s->keys; every group's result ends in one buffer, *fin
+static int sort_segments(qn_kf_store* s, const std::vector<SortGroup>& groups, const std::vector<uint32_t>& p0, unsigned long long** fin_out) {
+  hipStream_t st = s->stream;
+  unsigned long long* fin = nullptr;
+  for (const SortGroup& gr : groups) {
+    const uint32_t gp0 = p0[gr.s0], gn = p0[gr.s1] - gp0;
+    if (!gn) continue;
+    unsigned long long* sorted = s->keys.p + gp0; unsigned long long* other = s->keys_alt.p + gp0;
+    const bool small = radix_items(gn) == 1;
+    const uint32_t rb = radix_blocks(gn), ghn = rb * 256, hsb = scan_blocks(ghn);
+    for (int shift = 32; shift < 32 + gr.L + gr.sb; shift += 8) {
+      hipLaunchKernelGGL(small ? qn::k_map_radix_hist<1> : qn::k_map_radix_hist<QN_MAP_ITEMS>, dim3(rb), dim3(QN_BLOCK), 0, st, (const unsigned long long*)sorted, gn, shift, rb, s->hist.p);
+      hipLaunchKernelGGL(qn::k_scan_block, dim3(hsb), dim3(QN_BLOCK), 0, st, s->hist.p, ghn, s->hist.p, s->hist_sums.p);
+      hipLaunchKernelGGL(qn::k_scan_top, dim3(1), dim3(QN_BLOCK), 0, st, s->hist_sums.p, hsb);
+      hipLaunchKernelGGL(qn::k_scan_add, dim3(hsb), dim3(QN_BLOCK), 0, st, s->hist.p, ghn, s->hist_sums.p, gn);
+      hipLaunchKernelGGL(small ? qn::k_map_radix_scatter<1> : qn::k_map_radix_scatter<QN_MAP_ITEMS>, dim3(rb), dim3(QN_BLOCK), 0, st, (const unsigned long long*)sorted, gn, shift, rb,
+                         (const uint32_t*)s->hist.p, other);
+      std::swap(sorted, other);
+    }
+    unsigned long long* base = sorted - gp0;
+    if (!fin) fin = base;
+    else if (base != fin) KFCHK(s, hipMemcpyAsync(fin + gp0, sorted, sizeof(unsigned long long) * gn, hipMemcpyDeviceToDevice, st));
+  }
+  *fin_out = fin;
+  return QN_OK;
+}
+
 // ---- the one voxel-grid pipeline.  Submap t = the keyframes ids[seg_off[t] .. seg_off[t + 1]) (ids already checked) with the poses of the
 // same entries, transformed, concatenated in list order and voxel-grid at `leaf`, every submap into `out` (the caller's slot).
 // carry_intensity: the centroids average .w (the map), else w = 1.  A submap that trips PCL's overflow guard is passed through behind the
@@ -542,45 +592,12 @@ static int voxel_submaps(qn_kf_store* s, const int32_t* ids, const double* poses
     lbits[t] = bits_for(bb.nonfinite ? g.sentinel : g.sentinel - 1);  // the sentinel leaf needs key bits only when some point carries it
   }
   if (sum_vox + sum_trip == 0) return QN_OK;                        // every submap empty
-  // sort groups: consecutive submaps whose (submap, leaf) fields fit the 32 key bits above the point index
-  struct Group { uint32_t s0, s1; int L, sb; };
-  std::vector<Group> groups;
-  { uint32_t g0 = 0; int L = 0;
-    for (uint32_t t = 0; t < n_seg; t++) {
-      const int L2 = std::max(L, lbits[t]);
-      if (t > g0 && L2 + bits_for(t - g0) > 32) { groups.push_back(Group{g0, t, L, bits_for(t - 1 - g0)}); g0 = t; L = lbits[t]; }
-      else L = L2;
-    }
-    groups.push_back(Group{g0, n_seg, L, bits_for(n_seg - 1 - g0)}); }
-  size_t hn = 0;                                                    // the digit-major block histograms of the largest radix pass
-  for (const Group& gr : groups) {
-    for (uint32_t t = gr.s0; t < gr.s1; t++) sg[t].prefix = (t - gr.s0) << gr.L;
-    hn = std::max<size_t>(hn, 256 * (size_t)radix_blocks(p0[gr.s1] - p0[gr.s0]));
-  }
-  if (!dev_grow(s, out, sum_vox + sum_trip) || !dev_grow(s, s->hist, hn + 1) || !dev_grow(s, s->hist_sums, scan_blocks(hn))) return QN_ERR_HIP;
+  const std::vector<SortGroup> groups = sort_groups(lbits, n_seg, sg, p0);
+  if (!dev_grow(s, out, sum_vox + sum_trip) || !sort_scratch(s, groups, p0)) return QN_ERR_HIP;
   KFCHK(s, hipMemcpyAsync(s->tab.p + tb.seg, sg, tb.end - tb.seg, hipMemcpyHostToDevice, st));
   hipLaunchKernelGGL(qn::k_batch_keys, dim3(nt * QN_MAP_ITEMS), dim3(QN_BLOCK), 0, st, dkf, dblk, dks, dsg, (const float4*)s->concat.p, s->keys.p);
-  // stable LSD passes over each group's (submap, leaf) bits only, on its own point range; every group's result ends in one buffer
   unsigned long long* fin = nullptr;
-  for (const Group& gr : groups) {
-    const uint32_t gp0 = p0[gr.s0], gn = p0[gr.s1] - gp0;
-    if (!gn) continue;
-    unsigned long long* sorted = s->keys.p + gp0; unsigned long long* other = s->keys_alt.p + gp0;
-    const bool small = radix_items(gn) == 1;
-    const uint32_t rb = radix_blocks(gn), ghn = rb * 256, hsb = scan_blocks(ghn);
-    for (int shift = 32; shift < 32 + gr.L + gr.sb; shift += 8) {
-      hipLaunchKernelGGL(small ? qn::k_map_radix_hist<1> : qn::k_map_radix_hist<QN_MAP_ITEMS>, dim3(rb), dim3(QN_BLOCK), 0, st, (const unsigned long long*)sorted, gn, shift, rb, s->hist.p);
-      hipLaunchKernelGGL(qn::k_scan_block, dim3(hsb), dim3(QN_BLOCK), 0, st, s->hist.p, ghn, s->hist.p, s->hist_sums.p);
-      hipLaunchKernelGGL(qn::k_scan_top, dim3(1), dim3(QN_BLOCK), 0, st, s->hist_sums.p, hsb);
-      hipLaunchKernelGGL(qn::k_scan_add, dim3(hsb), dim3(QN_BLOCK), 0, st, s->hist.p, ghn, s->hist_sums.p, gn);
-      hipLaunchKernelGGL(small ? qn::k_map_radix_scatter<1> : qn::k_map_radix_scatter<QN_MAP_ITEMS>, dim3(rb), dim3(QN_BLOCK), 0, st, (const unsigned long long*)sorted, gn, shift, rb,
-                         (const uint32_t*)s->hist.p, other);
-      std::swap(sorted, other);
-    }
-    unsigned long long* base = sorted - gp0;
-    if (!fin) fin = base;
-    else if (base != fin) KFCHK(s, hipMemcpyAsync(fin + gp0, sorted, sizeof(unsigned long long) * gn, hipMemcpyDeviceToDevice, st));
-  }
+  { const int src = sort_segments(s, groups, p0, &fin); if (src != QN_OK) return src; }
   // leaves of all submaps at once: heads, exclusive scan, bounds, one thread per leaf
   const uint32_t sb = scan_blocks(n);
   hipLaunchKernelGGL(qn::k_batch_leaf_flags, dim3(nt * QN_MAP_ITEMS), dim3(QN_BLOCK), 0, st, dkf, dblk, dks, dsg, (const unsigned long long*)fin, s->flag.p);
@@ -610,6 +627,83 @@ static int voxel_submaps(qn_kf_store* s, const int32_t* ids, const double* poses
     const bool tr = sg[t].tripped != 0;
     res[t] = SubmapOut{out.p + (tr ? sum_vox + trip_off[t] : s->seg_res_host.p[2 * t]), tr ? ntrip[t] : s->seg_res_host.p[2 * t + 1], QN_OK};
   }
+  return QN_OK;
+}
+
+// ---- a sorted-key cell index over arbitrary device clouds, for bounded-radius searches (qn_overlap.hip): the front half of the voxel-grid pipeline with
+// every cloud as its own segment under the identity pose - the same transform / box kernels, voxel_dims(), segment-tagged keys and stable radix passes.
+// The cell edge of a cloud is at least (radius + 2^-21 max|coordinate|) (1 + 1e-5): two points whose f32 squared distance is <= float(radius^2) are at most
+// radius (1 + 2^-21) apart along an axis, and their f32 cell coordinates floor(x * inv) each carry a rounding error of at most 2^-24 of their size
+// (<= max|coordinate| / edge), so the two coordinates differ by at most 1 and the partner lies in the 3 x 3 x 3 block around the query's cell.  The edge is
+// widened by a quarter at a time while the cloud's cell count needs more than QN_CELL_LEAF_BITS key bits (or trips voxel_dims' own guard): it depends on the
+// cloud and the radius alone, never on the other clouds of the call.  One host synchronisation (the boxes).  The index lives in the pipeline's scratch.
+#define QN_CELL_LEAF_BITS 26
+int qn_kf_int_cell_index(qn_kf_store* s, const float4* const* clouds, const uint32_t* n_pts, uint32_t count, double radius,
+                         qn_kf_int_cell_grid* grids, const float4** points, const unsigned long long** keys) {
+  size_t total = 0, tiles = 0;
+  for (uint32_t k = 0; k < count; k++) { total += n_pts[k]; tiles += tiles_of(n_pts[k]); grids[k] = qn_kf_int_cell_grid{}; }
+  *points = nullptr; *keys = nullptr;
+  if (total >= 0xffffffffull) return QN_ERR_CAPACITY;
+  if (total == 0) return QN_OK;
+  KFCHK(s, hipSetDevice(s->device));
+  const uint32_t n = (uint32_t)total, nt = (uint32_t)tiles;
+  const Tables tb(count, tiles, count);
+  if (!dev_grow(s, s->concat, n) || !dev_grow(s, s->keys, n) || !dev_grow(s, s->keys_alt, n) || !dev_grow(s, s->tile_box, nt) || !dev_grow(s, s->seg_box, count) ||
+      !dev_grow(s, s->tab, tb.end) || !pin_grow(s, s->tab_host, tb.end) || !pin_grow(s, s->seg_box_host, count)) return QN_ERR_HIP;
+  char* h = s->tab_host.p;
+  qn::MapKf* kfs = (qn::MapKf*)(h + tb.kf); uint32_t* blk = (uint32_t*)(h + tb.blk); uint32_t* kseg = (uint32_t*)(h + tb.kseg); uint32_t* toff = (uint32_t*)(h + tb.toff);
+  double* pose = (double*)(h + tb.pose);
+  std::vector<uint32_t> p0(count + 1);
+  uint32_t off = 0, b0 = 0;
+  for (uint32_t k = 0; k < count; k++) {
+    for (int i = 0; i < 16; i++) pose[16 * (size_t)k + i] = (i % 5 == 0) ? 1.0 : 0.0;
+    const uint32_t ntk = tiles_of(n_pts[k]);
+    toff[k] = b0; p0[k] = off; kseg[k] = k;
+    kfs[k] = qn::MapKf{clouds[k], off, n_pts[k], b0, 0};
+    for (uint32_t b = 0; b < ntk; b++) blk[b0 + b] = k;
+    off += n_pts[k]; b0 += ntk;
+  }
+  toff[count] = b0; p0[count] = off;
+  hipStream_t st = s->stream;
+  KFCHK(s, hipMemcpyAsync(s->tab.p, h, tb.seg, hipMemcpyHostToDevice, st));
+  const char* d = s->tab.p;
+  const qn::MapKf* dkf = (const qn::MapKf*)(d + tb.kf); const uint32_t* dblk = (const uint32_t*)(d + tb.blk); const uint32_t* dks = (const uint32_t*)(d + tb.kseg);
+  const qn::BatchSeg* dsg = (const qn::BatchSeg*)(d + tb.seg);
+  hipLaunchKernelGGL(qn::k_map_transform, dim3(nt), dim3(QN_BLOCK), 0, st, dkf, dblk, (const double*)(d + tb.pose), s->concat.p, s->tile_box.p);
+  hipLaunchKernelGGL(qn::k_seg_bbox_reduce, dim3(count), dim3(QN_BLOCK), 0, st, (const qn::BBoxOut*)s->tile_box.p, (const uint32_t*)(d + tb.toff), s->seg_box.p);
+  KFCHK(s, hipMemcpyAsync(s->seg_box_host.p, s->seg_box.p, sizeof(qn::BBoxOut) * count, hipMemcpyDeviceToHost, st));
+  KFCHK(s, hipGetLastError());
+  KFCHK(s, hipStreamSynchronize(st));                               // the one sync: each cloud's box sizes its cells
+  qn::BatchSeg* sg = (qn::BatchSeg*)(h + tb.seg); std::vector<int> lbits(count);
+  for (uint32_t k = 0; k < count; k++) {
+    qn::BatchSeg& g = sg[k];
+    g = qn::BatchSeg{}; g.p0 = p0[k]; g.p1 = p0[k + 1]; g.sentinel = 1; g.tripped = 0;
+    g.vd = qn::VoxelDims{1.0f, {0, 0, 0}, 1, 1};
+    const qn::BBoxOut bb = s->seg_box_host.p[k];
+    const uint32_t nfin = n_pts[k] - bb.nonfinite;
+    long long cells = 1;
+    if (nfin) {
+      double maxabs = 0.0;
+      for (int a = 0; a < 3; a++) maxabs = std::max(maxabs, (double)std::max(std::fabs(qn::ord2f(bb.mn[a])), std::fabs(qn::ord2f(bb.mx[a]))));
+      double edge = std::max((radius + std::ldexp(maxabs, -21)) * (1.0 + 1e-5), 1e-30);
+      while (!voxel_dims(bb, edge, &g.vd, &cells) || cells >= (1ll << QN_CELL_LEAF_BITS)) edge *= 1.25;
+      g.sentinel = (uint32_t)cells; g.nvox = nfin;
+    }
+    lbits[k] = bits_for(bb.nonfinite ? g.sentinel : g.sentinel - 1);
+    qn_kf_int_cell_grid& o = grids[k];
+    o.p0 = g.p0; o.n = n_pts[k]; o.n_finite = nfin; o.inv = g.vd.inv;
+    for (int a = 0; a < 3; a++) o.minb[a] = g.vd.minb[a];
+    o.div[0] = g.vd.div0; o.div[1] = g.vd.div01 / g.vd.div0; o.div[2] = (int)(cells / g.vd.div01);
+  }
+  const std::vector<SortGroup> groups = sort_groups(lbits, count, sg, p0);
+  for (uint32_t k = 0; k < count; k++) grids[k].prefix = sg[k].prefix;
+  if (!sort_scratch(s, groups, p0)) return QN_ERR_HIP;
+  KFCHK(s, hipMemcpyAsync(s->tab.p + tb.seg, sg, tb.end - tb.seg, hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(qn::k_batch_keys, dim3(nt * QN_MAP_ITEMS), dim3(QN_BLOCK), 0, st, dkf, dblk, dks, dsg, (const float4*)s->concat.p, s->keys.p);
+  unsigned long long* fin = nullptr;
+  { const int src = sort_segments(s, groups, p0, &fin); if (src != QN_OK) return src; }
+  KFCHK(s, hipGetLastError());
+  *points = s->concat.p; *keys = fin;
   return QN_OK;
 }
 

@@ -25,11 +25,12 @@ const float4* qn_kf_int_keyframe(const qn_kf_store* s, int32_t id, uint32_t* n);
 // per-store state of another translation unit (slot QN_KF_INT_EXT_SC: qn_sc.hip's descriptors, QN_KF_INT_EXT_QUATRO: the resident Quatro features of
 // qn_kf_quatro.inc, QN_KF_INT_EXT_VERIFY: qn_verify.hip's record of the latest multi-pair verification, QN_KF_INT_EXT_SUBMAP: the resident local submaps of
 // qn_kf_submap.inc): nullptr until set; the store owns it from qn_kf_int_set_ext on and calls `release` from qn_kf_store_destroy once its stream has drained.
-#define QN_KF_INT_EXT 4
+#define QN_KF_INT_EXT 5
 #define QN_KF_INT_EXT_SC 0
 #define QN_KF_INT_EXT_QUATRO 1
 #define QN_KF_INT_EXT_VERIFY 2
 #define QN_KF_INT_EXT_SUBMAP 3
+#define QN_KF_INT_EXT_OVERLAP 4                                                  // qn_overlap.hip: the per-point results of the latest overlap call
 typedef void (*qn_kf_int_release_fn)(void*);
 void* qn_kf_int_ext(const qn_kf_store* s, int which);
 void qn_kf_int_set_ext(qn_kf_store* s, int which, void* p, qn_kf_int_release_fn release);
@@ -61,3 +62,16 @@ void qn_kf_int_verify_stale(qn_kf_store* s, int from, const int32_t* ids, uint32
 // in order in f64; g = Rz(-yaw) from the C library's cos / sin in f64, each entry rounded to f32.  Twins: scancontext.relative_pose / seed_from_yaw.
 void qn_kf_int_relative_pose(const double* Pc, const double* Pi, double* Q);
 void qn_kf_int_seed_from_yaw(double yaw, float* g);
+// qn_kf_verify_cloud(pair, QN_VERIFY_FINAL) without its synchronisation: the launch is enqueued on the store's stream and the pointer is good for work
+// enqueued there afterwards (qn_overlap.hip measures many pairs per call and may not synchronise once per pair).  Same statuses, same buffer, same lifetime.
+int qn_kf_int_verify_final_async(qn_kf_store* s, uint32_t pair, const float4** d_xyz, uint32_t* n);
+uint32_t qn_kf_int_verify_pairs(const qn_kf_store* s);                            // pairs of the live verify record, 0 when there is none
+// A sorted-key cell index over `count` device clouds (float4; clouds[k] may be nullptr when n[k] == 0), built by the front half of the store's voxel-grid
+// pipeline (qn_cloud.hip) with every cloud as its own segment: *points = the clouds concatenated (cloud k at grids[k].p0), *keys = one 64-bit key per point,
+// ((prefix | cell) << 32 | position in *points), sorted inside every cloud's range [p0, p0 + n) by cell, a cell's points in ascending original order, the
+// non-finite points behind the n_finite finite ones.  cell = cx + cy div[0] + cz div[0] div[1] with c = (int)(floorf(x * inv) - (float)minb); the cell edge
+// is >= radius with the margin that makes the 3 x 3 x 3 block around a query's cell hold every point within radius (argument: qn_cloud.hip).  Enqueued on the
+// store's stream after one host synchronisation; the buffers are the pipeline's scratch, good until the next call that runs the pipeline.
+struct qn_kf_int_cell_grid { uint32_t p0, n, n_finite, prefix; float inv; int minb[3]; int div[3]; };
+int qn_kf_int_cell_index(qn_kf_store* s, const float4* const* clouds, const uint32_t* n, uint32_t count, double radius,
+                         qn_kf_int_cell_grid* grids, const float4** points, const unsigned long long** keys);

@@ -1,0 +1,273 @@
+// qn_overlap.hip - the two-way overlap of cloud pairs on the GPU (qn_kf_overlap_batch, qn_kf_verify_overlap, qn_kf_overlap_points: include/qn_engine.h).
+// For clouds A and B in one frame and a radius r: every point's exact nearest neighbour in the other cloud when it lies within r (f32 squared distance
+// <= float(r * r), the oracle's sqdist3 arithmetic, ties to the lowest index), and per direction the number of such points and the f64 sum of their squared
+// distances.  The numpy twin qn_amd/overlap.py is the specification; the results equal it bit for bit.
+//   index   qn_kf_int_cell_index (qn_cloud.hip): the front half of the store's voxel-grid pipeline with every cloud a segment - boxes, cell keys, stable
+//           radix passes - gives each cloud sorted by cell (edge >= r, x fastest), and k_overlap_gather lays the sorted points and their cells out flat;
+//   search  k_overlap_search, one query per lane, the pair and direction a grid dimension.  Queries are walked in the sorted order of their OWN cloud:
+//           neighbouring lanes are neighbouring points, and since both grids have cells of about r they read the same or adjacent runs of the other
+//           cloud (sorting the queries a second time by the other cloud's grid would buy the same locality for one more sort per cloud);
+//   reduce  k_overlap_reduce, one block per pair and direction over the per-point results in original point order: a fixed order, no atomics, so a rerun
+//           gives the same bits and a pair's sums do not depend on which other pairs share the call.
+// Exactness at cell borders: the cell edge carries the margin derived in qn_cloud.hip (qn_kf_int_cell_index), so a partner within r has f32 cell coordinates
+// within one of the query's on every axis, whichever way either rounds; the query's coordinates come from the very expression k_batch_keys uses.  A minimum
+// that is <= float(r * r) is therefore found among the 27 cells, and so is every point that ties with it; a minimum above it is reported as no partner.
+// Host synchronisations per call: two, whatever the number of pairs (the boxes; the records).
+#include <hip/hip_runtime.h>
+#include <cmath>
+#include <cstring>
+#include <new>
+#include <vector>
+#include <algorithm>
+#include "../../include/qn_engine.h"
+#include "qn_kf_internal.h"
+
+namespace {
+
+#define QN_OV_BLOCK 256
+struct OvSeg { uint32_t p0, n, nfin, prefix; float inv; float minb[3]; int div[3]; };
+struct OvRes { double sum; uint32_t inliers, pad; };
+
+// the sorted order laid out flat: point t of a cloud's sorted range with its original index (bits in .w), and its (prefix | cell) word
+__global__ void __launch_bounds__(QN_OV_BLOCK) k_overlap_gather(const OvSeg* __restrict__ segs, const unsigned long long* __restrict__ keys, const float4* __restrict__ pts,
+                                                                 float4* __restrict__ spts, uint32_t* __restrict__ cells) {
+  const OvSeg S = segs[blockIdx.y];
+  const uint32_t t = blockIdx.x * QN_OV_BLOCK + threadIdx.x;
+  if (t >= S.n) return;
+  const uint32_t g = S.p0 + t;
+  const unsigned long long key = keys[g];
+  const uint32_t src = (uint32_t)key;
+  const float4 p = pts[src];
+  spts[g] = make_float4(p.x, p.y, p.z, __uint_as_float(src - S.p0));
+  cells[g] = (uint32_t)(key >> 32);
+}
+
+__device__ __forceinline__ int cell_coord(float x, float inv, float minb, int div) {
+  // k_batch_keys' expression; clamped in float so that a query far outside the other cloud's box stays a valid int (it then has no cell to visit)
+  const float c = floorf(x * inv) - minb;
+  return (int)fminf(fmaxf(c, -2.0f), (float)div + 1.0f);
+}
+
+// One query per lane.  Nine x-runs (cells x-1 .. x+1 of one (y, z) are consecutive keys), each found by a binary search over the sorted cell words that starts
+// where the previous run ended (runs are visited in ascending key order), then read four candidates a trip.
+__global__ void __launch_bounds__(QN_OV_BLOCK) k_overlap_search(const OvSeg* __restrict__ segs, const float4* __restrict__ spts, const uint32_t* __restrict__ cells, float r2,
+                                                                 float* __restrict__ nn_d2, int32_t* __restrict__ nn_idx) {
+  const OvSeg Q = segs[blockIdx.y];
+  const uint32_t t = blockIdx.x * QN_OV_BLOCK + threadIdx.x;
+  if (t >= Q.n) return;
+  const OvSeg T = segs[blockIdx.y ^ 1u];
+  const float4 q = spts[Q.p0 + t];
+  const uint32_t qi = __float_as_uint(q.w);
+  float best = INFINITY; uint32_t bi = 0xffffffffu;
+  if (t < Q.nfin && T.nfin) {
+    const int cx = cell_coord(q.x, T.inv, T.minb[0], T.div[0]), cy = cell_coord(q.y, T.inv, T.minb[1], T.div[1]), cz = cell_coord(q.z, T.inv, T.minb[2], T.div[2]);
+    const int x0 = max(cx - 1, 0), x1 = min(cx + 1, T.div[0] - 1);
+    if (x0 <= x1) {
+      uint32_t lo = T.p0;
+      const uint32_t end = T.p0 + T.nfin;
+      for (int dz = -1; dz <= 1; dz++) {
+        const int z = cz + dz;
+        if ((unsigned)z >= (unsigned)T.div[2]) continue;
+        for (int dy = -1; dy <= 1; dy++) {
+          const int y = cy + dy;
+          if ((unsigned)y >= (unsigned)T.div[1]) continue;
+          const uint32_t k0 = T.prefix | (uint32_t)(x0 + (y + z * T.div[1]) * T.div[0]), k1 = k0 + (uint32_t)(x1 - x0);
+          uint32_t a = lo, b = end;
+          while (a < b) { const uint32_t m = (a + b) >> 1; if (cells[m] < k0) a = m + 1; else b = m; }
+          for (;;) {
+            if (a >= end) break;
+            uint32_t c[4]; float4 p[4];
+#pragma unroll
+            for (int j = 0; j < 4; j++) { const uint32_t i = min(a + j, end - 1); c[j] = cells[i]; p[j] = spts[i]; }
+            bool more = true;
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+              more = more && a + j < end && c[j] <= k1;
+              if (more) {
+                const float dx = q.x - p[j].x, dy2 = q.y - p[j].y, dz2 = q.z - p[j].z;
+                const float d2 = dx * dx + dy2 * dy2 + dz2 * dz2;
+                const uint32_t id = __float_as_uint(p[j].w);
+                if (d2 < best || (d2 == best && id < bi)) { best = d2; bi = id; }
+              }
+            }
+            if (!more) break;
+            a += 4;
+          }
+          lo = a;
+        }
+      }
+    }
+  }
+  if (!(best <= r2)) { best = INFINITY; bi = 0xffffffffu; }
+  nn_d2[Q.p0 + qi] = best;
+  nn_idx[Q.p0 + qi] = (int32_t)bi;
+}
+
+// one block per pair and direction: thread i sums points i, i + 256, ... in f64, then a butterfly inside each wave and the waves in order
+__global__ void __launch_bounds__(QN_OV_BLOCK) k_overlap_reduce(const OvSeg* __restrict__ segs, const float* __restrict__ nn_d2, OvRes* __restrict__ res) {
+  __shared__ double wsum[QN_OV_BLOCK / 64];
+  __shared__ uint32_t wcnt[QN_OV_BLOCK / 64];
+  const OvSeg S = segs[blockIdx.x];
+  double acc = 0.0; uint32_t cnt = 0;
+  for (uint32_t i = threadIdx.x; i < S.n; i += QN_OV_BLOCK) {
+    const float v = nn_d2[S.p0 + i];
+    if (v < INFINITY) { acc = acc + (double)v; cnt++; }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) { acc = acc + __shfl_xor(acc, o); cnt += __shfl_xor(cnt, o); }
+  if ((threadIdx.x & 63) == 0) { wsum[threadIdx.x >> 6] = acc; wcnt[threadIdx.x >> 6] = cnt; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < QN_OV_BLOCK / 64; w++) { acc = acc + wsum[w]; cnt += wcnt[w]; }
+    OvRes r; r.sum = acc; r.inliers = cnt; r.pad = 0;
+    res[blockIdx.x] = r;
+  }
+}
+
+// the per-point results of the latest overlap call (store slot QN_KF_INT_EXT_OVERLAP), in buffers of their own: the store's scratch may be reused by any
+// other call before qn_kf_overlap_points asks
+struct OvSlot { uint32_t p0[2], n[2]; int status; };
+struct OverlapState {
+  bool live = false; std::vector<OvSlot> slots;
+  float* d2 = nullptr; int32_t* idx = nullptr; size_t cap = 0;
+  ~OverlapState() { if (d2) (void)hipFree(d2); if (idx) (void)hipFree(idx); }
+};
+void overlap_release(void* p) { delete (OverlapState*)p; }
+
+int fail(qn_kf_store* s, const char* msg) { qn_kf_int_set_error(s, msg); return QN_ERR_HIP; }
+
+// the pairs (A_j = cl[2 j], B_j = cl[2 j + 1]) whose pre[j] is QN_OK; arguments already checked
+int overlap_run(qn_kf_store* s, std::vector<const float4*>& cl, std::vector<uint32_t>& n, const std::vector<int>& pre, uint32_t P, double radius, qn_overlap* out, int* status) {
+  OverlapState* st = (OverlapState*)qn_kf_int_ext(s, QN_KF_INT_EXT_OVERLAP);
+  if (!st) {
+    st = new (std::nothrow) OverlapState();
+    if (!st) return fail(s, "qn_kf_overlap: out of memory");
+    qn_kf_int_set_ext(s, QN_KF_INT_EXT_OVERLAP, st, overlap_release);
+  }
+  st->live = false;
+  for (uint32_t j = 0; j < P; j++) {
+    memset(&out[j], 0, sizeof(out[j]));
+    status[j] = pre[j] != QN_OK ? pre[j] : (n[2 * j] == 0 || n[2 * j + 1] == 0) ? QN_ERR_EMPTY_CLOUD : QN_OK;
+    if (status[j] != QN_OK) { n[2 * j] = n[2 * j + 1] = 0; cl[2 * j] = cl[2 * j + 1] = nullptr; }
+  }
+  const uint32_t S = 2 * P;
+  std::vector<qn_kf_int_cell_grid> grid(S);
+  const float4* pts = nullptr; const unsigned long long* keys = nullptr;
+  const int rc = qn_kf_int_cell_index(s, cl.data(), n.data(), S, radius, grid.data(), &pts, &keys);      // sync 1 of 2
+  if (rc != QN_OK) return rc;
+  size_t total = 0; uint32_t nmax = 0;
+  for (uint32_t k = 0; k < S; k++) { total += n[k]; nmax = std::max(nmax, n[k]); }
+  st->slots.assign(P, OvSlot{});
+  for (uint32_t j = 0; j < P; j++) {
+    OvSlot& o = st->slots[j];
+    for (int d = 0; d < 2; d++) { o.p0[d] = grid[2 * j + d].p0; o.n[d] = n[2 * j + d]; }
+    o.status = status[j];
+  }
+  if (total == 0) { st->live = true; return QN_OK; }
+  if (hipSetDevice(qn_kf_int_device(s)) != hipSuccess) return fail(s, "qn_kf_overlap: hipSetDevice failed");
+  hipStream_t stream = qn_kf_int_stream(s);
+  if (total > st->cap) {
+    if (st->d2) (void)hipFree(st->d2); if (st->idx) (void)hipFree(st->idx);
+    st->d2 = nullptr; st->idx = nullptr; st->cap = 0;
+    const size_t cap = total + total / 2;
+    if (hipMalloc(&st->d2, sizeof(float) * cap) != hipSuccess || hipMalloc(&st->idx, sizeof(int32_t) * cap) != hipSuccess) { (void)hipGetLastError(); return fail(s, "qn_kf_overlap: hipMalloc failed"); }
+    st->cap = cap;
+  }
+  const size_t seg_bytes = (sizeof(OvSeg) * S + 15) & ~(size_t)15, res_bytes = sizeof(OvRes) * S;
+  OvSeg* d_seg = (OvSeg*)qn_kf_int_scratch(s, 0, seg_bytes);
+  float4* d_spts = (float4*)qn_kf_int_scratch(s, 1, sizeof(float4) * total);
+  uint32_t* d_cells = (uint32_t*)qn_kf_int_scratch(s, 2, sizeof(uint32_t) * total);
+  OvRes* d_res = (OvRes*)qn_kf_int_scratch(s, 3, res_bytes);
+  char* h = (char*)qn_kf_int_pinned(s, seg_bytes + res_bytes);
+  if (!d_seg || !d_spts || !d_cells || !d_res || !h) return fail(s, "qn_kf_overlap: scratch allocation failed");
+  OvSeg* h_seg = (OvSeg*)h; OvRes* h_res = (OvRes*)(h + seg_bytes);
+  for (uint32_t k = 0; k < S; k++) {
+    const qn_kf_int_cell_grid& g = grid[k];
+    OvSeg& o = h_seg[k];
+    o.p0 = g.p0; o.n = g.n; o.nfin = g.n_finite; o.prefix = g.prefix; o.inv = g.inv;
+    for (int a = 0; a < 3; a++) { o.minb[a] = (float)g.minb[a]; o.div[a] = g.div[a]; }
+  }
+  const double rr = radius * radius;
+  const float r2 = (float)rr;
+  const dim3 grid2((nmax + QN_OV_BLOCK - 1) / QN_OV_BLOCK, S);
+  if (hipMemcpyAsync(d_seg, h_seg, sizeof(OvSeg) * S, hipMemcpyHostToDevice, stream) != hipSuccess) return fail(s, "qn_kf_overlap: upload failed");
+  hipLaunchKernelGGL(k_overlap_gather, grid2, dim3(QN_OV_BLOCK), 0, stream, (const OvSeg*)d_seg, keys, pts, d_spts, d_cells);
+  hipLaunchKernelGGL(k_overlap_search, grid2, dim3(QN_OV_BLOCK), 0, stream, (const OvSeg*)d_seg, (const float4*)d_spts, (const uint32_t*)d_cells, r2, st->d2, st->idx);
+  hipLaunchKernelGGL(k_overlap_reduce, dim3(S), dim3(QN_OV_BLOCK), 0, stream, (const OvSeg*)d_seg, (const float*)st->d2, d_res);
+  if (hipGetLastError() != hipSuccess || hipMemcpyAsync(h_res, d_res, res_bytes, hipMemcpyDeviceToHost, stream) != hipSuccess ||
+      hipStreamSynchronize(stream) != hipSuccess) return fail(s, "qn_kf_overlap: the search failed");      // sync 2 of 2
+  for (uint32_t j = 0; j < P; j++) {
+    if (status[j] != QN_OK) continue;
+    qn_overlap_dir* d[2] = {&out[j].a_to_b, &out[j].b_to_a};
+    for (int k = 0; k < 2; k++) {
+      d[k]->n = grid[2 * j + k].n; d[k]->n_finite = grid[2 * j + k].n_finite; d[k]->inliers = h_res[2 * j + k].inliers; d[k]->reserved = 0; d[k]->sum_d2 = h_res[2 * j + k].sum;
+    }
+  }
+  st->live = true;
+  return QN_OK;
+}
+
+// n records of 16 bytes inside one device allocation of the store's device (a host pointer would fault the GPU)
+bool device_cloud_ok(int dev, const float* p, uint32_t n) {
+  if (!n) return true;
+  if (!p || ((uintptr_t)p & 15)) return false;
+  hipPointerAttribute_t a{};
+  if (hipPointerGetAttributes(&a, p) != hipSuccess || a.type != hipMemoryTypeDevice || a.device != dev) { (void)hipGetLastError(); return false; }
+  hipDeviceptr_t base = nullptr; size_t size = 0;
+  if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) { (void)hipGetLastError(); return false; }
+  return (const char*)p >= (const char*)base && (size_t)((const char*)p - (const char*)base) + 16 * (size_t)n <= size;
+}
+
+bool radius_ok(double r) { return std::isfinite(r) && r > 0.0; }
+const uint32_t kMaxPairs = 32767;       // the pair and direction are the grid's y dimension
+
+}  // namespace
+
+extern "C" int qn_kf_overlap_batch(qn_kf_store* s, const float* const* d_a, const uint32_t* n_a, const float* const* d_b, const uint32_t* n_b, uint32_t n_pairs,
+                                   double radius, qn_overlap* out, int* status) {
+  if (!s || !d_a || !n_a || !d_b || !n_b || n_pairs == 0 || !out || !status || !radius_ok(radius)) return QN_ERR_INVALID_ARG;
+  if (n_pairs > kMaxPairs) return QN_ERR_CAPACITY;
+  const int dev = qn_kf_int_device(s);
+  if (hipSetDevice(dev) != hipSuccess) return fail(s, "qn_kf_overlap_batch: hipSetDevice failed");
+  for (uint32_t j = 0; j < n_pairs; j++) if (!device_cloud_ok(dev, d_a[j], n_a[j]) || !device_cloud_ok(dev, d_b[j], n_b[j])) return QN_ERR_INVALID_ARG;
+  std::vector<const float4*> cl(2 * (size_t)n_pairs); std::vector<uint32_t> n(2 * (size_t)n_pairs);
+  for (uint32_t j = 0; j < n_pairs; j++) { cl[2 * j] = (const float4*)d_a[j]; n[2 * j] = n_a[j]; cl[2 * j + 1] = (const float4*)d_b[j]; n[2 * j + 1] = n_b[j]; }
+  return overlap_run(s, cl, n, std::vector<int>(n_pairs, QN_OK), n_pairs, radius, out, status);
+}
+
+extern "C" int qn_kf_verify_overlap(qn_kf_store* s, const uint32_t* pairs, uint32_t n_pairs, double radius, qn_overlap* out, int* status) {
+  if (!s || n_pairs == 0 || !out || !status || !radius_ok(radius)) return QN_ERR_INVALID_ARG;
+  if (n_pairs > kMaxPairs) return QN_ERR_CAPACITY;
+  const uint32_t have = qn_kf_int_verify_pairs(s);
+  if (!have) return QN_ERR_NOT_READY;
+  if (!pairs && n_pairs != have) return QN_ERR_INVALID_ARG;
+  if (pairs) {
+    std::vector<uint8_t> seen(have, 0);
+    for (uint32_t j = 0; j < n_pairs; j++) { if (pairs[j] >= have || seen[pairs[j]]) return QN_ERR_INVALID_ARG; seen[pairs[j]] = 1; }
+  }
+  std::vector<const float4*> cl(2 * (size_t)n_pairs, nullptr); std::vector<uint32_t> n(2 * (size_t)n_pairs, 0); std::vector<int> pre(n_pairs, QN_OK);
+  for (uint32_t j = 0; j < n_pairs; j++) {
+    const uint32_t pj = pairs ? pairs[j] : j;
+    int rc = qn_kf_int_verify_final_async(s, pj, &cl[2 * j], &n[2 * j]);
+    if (rc == QN_OK) rc = qn_kf_verify_cloud(s, pj, QN_VERIFY_DST, (const float**)&cl[2 * j + 1], &n[2 * j + 1]);
+    if (rc == QN_ERR_NOT_READY) { pre[j] = rc; cl[2 * j] = cl[2 * j + 1] = nullptr; n[2 * j] = n[2 * j + 1] = 0; }
+    else if (rc != QN_OK) return rc;
+  }
+  return overlap_run(s, cl, n, pre, n_pairs, radius, out, status);
+}
+
+extern "C" int qn_kf_overlap_points(qn_kf_store* s, uint32_t pair_slot, int dir, float* nn_d2_out, int32_t* nn_idx_out) {
+  if (!s || (dir != 0 && dir != 1) || (!nn_d2_out && !nn_idx_out)) return QN_ERR_INVALID_ARG;
+  OverlapState* st = (OverlapState*)qn_kf_int_ext(s, QN_KF_INT_EXT_OVERLAP);
+  if (!st || !st->live) return QN_ERR_NOT_READY;
+  if (pair_slot >= st->slots.size()) return QN_ERR_INVALID_ARG;
+  const OvSlot& o = st->slots[pair_slot];
+  if (o.status != QN_OK) return QN_ERR_NOT_READY;
+  if (hipSetDevice(qn_kf_int_device(s)) != hipSuccess) return fail(s, "qn_kf_overlap_points: hipSetDevice failed");
+  hipStream_t stream = qn_kf_int_stream(s);
+  bool ok = true;
+  if (nn_d2_out) ok = ok && hipMemcpyAsync(nn_d2_out, st->d2 + o.p0[dir], sizeof(float) * o.n[dir], hipMemcpyDeviceToHost, stream) == hipSuccess;
+  if (nn_idx_out) ok = ok && hipMemcpyAsync(nn_idx_out, st->idx + o.p0[dir], sizeof(int32_t) * o.n[dir], hipMemcpyDeviceToHost, stream) == hipSuccess;
+  ok = ok && hipStreamSynchronize(stream) == hipSuccess;
+  return ok ? QN_OK : fail(s, "qn_kf_overlap_points: the copy failed");
+}

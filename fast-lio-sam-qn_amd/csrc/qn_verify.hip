@@ -260,7 +260,15 @@ extern "C" int qn_kf_verify_loop_pairs(qn_kf_store* s, qn_ctx* ctx, const int32_
   return qn_kf_int_verify_record(s, QN_KF_VERIFY_GICP, rec.data(), n_pairs);
 }
 
-extern "C" int qn_kf_verify_cloud(qn_kf_store* s, uint32_t pair, int which, const float** d_xyz, uint32_t* n) {
+static int verify_cloud(qn_kf_store* s, uint32_t pair, int which, const float** d_xyz, uint32_t* n, bool sync);
+extern "C" int qn_kf_verify_cloud(qn_kf_store* s, uint32_t pair, int which, const float** d_xyz, uint32_t* n) { return verify_cloud(s, pair, which, d_xyz, n, true); }
+int qn_kf_int_verify_final_async(qn_kf_store* s, uint32_t pair, const float4** d_xyz, uint32_t* n) { return verify_cloud(s, pair, QN_VERIFY_FINAL, (const float**)d_xyz, n, false); }
+uint32_t qn_kf_int_verify_pairs(const qn_kf_store* s) {
+  const VerifyState* st = (const VerifyState*)qn_kf_int_ext(s, QN_KF_INT_EXT_VERIFY);
+  return st && st->live ? (uint32_t)st->p.size() : 0u;
+}
+// sync = false (qn_kf_int_verify_final_async): the launch is left on the store's stream
+static int verify_cloud(qn_kf_store* s, uint32_t pair, int which, const float** d_xyz, uint32_t* n, bool sync) {
   if (!s || !d_xyz || !n || which < QN_VERIFY_SRC || which > QN_VERIFY_FINAL) return QN_ERR_INVALID_ARG;
   *d_xyz = nullptr; *n = 0;
   VerifyState* st = (VerifyState*)qn_kf_int_ext(s, QN_KF_INT_EXT_VERIFY);
@@ -286,7 +294,7 @@ extern "C" int qn_kf_verify_cloud(qn_kf_store* s, uint32_t pair, int which, cons
   m.coarse = st->c2f() ? 1 : 0; m.fine = which == QN_VERIFY_FINAL ? 1 : 0;
   for (int i = 0; i < 12; i++) { m.Tq[i] = q.Tq[i]; m.Tg[i] = q.Tg[i]; }
   hipLaunchKernelGGL(k_verify_cloud, dim3((q.ns + 255) / 256), dim3(256), 0, stream, q.src, q.ns, m, out);
-  if (hipGetLastError() != hipSuccess || hipStreamSynchronize(stream) != hipSuccess) { qn_kf_int_set_error(s, "qn_kf_verify_cloud: the transform failed"); return QN_ERR_HIP; }
+  if (hipGetLastError() != hipSuccess || (sync && hipStreamSynchronize(stream) != hipSuccess)) { qn_kf_int_set_error(s, "qn_kf_verify_cloud: the transform failed"); return QN_ERR_HIP; }
   *d_xyz = (const float*)out; *n = q.ns;
   return QN_OK;
 }

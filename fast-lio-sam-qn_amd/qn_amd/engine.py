@@ -649,6 +649,16 @@ class ScParams(C.Structure):
         super().__init__(n_rings, n_sectors, max_radius, lidar_height, ringkey_prefilter, 0)
 
 
+class OverlapDir(C.Structure):
+    """qn_overlap_dir (24 bytes): one direction of a pair's overlap record"""
+    _fields_ = [("n", C.c_uint32), ("n_finite", C.c_uint32), ("inliers", C.c_uint32), ("reserved", C.c_uint32), ("sum_d2", C.c_double)]
+
+
+class Overlap(C.Structure):
+    """qn_overlap (48 bytes)"""
+    _fields_ = [("a_to_b", OverlapDir), ("b_to_a", OverlapDir)]
+
+
 class KeyframeStore:
     """Device-resident keyframe clouds + LoopClosure::setSrcAndDstCloud on the GPU (loop_closure.cpp:58-108)."""
 
@@ -997,6 +1007,53 @@ class KeyframeStore:
             if l.hipMemcpy(out.ctypes.data, ptr, 16 * n.value, 2) != 0:
                 raise EngineError(QN_ERR_HIP, "verify_cloud: read-back failed")
         return np.ascontiguousarray(out[:, :3])
+
+    # ---- the two-way overlap of cloud pairs (qn_kf_overlap_batch / qn_kf_verify_overlap / qn_kf_overlap_points; numpy twin: qn_amd/overlap.py)
+    @staticmethod
+    def _overlap_records(out, status, n):
+        def one(d):
+            return dict(n=int(d.n), n_finite=int(d.n_finite), inliers=int(d.inliers), sum_d2=float(d.sum_d2))
+        return [dict(a_to_b=one(out[j].a_to_b), b_to_a=one(out[j].b_to_a), status=int(status[j])) for j in range(n)]
+
+    def overlap_batch(self, pairs, radius):
+        """qn_kf_overlap_batch: pairs = [(ptr_a, n_a, ptr_b, n_b), ...], device pointers (int addresses) of float4 records in one frame -> one dict per pair:
+        a_to_b / b_to_a (each n, n_finite, inliers, sum_d2, as overlap.direction's) and status (QN_ERR_EMPTY_CLOUD for a pair with an empty side: a zero
+        record).  overlap.overlap_fraction / overlap.inlier_rmse take a direction dict."""
+        pairs = list(pairs); n = len(pairs)
+        if any(len(p) != 4 for p in pairs):
+            raise ValueError("overlap_batch: a pair is (ptr_a, n_a, ptr_b, n_b)")
+        pa = (C.c_void_p * max(n, 1))(*[p[0] for p in pairs]); pb = (C.c_void_p * max(n, 1))(*[p[2] for p in pairs])
+        na = np.array([p[1] for p in pairs] or [0], np.uint32); nb = np.array([p[3] for p in pairs] or [0], np.uint32)
+        out = (Overlap * max(n, 1))(); status = np.zeros(max(n, 1), np.int32)
+        self._check(self._l.qn_kf_overlap_batch(self.h, pa, _p(na), pb, _p(nb), C.c_uint32(n), C.c_double(radius), out, _p(status)))
+        self._overlap_n = [(int(p[1]), int(p[3])) if status[j] == QN_OK else (0, 0) for j, p in enumerate(pairs)]
+        return self._overlap_records(out, status, n)
+
+    def verify_overlap(self, radius, pairs=None, n_pairs=None):
+        """qn_kf_verify_overlap: pair j of the latest verify_loop_pairs[_c2f] / _submap[_c2f] call, A = its QN_VERIFY_FINAL cloud against B = its QN_VERIFY_DST
+        cloud.  pairs None: all n_pairs pairs of that call (n_pairs = how many it had).  -> one dict per listed pair, as overlap_batch's (status QN_ERR_NOT_READY
+        for a pair whose registration did not run)."""
+        if pairs is None:
+            if n_pairs is None:
+                raise ValueError("verify_overlap: give the pair indices, or n_pairs of the verify call for all of them")
+            idx = None; n = int(n_pairs)
+        else:
+            idx = np.ascontiguousarray(np.atleast_1d(pairs), dtype=np.uint32); n = len(idx)
+        out = (Overlap * max(n, 1))(); status = np.zeros(max(n, 1), np.int32)
+        self._check(self._l.qn_kf_verify_overlap(self.h, _p(idx) if idx is not None and n else None, C.c_uint32(n), C.c_double(radius), out, _p(status)))
+        self._overlap_n = [(int(out[j].a_to_b.n), int(out[j].b_to_a.n)) for j in range(n)]
+        return self._overlap_records(out, status, n)
+
+    def overlap_points(self, pair_slot, direction):
+        """qn_kf_overlap_points: the per-point results of the latest overlap_batch / verify_overlap for its pair `pair_slot`, direction 0 (A against B) or
+        1 (B against A) -> nn_d2 (n,) float32 (+inf: no partner within the radius), nn_idx (n,) int32 (-1)"""
+        sizes = getattr(self, "_overlap_n", None)
+        if sizes is None or not 0 <= int(pair_slot) < len(sizes) or direction not in (0, 1):
+            raise ValueError("overlap_points: no such pair or direction in the latest overlap call")
+        n = sizes[int(pair_slot)][direction]
+        d2 = np.zeros(max(n, 1), np.float32); idx = np.zeros(max(n, 1), np.int32)
+        self._check(self._l.qn_kf_overlap_points(self.h, C.c_uint32(pair_slot), C.c_int(direction), _p(d2), _p(idx)))
+        return d2[:n].copy(), idx[:n].copy()
 
     # ---- Scan Context loop candidates (qn_kf_sc_*; numpy twin: qn_amd/scancontext.py)
     def sc_set_params(self, params=None, **kw):

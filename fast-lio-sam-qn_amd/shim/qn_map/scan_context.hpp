@@ -269,4 +269,21 @@ inline std::vector<ScVerifiedPair> verifyLoopPairsSubmapCoarseToFine(qn_kf_store
   return out;
 }
 
+// the two-way overlap of every pair of the latest verifyLoopPairs* call on `store` (qn_kf_verify_overlap): the pair's aligned source against its target, each
+// way, within `radius`.  n_pairs = the size of that call's result.  A loop whose overlaps are small either way is a false positive whatever its score says;
+// the inlier RMSE is a natural scale for the loop factor's noise.  status: QN_ERR_NOT_READY for a pair whose registration did not run (a zero record).
+struct VerifiedOverlap { qn_overlap rec; int status; };
+inline double overlapFraction(const qn_overlap_dir& d) { return d.n_finite ? (double)d.inliers / (double)d.n_finite : 0.0; }
+inline double inlierRmse(const qn_overlap_dir& d) { return d.inliers ? std::sqrt(d.sum_d2 / (double)d.inliers) : 0.0; }
+inline std::vector<VerifiedOverlap> verifyOverlap(qn_kf_store* store, size_t n_pairs, double radius) {
+  std::vector<VerifiedOverlap> out;
+  if (n_pairs == 0) return out;
+  std::vector<qn_overlap> rec(n_pairs);
+  std::vector<int> status(n_pairs);
+  const int rc = qn_kf_verify_overlap(store, nullptr, (uint32_t)n_pairs, radius, rec.data(), status.data());
+  if (rc != QN_OK) throw std::runtime_error(std::string("[qn_map] qn_kf_verify_overlap: ") + qn_status_str(rc) + " " + qn_kf_last_error(store));
+  for (size_t k = 0; k < n_pairs; k++) out.push_back(VerifiedOverlap{rec[k], status[k]});
+  return out;
+}
+
 }  // namespace qn_map

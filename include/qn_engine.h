@@ -457,6 +457,37 @@ int  qn_kf_verify_loop_pairs_submap(qn_kf_store*, qn_ctx*, const int32_t* query,
 int  qn_kf_verify_loop_pairs_submap_c2f(qn_kf_store*, qn_ctx*, const int32_t* query, const int32_t* cand, uint32_t n_pairs, double score_thr,
                                         qn_gicp_result* results, double* T_total /* n_pairs x 16 */, double* T_quatro /* n_pairs x 16 or NULL */,
                                         int* valid, int* status);
+/* ---- the two-way overlap of cloud pairs (csrc/qn_overlap.hip; numpy twin and specification: qn_amd/overlap.py) ----------------------------------------
+ * The acceptance rule of every verify call above is the reference's: converged && score < thr, score = the mean squared 1-NN distance of ALL aligned source
+ * points, one way.  These calls measure what that number cannot say: how much of each cloud found a partner in the other, and how well those partners fit.
+ * For clouds A and B in one frame and a radius r (r2 = float(r * r), the product in f64): d2(a, b) = the f32 squared distance (f32 differences, dx dx + dy dy
+ * + dz dz summed left to right, no fused multiply-add).  Per point a of A: nn_d2 = min over the finite b of d2(a, b) if that is <= r2, else +inf; nn_idx =
+ * the lowest index b that attains it, else -1.  A non-finite point has +inf / -1 and is nobody's neighbour.  The search is exact (a sorted-key cell index,
+ * cell edge >= r; never a dense table, so the clouds' extent costs nothing), the results equal the twin's bit for bit, sum_d2 up to the order of an f64 sum;
+ * that order is fixed: a rerun gives the same bits and a pair's record does not depend on which other pairs share the call.
+ * qn_overlap_dir (24 bytes) one direction: n points, n_finite finite ones, inliers = points with a partner, sum_d2 = the f64 sum of their nn_d2.
+ * qn_overlap (48 bytes): a_to_b (every point of A against B) and b_to_a.  The derived figures are the caller's: overlap = inliers / n_finite, inlier RMSE =
+ * sqrt(sum_d2 / inliers), each 0 when its denominator is (qn_amd.overlap.overlap_fraction / inlier_rmse, qn_map::overlapFraction / inlierRmse).
+ * qn_kf_overlap_batch: pair j = device clouds d_a[j] (n_a[j] records) and d_b[j], float4 records (stride 16, 16-byte aligned; .w ignored), each inside one
+ *   allocation of the store's device (checked), complete when the call is made.  All pairs run in ONE pass on the store's stream, the pair a grid dimension;
+ *   two host synchronisations per call whatever n_pairs is.  A pair with an empty side: status[j] = QN_ERR_EMPTY_CLOUD and an all-zero record, the others
+ *   still run.  The store's assemble, map and batch slots, its entries and its verify record are not touched (the voxel pipeline's scratch is used).
+ * qn_kf_verify_overlap: pair pairs[j] (pairs NULL: pair j, and n_pairs must be that call's n_pairs) of the store's latest qn_kf_verify_loop_pairs[_c2f] /
+ *   _submap[_c2f] call with A = its QN_VERIFY_FINAL cloud and B = its QN_VERIFY_DST cloud, as qn_kf_verify_cloud serves them (FINAL is produced on demand in
+ *   that call's buffer, without its per-pair synchronisation): the records equal qn_kf_overlap_batch on those two clouds.  The call returns QN_ERR_NOT_READY
+ *   when qn_kf_verify_cloud would for every pair (no verify call yet, or its clouds are gone); status[j] = QN_ERR_NOT_READY with a zero record for a pair whose
+ *   registration did not run, the others still run.  The verify record and its lifetime rules are unchanged.
+ * qn_kf_overlap_points: the per-point results of the store's latest overlap call (either form) for its pair `pair_slot` (the position in that call's list),
+ *   dir 0 = A against B (n_a values), 1 = B against A; either output may be NULL, not both.  One synchronous copy.  They live in a buffer of their own until the
+ *   next overlap call.  QN_ERR_NOT_READY: no overlap call yet, or a pair that did not run.
+ * QN_ERR_INVALID_ARG before anything runs, store unchanged: a null pointer, n_pairs == 0, radius not finite or <= 0, a bad device pointer, a pair index out
+ * of range or repeated, a bad dir.  QN_ERR_CAPACITY: more than 32767 pairs, or 2^32 points in one call.                                                   */
+typedef struct qn_overlap_dir { uint32_t n, n_finite, inliers, reserved; double sum_d2; } qn_overlap_dir;      /* 24 bytes */
+typedef struct qn_overlap { qn_overlap_dir a_to_b, b_to_a; } qn_overlap;                                         /* 48 bytes */
+int  qn_kf_overlap_batch(qn_kf_store*, const float* const* d_a, const uint32_t* n_a, const float* const* d_b, const uint32_t* n_b, uint32_t n_pairs,
+                         double radius, qn_overlap* out, int* status);
+int  qn_kf_verify_overlap(qn_kf_store*, const uint32_t* pairs /* NULL: all */, uint32_t n_pairs, double radius, qn_overlap* out, int* status);
+int  qn_kf_overlap_points(qn_kf_store*, uint32_t pair_slot, int dir, float* nn_d2_out, int32_t* nn_idx_out);
 /* the corrected global map = the three loops of FastLioSamQn that rebuild it from every keyframe with its corrected pose
  * (fast_lio_sam_qn.cpp:302-316 visTimerFunc, :398-411 saveFlagCallback, :435-448 the destructor's result.pcd): transformPcd of each
  * listed keyframe, concatenation in `ids` order (ids may repeat), voxelizePcd at save_voxel_resolution (pcl::VoxelGrid,

@@ -218,7 +218,29 @@ def _oracle_relative(orc, scans, poses, k, c, yaw, submap_range, voxel, max_corr
     g = orc.GicpOracle(k=15, max_iter=32, max_corr_dist=max_corr_dist, trans_eps=0.01)
     g.set_source(src); g.compute_covariances(0); g.set_target(dst); g.compute_covariances(1)
     r = g.align(scancontext.seed_from_yaw(yaw).astype(np.float64))
-    return dict(valid=bool(r["converged"] and r["fitness"] < score_thr), converged=r["converged"], score=r["fitness"], T=r["Tf"].astype(np.float64))
+    return dict(valid=bool(r["converged"] and r["fitness"] < score_thr), converged=r["converged"], score=r["fitness"], T=r["Tf"].astype(np.float64), _src=src, _dst=dst)
+
+
+def _oracle_scan_c2f(orc, scans, q, c, voxel, max_corr_dist, score_thr):
+    """verify_loop_pairs_c2f for one pair on the CPU oracle: scan to scan, each in its own sensor frame"""
+    src, dst = orc.voxel_grid(scans[q], voxel), orc.voxel_grid(scans[c], voxel)
+    r = dict(orc.coarse_to_fine_alignment(src, dst, max_corr_dist=max_corr_dist, score_thr=score_thr))
+    r["_src"] = src; r["_dst"] = dst
+    return r
+
+
+def _overlap_figures(rec):
+    from qn_amd import overlap
+    return dict(overlap_ab=overlap.overlap_fraction(rec["a_to_b"]), overlap_ba=overlap.overlap_fraction(rec["b_to_a"]),
+                rmse_ab=overlap.inlier_rmse(rec["a_to_b"]), rmse_ba=overlap.inlier_rmse(rec["b_to_a"]))
+
+
+def _oracle_overlap(r, radius):
+    """the twin on the oracle's own clouds: the source through the pair's T (f64, rounded to f32) against the target"""
+    from qn_amd import overlap
+    src = np.asarray(r["_src"], np.float64)[:, :3]; T = np.asarray(r["T"], np.float64)
+    final = (src @ T[:3, :3].T + T[:3, 3]).astype(np.float32)
+    return _overlap_figures(overlap.overlap(final, np.asarray(r["_dst"], np.float32)[:, :3], radius))
 
 
 def _oracle_submap_relative(orc, scans, poses, q, c, yaw, submap_range, voxel, max_corr_dist, score_thr, use_quatro):
@@ -229,16 +251,18 @@ def _oracle_submap_relative(orc, scans, poses, q, c, yaw, submap_range, voxel, m
         return orc.assemble_submap(scans, {i: scancontext.relative_pose(poses[x], poses[i]) for i in sub}, sub, voxel)
     src, dst = local(q), local(c)
     if use_quatro:
-        return orc.coarse_to_fine_alignment(src, dst, max_corr_dist=max_corr_dist, score_thr=score_thr)
+        r = dict(orc.coarse_to_fine_alignment(src, dst, max_corr_dist=max_corr_dist, score_thr=score_thr))
+        r["_src"] = src; r["_dst"] = dst
+        return r
     g = orc.GicpOracle(k=15, max_iter=32, max_corr_dist=max_corr_dist, trans_eps=0.01)
     g.set_source(src); g.compute_covariances(0); g.set_target(dst); g.compute_covariances(1)
     r = g.align(scancontext.seed_from_yaw(yaw).astype(np.float64))
-    return dict(valid=bool(r["converged"] and r["fitness"] < score_thr), converged=r["converged"], score=r["fitness"], T=r["Tf"].astype(np.float64))
+    return dict(valid=bool(r["converged"] and r["fitness"] < score_thr), converged=r["converged"], score=r["fitness"], T=r["Tf"].astype(np.float64), _src=src, _dst=dst)
 
 
 def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, submap_range=5, score_thr=1.5, verbose=True, backend="gpu", save_dir=None,
         save_map_leaf=None, sensor="uniform", detector="radius", sc_max_dist=0.3, yaw_bias=0.006, verify="reference", sc_top_k=1, loop_every=1, catch_up=False,
-        submap_matching=False):
+        submap_matching=False, min_overlap=None, overlap_radius=None):
     """sensor = "uniform": keyframe clouds sampled uniformly by area inside a disc (make_stream); "spinning": ray-cast spinning-LiDAR
     scans from the ground-truth poses of the same figure-8 (make_lidar_stream).  detector = "radius": the candidate is the closest older
     keyframe within `radius` of the corrected position (LC:34-56); "scancontext": the older keyframe nearest by Scan Context distance, kept
@@ -262,7 +286,11 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
     submap_range of the query / the candidate, each submap in its centre's own sensor frame and placed with the RAW ODOMETRY poses, so no pose-graph update
     ever invalidates one.  At a tick the keyframes involved are described (KeyframeStore.submap_describe, with FPFH rows when use_quatro) unless their entry
     is still current - a window is final once submap_range later keyframes exist - and the pairs go through ONE verify_loop_pairs_submap
-    (verify_loop_pairs_submap_c2f with use_quatro).  The oracle backend assembles the same windows (orc.assemble_submap, scancontext.relative_pose)."""
+    (verify_loop_pairs_submap_c2f with use_quatro).  The oracle backend assembles the same windows (orc.assemble_submap, scancontext.relative_pose).
+    min_overlap = F with overlap_radius = R (verify="relative"; default None: off, the run is what it is without them): after every verification the two-way
+    overlap of each pair is measured (KeyframeStore.verify_overlap on the pairs' resident clouds; the oracle backend runs the twin qn_amd.overlap on its own
+    clouds), printed per attempt, and a pair counts as valid only if the registration says so AND both directions' overlap are >= F.  A single query's
+    candidates then go through the many-pair verify calls (the same records), which keep what verify_overlap needs.  out["overlaps"]: one dict per pair."""
     if detector not in ("radius", "scancontext"):
         raise ValueError("detector must be 'radius' or 'scancontext', not %r" % (detector,))
     if verify not in ("reference", "relative"):
@@ -275,6 +303,30 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
         raise ValueError("loop_every > 1 / catch_up need verify='relative' and detector='scancontext'")
     if submap_matching and verify != "relative":
         raise ValueError("submap_matching needs verify='relative' (the reference's world-frame submap matching is verify='reference' without it)")
+    gate = min_overlap is not None
+    if gate and verify != "relative":
+        raise ValueError("min_overlap needs verify='relative' (the verify calls that keep their pairs' clouds)")
+    if gate and not (overlap_radius is not None and np.isfinite(overlap_radius) and overlap_radius > 0):
+        raise ValueError("min_overlap needs overlap_radius > 0, not %r" % (overlap_radius,))
+    overlaps = []
+
+    def apply_gate(rs, pairs):
+        """measure every pair of the verification that just ran, print, and clear `valid` where either overlap is below min_overlap"""
+        if not gate:
+            return rs
+        if backend == "gpu":
+            figs = [dict(_overlap_figures(o), status=o["status"]) for o in store.verify_overlap(overlap_radius, n_pairs=len(rs))]
+        else:
+            figs = [dict(_oracle_overlap(r, overlap_radius), status=0) for r in rs]
+        for r, f, (q, c) in zip(rs, figs, pairs):
+            keep = bool(r["valid"]) and f["status"] == 0 and f["overlap_ab"] >= min_overlap and f["overlap_ba"] >= min_overlap
+            f.update(query=q, cand=c, valid=bool(r["valid"]), accepted=keep, score=r["score"])
+            overlaps.append(f)
+            if verbose:
+                print("overlap (%d, %d): src->dst %.3f (rmse %.3f m), dst->src %.3f (rmse %.3f m); registration %s, loop %s"
+                      % (q, c, f["overlap_ab"], f["rmse_ab"], f["overlap_ba"], f["rmse_ba"], "valid" if r["valid"] else "invalid", "kept" if keep else "dropped"))
+            r["valid"] = keep
+        return rs
     if sensor == "uniform":
         scans, gt, odom, stamps = make_stream(n_kf, seed, yaw_bias=yaw_bias)
     elif sensor == "spinning":
@@ -353,13 +405,13 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
             elif use_quatro and backend == "gpu":
                 rs = store.verify_loop_pairs_c2f(ctx, [ids[q] for q in pq], [ids[x] for x in pc], score_thr)
             elif use_quatro:
-                rs = [orc.coarse_to_fine_alignment(orc.voxel_grid(scans[q], voxel), orc.voxel_grid(scans[x], voxel), max_corr_dist=1.5 * radius, score_thr=score_thr)
-                      for q, x in zip(pq, pc)]
+                rs = [_oracle_scan_c2f(orc, scans, q, x, voxel, 1.5 * radius, score_thr) for q, x in zip(pq, pc)]
             elif backend == "gpu":
                 rs = store.verify_loop_pairs(ctx, [ids[q] for q in pq], [ids[x] for x in pc], py, corrected[:k + 1], submap_range, voxel, score_thr)
             else:
                 rs = [_oracle_relative(orc, scans, corrected[:k + 1], q, x, y, submap_range, voxel, 1.5 * radius, score_thr) for q, x, y in zip(pq, pc, py)]
             t_reg.append(time.perf_counter() - t0)
+            rs = apply_gate(rs, list(zip(pq, pc)))
             added = False
             for q in queries:
                 ok = [(rs[j]["score"], j) for j in range(len(pq)) if pq[j] == q and rs[j]["valid"]]
@@ -400,15 +452,17 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
             elif submap_matching:
                 rs = [_oracle_submap_relative(orc, scans, odom[:k + 1], k, x, y, submap_range, voxel, 1.5 * radius, score_thr, use_quatro) for x, y in zip(cand, yaws)]
             elif use_quatro and backend == "gpu":
-                rs = store.verify_loop_candidates_c2f(ctx, ids[k], [ids[x] for x in cand], score_thr)
+                rs = (store.verify_loop_pairs_c2f(ctx, [ids[k]] * len(cand), [ids[x] for x in cand], score_thr) if gate else
+                      store.verify_loop_candidates_c2f(ctx, ids[k], [ids[x] for x in cand], score_thr))
             elif use_quatro:
-                rs = [orc.coarse_to_fine_alignment(orc.voxel_grid(scans[k], voxel), orc.voxel_grid(scans[x], voxel), max_corr_dist=1.5 * radius, score_thr=score_thr)
-                      for x in cand]
+                rs = [_oracle_scan_c2f(orc, scans, k, x, voxel, 1.5 * radius, score_thr) for x in cand]
             elif backend == "gpu":
-                rs = store.verify_loop_candidates(ctx, ids[k], [ids[x] for x in cand], yaws, corrected[:k + 1], submap_range, voxel, score_thr)
+                rs = (store.verify_loop_pairs(ctx, [ids[k]] * len(cand), [ids[x] for x in cand], yaws, corrected[:k + 1], submap_range, voxel, score_thr) if gate else
+                      store.verify_loop_candidates(ctx, ids[k], [ids[x] for x in cand], yaws, corrected[:k + 1], submap_range, voxel, score_thr))
             else:
                 rs = [_oracle_relative(orc, scans, corrected[:k + 1], k, x, y, submap_range, voxel, 1.5 * radius, score_thr) for x, y in zip(cand, yaws)]
             t_reg.append(time.perf_counter() - t0)
+            rs = apply_gate(rs, [(k, x) for x in cand])
             ok = [(r["score"], j) for j, r in enumerate(rs) if r["valid"]]
             if not ok:
                 continue
@@ -455,13 +509,15 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
     out = dict(sensor=sensor, detector=detector, n_keyframes=n_kf, loops=len(loops), attempts=len(t_reg), ate_odometry=ate(odom, gt), ate_corrected=ate(corrected, gt),
                ms_per_attempt=1e3 * float(np.mean(t_reg)) if t_reg else None, quatro=use_quatro, verify=verify, loop_list=loops, poses=corrected,
                loop_T=loop_T, gt=gt, loop_every=loop_every, catch_up=catch_up, submap_matching=submap_matching)
+    if gate:
+        out["overlaps"] = overlaps
     if save_dir:
         write_kitti_tum(save_dir, corrected, stamps)
         if save_map_leaf is not None and backend == "gpu":
             n = store.build_map(ids, corrected, save_map_leaf)
             write_pcd_xyzi(os.path.join(save_dir, "map.pcd"), store.download_map(n))
     if verbose:
-        print({k: v for k, v in out.items() if k not in ("poses", "loop_list", "loop_T", "gt")})
+        print({k: v for k, v in out.items() if k not in ("poses", "loop_list", "loop_T", "gt", "overlaps")})
     if backend == "gpu":
         ctx.close(); store.close()
     return out
@@ -485,7 +541,11 @@ if __name__ == "__main__":
     ap.add_argument("--catch-up", action="store_true", help="with --loop-every: a tick checks every keyframe added since the last one, in one batched verification")
     ap.add_argument("--submap-matching", action="store_true",
                     help="with --verify relative: submap against submap from resident local submaps (the reference's enable_submap_matching, drift-free); with --quatro coarse to fine")
+    ap.add_argument("--min-overlap", type=float, default=None,
+                    help="with --verify relative and --overlap-radius: add a loop only if it is valid and both directions' overlap (aligned source <-> target) reach this fraction")
+    ap.add_argument("--overlap-radius", type=float, default=None, help="with --min-overlap: the radius [m] within which a point counts as having a partner")
     ap.add_argument("--backend", choices=["gpu", "oracle"], default="gpu", help="the engine on the GPU, or the CPU oracle")
     a = ap.parse_args()
     run(a.keyframes, a.seed, a.quatro, save_dir=a.save_dir, save_map_leaf=a.save_map_leaf, sensor=a.sensor, detector=a.detector, yaw_bias=a.yaw_bias,
-        verify=a.verify, sc_top_k=a.sc_top_k, backend=a.backend, loop_every=a.loop_every, catch_up=a.catch_up, submap_matching=a.submap_matching)
+        verify=a.verify, sc_top_k=a.sc_top_k, backend=a.backend, loop_every=a.loop_every, catch_up=a.catch_up, submap_matching=a.submap_matching,
+        min_overlap=a.min_overlap, overlap_radius=a.overlap_radius)
