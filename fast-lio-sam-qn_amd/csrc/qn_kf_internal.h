@@ -25,12 +25,13 @@ const float4* qn_kf_int_keyframe(const qn_kf_store* s, int32_t id, uint32_t* n);
 // per-store state of another translation unit (slot QN_KF_INT_EXT_SC: qn_sc.hip's descriptors, QN_KF_INT_EXT_QUATRO: the resident Quatro features of
 // qn_kf_quatro.inc, QN_KF_INT_EXT_VERIFY: qn_verify.hip's record of the latest multi-pair verification, QN_KF_INT_EXT_SUBMAP: the resident local submaps of
 // qn_kf_submap.inc): nullptr until set; the store owns it from qn_kf_int_set_ext on and calls `release` from qn_kf_store_destroy once its stream has drained.
-#define QN_KF_INT_EXT 5
+#define QN_KF_INT_EXT 6
 #define QN_KF_INT_EXT_SC 0
 #define QN_KF_INT_EXT_QUATRO 1
 #define QN_KF_INT_EXT_VERIFY 2
 #define QN_KF_INT_EXT_SUBMAP 3
 #define QN_KF_INT_EXT_OVERLAP 4                                                  // qn_overlap.hip: the per-point results of the latest overlap call
+#define QN_KF_INT_EXT_RANGE 5                                                    // qn_freespace.hip: range images and the classes of the latest check
 typedef void (*qn_kf_int_release_fn)(void*);
 void* qn_kf_int_ext(const qn_kf_store* s, int which);
 void qn_kf_int_set_ext(qn_kf_store* s, int which, void* p, qn_kf_int_release_fn release);

@@ -659,6 +659,42 @@ class Overlap(C.Structure):
     _fields_ = [("a_to_b", OverlapDir), ("b_to_a", OverlapDir)]
 
 
+class RangeParams(C.Structure):
+    """qn_range_params (56 bytes): the range-image shape, field of view, blind radius, and the free-space check's window and tolerances"""
+    _fields_ = [("n_rows", C.c_uint32), ("n_cols", C.c_uint32), ("el_lo", C.c_double), ("el_hi", C.c_double), ("min_range", C.c_double),
+                ("window_rows", C.c_uint32), ("window_cols", C.c_uint32), ("tol_abs", C.c_double), ("tol_rel", C.c_double)]
+
+    def __init__(self, n_rows=64, n_cols=1800, el_lo=-0.4363323129985824, el_hi=0.038397243543875255, min_range=2.0, window_rows=1, window_cols=1,
+                 tol_abs=0.3, tol_rel=0.02):
+        super().__init__(n_rows, n_cols, el_lo, el_hi, min_range, window_rows, window_cols, tol_abs, tol_rel)
+
+    @classmethod
+    def for_sensor(cls, sensor, **kw):
+        """The image of a synth.SpinningLidar: a row per beam, a column per azimuth step, the edges half a beam spacing outside el_min / el_max
+        (freespace.Params.for_sensor)"""
+        from . import freespace
+        return cls.from_twin(freespace.Params.for_sensor(sensor, **kw))
+
+    @classmethod
+    def from_twin(cls, p):
+        return cls(*[getattr(p, f) for f, _ in cls._fields_])
+
+    def twin(self):
+        """-> the freespace.Params with these values"""
+        from . import freespace
+        return freespace.Params(**{f: getattr(self, f) for f, _ in self._fields_})
+
+
+class FreespaceDir(C.Structure):
+    """qn_freespace_dir (32 bytes): one direction of a pair's free-space record"""
+    _fields_ = [(f, C.c_uint32) for f in ("n", "n_finite", "in_fov", "observed", "seen_through", "occluded", "agree", "reserved")]
+
+
+class Freespace(C.Structure):
+    """qn_freespace (64 bytes)"""
+    _fields_ = [("q_in_c", FreespaceDir), ("c_in_q", FreespaceDir)]
+
+
 class KeyframeStore:
     """Device-resident keyframe clouds + LoopClosure::setSrcAndDstCloud on the GPU (loop_closure.cpp:58-108)."""
 
@@ -1054,6 +1090,59 @@ class KeyframeStore:
         d2 = np.zeros(max(n, 1), np.float32); idx = np.zeros(max(n, 1), np.int32)
         self._check(self._l.qn_kf_overlap_points(self.h, C.c_uint32(pair_slot), C.c_int(direction), _p(d2), _p(idx)))
         return d2[:n].copy(), idx[:n].copy()
+
+    # ---- range images and the free-space check of loop pairs (qn_kf_range_* / qn_kf_freespace_*; numpy twin: qn_amd/freespace.py)
+    def range_set_params(self, params=None, **kw):
+        """qn_kf_range_set_params: a RangeParams (or a freespace.Params), or its fields as keywords (the rest default).  A change of the shape, the angles or
+        min_range discards every image."""
+        p = RangeParams(**kw) if params is None else params
+        if not isinstance(p, RangeParams):
+            p = RangeParams.from_twin(p)
+        self._check(self._l.qn_kf_range_set_params(self.h, C.byref(p)))
+
+    def range_params(self):
+        p = RangeParams()
+        self._check(self._l.qn_kf_range_get_params(self.h, C.byref(p)))
+        return p
+
+    def range_describe(self, ids):
+        """qn_kf_range_describe: the near / far range images of these keyframes, on the GPU from their resident records (describing again replaces)
+        -> per id its status (QN_ERR_EMPTY_CLOUD: no kept point, an all-empty image)"""
+        ids = np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+        status = np.zeros(max(len(ids), 1), np.int32)
+        self._check(self._l.qn_kf_range_describe(self.h, _p(ids) if len(ids) else None, C.c_uint32(len(ids)), _p(status)))
+        return [int(v) for v in status[:len(ids)]]
+
+    def range_images(self, kid):
+        """-> (near, far), each (n_rows, n_cols) float32, of a described keyframe (qn_kf_range_get)"""
+        p = self.range_params()
+        near = np.zeros((p.n_rows, p.n_cols), np.float32); far = np.zeros((p.n_rows, p.n_cols), np.float32)
+        self._check(self._l.qn_kf_range_get(self.h, C.c_int32(kid), _p(near), _p(far)))
+        return near, far
+
+    def freespace_batch(self, query, cand, T):
+        """qn_kf_freespace_batch: pair j = (query[j], cand[j], T[j]), T[j] the 4x4 f64 that maps the query's sensor frame into the candidate's (what the
+        verify calls estimate) -> one dict per pair: q_in_c / c_in_q (each n, n_finite, in_fov, observed, seen_through, occluded, agree, as
+        freespace.direction's) and status.  freespace.see_through_fraction takes a direction dict."""
+        q, c, n = self._pairs(query, cand)
+        T = np.ascontiguousarray(np.asarray(T, dtype=np.float64).reshape(-1, 16))
+        if len(T) != n:
+            raise ValueError("freespace_batch: %d pairs but %d transforms" % (n, len(T)))
+        out = (Freespace * max(n, 1))(); status = np.zeros(max(n, 1), np.int32)
+        self._check(self._l.qn_kf_freespace_batch(self.h, _p(q) if n else None, _p(c) if n else None, _p(T) if n else None, C.c_uint32(n), out, _p(status)))
+        self._freespace_n = [(int(out[j].q_in_c.n), int(out[j].c_in_q.n)) for j in range(n)]
+        d = lambda r: {f: int(getattr(r, f)) for f, _ in FreespaceDir._fields_ if f != "reserved"}
+        return [dict(q_in_c=d(out[j].q_in_c), c_in_q=d(out[j].c_in_q), status=int(status[j])) for j in range(n)]
+
+    def freespace_points(self, pair_slot, direction):
+        """qn_kf_freespace_points: the class byte of every record (freespace.DROPPED .. AGREE) of the latest freespace_batch for its pair `pair_slot`,
+        direction 0 (the query's records in the candidate's images) or 1 -> (n,) uint8"""
+        sizes = getattr(self, "_freespace_n", None)
+        if sizes is None or not (0 <= pair_slot < len(sizes)) or direction not in (0, 1):
+            raise ValueError("freespace_points: no such pair or direction in the latest freespace call")
+        out = np.zeros(max(sizes[pair_slot][direction], 1), np.uint8)
+        self._check(self._l.qn_kf_freespace_points(self.h, C.c_uint32(pair_slot), C.c_int(direction), _p(out)))
+        return out[:sizes[pair_slot][direction]]
 
     # ---- Scan Context loop candidates (qn_kf_sc_*; numpy twin: qn_amd/scancontext.py)
     def sc_set_params(self, params=None, **kw):

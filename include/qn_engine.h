@@ -488,6 +488,58 @@ int  qn_kf_overlap_batch(qn_kf_store*, const float* const* d_a, const uint32_t* 
                          double radius, qn_overlap* out, int* status);
 int  qn_kf_verify_overlap(qn_kf_store*, const uint32_t* pairs /* NULL: all */, uint32_t n_pairs, double radius, qn_overlap* out, int* status);
 int  qn_kf_overlap_points(qn_kf_store*, uint32_t pair_slot, int dir, float* nn_d2_out, int32_t* nn_idx_out);
+/* ---- range images of keyframes and the free-space (see-through) check of loop pairs (csrc/qn_freespace.hip; numpy twin and specification: qn_amd/freespace.py)
+ * Score and overlap speak about the points that found a partner.  A point WITHOUT one is either merely out of the other scan's view (occluded, beyond range,
+ * outside the field of view: normal in every true revisit) or it contradicts the other scan: under the hypothesised transform it sits where that scan's rays
+ * passed on their way to a farther surface.  These calls count the second kind.  Everything happens in a keyframe's SENSOR frame (PosePcd::pcd_), from its raw
+ * resident records.  All arithmetic is f64 from the f32 records, no fused multiply-add, no transcendental on the device, the correctly rounded f64 sqrt; every
+ * result is an integer or a min / max of f32 values, so images, classes and counts equal the twin's bit for bit and a rerun, or the same pair inside another
+ * batch, gives the same record.
+ * qn_range_params: n_rows x n_cols pixels (caps: QN_RANGE_MAX_ROWS = 1024, QN_RANGE_MAX_COLS = 8192); el_lo / el_hi [rad] = the lower edge of row 0 and the
+ *   upper edge of the last row, -pi/2 < el_lo < el_hi < pi/2; min_range >= 0; window_rows, window_cols (default 1, 1); tol_abs, tol_rel (default 0.3, 0.02).
+ *   Host tables from the C library: t[i] = tan(el_lo + i (el_hi - el_lo) / n_rows), i = 0 .. n_rows; (c[j], s[j]) = (cos, sin)(2 pi j / n_cols).
+ * Projection of (x, y, z): rho2 = x x + y y, rho = sqrt(rho2), r = sqrt(rho2 + z z); row = #{edges i in 0 .. n_rows : z >= rho t[i]} - 1 (-1 or n_rows: outside
+ *   the field of view); column = #{j in 1 .. n_cols - 1 : azimuth >= azimuth of (c[j], s[j])} by Scan Context's half-plane and cross-product test.  Both
+ *   counts are defined by the twin's bisection (lo / hi, mid = (lo + hi) >> 1, predicate true -> lo = mid + 1), evaluated at the same indices on both sides.
+ *   A point is DROPPED when a coordinate is not finite, r < min_range, or it is outside the field of view.
+ * Images of a keyframe: near[row][col] = min, far[row][col] = max over its kept points of (float)r; an empty pixel holds +inf / 0.
+ * Check of (q, c, T), T = row-major 4x4 f64 mapping q's sensor frame into c's (results[j].T64 or T_total of the verify calls above): direction 0 (q_in_c) =
+ *   every record of q through T, ((T0 x + T1 y) + T2 z) + T3 in f64 and not rounded, against c's images; direction 1 (c_in_q) = every record of c through
+ *   inv(T) = [R^T | -R^T t] (the host arithmetic of qn_kf_verify_loop_candidates' relative poses) against q's images.  For a kept point with range r at
+ *   (row, col): R_near = min of near and R_far = max of far over the rows row +- window_rows that exist and the columns col +- window_cols, wrapping;
+ *   tol = tol_abs + tol_rel r.  One class byte per point: 0 dropped; 1 unobserved (the window holds no return); 2 SEEN THROUGH (r + tol < R_near); 3 occluded
+ *   (r > R_far + tol); 4 agree.  qn_freespace_dir (32 bytes): n records, n_finite, in_fov (the kept ones), observed (classes 2 + 3 + 4), seen_through,
+ *   occluded, agree, reserved.  qn_freespace (64 bytes): q_in_c, c_in_q.  The derived figure is the caller's: see-through fraction = seen_through / observed,
+ *   0 when observed is 0 (qn_amd.freespace.see_through_fraction, qn_map::seeThroughFraction).
+ * qn_kf_range_set_params / _get_params: per store (defaults: 64 x 1800, -25 .. 2.2 degrees, min_range 2).  A change of n_rows, n_cols, el_lo, el_hi or
+ *   min_range discards every image; the window and the tolerances may change freely.  QN_ERR_INVALID_ARG: a null pointer, a bad range of angles, a zero size
+ *   or one above the caps, a non-finite or negative min_range or tolerance, a window that covers a whole dimension (window_rows >= n_rows or
+ *   2 window_cols + 1 > n_cols).
+ * qn_kf_range_describe: the images of the listed keyframes in ONE pass on the store's stream, the keyframe a grid dimension; they stay resident in a
+ *   store-owned block indexed by keyframe id, 8 n_rows n_cols bytes per keyframe (0.92 MB at 64 x 1800).  Describing again replaces.  status[i] =
+ *   QN_ERR_EMPTY_CLOUD for a keyframe with no kept point (a valid all-empty image).  One host synchronisation.  QN_ERR_INVALID_ARG: a null pointer,
+ *   count == 0, a bad id.
+ * qn_kf_range_get: one synchronous copy of the images (either output may be NULL, not both).  QN_ERR_NOT_READY for a keyframe never described.
+ * qn_kf_freespace_batch: pair j = (query[j], cand[j], T16[16 j ..]); all pairs and both directions in ONE pass on the store's stream, (pair, direction) a grid
+ *   dimension, the counts reduced in a fixed order through per-block slots; one host synchronisation per call whatever n_pairs is.  Pairs may repeat.
+ *   status[j] = QN_ERR_EMPTY_CLOUD when one of the keyframes has no record at all (the record is still filled).  QN_ERR_INVALID_ARG before anything runs:
+ *   a null pointer, n_pairs == 0, a bad id, query[j] == cand[j], a non-finite T, a keyframe without images.  QN_ERR_CAPACITY: more than 32767 pairs, or 2^32
+ *   records in one call.  The store's slots, entries, images and verify record are not touched.
+ * qn_kf_freespace_points: the class bytes of the latest qn_kf_freespace_batch for its pair `pair_slot`, dir 0 = q's records (n of q_in_c), 1 = c's.  They live
+ *   in a buffer of their own until the next successful call.  QN_ERR_NOT_READY before any call; QN_ERR_INVALID_ARG: a null pointer, a bad slot or dir.
+ * A refused call (INVALID_ARG, NOT_READY, CAPACITY) leaves the images and the per-point classes as they were.                                              */
+#define QN_RANGE_MAX_ROWS 1024
+#define QN_RANGE_MAX_COLS 8192
+typedef struct qn_range_params { uint32_t n_rows, n_cols; double el_lo, el_hi, min_range; uint32_t window_rows, window_cols; double tol_abs, tol_rel; } qn_range_params;  /* 56 bytes */
+typedef struct qn_freespace_dir { uint32_t n, n_finite, in_fov, observed, seen_through, occluded, agree, reserved; } qn_freespace_dir;      /* 32 bytes */
+typedef struct qn_freespace { qn_freespace_dir q_in_c, c_in_q; } qn_freespace;                                                              /* 64 bytes */
+int  qn_kf_range_set_params(qn_kf_store*, const qn_range_params*);
+int  qn_kf_range_get_params(qn_kf_store*, qn_range_params*);
+int  qn_kf_range_describe(qn_kf_store*, const int32_t* ids, uint32_t count, int* status);
+int  qn_kf_range_get(qn_kf_store*, int32_t id, float* near_out /* n_rows x n_cols */, float* far_out);
+int  qn_kf_freespace_batch(qn_kf_store*, const int32_t* query, const int32_t* cand, const double* T16 /* n_pairs x 16 */, uint32_t n_pairs,
+                           qn_freespace* out, int* status);
+int  qn_kf_freespace_points(qn_kf_store*, uint32_t pair_slot, int dir, uint8_t* class_out /* one byte per record */);
 /* the corrected global map = the three loops of FastLioSamQn that rebuild it from every keyframe with its corrected pose
  * (fast_lio_sam_qn.cpp:302-316 visTimerFunc, :398-411 saveFlagCallback, :435-448 the destructor's result.pcd): transformPcd of each
  * listed keyframe, concatenation in `ids` order (ids may repeat), voxelizePcd at save_voxel_resolution (pcl::VoxelGrid,

@@ -262,7 +262,7 @@ def _oracle_submap_relative(orc, scans, poses, q, c, yaw, submap_range, voxel, m
 
 def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, submap_range=5, score_thr=1.5, verbose=True, backend="gpu", save_dir=None,
         save_map_leaf=None, sensor="uniform", detector="radius", sc_max_dist=0.3, yaw_bias=0.006, verify="reference", sc_top_k=1, loop_every=1, catch_up=False,
-        submap_matching=False, min_overlap=None, overlap_radius=None):
+        submap_matching=False, min_overlap=None, overlap_radius=None, max_see_through=None, range_params=None):
     """sensor = "uniform": keyframe clouds sampled uniformly by area inside a disc (make_stream); "spinning": ray-cast spinning-LiDAR
     scans from the ground-truth poses of the same figure-8 (make_lidar_stream).  detector = "radius": the candidate is the closest older
     keyframe within `radius` of the corrected position (LC:34-56); "scancontext": the older keyframe nearest by Scan Context distance, kept
@@ -290,7 +290,12 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
     min_overlap = F with overlap_radius = R (verify="relative"; default None: off, the run is what it is without them): after every verification the two-way
     overlap of each pair is measured (KeyframeStore.verify_overlap on the pairs' resident clouds; the oracle backend runs the twin qn_amd.overlap on its own
     clouds), printed per attempt, and a pair counts as valid only if the registration says so AND both directions' overlap are >= F.  A single query's
-    candidates then go through the many-pair verify calls (the same records), which keep what verify_overlap needs.  out["overlaps"]: one dict per pair."""
+    candidates then go through the many-pair verify calls (the same records), which keep what verify_overlap needs.  out["overlaps"]: one dict per pair.
+    max_see_through = F (verify="relative"; default None: off, the run is what it is without it): every keyframe's range images are made on arrival
+    (KeyframeStore.range_describe; range_params, a freespace.Params, defaults to the simulated sensor's image, or to a 32 x 360 image over +-60 degrees for
+    the uniform clouds), after every verification each pair's T goes through the free-space check (KeyframeStore.freespace_batch, one pass for all pairs; the
+    oracle backend runs the twin qn_amd.freespace on the raw scans), printed per attempt, and a pair counts as valid only if it was valid so far AND neither
+    direction's share of observed points that the other scan saw through exceeds F.  out["see_through"]: one dict per pair."""
     if detector not in ("radius", "scancontext"):
         raise ValueError("detector must be 'radius' or 'scancontext', not %r" % (detector,))
     if verify not in ("reference", "relative"):
@@ -308,7 +313,43 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
         raise ValueError("min_overlap needs verify='relative' (the verify calls that keep their pairs' clouds)")
     if gate and not (overlap_radius is not None and np.isfinite(overlap_radius) and overlap_radius > 0):
         raise ValueError("min_overlap needs overlap_radius > 0, not %r" % (overlap_radius,))
-    overlaps = []
+    fgate = max_see_through is not None
+    if fgate and verify != "relative":
+        raise ValueError("max_see_through needs verify='relative' (a transform between two sensor frames)")
+    if fgate and not (np.isfinite(max_see_through) and max_see_through >= 0):
+        raise ValueError("max_see_through must be a fraction >= 0, not %r" % (max_see_through,))
+    overlaps = []; see_through = []; fs_images = {}
+
+    def apply_freespace(rs, pairs):
+        """check every pair's T against the two keyframes' range images, print, and clear `valid` where either direction is seen through too much"""
+        if not fgate:
+            return rs
+        from qn_amd import freespace
+        live = [j for j, r in enumerate(rs) if np.all(np.isfinite(np.asarray(r["T"], np.float64)))]
+        recs = {}
+        if live and backend == "gpu":
+            out = store.freespace_batch([ids[pairs[j][0]] for j in live], [ids[pairs[j][1]] for j in live], [rs[j]["T"] for j in live])
+            recs = dict(zip(live, out))
+        elif live:
+            for j in live:
+                q, c = pairs[j]
+                for x in (q, c):
+                    if x not in fs_images:
+                        fs_images[x] = freespace.range_images(scans[x], fs_params)
+                recs[j] = freespace.freespace(scans[q], scans[c], rs[j]["T"], fs_params, q_images=fs_images[q], c_images=fs_images[c])
+        for j, (r, (q, c)) in enumerate(zip(rs, pairs)):
+            f = dict(query=q, cand=c, valid=bool(r["valid"]), score=r["score"], q_in_c=None, c_in_q=None, observed=(0, 0))
+            if j in recs:
+                a, b = recs[j]["q_in_c"], recs[j]["c_in_q"]
+                f.update(q_in_c=freespace.see_through_fraction(a), c_in_q=freespace.see_through_fraction(b), observed=(a["observed"], b["observed"]))
+            keep = bool(r["valid"]) and j in recs and f["q_in_c"] <= max_see_through and f["c_in_q"] <= max_see_through
+            f["accepted"] = keep
+            see_through.append(f)
+            if verbose and j in recs:
+                print("see-through (%d, %d): query in candidate %.4f of %d, candidate in query %.4f of %d; so far %s, loop %s"
+                      % (q, c, f["q_in_c"], f["observed"][0], f["c_in_q"], f["observed"][1], "valid" if r["valid"] else "invalid", "kept" if keep else "dropped"))
+            r["valid"] = keep
+        return rs
 
     def apply_gate(rs, pairs):
         """measure every pair of the verification that just ran, print, and clear `valid` where either overlap is below min_overlap"""
@@ -350,6 +391,12 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
         if scans is None:
             from qn_amd import synth
             scans = [synth.lidar_scan(prims, lidar, T, int(sd))[:, :3] for T, sd in zip(gt, seeds)]
+    if fgate:
+        from qn_amd import freespace
+        fs_params = range_params if range_params is not None else (freespace.Params.for_sensor(lidar) if sensor == "spinning" else
+                                                                   freespace.Params(n_rows=32, n_cols=360, el_lo=-np.pi / 3, el_hi=np.pi / 3, min_range=1.0))
+        if backend == "gpu":
+            store.range_set_params(fs_params)
     pg = PoseGraph(); ids = []; corrected = []; sc_descs = {}
     prior_var = np.array([1e-4, 1e-4, 1e-4, 1e-2, 1e-2, 1e-2]); odom_var = prior_var.copy()   # FQ:112-114, 132-133 (rot, then trans)
     loops = []; t_reg = []; loop_T = []; last_tick = -1
@@ -364,6 +411,8 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
     for k in range(n_kf):
         if backend == "gpu":
             ids.append(store.add(scans[k]) if scans is not None else cast_ids[k])
+            if fgate:                                                                        # the keyframe's range images, once, on arrival
+                store.range_describe([ids[k]])
         pose = odom[k] if k == 0 else corrected[-1] @ (inv(odom[k - 1]) @ odom[k])           # realtime pose = last corrected * delta odom (FQ:93-103)
         pg.add_pose(pose); corrected.append(pose)
         if k == 0:
@@ -411,7 +460,7 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
             else:
                 rs = [_oracle_relative(orc, scans, corrected[:k + 1], q, x, y, submap_range, voxel, 1.5 * radius, score_thr) for q, x, y in zip(pq, pc, py)]
             t_reg.append(time.perf_counter() - t0)
-            rs = apply_gate(rs, list(zip(pq, pc)))
+            rs = apply_freespace(apply_gate(rs, list(zip(pq, pc))), list(zip(pq, pc)))
             added = False
             for q in queries:
                 ok = [(rs[j]["score"], j) for j in range(len(pq)) if pq[j] == q and rs[j]["valid"]]
@@ -462,7 +511,7 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
             else:
                 rs = [_oracle_relative(orc, scans, corrected[:k + 1], k, x, y, submap_range, voxel, 1.5 * radius, score_thr) for x, y in zip(cand, yaws)]
             t_reg.append(time.perf_counter() - t0)
-            rs = apply_gate(rs, [(k, x) for x in cand])
+            rs = apply_freespace(apply_gate(rs, [(k, x) for x in cand]), [(k, x) for x in cand])
             ok = [(r["score"], j) for j, r in enumerate(rs) if r["valid"]]
             if not ok:
                 continue
@@ -511,13 +560,15 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
                loop_T=loop_T, gt=gt, loop_every=loop_every, catch_up=catch_up, submap_matching=submap_matching)
     if gate:
         out["overlaps"] = overlaps
+    if fgate:
+        out["see_through"] = see_through
     if save_dir:
         write_kitti_tum(save_dir, corrected, stamps)
         if save_map_leaf is not None and backend == "gpu":
             n = store.build_map(ids, corrected, save_map_leaf)
             write_pcd_xyzi(os.path.join(save_dir, "map.pcd"), store.download_map(n))
     if verbose:
-        print({k: v for k, v in out.items() if k not in ("poses", "loop_list", "loop_T", "gt", "overlaps")})
+        print({k: v for k, v in out.items() if k not in ("poses", "loop_list", "loop_T", "gt", "overlaps", "see_through")})
     if backend == "gpu":
         ctx.close(); store.close()
     return out
@@ -544,8 +595,10 @@ if __name__ == "__main__":
     ap.add_argument("--min-overlap", type=float, default=None,
                     help="with --verify relative and --overlap-radius: add a loop only if it is valid and both directions' overlap (aligned source <-> target) reach this fraction")
     ap.add_argument("--overlap-radius", type=float, default=None, help="with --min-overlap: the radius [m] within which a point counts as having a partner")
+    ap.add_argument("--max-see-through", type=float, default=None,
+                    help="with --verify relative: add a loop only if neither scan sees through more than this share of the other's observed points under the verified transform")
     ap.add_argument("--backend", choices=["gpu", "oracle"], default="gpu", help="the engine on the GPU, or the CPU oracle")
     a = ap.parse_args()
     run(a.keyframes, a.seed, a.quatro, save_dir=a.save_dir, save_map_leaf=a.save_map_leaf, sensor=a.sensor, detector=a.detector, yaw_bias=a.yaw_bias,
         verify=a.verify, sc_top_k=a.sc_top_k, backend=a.backend, loop_every=a.loop_every, catch_up=a.catch_up, submap_matching=a.submap_matching,
-        min_overlap=a.min_overlap, overlap_radius=a.overlap_radius)
+        min_overlap=a.min_overlap, overlap_radius=a.overlap_radius, max_see_through=a.max_see_through)
