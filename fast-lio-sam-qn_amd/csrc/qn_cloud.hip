@@ -386,6 +386,7 @@ void* qn_kf_int_scratch(qn_kf_store* s, int which, size_t bytes) {
   return s->int_scratch[which];
 }
 const float4* qn_kf_int_keyframe(const qn_kf_store* s, int32_t id, uint32_t* n) { *n = s->sizes[id]; return s->clouds[id]; }
+bool qn_kf_int_has_intensity(const qn_kf_store* s, int32_t id) { return s->has_i[id] != 0; }
 void* qn_kf_int_ext(const qn_kf_store* s, int which) { return which >= 0 && which < QN_KF_INT_EXT ? s->ext[which] : nullptr; }
 void qn_kf_int_set_ext(qn_kf_store* s, int which, void* p, qn_kf_int_release_fn release) {
   if (which < 0 || which >= QN_KF_INT_EXT) return;
@@ -513,8 +514,9 @@ static int sort_segments(qn_kf_store* s, const std::vector<SortGroup>& groups, c
   return QN_OK;
 }
 
-// ---- the one voxel-grid pipeline.  Submap t = the keyframes ids[seg_off[t] .. seg_off[t + 1]) (ids already checked) with the poses of the
-// same entries, transformed, concatenated in list order and voxel-grid at `leaf`, every submap into `out` (the caller's slot).
+// ---- the one voxel-grid pipeline.  Submap t = the sources src[seg_off[t] .. seg_off[t + 1]) with the poses of the same entries, transformed,
+// concatenated in list order and voxel-grid at `leaf`, every submap into `out` (the caller's slot).  A source is (records, count, has intensity):
+// a resident keyframe for the callers that list ids (sources_of), or any device records of the same layout (qn_kf_int_build_map_from).
 // carry_intensity: the centroids average .w (the map), else w = 1.  A submap that trips PCL's overflow guard is passed through behind the
 // leaves: trip_whole = its whole concatenation, non-finite points and intensity included (the map: output = *input_), else its finite points
 // in concatenation order with w = 1 (assemble, batch).  res[t] = its records, their count and QN_OK, or QN_ERR_EMPTY_CLOUD when it has no
@@ -532,11 +534,18 @@ struct Tables {
   }
 };
 struct VoxelNotes { bool nonfinite, tripped; };      // a voxelized or tripped submap had non-finite points / some submap tripped the guard
-static int voxel_submaps(qn_kf_store* s, const int32_t* ids, const double* poses, const uint32_t* seg_off, uint32_t n_seg, double leaf,
+struct VoxSrc { const float4* pts; uint32_t n; uint8_t has_i; };
+// the resident keyframes ids[a .. b) (ids already checked) as sources, at the same positions a .. b of the result
+static std::vector<VoxSrc> sources_of(const qn_kf_store* s, const int32_t* ids, uint32_t a, uint32_t b) {
+  std::vector<VoxSrc> v(b);
+  for (uint32_t j = a; j < b; j++) v[j] = VoxSrc{s->clouds[ids[j]], s->sizes[ids[j]], s->has_i[ids[j]]};
+  return v;
+}
+static int voxel_submaps(qn_kf_store* s, const VoxSrc* src, const double* poses, const uint32_t* seg_off, uint32_t n_seg, double leaf,
                          bool carry_intensity, bool trip_whole, Buf<float4>& out, SubmapOut* res, VoxelNotes* notes) {
   const uint32_t e0 = seg_off[0], count = seg_off[n_seg] - e0;
   size_t total = 0, tiles = 0;
-  for (uint32_t j = e0; j < e0 + count; j++) { total += s->sizes[ids[j]]; tiles += tiles_of(s->sizes[ids[j]]); }
+  for (uint32_t j = e0; j < e0 + count; j++) { total += src[j].n; tiles += tiles_of(src[j].n); }
   for (uint32_t t = 0; t < n_seg; t++) res[t] = SubmapOut{nullptr, 0, QN_ERR_EMPTY_CLOUD};
   *notes = VoxelNotes{false, false};
   if (total >= 0xffffffffull) return QN_ERR_CAPACITY;
@@ -557,8 +566,8 @@ static int voxel_submaps(qn_kf_store* s, const int32_t* ids, const double* poses
   for (uint32_t t = 0; t < n_seg; t++) {
     toff[t] = b0; p0[t] = off;
     for (uint32_t j = seg_off[t]; j < seg_off[t + 1]; j++) {
-      const uint32_t k = j - e0, nk = s->sizes[ids[j]], ntk = tiles_of(nk);
-      kfs[k] = qn::MapKf{s->clouds[ids[j]], off, nk, b0, s->has_i[ids[j]]}; kseg[k] = t;
+      const uint32_t k = j - e0, nk = src[j].n, ntk = tiles_of(nk);
+      kfs[k] = qn::MapKf{src[j].pts, off, nk, b0, src[j].has_i}; kseg[k] = t;
       for (uint32_t b = 0; b < ntk; b++) blk[b0 + b] = k;
       off += nk; b0 += ntk;
     }
@@ -717,7 +726,7 @@ extern "C" int qn_kf_assemble(qn_kf_store* s, const int32_t* ids, const double* 
   if (!ids_valid(s, ids, 0, count)) return QN_ERR_INVALID_ARG;
   const uint32_t seg[2] = {0, count};
   SubmapOut r; VoxelNotes nt;
-  const int rc = voxel_submaps(s, ids, poses, seg, 1, leaf, false, false, s->out[slot], &r, &nt);
+  const int rc = voxel_submaps(s, sources_of(s, ids, 0, count).data(), poses, seg, 1, leaf, false, false, s->out[slot], &r, &nt);
   if (rc != QN_OK) return rc;
   if (r.status != QN_OK) return r.status;
   if (nt.nonfinite) s->last_error = kNonFiniteNote;
@@ -738,6 +747,16 @@ extern "C" int qn_kf_download(qn_kf_store* s, int slot, float* xyz_out) {       
 // the corrected global map (fast_lio_sam_qn.cpp:302-316, 398-411, 435-448): every listed keyframe transformed with its corrected pose,
 // concatenated in list order, voxel-grid at `leaf` with intensity; into the store's own map slot (never assemble slots 0 / 1).
 // Unlike qn_kf_assemble, a tripped overflow guard passes the WHOLE concatenation through, non-finite points included (output = *input_).
+static int build_map_sources(qn_kf_store* s, const VoxSrc* src, const double* poses, uint32_t count, double leaf, const float** d_xyzi_out, uint32_t* n_out) {
+  const uint32_t seg[2] = {0, count};
+  SubmapOut r; VoxelNotes nt;
+  const int rc = voxel_submaps(s, src, poses, seg, 1, leaf, true, true, s->map, &r, &nt);
+  if (rc != QN_OK) return rc;
+  if (r.status != QN_OK) return r.status;
+  if (nt.tripped) s->last_error = kOverflowWarning;
+  s->map_n = r.n; *d_xyzi_out = (const float*)r.ptr; *n_out = r.n;
+  return QN_OK;
+}
 extern "C" int qn_kf_build_map(qn_kf_store* s, const int32_t* ids, const double* poses, uint32_t count, double leaf,
                                const float** d_xyzi_out, uint32_t* n_out) {
   if (!s || (count && (!ids || !poses)) || !d_xyzi_out || !n_out || !(leaf > 0)) return QN_ERR_INVALID_ARG;
@@ -745,14 +764,16 @@ extern "C" int qn_kf_build_map(qn_kf_store* s, const int32_t* ids, const double*
   s->map_n = 0; s->last_error.clear();
   if (count == 0) return QN_ERR_EMPTY_CLOUD;
   if (!ids_valid(s, ids, 0, count)) return QN_ERR_INVALID_ARG;
-  const uint32_t seg[2] = {0, count};
-  SubmapOut r; VoxelNotes nt;
-  const int rc = voxel_submaps(s, ids, poses, seg, 1, leaf, true, true, s->map, &r, &nt);
-  if (rc != QN_OK) return rc;
-  if (r.status != QN_OK) return r.status;
-  if (nt.tripped) s->last_error = kOverflowWarning;
-  s->map_n = r.n; *d_xyzi_out = (const float*)r.ptr; *n_out = r.n;
-  return QN_OK;
+  return build_map_sources(s, sources_of(s, ids, 0, count).data(), poses, count, leaf, d_xyzi_out, n_out);
+}
+int qn_kf_int_build_map_from(qn_kf_store* s, const float4* const* pts, const uint32_t* n, const uint8_t* has_i, const double* poses, uint32_t count, double leaf,
+                             const float** d_xyzi_out, uint32_t* n_out) {
+  *d_xyzi_out = nullptr; *n_out = 0;
+  s->map_n = 0; s->last_error.clear();
+  if (count == 0) return QN_ERR_EMPTY_CLOUD;
+  std::vector<VoxSrc> src(count);
+  for (uint32_t k = 0; k < count; k++) src[k] = VoxSrc{n[k] ? pts[k] : nullptr, n[k], has_i[k]};
+  return build_map_sources(s, src.data(), poses, count, leaf, d_xyzi_out, n_out);
 }
 
 // the map into host records: only the 12 xyz bytes (offset 0) and the 4 intensity bytes (offset ioff) of each are written
@@ -779,7 +800,7 @@ extern "C" int qn_kf_assemble_batch(qn_kf_store* s, const int32_t* ids, const do
   for (uint32_t t = 0; t < n_seg; t++) { d_xyz_out[t] = nullptr; n_out[t] = 0; status[t] = QN_ERR_EMPTY_CLOUD; }
   s->bt_ptr.assign(n_seg, nullptr); s->bt_n.assign(n_seg, 0); s->last_error.clear();
   std::vector<SubmapOut> res(n_seg); VoxelNotes nt;
-  const int rc = voxel_submaps(s, ids, poses, seg_off, n_seg, leaf, false, false, s->bt_out, res.data(), &nt);
+  const int rc = voxel_submaps(s, sources_of(s, ids, seg_off[0], seg_off[n_seg]).data(), poses, seg_off, n_seg, leaf, false, false, s->bt_out, res.data(), &nt);
   if (rc != QN_OK) return rc;
   if (nt.nonfinite) s->last_error = kNonFiniteNote;
   if (nt.tripped) s->last_error = kOverflowWarning;
@@ -799,7 +820,7 @@ int qn_kf_int_voxel_windows(qn_kf_store* s, const int32_t* ids, const double* po
   std::vector<SubmapOut> res(n_seg); VoxelNotes nt;
   Buf<float4> out;
   s->last_error.clear();
-  const int rc = voxel_submaps(s, ids, poses, seg_off, n_seg, leaf, false, false, out, res.data(), &nt);
+  const int rc = voxel_submaps(s, sources_of(s, ids, seg_off[0], seg_off[n_seg]).data(), poses, seg_off, n_seg, leaf, false, false, out, res.data(), &nt);
   if (rc != QN_OK) { dev_free(out); return rc; }
   if (nt.nonfinite) s->last_error = kNonFiniteNote;
   if (nt.tripped) s->last_error = kOverflowWarning;

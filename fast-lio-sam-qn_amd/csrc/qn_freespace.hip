@@ -10,6 +10,7 @@
 //   k_freespace_check  one thread per record, (pair, direction) a grid dimension: transform, projection, the window's gathers, the class byte; the block's
 //                      counts by ballots and popcounts into its own slot;
 //   k_freespace_reduce one block per (pair, direction) over its blocks' slots in a fixed order.
+// The projection, the column table's staging, the window gather and the class rule live in qn_range.cuh (shared with qn_staticmap.hip).
 // The column table (16 bytes per column) is staged in LDS when it fits 64 KiB (up to 4096 columns); above that the bisection reads it from global memory (14
 // reads per point, L2 resident), because a 128 KiB stage would leave one block per CU.  The row table is read from global memory: the bisection's index differs
 // from lane to lane, so a scalar load cannot serve it.
@@ -23,57 +24,16 @@
 #include <vector>
 #include "../../include/qn_engine.h"
 #include "qn_kf_internal.h"
+#include "qn_range.cuh"
 
 namespace {
+using namespace qn_range;      // fs_stage / fs_project / fs_classify, RangeState: shared with qn_staticmap.hip
 
-#define FS_BLOCK 512
-#define FS_ITERS 4
-#define FS_TILE (FS_BLOCK * FS_ITERS)                   // records per block
-#define FS_WAVES (FS_BLOCK / 64)
-#define FS_LDS_MAX (64u << 10)                          // the column table is staged in LDS up to this size
-#define FS_INF_BITS 0x7F800000u
 #define FS_NCOUNT 5                                     // per block and per direction: finite, unobserved, seen through, occluded, agree
 
 struct RgKf { const float4* pts; uint32_t n; int32_t id; };
 struct FsSeg { const float4* pts; uint32_t n, p0, b0; int32_t img; double M[12]; };
 struct FsCnt { uint32_t c[FS_NCOUNT]; };
-
-template <bool LDS> __device__ __forceinline__ const double2* fs_stage(const double2* __restrict__ g, uint32_t nc) {
-  extern __shared__ __align__(16) unsigned char fs_smem[];
-  if (!LDS) return g;
-  double2* l = (double2*)fs_smem;
-  for (uint32_t t = threadIdx.x; t < nc; t += FS_BLOCK) l[t] = g[t];
-  __syncthreads();
-  return l;
-}
-
-// the twin's project(): false for a dropped point (the coordinates are finite)
-__device__ __forceinline__ bool fs_project(double x, double y, double z, const double* __restrict__ trow, uint32_t nr, const double2* cs, uint32_t nc, double min_range,
-                                           uint32_t& row, uint32_t& col, double& r) {
-  const double rho2 = x * x + y * y;
-  const double rho = __builtin_sqrt(rho2);
-  r = __builtin_sqrt(rho2 + z * z);
-  uint32_t lo = 0, hi = nr + 1;
-#pragma unroll 1
-  while (lo < hi) {
-    const uint32_t mid = (lo + hi) >> 1;
-    if (z >= rho * trow[mid]) lo = mid + 1; else hi = mid;
-  }
-  if (lo == 0 || lo == nr + 1 || !(r >= min_range)) return false;
-  row = lo - 1;
-  const int hp = (y > 0.0 || (y == 0.0 && x > 0.0)) ? 0 : 1;
-  lo = 1; hi = nc;
-#pragma unroll 1
-  while (lo < hi) {
-    const uint32_t mid = (lo + hi) >> 1;
-    const double2 b = cs[mid];
-    const int hb = (b.y > 0.0 || (b.y == 0.0 && b.x > 0.0)) ? 0 : 1;
-    const double cr = b.x * y - b.y * x;
-    if (hp > hb || (hp == hb && cr >= 0.0)) lo = mid + 1; else hi = mid;
-  }
-  col = lo - 1;
-  return true;
-}
 
 // grid (pixel tiles, keyframes)
 __global__ void __launch_bounds__(256) k_range_clear(const RgKf* __restrict__ kfs, uint32_t npix, uint32_t* __restrict__ img) {
@@ -145,28 +105,7 @@ __global__ void __launch_bounds__(FS_BLOCK) k_freespace_check(const FsSeg* __res
       const double px = ((m0 * x + m1 * y) + m2 * z) + m3;
       const double py = ((m4 * x + m5 * y) + m6 * z) + m7;
       const double pz = ((m8 * x + m9 * y) + m10 * z) + m11;
-      fin = __builtin_isfinite(px) && __builtin_isfinite(py) && __builtin_isfinite(pz);
-      uint32_t row, col; double r;
-      if (fin && fs_project(px, py, pz, trow, nr, ct, nc, min_range, row, col, r)) {
-        uint32_t rn = FS_INF_BITS, rf = 0u;
-#pragma unroll 1
-        for (int dr = -wr; dr <= wr; dr++) {
-          const int rr = (int)row + dr;
-          if ((unsigned)rr >= nr) continue;
-#pragma unroll 1
-          for (int dc = -wc; dc <= wc; dc++) {
-            int cc = (int)col + dc;                                  // 2 wc + 1 <= nc: one wrap is enough
-            cc = cc < 0 ? cc + (int)nc : (cc >= (int)nc ? cc - (int)nc : cc);
-            const uint32_t pix = (uint32_t)rr * nc + (uint32_t)cc;
-            rn = min(rn, near[pix]); rf = max(rf, far[pix]);
-          }
-        }
-        const double tol = tol_abs + tol_rel * r;
-        cls = 4u;
-        if (r > (double)__uint_as_float(rf) + tol) cls = 3u;
-        if (r + tol < (double)__uint_as_float(rn)) cls = 2u;
-        if (rn == FS_INF_BITS) cls = 1u;
-      }
+      cls = fs_classify(px, py, pz, trow, nr, ct, nc, min_range, wr, wc, tol_abs, tol_rel, near, far, fin);
       out[i] = (uint8_t)cls;
     }
     cf += __popcll(__ballot(fin));
@@ -215,17 +154,6 @@ __global__ void __launch_bounds__(256) k_freespace_reduce(const FsSeg* __restric
 #define RG_DESCRIBE_CHUNK 32768u                         // keyframes per describe launch (the grid's y dimension)
 const uint32_t kMaxPairs = 32767;                        // (pair, direction) is the grid's y dimension
 
-struct FsSlot { uint32_t p0[2], n[2]; };
-// The store's range-image state (slot QN_KF_INT_EXT_RANGE): parameters, the host tables on the device, image slots indexed by keyframe id (grown with the
-// store), and the per-point classes of the latest check in a buffer of their own (the store's scratch may be reused by any other call).
-struct RangeState {
-  qn_range_params p{};
-  double* tab = nullptr;                                 // t [n_rows + 1], padded to 16 bytes, then (cos, sin) [n_cols]
-  uint32_t* img = nullptr;                               // per keyframe id: near [n_rows * n_cols], far [n_rows * n_cols], as f32 bit patterns
-  size_t cap = 0;
-  std::vector<uint8_t> described;
-  bool live = false; std::vector<FsSlot> slots; uint8_t* cls = nullptr; size_t cls_cap = 0;
-};
 void range_release(void* v) {                            // called by qn_kf_store_destroy after its stream has drained
   RangeState* st = (RangeState*)v;
   (void)hipFree(st->tab); (void)hipFree(st->img); (void)hipFree(st->cls);
@@ -247,7 +175,6 @@ bool range_params_ok(const qn_range_params& p) {
          p.tol_abs >= 0.0 && std::isfinite(p.tol_rel) && p.tol_rel >= 0.0 && p.window_rows < p.n_rows && p.window_cols <= (QN_RANGE_MAX_COLS >> 1) &&
          2 * p.window_cols + 1 <= p.n_cols;
 }
-size_t range_cs_offset(uint32_t nr) { return ((size_t)nr + 2) & ~(size_t)1; }      // in doubles: the column table is 16-byte aligned
 // the host tables (freespace.tables): row edges as tangents and the column boundary directions, from the C library.  The angles go through volatiles so that
 // tan, cos and sin are the library calls the twin makes.
 std::vector<double> range_tables(const qn_range_params& p) {
@@ -304,7 +231,6 @@ int range_reserve(qn_kf_store* s, RangeState* st, size_t n) {
   st->img = d; st->cap = cap;
   return QN_OK;
 }
-size_t range_lds_bytes(const RangeState* st) { const size_t b = sizeof(double2) * (size_t)st->p.n_cols; return b <= FS_LDS_MAX ? b : 0; }
 
 }  // namespace
 

@@ -695,6 +695,23 @@ class Freespace(C.Structure):
     _fields_ = [("q_in_c", FreespaceDir), ("c_in_q", FreespaceDir)]
 
 
+class StaticParams(C.Structure):
+    """qn_static_params (8 bytes): the rule of the static map - a record is removed iff seen_through >= min_see_through and seen_through > agree_weight * agree"""
+    _fields_ = [("min_see_through", C.c_uint32), ("agree_weight", C.c_uint32)]
+
+    def __init__(self, min_see_through=2, agree_weight=1):
+        super().__init__(min_see_through, agree_weight)
+
+    @classmethod
+    def from_twin(cls, r):
+        return cls(int(r.min_see_through), int(r.agree_weight))
+
+    def twin(self):
+        """-> the staticmap.StaticParams with these values"""
+        from . import staticmap
+        return staticmap.StaticParams(int(self.min_see_through), int(self.agree_weight))
+
+
 class KeyframeStore:
     """Device-resident keyframe clouds + LoopClosure::setSrcAndDstCloud on the GPU (loop_closure.cpp:58-108)."""
 
@@ -1143,6 +1160,54 @@ class KeyframeStore:
         out = np.zeros(max(sizes[pair_slot][direction], 1), np.uint8)
         self._check(self._l.qn_kf_freespace_points(self.h, C.c_uint32(pair_slot), C.c_int(direction), _p(out)))
         return out[:sizes[pair_slot][direction]]
+
+    # ---- the static map: the corrected map without the records other keyframes saw through (qn_kf_static_* / qn_kf_build_map_static; twin: qn_amd/staticmap.py)
+    def static_classify(self, ids, poses, witnesses=None, radius=15.0, max_k=8, params=None):
+        """qn_kf_static_classify: every record of every listed keyframe (the list and the corrected poses build_map takes) against the range images of its
+        entry's witnesses, in one pass.  witnesses = (wit_off, wit), entry positions in CSR form; None: staticmap.witnesses(ids, poses, radius, max_k), the
+        up to max_k nearest entries of another keyframe within radius.  The witnesses' keyframes must have range images (range_describe).  params: a
+        StaticParams (or a staticmap.StaticParams); None: the defaults (2, 1).  -> dict(removed (count,) uint32, status (count,) list, wit_off, wit).
+        The votes stay resident for static_points / build_map_static until the next successful call."""
+        from . import staticmap
+        ids = np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+        n = len(ids)
+        poses = np.ascontiguousarray(np.asarray(poses, dtype=np.float64).reshape(-1, 16))
+        if len(poses) != n:
+            raise ValueError("static_classify: %d entries but %d poses" % (n, len(poses)))
+        if witnesses is None:
+            witnesses = staticmap.witnesses(ids, poses, radius, max_k)
+        off = np.ascontiguousarray(witnesses[0], dtype=np.uint32).reshape(-1); wit = np.ascontiguousarray(witnesses[1], dtype=np.uint32).reshape(-1)
+        if len(off) != n + 1 or (n and int(off[-1]) > len(wit)):
+            raise ValueError("static_classify: wit_off must be count + 1 offsets into wit")
+        p = StaticParams() if params is None else params
+        if not isinstance(p, StaticParams):
+            p = StaticParams.from_twin(p)
+        removed = np.zeros(max(n, 1), np.uint32); status = np.zeros(max(n, 1), np.int32)
+        self._check(self._l.qn_kf_static_classify(self.h, _p(ids) if n else None, _p(poses) if n else None, C.c_uint32(n), _p(off), _p(wit) if len(wit) else None,
+                                                  C.byref(p), _p(removed), _p(status)))
+        self._static_n = [self._sizes.get(int(i)) for i in ids]
+        return dict(removed=removed[:n].copy(), status=[int(v) for v in status[:n]], wit_off=off, wit=wit)
+
+    def static_points(self, entry):
+        """qn_kf_static_points: the votes of every record of entry `entry` of the latest static_classify -> (seen_through, agree, removed), each (n,) uint8"""
+        sizes = getattr(self, "_static_n", None)
+        if sizes is None or not (0 <= entry < len(sizes)) or sizes[entry] is None:
+            raise ValueError("static_points: no such entry in the latest static_classify")
+        n = sizes[entry]
+        out = [np.zeros(max(n, 1), np.uint8) for _ in range(3)]
+        self._check(self._l.qn_kf_static_points(self.h, C.c_uint32(entry), _p(out[0]), _p(out[1]), _p(out[2])))
+        return tuple(o[:n] for o in out)
+
+    def build_map_static(self, leaf):
+        """qn_kf_build_map_static: the static map of the latest static_classify - build_map of its list and poses without the removed records - into the
+        store's map slot -> number of map points (download_map serves it).  May be called again with another leaf."""
+        ptr = C.c_void_p(); n = C.c_uint32()
+        st = self._l.qn_kf_build_map_static(self.h, C.c_double(leaf), C.byref(ptr), C.byref(n))
+        if st not in (QN_ERR_NOT_READY, QN_ERR_INVALID_ARG):         # a refused call leaves the map slot as it was
+            self._map_n = 0
+        self._check(st)
+        self._map_n = n.value
+        return n.value
 
     # ---- Scan Context loop candidates (qn_kf_sc_*; numpy twin: qn_amd/scancontext.py)
     def sc_set_params(self, params=None, **kw):

@@ -552,6 +552,41 @@ int  qn_kf_add_xyzi(qn_kf_store*, const float* pts, uint32_t n, uint32_t stride_
 int  qn_kf_build_map(qn_kf_store*, const int32_t* ids, const double* poses16, uint32_t count, double leaf,
                      const float** d_xyzi_out /* float4: x y z intensity */, uint32_t* n_out);
 int  qn_kf_download_map(qn_kf_store*, void* out, uint32_t stride_bytes, uint32_t intensity_offset_bytes);
+/* ---- the static map: the corrected map without the records other keyframes saw through (csrc/qn_staticmap.hip; numpy twin and specification:
+ * qn_amd/staticmap.py)
+ * Whatever moved while the sensor drove past - cars, people - stays in qn_kf_build_map's map as a ghost trail.  The evidence to remove it is resident: a
+ * record of one keyframe is transient if, carried with the corrected poses into a neighbouring keyframe's SENSOR frame, it lies where that keyframe's rays
+ * passed on their way to a farther surface - class 2, SEEN THROUGH, of the free-space check above, with the same projection, images, window and tolerances
+ * (the store's qn_range_params).  These calls take that vote many to many, drop the records voted out and build the map from the rest.  Votes are integers
+ * and the map is the one voxel-grid pipeline's, so every byte equals the twin's bit for bit and a rerun gives the same bytes.
+ * List: ids[0 .. count) with poses16 (row-major 4x4 f64, sensor -> world), the list qn_kf_build_map takes; ids may repeat; a list position is an ENTRY.
+ * Witnesses of entry e: wit[wit_off[e] .. wit_off[e + 1]), entry positions, in the caller's order (qn_map::staticMapWitnesses / staticmap.witnesses make the
+ *   default list: the nearest entries of another keyframe).  A witness never has the entry's own keyframe id; at most 255 per entry.
+ * Votes of record p of entry e, over its witnesses w in list order: M = inv(P_w) P_e with inv(P) = [R^T | -R^T t] (the host arithmetic of
+ *   qn_kf_verify_loop_candidates' relative poses), the point ((M0 x + M1 y) + M2 z) + M3 in f64 and not rounded, its class against the images of keyframe
+ *   ids[w].  seen_through[p] = the witnesses giving class 2, agree[p] = those giving class 4, both u8 (exact under the 255 cap).
+ * Rule, qn_static_params (8 bytes): min_see_through (>= 1, default 2), agree_weight (default 1).  Record p is REMOVED iff seen_through >= min_see_through and
+ *   seen_through > agree_weight * agree, in exact integers.  A record with a non-finite coordinate gets no vote and is never removed.
+ * qn_kf_static_classify: ONE vote pass on the store's stream whatever count is (the entry a grid dimension, the witness loop inside the thread: a record is read
+ *   once and its three bytes written once), the kept records of every entry compacted in order into a store-owned buffer; one host synchronisation.
+ *   removed_per_entry[e] = its removed records; status[e] = QN_ERR_EMPTY_CLOUD for an entry without records.  The store keeps the list, the poses and per record
+ *   seen_through, agree and the removed flag until the next successful call.  Refused before anything runs, the state of the previous call left intact:
+ *   QN_ERR_INVALID_ARG: a null pointer (wit may be NULL when no entry has a witness), count == 0, a bad id, a non-finite pose, a witness whose keyframe has no
+ *   images (qn_kf_range_describe), a witness position >= count, a witness with the entry's own id, a non-monotone wit_off, min_see_through == 0;
+ *   QN_ERR_CAPACITY: more than 255 witnesses for an entry, or 2^32 records in the call.
+ * qn_kf_static_points: the bytes of entry `entry` of the latest classify, one per record (any output may be NULL, not all).  QN_ERR_NOT_READY before a
+ *   classify; QN_ERR_INVALID_ARG: a null store, no output, a bad entry.
+ * qn_kf_build_map_static: the static map of the latest classify = by definition qn_kf_build_map of the same list, poses and leaf over keyframes from which the
+ *   removed records have been deleted (order and intensity kept, an entry with nothing left contributes nothing; intensity averaging, point order and the
+ *   overflow-guard pass-through are qn_kf_build_map's) - into the store's map slot, so qn_kf_download_map serves it.  May be called again with another leaf.
+ *   QN_ERR_NOT_READY without a classify, or when a listed keyframe's records are no longer the ones the votes were taken on.  A refused call leaves the map
+ *   slot as it was.                                                                                                                                          */
+typedef struct qn_static_params { uint32_t min_see_through, agree_weight; } qn_static_params;      /* 8 bytes */
+void qn_static_default_params(qn_static_params* p);
+int  qn_kf_static_classify(qn_kf_store*, const int32_t* ids, const double* poses16, uint32_t count, const uint32_t* wit_off /* count + 1 */, const uint32_t* wit,
+                           const qn_static_params* params, uint32_t* removed_per_entry, int* status);
+int  qn_kf_static_points(qn_kf_store*, uint32_t entry, uint8_t* seen_through_out, uint8_t* agree_out, uint8_t* removed_out);
+int  qn_kf_build_map_static(qn_kf_store*, double leaf, const float** d_xyzi_out /* float4: x y z intensity */, uint32_t* n_out);
 /* LoopClosure::fetchClosestKeyframeIdx (loop_closure.cpp:34-56) generalised to the max_k nearest admissible keyframes,
  * ascending distance; out[0] is the reference's single choice.  Host code (O(#keyframes)).                        */
 int  qn_loop_candidates(const double* pos_xyz, const double* stamps, uint32_t n, uint32_t query, double radius, double tdiff,

@@ -17,7 +17,9 @@ point cloud across PCIe.  `backend="oracle"` runs the same loop with the CPU ora
 infrastructure: tests/test_replay.py compares the two); `save_dir` writes the corrected trajectory the way saveFlagCallback does
 (FQ:344-373): poses_kitti.txt (3x4 row-major, default stream precision) and poses_tum.txt ("#timestamp x y z qx qy qz qw", 8 decimals);
 with `save_map_leaf` the GPU backend also writes the corrected global map there as map.pcd (FQ:398-411: every keyframe with its corrected
-pose, voxel grid at save_voxel_resolution, on the device through qn_kf_build_map).
+pose, voxel grid at save_voxel_resolution, on the device through qn_kf_build_map); with `static_map` also map_static.pcd beside it, the same map without the
+records other keyframes saw through (qn_kf_static_classify / qn_kf_build_map_static).  `moving_boxes` puts boxes into the spinning sensor's scene that stand
+somewhere else in every keyframe - the ghost trails the static map is there to remove.
 The reference's extra iSAM2::update() calls after a loop (FQ:160-165) are iSAM2 relinearisation sweeps; the batch Gauss-Newton stand-in
 iterates to convergence instead.
 """
@@ -170,6 +172,20 @@ def make_lidar_stream(n_kf, seed, lidar=None, drift_yaw=0.004, drift_xy=0.03, ya
     return scene.primitives(), lidar, seeds, gt, odom, np.arange(n_kf) * 1.0
 
 
+MOVING_BOX_SIZE = (4.0, 2.0, 1.5)                                  # length (x), width (y), height [m]
+
+
+def moving_box_lane(j):
+    """the line y = const box j drives along"""
+    return 6.0 + 9.0 * j
+
+
+def moving_box_prims(n_boxes, k):
+    """the n_boxes PRIM_BOX primitives of keyframe k: box j drives along its lane, 2.5 m further in x per keyframe (wrapping over -35 .. 35)"""
+    from qn_amd import synth
+    return np.array([(synth.PRIM_BOX, (-35.0 + (2.5 * k + 23.0 * j) % 70.0, moving_box_lane(j)) + MOVING_BOX_SIZE + (0.0,)) for j in range(n_boxes)], dtype=synth.PRIM_DTYPE)
+
+
 def rot_to_quat(R):
     """(qx, qy, qz, qw) of a rotation matrix (what tf::Matrix3x3::getRotation yields in poseEigToPoseStamped, utilities.hpp)"""
     t = np.trace(R)
@@ -262,7 +278,8 @@ def _oracle_submap_relative(orc, scans, poses, q, c, yaw, submap_range, voxel, m
 
 def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, submap_range=5, score_thr=1.5, verbose=True, backend="gpu", save_dir=None,
         save_map_leaf=None, sensor="uniform", detector="radius", sc_max_dist=0.3, yaw_bias=0.006, verify="reference", sc_top_k=1, loop_every=1, catch_up=False,
-        submap_matching=False, min_overlap=None, overlap_radius=None, max_see_through=None, range_params=None):
+        submap_matching=False, min_overlap=None, overlap_radius=None, max_see_through=None, range_params=None, static_map=False, static_radius=15.0,
+        static_max_k=8, moving_boxes=0):
     """sensor = "uniform": keyframe clouds sampled uniformly by area inside a disc (make_stream); "spinning": ray-cast spinning-LiDAR
     scans from the ground-truth poses of the same figure-8 (make_lidar_stream).  detector = "radius": the candidate is the closest older
     keyframe within `radius` of the corrected position (LC:34-56); "scancontext": the older keyframe nearest by Scan Context distance, kept
@@ -295,7 +312,13 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
     (KeyframeStore.range_describe; range_params, a freespace.Params, defaults to the simulated sensor's image, or to a 32 x 360 image over +-60 degrees for
     the uniform clouds), after every verification each pair's T goes through the free-space check (KeyframeStore.freespace_batch, one pass for all pairs; the
     oracle backend runs the twin qn_amd.freespace on the raw scans), printed per attempt, and a pair counts as valid only if it was valid so far AND neither
-    direction's share of observed points that the other scan saw through exceeds F.  out["see_through"]: one dict per pair."""
+    direction's share of observed points that the other scan saw through exceeds F.  out["see_through"]: one dict per pair.
+    static_map (the GPU backend, with save_dir and save_map_leaf; default False: the run is what it is without it): after the run every keyframe's range images
+    are made (unless max_see_through made them on arrival), every record of every keyframe is checked against the images of its static_max_k nearest keyframes
+    within static_radius under the corrected poses (KeyframeStore.static_classify), and map_static.pcd - map.pcd without the records voted out - is written
+    beside map.pcd (KeyframeStore.build_map_static).  out["static_removed"]: the records removed, out["static_map_points"] / out["map_points"]: the maps' sizes.
+    moving_boxes = N (sensor="spinning" only; default 0: every run is what it was): N extra boxes in the scene that stand somewhere else in every keyframe
+    (moving_box_prims), so every keyframe is cast by a call of its own."""
     if detector not in ("radius", "scancontext"):
         raise ValueError("detector must be 'radius' or 'scancontext', not %r" % (detector,))
     if verify not in ("reference", "relative"):
@@ -318,6 +341,18 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
         raise ValueError("max_see_through needs verify='relative' (a transform between two sensor frames)")
     if fgate and not (np.isfinite(max_see_through) and max_see_through >= 0):
         raise ValueError("max_see_through must be a fraction >= 0, not %r" % (max_see_through,))
+    if int(moving_boxes) != moving_boxes or moving_boxes < 0:
+        raise ValueError("moving_boxes must be a whole number >= 0, not %r" % (moving_boxes,))
+    if moving_boxes and sensor != "spinning":
+        raise ValueError("moving_boxes needs sensor='spinning' (the boxes are primitives of the ray-cast scene)")
+    if static_map and backend != "gpu":
+        raise ValueError("static_map needs backend='gpu' (the oracle backend writes no map)")
+    if static_map and (save_dir is None or save_map_leaf is None):
+        raise ValueError("static_map needs save_dir and save_map_leaf (map_static.pcd is written beside map.pcd)")
+    if static_map and not (np.isfinite(save_map_leaf) and save_map_leaf > 0):
+        raise ValueError("static_map needs save_map_leaf > 0, not %r" % (save_map_leaf,))
+    if static_map and not (np.isfinite(static_radius) and static_radius >= 0 and int(static_max_k) == static_max_k and 0 <= static_max_k <= 255):
+        raise ValueError("static_map needs static_radius >= 0 and 0 <= static_max_k <= 255, not %r / %r" % (static_radius, static_max_k))
     overlaps = []; see_through = []; fs_images = {}
 
     def apply_freespace(rs, pairs):
@@ -383,15 +418,18 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
         g.setCorrespondenceRandomness(15); g.setMaximumIterations(32); g.setMaxCorrespondenceDistance(1.5 * radius); g.setTransformationEpsilon(0.01)
         quatro = engine.Quatro(ctx) if use_quatro else None
         loop_candidates = engine.loop_candidates
-        if scans is None:                                           # one call casts every keyframe into the store
+        if scans is None and moving_boxes:                          # the boxes stand elsewhere in every keyframe: one call per keyframe
+            cast_ids = [int(store.add_lidar_scans(np.concatenate([prims, moving_box_prims(moving_boxes, k)]), lidar, [gt[k]], [seeds[k]])[0]) for k in range(n_kf)]
+        elif scans is None:                                         # one call casts every keyframe into the store
             cast_ids = list(store.add_lidar_scans(prims, lidar, gt, seeds))
     else:
         from oracle import oracle as orc                           # the checker's side of the comparison (tests only)
         loop_candidates = orc.loop_candidates
         if scans is None:
             from qn_amd import synth
-            scans = [synth.lidar_scan(prims, lidar, T, int(sd))[:, :3] for T, sd in zip(gt, seeds)]
-    if fgate:
+            scans = [synth.lidar_scan(np.concatenate([prims, moving_box_prims(moving_boxes, k)]) if moving_boxes else prims, lidar, T, int(sd))[:, :3]
+                     for k, (T, sd) in enumerate(zip(gt, seeds))]
+    if fgate or static_map:
         from qn_amd import freespace
         fs_params = range_params if range_params is not None else (freespace.Params.for_sensor(lidar) if sensor == "spinning" else
                                                                    freespace.Params(n_rows=32, n_cols=360, el_lo=-np.pi / 3, el_hi=np.pi / 3, min_range=1.0))
@@ -567,6 +605,14 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
         if save_map_leaf is not None and backend == "gpu":
             n = store.build_map(ids, corrected, save_map_leaf)
             write_pcd_xyzi(os.path.join(save_dir, "map.pcd"), store.download_map(n))
+            if static_map:
+                out["map_points"] = n
+                if not fgate:                                                                # (with the gate on, every keyframe was described on arrival)
+                    store.range_describe(ids)
+                st = store.static_classify(ids, corrected, radius=static_radius, max_k=static_max_k)
+                n = store.build_map_static(save_map_leaf)
+                write_pcd_xyzi(os.path.join(save_dir, "map_static.pcd"), store.download_map(n))
+                out["static_removed"] = int(st["removed"].sum()); out["static_map_points"] = n
     if verbose:
         print({k: v for k, v in out.items() if k not in ("poses", "loop_list", "loop_T", "gt", "overlaps", "see_through")})
     if backend == "gpu":
@@ -597,8 +643,11 @@ if __name__ == "__main__":
     ap.add_argument("--overlap-radius", type=float, default=None, help="with --min-overlap: the radius [m] within which a point counts as having a partner")
     ap.add_argument("--max-see-through", type=float, default=None,
                     help="with --verify relative: add a loop only if neither scan sees through more than this share of the other's observed points under the verified transform")
+    ap.add_argument("--static-map", action="store_true",
+                    help="with --save-dir and --save-map-leaf: also write map_static.pcd, the map without the records other keyframes saw through")
+    ap.add_argument("--moving-boxes", type=int, default=0, help="with --sensor spinning: this many boxes that stand somewhere else in every keyframe")
     ap.add_argument("--backend", choices=["gpu", "oracle"], default="gpu", help="the engine on the GPU, or the CPU oracle")
     a = ap.parse_args()
     run(a.keyframes, a.seed, a.quatro, save_dir=a.save_dir, save_map_leaf=a.save_map_leaf, sensor=a.sensor, detector=a.detector, yaw_bias=a.yaw_bias,
         verify=a.verify, sc_top_k=a.sc_top_k, backend=a.backend, loop_every=a.loop_every, catch_up=a.catch_up, submap_matching=a.submap_matching,
-        min_overlap=a.min_overlap, overlap_radius=a.overlap_radius, max_see_through=a.max_see_through)
+        min_overlap=a.min_overlap, overlap_radius=a.overlap_radius, max_see_through=a.max_see_through, static_map=a.static_map, moving_boxes=a.moving_boxes)
