@@ -433,19 +433,31 @@ extern "C" int qn_kf_download_keyframe(qn_kf_store* s, int32_t id, float* xyzi_o
 }
 
 // pcl::VoxelGrid::applyFilter's grid from the bounding box of the finite points: leaf-index origin and divisions, number of cells;
-// returns false when PCL's overflow guard trips (its own arithmetic: f32 product, int64 cast; it warns and sets output = *input_)
+// returns false when the guard trips (PCL warns and sets output = *input_).  The guard, the same rule in the oracle (orc_voxel_guard) and the numpy
+// restatement (voxel_guard, tests/test_kf_map_api.py), with inv = 1 / (float)leaf and everything below in f32 unless said otherwise - tripped when
+//   (1) on any axis floor(min * inv) or floor(max * inv) is outside [-2^31, 2^31)            [deviation from PCL, which converts them to int unchecked]
+//   (2) on any axis (max - min) * inv is not below 2^63, infinite or NaN included            [deviation from PCL, which converts it to int64 unchecked]
+//   (3) pd = the product over the axes of int64((max - min) * inv) + 1 exceeds INT32_MAX     [PCL's own guard]
+//   (4) cells = the product over the axes of floor(max * inv) - floor(min * inv) + 1 exceeds INT32_MAX   [deviation: PCL's index wraps; the keys need cells < 2^31]
+// Every comparison is made in floating point before the conversion and the products leave at the first factor or partial product above INT32_MAX, so
+// no conversion is out of range and no integer overflows.  Not tripped implies every leaf index k_batch_keys forms lies in [0, cells).
 static bool voxel_dims(const qn::BBoxOut& bb, double leaf, qn::VoxelDims* vd, long long* cells_out) {
   vd->inv = 1.0f / (float)leaf;
-  long long cells = 1; int divb[3];
+  *cells_out = 0;
+  const float two31 = 2147483648.0f, two63 = 9223372036854775808.0f;
+  long long cells = 1, pd = 1; int divb[3];
   for (int d = 0; d < 3; d++) {
     const float mn = qn::ord2f(bb.mn[d]), mx = qn::ord2f(bb.mx[d]);
-    vd->minb[d] = (int)std::floor(mn * vd->inv); const int maxb = (int)std::floor(mx * vd->inv);
-    divb[d] = maxb - vd->minb[d] + 1; cells *= divb[d];
+    const float lo = std::floor(mn * vd->inv), hi = std::floor(mx * vd->inv), ext = (mx - mn) * vd->inv;
+    if (!(lo >= -two31 && lo < two31 && hi >= -two31 && hi < two31)) return false;
+    if (!(ext < two63)) return false;
+    const long long div = (long long)hi - (long long)lo + 1, pdf = (long long)ext + 1;
+    if (pdf > (long long)INT32_MAX || div > (long long)INT32_MAX) return false;
+    pd *= pdf; cells *= div;                                         // both factors <= INT32_MAX: no product above 2^62
+    if (pd > (long long)INT32_MAX || cells > (long long)INT32_MAX) return false;
+    vd->minb[d] = (int)lo; divb[d] = (int)div;
   }
-  long long pd = 1;
-  for (int d = 0; d < 3; d++) { const float mn = qn::ord2f(bb.mn[d]), mx = qn::ord2f(bb.mx[d]); pd *= (long long)((mx - mn) * vd->inv) + 1; }
   *cells_out = cells;
-  if (pd > (long long)INT32_MAX || cells > (long long)INT32_MAX) return false;
   vd->div0 = divb[0]; vd->div01 = divb[0] * divb[1];
   return true;
 }
@@ -695,6 +707,12 @@ int qn_kf_int_cell_index(qn_kf_store* s, const float4* const* clouds, const uint
       double maxabs = 0.0;
       for (int a = 0; a < 3; a++) maxabs = std::max(maxabs, (double)std::max(std::fabs(qn::ord2f(bb.mn[a])), std::fabs(qn::ord2f(bb.mx[a]))));
       double edge = std::max((radius + std::ldexp(maxabs, -21)) * (1.0 + 1e-5), 1e-30);
+      // the widening ends: edge >= 2^-21 max|coordinate| keeps every floor within 2^22, and a growing edge brings pd and cells down to at most 8 long
+      // before (float)edge overflows - unless an extent itself is not a finite f32, which trips the guard (2) at every edge: such a cloud has no index
+      for (int a = 0; a < 3; a++)
+        if (!std::isfinite(qn::ord2f(bb.mx[a]) - qn::ord2f(bb.mn[a]))) {
+          s->last_error = "cell index: the extent of a cloud overflows f32"; return QN_ERR_CAPACITY;
+        }
       while (!voxel_dims(bb, edge, &g.vd, &cells) || cells >= (1ll << QN_CELL_LEAF_BITS)) edge *= 1.25;
       g.sentinel = (uint32_t)cells; g.nvox = nfin;
     }

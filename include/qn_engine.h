@@ -311,8 +311,12 @@ int  qn_kf_download(qn_kf_store*, int slot, float* xyz_out /* n x 3 packed */);
  * what qn_kf_assemble builds for that list (ids may repeat, within and across submaps).  d_xyz_out[s] / n_out[s] / status[s] per submap
  * (float4, stride 16).  Storage is the store's own batch slot: slots 0/1 and the map slot are never touched.  Valid until the next
  * qn_kf_assemble_batch on this store or its destruction.  Returns QN_OK when the call ran; a submap that is empty after dropping non-finite
- * points gets status QN_ERR_EMPTY_CLOUD and n 0 without failing the others.  PCL's overflow guard is applied per submap from its own box:
- * a tripped submap is its finite points, unfiltered, in concatenation order (qn_kf_last_error carries the warning).  Bad id, non-monotone
+ * points gets status QN_ERR_EMPTY_CLOUD and n 0 without failing the others.  The overflow guard is applied per submap from the box [min, max] of
+ * its own finite points; with inv = 1 / (float)leaf, all in f32, it trips when (1) on any axis floor(min inv) or floor(max inv) is outside
+ * [-2^31, 2^31), or (2) on any axis (max - min) inv is not below 2^63 (infinite included), or (3) PCL's own product of int64((max - min) inv) + 1
+ * over the axes exceeds INT32_MAX, or (4) the cell count, the product of floor(max inv) - floor(min inv) + 1, exceeds INT32_MAX.  (1), (2) and (4)
+ * deviate from pcl::VoxelGrid, which converts out of range and lets its index wrap there; the same rule holds for
+ * qn_kf_assemble and qn_kf_build_map.  A tripped submap is its finite points, unfiltered, in concatenation order (qn_kf_last_error carries the warning).  Bad id, non-monotone
  * seg_off, leaf <= 0 or n_seg == 0: QN_ERR_INVALID_ARG before anything runs.  Two host synchronisations per call.                          */
 int  qn_kf_assemble_batch(qn_kf_store*, const int32_t* ids, const double* poses16, const uint32_t* seg_off, uint32_t n_seg, double leaf,
                           const float** d_xyz_out, uint32_t* n_out, int* status);

@@ -23,20 +23,49 @@ void orc_transform_pcd(const float* xyz, int n, const double* T, float* out) {
   }
 }
 
-// returns the number of output points (<= n); when the leaf grid would overflow 2^31 cells PCL warns and passes the input through unfiltered
+// The overflow guard, one rule shared with the engine (voxel_dims, qn_cloud.hip) and the numpy restatement (voxel_guard, tests/test_kf_map_api.py).
+// mn / mx: the box of the (finite) points; inv = 1 / leaf; all f32.  Tripped (returns 1) when
+//   (1) on any axis floor(min * inv) or floor(max * inv) is outside [-2^31, 2^31)   [deviation from PCL: it converts them to int unchecked]
+//   (2) on any axis (max - min) * inv is not below 2^63, infinite or NaN included   [deviation from PCL: it converts it to int64 unchecked]
+//   (3) pd = product of int64((max - min) * inv) + 1 > INT32_MAX                    [pcl::VoxelGrid::applyFilter's own guard, its own arithmetic]
+//   (4) cells = product of floor(max * inv) - floor(min * inv) + 1 > INT32_MAX      [deviation from PCL: its linear index would wrap]
+// Compared in floating point before any conversion; the products leave at the first factor or partial product above INT32_MAX.
+// Not tripped: minb / divb hold the grid and every leaf index lies in [0, cells).
+static int voxel_guard(const float* mn, const float* mx, float inv, int* minb, int* divb) {
+  const float two31 = 2147483648.0f, two63 = 9223372036854775808.0f;
+  int64_t pd = 1, cells = 1;
+  for (int d = 0; d < 3; d++) {
+    const float lo = std::floor(mn[d] * inv), hi = std::floor(mx[d] * inv), ext = (mx[d] - mn[d]) * inv;
+    if (!(lo >= -two31 && lo < two31 && hi >= -two31 && hi < two31)) return 1;
+    if (!(ext < two63)) return 1;
+    const int64_t div = (int64_t)hi - (int64_t)lo + 1, pdf = (int64_t)ext + 1;
+    if (pdf > (int64_t)INT32_MAX || div > (int64_t)INT32_MAX) return 1;
+    pd *= pdf; cells *= div;
+    if (pd > (int64_t)INT32_MAX || cells > (int64_t)INT32_MAX) return 1;
+    minb[d] = (int)lo; divb[d] = (int)div;
+  }
+  return 0;
+}
+static void bounding_box(const float* xyz, int n, float* mn, float* mx) {
+  for (int d = 0; d < 3; d++) mn[d] = mx[d] = xyz[d];
+  for (int i = 0; i < n; i++) for (int d = 0; d < 3; d++) { mn[d] = std::min(mn[d], xyz[3 * i + d]); mx[d] = std::max(mx[d], xyz[3 * i + d]); }
+}
+// 1 when the guard trips for this cloud (finite points only) at this leaf, else 0
+int orc_voxel_guard(const float* xyz, int n, float leaf) {
+  if (n == 0) return 0;
+  float mn[3], mx[3]; int minb[3], divb[3];
+  bounding_box(xyz, n, mn, mx);
+  return voxel_guard(mn, mx, 1.0f / leaf, minb, divb);
+}
+
+// returns the number of output points (<= n); when the guard trips PCL warns ("Leaf size is too small for the input dataset. Integer indices
+// would overflow.") and passes the input through unfiltered: output = *input_
 int orc_voxel_grid(const float* xyz, int n, float leaf, float* out) {
   if (n == 0) return 0;
   const float inv = 1.0f / leaf;
-  float mn[3] = {xyz[0], xyz[1], xyz[2]}, mx[3] = {xyz[0], xyz[1], xyz[2]};
-  for (int i = 0; i < n; i++) for (int d = 0; d < 3; d++) { mn[d] = std::min(mn[d], xyz[3 * i + d]); mx[d] = std::max(mx[d], xyz[3 * i + d]); }
-  int minb[3], divb[3];
-  for (int d = 0; d < 3; d++) { minb[d] = (int)std::floor(mn[d] * inv); const int maxb = (int)std::floor(mx[d] * inv); divb[d] = maxb - minb[d] + 1; }
-  // pcl::VoxelGrid::applyFilter's overflow guard, in PCL's own arithmetic: dx = int64((max - min) * inverse_leaf) + 1 per axis (f32
-  // product), "Leaf size is too small for the input dataset. Integer indices would overflow." -> output = *input_ (unfiltered).
-  {
-    const int64_t dx = (int64_t)((mx[0] - mn[0]) * inv) + 1, dy = (int64_t)((mx[1] - mn[1]) * inv) + 1, dz = (int64_t)((mx[2] - mn[2]) * inv) + 1;
-    if (dx * dy * dz > (int64_t)INT32_MAX) { std::memcpy(out, xyz, sizeof(float) * 3 * (size_t)n); return n; }
-  }
+  float mn[3], mx[3]; int minb[3], divb[3];
+  bounding_box(xyz, n, mn, mx);
+  if (voxel_guard(mn, mx, inv, minb, divb)) { std::memcpy(out, xyz, sizeof(float) * 3 * (size_t)n); return n; }
   std::vector<uint64_t> key(n);
   for (int i = 0; i < n; i++) {
     const int i0 = (int)(std::floor(xyz[3 * i] * inv) - (float)minb[0]);

@@ -239,6 +239,12 @@ def voxel_grid(xyz, leaf):
     return out[:m].copy()
 
 
+def voxel_guard(xyz, leaf):
+    """True when voxel_grid's overflow guard trips for this cloud (finite points) at this leaf: voxel_grid then returns the cloud unfiltered"""
+    xyz = _f32(xyz)
+    return bool(lib().orc_voxel_guard(_p(xyz), C.c_int(len(xyz)), C.c_float(leaf)))
+
+
 def assemble_submap(keyframes, poses, idxs, leaf):
     """setSrcAndDstCloud's inner loop (loop_closure.cpp:70-107): transformPcd of each keyframe, concatenate, voxelize."""
     parts = [transform_pcd(keyframes[i], poses[i]) for i in idxs]

@@ -12,22 +12,43 @@ MAP_SYMBOLS = ["qn_kf_add_xyzi", "qn_kf_build_map", "qn_kf_download_map"]
 INT32_MAX = 2 ** 31 - 1
 
 
+def voxel_guard(mn, mx, leaf):
+    """The overflow guard from the box of the finite points (f32 mn, mx) -> (tripped, minb, div), minb / div as Python ints (None when tripped).
+    The one rule of the engine (voxel_dims, qn_cloud.hip) and the oracle (voxel_guard, oracle/cloud_oracle.cpp), inv = 1 / float32(leaf), all f32: tripped when
+      (1) on any axis floor(min * inv) or floor(max * inv) is outside [-2^31, 2^31)      (deviation from PCL, which converts unchecked)
+      (2) on any axis (max - min) * inv is not below 2^63, infinite or NaN included      (deviation from PCL, which converts unchecked)
+      (3) pd = product of int64((max - min) * inv) + 1 > INT32_MAX                       (PCL's own guard)
+      (4) cells = product of floor(max * inv) - floor(min * inv) + 1 > INT32_MAX         (deviation from PCL, whose index wraps)
+    Compared in floating point before any conversion; the integers are Python's, which do not overflow.  An f32 product or difference that
+    overflows to infinity is IEEE arithmetic, not an error: it trips (1) or (2)."""
+    mn = np.asarray(mn, np.float32); mx = np.asarray(mx, np.float32)
+    with np.errstate(over="ignore", invalid="ignore"):                # inf and inf * 0 = NaN are values the rule names
+        inv = np.float32(1.0) / np.float32(leaf)
+        lo, hi, ext = np.floor(mn * inv), np.floor(mx * inv), (mx - mn) * inv
+    two31, two63 = np.float32(2.0 ** 31), np.float32(2.0 ** 63)
+    if not ((lo >= -two31) & (lo < two31) & (hi >= -two31) & (hi < two31)).all() or not (ext < two63).all():
+        return True, None, None
+    minb = [int(v) for v in lo]; div = [int(h) - int(l) + 1 for l, h in zip(lo, hi)]
+    pdf = [int(e) + 1 for e in ext]
+    if pdf[0] * pdf[1] * pdf[2] > INT32_MAX or div[0] * div[1] * div[2] > INT32_MAX:
+        return True, None, None
+    return False, minb, div
+
+
 def voxel_grid_xyzi(p4, leaf):
     """pcl::VoxelGrid (downsample_all_data_) on an (n, 4) float32 x y z intensity cloud, as the engine fixes it -> ((m, 4) float32, overflowed).
     Leaf index floor(p * inv) - min_b in f32; output in ascending leaf index; inside a leaf, f32 sums in ascending input order, / (float)count.
-    Non-finite xyz is dropped (a non-dense cloud); a NaN intensity on a finite point poisons its leaf's intensity.  PCL's overflow guard
-    (f32 product, int64 cast) returns the input unfiltered, non-finite points included."""
+    Non-finite xyz is dropped (a non-dense cloud); a NaN intensity on a finite point poisons its leaf's intensity.  The overflow guard
+    (voxel_guard) returns the input unfiltered, non-finite points included."""
     p4 = np.ascontiguousarray(p4, dtype=np.float32)
     q = p4[np.isfinite(p4[:, :3]).all(1)]
     if len(q) == 0:
         return np.zeros((0, 4), np.float32), False
     inv = np.float32(1.0) / np.float32(leaf)
-    mn, mx = q[:, :3].min(0), q[:, :3].max(0)
-    minb = np.floor(mn * inv).astype(np.int64); maxb = np.floor(mx * inv).astype(np.int64)
-    div = maxb - minb + 1
-    pd = int(np.prod(((mx - mn) * inv).astype(np.int64) + 1))
-    if pd > INT32_MAX or int(np.prod(div)) > INT32_MAX:
+    tripped, minb, div = voxel_guard(q[:, :3].min(0), q[:, :3].max(0), leaf)
+    if tripped:
         return p4.copy(), True
+    minb = np.array(minb, np.int64); div = np.array(div, np.int64)
     ijk = (np.floor(q[:, :3] * inv) - minb.astype(np.float32)).astype(np.int64)
     idx = ijk[:, 0] + ijk[:, 1] * div[0] + ijk[:, 2] * (div[0] * div[1])
     order = np.argsort(idx, kind="stable")
