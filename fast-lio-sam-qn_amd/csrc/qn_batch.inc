@@ -118,6 +118,15 @@ bool batch_supported(const qn_ctx* c) {      // everything else takes the classi
          c->tick_tb == 512 && c->tick_occ >= 4 && !c->dbg_counters;
 }
 
+// the context's argument arena of the lane launches (pinned + device, 4 MB each), made on first use
+int lane_args_arena(qn_ctx* c) {
+  if (c->args_h) return QN_OK;
+  c->args_cap = (size_t)4 << 20;
+  HIPCHK(c, hipHostMalloc(&c->args_h, c->args_cap, hipHostMallocDefault));
+  HIPCHK(c, hipMalloc(&c->args_d, c->args_cap));
+  return QN_OK;
+}
+
 int batch_ensure_lanes(qn_ctx* c) {
   HIPCHK(c, hipSetDevice(c->device));
   const int B = std::max(1, std::min(c->batch_lanes, 64));
@@ -137,11 +146,7 @@ int batch_ensure_lanes(qn_ctx* c) {
     }
     c->lanes.push_back(l);
   }
-  if (!c->args_h) {
-    c->args_cap = (size_t)4 << 20;
-    HIPCHK(c, hipHostMalloc(&c->args_h, c->args_cap, hipHostMallocDefault));
-    HIPCHK(c, hipMalloc(&c->args_d, c->args_cap));
-  }
+  { const int rc = lane_args_arena(c); if (rc != QN_OK) return rc; }
   for (qn_ctx* l : c->lanes) {            // every lane registers with the owner's parameters and knobs, as a batch member (no second stream, no persistent launches)
     if (l == c) continue;
     if (l->params.k_correspondences != c->params.k_correspondences) l->cloud[0].has_cov = l->cloud[1].has_cov = false;

@@ -19,7 +19,7 @@
 #include <algorithm>
 #include "../../include/qn_engine.h"
 #include "qn_util_kernels.cuh"
-#include "qn_kf_internal.h"
+#include "qn_kf_buf.h"
 
 namespace qn {
 
@@ -252,49 +252,24 @@ __global__ void k_batch_gather(const unsigned long long* __restrict__ keys, uint
 
 }  // namespace qn
 
-// a device (or pinned host) buffer of `cap` elements, grown only by dev_grow / pin_grow (contents not kept), freed with the store
-template <typename T> struct Buf { T* p = nullptr; size_t cap = 0; };
-
 struct qn_kf_store {
   int device = 0; hipStream_t stream = nullptr;
   std::vector<float4*> clouds; std::vector<uint32_t> sizes; std::vector<uint8_t> has_i;   // has_i: added by qn_kf_add_xyzi (.w = intensity)
-  Buf<char> staging;                                                                         // qn_kf_add's upload
+  DevBuf<char> staging;                                                                         // qn_kf_add's upload
   // scratch of the voxel-grid pipeline (voxel_submaps), shared by every entry point: per point, per scan block / radix histogram entry,
   // per tile (its box), per submap (box, leaf range); the call's tables (Tables) in one device buffer, uploaded from one pinned buffer
-  Buf<float4> concat; Buf<unsigned long long> keys, keys_alt; Buf<uint32_t> flag, pos, heads, ends;
-  Buf<uint32_t> sums, hist, hist_sums; Buf<qn::BBoxOut> tile_box, seg_box; Buf<uint32_t> seg_res;
-  Buf<char> tab, tab_host; Buf<qn::BBoxOut> seg_box_host; Buf<uint32_t> seg_res_host;        // *_host: pinned
+  DevBuf<float4> concat; DevBuf<unsigned long long> keys, keys_alt; DevBuf<uint32_t> flag, pos, heads, ends;
+  DevBuf<uint32_t> sums, hist, hist_sums; DevBuf<qn::BBoxOut> tile_box, seg_box; DevBuf<uint32_t> seg_res;
+  DevBuf<char> tab; PinBuf<char> tab_host; PinBuf<qn::BBoxOut> seg_box_host; PinBuf<uint32_t> seg_res_host;
   // the output slots: qn_kf_assemble's 0 / 1, the corrected global map, qn_kf_assemble_batch's (all submaps in one buffer)
-  Buf<float4> out[2]; uint32_t out_n[2] = {0, 0};
-  Buf<float4> map; uint32_t map_n = 0;
-  Buf<float4> bt_out; std::vector<const float4*> bt_ptr; std::vector<uint32_t> bt_n;
-  // scratch of other translation units (the ray-caster, qn_sim.hip): see qn_kf_internal.h
-  void* int_scratch[QN_KF_INT_SCRATCH] = {}; size_t int_scratch_cap[QN_KF_INT_SCRATCH] = {}; void* int_pinned = nullptr; size_t int_pinned_cap = 0;
+  DevBuf<float4> out[2]; uint32_t out_n[2] = {0, 0};
+  DevBuf<float4> map; uint32_t map_n = 0;
+  DevBuf<float4> bt_out; std::vector<const float4*> bt_ptr; std::vector<uint32_t> bt_n;
+  // scratch of other translation units (the ray-caster, qn_sim.hip), in bytes, sized exactly as asked: see qn_kf_internal.h
+  DevBuf<char> int_scratch[QN_KF_INT_SCRATCH]; PinBuf<char> int_pinned;
   void* ext[QN_KF_INT_EXT] = {}; qn_kf_int_release_fn ext_release[QN_KF_INT_EXT] = {};      // state of other translation units (qn_sc.hip)
   std::string last_error;
 };
-#define KFCHK(s, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { (s)->last_error = std::string(#call) + " -> " + hipGetErrorString(e_); return QN_ERR_HIP; } } while (0)
-
-// b grown to at least `need` elements (by half again); false when the allocation failed (last_error says why, the caller returns QN_ERR_HIP)
-template <typename T> static bool dev_grow(qn_kf_store* s, Buf<T>& b, size_t need) {
-  if (need <= b.cap) return true;
-  (void)hipFree(b.p); b.p = nullptr; b.cap = 0;
-  const hipError_t e = hipMalloc((void**)&b.p, sizeof(T) * (need + need / 2));
-  if (e != hipSuccess) { b.p = nullptr; s->last_error = std::string("hipMalloc -> ") + hipGetErrorString(e); return false; }
-  b.cap = need + need / 2;
-  return true;
-}
-template <typename T> static bool pin_grow(qn_kf_store* s, Buf<T>& b, size_t need) {
-  if (need <= b.cap) return true;
-  if (b.p) (void)hipHostFree(b.p);
-  b.p = nullptr; b.cap = 0;
-  const hipError_t e = hipHostMalloc((void**)&b.p, sizeof(T) * (need + need / 2), hipHostMallocDefault);
-  if (e != hipSuccess) { b.p = nullptr; s->last_error = std::string("hipHostMalloc -> ") + hipGetErrorString(e); return false; }
-  b.cap = need + need / 2;
-  return true;
-}
-template <typename T> static void dev_free(Buf<T>& b) { (void)hipFree(b.p); b = Buf<T>{}; }
-
 extern "C" int qn_kf_store_create(int device, qn_kf_store** out) {
   if (!out) return QN_ERR_INVALID_ARG;
   *out = nullptr;
@@ -309,27 +284,21 @@ extern "C" void qn_kf_store_destroy(qn_kf_store* s) {
   if (!s) return;
   (void)hipSetDevice(s->device); if (s->stream) (void)hipStreamSynchronize(s->stream);
   for (float4* p : s->clouds) (void)hipFree(p);
-  dev_free(s->staging); dev_free(s->concat); dev_free(s->keys); dev_free(s->keys_alt); dev_free(s->flag); dev_free(s->pos); dev_free(s->heads); dev_free(s->ends);
-  dev_free(s->sums); dev_free(s->hist); dev_free(s->hist_sums); dev_free(s->tile_box); dev_free(s->seg_box); dev_free(s->seg_res); dev_free(s->tab);
-  dev_free(s->out[0]); dev_free(s->out[1]); dev_free(s->map); dev_free(s->bt_out);
   for (int k = 0; k < QN_KF_INT_EXT; k++) if (s->ext[k] && s->ext_release[k]) s->ext_release[k](s->ext[k]);
-  for (void* p : s->int_scratch) (void)hipFree(p);
-  if (s->int_pinned) (void)hipHostFree(s->int_pinned);
-  if (s->tab_host.p) (void)hipHostFree(s->tab_host.p); if (s->seg_box_host.p) (void)hipHostFree(s->seg_box_host.p); if (s->seg_res_host.p) (void)hipHostFree(s->seg_res_host.p);
   if (s->stream) (void)hipStreamDestroy(s->stream);
-  delete s;
+  delete s;                                                          // (every buffer of the store goes with its member)
 }
 extern "C" const char* qn_kf_last_error(const qn_kf_store* s) { return s ? s->last_error.c_str() : "null store"; }
 
 // upload one keyframe cloud (sensor frame) - PosePcd::pcd_ - and keep it resident; ioff < 0: xyz only (.w = 1), else the intensity's byte offset
 static int kf_add(qn_kf_store* s, const float* xyz, uint32_t n, uint32_t stride, int ioff, int32_t* id_out) {
-  KFCHK(s, hipSetDevice(s->device));
+  QN_KFCHK(s, hipSetDevice(s->device));
   float4* d = nullptr;
   if (n) {
     const size_t bytes = (size_t)(n - 1) * stride + (ioff < 0 ? 12 : std::max(12, ioff + 4));
-    if (!dev_grow(s, s->staging, bytes)) return QN_ERR_HIP;
-    KFCHK(s, hipMalloc(&d, sizeof(float4) * n));
-    KFCHK(s, hipMemcpyAsync(s->staging.p, xyz, bytes, hipMemcpyHostToDevice, s->stream));
+    if (!s->staging.grow(s, bytes)) return QN_ERR_HIP;
+    QN_KFCHK(s, hipMalloc(&d, sizeof(float4) * n));
+    QN_KFCHK(s, hipMemcpyAsync(s->staging.p, xyz, bytes, hipMemcpyHostToDevice, s->stream));
     if (ioff < 0) hipLaunchKernelGGL(qn::k_pack_points, dim3((n + 255) / 256), dim3(256), 0, s->stream, s->staging.p, stride, n, d);
     else hipLaunchKernelGGL(qn::k_pack_xyzi, dim3((n + 255) / 256), dim3(256), 0, s->stream, (const char*)s->staging.p, stride, (uint32_t)ioff, n, d);
     const hipError_t e = hipStreamSynchronize(s->stream);
@@ -356,9 +325,9 @@ static bool device_layout_ok(uint32_t stride, int32_t ioff) { return ioff < 0 ? 
 int qn_kf_int_copy_async(qn_kf_store* s, const void* d_pts, uint32_t n, uint32_t stride, int32_t ioff, float4** out) {
   *out = nullptr;
   if (!n) return QN_OK;
-  KFCHK(s, hipSetDevice(s->device));
+  QN_KFCHK(s, hipSetDevice(s->device));
   float4* d = nullptr;
-  KFCHK(s, hipMalloc(&d, sizeof(float4) * n));
+  QN_KFCHK(s, hipMalloc(&d, sizeof(float4) * n));
   if (ioff < 0) hipLaunchKernelGGL(qn::k_pack_points, dim3((n + 255) / 256), dim3(256), 0, s->stream, (const char*)d_pts, stride, n, d);
   else hipLaunchKernelGGL(qn::k_pack_xyzi, dim3((n + 255) / 256), dim3(256), 0, s->stream, (const char*)d_pts, stride, (uint32_t)ioff, n, d);
   const hipError_t e = hipGetLastError();
@@ -377,13 +346,8 @@ hipStream_t qn_kf_int_stream(const qn_kf_store* s) { return s->stream; }
 size_t qn_kf_int_count(const qn_kf_store* s) { return s->clouds.size(); }
 void qn_kf_int_set_error(qn_kf_store* s, const char* msg) { s->last_error = msg; }
 void* qn_kf_int_scratch(qn_kf_store* s, int which, size_t bytes) {
-  if (which < 0 || which >= QN_KF_INT_SCRATCH) return nullptr;
-  if (bytes > s->int_scratch_cap[which]) {
-    (void)hipFree(s->int_scratch[which]); s->int_scratch[which] = nullptr; s->int_scratch_cap[which] = 0;
-    if (hipMalloc(&s->int_scratch[which], bytes) != hipSuccess) { s->int_scratch[which] = nullptr; return nullptr; }
-    s->int_scratch_cap[which] = bytes;
-  }
-  return s->int_scratch[which];
+  if (which < 0 || which >= QN_KF_INT_SCRATCH || !s->int_scratch[which].grow(s, bytes, true)) return nullptr;
+  return s->int_scratch[which].p;
 }
 const float4* qn_kf_int_keyframe(const qn_kf_store* s, int32_t id, uint32_t* n) { *n = s->sizes[id]; return s->clouds[id]; }
 bool qn_kf_int_has_intensity(const qn_kf_store* s, int32_t id) { return s->has_i[id] != 0; }
@@ -393,19 +357,11 @@ void qn_kf_int_set_ext(qn_kf_store* s, int which, void* p, qn_kf_int_release_fn 
   if (s->ext[which] && s->ext_release[which] && s->ext[which] != p) s->ext_release[which](s->ext[which]);
   s->ext[which] = p; s->ext_release[which] = release;
 }
-void* qn_kf_int_pinned(qn_kf_store* s, size_t bytes) {
-  if (bytes > s->int_pinned_cap) {
-    if (s->int_pinned) (void)hipHostFree(s->int_pinned);
-    s->int_pinned = nullptr; s->int_pinned_cap = 0;
-    if (hipHostMalloc(&s->int_pinned, bytes, hipHostMallocDefault) != hipSuccess) { s->int_pinned = nullptr; return nullptr; }
-    s->int_pinned_cap = bytes;
-  }
-  return s->int_pinned;
-}
+void* qn_kf_int_pinned(qn_kf_store* s, size_t bytes) { return s->int_pinned.grow(s, bytes, true) ? s->int_pinned.p : nullptr; }
 extern "C" int qn_kf_add_device(qn_kf_store* s, const float* d_pts, uint32_t n, uint32_t stride, int32_t ioff, int32_t* id_out) {
   if (!s || !id_out || (n && !d_pts) || !device_layout_ok(stride, ioff) || ((uintptr_t)d_pts & 3)) return QN_ERR_INVALID_ARG;
   if (n) {        // the records must lie inside one device allocation of this store's device: a host pointer here would fault the GPU
-    KFCHK(s, hipSetDevice(s->device));
+    QN_KFCHK(s, hipSetDevice(s->device));
     hipPointerAttribute_t a{};
     if (hipPointerGetAttributes(&a, d_pts) != hipSuccess || a.type != hipMemoryTypeDevice || a.device != s->device) { (void)hipGetLastError(); return QN_ERR_INVALID_ARG; }
     hipDeviceptr_t base = nullptr; size_t size = 0;
@@ -427,8 +383,8 @@ extern "C" int qn_kf_download_keyframe(qn_kf_store* s, int32_t id, float* xyzi_o
   if (!s || id < 0 || (size_t)id >= s->clouds.size() || (s->sizes[id] && !xyzi_out)) return QN_ERR_INVALID_ARG;
   const uint32_t n = s->sizes[id];
   if (!n) return QN_OK;
-  KFCHK(s, hipSetDevice(s->device));
-  KFCHK(s, hipMemcpy(xyzi_out, s->clouds[id], sizeof(float4) * n, hipMemcpyDeviceToHost));
+  QN_KFCHK(s, hipSetDevice(s->device));
+  QN_KFCHK(s, hipMemcpy(xyzi_out, s->clouds[id], sizeof(float4) * n, hipMemcpyDeviceToHost));
   return QN_OK;
 }
 
@@ -497,7 +453,7 @@ static std::vector<SortGroup> sort_groups(const std::vector<int>& lbits, uint32_
 static bool sort_scratch(qn_kf_store* s, const std::vector<SortGroup>& groups, const std::vector<uint32_t>& p0) {
   size_t hn = 0;
   for (const SortGroup& gr : groups) hn = std::max<size_t>(hn, 256 * (size_t)radix_blocks(p0[gr.s1] - p0[gr.s0]));
-  return dev_grow(s, s->hist, hn + 1) && dev_grow(s, s->hist_sums, scan_blocks(hn));
+  return s->hist.grow(s, hn + 1) && s->hist_sums.grow(s, scan_blocks(hn));
 }
 // stable LSD passes over each group's (segment, leaf) bits only, on its own point range of s->keys; every group's result ends in one buffer, *fin
 static int sort_segments(qn_kf_store* s, const std::vector<SortGroup>& groups, const std::vector<uint32_t>& p0, unsigned long long** fin_out) {
@@ -520,7 +476,7 @@ static int sort_segments(qn_kf_store* s, const std::vector<SortGroup>& groups, c
     }
     unsigned long long* base = sorted - gp0;
     if (!fin) fin = base;
-    else if (base != fin) KFCHK(s, hipMemcpyAsync(fin + gp0, sorted, sizeof(unsigned long long) * gn, hipMemcpyDeviceToDevice, st));
+    else if (base != fin) QN_KFCHK(s, hipMemcpyAsync(fin + gp0, sorted, sizeof(unsigned long long) * gn, hipMemcpyDeviceToDevice, st));
   }
   *fin_out = fin;
   return QN_OK;
@@ -540,9 +496,8 @@ struct SubmapOut { const float4* ptr; uint32_t n; int status; };
 struct Tables {
   size_t pose, kf, blk, kseg, toff, seg, end;
   Tables(uint32_t count, size_t tiles, uint32_t n_seg) {
-    const auto up = [](size_t b) { return (b + 15) & ~(size_t)15; };
-    pose = 0; kf = up(sizeof(double) * 16 * count); blk = up(kf + sizeof(qn::MapKf) * count); kseg = up(blk + 4 * tiles);
-    toff = up(kseg + 4 * (size_t)count); seg = up(toff + 4 * ((size_t)n_seg + 1)); end = seg + sizeof(qn::BatchSeg) * n_seg;
+    pose = 0; kf = qn_up16(sizeof(double) * 16 * count); blk = qn_up16(kf + sizeof(qn::MapKf) * count); kseg = qn_up16(blk + 4 * tiles);
+    toff = qn_up16(kseg + 4 * (size_t)count); seg = qn_up16(toff + 4 * ((size_t)n_seg + 1)); end = seg + sizeof(qn::BatchSeg) * n_seg;
   }
 };
 struct VoxelNotes { bool nonfinite, tripped; };      // a voxelized or tripped submap had non-finite points / some submap tripped the guard
@@ -554,7 +509,7 @@ static std::vector<VoxSrc> sources_of(const qn_kf_store* s, const int32_t* ids, 
   return v;
 }
 static int voxel_submaps(qn_kf_store* s, const VoxSrc* src, const double* poses, const uint32_t* seg_off, uint32_t n_seg, double leaf,
-                         bool carry_intensity, bool trip_whole, Buf<float4>& out, SubmapOut* res, VoxelNotes* notes) {
+                         bool carry_intensity, bool trip_whole, DevBuf<float4>& out, SubmapOut* res, VoxelNotes* notes) {
   const uint32_t e0 = seg_off[0], count = seg_off[n_seg] - e0;
   size_t total = 0, tiles = 0;
   for (uint32_t j = e0; j < e0 + count; j++) { total += src[j].n; tiles += tiles_of(src[j].n); }
@@ -562,13 +517,13 @@ static int voxel_submaps(qn_kf_store* s, const VoxSrc* src, const double* poses,
   *notes = VoxelNotes{false, false};
   if (total >= 0xffffffffull) return QN_ERR_CAPACITY;
   if (total == 0) return QN_OK;
-  KFCHK(s, hipSetDevice(s->device));
+  QN_KFCHK(s, hipSetDevice(s->device));
   const uint32_t n = (uint32_t)total, nt = (uint32_t)tiles;
   const Tables tb(count, tiles, n_seg);
-  if (!dev_grow(s, s->concat, n) || !dev_grow(s, s->keys, n) || !dev_grow(s, s->keys_alt, n) || !dev_grow(s, s->flag, n) || !dev_grow(s, s->pos, n + 1) ||
-      !dev_grow(s, s->heads, n) || !dev_grow(s, s->ends, n) || !dev_grow(s, s->sums, scan_blocks(n)) || !dev_grow(s, s->tile_box, nt) ||
-      !dev_grow(s, s->seg_box, n_seg) || !dev_grow(s, s->seg_res, 2 * (size_t)n_seg) || !dev_grow(s, s->tab, tb.end) || !pin_grow(s, s->tab_host, tb.end) ||
-      !pin_grow(s, s->seg_box_host, n_seg) || !pin_grow(s, s->seg_res_host, 2 * (size_t)n_seg)) return QN_ERR_HIP;
+  if (!s->concat.grow(s, n) || !s->keys.grow(s, n) || !s->keys_alt.grow(s, n) || !s->flag.grow(s, n) || !s->pos.grow(s, n + 1) ||
+      !s->heads.grow(s, n) || !s->ends.grow(s, n) || !s->sums.grow(s, scan_blocks(n)) || !s->tile_box.grow(s, nt) ||
+      !s->seg_box.grow(s, n_seg) || !s->seg_res.grow(s, 2 * (size_t)n_seg) || !s->tab.grow(s, tb.end) || !s->tab_host.grow(s, tb.end) ||
+      !s->seg_box_host.grow(s, n_seg) || !s->seg_res_host.grow(s, 2 * (size_t)n_seg)) return QN_ERR_HIP;
   // the tables in pinned memory (host, O(count + tiles)): poses, keyframe rows, tile -> keyframe, keyframe -> submap, each submap's tile range
   char* h = s->tab_host.p;
   qn::MapKf* kfs = (qn::MapKf*)(h + tb.kf); uint32_t* blk = (uint32_t*)(h + tb.blk); uint32_t* kseg = (uint32_t*)(h + tb.kseg); uint32_t* toff = (uint32_t*)(h + tb.toff);
@@ -586,15 +541,15 @@ static int voxel_submaps(qn_kf_store* s, const VoxSrc* src, const double* poses,
   }
   toff[n_seg] = b0; p0[n_seg] = off;
   hipStream_t st = s->stream;
-  KFCHK(s, hipMemcpyAsync(s->tab.p, h, tb.seg, hipMemcpyHostToDevice, st));
+  QN_KFCHK(s, hipMemcpyAsync(s->tab.p, h, tb.seg, hipMemcpyHostToDevice, st));
   // transformPcd + operator+= of every listed keyframe of every submap (loop_closure.cpp:76,83,89,92,102), per-tile boxes, per-submap reduce
   const char* d = s->tab.p;
   const qn::MapKf* dkf = (const qn::MapKf*)(d + tb.kf); const uint32_t* dblk = (const uint32_t*)(d + tb.blk); const uint32_t* dks = (const uint32_t*)(d + tb.kseg);
   const qn::BatchSeg* dsg = (const qn::BatchSeg*)(d + tb.seg);
   hipLaunchKernelGGL(qn::k_map_transform, dim3(nt), dim3(QN_BLOCK), 0, st, dkf, dblk, (const double*)(d + tb.pose), s->concat.p, s->tile_box.p);
   hipLaunchKernelGGL(qn::k_seg_bbox_reduce, dim3(n_seg), dim3(QN_BLOCK), 0, st, (const qn::BBoxOut*)s->tile_box.p, (const uint32_t*)(d + tb.toff), s->seg_box.p);
-  KFCHK(s, hipMemcpyAsync(s->seg_box_host.p, s->seg_box.p, sizeof(qn::BBoxOut) * n_seg, hipMemcpyDeviceToHost, st));
-  KFCHK(s, hipStreamSynchronize(st));                               // sync 1 of 2: each submap's box sizes its grid
+  QN_KFCHK(s, hipMemcpyAsync(s->seg_box_host.p, s->seg_box.p, sizeof(qn::BBoxOut) * n_seg, hipMemcpyDeviceToHost, st));
+  QN_KFCHK(s, hipStreamSynchronize(st));                            // sync 1 of 2: each submap's box sizes its grid
   // per submap: pcl::VoxelGrid's grid and overflow guard (voxel_dims), its sentinel leaf and the key bits it needs
   qn::BatchSeg* sg = (qn::BatchSeg*)(h + tb.seg); std::vector<int> lbits(n_seg); std::vector<uint32_t> nfin(n_seg), ntrip(n_seg, 0), trip_off(n_seg, 0);
   std::vector<uint8_t> live(n_seg, 0);
@@ -614,8 +569,8 @@ static int voxel_submaps(qn_kf_store* s, const VoxSrc* src, const double* poses,
   }
   if (sum_vox + sum_trip == 0) return QN_OK;                        // every submap empty
   const std::vector<SortGroup> groups = sort_groups(lbits, n_seg, sg, p0);
-  if (!dev_grow(s, out, sum_vox + sum_trip) || !sort_scratch(s, groups, p0)) return QN_ERR_HIP;
-  KFCHK(s, hipMemcpyAsync(s->tab.p + tb.seg, sg, tb.end - tb.seg, hipMemcpyHostToDevice, st));
+  if (!out.grow(s, sum_vox + sum_trip) || !sort_scratch(s, groups, p0)) return QN_ERR_HIP;
+  QN_KFCHK(s, hipMemcpyAsync(s->tab.p + tb.seg, sg, tb.end - tb.seg, hipMemcpyHostToDevice, st));
   hipLaunchKernelGGL(qn::k_batch_keys, dim3(nt * QN_MAP_ITEMS), dim3(QN_BLOCK), 0, st, dkf, dblk, dks, dsg, (const float4*)s->concat.p, s->keys.p);
   unsigned long long* fin = nullptr;
   { const int src = sort_segments(s, groups, p0, &fin); if (src != QN_OK) return src; }
@@ -636,13 +591,13 @@ static int voxel_submaps(qn_kf_store* s, const VoxSrc* src, const double* poses,
   for (uint32_t t = 0; t < n_seg; t++) {                            // rare: tripped guards, passed through behind the leaves
     if (!live[t] || !sg[t].tripped) continue;
     float4* dst = out.p + sum_vox + trip_off[t];
-    if (trip_whole) KFCHK(s, hipMemcpyAsync(dst, s->concat.p + p0[t], sizeof(float4) * ntrip[t], hipMemcpyDeviceToDevice, st));
+    if (trip_whole) QN_KFCHK(s, hipMemcpyAsync(dst, s->concat.p + p0[t], sizeof(float4) * ntrip[t], hipMemcpyDeviceToDevice, st));
     else hipLaunchKernelGGL(qn::k_batch_gather, dim3((ntrip[t] + 255) / 256), dim3(256), 0, st, (const unsigned long long*)fin + p0[t], ntrip[t], (const float4*)s->concat.p, dst);
   }
   hipLaunchKernelGGL(qn::k_batch_counts, dim3((n_seg + 255) / 256), dim3(256), 0, st, dsg, n_seg, (const uint32_t*)s->pos.p, s->seg_res.p);
-  KFCHK(s, hipMemcpyAsync(s->seg_res_host.p, s->seg_res.p, sizeof(uint32_t) * 2 * n_seg, hipMemcpyDeviceToHost, st));
-  KFCHK(s, hipGetLastError());
-  KFCHK(s, hipStreamSynchronize(st));                               // sync 2 of 2: each submap's first leaf and leaf count
+  QN_KFCHK(s, hipMemcpyAsync(s->seg_res_host.p, s->seg_res.p, sizeof(uint32_t) * 2 * n_seg, hipMemcpyDeviceToHost, st));
+  QN_KFCHK(s, hipGetLastError());
+  QN_KFCHK(s, hipStreamSynchronize(st));                            // sync 2 of 2: each submap's first leaf and leaf count
   for (uint32_t t = 0; t < n_seg; t++) {
     if (!live[t]) continue;
     const bool tr = sg[t].tripped != 0;
@@ -666,11 +621,11 @@ int qn_kf_int_cell_index(qn_kf_store* s, const float4* const* clouds, const uint
   *points = nullptr; *keys = nullptr;
   if (total >= 0xffffffffull) return QN_ERR_CAPACITY;
   if (total == 0) return QN_OK;
-  KFCHK(s, hipSetDevice(s->device));
+  QN_KFCHK(s, hipSetDevice(s->device));
   const uint32_t n = (uint32_t)total, nt = (uint32_t)tiles;
   const Tables tb(count, tiles, count);
-  if (!dev_grow(s, s->concat, n) || !dev_grow(s, s->keys, n) || !dev_grow(s, s->keys_alt, n) || !dev_grow(s, s->tile_box, nt) || !dev_grow(s, s->seg_box, count) ||
-      !dev_grow(s, s->tab, tb.end) || !pin_grow(s, s->tab_host, tb.end) || !pin_grow(s, s->seg_box_host, count)) return QN_ERR_HIP;
+  if (!s->concat.grow(s, n) || !s->keys.grow(s, n) || !s->keys_alt.grow(s, n) || !s->tile_box.grow(s, nt) || !s->seg_box.grow(s, count) ||
+      !s->tab.grow(s, tb.end) || !s->tab_host.grow(s, tb.end) || !s->seg_box_host.grow(s, count)) return QN_ERR_HIP;
   char* h = s->tab_host.p;
   qn::MapKf* kfs = (qn::MapKf*)(h + tb.kf); uint32_t* blk = (uint32_t*)(h + tb.blk); uint32_t* kseg = (uint32_t*)(h + tb.kseg); uint32_t* toff = (uint32_t*)(h + tb.toff);
   double* pose = (double*)(h + tb.pose);
@@ -686,15 +641,15 @@ int qn_kf_int_cell_index(qn_kf_store* s, const float4* const* clouds, const uint
   }
   toff[count] = b0; p0[count] = off;
   hipStream_t st = s->stream;
-  KFCHK(s, hipMemcpyAsync(s->tab.p, h, tb.seg, hipMemcpyHostToDevice, st));
+  QN_KFCHK(s, hipMemcpyAsync(s->tab.p, h, tb.seg, hipMemcpyHostToDevice, st));
   const char* d = s->tab.p;
   const qn::MapKf* dkf = (const qn::MapKf*)(d + tb.kf); const uint32_t* dblk = (const uint32_t*)(d + tb.blk); const uint32_t* dks = (const uint32_t*)(d + tb.kseg);
   const qn::BatchSeg* dsg = (const qn::BatchSeg*)(d + tb.seg);
   hipLaunchKernelGGL(qn::k_map_transform, dim3(nt), dim3(QN_BLOCK), 0, st, dkf, dblk, (const double*)(d + tb.pose), s->concat.p, s->tile_box.p);
   hipLaunchKernelGGL(qn::k_seg_bbox_reduce, dim3(count), dim3(QN_BLOCK), 0, st, (const qn::BBoxOut*)s->tile_box.p, (const uint32_t*)(d + tb.toff), s->seg_box.p);
-  KFCHK(s, hipMemcpyAsync(s->seg_box_host.p, s->seg_box.p, sizeof(qn::BBoxOut) * count, hipMemcpyDeviceToHost, st));
-  KFCHK(s, hipGetLastError());
-  KFCHK(s, hipStreamSynchronize(st));                               // the one sync: each cloud's box sizes its cells
+  QN_KFCHK(s, hipMemcpyAsync(s->seg_box_host.p, s->seg_box.p, sizeof(qn::BBoxOut) * count, hipMemcpyDeviceToHost, st));
+  QN_KFCHK(s, hipGetLastError());
+  QN_KFCHK(s, hipStreamSynchronize(st));                            // the one sync: each cloud's box sizes its cells
   qn::BatchSeg* sg = (qn::BatchSeg*)(h + tb.seg); std::vector<int> lbits(count);
   for (uint32_t k = 0; k < count; k++) {
     qn::BatchSeg& g = sg[k];
@@ -725,11 +680,11 @@ int qn_kf_int_cell_index(qn_kf_store* s, const float4* const* clouds, const uint
   const std::vector<SortGroup> groups = sort_groups(lbits, count, sg, p0);
   for (uint32_t k = 0; k < count; k++) grids[k].prefix = sg[k].prefix;
   if (!sort_scratch(s, groups, p0)) return QN_ERR_HIP;
-  KFCHK(s, hipMemcpyAsync(s->tab.p + tb.seg, sg, tb.end - tb.seg, hipMemcpyHostToDevice, st));
+  QN_KFCHK(s, hipMemcpyAsync(s->tab.p + tb.seg, sg, tb.end - tb.seg, hipMemcpyHostToDevice, st));
   hipLaunchKernelGGL(qn::k_batch_keys, dim3(nt * QN_MAP_ITEMS), dim3(QN_BLOCK), 0, st, dkf, dblk, dks, dsg, (const float4*)s->concat.p, s->keys.p);
   unsigned long long* fin = nullptr;
   { const int src = sort_segments(s, groups, p0, &fin); if (src != QN_OK) return src; }
-  KFCHK(s, hipGetLastError());
+  QN_KFCHK(s, hipGetLastError());
   *points = s->concat.p; *keys = fin;
   return QN_OK;
 }
@@ -757,8 +712,8 @@ extern "C" int qn_kf_download(qn_kf_store* s, int slot, float* xyz_out) {       
   if (!s || !xyz_out || (slot != 0 && slot != 1)) return QN_ERR_INVALID_ARG;
   const uint32_t n = s->out_n[slot];
   if (!n) return QN_OK;
-  KFCHK(s, hipSetDevice(s->device));
-  KFCHK(s, hipMemcpy2D(xyz_out, 12, s->out[slot].p, 16, 12, n, hipMemcpyDeviceToHost));
+  QN_KFCHK(s, hipSetDevice(s->device));
+  QN_KFCHK(s, hipMemcpy2D(xyz_out, 12, s->out[slot].p, 16, 12, n, hipMemcpyDeviceToHost));
   return QN_OK;
 }
 
@@ -799,9 +754,9 @@ extern "C" int qn_kf_download_map(qn_kf_store* s, void* out, uint32_t stride, ui
   if (!s || !out || !xyzi_layout_ok(stride, ioff)) return QN_ERR_INVALID_ARG;
   const uint32_t n = s->map_n;
   if (!n) return QN_OK;
-  KFCHK(s, hipSetDevice(s->device));
-  KFCHK(s, hipMemcpy2D(out, stride, s->map.p, 16, 12, n, hipMemcpyDeviceToHost));
-  KFCHK(s, hipMemcpy2D((char*)out + ioff, stride, (const char*)s->map.p + 12, 16, 4, n, hipMemcpyDeviceToHost));
+  QN_KFCHK(s, hipSetDevice(s->device));
+  QN_KFCHK(s, hipMemcpy2D(out, stride, s->map.p, 16, 12, n, hipMemcpyDeviceToHost));
+  QN_KFCHK(s, hipMemcpy2D((char*)out + ioff, stride, (const char*)s->map.p + 12, 16, 4, n, hipMemcpyDeviceToHost));
   return QN_OK;
 }
 
@@ -831,23 +786,21 @@ extern "C" int qn_kf_assemble_batch(qn_kf_store* s, const int32_t* ids, const do
 }
 
 int qn_kf_int_voxel_windows(qn_kf_store* s, const int32_t* ids, const double* poses, const uint32_t* seg_off, uint32_t n_seg, double leaf,
-                            float4** block, const float4** ptr, uint32_t* n, int* status) {
-  *block = nullptr;
+                            DevBuf<float4>& block, const float4** ptr, uint32_t* n, int* status) {
+  block.reset();
   for (uint32_t t = 0; t < n_seg; t++) { ptr[t] = nullptr; n[t] = 0; status[t] = QN_ERR_EMPTY_CLOUD; }
   if (n_seg == 0) return QN_OK;
   std::vector<SubmapOut> res(n_seg); VoxelNotes nt;
-  Buf<float4> out;
   s->last_error.clear();
-  const int rc = voxel_submaps(s, sources_of(s, ids, seg_off[0], seg_off[n_seg]).data(), poses, seg_off, n_seg, leaf, false, false, out, res.data(), &nt);
-  if (rc != QN_OK) { dev_free(out); return rc; }
+  const int rc = voxel_submaps(s, sources_of(s, ids, seg_off[0], seg_off[n_seg]).data(), poses, seg_off, n_seg, leaf, false, false, block, res.data(), &nt);
+  if (rc != QN_OK) { block.reset(); return rc; }
   if (nt.nonfinite) s->last_error = kNonFiniteNote;
   if (nt.tripped) s->last_error = kOverflowWarning;
   for (uint32_t t = 0; t < n_seg; t++) { ptr[t] = res[t].ptr; n[t] = res[t].n; status[t] = res[t].status; }
-  *block = out.p;
   return QN_OK;
 }
 
-int qn_kf_int_voxel_each(qn_kf_store* s, const int32_t* ids, uint32_t count, double leaf, float4** block, const float4** ptr, uint32_t* n, int* status) {
+int qn_kf_int_voxel_each(qn_kf_store* s, const int32_t* ids, uint32_t count, double leaf, DevBuf<float4>& block, const float4** ptr, uint32_t* n, int* status) {
   std::vector<uint32_t> seg(count + 1);
   for (uint32_t t = 0; t <= count; t++) seg[t] = t;
   std::vector<double> eye(16 * (size_t)count, 0.0);
@@ -864,8 +817,8 @@ extern "C" int qn_kf_download_batch(qn_kf_store* s, uint32_t seg, float* xyz_out
   if (!s || !xyz_out || seg >= s->bt_n.size()) return QN_ERR_INVALID_ARG;
   const uint32_t n = s->bt_n[seg];
   if (!n) return QN_OK;
-  KFCHK(s, hipSetDevice(s->device));
-  KFCHK(s, hipMemcpy2D(xyz_out, 12, s->bt_ptr[seg], 16, 12, n, hipMemcpyDeviceToHost));
+  QN_KFCHK(s, hipSetDevice(s->device));
+  QN_KFCHK(s, hipMemcpy2D(xyz_out, 12, s->bt_ptr[seg], 16, 12, n, hipMemcpyDeviceToHost));
   return QN_OK;
 }
 

@@ -23,7 +23,6 @@
 #include <string>
 #include <vector>
 #include "../../include/qn_engine.h"
-#include "qn_kf_internal.h"
 #include "qn_range.cuh"
 
 namespace {
@@ -154,15 +153,6 @@ __global__ void __launch_bounds__(256) k_freespace_reduce(const FsSeg* __restric
 #define RG_DESCRIBE_CHUNK 32768u                         // keyframes per describe launch (the grid's y dimension)
 const uint32_t kMaxPairs = 32767;                        // (pair, direction) is the grid's y dimension
 
-void range_release(void* v) {                            // called by qn_kf_store_destroy after its stream has drained
-  RangeState* st = (RangeState*)v;
-  (void)hipFree(st->tab); (void)hipFree(st->img); (void)hipFree(st->cls);
-  delete st;
-}
-
-int fail(qn_kf_store* s, const char* msg) { qn_kf_int_set_error(s, msg); return QN_ERR_HIP; }
-#define RGCHK(s, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { qn_kf_int_set_error((s), (std::string(#call) + " -> " + hipGetErrorString(e_)).c_str()); return QN_ERR_HIP; } } while (0)
-
 qn_range_params range_default_params() {
   qn_range_params p{};
   p.n_rows = 64; p.n_cols = 1800; p.el_lo = -25.0 * M_PI / 180.0; p.el_hi = 2.2 * M_PI / 180.0; p.min_range = 2.0;
@@ -193,42 +183,20 @@ std::vector<double> range_tables(const qn_range_params& p) {
   }
   return t;
 }
-int range_upload_tables(qn_kf_store* s, RangeState* st) {
-  const std::vector<double> t = range_tables(st->p);
-  (void)hipFree(st->tab); st->tab = nullptr;
-  RGCHK(s, hipMalloc(&st->tab, sizeof(double) * t.size()));
-  RGCHK(s, hipMemcpy(st->tab, t.data(), sizeof(double) * t.size(), hipMemcpyHostToDevice));
-  return QN_OK;
-}
 int range_state(qn_kf_store* s, RangeState** out) {
-  RangeState* st = (RangeState*)qn_kf_int_ext(s, QN_KF_INT_EXT_RANGE);
-  if (!st) {
-    RGCHK(s, hipSetDevice(qn_kf_int_device(s)));
-    st = new (std::nothrow) RangeState();
-    if (!st) return fail(s, "qn_kf_range: out of memory");
+  return qn_kf_ext_state(s, QN_KF_INT_EXT_RANGE, out, [s](RangeState* st) -> int {
+    QN_KFCHK(s, hipSetDevice(qn_kf_int_device(s)));
     st->p = range_default_params();
-    const int rc = range_upload_tables(s, st);
-    if (rc != QN_OK) { range_release(st); return rc; }
-    qn_kf_int_set_ext(s, QN_KF_INT_EXT_RANGE, st, range_release);
-  }
-  *out = st;
-  return QN_OK;
+    const std::vector<double> t = range_tables(st->p);
+    return st->tab.assign(s, t.data(), t.size()) ? QN_OK : QN_ERR_HIP;
+  });
 }
 // image slots for every keyframe id < n (contents of existing slots kept)
 int range_reserve(qn_kf_store* s, RangeState* st, size_t n) {
   if (n <= st->cap) return QN_OK;
   const size_t cap = std::max<size_t>({n, st->cap + st->cap / 2, 16});
-  const size_t per = 2 * (size_t)st->p.n_rows * st->p.n_cols;
-  uint32_t* d = nullptr;
-  if (hipMalloc(&d, sizeof(uint32_t) * per * cap) != hipSuccess) { (void)hipGetLastError(); return fail(s, "qn_kf_range: image storage allocation failed"); }
-  if (st->cap) {
-    const hipStream_t str = qn_kf_int_stream(s);
-    if (hipMemcpyAsync(d, st->img, sizeof(uint32_t) * per * st->cap, hipMemcpyDeviceToDevice, str) != hipSuccess || hipStreamSynchronize(str) != hipSuccess) {
-      (void)hipFree(d); return fail(s, "qn_kf_range: moving the images failed");
-    }
-  }
-  (void)hipFree(st->img);
-  st->img = d; st->cap = cap;
+  if (!st->img.grow_keep(s, 2 * (size_t)st->p.n_rows * st->p.n_cols * cap, qn_kf_int_stream(s))) return QN_ERR_HIP;
+  st->cap = cap;
   return QN_OK;
 }
 
@@ -242,12 +210,13 @@ extern "C" int qn_kf_range_set_params(qn_kf_store* s, const qn_range_params* p) 
   const qn_range_params& o = st->p;
   const bool same_images = o.n_rows == p->n_rows && o.n_cols == p->n_cols && o.el_lo == p->el_lo && o.el_hi == p->el_hi && o.min_range == p->min_range;
   if (same_images) { st->p = *p; return QN_OK; }            // the images do not depend on the window or the tolerances
-  RGCHK(s, hipSetDevice(qn_kf_int_device(s)));
-  RGCHK(s, hipStreamSynchronize(qn_kf_int_stream(s)));      // no launch of this store may still read the old images
-  (void)hipFree(st->img); st->img = nullptr; st->cap = 0;
+  QN_KFCHK(s, hipSetDevice(qn_kf_int_device(s)));
+  QN_KFCHK(s, hipStreamSynchronize(qn_kf_int_stream(s)));   // no launch of this store may still read the old images
+  st->img.reset(); st->cap = 0;
   st->described.assign(st->described.size(), 0);
   st->p = *p;
-  return range_upload_tables(s, st);
+  const std::vector<double> t = range_tables(st->p);
+  return st->tab.assign(s, t.data(), t.size()) ? QN_OK : QN_ERR_HIP;
 }
 extern "C" int qn_kf_range_get_params(qn_kf_store* s, qn_range_params* p) {
   if (!s || !p) return QN_ERR_INVALID_ARG;
@@ -265,7 +234,7 @@ extern "C" int qn_kf_range_describe(qn_kf_store* s, const int32_t* ids, uint32_t
   RangeState* st = nullptr;
   int rc = range_state(s, &st);
   if (rc != QN_OK) return rc;
-  RGCHK(s, hipSetDevice(qn_kf_int_device(s)));
+  QN_KFCHK(s, hipSetDevice(qn_kf_int_device(s)));
   // each listed keyframe once (an id listed twice gets the same image either way)
   std::vector<int32_t> slot_of(n_kf, -1);
   std::vector<RgKf> todo;
@@ -285,26 +254,26 @@ extern "C" int qn_kf_range_describe(qn_kf_store* s, const int32_t* ids, uint32_t
   RgKf* d_kfs = (RgKf*)qn_kf_int_scratch(s, 0, sizeof(RgKf) * m_all);
   uint32_t* d_cnt = (uint32_t*)qn_kf_int_scratch(s, 1, sizeof(uint32_t) * m_all);
   uint32_t* h_cnt = (uint32_t*)qn_kf_int_pinned(s, sizeof(uint32_t) * m_all);
-  if (!d_kfs || !d_cnt || !h_cnt) return fail(s, "qn_kf_range_describe: scratch allocation failed");
+  if (!d_kfs || !d_cnt || !h_cnt) return qn_kf_fail(s, "qn_kf_range_describe: scratch allocation failed");
   const hipStream_t str = qn_kf_int_stream(s);
-  RGCHK(s, hipMemcpyAsync(d_kfs, todo.data(), sizeof(RgKf) * m_all, hipMemcpyHostToDevice, str));
-  RGCHK(s, hipMemsetAsync(d_cnt, 0, sizeof(uint32_t) * m_all, str));
-  const double* trow = st->tab;
-  const double2* cs = (const double2*)(st->tab + range_cs_offset(nr));
+  QN_KFCHK(s, hipMemcpyAsync(d_kfs, todo.data(), sizeof(RgKf) * m_all, hipMemcpyHostToDevice, str));
+  QN_KFCHK(s, hipMemsetAsync(d_cnt, 0, sizeof(uint32_t) * m_all, str));
+  const double* trow = st->tab.p;
+  const double2* cs = (const double2*)(st->tab.p + range_cs_offset(nr));
   const size_t lds = range_lds_bytes(st);
   for (size_t a = 0; a < m_all; a += RG_DESCRIBE_CHUNK) {
     const uint32_t m = (uint32_t)std::min<size_t>(RG_DESCRIBE_CHUNK, m_all - a);
     uint32_t nmax = 0;
     for (uint32_t k = 0; k < m; k++) nmax = std::max(nmax, todo[a + k].n);
-    hipLaunchKernelGGL(k_range_clear, dim3((npix + 255) / 256, m), dim3(256), 0, str, (const RgKf*)(d_kfs + a), npix, st->img);
+    hipLaunchKernelGGL(k_range_clear, dim3((npix + 255) / 256, m), dim3(256), 0, str, (const RgKf*)(d_kfs + a), npix, st->img.p);
     if (!nmax) continue;
     const dim3 grid((nmax + FS_TILE - 1) / FS_TILE, m);
-    if (lds) hipLaunchKernelGGL(k_range_bin<true>, grid, dim3(FS_BLOCK), lds, str, (const RgKf*)(d_kfs + a), trow, cs, nr, nc, st->p.min_range, st->img, d_cnt + a);
-    else hipLaunchKernelGGL(k_range_bin<false>, grid, dim3(FS_BLOCK), 0, str, (const RgKf*)(d_kfs + a), trow, cs, nr, nc, st->p.min_range, st->img, d_cnt + a);
+    if (lds) hipLaunchKernelGGL(k_range_bin<true>, grid, dim3(FS_BLOCK), lds, str, (const RgKf*)(d_kfs + a), trow, cs, nr, nc, st->p.min_range, st->img.p, d_cnt + a);
+    else hipLaunchKernelGGL(k_range_bin<false>, grid, dim3(FS_BLOCK), 0, str, (const RgKf*)(d_kfs + a), trow, cs, nr, nc, st->p.min_range, st->img.p, d_cnt + a);
   }
-  RGCHK(s, hipGetLastError());
-  RGCHK(s, hipMemcpyAsync(h_cnt, d_cnt, sizeof(uint32_t) * m_all, hipMemcpyDeviceToHost, str));
-  RGCHK(s, hipStreamSynchronize(str));                      // the one synchronisation: the kept counts, and the scratch may be reused
+  QN_KFCHK(s, hipGetLastError());
+  QN_KFCHK(s, hipMemcpyAsync(h_cnt, d_cnt, sizeof(uint32_t) * m_all, hipMemcpyDeviceToHost, str));
+  QN_KFCHK(s, hipStreamSynchronize(str));                   // the one synchronisation: the kept counts, and the scratch may be reused
   for (const RgKf& k : todo) st->described[k.id] = 1;
   for (uint32_t k = 0; k < count; k++) status[k] = h_cnt[slot_of[ids[k]]] ? QN_OK : QN_ERR_EMPTY_CLOUD;
   return QN_OK;
@@ -314,13 +283,13 @@ extern "C" int qn_kf_range_get(qn_kf_store* s, int32_t id, float* near_out, floa
   if (!s || id < 0 || (size_t)id >= qn_kf_int_count(s) || (!near_out && !far_out)) return QN_ERR_INVALID_ARG;
   RangeState* st = (RangeState*)qn_kf_int_ext(s, QN_KF_INT_EXT_RANGE);
   if (!st || (size_t)id >= st->described.size() || !st->described[id]) return QN_ERR_NOT_READY;
-  RGCHK(s, hipSetDevice(qn_kf_int_device(s)));
+  QN_KFCHK(s, hipSetDevice(qn_kf_int_device(s)));
   const hipStream_t str = qn_kf_int_stream(s);
   const size_t npix = (size_t)st->p.n_rows * st->p.n_cols;
-  const uint32_t* base = st->img + (size_t)id * 2 * npix;
-  if (near_out) RGCHK(s, hipMemcpyAsync(near_out, base, sizeof(float) * npix, hipMemcpyDeviceToHost, str));
-  if (far_out) RGCHK(s, hipMemcpyAsync(far_out, base + npix, sizeof(float) * npix, hipMemcpyDeviceToHost, str));
-  RGCHK(s, hipStreamSynchronize(str));
+  const uint32_t* base = st->img.p + (size_t)id * 2 * npix;
+  if (near_out) QN_KFCHK(s, hipMemcpyAsync(near_out, base, sizeof(float) * npix, hipMemcpyDeviceToHost, str));
+  if (far_out) QN_KFCHK(s, hipMemcpyAsync(far_out, base + npix, sizeof(float) * npix, hipMemcpyDeviceToHost, str));
+  QN_KFCHK(s, hipStreamSynchronize(str));
   return QN_OK;
 }
 
@@ -348,22 +317,16 @@ extern "C" int qn_kf_freespace_batch(qn_kf_store* s, const int32_t* query, const
       total += n; blocks += (n + FS_TILE - 1) / FS_TILE; nmax = std::max(nmax, n);
       if (total > 0xFFFFFFFFull) return QN_ERR_CAPACITY;
     }
-  RGCHK(s, hipSetDevice(qn_kf_int_device(s)));
+  QN_KFCHK(s, hipSetDevice(qn_kf_int_device(s)));
   const hipStream_t str = qn_kf_int_stream(s);
-  const size_t seg_bytes = (sizeof(FsSeg) * S + 15) & ~(size_t)15, res_bytes = sizeof(FsCnt) * S;
+  const size_t seg_bytes = qn_up16(sizeof(FsSeg) * S), res_bytes = sizeof(FsCnt) * S;
   FsSeg* d_seg = (FsSeg*)qn_kf_int_scratch(s, 0, seg_bytes);
   FsCnt* d_slots = (FsCnt*)qn_kf_int_scratch(s, 1, sizeof(FsCnt) * std::max<uint64_t>(blocks, 1));
   FsCnt* d_res = (FsCnt*)qn_kf_int_scratch(s, 2, res_bytes);
   char* h = (char*)qn_kf_int_pinned(s, seg_bytes + res_bytes);
-  if (!d_seg || !d_slots || !d_res || !h) return fail(s, "qn_kf_freespace_batch: scratch allocation failed");
-  if (total > st->cls_cap) {
-    uint8_t* c = nullptr;
-    const size_t cap = (size_t)(total + total / 2);
-    if (hipMalloc(&c, cap) != hipSuccess) { (void)hipGetLastError(); return fail(s, "qn_kf_freespace_batch: hipMalloc failed"); }
-    (void)hipFree(st->cls);                                 // (waits for the device: nothing still reads the old classes)
-    st->cls = c; st->cls_cap = cap;
-  }
-  st->live = false;
+  if (!d_seg || !d_slots || !d_res || !h) return qn_kf_fail(s, "qn_kf_freespace_batch: scratch allocation failed");
+  st->live = false;                                         // from here on the previous check is gone
+  if (!st->cls.grow(s, total)) return QN_ERR_HIP;
   FsSeg* h_seg = (FsSeg*)h; FsCnt* h_res = (FsCnt*)(h + seg_bytes);
   for (uint32_t j = 0; j < n_pairs; j++) {
     const double* T = T16 + 16 * (size_t)j;
@@ -381,22 +344,22 @@ extern "C" int qn_kf_freespace_batch(qn_kf_store* s, const int32_t* query, const
       memcpy(g.M, d == 0 ? T : inv, sizeof(double) * 12);
     }
   }
-  RGCHK(s, hipMemcpyAsync(d_seg, h_seg, sizeof(FsSeg) * S, hipMemcpyHostToDevice, str));
+  QN_KFCHK(s, hipMemcpyAsync(d_seg, h_seg, sizeof(FsSeg) * S, hipMemcpyHostToDevice, str));
   const qn_range_params& p = st->p;
-  const double* trow = st->tab;
-  const double2* cs = (const double2*)(st->tab + range_cs_offset(p.n_rows));
+  const double* trow = st->tab.p;
+  const double2* cs = (const double2*)(st->tab.p + range_cs_offset(p.n_rows));
   const size_t lds = range_lds_bytes(st);
   if (nmax) {
     const dim3 grid((nmax + FS_TILE - 1) / FS_TILE, S);
     if (lds) hipLaunchKernelGGL(k_freespace_check<true>, grid, dim3(FS_BLOCK), lds, str, (const FsSeg*)d_seg, trow, cs, p.n_rows, p.n_cols, p.min_range, (int)p.window_rows,
-                                (int)p.window_cols, p.tol_abs, p.tol_rel, (const uint32_t*)st->img, st->cls, d_slots);
+                                (int)p.window_cols, p.tol_abs, p.tol_rel, (const uint32_t*)st->img.p, st->cls.p, d_slots);
     else hipLaunchKernelGGL(k_freespace_check<false>, grid, dim3(FS_BLOCK), 0, str, (const FsSeg*)d_seg, trow, cs, p.n_rows, p.n_cols, p.min_range, (int)p.window_rows,
-                            (int)p.window_cols, p.tol_abs, p.tol_rel, (const uint32_t*)st->img, st->cls, d_slots);
+                            (int)p.window_cols, p.tol_abs, p.tol_rel, (const uint32_t*)st->img.p, st->cls.p, d_slots);
   }
   hipLaunchKernelGGL(k_freespace_reduce, dim3(S), dim3(256), 0, str, (const FsSeg*)d_seg, (const FsCnt*)d_slots, d_res);
-  RGCHK(s, hipGetLastError());
-  RGCHK(s, hipMemcpyAsync(h_res, d_res, res_bytes, hipMemcpyDeviceToHost, str));
-  RGCHK(s, hipStreamSynchronize(str));                      // the one synchronisation of the call
+  QN_KFCHK(s, hipGetLastError());
+  QN_KFCHK(s, hipMemcpyAsync(h_res, d_res, res_bytes, hipMemcpyDeviceToHost, str));
+  QN_KFCHK(s, hipStreamSynchronize(str));                   // the one synchronisation of the call
   for (uint32_t j = 0; j < n_pairs; j++) {
     qn_freespace_dir* d[2] = {&out[j].q_in_c, &out[j].c_in_q};
     for (int k = 0; k < 2; k++) {
@@ -418,9 +381,9 @@ extern "C" int qn_kf_freespace_points(qn_kf_store* s, uint32_t pair_slot, int di
   if (pair_slot >= st->slots.size()) return QN_ERR_INVALID_ARG;
   const FsSlot& o = st->slots[pair_slot];
   if (o.n[dir] == 0) return QN_OK;
-  RGCHK(s, hipSetDevice(qn_kf_int_device(s)));
+  QN_KFCHK(s, hipSetDevice(qn_kf_int_device(s)));
   const hipStream_t str = qn_kf_int_stream(s);
-  RGCHK(s, hipMemcpyAsync(class_out, st->cls + o.p0[dir], o.n[dir], hipMemcpyDeviceToHost, str));
-  RGCHK(s, hipStreamSynchronize(str));
+  QN_KFCHK(s, hipMemcpyAsync(class_out, st->cls.p + o.p0[dir], o.n[dir], hipMemcpyDeviceToHost, str));
+  QN_KFCHK(s, hipStreamSynchronize(str));
   return QN_OK;
 }

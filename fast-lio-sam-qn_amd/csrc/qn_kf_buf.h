@@ -1,0 +1,96 @@
+// qn_kf_buf.h - the host plumbing every translation unit around a qn_kf_store shares: one error macro, one owned buffer with two ways to grow, one
+// get-or-create of a unit's per-store state.  Header only.  Rule of the buffers: a call that fails leaves nothing stale behind - a buffer that could not
+// be grown is empty, a slot array that could not be moved is the old one, and the HIP runtime's sticky error is cleared (a hipGetLastError() behind a later
+// launch on this thread would otherwise report the old out-of-memory as its own).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <new>
+#include <string>
+#include <utility>
+#include "qn_kf_internal.h"
+
+#define QN_KFCHK(s, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { (void)hipGetLastError(); qn_kf_int_set_error((s), (std::string(#call) + " -> " + hipGetErrorString(e_)).c_str()); return QN_ERR_HIP; } } while (0)
+inline int qn_kf_fail(qn_kf_store* s, const char* msg) { qn_kf_int_set_error(s, msg); return QN_ERR_HIP; }
+inline size_t qn_up16(size_t b) { return (b + 15) & ~(size_t)15; }
+
+// `cap` elements of device (DevBuf) or pinned host (PinBuf) memory, freed with their owner.  Move-only.
+template <typename T, bool kPinned> struct KfBuf {
+  T* p = nullptr; size_t cap = 0;
+  KfBuf() = default;
+  KfBuf(KfBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+  KfBuf& operator=(KfBuf&& o) noexcept { swap(o); return *this; }      // (o takes the old buffer and frees it)
+  ~KfBuf() { reset(); }
+  void swap(KfBuf& o) noexcept { std::swap(p, o.p); std::swap(cap, o.cap); }
+  void reset() {
+    if (p) (void)(kPinned ? hipHostFree(p) : hipFree(p));
+    p = nullptr; cap = 0;
+  }
+  // at least `need` elements, the old contents dead: nothing when they fit, else freed first and allocated half again as large (exact: just `need`).
+  // false: the buffer is empty and last_error says why (the caller returns QN_ERR_HIP).
+  bool grow(qn_kf_store* s, size_t need, bool exact = false) {
+    if (need <= cap) return true;
+    reset();
+    const size_t n = exact ? need : need + need / 2;
+    if (!(p = alloc(s, n))) return false;
+    cap = n;
+    return true;
+  }
+  // slot arrays: new_cap elements whose first `cap` are the old ones, copied on `stream` and synchronised before the old buffer goes.
+  // false: the buffer is as it was.
+  bool grow_keep(qn_kf_store* s, size_t new_cap, hipStream_t stream) {
+    static_assert(!kPinned, "device buffers only");
+    KfBuf g;
+    if (!(g.p = alloc(s, new_cap))) return false;
+    g.cap = new_cap;
+    if (cap) {
+      hipError_t e = hipMemcpyAsync(g.p, p, sizeof(T) * cap, hipMemcpyDeviceToDevice, stream);
+      if (e == hipSuccess) e = hipStreamSynchronize(stream);
+      if (e != hipSuccess) return failed(s, "moving a slot array -> ", e);
+    }
+    swap(g);
+    return true;
+  }
+  // exactly the n elements at `host`, copied before it returns (tables)
+  bool assign(qn_kf_store* s, const T* host, size_t n) {
+    static_assert(!kPinned, "device buffers only");
+    reset();
+    if (!(p = alloc(s, n))) return false;
+    cap = n;
+    const hipError_t e = hipMemcpy(p, host, sizeof(T) * n, hipMemcpyHostToDevice);
+    if (e == hipSuccess) return true;
+    reset();
+    return failed(s, "hipMemcpy -> ", e);
+  }
+
+ private:
+  static T* alloc(qn_kf_store* s, size_t n) {
+    void* q = nullptr;
+    const hipError_t e = kPinned ? hipHostMalloc(&q, sizeof(T) * n, hipHostMallocDefault) : hipMalloc(&q, sizeof(T) * n);
+    if (e != hipSuccess) failed(s, kPinned ? "hipHostMalloc -> " : "hipMalloc -> ", e);
+    return e == hipSuccess ? (T*)q : nullptr;
+  }
+  // every failure of a buffer ends here: the sticky error cleared, last_error set
+  static bool failed(qn_kf_store* s, const char* what, hipError_t e) {
+    (void)hipGetLastError();
+    qn_kf_int_set_error(s, (std::string(what) + hipGetErrorString(e)).c_str());
+    return false;
+  }
+};
+
+// the state a translation unit keeps in extension slot `slot`, made on first use (first_use(st): QN_OK, or a status with which nothing is registered) and
+// deleted by the store once its stream has drained
+template <typename St, typename FirstUse> int qn_kf_ext_state(qn_kf_store* s, int slot, St** out, FirstUse first_use) {
+  St* st = (St*)qn_kf_int_ext(s, slot);
+  if (!st) {
+    st = new (std::nothrow) St();
+    if (!st) return qn_kf_fail(s, "qn_kf: out of memory");
+    const int rc = first_use(st);
+    if (rc != QN_OK) { delete st; return rc; }
+    qn_kf_int_set_ext(s, slot, st, [](void* p) { delete (St*)p; });
+  }
+  *out = st;
+  return QN_OK;
+}
+template <typename St> int qn_kf_ext_state(qn_kf_store* s, int slot, St** out) {
+  return qn_kf_ext_state(s, slot, out, [](St*) { return QN_OK; });
+}

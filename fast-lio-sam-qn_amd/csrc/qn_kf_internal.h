@@ -7,6 +7,11 @@
 #include <cstddef>
 #include "../../include/qn_engine.h"
 
+// the owned buffers of the store and of every unit around it (qn_kf_buf.h, with the error macro and the get-or-create of a unit's state)
+template <typename T, bool kPinned> struct KfBuf;
+template <typename T> using DevBuf = KfBuf<T, false>;                            // device memory
+template <typename T> using PinBuf = KfBuf<T, true>;                             // pinned host memory
+
 int  qn_kf_int_device(const qn_kf_store* s);
 hipStream_t qn_kf_int_stream(const qn_kf_store* s);
 size_t qn_kf_int_count(const qn_kf_store* s);                                    // keyframes stored so far
@@ -26,6 +31,7 @@ bool qn_kf_int_has_intensity(const qn_kf_store* s, int32_t id);                 
 // per-store state of another translation unit (slot QN_KF_INT_EXT_SC: qn_sc.hip's descriptors, QN_KF_INT_EXT_QUATRO: the resident Quatro features of
 // qn_kf_quatro.inc, QN_KF_INT_EXT_VERIFY: qn_verify.hip's record of the latest multi-pair verification, QN_KF_INT_EXT_SUBMAP: the resident local submaps of
 // qn_kf_submap.inc): nullptr until set; the store owns it from qn_kf_int_set_ext on and calls `release` from qn_kf_store_destroy once its stream has drained.
+// Units reach their state through qn_kf_ext_state (qn_kf_buf.h), which makes it on first use.
 #define QN_KF_INT_EXT 7
 #define QN_KF_INT_EXT_SC 0
 #define QN_KF_INT_EXT_QUATRO 1
@@ -38,14 +44,14 @@ typedef void (*qn_kf_int_release_fn)(void*);
 void* qn_kf_int_ext(const qn_kf_store* s, int which);
 void qn_kf_int_set_ext(qn_kf_store* s, int which, void* p, qn_kf_int_release_fn release);
 // keyframes ids[0 .. count) each alone in its sensor frame (the identity pose), voxel grid at `leaf`: what qn_kf_assemble({id}, {identity}, leaf) builds,
-// through the one voxel-grid pipeline as a batch of `count` submaps.  Every cloud lands in ONE new device allocation (*block, nullptr when all are empty)
-// that the caller owns from here on (hipFree); ptr / n / status per keyframe as qn_kf_assemble_batch's.  The store's assemble, map and batch slots are
+// through the one voxel-grid pipeline as a batch of `count` submaps.  Every cloud lands in ONE new device allocation (block, the caller's; empty when all clouds are,
+// or on an error return); ptr / n / status per keyframe as qn_kf_assemble_batch's.  The store's assemble, map and batch slots are
 // not touched.  Two host synchronisations.  ids are not checked.
-int qn_kf_int_voxel_each(qn_kf_store* s, const int32_t* ids, uint32_t count, double leaf, float4** block, const float4** ptr, uint32_t* n, int* status);
+int qn_kf_int_voxel_each(qn_kf_store* s, const int32_t* ids, uint32_t count, double leaf, DevBuf<float4>& block, const float4** ptr, uint32_t* n, int* status);
 // the general form: submap t = keyframes ids[seg_off[t] .. seg_off[t + 1]) with the poses of the same entries (row-major 4x4 f64), what qn_kf_assemble_batch builds
 // for those lists - the same pipeline, the same bytes - but into ONE new allocation the caller owns (as above) instead of the store's batch slot.
 int qn_kf_int_voxel_windows(qn_kf_store* s, const int32_t* ids, const double* poses, const uint32_t* seg_off, uint32_t n_seg, double leaf,
-                            float4** block, const float4** ptr, uint32_t* n, int* status);
+                            DevBuf<float4>& block, const float4** ptr, uint32_t* n, int* status);
 // qn_verify.hip: what qn_kf_verify_cloud serves for pair j of the latest multi-pair verification.  src / dst: the pair's two clouds (batch segments on the
 // GICP path, described clouds on the coarse-to-fine path, resident local submaps on the two submap paths); stage: 0 nothing registered, 1 T_quatro solved
 // (coarse-to-fine only), 2 the GICP stage ran (Tg = its f32 T).  qn_kf_int_verify_record replaces the store's record; `kind` says which call made it.

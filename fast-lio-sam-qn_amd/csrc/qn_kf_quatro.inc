@@ -13,17 +13,14 @@
 // wrap (NormalsK / SpfhK / FpfhK <8>, RowsToOriginalK), so the rows are bit-identical to qn_fpfh's by construction.  Grid scratch per keyframe: two cell tables
 // of max_cells + 1 words; keyframes are taken in chunks whose scratch stays under QN_KFQ_SCRATCH_BYTES (one chunk for every S the budget holds).
 #include <memory>
-#include "qn_kf_internal.h"
+#include "qn_kf_buf.h"
 #define QN_KFQ_SCRATCH_BYTES ((size_t)1 << 30)
 #define QN_KFQ_MAX_CHUNK 4096u
 
 namespace {
 
 // one describe call's device memory: the clouds (the voxel pipeline's output buffer) and the FPFH rows; freed when no entry names it any more
-struct KfqBlock {
-  float4* pts = nullptr; float* rows = nullptr;
-  ~KfqBlock() { if (pts) (void)hipFree(pts); if (rows) (void)hipFree(rows); }
-};
+struct KfqBlock { DevBuf<float4> pts; DevBuf<float> rows; };
 struct KfqEntry {
   std::shared_ptr<KfqBlock> blk; float4* pts = nullptr; float* rows = nullptr; uint32_t n = 0;
   double leaf = 0, rn = 0, rf = 0; uint32_t max_cells = 0; int status = QN_OK; bool described = false;
@@ -33,17 +30,13 @@ struct KfqEntry {
 struct KfqSlot { uint32_t* cell_start; uint32_t* counts; unsigned long long* status; BBoxAcc* acc; GridDims* dims; };
 struct KfqState {
   std::vector<KfqEntry> e;
-  char* fixed = nullptr; uint32_t fixed_slots = 0, fixed_cells = 0;
-  char* pts = nullptr; size_t pts_cap = 0;
-  GridDims* dims_host = nullptr; uint32_t dims_host_cap = 0;
+  DevBuf<char> fixed; uint32_t fixed_slots = 0, fixed_cells = 0;      // every buffer here is sized exactly: the scratch runs up to QN_KFQ_SCRATCH_BYTES
+  DevBuf<char> pts;
+  PinBuf<GridDims> dims_host;
   uint32_t epoch = 0;
-  ~KfqState() {
-    if (fixed) (void)hipFree(fixed);
-    if (pts) (void)hipFree(pts);
-    if (dims_host) (void)hipHostFree(dims_host);
-  }
 };
-void kfq_release(void* p) { delete (KfqState*)p; }
+// a buffer of the store could not be grown: the context that was handed in says why too (qn_last_error)
+int kfq_no_memory(qn_kf_store* s, qn_ctx* c) { c->last_error = qn_kf_last_error(s); return QN_ERR_HIP; }
 size_t kfq_up(size_t b) { return (b + 255) & ~(size_t)255; }
 uint32_t kfq_status_words(uint32_t max_cells) { return max_cells / (QN_BLOCK * QN_SCAN_ITEMS) + 2; }
 // the slot tables, region by region: cell starts, cell counters, look-back status words, bounding-box accumulators, grid numbers - each region `slots` long
@@ -61,20 +54,20 @@ size_t kfq_point_bytes(uint32_t n) {      // raw, sorted, sorted_tmp, normals, c
 }
 KfqSlot kfq_slot(KfqState* st, uint32_t k) {
   const KfqFixed f(st->fixed_cells, st->fixed_slots);
-  char* b = st->fixed;
+  char* b = st->fixed.p;
   return KfqSlot{(uint32_t*)(b + f.tab * k), (uint32_t*)(b + f.off_counts + f.tab * k), (unsigned long long*)(b + f.off_stat + f.stat * k),
                  (BBoxAcc*)(b + f.off_acc + f.acc * k), (GridDims*)(b + f.off_dims + f.dims * k)};
 }
 // the slot tables for `slots` keyframes of a context with `max_cells`: (re)allocated and initialised on the context's stream when they do not fit
-int kfq_fixed(qn_ctx* c, KfqState* st, uint32_t slots) {
-  if (st->fixed && st->fixed_slots >= slots && st->fixed_cells == c->max_cells) return QN_OK;
-  if (st->fixed) { HIPCHK(c, hipStreamSynchronize(c->stream)); (void)hipFree(st->fixed); st->fixed = nullptr; st->fixed_slots = 0; }
+int kfq_fixed(qn_kf_store* s, qn_ctx* c, KfqState* st, uint32_t slots) {
+  if (st->fixed.p && st->fixed_slots >= slots && st->fixed_cells == c->max_cells) return QN_OK;
+  if (st->fixed.p) { HIPCHK(c, hipStreamSynchronize(c->stream)); st->fixed.reset(); st->fixed_slots = 0; }
   const KfqFixed f(c->max_cells, slots);
-  HIPCHK(c, hipMalloc(&st->fixed, f.end));
+  if (!st->fixed.grow(s, f.end, true)) return kfq_no_memory(s, c);
   st->fixed_slots = slots; st->fixed_cells = c->max_cells;
-  HIPCHK(c, hipMemsetAsync(st->fixed, 0, f.end, c->stream));
+  HIPCHK(c, hipMemsetAsync(st->fixed.p, 0, f.end, c->stream));
   // (the accumulator region is one array of slots x (QN_BBOX_MAX_BLOCKS + 1) entries: kfq_up keeps each slot's share a whole number of entries)
-  hipLaunchKernelGGL(k_bbox_acc_init, dim3(1), dim3(256), 0, c->stream, (BBoxAcc*)(st->fixed + f.off_acc), (int)(f.acc / sizeof(BBoxAcc) * slots));
+  hipLaunchKernelGGL(k_bbox_acc_init, dim3(1), dim3(256), 0, c->stream, (BBoxAcc*)(st->fixed.p + f.off_acc), (int)(f.acc / sizeof(BBoxAcc) * slots));
   HIPCHK(c, hipGetLastError());
   return QN_OK;
 }
@@ -100,11 +93,7 @@ int kfq_rows(qn_kf_store* s, qn_ctx* c, KfqState* st, const float4* const* vp, c
     }
     chunks.emplace_back(a, b); a = b;
   }
-  if (!live.empty() && !c->args_h) {                                               // the argument arena of the lane launches (qn_batch.inc)
-    c->args_cap = (size_t)4 << 20;
-    HIPCHK(c, hipHostMalloc(&c->args_h, c->args_cap, hipHostMallocDefault));
-    HIPCHK(c, hipMalloc(&c->args_d, c->args_cap));
-  }
+  if (!live.empty() && (rc = lane_args_arena(c)) != QN_OK) return rc;             // the argument arena of the lane launches (qn_batch.inc)
   uint32_t max_slots = 0; size_t max_pts = 0;
   for (const auto& ch : chunks) {
     max_slots = std::max<uint32_t>(max_slots, (uint32_t)(ch.second - ch.first));
@@ -112,15 +101,10 @@ int kfq_rows(qn_kf_store* s, qn_ctx* c, KfqState* st, const float4* const* vp, c
     max_pts = std::max(max_pts, p);
   }
   if (max_slots) {
-    if ((rc = kfq_fixed(c, st, max_slots)) != QN_OK) return rc;
-    if (max_pts > st->pts_cap) {
-      if (st->pts) { HIPCHK(c, hipStreamSynchronize(c->stream)); (void)hipFree(st->pts); st->pts = nullptr; st->pts_cap = 0; }
-      HIPCHK(c, hipMalloc(&st->pts, max_pts)); st->pts_cap = max_pts;
-    }
-    if (max_slots > st->dims_host_cap) {
-      if (st->dims_host) { HIPCHK(c, hipStreamSynchronize(c->stream)); (void)hipHostFree(st->dims_host); st->dims_host = nullptr; st->dims_host_cap = 0; }
-      HIPCHK(c, hipHostMalloc(&st->dims_host, sizeof(GridDims) * max_slots, hipHostMallocDefault)); st->dims_host_cap = max_slots;
-    }
+    if ((rc = kfq_fixed(s, c, st, max_slots)) != QN_OK) return rc;
+    // (a regrow waits for the context's stream first: that is where an asynchronous error of the previous call surfaces, with its message)
+    if ((max_pts > st->pts.cap && st->pts.p) || (max_slots > st->dims_host.cap && st->dims_host.p)) HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (!st->pts.grow(s, max_pts, true) || !st->dims_host.grow(s, max_slots, true)) return kfq_no_memory(s, c);
   }
   for (size_t ci = 0; ci < chunks.size(); ci++) {
     if (ci > 0) HIPCHK(c, hipStreamSynchronize(c->stream));                       // (the argument arena and the scratch are the previous chunk's until then)
@@ -132,7 +116,7 @@ int kfq_rows(qn_kf_store* s, qn_ctx* c, KfqState* st, const float4* const* vp, c
     // look-back status words and epoch are the slot's (swapped in around the call)
     BBoxAcc* const save_acc = c->bbox_acc; unsigned long long* const save_status = c->scan_status; const uint32_t save_epoch = c->build_epoch; const double save_cell = c->cell_override;
     c->cell_override = rf_d * 0.5;
-    char* p = st->pts;
+    char* p = st->pts.p;
     for (size_t j = chunks[ci].first; j < chunks[ci].second; j++) {
       const uint32_t i = live[j], n = vn[i], k = (uint32_t)(j - chunks[ci].first);
       const KfqSlot q = kfq_slot(st, k);
@@ -145,7 +129,7 @@ int kfq_rows(qn_kf_store* s, qn_ctx* c, KfqState* st, const float4* const* vp, c
       b.cell_of_pt = (uint32_t*)p; p += kfq_up(sizeof(uint32_t) * n);
       float* spfh = (float*)p; p += kfq_up(sizeof(float) * QN_FROW * n);
       float* fpfh_s = (float*)p; p += kfq_up(sizeof(float) * QN_FROW * n);
-      b.cell_start = q.cell_start; b.counts = q.counts; b.dims = q.dims; b.dims_host = st->dims_host + k;
+      b.cell_start = q.cell_start; b.counts = q.counts; b.dims = q.dims; b.dims_host = st->dims_host.p + k;
       c->bbox_acc = q.acc; c->scan_status = q.status;
       if (((++st->epoch) & 0x3fffffffu) == 0u) ++st->epoch;                        // (0 = the tag of the zero-initialised status words)
       c->build_epoch = st->epoch - 1;                                               // (prep_grid tags the build with ++build_epoch)
@@ -181,22 +165,20 @@ extern "C" int qn_kf_quatro_describe(qn_kf_store* s, qn_ctx* ctx, const int32_t*
   HIPCHK(ctx, hipSetDevice(ctx->device));
   qn_ctx* c = ctx;
   if (!c->qparams_set) { qn_quatro_default_params(&c->qparams); c->qparams_set = true; }
-  KfqState* st = (KfqState*)qn_kf_int_ext(s, QN_KF_INT_EXT_QUATRO);
-  if (!st) { st = new KfqState(); qn_kf_int_set_ext(s, QN_KF_INT_EXT_QUATRO, st, kfq_release); }
+  KfqState* st = nullptr;
+  int rc = qn_kf_ext_state(s, QN_KF_INT_EXT_QUATRO, &st);
+  if (rc != QN_OK) return rc;
   // ---- the clouds: one batch of `count` identity-pose submaps through the store's voxel pipeline (two host synchronisations), into a new block
   std::vector<const float4*> vp(count, nullptr); std::vector<uint32_t> vn(count, 0); std::vector<int> vs(count, QN_ERR_EMPTY_CLOUD);
-  float4* vblock = nullptr;
-  int rc = qn_kf_int_voxel_each(s, ids, count, leaf, &vblock, vp.data(), vn.data(), vs.data());
+  auto blk = std::make_shared<KfqBlock>();
+  rc = qn_kf_int_voxel_each(s, ids, count, leaf, blk->pts, vp.data(), vn.data(), vs.data());
   if (rc != QN_OK) return rc;                                                       // (an allocation failure: no entry changed)
-  auto blk = std::make_shared<KfqBlock>(); blk->pts = vblock;
   size_t total = 0; std::vector<size_t> roff(count, 0);
   for (uint32_t i = 0; i < count; i++) if (vs[i] == QN_OK) { roff[i] = total; total += vn[i]; }
-  if (total) {
-    if (hipMalloc(&blk->rows, sizeof(float) * QN_FROW * total) != hipSuccess) { (void)hipGetLastError(); blk->rows = nullptr; c->last_error = "qn_kf_quatro_describe: hipMalloc of the FPFH rows failed"; qn_kf_int_set_error(s, c->last_error.c_str()); return QN_ERR_HIP; }
-  }
+  if (!blk->rows.grow(s, QN_FROW * total, true)) return kfq_no_memory(s, c);
   // ---- K9-K11 of every non-empty keyframe, a chunk of keyframes per nine k_lanes launches
   const double rn_d = c->qparams.fpfh_normal_radius, rf_d = c->qparams.fpfh_radius;
-  if ((rc = kfq_rows(s, c, st, vp.data(), vn.data(), vs.data(), count, blk->rows, roff.data())) != QN_OK) return rc;
+  if ((rc = kfq_rows(s, c, st, vp.data(), vn.data(), vs.data(), count, blk->rows.p, roff.data())) != QN_OK) return rc;
   // ---- the entries: describing again replaces (the block of a replaced entry goes when no entry names it)
   qn_kf_int_verify_stale(s, QN_KF_VERIFY_FROM_SCANS, ids, count);                                         // (a multi-pair coarse-to-fine record that names one of them goes)
   if (st->e.size() < n_kf) st->e.resize(n_kf);
@@ -204,7 +186,7 @@ extern "C" int qn_kf_quatro_describe(qn_kf_store* s, qn_ctx* ctx, const int32_t*
     KfqEntry& e = st->e[ids[i]];
     e = KfqEntry{};
     e.described = true; e.leaf = leaf; e.rn = rn_d; e.rf = rf_d; e.max_cells = c->max_cells; e.status = vs[i];
-    if (vs[i] == QN_OK) { e.blk = blk; e.pts = const_cast<float4*>(vp[i]); e.rows = blk->rows + QN_FROW * roff[i]; e.n = vn[i]; }
+    if (vs[i] == QN_OK) { e.blk = blk; e.pts = const_cast<float4*>(vp[i]); e.rows = blk->rows.p + QN_FROW * roff[i]; e.n = vn[i]; }
     status[i] = vs[i];
   }
   return QN_OK;

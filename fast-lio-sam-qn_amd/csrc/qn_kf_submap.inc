@@ -19,7 +19,6 @@ namespace {
 
 struct KfsEntry : KfqEntry { uint32_t range = 0; bool has_rows = false; };
 struct KfsState { std::vector<KfsEntry> e; };
-void kfs_release(void* p) { delete (KfsState*)p; }
 
 const KfsEntry* kfs_entry(const qn_kf_store* s, int32_t id) {
   const KfsState* st = (const KfsState*)qn_kf_int_ext(s, QN_KF_INT_EXT_SUBMAP);
@@ -53,24 +52,23 @@ extern "C" int qn_kf_submap_describe(qn_kf_store* s, qn_ctx* ctx, const int32_t*
   HIPCHK(ctx, hipSetDevice(ctx->device));
   qn_ctx* c = ctx;
   if (!c->qparams_set) { qn_quatro_default_params(&c->qparams); c->qparams_set = true; }
-  KfsState* st = (KfsState*)qn_kf_int_ext(s, QN_KF_INT_EXT_SUBMAP);
-  if (!st) { st = new KfsState(); qn_kf_int_set_ext(s, QN_KF_INT_EXT_SUBMAP, st, kfs_release); }
-  KfqState* scratch = (KfqState*)qn_kf_int_ext(s, QN_KF_INT_EXT_QUATRO);             // (the grids' scratch is the scan entries' too: one arena per store)
-  if (with_features && !scratch) { scratch = new KfqState(); qn_kf_int_set_ext(s, QN_KF_INT_EXT_QUATRO, scratch, kfq_release); }
+  KfsState* st = nullptr; KfqState* scratch = nullptr;                               // (the grids' scratch is the scan entries' too: one arena per store)
+  int rc = qn_kf_ext_state(s, QN_KF_INT_EXT_SUBMAP, &st);
+  if (rc == QN_OK && with_features) rc = qn_kf_ext_state(s, QN_KF_INT_EXT_QUATRO, &scratch);
+  if (rc != QN_OK) return rc;
   // ---- the clouds: one batch of `count` windows through the store's voxel pipeline (two host synchronisations), into a new block
   std::vector<const float4*> vp(count, nullptr); std::vector<uint32_t> vn(count, 0); std::vector<int> vs(count, QN_ERR_EMPTY_CLOUD);
-  float4* vblock = nullptr;
-  int rc = qn_kf_int_voxel_windows(s, wid.data(), rel.data(), seg.data(), count, leaf, &vblock, vp.data(), vn.data(), vs.data());
+  auto blk = std::make_shared<KfqBlock>();
+  rc = qn_kf_int_voxel_windows(s, wid.data(), rel.data(), seg.data(), count, leaf, blk->pts, vp.data(), vn.data(), vs.data());
   if (rc != QN_OK) return rc;                                                       // (an allocation failure: no entry changed)
-  auto blk = std::make_shared<KfqBlock>(); blk->pts = vblock;
   size_t total = 0; std::vector<size_t> roff(count, 0);
   for (uint32_t i = 0; i < count; i++) {
     if (vs[i] == QN_OK && vn[i] > c->max_points) vs[i] = QN_ERR_CAPACITY;           // (no lane of this context could take it)
     if (vs[i] == QN_OK) { roff[i] = total; total += vn[i]; }
   }
   if (with_features && total) {
-    if (hipMalloc(&blk->rows, sizeof(float) * QN_FROW * total) != hipSuccess) { (void)hipGetLastError(); blk->rows = nullptr; c->last_error = "qn_kf_submap_describe: hipMalloc of the FPFH rows failed"; qn_kf_int_set_error(s, c->last_error.c_str()); return QN_ERR_HIP; }
-    if ((rc = kfq_rows(s, c, scratch, vp.data(), vn.data(), vs.data(), count, blk->rows, roff.data())) != QN_OK) return rc;
+    if (!blk->rows.grow(s, QN_FROW * total, true)) return kfq_no_memory(s, c);
+    if ((rc = kfq_rows(s, c, scratch, vp.data(), vn.data(), vs.data(), count, blk->rows.p, roff.data())) != QN_OK) return rc;
   }
   // ---- the entries: describing again replaces (the block of a replaced entry goes when no entry names it); a window over capacity leaves no entry
   qn_kf_int_verify_stale(s, QN_KF_VERIFY_FROM_SUBMAPS, ids, count);
@@ -82,7 +80,7 @@ extern "C" int qn_kf_submap_describe(qn_kf_store* s, qn_ctx* ctx, const int32_t*
     if (vs[i] == QN_ERR_CAPACITY) continue;
     e.described = true; e.leaf = leaf; e.rn = c->qparams.fpfh_normal_radius; e.rf = c->qparams.fpfh_radius; e.max_cells = c->max_cells; e.status = vs[i];
     e.range = submap_range; e.has_rows = with_features != 0;
-    if (vs[i] == QN_OK) { e.blk = blk; e.pts = const_cast<float4*>(vp[i]); e.rows = with_features ? blk->rows + QN_FROW * roff[i] : nullptr; e.n = vn[i]; }
+    if (vs[i] == QN_OK) { e.blk = blk; e.pts = const_cast<float4*>(vp[i]); e.rows = with_features ? blk->rows.p + QN_FROW * roff[i] : nullptr; e.n = vn[i]; }
   }
   return QN_OK;
 }

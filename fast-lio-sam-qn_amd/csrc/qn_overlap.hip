@@ -20,7 +20,7 @@
 #include <vector>
 #include <algorithm>
 #include "../../include/qn_engine.h"
-#include "qn_kf_internal.h"
+#include "qn_kf_buf.h"
 
 namespace {
 
@@ -129,21 +129,14 @@ __global__ void __launch_bounds__(QN_OV_BLOCK) k_overlap_reduce(const OvSeg* __r
 struct OvSlot { uint32_t p0[2], n[2]; int status; };
 struct OverlapState {
   bool live = false; std::vector<OvSlot> slots;
-  float* d2 = nullptr; int32_t* idx = nullptr; size_t cap = 0;
-  ~OverlapState() { if (d2) (void)hipFree(d2); if (idx) (void)hipFree(idx); }
+  DevBuf<float> d2; DevBuf<int32_t> idx;
 };
-void overlap_release(void* p) { delete (OverlapState*)p; }
-
-int fail(qn_kf_store* s, const char* msg) { qn_kf_int_set_error(s, msg); return QN_ERR_HIP; }
 
 // the pairs (A_j = cl[2 j], B_j = cl[2 j + 1]) whose pre[j] is QN_OK; arguments already checked
 int overlap_run(qn_kf_store* s, std::vector<const float4*>& cl, std::vector<uint32_t>& n, const std::vector<int>& pre, uint32_t P, double radius, qn_overlap* out, int* status) {
-  OverlapState* st = (OverlapState*)qn_kf_int_ext(s, QN_KF_INT_EXT_OVERLAP);
-  if (!st) {
-    st = new (std::nothrow) OverlapState();
-    if (!st) return fail(s, "qn_kf_overlap: out of memory");
-    qn_kf_int_set_ext(s, QN_KF_INT_EXT_OVERLAP, st, overlap_release);
-  }
+  OverlapState* st = nullptr;
+  int rc = qn_kf_ext_state(s, QN_KF_INT_EXT_OVERLAP, &st);
+  if (rc != QN_OK) return rc;
   st->live = false;
   for (uint32_t j = 0; j < P; j++) {
     memset(&out[j], 0, sizeof(out[j]));
@@ -153,7 +146,7 @@ int overlap_run(qn_kf_store* s, std::vector<const float4*>& cl, std::vector<uint
   const uint32_t S = 2 * P;
   std::vector<qn_kf_int_cell_grid> grid(S);
   const float4* pts = nullptr; const unsigned long long* keys = nullptr;
-  const int rc = qn_kf_int_cell_index(s, cl.data(), n.data(), S, radius, grid.data(), &pts, &keys);      // sync 1 of 2
+  rc = qn_kf_int_cell_index(s, cl.data(), n.data(), S, radius, grid.data(), &pts, &keys);      // sync 1 of 2
   if (rc != QN_OK) return rc;
   size_t total = 0; uint32_t nmax = 0;
   for (uint32_t k = 0; k < S; k++) { total += n[k]; nmax = std::max(nmax, n[k]); }
@@ -164,22 +157,16 @@ int overlap_run(qn_kf_store* s, std::vector<const float4*>& cl, std::vector<uint
     o.status = status[j];
   }
   if (total == 0) { st->live = true; return QN_OK; }
-  if (hipSetDevice(qn_kf_int_device(s)) != hipSuccess) return fail(s, "qn_kf_overlap: hipSetDevice failed");
+  QN_KFCHK(s, hipSetDevice(qn_kf_int_device(s)));
   hipStream_t stream = qn_kf_int_stream(s);
-  if (total > st->cap) {
-    if (st->d2) (void)hipFree(st->d2); if (st->idx) (void)hipFree(st->idx);
-    st->d2 = nullptr; st->idx = nullptr; st->cap = 0;
-    const size_t cap = total + total / 2;
-    if (hipMalloc(&st->d2, sizeof(float) * cap) != hipSuccess || hipMalloc(&st->idx, sizeof(int32_t) * cap) != hipSuccess) { (void)hipGetLastError(); return fail(s, "qn_kf_overlap: hipMalloc failed"); }
-    st->cap = cap;
-  }
-  const size_t seg_bytes = (sizeof(OvSeg) * S + 15) & ~(size_t)15, res_bytes = sizeof(OvRes) * S;
+  if (!st->d2.grow(s, total) || !st->idx.grow(s, total)) return QN_ERR_HIP;
+  const size_t seg_bytes = qn_up16(sizeof(OvSeg) * S), res_bytes = sizeof(OvRes) * S;
   OvSeg* d_seg = (OvSeg*)qn_kf_int_scratch(s, 0, seg_bytes);
   float4* d_spts = (float4*)qn_kf_int_scratch(s, 1, sizeof(float4) * total);
   uint32_t* d_cells = (uint32_t*)qn_kf_int_scratch(s, 2, sizeof(uint32_t) * total);
   OvRes* d_res = (OvRes*)qn_kf_int_scratch(s, 3, res_bytes);
   char* h = (char*)qn_kf_int_pinned(s, seg_bytes + res_bytes);
-  if (!d_seg || !d_spts || !d_cells || !d_res || !h) return fail(s, "qn_kf_overlap: scratch allocation failed");
+  if (!d_seg || !d_spts || !d_cells || !d_res || !h) return qn_kf_fail(s, "qn_kf_overlap: scratch allocation failed");
   OvSeg* h_seg = (OvSeg*)h; OvRes* h_res = (OvRes*)(h + seg_bytes);
   for (uint32_t k = 0; k < S; k++) {
     const qn_kf_int_cell_grid& g = grid[k];
@@ -190,12 +177,13 @@ int overlap_run(qn_kf_store* s, std::vector<const float4*>& cl, std::vector<uint
   const double rr = radius * radius;
   const float r2 = (float)rr;
   const dim3 grid2((nmax + QN_OV_BLOCK - 1) / QN_OV_BLOCK, S);
-  if (hipMemcpyAsync(d_seg, h_seg, sizeof(OvSeg) * S, hipMemcpyHostToDevice, stream) != hipSuccess) return fail(s, "qn_kf_overlap: upload failed");
+  QN_KFCHK(s, hipMemcpyAsync(d_seg, h_seg, sizeof(OvSeg) * S, hipMemcpyHostToDevice, stream));
   hipLaunchKernelGGL(k_overlap_gather, grid2, dim3(QN_OV_BLOCK), 0, stream, (const OvSeg*)d_seg, keys, pts, d_spts, d_cells);
-  hipLaunchKernelGGL(k_overlap_search, grid2, dim3(QN_OV_BLOCK), 0, stream, (const OvSeg*)d_seg, (const float4*)d_spts, (const uint32_t*)d_cells, r2, st->d2, st->idx);
-  hipLaunchKernelGGL(k_overlap_reduce, dim3(S), dim3(QN_OV_BLOCK), 0, stream, (const OvSeg*)d_seg, (const float*)st->d2, d_res);
-  if (hipGetLastError() != hipSuccess || hipMemcpyAsync(h_res, d_res, res_bytes, hipMemcpyDeviceToHost, stream) != hipSuccess ||
-      hipStreamSynchronize(stream) != hipSuccess) return fail(s, "qn_kf_overlap: the search failed");      // sync 2 of 2
+  hipLaunchKernelGGL(k_overlap_search, grid2, dim3(QN_OV_BLOCK), 0, stream, (const OvSeg*)d_seg, (const float4*)d_spts, (const uint32_t*)d_cells, r2, st->d2.p, st->idx.p);
+  hipLaunchKernelGGL(k_overlap_reduce, dim3(S), dim3(QN_OV_BLOCK), 0, stream, (const OvSeg*)d_seg, (const float*)st->d2.p, d_res);
+  QN_KFCHK(s, hipGetLastError());
+  QN_KFCHK(s, hipMemcpyAsync(h_res, d_res, res_bytes, hipMemcpyDeviceToHost, stream));
+  QN_KFCHK(s, hipStreamSynchronize(stream));             // sync 2 of 2
   for (uint32_t j = 0; j < P; j++) {
     if (status[j] != QN_OK) continue;
     qn_overlap_dir* d[2] = {&out[j].a_to_b, &out[j].b_to_a};
@@ -228,7 +216,7 @@ extern "C" int qn_kf_overlap_batch(qn_kf_store* s, const float* const* d_a, cons
   if (!s || !d_a || !n_a || !d_b || !n_b || n_pairs == 0 || !out || !status || !radius_ok(radius)) return QN_ERR_INVALID_ARG;
   if (n_pairs > kMaxPairs) return QN_ERR_CAPACITY;
   const int dev = qn_kf_int_device(s);
-  if (hipSetDevice(dev) != hipSuccess) return fail(s, "qn_kf_overlap_batch: hipSetDevice failed");
+  QN_KFCHK(s, hipSetDevice(dev));
   for (uint32_t j = 0; j < n_pairs; j++) if (!device_cloud_ok(dev, d_a[j], n_a[j]) || !device_cloud_ok(dev, d_b[j], n_b[j])) return QN_ERR_INVALID_ARG;
   std::vector<const float4*> cl(2 * (size_t)n_pairs); std::vector<uint32_t> n(2 * (size_t)n_pairs);
   for (uint32_t j = 0; j < n_pairs; j++) { cl[2 * j] = (const float4*)d_a[j]; n[2 * j] = n_a[j]; cl[2 * j + 1] = (const float4*)d_b[j]; n[2 * j + 1] = n_b[j]; }
@@ -263,11 +251,10 @@ extern "C" int qn_kf_overlap_points(qn_kf_store* s, uint32_t pair_slot, int dir,
   if (pair_slot >= st->slots.size()) return QN_ERR_INVALID_ARG;
   const OvSlot& o = st->slots[pair_slot];
   if (o.status != QN_OK) return QN_ERR_NOT_READY;
-  if (hipSetDevice(qn_kf_int_device(s)) != hipSuccess) return fail(s, "qn_kf_overlap_points: hipSetDevice failed");
+  QN_KFCHK(s, hipSetDevice(qn_kf_int_device(s)));
   hipStream_t stream = qn_kf_int_stream(s);
-  bool ok = true;
-  if (nn_d2_out) ok = ok && hipMemcpyAsync(nn_d2_out, st->d2 + o.p0[dir], sizeof(float) * o.n[dir], hipMemcpyDeviceToHost, stream) == hipSuccess;
-  if (nn_idx_out) ok = ok && hipMemcpyAsync(nn_idx_out, st->idx + o.p0[dir], sizeof(int32_t) * o.n[dir], hipMemcpyDeviceToHost, stream) == hipSuccess;
-  ok = ok && hipStreamSynchronize(stream) == hipSuccess;
-  return ok ? QN_OK : fail(s, "qn_kf_overlap_points: the copy failed");
+  if (nn_d2_out) QN_KFCHK(s, hipMemcpyAsync(nn_d2_out, st->d2.p + o.p0[dir], sizeof(float) * o.n[dir], hipMemcpyDeviceToHost, stream));
+  if (nn_idx_out) QN_KFCHK(s, hipMemcpyAsync(nn_idx_out, st->idx.p + o.p0[dir], sizeof(int32_t) * o.n[dir], hipMemcpyDeviceToHost, stream));
+  QN_KFCHK(s, hipStreamSynchronize(stream));
+  return QN_OK;
 }

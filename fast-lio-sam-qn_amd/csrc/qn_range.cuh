@@ -9,6 +9,7 @@
 #include <cstddef>
 #include <vector>
 #include "../../include/qn_engine.h"
+#include "qn_kf_buf.h"
 
 #define FS_BLOCK 512
 #define FS_ITERS 4
@@ -103,11 +104,11 @@ struct FsSlot { uint32_t p0[2], n[2]; };
 // call).
 struct RangeState {
   qn_range_params p{};
-  double* tab = nullptr;                                 // t [n_rows + 1], padded to 16 bytes, then (cos, sin) [n_cols]
-  uint32_t* img = nullptr;                               // per keyframe id: near [n_rows * n_cols], far [n_rows * n_cols], as f32 bit patterns
-  size_t cap = 0;
+  DevBuf<double> tab;                                    // t [n_rows + 1], padded to 16 bytes, then (cos, sin) [n_cols]
+  DevBuf<uint32_t> img;                                  // per keyframe id: near [n_rows * n_cols], far [n_rows * n_cols], as f32 bit patterns
+  size_t cap = 0;                                        // keyframe slots of img
   std::vector<uint8_t> described;
-  bool live = false; std::vector<FsSlot> slots; uint8_t* cls = nullptr; size_t cls_cap = 0;
+  bool live = false; std::vector<FsSlot> slots; DevBuf<uint8_t> cls;
 };
 inline size_t range_cs_offset(uint32_t nr) { return ((size_t)nr + 2) & ~(size_t)1; }      // in doubles: the column table is 16-byte aligned
 inline size_t range_lds_bytes(const RangeState* st) { const size_t b = sizeof(double2) * (size_t)st->p.n_cols; return b <= FS_LDS_MAX ? b : 0; }

@@ -22,7 +22,7 @@
 #include <string>
 #include <vector>
 #include "../../include/qn_engine.h"
-#include "qn_kf_internal.h"
+#include "qn_kf_buf.h"
 
 namespace qn {
 
@@ -294,21 +294,11 @@ __global__ void k_sc_gather(const unsigned long long* __restrict__ keys, const i
 // The store's Scan Context state: parameters, host tables on the device, and descriptor slots indexed by keyframe id (grown with the store).
 struct ScState {
   qn_sc_params p{};
-  double* tab = nullptr;                                   // edges2 [nr + 1], cos [ns], sin [ns]
-  float* desc = nullptr; double* rk = nullptr; double* cn = nullptr; double* ss = nullptr;
-  size_t cap = 0;
+  DevBuf<double> tab;                                      // edges2 [nr + 1], cos [ns], sin [ns]
+  DevBuf<float> desc; DevBuf<double> rk, cn, ss;           // per keyframe id: n_rings * n_sectors, n_rings, n_sectors, n_sectors
+  size_t cap = 0;                                          // keyframe slots of the four
   std::vector<uint8_t> described;                          // per keyframe id, under the current parameters
 };
-
-static void sc_free_arrays(ScState* st) {
-  (void)hipFree(st->desc); (void)hipFree(st->rk); (void)hipFree(st->cn); (void)hipFree(st->ss);
-  st->desc = nullptr; st->rk = nullptr; st->cn = nullptr; st->ss = nullptr; st->cap = 0;
-}
-static void sc_release(void* v) {                          // called by qn_kf_store_destroy after its stream has drained
-  ScState* st = (ScState*)v;
-  sc_free_arrays(st); (void)hipFree(st->tab);
-  delete st;
-}
 
 static qn_sc_params sc_default_params() {
   qn_sc_params p{};
@@ -336,50 +326,31 @@ static std::vector<double> sc_tables(const qn_sc_params& p) {
   return t;
 }
 
-#define SCCHK(s, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { qn_kf_int_set_error((s), (std::string(#call) + " -> " + hipGetErrorString(e_)).c_str()); return QN_ERR_HIP; } } while (0)
-
-static int sc_upload_tables(qn_kf_store* s, ScState* st) {
-  const std::vector<double> t = sc_tables(st->p);
-  (void)hipFree(st->tab); st->tab = nullptr;
-  SCCHK(s, hipMalloc(&st->tab, sizeof(double) * t.size()));
-  SCCHK(s, hipMemcpy(st->tab, t.data(), sizeof(double) * t.size(), hipMemcpyHostToDevice));
-  return QN_OK;
-}
 static int sc_state(qn_kf_store* s, ScState** out) {
-  ScState* st = (ScState*)qn_kf_int_ext(s, QN_KF_INT_EXT_SC);
-  if (!st) {
-    SCCHK(s, hipSetDevice(qn_kf_int_device(s)));
-    st = new ScState();
+  return qn_kf_ext_state(s, QN_KF_INT_EXT_SC, out, [s](ScState* st) -> int {
+    QN_KFCHK(s, hipSetDevice(qn_kf_int_device(s)));
     st->p = sc_default_params();
-    const int rc = sc_upload_tables(s, st);
-    if (rc != QN_OK) { sc_release(st); return rc; }
-    qn_kf_int_set_ext(s, QN_KF_INT_EXT_SC, st, sc_release);
-  }
-  *out = st;
-  return QN_OK;
+    const std::vector<double> t = sc_tables(st->p);
+    return st->tab.assign(s, t.data(), t.size()) ? QN_OK : QN_ERR_HIP;
+  });
 }
-// descriptor slots for every keyframe id < n (contents of existing slots kept)
+// descriptor slots for every keyframe id < n (contents of existing slots kept).  All four arrays move or none: exact-size temporaries take the copies
+// behind one synchronisation and are swapped in at the end; an early return frees them and leaves the old slots.
 static int sc_reserve(qn_kf_store* s, ScState* st, size_t n) {
   if (n <= st->cap) return QN_OK;
   const size_t cap = std::max<size_t>({n, 2 * st->cap, 64});
-  const size_t nb = (size_t)st->p.n_rings * st->p.n_sectors;
-  float* d = nullptr; double *r = nullptr, *c = nullptr, *q = nullptr;
-  if (hipMalloc(&d, sizeof(float) * nb * cap) != hipSuccess || hipMalloc(&r, sizeof(double) * st->p.n_rings * cap) != hipSuccess ||
-      hipMalloc(&c, sizeof(double) * st->p.n_sectors * cap) != hipSuccess || hipMalloc(&q, sizeof(double) * st->p.n_sectors * cap) != hipSuccess) {
-    (void)hipFree(d); (void)hipFree(r); (void)hipFree(c); (void)hipFree(q);
-    qn_kf_int_set_error(s, "qn_kf_sc: descriptor storage allocation failed");
-    return QN_ERR_HIP;
-  }
-  const hipStream_t str = qn_kf_int_stream(s);
+  const size_t nr = st->p.n_rings, ns = st->p.n_sectors;
+  DevBuf<float> d; DevBuf<double> r, c, q;
+  if (!d.grow(s, nr * ns * cap, true) || !r.grow(s, nr * cap, true) || !c.grow(s, ns * cap, true) || !q.grow(s, ns * cap, true)) return QN_ERR_HIP;
   if (st->cap) {
-    SCCHK(s, hipMemcpyAsync(d, st->desc, sizeof(float) * nb * st->cap, hipMemcpyDeviceToDevice, str));
-    SCCHK(s, hipMemcpyAsync(r, st->rk, sizeof(double) * st->p.n_rings * st->cap, hipMemcpyDeviceToDevice, str));
-    SCCHK(s, hipMemcpyAsync(c, st->cn, sizeof(double) * st->p.n_sectors * st->cap, hipMemcpyDeviceToDevice, str));
-    SCCHK(s, hipMemcpyAsync(q, st->ss, sizeof(double) * st->p.n_sectors * st->cap, hipMemcpyDeviceToDevice, str));
-    SCCHK(s, hipStreamSynchronize(str));                    // the old slots may go
+    const hipStream_t str = qn_kf_int_stream(s);
+    QN_KFCHK(s, hipMemcpyAsync(d.p, st->desc.p, sizeof(float) * st->desc.cap, hipMemcpyDeviceToDevice, str));
+    QN_KFCHK(s, hipMemcpyAsync(r.p, st->rk.p, sizeof(double) * st->rk.cap, hipMemcpyDeviceToDevice, str));
+    QN_KFCHK(s, hipMemcpyAsync(c.p, st->cn.p, sizeof(double) * st->cn.cap, hipMemcpyDeviceToDevice, str));
+    QN_KFCHK(s, hipMemcpyAsync(q.p, st->ss.p, sizeof(double) * st->ss.cap, hipMemcpyDeviceToDevice, str));
+    QN_KFCHK(s, hipStreamSynchronize(str));                  // the old slots may go
   }
-  sc_free_arrays(st);
-  st->desc = d; st->rk = r; st->cn = c; st->ss = q; st->cap = cap;
+  st->desc.swap(d); st->rk.swap(r); st->cn.swap(c); st->ss.swap(q); st->cap = cap;      // (the old slots go with d, r, c, q)
   return QN_OK;
 }
 
@@ -391,12 +362,13 @@ extern "C" int qn_kf_sc_set_params(qn_kf_store* s, const qn_sc_params* p) {
   const qn_sc_params& o = st->p;
   const bool same_shape = o.n_rings == p->n_rings && o.n_sectors == p->n_sectors && o.max_radius == p->max_radius && o.lidar_height == p->lidar_height;
   if (same_shape) { st->p.ringkey_prefilter = p->ringkey_prefilter; return QN_OK; }   // the descriptors do not depend on the prefilter
-  SCCHK(s, hipSetDevice(qn_kf_int_device(s)));
-  SCCHK(s, hipStreamSynchronize(qn_kf_int_stream(s)));      // no launch of this store may still read the old slots
-  sc_free_arrays(st);
+  QN_KFCHK(s, hipSetDevice(qn_kf_int_device(s)));
+  QN_KFCHK(s, hipStreamSynchronize(qn_kf_int_stream(s)));   // no launch of this store may still read the old slots
+  st->desc.reset(); st->rk.reset(); st->cn.reset(); st->ss.reset(); st->cap = 0;
   st->described.assign(st->described.size(), 0);
   st->p = *p; st->p.pad_ = 0;
-  return sc_upload_tables(s, st);
+  const std::vector<double> t = sc_tables(st->p);
+  return st->tab.assign(s, t.data(), t.size()) ? QN_OK : QN_ERR_HIP;
 }
 extern "C" int qn_kf_sc_get_params(qn_kf_store* s, qn_sc_params* p) {
   if (!s || !p) return QN_ERR_INVALID_ARG;
@@ -414,7 +386,7 @@ extern "C" int qn_kf_sc_describe(qn_kf_store* s, const int32_t* ids, uint32_t co
   ScState* st = nullptr;
   int rc = sc_state(s, &st);
   if (rc != QN_OK) return rc;
-  SCCHK(s, hipSetDevice(qn_kf_int_device(s)));
+  QN_KFCHK(s, hipSetDevice(qn_kf_int_device(s)));
   if (st->described.size() < n_kf) st->described.resize(n_kf, 0);
   // the ids not described yet, each once (describing again would write the same bits)
   std::vector<uint8_t> seen(n_kf, 0);
@@ -436,20 +408,20 @@ extern "C" int qn_kf_sc_describe(qn_kf_store* s, const int32_t* ids, uint32_t co
   uint32_t* d_bins = (uint32_t*)qn_kf_int_scratch(s, 1, sizeof(uint32_t) * (size_t)nb * chunk);
   if (!d_kfs || !d_bins) { qn_kf_int_set_error(s, "qn_kf_sc_describe: scratch allocation failed"); return QN_ERR_HIP; }
   const hipStream_t str = qn_kf_int_stream(s);
-  SCCHK(s, hipMemcpyAsync(d_kfs, todo.data(), sizeof(qn::ScKf) * todo.size(), hipMemcpyHostToDevice, str));
+  QN_KFCHK(s, hipMemcpyAsync(d_kfs, todo.data(), sizeof(qn::ScKf) * todo.size(), hipMemcpyHostToDevice, str));
   for (size_t a = 0; a < todo.size(); a += chunk) {
     const uint32_t m = (uint32_t)std::min<size_t>(chunk, todo.size() - a);
     uint32_t nmax = 0;
     for (uint32_t k = 0; k < m; k++) nmax = std::max(nmax, todo[a + k].n);
-    SCCHK(s, hipMemsetAsync(d_bins, 0, sizeof(uint32_t) * (size_t)nb * m, str));
+    QN_KFCHK(s, hipMemsetAsync(d_bins, 0, sizeof(uint32_t) * (size_t)nb * m, str));
     if (nmax)
       hipLaunchKernelGGL(qn::k_sc_bin, dim3((nmax + SC_BIN_TILE - 1) / SC_BIN_TILE, m), dim3(SC_BIN_BLOCK), sizeof(uint32_t) * nb, str,
-                         (const qn::ScKf*)(d_kfs + a), (const double*)st->tab, nr, ns, st->p.lidar_height, d_bins);
+                         (const qn::ScKf*)(d_kfs + a), (const double*)st->tab.p, nr, ns, st->p.lidar_height, d_bins);
     hipLaunchKernelGGL(qn::k_sc_finish, dim3(m), dim3(SC_BIN_BLOCK), 0, str, (const qn::ScKf*)(d_kfs + a), (const uint32_t*)d_bins, nr, ns,
-                       st->desc, st->rk, st->cn, st->ss);
+                       st->desc.p, st->rk.p, st->cn.p, st->ss.p);
   }
-  SCCHK(s, hipGetLastError());
-  SCCHK(s, hipStreamSynchronize(str));                      // the one synchronisation: the scratch (host table) may be reused
+  QN_KFCHK(s, hipGetLastError());
+  QN_KFCHK(s, hipStreamSynchronize(str));                   // the one synchronisation: the scratch (host table) may be reused
   for (const qn::ScKf& k : todo) st->described[k.id] = 1;
   return QN_OK;
 }
@@ -458,13 +430,13 @@ extern "C" int qn_kf_sc_get(qn_kf_store* s, int32_t id, float* desc, double* rin
   if (!s || id < 0 || (size_t)id >= qn_kf_int_count(s)) return QN_ERR_INVALID_ARG;
   ScState* st = (ScState*)qn_kf_int_ext(s, QN_KF_INT_EXT_SC);
   if (!st || (size_t)id >= st->described.size() || !st->described[id]) return QN_ERR_NOT_READY;
-  SCCHK(s, hipSetDevice(qn_kf_int_device(s)));
+  QN_KFCHK(s, hipSetDevice(qn_kf_int_device(s)));
   const hipStream_t str = qn_kf_int_stream(s);
   const size_t nr = st->p.n_rings, ns = st->p.n_sectors;
-  if (desc) SCCHK(s, hipMemcpyAsync(desc, st->desc + (size_t)id * nr * ns, sizeof(float) * nr * ns, hipMemcpyDeviceToHost, str));
-  if (ringkey) SCCHK(s, hipMemcpyAsync(ringkey, st->rk + (size_t)id * nr, sizeof(double) * nr, hipMemcpyDeviceToHost, str));
-  if (colnorm) SCCHK(s, hipMemcpyAsync(colnorm, st->cn + (size_t)id * ns, sizeof(double) * ns, hipMemcpyDeviceToHost, str));
-  SCCHK(s, hipStreamSynchronize(str));
+  if (desc) QN_KFCHK(s, hipMemcpyAsync(desc, st->desc.p + (size_t)id * nr * ns, sizeof(float) * nr * ns, hipMemcpyDeviceToHost, str));
+  if (ringkey) QN_KFCHK(s, hipMemcpyAsync(ringkey, st->rk.p + (size_t)id * nr, sizeof(double) * nr, hipMemcpyDeviceToHost, str));
+  if (colnorm) QN_KFCHK(s, hipMemcpyAsync(colnorm, st->cn.p + (size_t)id * ns, sizeof(double) * ns, hipMemcpyDeviceToHost, str));
+  QN_KFCHK(s, hipStreamSynchronize(str));
   return QN_OK;
 }
 
@@ -480,7 +452,7 @@ extern "C" int qn_kf_sc_query(qn_kf_store* s, const int32_t* query_ids, uint32_t
   for (uint32_t k = 0; k < nq; k++)
     if (!st || (size_t)query_ids[k] >= st->described.size() || !st->described[query_ids[k]]) return QN_ERR_NOT_READY;
 
-  SCCHK(s, hipSetDevice(qn_kf_int_device(s)));
+  QN_KFCHK(s, hipSetDevice(qn_kf_int_device(s)));
   const hipStream_t str = qn_kf_int_stream(s);
   const uint32_t N = (uint32_t)n_kf, nr = st->p.n_rings, ns = st->p.n_sectors, P = st->p.ringkey_prefilter, K = top_k;
   const bool pre = P > 0;
@@ -506,7 +478,7 @@ extern "C" int qn_kf_sc_query(qn_kf_store* s, const int32_t* query_ids, uint32_t
   memcpy(h_in.data(), stamps, sizeof(double) * N);
   memcpy(h_in.data() + sizeof(double) * N, query_ids, sizeof(int32_t) * nq);
   for (uint32_t c = 0; c < N; c++) h_in[sizeof(double) * N + sizeof(int32_t) * nq + c] = c < st->described.size() ? (char)st->described[c] : 0;
-  SCCHK(s, hipMemcpyAsync(d_in, h_in.data(), in_bytes, hipMemcpyHostToDevice, str));
+  QN_KFCHK(s, hipMemcpyAsync(d_in, h_in.data(), in_bytes, hipMemcpyHostToDevice, str));
   const double* d_stamps = (const double*)d_in;
   const int32_t* d_q = (const int32_t*)(d_in + sizeof(double) * N);
   const uint8_t* d_valid = (const uint8_t*)(d_in + sizeof(double) * N + sizeof(int32_t) * nq);
@@ -515,7 +487,7 @@ extern "C" int qn_kf_sc_query(qn_kf_store* s, const int32_t* query_ids, uint32_t
   int32_t* r_sh = r_ids + (size_t)nq * K;
   uint32_t* r_n = (uint32_t*)(r_sh + (size_t)nq * K);
   // k_sc_dist: waves per block from the LDS stage of one candidate (column sums of squares, then the descriptor), 16-byte aligned
-  const uint32_t stage = (uint32_t)((sizeof(double) * ns + sizeof(float) * nr * ns + 15) & ~(size_t)15);
+  const uint32_t stage = (uint32_t)qn_up16(sizeof(double) * ns + sizeof(float) * nr * ns);
   const uint32_t waves = std::max<uint32_t>(1, std::min<uint32_t>(4, (64u << 10) / stage));
   const uint32_t per_block = waves * SC_DIST_ITERS;
   for (uint32_t a = 0; a < nq; a += qc) {
@@ -524,21 +496,21 @@ extern "C" int qn_kf_sc_query(qn_kf_store* s, const int32_t* query_ids, uint32_t
     const int32_t* list = nullptr;
     const uint32_t* list_n = nullptr;
     if (pre) {
-      hipLaunchKernelGGL(qn::k_sc_ringkey, dim3((N + 255) / 256, rows), dim3(256), 0, str, (const double*)st->rk, nr, qids, d_stamps, d_valid, tdiff, N, d_rkeys);
+      hipLaunchKernelGGL(qn::k_sc_ringkey, dim3((N + 255) / 256, rows), dim3(256), 0, str, (const double*)st->rk.p, nr, qids, d_stamps, d_valid, tdiff, N, d_rkeys);
       uint32_t* ln = (uint32_t*)(d_list + (size_t)qc * P);
       hipLaunchKernelGGL(qn::k_sc_select, dim3(rows), dim3(SC_SEL_BLOCK), 0, str, (const unsigned long long*)d_rkeys, (const int32_t*)nullptr, N, P, d_list, ln);
       list = d_list; list_n = ln;
     }
     hipLaunchKernelGGL(qn::k_sc_dist, dim3((M + per_block - 1) / per_block, rows), dim3(64 * waves), (size_t)waves * stage, str,
-                       (const float*)st->desc, (const double*)st->ss, nr, ns, qids, d_stamps, d_valid, tdiff, list, list_n, M, stage, d_keys, d_shift);
+                       (const float*)st->desc.p, (const double*)st->ss.p, nr, ns, qids, d_stamps, d_valid, tdiff, list, list_n, M, stage, d_keys, d_shift);
     uint32_t* sel_n = (uint32_t*)(d_sel + (size_t)qc * K);
     hipLaunchKernelGGL(qn::k_sc_select, dim3(rows), dim3(SC_SEL_BLOCK), 0, str, (const unsigned long long*)d_keys, list, M, K, d_sel, sel_n);
     hipLaunchKernelGGL(qn::k_sc_gather, dim3((rows * K + 255) / 256), dim3(256), 0, str, (const unsigned long long*)d_keys, (const int32_t*)d_shift, list, M,
                        (const int32_t*)d_sel, (const uint32_t*)sel_n, rows, K, a, r_ids, r_d, r_sh, r_n);
   }
-  SCCHK(s, hipGetLastError());
-  SCCHK(s, hipMemcpyAsync(h_res, d_res, res_bytes, hipMemcpyDeviceToHost, str));
-  SCCHK(s, hipStreamSynchronize(str));                      // the one synchronisation of the call
+  QN_KFCHK(s, hipGetLastError());
+  QN_KFCHK(s, hipMemcpyAsync(h_res, d_res, res_bytes, hipMemcpyDeviceToHost, str));
+  QN_KFCHK(s, hipStreamSynchronize(str));                   // the one synchronisation of the call
   const size_t nk = (size_t)nq * K;
   memcpy(dist_out, h_res, sizeof(double) * nk);
   memcpy(ids_out, h_res + sizeof(double) * nk, sizeof(int32_t) * nk);

@@ -13,7 +13,7 @@
 #include <vector>
 #include "../../include/qn_engine.h"
 #include "qn_util_kernels.cuh"
-#include "qn_kf_internal.h"
+#include "qn_kf_buf.h"
 
 namespace qn {
 
@@ -139,8 +139,6 @@ static bool prims_ok(const qn_sim_prim* prims, uint32_t n) {
 }
 static bool table_ok(const double* v, uint32_t n) { if (!v) return false; for (uint32_t i = 0; i < n; i++) if (!(v[i] >= -1.0 && v[i] <= 1.0)) return false; return true; }
 
-#define SIMCHK(s, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { qn_kf_int_set_error((s), (std::string(#call) + " -> " + hipGetErrorString(e_)).c_str()); return QN_ERR_HIP; } } while (0)
-
 extern "C" int qn_sim_lidar_to_store(qn_kf_store* s, const qn_sim_prim* prims, uint32_t n_prims, const qn_sim_sensor* sen, const double* poses16,
                                      const uint32_t* seeds, uint32_t n_scans, int32_t* ids_out, uint32_t* n_out) {
   // ---- every argument is checked before anything is enqueued; the store is unchanged on any error return before the copies
@@ -155,7 +153,7 @@ extern "C" int qn_sim_lidar_to_store(qn_kf_store* s, const qn_sim_prim* prims, u
   if (!finite_all(poses16, 16 * (size_t)n_scans) || !prims_ok(prims, n_prims)) return QN_ERR_INVALID_ARG;
   if (qn_kf_int_count(s) + n_scans > 0x7fffffffull) return QN_ERR_CAPACITY;
 
-  SIMCHK(s, hipSetDevice(qn_kf_int_device(s)));
+  QN_KFCHK(s, hipSetDevice(qn_kf_int_device(s)));
   const hipStream_t st = qn_kf_int_stream(s);
   const size_t m = (size_t)rays * n_scans;                          // <= 2^27: every index below fits in uint32_t
   const uint32_t sbf = (uint32_t)((m + QN_BLOCK * QN_SCAN_ITEMS - 1) / (QN_BLOCK * QN_SCAN_ITEMS));
@@ -168,7 +166,7 @@ extern "C" int qn_sim_lidar_to_store(qn_kf_store* s, const qn_sim_prim* prims, u
   float4* d_cmp = (float4*)qn_kf_int_scratch(s, 5, sizeof(float4) * m);
   uint32_t* d_off = (uint32_t*)qn_kf_int_scratch(s, 6, sizeof(uint32_t) * (n_scans + 1));
   uint32_t* h_off = (uint32_t*)qn_kf_int_pinned(s, sizeof(uint32_t) * (n_scans + 1));
-  if (!d_in || !d_res || !d_flag || !d_pos || !d_sums || !d_cmp || !d_off || !h_off) { qn_kf_int_set_error(s, "qn_sim_lidar_to_store: scratch allocation failed"); return QN_ERR_HIP; }
+  if (!d_in || !d_res || !d_flag || !d_pos || !d_sums || !d_cmp || !d_off || !h_off) return qn_kf_fail(s, "qn_sim_lidar_to_store: scratch allocation failed");
 
   // inputs: primitives, the four tables, poses, seeds - one packed upload (8-byte aligned sections)
   char* w = d_in;
@@ -186,7 +184,7 @@ extern "C" int qn_sim_lidar_to_store(qn_kf_store* s, const qn_sim_prim* prims, u
   hw += tab;
   memcpy(hw, poses16, sizeof(double) * 16 * n_scans); hw += sizeof(double) * 16 * n_scans;
   memcpy(hw, seeds, sizeof(uint32_t) * n_scans);
-  SIMCHK(s, hipMemcpyAsync(d_in, h_in.data(), h_in.size(), hipMemcpyHostToDevice, st));
+  QN_KFCHK(s, hipMemcpyAsync(d_in, h_in.data(), h_in.size(), hipMemcpyHostToDevice, st));
 
   qn::SimSensor ss{d_tab, d_tab + sen->n_beams, d_tab + 2 * sen->n_beams, d_tab + 2 * sen->n_beams + sen->n_cols, sen->n_beams, sen->n_cols,
                    sen->min_range, sen->max_range, sen->sigma * 1.7320508075688772};
@@ -197,9 +195,9 @@ extern "C" int qn_sim_lidar_to_store(qn_kf_store* s, const qn_sim_prim* prims, u
   hipLaunchKernelGGL(qn::k_scan_add_total, dim3(sbf), dim3(QN_BLOCK), 0, st, d_pos, (uint32_t)m, (const uint32_t*)d_sums, (const uint32_t*)d_flag);
   hipLaunchKernelGGL(qn::k_sim_compact, dim3((uint32_t)((m + 255) / 256)), dim3(256), 0, st, (const float4*)d_res, (const uint32_t*)d_flag, (const uint32_t*)d_pos, (uint32_t)m, d_cmp);
   hipLaunchKernelGGL(qn::k_sim_offsets, dim3((n_scans + 1 + 255) / 256), dim3(256), 0, st, (const uint32_t*)d_pos, rays, n_scans, d_off);
-  SIMCHK(s, hipGetLastError());
-  SIMCHK(s, hipMemcpyAsync(h_off, d_off, sizeof(uint32_t) * (n_scans + 1), hipMemcpyDeviceToHost, st));
-  SIMCHK(s, hipStreamSynchronize(st));                              // sync 1 of 2: the per-scan counts size the keyframes
+  QN_KFCHK(s, hipGetLastError());
+  QN_KFCHK(s, hipMemcpyAsync(h_off, d_off, sizeof(uint32_t) * (n_scans + 1), hipMemcpyDeviceToHost, st));
+  QN_KFCHK(s, hipStreamSynchronize(st));                           // sync 1 of 2: the per-scan counts size the keyframes
 
   // each scan -> one keyframe through the adopt path of qn_kf_add_device (float4 records, intensity at byte 12)
   std::vector<float4*> bufs(n_scans, nullptr);

@@ -21,7 +21,6 @@
 #include <string>
 #include <vector>
 #include "../../include/qn_engine.h"
-#include "qn_kf_internal.h"
 #include "qn_range.cuh"
 
 namespace {
@@ -150,17 +149,9 @@ struct StaticState {
   bool live = false;
   std::vector<int32_t> ids; std::vector<double> poses; std::vector<SvHostEntry> ent;
   uint64_t total = 0;
-  uint8_t* votes = nullptr; size_t votes_cap = 0;        // 3 * votes_cap bytes: the planes of the live call are `total` apart
-  float4* kept = nullptr; size_t kept_cap = 0;
+  DevBuf<uint8_t> votes;                                 // three planes, those of the live call `total` apart
+  DevBuf<float4> kept;
 };
-void static_release(void* v) {                           // called by qn_kf_store_destroy after its stream has drained
-  StaticState* st = (StaticState*)v;
-  (void)hipFree(st->votes); (void)hipFree(st->kept);
-  delete st;
-}
-int fail(qn_kf_store* s, const char* msg) { qn_kf_int_set_error(s, msg); return QN_ERR_HIP; }
-#define SVCHK(s, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { qn_kf_int_set_error((s), (std::string(#call) + " -> " + hipGetErrorString(e_)).c_str()); return QN_ERR_HIP; } } while (0)
-size_t up16(size_t b) { return (b + 15) & ~(size_t)15; }
 
 }  // namespace
 
@@ -199,38 +190,23 @@ extern "C" int qn_kf_static_classify(qn_kf_store* s, const int32_t* ids, const d
     total += n; tiles += (n + FS_TILE - 1) / FS_TILE; nmax = std::max(nmax, n);
     if (total > 0xFFFFFFFFull) return QN_ERR_CAPACITY;
   }
-  SVCHK(s, hipSetDevice(qn_kf_int_device(s)));
-  StaticState* st = (StaticState*)qn_kf_int_ext(s, QN_KF_INT_EXT_STATIC);
-  if (!st) {
-    st = new (std::nothrow) StaticState();
-    if (!st) return fail(s, "qn_kf_static_classify: out of memory");
-    qn_kf_int_set_ext(s, QN_KF_INT_EXT_STATIC, st, static_release);
-  }
+  QN_KFCHK(s, hipSetDevice(qn_kf_int_device(s)));
+  StaticState* st = nullptr;
+  const int rc = qn_kf_ext_state(s, QN_KF_INT_EXT_STATIC, &st);
+  if (rc != QN_OK) return rc;
   const hipStream_t str = qn_kf_int_stream(s);
   const uint32_t nt = (uint32_t)tiles;
-  const size_t ent_bytes = up16(sizeof(SvEntry) * count), wit_bytes = up16(sizeof(SvWit) * std::max<uint32_t>(n_wit, 1)), rem_bytes = sizeof(uint32_t) * count;
+  const size_t ent_bytes = qn_up16(sizeof(SvEntry) * count), wit_bytes = qn_up16(sizeof(SvWit) * std::max<uint32_t>(n_wit, 1)), rem_bytes = sizeof(uint32_t) * count;
   SvEntry* d_ent = (SvEntry*)qn_kf_int_scratch(s, 0, ent_bytes);
   SvWit* d_wit = (SvWit*)qn_kf_int_scratch(s, 1, wit_bytes);
   uint32_t* d_tile = (uint32_t*)qn_kf_int_scratch(s, 2, sizeof(uint32_t) * (2 * (size_t)nt + 1));      // kept counts [nt], then offsets [nt + 1]
   uint32_t* d_rem = (uint32_t*)qn_kf_int_scratch(s, 3, rem_bytes);
   char* h = (char*)qn_kf_int_pinned(s, ent_bytes + wit_bytes + rem_bytes);
-  if (!d_ent || !d_wit || !d_tile || !d_rem || !h) return fail(s, "qn_kf_static_classify: scratch allocation failed");
+  if (!d_ent || !d_wit || !d_tile || !d_rem || !h) return qn_kf_fail(s, "qn_kf_static_classify: scratch allocation failed");
   // from here on the previous classify is gone
   st->live = false;
-  if (total > st->votes_cap) {
-    uint8_t* v = nullptr;
-    const size_t cap = (size_t)(total + total / 2);
-    if (hipMalloc(&v, 3 * cap) != hipSuccess) { (void)hipGetLastError(); return fail(s, "qn_kf_static_classify: hipMalloc failed"); }
-    (void)hipFree(st->votes);                               // (waits for the device: nothing still reads the old bytes)
-    st->votes = v; st->votes_cap = cap;
-  }
-  if (total > st->kept_cap) {
-    float4* k = nullptr;
-    const size_t cap = (size_t)(total + total / 2);
-    if (hipMalloc(&k, sizeof(float4) * cap) != hipSuccess) { (void)hipGetLastError(); return fail(s, "qn_kf_static_classify: hipMalloc failed"); }
-    (void)hipFree(st->kept);
-    st->kept = k; st->kept_cap = cap;
-  }
+  // (3 * total bytes: grows at the same totals as a buffer of `total` three-byte records would)
+  if (!st->votes.grow(s, 3 * (size_t)total) || !st->kept.grow(s, total)) return QN_ERR_HIP;
   SvEntry* h_ent = (SvEntry*)h; SvWit* h_wit = (SvWit*)(h + ent_bytes); uint32_t* h_rem = (uint32_t*)(h + ent_bytes + wit_bytes);
   uint32_t b0 = 0;
   for (uint32_t e = 0; e < count; e++) {
@@ -246,15 +222,15 @@ extern "C" int qn_kf_static_classify(qn_kf_store* s, const int32_t* ids, const d
       g.img = ids[w]; g.pad[0] = g.pad[1] = g.pad[2] = 0;
     }
   }
-  SVCHK(s, hipMemcpyAsync(d_ent, h_ent, sizeof(SvEntry) * count, hipMemcpyHostToDevice, str));
-  if (n_wit) SVCHK(s, hipMemcpyAsync(d_wit, h_wit, sizeof(SvWit) * n_wit, hipMemcpyHostToDevice, str));
-  uint8_t* d_st = st->votes; uint8_t* d_ag = st->votes + total; uint8_t* d_rm = st->votes + 2 * total;
+  QN_KFCHK(s, hipMemcpyAsync(d_ent, h_ent, sizeof(SvEntry) * count, hipMemcpyHostToDevice, str));
+  if (n_wit) QN_KFCHK(s, hipMemcpyAsync(d_wit, h_wit, sizeof(SvWit) * n_wit, hipMemcpyHostToDevice, str));
+  uint8_t* d_st = st->votes.p; uint8_t* d_ag = d_st + total; uint8_t* d_rm = d_st + 2 * total;
   if (nt) {
     const qn_range_params p = rs ? rs->p : qn_range_params{};      // (records but no witness at all: nothing is projected, the tables are not read)
-    const double* trow = rs ? rs->tab : nullptr;
-    const double2* cs = rs ? (const double2*)(rs->tab + range_cs_offset(p.n_rows)) : nullptr;
+    const double* trow = rs ? rs->tab.p : nullptr;
+    const double2* cs = rs ? (const double2*)(rs->tab.p + range_cs_offset(p.n_rows)) : nullptr;
     const size_t lds = rs ? range_lds_bytes(rs) : 0;
-    const uint32_t* img = rs ? rs->img : nullptr;
+    const uint32_t* img = rs ? rs->img.p : nullptr;
     for (uint32_t a = 0; a < count; a += SV_CHUNK) {
       const uint32_t m = std::min<uint32_t>(SV_CHUNK, count - a);
       uint32_t cmax = 0;
@@ -273,14 +249,14 @@ extern "C" int qn_kf_static_classify(qn_kf_store* s, const int32_t* ids, const d
       for (uint32_t k = 0; k < m; k++) cmax = std::max(cmax, ent[a + k].n);
       if (!cmax) continue;
       hipLaunchKernelGGL(k_static_compact, dim3((cmax + FS_TILE - 1) / FS_TILE, m), dim3(FS_BLOCK), 0, str, (const SvEntry*)(d_ent + a), (const uint8_t*)d_rm,
-                         (const uint32_t*)(d_tile + nt), st->kept);
+                         (const uint32_t*)(d_tile + nt), st->kept.p);
     }
-    SVCHK(s, hipGetLastError());
-    SVCHK(s, hipMemcpyAsync(h_rem, d_rem, rem_bytes, hipMemcpyDeviceToHost, str));
+    QN_KFCHK(s, hipGetLastError());
+    QN_KFCHK(s, hipMemcpyAsync(h_rem, d_rem, rem_bytes, hipMemcpyDeviceToHost, str));
   } else {
     memset(h_rem, 0, rem_bytes);
   }
-  SVCHK(s, hipStreamSynchronize(str));                      // the one synchronisation of the call
+  QN_KFCHK(s, hipStreamSynchronize(str));                   // the one synchronisation of the call
   uint32_t koff = 0;
   for (uint32_t e = 0; e < count; e++) {
     ent[e].kept_off = koff; ent[e].kept_n = ent[e].n - h_rem[e]; koff += ent[e].kept_n;
@@ -299,12 +275,12 @@ extern "C" int qn_kf_static_points(qn_kf_store* s, uint32_t entry, uint8_t* seen
   if (entry >= st->ent.size()) return QN_ERR_INVALID_ARG;
   const SvHostEntry& o = st->ent[entry];
   if (o.n == 0) return QN_OK;
-  SVCHK(s, hipSetDevice(qn_kf_int_device(s)));
+  QN_KFCHK(s, hipSetDevice(qn_kf_int_device(s)));
   const hipStream_t str = qn_kf_int_stream(s);
   uint8_t* out[3] = {seen_through_out, agree_out, removed_out};
   for (int k = 0; k < 3; k++)
-    if (out[k]) SVCHK(s, hipMemcpyAsync(out[k], st->votes + (size_t)k * st->total + o.p0, o.n, hipMemcpyDeviceToHost, str));
-  SVCHK(s, hipStreamSynchronize(str));
+    if (out[k]) QN_KFCHK(s, hipMemcpyAsync(out[k], st->votes.p + (size_t)k * st->total + o.p0, o.n, hipMemcpyDeviceToHost, str));
+  QN_KFCHK(s, hipStreamSynchronize(str));
   return QN_OK;
 }
 
@@ -318,6 +294,6 @@ extern "C" int qn_kf_build_map_static(qn_kf_store* s, double leaf, const float**
     if ((size_t)st->ids[e] >= qn_kf_int_count(s) || qn_kf_int_keyframe(s, st->ids[e], &n) != st->ent[e].pts || n != st->ent[e].n) return QN_ERR_NOT_READY;
   }
   std::vector<const float4*> pts(count); std::vector<uint32_t> n(count); std::vector<uint8_t> has_i(count);
-  for (uint32_t e = 0; e < count; e++) { pts[e] = st->kept + st->ent[e].kept_off; n[e] = st->ent[e].kept_n; has_i[e] = st->ent[e].has_i; }
+  for (uint32_t e = 0; e < count; e++) { pts[e] = st->kept.p + st->ent[e].kept_off; n[e] = st->ent[e].kept_n; has_i[e] = st->ent[e].has_i; }
   return qn_kf_int_build_map_from(s, pts.data(), n.data(), has_i.data(), st->poses.data(), count, leaf, d_xyzi_out, n_out);
 }

@@ -17,7 +17,7 @@
 #include <memory>
 #include <vector>
 #include "../../include/qn_engine.h"
-#include "qn_kf_internal.h"
+#include "qn_kf_buf.h"
 
 int qn_ctx_int_device(const qn_ctx* c);
 
@@ -127,10 +127,8 @@ struct VerifyState {
   bool c2f() const { return kind == QN_KF_VERIFY_C2F || kind == QN_KF_VERIFY_SUBMAP_C2F; }
   int from() const { return kind >= QN_KF_VERIFY_SUBMAP ? QN_KF_VERIFY_FROM_SUBMAPS : kind; }
   std::vector<qn_kf_int_verify_pair> p; std::vector<size_t> off;
-  float4* arena = nullptr; size_t arena_cap = 0;
-  ~VerifyState() { if (arena) (void)hipFree(arena); }
+  DevBuf<float4> arena;
 };
-void verify_release(void* p) { delete (VerifyState*)p; }
 
 // the two clouds qn_kf_verify_cloud computes: COARSE = transformPcd(src, T_quatro) (k_transform_cloud_f64's f64 order, rounded to f32); FINAL = that (or src on
 // the GICP path) through the GICP T as align() fills aligned_ (k_transform_cloud: xform_query<1> with the f32 entries).  One point per thread.
@@ -158,12 +156,9 @@ __global__ void k_verify_cloud(const float4* __restrict__ in, uint32_t n, Verify
 }  // namespace
 
 int qn_kf_int_verify_record(qn_kf_store* s, int kind, const qn_kf_int_verify_pair* p, uint32_t n) {
-  VerifyState* st = (VerifyState*)qn_kf_int_ext(s, QN_KF_INT_EXT_VERIFY);
-  if (!st) {
-    st = new (std::nothrow) VerifyState();
-    if (!st) return QN_ERR_HIP;
-    qn_kf_int_set_ext(s, QN_KF_INT_EXT_VERIFY, st, verify_release);
-  }
+  VerifyState* st = nullptr;
+  const int rc = qn_kf_ext_state(s, QN_KF_INT_EXT_VERIFY, &st);
+  if (rc != QN_OK) return rc;
   st->kind = kind; st->p.assign(p, p + n); st->off.assign(n + 1, 0);
   for (uint32_t j = 0; j < n; j++) st->off[j + 1] = st->off[j] + 2 * (size_t)p[j].ns;
   st->live = true;
@@ -280,21 +275,19 @@ static int verify_cloud(qn_kf_store* s, uint32_t pair, int which, const float** 
   // COARSE needs the solved Quatro stage (coarse-to-fine only), FINAL the registration
   if (which == QN_VERIFY_COARSE ? (!st->c2f() || q.stage < 1) : q.stage < 2) return QN_ERR_NOT_READY;
   if (q.ns == 0 || !q.src) return QN_ERR_NOT_READY;
-  const int dev = qn_kf_int_device(s);
   hipStream_t stream = qn_kf_int_stream(s);
-  if (hipSetDevice(dev) != hipSuccess) { qn_kf_int_set_error(s, "qn_kf_verify_cloud: hipSetDevice failed"); return QN_ERR_HIP; }
+  QN_KFCHK(s, hipSetDevice(qn_kf_int_device(s)));
+  // the arena of the record's pairs, sized exactly; the record stays when it cannot be had (QN_ERR_HIP, the next call tries again)
   const size_t need = st->off.back();
-  if (need > st->arena_cap) {
-    if (st->arena) { (void)hipStreamSynchronize(stream); (void)hipFree(st->arena); st->arena = nullptr; st->arena_cap = 0; }
-    if (hipMalloc(&st->arena, sizeof(float4) * need) != hipSuccess) { (void)hipGetLastError(); st->arena = nullptr; qn_kf_int_set_error(s, "qn_kf_verify_cloud: hipMalloc failed"); return QN_ERR_HIP; }
-    st->arena_cap = need;
-  }
-  float4* out = st->arena + st->off[pair] + (which == QN_VERIFY_FINAL ? q.ns : 0);
+  if (need > st->arena.cap && st->arena.p) (void)hipStreamSynchronize(stream);      // (clouds handed out unsynchronised may still be read)
+  if (!st->arena.grow(s, need, true)) return QN_ERR_HIP;
+  float4* out = st->arena.p + st->off[pair] + (which == QN_VERIFY_FINAL ? q.ns : 0);
   VerifyXf m{};
   m.coarse = st->c2f() ? 1 : 0; m.fine = which == QN_VERIFY_FINAL ? 1 : 0;
   for (int i = 0; i < 12; i++) { m.Tq[i] = q.Tq[i]; m.Tg[i] = q.Tg[i]; }
   hipLaunchKernelGGL(k_verify_cloud, dim3((q.ns + 255) / 256), dim3(256), 0, stream, q.src, q.ns, m, out);
-  if (hipGetLastError() != hipSuccess || (sync && hipStreamSynchronize(stream) != hipSuccess)) { qn_kf_int_set_error(s, "qn_kf_verify_cloud: the transform failed"); return QN_ERR_HIP; }
+  QN_KFCHK(s, hipGetLastError());
+  if (sync) QN_KFCHK(s, hipStreamSynchronize(stream));
   *d_xyz = (const float*)out; *n = q.ns;
   return QN_OK;
 }
