@@ -263,7 +263,7 @@ struct qn_kf_store {
   DevBuf<char> tab; PinBuf<char> tab_host; PinBuf<qn::BBoxOut> seg_box_host; PinBuf<uint32_t> seg_res_host;
   // the output slots: qn_kf_assemble's 0 / 1, the corrected global map, qn_kf_assemble_batch's (all submaps in one buffer)
   DevBuf<float4> out[2]; uint32_t out_n[2] = {0, 0};
-  DevBuf<float4> map; uint32_t map_n = 0;
+  DevBuf<float4> map; uint32_t map_n = 0; uint64_t map_gen = 0;                                 // map_gen: advanced by every attempt to build a map
   DevBuf<float4> bt_out; std::vector<const float4*> bt_ptr; std::vector<uint32_t> bt_n;
   // scratch of other translation units (the ray-caster, qn_sim.hip), in bytes, sized exactly as asked: see qn_kf_internal.h
   DevBuf<char> int_scratch[QN_KF_INT_SCRATCH]; PinBuf<char> int_pinned;
@@ -734,7 +734,7 @@ extern "C" int qn_kf_build_map(qn_kf_store* s, const int32_t* ids, const double*
                                const float** d_xyzi_out, uint32_t* n_out) {
   if (!s || (count && (!ids || !poses)) || !d_xyzi_out || !n_out || !(leaf > 0)) return QN_ERR_INVALID_ARG;
   *d_xyzi_out = nullptr; *n_out = 0;
-  s->map_n = 0; s->last_error.clear();
+  s->map_n = 0; s->map_gen++; s->last_error.clear();
   if (count == 0) return QN_ERR_EMPTY_CLOUD;
   if (!ids_valid(s, ids, 0, count)) return QN_ERR_INVALID_ARG;
   return build_map_sources(s, sources_of(s, ids, 0, count).data(), poses, count, leaf, d_xyzi_out, n_out);
@@ -742,11 +742,16 @@ extern "C" int qn_kf_build_map(qn_kf_store* s, const int32_t* ids, const double*
 int qn_kf_int_build_map_from(qn_kf_store* s, const float4* const* pts, const uint32_t* n, const uint8_t* has_i, const double* poses, uint32_t count, double leaf,
                              const float** d_xyzi_out, uint32_t* n_out) {
   *d_xyzi_out = nullptr; *n_out = 0;
-  s->map_n = 0; s->last_error.clear();
+  s->map_n = 0; s->map_gen++; s->last_error.clear();
   if (count == 0) return QN_ERR_EMPTY_CLOUD;
   std::vector<VoxSrc> src(count);
   for (uint32_t k = 0; k < count; k++) src[k] = VoxSrc{n[k] ? pts[k] : nullptr, n[k], has_i[k]};
   return build_map_sources(s, src.data(), poses, count, leaf, d_xyzi_out, n_out);
+}
+
+const float4* qn_kf_int_map(const qn_kf_store* s, uint32_t* n, uint64_t* generation) {
+  *n = s->map_n; *generation = s->map_gen;
+  return s->map_n ? s->map.p : nullptr;
 }
 
 // the map into host records: only the 12 xyz bytes (offset 0) and the 4 intensity bytes (offset ioff) of each are written

@@ -712,6 +712,19 @@ class StaticParams(C.Structure):
         return staticmap.StaticParams(int(self.min_see_through), int(self.agree_weight))
 
 
+class NormalParams(C.Structure):
+    """qn_normal_params (16 bytes): the neighbourhood radius of the map normals and the fewest neighbours (the point included) that make one"""
+    _fields_ = [("radius", C.c_double), ("min_neighbors", C.c_uint32), ("reserved", C.c_uint32)]
+
+    def __init__(self, radius=0.6, min_neighbors=5):
+        super().__init__(radius, min_neighbors, 0)
+
+    def twin(self):
+        """-> the mapnormals.NormalParams with these values"""
+        from . import mapnormals
+        return mapnormals.NormalParams(float(self.radius), int(self.min_neighbors))
+
+
 class KeyframeStore:
     """Device-resident keyframe clouds + LoopClosure::setSrcAndDstCloud on the GPU (loop_closure.cpp:58-108)."""
 
@@ -1208,6 +1221,33 @@ class KeyframeStore:
         self._check(st)
         self._map_n = n.value
         return n.value
+
+    # ---- normals and curvature of the map slot (qn_kf_map_normals / qn_kf_download_map_normals / qn_kf_map_moments; numpy twin: qn_amd/mapnormals.py)
+    def map_normals(self, params=None, viewpoints=None):
+        """qn_kf_map_normals on the map of the latest build_map / build_map_static, then its download.  params: a NormalParams (or a mapnormals.NormalParams);
+        None: the defaults (0.6, 5).  viewpoints: (V, 3) f64 the normals are turned towards (the nearest one of each point; the corrected keyframe positions as
+        a rule), None or empty: the largest component of each normal is made positive.  -> dict(normals (n, 3) f32, curvature (n,) f32, count (n,) uint32,
+        view_idx (n,) int32, ptr (the device address of the n float4 records nx ny nz curvature)), equal to mapnormals.normals of the downloaded map."""
+        p = NormalParams() if params is None else params
+        if not isinstance(p, NormalParams):
+            p = NormalParams(float(p.radius), int(p.min_neighbors))
+        v = np.zeros((0, 3)) if viewpoints is None else np.ascontiguousarray(np.asarray(viewpoints, dtype=np.float64).reshape(-1, 3))
+        ptr = C.c_void_p(); n = C.c_uint32()
+        self._check(self._l.qn_kf_map_normals(self.h, C.byref(p), _p(v) if len(v) else None, C.c_uint32(len(v)), C.byref(ptr), C.byref(n)))
+        self._normals_n = n.value
+        out = np.zeros((max(n.value, 1), 4), np.float32); cnt = np.zeros(max(n.value, 1), np.uint32); view = np.zeros(max(n.value, 1), np.int32)
+        self._check(self._l.qn_kf_download_map_normals(self.h, _p(out), _p(cnt), _p(view)))
+        out = out[:n.value]
+        return dict(normals=out[:, :3].copy(), curvature=out[:, 3].copy(), count=cnt[:n.value], view_idx=view[:n.value], ptr=ptr.value)
+
+    def map_moments(self):
+        """qn_kf_map_moments: the integer moments behind the latest map_normals -> (s1 (n, 3) int64, s2 (n, 6) int64)"""
+        n = getattr(self, "_normals_n", None)
+        if n is None:
+            raise ValueError("map_moments: no map_normals call yet")
+        s1 = np.zeros((max(n, 1), 3), np.int64); s2 = np.zeros((max(n, 1), 6), np.int64)
+        self._check(self._l.qn_kf_map_moments(self.h, _p(s1), _p(s2)))
+        return s1[:n], s2[:n]
 
     # ---- Scan Context loop candidates (qn_kf_sc_*; numpy twin: qn_amd/scancontext.py)
     def sc_set_params(self, params=None, **kw):

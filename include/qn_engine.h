@@ -591,6 +591,32 @@ int  qn_kf_static_classify(qn_kf_store*, const int32_t* ids, const double* poses
                            const qn_static_params* params, uint32_t* removed_per_entry, int* status);
 int  qn_kf_static_points(qn_kf_store*, uint32_t entry, uint8_t* seen_through_out, uint8_t* agree_out, uint8_t* removed_out);
 int  qn_kf_build_map_static(qn_kf_store*, double leaf, const float** d_xyzi_out /* float4: x y z intensity */, uint32_t* n_out);
+/* ---- normals and curvature of the map (csrc/qn_mapnormals.hip; numpy twin and specification: qn_amd/mapnormals.py)
+ * A surface normal and PCL's surface variation for every point of the store's map slot as the latest qn_kf_build_map / qn_kf_build_map_static left it - a
+ * passed-through map with its non-finite records included - from the point's fixed-radius neighbourhood, on the GPU.
+ * qn_normal_params (16 bytes): radius (finite, > 0, default 0.6), min_neighbors (>= 3, default 5), reserved (0).
+ * Neighbours of point p: the finite map points q, p included, with the f32 squared distance (the overlap measure's arithmetic) <= float(radius * radius).
+ * Moments: the offsets q - p (f32) times 2^e, e the largest integer with radius * 2^e <= 2^20, rounded half to even to integers di; count, s1[3] = sum di and
+ *   s2[6] = sum di dj (xx xy xz yy yz zz) are exact integers (u32, int64), equal to the twin's bit for bit whatever order the neighbours are met in.
+ * Covariance (f64, no fused multiply-add): m = s1 / count, C_ij = s2_ij / count - m_i m_j.  normal = the unit eigenvector of the smallest eigenvalue l0 of C,
+ *   curvature = l0 / (l0 + l1 + l2) with l0 clamped at 0; both f32.  All four are NaN when count < min_neighbors or the trace of C is <= 0.
+ * Orientation: view_idx = the viewpoint (viewpoints_xyz, n_view x 3 f64, the corrected keyframe positions as a rule) nearest to p in f64, the lowest index on
+ *   ties, -1 when n_view == 0 or p is non-finite; the normal is turned to face it (negated when n . (v - p) < 0).  With n_view == 0 the normal's component of
+ *   largest magnitude is made positive (the lowest axis on a tie).
+ * qn_kf_map_normals: one pass on the store's stream over the map indexed by cells of about the radius; two host synchronisations.  *d_normals_out = n float4
+ *   records (nx ny nz curvature) at the map's own indices, in store-owned memory good until the next successful call; the results stay resident for the
+ *   two downloads.  QN_ERR_NOT_READY without a map.  QN_ERR_INVALID_ARG: a null pointer, a non-finite or non-positive radius, min_neighbors < 3,
+ *   reserved != 0, a non-finite viewpoint, n_view > 0 with a null array.  QN_ERR_CAPACITY: 2^21 or more map points in one 3 x 3 x 3 block of cells (the int64
+ *   moments would no longer be provably exact), or a map whose extent overflows f32.  A refused call leaves the previous results intact.
+ * qn_kf_download_map_normals: normals4_out (n x 4 floats), count_out (n), view_idx_out (n); any may be NULL, not all.  qn_kf_map_moments: s1_out (n x 3),
+ *   s2_out (n x 6), for tests; either may be NULL, not both.  QN_ERR_NOT_READY before a successful qn_kf_map_normals and after a later map build replaced
+ *   the slot the results were computed from.                                                                                                               */
+typedef struct qn_normal_params { double radius; uint32_t min_neighbors, reserved; } qn_normal_params;      /* 16 bytes */
+void qn_normal_default_params(qn_normal_params* p);
+int  qn_kf_map_normals(qn_kf_store*, const qn_normal_params* params, const double* viewpoints_xyz, uint32_t n_view,
+                       const float** d_normals_out /* float4: nx ny nz curvature */, uint32_t* n_out);
+int  qn_kf_download_map_normals(qn_kf_store*, float* normals4_out, uint32_t* count_out, int32_t* view_idx_out);
+int  qn_kf_map_moments(qn_kf_store*, int64_t* s1_out /* n x 3 */, int64_t* s2_out /* n x 6 */);
 /* LoopClosure::fetchClosestKeyframeIdx (loop_closure.cpp:34-56) generalised to the max_k nearest admissible keyframes,
  * ascending distance; out[0] is the reference's single choice.  Host code (O(#keyframes)).                        */
 int  qn_loop_candidates(const double* pos_xyz, const double* stamps, uint32_t n, uint32_t query, double radius, double tdiff,

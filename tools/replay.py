@@ -221,6 +221,15 @@ def write_pcd_xyzi(path, pts):
             f.write("%.9g %.9g %.9g %.9g\n" % (p[0], p[1], p[2], p[3]))
 
 
+def write_pcd_xyzi_normal(path, pts, normals, curvature):
+    """PCD v0.7 ASCII, FIELDS x y z intensity normal_x normal_y normal_z curvature (a PointXYZINormal cloud); a point without a normal carries nan"""
+    with open(path, "w") as f:
+        f.write("# .PCD v0.7 - Point Cloud Data file format\nVERSION 0.7\nFIELDS x y z intensity normal_x normal_y normal_z curvature\nSIZE 4 4 4 4 4 4 4 4\n"
+                "TYPE F F F F F F F F\nCOUNT 1 1 1 1 1 1 1 1\nWIDTH %d\nHEIGHT 1\nVIEWPOINT 0 0 0 1 0 0 0\nPOINTS %d\nDATA ascii\n" % (len(pts), len(pts)))
+        for p, n, c in zip(pts, normals, curvature):
+            f.write("%.9g %.9g %.9g %.9g %.9g %.9g %.9g %.9g\n" % (p[0], p[1], p[2], p[3], n[0], n[1], n[2], c))
+
+
 def ate(poses, gt):
     return float(np.sqrt(np.mean([np.sum((a[:3, 3] - b[:3, 3]) ** 2) for a, b in zip(poses, gt)])))
 
@@ -279,7 +288,7 @@ def _oracle_submap_relative(orc, scans, poses, q, c, yaw, submap_range, voxel, m
 def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, submap_range=5, score_thr=1.5, verbose=True, backend="gpu", save_dir=None,
         save_map_leaf=None, sensor="uniform", detector="radius", sc_max_dist=0.3, yaw_bias=0.006, verify="reference", sc_top_k=1, loop_every=1, catch_up=False,
         submap_matching=False, min_overlap=None, overlap_radius=None, max_see_through=None, range_params=None, static_map=False, static_radius=15.0,
-        static_max_k=8, moving_boxes=0):
+        static_max_k=8, moving_boxes=0, save_map_normals=False, normal_radius=0.6, normal_min_neighbors=5):
     """sensor = "uniform": keyframe clouds sampled uniformly by area inside a disc (make_stream); "spinning": ray-cast spinning-LiDAR
     scans from the ground-truth poses of the same figure-8 (make_lidar_stream).  detector = "radius": the candidate is the closest older
     keyframe within `radius` of the corrected position (LC:34-56); "scancontext": the older keyframe nearest by Scan Context distance, kept
@@ -317,6 +326,10 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
     are made (unless max_see_through made them on arrival), every record of every keyframe is checked against the images of its static_max_k nearest keyframes
     within static_radius under the corrected poses (KeyframeStore.static_classify), and map_static.pcd - map.pcd without the records voted out - is written
     beside map.pcd (KeyframeStore.build_map_static).  out["static_removed"]: the records removed, out["static_map_points"] / out["map_points"]: the maps' sizes.
+    save_map_normals (the GPU backend, with save_dir and save_map_leaf; default False): map.pcd (and map_static.pcd) carry normal_x normal_y normal_z curvature
+    beside x y z intensity - every map point's surface normal from its neighbours within normal_radius (at least normal_min_neighbors of them, else nan), turned
+    towards the nearest corrected keyframe position, on the device from the resident map (KeyframeStore.map_normals).  out["map_normals_valid"]: the points of
+    map.pcd that have one.
     moving_boxes = N (sensor="spinning" only; default 0: every run is what it was): N extra boxes in the scene that stand somewhere else in every keyframe
     (moving_box_prims), so every keyframe is cast by a call of its own."""
     if detector not in ("radius", "scancontext"):
@@ -353,6 +366,12 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
         raise ValueError("static_map needs save_map_leaf > 0, not %r" % (save_map_leaf,))
     if static_map and not (np.isfinite(static_radius) and static_radius >= 0 and int(static_max_k) == static_max_k and 0 <= static_max_k <= 255):
         raise ValueError("static_map needs static_radius >= 0 and 0 <= static_max_k <= 255, not %r / %r" % (static_radius, static_max_k))
+    if save_map_normals and backend != "gpu":
+        raise ValueError("save_map_normals needs backend='gpu' (the oracle backend writes no map)")
+    if save_map_normals and (save_dir is None or save_map_leaf is None):
+        raise ValueError("save_map_normals needs save_dir and save_map_leaf (the normals are fields of map.pcd)")
+    if save_map_normals and not (np.isfinite(normal_radius) and normal_radius > 0 and int(normal_min_neighbors) == normal_min_neighbors and normal_min_neighbors >= 3):
+        raise ValueError("save_map_normals needs normal_radius > 0 and normal_min_neighbors >= 3, not %r / %r" % (normal_radius, normal_min_neighbors))
     overlaps = []; see_through = []; fs_images = {}
 
     def apply_freespace(rs, pairs):
@@ -603,15 +622,26 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
     if save_dir:
         write_kitti_tum(save_dir, corrected, stamps)
         if save_map_leaf is not None and backend == "gpu":
+            def write_map(name, n):
+                """the map slot as a .pcd, with the normals of its points when asked -> the points that have one"""
+                if not save_map_normals:
+                    write_pcd_xyzi(os.path.join(save_dir, name), store.download_map(n))
+                    return None
+                from qn_amd import engine
+                nr = store.map_normals(engine.NormalParams(normal_radius, int(normal_min_neighbors)), np.array([T[:3, 3] for T in corrected]))
+                write_pcd_xyzi_normal(os.path.join(save_dir, name), store.download_map(n), nr["normals"], nr["curvature"])
+                return int(np.isfinite(nr["curvature"]).sum())
             n = store.build_map(ids, corrected, save_map_leaf)
-            write_pcd_xyzi(os.path.join(save_dir, "map.pcd"), store.download_map(n))
+            valid = write_map("map.pcd", n)
+            if save_map_normals:
+                out["map_points"] = n; out["map_normals_valid"] = valid
             if static_map:
                 out["map_points"] = n
                 if not fgate:                                                                # (with the gate on, every keyframe was described on arrival)
                     store.range_describe(ids)
                 st = store.static_classify(ids, corrected, radius=static_radius, max_k=static_max_k)
                 n = store.build_map_static(save_map_leaf)
-                write_pcd_xyzi(os.path.join(save_dir, "map_static.pcd"), store.download_map(n))
+                write_map("map_static.pcd", n)
                 out["static_removed"] = int(st["removed"].sum()); out["static_map_points"] = n
     if verbose:
         print({k: v for k, v in out.items() if k not in ("poses", "loop_list", "loop_T", "gt", "overlaps", "see_through")})
@@ -645,9 +675,15 @@ if __name__ == "__main__":
                     help="with --verify relative: add a loop only if neither scan sees through more than this share of the other's observed points under the verified transform")
     ap.add_argument("--static-map", action="store_true",
                     help="with --save-dir and --save-map-leaf: also write map_static.pcd, the map without the records other keyframes saw through")
+    ap.add_argument("--save-map-normals", action="store_true",
+                    help="with --save-dir and --save-map-leaf: map.pcd also carries normal_x normal_y normal_z curvature, estimated on the GPU from the resident map")
+    ap.add_argument("--normal-radius", type=float, default=0.6, help="with --save-map-normals: the neighbourhood radius [m]")
     ap.add_argument("--moving-boxes", type=int, default=0, help="with --sensor spinning: this many boxes that stand somewhere else in every keyframe")
     ap.add_argument("--backend", choices=["gpu", "oracle"], default="gpu", help="the engine on the GPU, or the CPU oracle")
     a = ap.parse_args()
+    if a.save_map_normals and (a.save_dir is None or a.save_map_leaf is None):
+        ap.error("--save-map-normals needs --save-dir and --save-map-leaf")
     run(a.keyframes, a.seed, a.quatro, save_dir=a.save_dir, save_map_leaf=a.save_map_leaf, sensor=a.sensor, detector=a.detector, yaw_bias=a.yaw_bias,
         verify=a.verify, sc_top_k=a.sc_top_k, backend=a.backend, loop_every=a.loop_every, catch_up=a.catch_up, submap_matching=a.submap_matching,
-        min_overlap=a.min_overlap, overlap_radius=a.overlap_radius, max_see_through=a.max_see_through, static_map=a.static_map, moving_boxes=a.moving_boxes)
+        min_overlap=a.min_overlap, overlap_radius=a.overlap_radius, max_see_through=a.max_see_through, static_map=a.static_map, moving_boxes=a.moving_boxes,
+        save_map_normals=a.save_map_normals, normal_radius=a.normal_radius)
