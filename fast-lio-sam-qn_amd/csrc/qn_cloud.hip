@@ -754,6 +754,15 @@ const float4* qn_kf_int_map(const qn_kf_store* s, uint32_t* n, uint64_t* generat
   return s->map_n ? s->map.p : nullptr;
 }
 
+// the first n_kept records at d_kept (device memory, not the slot itself; n_kept <= the slot's points) become the map slot, copied on the store's stream, and
+// the slot's generation advances as after a build: what a filter of the map leaves behind (qn_mapoutliers.hip)
+int qn_kf_int_map_shrink(qn_kf_store* s, const float4* d_kept, uint32_t n_kept) {
+  if (n_kept > s->map_n || (n_kept && !d_kept)) return QN_ERR_INVALID_ARG;
+  if (n_kept) QN_KFCHK(s, hipMemcpyAsync(s->map.p, d_kept, sizeof(float4) * (size_t)n_kept, hipMemcpyDeviceToDevice, s->stream));
+  s->map_n = n_kept; s->map_gen++;
+  return QN_OK;
+}
+
 // the map into host records: only the 12 xyz bytes (offset 0) and the 4 intensity bytes (offset ioff) of each are written
 extern "C" int qn_kf_download_map(qn_kf_store* s, void* out, uint32_t stride, uint32_t ioff) {
   if (!s || !out || !xyzi_layout_ok(stride, ioff)) return QN_ERR_INVALID_ARG;

@@ -32,7 +32,7 @@ bool qn_kf_int_has_intensity(const qn_kf_store* s, int32_t id);                 
 // qn_kf_quatro.inc, QN_KF_INT_EXT_VERIFY: qn_verify.hip's record of the latest multi-pair verification, QN_KF_INT_EXT_SUBMAP: the resident local submaps of
 // qn_kf_submap.inc): nullptr until set; the store owns it from qn_kf_int_set_ext on and calls `release` from qn_kf_store_destroy once its stream has drained.
 // Units reach their state through qn_kf_ext_state (qn_kf_buf.h), which makes it on first use.
-#define QN_KF_INT_EXT 8
+#define QN_KF_INT_EXT 9
 #define QN_KF_INT_EXT_SC 0
 #define QN_KF_INT_EXT_QUATRO 1
 #define QN_KF_INT_EXT_VERIFY 2
@@ -41,6 +41,7 @@ bool qn_kf_int_has_intensity(const qn_kf_store* s, int32_t id);                 
 #define QN_KF_INT_EXT_RANGE 5                                                    // qn_freespace.hip: range images and the classes of the latest check
 #define QN_KF_INT_EXT_STATIC 6                                                   // qn_staticmap.hip: the list, votes and kept records of the latest static classify
 #define QN_KF_INT_EXT_NORMALS 7                                                  // qn_mapnormals.hip: the normals and moments of the map slot
+#define QN_KF_INT_EXT_OUTLIERS 8                                                 // qn_mapoutliers.hip: the classification of the map slot's points
 typedef void (*qn_kf_int_release_fn)(void*);
 void* qn_kf_int_ext(const qn_kf_store* s, int which);
 void qn_kf_int_set_ext(qn_kf_store* s, int which, void* p, qn_kf_int_release_fn release);
@@ -88,6 +89,10 @@ int qn_kf_int_cell_index(qn_kf_store* s, const float4* const* clouds, const uint
 // the map slot as the latest qn_kf_build_map / qn_kf_build_map_static left it (nullptr and *n = 0 without a map) and its generation, which every attempt to
 // build a map advances: what was computed from the slot at another generation is stale.
 const float4* qn_kf_int_map(const qn_kf_store* s, uint32_t* n, uint64_t* generation);
+// shrinks the map slot to a compacted prefix: its first n_kept records become the n_kept records at d_kept (device memory other than the slot; n_kept <= the
+// slot's points, else QN_ERR_INVALID_ARG), copied on the store's stream without a synchronisation, and the generation advances as after a build.  n_kept == 0
+// leaves the store without a map.
+int qn_kf_int_map_shrink(qn_kf_store* s, const float4* d_kept, uint32_t n_kept);
 // qn_kf_build_map with its sources given directly instead of by keyframe id: entry k = n[k] float4 records at pts[k] (device memory of this store's device,
 // nullptr when n[k] == 0), has_i[k] = their .w is an intensity (else the map counts it as 0), transformed with poses[16 k ..].  The same pipeline, the same map
 // slot, the same statuses and notes: for pts / n / has_i of resident keyframes it IS qn_kf_build_map of their ids.  Arguments are not checked.

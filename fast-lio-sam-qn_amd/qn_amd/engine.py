@@ -3,6 +3,7 @@
 (fast_lio_sam_qn/src/loop_closure.cpp:9-16, 120-133), argument meaning and failure
 behaviour included (no exceptions for a failed registration: hasConverged() == False)."""
 import ctypes as C
+import math
 import os
 import numpy as np
 from . import build as _build
@@ -725,6 +726,25 @@ class NormalParams(C.Structure):
         return mapnormals.NormalParams(float(self.radius), int(self.min_neighbors))
 
 
+class OutlierParams(C.Structure):
+    """qn_outlier_params (24 bytes): the neighbourhood radius, PCL's std_mul and the k nearest neighbours of the map's outlier filter"""
+    _fields_ = [("radius", C.c_double), ("std_mul", C.c_double), ("k", C.c_uint32), ("reserved", C.c_uint32)]
+
+    def __init__(self, radius=1.0, std_mul=2.0, k=8):
+        super().__init__(radius, std_mul, k, 0)
+
+    def twin(self):
+        """-> the mapoutliers.OutlierParams with these values"""
+        from . import mapoutliers
+        return mapoutliers.OutlierParams(float(self.radius), float(self.std_mul), int(self.k))
+
+
+class OutlierStats(C.Structure):
+    """qn_outlier_stats (64 bytes); mean_q, std_q and thr_q in units of 2^-quant_exp m"""
+    _fields_ = [(f, C.c_uint32) for f in ("n", "n_finite", "dense", "sparse", "removed")] + [("quant_exp", C.c_int32), ("sum_q", C.c_uint64), ("sum_q2", C.c_uint64),
+                                                                                              ("mean_q", C.c_double), ("std_q", C.c_double), ("thr_q", C.c_double)]
+
+
 class KeyframeStore:
     """Device-resident keyframe clouds + LoopClosure::setSrcAndDstCloud on the GPU (loop_closure.cpp:58-108)."""
 
@@ -1248,6 +1268,33 @@ class KeyframeStore:
         s1 = np.zeros((max(n, 1), 3), np.int64); s2 = np.zeros((max(n, 1), 6), np.int64)
         self._check(self._l.qn_kf_map_moments(self.h, _p(s1), _p(s2)))
         return s1[:n], s2[:n]
+
+    # ---- isolated noise points of the map slot (qn_kf_map_outliers / qn_kf_map_outlier_points / qn_kf_map_remove_outliers; numpy twin: qn_amd/mapoutliers.py)
+    def map_outliers(self, params=None):
+        """qn_kf_map_outliers on the map of the latest build_map / build_map_static, then its per-point download.  params: an OutlierParams (or a
+        mapoutliers.OutlierParams); None: the defaults (1.0, 2.0, 8).  -> (stats, count (n,) uint32, mean_q (n,) uint32, removed (n,) uint8), equal to
+        mapoutliers.classify of the downloaded map.  stats: a dict of the fields of qn_outlier_stats plus, in metres, mean, std and threshold (each the _q
+        value times 2^-quant_exp).  The map slot is not touched; map_remove_outliers applies the result."""
+        p = OutlierParams() if params is None else params
+        if not isinstance(p, OutlierParams):
+            p = OutlierParams(float(p.radius), float(p.std_mul), int(p.k))
+        st = OutlierStats()
+        self._check(self._l.qn_kf_map_outliers(self.h, C.byref(p), C.byref(st)))
+        n = int(st.n)
+        cnt = np.zeros(max(n, 1), np.uint32); mq = np.zeros(max(n, 1), np.uint32); rm = np.zeros(max(n, 1), np.uint8)
+        self._check(self._l.qn_kf_map_outlier_points(self.h, _p(cnt), _p(mq), _p(rm)))
+        stats = {f: getattr(st, f) for f, _ in OutlierStats._fields_}
+        unit = math.ldexp(1.0, -int(st.quant_exp))
+        stats.update(mean=st.mean_q * unit, std=st.std_q * unit, threshold=st.thr_q * unit)
+        return stats, cnt[:n], mq[:n], rm[:n]
+
+    def map_remove_outliers(self):
+        """qn_kf_map_remove_outliers: the records the latest map_outliers kept become the map slot, in order -> (ptr, n): the device address of the n float4
+        records x y z intensity.  download_map and map_normals serve the filtered map; the classification and any map normals are stale afterwards."""
+        ptr = C.c_void_p(); n = C.c_uint32()
+        self._check(self._l.qn_kf_map_remove_outliers(self.h, C.byref(ptr), C.byref(n)))
+        self._map_n = n.value
+        return ptr.value, n.value
 
     # ---- Scan Context loop candidates (qn_kf_sc_*; numpy twin: qn_amd/scancontext.py)
     def sc_set_params(self, params=None, **kw):

@@ -617,6 +617,45 @@ int  qn_kf_map_normals(qn_kf_store*, const qn_normal_params* params, const doubl
                        const float** d_normals_out /* float4: nx ny nz curvature */, uint32_t* n_out);
 int  qn_kf_download_map_normals(qn_kf_store*, float* normals4_out, uint32_t* count_out, int32_t* view_idx_out);
 int  qn_kf_map_moments(qn_kf_store*, int64_t* s1_out /* n x 3 */, int64_t* s2_out /* n x 6 */);
+/* ---- isolated noise points of the map (csrc/qn_mapoutliers.hip; numpy twin and specification: qn_amd/mapoutliers.py)
+ * Stray returns survive the voxel grid and the static vote: mixed pixels off object edges, dust, single hits in mid-air.  These calls find and remove them in
+ * the store's map slot as the latest build left it - a passed-through map with its non-finite records included - by PCL's RadiusOutlierRemoval and
+ * StatisticalOutlierRemoval rules over one exact bounded-radius k-nearest selection per map point, on the GPU.
+ * qn_outlier_params (24 bytes): radius (finite, > 0, default 1.0), std_mul (finite, >= 0, default 2.0), k (1 .. QN_OUTLIER_MAX_K = 32, default 8),
+ *   reserved (0).  The defaults are interface choices, not measurements.
+ * Neighbours of a finite point p: the finite map points q at ANOTHER INDEX than p with the f32 squared distance d2 (the overlap measure's arithmetic: f32
+ *   differences, dx dx + dy dy + dz dz left to right, no fused multiply-add) <= float(radius * radius); a duplicate of p at another index counts.  count =
+ *   their number (u32).
+ * Sparse: count < k.  The point is an outlier outright (the radius rule with min_neighbors = k), its mean_q is 0xffffffff, it takes no part in the statistics.
+ * Dense: count >= k.  The k smallest d2 as a multiset, ascending; s = their correctly rounded f64 roots (of the f32 values widened to f64) summed in that
+ *   order in f64; mean_q = (uint32) rint(s / k * 2^e), half to even, e the largest integer with radius * 2^e <= 2^16 (within [-126, 127]); mean_q <= 2^16 + 1.
+ * Statistics over the dense points, exact integers: dense = N, sum_q, sum_q2 = the sums of mean_q and of its square (u64).
+ * Threshold (host, f64, no contraction): mean = sum_q / N; var = N > 1 ? (sum_q2 - sum_q * sum_q / N) / (N - 1) : 0, clamped at 0; thr_q = mean + std_mul *
+ *   sqrt(var); all 0 when N == 0.
+ * Removed: a finite point that is sparse or has (double)mean_q > thr_q.  A non-finite record has count 0 and mean_q 0xffffffff and is never removed.
+ * count, mean_q, the removed flags and the statistics are integers (the f64 values follow from them), equal to the twin's bit for bit whatever order the
+ *   neighbours are met in; a rerun gives the same bytes.
+ * qn_outlier_stats (64 bytes): n, n_finite, dense, sparse, removed, quant_exp (e); sum_q, sum_q2; mean_q, std_q, thr_q in units of 2^-e m.
+ * qn_kf_map_outliers: classifies the map slot as it stands; the slot itself is not touched.  The per-point results stay resident for the slot's generation
+ *   (any later map build, successful or not, ends it).  At most three host synchronisations.  QN_ERR_NOT_READY without a map.  QN_ERR_INVALID_ARG: a null
+ *   pointer, a non-finite or non-positive radius, a non-finite or negative std_mul, k outside 1 .. 32, reserved != 0.  QN_ERR_CAPACITY: 2^30 or more map
+ *   points (sum_q2 would no longer be provably exact), or a map whose extent overflows f32.  A refused call leaves the previous classification intact.
+ * qn_kf_map_outlier_points: count_out, mean_q_out, removed_out (one byte per point), each at the map's own indices; any may be NULL, not all.
+ *   QN_ERR_NOT_READY before a successful qn_kf_map_outliers and once the slot's generation has moved on.
+ * qn_kf_map_remove_outliers: applies the live classification: the kept records, in order and all 16 bytes each, become the map slot (*d_xyzi_out, *n_out;
+ *   NULL and 0 when nothing is left).  The slot's generation advances, so the classification and any map normals go stale; qn_kf_download_map and
+ *   qn_kf_map_normals serve the filtered map.  QN_ERR_NOT_READY without a live classification, and the slot is then unchanged.                              */
+#define QN_OUTLIER_MAX_K 32
+typedef struct qn_outlier_params { double radius; double std_mul; uint32_t k; uint32_t reserved; } qn_outlier_params;      /* 24 bytes */
+typedef struct qn_outlier_stats {
+  uint32_t n, n_finite, dense, sparse, removed; int32_t quant_exp;
+  uint64_t sum_q, sum_q2;
+  double mean_q, std_q, thr_q;
+} qn_outlier_stats;                                                                                                          /* 64 bytes */
+void qn_outlier_default_params(qn_outlier_params* p);
+int  qn_kf_map_outliers(qn_kf_store*, const qn_outlier_params* params, qn_outlier_stats* stats_out);
+int  qn_kf_map_outlier_points(qn_kf_store*, uint32_t* count_out, uint32_t* mean_q_out, uint8_t* removed_out);
+int  qn_kf_map_remove_outliers(qn_kf_store*, const float** d_xyzi_out /* float4: x y z intensity */, uint32_t* n_out);
 /* LoopClosure::fetchClosestKeyframeIdx (loop_closure.cpp:34-56) generalised to the max_k nearest admissible keyframes,
  * ascending distance; out[0] is the reference's single choice.  Host code (O(#keyframes)).                        */
 int  qn_loop_candidates(const double* pos_xyz, const double* stamps, uint32_t n, uint32_t query, double radius, double tdiff,

@@ -288,7 +288,8 @@ def _oracle_submap_relative(orc, scans, poses, q, c, yaw, submap_range, voxel, m
 def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, submap_range=5, score_thr=1.5, verbose=True, backend="gpu", save_dir=None,
         save_map_leaf=None, sensor="uniform", detector="radius", sc_max_dist=0.3, yaw_bias=0.006, verify="reference", sc_top_k=1, loop_every=1, catch_up=False,
         submap_matching=False, min_overlap=None, overlap_radius=None, max_see_through=None, range_params=None, static_map=False, static_radius=15.0,
-        static_max_k=8, moving_boxes=0, save_map_normals=False, normal_radius=0.6, normal_min_neighbors=5):
+        static_max_k=8, moving_boxes=0, save_map_normals=False, normal_radius=0.6, normal_min_neighbors=5, map_outliers=False,
+        outlier_radius=1.0, outlier_k=8, outlier_std=2.0):
     """sensor = "uniform": keyframe clouds sampled uniformly by area inside a disc (make_stream); "spinning": ray-cast spinning-LiDAR
     scans from the ground-truth poses of the same figure-8 (make_lidar_stream).  detector = "radius": the candidate is the closest older
     keyframe within `radius` of the corrected position (LC:34-56); "scancontext": the older keyframe nearest by Scan Context distance, kept
@@ -330,6 +331,10 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
     beside x y z intensity - every map point's surface normal from its neighbours within normal_radius (at least normal_min_neighbors of them, else nan), turned
     towards the nearest corrected keyframe position, on the device from the resident map (KeyframeStore.map_normals).  out["map_normals_valid"]: the points of
     map.pcd that have one.
+    map_outliers (the GPU backend, with save_dir and save_map_leaf; default False): the map (and the static map) is filtered on the device before it is
+    written and before its normals are made: every point with fewer than outlier_k neighbours within outlier_radius, or whose mean distance to its outlier_k
+    nearest exceeds the map's mean by more than outlier_std standard deviations, is removed (KeyframeStore.map_outliers / map_remove_outliers).
+    out["map_outliers_removed"] (and out["static_outliers_removed"]): the points removed; out["map_points"] / out["static_map_points"]: what was written.
     moving_boxes = N (sensor="spinning" only; default 0: every run is what it was): N extra boxes in the scene that stand somewhere else in every keyframe
     (moving_box_prims), so every keyframe is cast by a call of its own."""
     if detector not in ("radius", "scancontext"):
@@ -372,6 +377,13 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
         raise ValueError("save_map_normals needs save_dir and save_map_leaf (the normals are fields of map.pcd)")
     if save_map_normals and not (np.isfinite(normal_radius) and normal_radius > 0 and int(normal_min_neighbors) == normal_min_neighbors and normal_min_neighbors >= 3):
         raise ValueError("save_map_normals needs normal_radius > 0 and normal_min_neighbors >= 3, not %r / %r" % (normal_radius, normal_min_neighbors))
+    if map_outliers and backend != "gpu":
+        raise ValueError("map_outliers needs backend='gpu' (the oracle backend writes no map)")
+    if map_outliers and (save_dir is None or save_map_leaf is None):
+        raise ValueError("map_outliers needs save_dir and save_map_leaf (it filters the map that map.pcd is written from)")
+    if map_outliers and not (np.isfinite(outlier_radius) and outlier_radius > 0 and np.isfinite(outlier_std) and outlier_std >= 0 and int(outlier_k) == outlier_k
+                             and 1 <= outlier_k <= 32):
+        raise ValueError("map_outliers needs outlier_radius > 0, outlier_std >= 0 and 1 <= outlier_k <= 32, not %r / %r / %r" % (outlier_radius, outlier_std, outlier_k))
     overlaps = []; see_through = []; fs_images = {}
 
     def apply_freespace(rs, pairs):
@@ -631,8 +643,17 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
                 nr = store.map_normals(engine.NormalParams(normal_radius, int(normal_min_neighbors)), np.array([T[:3, 3] for T in corrected]))
                 write_pcd_xyzi_normal(os.path.join(save_dir, name), store.download_map(n), nr["normals"], nr["curvature"])
                 return int(np.isfinite(nr["curvature"]).sum())
-            n = store.build_map(ids, corrected, save_map_leaf)
+            def filter_map(n):
+                """the outliers of the map slot removed in place -> (the points left, the points removed)"""
+                if not map_outliers:
+                    return n, None
+                from qn_amd import engine
+                st = store.map_outliers(engine.OutlierParams(outlier_radius, outlier_std, int(outlier_k)))[0]
+                return store.map_remove_outliers()[1], int(st["removed"])
+            n, removed = filter_map(store.build_map(ids, corrected, save_map_leaf))
             valid = write_map("map.pcd", n)
+            if map_outliers:
+                out["map_points"] = n; out["map_outliers_removed"] = removed
             if save_map_normals:
                 out["map_points"] = n; out["map_normals_valid"] = valid
             if static_map:
@@ -640,8 +661,10 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
                 if not fgate:                                                                # (with the gate on, every keyframe was described on arrival)
                     store.range_describe(ids)
                 st = store.static_classify(ids, corrected, radius=static_radius, max_k=static_max_k)
-                n = store.build_map_static(save_map_leaf)
+                n, removed = filter_map(store.build_map_static(save_map_leaf))
                 write_map("map_static.pcd", n)
+                if map_outliers:
+                    out["static_outliers_removed"] = removed
                 out["static_removed"] = int(st["removed"].sum()); out["static_map_points"] = n
     if verbose:
         print({k: v for k, v in out.items() if k not in ("poses", "loop_list", "loop_T", "gt", "overlaps", "see_through")})
@@ -678,12 +701,20 @@ if __name__ == "__main__":
     ap.add_argument("--save-map-normals", action="store_true",
                     help="with --save-dir and --save-map-leaf: map.pcd also carries normal_x normal_y normal_z curvature, estimated on the GPU from the resident map")
     ap.add_argument("--normal-radius", type=float, default=0.6, help="with --save-map-normals: the neighbourhood radius [m]")
+    ap.add_argument("--map-outliers", action="store_true",
+                    help="with --save-dir and --save-map-leaf: isolated noise points are removed from the map on the GPU before it (and its normals) are written")
+    ap.add_argument("--outlier-radius", type=float, default=1.0, help="with --map-outliers: the neighbourhood radius [m]")
+    ap.add_argument("--outlier-k", type=int, default=8, help="with --map-outliers: the nearest neighbours the mean distance is taken over (fewer within the radius: removed)")
+    ap.add_argument("--outlier-std", type=float, default=2.0, help="with --map-outliers: removed above the mean of the mean distances plus this many standard deviations")
     ap.add_argument("--moving-boxes", type=int, default=0, help="with --sensor spinning: this many boxes that stand somewhere else in every keyframe")
     ap.add_argument("--backend", choices=["gpu", "oracle"], default="gpu", help="the engine on the GPU, or the CPU oracle")
     a = ap.parse_args()
     if a.save_map_normals and (a.save_dir is None or a.save_map_leaf is None):
         ap.error("--save-map-normals needs --save-dir and --save-map-leaf")
+    if a.map_outliers and (a.save_dir is None or a.save_map_leaf is None):
+        ap.error("--map-outliers needs --save-dir and --save-map-leaf")
     run(a.keyframes, a.seed, a.quatro, save_dir=a.save_dir, save_map_leaf=a.save_map_leaf, sensor=a.sensor, detector=a.detector, yaw_bias=a.yaw_bias,
         verify=a.verify, sc_top_k=a.sc_top_k, backend=a.backend, loop_every=a.loop_every, catch_up=a.catch_up, submap_matching=a.submap_matching,
         min_overlap=a.min_overlap, overlap_radius=a.overlap_radius, max_see_through=a.max_see_through, static_map=a.static_map, moving_boxes=a.moving_boxes,
-        save_map_normals=a.save_map_normals, normal_radius=a.normal_radius)
+        save_map_normals=a.save_map_normals, normal_radius=a.normal_radius, map_outliers=a.map_outliers, outlier_radius=a.outlier_radius, outlier_k=a.outlier_k,
+        outlier_std=a.outlier_std)
