@@ -60,6 +60,7 @@ extern "C" const char* qn_status_str(int s) {
     case QN_OK: return "ok"; case QN_ERR_INVALID_ARG: return "invalid argument"; case QN_ERR_EMPTY_CLOUD: return "empty cloud";
     case QN_ERR_CAPACITY: return "cloud exceeds context capacity"; case QN_ERR_NOT_READY: return "clouds/covariances not set";
     case QN_ERR_HIP: return "HIP runtime error"; case QN_ERR_NO_DEVICE: return "no gfx950 device (no CPU fallback)";
+    case QN_ERR_INTERNAL: return "internal error (a bounded loop left its bound)";
   }
   return "unknown status";
 }

@@ -32,7 +32,7 @@ bool qn_kf_int_has_intensity(const qn_kf_store* s, int32_t id);                 
 // qn_kf_quatro.inc, QN_KF_INT_EXT_VERIFY: qn_verify.hip's record of the latest multi-pair verification, QN_KF_INT_EXT_SUBMAP: the resident local submaps of
 // qn_kf_submap.inc): nullptr until set; the store owns it from qn_kf_int_set_ext on and calls `release` from qn_kf_store_destroy once its stream has drained.
 // Units reach their state through qn_kf_ext_state (qn_kf_buf.h), which makes it on first use.
-#define QN_KF_INT_EXT 9
+#define QN_KF_INT_EXT 10
 #define QN_KF_INT_EXT_SC 0
 #define QN_KF_INT_EXT_QUATRO 1
 #define QN_KF_INT_EXT_VERIFY 2
@@ -42,6 +42,7 @@ bool qn_kf_int_has_intensity(const qn_kf_store* s, int32_t id);                 
 #define QN_KF_INT_EXT_STATIC 6                                                   // qn_staticmap.hip: the list, votes and kept records of the latest static classify
 #define QN_KF_INT_EXT_NORMALS 7                                                  // qn_mapnormals.hip: the normals and moments of the map slot
 #define QN_KF_INT_EXT_OUTLIERS 8                                                 // qn_mapoutliers.hip: the classification of the map slot's points
+#define QN_KF_INT_EXT_GROUND 9                                                   // qn_mapground.hip: the ground classes and the occupancy grid of the map slot
 typedef void (*qn_kf_int_release_fn)(void*);
 void* qn_kf_int_ext(const qn_kf_store* s, int which);
 void qn_kf_int_set_ext(qn_kf_store* s, int which, void* p, qn_kf_int_release_fn release);

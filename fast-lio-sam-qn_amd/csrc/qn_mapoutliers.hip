@@ -15,8 +15,8 @@
 //             into the block's own slot; k_mo_reduce adds the slots up.  No atomics.
 //   flag      k_mo_flag, one point per lane in the map's own order: removed = sparse or double(mean_q) > thr_q; the block's kept count into its slot;
 //             k_mo_scan (one block) turns the counts into offsets, the last one the number kept.
-//   compact   k_mo_compact (qn_kf_map_remove_outliers only): the kept records of a block to its offset, in order, by ballot / popcount ranks and the waves'
-//             counts through LDS - the static map's scheme: stable and the same on every run.  The records go to scratch and from there to the front of the
+//   compact   k_mo_scan and k_mo_compact live in qn_map_compact.cuh, shared with qn_mapground.hip.  k_mo_compact (qn_kf_map_remove_outliers only): the kept
+//             records of a block to its offset, in order, by ballot / popcount ranks and the waves' counts through LDS - the static map's scheme: stable and the same on every run.  The records go to scratch and from there to the front of the
 //             map slot (qn_kf_int_map_shrink), which advances the slot's generation.
 // Host synchronisations of a classify: the index's, one for the statistics (the threshold is host arithmetic), one at the end.  Results are written into the
 // spare one of two buffer sets and the sets are swapped on success, so a refused call leaves the previous classification as it was.
@@ -27,12 +27,10 @@
 #include <new>
 #include "../../include/qn_engine.h"
 #include "qn_kf_buf.h"
+#include "qn_map_compact.cuh"
 
 namespace {
 
-#define MO_BLOCK 256
-#define MO_WAVES (MO_BLOCK / 64)
-#define MO_SCAN_BLOCK 1024
 #define MO_MAX_POINTS (1u << 30)
 #define MO_NO_MEAN 0xffffffffu
 
@@ -189,47 +187,6 @@ __global__ void __launch_bounds__(MO_BLOCK) k_mo_flag(uint32_t n, const float4* 
     for (int w = 0; w < MO_WAVES; w++) acc += wk[w];
     blk_kept[blockIdx.x] = acc;
   }
-}
-
-// one block: off[b] = the kept records of the blocks before b, off[nb] = all of them (k_static_scan's scheme: thread i scans the blocks
-// [i chunk, (i + 1) chunk), the threads' sums through a wave scan and the waves in order)
-__global__ void __launch_bounds__(MO_SCAN_BLOCK) k_mo_scan(const uint32_t* __restrict__ cnt, uint32_t nb, uint32_t* __restrict__ off) {
-  __shared__ uint32_t ws[MO_SCAN_BLOCK / 64];
-  const uint32_t chunk = (nb + MO_SCAN_BLOCK - 1) / MO_SCAN_BLOCK;
-  const uint32_t a = min(threadIdx.x * chunk, nb), b = min(a + chunk, nb);
-  uint32_t sum = 0;
-  for (uint32_t t = a; t < b; t++) sum += cnt[t];
-  const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  uint32_t v = sum;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) { const uint32_t u = __shfl_up(v, o); if ((int)lane >= o) v += u; }
-  if (lane == 63) ws[wv] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint32_t acc = 0;
-    for (int w = 0; w < MO_SCAN_BLOCK / 64; w++) { const uint32_t u = ws[w]; ws[w] = acc; acc += u; }
-  }
-  __syncthreads();
-  uint32_t run = ws[wv] + v - sum;
-  for (uint32_t t = a; t < b; t++) { off[t] = run; run += cnt[t]; }
-  if (threadIdx.x == MO_SCAN_BLOCK - 1) off[nb] = run;              // the last thread's range ends at nb
-}
-
-// the block's kept records, in order, to kept[off[block] ..]
-__global__ void __launch_bounds__(MO_BLOCK) k_mo_compact(uint32_t n, const float4* __restrict__ map, const uint8_t* __restrict__ removed, const uint32_t* __restrict__ off,
-                                                         float4* __restrict__ kept) {
-  __shared__ uint32_t wk[MO_WAVES];
-  const uint32_t i = blockIdx.x * MO_BLOCK + threadIdx.x;
-  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const bool keep = i < n && removed[i] == 0;
-  const float4 p = keep ? map[i] : make_float4(0.f, 0.f, 0.f, 0.f);
-  const unsigned long long bal = __ballot(keep);
-  if (lane == 0) wk[wave] = (uint32_t)__popcll(bal);
-  __syncthreads();
-  uint32_t before = off[blockIdx.x];
-#pragma unroll
-  for (int w = 0; w < MO_WAVES; w++) if ((uint32_t)w < wave) before += wk[w];
-  if (keep) kept[before + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull))] = p;
 }
 
 // The store's outlier state (slot QN_KF_INT_EXT_OUTLIERS): two sets of per-point buffers, the live one holding the classification of the latest successful

@@ -8,7 +8,7 @@ import os
 import numpy as np
 from . import build as _build
 
-QN_OK, QN_ERR_INVALID_ARG, QN_ERR_EMPTY_CLOUD, QN_ERR_CAPACITY, QN_ERR_NOT_READY, QN_ERR_HIP, QN_ERR_NO_DEVICE = range(7)
+QN_OK, QN_ERR_INVALID_ARG, QN_ERR_EMPTY_CLOUD, QN_ERR_CAPACITY, QN_ERR_NOT_READY, QN_ERR_HIP, QN_ERR_NO_DEVICE, QN_ERR_INTERNAL = range(8)
 QN_SOURCE, QN_TARGET = 0, 1
 QN_VERIFY_SRC, QN_VERIFY_DST, QN_VERIFY_COARSE, QN_VERIFY_FINAL = 0, 1, 2, 3
 FLOAT_MAX = 3.4028234663852886e38
@@ -745,6 +745,38 @@ class OutlierStats(C.Structure):
                                                                                               ("mean_q", C.c_double), ("std_q", C.c_double), ("thr_q", C.c_double)]
 
 
+class GroundParams(C.Structure):
+    """qn_ground_params (40 bytes): the grid edge, the largest ground slope (rise over run), the ground tolerance, the clearance below which a point occupies
+    its column, and the points a column needs to seed the ground.  The defaults are interface choices, not measurements."""
+    _fields_ = [("cell", C.c_double), ("max_slope", C.c_double), ("ground_tol", C.c_double), ("clearance", C.c_double), ("min_points", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+    def __init__(self, cell=0.5, max_slope=0.3, ground_tol=0.2, clearance=2.0, min_points=1):
+        super().__init__(cell, max_slope, ground_tol, clearance, min_points, 0)
+
+    def twin(self):
+        """-> the mapground.GroundParams with these values"""
+        from . import mapground
+        return mapground.GroundParams(float(self.cell), float(self.max_slope), float(self.ground_tol), float(self.clearance), int(self.min_points))
+
+
+class GroundStats(C.Structure):
+    """qn_ground_stats (80 bytes); rounds is the only field the twin does not share"""
+    _fields_ = ([(f, C.c_uint32) for f in ("n", "n_finite", "n_none", "n_ground", "n_obstacle", "n_overhead", "n_below", "width", "height", "seeded", "occupied",
+                                           "free", "unknown")] +
+                [(f, C.c_int32) for f in ("quant_exp", "step_s", "step_d", "tol_q", "clear_q")] + [("rounds", C.c_uint32), ("reserved", C.c_uint32)])
+
+
+class GroundGrid(C.Structure):
+    """qn_ground_grid (40 bytes): the corner of column (0, 0), the edge, the size and the height unit 2^-quant_exp m of the occupancy grid"""
+    _fields_ = [("origin_x", C.c_double), ("origin_y", C.c_double), ("cell", C.c_double), ("width", C.c_uint32), ("height", C.c_uint32), ("quant_exp", C.c_int32),
+                ("reserved", C.c_uint32)]
+
+
+QN_GROUND_NONE, QN_GROUND_GROUND, QN_GROUND_OBSTACLE, QN_GROUND_OVERHEAD, QN_GROUND_BELOW = range(5)
+QN_GROUND_MAX_CELLS = 1 << 26
+
+
 class KeyframeStore:
     """Device-resident keyframe clouds + LoopClosure::setSrcAndDstCloud on the GPU (loop_closure.cpp:58-108)."""
 
@@ -1293,6 +1325,42 @@ class KeyframeStore:
         records x y z intensity.  download_map and map_normals serve the filtered map; the classification and any map normals are stale afterwards."""
         ptr = C.c_void_p(); n = C.c_uint32()
         self._check(self._l.qn_kf_map_remove_outliers(self.h, C.byref(ptr), C.byref(n)))
+        self._map_n = n.value
+        return ptr.value, n.value
+
+    # ---- the ground of the map slot and its occupancy grid (qn_kf_map_ground / _points / _grid / qn_kf_map_keep_classes; numpy twin: qn_amd/mapground.py)
+    def map_ground(self, params=None):
+        """qn_kf_map_ground on the map of the latest build or filter, then its per-point download.  params: a GroundParams (or a mapground.GroundParams); None:
+        the defaults.  -> (stats, classes (n,) uint8, height_q (n,) int32), equal to mapground.classify of the downloaded map; stats: a dict of the fields of
+        qn_ground_stats (rounds is the GPU's own).  The map slot is not touched; map_ground_grid serves the grid, map_keep_classes applies the classes."""
+        p = GroundParams() if params is None else params
+        if not isinstance(p, GroundParams):
+            p = GroundParams(float(p.cell), float(p.max_slope), float(p.ground_tol), float(p.clearance), int(p.min_points))
+        st = GroundStats()
+        self._check(self._l.qn_kf_map_ground(self.h, C.byref(p), C.byref(st)))
+        n = int(st.n)
+        cls = np.zeros(max(n, 1), np.uint8); hq = np.zeros(max(n, 1), np.int32)
+        self._check(self._l.qn_kf_map_ground_points(self.h, _p(cls), _p(hq)))
+        stats = {f: getattr(st, f) for f, _ in GroundStats._fields_ if f != "reserved"}
+        return stats, cls[:n], hq[:n]
+
+    def map_ground_grid(self):
+        """qn_kf_map_ground_grid -> (info, ground_q (H, W) int32, occupancy (H, W) uint8) of the latest map_ground: info a dict of origin_x, origin_y, cell, width,
+        height, quant_exp; the arrays row-major with y the slow axis; ground_q in units of 2^-quant_exp m; occupancy 0 unknown, 1 free, 2 occupied."""
+        g = GroundGrid()
+        self._check(self._l.qn_kf_map_ground_grid(self.h, C.byref(g), None, None))
+        W, H = int(g.width), int(g.height)
+        gq = np.zeros(max(W * H, 1), np.int32); occ = np.zeros(max(W * H, 1), np.uint8)
+        self._check(self._l.qn_kf_map_ground_grid(self.h, C.byref(g), _p(gq), _p(occ)))
+        info = {f: getattr(g, f) for f, _ in GroundGrid._fields_ if f != "reserved"}
+        return info, gq[:W * H].reshape(H, W), occ[:W * H].reshape(H, W)
+
+    def map_keep_classes(self, mask):
+        """qn_kf_map_keep_classes: the records of the latest map_ground whose class bit (1 << class) is set in mask become the map slot, in order -> (ptr, n):
+        the device address of the n float4 records x y z intensity.  download_map, map_normals and map_outliers serve the kept map; the ground results, any
+        outlier classification and any map normals are stale afterwards."""
+        ptr = C.c_void_p(); n = C.c_uint32()
+        self._check(self._l.qn_kf_map_keep_classes(self.h, C.c_uint32(int(mask) & 0xffffffff), C.byref(ptr), C.byref(n)))
         self._map_n = n.value
         return ptr.value, n.value
 

@@ -35,7 +35,8 @@ enum {
   QN_ERR_CAPACITY = 3,        /* cloud larger than the context's max_points                  */
   QN_ERR_NOT_READY = 4,       /* align before both clouds and both covariance sets exist     */
   QN_ERR_HIP = 5,             /* a HIP runtime call failed; see qn_last_error()              */
-  QN_ERR_NO_DEVICE = 6        /* no gfx950 device: the engine has NO CPU fallback            */
+  QN_ERR_NO_DEVICE = 6,       /* no gfx950 device: the engine has NO CPU fallback            */
+  QN_ERR_INTERNAL = 7         /* a bounded device loop did not end within its proven bound   */
 };
 
 enum { QN_SOURCE = 0, QN_TARGET = 1 };
@@ -656,6 +657,70 @@ void qn_outlier_default_params(qn_outlier_params* p);
 int  qn_kf_map_outliers(qn_kf_store*, const qn_outlier_params* params, qn_outlier_stats* stats_out);
 int  qn_kf_map_outlier_points(qn_kf_store*, uint32_t* count_out, uint32_t* mean_q_out, uint8_t* removed_out);
 int  qn_kf_map_remove_outliers(qn_kf_store*, const float** d_xyzi_out /* float4: x y z intensity */, uint32_t* n_out);
+/* ---- the map's ground and its occupancy grid (csrc/qn_mapground.hip; numpy twin and specification: qn_amd/mapground.py)
+ * What a user does with the corrected map next: split the ground from what stands on it, and flatten the result into the 2-D occupancy grid a planner or
+ * map_server loads (the "pcd2pgm" step over the saved map).  These calls do it on the GPU for the store's map slot as the latest build or filter left it.
+ * Heights are quantised once; everything afterwards is an integer, independent of any order, and equal to the twin's bit for bit.
+ * qn_ground_params (40 bytes): cell (grid edge in m; finite, > 0; default 0.5), max_slope (rise over run the ground may have; finite, > 0; default 0.3),
+ *   ground_tol (finite, >= 0; default 0.2), clearance (finite, > ground_tol; default 2.0), min_points (>= 1; default 1), reserved (0).  The defaults are
+ *   interface choices, not measurements.
+ * Units: e = the largest integer with cell * 2^e <= 2^10 (kept within [-126, 127]).  zq = (int32) rint(z * 2^e), half to even, the f32 z widened to f64 first
+ *   (the product is exact).  Host f64, no contraction: step_s = max(1, rint(max_slope * cell * 2^e)), step_d = (step_s * 181) >> 7 (a diagonal step, 181 / 128
+ *   being sqrt 2 rounded down), tol_q = rint(ground_tol * 2^e), clear_q = rint(clearance * 2^e); QN_ERR_INVALID_ARG when one of them is >= 2^30.
+ *   QN_ERR_CAPACITY when a finite point has |zq| >= 2^30.
+ * Columns: a finite point is one whose x, y and z are all finite.  Its column, in x and y only, is the voxel grid's arithmetic c = (int)(floorf(x * inv) -
+ *   (float)minb) with inv = (float)(1 / cell); minb and the grid W x H (width along x, height along y) come from the finite points' extremes.
+ *   QN_ERR_CAPACITY, before any grid-sized allocation, when floorf(x * inv) leaves the int32 range, when W or H exceeds 2^24 (below that the f32 subtraction
+ *   is exact) or when W * H > QN_GROUND_MAX_CELLS = 2^26.  Without a finite point the grid is 0 x 0.
+ * Seeds: cnt(c) = the finite points of column c; seed(c) = the smallest zq of the column when cnt(c) >= min_points, else INF = INT32_MAX.
+ * Ground envelope g: the greatest function on the dense grid with g(c) <= seed(c) and g(c) <= g(n) + step(n, c) for the eight neighbours n (step_s for a
+ *   straight one, step_d for a diagonal one; the sum saturates at INF).  It is unique; because step_s <= step_d <= 2 step_s it is g(c) = min over the seeded s of seed(s) + step_d *
+ *   min(dx, dy) + step_s * (max(dx, dy) - min(dx, dy)).  Empty columns get a value too; without a seeded column every g is INF.  No relaxation schedule
+ *   changes it.
+ * Classes, one byte per point, from h = zq - g(column): QN_GROUND_NONE 0 (a non-finite record, or g = INF), QN_GROUND_GROUND 1 (-tol_q <= h <= tol_q),
+ *   QN_GROUND_OBSTACLE 2 (tol_q < h <= clear_q), QN_GROUND_OVERHEAD 3 (h > clear_q), QN_GROUND_BELOW 4 (h < -tol_q: only possible in an unseeded column).
+ *   height_q = max(h, INT32_MIN + 1) (int32; h < 2^31 always), INT32_MIN for class 0.
+ * Occupancy, one byte per column: 0 unknown (no finite point), 2 occupied (at least one OBSTACLE point), 1 free (everything else).  OVERHEAD points do not
+ *   occupy: a bridge or a canopy stays drivable.
+ * qn_ground_stats (80 bytes): n, n_finite; n_none, n_ground, n_obstacle, n_overhead, n_below (the five class counts); width, height; seeded, occupied, free,
+ *   unknown (columns); quant_exp (e), step_s, step_d, tol_q, clear_q; rounds = the relaxation launches the GPU ran - it depends on the schedule and is the only
+ *   field the twin does not share; reserved (0).
+ * qn_ground_grid (40 bytes): origin_x, origin_y (minb * cell, f64: the corner of column (0, 0)), cell, width, height, quant_exp, reserved (0).
+ * qn_kf_map_ground: classifies the map slot as it stands; the slot itself is not touched.  The results stay resident for the slot's generation (any later map
+ *   build or filter, successful or not, ends it).  Host synchronisations: 2 + ceil(rounds / 8) - the extent, the envelope's flags every
+ *   QN_GROUND_ROUNDS_PER_CHECK = 8 launches, the counts.  The relaxation stops with QN_ERR_INTERNAL after max(W, H) + 2 rounds (a change crosses at most
+ *   max(W, H) cells; never seen).  QN_ERR_NOT_READY without a map.  QN_ERR_INVALID_ARG: a null pointer, a parameter outside the ranges above, reserved != 0,
+ *   a unit >= 2^30.  QN_ERR_CAPACITY as above.  A refused call leaves the previous results intact.
+ * qn_kf_map_ground_points: class_out (one byte per point) and height_q_out at the map's own indices; either may be NULL, not both.  QN_ERR_NOT_READY before a
+ *   successful qn_kf_map_ground and once the slot's generation has moved on.
+ * qn_kf_map_ground_grid: *info_out and the two arrays, row-major with y the slow axis (column (ix, iy) at iy * width + ix); the arrays may be NULL to fetch
+ *   the dimensions first.  ground_q is g in units of 2^-e m.  QN_ERR_NOT_READY as above.
+ * qn_kf_map_keep_classes: the records whose class bit (1 << class) is set in class_mask become the map slot, in order and all 16 bytes each (*d_xyzi_out,
+ *   *n_out; NULL and 0 when nothing is left).  The generation advances, so normals, outlier and ground results go stale; qn_kf_download_map,
+ *   qn_kf_map_normals and qn_kf_map_outliers then serve the kept map.  QN_ERR_NOT_READY without a live classification, and the slot is then unchanged.
+ *   QN_ERR_INVALID_ARG: class_mask 0 or with a bit >= 5 set, a null pointer.                                                                          */
+#define QN_GROUND_MAX_CELLS (1u << 26)
+#define QN_GROUND_ROUNDS_PER_CHECK 8
+#define QN_GROUND_NONE 0
+#define QN_GROUND_GROUND 1
+#define QN_GROUND_OBSTACLE 2
+#define QN_GROUND_OVERHEAD 3
+#define QN_GROUND_BELOW 4
+typedef struct qn_ground_params { double cell, max_slope, ground_tol, clearance; uint32_t min_points; uint32_t reserved; } qn_ground_params;   /* 40 bytes */
+typedef struct qn_ground_stats {
+  uint32_t n, n_finite;
+  uint32_t n_none, n_ground, n_obstacle, n_overhead, n_below;
+  uint32_t width, height;
+  uint32_t seeded, occupied, free, unknown;
+  int32_t quant_exp, step_s, step_d, tol_q, clear_q;
+  uint32_t rounds, reserved;
+} qn_ground_stats;                                                                                                           /* 80 bytes */
+typedef struct qn_ground_grid { double origin_x, origin_y, cell; uint32_t width, height; int32_t quant_exp; uint32_t reserved; } qn_ground_grid;   /* 40 bytes */
+void qn_ground_default_params(qn_ground_params* p);
+int  qn_kf_map_ground(qn_kf_store*, const qn_ground_params* params, qn_ground_stats* stats_out);
+int  qn_kf_map_ground_points(qn_kf_store*, uint8_t* class_out, int32_t* height_q_out);
+int  qn_kf_map_ground_grid(qn_kf_store*, qn_ground_grid* info_out, int32_t* ground_q_out, uint8_t* occupancy_out);
+int  qn_kf_map_keep_classes(qn_kf_store*, uint32_t class_mask, const float** d_xyzi_out /* float4: x y z intensity */, uint32_t* n_out);
 /* LoopClosure::fetchClosestKeyframeIdx (loop_closure.cpp:34-56) generalised to the max_k nearest admissible keyframes,
  * ascending distance; out[0] is the reference's single choice.  Host code (O(#keyframes)).                        */
 int  qn_loop_candidates(const double* pos_xyz, const double* stamps, uint32_t n, uint32_t query, double radius, double tdiff,

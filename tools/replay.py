@@ -221,6 +221,15 @@ def write_pcd_xyzi(path, pts):
             f.write("%.9g %.9g %.9g %.9g\n" % (p[0], p[1], p[2], p[3]))
 
 
+def write_grid(save_dir, stem, info, occupancy):
+    """stem.pgm and stem.yaml in map_server's conventions (qn_amd/mapground.to_pgm / map_yaml)"""
+    from qn_amd import mapground
+    with open(os.path.join(save_dir, stem + ".pgm"), "wb") as f:
+        f.write(mapground.to_pgm(occupancy))
+    with open(os.path.join(save_dir, stem + ".yaml"), "w") as f:
+        f.write(mapground.map_yaml(info, stem + ".pgm"))
+
+
 def write_pcd_xyzi_normal(path, pts, normals, curvature):
     """PCD v0.7 ASCII, FIELDS x y z intensity normal_x normal_y normal_z curvature (a PointXYZINormal cloud); a point without a normal carries nan"""
     with open(path, "w") as f:
@@ -289,7 +298,8 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
         save_map_leaf=None, sensor="uniform", detector="radius", sc_max_dist=0.3, yaw_bias=0.006, verify="reference", sc_top_k=1, loop_every=1, catch_up=False,
         submap_matching=False, min_overlap=None, overlap_radius=None, max_see_through=None, range_params=None, static_map=False, static_radius=15.0,
         static_max_k=8, moving_boxes=0, save_map_normals=False, normal_radius=0.6, normal_min_neighbors=5, map_outliers=False,
-        outlier_radius=1.0, outlier_k=8, outlier_std=2.0):
+        outlier_radius=1.0, outlier_k=8, outlier_std=2.0, occupancy_grid=False, grid_cell=0.5, max_slope=0.3, ground_tol=0.2, clearance=2.0,
+        drop_ground=False):
     """sensor = "uniform": keyframe clouds sampled uniformly by area inside a disc (make_stream); "spinning": ray-cast spinning-LiDAR
     scans from the ground-truth poses of the same figure-8 (make_lidar_stream).  detector = "radius": the candidate is the closest older
     keyframe within `radius` of the corrected position (LC:34-56); "scancontext": the older keyframe nearest by Scan Context distance, kept
@@ -335,6 +345,13 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
     written and before its normals are made: every point with fewer than outlier_k neighbours within outlier_radius, or whose mean distance to its outlier_k
     nearest exceeds the map's mean by more than outlier_std standard deviations, is removed (KeyframeStore.map_outliers / map_remove_outliers).
     out["map_outliers_removed"] (and out["static_outliers_removed"]): the points removed; out["map_points"] / out["static_map_points"]: what was written.
+    occupancy_grid (with save_dir and save_map_leaf; default False): the ground of the map as it is written - after the outlier filter when given - is
+    segmented and the map flattened into map.pgm and map.yaml, the 2-D occupancy grid a planner or map_server loads (columns of grid_cell m; ground slopes up
+    to max_slope rise over run; a point within ground_tol of the ground envelope is ground, one up to clearance above it occupies its column, one higher does
+    not: qn_amd/mapground.py), and with static_map map_static.pgm / map_static.yaml beside map_static.pcd.  On the GPU backend by KeyframeStore.map_ground /
+    map_ground_grid; on the oracle backend, which has no map of its own, the map is the oracle's voxel grid over every keyframe (map.pcd, intensity 0) and the
+    grid the numpy twin's.  out["grid"]: width, height, occupied, free, unknown, n_ground.  drop_ground (with occupancy_grid): map.pcd is written without its
+    GROUND class (KeyframeStore.map_keep_classes), the grid still comes from the whole map.
     moving_boxes = N (sensor="spinning" only; default 0: every run is what it was): N extra boxes in the scene that stand somewhere else in every keyframe
     (moving_box_prims), so every keyframe is cast by a call of its own."""
     if detector not in ("radius", "scancontext"):
@@ -384,6 +401,13 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
     if map_outliers and not (np.isfinite(outlier_radius) and outlier_radius > 0 and np.isfinite(outlier_std) and outlier_std >= 0 and int(outlier_k) == outlier_k
                              and 1 <= outlier_k <= 32):
         raise ValueError("map_outliers needs outlier_radius > 0, outlier_std >= 0 and 1 <= outlier_k <= 32, not %r / %r / %r" % (outlier_radius, outlier_std, outlier_k))
+    if occupancy_grid and (save_dir is None or save_map_leaf is None):
+        raise ValueError("occupancy_grid needs save_dir and save_map_leaf (the grid is made from the map that map.pcd is written from)")
+    if drop_ground and not occupancy_grid:
+        raise ValueError("drop_ground needs occupancy_grid (the ground comes from its segmentation)")
+    if occupancy_grid:
+        from qn_amd import mapground
+        mapground.units((grid_cell, max_slope, ground_tol, clearance, 1))                         # (raises ValueError on a parameter outside its range)
     overlaps = []; see_through = []; fs_images = {}
 
     def apply_freespace(rs, pairs):
@@ -650,7 +674,18 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
                 from qn_amd import engine
                 st = store.map_outliers(engine.OutlierParams(outlier_radius, outlier_std, int(outlier_k)))[0]
                 return store.map_remove_outliers()[1], int(st["removed"])
+            def ground_stage(stem, n):
+                """the occupancy grid of the map slot written as stem.pgm / stem.yaml; with drop_ground the GROUND class leaves the slot -> the points left"""
+                if not occupancy_grid:
+                    return n
+                from qn_amd import engine, mapground
+                st = store.map_ground(engine.GroundParams(grid_cell, max_slope, ground_tol, clearance, 1))[0]
+                info, _, occ = store.map_ground_grid()
+                write_grid(save_dir, stem, mapground.GridInfo(*(info[f] for f in mapground.GridInfo._fields)), occ)
+                out["grid" if stem == "map" else "static_grid"] = {k: int(st[k]) for k in ("width", "height", "occupied", "free", "unknown", "n_ground")}
+                return store.map_keep_classes(0b11101)[1] if drop_ground else n
             n, removed = filter_map(store.build_map(ids, corrected, save_map_leaf))
+            n = ground_stage("map", n)
             valid = write_map("map.pcd", n)
             if map_outliers:
                 out["map_points"] = n; out["map_outliers_removed"] = removed
@@ -662,10 +697,19 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
                     store.range_describe(ids)
                 st = store.static_classify(ids, corrected, radius=static_radius, max_k=static_max_k)
                 n, removed = filter_map(store.build_map_static(save_map_leaf))
+                n = ground_stage("map_static", n)
                 write_map("map_static.pcd", n)
                 if map_outliers:
                     out["static_outliers_removed"] = removed
                 out["static_removed"] = int(st["removed"].sum()); out["static_map_points"] = n
+        elif occupancy_grid:                                                                 # the oracle backend: the oracle's voxel grid, the twin's grid
+            from qn_amd import mapground
+            xyz = np.asarray(orc.assemble_submap(scans, corrected, list(range(len(scans))), save_map_leaf), np.float32)[:, :3]
+            pts = np.concatenate([xyz, np.zeros((len(xyz), 1), np.float32)], axis=1)
+            r = mapground.classify(pts, (grid_cell, max_slope, ground_tol, clearance, 1))
+            write_grid(save_dir, "map", r["info"], r["occupancy"])
+            out["grid"] = {k: int(getattr(r["stats"], k)) for k in ("width", "height", "occupied", "free", "unknown", "n_ground")}
+            write_pcd_xyzi(os.path.join(save_dir, "map.pcd"), mapground.keep(pts, r["classes"], 0b11101) if drop_ground else pts)
     if verbose:
         print({k: v for k, v in out.items() if k not in ("poses", "loop_list", "loop_T", "gt", "overlaps", "see_through")})
     if backend == "gpu":
@@ -706,6 +750,13 @@ if __name__ == "__main__":
     ap.add_argument("--outlier-radius", type=float, default=1.0, help="with --map-outliers: the neighbourhood radius [m]")
     ap.add_argument("--outlier-k", type=int, default=8, help="with --map-outliers: the nearest neighbours the mean distance is taken over (fewer within the radius: removed)")
     ap.add_argument("--outlier-std", type=float, default=2.0, help="with --map-outliers: removed above the mean of the mean distances plus this many standard deviations")
+    ap.add_argument("--occupancy-grid", action="store_true",
+                    help="with --save-dir and --save-map-leaf: also write map.pgm and map.yaml, the map's 2-D occupancy grid (ground segmented, obstacles projected)")
+    ap.add_argument("--grid-cell", type=float, default=0.5, help="with --occupancy-grid: the grid's cell edge [m]")
+    ap.add_argument("--max-slope", type=float, default=0.3, help="with --occupancy-grid: the steepest ground, rise over run")
+    ap.add_argument("--ground-tol", type=float, default=0.2, help="with --occupancy-grid: a point within this of the ground envelope is ground [m]")
+    ap.add_argument("--clearance", type=float, default=2.0, help="with --occupancy-grid: a point higher than this above the ground does not occupy its cell [m]")
+    ap.add_argument("--drop-ground", action="store_true", help="with --occupancy-grid: map.pcd is written without the ground points")
     ap.add_argument("--moving-boxes", type=int, default=0, help="with --sensor spinning: this many boxes that stand somewhere else in every keyframe")
     ap.add_argument("--backend", choices=["gpu", "oracle"], default="gpu", help="the engine on the GPU, or the CPU oracle")
     a = ap.parse_args()
@@ -713,8 +764,13 @@ if __name__ == "__main__":
         ap.error("--save-map-normals needs --save-dir and --save-map-leaf")
     if a.map_outliers and (a.save_dir is None or a.save_map_leaf is None):
         ap.error("--map-outliers needs --save-dir and --save-map-leaf")
+    if a.occupancy_grid and (a.save_dir is None or a.save_map_leaf is None):
+        ap.error("--occupancy-grid needs --save-dir and --save-map-leaf")
+    if a.drop_ground and not a.occupancy_grid:
+        ap.error("--drop-ground needs --occupancy-grid")
     run(a.keyframes, a.seed, a.quatro, save_dir=a.save_dir, save_map_leaf=a.save_map_leaf, sensor=a.sensor, detector=a.detector, yaw_bias=a.yaw_bias,
         verify=a.verify, sc_top_k=a.sc_top_k, backend=a.backend, loop_every=a.loop_every, catch_up=a.catch_up, submap_matching=a.submap_matching,
         min_overlap=a.min_overlap, overlap_radius=a.overlap_radius, max_see_through=a.max_see_through, static_map=a.static_map, moving_boxes=a.moving_boxes,
         save_map_normals=a.save_map_normals, normal_radius=a.normal_radius, map_outliers=a.map_outliers, outlier_radius=a.outlier_radius, outlier_k=a.outlier_k,
-        outlier_std=a.outlier_std)
+        outlier_std=a.outlier_std, occupancy_grid=a.occupancy_grid, grid_cell=a.grid_cell, max_slope=a.max_slope, ground_tol=a.ground_tol,
+        clearance=a.clearance, drop_ground=a.drop_ground)
