@@ -1,9 +1,10 @@
 // qn_kf_buf.h - the host plumbing every translation unit around a qn_kf_store shares: one error macro, one owned buffer with two ways to grow, one
-// get-or-create of a unit's per-store state.  Header only.  Rule of the buffers: a call that fails leaves nothing stale behind - a buffer that could not
+// get-or-create of a unit's per-store state, one pair of result sets for the units whose results belong to the map slot.  Header only.  Rule of the buffers: a call that fails leaves nothing stale behind - a buffer that could not
 // be grown is empty, a slot array that could not be moved is the old one, and the HIP runtime's sticky error is cleared (a hipGetLastError() behind a later
 // launch on this thread would otherwise report the old out-of-memory as its own).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <cmath>
 #include <new>
 #include <string>
 #include <utility>
@@ -93,4 +94,29 @@ template <typename St, typename FirstUse> int qn_kf_ext_state(qn_kf_store* s, in
 }
 template <typename St> int qn_kf_ext_state(qn_kf_store* s, int slot, St** out) {
   return qn_kf_ext_state(s, slot, out, [](St*) { return QN_OK; });
+}
+
+// The per-store state of a unit whose results belong to the map slot as it stood at one generation (qn_mapnormals.hip, qn_mapoutliers.hip, qn_mapground.hip):
+// two result sets, the live one holding what the latest successful call computed for the map of generation `gen` with its n points.  A call writes spare()
+// and commits on success, so a refused call leaves the previous results as they were.
+template <typename Set> struct KfMapResults {
+  bool live = false; uint64_t gen = 0; uint32_t n = 0; int cur = 0;
+  Set set[2];
+  Set& spare() { return set[live ? 1 - cur : cur]; }
+  void commit(uint64_t map_gen, uint32_t map_n) { if (live) cur = 1 - cur; live = true; gen = map_gen; n = map_n; }
+  // the live set of the state in extension slot `slot` if it is that of the map slot as it stands (*map its records, *n their number), else nullptr
+  static const Set* lookup(qn_kf_store* s, int slot, const float4** map, uint32_t* n) {
+    const KfMapResults* st = (const KfMapResults*)qn_kf_int_ext(s, slot);
+    uint64_t map_gen = 0;
+    *map = qn_kf_int_map(s, n, &map_gen);
+    return st && st->live && *map && st->gen == map_gen && st->n == *n ? &st->set[st->cur] : nullptr;
+  }
+};
+
+// the largest e with x 2^e <= 2^bits, within the exponents of normal f32 powers of two (the twins' quant_exponent): the scale 2^e of a unit's integers
+inline int qn_quant_exponent(double x, int bits) {
+  int ex = 0;
+  const double m = std::frexp(x, &ex);                   // x = m 2^ex, 0.5 <= m < 1
+  const int e = (m == 0.5 ? bits + 1 : bits) - ex;
+  return e < -126 ? -126 : e > 127 ? 127 : e;
 }

@@ -18,13 +18,13 @@
 //             QN_GROUND_ROUNDS_PER_CHECK rounds, then reads the flags, and stops at the first round that changed nothing (both buffers then hold g).  A round
 //             carries a change across at least one column, so max(W, H) + 2 rounds bound the loop (QN_ERR_INTERNAL beyond it).
 //   classify  k_mg_classify, one point per lane in the map's own order: the class byte, height_q, the column's occupied byte (a plain store of the same value
-//             by whoever finds an obstacle), the five class counts of the block by ballots into its slot.  k_mg_occ_count counts the occupied and the unknown
-//             columns; k_mg_sum adds slots up.
-//   keep      qn_kf_map_keep_classes: k_mg_keep_flag (the removed byte from the class mask, the block's kept count), then the scan and the stable compaction of
-//             qn_map_compact.cuh that the outlier filter uses, and qn_kf_int_map_shrink, which advances the slot's generation.
+//             by whoever finds an obstacle), the five class counts of the block into its slot.  k_mg_occ_count counts the occupied and the unknown columns.  Every
+//             count of a block goes through block_count and is added up by k_slot_fold (qn_map_compact.cuh).
+//   keep      qn_kf_map_keep_classes: k_mg_keep_flag (the removed byte from the class mask, the block's kept count), then the scan and the shared end of the
+//             map's filters (qn_map_compact.cuh), which the outlier filter uses.
 // Host synchronisations of a classify: 2 + ceil(rounds / QN_GROUND_ROUNDS_PER_CHECK) - the extent, the flags of every batch of rounds, the counts at the end.
-// No f32 or f64 arithmetic on the device after k_mg_bin's quantisation.  Results go into the spare one of two buffer sets, swapped on success, so a refused
-// call leaves the previous results as they were.
+// No f32 or f64 arithmetic on the device after k_mg_bin's quantisation.  Results are committed only on success (KfMapResults, qn_kf_buf.h), so a refused call
+// leaves the previous results as they were.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <climits>
@@ -42,7 +42,7 @@
 namespace {
 
 #define MG_WAVES (MG_BLOCK / 64)
-#define MG_SUM_BLOCK 1024
+#define MG_SUM_BLOCK MO_SCAN_BLOCK
 #define MG_HALO (MG_TILE + 2)
 #define MG_INF INT32_MAX
 #define MG_NO_COL 0xffffffffu
@@ -50,6 +50,7 @@ namespace {
 #define MG_MAX_SIDE (1u << 24)
 
 static_assert(MG_BLOCK * 4 == MG_TILE * MG_TILE, "k_mg_relax: four columns of the tile per thread");
+static_assert(MG_BLOCK == MO_BLOCK, "block_count counts the waves of MO_BLOCK threads");
 
 __device__ __forceinline__ float mg_wave_min(float v) {
 #pragma unroll
@@ -65,7 +66,6 @@ __device__ __forceinline__ float mg_wave_max(float v) {
 // the finite points of the block: slots[8 b ..] = min x, min y, min z, max x, max y, max z (f32 bits), their number, 0
 __global__ void __launch_bounds__(MG_BLOCK) k_mg_extent(uint32_t n, const float4* __restrict__ map, uint32_t* __restrict__ slots) {
   __shared__ float ws[6][MG_WAVES];
-  __shared__ uint32_t wc[MG_WAVES];
   const uint32_t i = blockIdx.x * MG_BLOCK + threadIdx.x;
   float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
   bool fin = false;
@@ -74,23 +74,17 @@ __global__ void __launch_bounds__(MG_BLOCK) k_mg_extent(uint32_t n, const float4
     fin = isfinite(p.x) && isfinite(p.y) && isfinite(p.z);
     if (fin) { lo[0] = hi[0] = p.x; lo[1] = hi[1] = p.y; lo[2] = hi[2] = p.z; }
   }
-  const uint32_t c = (uint32_t)__popcll(__ballot(fin));
   const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
   for (int a = 0; a < 3; a++) {
     const float l = mg_wave_min(lo[a]), h = mg_wave_max(hi[a]);
     if (lane == 0) { ws[a][wave] = l; ws[3 + a][wave] = h; }
   }
-  if (lane == 0) wc[wave] = c;
-  __syncthreads();
+  block_count(slots + 8 * (size_t)blockIdx.x + 6, fin);  // (its barrier is the one the extremes wait for)
   if (threadIdx.x < 6) {
     float v = ws[threadIdx.x][0];
     for (int w = 1; w < MG_WAVES; w++) v = threadIdx.x < 3 ? fminf(v, ws[threadIdx.x][w]) : fmaxf(v, ws[threadIdx.x][w]);
     slots[8 * (size_t)blockIdx.x + threadIdx.x] = __float_as_uint(v);
-  } else if (threadIdx.x == 6) {
-    uint32_t acc = 0;
-    for (int w = 0; w < MG_WAVES; w++) acc += wc[w];
-    slots[8 * (size_t)blockIdx.x + 6] = acc;
   }
 }
 
@@ -112,8 +106,7 @@ __global__ void __launch_bounds__(MG_SUM_BLOCK) k_mg_extent_sum(const uint32_t* 
     const float l = mg_wave_min(lo[a]), h = mg_wave_max(hi[a]);
     if (lane == 0) { ws[a][wave] = l; ws[3 + a][wave] = h; }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o);
+  c = wave_sum(c);
   if (lane == 0) wc[wave] = c;
   __syncthreads();
   if (threadIdx.x < 6) {
@@ -151,7 +144,6 @@ __global__ void __launch_bounds__(MG_BLOCK) k_mg_bin(uint32_t n, const float4* _
 // one column per lane: (count, lowest) -> the seed in place, the occupancy base, the block's seeded columns into its slot
 __global__ void __launch_bounds__(MG_BLOCK) k_mg_seed(uint32_t cells, const uint32_t* __restrict__ cnt, int32_t* __restrict__ seed, uint32_t min_points,
                                                       uint8_t* __restrict__ occ, uint32_t* __restrict__ slots) {
-  __shared__ uint32_t wk[MG_WAVES];
   const uint32_t c = blockIdx.x * MG_BLOCK + threadIdx.x;
   bool seeded = false;
   if (c < cells) {
@@ -160,14 +152,7 @@ __global__ void __launch_bounds__(MG_BLOCK) k_mg_seed(uint32_t cells, const uint
     if (!seeded) seed[c] = MG_INF;
     occ[c] = k ? 1 : 0;
   }
-  const uint32_t w = (uint32_t)__popcll(__ballot(seeded));
-  if ((threadIdx.x & 63) == 0) wk[threadIdx.x >> 6] = w;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint32_t acc = 0;
-    for (int v = 0; v < MG_WAVES; v++) acc += wk[v];
-    slots[blockIdx.x] = acc;
-  }
+  block_count(slots + blockIdx.x, seeded);
 }
 
 __device__ __forceinline__ int mg_step(int v, int step) { return v > MG_INF - step ? MG_INF : v + step; }       // v + step saturating at INF (INF stays INF)
@@ -214,7 +199,6 @@ __global__ void __launch_bounds__(MG_BLOCK) k_mg_relax(const int32_t* __restrict
 __global__ void __launch_bounds__(MG_BLOCK) k_mg_classify(uint32_t n, const int32_t* __restrict__ zq, const uint32_t* __restrict__ col, const int32_t* __restrict__ g,
                                                           int tol_q, int clear_q, uint8_t* __restrict__ cls, int32_t* __restrict__ height, uint8_t* __restrict__ occ,
                                                           uint32_t* __restrict__ slots) {
-  __shared__ uint32_t wk[5][MG_WAVES];
   const uint32_t i = blockIdx.x * MG_BLOCK + threadIdx.x;
   int c = -1;                                            // (past the end: counted nowhere)
   if (i < n) {
@@ -232,102 +216,31 @@ __global__ void __launch_bounds__(MG_BLOCK) k_mg_classify(uint32_t n, const int3
     }
     cls[i] = (uint8_t)c; height[i] = hq;
   }
-#pragma unroll
-  for (int v = 0; v < 5; v++) {
-    const uint32_t w = (uint32_t)__popcll(__ballot(c == v));
-    if ((threadIdx.x & 63) == 0) wk[v][threadIdx.x >> 6] = w;
-  }
-  __syncthreads();
-  if (threadIdx.x < 5) {
-    uint32_t acc = 0;
-    for (int w = 0; w < MG_WAVES; w++) acc += wk[threadIdx.x][w];
-    slots[5 * (size_t)blockIdx.x + threadIdx.x] = acc;
-  }
+  block_count(slots + 5 * (size_t)blockIdx.x, c == QN_GROUND_NONE, c == QN_GROUND_GROUND, c == QN_GROUND_OBSTACLE, c == QN_GROUND_OVERHEAD, c == QN_GROUND_BELOW);
 }
 
 // one column per lane: the block's occupied and unknown columns into slots[2 b ..]
 __global__ void __launch_bounds__(MG_BLOCK) k_mg_occ_count(uint32_t cells, const uint8_t* __restrict__ occ, uint32_t* __restrict__ slots) {
-  __shared__ uint32_t wk[2][MG_WAVES];
   const uint32_t c = blockIdx.x * MG_BLOCK + threadIdx.x;
   const int v = c < cells ? (int)occ[c] : 1;
-  const uint32_t a = (uint32_t)__popcll(__ballot(v == 2)), b = (uint32_t)__popcll(__ballot(v == 0));
-  if ((threadIdx.x & 63) == 0) { wk[0][threadIdx.x >> 6] = a; wk[1][threadIdx.x >> 6] = b; }
-  __syncthreads();
-  if (threadIdx.x < 2) {
-    uint32_t acc = 0;
-    for (int w = 0; w < MG_WAVES; w++) acc += wk[threadIdx.x][w];
-    slots[2 * (size_t)blockIdx.x + threadIdx.x] = acc;
-  }
-}
-
-// one block: out[j] = the sum over the nb blocks of slots[stride b + j], j < stride <= 5
-__global__ void __launch_bounds__(MG_SUM_BLOCK) k_mg_sum(const uint32_t* __restrict__ slots, uint32_t nb, uint32_t stride, uint32_t* __restrict__ out) {
-  __shared__ uint32_t ws[5][MG_SUM_BLOCK / 64];
-  uint32_t a[5] = {0, 0, 0, 0, 0};
-  for (uint32_t b = threadIdx.x; b < nb; b += MG_SUM_BLOCK) {
-#pragma unroll
-    for (int j = 0; j < 5; j++) if ((uint32_t)j < stride) a[j] += slots[(size_t)stride * b + j];
-  }
-#pragma unroll
-  for (int j = 0; j < 5; j++) {
-    uint32_t v = a[j];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
-    if ((threadIdx.x & 63) == 0) ws[j][threadIdx.x >> 6] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < stride) {
-    uint32_t acc = 0;
-    for (int w = 0; w < MG_SUM_BLOCK / 64; w++) acc += ws[threadIdx.x][w];
-    out[threadIdx.x] = acc;
-  }
+  block_count(slots + 2 * (size_t)blockIdx.x, v == 2, v == 0);
 }
 
 // one point per lane: removed = the class's bit is not in the mask; the block's kept records into its slot (what k_mo_scan / k_mo_compact go on from)
 __global__ void __launch_bounds__(MO_BLOCK) k_mg_keep_flag(uint32_t n, const uint8_t* __restrict__ cls, uint32_t mask, uint8_t* __restrict__ removed,
                                                            uint32_t* __restrict__ blk_kept) {
-  __shared__ uint32_t wk[MO_WAVES];
   const uint32_t i = blockIdx.x * MO_BLOCK + threadIdx.x;
   bool keep = false;
   if (i < n) {
     keep = ((mask >> cls[i]) & 1u) != 0;
     removed[i] = keep ? 0 : 1;
   }
-  const uint32_t c = (uint32_t)__popcll(__ballot(keep));
-  if ((threadIdx.x & 63) == 0) wk[threadIdx.x >> 6] = c;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint32_t acc = 0;
-    for (int w = 0; w < MO_WAVES; w++) acc += wk[w];
-    blk_kept[blockIdx.x] = acc;
-  }
+  block_count(blk_kept + blockIdx.x, keep);
 }
 
-// The store's ground state (slot QN_KF_INT_EXT_GROUND): two sets of buffers, the live one holding the results of the latest successful call for the map of
-// generation `gen` with its n points; a call writes the other set and swaps on success.
-struct MgSet { DevBuf<uint8_t> cls, occ; DevBuf<int32_t> height, ground; };
-struct GroundState {
-  bool live = false; uint64_t gen = 0; uint32_t n = 0; int cur = 0;
-  qn_ground_grid info[2];
-  MgSet set[2];
-};
-
-// the live results if they are those of the map slot as it stands, else nullptr
-GroundState* live_state(qn_kf_store* s, const float4** map) {
-  GroundState* st = (GroundState*)qn_kf_int_ext(s, QN_KF_INT_EXT_GROUND);
-  uint32_t map_n = 0; uint64_t gen = 0;
-  *map = qn_kf_int_map(s, &map_n, &gen);
-  if (!st || !st->live || !*map || st->gen != gen || st->n != map_n) return nullptr;
-  return st;
-}
-
-// the largest e with cell 2^e <= 2^10, within the exponents of normal f32 powers of two (mapground.quant_exponent)
-int quant_exponent(double cell) {
-  int x = 0;
-  const double m = std::frexp(cell, &x);                 // cell = m 2^x, 0.5 <= m < 1
-  const int e = m == 0.5 ? 11 - x : 10 - x;
-  return e < -126 ? -126 : e > 127 ? 127 : e;
-}
+// the store's ground state (slot QN_KF_INT_EXT_GROUND)
+struct MgSet { DevBuf<uint8_t> cls, occ; DevBuf<int32_t> height, ground; qn_ground_grid info; };
+typedef KfMapResults<MgSet> GroundState;
 
 }  // namespace
 
@@ -343,7 +256,7 @@ extern "C" int qn_kf_map_ground(qn_kf_store* s, const qn_ground_params* params, 
   if (!std::isfinite(P.cell) || !(P.cell > 0.0) || !std::isfinite(P.max_slope) || !(P.max_slope > 0.0) || !std::isfinite(P.ground_tol) || !(P.ground_tol >= 0.0) ||
       !std::isfinite(P.clearance) || !(P.clearance > P.ground_tol) || P.min_points < 1 || P.reserved != 0)
     return QN_ERR_INVALID_ARG;
-  const int e = quant_exponent(P.cell);
+  const int e = qn_quant_exponent(P.cell, 10);           // a cell is 2^9 .. 2^10 units: the steps, tolerances and |zq| refused at 2^30 span 2^20 cells, h fits 64 bits
   const double scale = std::ldexp(1.0, e);
   const double fs = std::rint(P.max_slope * P.cell * scale), ft = std::rint(P.ground_tol * scale), fc = std::rint(P.clearance * scale);
   if (!(fs < (double)MG_LIMIT && ft < (double)MG_LIMIT && fc < (double)MG_LIMIT)) return QN_ERR_INVALID_ARG;
@@ -404,8 +317,7 @@ extern "C" int qn_kf_map_ground(qn_kf_store* s, const qn_ground_params* params, 
   r.width = G.W; r.height = G.H;
   const uint32_t cells = G.W * G.H, cb = (cells + MG_BLOCK - 1) / MG_BLOCK;
   // ---- the buffers: the spare result set, and scratch (1: zq, 2: columns, 3: slots and sums, 4: column counts, 5: the envelope's other buffer, 6: flags)
-  const int spare = st->live ? 1 - st->cur : st->cur;
-  MgSet& o = st->set[spare];
+  MgSet& o = st->spare();
   if (!o.cls.grow(s, std::max<size_t>(n, 1)) || !o.height.grow(s, std::max<size_t>(n, 1)) || !o.occ.grow(s, std::max<size_t>(cells, 1)) ||
       !o.ground.grow(s, std::max<size_t>(cells, 1)))
     return QN_ERR_HIP;
@@ -427,7 +339,7 @@ extern "C" int qn_kf_map_ground(qn_kf_store* s, const qn_ground_params* params, 
   uint32_t rounds = 0;
   if (cells) {
     hipLaunchKernelGGL(k_mg_seed, dim3(cb), dim3(MG_BLOCK), 0, stream, cells, (const uint32_t*)d_cnt, o.ground.p, P.min_points, o.occ.p, d_slots);
-    hipLaunchKernelGGL(k_mg_sum, dim3(1), dim3(MG_SUM_BLOCK), 0, stream, (const uint32_t*)d_slots, cb, 1u, d_sums);
+    hipLaunchKernelGGL((k_slot_fold<uint32_t, 1>), dim3(1), dim3(MG_SUM_BLOCK), 0, stream, (const uint32_t*)d_slots, cb, d_sums);
     QN_KFCHK(s, hipGetLastError());
     // ---- the envelope: rounds in batches, the flags read once a batch; max(W, H) + 2 rounds bound the loop
     const uint32_t tiles_x = (G.W + MG_TILE - 1) / MG_TILE, tiles_y = (G.H + MG_TILE - 1) / MG_TILE;
@@ -452,10 +364,10 @@ extern "C" int qn_kf_map_ground(qn_kf_store* s, const qn_ground_params* params, 
   }
   hipLaunchKernelGGL(k_mg_classify, dim3(nb), dim3(MG_BLOCK), 0, stream, n, (const int32_t*)d_zq, (const uint32_t*)d_col, (const int32_t*)o.ground.p, tol_q, clear_q,
                      o.cls.p, o.height.p, o.occ.p, d_slots);
-  hipLaunchKernelGGL(k_mg_sum, dim3(1), dim3(MG_SUM_BLOCK), 0, stream, (const uint32_t*)d_slots, nb, 5u, d_sums + 1);
+  hipLaunchKernelGGL((k_slot_fold<uint32_t, 5>), dim3(1), dim3(MG_SUM_BLOCK), 0, stream, (const uint32_t*)d_slots, nb, d_sums + 1);
   if (cells) {
     hipLaunchKernelGGL(k_mg_occ_count, dim3(cb), dim3(MG_BLOCK), 0, stream, cells, (const uint8_t*)o.occ.p, d_slots);
-    hipLaunchKernelGGL(k_mg_sum, dim3(1), dim3(MG_SUM_BLOCK), 0, stream, (const uint32_t*)d_slots, cb, 2u, d_sums + 6);
+    hipLaunchKernelGGL((k_slot_fold<uint32_t, 2>), dim3(1), dim3(MG_SUM_BLOCK), 0, stream, (const uint32_t*)d_slots, cb, d_sums + 6);
   }
   QN_KFCHK(s, hipGetLastError());
   QN_KFCHK(s, hipMemcpyAsync(h, d_sums, sizeof(uint32_t) * 8, hipMemcpyDeviceToHost, stream));
@@ -464,51 +376,48 @@ extern "C" int qn_kf_map_ground(qn_kf_store* s, const qn_ground_params* params, 
   r.n_none = h[1]; r.n_ground = h[2]; r.n_obstacle = h[3]; r.n_overhead = h[4]; r.n_below = h[5];
   r.occupied = h[6]; r.unknown = h[7]; r.free = cells - h[6] - h[7];
   r.rounds = rounds;
-  st->cur = spare; st->live = true; st->gen = gen; st->n = n; st->info[spare] = info;
+  o.info = info;
+  st->commit(gen, n);
   *stats_out = r;
   return QN_OK;
 }
 
 extern "C" int qn_kf_map_ground_points(qn_kf_store* s, uint8_t* class_out, int32_t* height_q_out) {
   if (!s || (!class_out && !height_q_out)) return QN_ERR_INVALID_ARG;
-  const float4* map = nullptr;
-  const GroundState* st = live_state(s, &map);
-  if (!st) return QN_ERR_NOT_READY;
-  const MgSet& o = st->set[st->cur];
-  const size_t n = st->n;
+  const float4* map = nullptr; uint32_t n = 0;
+  const MgSet* o = GroundState::lookup(s, QN_KF_INT_EXT_GROUND, &map, &n);
+  if (!o) return QN_ERR_NOT_READY;
   QN_KFCHK(s, hipSetDevice(qn_kf_int_device(s)));
   hipStream_t stream = qn_kf_int_stream(s);
-  if (class_out) QN_KFCHK(s, hipMemcpyAsync(class_out, o.cls.p, n, hipMemcpyDeviceToHost, stream));
-  if (height_q_out) QN_KFCHK(s, hipMemcpyAsync(height_q_out, o.height.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, stream));
+  if (class_out) QN_KFCHK(s, hipMemcpyAsync(class_out, o->cls.p, n, hipMemcpyDeviceToHost, stream));
+  if (height_q_out) QN_KFCHK(s, hipMemcpyAsync(height_q_out, o->height.p, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, stream));
   QN_KFCHK(s, hipStreamSynchronize(stream));
   return QN_OK;
 }
 
 extern "C" int qn_kf_map_ground_grid(qn_kf_store* s, qn_ground_grid* info_out, int32_t* ground_q_out, uint8_t* occupancy_out) {
   if (!s || !info_out) return QN_ERR_INVALID_ARG;
-  const float4* map = nullptr;
-  const GroundState* st = live_state(s, &map);
-  if (!st) return QN_ERR_NOT_READY;
-  const MgSet& o = st->set[st->cur];
-  const qn_ground_grid& g = st->info[st->cur];
+  const float4* map = nullptr; uint32_t n = 0;
+  const MgSet* o = GroundState::lookup(s, QN_KF_INT_EXT_GROUND, &map, &n);
+  if (!o) return QN_ERR_NOT_READY;
+  const qn_ground_grid& g = o->info;
   const size_t cells = (size_t)g.width * g.height;
   *info_out = g;
   if (!cells || (!ground_q_out && !occupancy_out)) return QN_OK;
   QN_KFCHK(s, hipSetDevice(qn_kf_int_device(s)));
   hipStream_t stream = qn_kf_int_stream(s);
-  if (ground_q_out) QN_KFCHK(s, hipMemcpyAsync(ground_q_out, o.ground.p, sizeof(int32_t) * cells, hipMemcpyDeviceToHost, stream));
-  if (occupancy_out) QN_KFCHK(s, hipMemcpyAsync(occupancy_out, o.occ.p, cells, hipMemcpyDeviceToHost, stream));
+  if (ground_q_out) QN_KFCHK(s, hipMemcpyAsync(ground_q_out, o->ground.p, sizeof(int32_t) * cells, hipMemcpyDeviceToHost, stream));
+  if (occupancy_out) QN_KFCHK(s, hipMemcpyAsync(occupancy_out, o->occ.p, cells, hipMemcpyDeviceToHost, stream));
   QN_KFCHK(s, hipStreamSynchronize(stream));
   return QN_OK;
 }
 
 extern "C" int qn_kf_map_keep_classes(qn_kf_store* s, uint32_t class_mask, const float** d_xyzi_out, uint32_t* n_out) {
   if (!s || !d_xyzi_out || !n_out || class_mask == 0 || (class_mask & ~31u)) return QN_ERR_INVALID_ARG;
-  const float4* map = nullptr;
-  GroundState* st = live_state(s, &map);
-  if (!st) return QN_ERR_NOT_READY;
-  const MgSet& o = st->set[st->cur];
-  const uint32_t n = st->n, nb = (n + MO_BLOCK - 1) / MO_BLOCK;
+  const float4* map = nullptr; uint32_t n = 0;
+  const MgSet* o = GroundState::lookup(s, QN_KF_INT_EXT_GROUND, &map, &n);
+  if (!o) return QN_ERR_NOT_READY;
+  const uint32_t nb = (n + MO_BLOCK - 1) / MO_BLOCK;
   QN_KFCHK(s, hipSetDevice(qn_kf_int_device(s)));
   hipStream_t stream = qn_kf_int_stream(s);
   float4* d_kept = (float4*)qn_kf_int_scratch(s, 1, sizeof(float4) * (size_t)n);
@@ -517,18 +426,10 @@ extern "C" int qn_kf_map_keep_classes(qn_kf_store* s, uint32_t class_mask, const
   uint32_t* h = (uint32_t*)qn_kf_int_pinned(s, 64);
   if (!d_kept || !d_removed || !d_blk || !h) return qn_kf_fail(s, "qn_kf_map_keep_classes: scratch allocation failed");
   uint32_t* d_off = d_blk + nb;
-  hipLaunchKernelGGL(k_mg_keep_flag, dim3(nb), dim3(MO_BLOCK), 0, stream, n, (const uint8_t*)o.cls.p, class_mask, d_removed, d_blk);
+  hipLaunchKernelGGL(k_mg_keep_flag, dim3(nb), dim3(MO_BLOCK), 0, stream, n, (const uint8_t*)o->cls.p, class_mask, d_removed, d_blk);
   hipLaunchKernelGGL(k_mo_scan, dim3(1), dim3(MO_SCAN_BLOCK), 0, stream, (const uint32_t*)d_blk, nb, d_off);
-  hipLaunchKernelGGL(k_mo_compact, dim3(nb), dim3(MO_BLOCK), 0, stream, n, map, (const uint8_t*)d_removed, (const uint32_t*)d_off, d_kept);
   QN_KFCHK(s, hipGetLastError());
   QN_KFCHK(s, hipMemcpyAsync(h, d_off + nb, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
   QN_KFCHK(s, hipStreamSynchronize(stream));
-  const uint32_t kept = h[0];
-  // from here on the slot changes: its generation advances, so these results, any outlier classification and any map normals are stale
-  const int rc = qn_kf_int_map_shrink(s, d_kept, kept);
-  if (rc != QN_OK) return rc;
-  QN_KFCHK(s, hipStreamSynchronize(stream));
-  uint32_t m = 0; uint64_t gen = 0;
-  *d_xyzi_out = (const float*)qn_kf_int_map(s, &m, &gen); *n_out = m;
-  return QN_OK;
+  return qn_kf_map_compact_shrink(s, map, n, d_removed, d_off, d_kept, h[0], d_xyzi_out, n_out);
 }

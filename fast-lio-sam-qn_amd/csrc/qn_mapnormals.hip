@@ -5,22 +5,19 @@
 // and the curvature; the nearest viewpoint orients the normal.  Count, moments and viewpoint index equal the twin's bit for bit, and so does the covariance:
 // the integer sums do not depend on the order the neighbours are met in, and the f64 arithmetic behind them is the same IEEE operations in the same order (the
 // library is built without contraction).  Only the eigen solve differs from the twin's LAPACK call, by what two backward-stable solves may differ.
-//   index     qn_kf_int_cell_index (qn_cloud.hip) over the map as one cloud, one segment: cells of edge >= r with the margin that puts every point within r
-//             into the 3 x 3 x 3 block around the query's cell (argument there), points sorted by cell, the non-finite ones behind; k_mn_gather lays the sorted
-//             points (original index in .w) and their cell words out flat.
+//   index     qn_kf_int_cell_index (qn_cloud.hip) over the map as one cloud, one segment; k_cell_gather lays the sorted points (original index in .w) and their
+//             cell words out flat (qn_cell_walk.cuh, with the walk and its exactness argument).
 //   normals   k_map_normals, one point per lane, 256 lanes a block, in the sorted order: neighbouring lanes are neighbouring points and read the same runs.
-//             The 27 cells are nine x-runs (cells x-1 .. x+1 of one (y, z) are consecutive keys), each located once by a binary search that starts where the
-//             previous run ended; candidates are read four a trip and scored with sqdist3; k, s1[3], s2[6] stay in registers (u32 and int64; di * dj is one
-//             64-bit multiply-add).  Then the viewpoints pass through LDS in tiles of 256 (three f64 planes, every lane reads the same address: a
-//             broadcast), the covariance and the cyclic Jacobi solve (qn_eig3.cuh, a fixed sweep count) run in the same thread, and the results go back to the
-//             point's own index in the map.  No atomics, no scratch memory; two host synchronisations a call (the index's, and one at the end).
+//             The candidates of the walk within r: k, s1[3], s2[6] stay in registers (u32 and int64; di * dj is one 64-bit multiply-add).  Then the
+//             viewpoints pass through LDS in tiles of 256 (three f64 planes, every lane reads the same address: a broadcast), the covariance and the cyclic
+//             Jacobi solve (qn_eig3.cuh, a fixed sweep count) run in the same thread, and the results go back to the point's own index in the map.  No
+//             atomics, no scratch memory; two host synchronisations a call (the index's, and one at the end).
 // One lane per point rather than a few lanes per point with a cross-lane reduce: a map point at the usual leaf has tens of neighbours among one or two hundred
 // candidates, the lanes of a wave walk the same runs, and the solve and the viewpoint loop - the larger part of the arithmetic - are per point either way.
 // Overflow: |di| <= 2^20 + 1 (|d| <= r (1 + 2^-21) and r 2^e <= 2^20), so |di dj| < 2^41 and the int64 sums are exact below 2^21 neighbours.  The kernel
 // counts the candidates it scans per point - the points of the 3 x 3 x 3 block - and raises a flag at 2^21; the call then returns QN_ERR_CAPACITY.  (The
 // cell-count bound of the index does not exclude this by itself: a passed-through, unfiltered map may put any number of points into one cell.)  Results are
-// written into the spare one of two buffer sets and the sets are swapped on success, so a refused call - this refusal included - leaves the previous results
-// as they were.
+// committed only on success (KfMapResults, qn_kf_buf.h), so a refused call - this refusal included - leaves the previous results as they were.
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include <cstring>
@@ -28,35 +25,16 @@
 #include <vector>
 #include "../../include/qn_engine.h"
 #include "qn_kf_buf.h"
+#include "qn_cell_walk.cuh"
 #include "qn_eig3.cuh"
 
 namespace {
 
-#define MN_BLOCK 256
+#define MN_BLOCK QN_CW_BLOCK
 #define MN_VTILE 256                                     // viewpoints per LDS tile (3 x 256 f64 = 6 KiB)
 #define MN_MAX_BLOCK_POINTS (1u << 21)
 
-struct MnSeg { uint32_t n, nfin, prefix; float inv; float minb[3]; int div[3]; };
-
-// the sorted order laid out flat (k_overlap_gather's layout for the one segment at 0): sorted point t with its original index (bits in .w), and its cell word
-__global__ void __launch_bounds__(MN_BLOCK) k_mn_gather(uint32_t n, const unsigned long long* __restrict__ keys, const float4* __restrict__ pts,
-                                                        float4* __restrict__ spts, uint32_t* __restrict__ cells) {
-  const uint32_t t = blockIdx.x * MN_BLOCK + threadIdx.x;
-  if (t >= n) return;
-  const unsigned long long key = keys[t];
-  const uint32_t src = (uint32_t)key;
-  const float4 p = pts[src];
-  spts[t] = make_float4(p.x, p.y, p.z, __uint_as_float(src));
-  cells[t] = (uint32_t)(key >> 32);
-}
-
-__device__ __forceinline__ int mn_cell_coord(float x, float inv, float minb, int div) {
-  // k_batch_keys' expression (the query is a point of the indexed cloud: the clamp never binds, it only keeps the conversion defined)
-  const float c = floorf(x * inv) - minb;
-  return (int)fminf(fmaxf(c, -2.0f), (float)div + 1.0f);
-}
-
-__global__ void __launch_bounds__(MN_BLOCK) k_map_normals(const MnSeg S, const float4* __restrict__ spts, const uint32_t* __restrict__ cells, float r2, float scale,
+__global__ void __launch_bounds__(MN_BLOCK) k_map_normals(const CellSeg S, const float4* __restrict__ spts, const uint32_t* __restrict__ cells, float r2, float scale,
                                                           uint32_t min_nb, const double* __restrict__ views, uint32_t nv, float4* __restrict__ normals,
                                                           uint32_t* __restrict__ count, int32_t* __restrict__ view_idx, long long* __restrict__ s1_out,
                                                           long long* __restrict__ s2_out, uint32_t* __restrict__ flag) {
@@ -69,49 +47,16 @@ __global__ void __launch_bounds__(MN_BLOCK) k_map_normals(const MnSeg S, const f
   uint32_t k = 0, scanned = 0;
   long long sx = 0, sy = 0, sz = 0, sxx = 0, sxy = 0, sxz = 0, syy = 0, syz = 0, szz = 0;
   if (fin) {
-    const int cx = mn_cell_coord(q.x, S.inv, S.minb[0], S.div[0]), cy = mn_cell_coord(q.y, S.inv, S.minb[1], S.div[1]), cz = mn_cell_coord(q.z, S.inv, S.minb[2], S.div[2]);
-    const int x0 = max(cx - 1, 0), x1 = min(cx + 1, S.div[0] - 1);
-    if (x0 <= x1) {
-      uint32_t lo = 0;
-      const uint32_t end = S.nfin;
-      for (int dz = -1; dz <= 1; dz++) {
-        const int z = cz + dz;
-        if ((unsigned)z >= (unsigned)S.div[2]) continue;
-        for (int dy = -1; dy <= 1; dy++) {
-          const int y = cy + dy;
-          if ((unsigned)y >= (unsigned)S.div[1]) continue;
-          const uint32_t k0 = S.prefix | (uint32_t)(x0 + (y + z * S.div[1]) * S.div[0]), k1 = k0 + (uint32_t)(x1 - x0);
-          uint32_t a = lo, b = end;
-          while (a < b) { const uint32_t m = (a + b) >> 1; if (cells[m] < k0) a = m + 1; else b = m; }
-          for (;;) {
-            if (a >= end) break;
-            uint32_t c[4]; float4 p[4];
-#pragma unroll
-            for (int j = 0; j < 4; j++) { const uint32_t i = min(a + j, end - 1); c[j] = cells[i]; p[j] = spts[i]; }
-            bool more = true;
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-              more = more && a + j < end && c[j] <= k1;
-              if (more) {
-                scanned++;
-                const float dx = q.x - p[j].x, dy2 = q.y - p[j].y, dz2 = q.z - p[j].z;
-                const float d2 = dx * dx + dy2 * dy2 + dz2 * dz2;
-                if (d2 <= r2) {
-                  const int ix = (int)rintf((p[j].x - q.x) * scale), iy = (int)rintf((p[j].y - q.y) * scale), iz = (int)rintf((p[j].z - q.z) * scale);
-                  k++;
-                  sx += ix; sy += iy; sz += iz;
-                  sxx += (long long)ix * ix; sxy += (long long)ix * iy; sxz += (long long)ix * iz;
-                  syy += (long long)iy * iy; syz += (long long)iy * iz; szz += (long long)iz * iz;
-                }
-              }
-            }
-            if (!more) break;
-            a += 4;
-          }
-          lo = a;
-        }
+    cell_walk(S, spts, cells, q, [&](uint32_t, const float4& p, float d2) {
+      scanned++;
+      if (d2 <= r2) {
+        const int ix = (int)rintf((p.x - q.x) * scale), iy = (int)rintf((p.y - q.y) * scale), iz = (int)rintf((p.z - q.z) * scale);
+        k++;
+        sx += ix; sy += iy; sz += iz;
+        sxx += (long long)ix * ix; sxy += (long long)ix * iy; sxz += (long long)ix * iz;
+        syy += (long long)iy * iy; syz += (long long)iy * iz; szz += (long long)iz * iz;
       }
-    }
+    });
     if (scanned >= MN_MAX_BLOCK_POINTS) *flag = 1u;      // (every writer stores the same word)
   }
 
@@ -180,31 +125,9 @@ __global__ void __launch_bounds__(MN_BLOCK) k_map_normals(const MnSeg S, const f
   s2[0] = sxx; s2[1] = sxy; s2[2] = sxz; s2[3] = syy; s2[4] = syz; s2[5] = szz;
 }
 
-// The store's normals state (slot QN_KF_INT_EXT_NORMALS): two sets of per-point buffers, the live one holding the results of the latest successful call, for
-// the map of generation `gen` with its n points; a call writes the other set and swaps on success.
+// the store's normals state (slot QN_KF_INT_EXT_NORMALS)
 struct MnSet { DevBuf<float4> normals; DevBuf<uint32_t> count; DevBuf<int32_t> view; DevBuf<long long> s1, s2; };
-struct NormalState {
-  bool live = false; uint64_t gen = 0; uint32_t n = 0; int cur = 0;
-  MnSet set[2];
-};
-
-// the live results if they are those of the map slot as it stands, else nullptr
-const MnSet* live_set(qn_kf_store* s, uint32_t* n) {
-  NormalState* st = (NormalState*)qn_kf_int_ext(s, QN_KF_INT_EXT_NORMALS);
-  uint32_t map_n = 0; uint64_t gen = 0;
-  (void)qn_kf_int_map(s, &map_n, &gen);
-  if (!st || !st->live || st->gen != gen || st->n != map_n) return nullptr;
-  *n = st->n;
-  return &st->set[st->cur];
-}
-
-// the largest e with r 2^e <= 2^20, within the exponents of normal f32 powers of two (mapnormals.quant_exponent)
-int quant_exponent(double r) {
-  int x = 0;
-  const double m = std::frexp(r, &x);                    // r = m 2^x, 0.5 <= m < 1
-  const int e = m == 0.5 ? 21 - x : 20 - x;
-  return e < -126 ? -126 : e > 127 ? 127 : e;
-}
+typedef KfMapResults<MnSet> NormalState;
 
 }  // namespace
 
@@ -226,7 +149,7 @@ extern "C" int qn_kf_map_normals(qn_kf_store* s, const qn_normal_params* params,
   NormalState* st = nullptr;
   int rc = qn_kf_ext_state(s, QN_KF_INT_EXT_NORMALS, &st);
   if (rc != QN_OK) return rc;
-  MnSet& o = st->set[st->live ? 1 - st->cur : st->cur];
+  MnSet& o = st->spare();
   if (!o.normals.grow(s, n) || !o.count.grow(s, n) || !o.view.grow(s, n) || !o.s1.grow(s, 3 * (size_t)n) || !o.s2.grow(s, 6 * (size_t)n)) return QN_ERR_HIP;
   qn_kf_int_cell_grid g;
   const float4* pts = nullptr; const unsigned long long* keys = nullptr;
@@ -246,14 +169,12 @@ extern "C" int qn_kf_map_normals(qn_kf_store* s, const qn_normal_params* params,
     QN_KFCHK(s, hipMemcpyAsync(d_views, h, sizeof(double) * 3 * (size_t)n_view, hipMemcpyHostToDevice, stream));
   }
   QN_KFCHK(s, hipMemsetAsync(d_flag, 0, 16, stream));
-  MnSeg seg;
-  seg.n = g.n; seg.nfin = g.n_finite; seg.prefix = g.prefix; seg.inv = g.inv;
-  for (int a = 0; a < 3; a++) { seg.minb[a] = (float)g.minb[a]; seg.div[a] = g.div[a]; }
+  const CellSeg seg = cell_seg(g);
   const double rr = params->radius * params->radius;
   const float r2 = (float)rr;
-  const float scale = std::ldexp(1.0f, quant_exponent(params->radius));
+  const float scale = std::ldexp(1.0f, qn_quant_exponent(params->radius, 20));          // r 2^e <= 2^20: the overflow bound of the header comment
   const dim3 grid((n + MN_BLOCK - 1) / MN_BLOCK);
-  hipLaunchKernelGGL(k_mn_gather, grid, dim3(MN_BLOCK), 0, stream, n, keys, pts, d_spts, d_cells);
+  hipLaunchKernelGGL(k_cell_gather, grid, dim3(MN_BLOCK), 0, stream, seg, keys, pts, d_spts, d_cells);
   hipLaunchKernelGGL(k_map_normals, grid, dim3(MN_BLOCK), 0, stream, seg, (const float4*)d_spts, (const uint32_t*)d_cells, r2, scale, params->min_neighbors,
                      (const double*)d_views, n_view, o.normals.p, o.count.p, o.view.p, o.s1.p, o.s2.p, d_flag);
   QN_KFCHK(s, hipGetLastError());
@@ -263,16 +184,15 @@ extern "C" int qn_kf_map_normals(qn_kf_store* s, const qn_normal_params* params,
     qn_kf_int_set_error(s, "qn_kf_map_normals: 2^21 or more map points in one 3 x 3 x 3 block of cells");
     return QN_ERR_CAPACITY;
   }
-  if (st->live) st->cur = 1 - st->cur;
-  st->live = true; st->gen = gen; st->n = n;
+  st->commit(gen, n);
   *d_normals_out = (const float*)o.normals.p; *n_out = n;
   return QN_OK;
 }
 
 extern "C" int qn_kf_download_map_normals(qn_kf_store* s, float* normals4_out, uint32_t* count_out, int32_t* view_idx_out) {
   if (!s || (!normals4_out && !count_out && !view_idx_out)) return QN_ERR_INVALID_ARG;
-  uint32_t n = 0;
-  const MnSet* o = live_set(s, &n);
+  uint32_t n = 0; const float4* map = nullptr;
+  const MnSet* o = NormalState::lookup(s, QN_KF_INT_EXT_NORMALS, &map, &n);
   if (!o) return QN_ERR_NOT_READY;
   QN_KFCHK(s, hipSetDevice(qn_kf_int_device(s)));
   hipStream_t stream = qn_kf_int_stream(s);
@@ -285,8 +205,8 @@ extern "C" int qn_kf_download_map_normals(qn_kf_store* s, float* normals4_out, u
 
 extern "C" int qn_kf_map_moments(qn_kf_store* s, int64_t* s1_out, int64_t* s2_out) {
   if (!s || (!s1_out && !s2_out)) return QN_ERR_INVALID_ARG;
-  uint32_t n = 0;
-  const MnSet* o = live_set(s, &n);
+  uint32_t n = 0; const float4* map = nullptr;
+  const MnSet* o = NormalState::lookup(s, QN_KF_INT_EXT_NORMALS, &map, &n);
   if (!o) return QN_ERR_NOT_READY;
   QN_KFCHK(s, hipSetDevice(qn_kf_int_device(s)));
   hipStream_t stream = qn_kf_int_stream(s);

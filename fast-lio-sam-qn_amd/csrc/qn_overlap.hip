@@ -4,14 +4,13 @@
 // distances.  The numpy twin qn_amd/overlap.py is the specification; the results equal it bit for bit.
 //   index   qn_kf_int_cell_index (qn_cloud.hip): the front half of the store's voxel-grid pipeline with every cloud a segment - boxes, cell keys, stable
 //           radix passes - gives each cloud sorted by cell (edge >= r, x fastest), and k_overlap_gather lays the sorted points and their cells out flat;
-//   search  k_overlap_search, one query per lane, the pair and direction a grid dimension.  Queries are walked in the sorted order of their OWN cloud:
-//           neighbouring lanes are neighbouring points, and since both grids have cells of about r they read the same or adjacent runs of the other
-//           cloud (sorting the queries a second time by the other cloud's grid would buy the same locality for one more sort per cloud);
+//   search  k_overlap_search, one query per lane, the pair and direction a grid dimension, the walk of qn_cell_walk.cuh (the exactness argument at cell
+//           borders is there) over the other cloud.  Queries are walked in the sorted order of their OWN cloud: neighbouring lanes are neighbouring points,
+//           and since both grids have cells of about r they read the same or adjacent runs of the other cloud (sorting the queries a second time by the
+//           other cloud's grid would buy the same locality for one more sort per cloud).  A minimum that is <= float(r * r) is found among the 27 cells,
+//           and so is every point that ties with it; a minimum above it is reported as no partner;
 //   reduce  k_overlap_reduce, one block per pair and direction over the per-point results in original point order: a fixed order, no atomics, so a rerun
 //           gives the same bits and a pair's sums do not depend on which other pairs share the call.
-// Exactness at cell borders: the cell edge carries the margin derived in qn_cloud.hip (qn_kf_int_cell_index), so a partner within r has f32 cell coordinates
-// within one of the query's on every axis, whichever way either rounds; the query's coordinates come from the very expression k_batch_keys uses.  A minimum
-// that is <= float(r * r) is therefore found among the 27 cells, and so is every point that ties with it; a minimum above it is reported as no partner.
 // Host synchronisations per call: two, whatever the number of pairs (the boxes; the records).
 #include <hip/hip_runtime.h>
 #include <cmath>
@@ -21,82 +20,34 @@
 #include <algorithm>
 #include "../../include/qn_engine.h"
 #include "qn_kf_buf.h"
+#include "qn_cell_walk.cuh"
 
 namespace {
 
-#define QN_OV_BLOCK 256
-struct OvSeg { uint32_t p0, n, nfin, prefix; float inv; float minb[3]; int div[3]; };
+#define QN_OV_BLOCK 256                                  // k_overlap_reduce's block
 struct OvRes { double sum; uint32_t inliers, pad; };
 
-// the sorted order laid out flat: point t of a cloud's sorted range with its original index (bits in .w), and its (prefix | cell) word
-__global__ void __launch_bounds__(QN_OV_BLOCK) k_overlap_gather(const OvSeg* __restrict__ segs, const unsigned long long* __restrict__ keys, const float4* __restrict__ pts,
+// qn_cell_walk.cuh's gather, the pair and direction a grid dimension
+__global__ void __launch_bounds__(QN_CW_BLOCK) k_overlap_gather(const CellSeg* __restrict__ segs, const unsigned long long* __restrict__ keys, const float4* __restrict__ pts,
                                                                  float4* __restrict__ spts, uint32_t* __restrict__ cells) {
-  const OvSeg S = segs[blockIdx.y];
-  const uint32_t t = blockIdx.x * QN_OV_BLOCK + threadIdx.x;
-  if (t >= S.n) return;
-  const uint32_t g = S.p0 + t;
-  const unsigned long long key = keys[g];
-  const uint32_t src = (uint32_t)key;
-  const float4 p = pts[src];
-  spts[g] = make_float4(p.x, p.y, p.z, __uint_as_float(src - S.p0));
-  cells[g] = (uint32_t)(key >> 32);
+  cell_gather(segs[blockIdx.y], keys, pts, spts, cells);
 }
 
-__device__ __forceinline__ int cell_coord(float x, float inv, float minb, int div) {
-  // k_batch_keys' expression; clamped in float so that a query far outside the other cloud's box stays a valid int (it then has no cell to visit)
-  const float c = floorf(x * inv) - minb;
-  return (int)fminf(fmaxf(c, -2.0f), (float)div + 1.0f);
-}
-
-// One query per lane.  Nine x-runs (cells x-1 .. x+1 of one (y, z) are consecutive keys), each found by a binary search over the sorted cell words that starts
-// where the previous run ended (runs are visited in ascending key order), then read four candidates a trip.
-__global__ void __launch_bounds__(QN_OV_BLOCK) k_overlap_search(const OvSeg* __restrict__ segs, const float4* __restrict__ spts, const uint32_t* __restrict__ cells, float r2,
+// one query per lane: the nearest candidate of the walk, ties to the lowest original index
+__global__ void __launch_bounds__(QN_CW_BLOCK) k_overlap_search(const CellSeg* __restrict__ segs, const float4* __restrict__ spts, const uint32_t* __restrict__ cells, float r2,
                                                                  float* __restrict__ nn_d2, int32_t* __restrict__ nn_idx) {
-  const OvSeg Q = segs[blockIdx.y];
-  const uint32_t t = blockIdx.x * QN_OV_BLOCK + threadIdx.x;
+  const CellSeg Q = segs[blockIdx.y];
+  const uint32_t t = blockIdx.x * QN_CW_BLOCK + threadIdx.x;
   if (t >= Q.n) return;
-  const OvSeg T = segs[blockIdx.y ^ 1u];
+  const CellSeg T = segs[blockIdx.y ^ 1u];
   const float4 q = spts[Q.p0 + t];
   const uint32_t qi = __float_as_uint(q.w);
   float best = INFINITY; uint32_t bi = 0xffffffffu;
   if (t < Q.nfin && T.nfin) {
-    const int cx = cell_coord(q.x, T.inv, T.minb[0], T.div[0]), cy = cell_coord(q.y, T.inv, T.minb[1], T.div[1]), cz = cell_coord(q.z, T.inv, T.minb[2], T.div[2]);
-    const int x0 = max(cx - 1, 0), x1 = min(cx + 1, T.div[0] - 1);
-    if (x0 <= x1) {
-      uint32_t lo = T.p0;
-      const uint32_t end = T.p0 + T.nfin;
-      for (int dz = -1; dz <= 1; dz++) {
-        const int z = cz + dz;
-        if ((unsigned)z >= (unsigned)T.div[2]) continue;
-        for (int dy = -1; dy <= 1; dy++) {
-          const int y = cy + dy;
-          if ((unsigned)y >= (unsigned)T.div[1]) continue;
-          const uint32_t k0 = T.prefix | (uint32_t)(x0 + (y + z * T.div[1]) * T.div[0]), k1 = k0 + (uint32_t)(x1 - x0);
-          uint32_t a = lo, b = end;
-          while (a < b) { const uint32_t m = (a + b) >> 1; if (cells[m] < k0) a = m + 1; else b = m; }
-          for (;;) {
-            if (a >= end) break;
-            uint32_t c[4]; float4 p[4];
-#pragma unroll
-            for (int j = 0; j < 4; j++) { const uint32_t i = min(a + j, end - 1); c[j] = cells[i]; p[j] = spts[i]; }
-            bool more = true;
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-              more = more && a + j < end && c[j] <= k1;
-              if (more) {
-                const float dx = q.x - p[j].x, dy2 = q.y - p[j].y, dz2 = q.z - p[j].z;
-                const float d2 = dx * dx + dy2 * dy2 + dz2 * dz2;
-                const uint32_t id = __float_as_uint(p[j].w);
-                if (d2 < best || (d2 == best && id < bi)) { best = d2; bi = id; }
-              }
-            }
-            if (!more) break;
-            a += 4;
-          }
-          lo = a;
-        }
-      }
-    }
+    cell_walk(T, spts, cells, q, [&](uint32_t, const float4& p, float d2) {
+      const uint32_t id = __float_as_uint(p.w);
+      if (d2 < best || (d2 == best && id < bi)) { best = d2; bi = id; }
+    });
   }
   if (!(best <= r2)) { best = INFINITY; bi = 0xffffffffu; }
   nn_d2[Q.p0 + qi] = best;
@@ -104,10 +55,10 @@ __global__ void __launch_bounds__(QN_OV_BLOCK) k_overlap_search(const OvSeg* __r
 }
 
 // one block per pair and direction: thread i sums points i, i + 256, ... in f64, then a butterfly inside each wave and the waves in order
-__global__ void __launch_bounds__(QN_OV_BLOCK) k_overlap_reduce(const OvSeg* __restrict__ segs, const float* __restrict__ nn_d2, OvRes* __restrict__ res) {
+__global__ void __launch_bounds__(QN_OV_BLOCK) k_overlap_reduce(const CellSeg* __restrict__ segs, const float* __restrict__ nn_d2, OvRes* __restrict__ res) {
   __shared__ double wsum[QN_OV_BLOCK / 64];
   __shared__ uint32_t wcnt[QN_OV_BLOCK / 64];
-  const OvSeg S = segs[blockIdx.x];
+  const CellSeg S = segs[blockIdx.x];
   double acc = 0.0; uint32_t cnt = 0;
   for (uint32_t i = threadIdx.x; i < S.n; i += QN_OV_BLOCK) {
     const float v = nn_d2[S.p0 + i];
@@ -160,27 +111,22 @@ int overlap_run(qn_kf_store* s, std::vector<const float4*>& cl, std::vector<uint
   QN_KFCHK(s, hipSetDevice(qn_kf_int_device(s)));
   hipStream_t stream = qn_kf_int_stream(s);
   if (!st->d2.grow(s, total) || !st->idx.grow(s, total)) return QN_ERR_HIP;
-  const size_t seg_bytes = qn_up16(sizeof(OvSeg) * S), res_bytes = sizeof(OvRes) * S;
-  OvSeg* d_seg = (OvSeg*)qn_kf_int_scratch(s, 0, seg_bytes);
+  const size_t seg_bytes = qn_up16(sizeof(CellSeg) * S), res_bytes = sizeof(OvRes) * S;
+  CellSeg* d_seg = (CellSeg*)qn_kf_int_scratch(s, 0, seg_bytes);
   float4* d_spts = (float4*)qn_kf_int_scratch(s, 1, sizeof(float4) * total);
   uint32_t* d_cells = (uint32_t*)qn_kf_int_scratch(s, 2, sizeof(uint32_t) * total);
   OvRes* d_res = (OvRes*)qn_kf_int_scratch(s, 3, res_bytes);
   char* h = (char*)qn_kf_int_pinned(s, seg_bytes + res_bytes);
   if (!d_seg || !d_spts || !d_cells || !d_res || !h) return qn_kf_fail(s, "qn_kf_overlap: scratch allocation failed");
-  OvSeg* h_seg = (OvSeg*)h; OvRes* h_res = (OvRes*)(h + seg_bytes);
-  for (uint32_t k = 0; k < S; k++) {
-    const qn_kf_int_cell_grid& g = grid[k];
-    OvSeg& o = h_seg[k];
-    o.p0 = g.p0; o.n = g.n; o.nfin = g.n_finite; o.prefix = g.prefix; o.inv = g.inv;
-    for (int a = 0; a < 3; a++) { o.minb[a] = (float)g.minb[a]; o.div[a] = g.div[a]; }
-  }
+  CellSeg* h_seg = (CellSeg*)h; OvRes* h_res = (OvRes*)(h + seg_bytes);
+  for (uint32_t k = 0; k < S; k++) h_seg[k] = cell_seg(grid[k]);
   const double rr = radius * radius;
   const float r2 = (float)rr;
-  const dim3 grid2((nmax + QN_OV_BLOCK - 1) / QN_OV_BLOCK, S);
-  QN_KFCHK(s, hipMemcpyAsync(d_seg, h_seg, sizeof(OvSeg) * S, hipMemcpyHostToDevice, stream));
-  hipLaunchKernelGGL(k_overlap_gather, grid2, dim3(QN_OV_BLOCK), 0, stream, (const OvSeg*)d_seg, keys, pts, d_spts, d_cells);
-  hipLaunchKernelGGL(k_overlap_search, grid2, dim3(QN_OV_BLOCK), 0, stream, (const OvSeg*)d_seg, (const float4*)d_spts, (const uint32_t*)d_cells, r2, st->d2.p, st->idx.p);
-  hipLaunchKernelGGL(k_overlap_reduce, dim3(S), dim3(QN_OV_BLOCK), 0, stream, (const OvSeg*)d_seg, (const float*)st->d2.p, d_res);
+  const dim3 grid2((nmax + QN_CW_BLOCK - 1) / QN_CW_BLOCK, S);
+  QN_KFCHK(s, hipMemcpyAsync(d_seg, h_seg, sizeof(CellSeg) * S, hipMemcpyHostToDevice, stream));
+  hipLaunchKernelGGL(k_overlap_gather, grid2, dim3(QN_CW_BLOCK), 0, stream, (const CellSeg*)d_seg, keys, pts, d_spts, d_cells);
+  hipLaunchKernelGGL(k_overlap_search, grid2, dim3(QN_CW_BLOCK), 0, stream, (const CellSeg*)d_seg, (const float4*)d_spts, (const uint32_t*)d_cells, r2, st->d2.p, st->idx.p);
+  hipLaunchKernelGGL(k_overlap_reduce, dim3(S), dim3(QN_OV_BLOCK), 0, stream, (const CellSeg*)d_seg, (const float*)st->d2.p, d_res);
   QN_KFCHK(s, hipGetLastError());
   QN_KFCHK(s, hipMemcpyAsync(h_res, d_res, res_bytes, hipMemcpyDeviceToHost, stream));
   QN_KFCHK(s, hipStreamSynchronize(stream));             // sync 2 of 2

@@ -11,8 +11,8 @@ from qn_amd import engine, mapground as mg
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMBOLS = ["qn_ground_default_params", "qn_kf_map_ground", "qn_kf_map_ground_points", "qn_kf_map_ground_grid", "qn_kf_map_keep_classes"]
-KERNELS = ("k_mg_extent", "k_mg_extent_sum", "k_mg_bin", "k_mg_seed", "k_mg_relax", "k_mg_classify", "k_mg_occ_count", "k_mg_sum", "k_mg_keep_flag", "k_mo_scan",
-           "k_mo_compact")
+KERNELS = ("k_mg_extent", "k_mg_extent_sum", "k_mg_bin", "k_mg_seed", "k_mg_relax", "k_mg_classify", "k_mg_occ_count", "k_slot_fold<unsigned int, 1>",
+           "k_slot_fold<unsigned int, 2>", "k_slot_fold<unsigned int, 5>", "k_mg_keep_flag", "k_mo_scan", "k_mo_compact")
 
 
 def test_header_declares_and_library_exports_the_api():
@@ -93,9 +93,10 @@ def test_the_kernels_have_no_scratch_and_no_spills():
 
 
 def test_no_floating_point_in_the_kernels_behind_the_quantisation():
-    """only the extent and the bin kernels (before and at the quantisation) may name a floating-point type"""
-    src = open(os.path.join(ROOT, "fast-lio-sam-qn_amd", "csrc", "qn_mapground.hip")).read()
-    for k in ("k_mg_seed", "k_mg_relax", "k_mg_classify", "k_mg_occ_count", "k_mg_sum", "k_mg_keep_flag"):
+    """only the extent and the bin kernels (before and at the quantisation) may name a floating-point type; the count tail and the fold of the slots that the
+    others share live in qn_map_compact.cuh"""
+    src = "".join(open(os.path.join(ROOT, "fast-lio-sam-qn_amd", "csrc", f)).read() for f in ("qn_map_compact.cuh", "qn_mapground.hip"))
+    for k in ("k_mg_seed", "k_mg_relax", "k_mg_classify", "k_mg_occ_count", "k_slot_fold", "block_count", "k_mg_keep_flag"):
         i = src.index(" " + k + "(")
         body = src[i:src.index("\n}\n", i)]
         assert not re.search(r"\b(float|double|float4)\b", body), k
