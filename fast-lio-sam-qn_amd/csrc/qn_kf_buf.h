@@ -109,7 +109,13 @@ template <typename Set> struct KfMapResults {
     const KfMapResults* st = (const KfMapResults*)qn_kf_int_ext(s, slot);
     uint64_t map_gen = 0;
     *map = qn_kf_int_map(s, n, &map_gen);
-    return st && st->live && *map && st->gen == map_gen && st->n == *n ? &st->set[st->cur] : nullptr;
+    return st ? st->current(s, map, n) : nullptr;
+  }
+  // the same for a state that is reached another way than as a slot of its own
+  const Set* current(qn_kf_store* s, const float4** map, uint32_t* map_n) const {
+    uint64_t map_gen = 0;
+    *map = qn_kf_int_map(s, map_n, &map_gen);
+    return live && *map && gen == map_gen && n == *map_n ? &set[cur] : nullptr;
   }
 };
 

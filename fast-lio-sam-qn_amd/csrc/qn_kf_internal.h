@@ -41,7 +41,7 @@ bool qn_kf_int_has_intensity(const qn_kf_store* s, int32_t id);                 
 #define QN_KF_INT_EXT_RANGE 5                                                    // qn_freespace.hip: range images and the classes of the latest check
 #define QN_KF_INT_EXT_STATIC 6                                                   // qn_staticmap.hip: the list, votes and kept records of the latest static classify
 #define QN_KF_INT_EXT_NORMALS 7                                                  // qn_mapnormals.hip: the normals and moments of the map slot
-#define QN_KF_INT_EXT_OUTLIERS 8                                                 // qn_mapoutliers.hip: the classification of the map slot's points
+#define QN_KF_INT_EXT_OUTLIERS 8                                                 // qn_mapoutliers.hip: the classification of the map slot's points, and the clusters of qn_mapclusters.inc
 #define QN_KF_INT_EXT_GROUND 9                                                   // qn_mapground.hip: the ground classes and the occupancy grid of the map slot
 typedef void (*qn_kf_int_release_fn)(void*);
 void* qn_kf_int_ext(const qn_kf_store* s, int which);
@@ -99,3 +99,6 @@ int qn_kf_int_map_shrink(qn_kf_store* s, const float4* d_kept, uint32_t n_kept);
 // slot, the same statuses and notes: for pts / n / has_i of resident keyframes it IS qn_kf_build_map of their ids.  Arguments are not checked.
 int qn_kf_int_build_map_from(qn_kf_store* s, const float4* const* pts, const uint32_t* n, const uint8_t* has_i, const double* poses, uint32_t count, double leaf,
                              const float** d_xyzi_out, uint32_t* n_out);
+// qn_mapground.hip: the resident class bytes (one per map point, device memory) of the live qn_kf_map_ground classification if it is that of the map slot as
+// it stands, else nullptr (qn_mapclusters.inc reads them for its class mask)
+const uint8_t* qn_kf_int_ground_classes(qn_kf_store* s);

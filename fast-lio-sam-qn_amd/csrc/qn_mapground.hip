@@ -244,6 +244,12 @@ typedef KfMapResults<MgSet> GroundState;
 
 }  // namespace
 
+const uint8_t* qn_kf_int_ground_classes(qn_kf_store* s) {
+  const float4* map = nullptr; uint32_t n = 0;
+  const MgSet* o = GroundState::lookup(s, QN_KF_INT_EXT_GROUND, &map, &n);
+  return o ? o->cls.p : nullptr;
+}
+
 extern "C" void qn_ground_default_params(qn_ground_params* p) {
   if (!p) return;
   p->cell = 0.5; p->max_slope = 0.3; p->ground_tol = 0.2; p->clearance = 2.0; p->min_points = 1; p->reserved = 0;      // interface choices, not measurements

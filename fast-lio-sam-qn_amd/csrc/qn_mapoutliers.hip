@@ -18,9 +18,12 @@
 //   compact   qn_kf_map_remove_outliers only: the shared end of the map's filters (qn_map_compact.cuh, with the count tail, the fold and the scan).
 // Host synchronisations of a classify: the index's, one for the statistics (the threshold is host arithmetic), one at the end.  Results are committed only
 // on success (KfMapResults, qn_kf_buf.h), so a refused call leaves the previous classification as it was.
+// The map's other point filter, the clusters (qn_mapclusters.inc, included at the end), is part of this translation unit: it shares the index, the walk, the
+// scan and the compaction instantiated here, and its results hang on this unit's slot of the store (MoUnit below).
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cmath>
+#include <cstddef>
 #include <cstring>
 #include <new>
 #include "../../include/qn_engine.h"
@@ -111,6 +114,14 @@ __global__ void __launch_bounds__(MO_BLOCK) k_mo_flag(uint32_t n, const float4* 
 // the store's outlier state (slot QN_KF_INT_EXT_OUTLIERS): of the classified map's points `kept` stay
 struct MoSet { DevBuf<uint32_t> count, mean_q, off; DevBuf<uint8_t> removed; uint32_t kept = 0; };
 typedef KfMapResults<MoSet> OutlierState;
+// what the slot holds: the outlier results in front (OutlierState::lookup reads the slot as them), and the cluster results of qn_mapclusters.inc, made on
+// that unit's first use and released with the store
+struct MoUnit {
+  OutlierState outliers;
+  void* clusters = nullptr; void (*release)(void*) = nullptr;
+  ~MoUnit() { if (clusters) release(clusters); }
+};
+static_assert(offsetof(MoUnit, outliers) == 0, "OutlierState::lookup reads the slot as the outlier results");
 
 }  // namespace
 
@@ -133,9 +144,10 @@ extern "C" int qn_kf_map_outliers(qn_kf_store* s, const qn_outlier_params* param
     return QN_ERR_CAPACITY;
   }
   QN_KFCHK(s, hipSetDevice(qn_kf_int_device(s)));
-  OutlierState* st = nullptr;
-  int rc = qn_kf_ext_state(s, QN_KF_INT_EXT_OUTLIERS, &st);
+  MoUnit* unit = nullptr;
+  int rc = qn_kf_ext_state(s, QN_KF_INT_EXT_OUTLIERS, &unit);
   if (rc != QN_OK) return rc;
+  OutlierState* st = &unit->outliers;
   const uint32_t nb = (n + MO_BLOCK - 1) / MO_BLOCK;
   MoSet& o = st->spare();
   if (!o.count.grow(s, n) || !o.mean_q.grow(s, n) || !o.removed.grow(s, n) || !o.off.grow(s, (size_t)nb + 1)) return QN_ERR_HIP;
@@ -215,3 +227,5 @@ extern "C" int qn_kf_map_remove_outliers(qn_kf_store* s, const float** d_xyzi_ou
   if (!d_kept) return qn_kf_fail(s, "qn_kf_map_remove_outliers: scratch allocation failed");
   return qn_kf_map_compact_shrink(s, map, n, o->removed.p, o->off.p, d_kept, o->kept, d_xyzi_out, n_out);
 }
+
+#include "qn_mapclusters.inc"

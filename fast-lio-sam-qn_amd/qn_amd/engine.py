@@ -777,6 +777,35 @@ QN_GROUND_NONE, QN_GROUND_GROUND, QN_GROUND_OBSTACLE, QN_GROUND_OVERHEAD, QN_GRO
 QN_GROUND_MAX_CELLS = 1 << 26
 
 
+class ClusterParams(C.Structure):
+    """qn_cluster_params (24 bytes): the joining distance, the smallest and the largest component that is a cluster, and the ground classes that take part
+    (0: every finite point).  The defaults are interface choices, not measurements."""
+    _fields_ = [("tolerance", C.c_double), ("min_size", C.c_uint32), ("max_size", C.c_uint32), ("class_mask", C.c_uint32), ("reserved", C.c_uint32)]
+
+    def __init__(self, tolerance=0.5, min_size=10, max_size=0xffffffff, class_mask=0):
+        super().__init__(tolerance, min_size, max_size, class_mask, 0)
+
+    def twin(self):
+        """-> the mapclusters.ClusterParams with these values"""
+        from . import mapclusters
+        return mapclusters.ClusterParams(float(self.tolerance), int(self.min_size), int(self.max_size), int(self.class_mask))
+
+
+class ClusterStats(C.Structure):
+    """qn_cluster_stats (56 bytes)"""
+    _fields_ = ([(f, C.c_uint32) for f in ("n", "n_finite", "members", "components", "clusters", "too_small", "too_large", "clustered_points", "rejected_points",
+                                           "largest")] + [("quant_exp", C.c_int32), ("reserved", C.c_uint32), ("edges", C.c_uint64)])
+
+
+class ClusterInfo(C.Structure):
+    """qn_cluster_info (56 bytes): a cluster's root, size, box and quantised coordinate sums"""
+    _fields_ = [("root", C.c_uint32), ("size", C.c_uint32), ("lo", C.c_float * 3), ("hi", C.c_float * 3), ("sum_q", C.c_int64 * 3)]
+
+
+QN_CLUSTER_REJECTED, QN_CLUSTER_NONE = -1, -2
+assert (C.sizeof(ClusterParams), C.sizeof(ClusterStats), C.sizeof(ClusterInfo)) == (24, 56, 56)             # the records of include/qn_engine.h
+
+
 class KeyframeStore:
     """Device-resident keyframe clouds + LoopClosure::setSrcAndDstCloud on the GPU (loop_closure.cpp:58-108)."""
 
@@ -1361,6 +1390,41 @@ class KeyframeStore:
         outlier classification and any map normals are stale afterwards."""
         ptr = C.c_void_p(); n = C.c_uint32()
         self._check(self._l.qn_kf_map_keep_classes(self.h, C.c_uint32(int(mask) & 0xffffffff), C.byref(ptr), C.byref(n)))
+        self._map_n = n.value
+        return ptr.value, n.value
+
+    # ---- the map slot's points clustered into objects (qn_kf_map_clusters / _cluster_points / _cluster_list / qn_kf_map_drop_rejected_clusters; numpy twin:
+    # qn_amd/mapclusters.py)
+    def map_clusters(self, params=None):
+        """qn_kf_map_clusters on the map of the latest build or filter, then its downloads.  params: a ClusterParams (or a mapclusters.ClusterParams); None:
+        the defaults.  A class_mask != 0 needs the map_ground of the same map.  -> (stats, label (n,) int32, root (n,) uint32, size (n,) uint32, clusters),
+        equal to mapclusters.classify of the downloaded map; stats: a dict of the fields of qn_cluster_stats; clusters: a dict of root (C,) uint32, size (C,)
+        uint32, lo and hi (C, 3) float32, sum_q (C, 3) int64 and centroid (C, 3) float64 = sum_q / size * 2^-quant_exp.  The map slot is not touched;
+        map_drop_rejected_clusters applies the result."""
+        from . import mapclusters
+        p = ClusterParams() if params is None else params
+        if not isinstance(p, ClusterParams):
+            p = ClusterParams(float(p.tolerance), int(p.min_size), int(p.max_size), int(p.class_mask))
+        st = ClusterStats()
+        self._check(self._l.qn_kf_map_clusters(self.h, C.byref(p), C.byref(st)))
+        n = int(st.n)
+        label = np.zeros(max(n, 1), np.int32); root = np.zeros(max(n, 1), np.uint32); size = np.zeros(max(n, 1), np.uint32)
+        self._check(self._l.qn_kf_map_cluster_points(self.h, _p(label), _p(root), _p(size)))
+        cnt = C.c_uint32()
+        info = np.zeros(max(int(st.clusters), 1), mapclusters.INFO_DTYPE)
+        self._check(self._l.qn_kf_map_cluster_list(self.h, _p(info), C.c_uint32(len(info)), C.byref(cnt)))
+        info = info[:cnt.value]
+        stats = {f: getattr(st, f) for f, _ in ClusterStats._fields_ if f != "reserved"}
+        clusters = {f: info[f].copy() for f in ("root", "size", "lo", "hi", "sum_q")}
+        clusters["centroid"] = info["sum_q"].astype(np.float64) / info["size"].astype(np.float64)[:, None] * math.ldexp(1.0, -int(st.quant_exp))
+        return stats, label[:n], root[:n], size[:n], clusters
+
+    def map_drop_rejected_clusters(self):
+        """qn_kf_map_drop_rejected_clusters: the map slot without the members of the components the latest map_clusters rejected, in order -> (ptr, n): the
+        device address of the n float4 records x y z intensity.  Records that were not members stay.  Every result computed from the old slot is stale
+        afterwards."""
+        ptr = C.c_void_p(); n = C.c_uint32()
+        self._check(self._l.qn_kf_map_drop_rejected_clusters(self.h, C.byref(ptr), C.byref(n)))
         self._map_n = n.value
         return ptr.value, n.value
 

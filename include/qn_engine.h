@@ -721,6 +721,57 @@ int  qn_kf_map_ground(qn_kf_store*, const qn_ground_params* params, qn_ground_st
 int  qn_kf_map_ground_points(qn_kf_store*, uint8_t* class_out, int32_t* height_q_out);
 int  qn_kf_map_ground_grid(qn_kf_store*, qn_ground_grid* info_out, int32_t* ground_q_out, uint8_t* occupancy_out);
 int  qn_kf_map_keep_classes(qn_kf_store*, uint32_t class_mask, const float** d_xyzi_out /* float4: x y z intensity */, uint32_t* n_out);
+/* ---- the map's points clustered into objects (csrc/qn_mapclusters.inc, part of csrc/qn_mapoutliers.hip; numpy twin and specification: qn_amd/mapclusters.py)
+ * After qn_kf_map_ground every point is GROUND, OBSTACLE or OVERHEAD, but the obstacles are an unstructured set.  These calls run PCL's
+ * EuclideanClusterExtraction over the store's map slot on the GPU: connected components of the radius graph, each with a size, a box and a centroid, and the
+ * clumps too small (or too large) to be anything marked for removal.
+ * qn_cluster_params (24 bytes): tolerance (finite, > 0, default 0.5), min_size (>= 1, default 10), max_size (>= min_size, default 0xffffffff), class_mask
+ *   (bits 0 .. 4 only, default 0), reserved (0).  The defaults are interface choices, not measurements.
+ * Members: with class_mask == 0 every finite point of the map slot (x, y and z all finite); with class_mask != 0 a finite point whose ground class c has its
+ *   bit 1 << c set in the mask, the class being the live qn_kf_map_ground classification of the same slot generation.
+ *   (1 << QN_GROUND_OBSTACLE) | (1 << QN_GROUND_OVERHEAD) is the intended use.
+ * Edges: two members at DIFFERENT map indices are joined when their f32 squared distance (the overlap measure's arithmetic: f32 differences, dx dx + dy dy +
+ *   dz dz left to right, no fused multiply-add; symmetric) is <= float(tolerance * tolerance), inclusive.  A duplicate at another index is joined at distance
+ *   0.  edges = the number of unordered joined pairs (u64).
+ * Components: the connected components of that graph.  root[p] = the smallest map index of p's component, size[p] = its member count; a point that is not a
+ *   member has root 0xffffffff and size 0.
+ * Clusters: a component with min_size <= size <= max_size, numbered 0 .. C - 1 in ascending order of root.  label[p] (int32) = the number,
+ *   QN_CLUSTER_REJECTED -1 for the members of the other components, QN_CLUSTER_NONE -2 for the points that are not members.
+ * qn_cluster_info (56 bytes) per cluster: root, size, lo[3], hi[3] - the f32 minimum and maximum of the members' coordinates in the total order of the
+ *   sign-magnitude-to-ordered-integer image of the f32, so -0 < +0 - and sum_q[3], the int64 sums of xq = (int64) rint((double)x * 2^e), half to even, e the
+ *   largest integer with tolerance * 2^e <= 2^10 (within [-126, 127]; the product is exact).  The centroid is sum_q / size * 2^-e in f64, host arithmetic.
+ *   QN_ERR_CAPACITY when a member has |xq| >= 2^31; below that the sums over fewer than 2^32 points are exact.
+ * qn_cluster_stats (56 bytes): n, n_finite, members; components, clusters, too_small, too_large (components); clustered_points, rejected_points; largest
+ *   (the largest component's size); quant_exp (e), reserved (0); edges.
+ * Everything is an integer or an f32 selected by an order-free rule, equal to the twin's bit for bit whatever order neighbours are met in or unions happen; a
+ *   rerun gives the same bytes.
+ * qn_kf_map_clusters: classifies the map slot as it stands; the slot itself is not touched.  The results stay resident for the slot's generation (any later
+ *   map build or filter, successful or not, ends it).  At most four host synchronisations.  QN_ERR_NOT_READY without a map, or with class_mask != 0 and no
+ *   live ground classification of this generation.  QN_ERR_INVALID_ARG: a null pointer, a parameter outside the ranges above.  QN_ERR_CAPACITY as above, and
+ *   whatever the cell index refuses (a map whose extent overflows f32).  A refused call leaves the previous results intact.
+ * qn_kf_map_cluster_points: label_out, root_out, size_out at the map's own indices; any may be NULL, not all.  QN_ERR_NOT_READY before a successful
+ *   qn_kf_map_clusters and once the slot's generation has moved on.
+ * qn_kf_map_cluster_list: *count_out = C; out NULL: the count only; capacity < C: QN_ERR_CAPACITY and nothing written (*count_out included); else the C
+ *   records in cluster order.  QN_ERR_NOT_READY as above.
+ * qn_kf_map_drop_rejected_clusters: removes the members of rejected components; points that are not members - non-finite records, excluded ground - stay.
+ *   The kept records, in order and all 16 bytes each, become the map slot (*d_xyzi_out, *n_out; NULL and 0 when nothing is left).  The generation advances,
+ *   so normals, outlier, ground and cluster results go stale.  QN_ERR_NOT_READY without a live classification, and the slot is then unchanged.          */
+#define QN_CLUSTER_REJECTED (-1)
+#define QN_CLUSTER_NONE (-2)
+typedef struct qn_cluster_params { double tolerance; uint32_t min_size, max_size, class_mask, reserved; } qn_cluster_params;    /* 24 bytes */
+typedef struct qn_cluster_info { uint32_t root, size; float lo[3], hi[3]; int64_t sum_q[3]; } qn_cluster_info;                 /* 56 bytes */
+typedef struct qn_cluster_stats {
+  uint32_t n, n_finite, members;
+  uint32_t components, clusters, too_small, too_large;
+  uint32_t clustered_points, rejected_points, largest;
+  int32_t quant_exp; uint32_t reserved;
+  uint64_t edges;
+} qn_cluster_stats;                                                                                                          /* 56 bytes */
+void qn_cluster_default_params(qn_cluster_params* p);
+int  qn_kf_map_clusters(qn_kf_store*, const qn_cluster_params* params, qn_cluster_stats* stats_out);
+int  qn_kf_map_cluster_points(qn_kf_store*, int32_t* label_out, uint32_t* root_out, uint32_t* size_out);
+int  qn_kf_map_cluster_list(qn_kf_store*, qn_cluster_info* out, uint32_t capacity, uint32_t* count_out);
+int  qn_kf_map_drop_rejected_clusters(qn_kf_store*, const float** d_xyzi_out /* float4: x y z intensity */, uint32_t* n_out);
 /* LoopClosure::fetchClosestKeyframeIdx (loop_closure.cpp:34-56) generalised to the max_k nearest admissible keyframes,
  * ascending distance; out[0] is the reference's single choice.  Host code (O(#keyframes)).                        */
 int  qn_loop_candidates(const double* pos_xyz, const double* stamps, uint32_t n, uint32_t query, double radius, double tdiff,

@@ -239,6 +239,28 @@ def write_pcd_xyzi_normal(path, pts, normals, curvature):
             f.write("%.9g %.9g %.9g %.9g %.9g %.9g %.9g %.9g\n" % (p[0], p[1], p[2], p[3], n[0], n[1], n[2], c))
 
 
+def write_pcd_labelled(path, pts, label, normals=None, curvature=None):
+    """PCD v0.7 ASCII, FIELDS x y z intensity [normal_x normal_y normal_z curvature] label: the integer cluster number of every point (-1: in a rejected
+    clump, -2: not clustered at all)"""
+    nf = 4 if normals is None else 8
+    names = "x y z intensity" + ("" if normals is None else " normal_x normal_y normal_z curvature") + " label"
+    with open(path, "w") as f:
+        f.write("# .PCD v0.7 - Point Cloud Data file format\nVERSION 0.7\nFIELDS %s\nSIZE %s\nTYPE %s I\nCOUNT %s\nWIDTH %d\nHEIGHT 1\nVIEWPOINT 0 0 0 1 0 0 0\n"
+                "POINTS %d\nDATA ascii\n" % (names, " ".join(["4"] * (nf + 1)), " ".join(["F"] * nf), " ".join(["1"] * (nf + 1)), len(pts), len(pts)))
+        for i, p in enumerate(pts):
+            v = [p[0], p[1], p[2], p[3]] + ([] if normals is None else [normals[i][0], normals[i][1], normals[i][2], curvature[i]])
+            f.write(" ".join("%.9g" % x for x in v) + " %d\n" % label[i])
+
+
+def write_clusters_csv(path, clusters):
+    """one row per cluster of KeyframeStore.map_clusters: id, size, the box and the centroid (f32 / f64 values printed so that they read back exactly)"""
+    with open(path, "w") as f:
+        f.write("id,size,min_x,min_y,min_z,max_x,max_y,max_z,centroid_x,centroid_y,centroid_z\n")
+        for j in range(len(clusters["size"])):
+            f.write("%d,%d,%s,%s,%s\n" % (j, clusters["size"][j], ",".join("%.9g" % v for v in clusters["lo"][j]), ",".join("%.9g" % v for v in clusters["hi"][j]),
+                                          ",".join("%.17g" % v for v in clusters["centroid"][j])))
+
+
 def ate(poses, gt):
     return float(np.sqrt(np.mean([np.sum((a[:3, 3] - b[:3, 3]) ** 2) for a, b in zip(poses, gt)])))
 
@@ -299,7 +321,7 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
         submap_matching=False, min_overlap=None, overlap_radius=None, max_see_through=None, range_params=None, static_map=False, static_radius=15.0,
         static_max_k=8, moving_boxes=0, save_map_normals=False, normal_radius=0.6, normal_min_neighbors=5, map_outliers=False,
         outlier_radius=1.0, outlier_k=8, outlier_std=2.0, occupancy_grid=False, grid_cell=0.5, max_slope=0.3, ground_tol=0.2, clearance=2.0,
-        drop_ground=False):
+        drop_ground=False, map_clusters=False, cluster_tol=0.5, cluster_min=10, cluster_max=0xffffffff, drop_small_clusters=False):
     """sensor = "uniform": keyframe clouds sampled uniformly by area inside a disc (make_stream); "spinning": ray-cast spinning-LiDAR
     scans from the ground-truth poses of the same figure-8 (make_lidar_stream).  detector = "radius": the candidate is the closest older
     keyframe within `radius` of the corrected position (LC:34-56); "scancontext": the older keyframe nearest by Scan Context distance, kept
@@ -352,6 +374,13 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
     map_ground_grid; on the oracle backend, which has no map of its own, the map is the oracle's voxel grid over every keyframe (map.pcd, intensity 0) and the
     grid the numpy twin's.  out["grid"]: width, height, occupied, free, unknown, n_ground.  drop_ground (with occupancy_grid): map.pcd is written without its
     GROUND class (KeyframeStore.map_keep_classes), the grid still comes from the whole map.
+    map_clusters (the GPU backend, with save_dir and save_map_leaf; default False): the points of the map are clustered into objects on the device
+    (KeyframeStore.map_clusters: joined within cluster_tol, a clump of cluster_min .. cluster_max points is a cluster) - with occupancy_grid what stands on the
+    ground (the OBSTACLE and OVERHEAD classes, after the ground call), otherwise every finite point.  map.pcd gains an integer field label (the cluster's
+    number, -1 in a rejected clump, -2 not clustered) and clusters.csv lists id, size, box and centroid (with static_map: map_static.pcd and
+    clusters_static.csv too).  drop_small_clusters: the rejected clumps leave the map (KeyframeStore.map_drop_rejected_clusters).  The filters run in the order
+    outliers, ground, clusters, drop_ground, normals; with drop_small_clusters and drop_ground both, the ground that leaves is that of the map without the
+    clumps, segmented again.  out["clusters"] (and out["static_clusters"]): clusters, components, too_small, too_large, clustered_points, rejected_points.
     moving_boxes = N (sensor="spinning" only; default 0: every run is what it was): N extra boxes in the scene that stand somewhere else in every keyframe
     (moving_box_prims), so every keyframe is cast by a call of its own."""
     if detector not in ("radius", "scancontext"):
@@ -408,6 +437,15 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
     if occupancy_grid:
         from qn_amd import mapground
         mapground.units((grid_cell, max_slope, ground_tol, clearance, 1))                         # (raises ValueError on a parameter outside its range)
+    if drop_small_clusters and not map_clusters:
+        raise ValueError("drop_small_clusters needs map_clusters (the clumps come from its components)")
+    if map_clusters and backend != "gpu":
+        raise ValueError("map_clusters needs backend='gpu' (the oracle backend writes no map of its own)")
+    if map_clusters and (save_dir is None or save_map_leaf is None):
+        raise ValueError("map_clusters needs save_dir and save_map_leaf (the labels are a field of map.pcd)")
+    if map_clusters:
+        from qn_amd import mapclusters
+        mapclusters.check_params(mapclusters.ClusterParams(cluster_tol, cluster_min, cluster_max, 0))      # (raises ValueError on a parameter outside its range)
     overlaps = []; see_through = []; fs_images = {}
 
     def apply_freespace(rs, pairs):
@@ -658,14 +696,20 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
     if save_dir:
         write_kitti_tum(save_dir, corrected, stamps)
         if save_map_leaf is not None and backend == "gpu":
-            def write_map(name, n):
-                """the map slot as a .pcd, with the normals of its points when asked -> the points that have one"""
+            def write_map(name, n, label=None):
+                """the map slot as a .pcd, with the normals of its points when asked and their cluster labels when given -> the points that have a normal"""
                 if not save_map_normals:
-                    write_pcd_xyzi(os.path.join(save_dir, name), store.download_map(n))
+                    if label is None:
+                        write_pcd_xyzi(os.path.join(save_dir, name), store.download_map(n))
+                    else:
+                        write_pcd_labelled(os.path.join(save_dir, name), store.download_map(n), label)
                     return None
                 from qn_amd import engine
                 nr = store.map_normals(engine.NormalParams(normal_radius, int(normal_min_neighbors)), np.array([T[:3, 3] for T in corrected]))
-                write_pcd_xyzi_normal(os.path.join(save_dir, name), store.download_map(n), nr["normals"], nr["curvature"])
+                if label is None:
+                    write_pcd_xyzi_normal(os.path.join(save_dir, name), store.download_map(n), nr["normals"], nr["curvature"])
+                else:
+                    write_pcd_labelled(os.path.join(save_dir, name), store.download_map(n), label, nr["normals"], nr["curvature"])
                 return int(np.isfinite(nr["curvature"]).sum())
             def filter_map(n):
                 """the outliers of the map slot removed in place -> (the points left, the points removed)"""
@@ -675,20 +719,38 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
                 st = store.map_outliers(engine.OutlierParams(outlier_radius, outlier_std, int(outlier_k)))[0]
                 return store.map_remove_outliers()[1], int(st["removed"])
             def ground_stage(stem, n):
-                """the occupancy grid of the map slot written as stem.pgm / stem.yaml; with drop_ground the GROUND class leaves the slot -> the points left"""
-                if not occupancy_grid:
-                    return n
+                """the occupancy grid of the map slot written as stem.pgm / stem.yaml, then the clusters of what stands on the ground (of every finite point
+                without a grid) as stem's clusters .csv; then the rejected clumps and the GROUND class leave the slot when asked -> (the points left, their
+                cluster labels or None)"""
                 from qn_amd import engine, mapground
-                st = store.map_ground(engine.GroundParams(grid_cell, max_slope, ground_tol, clearance, 1))[0]
-                info, _, occ = store.map_ground_grid()
-                write_grid(save_dir, stem, mapground.GridInfo(*(info[f] for f in mapground.GridInfo._fields)), occ)
-                out["grid" if stem == "map" else "static_grid"] = {k: int(st[k]) for k in ("width", "height", "occupied", "free", "unknown", "n_ground")}
-                return store.map_keep_classes(0b11101)[1] if drop_ground else n
+                cls = label = None
+                if occupancy_grid:
+                    st, cls, _ = store.map_ground(engine.GroundParams(grid_cell, max_slope, ground_tol, clearance, 1))
+                    info, _, occ = store.map_ground_grid()
+                    write_grid(save_dir, stem, mapground.GridInfo(*(info[f] for f in mapground.GridInfo._fields)), occ)
+                    out["grid" if stem == "map" else "static_grid"] = {k: int(st[k]) for k in ("width", "height", "occupied", "free", "unknown", "n_ground")}
+                if map_clusters:
+                    mask = ((1 << mapground.OBSTACLE) | (1 << mapground.OVERHEAD)) if occupancy_grid else 0
+                    st, label, _, _, cl = store.map_clusters(engine.ClusterParams(cluster_tol, int(cluster_min), int(cluster_max), mask))
+                    write_clusters_csv(os.path.join(save_dir, "clusters.csv" if stem == "map" else "clusters_static.csv"), cl)
+                    out["clusters" if stem == "map" else "static_clusters"] = {k: int(st[k]) for k in ("clusters", "components", "too_small", "too_large",
+                                                                                                     "clustered_points", "rejected_points")}
+                    if drop_small_clusters:
+                        n = store.map_drop_rejected_clusters()[1]
+                        label = label[label != engine.QN_CLUSTER_REJECTED]
+                        if drop_ground:                                                      # the slot has changed: the ground of what is left
+                            cls = store.map_ground(engine.GroundParams(grid_cell, max_slope, ground_tol, clearance, 1))[1]
+                if drop_ground:
+                    n = store.map_keep_classes(0b11101)[1]
+                    label = None if label is None else label[cls != mapground.GROUND]
+                return n, label
             n, removed = filter_map(store.build_map(ids, corrected, save_map_leaf))
-            n = ground_stage("map", n)
-            valid = write_map("map.pcd", n)
+            n, label = ground_stage("map", n)
+            valid = write_map("map.pcd", n, label)
             if map_outliers:
                 out["map_points"] = n; out["map_outliers_removed"] = removed
+            if map_clusters:
+                out["map_points"] = n
             if save_map_normals:
                 out["map_points"] = n; out["map_normals_valid"] = valid
             if static_map:
@@ -697,8 +759,8 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
                     store.range_describe(ids)
                 st = store.static_classify(ids, corrected, radius=static_radius, max_k=static_max_k)
                 n, removed = filter_map(store.build_map_static(save_map_leaf))
-                n = ground_stage("map_static", n)
-                write_map("map_static.pcd", n)
+                n, label = ground_stage("map_static", n)
+                write_map("map_static.pcd", n, label)
                 if map_outliers:
                     out["static_outliers_removed"] = removed
                 out["static_removed"] = int(st["removed"].sum()); out["static_map_points"] = n
@@ -757,6 +819,13 @@ if __name__ == "__main__":
     ap.add_argument("--ground-tol", type=float, default=0.2, help="with --occupancy-grid: a point within this of the ground envelope is ground [m]")
     ap.add_argument("--clearance", type=float, default=2.0, help="with --occupancy-grid: a point higher than this above the ground does not occupy its cell [m]")
     ap.add_argument("--drop-ground", action="store_true", help="with --occupancy-grid: map.pcd is written without the ground points")
+    ap.add_argument("--map-clusters", action="store_true",
+                    help="with --save-dir and --save-map-leaf: the map's points are clustered into objects on the GPU (with --occupancy-grid: what stands on the ground); "
+                         "map.pcd gains an integer label field and clusters.csv lists id, size, box and centroid")
+    ap.add_argument("--cluster-tol", type=float, default=0.5, help="with --map-clusters: points this close are joined [m]")
+    ap.add_argument("--cluster-min", type=int, default=10, help="with --map-clusters: the fewest points of a cluster")
+    ap.add_argument("--cluster-max", type=int, default=0xffffffff, help="with --map-clusters: the most points of a cluster")
+    ap.add_argument("--drop-small-clusters", action="store_true", help="with --map-clusters: the clumps that are no cluster leave the map")
     ap.add_argument("--moving-boxes", type=int, default=0, help="with --sensor spinning: this many boxes that stand somewhere else in every keyframe")
     ap.add_argument("--backend", choices=["gpu", "oracle"], default="gpu", help="the engine on the GPU, or the CPU oracle")
     a = ap.parse_args()
@@ -768,9 +837,14 @@ if __name__ == "__main__":
         ap.error("--occupancy-grid needs --save-dir and --save-map-leaf")
     if a.drop_ground and not a.occupancy_grid:
         ap.error("--drop-ground needs --occupancy-grid")
+    if a.map_clusters and (a.save_dir is None or a.save_map_leaf is None):
+        ap.error("--map-clusters needs --save-dir and --save-map-leaf")
+    if a.drop_small_clusters and not a.map_clusters:
+        ap.error("--drop-small-clusters needs --map-clusters")
     run(a.keyframes, a.seed, a.quatro, save_dir=a.save_dir, save_map_leaf=a.save_map_leaf, sensor=a.sensor, detector=a.detector, yaw_bias=a.yaw_bias,
         verify=a.verify, sc_top_k=a.sc_top_k, backend=a.backend, loop_every=a.loop_every, catch_up=a.catch_up, submap_matching=a.submap_matching,
         min_overlap=a.min_overlap, overlap_radius=a.overlap_radius, max_see_through=a.max_see_through, static_map=a.static_map, moving_boxes=a.moving_boxes,
         save_map_normals=a.save_map_normals, normal_radius=a.normal_radius, map_outliers=a.map_outliers, outlier_radius=a.outlier_radius, outlier_k=a.outlier_k,
         outlier_std=a.outlier_std, occupancy_grid=a.occupancy_grid, grid_cell=a.grid_cell, max_slope=a.max_slope, ground_tol=a.ground_tol,
-        clearance=a.clearance, drop_ground=a.drop_ground)
+        clearance=a.clearance, drop_ground=a.drop_ground, map_clusters=a.map_clusters, cluster_tol=a.cluster_tol, cluster_min=a.cluster_min,
+        cluster_max=a.cluster_max, drop_small_clusters=a.drop_small_clusters)
