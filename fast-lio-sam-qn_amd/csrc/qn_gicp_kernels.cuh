@@ -842,29 +842,34 @@ struct NnLaneK {
       kz[d] = (((uint32_t)(z >> 2) * tile_zy) << 7) | ((uint32_t)(z & 3) << 5);
       ky[d] = (((uint32_t)(y >> 2) * (uint32_t)tgt.ntx) << 7) | ((uint32_t)(y & 3) << 3);
     }
-#pragma unroll 1
-    for (int part = 0; part < 2; part++) {
-      if (!__any(scan && part < ntr)) break;
-      const int tx = tx0 + part, xa = max(x0, tx << 3), xb = min(x1, (tx << 3) + 7);
-      const uint32_t kx = ((uint32_t)tx << 7) | (uint32_t)(xa & 7), xlen = (uint32_t)(xb - xa) + 1u;
-      const bool pv = scan && part < ntr;
-      uint32_t s[QN_LANE_ROWS], e[QN_LANE_ROWS];
+    // A row that crosses a tile boundary is two runs of pts[] (part 0: the cells x0 .. end of tile tx0, part 1: tile tx0 + 1 from its first cell to x1).  Both parts'
+    // bounds are fetched up front (36 loads in flight together) and every row is walked ONCE, as one virtual run of len0 + len1 candidates: a row visit's trip count
+    // is the wave's longest combined run - not its longest first part plus its longest second part, with nine more visits for the lanes that cross.
+    const bool two = scan && ntr == 2;
+    const int xb0 = min(x1, (tx0 << 3) + 7);
+    const uint32_t kx0 = ((uint32_t)tx0 << 7) | (uint32_t)(x0 & 7), xlen0 = (uint32_t)(xb0 - x0) + 1u;
+    const uint32_t kx1 = (uint32_t)(tx0 + 1) << 7, xlen1 = (uint32_t)(x1 - ((tx0 + 1) << 3)) + 1u;      // (read only where `two`)
+    uint32_t s0[QN_LANE_ROWS], len0[QN_LANE_ROWS], off1[QN_LANE_ROWS], tot[QN_LANE_ROWS];
 #pragma unroll
-      for (int rr = 0; rr < QN_LANE_ROWS; rr++) {
-        const int dz = rr / 3, dy = rr % 3;                              // (compile-time: the rows of a 3 x 3 box, those beyond the query's own box empty)
-        s[rr] = 0; e[rr] = 0;
-        if (pv && dy < nyr && dz < nzr) { const uint32_t k0 = kz[dz] + ky[dy] + kx; s[rr] = cs[k0]; e[rr] = cs[k0 + xlen]; }
-      }
+    for (int rr = 0; rr < QN_LANE_ROWS; rr++) {
+      const int dz = rr / 3, dy = rr % 3;                                // (compile-time: the rows of a 3 x 3 box, those beyond the query's own box empty)
+      const bool rv = scan && dy < nyr && dz < nzr;
+      uint32_t a0 = 0, b0 = 0, a1 = 0, b1 = 0;
+      const uint32_t kr = kz[dz] + ky[dy];
+      if (rv) { a0 = cs[kr + kx0]; b0 = cs[kr + kx0 + xlen0]; }
+      if (rv && two) { a1 = cs[kr + kx1]; b1 = cs[kr + kx1 + xlen1]; }
+      s0[rr] = a0; len0[rr] = b0 - a0; off1[rr] = a1 - len0[rr]; tot[rr] = len0[rr] + (b1 - a1);
+    }
 #pragma unroll
-      for (int rr = 0; rr < QN_LANE_ROWS; rr++) {
-        for (uint32_t u = s[rr]; u < e[rr]; u += 4) {                    // four candidates per trip, all four loads in flight (a row is 3 cells: one trip, rarely two)
-          const uint32_t last = e[rr] - 1u;
-          const float4 c0 = pts[u], c1 = pts[min(u + 1u, last)], c2 = pts[min(u + 2u, last)], c3 = pts[min(u + 3u, last)];
-          sink.consider<true>(true, sqdist(qx, qy, qz, c0.x, c0.y, c0.z), __float_as_uint(c0.w));
-          sink.consider<true>(u + 1u <= last, sqdist(qx, qy, qz, c1.x, c1.y, c1.z), __float_as_uint(c1.w));
-          sink.consider<true>(u + 2u <= last, sqdist(qx, qy, qz, c2.x, c2.y, c2.z), __float_as_uint(c2.w));
-          sink.consider<true>(u + 3u <= last, sqdist(qx, qy, qz, c3.x, c3.y, c3.z), __float_as_uint(c3.w));
-        }
+    for (int rr = 0; rr < QN_LANE_ROWS; rr++) {
+      const uint32_t l0 = len0[rr], sa = s0[rr], sb = off1[rr], last = tot[rr] - 1u;
+      for (uint32_t v = 0; v < tot[rr]; v += 4) {                        // four candidates per trip, all four loads in flight (a row is 3 cells: one trip, rarely two)
+        const uint32_t v1 = min(v + 1u, last), v2 = min(v + 2u, last), v3 = min(v + 3u, last);      // virtual position v -> pts[v + (v < len0 ? s0 : s1 - len0)]
+        const float4 c0 = pts[v + (v < l0 ? sa : sb)], c1 = pts[v1 + (v1 < l0 ? sa : sb)], c2 = pts[v2 + (v2 < l0 ? sa : sb)], c3 = pts[v3 + (v3 < l0 ? sa : sb)];
+        sink.consider<true>(true, sqdist(qx, qy, qz, c0.x, c0.y, c0.z), __float_as_uint(c0.w));
+        sink.consider<true>(v + 1u <= last, sqdist(qx, qy, qz, c1.x, c1.y, c1.z), __float_as_uint(c1.w));
+        sink.consider<true>(v + 2u <= last, sqdist(qx, qy, qz, c2.x, c2.y, c2.z), __float_as_uint(c2.w));
+        sink.consider<true>(v + 3u <= last, sqdist(qx, qy, qz, c3.x, c3.y, c3.z), __float_as_uint(c3.w));
       }
     }
     // certification: nearest face of the scanned box that has unseen cells behind it (wave_search's rule, on the query's own box)
