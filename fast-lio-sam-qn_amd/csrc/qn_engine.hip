@@ -232,6 +232,7 @@ extern "C" void qn_ctx_destroy(qn_ctx* c) {
 static int clouds_valid(qn_ctx* c);
 extern "C" void* qn_ctx_stream(qn_ctx* c) { return c ? (void*)c->stream : nullptr; }
 int qn_ctx_int_device(const qn_ctx* c) { return c->device; }      // (for other translation units: qn_verify.hip)
+int qn_ctx_int_max_points(const qn_ctx* c) { return (int)c->max_points; }
 extern "C" int qn_ctx_synchronize(qn_ctx* c) {
   if (!c) return QN_ERR_INVALID_ARG;
   HIPCHK(c, hipStreamSynchronize(c->stream));

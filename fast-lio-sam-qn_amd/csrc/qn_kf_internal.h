@@ -64,9 +64,12 @@ int qn_kf_int_voxel_windows(qn_kf_store* s, const int32_t* ids, const double* po
 #define QN_KF_VERIFY_C2F 1
 #define QN_KF_VERIFY_SUBMAP 2
 #define QN_KF_VERIFY_SUBMAP_C2F 3
+#define QN_KF_VERIFY_MAP 4                                                       // qn_kf_map_localize (qn_maplocalize.inc): cand = -1, src = the scan cloud, dst = the crop
+#define QN_KF_VERIFY_MAP_C2F 5
 #define QN_KF_VERIFY_FROM_BATCH 0
 #define QN_KF_VERIFY_FROM_SCANS 1
 #define QN_KF_VERIFY_FROM_SUBMAPS 2
+#define QN_KF_VERIFY_FROM_MAP 3                                                  // copies the verify unit owns itself: only the next crop or localise call ends them
 struct qn_kf_int_verify_pair { const float4* src; uint32_t ns; const float4* dst; uint32_t nt; int32_t query, cand; int stage; double Tq[16]; float Tg[16]; };
 int  qn_kf_int_verify_record(qn_kf_store* s, int kind, const qn_kf_int_verify_pair* p, uint32_t n);
 void qn_kf_int_verify_stale(qn_kf_store* s, int from, const int32_t* ids, uint32_t count);

@@ -1081,3 +1081,9 @@ extern "C" int qn_coarse_to_fine_align_batch(qn_ctx* const* ctxs, uint32_t n_ctx
                                              qn_gicp_result* results, double* T_total, double* T_quatro, int* valid, int* status) {
   return c2f_batch(ctxs, n_ctx, pairs, n_pairs, score_thr, results, T_total, T_quatro, valid, status, nullptr);
 }
+// the same on one context, with each pair's stage (for another translation unit: qn_maplocalize.inc)
+int qn_ctx_int_c2f_batch_stage(qn_ctx* ctx, const qn_pair_desc* pairs, uint32_t n_pairs, double score_thr, qn_gicp_result* results, double* T_total, double* T_quatro,
+                               int* valid, int* status, int* stage) {
+  qn_ctx* const one[1] = {ctx};
+  return c2f_batch(one, 1, pairs, n_pairs, score_thr, results, T_total, T_quatro, valid, status, nullptr, stage);
+}

@@ -117,6 +117,9 @@ extern "C" int qn_kf_verify_loop_candidates(qn_kf_store* s, qn_ctx* ctx, int32_t
   return QN_OK;
 }
 
+// ------------------------------------------------------------------ scans against the map itself: the crops and qn_kf_map_localize[_c2f]
+#include "qn_maplocalize.inc"
+
 // ------------------------------------------------------------------ many queries in one call
 namespace {
 
@@ -124,11 +127,22 @@ namespace {
 // COARSE and FINAL of pair j at fixed places (2 * (sum of ns before j), then + ns), so every pointer handed out stays valid until the record is replaced
 struct VerifyState {
   bool live = false; int kind = QN_KF_VERIFY_GICP;
-  bool c2f() const { return kind == QN_KF_VERIFY_C2F || kind == QN_KF_VERIFY_SUBMAP_C2F; }
-  int from() const { return kind >= QN_KF_VERIFY_SUBMAP ? QN_KF_VERIFY_FROM_SUBMAPS : kind; }
+  bool c2f() const { return kind == QN_KF_VERIFY_C2F || kind == QN_KF_VERIFY_SUBMAP_C2F || kind == QN_KF_VERIFY_MAP_C2F; }
+  int from() const { return kind >= QN_KF_VERIFY_MAP ? QN_KF_VERIFY_FROM_MAP : kind >= QN_KF_VERIFY_SUBMAP ? QN_KF_VERIFY_FROM_SUBMAPS : kind; }
   std::vector<qn_kf_int_verify_pair> p; std::vector<size_t> off;
   DevBuf<float4> arena;
+  MlState ml;                                                            // qn_maplocalize.inc: the crops and scan clouds a QN_KF_VERIFY_MAP[_C2F] record names
 };
+
+MlState* ml_state(qn_kf_store* s, int* rc) {
+  VerifyState* st = nullptr;
+  *rc = qn_kf_ext_state(s, QN_KF_INT_EXT_VERIFY, &st);
+  return *rc == QN_OK ? &st->ml : nullptr;
+}
+void ml_verify_drop(qn_kf_store* s) {
+  VerifyState* st = (VerifyState*)qn_kf_int_ext(s, QN_KF_INT_EXT_VERIFY);
+  if (st && st->live && st->from() == QN_KF_VERIFY_FROM_MAP) st->live = false;
+}
 
 // the two clouds qn_kf_verify_cloud computes: COARSE = transformPcd(src, T_quatro) (k_transform_cloud_f64's f64 order, rounded to f32); FINAL = that (or src on
 // the GICP path) through the GICP T as align() fills aligned_ (k_transform_cloud: xform_query<1> with the f32 entries).  One point per thread.

@@ -806,6 +806,29 @@ QN_CLUSTER_REJECTED, QN_CLUSTER_NONE = -1, -2
 assert (C.sizeof(ClusterParams), C.sizeof(ClusterStats), C.sizeof(ClusterInfo)) == (24, 56, 56)             # the records of include/qn_engine.h
 
 
+class LocalizeParams(C.Structure):
+    """qn_localize_params (32 bytes): the crop radius around the guess, the scan's voxel leaf, the score threshold and the crop shape (QN_LOCALIZE_SPHERE /
+    QN_LOCALIZE_CYLINDER); the defaults are config.yaml's radius, voxel and score."""
+    _fields_ = [("radius", C.c_double), ("leaf", C.c_double), ("score_thr", C.c_double), ("shape", C.c_uint32), ("reserved", C.c_uint32)]
+
+    def __init__(self, radius=35.0, leaf=0.3, score_thr=1.5, shape=0):
+        super().__init__(radius, leaf, score_thr, shape, 0)
+
+    def twin(self):
+        """-> the maplocalize.LocalizeParams with these values"""
+        from . import maplocalize
+        return maplocalize.LocalizeParams(float(self.radius), float(self.leaf), float(self.score_thr), int(self.shape))
+
+
+class LocalizeStats(C.Structure):
+    """qn_localize_stats (40 bytes)"""
+    _fields_ = ([(f, C.c_uint32) for f in ("n_map", "n_pairs", "n_scans", "n_crops", "passes", "reserved")] + [("crop_points", C.c_uint64), ("generation", C.c_uint64)])
+
+
+QN_LOCALIZE_SPHERE, QN_LOCALIZE_CYLINDER = 0, 1
+assert (C.sizeof(LocalizeParams), C.sizeof(LocalizeStats)) == (32, 40)                                      # the records of include/qn_engine.h
+
+
 class KeyframeStore:
     """Device-resident keyframe clouds + LoopClosure::setSrcAndDstCloud on the GPU (loop_closure.cpp:58-108)."""
 
@@ -1427,6 +1450,68 @@ class KeyframeStore:
         self._check(self._l.qn_kf_map_drop_rejected_clusters(self.h, C.byref(ptr), C.byref(n)))
         self._map_n = n.value
         return ptr.value, n.value
+
+    # ---- scans localised in the map slot (qn_kf_map_crop / _crop_get / qn_kf_map_localize[_c2f]; numpy twin of the crop: qn_amd/maplocalize.py)
+    def map_crop(self, centres, radius, shape=0):
+        """qn_kf_map_crop: the neighbourhoods of `centres` ((Q, 3), rounded to f32) cut out of the map slot, then their downloads -> one dict per centre:
+        n, ptr (device address of the n float4 records x y z intensity, None when empty; valid until the next map_crop / map_localize), xyzi (n, 4) float32 and
+        idx (n,) uint32 (ascending map indices), equal to maplocalize.crop of the downloaded map."""
+        c = np.ascontiguousarray(np.asarray(centres, dtype=np.float64).reshape(-1, 3))
+        counts = np.zeros(max(len(c), 1), np.uint32)
+        self._check(self._l.qn_kf_map_crop(self.h, _p(c) if len(c) else None, C.c_uint32(len(c)), C.c_double(radius), C.c_uint32(shape), _p(counts)))
+        return [self.map_crop_get(k) for k in range(len(c))]
+
+    def map_crop_get(self, crop):
+        """qn_kf_map_crop_get and the download of crop `crop` of the latest map_crop / map_localize -> dict(n, ptr, xyzi, idx)"""
+        ptr = C.c_void_p(); n = C.c_uint32()
+        self._check(self._l.qn_kf_map_crop_get(self.h, C.c_uint32(crop), C.byref(ptr), C.byref(n), None))
+        idx = np.zeros(max(n.value, 1), np.uint32); xyzi = np.zeros((n.value, 4), np.float32)
+        if n.value:
+            self._check(self._l.qn_kf_map_crop_get(self.h, C.c_uint32(crop), C.byref(ptr), C.byref(n), _p(idx)))
+            l = self._l; l.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]; l.hipMemcpy.restype = C.c_int
+            if l.hipMemcpy(xyzi.ctypes.data, ptr, 16 * n.value, 2) != 0:
+                raise EngineError(QN_ERR_HIP, "map_crop_get: read-back failed")
+        return dict(n=int(n.value), ptr=ptr.value, xyzi=xyzi, idx=idx[:n.value].copy())
+
+    def _localize_args(self, query, guesses, params):
+        q = np.ascontiguousarray(np.atleast_1d(query), dtype=np.int32)
+        g = np.ascontiguousarray(np.asarray(guesses, dtype=np.float64).reshape(-1, 16))
+        if len(q) != len(g):
+            raise ValueError("map_localize: %d queries but %d guesses" % (len(q), len(g)))
+        p = LocalizeParams() if params is None else params
+        if not isinstance(p, LocalizeParams):
+            p = LocalizeParams(float(p.radius), float(p.leaf), float(p.score_thr), int(p.shape))
+        return q, g, p, len(q)
+
+    def map_localize(self, ctx, query, guesses, params=None):
+        """qn_kf_map_localize: pair j = keyframe query[j] (alone in its sensor frame, voxel grid at params.leaf) registered against the crop of the map slot
+        around the translation of guesses[j] (4x4, map <- sensor, rounded to f32), seeded with that guess = gicp_align_batch(ctx, [(scan cloud, crop)],
+        guesses=[g]) record for record.  -> (one dict per pair as verify_loop_pairs', T = the pose in the map; stats: a dict of the fields of qn_localize_stats).
+        verify_cloud / verify_overlap serve the pairs afterwards; map_crop_get(k) the k-th distinct crop."""
+        q, g, p, n = self._localize_args(query, guesses, params)
+        results = (GicpResult * max(n, 1))(); valid = np.zeros(max(n, 1), np.int32); status = np.zeros(max(n, 1), np.int32); st = LocalizeStats()
+        rc = self._l.qn_kf_map_localize(self.h, ctx.h, C.byref(p), _p(q) if n else None, _p(g) if n else None, C.c_uint32(n), results, _p(valid), _p(status), C.byref(st))
+        if rc != QN_OK:
+            raise EngineError(rc, self._l.qn_status_str(rc).decode() + ": " + self._l.qn_kf_last_error(self.h).decode() + " / " + lib().qn_last_error(ctx.h).decode())
+        stats = {f: int(getattr(st, f)) for f, _ in LocalizeStats._fields_ if f != "reserved"}
+        return [dict(valid=bool(valid[j]), converged=bool(results[j].converged), score=results[j].fitness, iterations=results[j].iterations,
+                     T=np.array(results[j].T, dtype=np.float32).reshape(4, 4).astype(np.float64), status=int(status[j]), record=results[j]) for j in range(n)], stats
+
+    def map_localize_c2f(self, ctx, query, guesses, params=None):
+        """qn_kf_map_localize_c2f: the same clouds coarse to fine (Quatro -> transformPcd -> Nano-GICP); only the guess's translation is used, as the crop
+        centre = coarse_to_fine_align_batch([ctx], [(scan cloud, crop)]) record for record.  -> (one dict per pair as verify_loop_pairs_c2f's, T = the pose in
+        the map; stats)."""
+        q, g, p, n = self._localize_args(query, guesses, params)
+        results = (GicpResult * max(n, 1))(); valid = np.zeros(max(n, 1), np.int32); status = np.zeros(max(n, 1), np.int32); st = LocalizeStats()
+        Tt = np.zeros((max(n, 1), 4, 4)); Tq = np.zeros((max(n, 1), 4, 4))
+        rc = self._l.qn_kf_map_localize_c2f(self.h, ctx.h, C.byref(p), _p(q) if n else None, _p(g) if n else None, C.c_uint32(n), results, _p(Tt), _p(Tq),
+                                            _p(valid), _p(status), C.byref(st))
+        if rc != QN_OK:
+            raise EngineError(rc, self._l.qn_status_str(rc).decode() + ": " + self._l.qn_kf_last_error(self.h).decode() + " / " + lib().qn_last_error(ctx.h).decode())
+        stats = {f: int(getattr(st, f)) for f, _ in LocalizeStats._fields_ if f != "reserved"}
+        return [dict(valid=bool(valid[j]), converged=bool(results[j].converged), score=results[j].fitness, iterations=results[j].iterations, T=Tt[j].copy(),
+                     T_quatro=Tq[j].copy(), T_gicp=np.array(results[j].T, dtype=np.float32).reshape(4, 4).astype(np.float64), status=int(status[j]),
+                     record=results[j]) for j in range(n)], stats
 
     # ---- Scan Context loop candidates (qn_kf_sc_*; numpy twin: qn_amd/scancontext.py)
     def sc_set_params(self, params=None, **kw):

@@ -405,7 +405,8 @@ int  qn_kf_verify_loop_pairs_c2f(qn_kf_store*, qn_ctx*, const int32_t* query, co
  * COARSE, no registration for FINAL).  QN_ERR_INVALID_ARG: a null pointer, pair >= that call's n_pairs, or a bad `which`.  The pointers stay valid until
  * the next qn_kf_verify_loop_pairs[_c2f] call, the next qn_kf_assemble_batch on the store (any caller: the GICP path's clouds live in its batch slot), a
  * qn_kf_quatro_describe of a keyframe the latest coarse-to-fine call involved, or the store's destruction.  The latest call may also be
- * qn_kf_verify_loop_pairs_submap[_c2f] (below): SRC / DST are then the two resident local submaps, valid until one of them is described again or released.  */
+ * qn_kf_verify_loop_pairs_submap[_c2f] (below): SRC / DST are then the two resident local submaps, valid until one of them is described again or released;
+ * or qn_kf_map_localize[_c2f] (further below): SRC is the scan cloud, DST the map crop, valid until the next crop or localise call.  */
 #define QN_VERIFY_SRC 0
 #define QN_VERIFY_DST 1
 #define QN_VERIFY_COARSE 2
@@ -772,6 +773,53 @@ int  qn_kf_map_clusters(qn_kf_store*, const qn_cluster_params* params, qn_cluste
 int  qn_kf_map_cluster_points(qn_kf_store*, int32_t* label_out, uint32_t* root_out, uint32_t* size_out);
 int  qn_kf_map_cluster_list(qn_kf_store*, qn_cluster_info* out, uint32_t capacity, uint32_t* count_out);
 int  qn_kf_map_drop_rejected_clusters(qn_kf_store*, const float** d_xyzi_out /* float4: x y z intensity */, uint32_t* n_out);
+/* ---- scans localised in the corrected map: crop and register (csrc/qn_maplocalize.inc, part of csrc/qn_verify.hip; numpy twin and specification of the crop:
+ * qn_amd/maplocalize.py).  The reference saves its map "for FAST-LIO-Localization-QN" (config.yaml, save_map_bag): Quatro + Nano-GICP of a scan against the
+ * neighbourhood of a pose guess in the saved map.  Here the map slot never leaves the device: the neighbourhoods are cut out by one streaming pass and handed to
+ * the batch registration as device pairs.
+ * Membership: a map record p (the float4 of the map slot) is a member of the crop (c, R, shape) iff x, y and z are finite and d2 <= r2, inclusive, with c three
+ *   f32 values (the caller's f64 centre rounded to f32), r2 = float(R * R), the product taken in f64, dx = p.x - c.x (dy, dz likewise) in f32 and
+ *   d2 = (dx dx + dy dy) + dz dz summed left to right with no fused multiply-add.  QN_LOCALIZE_CYLINDER leaves dz dz out (an upright cylinder without ends; z must
+ *   still be finite); QN_LOCALIZE_SPHERE is the default.  Non-finite records are never members.
+ * A crop holds its members' full 16-byte records in ascending map index, and a uint32 map index goes with every record.  Crops, indices and counts equal the twin's
+ *   bit for bit and a rerun gives the same bytes: brute force over the slot, 64 centres per pass (more centres: further passes), a record loaded once per kernel per
+ *   pass, no atomics.  Limits: 32767 centres per call and fewer than 2^32 crop records in all, else QN_ERR_CAPACITY.
+ * qn_kf_map_crop: counts_out[c] = the members of crop c.  Two host synchronisations.  QN_ERR_INVALID_ARG before anything runs: a null pointer, n_crops == 0, a
+ *   non-finite centre, a radius that is not finite or <= 0, a bad shape.  QN_ERR_NOT_READY without a map.  The crops are COPIES in a buffer of their own (not the
+ *   voxel pipeline's scratch): a later map build or filter does not touch them.
+ * qn_kf_map_crop_get: crop `crop` of the latest crop (or localise) call as a device pointer (float4: x y z intensity; NULL when empty) and count; idx_out (host,
+ *   may be NULL) receives the n map indices (one host synchronisation).  The pointer is valid until the next crop or localise call or the store's destruction.
+ *   QN_ERR_NOT_READY before such a call, QN_ERR_INVALID_ARG for a null pointer or crop >= that call's crops.
+ * qn_localize_params (32 bytes): radius (35.0), leaf (0.3), score_thr (1.5), shape (sphere), reserved (0) - config.yaml's radius, voxel and score.
+ * qn_kf_map_localize: pair j registers keyframe query[j] - alone in its sensor frame, voxel grid at `leaf`, each distinct query once - against the crop around the
+ *   translation of g_j, where g_j is guess16[16 j ..] (row-major 4x4, map <- sensor) with every entry rounded to f32: one rounding, the same numbers for the crop
+ *   centre and for the seed.  Pairs whose centres have the same f32 bits share one crop (heading hypotheses at one position).  The pairs are grouped by query
+ *   (stable) into ONE qn_gicp_align_batch_guess and the records scattered back to caller order: record j equals qn_gicp_align_batch_guess on (scan cloud, crop,
+ *   g_j) bit for bit, and its T / T64 is the scan's pose in the map.
+ * qn_kf_map_localize_c2f: the same clouds coarse to fine; the centre comes from the guess, its rotation is ignored.  Record j, T_total (the pose) and T_quatro
+ *   (may be NULL) equal qn_coarse_to_fine_align_batch({ctx}) on the same two clouds bit for bit.
+ * status[j]: QN_ERR_EMPTY_CLOUD for an empty scan or an empty crop, QN_ERR_CAPACITY for a scan or crop above the context's max_points; the other pairs still run.
+ *   Whole call: QN_ERR_NOT_READY without a map; QN_ERR_INVALID_ARG before anything runs, with store, record and context unchanged - a null pointer, n_pairs == 0,
+ *   a bad id, a non-finite guess or a last row other than 0 0 0 1, bad params, store and context on different devices.
+ *   Four host synchronisations (two for the crops, two for the scans' voxel grids) besides the batch registration's own.
+ * qn_localize_stats (40 bytes): n_map, n_pairs, n_scans (distinct queries), n_crops (distinct centres), passes, reserved; crop_points (all crops), generation
+ *   (the map slot's generation the crops were cut from).
+ * Verify record: each localise call leaves the record qn_kf_verify_cloud and qn_kf_verify_overlap serve, pair j with SRC = the scan cloud, DST = the crop,
+ *   COARSE (coarse-to-fine only) and FINAL as for a verified loop pair.  The a_to_b overlap of FINAL against the crop is the share of the scan that the map
+ *   explains; b_to_a is small by construction (the crop is a whole neighbourhood, the scan sees part of it).  The record goes stale at the next crop or
+ *   localise call, or at the next verify call; a rebuilt or filtered map does NOT invalidate it.                                                          */
+#define QN_LOCALIZE_SPHERE 0
+#define QN_LOCALIZE_CYLINDER 1
+typedef struct qn_localize_params { double radius, leaf, score_thr; uint32_t shape, reserved; } qn_localize_params;                     /* 32 bytes */
+typedef struct qn_localize_stats { uint32_t n_map, n_pairs, n_scans, n_crops, passes, reserved; uint64_t crop_points, generation; } qn_localize_stats;   /* 40 bytes */
+void qn_localize_default_params(qn_localize_params* p);
+int  qn_kf_map_crop(qn_kf_store*, const double* centres_xyz /* n_crops x 3 */, uint32_t n_crops, double radius, uint32_t shape, uint32_t* counts_out);
+int  qn_kf_map_crop_get(qn_kf_store*, uint32_t crop, const float** d_xyzi /* float4: x y z intensity */, uint32_t* n, uint32_t* idx_out /* may be NULL */);
+int  qn_kf_map_localize(qn_kf_store*, qn_ctx*, const qn_localize_params* params, const int32_t* query, const double* guess16 /* n_pairs x 16, map <- sensor */,
+                        uint32_t n_pairs, qn_gicp_result* results, int* valid, int* status, qn_localize_stats* stats_out /* may be NULL */);
+int  qn_kf_map_localize_c2f(qn_kf_store*, qn_ctx*, const qn_localize_params* params, const int32_t* query, const double* guess16 /* n_pairs x 16 */,
+                            uint32_t n_pairs, qn_gicp_result* results, double* T_total, double* T_quatro /* may be NULL */, int* valid, int* status,
+                            qn_localize_stats* stats_out /* may be NULL */);
 /* LoopClosure::fetchClosestKeyframeIdx (loop_closure.cpp:34-56) generalised to the max_k nearest admissible keyframes,
  * ascending distance; out[0] is the reference's single choice.  Host code (O(#keyframes)).                        */
 int  qn_loop_candidates(const double* pos_xyz, const double* stamps, uint32_t n, uint32_t query, double radius, double tdiff,

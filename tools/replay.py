@@ -321,7 +321,8 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
         submap_matching=False, min_overlap=None, overlap_radius=None, max_see_through=None, range_params=None, static_map=False, static_radius=15.0,
         static_max_k=8, moving_boxes=0, save_map_normals=False, normal_radius=0.6, normal_min_neighbors=5, map_outliers=False,
         outlier_radius=1.0, outlier_k=8, outlier_std=2.0, occupancy_grid=False, grid_cell=0.5, max_slope=0.3, ground_tol=0.2, clearance=2.0,
-        drop_ground=False, map_clusters=False, cluster_tol=0.5, cluster_min=10, cluster_max=0xffffffff, drop_small_clusters=False):
+        drop_ground=False, map_clusters=False, cluster_tol=0.5, cluster_min=10, cluster_max=0xffffffff, drop_small_clusters=False,
+        localize_every=0, localize_radius=35.0, localize_shift=0.5, localize_yaw=3.0):
     """sensor = "uniform": keyframe clouds sampled uniformly by area inside a disc (make_stream); "spinning": ray-cast spinning-LiDAR
     scans from the ground-truth poses of the same figure-8 (make_lidar_stream).  detector = "radius": the candidate is the closest older
     keyframe within `radius` of the corrected position (LC:34-56); "scancontext": the older keyframe nearest by Scan Context distance, kept
@@ -381,6 +382,12 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
     clusters_static.csv too).  drop_small_clusters: the rejected clumps leave the map (KeyframeStore.map_drop_rejected_clusters).  The filters run in the order
     outliers, ground, clusters, drop_ground, normals; with drop_small_clusters and drop_ground both, the ground that leaves is that of the map without the
     clumps, segmented again.  out["clusters"] (and out["static_clusters"]): clusters, components, too_small, too_large, clustered_points, rejected_points.
+    localize_every = N > 0 (the GPU backend, with save_dir; default 0: off): once the corrected map stands (the map map.pcd is written from, filters included;
+    without save_map_leaf a map at `voxel`), every N-th keyframe is localised in it on the device (KeyframeStore.map_localize, map_localize_c2f with use_quatro)
+    from its corrected pose displaced by localize_shift metres and localize_yaw degrees, against the crop of localize_radius around that guess (a radius below
+    the scans' reach leaves far scan points without a partner and raises the score).  localized_tum.txt: one row per chosen keyframe, the pose found.
+    out["localized"]: per chosen keyframe id, valid, status, score and the translation [m] / rotation [rad] error of guess and result against the corrected pose
+    the map was built with (guess_t_err, guess_r_err, t_err, r_err).
     moving_boxes = N (sensor="spinning" only; default 0: every run is what it was): N extra boxes in the scene that stand somewhere else in every keyframe
     (moving_box_prims), so every keyframe is cast by a call of its own."""
     if detector not in ("radius", "scancontext"):
@@ -446,6 +453,14 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
     if map_clusters:
         from qn_amd import mapclusters
         mapclusters.check_params(mapclusters.ClusterParams(cluster_tol, cluster_min, cluster_max, 0))      # (raises ValueError on a parameter outside its range)
+    if int(localize_every) != localize_every or localize_every < 0:
+        raise ValueError("localize_every must be a whole number >= 0, not %r" % (localize_every,))
+    if localize_every and backend != "gpu":
+        raise ValueError("localize_every needs backend='gpu' (the map it localises in is the store's)")
+    if localize_every and save_dir is None:
+        raise ValueError("localize_every needs save_dir (localized_tum.txt is written there)")
+    if localize_every and not (np.isfinite(localize_radius) and localize_radius > 0 and np.isfinite(localize_shift) and np.isfinite(localize_yaw)):
+        raise ValueError("localize_every needs localize_radius > 0 and a finite shift and yaw, not %r / %r / %r" % (localize_radius, localize_shift, localize_yaw))
     overlaps = []; see_through = []; fs_images = {}
 
     def apply_freespace(rs, pairs):
@@ -693,8 +708,31 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
         out["overlaps"] = overlaps
     if fgate:
         out["see_through"] = see_through
+    def localize_stage():
+        """every localize_every-th keyframe localised in the map slot as it stands from its displaced corrected pose; fills out["localized"], writes localized_tum.txt"""
+        from qn_amd import engine, synth
+        pick = list(range(0, len(ids), int(localize_every)))
+        a = np.radians(localize_yaw); D = np.eye(4)
+        D[:2, :2] = [[np.cos(a), -np.sin(a)], [np.sin(a), np.cos(a)]]; D[:3, 3] = (0.6 * localize_shift, 0.8 * localize_shift, 0.0)
+        guesses = [corrected[k] @ D for k in pick]
+        call = store.map_localize_c2f if use_quatro else store.map_localize
+        rs, lst = call(ctx, [ids[k] for k in pick], guesses, engine.LocalizeParams(localize_radius, voxel, score_thr, 0))
+        out["localized"] = []
+        for k, G, r in zip(pick, guesses, rs):
+            gt_err, gr_err = synth.pose_error(G, corrected[k]); t_err, r_err = synth.pose_error(r["T"], corrected[k])
+            out["localized"].append(dict(id=k, valid=r["valid"], status=r["status"], score=r["score"], guess_t_err=gt_err, guess_r_err=gr_err, t_err=t_err,
+                                         r_err=r_err, T=r["T"]))
+        out["localize_stats"] = lst
+        with open(os.path.join(save_dir, "localized_tum.txt"), "w") as ft:
+            ft.write("#timestamp x y z qx qy qz qw\n")
+            for k, r in zip(pick, rs):
+                q = rot_to_quat(r["T"][:3, :3])
+                ft.write("%.8f %.8f %.8f %.8f %.8f %.8f %.8f %.8f\n" % (stamps[k], r["T"][0, 3], r["T"][1, 3], r["T"][2, 3], q[0], q[1], q[2], q[3]))
     if save_dir:
         write_kitti_tum(save_dir, corrected, stamps)
+        if localize_every and save_map_leaf is None:
+            store.build_map(ids, corrected, voxel)
+            localize_stage()
         if save_map_leaf is not None and backend == "gpu":
             def write_map(name, n, label=None):
                 """the map slot as a .pcd, with the normals of its points when asked and their cluster labels when given -> the points that have a normal"""
@@ -747,6 +785,8 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
             n, removed = filter_map(store.build_map(ids, corrected, save_map_leaf))
             n, label = ground_stage("map", n)
             valid = write_map("map.pcd", n, label)
+            if localize_every:
+                localize_stage()
             if map_outliers:
                 out["map_points"] = n; out["map_outliers_removed"] = removed
             if map_clusters:
@@ -773,7 +813,10 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
             out["grid"] = {k: int(getattr(r["stats"], k)) for k in ("width", "height", "occupied", "free", "unknown", "n_ground")}
             write_pcd_xyzi(os.path.join(save_dir, "map.pcd"), mapground.keep(pts, r["classes"], 0b11101) if drop_ground else pts)
     if verbose:
-        print({k: v for k, v in out.items() if k not in ("poses", "loop_list", "loop_T", "gt", "overlaps", "see_through")})
+        print({k: v for k, v in out.items() if k not in ("poses", "loop_list", "loop_T", "gt", "overlaps", "see_through", "localized")})
+        for r in out.get("localized", []):
+            print("localized keyframe %d: valid %s, score %.4f, guess %.3f m / %.2f deg -> %.4f m / %.3f deg" %
+                  (r["id"], r["valid"], r["score"], r["guess_t_err"], np.degrees(r["guess_r_err"]), r["t_err"], np.degrees(r["r_err"])))
     if backend == "gpu":
         ctx.close(); store.close()
     return out
@@ -826,6 +869,12 @@ if __name__ == "__main__":
     ap.add_argument("--cluster-min", type=int, default=10, help="with --map-clusters: the fewest points of a cluster")
     ap.add_argument("--cluster-max", type=int, default=0xffffffff, help="with --map-clusters: the most points of a cluster")
     ap.add_argument("--drop-small-clusters", action="store_true", help="with --map-clusters: the clumps that are no cluster leave the map")
+    ap.add_argument("--localize-every", type=int, default=0,
+                    help="with --save-dir: once the map stands, every N-th keyframe is localised in it on the device from its displaced corrected pose (with --quatro coarse to "
+                         "fine); writes localized_tum.txt")
+    ap.add_argument("--localize-radius", type=float, default=35.0, help="with --localize-every: the radius of the map crop around the guess [m]")
+    ap.add_argument("--localize-shift", type=float, default=0.5, help="with --localize-every: the guess is this far from the corrected pose [m]")
+    ap.add_argument("--localize-yaw", type=float, default=3.0, help="with --localize-every: and turned by this much [deg]")
     ap.add_argument("--moving-boxes", type=int, default=0, help="with --sensor spinning: this many boxes that stand somewhere else in every keyframe")
     ap.add_argument("--backend", choices=["gpu", "oracle"], default="gpu", help="the engine on the GPU, or the CPU oracle")
     a = ap.parse_args()
@@ -847,4 +896,5 @@ if __name__ == "__main__":
         save_map_normals=a.save_map_normals, normal_radius=a.normal_radius, map_outliers=a.map_outliers, outlier_radius=a.outlier_radius, outlier_k=a.outlier_k,
         outlier_std=a.outlier_std, occupancy_grid=a.occupancy_grid, grid_cell=a.grid_cell, max_slope=a.max_slope, ground_tol=a.ground_tol,
         clearance=a.clearance, drop_ground=a.drop_ground, map_clusters=a.map_clusters, cluster_tol=a.cluster_tol, cluster_min=a.cluster_min,
-        cluster_max=a.cluster_max, drop_small_clusters=a.drop_small_clusters)
+        cluster_max=a.cluster_max, drop_small_clusters=a.drop_small_clusters, localize_every=a.localize_every, localize_radius=a.localize_radius,
+        localize_shift=a.localize_shift, localize_yaw=a.localize_yaw)
