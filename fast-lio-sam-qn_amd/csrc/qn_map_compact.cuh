@@ -5,6 +5,8 @@
 //             MO_BLOCK records (block_count); k_mo_scan (one block) turns the counts into offsets, the last one the number kept; k_mo_compact moves a block's
 //             kept records to its offset, in order, by ballot / popcount ranks and the waves' counts through LDS - the static map's scheme: stable and the
 //             same on every run; qn_kf_map_compact_shrink makes the kept records the slot.
+// A unit that counts but never filters the map slot (qn_mapoccupancy.inc in qn_staticmap.hip) defines QN_MAP_COUNTS_ONLY first and gets the counts alone, so it
+// carries no copy of the compaction kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -65,6 +67,7 @@ __global__ void __launch_bounds__(MO_SCAN_BLOCK) k_slot_fold(const W* __restrict
   }
 }
 
+#ifndef QN_MAP_COUNTS_ONLY
 // one block: off[b] = the kept records of the blocks before b, off[nb] = all of them (k_static_scan's scheme: thread i scans the blocks
 // [i chunk, (i + 1) chunk), the threads' sums through a wave scan and the waves in order)
 __global__ void __launch_bounds__(MO_SCAN_BLOCK) k_mo_scan(const uint32_t* __restrict__ cnt, uint32_t nb, uint32_t* __restrict__ off) {
@@ -121,5 +124,6 @@ inline int qn_kf_map_compact_shrink(qn_kf_store* s, const float4* map, uint32_t 
   *d_xyzi_out = (const float*)qn_kf_int_map(s, n_out, &gen);
   return QN_OK;
 }
+#endif  // QN_MAP_COUNTS_ONLY
 
 }  // namespace

@@ -1,0 +1,442 @@
+// qn_mapoccupancy.inc - a 3-D occupancy map (occupied, free, unknown) by ray carving on the GPU (qn_kf_map_occupancy, qn_kf_map_occupancy_grid,
+// qn_kf_map_occupancy_list, qn_kf_map_occupancy_slice: include/qn_engine.h).  The numpy twin qn_amd/mapoccupancy.py is the specification: every record of a
+// listed keyframe is a ray from that entry's corrected sensor position O to the world point W; both ends are quantised once (f64, no contraction, half to even,
+// 10 fractional bits of a voxel), and everything behind that is an integer: the voxel walk, the u32 hit and miss counts, the class rule.  Integer adds commute,
+// so every byte equals the twin's whatever the order of the atomics.
+//   extent    k_oc_extent, grid (tiles of the largest entry of the launch, entries) as k_static_vote's, one record per lane: the record is accepted or skipped
+//             (oc_ray: non-finite, near, far - f32, left to right, no fused multiply-add), A and B are formed, a ray end of 2^20 voxels or more raises the
+//             capacity flag; the per-axis extremes of c(A) and c(B) by a wave reduction and one integer atomicMin / atomicMax per wave; the five record counts by
+//             block_count into the block's slot, k_slot_fold adds the slots up.  One host read: the host derives the grid and refuses before anything grid-sized
+//             is allocated.
+//   carve     k_oc_carve, the same grid, one ray per lane: oc_ray again (nothing is stored between the passes), then oc_walk, which names no floating-point
+//             type: hits[v_n] += 1 and misses[v_i] += 1 for i < n - shell by integer atomicAdd.  All rays of a block belong to one entry and start in the same
+//             voxel v_0, the hottest address there is: a wave folds its adds to v_0 into one add of the popcount (one atomic a wave instead of one a lane).  The
+//             voxels further out are added to lane by lane; a lane stops after its last miss, n - shell steps, since the end voxel is known without walking.
+//   classify  k_oc_classify, one voxel per lane: the class byte, the three class counts (block_count) and the block's hit and miss sums (u64) into slots,
+//             k_slot_fold adds them up.  One host read.
+//   list      k_oc_list_flag / k_static_scan / k_oc_list_pick: the count, scan and compact idiom of qn_map_compact.cuh over the voxels in linear order, stable;
+//             the scan is this unit's own k_static_scan (the scheme k_mo_scan was taken from) without entries.
+//   slice     k_oc_slice, one column per lane.
+// Host synchronisations of qn_kf_map_occupancy: two - the extent, the counts.  Integer atomics only, no scratch memory, no dynamically indexed private array.
+// Part of qn_staticmap.hip's translation unit (included at its end), the unit that turns a list with poses into per-record ray evidence: the results hang on
+// that unit's StaticState and take no slot of their own.  They do not depend on the map slot.
+#include <climits>
+#include <cstdlib>
+#define QN_MAP_COUNTS_ONLY                              // block_count and k_slot_fold; the scan is this unit's own
+#include "qn_map_compact.cuh"
+
+namespace {
+
+#define OC_BLOCK MO_BLOCK
+#define OC_S 10                                          // fractional bits of the fixed point
+#define OC_ONE (1 << OC_S)
+#define OC_COORD_LIMIT 1048576.0                         // 2^20 voxels
+#define OC_MAX_SIDE (1u << 15)
+#define OC_CHUNK 32768u                                  // entries per launch (the grid's y dimension)
+#define OC_RAY 0
+#define OC_NONFINITE 1
+#define OC_NEAR 2
+#define OC_FAR 3
+#define OC_CAPACITY 4
+
+struct OcEntry { const float4* pts; uint32_t n, b0; double P[12]; };          // records, first block slot, the pose's three rows; 112 bytes
+struct OcGrid { int32_t minc[3]; uint32_t W, H, cells; };
+
+// the quantisation, shared by the two passes: the status of record p under pose rows P, and for a ray its fixed-point ends
+__device__ __forceinline__ int oc_ray(const float4 p, const double* __restrict__ P, double inv, float lo2, float hi2, int32_t (&A)[3], int32_t (&B)[3]) {
+  if (!(isfinite(p.x) && isfinite(p.y) && isfinite(p.z))) return OC_NONFINITE;
+  const float d2 = (p.x * p.x + p.y * p.y) + p.z * p.z;
+  if (d2 < lo2) return OC_NEAR;
+  if (d2 > hi2) return OC_FAR;
+  const double x = p.x, y = p.y, z = p.z;
+  double o[3], w[3];
+  bool ok = true;
+#pragma unroll
+  for (int k = 0; k < 3; k++) {
+    o[k] = P[4 * k + 3] * inv;
+    w[k] = (((P[4 * k] * x + P[4 * k + 1] * y) + P[4 * k + 2] * z) + P[4 * k + 3]) * inv;
+    ok = ok && fabs(o[k]) < OC_COORD_LIMIT && fabs(w[k]) < OC_COORD_LIMIT;      // (a NaN fails the comparison)
+  }
+  if (!ok) return OC_CAPACITY;
+#pragma unroll
+  for (int k = 0; k < 3; k++) { A[k] = (int32_t)rint(o[k] * 1024.0); B[k] = (int32_t)rint(w[k] * 1024.0); }      // |.| <= 2^30
+  return OC_RAY;
+}
+
+__device__ __forceinline__ int oc_wave_min(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_down(v, o));
+  return v;
+}
+__device__ __forceinline__ int oc_wave_max(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_down(v, o));
+  return v;
+}
+
+// ext[0 .. 3) / ext[3 .. 6): the smallest / largest voxel coordinate of a ray end, ext[6]: 1 when a ray end is out of range; slots[5 b ..]: the block's records,
+// rays, non-finite, near and far records
+__global__ void __launch_bounds__(OC_BLOCK) k_oc_extent(const OcEntry* __restrict__ ents, double inv, float lo2, float hi2, int32_t* __restrict__ ext,
+                                                        uint32_t* __restrict__ slots) {
+  const OcEntry* E = ents + blockIdx.y;
+  const uint32_t n = E->n;
+  if (blockIdx.x * OC_BLOCK >= n) return;                            // uniform over the block
+  const uint32_t i = blockIdx.x * OC_BLOCK + threadIdx.x;
+  int st = -1;                                                       // (past the end: counted nowhere)
+  int32_t lo[3] = {INT_MAX, INT_MAX, INT_MAX}, hi[3] = {INT_MIN, INT_MIN, INT_MIN};
+  if (i < n) {
+    int32_t A[3], B[3];
+    st = oc_ray(E->pts[i], E->P, inv, lo2, hi2, A, B);
+    if (st == OC_RAY) {
+#pragma unroll
+      for (int k = 0; k < 3; k++) { const int32_t a = A[k] >> OC_S, b = B[k] >> OC_S; lo[k] = min(a, b); hi[k] = max(a, b); }
+    }
+    if (st == OC_CAPACITY) ext[6] = 1;                               // (a plain store of the same value by whoever finds one)
+  }
+#pragma unroll
+  for (int k = 0; k < 3; k++) { lo[k] = oc_wave_min(lo[k]); hi[k] = oc_wave_max(hi[k]); }
+  if ((threadIdx.x & 63) == 0 && lo[0] != INT_MAX) {
+#pragma unroll
+    for (int k = 0; k < 3; k++) { atomicMin(&ext[k], lo[k]); atomicMax(&ext[3 + k], hi[k]); }
+  }
+  block_count(slots + 5 * (size_t)(E->b0 + blockIdx.x), st >= 0, st == OC_RAY, st == OC_NONFINITE, st == OC_NEAR, st == OC_FAR);
+}
+
+// The walk of one ray a lane, integers only.  Every lane of the wave calls it (ray: this lane has one); all rays of the wave start in the same voxel.
+// c, r, D, rem and the step are kept per axis in scalars; D <= 2^31 and r <= D + 2^10 fit 32 bits, their products 64.  FOLD: the wave's adds to v_0 as one
+// add of the popcount (false: one a lane like every other voxel - the yardstick of tools/gpu_map_occupancy_time.py --no-fold; the same bytes).
+template <bool FOLD>
+__device__ __forceinline__ void oc_walk(bool ray, const int32_t (&A)[3], const int32_t (&B)[3], const OcGrid G, uint32_t shell, uint32_t* __restrict__ hits,
+                                        uint32_t* __restrict__ misses) {
+  const int32_t stride[3] = {1, (int32_t)G.W, (int32_t)(G.W * G.H)};
+  uint32_t r[3], D[3], rem[3]; int32_t step[3];
+  uint32_t n = 0; int32_t lin = 0, lend = 0;
+#pragma unroll
+  for (int k = 0; k < 3; k++) {
+    const int32_t c = A[k] >> OC_S, e = B[k] >> OC_S;                 // arithmetic shifts: floors
+    const bool up = B[k] > A[k];
+    D[k] = up ? (uint32_t)B[k] - (uint32_t)A[k] : (uint32_t)A[k] - (uint32_t)B[k];
+    rem[k] = (uint32_t)(e > c ? e - c : c - e);
+    r[k] = (uint32_t)(up ? (c + 1) * OC_ONE - A[k] : A[k] - c * OC_ONE);
+    step[k] = up ? stride[k] : -stride[k];
+    lin += (c - G.minc[k]) * stride[k]; lend += (e - G.minc[k]) * stride[k];
+    n += rem[k];
+  }
+  const uint32_t carve = ray && n > shell ? n - shell : 0;           // the voxels v_0 .. v_(carve - 1) get a miss
+  // v_0 is the same voxel in every lane: one add of the popcount for the wave
+  if (FOLD) {
+    const unsigned long long first = __ballot(carve > 0);
+    if (carve > 0 && (threadIdx.x & 63) == (uint32_t)(__ffsll((long long)first) - 1) && (uint32_t)lin < G.cells) atomicAdd(&misses[lin], (uint32_t)__popcll(first));
+  }
+  if (!ray) return;
+  if ((uint32_t)lend < G.cells) atomicAdd(&hits[lend], 1u);          // (always inside: the extremes made the grid; kept as a guard)
+  uint32_t r0 = r[0], r1 = r[1], r2 = r[2], m0 = rem[0], m1 = rem[1], m2 = rem[2];
+  const uint32_t D0 = D[0], D1 = D[1], D2 = D[2];
+  for (uint32_t i = 0; i < carve; i++) {
+    if ((!FOLD || i != 0) && (uint32_t)lin < G.cells) atomicAdd(&misses[lin], 1u);
+    // among the axes that still have a step to make, the smallest r / D; a tie goes to the lowest axis
+    int b; uint32_t rb, Db;
+    if (m0 > 0) { b = 0; rb = r0; Db = D0; } else if (m1 > 0) { b = 1; rb = r1; Db = D1; } else { b = 2; rb = r2; Db = D2; }
+    if (m1 > 0 && b < 1 && (unsigned long long)r1 * Db < (unsigned long long)rb * D1) { b = 1; rb = r1; Db = D1; }
+    if (m2 > 0 && b < 2 && (unsigned long long)r2 * Db < (unsigned long long)rb * D2) b = 2;
+    if (b == 0) { lin += step[0]; r0 += OC_ONE; m0--; }
+    else if (b == 1) { lin += step[1]; r1 += OC_ONE; m1--; }
+    else { lin += step[2]; r2 += OC_ONE; m2--; }
+  }
+}
+
+// the grid of k_oc_extent: every ray's hit and misses
+template <bool FOLD>
+__global__ void __launch_bounds__(OC_BLOCK) k_oc_carve(const OcEntry* __restrict__ ents, double inv, float lo2, float hi2, const OcGrid G, uint32_t shell,
+                                                       uint32_t* __restrict__ hits, uint32_t* __restrict__ misses) {
+  const OcEntry* E = ents + blockIdx.y;
+  const uint32_t n = E->n;
+  if (blockIdx.x * OC_BLOCK >= n) return;                            // uniform over the block
+  const uint32_t i = blockIdx.x * OC_BLOCK + threadIdx.x;
+  int32_t A[3] = {0, 0, 0}, B[3] = {0, 0, 0};
+  bool ray = false;
+  if (i < n) ray = oc_ray(E->pts[i], E->P, inv, lo2, hi2, A, B) == OC_RAY;
+  oc_walk<FOLD>(ray, A, B, G, shell, hits, misses);
+}
+
+// one voxel per lane: the class byte; cslots[3 b ..] = the block's occupied, free and unknown voxels, tslots[2 b ..] = its hits and misses
+__global__ void __launch_bounds__(OC_BLOCK) k_oc_classify(uint32_t cells, const uint32_t* __restrict__ hits, const uint32_t* __restrict__ misses, uint32_t min_hits,
+                                                          uint32_t hit_weight, uint8_t* __restrict__ cls, uint32_t* __restrict__ cslots,
+                                                          unsigned long long* __restrict__ tslots) {
+  __shared__ unsigned long long wt[2][MO_WAVES];
+  const uint32_t i = blockIdx.x * OC_BLOCK + threadIdx.x;
+  int c = -1;                                                        // (past the end: counted nowhere)
+  uint32_t h = 0, m = 0;
+  if (i < cells) {
+    h = hits[i]; m = misses[i];
+    c = (h | m) == 0 ? QN_OCC_UNKNOWN : (h >= min_hits && (unsigned long long)h * hit_weight >= (unsigned long long)m) ? QN_OCC_OCCUPIED : QN_OCC_FREE;
+    cls[i] = (uint8_t)c;
+  }
+  const unsigned long long th = wave_sum((unsigned long long)h), tm = wave_sum((unsigned long long)m);
+  if ((threadIdx.x & 63) == 0) { wt[0][threadIdx.x >> 6] = th; wt[1][threadIdx.x >> 6] = tm; }
+  block_count(cslots + 3 * (size_t)blockIdx.x, c == QN_OCC_OCCUPIED, c == QN_OCC_FREE, c == QN_OCC_UNKNOWN);      // (its barrier is the one the sums wait for)
+  if (threadIdx.x < 2) {
+    unsigned long long acc = 0;
+    for (int w = 0; w < MO_WAVES; w++) acc += wt[threadIdx.x][w];
+    tslots[2 * (size_t)blockIdx.x + threadIdx.x] = acc;
+  }
+}
+
+// one voxel per lane: the block's voxels whose class bit is in the mask into its slot (what k_mo_scan goes on from)
+__global__ void __launch_bounds__(MO_BLOCK) k_oc_list_flag(uint32_t cells, const uint8_t* __restrict__ cls, uint32_t mask, uint32_t* __restrict__ blk) {
+  const uint32_t i = blockIdx.x * MO_BLOCK + threadIdx.x;
+  block_count(blk + blockIdx.x, i < cells && ((mask >> cls[i]) & 1u) != 0);
+}
+
+// the block's listed voxels, in linear order, to ijk / hits / misses at off[block] .. (k_mo_compact's ranks)
+__global__ void __launch_bounds__(MO_BLOCK) k_oc_list_pick(uint32_t cells, const uint8_t* __restrict__ cls, uint32_t mask, const uint32_t* __restrict__ off,
+                                                           const uint32_t* __restrict__ hits, const uint32_t* __restrict__ misses, uint32_t W, uint32_t H,
+                                                           int32_t* __restrict__ ijk, uint32_t* __restrict__ h_out, uint32_t* __restrict__ m_out) {
+  __shared__ uint32_t wk[MO_WAVES];
+  const uint32_t i = blockIdx.x * MO_BLOCK + threadIdx.x;
+  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const bool keep = i < cells && ((mask >> cls[i]) & 1u) != 0;
+  const unsigned long long bal = __ballot(keep);
+  if (lane == 0) wk[wave] = (uint32_t)__popcll(bal);
+  __syncthreads();
+  uint32_t before = off[blockIdx.x];
+#pragma unroll
+  for (int w = 0; w < MO_WAVES; w++) if ((uint32_t)w < wave) before += wk[w];
+  if (keep) {
+    const size_t j = before + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
+    const uint32_t row = i / W;
+    ijk[3 * j] = (int32_t)(i - row * W); ijk[3 * j + 1] = (int32_t)(row % H); ijk[3 * j + 2] = (int32_t)(row / H);
+    h_out[j] = hits[i]; m_out[j] = misses[i];
+  }
+}
+
+// one column per lane: the largest class over the layers lo .. hi (2 occupied, else 1 free, else 0)
+__global__ void __launch_bounds__(OC_BLOCK) k_oc_slice(uint32_t cols, const uint8_t* __restrict__ cls, uint32_t lo, uint32_t hi, uint8_t* __restrict__ out) {
+  const uint32_t c = blockIdx.x * OC_BLOCK + threadIdx.x;
+  if (c >= cols) return;
+  uint32_t v = 0;
+  for (uint32_t z = lo; z <= hi; z++) v = max(v, (uint32_t)cls[(size_t)z * cols + c]);
+  out[c] = (uint8_t)v;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- host side
+// The occupancy results of the latest successful call (a member of the unit's StaticState)
+struct OccState {
+  bool live = false;
+  DevBuf<uint32_t> hits, misses;
+  DevBuf<uint8_t> cls;
+  qn_occupancy_grid info;
+};
+
+const OccState* oc_live(qn_kf_store* s) {
+  const StaticState* st = (const StaticState*)qn_kf_int_ext(s, QN_KF_INT_EXT_STATIC);
+  return st && st->occ && st->occ->live ? st->occ.get() : nullptr;
+}
+
+// the launches of a kernel over the entries, OC_CHUNK of them at a time: f(first entry, grid)
+template <typename F> void oc_each_chunk(const OcEntry* ent, uint32_t count, F f) {
+  for (uint32_t a = 0; a < count; a += OC_CHUNK) {
+    const uint32_t m = std::min<uint32_t>(OC_CHUNK, count - a);
+    uint32_t cmax = 0;
+    for (uint32_t k = 0; k < m; k++) cmax = std::max(cmax, ent[a + k].n);
+    if (cmax) f(a, dim3((cmax + OC_BLOCK - 1) / OC_BLOCK, m));
+  }
+}
+
+}  // namespace
+
+extern "C" void qn_occupancy_default_params(qn_occupancy_params* p) {
+  if (!p) return;
+  memset(p, 0, sizeof(*p));
+  p->voxel = 0.3; p->min_range = 0.5; p->max_range = 60.0; p->shell = 1; p->min_hits = 1; p->hit_weight = 2;      // interface choices, not measurements
+}
+
+extern "C" int qn_kf_map_occupancy(qn_kf_store* s, const int32_t* ids, const double* poses16, uint32_t count, const qn_occupancy_params* params,
+                                   qn_occupancy_stats* stats_out) {
+  // ---- every argument is checked before anything runs
+  if (!s || !ids || !poses16 || count == 0 || !params || !stats_out) return QN_ERR_INVALID_ARG;
+  const qn_occupancy_params P = *params;
+  if (!std::isfinite(P.voxel) || !(P.voxel > 0.0) || !std::isfinite(P.min_range) || !(P.min_range >= 0.0) || !std::isfinite(P.max_range) ||
+      !(P.max_range > P.min_range) || P.min_hits < 1 || P.hit_weight < 1 || P.reserved[0] != 0 || P.reserved[1] != 0 || P.reserved[2] != 0)
+    return QN_ERR_INVALID_ARG;
+  const size_t n_kf = qn_kf_int_count(s);
+  for (uint32_t e = 0; e < count; e++) {
+    if (ids[e] < 0 || (size_t)ids[e] >= n_kf) return QN_ERR_INVALID_ARG;
+    for (int k = 0; k < 16; k++) if (!std::isfinite(poses16[16 * (size_t)e + k])) return QN_ERR_INVALID_ARG;
+  }
+  uint64_t total = 0, tiles = 0;
+  std::vector<OcEntry> ent(count);
+  for (uint32_t e = 0; e < count; e++) {
+    uint32_t n = 0;
+    const float4* pts = qn_kf_int_keyframe(s, ids[e], &n);
+    ent[e].pts = pts; ent[e].n = n; ent[e].b0 = (uint32_t)tiles;
+    memcpy(ent[e].P, poses16 + 16 * (size_t)e, sizeof(double) * 12);
+    total += n; tiles += (n + OC_BLOCK - 1) / OC_BLOCK;
+    if (total > 0xFFFFFFFFull) return QN_ERR_CAPACITY;
+  }
+  QN_KFCHK(s, hipSetDevice(qn_kf_int_device(s)));
+  StaticState* unit = nullptr;
+  const int rc = qn_kf_ext_state(s, QN_KF_INT_EXT_STATIC, &unit);
+  if (rc != QN_OK) return rc;
+  if (!unit->occ) unit->occ.reset(new (std::nothrow) OccState());
+  if (!unit->occ) return qn_kf_fail(s, "qn_kf_map_occupancy: out of memory");
+  OccState* st = unit->occ.get();
+  const hipStream_t str = qn_kf_int_stream(s);
+  const uint32_t nt = (uint32_t)tiles;
+  const double inv = 1.0 / P.voxel;
+  const float lo2 = (float)(P.min_range * P.min_range), hi2 = (float)(P.max_range * P.max_range);
+  // ---- scratch (0: the entries, 3: the blocks' count slots, 4: the blocks' u64 sums, 5: the extent and every folded sum) and the pinned mirror of 0 and 5.
+  // The small block: ext[8] (int32), the five record sums, the three class sums (u32), the two totals (u64 at byte 64)
+  const size_t ent_bytes = qn_up16(sizeof(OcEntry) * count), small_bytes = 80;
+  OcEntry* d_ent = (OcEntry*)qn_kf_int_scratch(s, 0, ent_bytes);
+  uint32_t* d_slots = (uint32_t*)qn_kf_int_scratch(s, 3, sizeof(uint32_t) * 5 * std::max<size_t>(nt, 1));
+  char* d_small = (char*)qn_kf_int_scratch(s, 5, small_bytes);
+  char* h = (char*)qn_kf_int_pinned(s, ent_bytes + 2 * small_bytes);
+  if (!d_ent || !d_slots || !d_small || !h) return qn_kf_fail(s, "qn_kf_map_occupancy: scratch allocation failed");
+  int32_t* d_ext = (int32_t*)d_small; uint32_t* d_sums = (uint32_t*)(d_small + 32); unsigned long long* d_tot = (unsigned long long*)(d_small + 64);
+  memcpy(h, ent.data(), sizeof(OcEntry) * count);
+  int32_t* h_init = (int32_t*)(h + ent_bytes);
+  memset(h_init, 0, small_bytes);
+  for (int k = 0; k < 3; k++) { h_init[k] = INT_MAX; h_init[3 + k] = INT_MIN; }
+  char* h_small = h + ent_bytes + small_bytes;
+  QN_KFCHK(s, hipMemcpyAsync(d_ent, h, sizeof(OcEntry) * count, hipMemcpyHostToDevice, str));
+  QN_KFCHK(s, hipMemcpyAsync(d_small, h_init, small_bytes, hipMemcpyHostToDevice, str));
+  // ---- the extent
+  if (nt) {
+    oc_each_chunk(ent.data(), count, [&](uint32_t a, dim3 grid) {
+      hipLaunchKernelGGL(k_oc_extent, grid, dim3(OC_BLOCK), 0, str, (const OcEntry*)(d_ent + a), inv, lo2, hi2, d_ext, d_slots);
+    });
+    hipLaunchKernelGGL((k_slot_fold<uint32_t, 5>), dim3(1), dim3(MO_SCAN_BLOCK), 0, str, (const uint32_t*)d_slots, nt, d_sums);
+    QN_KFCHK(s, hipGetLastError());
+  }
+  QN_KFCHK(s, hipMemcpyAsync(h_small, d_small, small_bytes, hipMemcpyDeviceToHost, str));
+  QN_KFCHK(s, hipStreamSynchronize(str));                   // sync 1: the extent
+  const int32_t* ext = (const int32_t*)h_small; const uint32_t* sums = (const uint32_t*)(h_small + 32);
+  if (ext[6]) {
+    qn_kf_int_set_error(s, "qn_kf_map_occupancy: a ray end of 2^20 voxels or more from the origin");
+    return QN_ERR_CAPACITY;
+  }
+  qn_occupancy_stats r;
+  memset(&r, 0, sizeof(r));
+  r.n_records = sums[0]; r.n_rays = sums[1]; r.n_nonfinite = sums[2]; r.n_near = sums[3]; r.n_far = sums[4];
+  qn_occupancy_grid info;
+  memset(&info, 0, sizeof(info));
+  info.voxel = P.voxel;
+  OcGrid G;
+  memset(&G, 0, sizeof(G));
+  if (r.n_rays) {
+    uint64_t side[3];
+    for (int k = 0; k < 3; k++) side[k] = (uint64_t)((int64_t)ext[3 + k] - (int64_t)ext[k] + 1);
+    if (side[0] > OC_MAX_SIDE || side[1] > OC_MAX_SIDE || side[2] > OC_MAX_SIDE || side[0] * side[1] * side[2] > (uint64_t)QN_OCC_MAX_CELLS) {
+      qn_kf_int_set_error(s, "qn_kf_map_occupancy: a grid of more than 2^27 voxels (or 2^15 a side)");
+      return QN_ERR_CAPACITY;
+    }
+    for (int k = 0; k < 3; k++) { G.minc[k] = info.minc[k] = ext[k]; info.origin[k] = (double)ext[k] * P.voxel; }
+    G.W = info.width = (uint32_t)side[0]; G.H = info.height = (uint32_t)side[1]; info.depth = (uint32_t)side[2];
+    G.cells = (uint32_t)(side[0] * side[1] * side[2]);
+  }
+  r.width = info.width; r.height = info.height; r.depth = info.depth;
+  const uint32_t cells = G.cells, cb = (cells + OC_BLOCK - 1) / OC_BLOCK;
+  // ---- from here on the previous result is gone
+  st->live = false;
+  if (cells) {
+    if (!st->hits.grow(s, cells) || !st->misses.grow(s, cells) || !st->cls.grow(s, cells)) return QN_ERR_HIP;
+    d_slots = (uint32_t*)qn_kf_int_scratch(s, 3, sizeof(uint32_t) * std::max<size_t>(5 * (size_t)nt, 3 * (size_t)cb));      // (unchanged when it fits: nothing reads the old slots any more)
+    unsigned long long* d_tslots = (unsigned long long*)qn_kf_int_scratch(s, 4, sizeof(unsigned long long) * 2 * (size_t)cb);
+    if (!d_slots || !d_tslots) return qn_kf_fail(s, "qn_kf_map_occupancy: scratch allocation failed");
+    QN_KFCHK(s, hipMemsetAsync(st->hits.p, 0, sizeof(uint32_t) * (size_t)cells, str));
+    QN_KFCHK(s, hipMemsetAsync(st->misses.p, 0, sizeof(uint32_t) * (size_t)cells, str));
+    // ---- carve, classify and count
+    const bool fold = getenv("QN_OCC_NO_FOLD") == nullptr;  // (a measuring switch: the results are the same bytes either way)
+    oc_each_chunk(ent.data(), count, [&](uint32_t a, dim3 grid) {
+      if (fold) hipLaunchKernelGGL(k_oc_carve<true>, grid, dim3(OC_BLOCK), 0, str, (const OcEntry*)(d_ent + a), inv, lo2, hi2, G, P.shell, st->hits.p, st->misses.p);
+      else hipLaunchKernelGGL(k_oc_carve<false>, grid, dim3(OC_BLOCK), 0, str, (const OcEntry*)(d_ent + a), inv, lo2, hi2, G, P.shell, st->hits.p, st->misses.p);
+    });
+    hipLaunchKernelGGL(k_oc_classify, dim3(cb), dim3(OC_BLOCK), 0, str, cells, (const uint32_t*)st->hits.p, (const uint32_t*)st->misses.p, P.min_hits, P.hit_weight,
+                       st->cls.p, d_slots, d_tslots);
+    hipLaunchKernelGGL((k_slot_fold<uint32_t, 3>), dim3(1), dim3(MO_SCAN_BLOCK), 0, str, (const uint32_t*)d_slots, cb, d_sums + 5);
+    hipLaunchKernelGGL((k_slot_fold<unsigned long long, 2>), dim3(1), dim3(MO_SCAN_BLOCK), 0, str, (const unsigned long long*)d_tslots, cb, d_tot);
+    QN_KFCHK(s, hipGetLastError());
+    QN_KFCHK(s, hipMemcpyAsync(h_small, d_small, small_bytes, hipMemcpyDeviceToHost, str));
+    QN_KFCHK(s, hipStreamSynchronize(str));                 // sync 2: the counts
+    const unsigned long long* tot = (const unsigned long long*)(h_small + 64);
+    r.occupied = sums[5]; r.free = sums[6]; r.unknown = sums[7];
+    r.total_hits = tot[0]; r.total_misses = tot[1];
+  }
+  st->info = info;
+  st->live = true;
+  *stats_out = r;
+  return QN_OK;
+}
+
+extern "C" int qn_kf_map_occupancy_grid(qn_kf_store* s, qn_occupancy_grid* info_out, uint32_t* hits_out, uint32_t* misses_out, uint8_t* class_out) {
+  if (!s || !info_out) return QN_ERR_INVALID_ARG;
+  const OccState* o = oc_live(s);
+  if (!o) return QN_ERR_NOT_READY;
+  const qn_occupancy_grid& g = o->info;
+  const size_t cells = (size_t)g.width * g.height * g.depth;
+  *info_out = g;
+  if (!cells || (!hits_out && !misses_out && !class_out)) return QN_OK;
+  QN_KFCHK(s, hipSetDevice(qn_kf_int_device(s)));
+  const hipStream_t str = qn_kf_int_stream(s);
+  if (hits_out) QN_KFCHK(s, hipMemcpyAsync(hits_out, o->hits.p, sizeof(uint32_t) * cells, hipMemcpyDeviceToHost, str));
+  if (misses_out) QN_KFCHK(s, hipMemcpyAsync(misses_out, o->misses.p, sizeof(uint32_t) * cells, hipMemcpyDeviceToHost, str));
+  if (class_out) QN_KFCHK(s, hipMemcpyAsync(class_out, o->cls.p, cells, hipMemcpyDeviceToHost, str));
+  QN_KFCHK(s, hipStreamSynchronize(str));
+  return QN_OK;
+}
+
+extern "C" int qn_kf_map_occupancy_list(qn_kf_store* s, uint32_t class_mask, uint32_t* n_out, int32_t* ijk_out, uint32_t* hits_out, uint32_t* misses_out) {
+  if (!s || !n_out || class_mask == 0 || (class_mask & ~7u)) return QN_ERR_INVALID_ARG;
+  const OccState* o = oc_live(s);
+  if (!o) return QN_ERR_NOT_READY;
+  const qn_occupancy_grid& g = o->info;
+  const uint32_t cells = g.width * g.height * g.depth, nb = (cells + MO_BLOCK - 1) / MO_BLOCK;
+  *n_out = 0;
+  if (!cells) return QN_OK;
+  QN_KFCHK(s, hipSetDevice(qn_kf_int_device(s)));
+  const hipStream_t str = qn_kf_int_stream(s);
+  uint32_t* d_blk = (uint32_t*)qn_kf_int_scratch(s, 3, sizeof(uint32_t) * (2 * (size_t)nb + 1));      // the blocks' counts, then their offsets and the total
+  uint32_t* h = (uint32_t*)qn_kf_int_pinned(s, 64);
+  if (!d_blk || !h) return qn_kf_fail(s, "qn_kf_map_occupancy_list: scratch allocation failed");
+  uint32_t* d_off = d_blk + nb;
+  hipLaunchKernelGGL(k_oc_list_flag, dim3(nb), dim3(MO_BLOCK), 0, str, cells, (const uint8_t*)o->cls.p, class_mask, d_blk);
+  hipLaunchKernelGGL(k_static_scan, dim3(1), dim3(SV_SCAN_BLOCK), 0, str, (const uint32_t*)d_blk, nb, d_off, (const SvEntry*)nullptr, 0u, (uint32_t*)nullptr);      // (no entries: the scan alone)
+  QN_KFCHK(s, hipGetLastError());
+  QN_KFCHK(s, hipMemcpyAsync(h, d_off + nb, sizeof(uint32_t), hipMemcpyDeviceToHost, str));
+  QN_KFCHK(s, hipStreamSynchronize(str));
+  const uint32_t n = h[0];
+  *n_out = n;
+  if (!n || (!ijk_out && !hits_out && !misses_out)) return QN_OK;
+  int32_t* d_ijk = (int32_t*)qn_kf_int_scratch(s, 1, sizeof(int32_t) * 3 * (size_t)n);
+  uint32_t* d_hm = (uint32_t*)qn_kf_int_scratch(s, 2, sizeof(uint32_t) * 2 * (size_t)n);
+  if (!d_ijk || !d_hm) return qn_kf_fail(s, "qn_kf_map_occupancy_list: scratch allocation failed");
+  hipLaunchKernelGGL(k_oc_list_pick, dim3(nb), dim3(MO_BLOCK), 0, str, cells, (const uint8_t*)o->cls.p, class_mask, (const uint32_t*)d_off, (const uint32_t*)o->hits.p,
+                     (const uint32_t*)o->misses.p, g.width, g.height, d_ijk, d_hm, d_hm + n);
+  QN_KFCHK(s, hipGetLastError());
+  if (ijk_out) QN_KFCHK(s, hipMemcpyAsync(ijk_out, d_ijk, sizeof(int32_t) * 3 * (size_t)n, hipMemcpyDeviceToHost, str));
+  if (hits_out) QN_KFCHK(s, hipMemcpyAsync(hits_out, d_hm, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, str));
+  if (misses_out) QN_KFCHK(s, hipMemcpyAsync(misses_out, d_hm + n, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, str));
+  QN_KFCHK(s, hipStreamSynchronize(str));
+  return QN_OK;
+}
+
+extern "C" int qn_kf_map_occupancy_slice(qn_kf_store* s, int32_t iz_lo, int32_t iz_hi, uint8_t* occupancy_out) {
+  if (!s || !occupancy_out || iz_lo > iz_hi) return QN_ERR_INVALID_ARG;
+  const OccState* o = oc_live(s);
+  if (!o) return QN_ERR_NOT_READY;
+  const qn_occupancy_grid& g = o->info;
+  const uint32_t cols = g.width * g.height;
+  if (!cols) return QN_OK;
+  const int64_t lo = std::max<int64_t>(iz_lo, 0), hi = std::min<int64_t>(iz_hi, (int64_t)g.depth - 1);
+  if (lo > hi) { memset(occupancy_out, 0, cols); return QN_OK; }      // no layer of the grid in the range
+  QN_KFCHK(s, hipSetDevice(qn_kf_int_device(s)));
+  const hipStream_t str = qn_kf_int_stream(s);
+  uint8_t* d_out = (uint8_t*)qn_kf_int_scratch(s, 1, cols);
+  if (!d_out) return qn_kf_fail(s, "qn_kf_map_occupancy_slice: scratch allocation failed");
+  hipLaunchKernelGGL(k_oc_slice, dim3((cols + OC_BLOCK - 1) / OC_BLOCK), dim3(OC_BLOCK), 0, str, cols, (const uint8_t*)o->cls.p, (uint32_t)lo, (uint32_t)hi, d_out);
+  QN_KFCHK(s, hipGetLastError());
+  QN_KFCHK(s, hipMemcpyAsync(occupancy_out, d_out, cols, hipMemcpyDeviceToHost, str));
+  QN_KFCHK(s, hipStreamSynchronize(str));
+  return QN_OK;
+}

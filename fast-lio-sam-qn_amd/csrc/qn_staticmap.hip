@@ -17,6 +17,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <string>
 #include <vector>
@@ -151,6 +152,7 @@ struct StaticState {
   uint64_t total = 0;
   DevBuf<uint8_t> votes;                                 // three planes, those of the live call `total` apart
   DevBuf<float4> kept;
+  std::shared_ptr<struct OccState> occ;                  // the occupancy map of qn_mapoccupancy.inc (included at the end, where the type is completed)
 };
 
 }  // namespace
@@ -297,3 +299,5 @@ extern "C" int qn_kf_build_map_static(qn_kf_store* s, double leaf, const float**
   for (uint32_t e = 0; e < count; e++) { pts[e] = st->kept.p + st->ent[e].kept_off; n[e] = st->ent[e].kept_n; has_i[e] = st->ent[e].has_i; }
   return qn_kf_int_build_map_from(s, pts.data(), n.data(), has_i.data(), st->poses.data(), count, leaf, d_xyzi_out, n_out);
 }
+
+#include "qn_mapoccupancy.inc"

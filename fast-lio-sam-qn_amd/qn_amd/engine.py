@@ -777,6 +777,37 @@ QN_GROUND_NONE, QN_GROUND_GROUND, QN_GROUND_OBSTACLE, QN_GROUND_OVERHEAD, QN_GRO
 QN_GROUND_MAX_CELLS = 1 << 26
 
 
+class OccupancyParams(C.Structure):
+    """qn_occupancy_params (48 bytes): the voxel edge, the ranges between which a record is a ray, the voxels before a ray's end that are not carved, the hits a
+    voxel needs to be occupied and the weight of a hit against a miss.  The defaults are interface choices, not measurements."""
+    _fields_ = [("voxel", C.c_double), ("min_range", C.c_double), ("max_range", C.c_double), ("shell", C.c_uint32), ("min_hits", C.c_uint32),
+                ("hit_weight", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+    def __init__(self, voxel=0.3, min_range=0.5, max_range=60.0, shell=1, min_hits=1, hit_weight=2):
+        super().__init__(voxel, min_range, max_range, shell, min_hits, hit_weight)
+
+    def twin(self):
+        """-> the mapoccupancy.OccupancyParams with these values"""
+        from . import mapoccupancy
+        return mapoccupancy.OccupancyParams(float(self.voxel), float(self.min_range), float(self.max_range), int(self.shell), int(self.min_hits),
+                                            int(self.hit_weight))
+
+
+class OccupancyStats(C.Structure):
+    """qn_occupancy_stats (64 bytes): every field is an integer the twin shares"""
+    _fields_ = ([(f, C.c_uint32) for f in ("n_records", "n_rays", "n_nonfinite", "n_near", "n_far", "width", "height", "depth", "occupied", "free", "unknown",
+                                           "reserved")] + [("total_hits", C.c_uint64), ("total_misses", C.c_uint64)])
+
+
+class OccupancyGrid(C.Structure):
+    """qn_occupancy_grid (56 bytes): the corner of voxel (0, 0, 0), the edge, the size and the voxel coordinates of that corner"""
+    _fields_ = [("origin", C.c_double * 3), ("voxel", C.c_double), ("width", C.c_uint32), ("height", C.c_uint32), ("depth", C.c_uint32), ("minc", C.c_int32 * 3)]
+
+
+QN_OCC_UNKNOWN, QN_OCC_FREE, QN_OCC_OCCUPIED = range(3)
+QN_OCC_MAX_CELLS = 1 << 27
+
+
 class ClusterParams(C.Structure):
     """qn_cluster_params (24 bytes): the joining distance, the smallest and the largest component that is a cluster, and the ground classes that take part
     (0: every finite point).  The defaults are interface choices, not measurements."""
@@ -1415,6 +1446,56 @@ class KeyframeStore:
         self._check(self._l.qn_kf_map_keep_classes(self.h, C.c_uint32(int(mask) & 0xffffffff), C.byref(ptr), C.byref(n)))
         self._map_n = n.value
         return ptr.value, n.value
+
+    # ---- a 3-D occupancy map by ray carving (qn_kf_map_occupancy / _grid / _list / _slice; numpy twin: qn_amd/mapoccupancy.py)
+    def map_occupancy(self, ids, poses, params=None):
+        """qn_kf_map_occupancy over the list build_map takes: every record of every listed keyframe is a ray from the entry's sensor position to the world point.
+        params: an OccupancyParams (or a mapoccupancy.OccupancyParams); None: the defaults.  -> stats, a dict of the fields of qn_occupancy_stats, equal to
+        those of mapoccupancy.classify of the same keyframes.  The map slot is neither read nor touched; map_occupancy_grid / _list / _slice serve the volume."""
+        ids = np.ascontiguousarray(ids, dtype=np.int32); poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(len(ids), 16)
+        p = OccupancyParams() if params is None else params
+        if not isinstance(p, OccupancyParams):
+            p = OccupancyParams(float(p.voxel), float(p.min_range), float(p.max_range), int(p.shell), int(p.min_hits), int(p.hit_weight))
+        st = OccupancyStats()
+        self._check(self._l.qn_kf_map_occupancy(self.h, _p(ids), _p(poses), C.c_uint32(len(ids)), C.byref(p), C.byref(st)))
+        return {f: int(getattr(st, f)) for f, _ in OccupancyStats._fields_ if f != "reserved"}
+
+    @staticmethod
+    def _occupancy_info(g):
+        return dict(origin=tuple(float(v) for v in g.origin), voxel=float(g.voxel), width=int(g.width), height=int(g.height), depth=int(g.depth),
+                    minc=tuple(int(v) for v in g.minc))
+
+    def map_occupancy_grid(self):
+        """qn_kf_map_occupancy_grid -> (info, hits (D, H, W) uint32, misses (D, H, W) uint32, classes (D, H, W) uint8) of the latest map_occupancy: info a dict of
+        origin, voxel, width, height, depth, minc; x the fastest axis, z the slowest; classes 0 unknown, 1 free, 2 occupied."""
+        g = OccupancyGrid()
+        self._check(self._l.qn_kf_map_occupancy_grid(self.h, C.byref(g), None, None, None))
+        W, H, D = int(g.width), int(g.height), int(g.depth)
+        n = W * H * D
+        hits = np.zeros(max(n, 1), np.uint32); misses = np.zeros(max(n, 1), np.uint32); cls = np.zeros(max(n, 1), np.uint8)
+        self._check(self._l.qn_kf_map_occupancy_grid(self.h, C.byref(g), _p(hits), _p(misses), _p(cls)))
+        return self._occupancy_info(g), hits[:n].reshape(D, H, W), misses[:n].reshape(D, H, W), cls[:n].reshape(D, H, W)
+
+    def map_occupancy_list(self, mask=1 << QN_OCC_OCCUPIED):
+        """qn_kf_map_occupancy_list -> (ijk (m, 3) int32 grid indices, hits (m,) uint32, misses (m,) uint32) of the voxels whose class bit (1 << class) is set in
+        mask, in ascending linear index"""
+        m = C.c_uint32(int(mask) & 0xffffffff); n = C.c_uint32()
+        self._check(self._l.qn_kf_map_occupancy_list(self.h, m, C.byref(n), None, None, None))
+        k = int(n.value)
+        ijk = np.zeros((max(k, 1), 3), np.int32); hits = np.zeros(max(k, 1), np.uint32); misses = np.zeros(max(k, 1), np.uint32)
+        if k:
+            self._check(self._l.qn_kf_map_occupancy_list(self.h, m, C.byref(n), _p(ijk), _p(hits), _p(misses)))
+        return ijk[:k], hits[:k], misses[:k]
+
+    def map_occupancy_slice(self, iz_lo, iz_hi):
+        """qn_kf_map_occupancy_slice -> (H, W) uint8: per column over the layers iz_lo .. iz_hi (inclusive, clipped to the grid) 2 if any voxel is occupied, else 1
+        if any is free, else 0 - the values of map_ground_grid's occupancy, so mapground.to_pgm / map_yaml serve it"""
+        g = OccupancyGrid()
+        self._check(self._l.qn_kf_map_occupancy_grid(self.h, C.byref(g), None, None, None))
+        W, H = int(g.width), int(g.height)
+        out = np.zeros(max(W * H, 1), np.uint8)
+        self._check(self._l.qn_kf_map_occupancy_slice(self.h, C.c_int32(int(iz_lo)), C.c_int32(int(iz_hi)), _p(out)))
+        return out[:W * H].reshape(H, W)
 
     # ---- the map slot's points clustered into objects (qn_kf_map_clusters / _cluster_points / _cluster_list / qn_kf_map_drop_rejected_clusters; numpy twin:
     # qn_amd/mapclusters.py)

@@ -722,6 +722,65 @@ int  qn_kf_map_ground(qn_kf_store*, const qn_ground_params* params, qn_ground_st
 int  qn_kf_map_ground_points(qn_kf_store*, uint8_t* class_out, int32_t* height_q_out);
 int  qn_kf_map_ground_grid(qn_kf_store*, qn_ground_grid* info_out, int32_t* ground_q_out, uint8_t* occupancy_out);
 int  qn_kf_map_keep_classes(qn_kf_store*, uint32_t class_mask, const float** d_xyzi_out /* float4: x y z intensity */, uint32_t* n_out);
+/* ---- a 3-D occupancy map by ray carving (csrc/qn_mapoccupancy.inc, part of csrc/qn_staticmap.hip; numpy twin and specification: qn_amd/mapoccupancy.py)
+ * The ground grid above calls a column free when it holds points and no obstacle: a statement about returns, not about space.  Every keyframe record is also a
+ * ray from that keyframe's corrected sensor position to a world point; these calls walk the rays of a list of keyframes through a voxel grid on the GPU and
+ * leave an OctoMap-style volume in which every voxel is occupied, observed free or never observed.  Both ray ends are quantised once; everything afterwards is
+ * an integer, independent of any order, and equal to the twin's bit for bit.
+ * Input: the list qn_kf_build_map takes - ids[0 .. count) and poses16 (row-major 4x4 f64, sensor -> world).  Ids may repeat; a list position is an entry.
+ * qn_occupancy_params (48 bytes): voxel (edge in m; finite, > 0; default 0.3), min_range (finite, >= 0; default 0.5), max_range (finite, > min_range; default
+ *   60), shell (default 1), min_hits (>= 1; default 1), hit_weight (>= 1; default 2), reserved[3] (0).  The defaults are interface choices, not measurements.
+ * Accepted records: record p = (x, y, z) of entry e, f32, sensor frame, is skipped and counted n_nonfinite when a coordinate is not finite.  Otherwise
+ *   d2 = x x + y y + z z in f32, left to right, no fused multiply-add (the overlap measure's arithmetic); the record is skipped and counted n_near when
+ *   d2 < float(min_range * min_range), n_far when d2 > float(max_range * max_range) (the squares in f64, rounded once).  Everything else is a ray.  A far
+ *   record is dropped whole instead of having its ray truncated: truncation needs a square root on the path.
+ * Ray ends, f64, no contraction: origin O = (P3, P7, P11); end W = ((P0 x + P1 y) + P2 z) + P3 per row (the static vote's arithmetic), the f32 coordinates
+ *   widened first; inv = 1.0 / voxel, computed on the host.  Fixed point with S = 10 fractional bits: A_k = (int64) rint((O_k * inv) * 1024.0), B_k likewise
+ *   from W, rounded half to even.  QN_ERR_CAPACITY when a ray has |O_k * inv| or |W_k * inv| >= 2^20.
+ * Walk, integers only: c = A >> S (an arithmetic shift, so a floor), cend = B >> S.  Per axis k: s_k = sign(B_k - A_k), D_k = |B_k - A_k|, rem_k =
+ *   |cend_k - c_k|, r_k = ((c_k + 1) << S) - A_k when s_k > 0, else A_k - (c_k << S) (0 for an origin on a face heading down: it steps at once).
+ *   n = rem_x + rem_y + rem_z times: among the axes with rem_k > 0 the one with the smallest r_k / D_k, compared as r_a D_b < r_b D_a in 64 bits; on a tie
+ *   the lowest axis; then c_k += s_k, r_k += 1 << S, rem_k -= 1.  The visited voxels are v_0 = c(A), ..., v_n = c(B).
+ * Counts, u32 per voxel: hits[v_n] += 1; misses[v_i] += 1 for 0 <= i < n - shell (none when n <= shell).  A ray never carves its own end voxel; shell keeps
+ *   the last voxels before a surface out of the carving, so grazing neighbours do not erode it.
+ * Grid: minc, maxc per axis from c(A) and c(B) of all rays (the walk is monotone per axis, so it stays inside).  W x H x D, x fastest, z slowest: voxel
+ *   (ix, iy, iz) at linear index (iz H + iy) W + ix.  QN_ERR_CAPACITY, before any grid-sized allocation, when a dimension exceeds 2^15 or W H D >
+ *   QN_OCC_MAX_CELLS = 2^27.  Without a ray the grid is 0 x 0 x 0.
+ * Classes, one byte per voxel: QN_OCC_UNKNOWN 0 (hits = misses = 0), QN_OCC_OCCUPIED 2 (hits >= min_hits and (u64) hits * hit_weight >= misses),
+ *   QN_OCC_FREE 1 (everything else).
+ * qn_occupancy_stats (64 bytes): n_records, n_rays, n_nonfinite, n_near, n_far; width, height, depth; occupied, free, unknown (voxels); reserved (0);
+ *   total_hits, total_misses (u64).  Every field is an integer and is shared with the twin.
+ * qn_occupancy_grid (56 bytes): origin[3] (minc * voxel, f64: the corner of voxel (0, 0, 0)), voxel, width, height, depth, minc[3].
+ * qn_kf_map_occupancy: QN_ERR_INVALID_ARG, before anything runs and with the previous result intact: a null pointer, count == 0, an id that names no
+ *   keyframe, a pose that is not finite, a parameter outside the ranges above, reserved != 0.  QN_ERR_CAPACITY as above (the previous result intact), and at
+ *   2^32 records.  The results stay resident until the next successful call; they do not depend on the map slot, and no map build ends them.  Two host
+ *   synchronisations: the extent, the counts.
+ * qn_kf_map_occupancy_grid: *info_out and the three arrays of W H D elements; the arrays may be NULL to fetch the dimensions first.  QN_ERR_NOT_READY before
+ *   a successful qn_kf_map_occupancy.
+ * qn_kf_map_occupancy_list: the voxels whose class bit (1 << class) is set in class_mask, in ascending linear index (a stable device compaction): *n_out
+ *   their number, ijk_out three grid indices each, hits_out, misses_out; the arrays may be NULL to fetch *n_out first.  QN_ERR_INVALID_ARG: mask 0 or a bit
+ *   >= 3.  QN_ERR_NOT_READY as above.
+ * qn_kf_map_occupancy_slice: occupancy_out (W x H, row-major with y the slow axis) - per column over the layers iz_lo .. iz_hi inclusive, clipped to the grid:
+ *   2 if any voxel is OCCUPIED, else 1 if any is FREE, else 0: the values of qn_kf_map_ground_grid's occupancy, where free here means that a ray passed.
+ *   QN_ERR_INVALID_ARG when iz_lo > iz_hi.  QN_ERR_NOT_READY as above.                                                                                  */
+#define QN_OCC_MAX_CELLS (1u << 27)
+#define QN_OCC_UNKNOWN 0
+#define QN_OCC_FREE 1
+#define QN_OCC_OCCUPIED 2
+typedef struct qn_occupancy_params { double voxel, min_range, max_range; uint32_t shell, min_hits, hit_weight; uint32_t reserved[3]; } qn_occupancy_params;   /* 48 bytes */
+typedef struct qn_occupancy_stats {
+  uint32_t n_records, n_rays, n_nonfinite, n_near, n_far;
+  uint32_t width, height, depth;
+  uint32_t occupied, free, unknown, reserved;
+  uint64_t total_hits, total_misses;
+} qn_occupancy_stats;                                                                                                        /* 64 bytes */
+typedef struct qn_occupancy_grid { double origin[3], voxel; uint32_t width, height, depth; int32_t minc[3]; } qn_occupancy_grid;   /* 56 bytes */
+void qn_occupancy_default_params(qn_occupancy_params* p);
+int  qn_kf_map_occupancy(qn_kf_store*, const int32_t* ids, const double* poses16, uint32_t count, const qn_occupancy_params* params,
+                         qn_occupancy_stats* stats_out);
+int  qn_kf_map_occupancy_grid(qn_kf_store*, qn_occupancy_grid* info_out, uint32_t* hits_out, uint32_t* misses_out, uint8_t* class_out);
+int  qn_kf_map_occupancy_list(qn_kf_store*, uint32_t class_mask, uint32_t* n_out, int32_t* ijk_out, uint32_t* hits_out, uint32_t* misses_out);
+int  qn_kf_map_occupancy_slice(qn_kf_store*, int32_t iz_lo, int32_t iz_hi, uint8_t* occupancy_out /* W x H, y slow */);
 /* ---- the map's points clustered into objects (csrc/qn_mapclusters.inc, part of csrc/qn_mapoutliers.hip; numpy twin and specification: qn_amd/mapclusters.py)
  * After qn_kf_map_ground every point is GROUND, OBSTACLE or OVERHEAD, but the obstacles are an unstructured set.  These calls run PCL's
  * EuclideanClusterExtraction over the store's map slot on the GPU: connected components of the radius graph, each with a size, a box and a centroid, and the

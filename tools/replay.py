@@ -230,6 +230,31 @@ def write_grid(save_dir, stem, info, occupancy):
         f.write(mapground.map_yaml(info, stem + ".pgm"))
 
 
+def write_pcd_voxels(path, centres, hits, misses):
+    """PCD v0.7 ASCII, FIELDS x y z hits misses: the centres of voxels of the 3-D occupancy map with their counts"""
+    with open(path, "w") as f:
+        f.write("# .PCD v0.7 - Point Cloud Data file format\nVERSION 0.7\nFIELDS x y z hits misses\nSIZE 4 4 4 4 4\nTYPE F F F U U\nCOUNT 1 1 1 1 1\n"
+                "WIDTH %d\nHEIGHT 1\nVIEWPOINT 0 0 0 1 0 0 0\nPOINTS %d\nDATA ascii\n" % (len(centres), len(centres)))
+        for c, h, m in zip(centres, hits, misses):
+            f.write("%.9g %.9g %.9g %d %d\n" % (np.float32(c[0]), np.float32(c[1]), np.float32(c[2]), h, m))
+
+
+def write_occupancy(save_dir, result, slice_z=None):
+    """the 3-D occupancy map `result` (the dict of qn_amd/mapoccupancy.classify, or the GPU's arrays in the same form) as occupied.pcd - the centres of the
+    occupied voxels with their hits and misses - and, with slice_z = (z_lo, z_hi) in metres, occupancy_slice.pgm / .yaml: the layers those heights fall in,
+    flattened (mapground.to_pgm / map_yaml: here free means that a ray passed) -> the layers (iz_lo, iz_hi) or None"""
+    from qn_amd import mapground, mapoccupancy
+    g = mapoccupancy.OccupancyGrid(*result["grid"])
+    ijk, hits, misses = mapoccupancy.voxel_list(result, 1 << mapoccupancy.OCCUPIED)
+    write_pcd_voxels(os.path.join(save_dir, "occupied.pcd"), mapoccupancy.centres(ijk, g), hits, misses)
+    if slice_z is None:
+        return None
+    lo, hi = mapoccupancy.layer_of(slice_z[0], g), mapoccupancy.layer_of(slice_z[1], g)
+    occ = result["slice"](lo, hi) if "slice" in result else mapoccupancy.slice2d(result["classes"], lo, hi)
+    write_grid(save_dir, "occupancy_slice", mapground.GridInfo(g.origin[0], g.origin[1], g.voxel, g.width, g.height, 0), occ)
+    return lo, hi
+
+
 def write_pcd_xyzi_normal(path, pts, normals, curvature):
     """PCD v0.7 ASCII, FIELDS x y z intensity normal_x normal_y normal_z curvature (a PointXYZINormal cloud); a point without a normal carries nan"""
     with open(path, "w") as f:
@@ -322,7 +347,8 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
         static_max_k=8, moving_boxes=0, save_map_normals=False, normal_radius=0.6, normal_min_neighbors=5, map_outliers=False,
         outlier_radius=1.0, outlier_k=8, outlier_std=2.0, occupancy_grid=False, grid_cell=0.5, max_slope=0.3, ground_tol=0.2, clearance=2.0,
         drop_ground=False, map_clusters=False, cluster_tol=0.5, cluster_min=10, cluster_max=0xffffffff, drop_small_clusters=False,
-        localize_every=0, localize_radius=35.0, localize_shift=0.5, localize_yaw=3.0):
+        localize_every=0, localize_radius=35.0, localize_shift=0.5, localize_yaw=3.0, occupancy_3d=False, occ_voxel=0.3, occ_min_range=0.5,
+        occ_max_range=60.0, occ_shell=1, occ_slice=None):
     """sensor = "uniform": keyframe clouds sampled uniformly by area inside a disc (make_stream); "spinning": ray-cast spinning-LiDAR
     scans from the ground-truth poses of the same figure-8 (make_lidar_stream).  detector = "radius": the candidate is the closest older
     keyframe within `radius` of the corrected position (LC:34-56); "scancontext": the older keyframe nearest by Scan Context distance, kept
@@ -388,6 +414,12 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
     the scans' reach leaves far scan points without a partner and raises the score).  localized_tum.txt: one row per chosen keyframe, the pose found.
     out["localized"]: per chosen keyframe id, valid, status, score and the translation [m] / rotation [rad] error of guess and result against the corrected pose
     the map was built with (guess_t_err, guess_r_err, t_err, r_err).
+    occupancy_3d (with save_dir; default False): the rays of every keyframe - from its corrected sensor position to each of its records within occ_min_range ..
+    occ_max_range - are walked through a grid of occ_voxel metres (qn_amd/mapoccupancy.py: a hit where a ray ends, a miss in the voxels it crossed but the last
+    occ_shell), on the GPU backend by KeyframeStore.map_occupancy, on the oracle backend by the numpy twin.  occupied.pcd: the centres of the occupied voxels,
+    FIELDS x y z hits misses.  occ_slice = (z_lo, z_hi) in metres: also occupancy_slice.pgm / .yaml, the layers of those heights flattened to the grid a planner
+    loads (occupied where any voxel is, else free where a ray passed, else unknown).  out["occupancy"]: rays, total_misses, width, height, depth, occupied, free,
+    unknown, and slice_layers with occ_slice.
     moving_boxes = N (sensor="spinning" only; default 0: every run is what it was): N extra boxes in the scene that stand somewhere else in every keyframe
     (moving_box_prims), so every keyframe is cast by a call of its own."""
     if detector not in ("radius", "scancontext"):
@@ -444,6 +476,16 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
     if occupancy_grid:
         from qn_amd import mapground
         mapground.units((grid_cell, max_slope, ground_tol, clearance, 1))                         # (raises ValueError on a parameter outside its range)
+    if occ_slice is not None and not occupancy_3d:
+        raise ValueError("occ_slice needs occupancy_3d (the slice is cut from its volume)")
+    if occupancy_3d and save_dir is None:
+        raise ValueError("occupancy_3d needs save_dir (occupied.pcd is written there)")
+    if occupancy_3d:
+        from qn_amd import mapoccupancy
+        occ_params = mapoccupancy.OccupancyParams(occ_voxel, occ_min_range, occ_max_range, occ_shell)
+        mapoccupancy.check_params(occ_params)                                                     # (raises ValueError on a parameter outside its range)
+        if occ_slice is not None and not (len(occ_slice) == 2 and np.isfinite(occ_slice).all() and occ_slice[0] <= occ_slice[1]):
+            raise ValueError("occ_slice must be two finite heights z_lo <= z_hi, not %r" % (occ_slice,))
     if drop_small_clusters and not map_clusters:
         raise ValueError("drop_small_clusters needs map_clusters (the clumps come from its components)")
     if map_clusters and backend != "gpu":
@@ -730,6 +772,20 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
                 ft.write("%.8f %.8f %.8f %.8f %.8f %.8f %.8f %.8f\n" % (stamps[k], r["T"][0, 3], r["T"][1, 3], r["T"][2, 3], q[0], q[1], q[2], q[3]))
     if save_dir:
         write_kitti_tum(save_dir, corrected, stamps)
+        if occupancy_3d:
+            if backend == "gpu":
+                from qn_amd import engine
+                st = store.map_occupancy(ids, corrected, engine.OccupancyParams(*occ_params))
+                info, hits, misses, cls = store.map_occupancy_grid()
+                res = dict(hits=hits, misses=misses, classes=cls, grid=mapoccupancy.OccupancyGrid(*(info[f] for f in mapoccupancy.OccupancyGrid._fields)),
+                           slice=store.map_occupancy_slice)
+            else:
+                res = mapoccupancy.classify(scans, corrected, occ_params)
+                st = res["stats"]._asdict()
+            layers = write_occupancy(save_dir, res, occ_slice)
+            out["occupancy"] = {k: int(st[k]) for k in ("n_rays", "total_misses", "width", "height", "depth", "occupied", "free", "unknown")}
+            if layers is not None:
+                out["occupancy"]["slice_layers"] = [int(layers[0]), int(layers[1])]
         if localize_every and save_map_leaf is None:
             store.build_map(ids, corrected, voxel)
             localize_stage()
@@ -875,6 +931,14 @@ if __name__ == "__main__":
     ap.add_argument("--localize-radius", type=float, default=35.0, help="with --localize-every: the radius of the map crop around the guess [m]")
     ap.add_argument("--localize-shift", type=float, default=0.5, help="with --localize-every: the guess is this far from the corrected pose [m]")
     ap.add_argument("--localize-yaw", type=float, default=3.0, help="with --localize-every: and turned by this much [deg]")
+    ap.add_argument("--occupancy-3d", action="store_true",
+                    help="with --save-dir: also write occupied.pcd, the occupied voxels of the 3-D occupancy map carved by every keyframe's rays (x y z hits misses)")
+    ap.add_argument("--occ-voxel", type=float, default=0.3, help="with --occupancy-3d: the voxel edge [m]")
+    ap.add_argument("--occ-min-range", type=float, default=0.5, help="with --occupancy-3d: records closer than this are no rays [m]")
+    ap.add_argument("--occ-max-range", type=float, default=60.0, help="with --occupancy-3d: records farther than this are no rays [m]")
+    ap.add_argument("--occ-shell", type=int, default=1, help="with --occupancy-3d: the voxels before a ray's end that it does not carve")
+    ap.add_argument("--occ-slice", type=float, nargs=2, default=None, metavar=("ZLO", "ZHI"),
+                    help="with --occupancy-3d: also write occupancy_slice.pgm / .yaml, the layers between these heights [m] flattened")
     ap.add_argument("--moving-boxes", type=int, default=0, help="with --sensor spinning: this many boxes that stand somewhere else in every keyframe")
     ap.add_argument("--backend", choices=["gpu", "oracle"], default="gpu", help="the engine on the GPU, or the CPU oracle")
     a = ap.parse_args()
@@ -890,6 +954,10 @@ if __name__ == "__main__":
         ap.error("--map-clusters needs --save-dir and --save-map-leaf")
     if a.drop_small_clusters and not a.map_clusters:
         ap.error("--drop-small-clusters needs --map-clusters")
+    if a.occupancy_3d and a.save_dir is None:
+        ap.error("--occupancy-3d needs --save-dir")
+    if a.occ_slice is not None and not a.occupancy_3d:
+        ap.error("--occ-slice needs --occupancy-3d")
     run(a.keyframes, a.seed, a.quatro, save_dir=a.save_dir, save_map_leaf=a.save_map_leaf, sensor=a.sensor, detector=a.detector, yaw_bias=a.yaw_bias,
         verify=a.verify, sc_top_k=a.sc_top_k, backend=a.backend, loop_every=a.loop_every, catch_up=a.catch_up, submap_matching=a.submap_matching,
         min_overlap=a.min_overlap, overlap_radius=a.overlap_radius, max_see_through=a.max_see_through, static_map=a.static_map, moving_boxes=a.moving_boxes,
@@ -897,4 +965,5 @@ if __name__ == "__main__":
         outlier_std=a.outlier_std, occupancy_grid=a.occupancy_grid, grid_cell=a.grid_cell, max_slope=a.max_slope, ground_tol=a.ground_tol,
         clearance=a.clearance, drop_ground=a.drop_ground, map_clusters=a.map_clusters, cluster_tol=a.cluster_tol, cluster_min=a.cluster_min,
         cluster_max=a.cluster_max, drop_small_clusters=a.drop_small_clusters, localize_every=a.localize_every, localize_radius=a.localize_radius,
-        localize_shift=a.localize_shift, localize_yaw=a.localize_yaw)
+        localize_shift=a.localize_shift, localize_yaw=a.localize_yaw, occupancy_3d=a.occupancy_3d, occ_voxel=a.occ_voxel, occ_min_range=a.occ_min_range,
+        occ_max_range=a.occ_max_range, occ_shell=a.occ_shell, occ_slice=a.occ_slice)
