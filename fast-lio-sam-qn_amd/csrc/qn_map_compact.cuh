@@ -1,12 +1,17 @@
-// qn_map_compact.cuh - what the units around the map slot share on the device besides the cell walk (qn_mapoutliers.hip, qn_mapground.hip):
+// qn_map_compact.cuh - what the units around the map slot share on the device besides the cell walk (qn_mapoutliers.hip with qn_mapclusters.inc, qn_mapground.hip,
+// qn_staticmap.hip with qn_mapoccupancy.inc, qn_verify.hip with qn_maplocalize.inc):
 //   counts    block_count: the lanes of a block for which each of up to five predicates holds, by ballot and popcount, one word per wave in LDS, into the
 //             block's own slot; k_slot_fold (one block) adds the slots up.  No atomics: integer sums, the same on every run.
+//   scan      scan_row: the exclusive scan of a row of per-block counts in one block; k_scan_rows, a block per row, is the kernel over it (one row: a filter's
+//             or a list's counts, the last word the total; a row per centre, in place: the crop), k_static_scan (qn_staticmap.hip) the one with a tail of its own.
+//   rank      lane_rank: a lane's place among the lanes of its wave for which a predicate holds, by ballot and popcount; block_rank: its place in the block, the
+//             waves' counts through LDS, on top of the block's offset from the scan - where a stable compaction puts the lane's record: the same on every run.
+//             The kernels with one predicate call block_rank and write their own payload there (k_mo_compact, k_mc_pick, k_mc_root_label, k_oc_list_pick);
+//             those with a table of their own (k_static_compact: rounds, k_ml_compact: centres) take lane_rank for the last term.
 //   compact   the order-preserving compaction of the slot's records: a unit's own flag kernel writes one removed byte per record and the kept count of every
-//             MO_BLOCK records (block_count); k_mo_scan (one block) turns the counts into offsets, the last one the number kept; k_mo_compact moves a block's
-//             kept records to its offset, in order, by ballot / popcount ranks and the waves' counts through LDS - the static map's scheme: stable and the
-//             same on every run; qn_kf_map_compact_shrink makes the kept records the slot.
-// A unit that counts but never filters the map slot (qn_mapoccupancy.inc in qn_staticmap.hip) defines QN_MAP_COUNTS_ONLY first and gets the counts alone, so it
-// carries no copy of the compaction kernels.
+//             MO_BLOCK records (block_count), k_scan_rows turns the counts into offsets, k_mo_compact moves a block's kept records to its offset, in order;
+//             qn_kf_map_compact_shrink makes the kept records the slot.  Templates on the record type: instantiated only in the units that filter the slot, so a
+//             unit that only counts, scans or lists carries no copy of the compaction kernel.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -67,10 +72,28 @@ __global__ void __launch_bounds__(MO_SCAN_BLOCK) k_slot_fold(const W* __restrict
   }
 }
 
-#ifndef QN_MAP_COUNTS_ONLY
-// one block: off[b] = the kept records of the blocks before b, off[nb] = all of them (k_static_scan's scheme: thread i scans the blocks
-// [i chunk, (i + 1) chunk), the threads' sums through a wave scan and the waves in order)
-__global__ void __launch_bounds__(MO_SCAN_BLOCK) k_mo_scan(const uint32_t* __restrict__ cnt, uint32_t nb, uint32_t* __restrict__ off) {
+// the set ballot bits below the calling lane: its rank among the lanes of its wave for which the predicate holds
+__device__ __forceinline__ uint32_t lane_rank(unsigned long long bal) {
+  const uint32_t lane = threadIdx.x & 63;
+  return (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
+}
+
+// base + the lanes of this block (MO_BLOCK threads, all of them here) before the calling one for which keep holds: where a stable compaction puts the lane's record
+__device__ __forceinline__ uint32_t block_rank(bool keep, uint32_t base) {
+  __shared__ uint32_t wk[MO_WAVES];
+  const uint32_t wave = threadIdx.x >> 6;
+  const unsigned long long bal = __ballot(keep);
+  if ((threadIdx.x & 63) == 0) wk[wave] = (uint32_t)__popcll(bal);
+  __syncthreads();
+#pragma unroll
+  for (int w = 0; w < MO_WAVES; w++) if ((uint32_t)w < wave) base += wk[w];
+  return base + lane_rank(bal);
+}
+
+// One block (MO_SCAN_BLOCK threads, all of them here): off[t] = the sum of cnt[0 .. t), t < nb.  Thread i scans the range [i chunk, (i + 1) chunk), the threads'
+// sums go through a wave scan and the waves in order.  cnt == off is allowed: a thread rewrites only the entries it summed.  Returns the sum up to the end of the
+// calling thread's range: in the last thread - its range ends at nb, empty or not - the sum of the row.
+__device__ __forceinline__ uint32_t scan_row(const uint32_t* cnt, uint32_t nb, uint32_t* off) {
   __shared__ uint32_t ws[MO_SCAN_BLOCK / 64];
   const uint32_t chunk = (nb + MO_SCAN_BLOCK - 1) / MO_SCAN_BLOCK;
   const uint32_t a = min(threadIdx.x * chunk, nb), b = min(a + chunk, nb);
@@ -88,34 +111,35 @@ __global__ void __launch_bounds__(MO_SCAN_BLOCK) k_mo_scan(const uint32_t* __res
   }
   __syncthreads();
   uint32_t run = ws[wv] + v - sum;
-  for (uint32_t t = a; t < b; t++) { off[t] = run; run += cnt[t]; }
-  if (threadIdx.x == MO_SCAN_BLOCK - 1) off[nb] = run;              // the last thread's range ends at nb
+  for (uint32_t t = a; t < b; t++) { const uint32_t u = cnt[t]; off[t] = run; run += u; }
+  return run;
 }
 
-// the block's kept records, in order, to kept[off[block] ..]
-__global__ void __launch_bounds__(MO_BLOCK) k_mo_compact(uint32_t n, const float4* __restrict__ map, const uint8_t* __restrict__ removed, const uint32_t* __restrict__ off,
-                                                         float4* __restrict__ kept) {
-  __shared__ uint32_t wk[MO_WAVES];
+// block r: row r of cnt (the rows nb apart) to its exclusive offsets in off, tot[r] = the row's sum.  One row with tot = off + nb: off[nb] is the total
+__global__ void __launch_bounds__(MO_SCAN_BLOCK) k_scan_rows(const uint32_t* cnt, uint32_t nb, uint32_t* off, uint32_t* tot) {
+  const uint32_t run = scan_row(cnt + (size_t)blockIdx.x * nb, nb, off + (size_t)blockIdx.x * nb);
+  if (threadIdx.x == MO_SCAN_BLOCK - 1) tot[blockIdx.x] = run;
+}
+
+// the block's kept records, in order, to kept[off[block] ..].  A template, like the call below, so that only a unit that filters the slot carries the kernel.
+template <typename R>
+__global__ void __launch_bounds__(MO_BLOCK) k_mo_compact(uint32_t n, const R* __restrict__ map, const uint8_t* __restrict__ removed, const uint32_t* __restrict__ off,
+                                                         R* __restrict__ kept) {
   const uint32_t i = blockIdx.x * MO_BLOCK + threadIdx.x;
-  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const bool keep = i < n && removed[i] == 0;
-  const float4 p = keep ? map[i] : make_float4(0.f, 0.f, 0.f, 0.f);
-  const unsigned long long bal = __ballot(keep);
-  if (lane == 0) wk[wave] = (uint32_t)__popcll(bal);
-  __syncthreads();
-  uint32_t before = off[blockIdx.x];
-#pragma unroll
-  for (int w = 0; w < MO_WAVES; w++) if ((uint32_t)w < wave) before += wk[w];
-  if (keep) kept[before + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull))] = p;
+  const R p = keep ? map[i] : R();
+  const uint32_t j = block_rank(keep, off[blockIdx.x]);
+  if (keep) kept[j] = p;
 }
 
-// The common end of the calls that filter the map slot: the `kept` records whose removed byte is 0, compacted by the offsets of k_mo_scan into d_kept (scratch),
+// The common end of the calls that filter the map slot: the `kept` records whose removed byte is 0, compacted by the offsets of k_scan_rows into d_kept (scratch),
 // become the slot.  From the shrink on the slot has changed: its generation advances, so every result computed from it - normals, an outlier classification,
 // the ground - is stale.
-inline int qn_kf_map_compact_shrink(qn_kf_store* s, const float4* map, uint32_t n, const uint8_t* d_removed, const uint32_t* d_off, float4* d_kept, uint32_t kept,
-                                    const float** d_xyzi_out, uint32_t* n_out) {
+template <typename R>
+int qn_kf_map_compact_shrink(qn_kf_store* s, const R* map, uint32_t n, const uint8_t* d_removed, const uint32_t* d_off, R* d_kept, uint32_t kept,
+                             const float** d_xyzi_out, uint32_t* n_out) {
   hipStream_t stream = qn_kf_int_stream(s);
-  hipLaunchKernelGGL(k_mo_compact, dim3((n + MO_BLOCK - 1) / MO_BLOCK), dim3(MO_BLOCK), 0, stream, n, map, d_removed, d_off, d_kept);
+  hipLaunchKernelGGL(k_mo_compact<R>, dim3((n + MO_BLOCK - 1) / MO_BLOCK), dim3(MO_BLOCK), 0, stream, n, map, d_removed, d_off, d_kept);
   QN_KFCHK(s, hipGetLastError());
   const int rc = qn_kf_int_map_shrink(s, d_kept, kept);
   if (rc != QN_OK) return rc;
@@ -124,6 +148,5 @@ inline int qn_kf_map_compact_shrink(qn_kf_store* s, const float4* map, uint32_t 
   *d_xyzi_out = (const float*)qn_kf_int_map(s, n_out, &gen);
   return QN_OK;
 }
-#endif  // QN_MAP_COUNTS_ONLY
 
 }  // namespace

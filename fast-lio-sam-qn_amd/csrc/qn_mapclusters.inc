@@ -6,7 +6,7 @@
 // ascending order of root; per cluster the box (f32 extremes in the order of the ordered-integer image, -0 < +0) and the int64 sums of xq = rint(x 2^e),
 // e = qn_quant_exponent(tolerance, 10), the product exact as the ground unit's zq.  The components of a graph depend on no schedule, the extremes and the
 // integer sums on no order: every byte equals the twin's whatever order the neighbours are met in or the unions happen, and a rerun gives the same bytes.
-//   members   class_mask != 0 only: k_mc_member / k_mo_scan / k_mc_pick compact the members stably into a scratch cloud with orig[] = their map indices, so
+//   members   class_mask != 0 only: k_mc_member / k_scan_rows / k_mc_pick compact the members stably into a scratch cloud with orig[] = their map indices, so
 //             the walk never gathers a class byte per candidate; stable, so "smaller cloud index <=> smaller map index" and the root rule survives.  With
 //             class_mask == 0 the cloud is the slot itself (the index puts the non-finite records behind the finite ones).
 //   index     qn_kf_int_cell_index (qn_cloud.hip) at radius = tolerance over that one cloud, k_cell_gather (qn_cell_walk.cuh, with the exactness argument).
@@ -26,9 +26,9 @@
 //             the map's own index; size by integer atomicAdd on the root's counter, one add per wave when its active lanes share a root (in cell-sorted order
 //             the common case), else one per lane.
 //   number    k_mc_number, one point per lane in the map's own order: ten counts a block (two five-predicate block_counts, k_slot_fold), the kept roots
-//             (root == own index, size in range) of every block for k_mo_scan, the largest size by a wave maximum and one atomicMax; k_mc_root_label gives
+//             (root == own index, size in range) of every block for k_scan_rows, the largest size by a wave maximum and one atomicMax; k_mc_root_label gives
 //             every kept root its rank - the cluster number - and every other root REJECTED; k_mc_finish copies label and size from the root to its members,
-//             writes NONE and the removed byte, and counts the records a drop keeps (k_mo_scan again: the offsets of the shared compaction).
+//             writes NONE and the removed byte, and counts the records a drop keeps (k_scan_rows again: the offsets of the shared compaction).
 //   info      after the counts are on the host (the list is sized from C): k_mc_info, one member per lane in the sorted order: atomicMin / atomicMax on the
 //             ordered-integer images of x, y, z and 64-bit integer atomicAdd of xq on the cluster's record, once per wave when its active lanes share a
 //             cluster, else per lane; k_mc_info_fin turns the images back into f32.  Integer atomics only.
@@ -86,24 +86,14 @@ __global__ void __launch_bounds__(MO_BLOCK) k_mc_member(uint32_t n, const float4
   block_count(blk + blockIdx.x, mem);
 }
 
-// the block's members, in order, to cloud[off[block] ..] with their map indices in orig (k_mo_compact's ranks)
+// the block's members, in order, to cloud[off[block] ..] with their map indices in orig
 __global__ void __launch_bounds__(MO_BLOCK) k_mc_pick(uint32_t n, const float4* __restrict__ map, const uint8_t* __restrict__ cls, uint32_t mask,
                                                       const uint32_t* __restrict__ off, float4* __restrict__ cloud, uint32_t* __restrict__ orig) {
-  __shared__ uint32_t wk[MO_WAVES];
   const uint32_t i = blockIdx.x * MO_BLOCK + threadIdx.x;
-  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const float4 p = i < n ? map[i] : make_float4(0.f, 0.f, 0.f, 0.f);
   const bool mem = i < n && mc_finite(p) && ((mask >> (cls[i] & 31u)) & 1u) != 0;
-  const unsigned long long bal = __ballot(mem);
-  if (lane == 0) wk[wave] = (uint32_t)__popcll(bal);
-  __syncthreads();
-  uint32_t before = off[blockIdx.x];
-#pragma unroll
-  for (int w = 0; w < MO_WAVES; w++) if ((uint32_t)w < wave) before += wk[w];
-  if (mem) {
-    const uint32_t d = before + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
-    cloud[d] = p; orig[d] = i;
-  }
+  const uint32_t d = block_rank(mem, off[blockIdx.x]);
+  if (mem) { cloud[d] = p; orig[d] = i; }
 }
 
 __global__ void __launch_bounds__(MO_BLOCK) k_mc_init(uint32_t nc, uint32_t* __restrict__ parent) {
@@ -193,19 +183,12 @@ __global__ void __launch_bounds__(MO_BLOCK) k_mc_number(uint32_t n, const float4
 // one record per lane: a kept root's label = its rank among the kept roots, every other root's REJECTED
 __global__ void __launch_bounds__(MO_BLOCK) k_mc_root_label(uint32_t n, const uint32_t* __restrict__ root, const uint32_t* __restrict__ size, uint32_t min_size,
                                                             uint32_t max_size, const uint32_t* __restrict__ off, int32_t* __restrict__ label) {
-  __shared__ uint32_t wk[MO_WAVES];
   const uint32_t i = blockIdx.x * MO_BLOCK + threadIdx.x;
-  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const bool isroot = i < n && root[i] == i;
   const uint32_t sz = isroot ? size[i] : 0u;
   const bool kept = isroot && sz >= min_size && sz <= max_size;
-  const unsigned long long bal = __ballot(kept);
-  if (lane == 0) wk[wave] = (uint32_t)__popcll(bal);
-  __syncthreads();
-  uint32_t before = off[blockIdx.x];
-#pragma unroll
-  for (int w = 0; w < MO_WAVES; w++) if ((uint32_t)w < wave) before += wk[w];
-  if (kept) label[i] = (int32_t)(before + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull)));
+  const uint32_t rank = block_rank(kept, off[blockIdx.x]);
+  if (kept) label[i] = (int32_t)rank;
   else if (isroot) label[i] = QN_CLUSTER_REJECTED;
 }
 
@@ -354,7 +337,7 @@ extern "C" int qn_kf_map_clusters(qn_kf_store* s, const qn_cluster_params* param
   const float4* cloud = map; const uint32_t* d_orig = nullptr; uint32_t nc = n;
   if (P.class_mask) {
     hipLaunchKernelGGL(k_mc_member, grid, block, 0, stream, n, map, d_cls, P.class_mask, d_blk);
-    hipLaunchKernelGGL(k_mo_scan, one, wide, 0, stream, (const uint32_t*)d_blk, nb, d_off);
+    hipLaunchKernelGGL(k_scan_rows, one, wide, 0, stream, (const uint32_t*)d_blk, nb, d_off, d_off + nb);
     QN_KFCHK(s, hipGetLastError());
     QN_KFCHK(s, hipMemcpyAsync(h, d_off + nb, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
     QN_KFCHK(s, hipStreamSynchronize(stream));           // the member count sizes the cloud
@@ -400,11 +383,11 @@ extern "C" int qn_kf_map_clusters(qn_kf_store* s, const qn_cluster_params* param
   hipLaunchKernelGGL(k_mc_number, grid, block, 0, stream, n, map, (const uint32_t*)o.root.p, (const uint32_t*)o.size.p, P.min_size, P.max_size, scale, d_w, d_blk,
                      d_sum + MC_STATS);
   hipLaunchKernelGGL((k_slot_fold<uint32_t, MC_STATS>), one, wide, 0, stream, (const uint32_t*)d_w, nb, d_sum);
-  hipLaunchKernelGGL(k_mo_scan, one, wide, 0, stream, (const uint32_t*)d_blk, nb, d_off);
+  hipLaunchKernelGGL(k_scan_rows, one, wide, 0, stream, (const uint32_t*)d_blk, nb, d_off, d_off + nb);
   hipLaunchKernelGGL(k_mc_root_label, grid, block, 0, stream, n, (const uint32_t*)o.root.p, (const uint32_t*)o.size.p, P.min_size, P.max_size, (const uint32_t*)d_off,
                      o.label.p);
   hipLaunchKernelGGL(k_mc_finish, grid, block, 0, stream, n, (const uint32_t*)o.root.p, o.size.p, o.label.p, o.removed.p, d_blk);
-  hipLaunchKernelGGL(k_mo_scan, one, wide, 0, stream, (const uint32_t*)d_blk, nb, o.off.p);
+  hipLaunchKernelGGL(k_scan_rows, one, wide, 0, stream, (const uint32_t*)d_blk, nb, o.off.p, o.off.p + nb);
   QN_KFCHK(s, hipGetLastError());
   QN_KFCHK(s, hipMemcpyAsync(h, d_sum, sizeof(uint32_t) * (MC_STATS + 1), hipMemcpyDeviceToHost, stream));
   QN_KFCHK(s, hipMemcpyAsync(h + 12, o.off.p + nb, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));

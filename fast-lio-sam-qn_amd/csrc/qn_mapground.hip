@@ -226,7 +226,7 @@ __global__ void __launch_bounds__(MG_BLOCK) k_mg_occ_count(uint32_t cells, const
   block_count(slots + 2 * (size_t)blockIdx.x, v == 2, v == 0);
 }
 
-// one point per lane: removed = the class's bit is not in the mask; the block's kept records into its slot (what k_mo_scan / k_mo_compact go on from)
+// one point per lane: removed = the class's bit is not in the mask; the block's kept records into its slot (what k_scan_rows / k_mo_compact go on from)
 __global__ void __launch_bounds__(MO_BLOCK) k_mg_keep_flag(uint32_t n, const uint8_t* __restrict__ cls, uint32_t mask, uint8_t* __restrict__ removed,
                                                            uint32_t* __restrict__ blk_kept) {
   const uint32_t i = blockIdx.x * MO_BLOCK + threadIdx.x;
@@ -433,7 +433,7 @@ extern "C" int qn_kf_map_keep_classes(qn_kf_store* s, uint32_t class_mask, const
   if (!d_kept || !d_removed || !d_blk || !h) return qn_kf_fail(s, "qn_kf_map_keep_classes: scratch allocation failed");
   uint32_t* d_off = d_blk + nb;
   hipLaunchKernelGGL(k_mg_keep_flag, dim3(nb), dim3(MO_BLOCK), 0, stream, n, (const uint8_t*)o->cls.p, class_mask, d_removed, d_blk);
-  hipLaunchKernelGGL(k_mo_scan, dim3(1), dim3(MO_SCAN_BLOCK), 0, stream, (const uint32_t*)d_blk, nb, d_off);
+  hipLaunchKernelGGL(k_scan_rows, dim3(1), dim3(MO_SCAN_BLOCK), 0, stream, (const uint32_t*)d_blk, nb, d_off, d_off + nb);
   QN_KFCHK(s, hipGetLastError());
   QN_KFCHK(s, hipMemcpyAsync(h, d_off + nb, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
   QN_KFCHK(s, hipStreamSynchronize(stream));

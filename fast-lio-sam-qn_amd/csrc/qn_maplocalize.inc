@@ -7,19 +7,17 @@
 //               k_ml_count    a block owns ML_BLOCK = 256 consecutive records, a thread loads its record once and tests it against the pass's centres (LDS, wave-uniform);
 //                             a centre's count of the block = ballot / popcount per wave, lane c keeping centre c's, the waves added through LDS into cnt[c][block];
 //                             any[block] = whether the block holds a member of any centre of the pass
-//               k_ml_scan     one block per centre, k_mo_scan's scheme in place: cnt[c][b] becomes the members of centre c before block b, tot[c] their number
+//               k_scan_rows   (qn_map_compact.cuh) one block per centre, in place: cnt[c][b] becomes the members of centre c before block b, tot[c] their number
 //               (one host read of tot sizes the crop block and its index buffer: crop c at base[c], the centres' totals added up in order)
 //               k_ml_compact  a block with any[block] == 0 returns before it loads a record; else the count kernel's tests again, a member of centre c going to
 //                             base[c] + cnt[c][block] + the members of the waves before + its ballot rank: ascending map index, no atomics, the same bytes on every run
 //   localise  host sequencing: the distinct crop centres (f32 bits of the guesses' translations) cropped once, each distinct query voxel-filtered alone in its
 //             sensor frame (qn_kf_int_voxel_each), the pairs grouped by query (stable) into ONE batched registration, the records scattered back to caller order
-// (the scheme is qn_map_compact.cuh's, generalised from one predicate to QN_ML_PASS per pass; that header is not included here - its kernels belong to the map
-// filters' two units - so the block sizes are restated)
+// (the scheme is qn_map_compact.cuh's, generalised from one predicate to QN_ML_PASS per pass: its scan kernel, its lane_rank, its block sizes)
 #define QN_ML_PASS 64
 #define QN_ML_MAX_CROPS 32767u
-#define ML_BLOCK 256
-#define ML_WAVES (ML_BLOCK / 64)
-#define ML_SCAN_BLOCK 1024
+#define ML_BLOCK MO_BLOCK
+#define ML_WAVES MO_WAVES
 
 int qn_ctx_int_max_points(const qn_ctx* c);
 // qn_coarse_to_fine_align_batch on one context (qn_quatro_host.inc) that also says how far each pair got: stage 0, 1 = T_quatro solved, 2 = the fine stage ran
@@ -72,31 +70,6 @@ __global__ void __launch_bounds__(ML_BLOCK) k_ml_count(uint32_t n, const float4*
   }
 }
 
-// block c: cnt[c][0 .. nb) from counts to exclusive offsets in place, tot[c] = their sum (k_mo_scan's scheme: thread i scans the blocks [i chunk, (i + 1) chunk),
-// the threads' sums through a wave scan and the waves in order; a thread rewrites only the entries it summed)
-__global__ void __launch_bounds__(ML_SCAN_BLOCK) k_ml_scan(uint32_t* cnt_all, uint32_t nb, uint32_t* __restrict__ tot) {
-  __shared__ uint32_t ws[ML_SCAN_BLOCK / 64];
-  uint32_t* cnt = cnt_all + (size_t)blockIdx.x * nb;
-  const uint32_t chunk = (nb + ML_SCAN_BLOCK - 1) / ML_SCAN_BLOCK;
-  const uint32_t a = min(threadIdx.x * chunk, nb), b = min(a + chunk, nb);
-  uint32_t sum = 0;
-  for (uint32_t t = a; t < b; t++) sum += cnt[t];
-  const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  uint32_t v = sum;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) { const uint32_t u = __shfl_up(v, o); if ((int)lane >= o) v += u; }
-  if (lane == 63) ws[wv] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint32_t acc = 0;
-    for (int w = 0; w < ML_SCAN_BLOCK / 64; w++) { const uint32_t u = ws[w]; ws[w] = acc; acc += u; }
-  }
-  __syncthreads();
-  uint32_t run = ws[wv] + v - sum;
-  for (uint32_t t = a; t < b; t++) { const uint32_t u = cnt[t]; cnt[t] = run; run += u; }
-  if (threadIdx.x == ML_SCAN_BLOCK - 1) tot[blockIdx.x] = run;          // the last thread's range ends at nb
-}
-
 __global__ void __launch_bounds__(ML_BLOCK) k_ml_compact(uint32_t n, const float4* __restrict__ map, const float4* __restrict__ ctr, uint32_t nc, float r2, uint32_t shape,
                                                          uint32_t nb, const uint32_t* __restrict__ off, const uint32_t* __restrict__ any,
                                                          const unsigned long long* __restrict__ base, float4* __restrict__ out, uint32_t* __restrict__ idx) {
@@ -126,7 +99,7 @@ __global__ void __launch_bounds__(ML_BLOCK) k_ml_compact(uint32_t n, const float
     const bool m = fin && ml_within(p, sc[c], r2, shape);
     const unsigned long long bal = __ballot(m);
     if (m) {
-      const unsigned long long dst = go[c] + wk[wave][c] + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
+      const unsigned long long dst = go[c] + wk[wave][c] + lane_rank(bal);
       out[dst] = p; idx[dst] = i;
     }
   }
@@ -164,7 +137,7 @@ int ml_crop(qn_kf_store* s, MlState& m, const float* centres, uint32_t nc, doubl
     const uint32_t c0 = ps * QN_ML_PASS, k = std::min<uint32_t>(QN_ML_PASS, nc - c0);
     hipLaunchKernelGGL(k_ml_count, dim3(nb), dim3(ML_BLOCK), 0, stream, n, map, m.ctr.p + c0, k, r2, shape, nb, m.cnt.p + (size_t)c0 * nb, m.any.p + (size_t)ps * nb);
   }
-  hipLaunchKernelGGL(k_ml_scan, dim3(nc), dim3(ML_SCAN_BLOCK), 0, stream, m.cnt.p, nb, m.tot.p);
+  hipLaunchKernelGGL(k_scan_rows, dim3(nc), dim3(MO_SCAN_BLOCK), 0, stream, (const uint32_t*)m.cnt.p, nb, m.cnt.p, m.tot.p);
   QN_KFCHK(s, hipGetLastError());
   std::vector<uint32_t> ht(nc);
   QN_KFCHK(s, hipMemcpyAsync(ht.data(), m.tot.p, sizeof(uint32_t) * nc, hipMemcpyDeviceToHost, stream));

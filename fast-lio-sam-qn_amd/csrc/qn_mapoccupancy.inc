@@ -14,16 +14,13 @@
 //             voxels further out are added to lane by lane; a lane stops after its last miss, n - shell steps, since the end voxel is known without walking.
 //   classify  k_oc_classify, one voxel per lane: the class byte, the three class counts (block_count) and the block's hit and miss sums (u64) into slots,
 //             k_slot_fold adds them up.  One host read.
-//   list      k_oc_list_flag / k_static_scan / k_oc_list_pick: the count, scan and compact idiom of qn_map_compact.cuh over the voxels in linear order, stable;
-//             the scan is this unit's own k_static_scan (the scheme k_mo_scan was taken from) without entries.
+//   list      k_oc_list_flag / k_scan_rows / k_oc_list_pick: the count, scan and rank idiom of qn_map_compact.cuh over the voxels in linear order, stable.
 //   slice     k_oc_slice, one column per lane.
 // Host synchronisations of qn_kf_map_occupancy: two - the extent, the counts.  Integer atomics only, no scratch memory, no dynamically indexed private array.
 // Part of qn_staticmap.hip's translation unit (included at its end), the unit that turns a list with poses into per-record ray evidence: the results hang on
 // that unit's StaticState and take no slot of their own.  They do not depend on the map slot.
 #include <climits>
 #include <cstdlib>
-#define QN_MAP_COUNTS_ONLY                              // block_count and k_slot_fold; the scan is this unit's own
-#include "qn_map_compact.cuh"
 
 namespace {
 
@@ -32,7 +29,6 @@ namespace {
 #define OC_ONE (1 << OC_S)
 #define OC_COORD_LIMIT 1048576.0                         // 2^20 voxels
 #define OC_MAX_SIDE (1u << 15)
-#define OC_CHUNK 32768u                                  // entries per launch (the grid's y dimension)
 #define OC_RAY 0
 #define OC_NONFINITE 1
 #define OC_NEAR 2
@@ -182,28 +178,20 @@ __global__ void __launch_bounds__(OC_BLOCK) k_oc_classify(uint32_t cells, const 
   }
 }
 
-// one voxel per lane: the block's voxels whose class bit is in the mask into its slot (what k_mo_scan goes on from)
+// one voxel per lane: the block's voxels whose class bit is in the mask into its slot (what k_scan_rows goes on from)
 __global__ void __launch_bounds__(MO_BLOCK) k_oc_list_flag(uint32_t cells, const uint8_t* __restrict__ cls, uint32_t mask, uint32_t* __restrict__ blk) {
   const uint32_t i = blockIdx.x * MO_BLOCK + threadIdx.x;
   block_count(blk + blockIdx.x, i < cells && ((mask >> cls[i]) & 1u) != 0);
 }
 
-// the block's listed voxels, in linear order, to ijk / hits / misses at off[block] .. (k_mo_compact's ranks)
+// the block's listed voxels, in linear order, to ijk / hits / misses at off[block] ..
 __global__ void __launch_bounds__(MO_BLOCK) k_oc_list_pick(uint32_t cells, const uint8_t* __restrict__ cls, uint32_t mask, const uint32_t* __restrict__ off,
                                                            const uint32_t* __restrict__ hits, const uint32_t* __restrict__ misses, uint32_t W, uint32_t H,
                                                            int32_t* __restrict__ ijk, uint32_t* __restrict__ h_out, uint32_t* __restrict__ m_out) {
-  __shared__ uint32_t wk[MO_WAVES];
   const uint32_t i = blockIdx.x * MO_BLOCK + threadIdx.x;
-  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const bool keep = i < cells && ((mask >> cls[i]) & 1u) != 0;
-  const unsigned long long bal = __ballot(keep);
-  if (lane == 0) wk[wave] = (uint32_t)__popcll(bal);
-  __syncthreads();
-  uint32_t before = off[blockIdx.x];
-#pragma unroll
-  for (int w = 0; w < MO_WAVES; w++) if ((uint32_t)w < wave) before += wk[w];
+  const size_t j = block_rank(keep, off[blockIdx.x]);
   if (keep) {
-    const size_t j = before + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
     const uint32_t row = i / W;
     ijk[3 * j] = (int32_t)(i - row * W); ijk[3 * j + 1] = (int32_t)(row % H); ijk[3 * j + 2] = (int32_t)(row / H);
     h_out[j] = hits[i]; m_out[j] = misses[i];
@@ -231,16 +219,6 @@ struct OccState {
 const OccState* oc_live(qn_kf_store* s) {
   const StaticState* st = (const StaticState*)qn_kf_int_ext(s, QN_KF_INT_EXT_STATIC);
   return st && st->occ && st->occ->live ? st->occ.get() : nullptr;
-}
-
-// the launches of a kernel over the entries, OC_CHUNK of them at a time: f(first entry, grid)
-template <typename F> void oc_each_chunk(const OcEntry* ent, uint32_t count, F f) {
-  for (uint32_t a = 0; a < count; a += OC_CHUNK) {
-    const uint32_t m = std::min<uint32_t>(OC_CHUNK, count - a);
-    uint32_t cmax = 0;
-    for (uint32_t k = 0; k < m; k++) cmax = std::max(cmax, ent[a + k].n);
-    if (cmax) f(a, dim3((cmax + OC_BLOCK - 1) / OC_BLOCK, m));
-  }
 }
 
 }  // namespace
@@ -303,7 +281,7 @@ extern "C" int qn_kf_map_occupancy(qn_kf_store* s, const int32_t* ids, const dou
   QN_KFCHK(s, hipMemcpyAsync(d_small, h_init, small_bytes, hipMemcpyHostToDevice, str));
   // ---- the extent
   if (nt) {
-    oc_each_chunk(ent.data(), count, [&](uint32_t a, dim3 grid) {
+    sv_each_chunk(ent.data(), count, OC_BLOCK, [&](uint32_t a, dim3 grid) {
       hipLaunchKernelGGL(k_oc_extent, grid, dim3(OC_BLOCK), 0, str, (const OcEntry*)(d_ent + a), inv, lo2, hi2, d_ext, d_slots);
     });
     hipLaunchKernelGGL((k_slot_fold<uint32_t, 5>), dim3(1), dim3(MO_SCAN_BLOCK), 0, str, (const uint32_t*)d_slots, nt, d_sums);
@@ -348,7 +326,7 @@ extern "C" int qn_kf_map_occupancy(qn_kf_store* s, const int32_t* ids, const dou
     QN_KFCHK(s, hipMemsetAsync(st->misses.p, 0, sizeof(uint32_t) * (size_t)cells, str));
     // ---- carve, classify and count
     const bool fold = getenv("QN_OCC_NO_FOLD") == nullptr;  // (a measuring switch: the results are the same bytes either way)
-    oc_each_chunk(ent.data(), count, [&](uint32_t a, dim3 grid) {
+    sv_each_chunk(ent.data(), count, OC_BLOCK, [&](uint32_t a, dim3 grid) {
       if (fold) hipLaunchKernelGGL(k_oc_carve<true>, grid, dim3(OC_BLOCK), 0, str, (const OcEntry*)(d_ent + a), inv, lo2, hi2, G, P.shell, st->hits.p, st->misses.p);
       else hipLaunchKernelGGL(k_oc_carve<false>, grid, dim3(OC_BLOCK), 0, str, (const OcEntry*)(d_ent + a), inv, lo2, hi2, G, P.shell, st->hits.p, st->misses.p);
     });
@@ -401,7 +379,7 @@ extern "C" int qn_kf_map_occupancy_list(qn_kf_store* s, uint32_t class_mask, uin
   if (!d_blk || !h) return qn_kf_fail(s, "qn_kf_map_occupancy_list: scratch allocation failed");
   uint32_t* d_off = d_blk + nb;
   hipLaunchKernelGGL(k_oc_list_flag, dim3(nb), dim3(MO_BLOCK), 0, str, cells, (const uint8_t*)o->cls.p, class_mask, d_blk);
-  hipLaunchKernelGGL(k_static_scan, dim3(1), dim3(SV_SCAN_BLOCK), 0, str, (const uint32_t*)d_blk, nb, d_off, (const SvEntry*)nullptr, 0u, (uint32_t*)nullptr);      // (no entries: the scan alone)
+  hipLaunchKernelGGL(k_scan_rows, dim3(1), dim3(MO_SCAN_BLOCK), 0, str, (const uint32_t*)d_blk, nb, d_off, d_off + nb);
   QN_KFCHK(s, hipGetLastError());
   QN_KFCHK(s, hipMemcpyAsync(h, d_off + nb, sizeof(uint32_t), hipMemcpyDeviceToHost, str));
   QN_KFCHK(s, hipStreamSynchronize(str));

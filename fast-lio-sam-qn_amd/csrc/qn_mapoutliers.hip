@@ -14,8 +14,8 @@
 //             sum run once per point after the scan.  dense, sum_q and sum_q2 are reduced over the wave by shuffles, over the block through LDS, and stored
 //             into the block's own slot; k_slot_fold adds the slots up.  No atomics.
 //   flag      k_mo_flag, one point per lane in the map's own order: removed = sparse or double(mean_q) > thr_q; the block's kept count into its slot;
-//             k_mo_scan (one block) turns the counts into offsets, the last one the number kept.
-//   compact   qn_kf_map_remove_outliers only: the shared end of the map's filters (qn_map_compact.cuh, with the count tail, the fold and the scan).
+//             k_scan_rows (one block) turns the counts into offsets, the last one the number kept.
+//   compact   qn_kf_map_remove_outliers only: the shared end of the map's filters (qn_map_compact.cuh, with the count tail, the fold, the scan and the rank).
 // Host synchronisations of a classify: the index's, one for the statistics (the threshold is host arithmetic), one at the end.  Results are committed only
 // on success (KfMapResults, qn_kf_buf.h), so a refused call leaves the previous classification as it was.
 // The map's other point filter, the clusters (qn_mapclusters.inc, included at the end), is part of this translation unit: it shares the index, the walk, the
@@ -192,7 +192,7 @@ extern "C" int qn_kf_map_outliers(qn_kf_store* s, const qn_outlier_params* param
     r.mean_q = mean; r.std_q = std::sqrt(var); r.thr_q = mean + params->std_mul * r.std_q;
   }
   hipLaunchKernelGGL(k_mo_flag, grid, dim3(MO_BLOCK), 0, stream, n, map, (const uint32_t*)o.count.p, (const uint32_t*)o.mean_q.p, k, r.thr_q, o.removed.p, d_blk);
-  hipLaunchKernelGGL(k_mo_scan, dim3(1), dim3(MO_SCAN_BLOCK), 0, stream, (const uint32_t*)d_blk, nb, o.off.p);
+  hipLaunchKernelGGL(k_scan_rows, dim3(1), dim3(MO_SCAN_BLOCK), 0, stream, (const uint32_t*)d_blk, nb, o.off.p, o.off.p + nb);
   QN_KFCHK(s, hipGetLastError());
   QN_KFCHK(s, hipMemcpyAsync(h_kept, o.off.p + nb, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
   QN_KFCHK(s, hipStreamSynchronize(stream));             // sync 3 of 3

@@ -7,10 +7,10 @@
 //   k_static_vote     grid (tiles, entries), one thread per record, the witness loop inside the thread: the record is read once, the 12 f64 of M and the image
 //                     slot of (entry, witness) come from a host-built table through wave-uniform loads, both counters stay in registers, the three bytes per
 //                     record (seen through, agree, removed) are written once; the tile's kept count by ballots and popcounts into its own slot.  No atomics.
-//   k_static_scan     one block: the exclusive scan of the tiles' kept counts in tile order (the entries' kept records end up back to back in list order), and each
-//                     entry's removed count.
+//   k_static_scan     one block: the exclusive scan of the tiles' kept counts in tile order (scan_row of qn_map_compact.cuh; the entries' kept records end up back
+//                     to back in list order), and each entry's removed count.
 //   k_static_compact  grid (tiles, entries): the kept records of a tile to its offset, in record order (ballot / popcount ranks inside a wave, the waves' and
-//                     rounds' counts in a fixed order through LDS): stable and the same on every run.
+//                     rounds' counts in a fixed order through LDS; lane_rank of qn_map_compact.cuh): stable and the same on every run.
 // The column table is staged in LDS up to 4096 columns and read from global memory above, as in qn_freespace.hip.
 // Host synchronisations: one per classify.  The map itself is the store's one voxel-grid pipeline over the kept records (qn_kf_int_build_map_from).
 #include <hip/hip_runtime.h>
@@ -23,13 +23,14 @@
 #include <vector>
 #include "../../include/qn_engine.h"
 #include "qn_range.cuh"
+#include "qn_map_compact.cuh"
 
 namespace {
 using namespace qn_range;
 
 #define SV_MAX_WITNESSES 255u                            // per entry: the u8 counters stay exact
-#define SV_CHUNK 32768u                                  // entries per launch (the grid's y dimension)
-#define SV_SCAN_BLOCK 1024
+#define SV_CHUNK 32768u                                  // entries per launch (the grid's y dimension), here and in qn_mapoccupancy.inc
+#define SV_SCAN_BLOCK MO_SCAN_BLOCK
 
 struct SvEntry { const float4* pts; uint32_t n, p0, w0, nw, b0, pad; };      // records, first record / witness row / tile of the entry
 struct SvWit { double M[12]; int32_t img; int32_t pad[3]; };                 // inv(P_w) P_e and the witness's image slot (its keyframe id); 112 bytes
@@ -84,29 +85,11 @@ __global__ void __launch_bounds__(FS_BLOCK) k_static_vote(const SvEntry* __restr
   }
 }
 
-// one block: off[t] = the kept records of the tiles before t (off[nt] = all), thread i scanning the tiles [i chunk, (i + 1) chunk), the threads' sums through a
-// wave scan and the waves in order; then removed[e] = n_e - the kept records of e's tiles
+// one block: off[t] = the kept records of the tiles before t, off[nt] = all (scan_row: qn_map_compact.cuh); then removed[e] = n_e - the kept records of e's tiles
 __global__ void __launch_bounds__(SV_SCAN_BLOCK) k_static_scan(const uint32_t* __restrict__ cnt, uint32_t nt, uint32_t* off, const SvEntry* __restrict__ ents,
                                                                 uint32_t count, uint32_t* __restrict__ removed) {
-  __shared__ uint32_t ws[SV_SCAN_BLOCK / 64];
-  const uint32_t chunk = (nt + SV_SCAN_BLOCK - 1) / SV_SCAN_BLOCK;
-  const uint32_t a = min(threadIdx.x * chunk, nt), b = min(a + chunk, nt);
-  uint32_t sum = 0;
-  for (uint32_t t = a; t < b; t++) sum += cnt[t];
-  const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  uint32_t v = sum;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) { const uint32_t u = __shfl_up(v, o); if ((int)lane >= o) v += u; }
-  if (lane == 63) ws[wv] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint32_t acc = 0;
-    for (int w = 0; w < SV_SCAN_BLOCK / 64; w++) { const uint32_t u = ws[w]; ws[w] = acc; acc += u; }
-  }
-  __syncthreads();
-  uint32_t run = ws[wv] + v - sum;
-  for (uint32_t t = a; t < b; t++) { off[t] = run; run += cnt[t]; }
-  if (threadIdx.x == SV_SCAN_BLOCK - 1) off[nt] = run;              // the last thread's range ends at nt
+  const uint32_t run = scan_row(cnt, nt, off);
+  if (threadIdx.x == SV_SCAN_BLOCK - 1) off[nt] = run;
   __syncthreads();
   for (uint32_t e = threadIdx.x; e < count; e += SV_SCAN_BLOCK) {
     const uint32_t n = ents[e].n, b0 = ents[e].b0, nb = (n + FS_TILE - 1) / FS_TILE;
@@ -138,11 +121,22 @@ __global__ void __launch_bounds__(FS_BLOCK) k_static_compact(const SvEntry* __re
     uint32_t before = acc;
 #pragma unroll
     for (int w = 0; w < FS_WAVES; w++) { const uint32_t c = cnt[it][w]; if ((uint32_t)w < wave) before += c; acc += c; }
-    if (keep[it]) kept[before + (uint32_t)__popcll(bal[it] & ((1ull << lane) - 1ull))] = p[it];
+    if (keep[it]) kept[before + lane_rank(bal[it])] = p[it];
   }
 }
 
 // ---------------------------------------------------------------------------------------------------------------- host side
+// the launches of a kernel over the entries (anything with the record count n), SV_CHUNK of them at a time: f(first entry, grid), the grid's x the tiles (of
+// `tile` records) of the chunk's largest entry; a chunk without a record is skipped
+template <typename E, typename F> void sv_each_chunk(const E* ent, uint32_t count, uint32_t tile, F f) {
+  for (uint32_t a = 0; a < count; a += SV_CHUNK) {
+    const uint32_t m = std::min<uint32_t>(SV_CHUNK, count - a);
+    uint32_t cmax = 0;
+    for (uint32_t k = 0; k < m; k++) cmax = std::max(cmax, ent[a + k].n);
+    if (cmax) f(a, dim3((cmax + tile - 1) / tile, m));
+  }
+}
+
 struct SvHostEntry { const float4* pts; uint32_t n; uint32_t p0; uint32_t kept_off, kept_n; uint8_t has_i; };
 // The store's static-map state (slot QN_KF_INT_EXT_STATIC): the list and poses of the latest classify, per record its three bytes (three planes of `total`
 // bytes: seen through, agree, removed) and the kept records of every entry back to back in list order.
@@ -233,26 +227,16 @@ extern "C" int qn_kf_static_classify(qn_kf_store* s, const int32_t* ids, const d
     const double2* cs = rs ? (const double2*)(rs->tab.p + range_cs_offset(p.n_rows)) : nullptr;
     const size_t lds = rs ? range_lds_bytes(rs) : 0;
     const uint32_t* img = rs ? rs->img.p : nullptr;
-    for (uint32_t a = 0; a < count; a += SV_CHUNK) {
-      const uint32_t m = std::min<uint32_t>(SV_CHUNK, count - a);
-      uint32_t cmax = 0;
-      for (uint32_t k = 0; k < m; k++) cmax = std::max(cmax, ent[a + k].n);
-      if (!cmax) continue;
-      const dim3 grid((cmax + FS_TILE - 1) / FS_TILE, m);
+    sv_each_chunk(ent.data(), count, FS_TILE, [&](uint32_t a, dim3 grid) {
       if (lds) hipLaunchKernelGGL(k_static_vote<true>, grid, dim3(FS_BLOCK), lds, str, (const SvEntry*)(d_ent + a), (const SvWit*)d_wit, trow, cs, p.n_rows, p.n_cols, p.min_range,
                                   (int)p.window_rows, (int)p.window_cols, p.tol_abs, p.tol_rel, img, params->min_see_through, params->agree_weight, d_st, d_ag, d_rm, d_tile);
       else hipLaunchKernelGGL(k_static_vote<false>, grid, dim3(FS_BLOCK), 0, str, (const SvEntry*)(d_ent + a), (const SvWit*)d_wit, trow, cs, p.n_rows, p.n_cols, p.min_range,
                               (int)p.window_rows, (int)p.window_cols, p.tol_abs, p.tol_rel, img, params->min_see_through, params->agree_weight, d_st, d_ag, d_rm, d_tile);
-    }
+    });
     hipLaunchKernelGGL(k_static_scan, dim3(1), dim3(SV_SCAN_BLOCK), 0, str, (const uint32_t*)d_tile, nt, d_tile + nt, (const SvEntry*)d_ent, count, d_rem);
-    for (uint32_t a = 0; a < count; a += SV_CHUNK) {
-      const uint32_t m = std::min<uint32_t>(SV_CHUNK, count - a);
-      uint32_t cmax = 0;
-      for (uint32_t k = 0; k < m; k++) cmax = std::max(cmax, ent[a + k].n);
-      if (!cmax) continue;
-      hipLaunchKernelGGL(k_static_compact, dim3((cmax + FS_TILE - 1) / FS_TILE, m), dim3(FS_BLOCK), 0, str, (const SvEntry*)(d_ent + a), (const uint8_t*)d_rm,
-                         (const uint32_t*)(d_tile + nt), st->kept.p);
-    }
+    sv_each_chunk(ent.data(), count, FS_TILE, [&](uint32_t a, dim3 grid) {
+      hipLaunchKernelGGL(k_static_compact, grid, dim3(FS_BLOCK), 0, str, (const SvEntry*)(d_ent + a), (const uint8_t*)d_rm, (const uint32_t*)(d_tile + nt), st->kept.p);
+    });
     QN_KFCHK(s, hipGetLastError());
     QN_KFCHK(s, hipMemcpyAsync(h_rem, d_rem, rem_bytes, hipMemcpyDeviceToHost, str));
   } else {

@@ -18,6 +18,7 @@
 #include <vector>
 #include "../../include/qn_engine.h"
 #include "qn_kf_buf.h"
+#include "qn_map_compact.cuh"
 
 int qn_ctx_int_device(const qn_ctx* c);
 

@@ -12,7 +12,7 @@ from qn_amd import engine, mapground as mg
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMBOLS = ["qn_ground_default_params", "qn_kf_map_ground", "qn_kf_map_ground_points", "qn_kf_map_ground_grid", "qn_kf_map_keep_classes"]
 KERNELS = ("k_mg_extent", "k_mg_extent_sum", "k_mg_bin", "k_mg_seed", "k_mg_relax", "k_mg_classify", "k_mg_occ_count", "k_slot_fold<unsigned int, 1>",
-           "k_slot_fold<unsigned int, 2>", "k_slot_fold<unsigned int, 5>", "k_mg_keep_flag", "k_mo_scan", "k_mo_compact")
+           "k_slot_fold<unsigned int, 2>", "k_slot_fold<unsigned int, 5>", "k_mg_keep_flag", "k_scan_rows", "k_mo_compact<HIP_vector_type<float, 4u> >")
 
 
 def test_header_declares_and_library_exports_the_api():
@@ -89,14 +89,17 @@ def test_the_kernels_have_no_scratch_and_no_spills():
         rows = [l for l in out.splitlines() if "::" + k + "(" in l]
         assert rows, k
         assert all(int(l.split()[0]) == 0 and " spill   0 " in l for l in rows), rows
-    assert len([l for l in out.splitlines() if "::k_mo_scan(" in l]) == 2          # one source, two units: the outlier filter's and this one's
+    # one source: the scan in the four units that launch it (qn_mapoutliers, qn_mapground, qn_staticmap, qn_verify), the record compaction only in the two that
+    # filter the slot - the static-map unit, which lists voxels, carries none
+    assert len([l for l in out.splitlines() if "::k_scan_rows(" in l]) == 4 and len([l for l in out.splitlines() if "::k_mo_compact<" in l]) == 2
 
 
 def test_no_floating_point_in_the_kernels_behind_the_quantisation():
-    """only the extent and the bin kernels (before and at the quantisation) may name a floating-point type; the count tail and the fold of the slots that the
-    others share live in qn_map_compact.cuh"""
+    """only the extent and the bin kernels (before and at the quantisation) may name a floating-point type; the count tail, the fold of the slots, the scan and the rank that
+    the others share live in qn_map_compact.cuh"""
     src = "".join(open(os.path.join(ROOT, "fast-lio-sam-qn_amd", "csrc", f)).read() for f in ("qn_map_compact.cuh", "qn_mapground.hip"))
-    for k in ("k_mg_seed", "k_mg_relax", "k_mg_classify", "k_mg_occ_count", "k_slot_fold", "block_count", "k_mg_keep_flag"):
+    for k in ("k_mg_seed", "k_mg_relax", "k_mg_classify", "k_mg_occ_count", "k_slot_fold", "block_count", "k_mg_keep_flag", "lane_rank", "block_rank", "scan_row",
+              "k_scan_rows"):
         i = src.index(" " + k + "(")
         body = src[i:src.index("\n}\n", i)]
         assert not re.search(r"\b(float|double|float4)\b", body), k

@@ -97,7 +97,7 @@ def test_the_crop_kernels_have_no_scratch():
     from qn_amd import build
     build.build()
     out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "scratch_report.py"), "--all"], capture_output=True, text=True, check=True).stdout
-    for k in ("k_ml_count", "k_ml_scan", "k_ml_compact"):
+    for k in ("k_ml_count", "k_scan_rows", "k_ml_compact"):
         rows = [l for l in out.splitlines() if k in l]
         assert rows, k
         assert all(int(l.split()[0]) == 0 and " spill   0 " in l for l in rows), rows

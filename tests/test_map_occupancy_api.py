@@ -12,7 +12,7 @@ from qn_amd import engine, mapoccupancy as mo
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "fast-lio-sam-qn_amd", "csrc")
 SYMBOLS = ["qn_occupancy_default_params", "qn_kf_map_occupancy", "qn_kf_map_occupancy_grid", "qn_kf_map_occupancy_list", "qn_kf_map_occupancy_slice"]
-KERNELS = ("k_oc_extent", "k_oc_carve<true>", "k_oc_carve<false>", "k_oc_classify", "k_oc_list_flag", "k_oc_list_pick", "k_oc_slice", "k_static_scan",
+KERNELS = ("k_oc_extent", "k_oc_carve<true>", "k_oc_carve<false>", "k_oc_classify", "k_oc_list_flag", "k_oc_list_pick", "k_oc_slice", "k_scan_rows",
            "k_slot_fold<unsigned int, 5>", "k_slot_fold<unsigned int, 3>", "k_slot_fold<unsigned long long, 2>")
 
 

@@ -74,7 +74,7 @@ def test_the_selection_kernels_have_no_scratch():
     from qn_amd import build
     build.build()
     out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "scratch_report.py"), "--all"], capture_output=True, text=True, check=True).stdout
-    for k in ("k_map_outliers<8>", "k_map_outliers<16>", "k_map_outliers<32>", "k_mo_flag", "k_mo_scan", "k_mo_compact", "k_slot_fold<unsigned long long, 3>",
+    for k in ("k_map_outliers<8>", "k_map_outliers<16>", "k_map_outliers<32>", "k_mo_flag", "k_scan_rows", "k_mo_compact", "k_slot_fold<unsigned long long, 3>",
               "k_cell_gather"):
         rows = [l for l in out.splitlines() if k in l]
         assert rows, k
