@@ -808,6 +808,35 @@ QN_OCC_UNKNOWN, QN_OCC_FREE, QN_OCC_OCCUPIED = range(3)
 QN_OCC_MAX_CELLS = 1 << 27
 
 
+class DistanceParams(C.Structure):
+    """qn_distance_params (16 bytes): the classes that count as sites (bit 1 << class) and the largest distance, in voxels, the field resolves.  The defaults
+    are interface choices, not measurements."""
+    _fields_ = [("site_mask", C.c_uint32), ("max_dist", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+    def __init__(self, site_mask=1 << QN_OCC_OCCUPIED, max_dist=16):
+        super().__init__(site_mask, max_dist)
+
+    def twin(self):
+        """-> the mapdistance.DistanceParams with these values"""
+        from . import mapdistance
+        return mapdistance.DistanceParams(int(self.site_mask), int(self.max_dist))
+
+
+class DistanceStats(C.Structure):
+    """qn_distance_stats (32 bytes): every field is an integer the twin shares"""
+    _fields_ = [("sites", C.c_uint32), ("reached", C.c_uint32), ("far", C.c_uint32), ("max_d2", C.c_uint32), ("sum_d2", C.c_uint64), ("reserved", C.c_uint32 * 2)]
+
+    def twin(self):
+        """-> the mapdistance.DistanceStats with these values"""
+        from . import mapdistance
+        return mapdistance.DistanceStats(int(self.sites), int(self.reached), int(self.far), int(self.max_d2), int(self.sum_d2))
+
+
+QN_DIST_FAR = 0xffff
+QN_DIST_MAX_RADIUS = 255
+QN_DIST_OUTSIDE = 0xff
+
+
 class ClusterParams(C.Structure):
     """qn_cluster_params (24 bytes): the joining distance, the smallest and the largest component that is a cluster, and the ground classes that take part
     (0: every finite point).  The defaults are interface choices, not measurements."""
@@ -1496,6 +1525,48 @@ class KeyframeStore:
         out = np.zeros(max(W * H, 1), np.uint8)
         self._check(self._l.qn_kf_map_occupancy_slice(self.h, C.c_int32(int(iz_lo)), C.c_int32(int(iz_hi)), _p(out)))
         return out[:W * H].reshape(H, W)
+
+    # ---- the occupancy map's Euclidean distance field (qn_kf_map_distance / _grid / _slice / _query; numpy twin: qn_amd/mapdistance.py)
+    def map_distance(self, params=None):
+        """qn_kf_map_distance over the class bytes of the latest map_occupancy: per voxel the squared distance, in voxels, to the nearest voxel whose class bit
+        is in site_mask, QN_DIST_FAR beyond max_dist.  params: a DistanceParams (or a mapdistance.DistanceParams); None: the defaults.  -> stats, a dict of the
+        fields of qn_distance_stats, equal to those of mapdistance.transform of the downloaded classes.  map_distance_grid / _slice / _query serve the field."""
+        p = DistanceParams() if params is None else params
+        if not isinstance(p, DistanceParams):
+            p = DistanceParams(int(p.site_mask), int(p.max_dist))
+        st = DistanceStats()
+        self._check(self._l.qn_kf_map_distance(self.h, C.byref(p), C.byref(st)))
+        return {f: int(getattr(st, f)) for f, _ in DistanceStats._fields_ if f != "reserved"}
+
+    def map_distance_grid(self):
+        """qn_kf_map_distance_grid -> (info, params, d2 (D, H, W) uint16) of the latest map_distance: info the occupancy grid's dict (map_occupancy_grid),
+        params a dict of site_mask and max_dist"""
+        g = OccupancyGrid(); p = DistanceParams()
+        self._check(self._l.qn_kf_map_distance_grid(self.h, C.byref(g), C.byref(p), None))
+        W, H, D = int(g.width), int(g.height), int(g.depth)
+        n = W * H * D
+        d2 = np.zeros(max(n, 1), np.uint16)
+        self._check(self._l.qn_kf_map_distance_grid(self.h, C.byref(g), C.byref(p), _p(d2)))
+        return self._occupancy_info(g), dict(site_mask=int(p.site_mask), max_dist=int(p.max_dist)), d2[:n].reshape(D, H, W)
+
+    def map_distance_slice(self, iz_lo, iz_hi):
+        """qn_kf_map_distance_slice -> (H, W) uint16: per column the smallest d2 over the layers iz_lo .. iz_hi (inclusive, clipped to the grid), QN_DIST_FAR
+        when the band misses the grid: the clearance of an upright body spanning those layers"""
+        g = OccupancyGrid(); p = DistanceParams()
+        self._check(self._l.qn_kf_map_distance_grid(self.h, C.byref(g), C.byref(p), None))
+        W, H = int(g.width), int(g.height)
+        out = np.zeros(max(W * H, 1), np.uint16)
+        self._check(self._l.qn_kf_map_distance_slice(self.h, C.c_int32(int(iz_lo)), C.c_int32(int(iz_hi)), _p(out)))
+        return out[:W * H].reshape(H, W)
+
+    def map_distance_query(self, xyz):
+        """qn_kf_map_distance_query: world points (n, 3) f64 -> (d2 (n,) uint16, class (n,) uint8) of the voxel each falls in; QN_DIST_FAR and QN_DIST_OUTSIDE
+        for a point that is not finite or outside the grid"""
+        xyz = np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
+        n = len(xyz)
+        d2 = np.zeros(max(n, 1), np.uint16); cls = np.zeros(max(n, 1), np.uint8)
+        self._check(self._l.qn_kf_map_distance_query(self.h, _p(xyz), C.c_uint32(n), _p(d2), _p(cls)))
+        return d2[:n], cls[:n]
 
     # ---- the map slot's points clustered into objects (qn_kf_map_clusters / _cluster_points / _cluster_list / qn_kf_map_drop_rejected_clusters; numpy twin:
     # qn_amd/mapclusters.py)

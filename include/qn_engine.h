@@ -781,6 +781,46 @@ int  qn_kf_map_occupancy(qn_kf_store*, const int32_t* ids, const double* poses16
 int  qn_kf_map_occupancy_grid(qn_kf_store*, qn_occupancy_grid* info_out, uint32_t* hits_out, uint32_t* misses_out, uint8_t* class_out);
 int  qn_kf_map_occupancy_list(qn_kf_store*, uint32_t class_mask, uint32_t* n_out, int32_t* ijk_out, uint32_t* hits_out, uint32_t* misses_out);
 int  qn_kf_map_occupancy_slice(qn_kf_store*, int32_t iz_lo, int32_t iz_hi, uint8_t* occupancy_out /* W x H, y slow */);
+/* ---- the occupancy map's Euclidean distance field (csrc/qn_mapdistance.inc, part of csrc/qn_staticmap.hip; numpy twin and specification: qn_amd/mapdistance.py)
+ * What a planner asks of an occupancy map first: how far is this place from the nearest obstacle - for the collision check of a trajectory, an inflated
+ * costmap, the clearance of a body of some height.  These calls run an exact Euclidean distance transform over the resident class bytes of the live
+ * qn_kf_map_occupancy result, W x H x D voxels with x fastest, and keep the field on the device.  Everything is an integer and equal to the twin's bit for bit;
+ * only the distance is returned, not the nearest site, so there is no tie to break.
+ * Sites: a voxel whose class bit (1 << class) is set in site_mask.  1 << QN_OCC_OCCUPIED is the default; (1 << QN_OCC_OCCUPIED) | (1 << QN_OCC_UNKNOWN) is
+ *   the conservative planner's choice, unknown space as an obstacle.  Nothing outside the grid is a site.
+ * Field, one uint16_t per voxel: d2[v] = min over sites s of (vx - sx)^2 + (vy - sy)^2 + (vz - sz)^2 in voxel units; a site has d2 = 0; QN_DIST_FAR
+ *   (0xffff) when that minimum exceeds max_dist^2 or there is no site.  max_dist <= QN_DIST_MAX_RADIUS = 255, so d2 <= 65025 < QN_DIST_FAR.  The distance in
+ *   metres is sqrt(d2) * voxel, host arithmetic.
+ * Passes: three, along x, y and z, each a windowed minimum of half-width max_dist that treats an intermediate value above max_dist^2 as infinite.  That is
+ *   exact under the cap: a site within max_dist has every per-axis offset <= max_dist.  No atomics, no floating point outside the query's quantisation.
+ * qn_distance_params (16 bytes): site_mask (bits 0 .. 2, not 0; default 1 << QN_OCC_OCCUPIED), max_dist (1 .. 255 voxels; default 16), reserved[2] (0).  The
+ *   defaults are interface choices, not measurements.
+ * qn_distance_stats (32 bytes): sites, reached (the voxels that are no site and have d2 <= max_dist^2), far (the rest): sites + reached + far == W H D;
+ *   max_d2 and sum_d2 (u64) over the reached voxels, 0 when there are none; reserved[2] (0).
+ * qn_kf_map_distance: QN_ERR_INVALID_ARG, before anything runs and with the previous field intact: a null pointer, site_mask 0 or with a bit >= 3, max_dist
+ *   0 or > 255, reserved != 0.  QN_ERR_NOT_READY without a live occupancy result.  A 0 x 0 x 0 grid succeeds with zero statistics.  Device memory: two grids
+ *   of at least 2 W H D bytes, the field and one temporary (grown half again as large, kept between calls); when they cannot be allocated QN_ERR_HIP with the previous field intact.  The field stays resident until
+ *   the next successful qn_kf_map_distance or the next successful qn_kf_map_occupancy; the latter ends it and the getters answer QN_ERR_NOT_READY again.  A
+ *   refused call of either leaves the field intact.  One host synchronisation: the statistics.
+ * qn_kf_map_distance_grid: *info_out (the occupancy grid's), *params_out (the parameters used) and d2_out, W H D values of 2 bytes; d2_out may be NULL to
+ *   fetch the dimensions first.  QN_ERR_NOT_READY without a live field.  One host synchronisation.
+ * qn_kf_map_distance_slice: d2_out (W x H values of 2 bytes, row-major with y the slow axis) - per column the smallest d2 over the layers iz_lo .. iz_hi
+ *   inclusive, clipped to the grid: the 3-D clearance of an upright body spanning those layers.  QN_DIST_FAR when the band misses the grid.
+ *   QN_ERR_INVALID_ARG when iz_lo > iz_hi or a pointer is null.  QN_ERR_NOT_READY as above.  One host synchronisation.
+ * qn_kf_map_distance_query: n world points (xyz, 3 f64 each) go to their voxel by the occupancy map's own arithmetic, c_k = ((int64) rint((x_k * inv) *
+ *   1024.0) >> 10) - minc_k with inv = 1.0 / voxel, no contraction, half to even.  d2_out[i] is the field's value there, class_out[i] the voxel's class.  A
+ *   point that is not finite, has |x_k * inv| >= 2^20, or falls outside the grid gets QN_DIST_FAR and QN_DIST_OUTSIDE (0xff).  QN_ERR_INVALID_ARG: n == 0 or
+ *   a null pointer.  QN_ERR_NOT_READY as above.  One lane per point: an upload of 24 n bytes, one kernel, a download of 3 n bytes; one host synchronisation. */
+#define QN_DIST_FAR 0xffffu
+#define QN_DIST_MAX_RADIUS 255u
+#define QN_DIST_OUTSIDE 0xffu
+typedef struct qn_distance_params { uint32_t site_mask, max_dist, reserved[2]; } qn_distance_params;                                    /* 16 bytes */
+typedef struct qn_distance_stats  { uint32_t sites, reached, far, max_d2; uint64_t sum_d2; uint32_t reserved[2]; } qn_distance_stats;  /* 32 bytes */
+void qn_distance_default_params(qn_distance_params* p);
+int  qn_kf_map_distance(qn_kf_store*, const qn_distance_params* params, qn_distance_stats* stats_out);
+int  qn_kf_map_distance_grid(qn_kf_store*, qn_occupancy_grid* info_out, qn_distance_params* params_out, uint16_t* d2_out);
+int  qn_kf_map_distance_slice(qn_kf_store*, int32_t iz_lo, int32_t iz_hi, uint16_t* d2_out /* W x H, y slow */);
+int  qn_kf_map_distance_query(qn_kf_store*, const double* xyz, uint32_t n, uint16_t* d2_out, uint8_t* class_out);
 /* ---- the map's points clustered into objects (csrc/qn_mapclusters.inc, part of csrc/qn_mapoutliers.hip; numpy twin and specification: qn_amd/mapclusters.py)
  * After qn_kf_map_ground every point is GROUND, OBSTACLE or OVERHEAD, but the obstacles are an unstructured set.  These calls run PCL's
  * EuclideanClusterExtraction over the store's map slot on the GPU: connected components of the radius graph, each with a size, a box and a centroid, and the

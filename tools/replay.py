@@ -242,8 +242,10 @@ def write_pcd_voxels(path, centres, hits, misses):
 def write_occupancy(save_dir, result, slice_z=None):
     """the 3-D occupancy map `result` (the dict of qn_amd/mapoccupancy.classify, or the GPU's arrays in the same form) as occupied.pcd - the centres of the
     occupied voxels with their hits and misses - and, with slice_z = (z_lo, z_hi) in metres, occupancy_slice.pgm / .yaml: the layers those heights fall in,
-    flattened (mapground.to_pgm / map_yaml: here free means that a ray passed) -> the layers (iz_lo, iz_hi) or None"""
-    from qn_amd import mapground, mapoccupancy
+    flattened (mapground.to_pgm / map_yaml: here free means that a ray passed); with result["d2_slice"] (the distance field's slice2d) and
+    result["robot_radius"] in metres also occupancy_inflated.pgm / .yaml, the slice with every column occupied whose clearance over those layers is at most the
+    radius: d2 <= floor((radius / voxel)^2) (mapdistance.inflate) -> the layers (iz_lo, iz_hi) or None"""
+    from qn_amd import mapdistance, mapground, mapoccupancy
     g = mapoccupancy.OccupancyGrid(*result["grid"])
     ijk, hits, misses = mapoccupancy.voxel_list(result, 1 << mapoccupancy.OCCUPIED)
     write_pcd_voxels(os.path.join(save_dir, "occupied.pcd"), mapoccupancy.centres(ijk, g), hits, misses)
@@ -252,6 +254,10 @@ def write_occupancy(save_dir, result, slice_z=None):
     lo, hi = mapoccupancy.layer_of(slice_z[0], g), mapoccupancy.layer_of(slice_z[1], g)
     occ = result["slice"](lo, hi) if "slice" in result else mapoccupancy.slice2d(result["classes"], lo, hi)
     write_grid(save_dir, "occupancy_slice", mapground.GridInfo(g.origin[0], g.origin[1], g.voxel, g.width, g.height, 0), occ)
+    if "d2_slice" in result:                                                                      # the slice inflated by the robot's radius
+        r2 = int(np.floor((float(result["robot_radius"]) / float(g.voxel)) ** 2))
+        d2 = result["d2_slice"](lo, hi)
+        write_grid(save_dir, "occupancy_inflated", mapground.GridInfo(g.origin[0], g.origin[1], g.voxel, g.width, g.height, 0), mapdistance.inflate(occ, d2, r2))
     return lo, hi
 
 
@@ -348,7 +354,7 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
         outlier_radius=1.0, outlier_k=8, outlier_std=2.0, occupancy_grid=False, grid_cell=0.5, max_slope=0.3, ground_tol=0.2, clearance=2.0,
         drop_ground=False, map_clusters=False, cluster_tol=0.5, cluster_min=10, cluster_max=0xffffffff, drop_small_clusters=False,
         localize_every=0, localize_radius=35.0, localize_shift=0.5, localize_yaw=3.0, occupancy_3d=False, occ_voxel=0.3, occ_min_range=0.5,
-        occ_max_range=60.0, occ_shell=1, occ_slice=None):
+        occ_max_range=60.0, occ_shell=1, occ_slice=None, occ_distance=False, occ_dist_max=16, occ_unknown_obstacle=False, robot_radius=None):
     """sensor = "uniform": keyframe clouds sampled uniformly by area inside a disc (make_stream); "spinning": ray-cast spinning-LiDAR
     scans from the ground-truth poses of the same figure-8 (make_lidar_stream).  detector = "radius": the candidate is the closest older
     keyframe within `radius` of the corrected position (LC:34-56); "scancontext": the older keyframe nearest by Scan Context distance, kept
@@ -420,6 +426,11 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
     FIELDS x y z hits misses.  occ_slice = (z_lo, z_hi) in metres: also occupancy_slice.pgm / .yaml, the layers of those heights flattened to the grid a planner
     loads (occupied where any voxel is, else free where a ray passed, else unknown).  out["occupancy"]: rays, total_misses, width, height, depth, occupied, free,
     unknown, and slice_layers with occ_slice.
+    occ_distance (with occupancy_3d; default False): the exact Euclidean distance field of that volume (qn_amd/mapdistance.py: per voxel the squared distance in
+    voxels to the nearest occupied voxel - with occ_unknown_obstacle to the nearest occupied or unknown one - up to occ_dist_max voxels), on the GPU backend by
+    KeyframeStore.map_distance, on the oracle backend by the numpy twin.  out["distance"]: sites, reached, far, max_d2, sum_d2, site_mask, max_dist.
+    robot_radius = M metres (with occ_distance and occ_slice): also occupancy_inflated.pgm / .yaml, the slice with every column occupied whose clearance over
+    the slice's layers is at most M: d2 <= floor((M / occ_voxel)^2).
     moving_boxes = N (sensor="spinning" only; default 0: every run is what it was): N extra boxes in the scene that stand somewhere else in every keyframe
     (moving_box_prims), so every keyframe is cast by a call of its own."""
     if detector not in ("radius", "scancontext"):
@@ -486,6 +497,14 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
         mapoccupancy.check_params(occ_params)                                                     # (raises ValueError on a parameter outside its range)
         if occ_slice is not None and not (len(occ_slice) == 2 and np.isfinite(occ_slice).all() and occ_slice[0] <= occ_slice[1]):
             raise ValueError("occ_slice must be two finite heights z_lo <= z_hi, not %r" % (occ_slice,))
+    if (occ_distance or robot_radius is not None or occ_unknown_obstacle) and not (occupancy_3d and occ_distance):
+        raise ValueError("occ_distance needs occupancy_3d, and occ_unknown_obstacle and robot_radius need occ_distance (the field is computed from its volume)")
+    if occ_distance:
+        from qn_amd import mapdistance
+        dist_params = mapdistance.DistanceParams((1 << mapoccupancy.OCCUPIED) | ((1 << mapoccupancy.UNKNOWN) if occ_unknown_obstacle else 0), occ_dist_max)
+        mapdistance.check_params(dist_params)                                                     # (raises ValueError on a parameter outside its range)
+        if robot_radius is not None and not (np.isfinite(robot_radius) and robot_radius >= 0.0):
+            raise ValueError("robot_radius must be finite and >= 0, not %r" % (robot_radius,))
     if drop_small_clusters and not map_clusters:
         raise ValueError("drop_small_clusters needs map_clusters (the clumps come from its components)")
     if map_clusters and backend != "gpu":
@@ -782,6 +801,17 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
             else:
                 res = mapoccupancy.classify(scans, corrected, occ_params)
                 st = res["stats"]._asdict()
+            if occ_distance:
+                if backend == "gpu":
+                    dst = store.map_distance(engine.DistanceParams(*dist_params))
+                    d2_slice = store.map_distance_slice
+                else:
+                    field = mapdistance.transform(res["classes"], dist_params)
+                    dst = field["stats"]._asdict()
+                    d2_slice = lambda lo, hi: mapdistance.slice2d(field["d2"], lo, hi)
+                out["distance"] = dict({k: int(dst[k]) for k in mapdistance.DistanceStats._fields}, site_mask=int(dist_params.site_mask), max_dist=int(dist_params.max_dist))
+                if robot_radius is not None:
+                    res["d2_slice"] = d2_slice; res["robot_radius"] = float(robot_radius)
             layers = write_occupancy(save_dir, res, occ_slice)
             out["occupancy"] = {k: int(st[k]) for k in ("n_rays", "total_misses", "width", "height", "depth", "occupied", "free", "unknown")}
             if layers is not None:
@@ -939,6 +969,12 @@ if __name__ == "__main__":
     ap.add_argument("--occ-shell", type=int, default=1, help="with --occupancy-3d: the voxels before a ray's end that it does not carve")
     ap.add_argument("--occ-slice", type=float, nargs=2, default=None, metavar=("ZLO", "ZHI"),
                     help="with --occupancy-3d: also write occupancy_slice.pgm / .yaml, the layers between these heights [m] flattened")
+    ap.add_argument("--occ-distance", action="store_true",
+                    help="with --occupancy-3d: also compute the volume's Euclidean distance field (per voxel the distance to the nearest occupied voxel)")
+    ap.add_argument("--occ-dist-max", type=int, default=16, help="with --occ-distance: the largest distance the field resolves [voxels, 1 .. 255]")
+    ap.add_argument("--occ-unknown-obstacle", action="store_true", help="with --occ-distance: unknown voxels are obstacles too")
+    ap.add_argument("--robot-radius", type=float, default=None, metavar="M",
+                    help="with --occ-distance and --occ-slice: also write occupancy_inflated.pgm / .yaml, the slice inflated by this radius [m]")
     ap.add_argument("--moving-boxes", type=int, default=0, help="with --sensor spinning: this many boxes that stand somewhere else in every keyframe")
     ap.add_argument("--backend", choices=["gpu", "oracle"], default="gpu", help="the engine on the GPU, or the CPU oracle")
     a = ap.parse_args()
@@ -958,6 +994,10 @@ if __name__ == "__main__":
         ap.error("--occupancy-3d needs --save-dir")
     if a.occ_slice is not None and not a.occupancy_3d:
         ap.error("--occ-slice needs --occupancy-3d")
+    if a.occ_distance and not a.occupancy_3d:
+        ap.error("--occ-distance needs --occupancy-3d")
+    if (a.occ_unknown_obstacle or a.robot_radius is not None) and not a.occ_distance:
+        ap.error("--occ-unknown-obstacle and --robot-radius need --occ-distance")
     run(a.keyframes, a.seed, a.quatro, save_dir=a.save_dir, save_map_leaf=a.save_map_leaf, sensor=a.sensor, detector=a.detector, yaw_bias=a.yaw_bias,
         verify=a.verify, sc_top_k=a.sc_top_k, backend=a.backend, loop_every=a.loop_every, catch_up=a.catch_up, submap_matching=a.submap_matching,
         min_overlap=a.min_overlap, overlap_radius=a.overlap_radius, max_see_through=a.max_see_through, static_map=a.static_map, moving_boxes=a.moving_boxes,
@@ -966,4 +1006,5 @@ if __name__ == "__main__":
         clearance=a.clearance, drop_ground=a.drop_ground, map_clusters=a.map_clusters, cluster_tol=a.cluster_tol, cluster_min=a.cluster_min,
         cluster_max=a.cluster_max, drop_small_clusters=a.drop_small_clusters, localize_every=a.localize_every, localize_radius=a.localize_radius,
         localize_shift=a.localize_shift, localize_yaw=a.localize_yaw, occupancy_3d=a.occupancy_3d, occ_voxel=a.occ_voxel, occ_min_range=a.occ_min_range,
-        occ_max_range=a.occ_max_range, occ_shell=a.occ_shell, occ_slice=a.occ_slice)
+        occ_max_range=a.occ_max_range, occ_shell=a.occ_shell, occ_slice=a.occ_slice, occ_distance=a.occ_distance, occ_dist_max=a.occ_dist_max,
+        occ_unknown_obstacle=a.occ_unknown_obstacle, robot_radius=a.robot_radius)
