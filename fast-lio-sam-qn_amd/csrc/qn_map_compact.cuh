@@ -1,5 +1,5 @@
 // qn_map_compact.cuh - what the units around the map slot share on the device besides the cell walk (qn_mapoutliers.hip with qn_mapclusters.inc, qn_mapground.hip,
-// qn_staticmap.hip with qn_mapoccupancy.inc and qn_mapdistance.inc, qn_verify.hip with qn_maplocalize.inc):
+// qn_staticmap.hip with qn_mapoccupancy.inc, qn_mapdistance.inc and qn_maproute.inc, qn_verify.hip with qn_maplocalize.inc):
 //   counts    block_count: the lanes of a block for which each of up to five predicates holds, by ballot and popcount, one word per wave in LDS, into the
 //             block's own slot; k_slot_fold (one block) adds the slots up.  No atomics: integer sums, the same on every run.
 //   scan      scan_row: the exclusive scan of a row of per-block counts in one block; k_scan_rows, a block per row, is the kernel over it (one row: a filter's

@@ -168,9 +168,11 @@ struct DistState {
   bool live = false;
   DevBuf<uint16_t> d2, tmp;
   qn_distance_params params;
+  std::shared_ptr<struct RouteState> route;              // the route field of qn_maproute.inc (included behind this file, where the type is completed)
 };
+void mr_end(RouteState*);                                // (qn_maproute.inc) a new distance field ends the route field of the previous one; its buffer stays
 
-void md_end(DistState* d) { if (d) d->live = false; }
+void md_end(DistState* d) { if (d) { d->live = false; mr_end(d->route.get()); } }
 
 // the occupancy result and its live field, or nullptr
 const DistState* md_live(qn_kf_store* s, const OccState** occ) {
@@ -236,6 +238,7 @@ extern "C" int qn_kf_map_distance(qn_kf_store* s, const qn_distance_params* para
   }
   st->params = P;
   st->live = true;
+  mr_end(st->route.get());
   *stats_out = r;
   return QN_OK;
 }

@@ -837,6 +837,38 @@ QN_DIST_MAX_RADIUS = 255
 QN_DIST_OUTSIDE = 0xff
 
 
+class RouteParams(C.Structure):
+    """qn_route_params (32 bytes): the classes that are passable (bit 1 << class), the smallest d2 a passable voxel has (0: no test), the band of layers, and
+    whether the field is the plane of columns.  The defaults are interface choices, not measurements."""
+    _fields_ = [("pass_mask", C.c_uint32), ("min_d2", C.c_uint32), ("iz_lo", C.c_int32), ("iz_hi", C.c_int32), ("planar", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+    def __init__(self, pass_mask=1 << QN_OCC_FREE, min_d2=4, iz_lo=0, iz_hi=0x7fffffff, planar=0):
+        super().__init__(pass_mask, min_d2, iz_lo, iz_hi, planar)
+
+    def twin(self):
+        """-> the maproute.RouteParams with these values"""
+        from . import maproute
+        return maproute.RouteParams(int(self.pass_mask), int(self.min_d2), int(self.iz_lo), int(self.iz_hi), int(self.planar))
+
+
+class RouteStats(C.Structure):
+    """qn_route_stats (64 bytes): every field but rounds and tile_visits - diagnostics of the GPU schedule - is an integer the twin shares"""
+    _fields_ = [("passable", C.c_uint32), ("blocked", C.c_uint32), ("reached", C.c_uint32), ("unreached", C.c_uint32), ("goals_used", C.c_uint32),
+                ("goals_blocked", C.c_uint32), ("max_cost", C.c_uint32), ("reserved0", C.c_uint32), ("sum_cost", C.c_uint64), ("rounds", C.c_uint64),
+                ("tile_visits", C.c_uint64), ("reserved", C.c_uint32 * 2)]
+
+    def twin(self):
+        """-> the maproute.RouteStats with these values"""
+        from . import maproute
+        return maproute.RouteStats(*(int(getattr(self, f)) for f in maproute.RouteStats._fields))
+
+
+QN_ROUTE_BLOCKED = 0xfffffffe
+QN_ROUTE_UNREACHED = 0xffffffff
+QN_ROUTE_MAX_POINTS = 1 << 20
+QN_ROUTE_ROUNDS_PER_CHECK = 8
+
+
 class ClusterParams(C.Structure):
     """qn_cluster_params (24 bytes): the joining distance, the smallest and the largest component that is a cluster, and the ground classes that take part
     (0: every finite point).  The defaults are interface choices, not measurements."""
@@ -1567,6 +1599,50 @@ class KeyframeStore:
         d2 = np.zeros(max(n, 1), np.uint16); cls = np.zeros(max(n, 1), np.uint8)
         self._check(self._l.qn_kf_map_distance_query(self.h, _p(xyz), C.c_uint32(n), _p(d2), _p(cls)))
         return d2[:n], cls[:n]
+
+    # ---- planning over the occupancy map: the cost-to-go field and paths (qn_kf_map_route / _grid / _query / _path; numpy twin: qn_amd/maproute.py)
+    def map_route(self, goals, params=None):
+        """qn_kf_map_route over the latest map_occupancy and map_distance: per voxel (per column in planar mode) the smallest 3-4-5 chamfer path cost to the
+        nearest of the world points `goals` (n, 3) f64 through passable voxels, QN_ROUTE_BLOCKED where not passable, QN_ROUTE_UNREACHED where cut off.  params:
+        a RouteParams (or a maproute.RouteParams); None: the defaults.  -> stats, a dict of the fields of qn_route_stats; all but rounds and tile_visits equal
+        those of maproute.field of the downloaded classes and d2.  map_route_grid / _query / _paths serve the field."""
+        p = RouteParams() if params is None else params
+        if not isinstance(p, RouteParams):
+            p = RouteParams(*(int(v) for v in p))
+        xyz = np.ascontiguousarray(goals, dtype=np.float64).reshape(-1, 3)
+        st = RouteStats()
+        self._check(self._l.qn_kf_map_route(self.h, _p(xyz), C.c_uint32(len(xyz)), C.byref(p), C.byref(st)))
+        return {f: int(getattr(st, f)) for f, _ in RouteStats._fields_ if not f.startswith("reserved")}
+
+    def map_route_grid(self):
+        """qn_kf_map_route_grid -> (info, params, cost (D, H, W) uint32, or (1, H, W) in planar mode) of the latest map_route: info the occupancy grid's dict,
+        params a dict of the fields of qn_route_params"""
+        g = OccupancyGrid(); p = RouteParams()
+        self._check(self._l.qn_kf_map_route_grid(self.h, C.byref(g), C.byref(p), None))
+        W, H, D = int(g.width), int(g.height), int(g.depth)
+        if p.planar:
+            D = 1 if W * H else 0
+        n = W * H * D
+        cost = np.zeros(max(n, 1), np.uint32)
+        self._check(self._l.qn_kf_map_route_grid(self.h, C.byref(g), C.byref(p), _p(cost)))
+        return self._occupancy_info(g), p.twin()._asdict(), cost[:n].reshape(D, H, W)
+
+    def map_route_query(self, xyz):
+        """qn_kf_map_route_query: world points (n, 3) f64 -> the field's value (n,) uint32 at each; QN_ROUTE_BLOCKED for a point that is not finite or outside"""
+        xyz = np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
+        n = len(xyz)
+        cost = np.zeros(max(n, 1), np.uint32)
+        self._check(self._l.qn_kf_map_route_query(self.h, _p(xyz), C.c_uint32(n), _p(cost)))
+        return cost[:n]
+
+    def map_route_paths(self, starts, max_len):
+        """qn_kf_map_route_path: world points (S, 3) f64 -> (len (S,) uint32: the voxels of each start's path down the field, start and goal included, 0 for a
+        start that is outside, blocked or unreached; ijk (S, max_len, 3) int32: the first min(len, max_len) of them, the rest 0).  cost // 3 + 1 bounds len."""
+        xyz = np.ascontiguousarray(starts, dtype=np.float64).reshape(-1, 3)
+        n, m = len(xyz), int(max_len)
+        lens = np.zeros(max(n, 1), np.uint32); ijk = np.zeros((max(n, 1), max(m, 1), 3), np.int32)
+        self._check(self._l.qn_kf_map_route_path(self.h, _p(xyz), C.c_uint32(n), C.c_uint32(m), _p(lens), _p(ijk)))
+        return lens[:n], ijk[:n]
 
     # ---- the map slot's points clustered into objects (qn_kf_map_clusters / _cluster_points / _cluster_list / qn_kf_map_drop_rejected_clusters; numpy twin:
     # qn_amd/mapclusters.py)

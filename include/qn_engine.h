@@ -821,6 +821,59 @@ int  qn_kf_map_distance(qn_kf_store*, const qn_distance_params* params, qn_dista
 int  qn_kf_map_distance_grid(qn_kf_store*, qn_occupancy_grid* info_out, qn_distance_params* params_out, uint16_t* d2_out);
 int  qn_kf_map_distance_slice(qn_kf_store*, int32_t iz_lo, int32_t iz_hi, uint16_t* d2_out /* W x H, y slow */);
 int  qn_kf_map_distance_query(qn_kf_store*, const double* xyz, uint32_t n, uint16_t* d2_out, uint8_t* class_out);
+/* ---- planning over the occupancy map: the cost-to-go field and paths (csrc/qn_maproute.inc, part of csrc/qn_staticmap.hip; numpy twin and specification:
+ * qn_amd/maproute.py)
+ * What a planner asks of the volume second: how far is it from here to there through free space with a given clearance, and along which voxels.  These calls
+ * compute, over the resident class bytes of the live qn_kf_map_occupancy result and the live qn_kf_map_distance field, the shortest-path cost from every voxel
+ * to the nearest of a set of goals, keep it on the device, and walk paths down it.  Shortest-path costs are unique integers: whatever the schedule of the relaxation,
+ * every value equals the twin's bit for bit.
+ * qn_route_params (32 bytes): pass_mask (class bits 0 .. 2, not 0; default 1 << QN_OCC_FREE), min_d2 (a voxel passes only if d2 >= min_d2; QN_DIST_FAR passes
+ *   any min_d2, 0 switches the test off; default 4), iz_lo, iz_hi (i32: the band of layers, inclusive, clipped to the grid; defaults 0 and INT32_MAX), planar (0
+ *   or 1; default 0), reserved[3] (0).  The defaults are interface choices, not measurements.
+ * Passable, 3-D (planar 0): voxel v iff its class bit is in pass_mask, d2[v] >= min_d2 and iz_lo <= vz <= iz_hi; the field is W x H x D.  Planar: the field is
+ *   W x H x 1; a column is passable iff the clipped band is not empty and every voxel of the column inside it passes the class and d2 tests - an upright body
+ *   moving in the plane, the companion of qn_kf_map_distance_slice.
+ * Moves: from v to v + o, o in {-1, 0, 1}^3 without 0, both ends inside the field; allowed iff every voxel v + o' is passable, o'_k in {0, o_k} on each axis k:
+ *   the 2, 4 or 8 voxels of the block the move spans.  No corner is cut and no diagonal slips between two obstacles; the rule is symmetric, so the graph is
+ *   undirected.  Cost 2 + |o|_1: 3 for a face move, 4 for an edge move, 5 for a corner move, the 3-4-5 chamfer metric: cost / 3 * voxel is the length in
+ *   metres, in open space between 5.7 % under (a face diagonal) and 10.6 % over (direction (3, 1, 1)) the Euclidean length.
+ * Goals: n world points (3 f64 each), 1 .. 2^20, each to its voxel by the occupancy map's own quantisation, exactly as in qn_kf_map_distance_query; in planar
+ *   mode only x and y choose the column, z must still be finite with |z * inv| < 2^20.  A goal whose voxel or column is passable has cost 0; every other goal
+ *   (not finite, outside, blocked) is ignored and counted in goals_blocked.  With no goal left the call still succeeds and nothing is reached.
+ * Field, one uint32_t per voxel (per column in planar mode): the smallest path cost to a goal, QN_ROUTE_BLOCKED (0xfffffffe) where the voxel is not passable,
+ *   QN_ROUTE_UNREACHED (0xffffffff) where it is passable but not connected to a goal.  A simple path has at most 2^27 voxels, so a cost is at most 5 * 2^27.
+ * qn_route_stats (64 bytes): passable, blocked, reached, unreached (passable = reached + unreached, passable + blocked = the field's cells), goals_used,
+ *   goals_blocked, max_cost, reserved0 (0), sum_cost (u64) over the reached cells - these equal the twin's; rounds and tile_visits (u64), diagnostics of the GPU
+ *   schedule that the twin does not have: the relaxation launches up to the first that changed nothing and the tiles they loaded; reserved[2] (0).
+ * qn_kf_map_route: QN_ERR_INVALID_ARG, before anything runs and with the previous field intact: a null pointer, n == 0 or n > 2^20, pass_mask 0 or with a bit
+ *   >= 3, planar > 1, reserved != 0, iz_lo > iz_hi, min_d2 > max_dist^2 of the live distance field (beyond the cap the distance is not known).
+ *   QN_ERR_NOT_READY without a live occupancy result and a live distance field.  A 0 x 0 x 0 grid succeeds with zero statistics.  Device memory: 4 bytes per
+ *   cell of the field (grown half again as large, kept between calls); when it cannot be allocated QN_ERR_HIP with the previous field intact.  QN_ERR_INTERNAL
+ *   if the relaxation has not settled after cells + 2 rounds, which bound it.  The field stays resident until the next successful qn_kf_map_route,
+ *   qn_kf_map_distance or qn_kf_map_occupancy; the latter two end it and the getters answer QN_ERR_NOT_READY again.  A refused call of any of the three leaves
+ *   the field byte-identical.  Host synchronisations: ceil(rounds / QN_ROUTE_ROUNDS_PER_CHECK) + 1 - one per batch of rounds, then the statistics,
+ *   which carry the goals' counts.  Integer arithmetic throughout; the only floating point is the quantisation of goals, starts and query points.
+ * qn_kf_map_route_grid: *info_out (the occupancy grid's), *params_out (the parameters used) and cost_out, W H D values of 4 bytes (W H in planar mode);
+ *   cost_out may be NULL to fetch the dimensions first.  QN_ERR_NOT_READY without a live field.
+ * qn_kf_map_route_query: cost_out[i] = the field's value at world point i, quantised like a goal; QN_ROUTE_BLOCKED for a point that is not finite or outside.
+ *   QN_ERR_INVALID_ARG: a null pointer, n == 0 or n > 2^20.
+ * qn_kf_map_route_path: S start points (3 f64 each, quantised like goals).  From the start's voxel: at v with cost c > 0 take the first allowed move to n with
+ *   cost[n] + w(v, n) == c, the moves enumerated with dz outermost, then dy, then dx, each in the order -1, 0, +1; stop at cost 0.  len_out[S]: the true number
+ *   of voxels, start and goal included, 0 for a start that is outside, blocked or unreached.  ijk_out: the first min(len, max_len) voxels of each path at
+ *   stride max_len, int32 x 3, the rest 0; in planar mode k = 0.  cost / 3 + 1 bounds len.  QN_ERR_INVALID_ARG: a null pointer, S == 0 or S > 2^20,
+ *   max_len == 0. */
+#define QN_ROUTE_BLOCKED 0xfffffffeu
+#define QN_ROUTE_UNREACHED 0xffffffffu
+#define QN_ROUTE_MAX_POINTS (1u << 20)
+#define QN_ROUTE_ROUNDS_PER_CHECK 8u                     /* an untuned choice: relaxation launches between two reads of the "anything changed" words */
+typedef struct qn_route_params { uint32_t pass_mask, min_d2; int32_t iz_lo, iz_hi; uint32_t planar, reserved[3]; } qn_route_params;     /* 32 bytes */
+typedef struct qn_route_stats  { uint32_t passable, blocked, reached, unreached, goals_used, goals_blocked, max_cost, reserved0; uint64_t sum_cost, rounds, tile_visits;
+                                 uint32_t reserved[2]; } qn_route_stats;                                                                /* 64 bytes */
+void qn_route_default_params(qn_route_params* p);
+int  qn_kf_map_route(qn_kf_store*, const double* goals_xyz, uint32_t n, const qn_route_params* params, qn_route_stats* stats_out);
+int  qn_kf_map_route_grid(qn_kf_store*, qn_occupancy_grid* info_out, qn_route_params* params_out, uint32_t* cost_out);
+int  qn_kf_map_route_query(qn_kf_store*, const double* xyz, uint32_t n, uint32_t* cost_out);
+int  qn_kf_map_route_path(qn_kf_store*, const double* starts_xyz, uint32_t n_starts, uint32_t max_len, uint32_t* len_out, int32_t* ijk_out);
 /* ---- the map's points clustered into objects (csrc/qn_mapclusters.inc, part of csrc/qn_mapoutliers.hip; numpy twin and specification: qn_amd/mapclusters.py)
  * After qn_kf_map_ground every point is GROUND, OBSTACLE or OVERHEAD, but the obstacles are an unstructured set.  These calls run PCL's
  * EuclideanClusterExtraction over the store's map slot on the GPU: connected components of the radius graph, each with a size, a box and a centroid, and the

@@ -354,7 +354,8 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
         outlier_radius=1.0, outlier_k=8, outlier_std=2.0, occupancy_grid=False, grid_cell=0.5, max_slope=0.3, ground_tol=0.2, clearance=2.0,
         drop_ground=False, map_clusters=False, cluster_tol=0.5, cluster_min=10, cluster_max=0xffffffff, drop_small_clusters=False,
         localize_every=0, localize_radius=35.0, localize_shift=0.5, localize_yaw=3.0, occupancy_3d=False, occ_voxel=0.3, occ_min_range=0.5,
-        occ_max_range=60.0, occ_shell=1, occ_slice=None, occ_distance=False, occ_dist_max=16, occ_unknown_obstacle=False, robot_radius=None):
+        occ_max_range=60.0, occ_shell=1, occ_slice=None, occ_distance=False, occ_dist_max=16, occ_unknown_obstacle=False, robot_radius=None, occ_route=None,
+        route_from=None, route_min_d2=4, route_planar=False):
     """sensor = "uniform": keyframe clouds sampled uniformly by area inside a disc (make_stream); "spinning": ray-cast spinning-LiDAR
     scans from the ground-truth poses of the same figure-8 (make_lidar_stream).  detector = "radius": the candidate is the closest older
     keyframe within `radius` of the corrected position (LC:34-56); "scancontext": the older keyframe nearest by Scan Context distance, kept
@@ -431,6 +432,12 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
     KeyframeStore.map_distance, on the oracle backend by the numpy twin.  out["distance"]: sites, reached, far, max_d2, sum_d2, site_mask, max_dist.
     robot_radius = M metres (with occ_distance and occ_slice): also occupancy_inflated.pgm / .yaml, the slice with every column occupied whose clearance over
     the slice's layers is at most M: d2 <= floor((M / occ_voxel)^2).
+    occ_route = (GX, GY, GZ) in metres (with occupancy_3d and occ_distance; default None): the cost-to-go field to that goal through the free voxels whose d2 is at
+    least route_min_d2 (qn_amd/maproute.py: the 3-4-5 chamfer cost of the shortest path, no corner cut), on the GPU backend by KeyframeStore.map_route, on the
+    oracle backend by the numpy twin, and the path down it from route_from = (X, Y, Z) (default: the last corrected keyframe position).  route_planar: the field
+    of columns instead, every voxel of a column over the band passable - the band being the layers of occ_slice, or without it the goal's layer.
+    out["route"]: passable, blocked, reached, unreached, goals_used, goals_blocked, max_cost, sum_cost, the parameters used, path_len and path_cost (None when
+    the start is outside, blocked or cut off).  route.csv: "x y z cost" per voxel of the path, the voxel's centre in metres and its cost, start first.
     moving_boxes = N (sensor="spinning" only; default 0: every run is what it was): N extra boxes in the scene that stand somewhere else in every keyframe
     (moving_box_prims), so every keyframe is cast by a call of its own."""
     if detector not in ("radius", "scancontext"):
@@ -505,6 +512,16 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
         mapdistance.check_params(dist_params)                                                     # (raises ValueError on a parameter outside its range)
         if robot_radius is not None and not (np.isfinite(robot_radius) and robot_radius >= 0.0):
             raise ValueError("robot_radius must be finite and >= 0, not %r" % (robot_radius,))
+    if (occ_route is None) and (route_from is not None or route_planar or route_min_d2 != 4):
+        raise ValueError("route_from, route_min_d2 and route_planar need occ_route")
+    if occ_route is not None:
+        if not (occupancy_3d and occ_distance):
+            raise ValueError("occ_route needs occupancy_3d and occ_distance (the field is computed from the volume and its distance field)")
+        from qn_amd import maproute
+        for name, v in (("occ_route", occ_route), ("route_from", route_from)):
+            if v is not None and not (len(v) == 3 and np.isfinite(np.asarray(v, np.float64)).all()):
+                raise ValueError("%s must be three finite coordinates, not %r" % (name, v))
+        maproute.check_params(maproute.RouteParams(1 << mapoccupancy.FREE, route_min_d2, 0, 0, int(bool(route_planar))), occ_dist_max)
     if drop_small_clusters and not map_clusters:
         raise ValueError("drop_small_clusters needs map_clusters (the clumps come from its components)")
     if map_clusters and backend != "gpu":
@@ -813,6 +830,31 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
                 if robot_radius is not None:
                     res["d2_slice"] = d2_slice; res["robot_radius"] = float(robot_radius)
             layers = write_occupancy(save_dir, res, occ_slice)
+            if occ_route is not None:
+                g = res["grid"]
+                lo, hi = 0, maproute.INT32_MAX
+                if route_planar:
+                    lo, hi = layers if layers is not None else (mapoccupancy.layer_of(occ_route[2], g),) * 2
+                rp = maproute.RouteParams(1 << mapoccupancy.FREE, int(route_min_d2), int(lo), int(hi), int(bool(route_planar)))
+                start = np.asarray(corrected[-1][:3, 3] if route_from is None else route_from, np.float64).reshape(1, 3)
+                if backend == "gpu":
+                    rst = store.map_route([occ_route], engine.RouteParams(*rp))
+                    at = int(store.map_route_query(start)[0])
+                    n, ijk = store.map_route_paths(start, at // 3 + 1 if at < maproute.BLOCKED else 1)
+                    cost = store.map_route_query(maproute.centres(g, ijk[0, :int(n[0])], rp)) if n[0] else np.zeros(0, np.uint32)
+                else:
+                    rf = maproute.field(res["classes"], field["d2"], g, [occ_route], rp)
+                    rst = rf["stats"]._asdict()
+                    at = int(maproute.query(rf["cost"], g, start, rp)[0])
+                    n, ijk = maproute.paths(rf["cost"], g, start, at // 3 + 1 if at < maproute.BLOCKED else 1, rp)
+                    v = ijk[0, :int(n[0])]
+                    cost = rf["cost"][v[:, 2], v[:, 1], v[:, 0]]
+                xyz = maproute.centres(g, ijk[0, :int(n[0])], rp)
+                with open(os.path.join(save_dir, "route.csv"), "w") as fr:
+                    fr.write("x y z cost\n")
+                    for q, c in zip(xyz, cost):
+                        fr.write("%.6f %.6f %.6f %d\n" % (q[0], q[1], q[2], int(c)))
+                out["route"] = dict({k: int(rst[k]) for k in maproute.RouteStats._fields}, **rp._asdict(), path_len=int(n[0]), path_cost=at if at < maproute.BLOCKED else None)
             out["occupancy"] = {k: int(st[k]) for k in ("n_rays", "total_misses", "width", "height", "depth", "occupied", "free", "unknown")}
             if layers is not None:
                 out["occupancy"]["slice_layers"] = [int(layers[0]), int(layers[1])]
@@ -975,6 +1017,11 @@ if __name__ == "__main__":
     ap.add_argument("--occ-unknown-obstacle", action="store_true", help="with --occ-distance: unknown voxels are obstacles too")
     ap.add_argument("--robot-radius", type=float, default=None, metavar="M",
                     help="with --occ-distance and --occ-slice: also write occupancy_inflated.pgm / .yaml, the slice inflated by this radius [m]")
+    ap.add_argument("--occ-route", type=float, nargs=3, default=None, metavar=("GX", "GY", "GZ"),
+                    help="with --occupancy-3d --occ-distance: the cost-to-go field to this goal [m] through free space and the path to it, written to route.csv")
+    ap.add_argument("--route-from", type=float, nargs=3, default=None, metavar=("X", "Y", "Z"), help="with --occ-route: the path's start [m] (default: the last keyframe's position)")
+    ap.add_argument("--route-min-d2", type=int, default=4, help="with --occ-route: the smallest squared distance to an obstacle, in voxels, a passable voxel has")
+    ap.add_argument("--route-planar", action="store_true", help="with --occ-route: plan in the plane of columns over the layers of --occ-slice (or the goal's layer)")
     ap.add_argument("--moving-boxes", type=int, default=0, help="with --sensor spinning: this many boxes that stand somewhere else in every keyframe")
     ap.add_argument("--backend", choices=["gpu", "oracle"], default="gpu", help="the engine on the GPU, or the CPU oracle")
     a = ap.parse_args()
@@ -998,6 +1045,10 @@ if __name__ == "__main__":
         ap.error("--occ-distance needs --occupancy-3d")
     if (a.occ_unknown_obstacle or a.robot_radius is not None) and not a.occ_distance:
         ap.error("--occ-unknown-obstacle and --robot-radius need --occ-distance")
+    if a.occ_route is not None and not (a.occupancy_3d and a.occ_distance):
+        ap.error("--occ-route needs --occupancy-3d and --occ-distance")
+    if a.occ_route is None and (a.route_from is not None or a.route_planar or a.route_min_d2 != 4):
+        ap.error("--route-from, --route-min-d2 and --route-planar need --occ-route")
     run(a.keyframes, a.seed, a.quatro, save_dir=a.save_dir, save_map_leaf=a.save_map_leaf, sensor=a.sensor, detector=a.detector, yaw_bias=a.yaw_bias,
         verify=a.verify, sc_top_k=a.sc_top_k, backend=a.backend, loop_every=a.loop_every, catch_up=a.catch_up, submap_matching=a.submap_matching,
         min_overlap=a.min_overlap, overlap_radius=a.overlap_radius, max_see_through=a.max_see_through, static_map=a.static_map, moving_boxes=a.moving_boxes,
@@ -1007,4 +1058,5 @@ if __name__ == "__main__":
         cluster_max=a.cluster_max, drop_small_clusters=a.drop_small_clusters, localize_every=a.localize_every, localize_radius=a.localize_radius,
         localize_shift=a.localize_shift, localize_yaw=a.localize_yaw, occupancy_3d=a.occupancy_3d, occ_voxel=a.occ_voxel, occ_min_range=a.occ_min_range,
         occ_max_range=a.occ_max_range, occ_shell=a.occ_shell, occ_slice=a.occ_slice, occ_distance=a.occ_distance, occ_dist_max=a.occ_dist_max,
-        occ_unknown_obstacle=a.occ_unknown_obstacle, robot_radius=a.robot_radius)
+        occ_unknown_obstacle=a.occ_unknown_obstacle, robot_radius=a.robot_radius, occ_route=a.occ_route, route_from=a.route_from, route_min_d2=a.route_min_d2,
+        route_planar=a.route_planar)
