@@ -1,12 +1,13 @@
 // qn_map_compact.cuh - what the units around the map slot share on the device besides the cell walk (qn_mapoutliers.hip with qn_mapclusters.inc, qn_mapground.hip,
-// qn_staticmap.hip with qn_mapoccupancy.inc, qn_mapdistance.inc and qn_maproute.inc, qn_verify.hip with qn_maplocalize.inc):
+// qn_staticmap.hip with qn_mapoccupancy.inc, qn_mapdistance.inc, qn_maproute.inc and qn_mapfrontier.inc, qn_verify.hip with qn_maplocalize.inc):
 //   counts    block_count: the lanes of a block for which each of up to five predicates holds, by ballot and popcount, one word per wave in LDS, into the
 //             block's own slot; k_slot_fold (one block) adds the slots up.  No atomics: integer sums, the same on every run.
 //   scan      scan_row: the exclusive scan of a row of per-block counts in one block; k_scan_rows, a block per row, is the kernel over it (one row: a filter's
 //             or a list's counts, the last word the total; a row per centre, in place: the crop), k_static_scan (qn_staticmap.hip) the one with a tail of its own.
 //   rank      lane_rank: a lane's place among the lanes of its wave for which a predicate holds, by ballot and popcount; block_rank: its place in the block, the
 //             waves' counts through LDS, on top of the block's offset from the scan - where a stable compaction puts the lane's record: the same on every run.
-//             The kernels with one predicate call block_rank and write their own payload there (k_mo_compact, k_mc_pick, k_mc_root_label, k_oc_list_pick);
+//             The kernels with one predicate call block_rank and write their own payload there (k_mo_compact, k_mc_pick, k_mc_root_label, k_oc_list_pick,
+//             k_mf_pick, k_mf_list_pick);
 //             those with a table of their own (k_static_compact: rounds, k_ml_compact: centres) take lane_rank for the last term.
 //   compact   the order-preserving compaction of the slot's records: a unit's own flag kernel writes one removed byte per record and the kept count of every
 //             MO_BLOCK records (block_count), k_scan_rows turns the counts into offsets, k_mo_compact moves a block's kept records to its offset, in order;

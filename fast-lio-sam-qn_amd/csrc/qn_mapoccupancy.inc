@@ -215,8 +215,10 @@ struct OccState {
   DevBuf<uint8_t> cls;
   qn_occupancy_grid info;
   std::shared_ptr<struct DistState> dist;                // the distance field of qn_mapdistance.inc (included behind this file, where the type is completed)
+  std::shared_ptr<struct FrontierState> frontier;        // the frontier regions of qn_mapfrontier.inc (included last), beside the field: they need only the classes
 };
 void md_end(DistState*);                                 // (qn_mapdistance.inc) a new occupancy result ends the field of the previous one; its buffers stay
+void mf_end(FrontierState*);                             // (qn_mapfrontier.inc) and the frontier regions of the previous one
 
 const OccState* oc_live(qn_kf_store* s) {
   const StaticState* st = (const StaticState*)qn_kf_int_ext(s, QN_KF_INT_EXT_STATIC);
@@ -346,6 +348,7 @@ extern "C" int qn_kf_map_occupancy(qn_kf_store* s, const int32_t* ids, const dou
   st->info = info;
   st->live = true;
   md_end(st->dist.get());
+  mf_end(st->frontier.get());
   *stats_out = r;
   return QN_OK;
 }

@@ -869,6 +869,42 @@ QN_ROUTE_MAX_POINTS = 1 << 20
 QN_ROUTE_ROUNDS_PER_CHECK = 8
 
 
+class FrontierParams(C.Structure):
+    """qn_frontier_params (32 bytes): the classes that are candidates and those that are unknown (bit 1 << class, no class in both), whether the space outside
+    the grid is unknown, the smallest component that is a region, and the band of layers.  The defaults are interface choices, not measurements."""
+    _fields_ = [("free_mask", C.c_uint32), ("unknown_mask", C.c_uint32), ("edge_unknown", C.c_uint32), ("min_size", C.c_uint32), ("iz_lo", C.c_int32),
+                ("iz_hi", C.c_int32), ("reserved", C.c_uint32 * 2)]
+
+    def __init__(self, free_mask=1 << QN_OCC_FREE, unknown_mask=1 << QN_OCC_UNKNOWN, edge_unknown=1, min_size=8, iz_lo=0, iz_hi=0x7fffffff):
+        super().__init__(free_mask, unknown_mask, edge_unknown, min_size, iz_lo, iz_hi)
+
+    def twin(self):
+        """-> the mapfrontier.FrontierParams with these values"""
+        from . import mapfrontier
+        return mapfrontier.FrontierParams(int(self.free_mask), int(self.unknown_mask), int(self.edge_unknown), int(self.min_size), int(self.iz_lo), int(self.iz_hi))
+
+
+class FrontierStats(C.Structure):
+    """qn_frontier_stats (48 bytes): every field but rounds - a diagnostic of the GPU schedule - is an integer the twin shares"""
+    _fields_ = [(f, C.c_uint32) for f in ("candidates", "frontier", "components", "regions", "too_small", "region_voxels", "rejected_voxels", "largest",
+                                          "unknown_faces", "rounds")] + [("reserved", C.c_uint32 * 2)]
+
+    def twin(self):
+        """-> the mapfrontier.FrontierStats with these values"""
+        from . import mapfrontier
+        return mapfrontier.FrontierStats(*(int(getattr(self, f)) for f in mapfrontier.FrontierStats._fields))
+
+
+class FrontierInfo(C.Structure):
+    """qn_frontier_info (64 bytes), the layout of mapfrontier.INFO_DTYPE: a region's root, size, box of grid indices, unknown faces and index sums"""
+    _fields_ = [("root", C.c_uint32), ("size", C.c_uint32), ("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3), ("faces", C.c_uint32), ("reserved", C.c_uint32),
+                ("sum", C.c_uint64 * 3)]
+
+
+QN_FRONTIER_REJECTED = -1
+QN_FRONTIER_NONE = -2
+
+
 class ClusterParams(C.Structure):
     """qn_cluster_params (24 bytes): the joining distance, the smallest and the largest component that is a cluster, and the ground classes that take part
     (0: every finite point).  The defaults are interface choices, not measurements."""
@@ -1643,6 +1679,66 @@ class KeyframeStore:
         lens = np.zeros(max(n, 1), np.uint32); ijk = np.zeros((max(n, 1), max(m, 1), 3), np.int32)
         self._check(self._l.qn_kf_map_route_path(self.h, _p(xyz), C.c_uint32(n), C.c_uint32(m), _p(lens), _p(ijk)))
         return lens[:n], ijk[:n]
+
+    # ---- exploration frontiers of the occupancy map (qn_kf_map_frontiers / _frontier_grid / _frontier_regions / _frontier_list / _frontier_costs; numpy twin:
+    # qn_amd/mapfrontier.py)
+    def map_frontiers(self, params=None):
+        """qn_kf_map_frontiers over the class bytes of the latest map_occupancy: the free voxels that border unknown space, grouped into 26-connected regions of
+        at least min_size voxels, numbered in ascending root.  params: a FrontierParams (or a mapfrontier.FrontierParams); None: the defaults.  -> stats, a dict
+        of the fields of qn_frontier_stats; all but rounds equal those of mapfrontier.frontier of the downloaded classes.  map_frontier_grid / _regions /
+        _list / _costs serve the result; neither map_distance nor map_route is needed, only map_frontier_costs reads the route field."""
+        p = FrontierParams() if params is None else params
+        if not isinstance(p, FrontierParams):
+            p = FrontierParams(*(int(v) for v in p))
+        st = FrontierStats()
+        self._check(self._l.qn_kf_map_frontiers(self.h, C.byref(p), C.byref(st)))
+        return {f: int(getattr(st, f)) for f, _ in FrontierStats._fields_ if f != "reserved"}
+
+    def map_frontier_grid(self):
+        """qn_kf_map_frontier_grid -> (info, params, labels (D, H, W) int32) of the latest map_frontiers: info the occupancy grid's dict, params a dict of the
+        fields of qn_frontier_params; a label is the region number, QN_FRONTIER_REJECTED or QN_FRONTIER_NONE"""
+        g = OccupancyGrid(); p = FrontierParams()
+        self._check(self._l.qn_kf_map_frontier_grid(self.h, C.byref(g), C.byref(p), None))
+        W, H, D = int(g.width), int(g.height), int(g.depth)
+        n = W * H * D
+        lab = np.zeros(max(n, 1), np.int32)
+        self._check(self._l.qn_kf_map_frontier_grid(self.h, C.byref(g), C.byref(p), _p(lab)))
+        return self._occupancy_info(g), p.twin()._asdict(), lab[:n].reshape(D, H, W)
+
+    def map_frontier_regions(self):
+        """qn_kf_map_frontier_regions -> the regions of the latest map_frontiers, a structured array of mapfrontier.INFO_DTYPE in region order"""
+        from . import mapfrontier
+        cnt = C.c_uint32()
+        st = self._l.qn_kf_map_frontier_regions(self.h, None, C.c_uint32(0), C.byref(cnt))
+        if st != QN_ERR_CAPACITY:
+            self._check(st)
+        info = np.zeros(max(int(cnt.value), 1), mapfrontier.INFO_DTYPE)
+        self._check(self._l.qn_kf_map_frontier_regions(self.h, _p(info), C.c_uint32(len(info)), C.byref(cnt)))
+        return info[:cnt.value]
+
+    def map_frontier_list(self):
+        """qn_kf_map_frontier_list -> (ijk (m, 3) int32 grid indices, label (m,) int32) of every frontier voxel of the latest map_frontiers, kept or rejected,
+        in ascending linear index"""
+        cnt = C.c_uint32()
+        st = self._l.qn_kf_map_frontier_list(self.h, None, None, C.c_uint32(0), C.byref(cnt))
+        if st != QN_ERR_CAPACITY:
+            self._check(st)
+        m = int(cnt.value)
+        ijk = np.zeros((max(m, 1), 3), np.int32); lab = np.zeros(max(m, 1), np.int32)
+        self._check(self._l.qn_kf_map_frontier_list(self.h, _p(ijk), _p(lab), C.c_uint32(len(lab)), C.byref(cnt)))
+        return ijk[:m], lab[:m]
+
+    def map_frontier_costs(self):
+        """qn_kf_map_frontier_costs with the field of the latest map_route -> (cost (R,) uint32, ijk (R, 3) int32): per region the smallest cost below
+        QN_ROUTE_BLOCKED over its voxels and the voxel attaining it (the smallest linear index on a tie); QN_ROUTE_UNREACHED and (0, 0, 0) without one"""
+        cnt = C.c_uint32()
+        st = self._l.qn_kf_map_frontier_regions(self.h, None, C.c_uint32(0), C.byref(cnt))
+        if st != QN_ERR_CAPACITY:
+            self._check(st)
+        R = int(cnt.value)
+        cost = np.zeros(max(R, 1), np.uint32); ijk = np.zeros((max(R, 1), 3), np.int32)
+        self._check(self._l.qn_kf_map_frontier_costs(self.h, _p(cost), _p(ijk)))
+        return cost[:R], ijk[:R]
 
     # ---- the map slot's points clustered into objects (qn_kf_map_clusters / _cluster_points / _cluster_list / qn_kf_map_drop_rejected_clusters; numpy twin:
     # qn_amd/mapclusters.py)

@@ -874,6 +874,54 @@ int  qn_kf_map_route(qn_kf_store*, const double* goals_xyz, uint32_t n, const qn
 int  qn_kf_map_route_grid(qn_kf_store*, qn_occupancy_grid* info_out, qn_route_params* params_out, uint32_t* cost_out);
 int  qn_kf_map_route_query(qn_kf_store*, const double* xyz, uint32_t n, uint32_t* cost_out);
 int  qn_kf_map_route_path(qn_kf_store*, const double* starts_xyz, uint32_t n_starts, uint32_t max_len, uint32_t* len_out, int32_t* ijk_out);
+/* ---- exploration frontiers of the occupancy map (csrc/qn_mapfrontier.inc, part of csrc/qn_staticmap.hip; numpy twin and specification:
+ * qn_amd/mapfrontier.py)
+ * What an explorer asks of the volume: where to go next to see more.  The answer is the set of frontiers, the free voxels that border unknown space, grouped
+ * into connected regions, each with a size, a box, a centroid and - with a live route field - the cost of reaching it.  These calls compute them over the
+ * resident class bytes of the live qn_kf_map_occupancy result and keep them on the device.  Everything is an integer; components are a set property and root,
+ * number, box and sums do not depend on any order, so every byte equals the twin's bit for bit whatever the schedule.  They need neither the distance field nor
+ * the route field; only qn_kf_map_frontier_costs reads the route field.
+ * qn_frontier_params (32 bytes): free_mask (class bits 0 .. 2, not 0; default 1 << QN_OCC_FREE), unknown_mask (class bits 0 .. 2, not 0, no bit of free_mask;
+ *   default 1 << QN_OCC_UNKNOWN), edge_unknown (0 or 1; default 1), min_size (>= 1; default 8), iz_lo, iz_hi (i32: the band of layers, inclusive, clipped to the
+ *   grid; defaults 0 and INT32_MAX), reserved[2] (0).  The defaults are interface choices, not measurements.
+ * Candidate: a voxel whose class bit is in free_mask and whose layer lies in the band.
+ * Frontier voxel: a candidate with at least one of its 6 face neighbours unknown.  A neighbour inside the grid is unknown iff its class bit is in unknown_mask;
+ *   the band does not apply to neighbours.  A neighbour outside the grid is unknown iff edge_unknown: the grid is the bounding box of the rays, so nothing was
+ *   seen beyond it.  faces[v] = the number of unknown face neighbours, 1 .. 6.
+ * Components: the connected components of the frontier voxels under 26-connectivity; root = the smallest linear index (iz H + iy) W + ix of the component,
+ *   size = its voxel count.  Regions: the components with size >= min_size, numbered 0 .. R - 1 in ascending root.
+ * Labels, one int32_t per voxel: the region number, QN_FRONTIER_REJECTED (-1) for the frontier voxels of smaller components, QN_FRONTIER_NONE (-2) elsewhere.
+ * qn_frontier_info (64 bytes), one per region: root, size, lo[3], hi[3] (the box of the grid indices ix, iy, iz), faces (the sum of faces[v], the opening's area
+ *   in voxel faces), reserved (0), sum[3] (u64: the sums of ix, iy, iz; the centroid is sum / size in grid indices, (minc + c + 0.5) * voxel in metres).
+ * qn_frontier_stats (48 bytes): candidates, frontier (voxels), components, regions, too_small (components), region_voxels, rejected_voxels, largest (the size
+ *   of the largest component, kept or not), unknown_faces (the sum of faces[v] over all frontier voxels) - these equal the twin's; rounds, a diagnostic of the GPU
+ *   schedule that the twin does not have (1: union-find needs no host loop); reserved[2] (0).
+ * qn_kf_map_frontiers: QN_ERR_INVALID_ARG, before anything runs and with the previous result intact: a null pointer, a mask that is 0 or has a bit >= 3, masks
+ *   that overlap, edge_unknown > 1, min_size == 0, iz_lo > iz_hi, reserved != 0.  QN_ERR_NOT_READY without a live occupancy result.  A 0 x 0 x 0 grid succeeds
+ *   with zero statistics.  Device memory: 4 bytes per voxel for the labels and 64 bytes per region (both grown half again as large, kept between calls); when the
+ *   labels cannot be allocated QN_ERR_HIP with the previous result intact.  The result stays resident until the next successful qn_kf_map_frontiers or
+ *   qn_kf_map_occupancy; the latter ends it and the getters answer QN_ERR_NOT_READY again; qn_kf_map_distance and qn_kf_map_route do not touch it.  A refused
+ *   call of either leaves the result byte-identical.  Two host synchronisations: the number of regions, the statistics.
+ * qn_kf_map_frontier_grid: *info_out (the occupancy grid's), *params_out (the parameters used) and label_out, W H D values of 4 bytes; label_out may be NULL to
+ *   fetch the dimensions first.  QN_ERR_NOT_READY without a live frontier result, here and below.
+ * qn_kf_map_frontier_regions: the R rows in region order; *count_out = R.  QN_ERR_CAPACITY, with *count_out set and nothing else written, when capacity < R.
+ * qn_kf_map_frontier_list: every frontier voxel (kept or rejected) in ascending linear index by a stable device compaction: ijk_out three grid indices each,
+ *   label_out its label; *count_out their number.  QN_ERR_CAPACITY, with *count_out set, when capacity is below it.  With capacity 0 the arrays may be NULL.
+ * qn_kf_map_frontier_costs: with the live route field of qn_kf_map_route (3-D or planar: a voxel reads its column's cell), per region the smallest cost
+ *   below QN_ROUTE_BLOCKED over its voxels into cost_out[R] and the voxel attaining it, the smallest linear index on a tie, into ijk_out[R x 3];
+ *   QN_ROUTE_UNREACHED and voxel (0, 0, 0) when no voxel of the region is reached.  QN_ERR_NOT_READY also without a live route field. */
+#define QN_FRONTIER_REJECTED (-1)
+#define QN_FRONTIER_NONE (-2)
+typedef struct qn_frontier_params { uint32_t free_mask, unknown_mask, edge_unknown, min_size; int32_t iz_lo, iz_hi; uint32_t reserved[2]; } qn_frontier_params;   /* 32 bytes */
+typedef struct qn_frontier_stats  { uint32_t candidates, frontier, components, regions, too_small, region_voxels, rejected_voxels, largest, unknown_faces, rounds,
+                                    reserved[2]; } qn_frontier_stats;                                                                  /* 48 bytes */
+typedef struct qn_frontier_info   { uint32_t root, size; int32_t lo[3], hi[3]; uint32_t faces, reserved; uint64_t sum[3]; } qn_frontier_info;   /* 64 bytes */
+void qn_frontier_default_params(qn_frontier_params* p);
+int  qn_kf_map_frontiers(qn_kf_store*, const qn_frontier_params* params, qn_frontier_stats* stats_out);
+int  qn_kf_map_frontier_grid(qn_kf_store*, qn_occupancy_grid* info_out, qn_frontier_params* params_out, int32_t* label_out /* W H D, may be NULL */);
+int  qn_kf_map_frontier_regions(qn_kf_store*, qn_frontier_info* info_out, uint32_t capacity, uint32_t* count_out);
+int  qn_kf_map_frontier_list(qn_kf_store*, int32_t* ijk_out, int32_t* label_out, uint32_t capacity, uint32_t* count_out);   /* every frontier voxel, ascending linear index */
+int  qn_kf_map_frontier_costs(qn_kf_store*, uint32_t* cost_out /* R */, int32_t* ijk_out /* R x 3 */);
 /* ---- the map's points clustered into objects (csrc/qn_mapclusters.inc, part of csrc/qn_mapoutliers.hip; numpy twin and specification: qn_amd/mapclusters.py)
  * After qn_kf_map_ground every point is GROUND, OBSTACLE or OVERHEAD, but the obstacles are an unstructured set.  These calls run PCL's
  * EuclideanClusterExtraction over the store's map slot on the GPU: connected components of the radius graph, each with a size, a box and a centroid, and the

@@ -355,7 +355,7 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
         drop_ground=False, map_clusters=False, cluster_tol=0.5, cluster_min=10, cluster_max=0xffffffff, drop_small_clusters=False,
         localize_every=0, localize_radius=35.0, localize_shift=0.5, localize_yaw=3.0, occupancy_3d=False, occ_voxel=0.3, occ_min_range=0.5,
         occ_max_range=60.0, occ_shell=1, occ_slice=None, occ_distance=False, occ_dist_max=16, occ_unknown_obstacle=False, robot_radius=None, occ_route=None,
-        route_from=None, route_min_d2=4, route_planar=False):
+        route_from=None, route_min_d2=4, route_planar=False, occ_frontiers=False, frontier_min_size=8):
     """sensor = "uniform": keyframe clouds sampled uniformly by area inside a disc (make_stream); "spinning": ray-cast spinning-LiDAR
     scans from the ground-truth poses of the same figure-8 (make_lidar_stream).  detector = "radius": the candidate is the closest older
     keyframe within `radius` of the corrected position (LC:34-56); "scancontext": the older keyframe nearest by Scan Context distance, kept
@@ -438,6 +438,13 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
     of columns instead, every voxel of a column over the band passable - the band being the layers of occ_slice, or without it the goal's layer.
     out["route"]: passable, blocked, reached, unreached, goals_used, goals_blocked, max_cost, sum_cost, the parameters used, path_len and path_cost (None when
     the start is outside, blocked or cut off).  route.csv: "x y z cost" per voxel of the path, the voxel's centre in metres and its cost, start first.
+    occ_frontiers (with occupancy_3d; default False): the exploration frontiers of that volume - the free voxels with an unknown face neighbour, the space outside
+    the grid unknown too, grouped into 26-connected regions of at least frontier_min_size voxels (qn_amd/mapfrontier.py), over the layers of occ_slice when
+    given, else over all - on the GPU backend by KeyframeStore.map_frontiers, on the oracle backend by the numpy twin.  It needs neither occ_distance nor
+    occ_route.  out["frontiers"]: candidates, frontier, components, regions, too_small, region_voxels, rejected_voxels, largest, unknown_faces and the parameters
+    used.  frontiers.csv: one row per region, "region size faces cx cy cz lo_x lo_y lo_z hi_x hi_y hi_z" - its number, voxels, unknown faces, centroid in metres
+    and box of grid indices; with occ_route the row also carries "reach ex ey ez", the cost in metres of reaching the region down the route field (inf when no
+    voxel of it is reached) and the centre of the voxel where it is entered (nan then).
     moving_boxes = N (sensor="spinning" only; default 0: every run is what it was): N extra boxes in the scene that stand somewhere else in every keyframe
     (moving_box_prims), so every keyframe is cast by a call of its own."""
     if detector not in ("radius", "scancontext"):
@@ -522,6 +529,11 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
             if v is not None and not (len(v) == 3 and np.isfinite(np.asarray(v, np.float64)).all()):
                 raise ValueError("%s must be three finite coordinates, not %r" % (name, v))
         maproute.check_params(maproute.RouteParams(1 << mapoccupancy.FREE, route_min_d2, 0, 0, int(bool(route_planar))), occ_dist_max)
+    if (occ_frontiers or frontier_min_size != 8) and not (occupancy_3d and occ_frontiers):
+        raise ValueError("occ_frontiers needs occupancy_3d, and frontier_min_size needs occ_frontiers (the regions are found in its volume)")
+    if occ_frontiers:
+        from qn_amd import mapfrontier
+        mapfrontier.check_params(mapfrontier.FrontierParams(min_size=frontier_min_size))          # (raises ValueError on a parameter outside its range)
     if drop_small_clusters and not map_clusters:
         raise ValueError("drop_small_clusters needs map_clusters (the clumps come from its components)")
     if map_clusters and backend != "gpu":
@@ -855,6 +867,34 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
                     for q, c in zip(xyz, cost):
                         fr.write("%.6f %.6f %.6f %d\n" % (q[0], q[1], q[2], int(c)))
                 out["route"] = dict({k: int(rst[k]) for k in maproute.RouteStats._fields}, **rp._asdict(), path_len=int(n[0]), path_cost=at if at < maproute.BLOCKED else None)
+            if occ_frontiers:
+                g = res["grid"]
+                flo, fhi = layers if layers is not None else (0, mapfrontier.INT32_MAX)
+                fp = mapfrontier.FrontierParams(min_size=int(frontier_min_size), iz_lo=int(flo), iz_hi=int(fhi))
+                reach = None
+                if backend == "gpu":
+                    fst = store.map_frontiers(engine.FrontierParams(*fp))
+                    finfo = store.map_frontier_regions()
+                    if occ_route is not None:
+                        reach = store.map_frontier_costs()
+                else:
+                    fr = mapfrontier.frontier(res["classes"], fp)
+                    fst, finfo = fr["stats"]._asdict(), fr["info"]
+                    if occ_route is not None:
+                        reach = mapfrontier.costs(fr["labels"], len(finfo), rf["cost"])
+                centroid = mapoccupancy.centres(mapfrontier.centroid(finfo), g)
+                with open(os.path.join(save_dir, "frontiers.csv"), "w") as ff:
+                    ff.write("region size faces cx cy cz lo_x lo_y lo_z hi_x hi_y hi_z" + (" reach ex ey ez" if reach is not None else "") + "\n")
+                    if reach is not None:
+                        metres = maproute.metres(reach[0], g.voxel)
+                        entry = np.where((reach[0] < maproute.BLOCKED)[:, None], mapoccupancy.centres(reach[1], g), np.nan)
+                    for k, r in enumerate(finfo):
+                        row = "%d %d %d %.6f %.6f %.6f %d %d %d %d %d %d" % ((k, int(r["size"]), int(r["faces"])) + tuple(centroid[k]) + tuple(int(v) for v in r["lo"]) +
+                                                                            tuple(int(v) for v in r["hi"]))
+                        if reach is not None:
+                            row += " %.6f %.6f %.6f %.6f" % ((float(metres[k]),) + tuple(entry[k]))
+                        ff.write(row + "\n")
+                out["frontiers"] = dict({k: int(fst[k]) for k in mapfrontier.FrontierStats._fields}, **fp._asdict())
             out["occupancy"] = {k: int(st[k]) for k in ("n_rays", "total_misses", "width", "height", "depth", "occupied", "free", "unknown")}
             if layers is not None:
                 out["occupancy"]["slice_layers"] = [int(layers[0]), int(layers[1])]
@@ -1022,6 +1062,10 @@ if __name__ == "__main__":
     ap.add_argument("--route-from", type=float, nargs=3, default=None, metavar=("X", "Y", "Z"), help="with --occ-route: the path's start [m] (default: the last keyframe's position)")
     ap.add_argument("--route-min-d2", type=int, default=4, help="with --occ-route: the smallest squared distance to an obstacle, in voxels, a passable voxel has")
     ap.add_argument("--route-planar", action="store_true", help="with --occ-route: plan in the plane of columns over the layers of --occ-slice (or the goal's layer)")
+    ap.add_argument("--occ-frontiers", action="store_true",
+                    help="with --occupancy-3d: also find the exploration frontiers, the free voxels beside unknown space grouped into regions, written to frontiers.csv "
+                         "(over the layers of --occ-slice when given; with --occ-route each region's reach cost and entry voxel too)")
+    ap.add_argument("--frontier-min-size", type=int, default=8, help="with --occ-frontiers: the smallest component, in voxels, that is a region")
     ap.add_argument("--moving-boxes", type=int, default=0, help="with --sensor spinning: this many boxes that stand somewhere else in every keyframe")
     ap.add_argument("--backend", choices=["gpu", "oracle"], default="gpu", help="the engine on the GPU, or the CPU oracle")
     a = ap.parse_args()
@@ -1049,6 +1093,10 @@ if __name__ == "__main__":
         ap.error("--occ-route needs --occupancy-3d and --occ-distance")
     if a.occ_route is None and (a.route_from is not None or a.route_planar or a.route_min_d2 != 4):
         ap.error("--route-from, --route-min-d2 and --route-planar need --occ-route")
+    if a.occ_frontiers and not a.occupancy_3d:
+        ap.error("--occ-frontiers needs --occupancy-3d")
+    if a.frontier_min_size != 8 and not a.occ_frontiers:
+        ap.error("--frontier-min-size needs --occ-frontiers")
     run(a.keyframes, a.seed, a.quatro, save_dir=a.save_dir, save_map_leaf=a.save_map_leaf, sensor=a.sensor, detector=a.detector, yaw_bias=a.yaw_bias,
         verify=a.verify, sc_top_k=a.sc_top_k, backend=a.backend, loop_every=a.loop_every, catch_up=a.catch_up, submap_matching=a.submap_matching,
         min_overlap=a.min_overlap, overlap_radius=a.overlap_radius, max_see_through=a.max_see_through, static_map=a.static_map, moving_boxes=a.moving_boxes,
@@ -1059,4 +1107,4 @@ if __name__ == "__main__":
         localize_shift=a.localize_shift, localize_yaw=a.localize_yaw, occupancy_3d=a.occupancy_3d, occ_voxel=a.occ_voxel, occ_min_range=a.occ_min_range,
         occ_max_range=a.occ_max_range, occ_shell=a.occ_shell, occ_slice=a.occ_slice, occ_distance=a.occ_distance, occ_dist_max=a.occ_dist_max,
         occ_unknown_obstacle=a.occ_unknown_obstacle, robot_radius=a.robot_radius, occ_route=a.occ_route, route_from=a.route_from, route_min_d2=a.route_min_d2,
-        route_planar=a.route_planar)
+        route_planar=a.route_planar, occ_frontiers=a.occ_frontiers, frontier_min_size=a.frontier_min_size)
