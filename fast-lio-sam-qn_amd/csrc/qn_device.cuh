@@ -28,6 +28,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "qn_eig3.cuh"
 
 namespace qn {
 
@@ -1013,42 +1014,7 @@ __device__ __forceinline__ M3 m3_inverse(const M3& a) {
   return r;
 }
 
-// symmetric 3x3 eigen-decomposition (cyclic Jacobi, f64); eigenvalues descending, V columns.
-__device__ inline void sym_eig3(const double A[6] /* xx xy xz yy yz zz */, double w[3], double V[3][3]) {
-  double a[3][3] = {{A[0], A[1], A[2]}, {A[1], A[3], A[4]}, {A[2], A[4], A[5]}};
-  double v[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
-  for (int sweep = 0; sweep < 32; sweep++) {
-    double off = fabs(a[0][1]) + fabs(a[0][2]) + fabs(a[1][2]);
-    double diag = fabs(a[0][0]) + fabs(a[1][1]) + fabs(a[2][2]);
-    if (off <= 1e-300 || off <= 1e-17 * diag) break;
-#pragma unroll
-    for (int pq = 0; pq < 3; pq++) {
-      const int p = pq == 2 ? 1 : 0, q = pq == 0 ? 1 : 2;
-      if (a[p][q] == 0.0) continue;
-      double theta = (a[q][q] - a[p][p]) / (2.0 * a[p][q]);
-      double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-      double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-#pragma unroll
-      for (int k = 0; k < 3; k++) { double akp = a[k][p], akq = a[k][q]; a[k][p] = c*akp - s*akq; a[k][q] = s*akp + c*akq; }
-#pragma unroll
-      for (int k = 0; k < 3; k++) { double apk = a[p][k], aqk = a[q][k]; a[p][k] = c*apk - s*aqk; a[q][k] = s*apk + c*aqk; }
-#pragma unroll
-      for (int k = 0; k < 3; k++) { double vkp = v[k][p], vkq = v[k][q]; v[k][p] = c*vkp - s*vkq; v[k][q] = s*vkp + c*vkq; }
-    }
-  }
-  // sort descending (3-element network), carrying columns
-  double e0 = a[0][0], e1 = a[1][1], e2 = a[2][2];
-  int i0 = 0, i1 = 1, i2 = 2;
-  if (e0 < e1) { double t = e0; e0 = e1; e1 = t; int ti = i0; i0 = i1; i1 = ti; }
-  if (e1 < e2) { double t = e1; e1 = e2; e2 = t; int ti = i1; i1 = i2; i2 = ti; }
-  if (e0 < e1) { double t = e0; e0 = e1; e1 = t; int ti = i0; i0 = i1; i1 = ti; }
-  w[0] = e0; w[1] = e1; w[2] = e2;
-#pragma unroll
-  for (int r = 0; r < 3; r++) {
-    V[r][0] = i0 == 0 ? v[r][0] : (i0 == 1 ? v[r][1] : v[r][2]);
-    V[r][1] = i1 == 0 ? v[r][0] : (i1 == 1 ? v[r][1] : v[r][2]);
-    V[r][2] = i2 == 0 ? v[r][0] : (i2 == 1 ? v[r][1] : v[r][2]);
-  }
-}
+// sym_eig3, the symmetric 3 x 3 eigen decomposition of the covariance and normal kernels (eigenvalues descending, V columns), is in qn_eig3.cuh: plain C++ there,
+// so that a host build can test it.
 
 }  // namespace qn

@@ -1328,6 +1328,25 @@ extern "C" int qn_debug_selftest(qn_ctx* c, uint32_t n_waves, uint32_t seed, uin
   *mismatches = bad;
   return QN_OK;
 }
+// developer / test entry point: the device builds of the two 3 x 3 eigen solvers on the caller's matrices (k_debug_eig3, qn_selftest.cuh)
+extern "C" int qn_debug_eig3(qn_ctx* c, int which, const double* a6, uint32_t n, double* w_out, double* v_out) {
+  if (!c || !a6 || !w_out || !v_out || which < 0 || which > 1 || n > QN_DEBUG_EIG3_MAX) return QN_ERR_INVALID_ARG;
+  if (n == 0) return QN_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  double* d = nullptr;                                          // a6 [6 n] | w [3 n] | V [9 n]
+  HIPCHK(c, hipMalloc(&d, 18 * (size_t)n * sizeof(double)));
+  double* d_w = d + 6 * (size_t)n; double* d_v = d + 9 * (size_t)n;
+  int rc = QN_OK;
+  if (hipMemcpyAsync(d, a6, 6 * (size_t)n * sizeof(double), hipMemcpyHostToDevice, c->stream) != hipSuccess) rc = QN_ERR_HIP;
+  if (rc == QN_OK) {
+    hipLaunchKernelGGL(k_debug_eig3, dim3((n + QN_EIG3_DEBUG_BLOCK - 1) / QN_EIG3_DEBUG_BLOCK), dim3(QN_EIG3_DEBUG_BLOCK), 0, c->stream, which, (const double*)d, n, d_w, d_v);
+    if (hipGetLastError() != hipSuccess || hipMemcpyAsync(w_out, d_w, 3 * (size_t)n * sizeof(double), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+        hipMemcpyAsync(v_out, d_v, 9 * (size_t)n * sizeof(double), hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) rc = QN_ERR_HIP;
+  }
+  (void)hipFree(d);
+  if (rc != QN_OK) { c->last_error = "debug_eig3: HIP call failed"; return rc; }
+  return QN_OK;
+}
 extern "C" int qn_debug_get_counters(qn_ctx* c, uint32_t out[16]) {
   if (!c || !c->dbg_counters) return QN_ERR_INVALID_ARG;
   if (hipStreamSynchronize(c->stream) != hipSuccess) return QN_ERR_HIP;

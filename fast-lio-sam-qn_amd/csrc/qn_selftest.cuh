@@ -54,4 +54,28 @@ static __global__ void __launch_bounds__(64) k_selftest_wave(const uint32_t* __r
   if (nbad) atomicAdd(bad, nbad);
 }
 
+// qn_debug_eig3: the device builds of the two 3 x 3 eigen solvers (qn_eig3.cuh) on caller-supplied matrices, one matrix per lane; which = 0 qn_eig3_jacobi,
+// 1 sym_eig3.  a6[6 i ..] = (xx, xy, xz, yy, yz, zz) -> w[3 i ..], V[9 i ..] row major, the eigenvector of w[k] in column k.  tests/test_gpu_eig3.py holds the
+// results to a 50-digit reference and to the host build of the same text.
+#define QN_EIG3_DEBUG_BLOCK 256
+static __global__ void __launch_bounds__(QN_EIG3_DEBUG_BLOCK) k_debug_eig3(int which, const double* __restrict__ a6, uint32_t n, double* __restrict__ w_out, double* __restrict__ v_out) {
+  const uint32_t i = blockIdx.x * QN_EIG3_DEBUG_BLOCK + threadIdx.x;
+  if (i >= n) return;
+  const double* a = a6 + 6 * (size_t)i;
+  double w[3], V[3][3];
+  if (which == 0) {
+    qn_eig3_jacobi(a[0], a[1], a[2], a[3], a[4], a[5], w, V);
+  } else {
+    const double A[6] = {a[0], a[1], a[2], a[3], a[4], a[5]};
+    sym_eig3(A, w, V);
+  }
+  double* wo = w_out + 3 * (size_t)i; double* vo = v_out + 9 * (size_t)i;
+#pragma unroll
+  for (int r = 0; r < 3; r++) {
+    wo[r] = w[r];
+#pragma unroll
+    for (int k = 0; k < 3; k++) vo[3 * r + k] = V[r][k];
+  }
+}
+
 }  // namespace qn

@@ -121,6 +121,18 @@ class Context:
         self.check(self._l.qn_debug_get(self.h, key.encode(), C.byref(v)))
         return v.value
 
+    def debug_eig3(self, which, a6):
+        """qn_debug_eig3: the device build of a 3 x 3 symmetric eigen solver (0: qn_eig3_jacobi, 1: sym_eig3) on the rows (xx, xy, xz, yy, yz, zz) of a6
+        -> w (n, 3), V (n, 3, 3) with the eigenvector of w[:, k] in V[:, :, k].  Test infrastructure."""
+        a = np.ascontiguousarray(a6, dtype=np.float64).reshape(-1, 6)
+        n = len(a)
+        if n == 0:
+            a = np.zeros((1, 6))                                      # (an empty array may have no address; the call refuses null pointers)
+        w = np.zeros((max(n, 1), 3)); V = np.zeros((max(n, 1), 3, 3))
+        self._l.qn_debug_eig3.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+        self.check(self._l.qn_debug_eig3(self.h, C.c_int(which), _p(a), C.c_uint32(n), _p(w), _p(V)))
+        return w[:n], V[:n]
+
     def grid_info(self, which):
         out = np.zeros(8)
         self.check(self._l.qn_debug_get_grid(self.h, C.c_int(which), _p(out)))

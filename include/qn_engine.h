@@ -1144,6 +1144,12 @@ int  qn_prof_get(qn_ctx*, int kernel_family, qn_kernel_stat* out);
 int  qn_debug_set(qn_ctx*, const char* key, double value);
 int  qn_debug_get_counters(qn_ctx*, uint32_t out[16]);
 int  qn_debug_selftest(qn_ctx*, uint32_t n_waves, uint32_t seed, uint32_t* mismatches);      /* developer / tests: the device's wave-level search primitives against plain restatements (csrc/qn_selftest.cuh) */
+/* developer / tests: the device builds of the two 3 x 3 symmetric eigen solvers (csrc/qn_eig3.cuh) on n caller-supplied matrices, one per lane.  which = 0:
+ * qn_eig3_jacobi (the map normals' solver, w unsorted), 1: sym_eig3 (the GICP covariances' and the Quatro normals', w descending).  a6 = (xx, xy, xz, yy, yz, zz)
+ * per matrix; w_out 3 n, v_out 9 n row major with the eigenvector of w[k] in column k.  A null pointer, which outside 0 .. 1 or n > QN_DEBUG_EIG3_MAX is
+ * QN_ERR_INVALID_ARG; n == 0 succeeds and writes nothing.  Nothing on the product path calls it. */
+#define QN_DEBUG_EIG3_MAX (1u << 24)
+int  qn_debug_eig3(qn_ctx*, int which, const double* a6, uint32_t n, double* w_out, double* v_out);
 int  qn_debug_get(qn_ctx*, const char* key, double* value);   /* "verify_mismatches" / "verify_passes" / "verify_first" after qn_debug_set("verify_track", 1); "feat_survivors" / "feat_fallbacks" (matrix-core feature matching) */
 int  qn_debug_get_grid(qn_ctx*, int which, double out[8]);
 int  qn_debug_get_partials(qn_ctx*, double* out, uint32_t* rows_per_buffer, double* state);   /* developer: both partial-row buffers and both state buffers after an align */

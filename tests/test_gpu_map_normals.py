@@ -3,17 +3,21 @@ qn_amd/mapnormals.py, run on the map the store itself downloads.  Bit for bit: c
 rerun.  Normals and curvature: within 2^-22 per component wherever the answer is well conditioned - the twin's relative eigen-gap (l1 - l0) / l2 >= 1e-3 and
 |n . (v - p)| >= 1e-6 |v - p| (without viewpoints the same margin between the normal's two largest components: the sign rule's own coin toss) - which is two
 f32 roundings of values <= 1 (2^-25 each) on top of two backward-stable f64 solves (angle error about 2^-53 / gap <= 1e-12), about 2^-24, times four.
-Elsewhere only unit length within 2^-22 is asked (and the curvature, which no gap touches).  The ill-conditioned share is printed and may not pass 10 % of
-the valid points.  The kernel's block is 256 points: the sizes 1, 2, 255, 256, 257 and 513 are its launch seams."""
+Elsewhere that comparison asks only for unit length within 2^-22 (and the curvature, which no gap touches).  The ill-conditioned share is printed and may not
+pass 10 % of the valid points.  Every valid point, ill conditioned or not, is held to its own covariance instead: the normal's Rayleigh quotient exceeds the
+smallest eigenvalue by at most 2^-44 of the trace, so no normal goes unchecked.  The kernel's block is 256 points: the sizes 1, 2, 255, 256, 257 and 513 are
+its launch seams."""
 import ctypes as C
 import math
 import subprocess
 import numpy as np
 import pytest
 from qn_amd import mapnormals as mn, staticmap as sm, synth
+import eig3_checks as chk
 
 pytestmark = pytest.mark.gpu
 TOL = 2.0 ** -22
+RAYLEIGH = 2.0 ** -44                                                # of trace(C): the bound on a normal's Rayleigh excess (equal_the_twin)
 B = 256                                                              # MN_BLOCK of csrc/qn_mapnormals.hip
 H = np.float32(0.3)
 SEN = synth.SpinningLidar(n_beams=16, n_cols=300)
@@ -63,6 +67,15 @@ def equal_the_twin(store, params, views, what, max_share=0.10):
     assert not dn.size or dn.max() <= TOL, (what, dn.max())
     assert not dc.size or dc.max() <= TOL, (what, dc.max())
     assert not unit.size or unit.max() <= TOL, (what, unit.max())
+    # every valid point, the ill-conditioned ones included: the normal's Rayleigh quotient on the point's own covariance lies within 2^-44 trace of the smallest
+    # eigenvalue.  A backward-stable solve puts the f64 normal's quotient within K eps ||C|| of l0 whatever the gap (K <= 128: tests/eig3_checks.py); rounding
+    # the normal to f32 adds at most l2 |e|^2 with |e| <= sqrt(3) 2^-25, about 2^-48.4 trace; 2^-44 is 16 times that.  So a collinear neighbourhood's normal
+    # is perpendicular to the line, and a nearly degenerate plane's lies in the right eigenspace - where the comparison above asks for unit length only.
+    C, tr = mn.covariance(want["count"], want["s1"], want["s2"])                     # (the kernel's C is the same bits)
+    excess = chk.rayleigh_excess(C[valid], tr[valid], got["normals"][valid]) if valid.any() else np.zeros(0)
+    print("%s: largest Rayleigh excess (n'Cn / n'n - l0) / trace over all %d valid points: 2^%.1f (bound 2^-44)"
+          % (what, valid.sum(), math.log2(max(float(excess.max()), 2.0 ** -99)) if excess.size else -99.0))
+    assert not excess.size or excess.max() <= RAYLEIGH, (what, excess.max())
     # a rerun returns the same bytes
     again = store.map_normals(engine.NormalParams(*params), views)
     a1, a2 = store.map_moments()
