@@ -29,6 +29,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "qn_eig3.cuh"
+#include "qn_step_math.cuh"
 
 namespace qn {
 
@@ -994,25 +995,7 @@ __device__ __forceinline__ void lane_ball_knn(const GridView& g, float qx, float
 }
 
 // ------------------------------------------------------------------ small dense f64 math
-struct M3 { double m[3][3]; };
-
-__device__ __forceinline__ M3 m3_inverse(const M3& a) {
-  const double (*m)[3] = a.m;
-  double c00 = m[1][1]*m[2][2] - m[1][2]*m[2][1];
-  double c01 = m[1][2]*m[2][0] - m[1][0]*m[2][2];
-  double c02 = m[1][0]*m[2][1] - m[1][1]*m[2][0];
-  double det = m[0][0]*c00 + m[0][1]*c01 + m[0][2]*c02;
-  double id = 1.0 / det;
-  M3 r;
-  r.m[0][0] = c00*id; r.m[1][0] = c01*id; r.m[2][0] = c02*id;
-  r.m[0][1] = (m[0][2]*m[2][1] - m[0][1]*m[2][2])*id;
-  r.m[1][1] = (m[0][0]*m[2][2] - m[0][2]*m[2][0])*id;
-  r.m[2][1] = (m[0][1]*m[2][0] - m[0][0]*m[2][1])*id;
-  r.m[0][2] = (m[0][1]*m[1][2] - m[0][2]*m[1][1])*id;
-  r.m[1][2] = (m[0][2]*m[1][0] - m[0][0]*m[1][2])*id;
-  r.m[2][2] = (m[0][0]*m[1][1] - m[0][1]*m[1][0])*id;
-  return r;
-}
+// M3 and m3_inverse, the adjugate inverse of C_B + R C_A R', are in qn_step_math.cuh: plain C++ there, so that a host build can test them.
 
 // sym_eig3, the symmetric 3 x 3 eigen decomposition of the covariance and normal kernels (eigenvalues descending, V columns), is in qn_eig3.cuh: plain C++ there,
 // so that a host build can test it.

@@ -1347,6 +1347,37 @@ extern "C" int qn_debug_eig3(qn_ctx* c, int which, const double* a6, uint32_t n,
   if (rc != QN_OK) { c->last_error = "debug_eig3: HIP call failed"; return rc; }
   return QN_OK;
 }
+namespace qn { hipError_t debug_launch_ldlt_solve6(const double* in, uint32_t n, double* out, hipStream_t stream); }      // qn_step_debug.hip
+// developer / test entry point: the device builds of the Gauss-Newton step's small dense routines on the caller's problems (k_debug_step_math, qn_selftest.cuh)
+extern "C" int qn_debug_step_math(qn_ctx* c, int which, const double* in, uint32_t n, double* out) {
+  static const uint32_t in_stride[QN_DEBUG_STEP_MATH_WHICH] = {43, 43, 59, 3, 9, 18}, out_stride[QN_DEBUG_STEP_MATH_WHICH] = {7, 6, 39, 9, 9, 3};
+  if (!c || !in || !out || which < 0 || which >= QN_DEBUG_STEP_MATH_WHICH || n > QN_DEBUG_STEP_MATH_MAX) return QN_ERR_INVALID_ARG;
+  if (n == 0) return QN_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t n_in = (size_t)in_stride[which] * n, n_out = (size_t)out_stride[which] * n;
+  double* d = nullptr;                                          // in | out | (which == 2) one GicpState per problem
+  HIPCHK(c, hipMalloc(&d, (n_in + n_out) * sizeof(double) + (which == 2 ? (size_t)n * sizeof(GicpState) : 0)));
+  double* d_out = d + n_in; GicpState* d_st = which == 2 ? reinterpret_cast<GicpState*>(d_out + n_out) : nullptr;
+  int rc = QN_OK;
+  if (hipMemcpyAsync(d, in, n_in * sizeof(double), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+      hipMemsetAsync(d_out, 0, n_out * sizeof(double) + (which == 2 ? (size_t)n * sizeof(GicpState) : 0), c->stream) != hipSuccess) rc = QN_ERR_HIP;
+  if (rc == QN_OK) {
+    const dim3 grid((n + QN_STEP_DEBUG_BLOCK - 1) / QN_STEP_DEBUG_BLOCK), block(QN_STEP_DEBUG_BLOCK);
+    switch (which) {
+      case 0: hipLaunchKernelGGL(k_debug_step_math<0>, grid, block, 0, c->stream, (const double*)d, n, d_out, d_st); break;
+      case 1: if (qn::debug_launch_ldlt_solve6(d, n, d_out, c->stream) != hipSuccess) rc = QN_ERR_HIP; break;      // (its kernel: qn_step_debug.hip)
+      case 2: hipLaunchKernelGGL(k_debug_step_math<2>, grid, block, 0, c->stream, (const double*)d, n, d_out, d_st); break;
+      case 3: hipLaunchKernelGGL(k_debug_step_math<3>, grid, block, 0, c->stream, (const double*)d, n, d_out, d_st); break;
+      case 4: hipLaunchKernelGGL(k_debug_step_math<4>, grid, block, 0, c->stream, (const double*)d, n, d_out, d_st); break;
+      default: hipLaunchKernelGGL(k_debug_step_math<5>, grid, block, 0, c->stream, (const double*)d, n, d_out, d_st); break;
+    }
+    if (rc != QN_OK || hipGetLastError() != hipSuccess || hipMemcpyAsync(out, d_out, n_out * sizeof(double), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+        hipStreamSynchronize(c->stream) != hipSuccess) rc = QN_ERR_HIP;
+  }
+  (void)hipFree(d);
+  if (rc != QN_OK) { c->last_error = "debug_step_math: HIP call failed"; return rc; }
+  return QN_OK;
+}
 extern "C" int qn_debug_get_counters(qn_ctx* c, uint32_t out[16]) {
   if (!c || !c->dbg_counters) return QN_ERR_INVALID_ARG;
   if (hipStreamSynchronize(c->stream) != hipSuccess) return QN_ERR_HIP;

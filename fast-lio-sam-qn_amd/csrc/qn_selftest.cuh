@@ -4,6 +4,7 @@
 // the registration path calls it.
 #pragma once
 #include "qn_device.cuh"
+#include "qn_gicp_kernels.cuh"
 
 namespace qn {
 
@@ -75,6 +76,77 @@ static __global__ void __launch_bounds__(QN_EIG3_DEBUG_BLOCK) k_debug_eig3(int w
     wo[r] = w[r];
 #pragma unroll
     for (int k = 0; k < 3; k++) vo[3 * r + k] = V[r][k];
+  }
+}
+
+// qn_debug_step_math: the device builds of the Gauss-Newton step's small dense f64 routines (qn_step_math.cuh, and d_propose of qn_gicp_kernels.cuh as it is) on
+// caller-supplied problems, one problem per lane in blocks of 64 lanes; the pivoted solve's SolveWork sits per lane in LDS (512 B x 64 = 32 KiB a block), as it sits
+// in LDS in the controller kernels.  WHICH and the record layouts: include/qn_engine.h at the declaration; WHICH = 1, the pivoted solve called directly, has its
+// kernel in qn_step_debug.hip, and that file says why it cannot stand here.  d_propose runs on the lane's own GicpState in global
+// memory (states, zeroed by the caller); it does not say which solve it took, so the unpivoted one is called once more on the same input for the path word.
+// tests/test_gpu_step_math.py holds the results to a 50-digit reference and to the host build of the same text.
+#define QN_STEP_DEBUG_BLOCK 64
+template <int WHICH>
+static __global__ void __launch_bounds__(QN_STEP_DEBUG_BLOCK) k_debug_step_math(const double* __restrict__ in, uint32_t n, double* __restrict__ out, GicpState* __restrict__ states) {
+  __shared__ SolveWork work[QN_STEP_DEBUG_BLOCK];
+  const uint32_t i = blockIdx.x * QN_STEP_DEBUG_BLOCK + threadIdx.x;
+  if (i >= n) return;
+  SolveWork* w = &work[threadIdx.x];                                   // (d_propose's; dropped where WHICH does not use it)
+  static_assert(WHICH != 1, "the pivoted solve's own kernel: qn_step_debug.hip");
+  if (WHICH == 0) {                                                    // A (36), lambda, b (6) -> x (6), ok
+    const double* r = in + 43 * (size_t)i; double* o = out + 7 * (size_t)i;
+    double rhs[6], x[6];
+    const bool ok = d_ldlt_solve6_fast(r, r[36], rhs, x, r + 37);
+#pragma unroll
+    for (int k = 0; k < 6; k++) o[k] = x[k];
+    o[6] = ok ? 1.0 : 0.0;
+  } else if (WHICH == 2) {                                             // H (36), b (6), lambda, x0 (16) -> d (6), delta (16), xi (16), path
+    const double* r = in + 59 * (size_t)i; double* o = out + 39 * (size_t)i;
+    GicpState* st = states + i;
+    for (int k = 0; k < 36; k++) st->H[k] = r[k];
+    for (int k = 0; k < 6; k++) st->b[k] = r[36 + k];
+    for (int k = 0; k < 16; k++) st->x0[k] = r[43 + k];
+    const double lambda = r[42];
+    d_propose(st, lambda, w);
+    for (int k = 0; k < 6; k++) o[k] = st->d[k];
+    for (int k = 0; k < 16; k++) { o[6 + k] = st->delta[k]; o[22 + k] = st->xi[k]; }
+    double Hl[36], rhs[6], dl[6];
+#pragma unroll
+    for (int a = 0; a < 6; a++)
+#pragma unroll
+      for (int b = 0; b < 6; b++) Hl[6 * a + b] = b <= a ? st->H[6 * a + b] : 0.0;
+    o[38] = d_ldlt_solve6_fast(Hl, lambda, rhs, dl, st->b) ? 0.0 : 1.0;
+  } else if (WHICH == 3) {                                             // om (3) -> R (9) row major
+    const double* r = in + 3 * (size_t)i; double* o = out + 9 * (size_t)i;
+    const double om[3] = {r[0], r[1], r[2]};
+    double R[3][3];
+    d_so3_exp(om, R);
+#pragma unroll
+    for (int a = 0; a < 3; a++)
+#pragma unroll
+      for (int b = 0; b < 3; b++) o[3 * a + b] = R[a][b];
+  } else if (WHICH == 4) {                                             // M (9) row major -> its inverse (9)
+    const double* r = in + 9 * (size_t)i; double* o = out + 9 * (size_t)i;
+    M3 m;
+#pragma unroll
+    for (int a = 0; a < 3; a++)
+#pragma unroll
+      for (int b = 0; b < 3; b++) m.m[a][b] = r[3 * a + b];
+    const M3 v = m3_inverse(m);
+#pragma unroll
+    for (int a = 0; a < 3; a++)
+#pragma unroll
+      for (int b = 0; b < 3; b++) o[3 * a + b] = v.m[a][b];
+  } else {                                                             // delta (16), rotation_epsilon, transformation_epsilon -> converged, mr, mt
+    const double* r = in + 18 * (size_t)i; double* o = out + 3 * (size_t)i;
+    double delta[16];
+#pragma unroll
+    for (int k = 0; k < 16; k++) delta[k] = r[k];
+    GicpConfig cfg = {};
+    cfg.rotation_epsilon = r[16]; cfg.transformation_epsilon = r[17];
+    double mr, mt;
+    o[0] = d_is_converged(delta, cfg, &mr, &mt) ? 1.0 : 0.0;
+    o[1] = mr; o[2] = mt;
   }
 }
 

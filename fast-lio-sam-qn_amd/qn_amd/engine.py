@@ -133,6 +133,24 @@ class Context:
         self.check(self._l.qn_debug_eig3(self.h, C.c_int(which), _p(a), C.c_uint32(n), _p(w), _p(V)))
         return w[:n], V[:n]
 
+    STEP_MATH_STRIDES = ((43, 7), (43, 6), (59, 39), (3, 9), (9, 9), (18, 3))          # (in, out) f64 per record of qn_debug_step_math, by `which`
+
+    def debug_step_math(self, which, records):
+        """qn_debug_step_math: the device build of one of the Gauss-Newton step's small dense routines (0 d_ldlt_solve6_fast, 1 d_ldlt_solve6, 2 d_propose,
+        3 d_so3_exp, 4 m3_inverse, 5 d_is_converged) on the rows of `records` (n, stride_in) -> (n, stride_out) f64; the record layouts are at the declaration
+        in include/qn_engine.h.  Test infrastructure."""
+        if not 0 <= which < len(self.STEP_MATH_STRIDES):
+            raise ValueError("debug_step_math: which = %r" % (which,))
+        si, so = self.STEP_MATH_STRIDES[which]
+        a = np.ascontiguousarray(records, dtype=np.float64).reshape(-1, si)
+        n = len(a)
+        if n == 0:
+            a = np.zeros((1, si))                                     # (an empty array may have no address; the call refuses null pointers)
+        out = np.zeros((max(n, 1), so))
+        self._l.qn_debug_step_math.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p]
+        self.check(self._l.qn_debug_step_math(self.h, C.c_int(which), _p(a), C.c_uint32(n), _p(out)))
+        return out[:n]
+
     def grid_info(self, which):
         out = np.zeros(8)
         self.check(self._l.qn_debug_get_grid(self.h, C.c_int(which), _p(out)))

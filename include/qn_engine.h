@@ -1150,6 +1150,20 @@ int  qn_debug_selftest(qn_ctx*, uint32_t n_waves, uint32_t seed, uint32_t* misma
  * QN_ERR_INVALID_ARG; n == 0 succeeds and writes nothing.  Nothing on the product path calls it. */
 #define QN_DEBUG_EIG3_MAX (1u << 24)
 int  qn_debug_eig3(qn_ctx*, int which, const double* a6, uint32_t n, double* w_out, double* v_out);
+/* developer / tests: the device builds of the Gauss-Newton step's small dense f64 routines (csrc/qn_step_math.cuh; d_propose of csrc/qn_gicp_kernels.cuh) on n
+ * caller-supplied problems, one per lane.  Records of f64 at a fixed stride per which, in[stride_in * i ..] -> out[stride_out * i ..]; matrices row major:
+ *   which  routine              in (stride)                                              out (stride)
+ *   0      d_ldlt_solve6_fast   A (36, full symmetric), lambda, b (6)            (43)    x (6), ok (1.0 / 0.0)                                         (7)
+ *   1      d_ldlt_solve6        the same; the right-hand side is -b              (43)    x (6)                                                         (6)
+ *   2      d_propose            H (36), b (6), lambda, x0 (16)                   (59)    d (6), delta (16), xi (16), path (0.0 fast, 1.0 pivoted)      (39)
+ *   3      d_so3_exp            om (3)                                           (3)     R (9)                                                         (9)
+ *   4      m3_inverse           M (9)                                            (9)     the inverse (9)                                               (9)
+ *   5      d_is_converged       delta (16), rotation_epsilon, transformation_epsilon (18)   converged (1.0 / 0.0), mr, mt                              (3)
+ * Every solve is of (A + lambda I) x = -b.  A null pointer, which outside 0 .. 5 or n > QN_DEBUG_STEP_MATH_MAX is QN_ERR_INVALID_ARG with nothing written;
+ * n == 0 succeeds and writes nothing.  Nothing on the product path calls it. */
+#define QN_DEBUG_STEP_MATH_WHICH 6
+#define QN_DEBUG_STEP_MATH_MAX (1u << 20)
+int  qn_debug_step_math(qn_ctx*, int which, const double* in, uint32_t n, double* out);
 int  qn_debug_get(qn_ctx*, const char* key, double* value);   /* "verify_mismatches" / "verify_passes" / "verify_first" after qn_debug_set("verify_track", 1); "feat_survivors" / "feat_fallbacks" (matrix-core feature matching) */
 int  qn_debug_get_grid(qn_ctx*, int which, double out[8]);
 int  qn_debug_get_partials(qn_ctx*, double* out, uint32_t* rows_per_buffer, double* state);   /* developer: both partial-row buffers and both state buffers after an align */
