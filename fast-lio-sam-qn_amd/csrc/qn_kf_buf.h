@@ -13,6 +13,14 @@
 #define QN_KFCHK(s, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { (void)hipGetLastError(); qn_kf_int_set_error((s), (std::string(#call) + " -> " + hipGetErrorString(e_)).c_str()); return QN_ERR_HIP; } } while (0)
 inline int qn_kf_fail(qn_kf_store* s, const char* msg) { qn_kf_int_set_error(s, msg); return QN_ERR_HIP; }
 inline size_t qn_up16(size_t b) { return (b + 15) & ~(size_t)15; }
+// `bytes` of device memory to the host on the store's stream, there when it returns: the one synchronisation of a getter that copies one buffer
+inline int qn_kf_download(qn_kf_store* s, void* dst, const void* src, size_t bytes) {
+  QN_KFCHK(s, hipSetDevice(qn_kf_int_device(s)));
+  const hipStream_t stream = qn_kf_int_stream(s);
+  QN_KFCHK(s, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, stream));
+  QN_KFCHK(s, hipStreamSynchronize(stream));
+  return QN_OK;
+}
 
 // `cap` elements of device (DevBuf) or pinned host (PinBuf) memory, freed with their owner.  Move-only.
 template <typename T, bool kPinned> struct KfBuf {

@@ -1,7 +1,14 @@
 // qn_map_compact.cuh - what the units around the map slot share on the device besides the cell walk (qn_mapoutliers.hip with qn_mapclusters.inc, qn_mapground.hip,
-// qn_staticmap.hip with qn_mapoccupancy.inc, qn_mapdistance.inc, qn_maproute.inc and qn_mapfrontier.inc, qn_verify.hip with qn_maplocalize.inc):
-//   counts    block_count: the lanes of a block for which each of up to five predicates holds, by ballot and popcount, one word per wave in LDS, into the
-//             block's own slot; k_slot_fold (one block) adds the slots up.  No atomics: integer sums, the same on every run.
+// qn_staticmap.hip with qn_mapoccupancy.inc, qn_mapdistance.inc, qn_maproute.inc and qn_mapfrontier.inc, qn_verify.hip with qn_maplocalize.inc); the lock-free
+// union-find of the clusters and the frontiers is qn_union_find.cuh, the dense grid's quantisation and index split are at the head of qn_mapoccupancy.inc:
+//   waves     wave_sum, wave_min, wave_max: a value folded over the 64 lanes by shuffles, lane 0 holds the result (int, u32, u64; f32 by fminf / fmaxf);
+//             wave_each_key: a callable run once per distinct key the lanes of a wave hold - the key, its first lane and the ballot of the lanes that share it -
+//             so that a wave folds its lanes of one key first and issues one set of atomics for them (k_mf_flatten, k_mf_relabel, k_mf_costs).
+//   counts    block_count: the lanes of a block for which each of up to five predicates holds, by ballot and popcount; block_sum, block_max: up to three values
+//             a lane folded over the block.  Each has one word per wave in LDS and a barrier of its own and writes the block's own slot; k_slot_fold (one
+//             block) adds the slots up, k_slot_max takes the largest.  No atomics: integer sums and extremes, the same on every run.  Three kernels whose calls
+//             measured slower with a fold's own barrier (k_md_axis<true>, k_mr_stats, k_mg_extent) keep their wave results in words of their own behind
+//             block_count's barrier, and say so where they do (profiles/EXPERIMENTS.md has the figures).
 //   scan      scan_row: the exclusive scan of a row of per-block counts in one block; k_scan_rows, a block per row, is the kernel over it (one row: a filter's
 //             or a list's counts, the last word the total; a row per centre, in place: the crop), k_static_scan (qn_staticmap.hip) the one with a tail of its own.
 //   rank      lane_rank: a lane's place among the lanes of its wave for which a predicate holds, by ballot and popcount; block_rank: its place in the block, the
@@ -24,10 +31,37 @@
 
 namespace {
 
-template <typename T> __device__ __forceinline__ T wave_sum(T v) {
+struct op_sum { template <typename T> __device__ T operator()(T a, T b) const { return a + b; } };
+struct op_min {
+  template <typename T> __device__ T operator()(T a, T b) const { return min(a, b); }
+  __device__ float operator()(float a, float b) const { return fminf(a, b); }
+};
+struct op_max {
+  template <typename T> __device__ T operator()(T a, T b) const { return max(a, b); }
+  __device__ float operator()(float a, float b) const { return fmaxf(a, b); }
+};
+
+// v folded over the wave (all 64 lanes here): lane 0 holds the result
+template <typename T, typename F> __device__ __forceinline__ T wave_fold(T v, F f) {
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
-  return v;                                              // (lane 0 holds the wave's sum)
+  for (int o = 32; o > 0; o >>= 1) v = f(v, __shfl_down(v, o));
+  return v;
+}
+template <typename T> __device__ __forceinline__ T wave_sum(T v) { return wave_fold(v, op_sum()); }
+template <typename T> __device__ __forceinline__ T wave_min(T v) { return wave_fold(v, op_min()); }
+template <typename T> __device__ __forceinline__ T wave_max(T v) { return wave_fold(v, op_max()); }
+
+// f(key, lead, same) once per distinct key among the lanes of the wave (all 64 here) for which has holds: lead the first lane that holds the key, same the
+// ballot of the lanes that do.  The loop is uniform over the wave, so f may shuffle and ballot
+template <typename K, typename F> __device__ __forceinline__ void wave_each_key(bool has, K key, F f) {
+  unsigned long long todo = __ballot(has);
+  while (todo) {
+    const int lead = __ffsll((long long)todo) - 1;
+    const K k0 = __shfl(key, lead);
+    const unsigned long long same = __ballot(has && key == k0);
+    f(k0, lead, same);
+    todo &= ~same;
+  }
 }
 
 // dst[j] = the number of lanes of this block (MO_BLOCK threads, all of them here) whose j-th predicate holds
@@ -48,6 +82,29 @@ template <typename... B> __device__ __forceinline__ void block_count(uint32_t* _
     dst[threadIdx.x] = acc;
   }
 }
+
+// dst[j] = the j-th value (one to three of type T) folded by f over the lanes of this block (MO_BLOCK threads, all of them here), behind a barrier of its own.
+// The words belong to the instantiation (F, T, the number of values), like block_count's: a kernel that calls the same one twice puts a __syncthreads() between
+// the calls, as k_mc_number does for block_count - the second call's writes would otherwise race with the first one's reads
+template <typename F, typename T, typename... V> __device__ __forceinline__ void block_fold(F f, T* __restrict__ dst, V... vals) {
+  constexpr int K = sizeof...(V);
+  static_assert(K >= 1 && K <= 3, "one to three values");
+  __shared__ T wk[K][MO_WAVES];
+  const T val[K] = {(T)vals...};
+#pragma unroll
+  for (int j = 0; j < K; j++) {
+    const T v = wave_fold(val[j], f);
+    if ((threadIdx.x & 63) == 0) wk[j][threadIdx.x >> 6] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < K) {
+    T acc = wk[threadIdx.x][0];
+    for (int w = 1; w < MO_WAVES; w++) acc = f(acc, wk[threadIdx.x][w]);
+    dst[threadIdx.x] = acc;
+  }
+}
+template <typename T, typename... V> __device__ __forceinline__ void block_sum(T* __restrict__ dst, V... vals) { block_fold(op_sum(), dst, vals...); }
+template <typename T, typename... V> __device__ __forceinline__ void block_max(T* __restrict__ dst, V... vals) { block_fold(op_max(), dst, vals...); }
 
 // one block: out[j] = the sum over the nb blocks of slots[K b + j], j < K
 template <typename W, int K>
@@ -70,6 +127,21 @@ __global__ void __launch_bounds__(MO_SCAN_BLOCK) k_slot_fold(const W* __restrict
     W acc = 0;
     for (int w = 0; w < MO_SCAN_BLOCK / 64; w++) acc += ws[threadIdx.x][w];
     out[threadIdx.x] = acc;
+  }
+}
+
+// one block: out[0] = the largest of the nb slots (0 without one); a template, like k_slot_fold, so that only a unit that launches it carries it
+template <typename W> __global__ void __launch_bounds__(MO_SCAN_BLOCK) k_slot_max(const W* __restrict__ slots, uint32_t nb, W* __restrict__ out) {
+  __shared__ W ws[MO_SCAN_BLOCK / 64];
+  W m = 0;
+  for (uint32_t b = threadIdx.x; b < nb; b += MO_SCAN_BLOCK) m = max(m, slots[b]);
+  m = wave_max(m);
+  if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = m;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    W top = 0;
+    for (int w = 0; w < MO_SCAN_BLOCK / 64; w++) top = max(top, ws[w]);
+    out[0] = top;
   }
 }
 

@@ -11,22 +11,13 @@
 //             class_mask == 0 the cloud is the slot itself (the index puts the non-finite records behind the finite ones).
 //   index     qn_kf_int_cell_index (qn_cloud.hip) at radius = tolerance over that one cloud, k_cell_gather (qn_cell_walk.cuh, with the exactness argument).
 //   hook      k_mc_hook, one point per lane, 256 lanes a block, in the sorted order: the walk's candidates with d2 <= r2 at a LOWER cloud index (each edge is
-//             met once, by its higher end; the lanes' counts are reduced through shuffles and LDS into the block's slot, k_slot_fold adds the slots up), and a
-//             lock-free union in parent[] over cloud indices: find the two roots, link the larger root under the smaller one only, by
-//             compare-and-swap(parent[hi], hi, lo), and on failure go on from the value the swap returned.
-//             Termination and safety: parent[x] <= x at every instant - it starts as x, a link stores a smaller root, path halving (an atomic min with a
-//             grandparent) only lowers it - so the forest is acyclic at every instant and a find, which moves to a strictly smaller index every trip, ends.  A
-//             value ever read from parent[x] stays an ancestor of x for good (links are added at roots only, halving shortcuts to an ancestor), so a stale
-//             read is never wrong, only longer.  A failed swap means parent[hi] was lowered by somebody else: the pair (a, b) the union goes on with is
-//             smaller in a well-founded order, so every union ends, and when it ends both ends have one root.  No lane ever waits on another lane, wave or
-//             block: there is no lock and no flag, a lane that loses a race has made progress through the winner's store.  Inside this kernel parent[] is
-//             read by agent-scope relaxed atomic loads and written by agent-scope atomics only (a plain load could be served from another XCD's stale L2
-//             line, and would then only walk a longer path; the atomics are what the argument needs).
+//             met once, by its higher end; block_sum puts the lanes' counts into the block's slot, k_slot_fold adds the slots up), and a
+//             lock-free union in parent[] over cloud indices (uf_unite: qn_union_find.cuh, with the safety and termination argument).
 //   flatten   k_mc_flatten, a launch of its own, so the kernel boundary makes parent[] coherent: root = the end of the parent chain, by plain loads, written at
 //             the map's own index; size by integer atomicAdd on the root's counter, one add per wave when its active lanes share a root (in cell-sorted order
 //             the common case), else one per lane.
 //   number    k_mc_number, one point per lane in the map's own order: ten counts a block (two five-predicate block_counts, k_slot_fold), the kept roots
-//             (root == own index, size in range) of every block for k_scan_rows, the largest size by a wave maximum and one atomicMax; k_mc_root_label gives
+//             (root == own index, size in range) of every block for k_scan_rows, the largest size by wave_max and one atomicMax; k_mc_root_label gives
 //             every kept root its rank - the cluster number - and every other root REJECTED; k_mc_finish copies label and size from the root to its members,
 //             writes NONE and the removed byte, and counts the records a drop keeps (k_scan_rows again: the offsets of the shared compaction).
 //   info      after the counts are on the host (the list is sized from C): k_mc_info, one member per lane in the sorted order: atomicMin / atomicMax on the
@@ -50,32 +41,6 @@ __device__ __forceinline__ bool mc_finite(const float4& p) { return isfinite(p.x
 // the ordered-integer image of an f32: ascending with the value, -0 below +0; and back
 __device__ __forceinline__ uint32_t mc_ord(float x) { const uint32_t b = __float_as_uint(x); return (b >> 31) ? ~b : (b | 0x80000000u); }
 __device__ __forceinline__ uint32_t mc_unord(uint32_t u) { return (u >> 31) ? (u & 0x7fffffffu) : ~u; }
-
-__device__ __forceinline__ uint32_t mc_ld(uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// the root of x as far as this lane can see; every trip moves to a strictly smaller index
-__device__ __forceinline__ uint32_t mc_find(uint32_t* parent, uint32_t x) {
-  for (;;) {
-    const uint32_t p = mc_ld(parent + x);
-    if (p == x) return x;
-    const uint32_t g = mc_ld(parent + p);
-    if (g == p) return p;
-    __hip_atomic_fetch_min(parent + x, g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);       // path halving: g is an ancestor of x and stays one
-    x = g;
-  }
-}
-
-// a and b into one tree: the larger root under the smaller one, never the other way
-__device__ __forceinline__ void mc_unite(uint32_t* parent, uint32_t a, uint32_t b) {
-  for (;;) {
-    a = mc_find(parent, a); b = mc_find(parent, b);
-    if (a == b) return;
-    const uint32_t hi = max(a, b), lo = min(a, b);
-    uint32_t seen = hi;
-    if (__hip_atomic_compare_exchange_strong(parent + hi, &seen, lo, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;
-    a = seen; b = lo;                                    // hi is a root no more: seen < hi is its new parent
-  }
-}
 
 // one record per lane in the map's own order: is it a member under the class mask; the block's members into its slot
 __global__ void __launch_bounds__(MO_BLOCK) k_mc_member(uint32_t n, const float4* __restrict__ map, const uint8_t* __restrict__ cls, uint32_t mask,
@@ -104,7 +69,6 @@ __global__ void __launch_bounds__(MO_BLOCK) k_mc_init(uint32_t nc, uint32_t* __r
 // one point per lane in the sorted order: the union of the point with every joined partner at a lower cloud index; the block's edges into its slot
 __global__ void __launch_bounds__(MO_BLOCK) k_mc_hook(const CellSeg S, const float4* __restrict__ spts, const uint32_t* __restrict__ cells, float r2,
                                                       uint32_t* parent, unsigned long long* __restrict__ slots) {
-  __shared__ unsigned long long ws[MO_WAVES];
   const uint32_t t = blockIdx.x * MO_BLOCK + threadIdx.x;
   unsigned long long e = 0;
   if (t < S.nfin) {                                      // (no early return: every thread of the block meets the barrier of the reduction)
@@ -112,17 +76,10 @@ __global__ void __launch_bounds__(MO_BLOCK) k_mc_hook(const CellSeg S, const flo
     const uint32_t qi = __float_as_uint(q.w);
     cell_walk(S, spts, cells, q, [&](uint32_t, const float4& p, float d2) {
       const uint32_t pj = __float_as_uint(p.w);
-      if (pj < qi && d2 <= r2) { e++; mc_unite(parent, qi, pj); }       // another index than the query's: a duplicate of it elsewhere is joined
+      if (pj < qi && d2 <= r2) { e++; uf_unite(parent, qi, pj); }       // another index than the query's: a duplicate of it elsewhere is joined
     });
   }
-  e = wave_sum(e);
-  if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = e;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned long long acc = 0;
-    for (int w = 0; w < MO_WAVES; w++) acc += ws[w];
-    slots[blockIdx.x] = acc;
-  }
+  block_sum(slots + blockIdx.x, e);
 }
 
 // one point per lane in the sorted order, after the hook's launch has ended: the root at the map's own index, the root's counter
@@ -174,9 +131,7 @@ __global__ void __launch_bounds__(MO_BLOCK) k_mc_number(uint32_t n, const float4
   __syncthreads();                                       // (the second count reuses the first one's words)
   block_count(slots + MC_STATS * (size_t)blockIdx.x + 5, isroot && sz > max_size, ok, mem && !ok, bad, false);
   block_count(blk + blockIdx.x, isroot && ok);
-  uint32_t big = isroot ? sz : 0u;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) big = max(big, __shfl_down(big, o));
+  const uint32_t big = wave_max(isroot ? sz : 0u);
   if ((threadIdx.x & 63) == 0 && big) atomicMax(largest, big);
 }
 
@@ -221,17 +176,6 @@ __global__ void __launch_bounds__(MO_BLOCK) k_mc_info_init(uint32_t C, qn_cluste
   for (int a = 0; a < 3; a++) { lo[a] = 0xffffffffu; hi[a] = 0u; o->sum_q[a] = 0; }
 }
 
-__device__ __forceinline__ uint32_t mc_wave_min(uint32_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_down(v, o));
-  return v;
-}
-__device__ __forceinline__ uint32_t mc_wave_max(uint32_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_down(v, o));
-  return v;
-}
-
 // one point per lane in the sorted order: a cluster's member into the cluster's record
 // (the coordinates come from the cloud itself: the index keeps a transformed copy, in which a -0 has become +0)
 __global__ void __launch_bounds__(MO_BLOCK) k_mc_info(const CellSeg S, const float4* __restrict__ spts, const float4* __restrict__ cloud, const uint32_t* __restrict__ orig,
@@ -259,8 +203,8 @@ __global__ void __launch_bounds__(MO_BLOCK) k_mc_info(const CellSeg S, const flo
   const int first = __ffsll((long long)bal) - 1;
   const int32_t l0 = __shfl(l, first);
   if (__ballot(act && l != l0) == 0) {                   // one cluster in the wave: the idle lanes carry the identities
-    ox = mc_wave_min(ox); oy = mc_wave_min(oy); oz = mc_wave_min(oz);
-    hx = mc_wave_max(hx); hy = mc_wave_max(hy); hz = mc_wave_max(hz);
+    ox = wave_min(ox); oy = wave_min(oy); oz = wave_min(oz);
+    hx = wave_max(hx); hy = wave_max(hy); hz = wave_max(hz);
     qx = wave_sum(qx); qy = wave_sum(qy); qz = wave_sum(qz);
     if ((threadIdx.x & 63) != 0) return;                 // (lane 0 holds the wave's results)
     l = l0;
@@ -442,11 +386,7 @@ extern "C" int qn_kf_map_cluster_list(qn_kf_store* s, qn_cluster_info* out, uint
   if (out && capacity < o->clusters) return QN_ERR_CAPACITY;
   *count_out = o->clusters;
   if (!out || !o->clusters) return QN_OK;
-  QN_KFCHK(s, hipSetDevice(qn_kf_int_device(s)));
-  hipStream_t stream = qn_kf_int_stream(s);
-  QN_KFCHK(s, hipMemcpyAsync(out, o->info.p, sizeof(qn_cluster_info) * (size_t)o->clusters, hipMemcpyDeviceToHost, stream));
-  QN_KFCHK(s, hipStreamSynchronize(stream));
-  return QN_OK;
+  return qn_kf_download(s, out, o->info.p, sizeof(qn_cluster_info) * (size_t)o->clusters);
 }
 
 extern "C" int qn_kf_map_drop_rejected_clusters(qn_kf_store* s, const float** d_xyzi_out, uint32_t* n_out) {

@@ -10,9 +10,9 @@
 //             distance to the answer, not max_dist.  Plain global loads: the neighbours of a block's voxels are the neighbours' blocks' voxels, served by L2.
 //             A result above max_dist^2 becomes FAR: a site within max_dist has every per-axis offset within max_dist, so it survives the windowed passes.
 //             The z pass (LAST) also counts: sites, reached and far voxels by block_count into the block's slot, the block's largest and summed reached d2
-//             into slots of their own; k_slot_fold adds the slots up, k_md_fold_max takes the largest.
+//             into slots of their own (wave_max, wave_sum and block_count's barrier: measured faster than block_max and block_sum); k_slot_fold adds the slots up, k_slot_max takes the largest.
 //   slice     k_md_slice, one column per lane: the smallest d2 over a band of layers.
-//   query     k_md_query, one point per lane: the voxel of an f64 world point by the occupancy map's quantisation (the only floating point in this file's kernels).
+//   query     k_md_query, one point per lane: the voxel of an f64 world point by the occupancy map's quantisation (oc_voxel; the only floating point in this file's kernels).
 // Every voxel and every slot has one writer, nothing is read and modified in place; no scratch memory, no dynamically indexed private array.  Host synchronisations of qn_kf_map_distance: one - the statistics.
 // Part of qn_staticmap.hip's translation unit (included after qn_mapoccupancy.inc): the field hangs on that file's OccState and takes no slot of its own.
 
@@ -96,36 +96,20 @@ __global__ void __launch_bounds__(MD_BLOCK) k_md_axis(uint32_t cells, uint32_t s
     g[i] = (uint16_t)best;
   }
   if (LAST) {
+    const bool in = i < cells, reached = in && best != 0 && best != QN_DIST_FAR;
+    const uint32_t m = reached ? best : 0u;
     __shared__ unsigned long long wt[MO_WAVES];
     __shared__ uint32_t wm[MO_WAVES];
-    const bool in = i < cells, reached = in && best != 0 && best != QN_DIST_FAR;
-    uint32_t m = reached ? best : 0u;
     const unsigned long long t = wave_sum((unsigned long long)m);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = max(m, (uint32_t)__shfl_down(m, o));
-    if ((threadIdx.x & 63) == 0) { wt[threadIdx.x >> 6] = t; wm[threadIdx.x >> 6] = m; }
-    block_count(cslots + 3 * (size_t)blockIdx.x, in && best == 0, reached, in && best == QN_DIST_FAR);      // (its barrier is the one the sums wait for)
+    const uint32_t mm = wave_max(m);
+    if ((threadIdx.x & 63) == 0) { wt[threadIdx.x >> 6] = t; wm[threadIdx.x >> 6] = mm; }
+    // its barrier is the one the sums wait for: block_max and block_sum, two barriers more, cost the call 0.8 % at 1e7 voxels (profiles/EXPERIMENTS.md)
+    block_count(cslots + 3 * (size_t)blockIdx.x, in && best == 0, reached, in && best == QN_DIST_FAR);
     if (threadIdx.x == 0) {
       unsigned long long acc = 0; uint32_t top = 0;
       for (int w = 0; w < MO_WAVES; w++) { acc += wt[w]; top = max(top, wm[w]); }
       tslots[blockIdx.x] = acc; mslots[blockIdx.x] = top;
     }
-  }
-}
-
-// one block: out[0] = the largest of the nb slots (0 without one)
-__global__ void __launch_bounds__(MO_SCAN_BLOCK) k_md_fold_max(const uint32_t* __restrict__ slots, uint32_t nb, uint32_t* __restrict__ out) {
-  __shared__ uint32_t ws[MO_SCAN_BLOCK / 64];
-  uint32_t m = 0;
-  for (uint32_t b = threadIdx.x; b < nb; b += MO_SCAN_BLOCK) m = max(m, slots[b]);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) m = max(m, (uint32_t)__shfl_down(m, o));
-  if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = m;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint32_t top = 0;
-    for (int w = 0; w < MO_SCAN_BLOCK / 64; w++) top = max(top, ws[w]);
-    out[0] = top;
   }
 }
 
@@ -138,25 +122,15 @@ __global__ void __launch_bounds__(MD_BLOCK) k_md_slice(uint32_t cols, const uint
   out[c] = (uint16_t)v;
 }
 
-// one point per lane: its voxel by the occupancy map's quantisation (f64, every operation rounded on its own, half to even), then the field's value and the
-// voxel's class there; FAR and OUTSIDE for a point that is not finite, 2^20 voxels or more from the origin, or outside the grid
+// one point per lane: its voxel by the occupancy map's quantisation (oc_voxel: qn_mapoccupancy.inc), then the field's value and the voxel's class there; FAR and
+// OUTSIDE for a point that is not finite, 2^20 voxels or more from the origin, or outside the grid
 __global__ void __launch_bounds__(MD_BLOCK) k_md_query(uint32_t n, const double* __restrict__ xyz, double inv, const OcGrid G, uint32_t D, const uint16_t* __restrict__ d2,
                                                        const uint8_t* __restrict__ cls, uint16_t* __restrict__ d2_out, uint8_t* __restrict__ cls_out) {
   const uint32_t i = blockIdx.x * MD_BLOCK + threadIdx.x;
   if (i >= n) return;
-  const uint32_t side[3] = {G.W, G.H, D};
-  long long c[3];
-  bool ok = true;
-#pragma unroll
-  for (int k = 0; k < 3; k++) {
-    const double t = xyz[3 * (size_t)i + k] * inv;
-    const bool in = fabs(t) < OC_COORD_LIMIT;                       // (a NaN fails the comparison, an infinity too)
-    c[k] = in ? (((long long)rint(t * 1024.0)) >> OC_S) - G.minc[k] : -1;
-    ok = ok && in && c[k] >= 0 && c[k] < (long long)side[k];
-  }
-  uint32_t v = QN_DIST_FAR, q = QN_DIST_OUTSIDE;
-  if (ok) {
-    const size_t lin = ((size_t)c[2] * G.H + (size_t)c[1]) * G.W + (size_t)c[0];
+  uint32_t x, y, z, v = QN_DIST_FAR, q = QN_DIST_OUTSIDE;
+  if (oc_voxel(xyz, i, inv, G, D, 0u, &x, &y, &z)) {
+    const size_t lin = ((size_t)z * G.H + y) * G.W + x;
     v = d2[lin]; q = cls[lin];
   }
   d2_out[i] = (uint16_t)v; cls_out[i] = (uint8_t)q;
@@ -194,8 +168,7 @@ extern "C" int qn_kf_map_distance(qn_kf_store* s, const qn_distance_params* para
   if (!s || !params || !stats_out) return QN_ERR_INVALID_ARG;
   const qn_distance_params P = *params;
   if (P.site_mask == 0 || (P.site_mask & ~7u) || P.max_dist < 1 || P.max_dist > QN_DIST_MAX_RADIUS || P.reserved[0] != 0 || P.reserved[1] != 0) return QN_ERR_INVALID_ARG;
-  StaticState* unit = (StaticState*)qn_kf_int_ext(s, QN_KF_INT_EXT_STATIC);
-  OccState* o = unit && unit->occ && unit->occ->live ? unit->occ.get() : nullptr;
+  OccState* o = oc_live_mut(s);
   if (!o) return QN_ERR_NOT_READY;
   const qn_occupancy_grid& g = o->info;
   const uint32_t cells = g.width * g.height * g.depth, cb = (cells + MD_BLOCK - 1) / MD_BLOCK;
@@ -227,7 +200,7 @@ extern "C" int qn_kf_map_distance(qn_kf_store* s, const qn_distance_params* para
                        (uint32_t*)nullptr, (unsigned long long*)nullptr);
     hipLaunchKernelGGL(k_md_axis<true>, dim3(cb), dim3(MD_BLOCK), 0, str, cells, WH, g.depth, P.max_dist, (const uint16_t*)st->tmp.p, st->d2.p, d_slots, d_mslots, d_tslots);
     hipLaunchKernelGGL((k_slot_fold<uint32_t, 3>), dim3(1), dim3(MO_SCAN_BLOCK), 0, str, (const uint32_t*)d_slots, cb, d_sums);
-    hipLaunchKernelGGL(k_md_fold_max, dim3(1), dim3(MO_SCAN_BLOCK), 0, str, (const uint32_t*)d_mslots, cb, d_sums + 3);
+    hipLaunchKernelGGL(k_slot_max<uint32_t>, dim3(1), dim3(MO_SCAN_BLOCK), 0, str, (const uint32_t*)d_mslots, cb, d_sums + 3);
     hipLaunchKernelGGL((k_slot_fold<unsigned long long, 1>), dim3(1), dim3(MO_SCAN_BLOCK), 0, str, (const unsigned long long*)d_tslots, cb, (unsigned long long*)(d_small + 16));
     QN_KFCHK(s, hipGetLastError());
     QN_KFCHK(s, hipMemcpyAsync(h, d_small, 32, hipMemcpyDeviceToHost, str));
@@ -252,11 +225,7 @@ extern "C" int qn_kf_map_distance_grid(qn_kf_store* s, qn_occupancy_grid* info_o
   const size_t cells = (size_t)g.width * g.height * g.depth;
   *info_out = g; *params_out = d->params;
   if (!cells || !d2_out) return QN_OK;
-  QN_KFCHK(s, hipSetDevice(qn_kf_int_device(s)));
-  const hipStream_t str = qn_kf_int_stream(s);
-  QN_KFCHK(s, hipMemcpyAsync(d2_out, d->d2.p, sizeof(uint16_t) * cells, hipMemcpyDeviceToHost, str));
-  QN_KFCHK(s, hipStreamSynchronize(str));
-  return QN_OK;
+  return qn_kf_download(s, d2_out, d->d2.p, sizeof(uint16_t) * cells);
 }
 
 extern "C" int qn_kf_map_distance_slice(qn_kf_store* s, int32_t iz_lo, int32_t iz_hi, uint16_t* d2_out) {
@@ -275,9 +244,7 @@ extern "C" int qn_kf_map_distance_slice(qn_kf_store* s, int32_t iz_lo, int32_t i
   if (!d_out) return qn_kf_fail(s, "qn_kf_map_distance_slice: scratch allocation failed");
   hipLaunchKernelGGL(k_md_slice, dim3((cols + MD_BLOCK - 1) / MD_BLOCK), dim3(MD_BLOCK), 0, str, cols, (const uint16_t*)d->d2.p, (uint32_t)lo, (uint32_t)hi, d_out);
   QN_KFCHK(s, hipGetLastError());
-  QN_KFCHK(s, hipMemcpyAsync(d2_out, d_out, sizeof(uint16_t) * (size_t)cols, hipMemcpyDeviceToHost, str));
-  QN_KFCHK(s, hipStreamSynchronize(str));
-  return QN_OK;
+  return qn_kf_download(s, d2_out, d_out, sizeof(uint16_t) * (size_t)cols);
 }
 
 extern "C" int qn_kf_map_distance_query(qn_kf_store* s, const double* xyz, uint32_t n, uint16_t* d2_out, uint8_t* class_out) {
@@ -297,12 +264,8 @@ extern "C" int qn_kf_map_distance_query(qn_kf_store* s, const double* xyz, uint3
   uint16_t* d_d2 = (uint16_t*)qn_kf_int_scratch(s, 1, sizeof(uint16_t) * (size_t)n);
   uint8_t* d_cls = (uint8_t*)qn_kf_int_scratch(s, 2, n);
   if (!d_xyz || !d_d2 || !d_cls) return qn_kf_fail(s, "qn_kf_map_distance_query: scratch allocation failed");
-  OcGrid G;
-  memset(&G, 0, sizeof(G));
-  for (int k = 0; k < 3; k++) G.minc[k] = g.minc[k];
-  G.W = g.width; G.H = g.height; G.cells = g.width * g.height * g.depth;
   QN_KFCHK(s, hipMemcpyAsync(d_xyz, xyz, sizeof(double) * 3 * (size_t)n, hipMemcpyHostToDevice, str));
-  hipLaunchKernelGGL(k_md_query, dim3((n + MD_BLOCK - 1) / MD_BLOCK), dim3(MD_BLOCK), 0, str, n, (const double*)d_xyz, 1.0 / g.voxel, G, g.depth, (const uint16_t*)d->d2.p,
+  hipLaunchKernelGGL(k_md_query, dim3((n + MD_BLOCK - 1) / MD_BLOCK), dim3(MD_BLOCK), 0, str, n, (const double*)d_xyz, 1.0 / g.voxel, oc_grid(g), g.depth, (const uint16_t*)d->d2.p,
                      (const uint8_t*)o->cls.p, d_d2, d_cls);
   QN_KFCHK(s, hipGetLastError());
   QN_KFCHK(s, hipMemcpyAsync(d2_out, d_d2, sizeof(uint16_t) * (size_t)n, hipMemcpyDeviceToHost, str));

@@ -13,22 +13,22 @@
 //   mark      k_mf_mark, one voxel per lane in linear order: the class byte, and for a candidate its six neighbours by plain global loads - the x neighbours lie
 //             in the cache lines the block reads anyway, the y and z neighbours are other blocks' rows, served by L2; nothing is staged in LDS.  label = the own
 //             linear index for a frontier voxel, MF_NOLABEL otherwise; the voxel's tile flagged (a plain store of 1, every writer the same value); candidates
-//             and frontier voxels counted by block_count, the faces summed through the waves.
+//             and frontier voxels counted by block_count, the faces summed by block_sum.
 //   tile      k_mf_tile, one MF_T^3 tile per block, one voxel per lane; a block whose tile holds no frontier voxel returns after one load.  The tile's voxels
 //             carry their place in the tile in LDS (a one-voxel rim of MF_NOLABEL spares the bounds tests) and fall to the smallest place among their 26
 //             neighbours and then to that voxel's own value (a pointer jump), in place, until nothing falls (__syncthreads_or).  Places order like linear
 //             indices, so every voxel ends at the smallest linear index of its component within the tile, and writes that.
 //   merge     k_mf_merge, one voxel per lane: a frontier voxel on a tile's rim unites, for each of its 13 neighbours at a smaller linear index that lie in
-//             another tile and are frontier voxels, the two roots: find with path halving, then atomicMin on the larger root, retried until stable.  Every value
-//             ever stored at label[v] is a voxel of v's component and no larger than v, so a stale read only costs another step.
+//             another tile and are frontier voxels, the two roots by uf_unite_min, label[] the parent array (qn_union_find.cuh: the lock-free union-find the
+//             clusters use, with the safety and termination argument; the link here is its atomic-min entry point, measured faster on this call).
 //   flatten   k_mf_flatten: every label becomes its root; the root's size by atomicAdd in a transient word per voxel (scratch, not kept).
 //   number    k_mf_roots counts the roots (components), those below min_size and the largest, and the kept roots per block; k_scan_rows gives their offsets
 //             and R (the first host synchronisation).  k_mf_pick writes a region's row at its block_rank and the number (or REJECTED) into the root's transient
 //             word; k_mf_relabel rewrites the label volume and adds a region voxel's indices and faces into a partial row by integer atomic min, max and add -
 //             the voxels of a wave that share a region folded first, and each block into one of up to MF_COPIES copies of the table (k_mf_rows_init), which
 //             k_mf_rows folds into the rows: a region that holds most of the frontier would otherwise serialise every wave on one cache line (measured: 6 ms
-//             of 12.6 on 1.08e7 voxels).  k_mf_flatten and k_mf_costs fold a wave's voxels of one root or region the same way.  k_slot_fold and k_md_fold_max
-//             fold the statistics (the second and last synchronisation).
+//             of 12.6 on 1.08e7 voxels).  k_mf_flatten and k_mf_costs fold a wave's voxels of one root or region the same way (wave_each_key).
+//             k_slot_fold and k_slot_max fold the statistics (the second and last synchronisation).
 //   getters   k_mf_list_flag / k_mf_list_pick: the stable compaction of qn_kf_map_occupancy_list.  k_mf_costs: one voxel per lane, a 64-bit atomicMin of
 //             (cost << 32) | linear index per region; the host unpacks it.
 // MF_T = 8 and MF_COPIES = 32 are untuned choices.  No scratch memory, no dynamically indexed private array, no floating point; plain vector stores and vector atomics only.
@@ -66,7 +66,6 @@ __device__ __forceinline__ uint32_t mf_faces(const uint8_t* __restrict__ cls, ui
 __global__ void __launch_bounds__(MF_BLOCK) k_mf_mark(uint32_t cells, uint32_t W, uint32_t H, uint32_t D, const uint8_t* __restrict__ cls, uint32_t fmask, uint32_t umask,
                                                       uint32_t edge, int32_t lo, int32_t hi, uint32_t tiles_x, uint32_t tiles_y, uint32_t* __restrict__ label,
                                                       uint32_t* __restrict__ tflag, uint32_t* __restrict__ slots) {
-  __shared__ uint32_t wf[MO_WAVES];
   const uint32_t i = blockIdx.x * MF_BLOCK + threadIdx.x;
   bool cand = false;
   uint32_t f = 0;
@@ -77,14 +76,8 @@ __global__ void __launch_bounds__(MF_BLOCK) k_mf_mark(uint32_t cells, uint32_t W
     label[i] = f ? i : MF_NOLABEL;
     if (f) tflag[((size_t)(z / MF_T) * tiles_y + y / MF_T) * tiles_x + x / MF_T] = 1u;
   }
-  const uint32_t wsum = wave_sum(f);
-  if ((threadIdx.x & 63) == 0) wf[threadIdx.x >> 6] = wsum;
-  block_count(slots + 3 * (size_t)blockIdx.x, cand, f != 0);          // (its barrier is the one the faces wait for)
-  if (threadIdx.x == 2) {
-    uint32_t acc = 0;
-    for (int w = 0; w < MO_WAVES; w++) acc += wf[w];
-    slots[3 * (size_t)blockIdx.x + 2] = acc;
-  }
+  block_count(slots + 3 * (size_t)blockIdx.x, cand, f != 0);
+  block_sum(slots + 3 * (size_t)blockIdx.x + 2, f);
 }
 
 // the LDS position (with the rim) of the tile voxel at place l
@@ -128,35 +121,11 @@ __global__ void __launch_bounds__(MF_TILE) k_mf_tile(uint32_t* __restrict__ labe
   if (front && cur != threadIdx.x) label[g] = ((bz * MF_T + (cur >> 6)) * H + by * MF_T + ((cur >> 3) & 7u)) * W + bx * MF_T + (cur & 7u);
 }
 
-__device__ __forceinline__ uint32_t mf_load(uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// the root of x's tree, halving the path on the way: a voxel's parent becomes its grandparent (atomicMin: a value only ever falls)
-__device__ __forceinline__ uint32_t mf_find(uint32_t* label, uint32_t x) {
-  uint32_t p = mf_load(label + x);
-  while (p != x) {
-    const uint32_t g = mf_load(label + p);
-    if (g != p) atomicMin(label + x, g);
-    x = p; p = g;
-  }
-  return x;
-}
-
-// the trees of a and b become one: the larger root is hung below the smaller
-__device__ __forceinline__ void mf_unite(uint32_t* label, uint32_t a, uint32_t b) {
-  for (;;) {
-    a = mf_find(label, a); b = mf_find(label, b);
-    if (a == b) return;
-    if (a < b) { const uint32_t t = a; a = b; b = t; }
-    const uint32_t old = atomicMin(label + a, b);                    // a was a root when it read label[a] == a
-    if (old == a) return;
-    a = old;                                                         // it no longer was: its parent of then (< a) and b are still to be united
-  }
-}
-
-// one voxel per lane: a frontier voxel on its tile's rim and its frontier neighbours in other tiles at smaller linear indices (every touching pair once)
+// one voxel per lane: a frontier voxel on its tile's rim and its frontier neighbours in other tiles at smaller linear indices (every touching pair once); label[]
+// is the parent array of uf_unite_min (qn_union_find.cuh, with the safety and termination argument): k_mf_tile left every word at most its own index
 __global__ void __launch_bounds__(MF_BLOCK) k_mf_merge(uint32_t cells, uint32_t W, uint32_t H, uint32_t D, uint32_t* label) {
   const uint32_t i = blockIdx.x * MF_BLOCK + threadIdx.x;
-  if (i >= cells || mf_load(label + i) == MF_NOLABEL) return;
+  if (i >= cells || uf_load(label + i) == MF_NOLABEL) return;
   const uint32_t row = i / W;
   const int x = (int)(i - row * W), z = (int)(row / H), y = (int)(row - (uint32_t)z * H);
   const int lx = x & 7, ly = y & 7, lz = z & 7;
@@ -172,7 +141,7 @@ __global__ void __launch_bounds__(MF_BLOCK) k_mf_merge(uint32_t cells, uint32_t 
         if (nx < 0 || nx >= (int)W || ny < 0 || ny >= (int)H || nz < 0 || nz >= (int)D) continue;
         if ((nx >> 3) == (x >> 3) && (ny >> 3) == (y >> 3) && (nz >> 3) == (z >> 3)) continue;      // the same tile: k_mf_tile joined them
         const uint32_t j = ((uint32_t)nz * H + (uint32_t)ny) * W + (uint32_t)nx;
-        if (mf_load(label + j) != MF_NOLABEL) mf_unite(label, i, j);
+        if (uf_load(label + j) != MF_NOLABEL) uf_unite_min(label, i, j);
       }
 }
 
@@ -181,41 +150,27 @@ __global__ void __launch_bounds__(MF_BLOCK) k_mf_flatten(uint32_t cells, uint32_
   const uint32_t i = blockIdx.x * MF_BLOCK + threadIdx.x;
   uint32_t r = MF_NOLABEL;
   if (i < cells) {
-    uint32_t p = mf_load(label + i);
+    uint32_t p = uf_load(label + i);
     if (p != MF_NOLABEL) {
       r = i;
-      while (p != r) { r = p; p = mf_load(label + r); }              // (a root's word is never written here, a voxel's word only with its root)
+      while (p != r) { r = p; p = uf_load(label + r); }              // (a root's word is never written here, a voxel's word only with its root)
       if (r != i) label[i] = r;
     }
   }
-  unsigned long long todo = __ballot(r != MF_NOLABEL);
-  while (todo) {                                                     // uniform over the wave: one trip per root the wave holds
-    const int lead = __ffsll((long long)todo) - 1;
-    const uint32_t r0 = __shfl(r, lead);
-    const unsigned long long same = __ballot(r == r0);
+  wave_each_key(r != MF_NOLABEL, r, [&](uint32_t r0, int lead, unsigned long long same) {
     if ((int)(threadIdx.x & 63) == lead) atomicAdd(aux + r0, (uint32_t)__popcll(same));
-    todo &= ~same;
-  }
+  });
 }
 
 // one voxel per lane: kept[b] = the block's roots with size >= min_size, slots[2 b ..] = its roots and those below min_size, mslots[b] = its largest size
 __global__ void __launch_bounds__(MF_BLOCK) k_mf_roots(uint32_t cells, const uint32_t* __restrict__ label, const uint32_t* __restrict__ aux, uint32_t min_size,
                                                        uint32_t* __restrict__ kept, uint32_t* __restrict__ slots, uint32_t* __restrict__ mslots) {
-  __shared__ uint32_t wm[MO_WAVES];
   const uint32_t i = blockIdx.x * MF_BLOCK + threadIdx.x;
   const bool root = i < cells && label[i] == i;
   const uint32_t size = root ? aux[i] : 0u;
-  uint32_t m = size;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) m = max(m, (uint32_t)__shfl_down(m, o));
-  if ((threadIdx.x & 63) == 0) wm[threadIdx.x >> 6] = m;
   block_count(kept + blockIdx.x, root && size >= min_size);
   block_count(slots + 2 * (size_t)blockIdx.x, root, root && size < min_size);      // (another instance, with LDS words of its own)
-  if (threadIdx.x == 2) {
-    uint32_t top = 0;
-    for (int w = 0; w < MO_WAVES; w++) top = max(top, wm[w]);
-    mslots[blockIdx.x] = top;
-  }
+  block_max(mslots + blockIdx.x, size);
 }
 
 // one voxel per lane: a kept root's row at its rank, in ascending root; aux[root] = the region number, or QN_FRONTIER_REJECTED
@@ -232,17 +187,6 @@ __global__ void __launch_bounds__(MF_BLOCK) k_mf_pick(uint32_t cells, const uint
   } else if (root) {
     aux[i] = (uint32_t)QN_FRONTIER_REJECTED;
   }
-}
-
-__device__ __forceinline__ int wave_min_all(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o));
-  return v;
-}
-__device__ __forceinline__ int wave_max_all(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o));
-  return v;
 }
 
 // n partial rows: the neutral elements of the box, zero faces and sums
@@ -275,16 +219,12 @@ __global__ void __launch_bounds__(MF_BLOCK) k_mf_relabel(uint32_t cells, uint32_
     x = (int)(i - row * W); z = (int)(row / H); y = (int)(row - (uint32_t)z * H);
     f = (int)mf_faces(cls, i, (uint32_t)x, (uint32_t)y, (uint32_t)z, W, H, D, umask, edge);
   }
-  unsigned long long todo = __ballot(in);
-  while (todo) {                                                     // uniform over the wave: one trip per region the wave holds
-    const int lead = __ffsll((long long)todo) - 1;
-    const int k0 = __shfl(k, lead);
-    const bool mine = in && k == k0;
-    const unsigned long long same = __ballot(mine);
-    const int x0 = wave_min_all(mine ? x : INT_MAX), y0 = wave_min_all(mine ? y : INT_MAX), z0 = wave_min_all(mine ? z : INT_MAX);
-    const int x1 = wave_max_all(mine ? x : INT_MIN), y1 = wave_max_all(mine ? y : INT_MIN), z1 = wave_max_all(mine ? z : INT_MIN);
+  wave_each_key(in, k, [&](int32_t k0, int, unsigned long long same) {      // one trip per region the wave holds
+    const bool mine = (same >> (threadIdx.x & 63)) & 1ull;
+    const int x0 = wave_min(mine ? x : INT_MAX), y0 = wave_min(mine ? y : INT_MAX), z0 = wave_min(mine ? z : INT_MAX);
+    const int x1 = wave_max(mine ? x : INT_MIN), y1 = wave_max(mine ? y : INT_MIN), z1 = wave_max(mine ? z : INT_MIN);
     const uint32_t sx = wave_sum(mine ? (uint32_t)x : 0u), sy = wave_sum(mine ? (uint32_t)y : 0u), sz = wave_sum(mine ? (uint32_t)z : 0u), sf = wave_sum(mine ? (uint32_t)f : 0u);
-    if ((threadIdx.x & 63) == 0) {                                   // (lane 0 holds the sums)
+    if ((threadIdx.x & 63) == 0) {                                   // (lane 0 holds the results)
       qn_frontier_info* r = part + (size_t)(blockIdx.x & pmask) * R + (uint32_t)k0;
       atomicMin(&r->lo[0], x0); atomicMin(&r->lo[1], y0); atomicMin(&r->lo[2], z0);
       atomicMax(&r->hi[0], x1); atomicMax(&r->hi[1], y1); atomicMax(&r->hi[2], z1);
@@ -292,8 +232,7 @@ __global__ void __launch_bounds__(MF_BLOCK) k_mf_relabel(uint32_t cells, uint32_
       atomicAdd((unsigned long long*)&r->sum[0], (unsigned long long)sx); atomicAdd((unsigned long long*)&r->sum[1], (unsigned long long)sy);
       atomicAdd((unsigned long long*)&r->sum[2], (unsigned long long)sz);
     }
-    todo &= ~same;
-  }
+  });
   block_count(slots + 2 * (size_t)blockIdx.x, in, k == QN_FRONTIER_REJECTED);
 }
 
@@ -328,11 +267,7 @@ __global__ void __launch_bounds__(MF_BLOCK) k_mf_list_pick(uint32_t cells, const
   const int32_t k = i < cells ? label[i] : QN_FRONTIER_NONE;
   const bool keep = k != QN_FRONTIER_NONE;
   const size_t j = block_rank(keep, off[blockIdx.x]);
-  if (keep) {
-    const uint32_t row = i / W;
-    ijk[3 * j] = (int32_t)(i - row * W); ijk[3 * j + 1] = (int32_t)(row % H); ijk[3 * j + 2] = (int32_t)(row / H);
-    lab[j] = k;
-  }
+  if (keep) { oc_ijk(i, W, H, ijk + 3 * j); lab[j] = k; }
 }
 
 // one voxel per lane: a region voxel the route field reaches offers (cost << 32) | linear index to its region; cols = W H, planar: a voxel reads its column
@@ -345,17 +280,10 @@ __global__ void __launch_bounds__(MF_BLOCK) k_mf_costs(uint32_t cells, uint32_t 
     const uint32_t c = cost[planar ? i % cols : i];
     if (c < QN_ROUTE_BLOCKED) { k = label[i]; mine = ((unsigned long long)c << 32) | i; }
   }
-  unsigned long long todo = __ballot(k >= 0);
-  while (todo) {                                                     // uniform over the wave: one trip and one atomicMin per region the wave holds
-    const int lead = __ffsll((long long)todo) - 1;
-    const int32_t k0 = __shfl(k, lead);
-    const unsigned long long same = __ballot(k == k0);
-    unsigned long long v = k == k0 ? mine : ~0ull;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = min(v, (unsigned long long)__shfl_xor(v, o));
-    if ((int)(threadIdx.x & 63) == lead) atomicMin(key + k0, v);
-    todo &= ~same;
-  }
+  wave_each_key(k >= 0, k, [&](int32_t k0, int, unsigned long long same) {      // one trip and one atomicMin per region the wave holds
+    const unsigned long long v = wave_min((same >> (threadIdx.x & 63)) & 1ull ? mine : ~0ull);
+    if ((threadIdx.x & 63) == 0) atomicMin(key + k0, v);             // (lane 0 holds the smallest)
+  });
 }
 
 // ---------------------------------------------------------------------------------------------------------------- host side
@@ -392,8 +320,7 @@ extern "C" int qn_kf_map_frontiers(qn_kf_store* s, const qn_frontier_params* par
   if (P.free_mask == 0 || (P.free_mask & ~7u) || P.unknown_mask == 0 || (P.unknown_mask & ~7u) || (P.free_mask & P.unknown_mask) || P.edge_unknown > 1 || P.min_size == 0 ||
       P.iz_lo > P.iz_hi || P.reserved[0] != 0 || P.reserved[1] != 0)
     return QN_ERR_INVALID_ARG;
-  StaticState* unit = (StaticState*)qn_kf_int_ext(s, QN_KF_INT_EXT_STATIC);
-  OccState* o = unit && unit->occ && unit->occ->live ? unit->occ.get() : nullptr;
+  OccState* o = oc_live_mut(s);
   if (!o) return QN_ERR_NOT_READY;
   const qn_occupancy_grid& g = o->info;
   const uint32_t W = g.width, H = g.height, D = g.depth, cells = W * H * D, cb = (cells + MF_BLOCK - 1) / MF_BLOCK;
@@ -438,7 +365,7 @@ extern "C" int qn_kf_map_frontiers(qn_kf_store* s, const qn_frontier_params* par
     hipLaunchKernelGGL(k_mf_roots, dim3(cb), dim3(MF_BLOCK), 0, str, cells, (const uint32_t*)lab, (const uint32_t*)d_aux, P.min_size, d_blk, d_slots, d_mslots);
     hipLaunchKernelGGL(k_scan_rows, dim3(1), dim3(MO_SCAN_BLOCK), 0, str, (const uint32_t*)d_blk, cb, d_off, d_off + cb);
     hipLaunchKernelGGL((k_slot_fold<uint32_t, 2>), dim3(1), dim3(MO_SCAN_BLOCK), 0, str, (const uint32_t*)d_slots, cb, d_sums + 3);
-    hipLaunchKernelGGL(k_md_fold_max, dim3(1), dim3(MO_SCAN_BLOCK), 0, str, (const uint32_t*)d_mslots, cb, d_sums + 5);
+    hipLaunchKernelGGL(k_slot_max<uint32_t>, dim3(1), dim3(MO_SCAN_BLOCK), 0, str, (const uint32_t*)d_mslots, cb, d_sums + 5);
     QN_KFCHK(s, hipGetLastError());
     QN_KFCHK(s, hipMemcpyAsync(h, d_off + cb, sizeof(uint32_t), hipMemcpyDeviceToHost, str));
     QN_KFCHK(s, hipStreamSynchronize(str));                  // sync 1: the number of regions
@@ -479,11 +406,7 @@ extern "C" int qn_kf_map_frontier_grid(qn_kf_store* s, qn_occupancy_grid* info_o
   const size_t cells = (size_t)g.width * g.height * g.depth;
   *info_out = g; *params_out = f->params;
   if (!cells || !label_out) return QN_OK;
-  QN_KFCHK(s, hipSetDevice(qn_kf_int_device(s)));
-  const hipStream_t str = qn_kf_int_stream(s);
-  QN_KFCHK(s, hipMemcpyAsync(label_out, f->label.p, sizeof(int32_t) * cells, hipMemcpyDeviceToHost, str));
-  QN_KFCHK(s, hipStreamSynchronize(str));
-  return QN_OK;
+  return qn_kf_download(s, label_out, f->label.p, sizeof(int32_t) * cells);
 }
 
 extern "C" int qn_kf_map_frontier_regions(qn_kf_store* s, qn_frontier_info* info_out, uint32_t capacity, uint32_t* count_out) {
@@ -495,11 +418,7 @@ extern "C" int qn_kf_map_frontier_regions(qn_kf_store* s, qn_frontier_info* info
   *count_out = R;
   if (capacity < R) return QN_ERR_CAPACITY;
   if (!R) return QN_OK;
-  QN_KFCHK(s, hipSetDevice(qn_kf_int_device(s)));
-  const hipStream_t str = qn_kf_int_stream(s);
-  QN_KFCHK(s, hipMemcpyAsync(info_out, f->info.p, sizeof(qn_frontier_info) * (size_t)R, hipMemcpyDeviceToHost, str));
-  QN_KFCHK(s, hipStreamSynchronize(str));
-  return QN_OK;
+  return qn_kf_download(s, info_out, f->info.p, sizeof(qn_frontier_info) * (size_t)R);
 }
 
 extern "C" int qn_kf_map_frontier_list(qn_kf_store* s, int32_t* ijk_out, int32_t* label_out, uint32_t capacity, uint32_t* count_out) {
@@ -557,9 +476,8 @@ extern "C" int qn_kf_map_frontier_costs(qn_kf_store* s, uint32_t* cost_out, int3
   QN_KFCHK(s, hipStreamSynchronize(str));
   for (uint32_t k = 0; k < R; k++) {
     const bool none = h[k] == ~0ull;
-    const uint32_t v = none ? 0u : (uint32_t)(h[k] & 0xffffffffull);
     cost_out[k] = none ? QN_ROUTE_UNREACHED : (uint32_t)(h[k] >> 32);
-    ijk_out[3 * (size_t)k] = (int32_t)(v % g.width); ijk_out[3 * (size_t)k + 1] = (int32_t)((v / g.width) % g.height); ijk_out[3 * (size_t)k + 2] = (int32_t)(v / cols);
+    oc_ijk(none ? 0u : (uint32_t)(h[k] & 0xffffffffull), g.width, g.height, ijk_out + 3 * (size_t)k);
   }
   return QN_OK;
 }

@@ -4,8 +4,8 @@
 // zq, the ground envelope g is the greatest function below the seeds whose rise between neighbouring columns is at most step_s (straight) / step_d (diagonal),
 // and a point's class follows from h = zq - g(column).  Everything after the quantisation is an integer and the envelope is unique, so every byte equals the
 // twin's whatever the order of the atomics and whatever the relaxation schedule.
-//   extent    k_mg_extent: the finite points' extremes in x, y and z and their number, one slot a block, then one block over the slots (k_mg_extent_sum).  No
-//             atomics.  The host derives the grid, checks the capacity rules (|zq| from the extremes of z: the quantisation is monotone) and refuses before
+//   extent    k_mg_extent: the finite points' extremes in x, y and z and their number (wave_min, wave_max, a table of its own, block_count), one slot a block,
+//             then one block over the slots (k_mg_extent_sum).  No atomics.  The host derives the grid, checks the capacity rules (|zq| from the extremes of z: the quantisation is monotone) and refuses before
 //             anything grid-sized is allocated.
 //   bin       k_mg_bin, one point per lane: zq and the column into scratch, atomicAdd on the column's count and atomicMin on its lowest zq - integer atomics,
 //             independent of their order.  k_mg_seed turns (count, lowest) into the seed in place, writes the occupancy base (0 unknown, 1 free) and counts the
@@ -41,7 +41,6 @@
 
 namespace {
 
-#define MG_WAVES (MG_BLOCK / 64)
 #define MG_SUM_BLOCK MO_SCAN_BLOCK
 #define MG_HALO (MG_TILE + 2)
 #define MG_INF INT32_MAX
@@ -50,22 +49,11 @@ namespace {
 #define MG_MAX_SIDE (1u << 24)
 
 static_assert(MG_BLOCK * 4 == MG_TILE * MG_TILE, "k_mg_relax: four columns of the tile per thread");
-static_assert(MG_BLOCK == MO_BLOCK, "block_count counts the waves of MO_BLOCK threads");
-
-__device__ __forceinline__ float mg_wave_min(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_down(v, o));
-  return v;
-}
-__device__ __forceinline__ float mg_wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_down(v, o));
-  return v;
-}
+static_assert(MG_BLOCK == MO_BLOCK, "block_count and the block folds take MO_BLOCK threads");
 
 // the finite points of the block: slots[8 b ..] = min x, min y, min z, max x, max y, max z (f32 bits), their number, 0
 __global__ void __launch_bounds__(MG_BLOCK) k_mg_extent(uint32_t n, const float4* __restrict__ map, uint32_t* __restrict__ slots) {
-  __shared__ float ws[6][MG_WAVES];
+  __shared__ float ws[6][MO_WAVES];
   const uint32_t i = blockIdx.x * MG_BLOCK + threadIdx.x;
   float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
   bool fin = false;
@@ -77,13 +65,14 @@ __global__ void __launch_bounds__(MG_BLOCK) k_mg_extent(uint32_t n, const float4
   const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
   for (int a = 0; a < 3; a++) {
-    const float l = mg_wave_min(lo[a]), h = mg_wave_max(hi[a]);
+    const float l = wave_min(lo[a]), h = wave_max(hi[a]);
     if (lane == 0) { ws[a][wave] = l; ws[3 + a][wave] = h; }
   }
-  block_count(slots + 8 * (size_t)blockIdx.x + 6, fin);  // (its barrier is the one the extremes wait for)
+  // its barrier is the one the extremes wait for: block_min and block_max, two barriers more, cost the call 2 % at 3e7 points (profiles/EXPERIMENTS.md)
+  block_count(slots + 8 * (size_t)blockIdx.x + 6, fin);
   if (threadIdx.x < 6) {
     float v = ws[threadIdx.x][0];
-    for (int w = 1; w < MG_WAVES; w++) v = threadIdx.x < 3 ? fminf(v, ws[threadIdx.x][w]) : fmaxf(v, ws[threadIdx.x][w]);
+    for (int w = 1; w < MO_WAVES; w++) v = threadIdx.x < 3 ? fminf(v, ws[threadIdx.x][w]) : fmaxf(v, ws[threadIdx.x][w]);
     slots[8 * (size_t)blockIdx.x + threadIdx.x] = __float_as_uint(v);
   }
 }
@@ -103,7 +92,7 @@ __global__ void __launch_bounds__(MG_SUM_BLOCK) k_mg_extent_sum(const uint32_t* 
   const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
   for (int a = 0; a < 3; a++) {
-    const float l = mg_wave_min(lo[a]), h = mg_wave_max(hi[a]);
+    const float l = wave_min(lo[a]), h = wave_max(hi[a]);
     if (lane == 0) { ws[a][wave] = l; ws[3 + a][wave] = h; }
   }
   c = wave_sum(c);

@@ -5,17 +5,19 @@
 // so every byte equals the twin's whatever the order of the atomics.
 //   extent    k_oc_extent, grid (tiles of the largest entry of the launch, entries) as k_static_vote's, one record per lane: the record is accepted or skipped
 //             (oc_ray: non-finite, near, far - f32, left to right, no fused multiply-add), A and B are formed, a ray end of 2^20 voxels or more raises the
-//             capacity flag; the per-axis extremes of c(A) and c(B) by a wave reduction and one integer atomicMin / atomicMax per wave; the five record counts by
+//             capacity flag; the per-axis extremes of c(A) and c(B) by wave_min / wave_max and one integer atomicMin / atomicMax per wave; the five record counts by
 //             block_count into the block's slot, k_slot_fold adds the slots up.  One host read: the host derives the grid and refuses before anything grid-sized
 //             is allocated.
 //   carve     k_oc_carve, the same grid, one ray per lane: oc_ray again (nothing is stored between the passes), then oc_walk, which names no floating-point
 //             type: hits[v_n] += 1 and misses[v_i] += 1 for i < n - shell by integer atomicAdd.  All rays of a block belong to one entry and start in the same
 //             voxel v_0, the hottest address there is: a wave folds its adds to v_0 into one add of the popcount (one atomic a wave instead of one a lane).  The
 //             voxels further out are added to lane by lane; a lane stops after its last miss, n - shell steps, since the end voxel is known without walking.
-//   classify  k_oc_classify, one voxel per lane: the class byte, the three class counts (block_count) and the block's hit and miss sums (u64) into slots,
-//             k_slot_fold adds them up.  One host read.
+//   classify  k_oc_classify, one voxel per lane: the class byte, the three class counts (block_count) and the block's hit and miss sums (u64, block_sum) into
+//             slots, k_slot_fold adds them up.  One host read.
 //   list      k_oc_list_flag / k_scan_rows / k_oc_list_pick: the count, scan and rank idiom of qn_map_compact.cuh over the voxels in linear order, stable.
 //   slice     k_oc_slice, one column per lane.
+//   grid      what every field over the dense grid shares (qn_mapdistance.inc, qn_maproute.inc, qn_mapfrontier.inc, included behind this file): oc_grid, oc_voxel -
+//             the one world-point-to-cell quantisation - and oc_ijk, the index split of the lists; on the host oc_live and oc_live_mut.
 // Host synchronisations of qn_kf_map_occupancy: two - the extent, the counts.  Integer atomics only, no scratch memory, no dynamically indexed private array.
 // Part of qn_staticmap.hip's translation unit (included at its end), the unit that turns a list with poses into per-record ray evidence: the results hang on
 // that unit's StaticState and take no slot of their own.  They do not depend on the map slot.
@@ -38,6 +40,40 @@ namespace {
 struct OcEntry { const float4* pts; uint32_t n, b0; double P[12]; };          // records, first block slot, the pose's three rows; 112 bytes
 struct OcGrid { int32_t minc[3]; uint32_t W, H, cells; };
 
+OcGrid oc_grid(const qn_occupancy_grid& g) {
+  OcGrid G;
+  memset(&G, 0, sizeof(G));
+  for (int k = 0; k < 3; k++) G.minc[k] = g.minc[k];
+  G.W = g.width; G.H = g.height; G.cells = g.width * g.height * g.depth;
+  return G;
+}
+
+// The dense grid's cell of world point i, for every field over the grid (the distance and route queries, goals and starts), by the map's own quantisation: f64,
+// every operation rounded on its own, half to even; false for a point that is not finite, 2^20 voxels or more from the origin, or outside the field of depth
+// Df.  Planar: x and y choose the column, z must only pass the limit.
+__device__ __forceinline__ bool oc_voxel(const double* __restrict__ xyz, uint32_t i, double inv, const OcGrid& G, uint32_t Df, uint32_t planar, uint32_t* cx, uint32_t* cy,
+                                         uint32_t* cz) {
+  const uint32_t side[3] = {G.W, G.H, Df};
+  long long c[3];
+  bool ok = true;
+#pragma unroll
+  for (int k = 0; k < 3; k++) {
+    const double t = xyz[3 * (size_t)i + k] * inv;
+    const bool in = fabs(t) < OC_COORD_LIMIT;                       // (a NaN fails the comparison, an infinity too)
+    c[k] = in ? (((long long)rint(t * 1024.0)) >> OC_S) - G.minc[k] : -1;
+    if (k == 2 && planar && in) c[k] = 0;
+    ok = ok && in && c[k] >= 0 && c[k] < (long long)side[k];
+  }
+  *cx = (uint32_t)c[0]; *cy = (uint32_t)c[1]; *cz = (uint32_t)c[2];
+  return ok;
+}
+
+// out[0 .. 3) = the voxel (x, y, z) at linear index i of a grid W wide and H high
+__host__ __device__ inline void oc_ijk(uint32_t i, uint32_t W, uint32_t H, int32_t* out) {
+  const uint32_t row = i / W;
+  out[0] = (int32_t)(i - row * W); out[1] = (int32_t)(row % H); out[2] = (int32_t)(row / H);
+}
+
 // the quantisation, shared by the two passes: the status of record p under pose rows P, and for a ray its fixed-point ends
 __device__ __forceinline__ int oc_ray(const float4 p, const double* __restrict__ P, double inv, float lo2, float hi2, int32_t (&A)[3], int32_t (&B)[3]) {
   if (!(isfinite(p.x) && isfinite(p.y) && isfinite(p.z))) return OC_NONFINITE;
@@ -57,17 +93,6 @@ __device__ __forceinline__ int oc_ray(const float4 p, const double* __restrict__
 #pragma unroll
   for (int k = 0; k < 3; k++) { A[k] = (int32_t)rint(o[k] * 1024.0); B[k] = (int32_t)rint(w[k] * 1024.0); }      // |.| <= 2^30
   return OC_RAY;
-}
-
-__device__ __forceinline__ int oc_wave_min(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_down(v, o));
-  return v;
-}
-__device__ __forceinline__ int oc_wave_max(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_down(v, o));
-  return v;
 }
 
 // ext[0 .. 3) / ext[3 .. 6): the smallest / largest voxel coordinate of a ray end, ext[6]: 1 when a ray end is out of range; slots[5 b ..]: the block's records,
@@ -90,7 +115,7 @@ __global__ void __launch_bounds__(OC_BLOCK) k_oc_extent(const OcEntry* __restric
     if (st == OC_CAPACITY) ext[6] = 1;                               // (a plain store of the same value by whoever finds one)
   }
 #pragma unroll
-  for (int k = 0; k < 3; k++) { lo[k] = oc_wave_min(lo[k]); hi[k] = oc_wave_max(hi[k]); }
+  for (int k = 0; k < 3; k++) { lo[k] = wave_min(lo[k]); hi[k] = wave_max(hi[k]); }
   if ((threadIdx.x & 63) == 0 && lo[0] != INT_MAX) {
 #pragma unroll
     for (int k = 0; k < 3; k++) { atomicMin(&ext[k], lo[k]); atomicMax(&ext[3 + k], hi[k]); }
@@ -159,7 +184,6 @@ __global__ void __launch_bounds__(OC_BLOCK) k_oc_carve(const OcEntry* __restrict
 __global__ void __launch_bounds__(OC_BLOCK) k_oc_classify(uint32_t cells, const uint32_t* __restrict__ hits, const uint32_t* __restrict__ misses, uint32_t min_hits,
                                                           uint32_t hit_weight, uint8_t* __restrict__ cls, uint32_t* __restrict__ cslots,
                                                           unsigned long long* __restrict__ tslots) {
-  __shared__ unsigned long long wt[2][MO_WAVES];
   const uint32_t i = blockIdx.x * OC_BLOCK + threadIdx.x;
   int c = -1;                                                        // (past the end: counted nowhere)
   uint32_t h = 0, m = 0;
@@ -168,14 +192,8 @@ __global__ void __launch_bounds__(OC_BLOCK) k_oc_classify(uint32_t cells, const 
     c = (h | m) == 0 ? QN_OCC_UNKNOWN : (h >= min_hits && (unsigned long long)h * hit_weight >= (unsigned long long)m) ? QN_OCC_OCCUPIED : QN_OCC_FREE;
     cls[i] = (uint8_t)c;
   }
-  const unsigned long long th = wave_sum((unsigned long long)h), tm = wave_sum((unsigned long long)m);
-  if ((threadIdx.x & 63) == 0) { wt[0][threadIdx.x >> 6] = th; wt[1][threadIdx.x >> 6] = tm; }
-  block_count(cslots + 3 * (size_t)blockIdx.x, c == QN_OCC_OCCUPIED, c == QN_OCC_FREE, c == QN_OCC_UNKNOWN);      // (its barrier is the one the sums wait for)
-  if (threadIdx.x < 2) {
-    unsigned long long acc = 0;
-    for (int w = 0; w < MO_WAVES; w++) acc += wt[threadIdx.x][w];
-    tslots[2 * (size_t)blockIdx.x + threadIdx.x] = acc;
-  }
+  block_count(cslots + 3 * (size_t)blockIdx.x, c == QN_OCC_OCCUPIED, c == QN_OCC_FREE, c == QN_OCC_UNKNOWN);
+  block_sum(tslots + 2 * (size_t)blockIdx.x, h, m);
 }
 
 // one voxel per lane: the block's voxels whose class bit is in the mask into its slot (what k_scan_rows goes on from)
@@ -191,11 +209,7 @@ __global__ void __launch_bounds__(MO_BLOCK) k_oc_list_pick(uint32_t cells, const
   const uint32_t i = blockIdx.x * MO_BLOCK + threadIdx.x;
   const bool keep = i < cells && ((mask >> cls[i]) & 1u) != 0;
   const size_t j = block_rank(keep, off[blockIdx.x]);
-  if (keep) {
-    const uint32_t row = i / W;
-    ijk[3 * j] = (int32_t)(i - row * W); ijk[3 * j + 1] = (int32_t)(row % H); ijk[3 * j + 2] = (int32_t)(row / H);
-    h_out[j] = hits[i]; m_out[j] = misses[i];
-  }
+  if (keep) { oc_ijk(i, W, H, ijk + 3 * j); h_out[j] = hits[i]; m_out[j] = misses[i]; }
 }
 
 // one column per lane: the largest class over the layers lo .. hi (2 occupied, else 1 free, else 0)
@@ -224,6 +238,7 @@ const OccState* oc_live(qn_kf_store* s) {
   const StaticState* st = (const StaticState*)qn_kf_int_ext(s, QN_KF_INT_EXT_STATIC);
   return st && st->occ && st->occ->live ? st->occ.get() : nullptr;
 }
+OccState* oc_live_mut(qn_kf_store* s) { return const_cast<OccState*>(oc_live(s)); }      // for the calls that hang a result of their own on it
 
 }  // namespace
 
@@ -304,8 +319,6 @@ extern "C" int qn_kf_map_occupancy(qn_kf_store* s, const int32_t* ids, const dou
   qn_occupancy_grid info;
   memset(&info, 0, sizeof(info));
   info.voxel = P.voxel;
-  OcGrid G;
-  memset(&G, 0, sizeof(G));
   if (r.n_rays) {
     uint64_t side[3];
     for (int k = 0; k < 3; k++) side[k] = (uint64_t)((int64_t)ext[3 + k] - (int64_t)ext[k] + 1);
@@ -313,10 +326,10 @@ extern "C" int qn_kf_map_occupancy(qn_kf_store* s, const int32_t* ids, const dou
       qn_kf_int_set_error(s, "qn_kf_map_occupancy: a grid of more than 2^27 voxels (or 2^15 a side)");
       return QN_ERR_CAPACITY;
     }
-    for (int k = 0; k < 3; k++) { G.minc[k] = info.minc[k] = ext[k]; info.origin[k] = (double)ext[k] * P.voxel; }
-    G.W = info.width = (uint32_t)side[0]; G.H = info.height = (uint32_t)side[1]; info.depth = (uint32_t)side[2];
-    G.cells = (uint32_t)(side[0] * side[1] * side[2]);
+    for (int k = 0; k < 3; k++) { info.minc[k] = ext[k]; info.origin[k] = (double)ext[k] * P.voxel; }
+    info.width = (uint32_t)side[0]; info.height = (uint32_t)side[1]; info.depth = (uint32_t)side[2];
   }
+  const OcGrid G = oc_grid(info);
   r.width = info.width; r.height = info.height; r.depth = info.depth;
   const uint32_t cells = G.cells, cb = (cells + OC_BLOCK - 1) / OC_BLOCK;
   // ---- from here on the previous result is gone
@@ -420,7 +433,5 @@ extern "C" int qn_kf_map_occupancy_slice(qn_kf_store* s, int32_t iz_lo, int32_t 
   if (!d_out) return qn_kf_fail(s, "qn_kf_map_occupancy_slice: scratch allocation failed");
   hipLaunchKernelGGL(k_oc_slice, dim3((cols + OC_BLOCK - 1) / OC_BLOCK), dim3(OC_BLOCK), 0, str, cols, (const uint8_t*)o->cls.p, (uint32_t)lo, (uint32_t)hi, d_out);
   QN_KFCHK(s, hipGetLastError());
-  QN_KFCHK(s, hipMemcpyAsync(occupancy_out, d_out, cols, hipMemcpyDeviceToHost, str));
-  QN_KFCHK(s, hipStreamSynchronize(str));
-  return QN_OK;
+  return qn_kf_download(s, occupancy_out, d_out, cols);
 }

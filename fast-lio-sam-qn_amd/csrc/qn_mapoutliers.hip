@@ -11,8 +11,8 @@
 //             query's.  The L smallest d2 live in L registers as u32 bit patterns (d2 >= 0: the f32 order is the u32 order), sorted
 //             ascending by a fully unrolled, statically indexed compare-exchange chain that is entered only when d2 < the current L-th; L is 8, 16 or 32, k
 //             rounded up (the k smallest are the first k of the L smallest).  No dynamically indexed private array, so no scratch.  The k f64 roots and their
-//             sum run once per point after the scan.  dense, sum_q and sum_q2 are reduced over the wave by shuffles, over the block through LDS, and stored
-//             into the block's own slot; k_slot_fold adds the slots up.  No atomics.
+//             sum run once per point after the scan.  dense, sum_q and sum_q2 go through block_sum into the block's own slot; k_slot_fold adds
+//             the slots up.  No atomics.
 //   flag      k_mo_flag, one point per lane in the map's own order: removed = sparse or double(mean_q) > thr_q; the block's kept count into its slot;
 //             k_scan_rows (one block) turns the counts into offsets, the last one the number kept.
 //   compact   qn_kf_map_remove_outliers only: the shared end of the map's filters (qn_map_compact.cuh, with the count tail, the fold, the scan and the rank).
@@ -30,6 +30,7 @@
 #include "qn_kf_buf.h"
 #include "qn_cell_walk.cuh"
 #include "qn_map_compact.cuh"
+#include "qn_union_find.cuh"
 
 namespace {
 
@@ -54,9 +55,8 @@ template <int L>
 __global__ void __launch_bounds__(MO_BLOCK) k_map_outliers(const CellSeg S, const float4* __restrict__ spts, const uint32_t* __restrict__ cells, float r2, double scale,
                                                            uint32_t k, uint32_t* __restrict__ count, uint32_t* __restrict__ mean_q,
                                                            unsigned long long* __restrict__ slots) {
-  __shared__ unsigned long long ws[3][MO_WAVES];
   const uint32_t t = blockIdx.x * MO_BLOCK + threadIdx.x;
-  const bool act = t < S.n;                              // (no early return: every thread of the block meets the barrier of the reduction)
+  const bool act = t < S.n;                              // (no early return: every thread of the block meets the barrier of block_sum)
   const bool fin = t < S.nfin;
   const float4 q = act ? spts[t] : make_float4(0.f, 0.f, 0.f, 0.f);
   const uint32_t qi = __float_as_uint(q.w);
@@ -86,14 +86,7 @@ __global__ void __launch_bounds__(MO_BLOCK) k_map_outliers(const CellSeg S, cons
   }
   if (act) { count[qi] = cnt; mean_q[qi] = mq; }
   const unsigned long long m64 = dense ? (unsigned long long)mq : 0ull;
-  const unsigned long long r0 = wave_sum(dense ? 1ull : 0ull), r1 = wave_sum(m64), r2s = wave_sum(m64 * m64);
-  if ((threadIdx.x & 63) == 0) { ws[0][threadIdx.x >> 6] = r0; ws[1][threadIdx.x >> 6] = r1; ws[2][threadIdx.x >> 6] = r2s; }
-  __syncthreads();
-  if (threadIdx.x < 3) {
-    unsigned long long acc = 0;
-    for (int w = 0; w < MO_WAVES; w++) acc += ws[threadIdx.x][w];
-    slots[3 * (size_t)blockIdx.x + threadIdx.x] = acc;
-  }
+  block_sum(slots + 3 * (size_t)blockIdx.x, dense ? 1ull : 0ull, m64, m64 * m64);
 }
 
 // one point per lane in the map's own order: the removed byte, and the block's kept records into its slot

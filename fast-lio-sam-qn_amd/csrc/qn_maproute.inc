@@ -22,10 +22,11 @@
 //             fixed point under the halo memory holds, and the fixed point of values that are costs of real paths is the shortest-path field.  The host
 //             launches QN_ROUTE_ROUNDS_PER_CHECK rounds, reads the rounds' "any tile changed" words and visit counts, and stops at the first round that
 //             changed nothing.  After k rounds every voxel whose shortest path crosses at most k - 1 tile faces is final: cells + 2 rounds bound the loop.
-//   stats     k_mr_stats: reached, unreached and blocked cells by block_count, the blocks' largest and summed cost; k_slot_fold and k_md_fold_max fold them.
+//   stats     k_mr_stats: reached, unreached and blocked cells by block_count, the blocks' largest and summed cost by wave_max, wave_sum and block_count's barrier; k_slot_fold
+//             and k_slot_max fold them.
 //   path      k_mr_path, one start per lane: a serial walk in global memory (S is small).     query  k_mr_query, one point per lane.
 // MR_T = 8 and QN_ROUTE_ROUNDS_PER_CHECK = 8 are untuned choices.  No scratch memory, no dynamically indexed private array; no floating point outside the quantisation
-// of goals, starts and query points; plain vector stores; the one integer atomic is the count of visited tiles, a diagnostic.
+// of goals, starts and query points (oc_voxel: qn_mapoccupancy.inc); plain vector stores; the one integer atomic is the count of visited tiles, a diagnostic.
 // Host synchronisations of qn_kf_map_route: ceil(rounds / QN_ROUTE_ROUNDS_PER_CHECK) + 1 - one per batch of rounds, then the statistics, which carry the goals' counts.
 // Part of qn_staticmap.hip's translation unit (included after qn_mapdistance.inc): the field hangs on that file's DistState and takes no slot of its own.
 
@@ -43,25 +44,6 @@ __host__ __device__ constexpr uint32_t mr_bit(int dx, int dy, int dz) { return 1
 // the voxels that must be passable for the move (dx, dy, dz): the block it spans
 __host__ __device__ constexpr uint32_t mr_need(int dx, int dy, int dz) {
   return mr_bit(0, 0, 0) | mr_bit(dx, 0, 0) | mr_bit(0, dy, 0) | mr_bit(0, 0, dz) | mr_bit(dx, dy, 0) | mr_bit(dx, 0, dz) | mr_bit(0, dy, dz) | mr_bit(dx, dy, dz);
-}
-
-// the field cell of world point i by the occupancy map's quantisation (f64, every operation rounded on its own, half to even); false for a point that is not
-// finite, 2^20 voxels or more from the origin, or outside the field.  Planar: x and y choose the column, z must only pass the limit.
-__device__ __forceinline__ bool mr_voxel(const double* __restrict__ xyz, uint32_t i, double inv, const OcGrid& G, uint32_t Df, uint32_t planar, uint32_t* cx, uint32_t* cy,
-                                         uint32_t* cz) {
-  const uint32_t side[3] = {G.W, G.H, Df};
-  long long c[3];
-  bool ok = true;
-#pragma unroll
-  for (int k = 0; k < 3; k++) {
-    const double t = xyz[3 * (size_t)i + k] * inv;
-    const bool in = fabs(t) < OC_COORD_LIMIT;                       // (a NaN fails the comparison, an infinity too)
-    c[k] = in ? (((long long)rint(t * 1024.0)) >> OC_S) - G.minc[k] : -1;
-    if (k == 2 && planar && in) c[k] = 0;
-    ok = ok && in && c[k] >= 0 && c[k] < (long long)side[k];
-  }
-  *cx = (uint32_t)c[0]; *cy = (uint32_t)c[1]; *cz = (uint32_t)c[2];
-  return ok;
 }
 
 // one cell per lane, linear order: BLOCKED or UNREACHED.  lo .. hi: the clipped band (lo > hi: it misses the grid); cols = W H
@@ -92,7 +74,7 @@ __global__ void __launch_bounds__(MR_BLOCK) k_mr_goals(uint32_t n, const double*
   bool used = false;
   if (i < n) {
     uint32_t x, y, z;
-    if (mr_voxel(xyz, i, inv, G, Df, planar, &x, &y, &z)) {
+    if (oc_voxel(xyz, i, inv, G, Df, planar, &x, &y, &z)) {
       const size_t lin = ((size_t)z * G.H + y) * G.W + x;
       if (cost[lin] != QN_ROUTE_BLOCKED) {
         cost[lin] = 0u;
@@ -179,18 +161,18 @@ __global__ void __launch_bounds__(MR_TILE) k_mr_relax(uint32_t* cost, uint32_t W
 // one cell per lane: cslots[3 b ..] = the block's reached, unreached and blocked cells, mslots[b] = its largest reached cost, tslots[b] = their sum
 __global__ void __launch_bounds__(MR_BLOCK) k_mr_stats(uint32_t cells, const uint32_t* __restrict__ cost, uint32_t* __restrict__ cslots, uint32_t* __restrict__ mslots,
                                                        unsigned long long* __restrict__ tslots) {
-  __shared__ unsigned long long wt[MO_WAVES];
-  __shared__ uint32_t wm[MO_WAVES];
   const uint32_t i = blockIdx.x * MR_BLOCK + threadIdx.x;
   const bool in = i < cells;
   const uint32_t v = in ? cost[i] : QN_ROUTE_BLOCKED;
   const bool reached = v < QN_ROUTE_BLOCKED;
-  uint32_t m = reached ? v : 0u;
+  const uint32_t m = reached ? v : 0u;
+  __shared__ unsigned long long wt[MO_WAVES];
+  __shared__ uint32_t wm[MO_WAVES];
   const unsigned long long t = wave_sum((unsigned long long)m);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) m = max(m, (uint32_t)__shfl_down(m, o));
-  if ((threadIdx.x & 63) == 0) { wt[threadIdx.x >> 6] = t; wm[threadIdx.x >> 6] = m; }
-  block_count(cslots + 3 * (size_t)blockIdx.x, reached, v == QN_ROUTE_UNREACHED, in && v == QN_ROUTE_BLOCKED);      // (its barrier is the one the sums wait for)
+  const uint32_t mm = wave_max(m);
+  if ((threadIdx.x & 63) == 0) { wt[threadIdx.x >> 6] = t; wm[threadIdx.x >> 6] = mm; }
+  // its barrier is the one the sums wait for, as in k_md_axis<true>, where block_max and block_sum measured slower (profiles/EXPERIMENTS.md)
+  block_count(cslots + 3 * (size_t)blockIdx.x, reached, v == QN_ROUTE_UNREACHED, in && v == QN_ROUTE_BLOCKED);
   if (threadIdx.x == 0) {
     unsigned long long acc = 0; uint32_t top = 0;
     for (int w = 0; w < MO_WAVES; w++) { acc += wt[w]; top = max(top, wm[w]); }
@@ -205,7 +187,7 @@ __global__ void __launch_bounds__(MR_BLOCK) k_mr_path(uint32_t n, const double* 
   if (i >= n) return;
   const int W = (int)G.W, H = (int)G.H, D = (int)Df;
   uint32_t sx, sy, sz, len = 0;
-  if (mr_voxel(xyz, i, inv, G, Df, planar, &sx, &sy, &sz)) {
+  if (oc_voxel(xyz, i, inv, G, Df, planar, &sx, &sy, &sz)) {
     int x = (int)sx, y = (int)sy, z = (int)sz;
     uint32_t cur = cost[((size_t)z * H + y) * W + x];
     int32_t* out = ijk_out + 3 * (size_t)max_len * i;
@@ -241,7 +223,7 @@ __global__ void __launch_bounds__(MR_BLOCK) k_mr_query(uint32_t n, const double*
   const uint32_t i = blockIdx.x * MR_BLOCK + threadIdx.x;
   if (i >= n) return;
   uint32_t x, y, z;
-  out[i] = mr_voxel(xyz, i, inv, G, Df, planar, &x, &y, &z) ? cost[((size_t)z * G.H + y) * G.W + x] : QN_ROUTE_BLOCKED;
+  out[i] = oc_voxel(xyz, i, inv, G, Df, planar, &x, &y, &z) ? cost[((size_t)z * G.H + y) * G.W + x] : QN_ROUTE_BLOCKED;
 }
 
 // ---------------------------------------------------------------------------------------------------------------- host side
@@ -260,14 +242,6 @@ const RouteState* mr_live(qn_kf_store* s, const OccState** occ) {
   return d && d->route && d->route->live ? d->route.get() : nullptr;
 }
 
-OcGrid mr_grid(const qn_occupancy_grid& g) {
-  OcGrid G;
-  memset(&G, 0, sizeof(G));
-  for (int k = 0; k < 3; k++) G.minc[k] = g.minc[k];
-  G.W = g.width; G.H = g.height; G.cells = g.width * g.height * g.depth;
-  return G;
-}
-
 // the field's depth: the grid's, or one layer of columns in planar mode
 uint32_t mr_depth(const qn_occupancy_grid& g, const qn_route_params& p) { return p.planar ? (g.width * g.height ? 1u : 0u) : g.depth; }
 
@@ -284,8 +258,7 @@ extern "C" int qn_kf_map_route(qn_kf_store* s, const double* goals_xyz, uint32_t
   if (!s || !goals_xyz || !params || !stats_out || n == 0 || n > QN_ROUTE_MAX_POINTS) return QN_ERR_INVALID_ARG;
   const qn_route_params P = *params;
   if (P.pass_mask == 0 || (P.pass_mask & ~7u) || P.planar > 1 || P.iz_lo > P.iz_hi || P.reserved[0] != 0 || P.reserved[1] != 0 || P.reserved[2] != 0) return QN_ERR_INVALID_ARG;
-  StaticState* unit = (StaticState*)qn_kf_int_ext(s, QN_KF_INT_EXT_STATIC);
-  OccState* o = unit && unit->occ && unit->occ->live ? unit->occ.get() : nullptr;
+  OccState* o = oc_live_mut(s);
   DistState* d = o && o->dist && o->dist->live ? o->dist.get() : nullptr;
   if (!d) return QN_ERR_NOT_READY;
   if (P.min_d2 > d->params.max_dist * d->params.max_dist) return QN_ERR_INVALID_ARG;      // beyond the cap the distance is not known
@@ -319,7 +292,7 @@ extern "C" int qn_kf_map_route(qn_kf_store* s, const double* goals_xyz, uint32_t
     st->live = false;
     if (nc.p) st->cost.swap(nc);
     uint32_t* cost = st->cost.p;
-    const OcGrid G = mr_grid(g);
+    const OcGrid G = oc_grid(g);
     const int32_t lo = std::max<int32_t>(P.iz_lo, 0), hi = (int32_t)std::min<int64_t>(P.iz_hi, (int64_t)g.depth - 1);
     QN_KFCHK(s, hipMemcpyAsync(d_xyz, goals_xyz, sizeof(double) * 3 * (size_t)n, hipMemcpyHostToDevice, str));
     QN_KFCHK(s, hipMemsetAsync(d_dirty, 0, sizeof(uint32_t) * 2 * (size_t)tiles, str));
@@ -353,7 +326,7 @@ extern "C" int qn_kf_map_route(qn_kf_store* s, const double* goals_xyz, uint32_t
     uint32_t* d_sums = (uint32_t*)d_small; uint32_t* d_mslots = d_slots + 3 * (size_t)cb;
     hipLaunchKernelGGL(k_mr_stats, dim3(cb), dim3(MR_BLOCK), 0, str, cells, (const uint32_t*)cost, d_slots, d_mslots, d_tslots);
     hipLaunchKernelGGL((k_slot_fold<uint32_t, 3>), dim3(1), dim3(MO_SCAN_BLOCK), 0, str, (const uint32_t*)d_slots, cb, d_sums);
-    hipLaunchKernelGGL(k_md_fold_max, dim3(1), dim3(MO_SCAN_BLOCK), 0, str, (const uint32_t*)d_mslots, cb, d_sums + 3);
+    hipLaunchKernelGGL(k_slot_max<uint32_t>, dim3(1), dim3(MO_SCAN_BLOCK), 0, str, (const uint32_t*)d_mslots, cb, d_sums + 3);
     hipLaunchKernelGGL((k_slot_fold<unsigned long long, 1>), dim3(1), dim3(MO_SCAN_BLOCK), 0, str, (const unsigned long long*)d_tslots, cb, (unsigned long long*)(d_small + 16));
     QN_KFCHK(s, hipGetLastError());
     QN_KFCHK(s, hipMemcpyAsync(h, d_small, 32, hipMemcpyDeviceToHost, str));
@@ -381,11 +354,7 @@ extern "C" int qn_kf_map_route_grid(qn_kf_store* s, qn_occupancy_grid* info_out,
   const size_t cells = (size_t)g.width * g.height * mr_depth(g, r->params);
   *info_out = g; *params_out = r->params;
   if (!cells || !cost_out) return QN_OK;
-  QN_KFCHK(s, hipSetDevice(qn_kf_int_device(s)));
-  const hipStream_t str = qn_kf_int_stream(s);
-  QN_KFCHK(s, hipMemcpyAsync(cost_out, r->cost.p, sizeof(uint32_t) * cells, hipMemcpyDeviceToHost, str));
-  QN_KFCHK(s, hipStreamSynchronize(str));
-  return QN_OK;
+  return qn_kf_download(s, cost_out, r->cost.p, sizeof(uint32_t) * cells);
 }
 
 extern "C" int qn_kf_map_route_query(qn_kf_store* s, const double* xyz, uint32_t n, uint32_t* cost_out) {
@@ -406,12 +375,10 @@ extern "C" int qn_kf_map_route_query(qn_kf_store* s, const double* xyz, uint32_t
   uint32_t* d_out = (uint32_t*)qn_kf_int_scratch(s, 1, sizeof(uint32_t) * (size_t)n);
   if (!d_xyz || !d_out) return qn_kf_fail(s, "qn_kf_map_route_query: scratch allocation failed");
   QN_KFCHK(s, hipMemcpyAsync(d_xyz, xyz, sizeof(double) * 3 * (size_t)n, hipMemcpyHostToDevice, str));
-  hipLaunchKernelGGL(k_mr_query, dim3((n + MR_BLOCK - 1) / MR_BLOCK), dim3(MR_BLOCK), 0, str, n, (const double*)d_xyz, 1.0 / g.voxel, mr_grid(g), Df, r->params.planar,
+  hipLaunchKernelGGL(k_mr_query, dim3((n + MR_BLOCK - 1) / MR_BLOCK), dim3(MR_BLOCK), 0, str, n, (const double*)d_xyz, 1.0 / g.voxel, oc_grid(g), Df, r->params.planar,
                      (const uint32_t*)r->cost.p, d_out);
   QN_KFCHK(s, hipGetLastError());
-  QN_KFCHK(s, hipMemcpyAsync(cost_out, d_out, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, str));
-  QN_KFCHK(s, hipStreamSynchronize(str));
-  return QN_OK;
+  return qn_kf_download(s, cost_out, d_out, sizeof(uint32_t) * (size_t)n);
 }
 
 extern "C" int qn_kf_map_route_path(qn_kf_store* s, const double* starts_xyz, uint32_t n_starts, uint32_t max_len, uint32_t* len_out, int32_t* ijk_out) {
@@ -435,7 +402,7 @@ extern "C" int qn_kf_map_route_path(qn_kf_store* s, const double* starts_xyz, ui
   if (!d_xyz || !d_len || !d_ijk) return qn_kf_fail(s, "qn_kf_map_route_path: scratch allocation failed");
   QN_KFCHK(s, hipMemcpyAsync(d_xyz, starts_xyz, sizeof(double) * 3 * (size_t)n, hipMemcpyHostToDevice, str));
   QN_KFCHK(s, hipMemsetAsync(d_ijk, 0, sizeof(int32_t) * words, str));
-  hipLaunchKernelGGL(k_mr_path, dim3((n + MR_BLOCK - 1) / MR_BLOCK), dim3(MR_BLOCK), 0, str, n, (const double*)d_xyz, 1.0 / g.voxel, mr_grid(g), Df, r->params.planar,
+  hipLaunchKernelGGL(k_mr_path, dim3((n + MR_BLOCK - 1) / MR_BLOCK), dim3(MR_BLOCK), 0, str, n, (const double*)d_xyz, 1.0 / g.voxel, oc_grid(g), Df, r->params.planar,
                      (const uint32_t*)r->cost.p, max_len, d_len, d_ijk);
   QN_KFCHK(s, hipGetLastError());
   QN_KFCHK(s, hipMemcpyAsync(len_out, d_len, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, str));

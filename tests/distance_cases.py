@@ -1,6 +1,6 @@
-"""The case table of the occupancy map's distance field (csrc/qn_mapdistance.inc: k_md_x, k_md_axis<false / true>, k_md_fold_max, k_md_slice, k_md_query, with
-k_slot_fold of csrc/qn_map_compact.cuh): deterministic inputs that put sites on chosen voxels, with what the construction itself determines stated in `expect`
-- never taken from the twin and never from engine output.  tests/test_map_distance_twin.py holds the twin (qn_amd/mapdistance.py) to the definition (its
+"""The case table of the occupancy map's distance field (csrc/qn_mapdistance.inc: k_md_x, k_md_axis<false / true>, k_md_slice, k_md_query, with
+block_count, block_max, block_sum, k_slot_fold and k_slot_max of csrc/qn_map_compact.cuh and oc_voxel of csrc/qn_mapoccupancy.inc): deterministic inputs that
+put sites on chosen voxels, with what the construction itself determines stated in `expect` - never taken from the twin and never from engine output.  tests/test_map_distance_twin.py holds the twin (qn_amd/mapdistance.py) to the definition (its
 brute()) and to these expectations; tests/test_gpu_map_distance.py holds the engine to the twin and to them.  Pure numpy, no GPU.
 
 Sites on chosen voxels: voxel 1.0, min_range 0, max_range 1e4 and shell 0xffffffff (no ray leaves a miss, so a voxel is OCCUPIED where a ray ends and UNKNOWN
@@ -13,7 +13,8 @@ A Case: name, records (n, 3) f32, occ (an mo.OccupancyParams), params (an md.Dis
 Seams and the constant each belongs to (restated from the source; whoever changes one there changes it here):
   MD_BLOCK = MO_BLOCK 256   voxels per block of k_md_x and k_md_axis, columns of k_md_slice, points of k_md_query; the halo of k_md_x is one block either side
   WAVE 64                   one ballot word of k_md_x: the line lengths 63 .. 65, 127 .. 129, 255 .. 257 are its word and block seams, 1025 is four blocks
-  MAX_RADIUS 255            the largest max_dist: 255^2 = 65025 is the largest d2, one below FAR's neighbourhood"""
+  MAX_RADIUS 255            the largest max_dist: 255^2 = 65025 is the largest d2, one below FAR's neighbourhood
+  MO_WAVES 4, MO_SCAN_BLOCK 1024   the words of block_max and block_sum, the stride of k_slot_fold and k_slot_max: fold_seams() below"""
 import functools
 import numpy as np
 from qn_amd import mapdistance as md, mapoccupancy as mo
@@ -26,7 +27,7 @@ POSE = np.eye(4); POSE[:3, 3] = 0.5
 OCC, FREE, UNK = 1 << mo.OCCUPIED, 1 << mo.FREE, 1 << mo.UNKNOWN
 LINE_LENGTHS = (1, 2, 63, 64, 65, 127, 128, 129, 255, 256, 257, 1025)
 LINE_RADII = (1, 16, 255)
-SLICE_CAP = 200000                                                   # voxels up to which the twin test runs brute()
+SLICE_CAP = 200000                                                   # voxels up to which the twin test runs brute(); a larger case states its whole field
 
 
 class Case:
@@ -129,8 +130,32 @@ def random_boxes():
     return out
 
 
+# ---- the seams of block_max, block_sum and k_slot_max: the largest d2 in exactly one lane of one block
+def fold_seams():
+    """site_mask = UNKNOWN, D = 1: a 3 x 3 square of occupied voxels centred at p, one voxel or more inside the grid - the centre reads 4, its ring 1 - and the
+    occupied far corner, which reads 1; every other voxel is a site.  p is lane 1 or 62 of the first or of the last wave of block 3, or lane 62 of block 1024
+    of 1027 (262 905 voxels), the second trip of the stride loop of k_slot_fold and k_slot_max (MO_SCAN_BLOCK 1024).  W = 255, not 256: with block b = row b, lane 1 would put the
+    square's side on the grid's edge, where nothing outside is a site and a second voxel reads 4; at 255 block b starts b voxels into row b.  Block 1026 of the
+    large case is ragged but holds only sites and the corner, so the ragged last block that holds p is a case of its own, 20 x 30: block 2 has the last 88
+    voxels, p = (10, 27) is its lane 38."""
+    out = []
+    for name, (W, H), lin in [("first-wave-lane-1", (255, 9), 3 * MD_BLOCK + 1), ("first-wave-lane-62", (255, 9), 3 * MD_BLOCK + 62),
+                              ("last-wave-lane-1", (255, 9), 3 * MD_BLOCK + 193), ("last-wave-lane-62", (255, 9), 3 * MD_BLOCK + 254),
+                              ("ragged-last-block", (20, 30), 2 * MD_BLOCK + 38), ("block-1024", (255, 1031), 1024 * MD_BLOCK + 62)]:
+        px, py = lin % W, lin // W
+        ring = [(px + dx, py + dy) for dy in (-1, 0, 1) for dx in (-1, 0, 1) if (dx, dy) != (0, 0)]
+        assert all(1 <= x < W - 1 and 1 <= y < H - 1 for x, y in ring) and max(W - 1 - px, H - 1 - py) > 3      # unknown voxels all round the square, the corner apart
+        rec = [[px, py, 0]] + [[x, y, 0] for x, y in ring] + [[W - 1, H - 1, 0]]
+        full = np.zeros((1, H, W), np.uint16)
+        for x, y in ring + [(W - 1, H - 1)]:
+            full[0, y, x] = 1
+        full[0, py, px] = 4
+        out.append(Case("fold-seams/" + name, rec, (UNK, 4), (W, H, 1), dict(full=full, stats=dict(max_d2=4, sum_d2=13, reached=10, sites=W * H - 10, far=0))))
+    return out
+
+
 GROUPS = {"lines-x": lambda: lines(0), "lines-y": lambda: lines(1), "lines-z": lambda: lines(2), "knife-edge": knife_edge, "wide-window": wide_window,
-          "no-site": no_site, "all-sites": all_sites, "fan": fan, "random": random_boxes}
+          "no-site": no_site, "all-sites": all_sites, "fan": fan, "random": random_boxes, "fold-seams": fold_seams}
 NAMES = list(GROUPS)
 
 

@@ -1,5 +1,5 @@
 """The case table of the occupancy map's route field (csrc/qn_maproute.inc: k_mr_init, k_mr_goals, k_mr_relax, k_mr_stats, k_mr_path, k_mr_query, with k_slot_fold
-of csrc/qn_map_compact.cuh and k_md_fold_max of csrc/qn_mapdistance.inc): deterministic wall layouts, with what the construction itself determines stated in
+and k_slot_max of csrc/qn_map_compact.cuh and oc_voxel of csrc/qn_mapoccupancy.inc): deterministic wall layouts, with what the construction itself determines stated in
 `expect` - never taken from the twin and never from engine output.  tests/test_map_route_twin.py holds the twin (qn_amd/maproute.py) to the definition (its
 dijkstra()) and to these expectations; tests/test_gpu_map_route.py holds the engine to the twin and to them.  Pure numpy, no GPU.
 

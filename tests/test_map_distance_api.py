@@ -12,7 +12,7 @@ from qn_amd import engine, mapdistance as md
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "fast-lio-sam-qn_amd", "csrc")
 SYMBOLS = ["qn_distance_default_params", "qn_kf_map_distance", "qn_kf_map_distance_grid", "qn_kf_map_distance_slice", "qn_kf_map_distance_query"]
-KERNELS = ("k_md_x", "k_md_axis<false>", "k_md_axis<true>", "k_md_fold_max", "k_md_slice", "k_md_query", "k_slot_fold<unsigned int, 3>",
+KERNELS = ("k_md_x", "k_md_axis<false>", "k_md_axis<true>", "k_slot_max<unsigned int>", "k_md_slice", "k_md_query", "k_slot_fold<unsigned int, 3>",
            "k_slot_fold<unsigned long long, 1>")
 
 
@@ -101,17 +101,22 @@ def test_the_kernels_have_no_scratch_and_no_spills():
 
 
 def test_no_floating_point_outside_the_query():
-    """the transform, slice and statistics kernels and the two bit searches name no floating-point type; the query's quantisation is the only place that does"""
+    """the transform, slice and statistics kernels, the fold of the largest (k_slot_max: qn_map_compact.cuh) and the two bit searches name no floating-point type;
+    the query's quantisation (oc_voxel: qn_mapoccupancy.inc, which the route shares) is the only place that does"""
     src = open(os.path.join(CSRC, "qn_mapdistance.inc")).read()
-    for k, least in (("md_left", 200), ("md_right", 200), ("k_md_x", 200), ("k_md_axis", 200), ("k_md_fold_max", 200), ("k_md_slice", 200)):
-        i = src.index(" " + k + "(")
-        body = src[i:src.index("\n}\n", i)]
+    compact = open(os.path.join(CSRC, "qn_map_compact.cuh")).read()
+    occ = open(os.path.join(CSRC, "qn_mapoccupancy.inc")).read()
+    for text, k, least in ((src, "md_left", 200), (src, "md_right", 200), (src, "k_md_x", 200), (src, "k_md_axis", 200), (compact, "k_slot_max", 200), (src, "k_md_slice", 200)):
+        i = text.index(" " + k + "(")
+        body = text[i:text.index("\n}\n", i)]
         assert len(body) > least and not re.search(r"\b(float|double|float4|double2)\b", body), k
     i = src.index(" k_md_query(")
-    q = src[i:src.index("\n}\n", i)]
-    assert "rint(t * 1024.0)" in q and "double" in q
+    assert "oc_voxel(" in src[src.index("{\n", i):src.index("\n}\n", i)]
+    i = occ.index(" oc_voxel(")
+    q = occ[i:occ.index("\n}\n", i)]
+    assert "rint(t * 1024.0)" in q and "double" in q and (src + occ).count("rint(t * 1024.0)") == 1      # the one quantisation of a world point
     device = src[:src.index("host side")]
-    assert len(re.findall(r"__global__", device)) == 5
+    assert len(re.findall(r"__global__", device)) == 4
 
 
 def test_shim_program_compiles_and_prints_its_refusals(tmp_path):

@@ -20,9 +20,10 @@ def test_transform_is_the_definition_on_the_table(g):
         assert cls.shape == c.sides[::-1], (c.name, cls.shape)
         got = md.transform(cls, c.params)
         dc.holds(c, got["d2"], _stats(got))
-        assert c.voxels <= dc.SLICE_CAP
-        want = md.brute(cls, c.params)
-        assert got["d2"].tobytes() == want["d2"].tobytes() and got["stats"] == want["stats"], (c.name, int((got["d2"] != want["d2"]).sum()))
+        assert c.voxels <= dc.SLICE_CAP or "full" in c.expect      # (brute() is voxels x sites: the large case of fold-seams, nearly all sites, states its whole field)
+        if c.voxels <= dc.SLICE_CAP:
+            want = md.brute(cls, c.params)
+            assert got["d2"].tobytes() == want["d2"].tobytes() and got["stats"] == want["stats"], (c.name, int((got["d2"] != want["d2"]).sum()))
         assert got["stats"] == md.stats_of(got["d2"], c.params.max_dist)
 
 

@@ -128,8 +128,8 @@ def test_the_kernels_have_no_scratch_and_no_spills():
 
 
 def test_no_floating_point_outside_the_quantisation():
-    """the field, statistics and walk kernels name no floating-point type in their bodies; mr_voxel, which goals, starts and query points share, is the only
-    place that computes with one"""
+    """the field, statistics and walk kernels name no floating-point type in their bodies; oc_voxel (qn_mapoccupancy.inc), which goals, starts and query
+    points share with the distance query, is the only place that computes with one"""
     src = open(os.path.join(CSRC, "qn_maproute.inc")).read()
     for k, least in (("k_mr_init", 200), ("k_mr_relax", 1500), ("k_mr_stats", 200)):
         i = src.index(" " + k + "(")
@@ -138,9 +138,10 @@ def test_no_floating_point_outside_the_quantisation():
     for k in ("k_mr_goals", "k_mr_path", "k_mr_query"):
         i = src.index(" " + k + "(")
         body = src[src.index("{\n", i):src.index("\n}\n", i)]
-        assert "mr_voxel(" in body and not re.search(r"\b(float|double|float4|double2)\b", body), k      # (the points and 1 / voxel are parameters)
-    i = src.index(" mr_voxel(")
-    q = src[i:src.index("\n}\n", i)]
+        assert "oc_voxel(" in body and not re.search(r"\b(float|double|float4|double2)\b", body), k      # (the points and 1 / voxel are parameters)
+    occ = open(os.path.join(CSRC, "qn_mapoccupancy.inc")).read()
+    i = occ.index(" oc_voxel(")
+    q = occ[i:occ.index("\n}\n", i)]
     assert "rint(t * 1024.0)" in q and "double" in q
     device = src[:src.index("host side")]
     assert len(re.findall(r"__global__", device)) == 6
