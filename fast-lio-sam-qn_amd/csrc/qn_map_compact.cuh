@@ -20,6 +20,9 @@
 //             MO_BLOCK records (block_count), k_scan_rows turns the counts into offsets, k_mo_compact moves a block's kept records to its offset, in order;
 //             qn_kf_map_compact_shrink makes the kept records the slot.  Templates on the record type: instantiated only in the units that filter the slot, so a
 //             unit that only counts, scans or lists carries no copy of the compaction kernel.
+// Tested directly: tests/test_gpu_map_prims.py runs the folds, the key walk, the slot folds, the scan and the rank on inputs no unit can produce, through
+// qn_kf_debug_map_prims (qn_map_selftest.hip), against the serial references of tests/map_prims_cases.py; tests/test_gpu_compact_seams.py has the seams of the
+// scan and the rank through the units.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>

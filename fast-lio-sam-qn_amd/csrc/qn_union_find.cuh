@@ -12,6 +12,10 @@
 // Inside the launch that unites, parent[] is read by agent-scope relaxed atomic loads (uf_load) and written by agent-scope atomics only: a plain load could be
 // served from another XCD's stale L2 line, and would then only walk a longer path; the atomics are what the argument needs.  The launch after it sees the
 // final forest through the kernel boundary.  Components are a set property, so the roots are the same whatever the schedule.
+// Tested directly: tests/union_find_model.py restates uf_find, uf_unite and uf_unite_min as step machines, one step an atomic memory operation, and
+// tests/test_union_find_model.py runs every interleaving of two and three lanes on four and five nodes through them (whoever changes this file changes the
+// model, and the other way round); tests/test_gpu_map_prims.py runs the device builds, through qn_kf_debug_map_prims (qn_map_selftest.hip), on paths, stars,
+// combs, cliques and starting forests against a serial union-find.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>

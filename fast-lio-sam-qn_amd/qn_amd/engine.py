@@ -1902,6 +1902,69 @@ class KeyframeStore:
                                            _p(ids), _p(D), _p(sh), _p(n)))
         return [(ids[r * k:r * k + n[r]].copy(), D[r * k:r * k + n[r]].copy(), sh[r * k:r * k + n[r]].copy()) for r in range(nq)]
 
+    # ---- developer / tests: the map units' shared device primitives on caller-supplied inputs (qn_kf_debug_map_prims; the records of include/qn_engine.h)
+    MAP_PRIMS_LANE = np.dtype([("i", "<i4"), ("u", "<u4"), ("f", "<f4"), ("zero", "<u4"), ("q", "<u8"), ("s", "<i8")])
+    MAP_PRIMS_WAVE = np.dtype([("imin", "<i4"), ("imax", "<i4"), ("usum", "<u4"), ("umin", "<u4"), ("umax", "<u4"), ("fmin", "<f4"), ("fmax", "<f4"), ("zero", "<u4"),
+                               ("qsum", "<u8"), ("qmin", "<u8"), ("ssum", "<i8"), ("zero2", "<u8")])
+    MAP_PRIMS_KEY_IN = np.dtype([("has", "<u4"), ("key", "<u4")])
+    MAP_PRIMS_KEY = np.dtype([("trip", "<u4"), ("lead", "<u4"), ("key", "<u4"), ("served", "<u4"), ("same", "<u8")])
+    MAP_PRIMS_BLOCK_IN = np.dtype([("pred", "<u4"), ("a", "<u4", (3,)), ("b", "<u8", (3,))])
+    MAP_PRIMS_BLOCK = np.dtype([("count", "<u4", (15,)), ("sum32", "<u4", (6,)), ("max32", "<u4", (6,)), ("again32", "<u4"), ("sum64", "<u8", (6,)),
+                                ("max64", "<u8", (6,)), ("again64", "<u8"), ("wide", "<u8", (2,))])
+    MAP_PRIMS_U64, MAP_PRIMS_MAX, MAP_PRIMS_IN_PLACE = 0x100, 0x200, 0x80000000
+    MAP_PRIMS_WAVES, MAP_PRIMS_KEYS, MAP_PRIMS_BLOCKS, MAP_PRIMS_SLOTS, MAP_PRIMS_SCAN, MAP_PRIMS_RANK, MAP_PRIMS_UNITE, MAP_PRIMS_UNITE_MIN = range(8)
+
+    def debug_map_prims(self, which, data, arg=0):
+        """qn_kf_debug_map_prims: routine `which` (the MAP_PRIMS_* numbers above) of the map units' shared device primitives on the caller's input.  data -> result:
+          WAVES      (256 B,) MAP_PRIMS_LANE                        -> (4 B,) MAP_PRIMS_WAVE
+          KEYS       (256 B,) MAP_PRIMS_KEY_IN; arg 1: int32 keys   -> ((256 B,) MAP_PRIMS_KEY, (4 B,) u32 trips)
+          BLOCKS     (256 B,) MAP_PRIMS_BLOCK_IN                    -> (B,) MAP_PRIMS_BLOCK
+          SLOTS      (nb, K) u32, or u64 with arg = MAP_PRIMS_U64 | K, or (nb,) u32 with arg = MAP_PRIMS_MAX; else arg = K      -> (K,) sums / (1,) the maximum
+          SCAN       (rows, nb) u32, arg = rows, | MAP_PRIMS_IN_PLACE     -> ((rows, nb) u32 offsets, (rows,) u32 totals)
+          RANK       ((256 B,) u8 keep, (B,) u32 bases)             -> (256 B,) u32
+          UNITE(_MIN) (n, (m, 2) u32 edges, None or the (n,) u32 starting forest), arg = edges a lane      -> ((n,) u32 raw parents, (n,) u32 roots)
+        A size that does not fit the routine's records is a ValueError here; everything else is the library's to refuse."""
+        u4, u8 = np.dtype("<u4"), np.dtype("<u8")
+
+        def need(a, dt, ok):
+            a = np.ascontiguousarray(a)
+            if a.dtype != dt or not ok(a):
+                raise ValueError("debug_map_prims(%d): %s %s does not fit the routine's records" % (which, a.dtype, a.shape))
+            return a
+
+        per_block = lambda a: a.ndim == 1 and len(a) % 256 == 0
+        arg = int(arg)
+        if which in (self.MAP_PRIMS_WAVES, self.MAP_PRIMS_KEYS, self.MAP_PRIMS_BLOCKS):
+            a = need(data, (self.MAP_PRIMS_LANE, self.MAP_PRIMS_KEY_IN, self.MAP_PRIMS_BLOCK_IN)[which], per_block)
+            n = len(a) // 256
+            parts = [a]
+            outs = [((4 * n,), self.MAP_PRIMS_WAVE)] if which == 0 else [((256 * n,), self.MAP_PRIMS_KEY), ((4 * n,), u4)] if which == 1 else [((n,), self.MAP_PRIMS_BLOCK)]
+        elif which == self.MAP_PRIMS_SLOTS:
+            wide, k = bool(arg & self.MAP_PRIMS_U64), 1 if arg == self.MAP_PRIMS_MAX else arg & 0xff
+            a = need(data, u8 if wide else u4, lambda a: a.size % max(k, 1) == 0)
+            n, parts, outs = a.size // max(k, 1), [a], [((k,), a.dtype)]
+        elif which == self.MAP_PRIMS_SCAN:
+            a = need(data, u4, lambda a: a.ndim == 2 and a.shape[0] == (arg & 0x7fffffff))
+            n, parts, outs = a.shape[1], [a], [(a.shape, u4), ((a.shape[0],), u4)]
+        elif which == self.MAP_PRIMS_RANK:
+            keep = need(data[0], np.dtype("u1"), per_block)
+            n = len(keep) // 256
+            parts, outs = [keep, need(data[1], u4, lambda b: b.shape == (n,))], [((256 * n,), u4)]
+        else:
+            n, edges, forest = data
+            edges = need(edges, u4, lambda e: e.ndim == 2 and e.shape[1] == 2)
+            parts = [np.array([len(edges), 0 if forest is None else 1], u4)] + ([] if forest is None else [need(forest, u4, lambda f: f.shape == (n,))]) + [edges]
+            outs = [((n,), u4), ((n,), u4)]
+        buf = np.frombuffer(b"".join(p.tobytes() for p in parts) + bytes(16), np.uint8).copy()
+        out = np.zeros(sum(int(np.prod(s)) * dt.itemsize for s, dt in outs) + 16, np.uint8)
+        self._l.qn_kf_debug_map_prims.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
+        self._check(self._l.qn_kf_debug_map_prims(self.h, C.c_int(which), _p(buf), C.c_uint32(n), C.c_uint32(arg), _p(out)))
+        res, at = [], 0
+        for s, dt in outs:
+            nbytes = int(np.prod(s)) * dt.itemsize
+            res.append(out[at:at + nbytes].view(dt).reshape(s).copy()); at += nbytes
+        return res[0] if len(res) == 1 else tuple(res)
+
 
 def loop_candidates(pos, stamps, query, radius, tdiff, max_k=64):
     pos = np.ascontiguousarray(pos, dtype=np.float64); stamps = np.ascontiguousarray(stamps, dtype=np.float64)

@@ -1164,6 +1164,35 @@ int  qn_debug_eig3(qn_ctx*, int which, const double* a6, uint32_t n, double* w_o
 #define QN_DEBUG_STEP_MATH_WHICH 6
 #define QN_DEBUG_STEP_MATH_MAX (1u << 20)
 int  qn_debug_step_math(qn_ctx*, int which, const double* in, uint32_t n, double* out);
+/* developer / tests: the device builds of what the map units share (csrc/qn_map_compact.cuh: the wave and block folds, the key walk, the slot folds, the row
+ * scan, the block rank; csrc/qn_union_find.cuh: the two linkers) on caller-supplied inputs, on the store's stream with the store's scratch
+ * (csrc/qn_map_selftest.hip).  Host arrays, packed, little endian; a block is 256 lanes = 4 waves of 64; u64 / i64 fields are 8-byte aligned in their records:
+ *   0  wave_sum / wave_min / wave_max.  n = blocks, arg = 0.  in per lane (32 B): {i32 i; u32 u; f32 f; u32 0; u64 q; i64 s}.  out per wave (64 B), what lane 0
+ *      holds: {i32 min i, max i; u32 sum u, min u, max u; f32 min f, max f; u32 0; u64 sum q, min q; i64 sum s; u64 0}.
+ *   1  wave_each_key.  n = blocks, arg = 0: the keys as uint32_t, 1: as int32_t.  in per lane (8 B): {u32 has; u32 key}.  out per lane (24 B): {u32 trip, lead,
+ *      key, served; u64 same} - the trip (from 0) that had the lane in its mask with the key, lead and mask the callable was handed there, served = the number
+ *      of such trips; trip = lead = 0xffffffff for a lane no trip had - then, after all lanes, a u32 per wave: its trips.
+ *   2  block_count / block_sum / block_max.  n = blocks, arg = 0.  in per lane (40 B): {u32 pred (bits 0 .. 4); u32 a[3]; u64 b[3]}.  out per block (232 B):
+ *      {u32 count[15], sum32[6], max32[6], again32; u64 sum64[6], max64[6], again64, wide[2]}.  count: block_count of the first K predicates, the results of
+ *      K = 1, 2, 3, 4, 5 one after the other; sum32 / max32: block_sum / block_max of the first K of a, K = 1, 2, 3 one after the other; sum64 / max64: the
+ *      same of b; again32 / again64: the one-value sum called a second time in the kernel, on a[1] / b[1], behind the __syncthreads() its header asks for;
+ *      wide: a[0] and a[1] summed in u64.
+ *   3  k_slot_fold / k_slot_max.  n = nb slots.  arg = K: uint32_t sums, K one of 1, 2, 3, 5, 10; 0x100 | K: unsigned long long sums, K one of 1, 2, 3; 0x200:
+ *      the uint32_t maximum (K = 1).  in: K nb words, slot b at K b.  out: K words.
+ *   4  k_scan_rows.  n = nb, arg = rows, | 0x80000000: in place (cnt == off).  in: rows x nb u32 counts.  out: rows x nb u32 exclusive offsets, then rows u32 totals.
+ *   5  block_rank.  n = blocks, arg = 0.  in: 256 keep bytes a block, then a u32 base a block.  out: a u32 per lane.
+ *   6  uf_unite, 7 uf_unite_min.  n = nodes, arg = the consecutive edges a lane takes, 1 .. 13 (lane t of 256 a block: the edges [t arg, (t + 1) arg)).  in: u32 m,
+ *      u32 forest (0 / 1), the n u32 parents of the starting forest when forest is 1 (else the identity), then m edges {u32 a, b}.  out: the n u32 parents as
+ *      the unite launch left them, then the n u32 roots after the flatten by plain loads.
+ * Three launches for 6 and 7: init, unite, flatten.  A second call may start from the parents the first one returned.  QN_ERR_INVALID_ARG with nothing
+ * launched and nothing written: a null pointer, which outside 0 .. 7, an arg other than the above, more than QN_DEBUG_MAP_PRIMS_MAX_BLOCKS blocks or rows,
+ * more than _MAX_NODES nodes, slots or rows x nb counts, more than _MAX_EDGES edges, an edge with an end >= n, a starting parent[x] > x.  n == 0 succeeds and
+ * writes nothing (6, 7: the two header words are still read).  Nothing on a product path calls it. */
+#define QN_DEBUG_MAP_PRIMS_WHICH 8
+#define QN_DEBUG_MAP_PRIMS_MAX_BLOCKS (1u << 16)
+#define QN_DEBUG_MAP_PRIMS_MAX_NODES (1u << 20)
+#define QN_DEBUG_MAP_PRIMS_MAX_EDGES (1u << 20)
+int  qn_kf_debug_map_prims(qn_kf_store*, int which, const void* in, uint32_t n, uint32_t arg, void* out);
 int  qn_debug_get(qn_ctx*, const char* key, double* value);   /* "verify_mismatches" / "verify_passes" / "verify_first" after qn_debug_set("verify_track", 1); "feat_survivors" / "feat_fallbacks" (matrix-core feature matching) */
 int  qn_debug_get_grid(qn_ctx*, int which, double out[8]);
 int  qn_debug_get_partials(qn_ctx*, double* out, uint32_t* rows_per_buffer, double* state);   /* developer: both partial-row buffers and both state buffers after an align */

@@ -89,9 +89,10 @@ def test_the_kernels_have_no_scratch_and_no_spills():
         rows = [l for l in out.splitlines() if "::" + k + "(" in l]
         assert rows, k
         assert all(int(l.split()[0]) == 0 and " spill   0 " in l for l in rows), rows
-    # one source: the scan in the four units that launch it (qn_mapoutliers, qn_mapground, qn_staticmap, qn_verify), the record compaction only in the two that
-    # filter the slot - the static-map unit, which lists voxels, carries none
-    assert len([l for l in out.splitlines() if "::k_scan_rows(" in l]) == 4 and len([l for l in out.splitlines() if "::k_mo_compact<" in l]) == 2
+    # one source: the scan in the four units that launch it (qn_mapoutliers, qn_mapground, qn_staticmap, qn_verify) and in the primitives' test entry
+    # (qn_map_selftest, which launches it on caller-supplied rows), the record compaction only in the two that filter the slot - the static-map unit, which lists
+    # voxels, carries none, and neither does the test entry
+    assert len([l for l in out.splitlines() if "::k_scan_rows(" in l]) == 5 and len([l for l in out.splitlines() if "::k_mo_compact<" in l]) == 2
 
 
 def test_no_floating_point_in_the_kernels_behind_the_quantisation():
