@@ -1378,6 +1378,36 @@ extern "C" int qn_debug_step_math(qn_ctx* c, int which, const double* in, uint32
   if (rc != QN_OK) { c->last_error = "debug_step_math: HIP call failed"; return rc; }
   return QN_OK;
 }
+namespace qn { hipError_t debug_launch_linearize(int which, const double* in, uint32_t n, uint32_t arg, double* out, hipStream_t stream); }      // qn_linearize_debug.hip
+// developer / test entry point: accumulate_point_n, emit_point with its folds, and reduce_rows on the caller's inputs (the kernels: qn_linearize_debug.hip)
+extern "C" int qn_debug_linearize(qn_ctx* c, int which, const double* in, uint32_t n, uint32_t arg, double* out) {
+  if (!c || !in || !out || which < 0 || which >= QN_DEBUG_LINEARIZE_WHICH) return QN_ERR_INVALID_ARG;
+  size_t n_in, n_out;
+  if (which == 0) {
+    if (arg != 0 || n > QN_DEBUG_LINEARIZE_MAX_POINTS) return QN_ERR_INVALID_ARG;
+    n_in = 37 * (size_t)n; n_out = 28 * (size_t)n;
+  } else if (which == 1) {
+    if (arg < 1 || arg > 4 || n > QN_DEBUG_LINEARIZE_MAX_BLOCKS) return QN_ERR_INVALID_ARG;
+    n_in = (25 + (size_t)arg * 256 * 13) * n; n_out = 5 * 28 * (size_t)n;
+  } else {
+    if ((arg != 256 && arg != 257 && arg != 512 && arg != 513) || n > QN_DEBUG_LINEARIZE_MAX_ROWS) return QN_ERR_INVALID_ARG;
+    n_in = 28 * (size_t)n; n_out = 28;
+  }
+  if (n == 0) return QN_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  double* d = nullptr;                                          // in | out
+  HIPCHK(c, hipMalloc(&d, (n_in + n_out) * sizeof(double)));
+  double* d_out = d + n_in;
+  int rc = QN_OK;
+  if (hipMemcpyAsync(d, in, n_in * sizeof(double), hipMemcpyHostToDevice, c->stream) != hipSuccess || hipMemsetAsync(d_out, 0, n_out * sizeof(double), c->stream) != hipSuccess) rc = QN_ERR_HIP;
+  if (rc == QN_OK) {
+    if (qn::debug_launch_linearize(which, d, n, arg, d_out, c->stream) != hipSuccess || hipMemcpyAsync(out, d_out, n_out * sizeof(double), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+        hipStreamSynchronize(c->stream) != hipSuccess) rc = QN_ERR_HIP;
+  }
+  (void)hipFree(d);
+  if (rc != QN_OK) { c->last_error = "debug_linearize: HIP call failed"; return rc; }
+  return QN_OK;
+}
 extern "C" int qn_debug_get_counters(qn_ctx* c, uint32_t out[16]) {
   if (!c || !c->dbg_counters) return QN_ERR_INVALID_ARG;
   if (hipStreamSynchronize(c->stream) != hipSuccess) return QN_ERR_HIP;

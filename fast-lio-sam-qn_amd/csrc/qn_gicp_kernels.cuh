@@ -5,13 +5,14 @@
 #pragma once
 #include "qn_device.cuh"
 #include "qn_step_math.cuh"
+#include "qn_linearize.cuh"
 #include "qn_knn_hist.cuh"
 #include "../../include/qn_engine.h"
 #include "qn_util_kernels.cuh"
 
 namespace qn {
 
-#define QN_NPART 28            // 21 (upper H) + 6 (b) + 1 (cost)
+// (QN_NPART = 28, the sums of a linearisation: qn_linearize.cuh)
 #define QN_ACC_MAX_BLOCKS 512  // accumulate grid = min(ceil(n / 256), this): fixed for a given n -> deterministic reduction tree
 #define QN_MAX_TRACE 1024
 
@@ -707,64 +708,7 @@ __global__ void __launch_bounds__(BLOCK, GROUP ? 5 : 6) k_nn_search(GridView src
 //          H += J^T M J (21 unique), b += J^T M e, cost += e^T M e.
 // phase 1: compute_error at the trial transform xi with the CACHED correspondences and the M of x0.
 // Fixed grid, fixed per-thread striding, fixed reduction tree => bitwise reproducible partials.
-// one correspondence's contribution: M = (C_B + R C_A R^T)^-1, e = mu_B - T mu_A, J = [skew(T mu_A) | -I];
-// acc[0..20] += upper J^T M J, acc[21..26] += J^T M e (both only when `lin`), acc[27] += e^T M e.
-// PLANE-regularised covariances are exactly C = I - 0.999 n n^T, so the kernels carry the normals (3 f64 per point
-// instead of 6):  C_B + R C_A R^T = (I - 0.999 n_B n_B^T) + (I - 0.999 m m^T),  m = R n_A.
-// Rx: 3x4 pose whose rotation block transforms the source normal (x0); Tx: 3x4 pose the residual is evaluated at (x0 when linearising,
-// xi in an LM trial pass).  J = [skew(T mu_A) | -I] is mostly zeros and ones: the products are written out term by term, in the order
-// of the dense formula, so the sums are bit-identical to it (adding an exact 0 or multiplying by -1 does not round).
-__device__ __forceinline__ void accumulate_point_n(const double (*Rx)[4], const double (*Tx)[4], const float4 pa, const float4 pb,
-                                                   const double na[3], const double nb[3], const bool lin, double acc[QN_NPART]) {
-  double m[3];
-#pragma unroll
-  for (int a = 0; a < 3; a++) m[a] = Rx[a][0] * na[0] + Rx[a][1] * na[1] + Rx[a][2] * na[2];
-  // R C_A R^T = R R^T - 0.999 m m^T.  R R^T is I to rounding for every pose the optimiser builds from the identity guess of
-  // loop_closure.cpp:124, but NOT for a caller's f32 guess with a rotation (pcl::Registration::align(output, guess)): its rows are
-  // orthonormal to 6e-8 only, the reference multiplies with the matrix as it is, and the difference is 1e-7 of the cost.
-  M3 rcr;
-#pragma unroll
-  for (int a = 0; a < 3; a++)
-#pragma unroll
-    for (int b = a; b < 3; b++) {      // the upper triangle, mirrored: the sum of two symmetric matrices, formed once per pair (a, b) - its inverse then has three cofactors less to form
-      const double g = Rx[a][0] * Rx[b][0] + Rx[a][1] * Rx[b][1] + Rx[a][2] * Rx[b][2];
-      rcr.m[a][b] = ((a == b ? 1.0 : 0.0) - 0.999 * nb[a] * nb[b]) + (g - 0.999 * m[a] * m[b]);
-      rcr.m[b][a] = rcr.m[a][b];
-    }
-  const M3 M = m3_inverse(rcr);
-  const double mA[3] = {(double)pa.x, (double)pa.y, (double)pa.z};
-  double tA[3], e[3], Me[3];
-#pragma unroll
-  for (int r = 0; r < 3; r++) tA[r] = Tx[r][0] * mA[0] + Tx[r][1] * mA[1] + Tx[r][2] * mA[2] + Tx[r][3];
-  e[0] = (double)pb.x - tA[0]; e[1] = (double)pb.y - tA[1]; e[2] = (double)pb.z - tA[2];
-#pragma unroll
-  for (int r = 0; r < 3; r++) Me[r] = M.m[r][0] * e[0] + M.m[r][1] * e[1] + M.m[r][2] * e[2];
-  acc[27] += e[0] * Me[0] + e[1] * Me[1] + e[2] * Me[2];
-  if (lin) {
-    const double x = tA[0], y = tA[1], z = tA[2];
-    // MS = M skew(tA): column 0 = M (0, z, -y), column 1 = M (-z, 0, x), column 2 = M (y, -x, 0);  M J = [MS | -M]
-    double MS[3][3];
-#pragma unroll
-    for (int r = 0; r < 3; r++) { MS[r][0] = M.m[r][1] * z + M.m[r][2] * (-y); MS[r][1] = M.m[r][0] * (-z) + M.m[r][2] * x; MS[r][2] = M.m[r][0] * y + M.m[r][1] * (-x); }
-    // upper J^T M J, row-major over (r, c >= r):  rows 0..2 = skew(tA)^T [MS | -M], rows 3..5 = M
-    // row 0: J[:,0] = (0, z, -y)
-    acc[0] += z * MS[1][0] + (-y) * MS[2][0]; acc[1] += z * MS[1][1] + (-y) * MS[2][1]; acc[2] += z * MS[1][2] + (-y) * MS[2][2];
-    // (the rotation-translation block -skew(tA)^T M is minus the TRANSPOSE of MS: M is symmetric bit for bit - the inverse of a mirrored matrix - so z (-M10) + (-y)(-M20)
-    //  and -(M01 z + M02 (-y)) are the same products and the same rounded sum: nine entries without a multiplication)
-    acc[3] += -MS[0][0]; acc[4] += -MS[1][0]; acc[5] += -MS[2][0];
-    // row 1: J[:,1] = (-z, 0, x)
-    acc[6] += (-z) * MS[0][1] + x * MS[2][1]; acc[7] += (-z) * MS[0][2] + x * MS[2][2];
-    acc[8] += -MS[0][1]; acc[9] += -MS[1][1]; acc[10] += -MS[2][1];
-    // row 2: J[:,2] = (y, -x, 0)
-    acc[11] += y * MS[0][2] + (-x) * MS[1][2];
-    acc[12] += -MS[0][2]; acc[13] += -MS[1][2]; acc[14] += -MS[2][2];
-    // rows 3..5: (-I)^T (-M) = M
-    acc[15] += M.m[0][0]; acc[16] += M.m[0][1]; acc[17] += M.m[0][2]; acc[18] += M.m[1][1]; acc[19] += M.m[1][2]; acc[20] += M.m[2][2];
-    // J^T M e
-    acc[21] += z * Me[1] + (-y) * Me[2]; acc[22] += (-z) * Me[0] + x * Me[2]; acc[23] += y * Me[0] + (-x) * Me[1];
-    acc[24] += -Me[0]; acc[25] += -Me[1]; acc[26] += -Me[2];
-  }
-}
+// (accumulate_point_n, one correspondence's contribution to the 28 sums: qn_linearize.cuh - plain C++ there, so that a host build can test it.)
 
 // Rows that another block of the SAME launch reads (the last block to finish runs the controller: controller_tail) leave their block as agent-scope write-through
 // stores and are read with agent-scope loads - the per-XCD L2s are never asked to be coherent (the hand-off of the persistent kernel, qn_persist.cuh).
@@ -773,25 +717,6 @@ __device__ __forceinline__ void pr_store(unsigned long long* p, unsigned long lo
 __device__ __forceinline__ unsigned long long pr_load(const unsigned long long* p) { return __hip_atomic_load((qn_gu64*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void row_store(double* p, double v, const bool coherent) {
   if (coherent) pr_store((unsigned long long*)p, (unsigned long long)__double_as_longlong(v)); else *p = v;
-}
-
-// block-level reduction of the 28 per-thread sums (DPP row sums + 2 cross-row shuffles per wave, then the 4 waves in order)
-__device__ __forceinline__ void reduce_block_partials(const double acc[QN_NPART], const bool lin, double* __restrict__ partials, double (*red)[QN_NPART], const uint32_t blk, const bool coherent = false) {
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  if (lin) {
-#pragma unroll
-    for (int t = 0; t < QN_NPART; t++) { double v = wave_sum_f64_dpp(acc[t]); if (lane == 63) red[wid][t] = v; }
-  } else {
-    double v = wave_sum_f64_dpp(acc[27]);
-    if (lane == 63) { for (int t = 0; t < 27; t++) red[wid][t] = 0; red[wid][27] = v; }
-  }
-  __syncthreads();
-  if (threadIdx.x < QN_NPART) {
-    double s = 0;
-#pragma unroll
-    for (int w = 0; w < QN_BLOCK / 64; w++) s += red[w][threadIdx.x];
-    row_store(&partials[(size_t)blk * QN_NPART + threadIdx.x], s, coherent);   // blk = LOGICAL block: the reduction tree does not depend on the block order
-  }
 }
 
 // ------------------------------------------------------------------ K4a'' first (unseeded) pass, one query per LANE
@@ -1150,7 +1075,8 @@ __device__ inline void solve_controller(GicpState* st, const double* sums, const
 // threads takes two pairs per thread - the ORDER of the additions is the same for every block size, so every caller (the controller tail of k_tick / k_accumulate /
 // k_far_reduce, k_solve, the persistent kernel's reducer) gets the same bits.  The loads of up to 32 rows per sub-sum are issued back to back (ONE memory round
 // trip - the rows sit in L2 / MALL, ~1 us away).  COHERENT: the rows were written by other blocks of THIS launch (row_store) - agent-scope loads.
-// Ends with a __syncthreads(); sums[] is valid for every thread afterwards.
+// Ends with a __syncthreads(); sums[] is valid for every thread afterwards.  (The four instantiations are held bit for bit to the order restated in
+// tests/linearize_checks.py, at 1 to 1153 rows: tests/test_gpu_linearize.py.)
 #define QN_ROWS_BATCH 32
 #define QN_ROW_SEGS 18
 template <int NT, bool COHERENT>

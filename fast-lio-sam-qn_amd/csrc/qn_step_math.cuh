@@ -1,5 +1,5 @@
 // qn_step_math.cuh - the small dense f64 arithmetic of a registration tick, each routine for one thread: the adjugate inverse of the 3 x 3 matrix C_B + R C_A R'
-// formed once per correspondence (m3_inverse; qn_tick.cuh, qn_gicp_kernels.cuh), and what the controller does with the reduced 6 x 6 system - the two LDL'
+// formed once per correspondence (m3_inverse; qn_tick.cuh, qn_linearize.cuh), and what the controller does with the reduced 6 x 6 system - the two LDL'
 // solves of (H + lambda I) d = -b (d_ldlt_solve6_fast, unpivoted and unrolled, and d_ldlt_solve6, diagonally pivoted, which d_propose in qn_gicp_kernels.cuh
 // takes when the first meets a pivot that is not positive), the rotation update exp(d[0:3]) (d_so3_exp), the product of two isometries (d_iso_mul) and the
 // convergence test on the step (d_is_converged, with the GicpConfig it reads).  Plain C++ as well, so that a host build can check them against a high-precision

@@ -68,7 +68,7 @@ struct TickArgs {
 // search scratch (7 x 64 f64 = 3.5 KB; DS operations of one wave execute in order, so no block barrier): lane (c, s) sums 8 of the 64
 // values of component c, three DPP steps fold the 8 sub-sums.  Then the 4 wave sums meet in a [4][28] LDS table.  ~150 wave
 // instructions instead of 28 x 6 shuffle steps (~600), and no LDS beyond what the search already owns, so 4+ blocks fit a CU.
-// Fixed order throughout: bitwise reproducible.
+// Fixed order throughout: bitwise reproducible.  (The order is restated in tests/linearize_checks.py and held bit for bit: tests/test_gpu_linearize.py.)
 __device__ __forceinline__ double dpp_xor_add(double v, const int which) {       // which: 0 -> lane ^ 1, 1 -> lane ^ 2 (quad_perm); 2 -> row_half_mirror (pairs l, 7 - l)
   union { double d; int i[2]; } a, b; a.d = v;
   if (which == 0) { b.i[0] = __builtin_amdgcn_mov_dpp(a.i[0], 0xB1, 0xF, 0xF, true); b.i[1] = __builtin_amdgcn_mov_dpp(a.i[1], 0xB1, 0xF, 0xF, true); }
@@ -98,7 +98,8 @@ __device__ __forceinline__ void pose_gram(const double* __restrict__ sx0, double
 }
 // One correspondence's contribution to the 28 sums (accumulate_point_n's arithmetic, term for term), produced SEVEN values at a time
 // and folded across the wave at once: a lane never holds the 28 f64 accumulators (56 VGPRs) next to the matrices they are made of,
-// which is what pushed this kernel to 240 VGPRs.  have = false: the lane contributes zeros.
+// which is what pushed this kernel to 240 VGPRs.  have = false: the lane contributes zeros.  (Both held bit for bit against accumulate_point_n, a lane without a
+// correspondence holding NaN, Inf or 1e300 and the pose a NaN included: tests/test_gpu_linearize.py through qn_debug_linearize.)
 __device__ __forceinline__ void emit_point(const bool have, const bool lin, const bool first, const double* __restrict__ sRx, const double* __restrict__ sTx, const double* __restrict__ sG, const float4 pa, const float4 pb,
                                            const double na[3], const double nb[3], double* __restrict__ wbuf, double* __restrict__ wrow) {
   // sRx / sTx: the 3 x 4 poses (row-major, stride 4) in LDS - Rx rotates the source normal (x0), Tx is the pose the residual is evaluated at (x0; xi in an LM trial pass);

@@ -151,6 +151,32 @@ class Context:
         self.check(self._l.qn_debug_step_math(self.h, C.c_int(which), _p(a), C.c_uint32(n), _p(out)))
         return out[:n]
 
+    LIN_POINT, LIN_EMIT, LIN_ROWS = 0, 1, 2                          # qn_debug_linearize's `which`
+    LIN_POINT_STRIDE, LIN_HEAD, LIN_LANE, LIN_BLOCK, LIN_NPART = 37, 25, 13, 256, 28
+
+    def debug_linearize(self, which, data, arg=0):
+        """qn_debug_linearize (the record layouts: include/qn_engine.h).  LIN_POINT: accumulate_point_n on the rows of data (n, 37) -> (n, 28).  LIN_EMIT:
+        emit_point on blocks of 256 lanes, data (blocks, 25 + arg x 256 x 13), arg = trips -> (blocks, 5, 28): the four wave rows, then the block's row.
+        LIN_ROWS: reduce_rows<NT, COHERENT> with arg = NT + COHERENT on data (rows, 28) -> (28,).  Test infrastructure."""
+        if which == self.LIN_POINT:
+            si, shape = self.LIN_POINT_STRIDE, lambda n: (n, self.LIN_NPART)
+        elif which == self.LIN_EMIT:
+            if arg not in (1, 2, 3, 4):
+                raise ValueError("debug_linearize: %r trips" % (arg,))
+            si, shape = self.LIN_HEAD + arg * self.LIN_BLOCK * self.LIN_LANE, lambda n: (n, 5, self.LIN_NPART)
+        elif which == self.LIN_ROWS:
+            si, shape = self.LIN_NPART, lambda n: (min(n, 1) * self.LIN_NPART,)
+        else:
+            raise ValueError("debug_linearize: which = %r" % (which,))
+        a = np.ascontiguousarray(data, dtype=np.float64).reshape(-1, si)
+        n = len(a)
+        if n == 0:
+            a = np.zeros((1, si))                                     # (an empty array may have no address; the call refuses null pointers)
+        out = np.zeros(max(int(np.prod(shape(n))), 1))
+        self._l.qn_debug_linearize.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
+        self.check(self._l.qn_debug_linearize(self.h, C.c_int(which), _p(a), C.c_uint32(n), C.c_uint32(arg), _p(out)))
+        return out[:int(np.prod(shape(n)))].reshape(shape(n))
+
     def grid_info(self, which):
         out = np.zeros(8)
         self.check(self._l.qn_debug_get_grid(self.h, C.c_int(which), _p(out)))

@@ -1164,6 +1164,24 @@ int  qn_debug_eig3(qn_ctx*, int which, const double* a6, uint32_t n, double* w_o
 #define QN_DEBUG_STEP_MATH_WHICH 6
 #define QN_DEBUG_STEP_MATH_MAX (1u << 20)
 int  qn_debug_step_math(qn_ctx*, int which, const double* in, uint32_t n, double* out);
+/* developer / tests: what stands between a correspondence and the 6 x 6 system of a registration tick, on caller-supplied inputs (csrc/qn_linearize_debug.hip).
+ * Packed f64 throughout; poses are 3 x 4 row major (rotation | translation); points are f64 values that are exactly f32 (they are converted with a cast);
+ * normals stand for the covariance I - 0.999 n n^T; lin and have are 0.0 or anything else; the 28 sums are the 21 upper entries of H = J^T M J row major,
+ * the 6 of b = J^T M e, then e^T M e.
+ *   0  accumulate_point_n (csrc/qn_linearize.cuh), one correspondence per lane, the accumulators starting at zero.  n = correspondences, arg = 0.
+ *      in per correspondence (37): Rx (12), Tx (12), pa (3), pb (3), na (3), nb (3), lin.  out per correspondence: the 28 sums.
+ *   1  emit_point as the kernels call it (csrc/qn_tick.cuh): blocks of 256 lanes = 4 waves, the block's pose pair in LDS with G = Rx Rx^T from pose_gram, the
+ *      transpose buffers and wave rows in LDS of AccumulateK::run's sizes.  n = blocks, arg = trips per lane, 1 .. 4; `first` is true on the first trip only.
+ *      in per block (25 + arg x 256 x 13): Rx (12), Tx (12), lin, then per trip and lane, lane fastest: have, pa (3), pb (3), na (3), nb (3) - a lane with
+ *      have = 0 hands its record over as it is.  out per block (5 x 28): the four wave rows as emit_point left them, then their sum in wave order.
+ *   2  reduce_rows (csrc/qn_gicp_kernels.cuh).  n = rows, arg = NT + COHERENT: 256, 257, 512 or 513.  in: n x 28.  out: the 28 sums.
+ * QN_ERR_INVALID_ARG with nothing launched and nothing written: a null pointer, which outside 0 .. 2, an arg other than the above, n above
+ * QN_DEBUG_LINEARIZE_MAX_POINTS / _MAX_BLOCKS / _MAX_ROWS.  n == 0 succeeds and writes nothing.  Nothing on a product path calls it. */
+#define QN_DEBUG_LINEARIZE_WHICH 3
+#define QN_DEBUG_LINEARIZE_MAX_POINTS (1u << 20)
+#define QN_DEBUG_LINEARIZE_MAX_BLOCKS (1u << 11)
+#define QN_DEBUG_LINEARIZE_MAX_ROWS (1u << 16)
+int  qn_debug_linearize(qn_ctx*, int which, const double* in, uint32_t n, uint32_t arg, double* out);
 /* developer / tests: the device builds of what the map units share (csrc/qn_map_compact.cuh: the wave and block folds, the key walk, the slot folds, the row
  * scan, the block rank; csrc/qn_union_find.cuh: the two linkers) on caller-supplied inputs, on the store's stream with the store's scratch
  * (csrc/qn_map_selftest.hip).  Host arrays, packed, little endian; a block is 256 lanes = 4 waves of 64; u64 / i64 fields are 8-byte aligned in their records:
