@@ -304,6 +304,7 @@ struct Best1 {                         // 1-NN, plus the squared distance of the
   float bd;                            // key's d2 as a float (+inf while there is no key): best <= second always, so a new point's d2 updates the runner-up as the MEDIAN of the three
   __device__ __forceinline__ void init() { key = QN_INF_KEY; second = __int_as_float(0x7f800000); bd = __int_as_float(0x7f800000); }
   // UNIQUE: the caller never shows a point twice (every scan of the engine: one pass over disjoint segments per round) - the `same point again` test is dropped
+  // (both forms and finish<1 | 2 | 4> lane for lane against a serial restatement, and stream_box's "each point of the box once": tests/test_gpu_search.py)
   template <bool UNIQUE = false>
   __device__ __forceinline__ void consider(bool on, float d2, uint32_t idx) {
     const unsigned long long k = pack_key(d2, idx);                   // branch-free (selects): no exec-mask region for the scheduler to sink loads into
@@ -656,6 +657,8 @@ __device__ __forceinline__ uint32_t stream_clusters(const GridView& g, WaveLds* 
 // best distance if known - then the next round certifies - else 2 r + cell, never beyond the proven
 // bound r_cap) and it retries, up to max_rounds.  Returns certified; r is updated to the radius the next
 // round would use; d_unseen = lower bound on the distance of every point NOT scanned in the last round.
+// (Called directly by tests/test_gpu_search.py through qn_debug_search, as are wave_search_single, wave_search_far16 and lane_ball_knn: the key against a brute force,
+//  and min(sqrt(second), d_unseen) - what the callers store as the tracking bound - against the exact distance to every other point, within 4 ulps.)
 template <int S, class Sink>
 __device__ __forceinline__ bool wave_search(const GridView& g, float qx, float qy, float qz, bool active, float& r, const float r_cap,
                                             int max_rounds, Sink& sink, WaveLds* lds, float& d_unseen) {

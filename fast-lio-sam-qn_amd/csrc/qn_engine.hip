@@ -1408,6 +1408,135 @@ extern "C" int qn_debug_linearize(qn_ctx* c, int which, const double* in, uint32
   if (rc != QN_OK) { c->last_error = "debug_linearize: HIP call failed"; return rc; }
   return QN_OK;
 }
+namespace qn { hipError_t debug_launch_search(int which, const GridView& g, uint32_t ncells, const uint32_t* in, uint32_t n, uint32_t arg, uint32_t* out, hipStream_t stream); }      // qn_search_debug.hip
+// developer / test entry point: the sinks, bounds, candidate streams and cooperative searches of qn_device.cuh on the caller's records against the grid of the cloud
+// last set (the kernels: qn_search_debug.hip; the record layouts: include/qn_engine.h).  Every record is checked here, before any launch.
+static bool ds_finite(uint32_t w) { return (w & 0x7f800000u) != 0x7f800000u; }
+static float ds_f(uint32_t w) { float f; memcpy(&f, &w, 4); return f; }
+static bool kmax_ok(uint32_t km) { return km == 16 || km == 20 || km == 24 || km == 32; }
+extern "C" int qn_debug_search(qn_ctx* c, int which, int grid, const void* in_v, uint32_t n, uint32_t arg, void* out_v) {
+  if (!c || !in_v || !out_v || which < 0 || which >= QN_DEBUG_SEARCH_WHICH || (grid != 0 && grid != 1)) return QN_ERR_INVALID_ARG;
+  const uint32_t* in = static_cast<const uint32_t*>(in_v);
+  const bool needs_grid = which != QN_DS_BEST1 && which != QN_DS_DIVMOD;
+  GridView g{}; GridDims d{};
+  if (needs_grid) {
+    CloudBuf& b = c->cloud[grid];
+    if (!b.has_grid || !b.dims_host) return QN_ERR_NOT_READY;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (join_target(c) != QN_OK || hipStreamSynchronize(c->stream) != hipSuccess || (c->stream2 && hipStreamSynchronize(c->stream2) != hipSuccess)) return QN_ERR_HIP;
+    d = *b.dims_host;
+    if (d.nonfinite || d.n == 0 || d.n != b.n) return QN_ERR_EMPTY_CLOUD;
+    if (d.ncells >= (1u << 22) || d.ncells > c->max_cells) return QN_ERR_CAPACITY;      // (divmod_small's range: a segment table is never longer than the cell table)
+    g = b.grid; g.dbg = nullptr;
+  }
+  size_t w_in = 0, w_out = 0;                                        // 32-bit words
+  const uint32_t ncells = d.ncells;
+  auto finite_rec = [&](const uint32_t* r, int a, int b_) { for (int i = a; i < b_; i++) if (!ds_finite(r[i])) return false; return true; };
+  switch (which) {
+    case QN_DS_DUMP:
+      if (n != d.n || arg != ncells) return QN_ERR_INVALID_ARG;
+      w_in = 0; w_out = (size_t)ncells + 1 + 4 * (size_t)n; break;
+    case QN_DS_BEST1: {
+      const uint32_t L = arg >> 16, S = arg & 7u;
+      if (n == 0 || n > QN_DEBUG_SEARCH_MAX_WAVES || L > QN_DEBUG_SEARCH_MAX_STEPS || (S != 1 && S != 2 && S != 4) || (arg & 0xfef8u)) return QN_ERR_INVALID_ARG;
+      w_in = ((size_t)L * 192 + 64) * n; w_out = 256 * (size_t)n; break; }
+    case QN_DS_BOUNDS:
+      if (n == 0 || n > QN_DEBUG_SEARCH_MAX_QUERIES || arg != 0) return QN_ERR_INVALID_ARG;
+      for (uint32_t i = 0; i < n; i++) {
+        const uint32_t* r = in + 8 * (size_t)i;
+        if (r[0] >= (uint32_t)d.ntx || r[1] >= (uint32_t)d.nty || r[2] >= (uint32_t)d.ntz || !finite_rec(r, 3, 8) || !(ds_f(r[6]) > 0.f)) return QN_ERR_INVALID_ARG;
+      }
+      w_in = 8 * (size_t)n; w_out = 16 * (size_t)n; break;
+    case QN_DS_DIVMOD:
+      if (n != 0 || arg != 0) return QN_ERR_INVALID_ARG;
+      w_in = 0; w_out = 6; break;
+    case QN_DS_STREAM_BOX:
+      if (n == 0 || n > QN_DEBUG_SEARCH_MAX_WAVES || arg == 0 || arg > QN_DEBUG_SEARCH_MAX_RECORDED) return QN_ERR_INVALID_ARG;
+      for (uint32_t i = 0; i < n; i++) {
+        const uint32_t* r = in + 12 * (size_t)i;
+        const int x0 = (int)r[0], x1 = (int)r[1], y0 = (int)r[2], y1 = (int)r[3], z0 = (int)r[4], z1 = (int)r[5];
+        if (x0 < 0 || x0 > x1 || x1 >= d.nx || y0 < 0 || y0 > y1 || y1 >= d.ny || z0 < 0 || z0 > z1 || z1 >= d.nz || r[6] > 2u || !finite_rec(r, 7, 11)) return QN_ERR_INVALID_ARG;
+        if (r[6] != 0u) {                                             // tile modes: the box the callers hand over, widened to whole tiles
+          if ((x0 & 7) || (y0 & 3) || (z0 & 3) || x1 != std::min((x1 | 7), d.nx - 1) || y1 != std::min((y1 | 3), d.ny - 1) || z1 != std::min((z1 | 3), d.nz - 1)) return QN_ERR_INVALID_ARG;
+          if (r[6] == 2u && !(ds_f(r[10]) >= 0.f)) return QN_ERR_INVALID_ARG;
+        }
+      }
+      w_in = 12 * (size_t)n; w_out = (4 + (size_t)arg) * n; break;
+    case QN_DS_WAVE_SEARCH1:
+      if (n == 0 || n > QN_DEBUG_SEARCH_MAX_QUERIES || arg < 1 || arg > 64) return QN_ERR_INVALID_ARG;
+      for (uint32_t i = 0; i < n; i++) {
+        const uint32_t* r = in + 8 * (size_t)i;                       // r_cap: +inf ("none proven") or a finite radius
+        if (!finite_rec(r, 0, 4) || !(ds_f(r[3]) > 0.f) || !(ds_f(r[4]) > 0.f) || r[4] > 0x7f800000u) return QN_ERR_INVALID_ARG;
+      }
+      w_in = 8 * (size_t)n; w_out = 8 * (size_t)n; break;
+    case QN_DS_WAVE_SEARCH_SINGLE:
+      if (n == 0 || n > QN_DEBUG_SEARCH_MAX_QUERIES || arg != 0) return QN_ERR_INVALID_ARG;
+      for (uint32_t i = 0; i < n; i++) {
+        const uint32_t* r = in + 8 * (size_t)i;                       // r_cap: +inf or a finite radius not below the first (below it the search would stand at one radius until its round limit)
+        if (!finite_rec(r, 0, 4) || !(ds_f(r[3]) > 0.f) || r[4] > 0x7f800000u || !(ds_f(r[4]) >= ds_f(r[3]))) return QN_ERR_INVALID_ARG;
+      }
+      w_in = 8 * (size_t)n; w_out = 8 * (size_t)n; break;
+    case QN_DS_WAVE_SEARCH_FAR16:
+      if (n == 0 || n > QN_DEBUG_SEARCH_MAX_QUERIES || (n & 15u) || arg != 0) return QN_ERR_INVALID_ARG;
+      for (uint32_t i = 0; i < n; i++) {
+        const uint32_t* r = in + 8 * (size_t)i;
+        if (!finite_rec(r, 0, 4) || !(ds_f(r[3]) > 0.f)) return QN_ERR_INVALID_ARG;
+      }
+      w_in = 8 * (size_t)n; w_out = 8 * (size_t)n; break;
+    case QN_DS_BESTK: {
+      const uint32_t KM = arg & 63u, k = (arg >> 8) & 63u, S = (arg >> 14) & 7u, L = arg >> 17;
+      if (n == 0 || n > QN_DEBUG_SEARCH_MAX_WAVES || L > QN_DEBUG_SEARCH_MAX_STEPS || !kmax_ok(KM) || k < 1 || k > KM || (S != 1 && S != 4) || (arg & 0xc0u)) return QN_ERR_INVALID_ARG;
+      w_in = ((size_t)L * 192 + 64) * n; w_out = 64 * (size_t)(2 * k + 4) * n; break; }
+    case QN_DS_WAVE_SEARCH_K: {
+      const uint32_t rounds = arg & 255u, KM = (arg >> 8) & 63u, k = (arg >> 16) & 63u;
+      if (n == 0 || n > QN_DEBUG_SEARCH_MAX_QUERIES || rounds < 1 || rounds > 64 || !kmax_ok(KM) || k < 1 || k > KM || (arg & 0xffc0c000u)) return QN_ERR_INVALID_ARG;
+      for (uint32_t i = 0; i < n; i++) {
+        const uint32_t* r = in + 8 * (size_t)i;
+        if (!finite_rec(r, 0, 4) || !(ds_f(r[3]) > 0.f) || !(ds_f(r[4]) > 0.f) || r[4] > 0x7f800000u) return QN_ERR_INVALID_ARG;
+      }
+      w_in = 8 * (size_t)n; w_out = (size_t)(2 * k + 4) * n; break; }
+    case QN_DS_STREAM_CLUSTERS: {
+      const uint32_t S = arg >> 24, cap = arg & 0xffffffu;
+      if (n == 0 || n > QN_DEBUG_SEARCH_MAX_WAVES || (S != 1 && S != 4) || cap == 0 || cap > QN_DEBUG_SEARCH_MAX_RECORDED) return QN_ERR_INVALID_ARG;
+      for (size_t i = 0; i < (size_t)n * 64; i++) {
+        const uint32_t* r = in + 8 * i;
+        if (!finite_rec(r, 0, 4) || !(ds_f(r[3]) > 0.f)) return QN_ERR_INVALID_ARG;
+        if (S == 4 && memcmp(r, in + 8 * ((i & ~(size_t)63) + (i & 15)), 20) != 0) return QN_ERR_INVALID_ARG;      // the four sub-slots of a query hold the same record
+      }
+      w_in = 8 * 64 * (size_t)n; w_out = (8 + 64 * (4 + 2 * (size_t)cap)) * n; break; }
+    case QN_DS_BALL_CELLS: {
+      const uint32_t v = arg >> 24, cap = arg & 0xffffffu, fg = v == 0u ? 1u : (v == 3u ? 16u : 8u);
+      if (n == 0 || n > QN_DEBUG_SEARCH_MAX_QUERIES || v > 3u || cap == 0 || cap > QN_DEBUG_SEARCH_MAX_RECORDED) return QN_ERR_INVALID_ARG;
+      for (uint32_t i = 0; i < n; i++) {
+        const uint32_t* r = in + 8 * (size_t)i;
+        if (!finite_rec(r, 0, 4) || !(ds_f(r[3]) > 0.f)) return QN_ERR_INVALID_ARG;
+      }
+      w_in = 8 * (size_t)n; w_out = (((size_t)n * fg + 63) / 64) * 64 * (2 + (size_t)cap); break; }
+    case QN_DS_LANE_BALL_KNN: default: {
+      const uint32_t KM = arg & 63u, k = (arg >> 8) & 63u;
+      if (n == 0 || n > QN_DEBUG_SEARCH_MAX_QUERIES || !kmax_ok(KM) || k < 1 || k > KM || (arg & 0xffffc0c0u)) return QN_ERR_INVALID_ARG;
+      for (uint32_t i = 0; i < n; i++) {
+        const uint32_t* r = in + 8 * (size_t)i;
+        if (!finite_rec(r, 0, 4) || !(ds_f(r[3]) > 0.f)) return QN_ERR_INVALID_ARG;
+      }
+      w_in = 8 * (size_t)n; w_out = (size_t)(2 * k + 4) * n; break; }
+  }
+  if (w_in + w_out > QN_DEBUG_SEARCH_MAX_WORDS) return QN_ERR_INVALID_ARG;
+  HIPCHK(c, hipSetDevice(c->device));
+  uint32_t* dv = nullptr;                                            // in | out
+  HIPCHK(c, hipMalloc(&dv, (w_in + w_out + 2) * sizeof(uint32_t)));
+  uint32_t* d_out = dv + ((w_in + 1) & ~(size_t)1);                   // (8-byte aligned: which 3 writes 64-bit words)
+  int rc = QN_OK;
+  if ((w_in && hipMemcpyAsync(dv, in, w_in * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream) != hipSuccess) || hipMemsetAsync(d_out, 0, w_out * sizeof(uint32_t), c->stream) != hipSuccess ||
+      (which == QN_DS_DIVMOD && hipMemsetAsync(d_out + 4, 0xff, 8, c->stream) != hipSuccess)) rc = QN_ERR_HIP;
+  if (rc == QN_OK) {
+    if (qn::debug_launch_search(which, g, ncells, dv, n, arg, d_out, c->stream) != hipSuccess || hipMemcpyAsync(out_v, d_out, w_out * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+        hipStreamSynchronize(c->stream) != hipSuccess) rc = QN_ERR_HIP;
+  }
+  (void)hipFree(dv);
+  if (rc != QN_OK) { c->last_error = "debug_search: HIP call failed"; return rc; }
+  return QN_OK;
+}
 extern "C" int qn_debug_get_counters(qn_ctx* c, uint32_t out[16]) {
   if (!c || !c->dbg_counters) return QN_ERR_INVALID_ARG;
   if (hipStreamSynchronize(c->stream) != hipSuccess) return QN_ERR_HIP;

@@ -177,6 +177,19 @@ class Context:
         self.check(self._l.qn_debug_linearize(self.h, C.c_int(which), _p(a), C.c_uint32(n), C.c_uint32(arg), _p(out)))
         return out[:int(np.prod(shape(n)))].reshape(shape(n))
 
+    DS_DUMP, DS_BEST1, DS_BOUNDS, DS_DIVMOD, DS_STREAM_BOX, DS_WAVE_SEARCH1, DS_WAVE_SEARCH_SINGLE, DS_WAVE_SEARCH_FAR16, DS_BESTK, DS_WAVE_SEARCH_K, DS_LANE_BALL_KNN, DS_STREAM_CLUSTERS, DS_BALL_CELLS = range(13)      # qn_debug_search's `which`
+
+    def debug_search(self, which, grid, words, n, arg, n_out):
+        """qn_debug_search (the record layouts: include/qn_engine.h): `words` = the packed uint32 input (floats as their bits), n and arg as the header says,
+        n_out = the uint32 words the call writes -> that many uint32.  Test infrastructure."""
+        a = np.ascontiguousarray(words, dtype=np.uint32).reshape(-1)
+        if a.size == 0:
+            a = np.zeros(1, dtype=np.uint32)                          # (an empty array may have no address; the call refuses null pointers)
+        out = np.zeros(max(int(n_out), 1), dtype=np.uint32)
+        self._l.qn_debug_search.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
+        self.check(self._l.qn_debug_search(self.h, C.c_int(which), C.c_int(grid), _p(a), C.c_uint32(n), C.c_uint32(arg), _p(out)))
+        return out[:int(n_out)]
+
     def grid_info(self, which):
         out = np.zeros(8)
         self.check(self._l.qn_debug_get_grid(self.h, C.c_int(which), _p(out)))

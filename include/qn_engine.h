@@ -1182,6 +1182,68 @@ int  qn_debug_step_math(qn_ctx*, int which, const double* in, uint32_t n, double
 #define QN_DEBUG_LINEARIZE_MAX_BLOCKS (1u << 11)
 #define QN_DEBUG_LINEARIZE_MAX_ROWS (1u << 16)
 int  qn_debug_linearize(qn_ctx*, int which, const double* in, uint32_t n, uint32_t arg, double* out);
+/* developer / tests: the result sinks, pruning bounds, candidate streams and cooperative searches of csrc/qn_device.cuh, called as they are on caller-supplied
+ * records (csrc/qn_search_debug.hip).  grid: 0 / 1, the source / target grid the context built for the cloud last set (fix the cell edge with the knob "cell");
+ * which 1 and 3 need none.  Host arrays of packed 32-bit words, floats as their bits; one wave of 64 lanes per block.
+ *   0  the grid as the device built it.  n = its points, arg = its padded cell count (tiles x 128).  out: cell_start (arg + 1), then per sorted point x, y, z and
+ *      the original index.
+ *   1  Best1.  n = waves, arg = S | UNIQUE << 8 | L << 16: L consider<UNIQUE> steps, then finish<S>, S one of 1, 2, 4.  in per wave: L x 64 x (on, d2, idx), lane
+ *      fastest, then the 64 `on` of finish.  out per lane: key low, key high, second, bd.
+ *   2  the bounds.  n = records, arg = 0.  in (8): tile tx, ty, tz, query x, y, z, radius r, face offset f.  out (16): tile_box_d2 | cap_of's o2 x, y, z and S |
+ *      cap_extent(r) axis 0, 1, 2 | cap_face_dist(f) axis 0, 1, 2 | cell_coord x, y, z | cell_key of that cell | 0.
+ *   3  divmod_small against / and % on the device: every n < 2^22 for d <= 128, and for every d < 2^22 the values 0, d - 1, d, 2^22 - 1, the largest multiple of d
+ *      below 2^22 and that +- 1.  n = arg = 0.  out: three 64-bit words - mismatches, pairs compared, the smallest mismatching n << 22 | d (all ones: none).
+ *   4  stream_box.  n = waves, arg = recorded candidates a wave at most.  in per wave (12): x0, x1, y0, y1, z0, z1 (cells, inclusive), mode (0 rows, 1 tiles, 2
+ *      tiles pruned by the ball), ball centre x, y, z, ball_r2, 0.  out per wave (4 + arg): candidates delivered, overflow (1: more than arg, the rest dropped),
+ *      the stream's return value, 0, then the original index of every candidate in delivery order.
+ *   5  wave_search<4, Best1>.  n = queries, 16 a wave, arg = max_rounds.  in per query (8): x, y, z, first radius, r_cap (+inf: none), active, 0, 0.  out per
+ *      query (8): key low, key high, second, d_unseen, certified, the radius left in r, 0, 0.
+ *   6  wave_search_single.  n = queries, one a wave, arg = 0.  in per query (8): x, y, z, first radius, r_cap (+inf, or finite and >= the first radius), 0, 0,
+ *      0.  out (8): key low, key high, second, d_unseen, then its SingleStats: rounds, candidates scanned, segments enumerated, the last radius.
+ *   7  wave_search_far16.  n = slots, a multiple of 16, 16 a wave, arg = 0.  in per slot (8): x, y, z, radius, member, 0, 0, 0.  out (8): key low, key high, second,
+ *      d_unseen, member, 0 ...
+ *   8  BestK<KMAX>.  n = waves, arg = KMAX | k << 8 | S << 14 | L << 17: KMAX one of 16, 20, 24, 32 (the four the product instantiates), 1 <= k <= KMAX, L
+ *      consider steps (the lazy queue: the whole wave flushes when one lane's queue holds QN_PEND_CAP), then finish<S>, S 1 or 4.  in: as 1.  out per lane
+ *      (2 k + 4): the k real entries ascending (key low, key high; all ones: none), w low, w high, found(), 0.
+ *   9  wave_search<4, BestK<KMAX>>.  n = queries, 16 a wave, arg = max_rounds | KMAX << 8 | k << 16.  in: as 5.  out per query (2 k + 4): the k entries
+ *      ascending, d_unseen, certified, the radius left in r, found().
+ *  10  lane_ball_knn<KMAX>, one query per lane.  n = queries, arg = KMAX | k << 8.  in per query (8): x, y, z, first radius, 0 ...  out per query (2 k + 4): the
+ *      k entries ascending, found(), 0, 0, 0.
+ *  11  build_clusters<S> with stream_clusters<S>: a first walk, then a REUSE second walk of the same clusters.  n = waves, arg = cap | S << 24, S 1 or 4.  in
+ *      per lane (8): x, y, z, r, todo, 0 .. (S = 4: the lanes l, l + 16, l + 32, l + 48 hold the same record).  out per wave: header (8): clusters, segments, the
+ *      first and the second walk's return value, overflow, 0 ..; then per lane (4 + 2 cap): cluster id, its box's tile mode, accepted in walk 1, in walk 2, then
+ *      the original indices the lane accepted under the callers' predicate `mine && in_tile && ccid == cid`, in delivery order: walk 1 (cap), walk 2 (cap).
+ *  12  the ball walks of csrc/qn_quatro_kernels.cuh.  n = queries, arg = cap | variant << 24: 0 for_each_in_ball_cells (a query per lane), 1
+ *      for_each_in_ball_cells_group<8>, 2 / 3 for_each_in_ball_cells_group_pre<8 | 16> (8 / 16 lanes a query, the group's QN_SEG_CAP table in LDS).  in per
+ *      query (8): x, y, z, r, on, 0 ..  out per lane, whole waves (2 + cap): delivered, overflow, then the sorted position of every point body() saw, in order.
+ * Everything is checked on the host before any launch; QN_ERR_INVALID_ARG with nothing launched and nothing written: a null pointer, which or grid out of range,
+ * a count of 0 or above QN_DEBUG_SEARCH_MAX_WAVES / _MAX_QUERIES / _MAX_STEPS (L) / _MAX_RECORDED (arg of 4), more than _MAX_WORDS words in and out together,
+ * a non-finite coordinate, a radius that is not finite and > 0, max_rounds outside 1 .. 64, a KMAX other than the four, k outside 1 .. KMAX, a tile or box outside the grid, a tile-mode box not widened to
+ * whole tiles, n or arg of 0 other than the grid's.  QN_ERR_NOT_READY: the context has no grid for that cloud; QN_ERR_EMPTY_CLOUD: the grid is empty (non-finite
+ * cloud).  Non-finite queries are refused.  By grep for finite_q, the product callers that screen them before they search are k_nn_search's grouped list
+ * pass (wave_search_far16), k_nn_track and k_tick; the queries of the k-NN kernels are the cloud's own points, finite because the grid build empties a cloud
+ * that holds another.  NOT screened: k_nn_search's first pass (wave_search<4>) and its one-entry-per-wave list pass (wave_search_single) hand a query over as
+ * the pose made it and rely on the searches' own `r == r` exits - those exits are not reached through this entry point.  Nothing on a product path calls it. */
+#define QN_DEBUG_SEARCH_WHICH 13
+#define QN_DS_DUMP 0
+#define QN_DS_BEST1 1
+#define QN_DS_BOUNDS 2
+#define QN_DS_DIVMOD 3
+#define QN_DS_STREAM_BOX 4
+#define QN_DS_WAVE_SEARCH1 5
+#define QN_DS_WAVE_SEARCH_SINGLE 6
+#define QN_DS_WAVE_SEARCH_FAR16 7
+#define QN_DS_BESTK 8
+#define QN_DS_WAVE_SEARCH_K 9
+#define QN_DS_LANE_BALL_KNN 10
+#define QN_DS_STREAM_CLUSTERS 11
+#define QN_DS_BALL_CELLS 12
+#define QN_DEBUG_SEARCH_MAX_WAVES (1u << 12)
+#define QN_DEBUG_SEARCH_MAX_QUERIES (1u << 16)
+#define QN_DEBUG_SEARCH_MAX_STEPS 64u
+#define QN_DEBUG_SEARCH_MAX_RECORDED (1u << 16)
+#define QN_DEBUG_SEARCH_MAX_WORDS (1u << 26)
+int  qn_debug_search(qn_ctx*, int which, int grid, const void* in, uint32_t n, uint32_t arg, void* out);
 /* developer / tests: the device builds of what the map units share (csrc/qn_map_compact.cuh: the wave and block folds, the key walk, the slot folds, the row
  * scan, the block rank; csrc/qn_union_find.cuh: the two linkers) on caller-supplied inputs, on the store's stream with the store's scratch
  * (csrc/qn_map_selftest.hip).  Host arrays, packed, little endian; a block is 256 lanes = 4 waves of 64; u64 / i64 fields are 8-byte aligned in their records:
