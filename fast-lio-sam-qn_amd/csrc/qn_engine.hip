@@ -15,6 +15,7 @@
 #include "qn_context.h"
 #include "qn_selftest.cuh"
 #include "qn_pool.h"
+#include "qn_kf_internal.h"   // C2fCached and the hooks other translation units reach this one through
 
 using namespace qn;
 

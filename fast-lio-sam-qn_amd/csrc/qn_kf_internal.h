@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <cstddef>
+#include <vector>
 #include "../../include/qn_engine.h"
 
 // the owned buffers of the store and of every unit around it (qn_kf_buf.h, with the error macro and the get-or-create of a unit's state)
@@ -73,6 +74,41 @@ int qn_kf_int_voxel_windows(qn_kf_store* s, const int32_t* ids, const double* po
 struct qn_kf_int_verify_pair { const float4* src; uint32_t ns; const float4* dst; uint32_t nt; int32_t query, cand; int stage; double Tq[16]; float Tg[16]; };
 int  qn_kf_int_verify_record(qn_kf_store* s, int kind, const qn_kf_int_verify_pair* p, uint32_t n);
 void qn_kf_int_verify_stale(qn_kf_store* s, int from, const int32_t* ids, uint32_t count);
+// a pair of the coarse-to-fine batch whose clouds and FPFH rows are resident already: the lane borrows both sides and builds no grid and no feature
+struct C2fCached { float4* src_pts; float* src_rows; float4* dst_pts; float* dst_rows; };
+// qn_coarse_to_fine_align_batch on one context (qn_quatro_host.inc) that also says how far each pair got (stage 0, 1 = T_quatro solved, 2 = the fine stage
+// ran); cached (or null): per pair, the resident points and rows its lane borrows
+int qn_ctx_int_c2f_batch_stage(qn_ctx* ctx, const qn_pair_desc* pairs, uint32_t n_pairs, double score_thr, qn_gicp_result* results, double* T_total, double* T_quatro,
+                               int* valid, int* status, const C2fCached* cached, int* stage);
+// The one pair driver behind every loop-verification entry point (qn_verify.hip).  A job = one pair whose clouds exist: src / dst (device float4, nullptr when
+// empty), query / cand for the record, group = the query's place among the call's distinct queries, pre = QN_OK "give it to the batch" or the status the pair
+// reports without running, guess = the f32 seed of the GICP form, src_rows / dst_rows = the resident FPFH rows of the coarse-to-fine form (nullptr: the lanes
+// make their own; when any job of a call has rows, every job's are lent).  qn_kf_int_verify_run fills every output with what a registration that did not run
+// reports, submits the QN_OK jobs stable-sorted by group (caller order within a query) to ONE qn_gicp_align_batch_guess or ONE coarse-to-fine batch, scatters
+// the records back to caller order and replaces the store's verify record with one of `kind` (QN_KF_VERIFY_KEEP: the store's record is left alone).
+// T_total (coarse-to-fine: required) / T_quatro may be nullptr.  When the batched run itself fails, nothing has been written and the record is not replaced.
+#define QN_KF_VERIFY_KEEP (-1)
+struct qn_kf_int_verify_job {
+  const float4* src; uint32_t ns; const float4* dst; uint32_t nt; int32_t query, cand; uint32_t group; int pre;
+  float guess[16]; float* src_rows; float* dst_rows;
+};
+int qn_kf_int_verify_run(qn_kf_store* s, qn_ctx* ctx, const qn_kf_int_verify_job* jobs, uint32_t n, double score_thr, bool c2f, int kind,
+                         qn_gicp_result* results, double* T_total, double* T_quatro, int* valid, int* status);
+// the distinct ids of ids[0 .. n) in order of first appearance (appended to u) and each entry's place in that list
+inline void qn_kf_int_distinct(const int32_t* ids, uint32_t n, std::vector<int32_t>& u, std::vector<uint32_t>& place) {
+  place.resize(n);
+  for (uint32_t j = 0; j < n; j++) {
+    uint32_t k = 0;
+    while (k < u.size() && u[k] != ids[j]) k++;
+    if (k == u.size()) u.push_back(ids[j]);
+    place[j] = k;
+  }
+}
+// the window lists of `count` centres, appended to ids / rel / seg (seg gets one end offset per centre): window of c = keyframes c - range .. c + range
+// inside the poses, keyframe i with inv(P_c) P_i (qn_kf_int_relative_pose).  keep_newest = false is the reference's `i < keyframes.size() - 1`
+// (loop_closure.cpp:98-104), true the local submap's `i < n_poses`.  QN_ERR_INVALID_ARG for a window member that is no keyframe (i >= n_kf).
+int qn_kf_int_windows(const int32_t* centres, uint32_t count, const double* poses, uint32_t n_poses, size_t n_kf, uint32_t range, bool keep_newest,
+                      std::vector<int32_t>& ids, std::vector<double>& rel, std::vector<uint32_t>& seg);
 // the pose and seed arithmetic qn_kf_verify_loop_candidates documents (include/qn_engine.h): Q = inv(Pc) Pi with inv(P) = [R^T | -R^T t], every entry summed
 // in order in f64; g = Rz(-yaw) from the C library's cos / sin in f64, each entry rounded to f32.  Twins: scancontext.relative_pose / seed_from_yaw.
 void qn_kf_int_relative_pose(const double* Pc, const double* Pi, double* Q);

@@ -192,122 +192,78 @@ extern "C" int qn_kf_quatro_describe(qn_kf_store* s, qn_ctx* ctx, const int32_t*
   return QN_OK;
 }
 
-static const KfqEntry* kfq_entry(const qn_kf_store* s, int32_t id) {
-  const KfqState* st = (const KfqState*)qn_kf_int_ext(s, QN_KF_INT_EXT_QUATRO);
+// the entry of keyframe `id` in a unit's per-store state (KfqState here, KfsState in qn_kf_submap.inc), nullptr until it is described
+template <class State>
+static auto kf_entry(const qn_kf_store* s, int slot, int32_t id) -> const typename decltype(State::e)::value_type* {
+  const State* st = (const State*)qn_kf_int_ext(s, slot);
   if (!st || id < 0 || (size_t)id >= st->e.size() || !st->e[id].described) return nullptr;
   return &st->e[id];
 }
+typedef const KfqEntry* (*KfqLookup)(const qn_kf_store* s, int32_t id);            // how a call finds its entries: scan entries, local submaps, local submaps with rows
+static const KfqEntry* kfq_entry(const qn_kf_store* s, int32_t id) { return kf_entry<KfqState>(s, QN_KF_INT_EXT_QUATRO, id); }
 
-extern "C" int qn_kf_quatro_cloud(qn_kf_store* s, int32_t id, const float** d_xyz, uint32_t* n) {
+// what a coarse-to-fine call on ctx may borrow: an entry described with the context's current Quatro radii and grid capacity (the rows are what its lanes would make)
+static bool kfq_usable(const KfqEntry* e, const qn_ctx* ctx) {
+  qn_quatro_params qp;
+  if (ctx->qparams_set) qp = ctx->qparams; else qn_quatro_default_params(&qp);
+  return e && e->rn == qp.fpfh_normal_radius && e->rf == qp.fpfh_radius && e->max_cells == ctx->max_cells;
+}
+
+// the read-backs of an entry: its cloud (qn_kf_quatro_cloud, qn_kf_submap_cloud) and its FPFH rows (qn_kf_quatro_features, qn_kf_submap_features)
+static int kfq_cloud(qn_kf_store* s, int32_t id, KfqLookup entry, const float** d_xyz, uint32_t* n) {
   if (!s || !d_xyz || !n || id < 0 || (size_t)id >= qn_kf_int_count(s)) return QN_ERR_INVALID_ARG;
   *d_xyz = nullptr; *n = 0;
-  const KfqEntry* e = kfq_entry(s, id);
+  const KfqEntry* e = entry(s, id);
   if (!e) return QN_ERR_NOT_READY;
   *d_xyz = (const float*)e->pts; *n = e->n;
   return QN_OK;
 }
-
-extern "C" int qn_kf_quatro_features(qn_kf_store* s, int32_t id, float* fpfh33_out) {
+static int kfq_features(qn_kf_store* s, int32_t id, KfqLookup entry, float* fpfh33_out, const char* failed) {
   if (!s || id < 0 || (size_t)id >= qn_kf_int_count(s)) return QN_ERR_INVALID_ARG;
-  const KfqEntry* e = kfq_entry(s, id);
+  const KfqEntry* e = entry(s, id);
   if (!e) return QN_ERR_NOT_READY;
   if (!e->n) return QN_OK;
   if (!fpfh33_out) return QN_ERR_INVALID_ARG;
   if (hipSetDevice(qn_kf_int_device(s)) != hipSuccess ||
       hipMemcpy2D(fpfh33_out, 33 * sizeof(float), e->rows, QN_FROW * sizeof(float), 33 * sizeof(float), e->n, hipMemcpyDeviceToHost) != hipSuccess) {
-    qn_kf_int_set_error(s, "qn_kf_quatro_features: read-back failed"); return QN_ERR_HIP;
+    qn_kf_int_set_error(s, failed); return QN_ERR_HIP;
   }
   return QN_OK;
 }
 
-extern "C" int qn_kf_verify_loop_candidates_c2f(qn_kf_store* s, qn_ctx* ctx, int32_t query, const int32_t* cand, uint32_t n_cand, double score_thr,
-                                                qn_gicp_result* results, double* T_total, double* T_quatro, int* valid, int* status) {
-  // ---- every argument before anything runs: the store's entries and the context stay as they were
-  if (!s || !ctx || !cand || n_cand == 0 || !results || !T_total || !valid || !status) return QN_ERR_INVALID_ARG;
-  if (qn_kf_int_device(s) != ctx->device) return QN_ERR_INVALID_ARG;
-  qn_quatro_params qp;
-  if (ctx->qparams_set) qp = ctx->qparams; else qn_quatro_default_params(&qp);
-  auto usable = [&](int32_t id) -> const KfqEntry* {      // described, with the context's current radii and grid capacity (the rows are what its lanes would make)
-    if (id < 0 || (size_t)id >= qn_kf_int_count(s)) return nullptr;
-    const KfqEntry* e = kfq_entry(s, id);
-    if (!e || e->rn != qp.fpfh_normal_radius || e->rf != qp.fpfh_radius || e->max_cells != ctx->max_cells) return nullptr;
-    return e;
-  };
-  const KfqEntry* q = usable(query);
-  if (!q) return QN_ERR_INVALID_ARG;
-  std::vector<qn_pair_desc> pairs(n_cand); std::vector<C2fCached> cached(n_cand);
-  for (uint32_t j = 0; j < n_cand; j++) {
-    if (cand[j] == query) return QN_ERR_INVALID_ARG;
-    for (uint32_t i = 0; i < j; i++) if (cand[i] == cand[j]) return QN_ERR_INVALID_ARG;
-    const KfqEntry* e = usable(cand[j]);
-    if (!e) return QN_ERR_INVALID_ARG;
-    pairs[j] = qn_pair_desc{(const float*)q->pts, q->n, (const float*)e->pts, e->n, 16u, 1};
-    cached[j] = C2fCached{q->pts, q->rows, e->pts, e->rows};
-  }
-  qn_ctx* const one[1] = {ctx};
-  return c2f_batch(one, 1, pairs.data(), n_cand, score_thr, results, T_total, T_quatro, valid, status, cached.data());
+extern "C" int qn_kf_quatro_cloud(qn_kf_store* s, int32_t id, const float** d_xyz, uint32_t* n) { return kfq_cloud(s, id, kfq_entry, d_xyz, n); }
+extern "C" int qn_kf_quatro_features(qn_kf_store* s, int32_t id, float* fpfh33_out) {
+  return kfq_features(s, id, kfq_entry, fpfh33_out, "qn_kf_quatro_features: read-back failed");
 }
 
-// the pairs of a multi-pair coarse-to-fine call on resident entries: `usable(id)` = the entry of keyframe id when the call may use it (described, rows made with
-// the context's radii and grid capacity), else nullptr; kind = the verify record the call leaves (qn_kf_internal.h).  Every argument is checked before anything
-// runs; then the pairs grouped by query (stable), ONE c2f_batch, records back in caller order.  qn_kf_verify_loop_pairs_c2f (scan entries) and
-// qn_kf_verify_loop_pairs_submap_c2f (local submaps, qn_kf_submap.inc) are this with their own entries.
-template <class Usable>
-static int kfq_pairs_c2f(qn_kf_store* s, qn_ctx* ctx, const Usable& usable, int kind, const int32_t* query, const int32_t* cand, uint32_t n_pairs, double score_thr,
+// a coarse-to-fine call on resident entries (`entry` finds them; kind = the verify record the call leaves, qn_kf_internal.h).  Every argument is checked before
+// anything runs: the store's entries, its verify record and the context stay as they were.  Then every pair goes to the pair driver (qn_kf_int_verify_run), the
+// lanes borrowing both sides' points and rows; an empty side is the batch's to report.  qn_kf_verify_loop_pairs_c2f (scan entries),
+// qn_kf_verify_loop_candidates_c2f (the same with the query repeated, no record) and qn_kf_verify_loop_pairs_submap_c2f (local submaps, qn_kf_submap.inc) are this.
+static int kfq_pairs_c2f(qn_kf_store* s, qn_ctx* ctx, KfqLookup entry, int kind, const int32_t* query, const int32_t* cand, uint32_t n_pairs, double score_thr,
                          qn_gicp_result* results, double* T_total, double* T_quatro, int* valid, int* status) {
   if (!s || !ctx || !query || !cand || n_pairs == 0 || !results || !T_total || !valid || !status) return QN_ERR_INVALID_ARG;
   if (qn_kf_int_device(s) != ctx->device) return QN_ERR_INVALID_ARG;
-  std::vector<int32_t> uq; std::vector<uint32_t> qi(n_pairs);                    // distinct queries in order of first appearance; pair j -> its place
+  std::vector<qn_kf_int_verify_job> jobs(n_pairs);
   for (uint32_t j = 0; j < n_pairs; j++) {
-    if (cand[j] == query[j] || !usable(query[j]) || !usable(cand[j])) return QN_ERR_INVALID_ARG;
+    const KfqEntry* q = entry(s, query[j]); const KfqEntry* e = entry(s, cand[j]);
+    if (cand[j] == query[j] || !kfq_usable(q, ctx) || !kfq_usable(e, ctx)) return QN_ERR_INVALID_ARG;
     for (uint32_t i = 0; i < j; i++) if (query[i] == query[j] && cand[i] == cand[j]) return QN_ERR_INVALID_ARG;
-    uint32_t k = 0;
-    while (k < uq.size() && uq[k] != query[j]) k++;
-    if (k == uq.size()) uq.push_back(query[j]);
-    qi[j] = k;
+    jobs[j] = qn_kf_int_verify_job{q->pts, q->n, e->pts, e->n, query[j], cand[j], 0, QN_OK, {}, q->rows, e->rows};
   }
-  // ---- the pairs grouped by query (stable), so that the candidates of one query run in consecutive lanes and share the source side; one c2f_batch for all
-  std::vector<uint32_t> order(n_pairs);
-  for (uint32_t j = 0; j < n_pairs; j++) order[j] = j;
-  std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return qi[a] < qi[b]; });
-  std::vector<qn_pair_desc> pairs(n_pairs); std::vector<C2fCached> cached(n_pairs);
-  for (uint32_t k = 0; k < n_pairs; k++) {
-    const KfqEntry* q = usable(query[order[k]]); const KfqEntry* e = usable(cand[order[k]]);
-    pairs[k] = qn_pair_desc{(const float*)q->pts, q->n, (const float*)e->pts, e->n, 16u, 1};
-    cached[k] = C2fCached{q->pts, q->rows, e->pts, e->rows};
-  }
-  std::vector<qn_gicp_result> res(n_pairs); std::vector<double> Tt(16 * (size_t)n_pairs), Tq(16 * (size_t)n_pairs);
-  std::vector<int> val(n_pairs, 0), st(n_pairs, QN_OK), stage(n_pairs, 0);
-  qn_ctx* const one[1] = {ctx};
-  const int rc = c2f_batch(one, 1, pairs.data(), n_pairs, score_thr, res.data(), Tt.data(), Tq.data(), val.data(), st.data(), cached.data(), stage.data());
-  if (rc != QN_OK) return rc;
-  // ---- back into caller order, and the verify record qn_kf_verify_cloud serves
-  std::vector<qn_kf_int_verify_pair> rec(n_pairs);
-  for (uint32_t k = 0; k < n_pairs; k++) {
-    const uint32_t j = order[k];
-    results[j] = res[k]; valid[j] = val[k]; status[j] = st[k];
-    memcpy(T_total + 16 * (size_t)j, Tt.data() + 16 * (size_t)k, 16 * sizeof(double));
-    if (T_quatro) memcpy(T_quatro + 16 * (size_t)j, Tq.data() + 16 * (size_t)k, 16 * sizeof(double));
-    qn_kf_int_verify_pair& r = rec[j];
-    r = qn_kf_int_verify_pair{(const float4*)pairs[k].src, pairs[k].ns, (const float4*)pairs[k].dst, pairs[k].nt, query[j], cand[j],
-                              st[k] == QN_ERR_HIP ? 0 : stage[k], {}, {}};
-    memcpy(r.Tq, Tq.data() + 16 * (size_t)k, sizeof(r.Tq));
-    memcpy(r.Tg, res[k].T, sizeof(r.Tg));
-  }
-  return qn_kf_int_verify_record(s, kind, rec.data(), n_pairs);
+  std::vector<int32_t> uq; std::vector<uint32_t> qi;
+  qn_kf_int_distinct(query, n_pairs, uq, qi);
+  for (uint32_t j = 0; j < n_pairs; j++) jobs[j].group = qi[j];
+  return qn_kf_int_verify_run(s, ctx, jobs.data(), n_pairs, score_thr, true, kind, results, T_total, T_quatro, valid, status);
+}
+
+extern "C" int qn_kf_verify_loop_candidates_c2f(qn_kf_store* s, qn_ctx* ctx, int32_t query, const int32_t* cand, uint32_t n_cand, double score_thr,
+                                                qn_gicp_result* results, double* T_total, double* T_quatro, int* valid, int* status) {
+  const std::vector<int32_t> q(cand ? n_cand : 0, query);
+  return kfq_pairs_c2f(s, ctx, kfq_entry, QN_KF_VERIFY_KEEP, q.data(), cand, n_cand, score_thr, results, T_total, T_quatro, valid, status);
 }
 
 extern "C" int qn_kf_verify_loop_pairs_c2f(qn_kf_store* s, qn_ctx* ctx, const int32_t* query, const int32_t* cand, uint32_t n_pairs, double score_thr,
                                            qn_gicp_result* results, double* T_total, double* T_quatro, int* valid, int* status) {
-  // ---- every argument before anything runs, per pair as qn_kf_verify_loop_candidates_c2f: the store's entries, its verify record and the context stay as they were
-  if (!s || !ctx) return QN_ERR_INVALID_ARG;
-  qn_quatro_params qp;
-  if (ctx->qparams_set) qp = ctx->qparams; else qn_quatro_default_params(&qp);
-  auto usable = [&](int32_t id) -> const KfqEntry* {
-    if (id < 0 || (size_t)id >= qn_kf_int_count(s)) return nullptr;
-    const KfqEntry* e = kfq_entry(s, id);
-    if (!e || e->rn != qp.fpfh_normal_radius || e->rf != qp.fpfh_radius || e->max_cells != ctx->max_cells) return nullptr;
-    return e;
-  };
-  return kfq_pairs_c2f(s, ctx, usable, QN_KF_VERIFY_C2F, query, cand, n_pairs, score_thr, results, T_total, T_quatro, valid, status);
+  return kfq_pairs_c2f(s, ctx, kfq_entry, QN_KF_VERIFY_C2F, query, cand, n_pairs, score_thr, results, T_total, T_quatro, valid, status);
 }

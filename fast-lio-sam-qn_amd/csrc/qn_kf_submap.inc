@@ -1,7 +1,7 @@
 // qn_kf_submap.inc - a keyframe's local submap, in that keyframe's own frame, built once and kept resident (qn_kf_submap_describe), and the drift-free
 // submap-to-submap verification of loop candidates that borrows it on both sides (qn_kf_verify_loop_pairs_submap, and coarse to fine from resident FPFH rows
-// qn_kf_verify_loop_pairs_submap_c2f).  Included by qn_engine.hip behind qn_kf_quatro.inc, whose describe machinery (kfq_rows) and pair driver (kfq_pairs_c2f)
-// it shares.
+// qn_kf_verify_loop_pairs_submap_c2f).  Included by qn_engine.hip behind qn_kf_quatro.inc, whose describe machinery (kfq_rows), read-backs and coarse-to-fine
+// pair call (kfq_pairs_c2f) it shares.
 //
 // The reference's third mode (config.yaml: enable_submap_matching true; loop_closure.cpp:70-84, 98-107) registers the submap around the query against the
 // submap around the candidate, both placed with the corrected poses - the whole trajectory's drift.  Here the submap around keyframe c is
@@ -20,11 +20,9 @@ namespace {
 struct KfsEntry : KfqEntry { uint32_t range = 0; bool has_rows = false; };
 struct KfsState { std::vector<KfsEntry> e; };
 
-const KfsEntry* kfs_entry(const qn_kf_store* s, int32_t id) {
-  const KfsState* st = (const KfsState*)qn_kf_int_ext(s, QN_KF_INT_EXT_SUBMAP);
-  if (!st || id < 0 || (size_t)id >= st->e.size() || !st->e[id].described) return nullptr;
-  return &st->e[id];
-}
+const KfsEntry* kfs_entry(const qn_kf_store* s, int32_t id) { return kf_entry<KfsState>(s, QN_KF_INT_EXT_SUBMAP, id); }
+const KfqEntry* kfs_cloud_entry(const qn_kf_store* s, int32_t id) { return kfs_entry(s, id); }
+const KfqEntry* kfs_rows_entry(const qn_kf_store* s, int32_t id) { const KfsEntry* e = kfs_entry(s, id); return e && e->has_rows ? e : nullptr; }
 
 }  // namespace
 
@@ -37,18 +35,8 @@ extern "C" int qn_kf_submap_describe(qn_kf_store* s, qn_ctx* ctx, const int32_t*
   for (uint32_t i = 0; i < count; i++) if (ids[i] < 0 || (size_t)ids[i] >= n_kf || (uint32_t)ids[i] >= n_poses) return QN_ERR_INVALID_ARG;
   for (size_t i = 0; i < (size_t)n_poses * 16; i++) if (!std::isfinite(poses[i])) return QN_ERR_INVALID_ARG;
   // ---- the lists: window t = local_submap_ids(ids[t], submap_range, n_poses), keyframe i with inv(P_c) P_i
-  std::vector<int32_t> wid; std::vector<double> rel; std::vector<uint32_t> seg(count + 1, 0);
-  for (uint32_t t = 0; t < count; t++) {
-    const long long c = ids[t];
-    for (long long i = c - (long long)submap_range; i <= c + (long long)submap_range; i++) {
-      if (i < 0 || i >= (long long)n_poses) continue;
-      if ((size_t)i >= n_kf) return QN_ERR_INVALID_ARG;                             // (a pose without a keyframe inside a window)
-      double Q[16];
-      qn_kf_int_relative_pose(poses + 16 * (size_t)c, poses + 16 * (size_t)i, Q);
-      wid.push_back((int32_t)i); rel.insert(rel.end(), Q, Q + 16);
-    }
-    seg[t + 1] = (uint32_t)wid.size();
-  }
+  std::vector<int32_t> wid; std::vector<double> rel; std::vector<uint32_t> seg(1, 0);
+  if (qn_kf_int_windows(ids, count, poses, n_poses, n_kf, submap_range, true, wid, rel, seg) != QN_OK) return QN_ERR_INVALID_ARG;
   HIPCHK(ctx, hipSetDevice(ctx->device));
   qn_ctx* c = ctx;
   if (!c->qparams_set) { qn_quatro_default_params(&c->qparams); c->qparams_set = true; }
@@ -85,26 +73,9 @@ extern "C" int qn_kf_submap_describe(qn_kf_store* s, qn_ctx* ctx, const int32_t*
   return QN_OK;
 }
 
-extern "C" int qn_kf_submap_cloud(qn_kf_store* s, int32_t id, const float** d_xyz, uint32_t* n) {
-  if (!s || !d_xyz || !n || id < 0 || (size_t)id >= qn_kf_int_count(s)) return QN_ERR_INVALID_ARG;
-  *d_xyz = nullptr; *n = 0;
-  const KfsEntry* e = kfs_entry(s, id);
-  if (!e) return QN_ERR_NOT_READY;
-  *d_xyz = (const float*)e->pts; *n = e->n;
-  return QN_OK;
-}
-
+extern "C" int qn_kf_submap_cloud(qn_kf_store* s, int32_t id, const float** d_xyz, uint32_t* n) { return kfq_cloud(s, id, kfs_cloud_entry, d_xyz, n); }
 extern "C" int qn_kf_submap_features(qn_kf_store* s, int32_t id, float* fpfh33_out) {
-  if (!s || id < 0 || (size_t)id >= qn_kf_int_count(s)) return QN_ERR_INVALID_ARG;
-  const KfsEntry* e = kfs_entry(s, id);
-  if (!e || !e->has_rows) return QN_ERR_NOT_READY;
-  if (!e->n) return QN_OK;
-  if (!fpfh33_out) return QN_ERR_INVALID_ARG;
-  if (hipSetDevice(qn_kf_int_device(s)) != hipSuccess ||
-      hipMemcpy2D(fpfh33_out, 33 * sizeof(float), e->rows, QN_FROW * sizeof(float), 33 * sizeof(float), e->n, hipMemcpyDeviceToHost) != hipSuccess) {
-    qn_kf_int_set_error(s, "qn_kf_submap_features: read-back failed"); return QN_ERR_HIP;
-  }
-  return QN_OK;
+  return kfq_features(s, id, kfs_rows_entry, fpfh33_out, "qn_kf_submap_features: read-back failed");
 }
 
 extern "C" int qn_kf_submap_release(qn_kf_store* s, const int32_t* ids, uint32_t count) {
@@ -125,65 +96,23 @@ extern "C" int qn_kf_verify_loop_pairs_submap(qn_kf_store* s, qn_ctx* ctx, const
   // ---- every argument before anything runs: the entries, the verify record and the context stay as they were
   if (!s || !ctx || !query || !cand || n_pairs == 0 || !results || !valid || !status) return QN_ERR_INVALID_ARG;
   if (qn_kf_int_device(s) != ctx->device) return QN_ERR_INVALID_ARG;
-  const size_t n_kf = qn_kf_int_count(s);
-  auto usable = [&](int32_t id) -> const KfsEntry* { return id < 0 || (size_t)id >= n_kf ? nullptr : kfs_entry(s, id); };
-  std::vector<int32_t> uq; std::vector<uint32_t> qi(n_pairs);                    // distinct queries in order of first appearance; pair j -> its place
+  std::vector<qn_kf_int_verify_job> jobs(n_pairs);
   for (uint32_t j = 0; j < n_pairs; j++) {
-    if (cand[j] == query[j] || !usable(query[j]) || !usable(cand[j])) return QN_ERR_INVALID_ARG;
+    const KfsEntry* q = kfs_entry(s, query[j]); const KfsEntry* e = kfs_entry(s, cand[j]);
+    if (cand[j] == query[j] || !q || !e) return QN_ERR_INVALID_ARG;
     for (uint32_t i = 0; i < j; i++) if (query[i] == query[j] && cand[i] == cand[j]) return QN_ERR_INVALID_ARG;
     if (yaw && !std::isfinite(yaw[j])) return QN_ERR_INVALID_ARG;
-    uint32_t k = 0;
-    while (k < uq.size() && uq[k] != query[j]) k++;
-    if (k == uq.size()) uq.push_back(query[j]);
-    qi[j] = k;
+    jobs[j] = qn_kf_int_verify_job{q->pts, q->n, e->pts, e->n, query[j], cand[j], 0, q->n == 0 || e->n == 0 ? QN_ERR_EMPTY_CLOUD : QN_OK, {}, nullptr, nullptr};
+    qn_kf_int_seed_from_yaw(yaw ? yaw[j] : 0.0, jobs[j].guess);
   }
-  // ---- one batched registration: the pairs whose clouds exist, grouped by query (stable) so that a query's pairs share the source's preparation
-  std::vector<uint32_t> order(n_pairs);
-  for (uint32_t j = 0; j < n_pairs; j++) order[j] = j;
-  std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return qi[a] < qi[b]; });
-  std::vector<qn_pair_desc> pairs; std::vector<float> g; std::vector<uint32_t> which;
-  std::vector<qn_kf_int_verify_pair> rec(n_pairs);
-  std::vector<qn_gicp_result> r0(n_pairs); std::vector<int> st0(n_pairs, QN_OK);
-  for (uint32_t j = 0; j < n_pairs; j++) {
-    const KfsEntry* q = usable(query[j]); const KfsEntry* e = usable(cand[j]);
-    memset(&r0[j], 0, sizeof(r0[j])); r0[j].fitness = DBL_MAX;                   // (what a registration that did not run reports: the batch's defaults)
-    for (int i = 0; i < 4; i++) { r0[j].T[5 * i] = 1.f; r0[j].T64[5 * i] = 1.0; }
-    st0[j] = q->n == 0 || e->n == 0 ? QN_ERR_EMPTY_CLOUD : QN_OK;
-    rec[j] = qn_kf_int_verify_pair{q->pts, q->n, e->pts, e->n, query[j], cand[j], 0, {}, {}};
-  }
-  for (uint32_t j : order) {
-    if (st0[j] != QN_OK) continue;
-    pairs.push_back(qn_pair_desc{(const float*)rec[j].src, rec[j].ns, (const float*)rec[j].dst, rec[j].nt, 16, 1});
-    float gj[16];
-    qn_kf_int_seed_from_yaw(yaw ? yaw[j] : 0.0, gj);
-    g.insert(g.end(), gj, gj + 16);
-    which.push_back(j);
-  }
-  const uint32_t m = (uint32_t)pairs.size();
-  std::vector<qn_gicp_result> res(m); std::vector<int> val(m, 0), st(m, QN_OK);
-  if (m) {
-    const int rc = qn_gicp_align_batch_guess(ctx, pairs.data(), g.data(), m, score_thr, res.data(), val.data(), st.data());
-    if (rc != QN_OK) return rc;                                                    // (nothing written: the caller's arrays and the record are the previous call's)
-  }
-  for (uint32_t j = 0; j < n_pairs; j++) { results[j] = r0[j]; valid[j] = 0; status[j] = st0[j]; }
-  for (uint32_t k = 0; k < m; k++) {
-    const uint32_t j = which[k];
-    results[j] = res[k]; valid[j] = val[k]; status[j] = st[k];
-    if (st[k] == QN_OK) { rec[j].stage = 2; memcpy(rec[j].Tg, res[k].T, sizeof(rec[j].Tg)); }
-  }
-  return qn_kf_int_verify_record(s, QN_KF_VERIFY_SUBMAP, rec.data(), n_pairs);
+  // ---- the pairs whose clouds exist through the pair driver: one batched registration, grouped by query
+  std::vector<int32_t> uq; std::vector<uint32_t> qi;
+  qn_kf_int_distinct(query, n_pairs, uq, qi);
+  for (uint32_t j = 0; j < n_pairs; j++) jobs[j].group = qi[j];
+  return qn_kf_int_verify_run(s, ctx, jobs.data(), n_pairs, score_thr, false, QN_KF_VERIFY_SUBMAP, results, nullptr, nullptr, valid, status);
 }
 
 extern "C" int qn_kf_verify_loop_pairs_submap_c2f(qn_kf_store* s, qn_ctx* ctx, const int32_t* query, const int32_t* cand, uint32_t n_pairs, double score_thr,
                                                   qn_gicp_result* results, double* T_total, double* T_quatro, int* valid, int* status) {
-  if (!s || !ctx) return QN_ERR_INVALID_ARG;
-  qn_quatro_params qp;
-  if (ctx->qparams_set) qp = ctx->qparams; else qn_quatro_default_params(&qp);
-  auto usable = [&](int32_t id) -> const KfqEntry* {      // described with rows, under the context's current radii and grid capacity
-    if (id < 0 || (size_t)id >= qn_kf_int_count(s)) return nullptr;
-    const KfsEntry* e = kfs_entry(s, id);
-    if (!e || !e->has_rows || e->rn != qp.fpfh_normal_radius || e->rf != qp.fpfh_radius || e->max_cells != ctx->max_cells) return nullptr;
-    return e;
-  };
-  return kfq_pairs_c2f(s, ctx, usable, QN_KF_VERIFY_SUBMAP_C2F, query, cand, n_pairs, score_thr, results, T_total, T_quatro, valid, status);
+  return kfq_pairs_c2f(s, ctx, kfs_rows_entry, QN_KF_VERIFY_SUBMAP_C2F, query, cand, n_pairs, score_thr, results, T_total, T_quatro, valid, status);
 }

@@ -12,7 +12,7 @@
 //               k_ml_compact  a block with any[block] == 0 returns before it loads a record; else the count kernel's tests again, a member of centre c going to
 //                             base[c] + cnt[c][block] + the members of the waves before + its ballot rank: ascending map index, no atomics, the same bytes on every run
 //   localise  host sequencing: the distinct crop centres (f32 bits of the guesses' translations) cropped once, each distinct query voxel-filtered alone in its
-//             sensor frame (qn_kf_int_voxel_each), the pairs grouped by query (stable) into ONE batched registration, the records scattered back to caller order
+//             sensor frame (qn_kf_int_voxel_each), then the pair driver of qn_verify.hip (qn_kf_int_verify_run): ONE batched registration, records in caller order
 // (the scheme is qn_map_compact.cuh's, generalised from one predicate to QN_ML_PASS per pass: its scan kernel, its lane_rank, its block sizes)
 #define QN_ML_PASS 64
 #define QN_ML_MAX_CROPS 32767u
@@ -20,9 +20,6 @@
 #define ML_WAVES MO_WAVES
 
 int qn_ctx_int_max_points(const qn_ctx* c);
-// qn_coarse_to_fine_align_batch on one context (qn_quatro_host.inc) that also says how far each pair got: stage 0, 1 = T_quatro solved, 2 = the fine stage ran
-int qn_ctx_int_c2f_batch_stage(qn_ctx* ctx, const qn_pair_desc* pairs, uint32_t n_pairs, double score_thr, qn_gicp_result* results, double* T_total, double* T_quatro,
-                               int* valid, int* status, int* stage);
 
 namespace {
 
@@ -187,14 +184,12 @@ int ml_localize(qn_kf_store* s, qn_ctx* ctx, const qn_localize_params* params, c
   MlState* m = ml_state(s, &rc);
   if (!m) return rc;
   // ---- the distinct queries and the distinct centres (the f32 bits of the guess's translation), in order of first appearance
-  std::vector<int32_t> uq; std::vector<float> uc; std::vector<uint32_t> qi(n_pairs), ci(n_pairs);
+  std::vector<int32_t> uq; std::vector<float> uc; std::vector<uint32_t> qi, ci(n_pairs);
+  qn_kf_int_distinct(query, n_pairs, uq, qi);
   for (uint32_t j = 0; j < n_pairs; j++) {
-    uint32_t k = 0;
-    while (k < uq.size() && uq[k] != query[j]) k++;
-    if (k == uq.size()) uq.push_back(query[j]);
-    qi[j] = k;
     const float t[3] = {g[16 * (size_t)j + 3], g[16 * (size_t)j + 7], g[16 * (size_t)j + 11]};
-    for (k = 0; 3 * (size_t)k < uc.size() && memcmp(&uc[3 * (size_t)k], t, sizeof(t)) != 0; k++) {}
+    uint32_t k = 0;
+    while (3 * (size_t)k < uc.size() && memcmp(&uc[3 * (size_t)k], t, sizeof(t)) != 0) k++;
     if (3 * (size_t)k == uc.size()) uc.insert(uc.end(), t, t + 3);
     ci[j] = k;
   }
@@ -204,50 +199,19 @@ int ml_localize(qn_kf_store* s, qn_ctx* ctx, const qn_localize_params* params, c
   if ((rc = ml_crop(s, *m, uc.data(), ncr, params->radius, params->shape, cn.data())) != QN_OK) return rc;
   std::vector<const float4*> vp(nq, nullptr); std::vector<uint32_t> vn(nq, 0); std::vector<int> vs(nq, QN_ERR_EMPTY_CLOUD);
   if ((rc = qn_kf_int_voxel_each(s, uq.data(), nq, params->leaf, m->scans, vp.data(), vn.data(), vs.data())) != QN_OK) return rc;
-  // ---- one batched registration: the pairs whose clouds exist and fit, grouped by query (stable) so that a query's pairs share the source's preparation
+  // ---- the pairs whose clouds exist and fit through the driver: one batched registration, cand = -1 in the record
   const uint32_t cap = (uint32_t)qn_ctx_int_max_points(ctx);
-  const double eye[16] = {1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0};
-  std::vector<qn_kf_int_verify_pair> rec(n_pairs);
+  std::vector<qn_kf_int_verify_job> jobs(n_pairs);
   for (uint32_t j = 0; j < n_pairs; j++) {
-    unset_record(&results[j]); valid[j] = 0;
-    if (T_total) memcpy(T_total + 16 * (size_t)j, eye, sizeof(eye));
-    if (T_quatro) memcpy(T_quatro + 16 * (size_t)j, eye, sizeof(eye));
     const uint32_t ns = vs[qi[j]] == QN_OK ? vn[qi[j]] : 0, nt = cn[ci[j]];
-    status[j] = vs[qi[j]] != QN_OK ? vs[qi[j]] : (ns == 0 || nt == 0) ? QN_ERR_EMPTY_CLOUD : (ns > cap || nt > cap) ? QN_ERR_CAPACITY : QN_OK;
-    rec[j] = qn_kf_int_verify_pair{ns ? vp[qi[j]] : nullptr, ns, nt ? m->pts.p + m->base[ci[j]] : nullptr, nt, query[j], -1, 0, {}, {}};
+    const int pre = vs[qi[j]] != QN_OK ? vs[qi[j]] : (ns == 0 || nt == 0) ? QN_ERR_EMPTY_CLOUD : (ns > cap || nt > cap) ? QN_ERR_CAPACITY : QN_OK;
+    jobs[j] = qn_kf_int_verify_job{ns ? vp[qi[j]] : nullptr, ns, nt ? m->pts.p + m->base[ci[j]] : nullptr, nt, query[j], -1, qi[j], pre, {}, nullptr, nullptr};
+    memcpy(jobs[j].guess, g.data() + 16 * (size_t)j, sizeof(jobs[j].guess));
   }
-  std::vector<uint32_t> order(n_pairs);
-  for (uint32_t j = 0; j < n_pairs; j++) order[j] = j;
-  std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return qi[a] < qi[b]; });
-  std::vector<qn_pair_desc> pairs; std::vector<float> gg; std::vector<uint32_t> which;
-  for (uint32_t j : order) {
-    if (status[j] != QN_OK) continue;
-    pairs.push_back(qn_pair_desc{(const float*)rec[j].src, rec[j].ns, (const float*)rec[j].dst, rec[j].nt, 16, 1});
-    gg.insert(gg.end(), g.begin() + 16 * (size_t)j, g.begin() + 16 * (size_t)j + 16);
-    which.push_back(j);
-  }
-  if (!pairs.empty()) {
-    const uint32_t k = (uint32_t)pairs.size();
-    std::vector<qn_gicp_result> res(k); std::vector<int> val(k, 0), st(k, QN_OK), stage(k, 0);
-    std::vector<double> Tt(16 * (size_t)k), Tq(16 * (size_t)k);
-    if (c2f) rc = qn_ctx_int_c2f_batch_stage(ctx, pairs.data(), k, params->score_thr, res.data(), Tt.data(), Tq.data(), val.data(), st.data(), stage.data());
-    else rc = qn_gicp_align_batch_guess(ctx, pairs.data(), gg.data(), k, params->score_thr, res.data(), val.data(), st.data());
-    if (rc != QN_OK) return rc;
-    for (uint32_t i = 0; i < k; i++) {
-      const uint32_t j = which[i];
-      results[j] = res[i]; valid[j] = val[i]; status[j] = st[i];
-      qn_kf_int_verify_pair& r = rec[j];
-      if (c2f) {
-        memcpy(T_total + 16 * (size_t)j, Tt.data() + 16 * (size_t)i, 16 * sizeof(double));
-        if (T_quatro) memcpy(T_quatro + 16 * (size_t)j, Tq.data() + 16 * (size_t)i, 16 * sizeof(double));
-        r.stage = st[i] == QN_ERR_HIP ? 0 : stage[i];
-        memcpy(r.Tq, Tq.data() + 16 * (size_t)i, sizeof(r.Tq));
-        memcpy(r.Tg, res[i].T, sizeof(r.Tg));
-      } else if (st[i] == QN_OK) { r.stage = 2; memcpy(r.Tg, res[i].T, sizeof(r.Tg)); }
-    }
-  }
+  rc = qn_kf_int_verify_run(s, ctx, jobs.data(), n_pairs, params->score_thr, c2f, c2f ? QN_KF_VERIFY_MAP_C2F : QN_KF_VERIFY_MAP, results, T_total, T_quatro, valid, status);
+  if (rc != QN_OK) return rc;
   if (stats_out) *stats_out = qn_localize_stats{n_map, n_pairs, nq, ncr, m->passes, 0, m->base[ncr], gen};
-  return qn_kf_int_verify_record(s, c2f ? QN_KF_VERIFY_MAP_C2F : QN_KF_VERIFY_MAP, rec.data(), n_pairs);
+  return QN_OK;
 }
 
 }  // namespace

@@ -850,8 +850,8 @@ struct C2fBorrow {
 };
 
 // a pair whose clouds and FPFH rows are resident already (qn_kf_verify_loop_candidates_c2f: the store's described keyframes): the lane borrows both sides - points and
-// descriptor rows, which is all the matching reads - and builds no grid and no feature (the rows are the ones quatro_fpfh makes of the same cloud: qn_kf_quatro_describe)
-struct C2fCached { float4* src_pts; float* src_rows; float4* dst_pts; float* dst_rows; };
+// descriptor rows, which is all the matching reads - and builds no grid and no feature (the rows are the ones quatro_fpfh makes of the same cloud: qn_kf_quatro_describe).
+// C2fCached itself: qn_kf_internal.h
 struct C2fCacheBorrow {
   qn_ctx* c = nullptr; CloudBuf cloud[2]; float* fpfh[2];
   void take(qn_ctx* lane, const C2fCached& k, uint32_t ns, uint32_t nt) {
@@ -1081,9 +1081,9 @@ extern "C" int qn_coarse_to_fine_align_batch(qn_ctx* const* ctxs, uint32_t n_ctx
                                              qn_gicp_result* results, double* T_total, double* T_quatro, int* valid, int* status) {
   return c2f_batch(ctxs, n_ctx, pairs, n_pairs, score_thr, results, T_total, T_quatro, valid, status, nullptr);
 }
-// the same on one context, with each pair's stage (for another translation unit: qn_maplocalize.inc)
+// the same on one context, with each pair's stage and, when the clouds are resident, their rows (for another translation unit: the pair driver of qn_verify.hip)
 int qn_ctx_int_c2f_batch_stage(qn_ctx* ctx, const qn_pair_desc* pairs, uint32_t n_pairs, double score_thr, qn_gicp_result* results, double* T_total, double* T_quatro,
-                               int* valid, int* status, int* stage) {
+                               int* valid, int* status, const C2fCached* cached, int* stage) {
   qn_ctx* const one[1] = {ctx};
-  return c2f_batch(one, 1, pairs, n_pairs, score_thr, results, T_total, T_quatro, valid, status, nullptr, stage);
+  return c2f_batch(one, 1, pairs, n_pairs, score_thr, results, T_total, T_quatro, valid, status, cached, stage);
 }

@@ -7,7 +7,10 @@
 // Host code only: the clouds are assembled by qn_kf_assemble_batch and registered by qn_gicp_align_batch_guess, both on the device.
 // The numpy twins (qn_amd/scancontext.py: relative_pose, seed_from_yaw) restate the poses and guesses bit for bit; the build's
 // -ffp-contract=off keeps every product a rounded multiply and a rounded add.
-// qn_kf_verify_loop_pairs runs the same step for many queries at once (one assembly, one registration), and qn_kf_verify_cloud serves the debug clouds
+// qn_kf_verify_loop_pairs runs the same step for many queries at once (one assembly, one registration; the single-query call is that with the query repeated).
+// Every verification entry point of the store - these two, the resident coarse-to-fine and submap forms (qn_kf_quatro.inc, qn_kf_submap.inc) and the map
+// localisation (qn_maplocalize.inc) - hands its pairs to ONE driver here, qn_kf_int_verify_run: defaults, grouping by query, one batched registration, the
+// records back in caller order, the verify record.  qn_kf_verify_cloud serves the debug clouds
 // loopTimerFunc publishes after each attempt (fast_lio_sam_qn.cpp:245-248) for any pair of the latest multi-pair call, GICP or coarse-to-fine.
 #include <hip/hip_runtime.h>
 #include <cfloat>
@@ -51,6 +54,24 @@ void seed_from_yaw(double yaw, float* g) {
 }  // namespace
 void qn_kf_int_relative_pose(const double* Pc, const double* Pi, double* Q) { relative_pose(Pc, Pi, Q); }
 void qn_kf_int_seed_from_yaw(double yaw, float* g) { seed_from_yaw(yaw, g); }
+// ids / rel / seg of `count` candidate windows (qn_kf_internal.h)
+int qn_kf_int_windows(const int32_t* centres, uint32_t count, const double* poses, uint32_t n_poses, size_t n_kf, uint32_t range, bool keep_newest,
+                      std::vector<int32_t>& ids, std::vector<double>& rel, std::vector<uint32_t>& seg) {
+  const long long end = (long long)n_poses - (keep_newest ? 0 : 1);
+  for (uint32_t t = 0; t < count; t++) {
+    const long long c = centres[t];
+    for (long long i = c - (long long)range; i <= c + (long long)range; i++) {
+      if (i < 0 || i >= end) continue;
+      if ((size_t)i >= n_kf) return QN_ERR_INVALID_ARG;                             // (a pose without a keyframe inside a window)
+      double Q[16];
+      relative_pose(poses + 16 * (size_t)c, poses + 16 * (size_t)i, Q);
+      ids.push_back((int32_t)i); rel.insert(rel.end(), Q, Q + 16);
+    }
+    seg.push_back((uint32_t)ids.size());
+  }
+  return QN_OK;
+}
+
 namespace {
 
 void unset_record(qn_gicp_result* r) {       // what a registration that did not run reports (the batch's defaults)
@@ -60,68 +81,117 @@ void unset_record(qn_gicp_result* r) {       // what a registration that did not
 
 }  // namespace
 
-extern "C" int qn_kf_verify_loop_candidates(qn_kf_store* s, qn_ctx* ctx, int32_t query, const int32_t* cand, const double* yaw, uint32_t n_cand,
-                                            const double* poses, uint32_t n_poses, uint32_t submap_range, double leaf, double score_thr,
-                                            qn_gicp_result* results, int* valid, int* status) {
-  // ---- every argument before anything runs: the store's batch slot and the context stay as they were
-  if (!s || !ctx || !cand || n_cand == 0 || !poses || !results || !valid || !status || !(leaf > 0)) return QN_ERR_INVALID_ARG;
+int qn_kf_int_verify_run(qn_kf_store* s, qn_ctx* ctx, const qn_kf_int_verify_job* jobs, uint32_t n, double score_thr, bool c2f, int kind,
+                         qn_gicp_result* results, double* T_total, double* T_quatro, int* valid, int* status) {
+  // ---- one batched registration over the jobs that may run, grouped by query (stable: caller order within a query) so that the candidates of one query
+  //      sit in consecutive lanes and share the source's preparation
+  std::vector<uint32_t> order(n);
+  for (uint32_t j = 0; j < n; j++) order[j] = j;
+  std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return jobs[a].group < jobs[b].group; });
+  std::vector<qn_pair_desc> pairs; std::vector<float> g; std::vector<C2fCached> cached; std::vector<uint32_t> which;
+  bool rows = false;
+  for (uint32_t j : order) {
+    const qn_kf_int_verify_job& b = jobs[j];
+    if (b.pre != QN_OK) continue;
+    pairs.push_back(qn_pair_desc{(const float*)b.src, b.ns, (const float*)b.dst, b.nt, 16, 1});
+    g.insert(g.end(), b.guess, b.guess + 16);
+    cached.push_back(C2fCached{const_cast<float4*>(b.src), b.src_rows, const_cast<float4*>(b.dst), b.dst_rows});
+    rows = rows || b.src_rows || b.dst_rows;
+    which.push_back(j);
+  }
+  const uint32_t m = (uint32_t)pairs.size();
+  std::vector<qn_gicp_result> res(m); std::vector<int> val(m, 0), st(m, QN_OK), stage(m, 0);
+  std::vector<double> Tt(c2f ? 16 * (size_t)m : 0), Tq(c2f ? 16 * (size_t)m : 0);
+  for (uint32_t k = 0; k < m; k++) unset_record(&res[k]);
+  if (m) {
+    const int rc = c2f ? qn_ctx_int_c2f_batch_stage(ctx, pairs.data(), m, score_thr, res.data(), Tt.data(), Tq.data(), val.data(), st.data(), rows ? cached.data() : nullptr, stage.data())
+                       : qn_gicp_align_batch_guess(ctx, pairs.data(), g.data(), m, score_thr, res.data(), val.data(), st.data());
+    if (rc != QN_OK) return rc;                                                    // (nothing written: the caller's arrays and the record are the previous call's)
+  }
+  // ---- every output as a registration that did not run leaves it, then the records back in caller order, and the record qn_kf_verify_cloud serves
+  const double eye[16] = {1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0};
+  std::vector<qn_kf_int_verify_pair> rec(n);
+  for (uint32_t j = 0; j < n; j++) {
+    const qn_kf_int_verify_job& b = jobs[j];
+    unset_record(&results[j]); valid[j] = 0; status[j] = b.pre;
+    if (T_total) memcpy(T_total + 16 * (size_t)j, eye, sizeof(eye));
+    if (T_quatro) memcpy(T_quatro + 16 * (size_t)j, eye, sizeof(eye));
+    rec[j] = qn_kf_int_verify_pair{b.src, b.ns, b.dst, b.nt, b.query, b.cand, 0, {}, {}};
+  }
+  for (uint32_t k = 0; k < m; k++) {
+    const uint32_t j = which[k];
+    results[j] = res[k]; valid[j] = val[k]; status[j] = st[k];
+    qn_kf_int_verify_pair& r = rec[j];
+    if (c2f) {
+      memcpy(T_total + 16 * (size_t)j, Tt.data() + 16 * (size_t)k, 16 * sizeof(double));
+      if (T_quatro) memcpy(T_quatro + 16 * (size_t)j, Tq.data() + 16 * (size_t)k, 16 * sizeof(double));
+      r.stage = st[k] == QN_ERR_HIP ? 0 : stage[k];
+      memcpy(r.Tq, Tq.data() + 16 * (size_t)k, sizeof(r.Tq));
+      memcpy(r.Tg, res[k].T, sizeof(r.Tg));
+    } else if (st[k] == QN_OK) { r.stage = 2; memcpy(r.Tg, res[k].T, sizeof(r.Tg)); }
+  }
+  return kind == QN_KF_VERIFY_KEEP ? QN_OK : qn_kf_int_verify_record(s, kind, rec.data(), n);
+}
+
+namespace {
+
+// qn_kf_verify_loop_pairs, and with kind = QN_KF_VERIFY_KEEP and the query repeated qn_kf_verify_loop_candidates
+int verify_pairs(qn_kf_store* s, qn_ctx* ctx, const int32_t* query, const int32_t* cand, const double* yaw, uint32_t n_pairs, const double* poses, uint32_t n_poses,
+                 uint32_t submap_range, double leaf, double score_thr, int kind, qn_gicp_result* results, int* valid, int* status) {
+  // ---- every argument before anything runs: the store's batch slot, its verify record and the context stay as they were
+  if (!s || !ctx || !query || !cand || n_pairs == 0 || !poses || !results || !valid || !status || !(leaf > 0)) return QN_ERR_INVALID_ARG;
   if (qn_kf_int_device(s) != qn_ctx_int_device(ctx)) return QN_ERR_INVALID_ARG;
   const size_t n_kf = qn_kf_int_count(s);
-  if (query < 0 || (size_t)query >= n_kf || (uint32_t)query >= n_poses) return QN_ERR_INVALID_ARG;
-  for (uint32_t j = 0; j < n_cand; j++) {
-    const int32_t c = cand[j];
-    if (c < 0 || (size_t)c >= n_kf || (uint32_t)c >= n_poses || c == query) return QN_ERR_INVALID_ARG;
-    for (uint32_t i = 0; i < j; i++) if (cand[i] == c) return QN_ERR_INVALID_ARG;
+  auto bad_id = [&](int32_t id) { return id < 0 || (size_t)id >= n_kf || (uint32_t)id >= n_poses; };
+  for (uint32_t j = 0; j < n_pairs; j++) {
+    if (bad_id(query[j]) || bad_id(cand[j]) || cand[j] == query[j]) return QN_ERR_INVALID_ARG;
+    for (uint32_t i = 0; i < j; i++) if (query[i] == query[j] && cand[i] == cand[j]) return QN_ERR_INVALID_ARG;
     if (yaw && !std::isfinite(yaw[j])) return QN_ERR_INVALID_ARG;
   }
   for (size_t i = 0; i < (size_t)n_poses * 16; i++) if (!std::isfinite(poses[i])) return QN_ERR_INVALID_ARG;
-  // ---- the lists: [query] with the identity, then each candidate's window (loop_submap_ids(query, c, submap_range, False, False, n_poses)[1]) relative to it
-  std::vector<int32_t> ids; std::vector<double> rel; std::vector<uint32_t> seg(n_cand + 2, 0);
-  ids.push_back(query);
+  // ---- the lists: each distinct query alone with the identity, then each distinct candidate's window relative to it (loop_submap_ids(query, c, submap_range,
+  //      False, False, n_poses)[1]), one segment per distinct keyframe: a window depends on c, the poses and submap_range, never on the query
+  std::vector<int32_t> uq, uc; std::vector<uint32_t> qi, ci;
+  qn_kf_int_distinct(query, n_pairs, uq, qi); qn_kf_int_distinct(cand, n_pairs, uc, ci);
+  const uint32_t nq = (uint32_t)uq.size(), S = nq + (uint32_t)uc.size();
+  std::vector<int32_t> ids; std::vector<double> rel; std::vector<uint32_t> seg(1, 0);
   const double eye[16] = {1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0};
-  rel.insert(rel.end(), eye, eye + 16);
-  seg[1] = 1;
-  for (uint32_t j = 0; j < n_cand; j++) {
-    const long long c = cand[j];
-    for (long long i = c - (long long)submap_range; i <= c + (long long)submap_range; i++) {
-      if (i < 0 || i >= (long long)n_poses - 1) continue;                // the reference's `i < keyframes.size() - 1` (loop_closure.cpp:98-104)
-      if ((size_t)i >= n_kf) return QN_ERR_INVALID_ARG;
-      double Q[16];
-      relative_pose(poses + 16 * (size_t)c, poses + 16 * (size_t)i, Q);
-      ids.push_back((int32_t)i); rel.insert(rel.end(), Q, Q + 16);
-    }
-    seg[j + 2] = (uint32_t)ids.size();
-  }
-  std::vector<float> guess(16 * (size_t)n_cand);
-  for (uint32_t j = 0; j < n_cand; j++) seed_from_yaw(yaw ? yaw[j] : 0.0, guess.data() + 16 * (size_t)j);
-  // ---- one assembly (two host synchronisations): segment 0 the source, segment 1 + j candidate j
-  const uint32_t S = n_cand + 1;
+  for (uint32_t k = 0; k < nq; k++) { ids.push_back(uq[k]); rel.insert(rel.end(), eye, eye + 16); seg.push_back((uint32_t)ids.size()); }
+  int rc = qn_kf_int_windows(uc.data(), (uint32_t)uc.size(), poses, n_poses, n_kf, submap_range, false, ids, rel, seg);
+  if (rc != QN_OK) return rc;
+  // ---- one assembly (two host synchronisations), then the pairs whose clouds exist through the driver
   std::vector<const float*> d_xyz(S, nullptr); std::vector<uint32_t> n(S, 0); std::vector<int> ast(S, QN_OK);
-  int rc = qn_kf_assemble_batch(s, ids.data(), rel.data(), seg.data(), S, leaf, d_xyz.data(), n.data(), ast.data());
+  rc = qn_kf_assemble_batch(s, ids.data(), rel.data(), seg.data(), S, leaf, d_xyz.data(), n.data(), ast.data());
   if (rc != QN_OK) return rc;
-  // ---- one batched registration over the candidates whose clouds exist, every pair naming the same source buffer (prepared once)
-  std::vector<qn_pair_desc> pairs; std::vector<float> g; std::vector<uint32_t> which;
-  for (uint32_t j = 0; j < n_cand; j++) {
-    unset_record(&results[j]); valid[j] = 0;
-    status[j] = ast[0] != QN_OK ? ast[0] : ast[1 + j];
-    if (status[j] != QN_OK) continue;
-    pairs.push_back(qn_pair_desc{d_xyz[0], n[0], d_xyz[1 + j], n[1 + j], 16, 1});
-    g.insert(g.end(), guess.begin() + 16 * (size_t)j, guess.begin() + 16 * (size_t)j + 16);
-    which.push_back(j);
+  std::vector<qn_kf_int_verify_job> jobs(n_pairs);
+  for (uint32_t j = 0; j < n_pairs; j++) {
+    const uint32_t a = qi[j], b = nq + ci[j];
+    jobs[j] = qn_kf_int_verify_job{(const float4*)d_xyz[a], n[a], (const float4*)d_xyz[b], n[b], query[j], cand[j], a, ast[a] != QN_OK ? ast[a] : ast[b], {}, nullptr, nullptr};
+    seed_from_yaw(yaw ? yaw[j] : 0.0, jobs[j].guess);
   }
-  if (pairs.empty()) return QN_OK;
-  const uint32_t m = (uint32_t)pairs.size();
-  std::vector<qn_gicp_result> res(m); std::vector<int> val(m, 0), st(m, QN_OK);
-  rc = qn_gicp_align_batch_guess(ctx, pairs.data(), g.data(), m, score_thr, res.data(), val.data(), st.data());
-  if (rc != QN_OK) return rc;
-  for (uint32_t k = 0; k < m; k++) { results[which[k]] = res[k]; valid[which[k]] = val[k]; status[which[k]] = st[k]; }
-  return QN_OK;
+  return qn_kf_int_verify_run(s, ctx, jobs.data(), n_pairs, score_thr, false, kind, results, nullptr, nullptr, valid, status);
+}
+
+}  // namespace
+
+extern "C" int qn_kf_verify_loop_candidates(qn_kf_store* s, qn_ctx* ctx, int32_t query, const int32_t* cand, const double* yaw, uint32_t n_cand,
+                                            const double* poses, uint32_t n_poses, uint32_t submap_range, double leaf, double score_thr,
+                                            qn_gicp_result* results, int* valid, int* status) {
+  // the pairs form with the query repeated (segment 0 the source, segment 1 + j candidate j), leaving no record of its own
+  const std::vector<int32_t> q(cand ? n_cand : 0, query);
+  return verify_pairs(s, ctx, q.data(), cand, yaw, n_cand, poses, n_poses, submap_range, leaf, score_thr, QN_KF_VERIFY_KEEP, results, valid, status);
+}
+
+extern "C" int qn_kf_verify_loop_pairs(qn_kf_store* s, qn_ctx* ctx, const int32_t* query, const int32_t* cand, const double* yaw, uint32_t n_pairs,
+                                       const double* poses, uint32_t n_poses, uint32_t submap_range, double leaf, double score_thr,
+                                       qn_gicp_result* results, int* valid, int* status) {
+  return verify_pairs(s, ctx, query, cand, yaw, n_pairs, poses, n_poses, submap_range, leaf, score_thr, QN_KF_VERIFY_GICP, results, valid, status);
 }
 
 // ------------------------------------------------------------------ scans against the map itself: the crops and qn_kf_map_localize[_c2f]
 #include "qn_maplocalize.inc"
 
-// ------------------------------------------------------------------ many queries in one call
+// ------------------------------------------------------------------ the record a call leaves and the clouds qn_kf_verify_cloud serves from it
 namespace {
 
 // the record of the latest qn_kf_verify_loop_pairs[_c2f] call (store slot QN_KF_INT_EXT_VERIFY) and the arena qn_kf_verify_cloud computes into:
@@ -187,87 +257,6 @@ void qn_kf_int_verify_stale(qn_kf_store* s, int from, const int32_t* ids, uint32
   for (uint32_t i = 0; i < count; i++)
     for (const qn_kf_int_verify_pair& q : st->p)
       if (q.query == ids[i] || q.cand == ids[i]) { st->live = false; return; }
-}
-
-extern "C" int qn_kf_verify_loop_pairs(qn_kf_store* s, qn_ctx* ctx, const int32_t* query, const int32_t* cand, const double* yaw, uint32_t n_pairs,
-                                       const double* poses, uint32_t n_poses, uint32_t submap_range, double leaf, double score_thr,
-                                       qn_gicp_result* results, int* valid, int* status) {
-  // ---- every argument before anything runs: the store's batch slot, its verify record and the context stay as they were
-  if (!s || !ctx || !query || !cand || n_pairs == 0 || !poses || !results || !valid || !status || !(leaf > 0)) return QN_ERR_INVALID_ARG;
-  if (qn_kf_int_device(s) != qn_ctx_int_device(ctx)) return QN_ERR_INVALID_ARG;
-  const size_t n_kf = qn_kf_int_count(s);
-  auto bad_id = [&](int32_t id) { return id < 0 || (size_t)id >= n_kf || (uint32_t)id >= n_poses; };
-  std::vector<int32_t> uq, uc;                                                    // distinct queries, distinct candidates, in order of first appearance
-  std::vector<uint32_t> qi(n_pairs), ci(n_pairs);                                 // pair j -> its place in uq / uc
-  auto place = [](std::vector<int32_t>& u, int32_t id) -> uint32_t {
-    for (size_t i = 0; i < u.size(); i++) if (u[i] == id) return (uint32_t)i;
-    u.push_back(id); return (uint32_t)(u.size() - 1);
-  };
-  for (uint32_t j = 0; j < n_pairs; j++) {
-    if (bad_id(query[j]) || bad_id(cand[j]) || cand[j] == query[j]) return QN_ERR_INVALID_ARG;
-    for (uint32_t i = 0; i < j; i++) if (query[i] == query[j] && cand[i] == cand[j]) return QN_ERR_INVALID_ARG;
-    if (yaw && !std::isfinite(yaw[j])) return QN_ERR_INVALID_ARG;
-    qi[j] = place(uq, query[j]); ci[j] = place(uc, cand[j]);
-  }
-  for (size_t i = 0; i < (size_t)n_poses * 16; i++) if (!std::isfinite(poses[i])) return QN_ERR_INVALID_ARG;
-  // ---- the lists: each distinct query alone with the identity, then each distinct candidate's window relative to it - the lists of
-  //      qn_kf_verify_loop_candidates, one segment per distinct keyframe (a window depends on c, the poses and submap_range, never on the query)
-  const uint32_t nq = (uint32_t)uq.size(), S = nq + (uint32_t)uc.size();
-  std::vector<int32_t> ids; std::vector<double> rel; std::vector<uint32_t> seg(S + 1, 0);
-  const double eye[16] = {1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0};
-  for (uint32_t k = 0; k < nq; k++) { ids.push_back(uq[k]); rel.insert(rel.end(), eye, eye + 16); seg[k + 1] = (uint32_t)ids.size(); }
-  for (size_t k = 0; k < uc.size(); k++) {
-    const long long c = uc[k];
-    for (long long i = c - (long long)submap_range; i <= c + (long long)submap_range; i++) {
-      if (i < 0 || i >= (long long)n_poses - 1) continue;                // the reference's `i < keyframes.size() - 1` (loop_closure.cpp:98-104)
-      if ((size_t)i >= n_kf) return QN_ERR_INVALID_ARG;
-      double Q[16];
-      relative_pose(poses + 16 * (size_t)c, poses + 16 * (size_t)i, Q);
-      ids.push_back((int32_t)i); rel.insert(rel.end(), Q, Q + 16);
-    }
-    seg[nq + k + 1] = (uint32_t)ids.size();
-  }
-  // ---- one assembly (two host synchronisations)
-  std::vector<const float*> d_xyz(S, nullptr); std::vector<uint32_t> n(S, 0); std::vector<int> ast(S, QN_OK);
-  int rc = qn_kf_assemble_batch(s, ids.data(), rel.data(), seg.data(), S, leaf, d_xyz.data(), n.data(), ast.data());
-  if (rc != QN_OK) return rc;
-  // ---- one batched registration: the pairs whose clouds exist, grouped by query (stable: caller order within a query) so that the candidates of one
-  //      query sit in consecutive lanes and share the source's preparation
-  std::vector<uint32_t> order(n_pairs);
-  for (uint32_t j = 0; j < n_pairs; j++) order[j] = j;
-  std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return qi[a] < qi[b]; });
-  std::vector<qn_pair_desc> pairs; std::vector<float> g; std::vector<uint32_t> which;
-  for (uint32_t j = 0; j < n_pairs; j++) {
-    unset_record(&results[j]); valid[j] = 0;
-    const int sq = ast[qi[j]], sc = ast[nq + ci[j]];
-    status[j] = sq != QN_OK ? sq : sc;
-  }
-  for (uint32_t j : order) {
-    if (status[j] != QN_OK) continue;
-    const uint32_t a = qi[j], b = nq + ci[j];
-    pairs.push_back(qn_pair_desc{d_xyz[a], n[a], d_xyz[b], n[b], 16, 1});
-    float gj[16];
-    seed_from_yaw(yaw ? yaw[j] : 0.0, gj);
-    g.insert(g.end(), gj, gj + 16);
-    which.push_back(j);
-  }
-  std::vector<qn_kf_int_verify_pair> rec(n_pairs);
-  for (uint32_t j = 0; j < n_pairs; j++) {
-    const uint32_t a = qi[j], b = nq + ci[j];
-    rec[j] = qn_kf_int_verify_pair{(const float4*)d_xyz[a], n[a], (const float4*)d_xyz[b], n[b], query[j], cand[j], 0, {}, {}};
-  }
-  if (!pairs.empty()) {
-    const uint32_t m = (uint32_t)pairs.size();
-    std::vector<qn_gicp_result> res(m); std::vector<int> val(m, 0), st(m, QN_OK);
-    rc = qn_gicp_align_batch_guess(ctx, pairs.data(), g.data(), m, score_thr, res.data(), val.data(), st.data());
-    if (rc != QN_OK) return rc;
-    for (uint32_t k = 0; k < m; k++) {
-      const uint32_t j = which[k];
-      results[j] = res[k]; valid[j] = val[k]; status[j] = st[k];
-      if (st[k] == QN_OK) { rec[j].stage = 2; memcpy(rec[j].Tg, res[k].T, sizeof(rec[j].Tg)); }
-    }
-  }
-  return qn_kf_int_verify_record(s, QN_KF_VERIFY_GICP, rec.data(), n_pairs);
 }
 
 static int verify_cloud(qn_kf_store* s, uint32_t pair, int which, const float** d_xyz, uint32_t* n, bool sync);

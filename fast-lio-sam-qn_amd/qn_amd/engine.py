@@ -1026,6 +1026,35 @@ QN_LOCALIZE_SPHERE, QN_LOCALIZE_CYLINDER = 0, 1
 assert (C.sizeof(LocalizeParams), C.sizeof(LocalizeStats)) == (32, 40)                                      # the records of include/qn_engine.h
 
 
+def _verify_out(n):
+    """the output arrays of a verification call over n pairs: records, valid, status, T_total, T_quatro (at least one entry each)"""
+    m = max(n, 1)
+    return (GicpResult * m)(), np.zeros(m, np.int32), np.zeros(m, np.int32), np.zeros((m, 4, 4)), np.zeros((m, 4, 4))
+
+
+def _yaw_arg(yaw, n, msg):
+    """the optional per-pair yaw list as the C argument: None, or n doubles (ValueError(msg % (n, len)) otherwise)"""
+    if yaw is None:
+        return None
+    y = np.ascontiguousarray(np.atleast_1d(yaw), dtype=np.float64)
+    if len(y) != n:
+        raise ValueError(msg % (n, len(y)))
+    return _p(y)
+
+
+def _gicp_dicts(results, valid, status, n):
+    """one dict per pair of a GICP-form verification: T = the f32 record as f64"""
+    return [dict(valid=bool(valid[j]), converged=bool(results[j].converged), score=results[j].fitness, iterations=results[j].iterations,
+                 T=np.array(results[j].T, dtype=np.float32).reshape(4, 4).astype(np.float64), status=int(status[j]), record=results[j]) for j in range(n)]
+
+
+def _c2f_dicts(results, Tt, Tq, valid, status, n):
+    """one dict per pair of a coarse-to-fine verification: T = T_gicp * T_quatro"""
+    return [dict(valid=bool(valid[j]), converged=bool(results[j].converged), score=results[j].fitness, iterations=results[j].iterations, T=Tt[j].copy(),
+                 T_quatro=Tq[j].copy(), T_gicp=np.array(results[j].T, dtype=np.float32).reshape(4, 4).astype(np.float64), status=int(status[j]),
+                 record=results[j]) for j in range(n)]
+
+
 class KeyframeStore:
     """Device-resident keyframe clouds + LoopClosure::setSrcAndDstCloud on the GPU (loop_closure.cpp:58-108)."""
 
@@ -1052,6 +1081,11 @@ class KeyframeStore:
     def _check(self, st):
         if st != QN_OK:
             raise EngineError(st, self._l.qn_status_str(st).decode() + ": " + self._l.qn_kf_last_error(self.h).decode())
+
+    def _raise(self, st, ctx):
+        """_check for a call that took a context as well: the message carries the store's and the context's side"""
+        if st != QN_OK:
+            raise EngineError(st, self._l.qn_status_str(st).decode() + ": " + self._l.qn_kf_last_error(self.h).decode() + " / " + lib().qn_last_error(ctx.h).decode())
 
     def add(self, xyz, intensity=None):
         """intensity (n,) given: qn_kf_add_xyzi, the keyframe carries it into build_map; otherwise qn_kf_add (intensity 0 in the map)."""
@@ -1185,23 +1219,19 @@ class KeyframeStore:
         as f64), status (QN_ERR_EMPTY_CLOUD for an empty candidate submap)."""
         cand = np.ascontiguousarray(np.atleast_1d(candidates), dtype=np.int32)
         K = len(cand)
-        y = None if yaw is None else np.ascontiguousarray(np.atleast_1d(yaw), dtype=np.float64)
-        if y is not None and len(y) != K:
-            raise ValueError("verify_loop_candidates: %d candidates but %d yaw values" % (K, len(y)))
+        y = _yaw_arg(yaw, K, "verify_loop_candidates: %d candidates but %d yaw values")
         P = np.ascontiguousarray(np.asarray(poses, dtype=np.float64).reshape(-1, 16))
-        results = (GicpResult * max(K, 1))(); valid = np.zeros(max(K, 1), np.int32); status = np.zeros(max(K, 1), np.int32)
-        st = self._l.qn_kf_verify_loop_candidates(self.h, ctx.h, C.c_int32(query), _p(cand) if K else None, _p(y) if y is not None else None, C.c_uint32(K),
+        results, valid, status, _, _ = _verify_out(K)
+        st = self._l.qn_kf_verify_loop_candidates(self.h, ctx.h, C.c_int32(query), _p(cand) if K else None, y, C.c_uint32(K),
                                                   _p(P), C.c_uint32(len(P)), C.c_uint32(submap_range), C.c_double(leaf), C.c_double(score_thr),
                                                   results, _p(valid), _p(status))
-        if st != QN_OK:
-            raise EngineError(st, self._l.qn_status_str(st).decode() + ": " + self._l.qn_kf_last_error(self.h).decode() + " / " + lib().qn_last_error(ctx.h).decode())
+        self._raise(st, ctx)
         self._batch_n = []
         for seg in range(K + 1):
             n = C.c_uint32()
             self._check(self._l.qn_kf_batch_count(self.h, C.c_uint32(seg), C.byref(n)))
             self._batch_n.append(n.value)
-        return [dict(valid=bool(valid[j]), converged=bool(results[j].converged), score=results[j].fitness, iterations=results[j].iterations,
-                     T=np.array(results[j].T, dtype=np.float32).reshape(4, 4).astype(np.float64), status=int(status[j]), record=results[j]) for j in range(K)]
+        return _gicp_dicts(results, valid, status, K)
 
     # ---- resident Quatro descriptors and the drift-free coarse-to-fine check (qn_kf_quatro_*, qn_kf_verify_loop_candidates_c2f)
     def quatro_describe(self, ctx, ids, leaf):
@@ -1231,15 +1261,11 @@ class KeyframeStore:
         coarse_to_fine_align_batch's: valid, converged, score, iterations, T (T_gicp * T_quatro: estimates inv(P_c) P_query), T_quatro, T_gicp, status."""
         cand = np.ascontiguousarray(np.atleast_1d(candidates), dtype=np.int32)
         K = len(cand)
-        results = (GicpResult * max(K, 1))(); valid = np.zeros(max(K, 1), np.int32); status = np.zeros(max(K, 1), np.int32)
-        Tt = np.zeros((max(K, 1), 4, 4)); Tq = np.zeros((max(K, 1), 4, 4))
+        results, valid, status, Tt, Tq = _verify_out(K)
         st = self._l.qn_kf_verify_loop_candidates_c2f(self.h, ctx.h, C.c_int32(query), _p(cand) if K else None, C.c_uint32(K), C.c_double(score_thr),
                                                       results, _p(Tt), _p(Tq), _p(valid), _p(status))
-        if st != QN_OK:
-            raise EngineError(st, self._l.qn_status_str(st).decode() + ": " + self._l.qn_kf_last_error(self.h).decode() + " / " + lib().qn_last_error(ctx.h).decode())
-        return [dict(valid=bool(valid[j]), converged=bool(results[j].converged), score=results[j].fitness, iterations=results[j].iterations, T=Tt[j].copy(),
-                     T_quatro=Tq[j].copy(), T_gicp=np.array(results[j].T, dtype=np.float32).reshape(4, 4).astype(np.float64), status=int(status[j]),
-                     record=results[j]) for j in range(K)]
+        self._raise(st, ctx)
+        return _c2f_dicts(results, Tt, Tq, valid, status, K)
 
     # ---- many queries in one verification (qn_kf_verify_loop_pairs[_c2f]) and the debug clouds of a verified pair (qn_kf_verify_cloud)
     @staticmethod
@@ -1255,37 +1281,29 @@ class KeyframeStore:
         yaw None: all 0.  The store's batch slot holds the distinct queries (order of first appearance), then the distinct candidates' windows
         (download_batch).  -> one dict per pair, as verify_loop_candidates'."""
         q, c, n = self._pairs(query, cand)
-        y = None if yaw is None else np.ascontiguousarray(np.atleast_1d(yaw), dtype=np.float64)
-        if y is not None and len(y) != n:
-            raise ValueError("verify_loop_pairs: %d pairs but %d yaw values" % (n, len(y)))
+        y = _yaw_arg(yaw, n, "verify_loop_pairs: %d pairs but %d yaw values")
         P = np.ascontiguousarray(np.asarray(poses, dtype=np.float64).reshape(-1, 16))
-        results = (GicpResult * max(n, 1))(); valid = np.zeros(max(n, 1), np.int32); status = np.zeros(max(n, 1), np.int32)
-        st = self._l.qn_kf_verify_loop_pairs(self.h, ctx.h, _p(q) if n else None, _p(c) if n else None, _p(y) if y is not None else None, C.c_uint32(n),
+        results, valid, status, _, _ = _verify_out(n)
+        st = self._l.qn_kf_verify_loop_pairs(self.h, ctx.h, _p(q) if n else None, _p(c) if n else None, y, C.c_uint32(n),
                                              _p(P), C.c_uint32(len(P)), C.c_uint32(submap_range), C.c_double(leaf), C.c_double(score_thr),
                                              results, _p(valid), _p(status))
-        if st != QN_OK:
-            raise EngineError(st, self._l.qn_status_str(st).decode() + ": " + self._l.qn_kf_last_error(self.h).decode() + " / " + lib().qn_last_error(ctx.h).decode())
+        self._raise(st, ctx)
         self._batch_n = []
         for seg in range(len(dict.fromkeys(q.tolist())) + len(dict.fromkeys(c.tolist()))):
             m = C.c_uint32()
             self._check(self._l.qn_kf_batch_count(self.h, C.c_uint32(seg), C.byref(m)))
             self._batch_n.append(m.value)
-        return [dict(valid=bool(valid[j]), converged=bool(results[j].converged), score=results[j].fitness, iterations=results[j].iterations,
-                     T=np.array(results[j].T, dtype=np.float32).reshape(4, 4).astype(np.float64), status=int(status[j]), record=results[j]) for j in range(n)]
+        return _gicp_dicts(results, valid, status, n)
 
     def verify_loop_pairs_c2f(self, ctx, query, cand, score_thr=1.5):
         """qn_kf_verify_loop_pairs_c2f: pair j checked as verify_loop_candidates_c2f(ctx, query[j], [cand[j]]) would, record for record, all pairs in one run
         of the batched coarse-to-fine lanes on ctx (both sides borrowed from the described keyframes).  -> one dict per pair, as verify_loop_candidates_c2f's."""
         q, c, n = self._pairs(query, cand)
-        results = (GicpResult * max(n, 1))(); valid = np.zeros(max(n, 1), np.int32); status = np.zeros(max(n, 1), np.int32)
-        Tt = np.zeros((max(n, 1), 4, 4)); Tq = np.zeros((max(n, 1), 4, 4))
+        results, valid, status, Tt, Tq = _verify_out(n)
         st = self._l.qn_kf_verify_loop_pairs_c2f(self.h, ctx.h, _p(q) if n else None, _p(c) if n else None, C.c_uint32(n), C.c_double(score_thr),
                                                  results, _p(Tt), _p(Tq), _p(valid), _p(status))
-        if st != QN_OK:
-            raise EngineError(st, self._l.qn_status_str(st).decode() + ": " + self._l.qn_kf_last_error(self.h).decode() + " / " + lib().qn_last_error(ctx.h).decode())
-        return [dict(valid=bool(valid[j]), converged=bool(results[j].converged), score=results[j].fitness, iterations=results[j].iterations, T=Tt[j].copy(),
-                     T_quatro=Tq[j].copy(), T_gicp=np.array(results[j].T, dtype=np.float32).reshape(4, 4).astype(np.float64), status=int(status[j]),
-                     record=results[j]) for j in range(n)]
+        self._raise(st, ctx)
+        return _c2f_dicts(results, Tt, Tq, valid, status, n)
 
     # ---- resident local submaps and the submap-to-submap check (qn_kf_submap_*, qn_kf_verify_loop_pairs_submap[_c2f])
     def submap_describe(self, ctx, ids, poses, submap_range, leaf, with_features=True):
@@ -1298,8 +1316,7 @@ class KeyframeStore:
         st = np.zeros(max(len(ids), 1), np.int32)
         rc = self._l.qn_kf_submap_describe(self.h, ctx.h, _p(ids) if len(ids) else None, C.c_uint32(len(ids)), _p(P) if len(P) else None, C.c_uint32(len(P)),
                                            C.c_uint32(submap_range), C.c_double(leaf), C.c_int(1 if with_features else 0), _p(st))
-        if rc != QN_OK:
-            raise EngineError(rc, self._l.qn_status_str(rc).decode() + ": " + self._l.qn_kf_last_error(self.h).decode() + " / " + lib().qn_last_error(ctx.h).decode())
+        self._raise(rc, ctx)
         return [int(v) for v in st[:len(ids)]]
 
     def submap_cloud(self, kid):
@@ -1328,31 +1345,23 @@ class KeyframeStore:
         scancontext.seed_from_yaw(yaw[j]) (None: 0), every pair in ONE batched registration on ctx = gicp_align_batch(..., guesses=) on the entry clouds,
         record for record.  -> one dict per pair, as verify_loop_pairs'."""
         q, c, n = self._pairs(query, cand)
-        y = None if yaw is None else np.ascontiguousarray(np.atleast_1d(yaw), dtype=np.float64)
-        if y is not None and len(y) != n:
-            raise ValueError("verify_loop_pairs_submap: %d pairs but %d yaw values" % (n, len(y)))
-        results = (GicpResult * max(n, 1))(); valid = np.zeros(max(n, 1), np.int32); status = np.zeros(max(n, 1), np.int32)
-        st = self._l.qn_kf_verify_loop_pairs_submap(self.h, ctx.h, _p(q) if n else None, _p(c) if n else None, _p(y) if y is not None else None, C.c_uint32(n),
+        y = _yaw_arg(yaw, n, "verify_loop_pairs_submap: %d pairs but %d yaw values")
+        results, valid, status, _, _ = _verify_out(n)
+        st = self._l.qn_kf_verify_loop_pairs_submap(self.h, ctx.h, _p(q) if n else None, _p(c) if n else None, y, C.c_uint32(n),
                                                     C.c_double(score_thr), results, _p(valid), _p(status))
-        if st != QN_OK:
-            raise EngineError(st, self._l.qn_status_str(st).decode() + ": " + self._l.qn_kf_last_error(self.h).decode() + " / " + lib().qn_last_error(ctx.h).decode())
-        return [dict(valid=bool(valid[j]), converged=bool(results[j].converged), score=results[j].fitness, iterations=results[j].iterations,
-                     T=np.array(results[j].T, dtype=np.float32).reshape(4, 4).astype(np.float64), status=int(status[j]), record=results[j]) for j in range(n)]
+        self._raise(st, ctx)
+        return _gicp_dicts(results, valid, status, n)
 
     def verify_loop_pairs_submap_c2f(self, ctx, query, cand, score_thr=1.5):
         """qn_kf_verify_loop_pairs_submap_c2f: pair j coarse to fine (Quatro -> transformPcd -> Nano-GICP) between the two resident local submaps, the lanes
         borrowing their points and FPFH rows = coarse_to_fine_align_batch([ctx]) on the entry clouds, record for record.  -> one dict per pair, as
         verify_loop_pairs_c2f's."""
         q, c, n = self._pairs(query, cand)
-        results = (GicpResult * max(n, 1))(); valid = np.zeros(max(n, 1), np.int32); status = np.zeros(max(n, 1), np.int32)
-        Tt = np.zeros((max(n, 1), 4, 4)); Tq = np.zeros((max(n, 1), 4, 4))
+        results, valid, status, Tt, Tq = _verify_out(n)
         st = self._l.qn_kf_verify_loop_pairs_submap_c2f(self.h, ctx.h, _p(q) if n else None, _p(c) if n else None, C.c_uint32(n), C.c_double(score_thr),
                                                         results, _p(Tt), _p(Tq), _p(valid), _p(status))
-        if st != QN_OK:
-            raise EngineError(st, self._l.qn_status_str(st).decode() + ": " + self._l.qn_kf_last_error(self.h).decode() + " / " + lib().qn_last_error(ctx.h).decode())
-        return [dict(valid=bool(valid[j]), converged=bool(results[j].converged), score=results[j].fitness, iterations=results[j].iterations, T=Tt[j].copy(),
-                     T_quatro=Tq[j].copy(), T_gicp=np.array(results[j].T, dtype=np.float32).reshape(4, 4).astype(np.float64), status=int(status[j]),
-                     record=results[j]) for j in range(n)]
+        self._raise(st, ctx)
+        return _c2f_dicts(results, Tt, Tq, valid, status, n)
 
     def verify_loop_candidates_submap(self, ctx, query, candidates, yaw=None, score_thr=1.5):
         """one query's candidates, submap against submap: verify_loop_pairs_submap with the query repeated"""
@@ -1882,29 +1891,23 @@ class KeyframeStore:
         guesses=[g]) record for record.  -> (one dict per pair as verify_loop_pairs', T = the pose in the map; stats: a dict of the fields of qn_localize_stats).
         verify_cloud / verify_overlap serve the pairs afterwards; map_crop_get(k) the k-th distinct crop."""
         q, g, p, n = self._localize_args(query, guesses, params)
-        results = (GicpResult * max(n, 1))(); valid = np.zeros(max(n, 1), np.int32); status = np.zeros(max(n, 1), np.int32); st = LocalizeStats()
+        results, valid, status, _, _ = _verify_out(n); st = LocalizeStats()
         rc = self._l.qn_kf_map_localize(self.h, ctx.h, C.byref(p), _p(q) if n else None, _p(g) if n else None, C.c_uint32(n), results, _p(valid), _p(status), C.byref(st))
-        if rc != QN_OK:
-            raise EngineError(rc, self._l.qn_status_str(rc).decode() + ": " + self._l.qn_kf_last_error(self.h).decode() + " / " + lib().qn_last_error(ctx.h).decode())
+        self._raise(rc, ctx)
         stats = {f: int(getattr(st, f)) for f, _ in LocalizeStats._fields_ if f != "reserved"}
-        return [dict(valid=bool(valid[j]), converged=bool(results[j].converged), score=results[j].fitness, iterations=results[j].iterations,
-                     T=np.array(results[j].T, dtype=np.float32).reshape(4, 4).astype(np.float64), status=int(status[j]), record=results[j]) for j in range(n)], stats
+        return _gicp_dicts(results, valid, status, n), stats
 
     def map_localize_c2f(self, ctx, query, guesses, params=None):
         """qn_kf_map_localize_c2f: the same clouds coarse to fine (Quatro -> transformPcd -> Nano-GICP); only the guess's translation is used, as the crop
         centre = coarse_to_fine_align_batch([ctx], [(scan cloud, crop)]) record for record.  -> (one dict per pair as verify_loop_pairs_c2f's, T = the pose in
         the map; stats)."""
         q, g, p, n = self._localize_args(query, guesses, params)
-        results = (GicpResult * max(n, 1))(); valid = np.zeros(max(n, 1), np.int32); status = np.zeros(max(n, 1), np.int32); st = LocalizeStats()
-        Tt = np.zeros((max(n, 1), 4, 4)); Tq = np.zeros((max(n, 1), 4, 4))
+        results, valid, status, Tt, Tq = _verify_out(n); st = LocalizeStats()
         rc = self._l.qn_kf_map_localize_c2f(self.h, ctx.h, C.byref(p), _p(q) if n else None, _p(g) if n else None, C.c_uint32(n), results, _p(Tt), _p(Tq),
                                             _p(valid), _p(status), C.byref(st))
-        if rc != QN_OK:
-            raise EngineError(rc, self._l.qn_status_str(rc).decode() + ": " + self._l.qn_kf_last_error(self.h).decode() + " / " + lib().qn_last_error(ctx.h).decode())
+        self._raise(rc, ctx)
         stats = {f: int(getattr(st, f)) for f, _ in LocalizeStats._fields_ if f != "reserved"}
-        return [dict(valid=bool(valid[j]), converged=bool(results[j].converged), score=results[j].fitness, iterations=results[j].iterations, T=Tt[j].copy(),
-                     T_quatro=Tq[j].copy(), T_gicp=np.array(results[j].T, dtype=np.float32).reshape(4, 4).astype(np.float64), status=int(status[j]),
-                     record=results[j]) for j in range(n)], stats
+        return _c2f_dicts(results, Tt, Tq, valid, status, n), stats
 
     # ---- Scan Context loop candidates (qn_kf_sc_*; numpy twin: qn_amd/scancontext.py)
     def sc_set_params(self, params=None, **kw):

@@ -406,7 +406,9 @@ int  qn_kf_verify_loop_pairs_c2f(qn_kf_store*, qn_ctx*, const int32_t* query, co
  * the next qn_kf_verify_loop_pairs[_c2f] call, the next qn_kf_assemble_batch on the store (any caller: the GICP path's clouds live in its batch slot), a
  * qn_kf_quatro_describe of a keyframe the latest coarse-to-fine call involved, or the store's destruction.  The latest call may also be
  * qn_kf_verify_loop_pairs_submap[_c2f] (below): SRC / DST are then the two resident local submaps, valid until one of them is described again or released;
- * or qn_kf_map_localize[_c2f] (further below): SRC is the scan cloud, DST the map crop, valid until the next crop or localise call.  */
+ * or qn_kf_map_localize[_c2f] (further below): SRC is the scan cloud, DST the map crop, valid until the next crop or localise call.
+ * One rule for every verification and localise call above and below: when the batched registration itself returns an error (the call's return value, not a
+ * pair's status), the call has written nothing to results / valid / status / T_total / T_quatro and has not replaced the record served here.  */
 #define QN_VERIFY_SRC 0
 #define QN_VERIFY_DST 1
 #define QN_VERIFY_COARSE 2

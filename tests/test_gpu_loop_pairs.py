@@ -252,6 +252,35 @@ def test_verify_cloud_c2f(street):
     assert e.value.status == engine.QN_ERR_NOT_READY
 
 
+def test_a_single_query_call_leaves_no_record_of_its_own(street):
+    """verify_loop_candidates ends a live GICP record (its assembly rebuilds the batch slot that record names) and no other; verify_loop_candidates_c2f
+    touches no record.  Either call's records are the pairs form's for the same pairs."""
+    from qn_amd import engine
+    st = street; store, ctx, gctx = st["store"], st["ctx"], st["gctx"]
+    q = st["pairs"][0][0]
+    cs, ys = zip(*[(c, y) for q2, c, y in st["pairs"] if q2 == q])
+    qs = [q] * len(cs)
+    assert len(cs) >= 2
+
+    def src_bytes():
+        a = store.verify_cloud(0, engine.QN_VERIFY_SRC)
+        assert len(a) > 0
+        return a.tobytes()
+    gwant = [_grec(o) for o in store.verify_loop_pairs(gctx, qs, cs, ys, st["drift"], RANGE, LEAF)]
+    assert [_grec(o) for o in store.verify_loop_candidates(gctx, q, cs, ys, st["drift"], RANGE, LEAF)] == gwant
+    with pytest.raises(engine.EngineError) as e:                                   # a GICP record: gone with the batch slot
+        store.verify_cloud(0, engine.QN_VERIFY_SRC)
+    assert e.value.status == engine.QN_ERR_NOT_READY
+    cwant = [_crec(o) for o in store.verify_loop_pairs_c2f(ctx, qs, cs)]
+    before = src_bytes()
+    assert [_grec(o) for o in store.verify_loop_candidates(gctx, q, cs, ys, st["drift"], RANGE, LEAF)] == gwant
+    assert src_bytes() == before                                                   # a coarse-to-fine record names described clouds: it stays
+    store.verify_loop_pairs(gctx, qs, cs, ys, st["drift"], RANGE, LEAF)
+    before = src_bytes()
+    assert [_crec(o) for o in store.verify_loop_candidates_c2f(ctx, q, cs)] == cwant
+    assert src_bytes() == before                                                   # the coarse-to-fine call assembles nothing: the GICP record stays
+
+
 def test_cpp_helpers_return_the_python_records(tmp_path):
     from qn_amd import build, engine
     build.build()
