@@ -1,4 +1,4 @@
-// qn_kf_buf.h - the host plumbing every translation unit around a qn_kf_store shares: one error macro, one owned buffer with two ways to grow, one
+// qn_kf_buf.h - the host plumbing every translation unit around a qn_kf_store shares: one error macro, one owned buffer with three ways to grow, one
 // get-or-create of a unit's per-store state, one pair of result sets for the units whose results belong to the map slot.  Header only.  Rule of the buffers: a call that fails leaves nothing stale behind - a buffer that could not
 // be grown is empty, a slot array that could not be moved is the old one, and the HIP runtime's sticky error is cleared (a hipGetLastError() behind a later
 // launch on this thread would otherwise report the old out-of-memory as its own).
@@ -44,6 +44,10 @@ template <typename T, bool kPinned> struct KfBuf {
     cap = n;
     return true;
   }
+  // results that must outlive a failed call: room for `need` elements with this buffer untouched - nothing when they fit, else `fresh` is allocated beside
+  // it (false: nothing changed).  Once everything the call needs is there, adopt(fresh) makes the larger one this buffer and the old one goes with `fresh`.
+  bool grow_beside(qn_kf_store* s, size_t need, KfBuf& fresh) const { return need <= cap || fresh.grow(s, need); }
+  void adopt(KfBuf& fresh) noexcept { if (fresh.p) swap(fresh); }
   // slot arrays: new_cap elements whose first `cap` are the old ones, copied on `stream` and synchronised before the old buffer goes.
   // false: the buffer is as it was.
   bool grow_keep(qn_kf_store* s, size_t new_cap, hipStream_t stream) {

@@ -1,20 +1,20 @@
 // qn_map_compact.cuh - what the units around the map slot share on the device besides the cell walk (qn_mapoutliers.hip with qn_mapclusters.inc, qn_mapground.hip,
 // qn_staticmap.hip with qn_mapoccupancy.inc, qn_mapdistance.inc, qn_maproute.inc and qn_mapfrontier.inc, qn_verify.hip with qn_maplocalize.inc); the lock-free
-// union-find of the clusters and the frontiers is qn_union_find.cuh, the dense grid's quantisation and index split are at the head of qn_mapoccupancy.inc:
+// union-find of the clusters and the frontiers is qn_union_find.cuh, what the fields over the dense occupancy grid share - geometry, tile, lists - qn_dense_grid.cuh:
 //   waves     wave_sum, wave_min, wave_max: a value folded over the 64 lanes by shuffles, lane 0 holds the result (int, u32, u64; f32 by fminf / fmaxf);
 //             wave_each_key: a callable run once per distinct key the lanes of a wave hold - the key, its first lane and the ballot of the lanes that share it -
 //             so that a wave folds its lanes of one key first and issues one set of atomics for them (k_mf_flatten, k_mf_relabel, k_mf_costs).
 //   counts    block_count: the lanes of a block for which each of up to five predicates holds, by ballot and popcount; block_sum, block_max: up to three values
 //             a lane folded over the block.  Each has one word per wave in LDS and a barrier of its own and writes the block's own slot; k_slot_fold (one
 //             block) adds the slots up, k_slot_max takes the largest.  No atomics: integer sums and extremes, the same on every run.  Three kernels whose calls
-//             measured slower with a fold's own barrier (k_md_axis<true>, k_mr_stats, k_mg_extent) keep their wave results in words of their own behind
-//             block_count's barrier, and say so where they do (profiles/EXPERIMENTS.md has the figures).
+//             measured slower with a fold's own barrier (k_md_axis<true> and k_mr_stats through dg_block_stats of qn_dense_grid.cuh, k_mg_extent) keep their wave
+//             results in words of their own behind block_count's barrier, and say so where they do (profiles/EXPERIMENTS.md has the figures).
 //   scan      scan_row: the exclusive scan of a row of per-block counts in one block; k_scan_rows, a block per row, is the kernel over it (one row: a filter's
 //             or a list's counts, the last word the total; a row per centre, in place: the crop), k_static_scan (qn_staticmap.hip) the one with a tail of its own.
 //   rank      lane_rank: a lane's place among the lanes of its wave for which a predicate holds, by ballot and popcount; block_rank: its place in the block, the
 //             waves' counts through LDS, on top of the block's offset from the scan - where a stable compaction puts the lane's record: the same on every run.
-//             The kernels with one predicate call block_rank and write their own payload there (k_mo_compact, k_mc_pick, k_mc_root_label, k_oc_list_pick,
-//             k_mf_pick, k_mf_list_pick);
+//             The kernels with one predicate call block_rank and write their own payload there (k_mo_compact, k_mc_pick, k_mc_root_label, k_mf_pick,
+//             k_dg_list_pick of qn_dense_grid.cuh for the two voxel lists);
 //             those with a table of their own (k_static_compact: rounds, k_ml_compact: centres) take lane_rank for the last term.
 //   compact   the order-preserving compaction of the slot's records: a unit's own flag kernel writes one removed byte per record and the kept count of every
 //             MO_BLOCK records (block_count), k_scan_rows turns the counts into offsets, k_mo_compact moves a block's kept records to its offset, in order;

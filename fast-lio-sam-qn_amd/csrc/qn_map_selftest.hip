@@ -1,21 +1,25 @@
 // qn_map_selftest.hip - qn_kf_debug_map_prims (include/qn_engine.h): the device builds of what the map units share - the wave and block folds, the key walk,
-// the slot folds, the row scan and the block rank of qn_map_compact.cuh, the two linkers of qn_union_find.cuh - on caller-supplied inputs, one routine a call.
+// the slot folds, the row scan and the block rank of qn_map_compact.cuh, the two linkers of qn_union_find.cuh, the index, tile and rim arithmetic and the
+// neighbourhood walk of qn_dense_grid.cuh - on caller-supplied inputs, one routine a call.
 // The kernels here only carry a lane's input to the headers' own functions and the result back; k_slot_fold, k_slot_max and k_scan_rows are launched as they
 // are.  The units can express only a few input patterns (a block's count is at most 256, a key is a region number, an edge joins geometric neighbours); here
 // the patterns are the caller's: tests/test_gpu_map_prims.py against the plain references of tests/map_prims_cases.py.  What the units instantiate, by grep
 // over csrc/ (each has a field here):
 //   wave folds   int min / max (k_mf_relabel, k_oc_extent), uint32_t sum (k_mf_relabel, k_mg_extent_sum) / min (k_mc_info) / max (k_mc_info, k_mc_number,
-//                k_md_axis, k_mr_stats, k_slot_max), unsigned long long sum (k_md_axis, k_mr_stats, k_slot_fold) / min (k_mf_costs), float min / max
+//                dg_block_stats, k_slot_max), unsigned long long sum (dg_block_stats, k_slot_fold) / min (k_mf_costs), float min / max
 //                (k_mg_extent, k_mg_extent_sum), long long sum (k_mc_info)
 //   key walk     uint32_t keys (k_mf_flatten), int32_t keys (k_mf_relabel, k_mf_costs)
 //   block folds  block_count of 1, 2, 3 and 5 predicates; block_sum<uint32_t> of one value (k_mf_mark), <unsigned long long> of one (k_mc_hook), of two
 //                uint32_t values widened (k_oc_classify) and of three (k_mo_flag); block_max<uint32_t> of one (k_mf_roots)
 //   slot folds   k_slot_fold<uint32_t, K> with K = 1, 2, 3, 5, 10; k_slot_fold<unsigned long long, K> with K = 1, 2, 3; k_slot_max<uint32_t>
+//   grid         oc_ijk and dg_index (every kernel of the four dense-grid files), dg_tile_of (k_mr_goals, k_mf_mark, k_mr_relax), dg_in_tile (k_mf_merge), dg_lane_pos
+//                over dg_local and dg_pos (k_mr_relax, k_mf_tile), dg_tile_origin (k_mr_relax, k_mf_tile), dg_each_neighbour (k_mr_relax, k_mf_tile, k_mf_merge)
 // Test infrastructure: it runs on the store's stream with the store's scratch (buffers 0 and 1), and nothing on a product path calls it.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
 #include "qn_map_compact.cuh"
+#include "qn_dense_grid.cuh"
 #include "qn_union_find.cuh"
 
 namespace {
@@ -127,6 +131,33 @@ __global__ void __launch_bounds__(MO_BLOCK) k_st_uf_flatten(uint32_t n, const ui
   root[x] = r;
 }
 
+// ---------------------------------------------------------------------------------------------------------------- 8: the grid geometry
+struct StVoxel { uint32_t x, y, z, index, tile, place, pos, zero; };
+static_assert(sizeof(StVoxel) == 32 && sizeof(DgIjk) == 12, "the records of include/qn_engine.h");
+
+// lane i: the split of linear index i, the index rebuilt from it, the voxel's tile, its place in the tile (the lane that holds it) and that place's LDS position
+__global__ void __launch_bounds__(MO_BLOCK) k_st_grid_voxels(uint32_t n, uint32_t W, uint32_t H, const DgTiles tiles, StVoxel* __restrict__ out) {
+  const uint32_t i = blockIdx.x * MO_BLOCK + threadIdx.x;
+  if (i >= n) return;
+  const DgIjk v = oc_ijk(i, W, H);
+  StVoxel r;
+  r.x = (uint32_t)v.x; r.y = (uint32_t)v.y; r.z = (uint32_t)v.z;
+  r.index = dg_index(v, W, H); r.tile = dg_tile_of(r.x, r.y, r.z, tiles);
+  r.place = dg_index(dg_in_tile(r.x), dg_in_tile(r.y), dg_in_tile(r.z), DG_T, DG_T); r.pos = dg_lane_pos(r.place); r.zero = 0;
+  out[i] = r;
+}
+
+// lane t: the first voxel of tile t; lane 0 also walks the neighbourhood and writes the offsets in the order it is handed them
+__global__ void __launch_bounds__(MO_BLOCK) k_st_grid_tiles(const DgTiles tiles, int32_t* __restrict__ origin, DgIjk* __restrict__ walk) {
+  const uint32_t t = blockIdx.x * MO_BLOCK + threadIdx.x;
+  if (t >= tiles.n) return;
+  const DgIjk o = dg_tile_origin(t, tiles);
+  origin[4 * (size_t)t] = o.x; origin[4 * (size_t)t + 1] = o.y; origin[4 * (size_t)t + 2] = o.z; origin[4 * (size_t)t + 3] = 0;
+  if (t != 0) return;
+  uint32_t k = 0;
+  dg_each_neighbour([&](int dx, int dy, int dz) { walk[k++] = DgIjk{dx, dy, dz}; });
+}
+
 bool st_fold_k(uint32_t arg) {
   const uint32_t k = arg & 0xffu;
   if ((arg & ~0xffu) == 0) return k == 1 || k == 2 || k == 3 || k == 5 || k == 10;
@@ -153,6 +184,7 @@ extern "C" int qn_kf_debug_map_prims(qn_kf_store* s, int which, const void* in, 
   if (!s || !in || !out || which < 0 || which >= QN_DEBUG_MAP_PRIMS_WHICH) return QN_ERR_INVALID_ARG;
   size_t in_bytes = 0, out_bytes = 0;
   uint32_t m = 0, forest = 0, rows = 0;
+  DgTiles tiles = {0, 0, 0, 0};
   switch (which) {
     case 0:
       if (arg != 0 || n > QN_DEBUG_MAP_PRIMS_MAX_BLOCKS) return QN_ERR_INVALID_ARG;
@@ -181,6 +213,14 @@ extern "C" int qn_kf_debug_map_prims(qn_kf_store* s, int which, const void* in, 
       if (arg != 0 || n > QN_DEBUG_MAP_PRIMS_MAX_BLOCKS) return QN_ERR_INVALID_ARG;
       in_bytes = (MO_BLOCK + sizeof(uint32_t)) * (size_t)n; out_bytes = sizeof(uint32_t) * MO_BLOCK * (size_t)n;
       break;
+    case 8: {
+      if (arg != 0 || n > QN_DEBUG_MAP_PRIMS_MAX_NODES) return QN_ERR_INVALID_ARG;
+      const uint32_t* side = (const uint32_t*)in;                    // (n == 0: nothing is read)
+      if (n && (side[0] == 0 || side[1] == 0 || side[2] == 0 || side[0] > n || side[1] > n || side[2] > n || (uint64_t)side[0] * side[1] * side[2] != n)) return QN_ERR_INVALID_ARG;
+      if (n) tiles = dg_tiles(side[0], side[1], side[2]);
+      in_bytes = sizeof(uint32_t) * 3; out_bytes = sizeof(StVoxel) * (size_t)n + 16 * (size_t)tiles.n + sizeof(DgIjk) * 26;
+      break;
+    }
     default: {
       if (arg < 1 || arg > 13 || n > QN_DEBUG_MAP_PRIMS_MAX_NODES) return QN_ERR_INVALID_ARG;
       const uint32_t* h = (const uint32_t*)in;
@@ -229,6 +269,13 @@ extern "C" int qn_kf_debug_map_prims(qn_kf_store* s, int which, const void* in, 
     case 5:
       hipLaunchKernelGGL(k_st_rank, grid, block, 0, str, (const uint8_t*)d_in, (const uint32_t*)(d_in + MO_BLOCK * (size_t)n), (uint32_t*)d_out);
       break;
+    case 8: {
+      const uint32_t* side = (const uint32_t*)in;
+      int32_t* origin = (int32_t*)(d_out + sizeof(StVoxel) * (size_t)n);
+      hipLaunchKernelGGL(k_st_grid_voxels, dim3(dg_blocks(n)), block, 0, str, n, side[0], side[1], tiles, (StVoxel*)d_out);
+      hipLaunchKernelGGL(k_st_grid_tiles, dim3(dg_blocks(tiles.n)), block, 0, str, tiles, origin, (DgIjk*)(origin + 4 * (size_t)tiles.n));
+      break;
+    }
     default: {
       const uint32_t* d_h = (const uint32_t*)d_in + 2;
       const uint32_t* d_edges = d_h + (forest ? n : 0);

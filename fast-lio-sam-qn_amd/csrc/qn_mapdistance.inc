@@ -9,12 +9,13 @@
 //             walking outwards from d = 0 and stopping once d d >= the best so far, which is exact (every later term is at least d d) and makes the cost the
 //             distance to the answer, not max_dist.  Plain global loads: the neighbours of a block's voxels are the neighbours' blocks' voxels, served by L2.
 //             A result above max_dist^2 becomes FAR: a site within max_dist has every per-axis offset within max_dist, so it survives the windowed passes.
-//             The z pass (LAST) also counts: sites, reached and far voxels by block_count into the block's slot, the block's largest and summed reached d2
-//             into slots of their own (wave_max, wave_sum and block_count's barrier: measured faster than block_max and block_sum); k_slot_fold adds the slots up, k_slot_max takes the largest.
-//   slice     k_md_slice, one column per lane: the smallest d2 over a band of layers.
+//             The z pass (LAST) also counts: sites, reached and far voxels, the block's largest and summed reached d2 into slots of their own (dg_block_stats:
+//             block_count(sites, reached, far), wave_max and wave_sum behind its barrier); dg_fold_stats folds the slots (k_slot_fold<uint32_t, 3>, k_slot_max).
+//   slice     the smallest d2 over a band of layers: k_dg_slice<uint16_t, op_min> of qn_dense_grid.cuh, one column per lane.
 //   query     k_md_query, one point per lane: the voxel of an f64 world point by the occupancy map's quantisation (oc_voxel; the only floating point in this file's kernels).
 // Every voxel and every slot has one writer, nothing is read and modified in place; no scratch memory, no dynamically indexed private array.  Host synchronisations of qn_kf_map_distance: one - the statistics.
-// Part of qn_staticmap.hip's translation unit (included after qn_mapoccupancy.inc): the field hangs on that file's OccState and takes no slot of its own.
+// Part of qn_staticmap.hip's translation unit (included after qn_mapoccupancy.inc): the field hangs on that file's OccState and takes no slot of its own; the
+// index arithmetic, the statistics tail, the slice, the point upload and the lookup of the live results are qn_dense_grid.cuh's.
 
 namespace {
 
@@ -75,8 +76,8 @@ __global__ void __launch_bounds__(MD_BLOCK) k_md_x(uint32_t cells, uint32_t W, c
 }
 
 // One voxel per lane, linear order: g[v] = min over |d| <= R, inside the axis, of f[v + d stride] + d d; above R^2: FAR.  n: the voxels along the axis, stride:
-// between two of them.  LAST: the z pass, which also leaves the block's counts - cslots[3 b ..] = its sites, reached and far voxels, mslots[b] = the largest
-// d2 of its reached voxels, tslots[b] = their sum.
+// between two of them - the kernel's own coordinate, not oc_ijk's split: with the split the call missed its timing bar twice (profiles/EXPERIMENTS.md).  LAST: the
+// z pass, which also leaves the block's counts - cslots[3 b ..] = its sites, reached and far voxels, mslots[b] = the largest d2 of its reached voxels, tslots[b] = their sum.
 template <bool LAST>
 __global__ void __launch_bounds__(MD_BLOCK) k_md_axis(uint32_t cells, uint32_t stride, uint32_t n, uint32_t R, const uint16_t* __restrict__ f, uint16_t* __restrict__ g,
                                                       uint32_t* __restrict__ cslots, uint32_t* __restrict__ mslots, unsigned long long* __restrict__ tslots) {
@@ -97,32 +98,11 @@ __global__ void __launch_bounds__(MD_BLOCK) k_md_axis(uint32_t cells, uint32_t s
   }
   if (LAST) {
     const bool in = i < cells, reached = in && best != 0 && best != QN_DIST_FAR;
-    const uint32_t m = reached ? best : 0u;
-    __shared__ unsigned long long wt[MO_WAVES];
-    __shared__ uint32_t wm[MO_WAVES];
-    const unsigned long long t = wave_sum((unsigned long long)m);
-    const uint32_t mm = wave_max(m);
-    if ((threadIdx.x & 63) == 0) { wt[threadIdx.x >> 6] = t; wm[threadIdx.x >> 6] = mm; }
-    // its barrier is the one the sums wait for: block_max and block_sum, two barriers more, cost the call 0.8 % at 1e7 voxels (profiles/EXPERIMENTS.md)
-    block_count(cslots + 3 * (size_t)blockIdx.x, in && best == 0, reached, in && best == QN_DIST_FAR);
-    if (threadIdx.x == 0) {
-      unsigned long long acc = 0; uint32_t top = 0;
-      for (int w = 0; w < MO_WAVES; w++) { acc += wt[w]; top = max(top, wm[w]); }
-      tslots[blockIdx.x] = acc; mslots[blockIdx.x] = top;
-    }
+    dg_block_stats(in && best == 0, reached, in && best == QN_DIST_FAR, reached ? best : 0u, cslots, mslots, tslots);
   }
 }
 
-// one column per lane: the smallest d2 over the layers lo .. hi
-__global__ void __launch_bounds__(MD_BLOCK) k_md_slice(uint32_t cols, const uint16_t* __restrict__ d2, uint32_t lo, uint32_t hi, uint16_t* __restrict__ out) {
-  const uint32_t c = blockIdx.x * MD_BLOCK + threadIdx.x;
-  if (c >= cols) return;
-  uint32_t v = QN_DIST_FAR;
-  for (uint32_t z = lo; z <= hi; z++) v = min(v, (uint32_t)d2[(size_t)z * cols + c]);
-  out[c] = (uint16_t)v;
-}
-
-// one point per lane: its voxel by the occupancy map's quantisation (oc_voxel: qn_mapoccupancy.inc), then the field's value and the voxel's class there; FAR and
+// one point per lane: its voxel by the occupancy map's quantisation (oc_voxel: qn_dense_grid.cuh), then the field's value and the voxel's class there; FAR and
 // OUTSIDE for a point that is not finite, 2^20 voxels or more from the origin, or outside the grid
 __global__ void __launch_bounds__(MD_BLOCK) k_md_query(uint32_t n, const double* __restrict__ xyz, double inv, const OcGrid G, uint32_t D, const uint16_t* __restrict__ d2,
                                                        const uint8_t* __restrict__ cls, uint16_t* __restrict__ d2_out, uint8_t* __restrict__ cls_out) {
@@ -130,7 +110,7 @@ __global__ void __launch_bounds__(MD_BLOCK) k_md_query(uint32_t n, const double*
   if (i >= n) return;
   uint32_t x, y, z, v = QN_DIST_FAR, q = QN_DIST_OUTSIDE;
   if (oc_voxel(xyz, i, inv, G, D, 0u, &x, &y, &z)) {
-    const size_t lin = ((size_t)z * G.H + y) * G.W + x;
+    const uint32_t lin = dg_index(x, y, z, G.W, G.H);
     v = d2[lin]; q = cls[lin];
   }
   d2_out[i] = (uint16_t)v; cls_out[i] = (uint8_t)q;
@@ -148,13 +128,6 @@ void mr_end(RouteState*);                                // (qn_maproute.inc) a 
 
 void md_end(DistState* d) { if (d) { d->live = false; mr_end(d->route.get()); } }
 
-// the occupancy result and its live field, or nullptr
-const DistState* md_live(qn_kf_store* s, const OccState** occ) {
-  const OccState* o = oc_live(s);
-  *occ = o;
-  return o && o->dist && o->dist->live ? o->dist.get() : nullptr;
-}
-
 }  // namespace
 
 extern "C" void qn_distance_default_params(qn_distance_params* p) {
@@ -168,10 +141,10 @@ extern "C" int qn_kf_map_distance(qn_kf_store* s, const qn_distance_params* para
   if (!s || !params || !stats_out) return QN_ERR_INVALID_ARG;
   const qn_distance_params P = *params;
   if (P.site_mask == 0 || (P.site_mask & ~7u) || P.max_dist < 1 || P.max_dist > QN_DIST_MAX_RADIUS || P.reserved[0] != 0 || P.reserved[1] != 0) return QN_ERR_INVALID_ARG;
-  OccState* o = oc_live_mut(s);
+  OccState* o = dg_mut(dg_live(s).occ);
   if (!o) return QN_ERR_NOT_READY;
   const qn_occupancy_grid& g = o->info;
-  const uint32_t cells = g.width * g.height * g.depth, cb = (cells + MD_BLOCK - 1) / MD_BLOCK;
+  const uint32_t cells = dg_cells(g), cb = dg_blocks(cells);
   qn_distance_stats r;
   memset(&r, 0, sizeof(r));
   if (!o->dist) o->dist.reset(new (std::nothrow) DistState());
@@ -182,7 +155,7 @@ extern "C" int qn_kf_map_distance(qn_kf_store* s, const qn_distance_params* para
     const hipStream_t str = qn_kf_int_stream(s);
     // ---- the two grids: a larger one is allocated beside the previous field, which goes only once both are there
     DevBuf<uint16_t> na, nb;
-    if ((cells > st->d2.cap && !na.grow(s, cells)) || (cells > st->tmp.cap && !nb.grow(s, cells))) return QN_ERR_HIP;
+    if (!st->d2.grow_beside(s, cells, na) || !st->tmp.grow_beside(s, cells, nb)) return QN_ERR_HIP;
     // ---- scratch (3: the blocks' three counts, then their largest d2; 4: their u64 sums; 5: the folded sums - sites, reached, far, max_d2 and sum_d2 at byte 16)
     uint32_t* d_slots = (uint32_t*)qn_kf_int_scratch(s, 3, sizeof(uint32_t) * 4 * (size_t)cb);
     unsigned long long* d_tslots = (unsigned long long*)qn_kf_int_scratch(s, 4, sizeof(unsigned long long) * (size_t)cb);
@@ -191,17 +164,12 @@ extern "C" int qn_kf_map_distance(qn_kf_store* s, const qn_distance_params* para
     if (!d_slots || !d_tslots || !d_small || !h) return qn_kf_fail(s, "qn_kf_map_distance: scratch allocation failed");
     // ---- from here on the previous field is gone
     st->live = false;
-    if (na.p) st->d2.swap(na);
-    if (nb.p) st->tmp.swap(nb);
-    uint32_t* d_sums = (uint32_t*)d_small; uint32_t* d_mslots = d_slots + 3 * (size_t)cb;
-    const uint32_t W = g.width, WH = g.width * g.height;
-    hipLaunchKernelGGL(k_md_x, dim3(cb), dim3(MD_BLOCK), 0, str, cells, W, (const uint8_t*)o->cls.p, P.site_mask, P.max_dist, st->d2.p);
-    hipLaunchKernelGGL(k_md_axis<false>, dim3(cb), dim3(MD_BLOCK), 0, str, cells, W, g.height, P.max_dist, (const uint16_t*)st->d2.p, st->tmp.p, (uint32_t*)nullptr,
+    st->d2.adopt(na); st->tmp.adopt(nb);
+    hipLaunchKernelGGL(k_md_x, dim3(cb), dim3(MD_BLOCK), 0, str, cells, g.width, (const uint8_t*)o->cls.p, P.site_mask, P.max_dist, st->d2.p);
+    hipLaunchKernelGGL(k_md_axis<false>, dim3(cb), dim3(MD_BLOCK), 0, str, cells, g.width, g.height, P.max_dist, (const uint16_t*)st->d2.p, st->tmp.p, (uint32_t*)nullptr,
                        (uint32_t*)nullptr, (unsigned long long*)nullptr);
-    hipLaunchKernelGGL(k_md_axis<true>, dim3(cb), dim3(MD_BLOCK), 0, str, cells, WH, g.depth, P.max_dist, (const uint16_t*)st->tmp.p, st->d2.p, d_slots, d_mslots, d_tslots);
-    hipLaunchKernelGGL((k_slot_fold<uint32_t, 3>), dim3(1), dim3(MO_SCAN_BLOCK), 0, str, (const uint32_t*)d_slots, cb, d_sums);
-    hipLaunchKernelGGL(k_slot_max<uint32_t>, dim3(1), dim3(MO_SCAN_BLOCK), 0, str, (const uint32_t*)d_mslots, cb, d_sums + 3);
-    hipLaunchKernelGGL((k_slot_fold<unsigned long long, 1>), dim3(1), dim3(MO_SCAN_BLOCK), 0, str, (const unsigned long long*)d_tslots, cb, (unsigned long long*)(d_small + 16));
+    hipLaunchKernelGGL(k_md_axis<true>, dim3(cb), dim3(MD_BLOCK), 0, str, cells, dg_cols(g), g.depth, P.max_dist, (const uint16_t*)st->tmp.p, st->d2.p, d_slots, d_slots + 3 * (size_t)cb, d_tslots);
+    dg_fold_stats(str, d_slots, d_tslots, cb, d_small);
     QN_KFCHK(s, hipGetLastError());
     QN_KFCHK(s, hipMemcpyAsync(h, d_small, 32, hipMemcpyDeviceToHost, str));
     QN_KFCHK(s, hipStreamSynchronize(str));                   // the one sync: the statistics
@@ -218,55 +186,39 @@ extern "C" int qn_kf_map_distance(qn_kf_store* s, const qn_distance_params* para
 
 extern "C" int qn_kf_map_distance_grid(qn_kf_store* s, qn_occupancy_grid* info_out, qn_distance_params* params_out, uint16_t* d2_out) {
   if (!s || !info_out || !params_out) return QN_ERR_INVALID_ARG;
-  const OccState* o = nullptr;
-  const DistState* d = md_live(s, &o);
-  if (!d) return QN_ERR_NOT_READY;
-  const qn_occupancy_grid& g = o->info;
-  const size_t cells = (size_t)g.width * g.height * g.depth;
-  *info_out = g; *params_out = d->params;
+  const DgLive L = dg_live(s);
+  if (!L.dist) return QN_ERR_NOT_READY;
+  const size_t cells = dg_cells(L.occ->info);
+  *info_out = L.occ->info; *params_out = L.dist->params;
   if (!cells || !d2_out) return QN_OK;
-  return qn_kf_download(s, d2_out, d->d2.p, sizeof(uint16_t) * cells);
+  return qn_kf_download(s, d2_out, L.dist->d2.p, sizeof(uint16_t) * cells);
 }
 
 extern "C" int qn_kf_map_distance_slice(qn_kf_store* s, int32_t iz_lo, int32_t iz_hi, uint16_t* d2_out) {
   if (!s || !d2_out || iz_lo > iz_hi) return QN_ERR_INVALID_ARG;
-  const OccState* o = nullptr;
-  const DistState* d = md_live(s, &o);
-  if (!d) return QN_ERR_NOT_READY;
-  const qn_occupancy_grid& g = o->info;
-  const uint32_t cols = g.width * g.height;
-  if (!cols) return QN_OK;
-  const int64_t lo = std::max<int64_t>(iz_lo, 0), hi = std::min<int64_t>(iz_hi, (int64_t)g.depth - 1);
-  if (lo > hi) { std::fill(d2_out, d2_out + cols, (uint16_t)QN_DIST_FAR); return QN_OK; }      // no layer of the grid in the band
-  QN_KFCHK(s, hipSetDevice(qn_kf_int_device(s)));
-  const hipStream_t str = qn_kf_int_stream(s);
-  uint16_t* d_out = (uint16_t*)qn_kf_int_scratch(s, 1, sizeof(uint16_t) * (size_t)cols);
-  if (!d_out) return qn_kf_fail(s, "qn_kf_map_distance_slice: scratch allocation failed");
-  hipLaunchKernelGGL(k_md_slice, dim3((cols + MD_BLOCK - 1) / MD_BLOCK), dim3(MD_BLOCK), 0, str, cols, (const uint16_t*)d->d2.p, (uint32_t)lo, (uint32_t)hi, d_out);
-  QN_KFCHK(s, hipGetLastError());
-  return qn_kf_download(s, d2_out, d_out, sizeof(uint16_t) * (size_t)cols);
+  const DgLive L = dg_live(s);
+  if (!L.dist) return QN_ERR_NOT_READY;
+  return dg_slice<uint16_t, op_min>(s, "qn_kf_map_distance_slice", L.occ->info, L.dist->d2.p, iz_lo, iz_hi, (uint16_t)QN_DIST_FAR, d2_out);
 }
 
 extern "C" int qn_kf_map_distance_query(qn_kf_store* s, const double* xyz, uint32_t n, uint16_t* d2_out, uint8_t* class_out) {
   if (!s || !xyz || n == 0 || !d2_out || !class_out) return QN_ERR_INVALID_ARG;
-  const OccState* o = nullptr;
-  const DistState* d = md_live(s, &o);
-  if (!d) return QN_ERR_NOT_READY;
-  const qn_occupancy_grid& g = o->info;
-  if (!((size_t)g.width * g.height * g.depth)) {                     // an empty grid: every point is outside
+  const DgLive L = dg_live(s);
+  if (!L.dist) return QN_ERR_NOT_READY;
+  const qn_occupancy_grid& g = L.occ->info;
+  if (!dg_cells(g)) {                                                // an empty grid: every point is outside
     std::fill(d2_out, d2_out + n, (uint16_t)QN_DIST_FAR); memset(class_out, QN_DIST_OUTSIDE, n);
     return QN_OK;
   }
   QN_KFCHK(s, hipSetDevice(qn_kf_int_device(s)));
   const hipStream_t str = qn_kf_int_stream(s);
   // ---- scratch (0: the points, 1: their d2, 2: their classes)
-  double* d_xyz = (double*)qn_kf_int_scratch(s, 0, sizeof(double) * 3 * (size_t)n);
   uint16_t* d_d2 = (uint16_t*)qn_kf_int_scratch(s, 1, sizeof(uint16_t) * (size_t)n);
   uint8_t* d_cls = (uint8_t*)qn_kf_int_scratch(s, 2, n);
-  if (!d_xyz || !d_d2 || !d_cls) return qn_kf_fail(s, "qn_kf_map_distance_query: scratch allocation failed");
-  QN_KFCHK(s, hipMemcpyAsync(d_xyz, xyz, sizeof(double) * 3 * (size_t)n, hipMemcpyHostToDevice, str));
-  hipLaunchKernelGGL(k_md_query, dim3((n + MD_BLOCK - 1) / MD_BLOCK), dim3(MD_BLOCK), 0, str, n, (const double*)d_xyz, 1.0 / g.voxel, oc_grid(g), g.depth, (const uint16_t*)d->d2.p,
-                     (const uint8_t*)o->cls.p, d_d2, d_cls);
+  if (!d_d2 || !d_cls) return qn_kf_fail(s, "qn_kf_map_distance_query: scratch allocation failed");
+  DgPoints pts;
+  if (dg_points(s, "qn_kf_map_distance_query", xyz, n, &pts) != QN_OK) return QN_ERR_HIP;
+  hipLaunchKernelGGL(k_md_query, pts.grid, dim3(MD_BLOCK), 0, str, n, pts.xyz, 1.0 / g.voxel, oc_grid(g), g.depth, (const uint16_t*)L.dist->d2.p, (const uint8_t*)L.occ->cls.p, d_d2, d_cls);
   QN_KFCHK(s, hipGetLastError());
   QN_KFCHK(s, hipMemcpyAsync(d2_out, d_d2, sizeof(uint16_t) * (size_t)n, hipMemcpyDeviceToHost, str));
   QN_KFCHK(s, hipMemcpyAsync(class_out, d_cls, n, hipMemcpyDeviceToHost, str));

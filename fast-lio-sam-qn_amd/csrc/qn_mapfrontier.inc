@@ -14,7 +14,7 @@
 //             in the cache lines the block reads anyway, the y and z neighbours are other blocks' rows, served by L2; nothing is staged in LDS.  label = the own
 //             linear index for a frontier voxel, MF_NOLABEL otherwise; the voxel's tile flagged (a plain store of 1, every writer the same value); candidates
 //             and frontier voxels counted by block_count, the faces summed by block_sum.
-//   tile      k_mf_tile, one MF_T^3 tile per block, one voxel per lane; a block whose tile holds no frontier voxel returns after one load.  The tile's voxels
+//   tile      k_mf_tile, one DG_T^3 tile per block, one voxel per lane; a block whose tile holds no frontier voxel returns after one load.  The tile's voxels
 //             carry their place in the tile in LDS (a one-voxel rim of MF_NOLABEL spares the bounds tests) and fall to the smallest place among their 26
 //             neighbours and then to that voxel's own value (a pointer jump), in place, until nothing falls (__syncthreads_or).  Places order like linear
 //             indices, so every voxel ends at the smallest linear index of its component within the tile, and writes that.
@@ -29,22 +29,17 @@
 //             k_mf_rows folds into the rows: a region that holds most of the frontier would otherwise serialise every wave on one cache line (measured: 6 ms
 //             of 12.6 on 1.08e7 voxels).  k_mf_flatten and k_mf_costs fold a wave's voxels of one root or region the same way (wave_each_key).
 //             k_slot_fold and k_slot_max fold the statistics (the second and last synchronisation).
-//   getters   k_mf_list_flag / k_mf_list_pick: the stable compaction of qn_kf_map_occupancy_list.  k_mf_costs: one voxel per lane, a 64-bit atomicMin of
+//   getters   MfList, the predicate and the payload of the stable voxel list of qn_dense_grid.cuh (as qn_kf_map_occupancy_list).  k_mf_costs: one voxel per lane, a 64-bit atomicMin of
 //             (cost << 32) | linear index per region; the host unpacks it.
-// MF_T = 8 and MF_COPIES = 32 are untuned choices.  No scratch memory, no dynamically indexed private array, no floating point; plain vector stores and vector atomics only.
+// DG_T = 8 (the tile, its rim in LDS, the 26-neighbour walk and the index arithmetic: qn_dense_grid.cuh) and MF_COPIES = 32 are untuned choices.  No scratch memory, no dynamically indexed private array, no floating point; plain vector stores and vector atomics only.
 // Part of qn_staticmap.hip's translation unit (included after qn_maproute.inc): the result hangs on OccState beside the distance field and takes no slot.
 
 namespace {
 
-#define MF_T 8                                           // the tile's side: an untuned choice
-#define MF_TILE (MF_T * MF_T * MF_T)                     // voxels of a tile = lanes of a block of k_mf_tile
-#define MF_H (MF_T + 2)
-#define MF_LDS (MF_H * MF_H * MF_H)
 #define MF_BLOCK MO_BLOCK
 #define MF_NOLABEL 0xffffffffu
 #define MF_COPIES 32u                                    // copies of the regions' partial rows, a power of two: an untuned choice
 #define MF_PART_ROWS (1u << 18)                          // partial rows at most (16 MB of scratch), one copy of the table at least
-static_assert(MF_T == 8 && MF_TILE == 512, "k_mf_tile takes a lane's voxel from the bits of threadIdx.x");
 static_assert((MF_COPIES & (MF_COPIES - 1)) == 0 && MF_COPIES <= MF_PART_ROWS, "a block chooses its copy by a mask");
 static_assert(sizeof(qn_frontier_info) == 64 && sizeof(qn_frontier_params) == 32 && sizeof(qn_frontier_stats) == 48, "the records of include/qn_engine.h");
 
@@ -64,39 +59,35 @@ __device__ __forceinline__ uint32_t mf_faces(const uint8_t* __restrict__ cls, ui
 
 // one voxel per lane, linear order: label, the tile's flag; slots[3 b ..] = the block's candidates, frontier voxels and unknown faces
 __global__ void __launch_bounds__(MF_BLOCK) k_mf_mark(uint32_t cells, uint32_t W, uint32_t H, uint32_t D, const uint8_t* __restrict__ cls, uint32_t fmask, uint32_t umask,
-                                                      uint32_t edge, int32_t lo, int32_t hi, uint32_t tiles_x, uint32_t tiles_y, uint32_t* __restrict__ label,
+                                                      uint32_t edge, int32_t lo, int32_t hi, const DgTiles tiles, uint32_t* __restrict__ label,
                                                       uint32_t* __restrict__ tflag, uint32_t* __restrict__ slots) {
   const uint32_t i = blockIdx.x * MF_BLOCK + threadIdx.x;
   bool cand = false;
   uint32_t f = 0;
   if (i < cells) {
-    const uint32_t row = i / W, x = i - row * W, z = row / H, y = row - z * H;
-    cand = ((fmask >> cls[i]) & 1u) != 0 && (int32_t)z >= lo && (int32_t)z <= hi;
+    const DgIjk v = oc_ijk(i, W, H);
+    const uint32_t x = (uint32_t)v.x, y = (uint32_t)v.y, z = (uint32_t)v.z;
+    cand = ((fmask >> cls[i]) & 1u) != 0 && v.z >= lo && v.z <= hi;
     if (cand) f = mf_faces(cls, i, x, y, z, W, H, D, umask, edge);
     label[i] = f ? i : MF_NOLABEL;
-    if (f) tflag[((size_t)(z / MF_T) * tiles_y + y / MF_T) * tiles_x + x / MF_T] = 1u;
+    if (f) tflag[dg_tile_of(x, y, z, tiles)] = 1u;
   }
   block_count(slots + 3 * (size_t)blockIdx.x, cand, f != 0);
   block_sum(slots + 3 * (size_t)blockIdx.x + 2, f);
 }
 
-// the LDS position (with the rim) of the tile voxel at place l
-__device__ __forceinline__ uint32_t mf_pos(uint32_t l) { return ((l >> 6) + 1) * (MF_H * MF_H) + (((l >> 3) & 7u) + 1) * MF_H + (l & 7u) + 1; }
-
 // One tile per block, one voxel per lane: every frontier voxel of the tile to the smallest linear index of its component within the tile (see the file header)
-__global__ void __launch_bounds__(MF_TILE) k_mf_tile(uint32_t* __restrict__ label, uint32_t W, uint32_t H, uint32_t D, uint32_t tiles_x, uint32_t tiles_y,
-                                                     const uint32_t* __restrict__ tflag) {
-  __shared__ uint32_t c[MF_LDS];
+__global__ void __launch_bounds__(DG_TILE) k_mf_tile(uint32_t* __restrict__ label, uint32_t W, uint32_t H, uint32_t D, const DgTiles tiles, const uint32_t* __restrict__ tflag) {
+  __shared__ uint32_t c[DG_LDS];
   const uint32_t tile = blockIdx.x;
   if (tflag[tile] == 0) return;                                      // uniform over the block
-  const uint32_t bx = tile % tiles_x, by = (tile / tiles_x) % tiles_y, bz = tile / (tiles_x * tiles_y);
-  for (uint32_t j = threadIdx.x; j < MF_LDS; j += MF_TILE) c[j] = MF_NOLABEL;
+  const DgIjk o = dg_tile_origin(tile, tiles);                       // the tile's first voxel
+  for (uint32_t j = threadIdx.x; j < DG_LDS; j += DG_TILE) c[j] = MF_NOLABEL;
   __syncthreads();
-  const uint32_t lx = threadIdx.x & 7u, ly = (threadIdx.x >> 3) & 7u, lz = threadIdx.x >> 6;
-  const uint32_t gx = bx * MF_T + lx, gy = by * MF_T + ly, gz = bz * MF_T + lz;
-  const bool in = gx < W && gy < H && gz < D;
-  const uint32_t g = in ? (gz * H + gy) * W + gx : 0u;
-  const int me = (int)mf_pos(threadIdx.x);
+  const DgIjk v = o + dg_local(threadIdx.x);
+  const bool in = (uint32_t)v.x < W && (uint32_t)v.y < H && (uint32_t)v.z < D;
+  const uint32_t g = in ? dg_index(v, W, H) : 0u;
+  const int me = (int)dg_lane_pos(threadIdx.x);
   const bool front = in && label[g] != MF_NOLABEL;
   if (front) c[me] = threadIdx.x;
   __syncthreads();
@@ -105,20 +96,14 @@ __global__ void __launch_bounds__(MF_TILE) k_mf_tile(uint32_t* __restrict__ labe
     bool fell = false;
     if (front) {
       uint32_t best = cur;
-#pragma unroll
-      for (int dz = -1; dz <= 1; dz++)
-#pragma unroll
-        for (int dy = -1; dy <= 1; dy++)
-#pragma unroll
-          for (int dx = -1; dx <= 1; dx++)
-            if ((dx | dy | dz) != 0) best = min(best, c[me + dz * MF_H * MF_H + dy * MF_H + dx]);
-      best = c[mf_pos(best)];                                        // (a value names a voxel of the same component, whose own value is no larger)
+      dg_each_neighbour([&](int dx, int dy, int dz) { best = min(best, c[me + dg_step(dx, dy, dz)]); });
+      best = c[dg_lane_pos(best)];                                        // (a value names a voxel of the same component, whose own value is no larger)
       fell = best < cur;
       if (fell) { cur = best; c[me] = cur; }
     }
     if (!__syncthreads_or(fell)) break;
   }
-  if (front && cur != threadIdx.x) label[g] = ((bz * MF_T + (cur >> 6)) * H + by * MF_T + ((cur >> 3) & 7u)) * W + bx * MF_T + (cur & 7u);
+  if (front && cur != threadIdx.x) label[g] = dg_index(o + dg_local(cur), W, H);
 }
 
 // one voxel per lane: a frontier voxel on its tile's rim and its frontier neighbours in other tiles at smaller linear indices (every touching pair once); label[]
@@ -126,23 +111,18 @@ __global__ void __launch_bounds__(MF_TILE) k_mf_tile(uint32_t* __restrict__ labe
 __global__ void __launch_bounds__(MF_BLOCK) k_mf_merge(uint32_t cells, uint32_t W, uint32_t H, uint32_t D, uint32_t* label) {
   const uint32_t i = blockIdx.x * MF_BLOCK + threadIdx.x;
   if (i >= cells || uf_load(label + i) == MF_NOLABEL) return;
-  const uint32_t row = i / W;
-  const int x = (int)(i - row * W), z = (int)(row / H), y = (int)(row - (uint32_t)z * H);
-  const int lx = x & 7, ly = y & 7, lz = z & 7;
-  if (lx != 0 && lx != 7 && ly != 0 && ly != 7 && lz != 0 && lz != 7) return;
-#pragma unroll
-  for (int dz = -1; dz <= 1; dz++)
-#pragma unroll
-    for (int dy = -1; dy <= 1; dy++)
-#pragma unroll
-      for (int dx = -1; dx <= 1; dx++) {
-        if (!(dz < 0 || (dz == 0 && (dy < 0 || (dy == 0 && dx < 0))))) continue;      // the 13 neighbours at smaller linear indices
-        const int nx = x + dx, ny = y + dy, nz = z + dz;
-        if (nx < 0 || nx >= (int)W || ny < 0 || ny >= (int)H || nz < 0 || nz >= (int)D) continue;
-        if ((nx >> 3) == (x >> 3) && (ny >> 3) == (y >> 3) && (nz >> 3) == (z >> 3)) continue;      // the same tile: k_mf_tile joined them
-        const uint32_t j = ((uint32_t)nz * H + (uint32_t)ny) * W + (uint32_t)nx;
-        if (uf_load(label + j) != MF_NOLABEL) uf_unite_min(label, i, j);
-      }
+  const DgIjk v = oc_ijk(i, W, H);
+  const int x = v.x, y = v.y, z = v.z;
+  const uint32_t lx = dg_in_tile((uint32_t)x), ly = dg_in_tile((uint32_t)y), lz = dg_in_tile((uint32_t)z), last = DG_T - 1;
+  if (lx != 0 && lx != last && ly != 0 && ly != last && lz != 0 && lz != last) return;
+  dg_each_neighbour([&](int dx, int dy, int dz) {
+    if (!(dz < 0 || (dz == 0 && (dy < 0 || (dy == 0 && dx < 0))))) return;        // the 13 neighbours at smaller linear indices
+    const int nx = x + dx, ny = y + dy, nz = z + dz;
+    if (nx < 0 || nx >= (int)W || ny < 0 || ny >= (int)H || nz < 0 || nz >= (int)D) return;
+    if (dg_tile_coord(nx) == dg_tile_coord(x) && dg_tile_coord(ny) == dg_tile_coord(y) && dg_tile_coord(nz) == dg_tile_coord(z)) return;      // the same tile: k_mf_tile joined them
+    const uint32_t j = dg_index((uint32_t)nx, (uint32_t)ny, (uint32_t)nz, W, H);
+    if (uf_load(label + j) != MF_NOLABEL) uf_unite_min(label, i, j);
+  });
 }
 
 // one voxel per lane: label = the root; aux[root] counts the component's voxels, the voxels of a wave that share a root in one atomicAdd
@@ -215,8 +195,8 @@ __global__ void __launch_bounds__(MF_BLOCK) k_mf_relabel(uint32_t cells, uint32_
   }
   int x = 0, y = 0, z = 0, f = 0;
   if (in) {
-    const uint32_t row = i / W;
-    x = (int)(i - row * W); z = (int)(row / H); y = (int)(row - (uint32_t)z * H);
+    const DgIjk v = oc_ijk(i, W, H);
+    x = v.x; y = v.y; z = v.z;
     f = (int)mf_faces(cls, i, (uint32_t)x, (uint32_t)y, (uint32_t)z, W, H, D, umask, edge);
   }
   wave_each_key(in, k, [&](int32_t k0, int, unsigned long long same) {      // one trip per region the wave holds
@@ -254,21 +234,12 @@ __global__ void __launch_bounds__(MF_BLOCK) k_mf_rows(uint32_t R, uint32_t copie
   o->faces = faces; o->reserved = 0; o->sum[0] = s0; o->sum[1] = s1; o->sum[2] = s2;
 }
 
-// one voxel per lane: the block's frontier voxels into its slot (what k_scan_rows goes on from)
-__global__ void __launch_bounds__(MF_BLOCK) k_mf_list_flag(uint32_t cells, const int32_t* __restrict__ label, uint32_t* __restrict__ blk) {
-  const uint32_t i = blockIdx.x * MF_BLOCK + threadIdx.x;
-  block_count(blk + blockIdx.x, i < cells && label[i] != QN_FRONTIER_NONE);
-}
-
-// the block's frontier voxels, in linear order, to ijk / lab at off[block] ..
-__global__ void __launch_bounds__(MF_BLOCK) k_mf_list_pick(uint32_t cells, const int32_t* __restrict__ label, const uint32_t* __restrict__ off, uint32_t W, uint32_t H,
-                                                           int32_t* __restrict__ ijk, int32_t* __restrict__ lab) {
-  const uint32_t i = blockIdx.x * MF_BLOCK + threadIdx.x;
-  const int32_t k = i < cells ? label[i] : QN_FRONTIER_NONE;
-  const bool keep = k != QN_FRONTIER_NONE;
-  const size_t j = block_rank(keep, off[blockIdx.x]);
-  if (keep) { oc_ijk(i, W, H, ijk + 3 * j); lab[j] = k; }
-}
+// the voxel list (k_dg_list_flag / k_dg_list_pick: qn_dense_grid.cuh): the frontier voxels, to ijk / lab
+struct MfList {
+  const int32_t* label; uint32_t W, H; DgIjk* ijk; int32_t* lab;
+  __device__ bool keep(uint32_t i) const { return label[i] != QN_FRONTIER_NONE; }
+  __device__ void put(uint32_t i, size_t j) const { ijk[j] = oc_ijk(i, W, H); lab[j] = label[i]; }
+};
 
 // one voxel per lane: a region voxel the route field reaches offers (cost << 32) | linear index to its region; cols = W H, planar: a voxel reads its column
 __global__ void __launch_bounds__(MF_BLOCK) k_mf_costs(uint32_t cells, uint32_t cols, uint32_t planar, const int32_t* __restrict__ label, const uint32_t* __restrict__ cost,
@@ -298,11 +269,15 @@ struct FrontierState {
 
 void mf_end(FrontierState* f) { if (f) f->live = false; }
 
-// the live occupancy result and its live frontier result, or nullptr
-const FrontierState* mf_live(qn_kf_store* s, const OccState** occ) {
-  const OccState* o = oc_live(s);
-  *occ = o;
-  return o && o->frontier && o->frontier->live ? o->frontier.get() : nullptr;
+// the lookup every entry point behind qn_kf_map_occupancy starts with (declared in qn_dense_grid.cuh; here all four states are complete)
+DgLive dg_live(qn_kf_store* s) {
+  DgLive L = {nullptr, nullptr, nullptr, nullptr};
+  const StaticState* st = (const StaticState*)qn_kf_int_ext(s, QN_KF_INT_EXT_STATIC);
+  if (st && st->occ && st->occ->live) L.occ = st->occ.get();
+  if (L.occ && L.occ->dist && L.occ->dist->live) L.dist = L.occ->dist.get();
+  if (L.dist && L.dist->route && L.dist->route->live) L.route = L.dist->route.get();
+  if (L.occ && L.occ->frontier && L.occ->frontier->live) L.frontier = L.occ->frontier.get();
+  return L;
 }
 
 }  // namespace
@@ -320,10 +295,10 @@ extern "C" int qn_kf_map_frontiers(qn_kf_store* s, const qn_frontier_params* par
   if (P.free_mask == 0 || (P.free_mask & ~7u) || P.unknown_mask == 0 || (P.unknown_mask & ~7u) || (P.free_mask & P.unknown_mask) || P.edge_unknown > 1 || P.min_size == 0 ||
       P.iz_lo > P.iz_hi || P.reserved[0] != 0 || P.reserved[1] != 0)
     return QN_ERR_INVALID_ARG;
-  OccState* o = oc_live_mut(s);
+  OccState* o = dg_mut(dg_live(s).occ);
   if (!o) return QN_ERR_NOT_READY;
   const qn_occupancy_grid& g = o->info;
-  const uint32_t W = g.width, H = g.height, D = g.depth, cells = W * H * D, cb = (cells + MF_BLOCK - 1) / MF_BLOCK;
+  const uint32_t W = g.width, H = g.height, D = g.depth, cells = dg_cells(g), cb = dg_blocks(cells);
   qn_frontier_stats r;
   memset(&r, 0, sizeof(r));
   if (!o->frontier) o->frontier.reset(new (std::nothrow) FrontierState());
@@ -332,15 +307,15 @@ extern "C" int qn_kf_map_frontiers(qn_kf_store* s, const qn_frontier_params* par
   if (cells) {
     QN_KFCHK(s, hipSetDevice(qn_kf_int_device(s)));
     const hipStream_t str = qn_kf_int_stream(s);
-    const uint32_t tx = (W + MF_T - 1) / MF_T, ty = (H + MF_T - 1) / MF_T, tz = (D + MF_T - 1) / MF_T, tiles = tx * ty * tz;
+    const DgTiles T = dg_tiles(W, H, D);
     // ---- a larger label volume is allocated beside the previous one, which goes only once the new one is there
     DevBuf<int32_t> nl;
-    if (cells > st->label.cap && !nl.grow(s, cells)) return QN_ERR_HIP;
+    if (!st->label.grow_beside(s, cells, nl)) return QN_ERR_HIP;
     // ---- scratch (1: the transient word per voxel - a root's size, then its number; 2: the tiles' flags; 3: the blocks' count slots, three words each; 4: the
     //      blocks' kept roots, their offsets and the total, then the blocks' largest sizes; 5: the folded sums - candidates, frontier, faces, components,
     //      too small, largest, region voxels, rejected voxels)
     uint32_t* d_aux = (uint32_t*)qn_kf_int_scratch(s, 1, sizeof(uint32_t) * (size_t)cells);
-    uint32_t* d_tflag = (uint32_t*)qn_kf_int_scratch(s, 2, sizeof(uint32_t) * (size_t)tiles);
+    uint32_t* d_tflag = (uint32_t*)qn_kf_int_scratch(s, 2, sizeof(uint32_t) * (size_t)T.n);
     uint32_t* d_slots = (uint32_t*)qn_kf_int_scratch(s, 3, sizeof(uint32_t) * 3 * (size_t)cb);
     uint32_t* d_blk = (uint32_t*)qn_kf_int_scratch(s, 4, sizeof(uint32_t) * (3 * (size_t)cb + 1));
     uint32_t* d_sums = (uint32_t*)qn_kf_int_scratch(s, 5, 32);
@@ -349,16 +324,16 @@ extern "C" int qn_kf_map_frontiers(qn_kf_store* s, const qn_frontier_params* par
     uint32_t* d_off = d_blk + cb; uint32_t* d_mslots = d_blk + 2 * (size_t)cb + 1;
     // ---- from here on the previous result is gone
     st->live = false;
-    if (nl.p) st->label.swap(nl);
+    st->label.adopt(nl);
     uint32_t* lab = (uint32_t*)st->label.p;
     const uint8_t* cls = (const uint8_t*)o->cls.p;
-    const int32_t lo = std::max<int32_t>(P.iz_lo, 0), hi = (int32_t)std::min<int64_t>(P.iz_hi, (int64_t)D - 1);
+    const DgBand band = dg_band(P.iz_lo, P.iz_hi, D);
     QN_KFCHK(s, hipMemsetAsync(d_aux, 0, sizeof(uint32_t) * (size_t)cells, str));
-    QN_KFCHK(s, hipMemsetAsync(d_tflag, 0, sizeof(uint32_t) * (size_t)tiles, str));
+    QN_KFCHK(s, hipMemsetAsync(d_tflag, 0, sizeof(uint32_t) * (size_t)T.n, str));
     // ---- mark, label: tile, merge, flatten
-    hipLaunchKernelGGL(k_mf_mark, dim3(cb), dim3(MF_BLOCK), 0, str, cells, W, H, D, cls, P.free_mask, P.unknown_mask, P.edge_unknown, lo, hi, tx, ty, lab, d_tflag, d_slots);
+    hipLaunchKernelGGL(k_mf_mark, dim3(cb), dim3(MF_BLOCK), 0, str, cells, W, H, D, cls, P.free_mask, P.unknown_mask, P.edge_unknown, band.lo, band.hi, T, lab, d_tflag, d_slots);
     hipLaunchKernelGGL((k_slot_fold<uint32_t, 3>), dim3(1), dim3(MO_SCAN_BLOCK), 0, str, (const uint32_t*)d_slots, cb, d_sums);
-    hipLaunchKernelGGL(k_mf_tile, dim3(tiles), dim3(MF_TILE), 0, str, lab, W, H, D, tx, ty, (const uint32_t*)d_tflag);
+    hipLaunchKernelGGL(k_mf_tile, dim3(T.n), dim3(DG_TILE), 0, str, lab, W, H, D, T, (const uint32_t*)d_tflag);
     hipLaunchKernelGGL(k_mf_merge, dim3(cb), dim3(MF_BLOCK), 0, str, cells, W, H, D, lab);
     hipLaunchKernelGGL(k_mf_flatten, dim3(cb), dim3(MF_BLOCK), 0, str, cells, lab, d_aux);
     // ---- number: the kept roots ranked in ascending index
@@ -378,18 +353,17 @@ extern "C" int qn_kf_map_frontiers(qn_kf_store* s, const qn_frontier_params* par
     const uint32_t rows = copies * std::max<uint32_t>(R, 1);
     qn_frontier_info* d_part = (qn_frontier_info*)qn_kf_int_scratch(s, 6, sizeof(qn_frontier_info) * (size_t)rows);
     if (!d_part) return qn_kf_fail(s, "qn_kf_map_frontiers: scratch allocation failed");
-    hipLaunchKernelGGL(k_mf_rows_init, dim3((rows + MF_BLOCK - 1) / MF_BLOCK), dim3(MF_BLOCK), 0, str, rows, d_part);
+    hipLaunchKernelGGL(k_mf_rows_init, dim3(dg_blocks(rows)), dim3(MF_BLOCK), 0, str, rows, d_part);
     hipLaunchKernelGGL(k_mf_pick, dim3(cb), dim3(MF_BLOCK), 0, str, cells, (const uint32_t*)lab, d_aux, P.min_size, (const uint32_t*)d_off, st->info.p);
     hipLaunchKernelGGL(k_mf_relabel, dim3(cb), dim3(MF_BLOCK), 0, str, cells, W, H, D, cls, P.unknown_mask, P.edge_unknown, st->label.p, (const uint32_t*)d_aux, R, copies - 1,
                        d_part, d_slots);
-    if (R) hipLaunchKernelGGL(k_mf_rows, dim3((R + MF_BLOCK - 1) / MF_BLOCK), dim3(MF_BLOCK), 0, str, R, copies, (const qn_frontier_info*)d_part, st->info.p);
+    if (R) hipLaunchKernelGGL(k_mf_rows, dim3(dg_blocks(R)), dim3(MF_BLOCK), 0, str, R, copies, (const qn_frontier_info*)d_part, st->info.p);
     hipLaunchKernelGGL((k_slot_fold<uint32_t, 2>), dim3(1), dim3(MO_SCAN_BLOCK), 0, str, (const uint32_t*)d_slots, cb, d_sums + 6);
     QN_KFCHK(s, hipGetLastError());
     QN_KFCHK(s, hipMemcpyAsync(h, d_sums, 32, hipMemcpyDeviceToHost, str));
     QN_KFCHK(s, hipStreamSynchronize(str));                  // sync 2, the last: the statistics
     r.candidates = h[0]; r.frontier = h[1]; r.unknown_faces = h[2]; r.components = h[3]; r.too_small = h[4]; r.largest = h[5]; r.region_voxels = h[6];
-    r.rejected_voxels = h[7]; r.regions = R;
-    r.rounds = 1;
+    r.rejected_voxels = h[7]; r.regions = R; r.rounds = 1;
   }
   st->params = P; st->stats = r;
   st->live = true;
@@ -399,52 +373,46 @@ extern "C" int qn_kf_map_frontiers(qn_kf_store* s, const qn_frontier_params* par
 
 extern "C" int qn_kf_map_frontier_grid(qn_kf_store* s, qn_occupancy_grid* info_out, qn_frontier_params* params_out, int32_t* label_out) {
   if (!s || !info_out || !params_out) return QN_ERR_INVALID_ARG;
-  const OccState* o = nullptr;
-  const FrontierState* f = mf_live(s, &o);
-  if (!f) return QN_ERR_NOT_READY;
-  const qn_occupancy_grid& g = o->info;
-  const size_t cells = (size_t)g.width * g.height * g.depth;
-  *info_out = g; *params_out = f->params;
+  const DgLive L = dg_live(s);
+  if (!L.frontier) return QN_ERR_NOT_READY;
+  const size_t cells = dg_cells(L.occ->info);
+  *info_out = L.occ->info; *params_out = L.frontier->params;
   if (!cells || !label_out) return QN_OK;
-  return qn_kf_download(s, label_out, f->label.p, sizeof(int32_t) * cells);
+  return qn_kf_download(s, label_out, L.frontier->label.p, sizeof(int32_t) * cells);
 }
 
 extern "C" int qn_kf_map_frontier_regions(qn_kf_store* s, qn_frontier_info* info_out, uint32_t capacity, uint32_t* count_out) {
   if (!s || !count_out || (!info_out && capacity)) return QN_ERR_INVALID_ARG;
-  const OccState* o = nullptr;
-  const FrontierState* f = mf_live(s, &o);
-  if (!f) return QN_ERR_NOT_READY;
-  const uint32_t R = f->stats.regions;
+  const DgLive L = dg_live(s);
+  if (!L.frontier) return QN_ERR_NOT_READY;
+  const uint32_t R = L.frontier->stats.regions;
   *count_out = R;
   if (capacity < R) return QN_ERR_CAPACITY;
   if (!R) return QN_OK;
-  return qn_kf_download(s, info_out, f->info.p, sizeof(qn_frontier_info) * (size_t)R);
+  return qn_kf_download(s, info_out, L.frontier->info.p, sizeof(qn_frontier_info) * (size_t)R);
 }
 
 extern "C" int qn_kf_map_frontier_list(qn_kf_store* s, int32_t* ijk_out, int32_t* label_out, uint32_t capacity, uint32_t* count_out) {
   if (!s || !count_out || ((!ijk_out || !label_out) && capacity)) return QN_ERR_INVALID_ARG;
-  const OccState* o = nullptr;
-  const FrontierState* f = mf_live(s, &o);
-  if (!f) return QN_ERR_NOT_READY;
-  const uint32_t n = f->stats.frontier;
+  const DgLive L = dg_live(s);
+  if (!L.frontier) return QN_ERR_NOT_READY;
+  const uint32_t n = L.frontier->stats.frontier;
   *count_out = n;
   if (capacity < n) return QN_ERR_CAPACITY;
   if (!n) return QN_OK;
-  const qn_occupancy_grid& g = o->info;
-  const uint32_t cells = g.width * g.height * g.depth, nb = (cells + MF_BLOCK - 1) / MF_BLOCK;
+  const qn_occupancy_grid& g = L.occ->info;
+  const uint32_t cells = dg_cells(g);
   QN_KFCHK(s, hipSetDevice(qn_kf_int_device(s)));
   const hipStream_t str = qn_kf_int_stream(s);
-  // ---- scratch (3: the blocks' counts, then their offsets and the total; 1: the voxels; 2: their labels)
-  uint32_t* d_blk = (uint32_t*)qn_kf_int_scratch(s, 3, sizeof(uint32_t) * (2 * (size_t)nb + 1));
-  int32_t* d_ijk = (int32_t*)qn_kf_int_scratch(s, 1, sizeof(int32_t) * 3 * (size_t)n);
+  // ---- scratch (3: dg_list_count's; 1: the voxels; 2: their labels)
+  DgIjk* d_ijk = (DgIjk*)qn_kf_int_scratch(s, 1, sizeof(DgIjk) * (size_t)n);
   int32_t* d_lab = (int32_t*)qn_kf_int_scratch(s, 2, sizeof(int32_t) * (size_t)n);
-  if (!d_blk || !d_ijk || !d_lab) return qn_kf_fail(s, "qn_kf_map_frontier_list: scratch allocation failed");
-  uint32_t* d_off = d_blk + nb;
-  hipLaunchKernelGGL(k_mf_list_flag, dim3(nb), dim3(MF_BLOCK), 0, str, cells, (const int32_t*)f->label.p, d_blk);
-  hipLaunchKernelGGL(k_scan_rows, dim3(1), dim3(MO_SCAN_BLOCK), 0, str, (const uint32_t*)d_blk, nb, d_off, d_off + nb);
-  hipLaunchKernelGGL(k_mf_list_pick, dim3(nb), dim3(MF_BLOCK), 0, str, cells, (const int32_t*)f->label.p, (const uint32_t*)d_off, g.width, g.height, d_ijk, d_lab);
+  const MfList list = {L.frontier->label.p, g.width, g.height, d_ijk, d_lab};
+  const uint32_t* d_off = d_ijk && d_lab ? dg_list_count(s, cells, list) : nullptr;
+  if (!d_off) return qn_kf_fail(s, "qn_kf_map_frontier_list: scratch allocation failed");
+  dg_list_pick(s, cells, list, d_off);
   QN_KFCHK(s, hipGetLastError());
-  QN_KFCHK(s, hipMemcpyAsync(ijk_out, d_ijk, sizeof(int32_t) * 3 * (size_t)n, hipMemcpyDeviceToHost, str));
+  QN_KFCHK(s, hipMemcpyAsync(ijk_out, d_ijk, sizeof(DgIjk) * (size_t)n, hipMemcpyDeviceToHost, str));
   QN_KFCHK(s, hipMemcpyAsync(label_out, d_lab, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, str));
   QN_KFCHK(s, hipStreamSynchronize(str));
   return QN_OK;
@@ -452,16 +420,12 @@ extern "C" int qn_kf_map_frontier_list(qn_kf_store* s, int32_t* ijk_out, int32_t
 
 extern "C" int qn_kf_map_frontier_costs(qn_kf_store* s, uint32_t* cost_out, int32_t* ijk_out) {
   if (!s || !cost_out || !ijk_out) return QN_ERR_INVALID_ARG;
-  const OccState* o = nullptr;
-  const FrontierState* f = mf_live(s, &o);
-  if (!f) return QN_ERR_NOT_READY;
-  const DistState* d = o->dist && o->dist->live ? o->dist.get() : nullptr;
-  const RouteState* rt = d && d->route && d->route->live ? d->route.get() : nullptr;
-  if (!rt) return QN_ERR_NOT_READY;
-  const uint32_t R = f->stats.regions;
+  const DgLive L = dg_live(s);
+  if (!L.frontier || !L.route) return QN_ERR_NOT_READY;
+  const uint32_t R = L.frontier->stats.regions;
   if (!R) return QN_OK;
-  const qn_occupancy_grid& g = o->info;
-  const uint32_t cols = g.width * g.height, cells = cols * g.depth;
+  const qn_occupancy_grid& g = L.occ->info;
+  const uint32_t cols = dg_cols(g), cells = dg_cells(g);
   QN_KFCHK(s, hipSetDevice(qn_kf_int_device(s)));
   const hipStream_t str = qn_kf_int_stream(s);
   // ---- scratch (1: the regions' keys) and their pinned mirror
@@ -469,15 +433,16 @@ extern "C" int qn_kf_map_frontier_costs(qn_kf_store* s, uint32_t* cost_out, int3
   unsigned long long* h = (unsigned long long*)qn_kf_int_pinned(s, sizeof(unsigned long long) * (size_t)R);
   if (!d_key || !h) return qn_kf_fail(s, "qn_kf_map_frontier_costs: scratch allocation failed");
   QN_KFCHK(s, hipMemsetAsync(d_key, 0xff, sizeof(unsigned long long) * (size_t)R, str));
-  hipLaunchKernelGGL(k_mf_costs, dim3((cells + MF_BLOCK - 1) / MF_BLOCK), dim3(MF_BLOCK), 0, str, cells, cols, rt->params.planar, (const int32_t*)f->label.p,
-                     (const uint32_t*)rt->cost.p, d_key);
+  hipLaunchKernelGGL(k_mf_costs, dim3(dg_blocks(cells)), dim3(MF_BLOCK), 0, str, cells, cols, L.route->params.planar, (const int32_t*)L.frontier->label.p,
+                     (const uint32_t*)L.route->cost.p, d_key);
   QN_KFCHK(s, hipGetLastError());
   QN_KFCHK(s, hipMemcpyAsync(h, d_key, sizeof(unsigned long long) * (size_t)R, hipMemcpyDeviceToHost, str));
   QN_KFCHK(s, hipStreamSynchronize(str));
   for (uint32_t k = 0; k < R; k++) {
     const bool none = h[k] == ~0ull;
     cost_out[k] = none ? QN_ROUTE_UNREACHED : (uint32_t)(h[k] >> 32);
-    oc_ijk(none ? 0u : (uint32_t)(h[k] & 0xffffffffull), g.width, g.height, ijk_out + 3 * (size_t)k);
+    const DgIjk v = oc_ijk(none ? 0u : (uint32_t)(h[k] & 0xffffffffull), g.width, g.height);
+    ijk_out[3 * (size_t)k] = v.x; ijk_out[3 * (size_t)k + 1] = v.y; ijk_out[3 * (size_t)k + 2] = v.z;
   }
   return QN_OK;
 }

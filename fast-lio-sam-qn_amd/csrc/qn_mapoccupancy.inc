@@ -14,10 +14,10 @@
 //             voxels further out are added to lane by lane; a lane stops after its last miss, n - shell steps, since the end voxel is known without walking.
 //   classify  k_oc_classify, one voxel per lane: the class byte, the three class counts (block_count) and the block's hit and miss sums (u64, block_sum) into
 //             slots, k_slot_fold adds them up.  One host read.
-//   list      k_oc_list_flag / k_scan_rows / k_oc_list_pick: the count, scan and rank idiom of qn_map_compact.cuh over the voxels in linear order, stable.
-//   slice     k_oc_slice, one column per lane.
-//   grid      what every field over the dense grid shares (qn_mapdistance.inc, qn_maproute.inc, qn_mapfrontier.inc, included behind this file): oc_grid, oc_voxel -
-//             the one world-point-to-cell quantisation - and oc_ijk, the index split of the lists; on the host oc_live and oc_live_mut.
+//   list      OcList, the predicate and the payload of the stable voxel list of qn_dense_grid.cuh (k_dg_list_flag / k_scan_rows / k_dg_list_pick).
+//   slice     the largest class over a band of layers: k_dg_slice<uint8_t, op_max> of qn_dense_grid.cuh, one column per lane.
+// The grid itself - OcGrid, the index arithmetic, the fixed point's OC_S and OC_COORD_LIMIT, the lookup of the live results - is qn_dense_grid.cuh's, shared with
+// the fields over it (qn_mapdistance.inc, qn_maproute.inc, qn_mapfrontier.inc, included behind this file).
 // Host synchronisations of qn_kf_map_occupancy: two - the extent, the counts.  Integer atomics only, no scratch memory, no dynamically indexed private array.
 // Part of qn_staticmap.hip's translation unit (included at its end), the unit that turns a list with poses into per-record ray evidence: the results hang on
 // that unit's StaticState and take no slot of their own.  They do not depend on the map slot.
@@ -27,9 +27,7 @@
 namespace {
 
 #define OC_BLOCK MO_BLOCK
-#define OC_S 10                                          // fractional bits of the fixed point
-#define OC_ONE (1 << OC_S)
-#define OC_COORD_LIMIT 1048576.0                         // 2^20 voxels
+#define OC_ONE (1 << OC_S)                               // (OC_S, OC_COORD_LIMIT: qn_dense_grid.cuh)
 #define OC_MAX_SIDE (1u << 15)
 #define OC_RAY 0
 #define OC_NONFINITE 1
@@ -38,42 +36,6 @@ namespace {
 #define OC_CAPACITY 4
 
 struct OcEntry { const float4* pts; uint32_t n, b0; double P[12]; };          // records, first block slot, the pose's three rows; 112 bytes
-struct OcGrid { int32_t minc[3]; uint32_t W, H, cells; };
-
-OcGrid oc_grid(const qn_occupancy_grid& g) {
-  OcGrid G;
-  memset(&G, 0, sizeof(G));
-  for (int k = 0; k < 3; k++) G.minc[k] = g.minc[k];
-  G.W = g.width; G.H = g.height; G.cells = g.width * g.height * g.depth;
-  return G;
-}
-
-// The dense grid's cell of world point i, for every field over the grid (the distance and route queries, goals and starts), by the map's own quantisation: f64,
-// every operation rounded on its own, half to even; false for a point that is not finite, 2^20 voxels or more from the origin, or outside the field of depth
-// Df.  Planar: x and y choose the column, z must only pass the limit.
-__device__ __forceinline__ bool oc_voxel(const double* __restrict__ xyz, uint32_t i, double inv, const OcGrid& G, uint32_t Df, uint32_t planar, uint32_t* cx, uint32_t* cy,
-                                         uint32_t* cz) {
-  const uint32_t side[3] = {G.W, G.H, Df};
-  long long c[3];
-  bool ok = true;
-#pragma unroll
-  for (int k = 0; k < 3; k++) {
-    const double t = xyz[3 * (size_t)i + k] * inv;
-    const bool in = fabs(t) < OC_COORD_LIMIT;                       // (a NaN fails the comparison, an infinity too)
-    c[k] = in ? (((long long)rint(t * 1024.0)) >> OC_S) - G.minc[k] : -1;
-    if (k == 2 && planar && in) c[k] = 0;
-    ok = ok && in && c[k] >= 0 && c[k] < (long long)side[k];
-  }
-  *cx = (uint32_t)c[0]; *cy = (uint32_t)c[1]; *cz = (uint32_t)c[2];
-  return ok;
-}
-
-// out[0 .. 3) = the voxel (x, y, z) at linear index i of a grid W wide and H high
-__host__ __device__ inline void oc_ijk(uint32_t i, uint32_t W, uint32_t H, int32_t* out) {
-  const uint32_t row = i / W;
-  out[0] = (int32_t)(i - row * W); out[1] = (int32_t)(row % H); out[2] = (int32_t)(row / H);
-}
-
 // the quantisation, shared by the two passes: the status of record p under pose rows P, and for a ray its fixed-point ends
 __device__ __forceinline__ int oc_ray(const float4 p, const double* __restrict__ P, double inv, float lo2, float hi2, int32_t (&A)[3], int32_t (&B)[3]) {
   if (!(isfinite(p.x) && isfinite(p.y) && isfinite(p.z))) return OC_NONFINITE;
@@ -196,30 +158,12 @@ __global__ void __launch_bounds__(OC_BLOCK) k_oc_classify(uint32_t cells, const 
   block_sum(tslots + 2 * (size_t)blockIdx.x, h, m);
 }
 
-// one voxel per lane: the block's voxels whose class bit is in the mask into its slot (what k_scan_rows goes on from)
-__global__ void __launch_bounds__(MO_BLOCK) k_oc_list_flag(uint32_t cells, const uint8_t* __restrict__ cls, uint32_t mask, uint32_t* __restrict__ blk) {
-  const uint32_t i = blockIdx.x * MO_BLOCK + threadIdx.x;
-  block_count(blk + blockIdx.x, i < cells && ((mask >> cls[i]) & 1u) != 0);
-}
-
-// the block's listed voxels, in linear order, to ijk / hits / misses at off[block] ..
-__global__ void __launch_bounds__(MO_BLOCK) k_oc_list_pick(uint32_t cells, const uint8_t* __restrict__ cls, uint32_t mask, const uint32_t* __restrict__ off,
-                                                           const uint32_t* __restrict__ hits, const uint32_t* __restrict__ misses, uint32_t W, uint32_t H,
-                                                           int32_t* __restrict__ ijk, uint32_t* __restrict__ h_out, uint32_t* __restrict__ m_out) {
-  const uint32_t i = blockIdx.x * MO_BLOCK + threadIdx.x;
-  const bool keep = i < cells && ((mask >> cls[i]) & 1u) != 0;
-  const size_t j = block_rank(keep, off[blockIdx.x]);
-  if (keep) { oc_ijk(i, W, H, ijk + 3 * j); h_out[j] = hits[i]; m_out[j] = misses[i]; }
-}
-
-// one column per lane: the largest class over the layers lo .. hi (2 occupied, else 1 free, else 0)
-__global__ void __launch_bounds__(OC_BLOCK) k_oc_slice(uint32_t cols, const uint8_t* __restrict__ cls, uint32_t lo, uint32_t hi, uint8_t* __restrict__ out) {
-  const uint32_t c = blockIdx.x * OC_BLOCK + threadIdx.x;
-  if (c >= cols) return;
-  uint32_t v = 0;
-  for (uint32_t z = lo; z <= hi; z++) v = max(v, (uint32_t)cls[(size_t)z * cols + c]);
-  out[c] = (uint8_t)v;
-}
+// the voxel list (k_dg_list_flag / k_dg_list_pick: qn_dense_grid.cuh): the voxels whose class bit is in the mask, to ijk / h_out / m_out
+struct OcList {
+  const uint8_t* cls; uint32_t mask; const uint32_t *hits, *misses; uint32_t W, H; DgIjk* ijk; uint32_t *h_out, *m_out;
+  __device__ bool keep(uint32_t i) const { return ((mask >> cls[i]) & 1u) != 0; }
+  __device__ void put(uint32_t i, size_t j) const { ijk[j] = oc_ijk(i, W, H); h_out[j] = hits[i]; m_out[j] = misses[i]; }
+};
 
 // ---------------------------------------------------------------------------------------------------------------- host side
 // The occupancy results of the latest successful call (a member of the unit's StaticState)
@@ -233,12 +177,6 @@ struct OccState {
 };
 void md_end(DistState*);                                 // (qn_mapdistance.inc) a new occupancy result ends the field of the previous one; its buffers stay
 void mf_end(FrontierState*);                             // (qn_mapfrontier.inc) and the frontier regions of the previous one
-
-const OccState* oc_live(qn_kf_store* s) {
-  const StaticState* st = (const StaticState*)qn_kf_int_ext(s, QN_KF_INT_EXT_STATIC);
-  return st && st->occ && st->occ->live ? st->occ.get() : nullptr;
-}
-OccState* oc_live_mut(qn_kf_store* s) { return const_cast<OccState*>(oc_live(s)); }      // for the calls that hang a result of their own on it
 
 }  // namespace
 
@@ -268,7 +206,7 @@ extern "C" int qn_kf_map_occupancy(qn_kf_store* s, const int32_t* ids, const dou
     const float4* pts = qn_kf_int_keyframe(s, ids[e], &n);
     ent[e].pts = pts; ent[e].n = n; ent[e].b0 = (uint32_t)tiles;
     memcpy(ent[e].P, poses16 + 16 * (size_t)e, sizeof(double) * 12);
-    total += n; tiles += (n + OC_BLOCK - 1) / OC_BLOCK;
+    total += n; tiles += dg_blocks(n);
     if (total > 0xFFFFFFFFull) return QN_ERR_CAPACITY;
   }
   QN_KFCHK(s, hipSetDevice(qn_kf_int_device(s)));
@@ -331,7 +269,7 @@ extern "C" int qn_kf_map_occupancy(qn_kf_store* s, const int32_t* ids, const dou
   }
   const OcGrid G = oc_grid(info);
   r.width = info.width; r.height = info.height; r.depth = info.depth;
-  const uint32_t cells = G.cells, cb = (cells + OC_BLOCK - 1) / OC_BLOCK;
+  const uint32_t cells = G.cells, cb = dg_blocks(cells);
   // ---- from here on the previous result is gone
   st->live = false;
   if (cells) {
@@ -368,10 +306,10 @@ extern "C" int qn_kf_map_occupancy(qn_kf_store* s, const int32_t* ids, const dou
 
 extern "C" int qn_kf_map_occupancy_grid(qn_kf_store* s, qn_occupancy_grid* info_out, uint32_t* hits_out, uint32_t* misses_out, uint8_t* class_out) {
   if (!s || !info_out) return QN_ERR_INVALID_ARG;
-  const OccState* o = oc_live(s);
+  const OccState* o = dg_live(s).occ;
   if (!o) return QN_ERR_NOT_READY;
   const qn_occupancy_grid& g = o->info;
-  const size_t cells = (size_t)g.width * g.height * g.depth;
+  const size_t cells = dg_cells(g);
   *info_out = g;
   if (!cells || (!hits_out && !misses_out && !class_out)) return QN_OK;
   QN_KFCHK(s, hipSetDevice(qn_kf_int_device(s)));
@@ -385,53 +323,40 @@ extern "C" int qn_kf_map_occupancy_grid(qn_kf_store* s, qn_occupancy_grid* info_
 
 extern "C" int qn_kf_map_occupancy_list(qn_kf_store* s, uint32_t class_mask, uint32_t* n_out, int32_t* ijk_out, uint32_t* hits_out, uint32_t* misses_out) {
   if (!s || !n_out || class_mask == 0 || (class_mask & ~7u)) return QN_ERR_INVALID_ARG;
-  const OccState* o = oc_live(s);
+  const OccState* o = dg_live(s).occ;
   if (!o) return QN_ERR_NOT_READY;
   const qn_occupancy_grid& g = o->info;
-  const uint32_t cells = g.width * g.height * g.depth, nb = (cells + MO_BLOCK - 1) / MO_BLOCK;
+  const uint32_t cells = dg_cells(g);
   *n_out = 0;
   if (!cells) return QN_OK;
   QN_KFCHK(s, hipSetDevice(qn_kf_int_device(s)));
   const hipStream_t str = qn_kf_int_stream(s);
-  uint32_t* d_blk = (uint32_t*)qn_kf_int_scratch(s, 3, sizeof(uint32_t) * (2 * (size_t)nb + 1));      // the blocks' counts, then their offsets and the total
+  OcList L = {o->cls.p, class_mask, o->hits.p, o->misses.p, g.width, g.height, nullptr, nullptr, nullptr};
   uint32_t* h = (uint32_t*)qn_kf_int_pinned(s, 64);
-  if (!d_blk || !h) return qn_kf_fail(s, "qn_kf_map_occupancy_list: scratch allocation failed");
-  uint32_t* d_off = d_blk + nb;
-  hipLaunchKernelGGL(k_oc_list_flag, dim3(nb), dim3(MO_BLOCK), 0, str, cells, (const uint8_t*)o->cls.p, class_mask, d_blk);
-  hipLaunchKernelGGL(k_scan_rows, dim3(1), dim3(MO_SCAN_BLOCK), 0, str, (const uint32_t*)d_blk, nb, d_off, d_off + nb);
+  const uint32_t* d_off = h ? dg_list_count(s, cells, L) : nullptr;
+  if (!d_off) return qn_kf_fail(s, "qn_kf_map_occupancy_list: scratch allocation failed");
   QN_KFCHK(s, hipGetLastError());
-  QN_KFCHK(s, hipMemcpyAsync(h, d_off + nb, sizeof(uint32_t), hipMemcpyDeviceToHost, str));
+  QN_KFCHK(s, hipMemcpyAsync(h, d_off + dg_blocks(cells), sizeof(uint32_t), hipMemcpyDeviceToHost, str));
   QN_KFCHK(s, hipStreamSynchronize(str));
   const uint32_t n = h[0];
   *n_out = n;
   if (!n || (!ijk_out && !hits_out && !misses_out)) return QN_OK;
-  int32_t* d_ijk = (int32_t*)qn_kf_int_scratch(s, 1, sizeof(int32_t) * 3 * (size_t)n);
-  uint32_t* d_hm = (uint32_t*)qn_kf_int_scratch(s, 2, sizeof(uint32_t) * 2 * (size_t)n);
-  if (!d_ijk || !d_hm) return qn_kf_fail(s, "qn_kf_map_occupancy_list: scratch allocation failed");
-  hipLaunchKernelGGL(k_oc_list_pick, dim3(nb), dim3(MO_BLOCK), 0, str, cells, (const uint8_t*)o->cls.p, class_mask, (const uint32_t*)d_off, (const uint32_t*)o->hits.p,
-                     (const uint32_t*)o->misses.p, g.width, g.height, d_ijk, d_hm, d_hm + n);
+  L.ijk = (DgIjk*)qn_kf_int_scratch(s, 1, sizeof(DgIjk) * (size_t)n);
+  L.h_out = (uint32_t*)qn_kf_int_scratch(s, 2, sizeof(uint32_t) * 2 * (size_t)n);
+  if (!L.ijk || !L.h_out) return qn_kf_fail(s, "qn_kf_map_occupancy_list: scratch allocation failed");
+  L.m_out = L.h_out + n;
+  dg_list_pick(s, cells, L, d_off);
   QN_KFCHK(s, hipGetLastError());
-  if (ijk_out) QN_KFCHK(s, hipMemcpyAsync(ijk_out, d_ijk, sizeof(int32_t) * 3 * (size_t)n, hipMemcpyDeviceToHost, str));
-  if (hits_out) QN_KFCHK(s, hipMemcpyAsync(hits_out, d_hm, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, str));
-  if (misses_out) QN_KFCHK(s, hipMemcpyAsync(misses_out, d_hm + n, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, str));
+  if (ijk_out) QN_KFCHK(s, hipMemcpyAsync(ijk_out, L.ijk, sizeof(DgIjk) * (size_t)n, hipMemcpyDeviceToHost, str));
+  if (hits_out) QN_KFCHK(s, hipMemcpyAsync(hits_out, L.h_out, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, str));
+  if (misses_out) QN_KFCHK(s, hipMemcpyAsync(misses_out, L.m_out, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, str));
   QN_KFCHK(s, hipStreamSynchronize(str));
   return QN_OK;
 }
 
 extern "C" int qn_kf_map_occupancy_slice(qn_kf_store* s, int32_t iz_lo, int32_t iz_hi, uint8_t* occupancy_out) {
   if (!s || !occupancy_out || iz_lo > iz_hi) return QN_ERR_INVALID_ARG;
-  const OccState* o = oc_live(s);
+  const OccState* o = dg_live(s).occ;
   if (!o) return QN_ERR_NOT_READY;
-  const qn_occupancy_grid& g = o->info;
-  const uint32_t cols = g.width * g.height;
-  if (!cols) return QN_OK;
-  const int64_t lo = std::max<int64_t>(iz_lo, 0), hi = std::min<int64_t>(iz_hi, (int64_t)g.depth - 1);
-  if (lo > hi) { memset(occupancy_out, 0, cols); return QN_OK; }      // no layer of the grid in the range
-  QN_KFCHK(s, hipSetDevice(qn_kf_int_device(s)));
-  const hipStream_t str = qn_kf_int_stream(s);
-  uint8_t* d_out = (uint8_t*)qn_kf_int_scratch(s, 1, cols);
-  if (!d_out) return qn_kf_fail(s, "qn_kf_map_occupancy_slice: scratch allocation failed");
-  hipLaunchKernelGGL(k_oc_slice, dim3((cols + OC_BLOCK - 1) / OC_BLOCK), dim3(OC_BLOCK), 0, str, cols, (const uint8_t*)o->cls.p, (uint32_t)lo, (uint32_t)hi, d_out);
-  QN_KFCHK(s, hipGetLastError());
-  return qn_kf_download(s, occupancy_out, d_out, cols);
+  return dg_slice<uint8_t, op_max>(s, "qn_kf_map_occupancy_slice", o->info, o->cls.p, iz_lo, iz_hi, (uint8_t)0, occupancy_out);
 }

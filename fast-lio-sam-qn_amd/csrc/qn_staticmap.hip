@@ -24,6 +24,7 @@
 #include "../../include/qn_engine.h"
 #include "qn_range.cuh"
 #include "qn_map_compact.cuh"
+#include "qn_dense_grid.cuh"
 #include "qn_union_find.cuh"
 
 namespace {

@@ -1954,7 +1954,8 @@ class KeyframeStore:
     MAP_PRIMS_BLOCK = np.dtype([("count", "<u4", (15,)), ("sum32", "<u4", (6,)), ("max32", "<u4", (6,)), ("again32", "<u4"), ("sum64", "<u8", (6,)),
                                 ("max64", "<u8", (6,)), ("again64", "<u8"), ("wide", "<u8", (2,))])
     MAP_PRIMS_U64, MAP_PRIMS_MAX, MAP_PRIMS_IN_PLACE = 0x100, 0x200, 0x80000000
-    MAP_PRIMS_WAVES, MAP_PRIMS_KEYS, MAP_PRIMS_BLOCKS, MAP_PRIMS_SLOTS, MAP_PRIMS_SCAN, MAP_PRIMS_RANK, MAP_PRIMS_UNITE, MAP_PRIMS_UNITE_MIN = range(8)
+    MAP_PRIMS_WAVES, MAP_PRIMS_KEYS, MAP_PRIMS_BLOCKS, MAP_PRIMS_SLOTS, MAP_PRIMS_SCAN, MAP_PRIMS_RANK, MAP_PRIMS_UNITE, MAP_PRIMS_UNITE_MIN, MAP_PRIMS_GRID = range(9)
+    MAP_PRIMS_VOXEL = np.dtype([("x", "<u4"), ("y", "<u4"), ("z", "<u4"), ("index", "<u4"), ("tile", "<u4"), ("place", "<u4"), ("pos", "<u4"), ("zero", "<u4")])
 
     def debug_map_prims(self, which, data, arg=0):
         """qn_kf_debug_map_prims: routine `which` (the MAP_PRIMS_* numbers above) of the map units' shared device primitives on the caller's input.  data -> result:
@@ -1965,6 +1966,7 @@ class KeyframeStore:
           SCAN       (rows, nb) u32, arg = rows, | MAP_PRIMS_IN_PLACE     -> ((rows, nb) u32 offsets, (rows,) u32 totals)
           RANK       ((256 B,) u8 keep, (B,) u32 bases)             -> (256 B,) u32
           UNITE(_MIN) (n, (m, 2) u32 edges, None or the (n,) u32 starting forest), arg = edges a lane      -> ((n,) u32 raw parents, (n,) u32 roots)
+          GRID       (W, H, D), the sides of a dense grid               -> ((W H D,) MAP_PRIMS_VOXEL, (tiles, 4) i32 tile origins, (26, 3) i32 walk offsets)
         A size that does not fit the routine's records is a ValueError here; everything else is the library's to refuse."""
         u4, u8 = np.dtype("<u4"), np.dtype("<u8")
 
@@ -1992,6 +1994,12 @@ class KeyframeStore:
             keep = need(data[0], np.dtype("u1"), per_block)
             n = len(keep) // 256
             parts, outs = [keep, need(data[1], u4, lambda b: b.shape == (n,))], [((256 * n,), u4)]
+        elif which == self.MAP_PRIMS_GRID:
+            sides = need(np.asarray(data, u4), u4, lambda a: a.shape == (3,))
+            n, parts = int(np.prod(sides.astype(np.uint64))), [sides]
+            t = np.uint64(8)                                         # DG_T of csrc/qn_dense_grid.cuh, the tile's side: the routine writes one origin a tile
+            tiles = int(np.prod((sides.astype(np.uint64) + t - np.uint64(1)) // t))
+            outs = [((n,), self.MAP_PRIMS_VOXEL), ((tiles, 4), np.dtype("<i4")), ((26, 3), np.dtype("<i4"))]
         else:
             n, edges, forest = data
             edges = need(edges, u4, lambda e: e.ndim == 2 and e.shape[1] == 2)

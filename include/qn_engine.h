@@ -1247,7 +1247,7 @@ int  qn_debug_linearize(qn_ctx*, int which, const double* in, uint32_t n, uint32
 #define QN_DEBUG_SEARCH_MAX_WORDS (1u << 26)
 int  qn_debug_search(qn_ctx*, int which, int grid, const void* in, uint32_t n, uint32_t arg, void* out);
 /* developer / tests: the device builds of what the map units share (csrc/qn_map_compact.cuh: the wave and block folds, the key walk, the slot folds, the row
- * scan, the block rank; csrc/qn_union_find.cuh: the two linkers) on caller-supplied inputs, on the store's stream with the store's scratch
+ * scan, the block rank; csrc/qn_union_find.cuh: the two linkers; csrc/qn_dense_grid.cuh: the dense grid's index, tile and rim arithmetic) on caller-supplied inputs, on the store's stream with the store's scratch
  * (csrc/qn_map_selftest.hip).  Host arrays, packed, little endian; a block is 256 lanes = 4 waves of 64; u64 / i64 fields are 8-byte aligned in their records:
  *   0  wave_sum / wave_min / wave_max.  n = blocks, arg = 0.  in per lane (32 B): {i32 i; u32 u; f32 f; u32 0; u64 q; i64 s}.  out per wave (64 B), what lane 0
  *      holds: {i32 min i, max i; u32 sum u, min u, max u; f32 min f, max f; u32 0; u64 sum q, min q; i64 sum s; u64 0}.
@@ -1266,11 +1266,15 @@ int  qn_debug_search(qn_ctx*, int which, int grid, const void* in, uint32_t n, u
  *   6  uf_unite, 7 uf_unite_min.  n = nodes, arg = the consecutive edges a lane takes, 1 .. 13 (lane t of 256 a block: the edges [t arg, (t + 1) arg)).  in: u32 m,
  *      u32 forest (0 / 1), the n u32 parents of the starting forest when forest is 1 (else the identity), then m edges {u32 a, b}.  out: the n u32 parents as
  *      the unite launch left them, then the n u32 roots after the flatten by plain loads.
+ *   8  the dense grid's geometry (dg_index, oc_ijk, dg_tile_of, dg_in_tile, dg_lane_pos, dg_tile_origin, dg_each_neighbour).  n = W H D voxels, arg = 0.  in: u32
+ *      W, H, D, none of them 0.  out per linear index (32 B): {u32 x, y, z of the split; the index rebuilt from them; the voxel's tile; its place in the tile
+ *      (the lane that holds it); the LDS position of that place in a tile kept with a one-voxel rim; 0}, then per tile (16 B): {i32 x, y, z of its first voxel;
+ *      0}, then the 26 offsets {i32 dx, dy, dz} in the order the neighbourhood walk hands them over.
  * Three launches for 6 and 7: init, unite, flatten.  A second call may start from the parents the first one returned.  QN_ERR_INVALID_ARG with nothing
- * launched and nothing written: a null pointer, which outside 0 .. 7, an arg other than the above, more than QN_DEBUG_MAP_PRIMS_MAX_BLOCKS blocks or rows,
- * more than _MAX_NODES nodes, slots or rows x nb counts, more than _MAX_EDGES edges, an edge with an end >= n, a starting parent[x] > x.  n == 0 succeeds and
- * writes nothing (6, 7: the two header words are still read).  Nothing on a product path calls it. */
-#define QN_DEBUG_MAP_PRIMS_WHICH 8
+ * launched and nothing written: a null pointer, which outside 0 .. 8, an arg other than the above, more than QN_DEBUG_MAP_PRIMS_MAX_BLOCKS blocks or rows,
+ * more than _MAX_NODES nodes, slots or rows x nb counts, more than _MAX_EDGES edges, an edge with an end >= n, a starting parent[x] > x, (8) a side of 0 or
+ * W H D != n.  n == 0 succeeds and writes nothing (6, 7: the two header words are still read).  Nothing on a product path calls it. */
+#define QN_DEBUG_MAP_PRIMS_WHICH 9
 #define QN_DEBUG_MAP_PRIMS_MAX_BLOCKS (1u << 16)
 #define QN_DEBUG_MAP_PRIMS_MAX_NODES (1u << 20)
 #define QN_DEBUG_MAP_PRIMS_MAX_EDGES (1u << 20)

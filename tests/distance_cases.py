@@ -1,5 +1,5 @@
-"""The case table of the occupancy map's distance field (csrc/qn_mapdistance.inc: k_md_x, k_md_axis<false / true>, k_md_slice, k_md_query, with
-block_count, block_max, block_sum, k_slot_fold and k_slot_max of csrc/qn_map_compact.cuh and oc_voxel of csrc/qn_mapoccupancy.inc): deterministic inputs that
+"""The case table of the occupancy map's distance field (csrc/qn_mapdistance.inc: k_md_x, k_md_axis<false / true>, k_md_query, with k_dg_slice and dg_block_stats of csrc/qn_dense_grid.cuh,
+block_count, block_max, block_sum, k_slot_fold and k_slot_max of csrc/qn_map_compact.cuh and oc_voxel of csrc/qn_dense_grid.cuh): deterministic inputs that
 put sites on chosen voxels, with what the construction itself determines stated in `expect` - never taken from the twin and never from engine output.  tests/test_map_distance_twin.py holds the twin (qn_amd/mapdistance.py) to the definition (its
 brute()) and to these expectations; tests/test_gpu_map_distance.py holds the engine to the twin and to them.  Pure numpy, no GPU.
 
@@ -11,7 +11,7 @@ A Case: name, records (n, 3) f32, occ (an mo.OccupancyParams), params (an md.Dis
 (every key optional): d2 {voxel (ix, iy, iz): value}, some voxels; full: the whole (D, H, W) field; stats {field: value}.
 
 Seams and the constant each belongs to (restated from the source; whoever changes one there changes it here):
-  MD_BLOCK = MO_BLOCK 256   voxels per block of k_md_x and k_md_axis, columns of k_md_slice, points of k_md_query; the halo of k_md_x is one block either side
+  MD_BLOCK = MO_BLOCK 256   voxels per block of k_md_x and k_md_axis, columns of k_dg_slice, points of k_md_query; the halo of k_md_x is one block either side
   WAVE 64                   one ballot word of k_md_x: the line lengths 63 .. 65, 127 .. 129, 255 .. 257 are its word and block seams, 1025 is four blocks
   MAX_RADIUS 255            the largest max_dist: 255^2 = 65025 is the largest d2, one below FAR's neighbourhood
   MO_WAVES 4, MO_SCAN_BLOCK 1024   the words of block_max and block_sum, the stride of k_slot_fold and k_slot_max: fold_seams() below"""

@@ -1,5 +1,5 @@
 """The case table of the occupancy map's frontier regions (csrc/qn_mapfrontier.inc: k_mf_mark, k_mf_tile, k_mf_merge, k_mf_flatten, k_mf_roots, k_mf_pick,
-k_mf_rows_init, k_mf_relabel, k_mf_rows, k_mf_list_flag, k_mf_list_pick, k_mf_costs, with block_count, block_sum, block_max, wave_each_key, k_slot_fold, k_slot_max, block_rank and k_scan_rows of
+k_mf_rows_init, k_mf_relabel, k_mf_rows, k_mf_costs, with k_dg_list_flag / _pick and the tile of csrc/qn_dense_grid.cuh and block_count, block_sum, block_max, wave_each_key, k_slot_fold, k_slot_max, block_rank and k_scan_rows of
 csrc/qn_map_compact.cuh and uf_unite_min of csrc/qn_union_find.cuh): deterministic three-class layouts, with what the construction itself determines
 stated in `expect` - never taken from the twin and never from engine output.
 tests/test_map_frontier_twin.py holds the twin (qn_amd/mapfrontier.py) to the definition (its brute()) and to these expectations;
@@ -15,7 +15,7 @@ region in region order (fields of mf.INFO_DTYPE, some or all); labels {voxel (ix
 costs [(cost, (ix, iy, iz))] per region.
 
 Seams and the constant each belongs to (restated from the source; whoever changes one there changes it here):
-  MF_T 8                    the side of a tile of k_mf_tile and of the rims k_mf_merge joins: lines of 8, 9, 10, 17 and 65 voxels end on, one past and two past a seam
+  DG_T 8                    the side of a tile of k_mf_tile and of the rims k_mf_merge joins: lines of 8, 9, 10, 17 and 65 voxels end on, one past and two past a seam
   MF_BLOCK = MO_BLOCK 256   voxels per block of the flat kernels (mark, merge, flatten, roots, pick, relabel, list, costs)
   MO_SCAN_BLOCK 1024        threads of k_scan_rows over the blocks' kept roots; the numbering case has 1728 regions in 134 blocks
   WAVE 64                   k_mf_flatten, k_mf_relabel and k_mf_costs fold the voxels of a wave that share a root or region (wave_each_key), one trip per region: the numbering case

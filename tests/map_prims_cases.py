@@ -1,5 +1,5 @@
-"""The inputs and the references for the direct tests of the map units' shared device primitives (csrc/qn_map_compact.cuh, csrc/qn_union_find.cuh through
-qn_kf_debug_map_prims; the records are those of include/qn_engine.h).  Pure numpy: every reference is a serial loop over Python ints or a numpy reduction in
+"""The inputs and the references for the direct tests of the map units' shared device primitives (csrc/qn_map_compact.cuh, csrc/qn_union_find.cuh and the
+geometry of csrc/qn_dense_grid.cuh through qn_kf_debug_map_prims; the records are those of include/qn_engine.h).  Pure numpy: every reference is a serial loop over Python ints or a numpy reduction in
 int64, and nothing here comes from engine output.  tests/test_gpu_map_prims.py runs the device on these, tests/test_map_prims_cpu.py checks that the table is
 what it says it is.
 
@@ -26,6 +26,10 @@ BLOCK_OUT = np.dtype([("count", "<u4", (15,)), ("sum32", "<u4", (6,)), ("max32",
 EDGE_LANES = (1, 13)                                                             # the edges a lane takes: one, and k_mf_merge's up to 13
 FOLD_K32, FOLD_K64 = (1, 2, 3, 5, 10), (1, 2, 3)                                 # the K of k_slot_fold the units launch, by grep over csrc/
 NBS = (1, 63, 64, 1023, 1024, 1025, 2049, 4097)
+TILE, RIM = 8, 10                                                                # DG_T and DG_H of csrc/qn_dense_grid.cuh: a tile's side, and with its one-voxel rim
+VOXEL = np.dtype([("x", "<u4"), ("y", "<u4"), ("z", "<u4"), ("index", "<u4"), ("tile", "<u4"), ("place", "<u4"), ("pos", "<u4"), ("zero", "<u4")])
+# (W, H, D): one side below, at and above the tile side on each axis, a one-voxel axis in each position, more than one 256-lane block, a partial last block
+GRID_SHAPES = ((1, 1, 1), (8, 8, 8), (7, 9, 8), (9, 17, 1), (16, 8, 9), (300, 1, 1), (1, 1, 300))
 
 
 def _rng(*seed):
@@ -422,3 +426,34 @@ def check_forest(parent, want, what):
     assert np.array_equal(p[p], p), "%s: a walk does not end within n steps" % what
     assert np.array_equal(p, want), "%s: a walk ends elsewhere than at the smallest node of the component, at %s" % (what, np.flatnonzero(p != want)[:8])
     assert np.array_equal(np.flatnonzero(parent == x), np.unique(want)), "%s: the roots are not the component minima" % what
+
+
+# ---------------------------------------------------------------------------------------------------------------- 8: the grid geometry
+def grid_reference(W, H, D):
+    """-> ((W H D,) VOXEL, (tiles, 4) i32 tile origins, (26, 3) i32 walk offsets) by numpy's own index arithmetic: x fastest, tiles numbered like voxels"""
+    tiles = tuple(-(-s // TILE) for s in (D, H, W))
+    z, y, x = np.unravel_index(np.arange(W * H * D), (D, H, W))
+    out = np.zeros(W * H * D, VOXEL)
+    out["x"], out["y"], out["z"] = x, y, z
+    out["index"] = np.ravel_multi_index((z, y, x), (D, H, W))
+    out["tile"] = np.ravel_multi_index((z // TILE, y // TILE, x // TILE), tiles)
+    out["place"] = np.ravel_multi_index((z % TILE, y % TILE, x % TILE), (TILE,) * 3)
+    out["pos"] = np.ravel_multi_index((z % TILE + 1, y % TILE + 1, x % TILE + 1), (RIM,) * 3)
+    bz, by, bx = np.unravel_index(np.arange(int(np.prod(tiles))), tiles)
+    origin = np.stack([bx * TILE, by * TILE, bz * TILE, 0 * bx], axis=1).astype(np.int32)
+    walk = np.array([(dx, dy, dz) for dz in (-1, 0, 1) for dy in (-1, 0, 1) for dx in (-1, 0, 1) if (dx, dy, dz) != (0, 0, 0)], np.int32)
+    return out, origin, walk
+
+
+def grid_reference_divmod(W, H, D):
+    """the same by a serial loop of divmod over Python ints, the way the device splits an index"""
+    tx, ty = -(-W // TILE), -(-H // TILE)
+    out = np.zeros(W * H * D, VOXEL)
+    for i in range(W * H * D):
+        row, x = divmod(i, W)
+        z, y = divmod(row, H)
+        (bx, lx), (by, ly), (bz, lz) = divmod(x, TILE), divmod(y, TILE), divmod(z, TILE)
+        out[i] = (x, y, z, (z * H + y) * W + x, (bz * ty + by) * tx + bx, (lz * TILE + ly) * TILE + lx, ((lz + 1) * RIM + ly + 1) * RIM + lx + 1, 0)
+    origin = np.array([(TILE * (t % tx), TILE * (t // tx % ty), TILE * (t // (tx * ty)), 0) for t in range(tx * ty * -(-D // TILE))], np.int32)
+    walk = np.array([(k % 3 - 1, k // 3 % 3 - 1, k // 9 - 1) for k in range(27) if k != 13], np.int32)
+    return out, origin, walk

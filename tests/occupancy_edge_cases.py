@@ -1,4 +1,4 @@
-"""The case table of the occupancy ray carving (csrc/qn_mapoccupancy.inc: k_oc_extent, k_oc_carve<FOLD>, k_oc_classify, k_oc_list_flag / _pick, k_oc_slice, with
+"""The case table of the occupancy ray carving (csrc/qn_mapoccupancy.inc: k_oc_extent, k_oc_carve<FOLD>, k_oc_classify, k_dg_list_flag / _pick and k_dg_slice of csrc/qn_dense_grid.cuh, with
 k_slot_fold and k_scan_rows of csrc/qn_map_compact.cuh and sv_each_chunk of csrc/qn_staticmap.hip): deterministic inputs, each built to put records ON an edge
 of the arithmetic or a seam of the launch, with what the construction itself determines stated in `expect` - never taken from the twin and never from engine
 output.  tests/test_occupancy_edges_cpu.py holds the twin (qn_amd/mapoccupancy.py) to a scalar restatement of the specification and to these expectations,
@@ -19,7 +19,7 @@ rays n_i = sum_k |c(B)_k - c(A)_k| with c = floor(. / 1024), total_hits = n_rays
 c(A) and c(B), and hits is the histogram of c(B): exact_expect() states them from the integers alone.
 
 Seams and the constant each belongs to (restated from the sources; whoever changes one there changes it here):
-  OC_BLOCK = MO_BLOCK 256   records per block of k_oc_extent / k_oc_carve, voxels per block of k_oc_classify / k_oc_list_*, columns of k_oc_slice (qn_map_compact.cuh)
+  OC_BLOCK = MO_BLOCK 256   records per block of k_oc_extent / k_oc_carve, voxels per block of k_oc_classify / k_dg_list_*, columns of k_dg_slice (qn_map_compact.cuh)
   WAVE 64                   the ballot of the fold, the wave reductions of the extent
   MO_SCAN_BLOCK 1024        threads of k_slot_fold and k_scan_rows: more slots than that and a thread's stride loop runs again (qn_map_compact.cuh)
   SV_CHUNK 32768            entries per launch of k_oc_extent / k_oc_carve (qn_staticmap.hip)
@@ -572,7 +572,7 @@ def class_rule():
     return out
 
 
-# ---- the seams of k_oc_classify, k_oc_list_* and k_oc_slice
+# ---- the seams of k_oc_classify, k_dg_list_* and k_dg_slice
 def cell_seams():
     out = []
     for W, H, D in ((17, 15, 1), (16, 16, 1), (257, 1, 1), (16, 16, 3)):

@@ -1,5 +1,5 @@
 """The case table of the occupancy map's route field (csrc/qn_maproute.inc: k_mr_init, k_mr_goals, k_mr_relax, k_mr_stats, k_mr_path, k_mr_query, with k_slot_fold
-and k_slot_max of csrc/qn_map_compact.cuh and oc_voxel of csrc/qn_mapoccupancy.inc): deterministic wall layouts, with what the construction itself determines stated in
+and k_slot_max of csrc/qn_map_compact.cuh and the tile, dg_block_stats and oc_voxel of csrc/qn_dense_grid.cuh): deterministic wall layouts, with what the construction itself determines stated in
 `expect` - never taken from the twin and never from engine output.  tests/test_map_route_twin.py holds the twin (qn_amd/maproute.py) to the definition (its
 dijkstra()) and to these expectations; tests/test_gpu_map_route.py holds the engine to the twin and to them.  Pure numpy, no GPU.
 
@@ -14,7 +14,7 @@ masks of cells that must be reached / must read UNREACHED, min_of: the names of 
 with the same field.
 
 Seams and the constant each belongs to (restated from the source; whoever changes one there changes it here):
-  MR_T 8                    the side of a tile of k_mr_relax: lines of 8, 9, 10, 17 and 65 voxels end on, one past and two past a tile seam
+  DG_T 8                    the side of a tile of k_mr_relax: lines of 8, 9, 10, 17 and 65 voxels end on, one past and two past a tile seam
   MR_BLOCK = MO_BLOCK 256   cells per block of k_mr_init and k_mr_stats, points of k_mr_goals, k_mr_path and k_mr_query"""
 import functools
 import numpy as np

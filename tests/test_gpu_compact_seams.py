@@ -153,7 +153,7 @@ def test_rank_seams_of_the_cluster_members(store, n):
 @pytest.mark.gpu
 @pytest.mark.parametrize("n", SIZES)
 def test_rank_seams_of_the_occupancy_list(store, n):
-    """k_oc_list_flag's count, k_scan_rows, k_oc_list_pick's block_rank on a grid of n x 1 x 1 voxels, for each of the three single-class masks.  One keyframe of
+    """k_dg_list_flag's count, k_scan_rows, k_dg_list_pick's block_rank (qn_dense_grid.cuh, on OcList) on a grid of n x 1 x 1 voxels, for each of the three single-class masks.  One keyframe of
     one record a quarter of a voxel from the sensor, listed once per hit with the sensor in the middle of a voxel: the ray ends in the voxel it starts in, a hit
     and no miss.  min_hits = 2: two hits make a voxel OCCUPIED, one FREE, none UNKNOWN.  The grid spans the rays' ends, so its first and its last voxel cannot
     be UNKNOWN: there the pattern gives way."""

@@ -1,5 +1,5 @@
 """The device builds of what the map units share - the wave and block folds, the key walk, the slot folds, the row scan and the block rank of
-csrc/qn_map_compact.cuh, the two linkers of csrc/qn_union_find.cuh - called directly through qn_kf_debug_map_prims (csrc/qn_map_selftest.hip) on the inputs of
+csrc/qn_map_compact.cuh, the two linkers of csrc/qn_union_find.cuh, the index, tile and rim arithmetic and the neighbourhood walk of csrc/qn_dense_grid.cuh - called directly through qn_kf_debug_map_prims (csrc/qn_map_selftest.hip) on the inputs of
 tests/map_prims_cases.py, which no unit can produce, against that file's serial references.  Every comparison is exact: integers by value, floats by value
 with +0 and -0 equal and a NaN lane ignored unless every lane is NaN.  The sign of a zero minimum or maximum is whatever fminf / fmaxf give, and no caller
 reads it: the only float callers, k_mg_extent and k_mg_extent_sum, hand the extremes to qn_kf_map_ground, which takes floor(x / cell) of them, compares and
@@ -146,6 +146,16 @@ def test_union_find_in_two_launches(store, linker, family, per):
     assert np.array_equal(root2, mc.uf_reference(family))
 
 
+@pytest.mark.parametrize("shape", mc.GRID_SHAPES, ids=["%dx%dx%d" % s for s in mc.GRID_SHAPES])
+def test_grid_geometry(store, shape):
+    """oc_ijk, dg_index, dg_tile_of, dg_in_tile, dg_lane_pos, dg_tile_origin and the order of dg_each_neighbour against numpy's unravel_index: exact"""
+    vox, origin, walk = store.debug_map_prims(store.MAP_PRIMS_GRID, shape)
+    want_vox, want_origin, want_walk = mc.grid_reference(*shape)
+    _fields(vox.reshape(-1, 1), want_vox.reshape(-1, 1), ["%s, index %d" % (shape, i) for i in range(len(want_vox))], "grid geometry")
+    assert np.array_equal(origin, want_origin), (shape, origin, want_origin)
+    assert np.array_equal(walk, want_walk), (walk, want_walk)
+
+
 def test_refusals_and_the_empty_input(store):
     from qn_amd import engine
     L = store._l
@@ -153,20 +163,24 @@ def test_refusals_and_the_empty_input(store):
     p = lambda x: x.ctypes.data_as(C.c_void_p)
     a = np.zeros(1 << 14, np.uint32); out = np.full(1 << 14, 7, np.uint32)
     call = lambda *args: L.qn_kf_debug_map_prims(*args)
-    for which in range(8):
+    for which in range(9):
         arg = {3: 2, 4: 1, 6: 1, 7: 13}.get(which, 0)
         assert call(None, which, p(a), 1, arg, p(out)) == engine.QN_ERR_INVALID_ARG
         assert call(store.h, which, None, 1, arg, p(out)) == engine.QN_ERR_INVALID_ARG
         assert call(store.h, which, p(a), 1, arg, None) == engine.QN_ERR_INVALID_ARG
         assert call(store.h, which, p(a), 0, arg, p(out)) == engine.QN_OK                      # n == 0: nothing written
-        cap = (1 << 20) if which in (3, 4, 6, 7) else (1 << 16)
+        cap = (1 << 20) if which in (3, 4, 6, 7, 8) else (1 << 16)
         assert call(store.h, which, p(a), cap + 1, arg, p(out)) == engine.QN_ERR_INVALID_ARG
-    for which, arg in ((-1, 0), (8, 0), (0, 1), (1, 2), (2, 1), (3, 0), (3, 4), (3, 0x104), (3, 0x201), (4, 0), (4, 0x80000000), (4, (1 << 16) + 1), (5, 1), (6, 0), (7, 14)):
+    for which, arg in ((-1, 0), (9, 0), (8, 0), (8, 1), (0, 1), (1, 2), (2, 1), (3, 0), (3, 4), (3, 0x104), (3, 0x201), (4, 0), (4, 0x80000000), (4, (1 << 16) + 1), (5, 1), (6, 0), (7, 14)):
         assert call(store.h, which, p(a), 1, arg, p(out)) == engine.QN_ERR_INVALID_ARG, (which, arg)
     for which in (6, 7):
         for words in ([(1 << 20) + 1, 0], [1, 2], [1, 0, 0, 4], [1, 0, 4, 0], [0, 1, 0, 2, 1, 1], [1, 1, 0, 1, 2, 3, 3, 4]):      # m, forest, then parents / edges; n = 4
             a[:8] = 0; a[:len(words)] = words
             assert call(store.h, which, p(a), 4, 1, p(out)) == engine.QN_ERR_INVALID_ARG, (which, words)
+    for n, sides in ((1, [0, 0, 0]), (6, [0, 2, 3]), (6, [1, 0, 6]), (6, [2, 3, 0]), (6, [2, 3, 2]), (6, [7, 1, 1]), (1 << 20, [1 << 10, 1 << 10, 2]), (0x10, [1 << 16, 1 << 16, 1 << 4])):
+        a[:3] = sides                                                            # a zero side, a product other than n, above the cap, a product that wraps 32 bits
+        assert call(store.h, 8, p(a), n, 0, p(out)) == engine.QN_ERR_INVALID_ARG, (n, sides)
+    a[:8] = 0
     assert (out == 7).all()
     with pytest.raises(ValueError):
         store.debug_map_prims(store.MAP_PRIMS_WAVES, np.zeros(255, mc.LANE))

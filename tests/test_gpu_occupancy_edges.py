@@ -1,4 +1,4 @@
-"""The occupancy kernels (k_oc_extent, k_oc_carve<true> and <false>, k_oc_classify, k_oc_list_flag / _pick, k_oc_slice, with k_slot_fold, k_scan_rows and
+"""The occupancy kernels (k_oc_extent, k_oc_carve<true> and <false>, k_oc_classify, k_dg_list_flag / _pick and k_dg_slice of qn_dense_grid.cuh, with k_slot_fold, k_scan_rows and
 sv_each_chunk behind them) on the edge cases of tests/occupancy_edge_cases.py: every byte against the numpy twin qn_amd/mapoccupancy.py - hits, misses,
 classes, all 13 statistics, the grid info, the lists under all seven masks, the slices, a rerun - with no tolerance, and then against what the generators
 state by construction (tests/test_occupancy_edges_cpu.py holds the twin to the same statements and to a scalar restatement, and shows which mistake each

@@ -12,7 +12,7 @@ from qn_amd import engine, mapdistance as md
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "fast-lio-sam-qn_amd", "csrc")
 SYMBOLS = ["qn_distance_default_params", "qn_kf_map_distance", "qn_kf_map_distance_grid", "qn_kf_map_distance_slice", "qn_kf_map_distance_query"]
-KERNELS = ("k_md_x", "k_md_axis<false>", "k_md_axis<true>", "k_slot_max<unsigned int>", "k_md_slice", "k_md_query", "k_slot_fold<unsigned int, 3>",
+KERNELS = ("k_md_x", "k_md_axis<false>", "k_md_axis<true>", "k_slot_max<unsigned int>", "k_dg_slice<unsigned short, (anonymous namespace)::op_min>", "k_md_query", "k_slot_fold<unsigned int, 3>",
            "k_slot_fold<unsigned long long, 1>")
 
 
@@ -88,6 +88,10 @@ def test_the_device_code_hangs_on_the_occupancy_state():
     call = inc[inc.index('extern "C" int qn_kf_map_distance('):inc.index('extern "C" int qn_kf_map_distance_grid(')]
     assert len(re.findall(r"hipStreamSynchronize", call)) == 1
     assert "block_count(" in inc and "k_slot_fold<" in inc
+    grid = open(os.path.join(CSRC, "qn_dense_grid.cuh")).read()      # the statistics tail and its folds are the dense grid's, shared with the route
+    assert "dg_block_stats(" in inc and "dg_fold_stats(" in inc and "atomic" not in grid
+    tail = grid[grid.index(" dg_block_stats("):grid.index(" dg_slice(")]
+    assert "block_count(" in tail and "k_slot_fold<" in tail and "k_slot_max<" in tail and "hipStreamSynchronize" not in tail
 
 
 def test_the_kernels_have_no_scratch_and_no_spills():
@@ -102,11 +106,12 @@ def test_the_kernels_have_no_scratch_and_no_spills():
 
 def test_no_floating_point_outside_the_query():
     """the transform, slice and statistics kernels, the fold of the largest (k_slot_max: qn_map_compact.cuh) and the two bit searches name no floating-point type;
-    the query's quantisation (oc_voxel: qn_mapoccupancy.inc, which the route shares) is the only place that does"""
+    the query's quantisation (oc_voxel: qn_dense_grid.cuh, which the route shares) is the only place that does"""
     src = open(os.path.join(CSRC, "qn_mapdistance.inc")).read()
     compact = open(os.path.join(CSRC, "qn_map_compact.cuh")).read()
-    occ = open(os.path.join(CSRC, "qn_mapoccupancy.inc")).read()
-    for text, k, least in ((src, "md_left", 200), (src, "md_right", 200), (src, "k_md_x", 200), (src, "k_md_axis", 200), (compact, "k_slot_max", 200), (src, "k_md_slice", 200)):
+    occ = open(os.path.join(CSRC, "qn_dense_grid.cuh")).read()
+    for text, k, least in ((src, "md_left", 200), (src, "md_right", 200), (src, "k_md_x", 200), (src, "k_md_axis", 200), (compact, "k_slot_max", 200), (occ, "k_dg_slice", 200),
+                           (occ, "dg_block_stats", 200)):
         i = text.index(" " + k + "(")
         body = text[i:text.index("\n}\n", i)]
         assert len(body) > least and not re.search(r"\b(float|double|float4|double2)\b", body), k
@@ -114,9 +119,10 @@ def test_no_floating_point_outside_the_query():
     assert "oc_voxel(" in src[src.index("{\n", i):src.index("\n}\n", i)]
     i = occ.index(" oc_voxel(")
     q = occ[i:occ.index("\n}\n", i)]
-    assert "rint(t * 1024.0)" in q and "double" in q and (src + occ).count("rint(t * 1024.0)") == 1      # the one quantisation of a world point
+    every = "".join(open(os.path.join(CSRC, f)).read() for f in sorted(os.listdir(CSRC)) if f.endswith((".hip", ".cuh", ".inc", ".h")))
+    assert "rint(t * 1024.0)" in q and "double" in q and every.count("rint(t * 1024.0)") == 1      # the one quantisation of a world point
     device = src[:src.index("host side")]
-    assert len(re.findall(r"__global__", device)) == 4
+    assert len(re.findall(r"__global__", device)) == 3 and "k_dg_slice<uint16_t, op_min>" in src      # (the slice kernel is the dense grid's)
 
 
 def test_shim_program_compiles_and_prints_its_refusals(tmp_path):

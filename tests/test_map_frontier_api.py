@@ -14,7 +14,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "fast-lio-sam-qn_amd", "csrc")
 SYMBOLS = ["qn_frontier_default_params", "qn_kf_map_frontiers", "qn_kf_map_frontier_grid", "qn_kf_map_frontier_regions", "qn_kf_map_frontier_list",
            "qn_kf_map_frontier_costs"]
-KERNELS = ("k_mf_mark", "k_mf_tile", "k_mf_merge", "k_mf_flatten", "k_mf_roots", "k_mf_pick", "k_mf_rows_init", "k_mf_relabel", "k_mf_rows", "k_mf_list_flag", "k_mf_list_pick", "k_mf_costs")
+KERNELS = ("k_mf_mark", "k_mf_tile", "k_mf_merge", "k_mf_flatten", "k_mf_roots", "k_mf_pick", "k_mf_rows_init", "k_mf_relabel", "k_mf_rows", "k_mf_costs")
+LIST_KERNELS = ("k_dg_list_flag", "k_dg_list_pick")                  # the voxel list's, of qn_dense_grid.cuh, instantiated on MfList
 # what the header, README and DESIGN.md all say of the unit
 SHARED = ("qn_amd/mapfrontier.py", "qn_mapfrontier.inc", "26-connect", "free_mask", "unknown_mask", "edge_unknown", "min_size", "ascending root", "interface choices")
 
@@ -55,7 +56,7 @@ def test_readme_design_and_the_twin_say_the_same():
         assert w in row and w in para and (w in twin or w == "qn_amd/mapfrontier.py"), w
     for s in SYMBOLS:
         assert s in row, s
-    for w in KERNELS:
+    for w in KERNELS + LIST_KERNELS:
         assert w in para, w
     for w in ("KeyframeStore.map_frontiers", "qn_map::mapFrontiers", "--occ-frontiers", "tools/gpu_map_frontier_time.py"):
         assert w in row, w
@@ -116,7 +117,7 @@ def test_the_device_code_hangs_on_the_occupancy_state():
     inc = open(os.path.join(CSRC, "qn_mapfrontier.inc")).read()
     assert "qn_amd/mapfrontier.py" in inc and "untuned" in inc and "union-find" in inc and "rounds = 1" in inc
     device = inc[:inc.index("host side")]
-    assert len(re.findall(r"__global__", device)) == len(KERNELS)
+    assert len(re.findall(r"__global__", device)) == len(KERNELS) and "struct MfList {" in device and "dg_list_count(" in inc and "dg_list_pick(" in inc
     call = inc[inc.index('extern "C" int qn_kf_map_frontiers('):inc.index('extern "C" int qn_kf_map_frontier_grid(')]
     assert len(re.findall(r"hipStreamSynchronize", call)) == 2      # the number of regions, the statistics
     assert "block_count(" in inc and "k_slot_fold<" in inc and "block_rank(" in inc and "k_scan_rows" in inc and "__syncthreads_or(" in inc
@@ -127,7 +128,7 @@ def test_the_kernels_have_no_scratch_and_no_spills():
     from qn_amd import build
     build.build()
     out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "scratch_report.py"), "--all"], capture_output=True, text=True, check=True).stdout
-    for k in KERNELS:
+    for k in KERNELS + tuple(k + "<(anonymous namespace)::MfList>" for k in LIST_KERNELS):
         rows = [l for l in out.splitlines() if "::" + k + "(" in l]
         assert rows, k
         assert all(int(l.split()[0]) == 0 and " spill   0 " in l for l in rows), rows

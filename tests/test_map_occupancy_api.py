@@ -12,7 +12,8 @@ from qn_amd import engine, mapoccupancy as mo
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "fast-lio-sam-qn_amd", "csrc")
 SYMBOLS = ["qn_occupancy_default_params", "qn_kf_map_occupancy", "qn_kf_map_occupancy_grid", "qn_kf_map_occupancy_list", "qn_kf_map_occupancy_slice"]
-KERNELS = ("k_oc_extent", "k_oc_carve<true>", "k_oc_carve<false>", "k_oc_classify", "k_oc_list_flag", "k_oc_list_pick", "k_oc_slice", "k_scan_rows",
+KERNELS = ("k_oc_extent", "k_oc_carve<true>", "k_oc_carve<false>", "k_oc_classify", "k_dg_list_flag<(anonymous namespace)::OcList>", "k_dg_list_pick<(anonymous namespace)::OcList>",
+           "k_dg_slice<unsigned char, (anonymous namespace)::op_max>", "k_scan_rows",
            "k_slot_fold<unsigned int, 5>", "k_slot_fold<unsigned int, 3>", "k_slot_fold<unsigned long long, 2>")
 
 
@@ -99,12 +100,16 @@ def test_the_kernels_have_no_scratch_and_no_spills():
 
 def test_no_floating_point_in_the_walk():
     """behind the quantisation (oc_ray, which the extent and the carve kernels share) the walk names no floating-point type: the whole of oc_walk - the setup, the
-    fold of the first voxel and the loop - and the kernels behind the counts"""
+    fold of the first voxel and the loop - and the kernels behind the counts: the list's predicate and payload here, its kernels and the slice kernel in
+    qn_dense_grid.cuh"""
     src = open(os.path.join(CSRC, "qn_mapoccupancy.inc")).read()
-    for k in ("oc_walk", "k_oc_classify", "k_oc_list_flag", "k_oc_list_pick", "k_oc_slice"):
-        i = src.index(" " + k + "(")
-        body = src[i:src.index("\n}\n", i)]
-        assert len(body) > 200 and not re.search(r"\b(float|double|float4|double2)\b", body), k
+    grid = open(os.path.join(CSRC, "qn_dense_grid.cuh")).read()
+    for text, k, end in ((src, " oc_walk(", "\n}\n"), (src, " k_oc_classify(", "\n}\n"), (src, "struct OcList {", "\n};\n"), (grid, " k_dg_list_flag(", "\n}\n"),
+                         (grid, " k_dg_list_pick(", "\n}\n"), (grid, " k_dg_slice(", "\n}\n")):
+        i = text.index(k)
+        body = text[i:text.index(end, i)]
+        assert len(body) > (150 if "list_flag" in k else 200) and not re.search(r"\b(float|double|float4|double2)\b", body), k
+    assert "keep(uint32_t i)" in src[src.index("struct OcList {"):] and "list.keep(i)" in grid and "list.put(i, j)" in grid and "block_rank(keep" in grid
     walk = src[src.index(" oc_walk("):]
     loop = walk[walk.index("for (uint32_t i = 0; i < carve; i++)"):walk.index("\n}\n")]
     assert "atomicAdd(&misses[lin], 1u)" in loop and "unsigned long long" in loop and not re.search(r"\b(float|double)\b", loop)

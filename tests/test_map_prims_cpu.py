@@ -2,6 +2,8 @@
 store for every routine, and the case table of tests/map_prims_cases.py is what it says it is - the counts of distinct keys, which sums wrap, the
 component counts of the graph families - with its references checked on inputs whose answers are known in closed form.  The device: tests/test_gpu_map_prims.py."""
 import ctypes as C
+import os
+import re
 import numpy as np
 import map_prims_cases as mc
 
@@ -13,15 +15,16 @@ def test_device_entry_is_declared_wrapped_and_refuses_a_null_store():
     L = engine.lib()
     L.qn_kf_debug_map_prims.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
     a = np.zeros(4096, np.uint32); out = np.full(4096, 7, np.uint32)
-    for which in range(8):
+    for which in range(9):
         for n in (0, 1):
             assert L.qn_kf_debug_map_prims(None, which, a.ctypes.data_as(C.c_void_p), n, 1, out.ctypes.data_as(C.c_void_p)) == engine.QN_ERR_INVALID_ARG
     assert (out == 7).all()
     K = engine.KeyframeStore
     for mine, theirs in ((mc.LANE, K.MAP_PRIMS_LANE), (mc.WAVE_OUT, K.MAP_PRIMS_WAVE), (mc.KEY_IN, K.MAP_PRIMS_KEY_IN), (mc.KEY_OUT, K.MAP_PRIMS_KEY),
-                         (mc.BLOCK_IN, K.MAP_PRIMS_BLOCK_IN), (mc.BLOCK_OUT, K.MAP_PRIMS_BLOCK)):
+                         (mc.BLOCK_IN, K.MAP_PRIMS_BLOCK_IN), (mc.BLOCK_OUT, K.MAP_PRIMS_BLOCK), (mc.VOXEL, K.MAP_PRIMS_VOXEL)):
         assert mine == theirs
-    assert [d.itemsize for d in (mc.LANE, mc.WAVE_OUT, mc.KEY_IN, mc.KEY_OUT, mc.BLOCK_IN, mc.BLOCK_OUT)] == [32, 64, 8, 24, 40, 232]      # include/qn_engine.h
+    assert [d.itemsize for d in (mc.LANE, mc.WAVE_OUT, mc.KEY_IN, mc.KEY_OUT, mc.BLOCK_IN, mc.BLOCK_OUT, mc.VOXEL)] == [32, 64, 8, 24, 40, 232, 32]      # include/qn_engine.h
+    assert K.MAP_PRIMS_GRID == 8 and re.search(r"#define\s+QN_DEBUG_MAP_PRIMS_WHICH\s+9\b", open(os.path.join(test_capi_symbols.ROOT, "include", "qn_engine.h")).read())
 
 
 def test_the_wave_cases_are_what_they_say():
@@ -146,3 +149,25 @@ def test_the_graph_families_are_what_they_say():
             continue
         raise AssertionError("check_forest let %r through" % (wrong,))
     mc.check_forest(bad, np.zeros(4, np.uint32), "a chain")
+
+
+def test_the_grid_references_agree_and_are_what_they_say():
+    """numpy's unravel_index / ravel_multi_index against a serial divmod loop, on the shapes the device runs; then what the shapes are there for"""
+    for W, H, D in mc.GRID_SHAPES:
+        a, b = mc.grid_reference(W, H, D), mc.grid_reference_divmod(W, H, D)
+        assert all(np.array_equal(p, q) for p, q in zip(a, b)), (W, H, D)
+        vox, origin, walk = a
+        assert np.array_equal(vox["index"], np.arange(W * H * D)) and vox["x"].max() == W - 1 and vox["y"].max() == H - 1 and vox["z"].max() == D - 1
+        assert len(origin) == int(vox["tile"].max()) + 1 and (vox["place"] < 512).all() and (vox["pos"] < 1000).all()
+        first = np.flatnonzero(vox["place"] == 0)                                    # the voxel at place 0 of a tile is the tile's origin
+        assert np.array_equal(np.stack([vox[f][first] for f in "xyz"], axis=1)[np.argsort(vox["tile"][first])], origin[:, :3])
+        assert len({(int(t), int(p)) for t, p in zip(vox["tile"], vox["place"])}) == W * H * D      # a tile and a place name one voxel
+    assert walk.shape == (26, 3) and walk[0].tolist() == [-1, -1, -1] and walk[1].tolist() == [0, -1, -1] and walk[12].tolist() == [-1, 0, 0] and walk[13].tolist() == [1, 0, 0]
+    assert walk[25].tolist() == [1, 1, 1] and len({tuple(w) for w in walk.tolist()}) == 26 and (0, 0, 0) not in {tuple(w) for w in walk.tolist()}
+    sides = {axis: sorted({s[axis] for s in mc.GRID_SHAPES}) for axis in range(3)}
+    for axis in range(3):                                                            # below, at and above the tile side on each axis; a one-voxel axis in each position
+        assert 1 in sides[axis] and mc.TILE in sides[axis] and any(mc.TILE > s > 0 for s in sides[axis]) and any(s > mc.TILE and s % mc.TILE for s in sides[axis])
+    assert any(W * H * D > 256 and (W * H * D) % 256 for W, H, D in mc.GRID_SHAPES) and max(W * H * D for W, H, D in mc.GRID_SHAPES) < 5000
+    vox, origin, _ = mc.grid_reference(9, 17, 1)
+    assert origin.tolist() == [[0, 0, 0, 0], [8, 0, 0, 0], [0, 8, 0, 0], [8, 8, 0, 0], [0, 16, 0, 0], [8, 16, 0, 0]]
+    assert tuple(vox[8 + 9 * 16]) == (8, 16, 0, 152, 5, 0, 111, 0) and tuple(vox[7 + 9 * 7]) == (7, 7, 0, 70, 0, 63, 188, 0)

@@ -128,18 +128,18 @@ def test_the_kernels_have_no_scratch_and_no_spills():
 
 
 def test_no_floating_point_outside_the_quantisation():
-    """the field, statistics and walk kernels name no floating-point type in their bodies; oc_voxel (qn_mapoccupancy.inc), which goals, starts and query
+    """the field, statistics and walk kernels name no floating-point type in their bodies; oc_voxel (qn_dense_grid.cuh), which goals, starts and query
     points share with the distance query, is the only place that computes with one"""
     src = open(os.path.join(CSRC, "qn_maproute.inc")).read()
-    for k, least in (("k_mr_init", 200), ("k_mr_relax", 1500), ("k_mr_stats", 200)):
-        i = src.index(" " + k + "(")
-        body = src[i:src.index("\n}\n", i)]
+    occ = open(os.path.join(CSRC, "qn_dense_grid.cuh")).read()
+    for text, k, least in ((src, "k_mr_init", 200), (src, "k_mr_relax", 1500), (src, "k_mr_stats", 200), (occ, "dg_block_stats", 200), (occ, "dg_each_neighbour", 200)):
+        i = text.index(" " + k + "(")
+        body = text[i:text.index("\n}\n", i)]
         assert len(body) > least and not re.search(r"\b(float|double|float4|double2)\b", body), k
     for k in ("k_mr_goals", "k_mr_path", "k_mr_query"):
         i = src.index(" " + k + "(")
         body = src[src.index("{\n", i):src.index("\n}\n", i)]
         assert "oc_voxel(" in body and not re.search(r"\b(float|double|float4|double2)\b", body), k      # (the points and 1 / voxel are parameters)
-    occ = open(os.path.join(CSRC, "qn_mapoccupancy.inc")).read()
     i = occ.index(" oc_voxel(")
     q = occ[i:occ.index("\n}\n", i)]
     assert "rint(t * 1024.0)" in q and "double" in q
