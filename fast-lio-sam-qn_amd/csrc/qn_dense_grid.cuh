@@ -1,8 +1,8 @@
 // qn_dense_grid.cuh - what every field over the dense occupancy grid shares, on the device and on the host: the W x H x D volume of qn_mapoccupancy.inc and the
-// fields computed from it (qn_mapdistance.inc, qn_maproute.inc, qn_mapfrontier.inc), all part of qn_staticmap.hip's translation unit, which includes this file
-// ahead of the four.  The next field over the grid starts from here, not from a copy of one of them:
+// fields computed from it (qn_mapdistance.inc, qn_maproute.inc, qn_mapfrontier.inc, qn_mapview.inc), all part of qn_staticmap.hip's translation unit, which includes this file
+// ahead of the five.  The next field over the grid starts from here, not from a copy of one of them:
 //   geometry  OcGrid / oc_grid: the grid as the kernels take it; oc_voxel: the one world-point-to-cell quantisation (distance query, route goals, starts and
-//             queries); dg_index and its inverse oc_ijk: voxel <-> linear index, x fastest (the kernels of the four files - but k_md_x and k_md_axis, which want one
+//             queries, the view gain's viewpoints); dg_index and its inverse oc_ijk: voxel <-> linear index, x fastest (the kernels of the four files - but k_md_x and k_md_axis, which want one
 //             coordinate and keep their one division: EXPERIMENTS.md -, the tile numbering below, the host of qn_kf_map_frontier_costs); dg_cols / dg_cells / dg_blocks: the sizes every entry point derives from qn_occupancy_grid.
 //   tile      the DG_T^3 tile of k_mr_relax and k_mf_tile, one voxel per lane, in LDS with a one-voxel rim: dg_local (lane -> place in the tile), dg_pos and
 //             dg_lane_pos (place, lane -> LDS position), dg_step (the LDS offset of a neighbour), dg_tile_origin (tile number -> its first voxel), dg_tile_of
@@ -17,7 +17,7 @@
 //             on a functor with the predicate and the payload (OcList, MfList); dg_list_count and dg_list_pick launch them (qn_kf_map_occupancy_list reads the
 //             count between the two, qn_kf_map_frontier_list knows it already).
 //   points    dg_points: n f64 points to scratch 0 and the launch grid of one point per lane (qn_kf_map_distance_query, qn_kf_map_route, _route_query, _route_path).
-//   lifetime  DgLive / dg_live: the live results of the chain occupancy -> distance -> route and occupancy -> frontier together, null from where the chain is
+//   lifetime  DgLive / dg_live: the live results of the chain occupancy -> distance -> route, occupancy -> frontier and occupancy -> view together, null from where the chain is
 //             broken (every entry point behind qn_kf_map_occupancy).  A result that outgrows its buffer: KfBuf::grow_beside / adopt (qn_kf_buf.h).
 // Tested directly: the index split, the tile numbering, the rim position and the order of the walk through qn_kf_debug_map_prims (qn_map_selftest.hip, routine 8;
 // tests/test_gpu_map_prims.py); the rest through the units.  Every kernel here is a template, so a unit carries only what it instantiates.
@@ -48,9 +48,10 @@ inline OcGrid oc_grid(const qn_occupancy_grid& g) { return OcGrid{{g.minc[0], g.
 
 // The dense grid's cell of world point i, for every field over the grid (the distance and route queries, goals and starts), by the map's own quantisation: f64,
 // every operation rounded on its own, half to even; false for a point that is not finite, 2^20 voxels or more from the origin, or outside the field of depth
-// Df.  Planar: x and y choose the column, z must only pass the limit.
+// Df.  Planar: x and y choose the column, z must only pass the limit.  fixed (the view gain's viewpoints; nullptr elsewhere): the point's fixed-point
+// integers themselves, 0 for a coordinate that fails the limit.
 __device__ __forceinline__ bool oc_voxel(const double* __restrict__ xyz, uint32_t i, double inv, const OcGrid& G, uint32_t Df, uint32_t planar, uint32_t* cx, uint32_t* cy,
-                                         uint32_t* cz) {
+                                         uint32_t* cz, int32_t* fixed = nullptr) {
   const uint32_t side[3] = {G.W, G.H, Df};
   long long c[3];
   bool ok = true;
@@ -58,7 +59,9 @@ __device__ __forceinline__ bool oc_voxel(const double* __restrict__ xyz, uint32_
   for (int k = 0; k < 3; k++) {
     const double t = xyz[3 * (size_t)i + k] * inv;
     const bool in = fabs(t) < OC_COORD_LIMIT;                       // (a NaN fails the comparison, an infinity too)
-    c[k] = in ? (((long long)rint(t * 1024.0)) >> OC_S) - G.minc[k] : -1;
+    const long long a = in ? (long long)rint(t * 1024.0) : 0;       // |a| <= 2^30
+    c[k] = in ? (a >> OC_S) - G.minc[k] : -1;
+    if (fixed) fixed[k] = (int32_t)a;
     if (k == 2 && planar && in) c[k] = 0;
     ok = ok && in && c[k] >= 0 && c[k] < (long long)side[k];
   }
@@ -194,9 +197,9 @@ inline int dg_points(qn_kf_store* s, const char* who, const double* xyz, uint32_
   return QN_OK;
 }
 
-// ---- result lifetime.  The results hang on each other - StaticState -> OccState -> DistState -> RouteState, OccState -> FrontierState, each in its unit's file - and
-// each is live only while the one it was computed from is: the live ones together, nullptr from where the chain is broken.  Defined in qn_mapfrontier.inc, the last.
-struct DgLive { const struct OccState* occ; const struct DistState* dist; const struct RouteState* route; const struct FrontierState* frontier; };
+// ---- result lifetime.  The results hang on each other - StaticState -> OccState -> DistState -> RouteState, OccState -> FrontierState, OccState -> ViewState, each in its
+// unit's file - and each is live only while the one it was computed from is: the live ones together, nullptr from where the chain is broken.  Defined in qn_mapview.inc, the last.
+struct DgLive { const struct OccState* occ; const struct DistState* dist; const struct RouteState* route; const struct FrontierState* frontier; const struct ViewState* view; };
 DgLive dg_live(qn_kf_store* s);
 template <typename T> T* dg_mut(const T* live) { return const_cast<T*>(live); }      // for the three calls that hang a result of their own on a live one
 

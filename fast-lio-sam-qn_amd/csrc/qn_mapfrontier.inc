@@ -269,16 +269,7 @@ struct FrontierState {
 
 void mf_end(FrontierState* f) { if (f) f->live = false; }
 
-// the lookup every entry point behind qn_kf_map_occupancy starts with (declared in qn_dense_grid.cuh; here all four states are complete)
-DgLive dg_live(qn_kf_store* s) {
-  DgLive L = {nullptr, nullptr, nullptr, nullptr};
-  const StaticState* st = (const StaticState*)qn_kf_int_ext(s, QN_KF_INT_EXT_STATIC);
-  if (st && st->occ && st->occ->live) L.occ = st->occ.get();
-  if (L.occ && L.occ->dist && L.occ->dist->live) L.dist = L.occ->dist.get();
-  if (L.dist && L.dist->route && L.dist->route->live) L.route = L.dist->route.get();
-  if (L.occ && L.occ->frontier && L.occ->frontier->live) L.frontier = L.occ->frontier.get();
-  return L;
-}
+// (dg_live, the lookup every entry point behind qn_kf_map_occupancy starts with: qn_mapview.inc, included last, where every state is complete)
 
 }  // namespace
 

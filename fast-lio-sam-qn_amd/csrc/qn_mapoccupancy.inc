@@ -174,9 +174,11 @@ struct OccState {
   qn_occupancy_grid info;
   std::shared_ptr<struct DistState> dist;                // the distance field of qn_mapdistance.inc (included behind this file, where the type is completed)
   std::shared_ptr<struct FrontierState> frontier;        // the frontier regions of qn_mapfrontier.inc (included last), beside the field: they need only the classes
+  std::shared_ptr<struct ViewState> view;                // the view gain of qn_mapview.inc (included behind it), beside them: it needs only the classes too
 };
 void md_end(DistState*);                                 // (qn_mapdistance.inc) a new occupancy result ends the field of the previous one; its buffers stay
 void mf_end(FrontierState*);                             // (qn_mapfrontier.inc) and the frontier regions of the previous one
+void mv_end(ViewState*);                                 // (qn_mapview.inc) and its view gain
 
 }  // namespace
 
@@ -300,6 +302,7 @@ extern "C" int qn_kf_map_occupancy(qn_kf_store* s, const int32_t* ids, const dou
   st->live = true;
   md_end(st->dist.get());
   mf_end(st->frontier.get());
+  mv_end(st->view.get());
   *stats_out = r;
   return QN_OK;
 }

@@ -290,3 +290,4 @@ extern "C" int qn_kf_build_map_static(qn_kf_store* s, double leaf, const float**
 #include "qn_mapdistance.inc"
 #include "qn_maproute.inc"
 #include "qn_mapfrontier.inc"
+#include "qn_mapview.inc"

@@ -974,6 +974,47 @@ QN_FRONTIER_REJECTED = -1
 QN_FRONTIER_NONE = -2
 
 
+class ViewParams(C.Structure):
+    """qn_view_params (32 bytes): the classes whose voxels are gain and those that stop a ray (bit 1 << class, no class in both; stop_mask may be 0), the gain
+    voxels a ray may pass through (0: no limit), and the band of layers in which a voxel is marked.  The defaults are interface choices, not measurements."""
+    _fields_ = [("gain_mask", C.c_uint32), ("stop_mask", C.c_uint32), ("max_through", C.c_uint32), ("iz_lo", C.c_int32), ("iz_hi", C.c_int32), ("reserved", C.c_uint32 * 3)]
+
+    def __init__(self, gain_mask=1 << QN_OCC_UNKNOWN, stop_mask=1 << QN_OCC_OCCUPIED, max_through=0, iz_lo=0, iz_hi=0x7fffffff):
+        super().__init__(gain_mask, stop_mask, max_through, iz_lo, iz_hi)
+
+    def twin(self):
+        """-> the mapview.ViewParams with these values"""
+        from . import mapview
+        return mapview.ViewParams(int(self.gain_mask), int(self.stop_mask), int(self.max_through), int(self.iz_lo), int(self.iz_hi))
+
+
+class ViewInfo(C.Structure):
+    """qn_view_info (48 bytes), the layout of mapview.VIEW_DTYPE: a viewpoint's status, gain, ray ends, grid voxel and steps"""
+    _fields_ = [("status", C.c_uint32), ("gain", C.c_uint32), ("blocked", C.c_uint32), ("escaped", C.c_uint32), ("spent", C.c_uint32), ("reached", C.c_uint32),
+                ("ijk", C.c_int32 * 3), ("reserved", C.c_uint32), ("steps", C.c_uint64)]
+
+    def twin(self):
+        """-> the one-element mapview.VIEW_DTYPE array with these values"""
+        from . import mapview
+        return np.frombuffer(bytes(self), mapview.VIEW_DTYPE).copy()
+
+
+class ViewStats(C.Structure):
+    """qn_view_stats (48 bytes): every field but passes - a diagnostic of the GPU schedule - is an integer the twin shares"""
+    _fields_ = [(f, C.c_uint32) for f in ("viewpoints", "outside", "rays", "covered", "max_cover", "passes")] + [("reserved", C.c_uint32 * 2), ("total_gain", C.c_uint64),
+                                                                                                               ("steps", C.c_uint64)]
+
+    def twin(self):
+        """-> the mapview.ViewStats with these values"""
+        from . import mapview
+        return mapview.ViewStats(*(int(getattr(self, f)) for f in mapview.ViewStats._fields))
+
+
+QN_VIEW_OK = 0
+QN_VIEW_OUTSIDE = 1
+QN_VIEW_MAX_OFFSET = 1 << 25
+
+
 class ClusterParams(C.Structure):
     """qn_cluster_params (24 bytes): the joining distance, the smallest and the largest component that is a cluster, and the ground classes that take part
     (0: every finite point).  The defaults are interface choices, not measurements."""
@@ -1817,6 +1858,35 @@ class KeyframeStore:
         cost = np.zeros(max(R, 1), np.uint32); ijk = np.zeros((max(R, 1), 3), np.int32)
         self._check(self._l.qn_kf_map_frontier_costs(self.h, _p(cost), _p(ijk)))
         return cost[:R], ijk[:R]
+
+    # ---- view gain over the occupancy map (qn_kf_map_view_gain / _view_grid; numpy twin: qn_amd/mapview.py)
+    def map_view_gain(self, viewpoints, offsets, params=None):
+        """qn_kf_map_view_gain over the class bytes of the latest map_occupancy: from each of the (Q, 3) f64 world viewpoints the rays of the (R, 3) int32 table
+        `offsets` (1024ths of a voxel: mapview.sensor_offsets makes one) are cast until a voxel of stop_mask, the grid's face, max_through gain voxels or their
+        end, and the distinct gain voxels they pass through are counted.  params: a ViewParams (or a mapview.ViewParams); None: the defaults.
+        -> (info, a structured array of mapview.VIEW_DTYPE, one row per viewpoint; stats, a dict of the fields of qn_view_stats): all but passes equal those of
+        mapview.gain of the downloaded classes.  map_view_grid serves the cover volume."""
+        from . import mapview
+        p = ViewParams() if params is None else params
+        if not isinstance(p, ViewParams):
+            p = ViewParams(*(int(v) for v in p))
+        xyz = np.ascontiguousarray(viewpoints, dtype=np.float64).reshape(-1, 3)
+        off = np.ascontiguousarray(offsets, dtype=np.int32).reshape(-1, 3)
+        info = np.zeros(max(len(xyz), 1), mapview.VIEW_DTYPE)
+        st = ViewStats()
+        self._check(self._l.qn_kf_map_view_gain(self.h, _p(xyz), C.c_uint32(len(xyz)), _p(off), C.c_uint32(len(off)), C.byref(p), _p(info), C.byref(st)))
+        return info[:len(xyz)], {f: int(getattr(st, f)) for f, _ in ViewStats._fields_ if f != "reserved"}
+
+    def map_view_grid(self):
+        """qn_kf_map_view_grid -> (info, params, cover (D, H, W) uint32) of the latest map_view_gain: info the occupancy grid's dict, params a dict of the fields
+        of qn_view_params; cover[v] is the number of viewpoints that marked voxel v"""
+        g = OccupancyGrid(); p = ViewParams()
+        self._check(self._l.qn_kf_map_view_grid(self.h, C.byref(g), C.byref(p), None))
+        W, H, D = int(g.width), int(g.height), int(g.depth)
+        n = W * H * D
+        cover = np.zeros(max(n, 1), np.uint32)
+        self._check(self._l.qn_kf_map_view_grid(self.h, C.byref(g), C.byref(p), _p(cover)))
+        return self._occupancy_info(g), p.twin()._asdict(), cover[:n].reshape(D, H, W)
 
     # ---- the map slot's points clustered into objects (qn_kf_map_clusters / _cluster_points / _cluster_list / qn_kf_map_drop_rejected_clusters; numpy twin:
     # qn_amd/mapclusters.py)

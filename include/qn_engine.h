@@ -924,6 +924,56 @@ int  qn_kf_map_frontier_grid(qn_kf_store*, qn_occupancy_grid* info_out, qn_front
 int  qn_kf_map_frontier_regions(qn_kf_store*, qn_frontier_info* info_out, uint32_t capacity, uint32_t* count_out);
 int  qn_kf_map_frontier_list(qn_kf_store*, int32_t* ijk_out, int32_t* label_out, uint32_t capacity, uint32_t* count_out);   /* every frontier voxel, ascending linear index */
 int  qn_kf_map_frontier_costs(qn_kf_store*, uint32_t* cost_out /* R */, int32_t* ijk_out /* R x 3 */);
+/* ---- view gain over the occupancy map (csrc/qn_mapview.inc, part of csrc/qn_staticmap.hip; numpy twin and specification: qn_amd/mapview.py)
+ * What decides between two frontier regions: standing here, how much unknown space would the sensor actually see?  A region's size and faces are the size of
+ * an opening, not the volume behind it.  The answer is next-best-view gain: the sensor's rays are cast from each candidate viewpoint through the resident class
+ * bytes of the live qn_kf_map_occupancy result, each ray stops at the first occupied voxel, and the distinct unknown voxels the rays pass through are counted.
+ * Everything behind the viewpoint's quantisation is an integer; distinct is a set property and the tallies are integer sums, so every byte equals the twin's,
+ * bit for bit, whatever the schedule, the pass split or the order of the rays.
+ * Input: q viewpoints xyz (world coordinates, f64), 1 <= q <= 2^16; a ray table offsets, r rows of three int32_t, 1 <= r <= 2^20: a ray's end relative to its
+ *   start in the occupancy map's fixed point, 1024ths of a voxel, every |component| <= QN_VIEW_MAX_OFFSET (2^25).  The table is the caller's data, so no sine or
+ *   cosine is evaluated on the device.
+ * qn_view_params (32 bytes): gain_mask (class bits 0 .. 2, not 0; default 1 << QN_OCC_UNKNOWN), stop_mask (class bits 0 .. 2, may be 0, no bit of gain_mask;
+ *   default 1 << QN_OCC_OCCUPIED), max_through (0: no limit; default 0), iz_lo, iz_hi (i32: the band of layers, inclusive, clipped to the grid; defaults 0 and
+ *   INT32_MAX), reserved[3] (0).  The defaults are interface choices, not measurements.
+ * Viewpoint: A_k = int64(rint((x_k * inv) * 1024)), the occupancy map's quantisation (f64, every operation rounded on its own, half to even).  QN_VIEW_OUTSIDE (1)
+ *   when a coordinate is not finite, |x_k * inv| >= 2^20 or the voxel c(A) = A >> 10 lies outside the grid, else QN_VIEW_OK (0).  An OUTSIDE viewpoint casts
+ *   nothing and its row is zero apart from the status.
+ * Ray r of an OK viewpoint: B = A + offsets[r]; the visited voxels v_0 = c(A) .. v_n = c(B) are those of the occupancy walk (the same integer rule, a tie to the
+ *   lowest axis, an origin on a face heading down steps at once), examined in order, v_0 included: (1) v_i outside the grid: the ray ESCAPED, it ends and v_i is
+ *   not counted in steps; (2) otherwise steps += 1, and if the class bit of v_i is in stop_mask the ray is BLOCKED and ends; (3) otherwise, if its class bit is in
+ *   gain_mask, the pair (viewpoint, v_i) is marked when the layer iz lies in the band, through += 1, band or not, and if max_through != 0 and through ==
+ *   max_through the ray is SPENT and ends; (4) if v_n has been examined without an end, the ray REACHED.  The four ray ends - blocked, escaped, spent, reached -
+ *   exclude each other; a ray with offset (0, 0, 0) examines v_0 only.
+ * qn_view_info (48 bytes), one per viewpoint: status, gain (the number of distinct voxels marked for the viewpoint), blocked, escaped, spent, reached (rays),
+ *   ijk[3] (the viewpoint's grid voxel, (0, 0, 0) when OUTSIDE), reserved (0), steps (u64).
+ * cover: one uint32_t per voxel, W H D, x fastest, linear index (iz H + iy) W + ix: the number of viewpoints that marked the voxel.  Sum cover = sum gain.
+ * qn_view_stats (48 bytes): viewpoints (q), outside, rays (r), covered (the voxels with cover >= 1), max_cover, total_gain, steps (the sum of the rows') - these
+ *   equal the twin's; passes, a diagnostic of the GPU schedule that the twin does not have; reserved[2] (0).
+ * qn_kf_map_view_gain: QN_ERR_INVALID_ARG, before anything runs and with the previous result intact: a null pointer, q or r outside its range, a gain_mask that
+ *   is 0 or has a bit >= 3, a stop_mask with a bit >= 3 or one of gain_mask, iz_lo > iz_hi, reserved != 0, an offset beyond the limit.  QN_ERR_NOT_READY without a
+ *   live occupancy result.  On a 0 x 0 x 0 grid every viewpoint is OUTSIDE and the call succeeds.  Device memory: 4 bytes per voxel for cover (grown half again as
+ *   large beside the previous volume, kept between calls); when it cannot be allocated QN_ERR_HIP with the previous result intact.  The result stays resident
+ *   until the next successful qn_kf_map_view_gain or qn_kf_map_occupancy; the latter ends it; qn_kf_map_distance, qn_kf_map_route and qn_kf_map_frontiers do not
+ *   touch it.  The kernels: k_mv_origin (the quantisation, one viewpoint per lane), k_mv_cast (one lane per viewpoint and ray; a bitset per viewpoint over its
+ *   reach box - the viewpoint's voxel +- ((max |offset component| >> 10) + 1), clipped to the grid - makes a voxel count once: a plain read first, the returning
+ *   atomicOr only when the bit looks unset), k_mv_stats (covered, max_cover and the sum in one pass over cover).  The viewpoints go in passes that fit a scratch
+ *   budget; the whole call is one synchronisation with the host whatever the number of passes.  Environment, read per call, the same bytes either way:
+ *   QN_VIEW_PASS=<n> caps the viewpoints of a pass, QN_VIEW_NO_PEEK=1 always issues the atomicOr (the yardstick of tools/gpu_map_view_time.py).
+ *   Time on an MI355X (tools/gpu_map_view_time.py; 57 600 rays of 20 m at voxel 0.3, a volume of 1.08e7 voxels): 0.67 / 0.73 / 1.95 ms for 1 / 16 / 256 viewpoints,
+ *   beside 200 ms for qn_kf_map_occupancy and 1.0 ms for qn_kf_map_frontiers on the same store (profiles/EXPERIMENTS.md).
+ * qn_kf_map_view_grid: *info_out (the occupancy grid's), *params_out (the parameters used) and cover_out, W H D values of 4 bytes; cover_out may be NULL to
+ *   fetch the dimensions first.  QN_ERR_NOT_READY without a live view result. */
+#define QN_VIEW_OK 0
+#define QN_VIEW_OUTSIDE 1
+#define QN_VIEW_MAX_OFFSET (1 << 25)
+typedef struct qn_view_params { uint32_t gain_mask, stop_mask, max_through; int32_t iz_lo, iz_hi; uint32_t reserved[3]; } qn_view_params;   /* 32 bytes */
+typedef struct qn_view_info   { uint32_t status, gain, blocked, escaped, spent, reached; int32_t ijk[3]; uint32_t reserved; uint64_t steps; } qn_view_info;   /* 48 bytes */
+typedef struct qn_view_stats  { uint32_t viewpoints, outside, rays, covered, max_cover, passes, reserved[2]; uint64_t total_gain, steps; } qn_view_stats;   /* 48 bytes */
+void qn_view_default_params(qn_view_params* p);
+int  qn_kf_map_view_gain(qn_kf_store*, const double* xyz /* Q x 3 */, uint32_t q, const int32_t* offsets /* R x 3 */, uint32_t r, const qn_view_params* params,
+                         qn_view_info* info_out /* Q */, qn_view_stats* stats_out);
+int  qn_kf_map_view_grid(qn_kf_store*, qn_occupancy_grid* info_out, qn_view_params* params_out, uint32_t* cover_out /* W H D, may be NULL */);
 /* ---- the map's points clustered into objects (csrc/qn_mapclusters.inc, part of csrc/qn_mapoutliers.hip; numpy twin and specification: qn_amd/mapclusters.py)
  * After qn_kf_map_ground every point is GROUND, OBSTACLE or OVERHEAD, but the obstacles are an unstructured set.  These calls run PCL's
  * EuclideanClusterExtraction over the store's map slot on the GPU: connected components of the radius graph, each with a size, a box and a centroid, and the

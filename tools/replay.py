@@ -355,7 +355,7 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
         drop_ground=False, map_clusters=False, cluster_tol=0.5, cluster_min=10, cluster_max=0xffffffff, drop_small_clusters=False,
         localize_every=0, localize_radius=35.0, localize_shift=0.5, localize_yaw=3.0, occupancy_3d=False, occ_voxel=0.3, occ_min_range=0.5,
         occ_max_range=60.0, occ_shell=1, occ_slice=None, occ_distance=False, occ_dist_max=16, occ_unknown_obstacle=False, robot_radius=None, occ_route=None,
-        route_from=None, route_min_d2=4, route_planar=False, occ_frontiers=False, frontier_min_size=8):
+        route_from=None, route_min_d2=4, route_planar=False, occ_frontiers=False, frontier_min_size=8, occ_view_gain=False, view_range=20.0, view_beams=16, view_azimuth=300):
     """sensor = "uniform": keyframe clouds sampled uniformly by area inside a disc (make_stream); "spinning": ray-cast spinning-LiDAR
     scans from the ground-truth poses of the same figure-8 (make_lidar_stream).  detector = "radius": the candidate is the closest older
     keyframe within `radius` of the corrected position (LC:34-56); "scancontext": the older keyframe nearest by Scan Context distance, kept
@@ -445,6 +445,13 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
     used.  frontiers.csv: one row per region, "region size faces cx cy cz lo_x lo_y lo_z hi_x hi_y hi_z" - its number, voxels, unknown faces, centroid in metres
     and box of grid indices; with occ_route the row also carries "reach ex ey ez", the cost in metres of reaching the region down the route field (inf when no
     voxel of it is reached) and the centre of the voxel where it is entered (nan then).
+    occ_view_gain (with occupancy_3d and occ_frontiers; default False): next-best-view gain, one viewpoint per frontier region - with occ_route the centre of the
+    region's cheapest voxel under the route field (its root voxel when no voxel of it is reached), else the centre of its root voxel.  From each viewpoint the rays
+    of a spinning sensor of view_beams beams between -15 and 15 degrees, view_azimuth steps a turn and view_range metres (mapview.sensor_offsets) are cast through
+    the volume until an occupied voxel, and the distinct unknown voxels they pass through are counted (qn_amd/mapview.py) - on the GPU backend by
+    KeyframeStore.map_view_gain, on the oracle backend by the numpy twin.  out["view_gain"]: viewpoints, outside, rays, covered, max_cover, total_gain, steps and
+    the sensor.  view_gain.csv: one row per region, "region x y z gain blocked escaped spent reached" - the viewpoint in metres, its gain and its rays by their
+    end.  frontiers.csv stays as it is.
     moving_boxes = N (sensor="spinning" only; default 0: every run is what it was): N extra boxes in the scene that stand somewhere else in every keyframe
     (moving_box_prims), so every keyframe is cast by a call of its own."""
     if detector not in ("radius", "scancontext"):
@@ -534,6 +541,16 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
     if occ_frontiers:
         from qn_amd import mapfrontier
         mapfrontier.check_params(mapfrontier.FrontierParams(min_size=frontier_min_size))          # (raises ValueError on a parameter outside its range)
+    if (occ_view_gain or view_range != 20.0 or view_beams != 16 or view_azimuth != 300) and not (occupancy_3d and occ_frontiers and occ_view_gain):
+        raise ValueError("occ_view_gain needs occupancy_3d and occ_frontiers, and view_range, view_beams and view_azimuth need occ_view_gain (a viewpoint per region)")
+    if occ_view_gain:
+        from qn_amd import mapview
+        if not (isinstance(view_beams, (int, np.integer)) and isinstance(view_azimuth, (int, np.integer)) and view_beams >= 1 and view_azimuth >= 1 and
+                view_beams * view_azimuth <= mapview.MAX_RAYS):
+            raise ValueError("view_beams and view_azimuth must be integers >= 1 with at most 2^20 rays in all")
+        if not (np.isfinite(view_range) and view_range > 0):
+            raise ValueError("view_range must be finite and > 0")
+        view_offsets = mapview.sensor_offsets(occ_voxel, view_range, view_beams, view_azimuth, -15.0, 15.0)      # (raises ValueError beyond the offset limit)
     if drop_small_clusters and not map_clusters:
         raise ValueError("drop_small_clusters needs map_clusters (the clumps come from its components)")
     if map_clusters and backend != "gpu":
@@ -895,6 +912,22 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
                             row += " %.6f %.6f %.6f %.6f" % ((float(metres[k]),) + tuple(entry[k]))
                         ff.write(row + "\n")
                 out["frontiers"] = dict({k: int(fst[k]) for k in mapfrontier.FrontierStats._fields}, **fp._asdict())
+                if occ_view_gain and len(finfo):
+                    root = finfo["root"].astype(np.int64)
+                    at = np.stack([root % g.width, (root // g.width) % g.height, root // (g.width * g.height)], axis=1)
+                    if reach is not None:
+                        at = np.where((reach[0] < maproute.BLOCKED)[:, None], reach[1], at)
+                    vps = mapoccupancy.centres(at, g)
+                    if backend == "gpu":
+                        vinfo, vst = store.map_view_gain(vps, view_offsets)
+                    else:
+                        vr = mapview.gain(res["classes"], g, vps, view_offsets)
+                        vinfo, vst = vr["info"], vr["stats"]._asdict()
+                    with open(os.path.join(save_dir, "view_gain.csv"), "w") as fv:
+                        fv.write("region x y z gain blocked escaped spent reached\n")
+                        for k, r in enumerate(vinfo):
+                            fv.write("%d %.6f %.6f %.6f %d %d %d %d %d\n" % ((k,) + tuple(vps[k]) + tuple(int(r[f]) for f in ("gain", "blocked", "escaped", "spent", "reached"))))
+                    out["view_gain"] = dict({k: int(vst[k]) for k in mapview.ViewStats._fields}, range=float(view_range), beams=int(view_beams), azimuth=int(view_azimuth))
             out["occupancy"] = {k: int(st[k]) for k in ("n_rays", "total_misses", "width", "height", "depth", "occupied", "free", "unknown")}
             if layers is not None:
                 out["occupancy"]["slice_layers"] = [int(layers[0]), int(layers[1])]
@@ -1066,6 +1099,12 @@ if __name__ == "__main__":
                     help="with --occupancy-3d: also find the exploration frontiers, the free voxels beside unknown space grouped into regions, written to frontiers.csv "
                          "(over the layers of --occ-slice when given; with --occ-route each region's reach cost and entry voxel too)")
     ap.add_argument("--frontier-min-size", type=int, default=8, help="with --occ-frontiers: the smallest component, in voxels, that is a region")
+    ap.add_argument("--occ-view-gain", action="store_true",
+                    help="with --occ-frontiers: also the next-best-view gain of one viewpoint per region (with --occ-route where the region is entered, else its root voxel): "
+                         "the distinct unknown voxels a spinning sensor's rays would pass through, written to view_gain.csv")
+    ap.add_argument("--view-range", type=float, default=20.0, help="with --occ-view-gain: the sensor's range [m]")
+    ap.add_argument("--view-beams", type=int, default=16, help="with --occ-view-gain: the sensor's beams, between -15 and 15 degrees")
+    ap.add_argument("--view-azimuth", type=int, default=300, help="with --occ-view-gain: the sensor's steps a turn")
     ap.add_argument("--moving-boxes", type=int, default=0, help="with --sensor spinning: this many boxes that stand somewhere else in every keyframe")
     ap.add_argument("--backend", choices=["gpu", "oracle"], default="gpu", help="the engine on the GPU, or the CPU oracle")
     a = ap.parse_args()
@@ -1097,6 +1136,10 @@ if __name__ == "__main__":
         ap.error("--occ-frontiers needs --occupancy-3d")
     if a.frontier_min_size != 8 and not a.occ_frontiers:
         ap.error("--frontier-min-size needs --occ-frontiers")
+    if a.occ_view_gain and not (a.occupancy_3d and a.occ_frontiers):
+        ap.error("--occ-view-gain needs --occupancy-3d and --occ-frontiers")
+    if (a.view_range != 20.0 or a.view_beams != 16 or a.view_azimuth != 300) and not a.occ_view_gain:
+        ap.error("--view-range, --view-beams and --view-azimuth need --occ-view-gain")
     run(a.keyframes, a.seed, a.quatro, save_dir=a.save_dir, save_map_leaf=a.save_map_leaf, sensor=a.sensor, detector=a.detector, yaw_bias=a.yaw_bias,
         verify=a.verify, sc_top_k=a.sc_top_k, backend=a.backend, loop_every=a.loop_every, catch_up=a.catch_up, submap_matching=a.submap_matching,
         min_overlap=a.min_overlap, overlap_radius=a.overlap_radius, max_see_through=a.max_see_through, static_map=a.static_map, moving_boxes=a.moving_boxes,
@@ -1107,4 +1150,5 @@ if __name__ == "__main__":
         localize_shift=a.localize_shift, localize_yaw=a.localize_yaw, occupancy_3d=a.occupancy_3d, occ_voxel=a.occ_voxel, occ_min_range=a.occ_min_range,
         occ_max_range=a.occ_max_range, occ_shell=a.occ_shell, occ_slice=a.occ_slice, occ_distance=a.occ_distance, occ_dist_max=a.occ_dist_max,
         occ_unknown_obstacle=a.occ_unknown_obstacle, robot_radius=a.robot_radius, occ_route=a.occ_route, route_from=a.route_from, route_min_d2=a.route_min_d2,
-        route_planar=a.route_planar, occ_frontiers=a.occ_frontiers, frontier_min_size=a.frontier_min_size)
+        route_planar=a.route_planar, occ_frontiers=a.occ_frontiers, frontier_min_size=a.frontier_min_size, occ_view_gain=a.occ_view_gain, view_range=a.view_range,
+        view_beams=a.view_beams, view_azimuth=a.view_azimuth)
