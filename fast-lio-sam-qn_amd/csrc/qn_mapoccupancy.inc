@@ -17,7 +17,8 @@
 //   list      OcList, the predicate and the payload of the stable voxel list of qn_dense_grid.cuh (k_dg_list_flag / k_scan_rows / k_dg_list_pick).
 //   slice     the largest class over a band of layers: k_dg_slice<uint8_t, op_max> of qn_dense_grid.cuh, one column per lane.
 // The grid itself - OcGrid, the index arithmetic, the fixed point's OC_S and OC_COORD_LIMIT, the lookup of the live results - is qn_dense_grid.cuh's, shared with
-// the fields over it (qn_mapdistance.inc, qn_maproute.inc, qn_mapfrontier.inc, included behind this file).
+// the fields over it (qn_mapdistance.inc, qn_maproute.inc, qn_mapfrontier.inc, included behind this file).  qn_mapoccupancy_update.inc, right behind this file,
+// brings the resident volume to another list in place with the same walk, classify pass and argument checks (qn_kf_map_occupancy_update).
 // Host synchronisations of qn_kf_map_occupancy: two - the extent, the counts.  Integer atomics only, no scratch memory, no dynamically indexed private array.
 // Part of qn_staticmap.hip's translation unit (included at its end), the unit that turns a list with poses into per-record ray evidence: the results hang on
 // that unit's StaticState and take no slot of their own.  They do not depend on the map slot.
@@ -87,8 +88,9 @@ __global__ void __launch_bounds__(OC_BLOCK) k_oc_extent(const OcEntry* __restric
 
 // The walk of one ray a lane, integers only.  Every lane of the wave calls it (ray: this lane has one); all rays of the wave start in the same voxel.
 // c, r, D, rem and the step are kept per axis in scalars; D <= 2^31 and r <= D + 2^10 fit 32 bits, their products 64.  FOLD: the wave's adds to v_0 as one
-// add of the popcount (false: one a lane like every other voxel - the yardstick of tools/gpu_map_occupancy_time.py --no-fold; the same bytes).
-template <bool FOLD>
+// add of the popcount (false: one a lane like every other voxel - the yardstick of tools/gpu_map_occupancy_time.py --no-fold; the same bytes).  SUB: the
+// same walk takes the ray's counts out again (qn_mapoccupancy_update.inc) - every add is 0xFFFFFFFF, -1 mod 2^32, the wave's folded one the popcount times that.
+template <bool FOLD, bool SUB = false>
 __device__ __forceinline__ void oc_walk(bool ray, const int32_t (&A)[3], const int32_t (&B)[3], const OcGrid G, uint32_t shell, uint32_t* __restrict__ hits,
                                         uint32_t* __restrict__ misses) {
   const int32_t stride[3] = {1, (int32_t)G.W, (int32_t)(G.W * G.H)};
@@ -106,17 +108,18 @@ __device__ __forceinline__ void oc_walk(bool ray, const int32_t (&A)[3], const i
     n += rem[k];
   }
   const uint32_t carve = ray && n > shell ? n - shell : 0;           // the voxels v_0 .. v_(carve - 1) get a miss
+  constexpr uint32_t one = SUB ? 0xFFFFFFFFu : 1u;
   // v_0 is the same voxel in every lane: one add of the popcount for the wave
   if (FOLD) {
     const unsigned long long first = __ballot(carve > 0);
-    if (carve > 0 && (threadIdx.x & 63) == (uint32_t)(__ffsll((long long)first) - 1) && (uint32_t)lin < G.cells) atomicAdd(&misses[lin], (uint32_t)__popcll(first));
+    if (carve > 0 && (threadIdx.x & 63) == (uint32_t)(__ffsll((long long)first) - 1) && (uint32_t)lin < G.cells) atomicAdd(&misses[lin], (uint32_t)__popcll(first) * one);
   }
   if (!ray) return;
-  if ((uint32_t)lend < G.cells) atomicAdd(&hits[lend], 1u);          // (always inside: the extremes made the grid; kept as a guard)
+  if ((uint32_t)lend < G.cells) atomicAdd(&hits[lend], one);         // (always inside: the extremes made the grid; kept as a guard)
   uint32_t r0 = r[0], r1 = r[1], r2 = r[2], m0 = rem[0], m1 = rem[1], m2 = rem[2];
   const uint32_t D0 = D[0], D1 = D[1], D2 = D[2];
   for (uint32_t i = 0; i < carve; i++) {
-    if ((!FOLD || i != 0) && (uint32_t)lin < G.cells) atomicAdd(&misses[lin], 1u);
+    if ((!FOLD || i != 0) && (uint32_t)lin < G.cells) { if (SUB) atomicAdd(&misses[lin], 0xFFFFFFFFu); else atomicAdd(&misses[lin], 1u); }
     // among the axes that still have a step to make, the smallest r / D; a tie goes to the lowest axis
     int b; uint32_t rb, Db;
     if (m0 > 0) { b = 0; rb = r0; Db = D0; } else if (m1 > 0) { b = 1; rb = r1; Db = D1; } else { b = 2; rb = r2; Db = D2; }
@@ -175,10 +178,39 @@ struct OccState {
   std::shared_ptr<struct DistState> dist;                // the distance field of qn_mapdistance.inc (included behind this file, where the type is completed)
   std::shared_ptr<struct FrontierState> frontier;        // the frontier regions of qn_mapfrontier.inc (included last), beside the field: they need only the classes
   std::shared_ptr<struct ViewState> view;                // the view gain of qn_mapview.inc (included behind it), beside them: it needs only the classes too
-};
+  std::shared_ptr<struct OccLedger> ledger;              // who contributed what to the counts (qn_mapoccupancy_update.inc, included behind this file); only
+};                                                       // qn_kf_map_occupancy_update leaves one, a successful qn_kf_map_occupancy drops it
 void md_end(DistState*);                                 // (qn_mapdistance.inc) a new occupancy result ends the field of the previous one; its buffers stay
 void mf_end(FrontierState*);                             // (qn_mapfrontier.inc) and the frontier regions of the previous one
 void mv_end(ViewState*);                                 // (qn_mapview.inc) and its view gain
+
+// Every argument of qn_kf_map_occupancy and qn_kf_map_occupancy_update (but the outputs), checked before anything runs: QN_ERR_INVALID_ARG, or QN_ERR_CAPACITY
+// at 2^32 records; QN_OK: ent[e] = the records and the pose rows of entry e, b0 its first block, *tiles the blocks of all
+int oc_check_list(qn_kf_store* s, const int32_t* ids, const double* poses16, uint32_t count, const qn_occupancy_params* params, std::vector<OcEntry>& ent,
+                  uint64_t* tiles) {
+  if (!s || !ids || !poses16 || count == 0 || !params) return QN_ERR_INVALID_ARG;
+  const qn_occupancy_params& P = *params;
+  if (!std::isfinite(P.voxel) || !(P.voxel > 0.0) || !std::isfinite(P.min_range) || !(P.min_range >= 0.0) || !std::isfinite(P.max_range) ||
+      !(P.max_range > P.min_range) || P.min_hits < 1 || P.hit_weight < 1 || P.reserved[0] != 0 || P.reserved[1] != 0 || P.reserved[2] != 0)
+    return QN_ERR_INVALID_ARG;
+  const size_t n_kf = qn_kf_int_count(s);
+  for (uint32_t e = 0; e < count; e++) {
+    if (ids[e] < 0 || (size_t)ids[e] >= n_kf) return QN_ERR_INVALID_ARG;
+    for (int k = 0; k < 16; k++) if (!std::isfinite(poses16[16 * (size_t)e + k])) return QN_ERR_INVALID_ARG;
+  }
+  uint64_t total = 0;
+  *tiles = 0;
+  ent.resize(count);
+  for (uint32_t e = 0; e < count; e++) {
+    uint32_t n = 0;
+    const float4* pts = qn_kf_int_keyframe(s, ids[e], &n);
+    ent[e].pts = pts; ent[e].n = n; ent[e].b0 = (uint32_t)*tiles;
+    memcpy(ent[e].P, poses16 + 16 * (size_t)e, sizeof(double) * 12);
+    total += n; *tiles += dg_blocks(n);
+    if (total > 0xFFFFFFFFull) return QN_ERR_CAPACITY;
+  }
+  return QN_OK;
+}
 
 }  // namespace
 
@@ -191,26 +223,12 @@ extern "C" void qn_occupancy_default_params(qn_occupancy_params* p) {
 extern "C" int qn_kf_map_occupancy(qn_kf_store* s, const int32_t* ids, const double* poses16, uint32_t count, const qn_occupancy_params* params,
                                    qn_occupancy_stats* stats_out) {
   // ---- every argument is checked before anything runs
-  if (!s || !ids || !poses16 || count == 0 || !params || !stats_out) return QN_ERR_INVALID_ARG;
+  if (!stats_out) return QN_ERR_INVALID_ARG;
+  uint64_t tiles = 0;
+  std::vector<OcEntry> ent;
+  const int ok = oc_check_list(s, ids, poses16, count, params, ent, &tiles);
+  if (ok != QN_OK) return ok;
   const qn_occupancy_params P = *params;
-  if (!std::isfinite(P.voxel) || !(P.voxel > 0.0) || !std::isfinite(P.min_range) || !(P.min_range >= 0.0) || !std::isfinite(P.max_range) ||
-      !(P.max_range > P.min_range) || P.min_hits < 1 || P.hit_weight < 1 || P.reserved[0] != 0 || P.reserved[1] != 0 || P.reserved[2] != 0)
-    return QN_ERR_INVALID_ARG;
-  const size_t n_kf = qn_kf_int_count(s);
-  for (uint32_t e = 0; e < count; e++) {
-    if (ids[e] < 0 || (size_t)ids[e] >= n_kf) return QN_ERR_INVALID_ARG;
-    for (int k = 0; k < 16; k++) if (!std::isfinite(poses16[16 * (size_t)e + k])) return QN_ERR_INVALID_ARG;
-  }
-  uint64_t total = 0, tiles = 0;
-  std::vector<OcEntry> ent(count);
-  for (uint32_t e = 0; e < count; e++) {
-    uint32_t n = 0;
-    const float4* pts = qn_kf_int_keyframe(s, ids[e], &n);
-    ent[e].pts = pts; ent[e].n = n; ent[e].b0 = (uint32_t)tiles;
-    memcpy(ent[e].P, poses16 + 16 * (size_t)e, sizeof(double) * 12);
-    total += n; tiles += dg_blocks(n);
-    if (total > 0xFFFFFFFFull) return QN_ERR_CAPACITY;
-  }
   QN_KFCHK(s, hipSetDevice(qn_kf_int_device(s)));
   StaticState* unit = nullptr;
   const int rc = qn_kf_ext_state(s, QN_KF_INT_EXT_STATIC, &unit);
@@ -300,6 +318,7 @@ extern "C" int qn_kf_map_occupancy(qn_kf_store* s, const int32_t* ids, const dou
   }
   st->info = info;
   st->live = true;
+  st->ledger.reset();                                       // (the counts are no longer those of an update: the next one starts from nothing)
   md_end(st->dist.get());
   mf_end(st->frontier.get());
   mv_end(st->view.get());

@@ -287,6 +287,7 @@ extern "C" int qn_kf_build_map_static(qn_kf_store* s, double leaf, const float**
 }
 
 #include "qn_mapoccupancy.inc"
+#include "qn_mapoccupancy_update.inc"
 #include "qn_mapdistance.inc"
 #include "qn_maproute.inc"
 #include "qn_mapfrontier.inc"

@@ -873,6 +873,13 @@ class OccupancyGrid(C.Structure):
     _fields_ = [("origin", C.c_double * 3), ("voxel", C.c_double), ("width", C.c_uint32), ("height", C.c_uint32), ("depth", C.c_uint32), ("minc", C.c_int32 * 3)]
 
 
+class OccupancyUpdate(C.Structure):
+    """qn_occupancy_update (64 bytes): what qn_kf_map_occupancy_update did - the entries kept, added and removed, whether it started from nothing, whether the
+    counts were moved to another box, the records the walks read, the box of the new grid outside which no count changed, the rays added and removed"""
+    _fields_ = ([(f, C.c_uint32) for f in ("entries_kept", "entries_added", "entries_removed", "rebuilt", "regridded", "records_walked")] +
+                [("dirty_lo", C.c_int32 * 3), ("dirty_hi", C.c_int32 * 3), ("rays_added", C.c_uint64), ("rays_removed", C.c_uint64)])
+
+
 QN_OCC_UNKNOWN, QN_OCC_FREE, QN_OCC_OCCUPIED = range(3)
 QN_OCC_MAX_CELLS = 1 << 27
 
@@ -1675,6 +1682,20 @@ class KeyframeStore:
         st = OccupancyStats()
         self._check(self._l.qn_kf_map_occupancy(self.h, _p(ids), _p(poses), C.c_uint32(len(ids)), C.byref(p), C.byref(st)))
         return {f: int(getattr(st, f)) for f, _ in OccupancyStats._fields_ if f != "reserved"}
+
+    def map_occupancy_update(self, ids, poses, params=None):
+        """qn_kf_map_occupancy_update: the resident volume brought to this list in place - the entries whose id and pose bytes the volume already holds are
+        kept, the others are walked in, and what the list no longer names is walked out again.  The arguments are map_occupancy's.  -> (stats, update): stats
+        the dict map_occupancy returns for the same list, update a dict of the fields of qn_occupancy_update (dirty_lo, dirty_hi as tuples), equal to
+        mapoccupancy.update's.  Afterwards every getter returns the bytes it returns after map_occupancy of the same list."""
+        ids = np.ascontiguousarray(ids, dtype=np.int32); poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(len(ids), 16)
+        p = OccupancyParams() if params is None else params
+        if not isinstance(p, OccupancyParams):
+            p = OccupancyParams(float(p.voxel), float(p.min_range), float(p.max_range), int(p.shell), int(p.min_hits), int(p.hit_weight))
+        st = OccupancyStats(); up = OccupancyUpdate()
+        self._check(self._l.qn_kf_map_occupancy_update(self.h, _p(ids), _p(poses), C.c_uint32(len(ids)), C.byref(p), C.byref(st), C.byref(up)))
+        upd = {f: (tuple(int(v) for v in getattr(up, f)) if f.startswith("dirty") else int(getattr(up, f))) for f, _ in OccupancyUpdate._fields_}
+        return {f: int(getattr(st, f)) for f, _ in OccupancyStats._fields_ if f != "reserved"}, upd
 
     @staticmethod
     def _occupancy_info(g):

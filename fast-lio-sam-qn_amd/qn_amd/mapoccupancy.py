@@ -25,6 +25,8 @@ takes: ids may repeat, a list position is an ENTRY) are walked through a voxel g
                a ray the grid is 0 x 0 x 0 and minc (0, 0, 0).
   classes      one byte per voxel: UNKNOWN 0 (hits = misses = 0), OCCUPIED 2 (hits >= min_hits and hits * hit_weight >= misses), FREE 1 (everything else).
 Everything after the quantisation is an integer and integer adds commute, so no order of anything changes a byte.
+  update       the same volume brought to another list in place (update(), the twin of csrc/qn_mapoccupancy_update.inc, qn_kf_map_occupancy_update): for the same
+               reason an entry's counts leave again when its rays are walked with -1, and the result is classify's of the new list in every byte.
 """
 import math
 from collections import namedtuple
@@ -249,3 +251,152 @@ def centres(ijk, grid):
     """the centres (minc + i + 0.5) * voxel of the voxels ijk -> (m, 3) f64"""
     g = OccupancyGrid(*grid)
     return (np.asarray(ijk, np.float64).reshape(-1, 3) + np.asarray(g.minc, np.float64) + 0.5) * float(g.voxel)
+
+
+# ---- the volume updated in place: the specification of qn_kf_map_occupancy_update (csrc/qn_mapoccupancy_update.inc)
+OccupancyUpdate = namedtuple("OccupancyUpdate", "entries_kept entries_added entries_removed rebuilt regridded records_walked dirty_lo dirty_hi rays_added rays_removed")
+
+
+def accumulate(A, B, minc, dims, shell, sign, hits, misses):
+    """the rays A -> B (fixed point, (m, 3) int64) walked through the grid at voxel minc of dims = (W, H, D): hits[v_n] += sign and misses[v_i] += sign for
+    i < n - shell, in place on the flat int64 arrays.  The walk is walk()'s, all rays one step a round."""
+    if not len(A):
+        return
+    Wd, Hd, Dd = (int(v) for v in dims)
+    cells = Wd * Hd * Dd
+    minc = np.asarray(minc, np.int64)
+    stride = np.array([1, Wd, Wd * Hd], np.int64)
+    c = A >> S; cend = B >> S
+    assert ((c >= minc) & (cend >= minc) & (c < minc + np.array([Wd, Hd, Dd])) & (cend < minc + np.array([Wd, Hd, Dd]))).all(), "a ray end outside the grid"
+    s = np.sign(B - A); D = np.abs(B - A); rem = np.abs(cend - c)
+    r = np.where(s > 0, ((c + 1) << S) - A, A - (c << S))
+    n = rem.sum(axis=1)
+    lin = ((c - minc) * stride).sum(axis=1)
+    hits += sign * np.bincount(((cend - minc) * stride).sum(axis=1), minlength=cells)
+    carve = n - int(shell)
+    step = s * stride
+    idx = np.arange(len(A))
+    i = 0
+    while True:
+        live = n[idx] > i
+        if not live.all():
+            idx = idx[live]
+        if not len(idx):
+            break
+        m = carve[idx] > i
+        if m.any():
+            misses += sign * np.bincount(lin[idx[m]], minlength=cells)
+        rr = r[idx]; DD = D[idx]; on = rem[idx] > 0
+        best = np.where(on[:, 0], 0, np.where(on[:, 1], 1, 2))
+        for k in (1, 2):
+            rb = np.take_along_axis(rr, best[:, None], 1)[:, 0]; Db = np.take_along_axis(DD, best[:, None], 1)[:, 0]
+            best = np.where(on[:, k] & (k > best) & (rr[:, k] * Db < rb * DD[:, k]), k, best)
+        lin[idx] += step[idx, best]
+        r[idx, best] += ONE
+        rem[idx, best] -= 1
+        i += 1
+
+
+def _pose44(rows34):
+    T = np.eye(4)
+    T[:3] = rows34
+    return T
+
+
+def update(ledger, clouds, ids, poses, params=None):
+    """The volume of `ledger` (None: none yet) brought to the list (ids, poses): clouds[id] = the (n, >= 3) f32 records of keyframe id, poses[e] the 4x4 f64 pose
+    of entry e.  -> (result, upd, ledger): result has the form of classify's and equals classify of the list in every array, statistic and the grid; upd is an
+    OccupancyUpdate; ledger is the new state (the one passed in is not changed, so a refused call - an exception - leaves it good).
+      ledger   ray_params (voxel, min_range, max_range, shell); rows, one per entry: id, the pose's first 12 doubles, the five record counts, the box (lo, hi) of
+               the entry's ray ends in voxel coordinates or None without a ray; minc, dims (W, H, D); hits, misses (flat int64); outside: the counts the last
+               regrid found in old voxels outside the new box (always 0, asserted).
+      match    a multiset: an entry is kept when its id and the bytes of its 12 doubles equal an unmatched row (so -0.0 is not 0.0); the unmatched rows are
+               removed, the unmatched entries added.  Without a ledger, or with another voxel, min_range, max_range or shell: rebuilt - every entry is added to
+               an empty volume.  min_hits and hit_weight only form the classes.
+      box      the union of the boxes of the new rows; without a ray 0 x 0 x 0 at minc (0, 0, 0).  CapacityError as classify raises it, before anything changes.
+      order    the removed rows' rays with -1 in the old grid (from clouds[row id] under the row's pose); when the box differs, the counts of the voxels both
+               boxes hold move, every other new voxel starts at 0; the added entries' rays with +1; the classes.
+      dirty    the union of the boxes of the added and removed rows minus the new minc, clipped to the new grid; (0, 0, 0) > (-1, -1, -1) when that is empty."""
+    p = OccupancyParams() if params is None else OccupancyParams(*params)
+    check_params(p)
+    ids = [int(i) for i in ids]
+    P = np.asarray(poses, np.float64).reshape(-1, 4, 4)
+    if not ids or len(P) != len(ids):
+        raise ValueError("mapoccupancy: %d entries but %d poses" % (len(ids), len(P)))
+    if not np.isfinite(P).all():
+        raise ValueError("mapoccupancy: a pose that is not finite")
+    ray_params = (float(p.voxel), float(p.min_range), float(p.max_range), int(p.shell))
+    rebuilt = ledger is None or ledger["ray_params"] != ray_params
+    old_rows = [] if rebuilt else ledger["rows"]
+    unmatched = {}
+    for k, row in enumerate(old_rows):
+        unmatched.setdefault((row["id"], row["pose"].tobytes()), []).append(k)
+    rows, fresh = [], []
+    for i, T in zip(ids, P):
+        pose = np.ascontiguousarray(T[:3])
+        left = unmatched.get((i, pose.tobytes()))
+        if left:
+            rows.append(old_rows[left.pop()])
+            continue
+        A, B, cnt = rays([clouds[i]], [T], p)
+        c = np.concatenate([A >> S, B >> S])
+        row = dict(id=i, pose=pose.copy(), cnt=tuple(cnt), box=(tuple(int(v) for v in c.min(axis=0)), tuple(int(v) for v in c.max(axis=0))) if len(A) else None)
+        rows.append(row); fresh.append((row, A, B))
+    gone = [old_rows[k] for left in unmatched.values() for k in left]
+    if sum(r["cnt"][0] for r in rows) >= 1 << 32:
+        raise CapacityError("mapoccupancy: 2^32 records or more")
+    boxes = [r["box"] for r in rows if r["box"]]
+    voxel = float(p.voxel)
+    if boxes:
+        minc = np.min([b[0] for b in boxes], axis=0).astype(np.int64); maxc = np.max([b[1] for b in boxes], axis=0).astype(np.int64)
+        dims = tuple(int(v) for v in maxc - minc + 1)
+        if max(dims) > MAX_SIDE or dims[0] * dims[1] * dims[2] > MAX_CELLS:
+            raise CapacityError("mapoccupancy: a grid of more than 2^27 voxels (or 2^15 a side)")
+    else:
+        minc = np.zeros(3, np.int64); dims = (0, 0, 0)
+    cells = dims[0] * dims[1] * dims[2]
+    outside = 0
+    if rebuilt:
+        regridded = False
+        hits = np.zeros(cells, np.int64); misses = np.zeros(cells, np.int64)
+    else:
+        ominc = np.asarray(ledger["minc"], np.int64); odims = tuple(ledger["dims"])
+        hits = ledger["hits"].copy(); misses = ledger["misses"].copy()
+        for row in gone:
+            A, B, _ = rays([clouds[row["id"]]], [_pose44(row["pose"])], p)
+            accumulate(A, B, ominc, odims, p.shell, -1, hits, misses)
+        assert (hits >= 0).all() and (misses >= 0).all(), "a count below zero"
+        regridded = odims != dims or (ominc != minc).any()
+        if regridded:
+            oh = hits.reshape(odims[::-1]); om = misses.reshape(odims[::-1])
+            hits = np.zeros(dims[::-1], np.int64); misses = np.zeros(dims[::-1], np.int64)
+            lo = np.maximum(ominc, minc); hi = np.minimum(ominc + odims, minc + dims)             # the voxels both boxes hold, hi exclusive
+            moved = 0
+            if (lo < hi).all():
+                src = tuple(slice(int(lo[k] - ominc[k]), int(hi[k] - ominc[k])) for k in (2, 1, 0))
+                dst = tuple(slice(int(lo[k] - minc[k]), int(hi[k] - minc[k])) for k in (2, 1, 0))
+                hits[dst] = oh[src]; misses[dst] = om[src]
+                moved = int(oh[src].sum() + om[src].sum())
+            outside = int(oh.sum() + om.sum()) - moved
+            assert outside == 0, "an old voxel outside the new box still held a count"
+            hits = hits.reshape(-1); misses = misses.reshape(-1)
+    for row, A, B in fresh:
+        accumulate(A, B, minc, dims, p.shell, +1, hits, misses)
+    walked = [r for r, _, _ in fresh] + gone
+    wb = [r["box"] for r in walked if r["box"]]
+    dlo, dhi = (0, 0, 0), (-1, -1, -1)
+    if wb:
+        a = np.maximum(np.min([b[0] for b in wb], axis=0) - minc, 0); b = np.minimum(np.max([b[1] for b in wb], axis=0) - minc, np.array(dims) - 1)
+        if (a <= b).all():
+            dlo, dhi = tuple(int(v) for v in a), tuple(int(v) for v in b)
+    upd = OccupancyUpdate(len(ids) - len(fresh), len(fresh), len(gone), int(rebuilt), int(regridded), sum(r["cnt"][0] for r in walked), dlo, dhi,
+                          sum(r["cnt"][1] for r, _, _ in fresh), sum(r["cnt"][1] for r in gone))
+    shape = dims[::-1]
+    h = hits.astype(np.uint32).reshape(shape); m = misses.astype(np.uint32).reshape(shape)
+    cls = class_of(h, m, int(p.min_hits), int(p.hit_weight))
+    cnt = [sum(r["cnt"][k] for r in rows) for k in range(5)]
+    stats = OccupancyStats(*cnt, int(h.sum(dtype=np.uint64)), int(m.sum(dtype=np.uint64)), dims[0], dims[1], dims[2], int((cls == OCCUPIED).sum()),
+                           int((cls == FREE).sum()), int((cls == UNKNOWN).sum()))
+    grid = OccupancyGrid(tuple(float(v) * voxel for v in minc), voxel, dims[0], dims[1], dims[2], tuple(int(v) for v in minc))
+    new = dict(ray_params=ray_params, rows=rows, minc=tuple(int(v) for v in minc), dims=dims, hits=hits, misses=misses, outside=outside)
+    return dict(hits=h, misses=m, classes=cls, stats=stats, grid=grid), upd, new

@@ -38,6 +38,24 @@ inline MapOccupancy mapOccupancy(qn_kf_store* store, const std::vector<int32_t>&
   return out;
 }
 
+// the resident volume brought to this list in place (qn_kf_map_occupancy_update): the entries whose id and pose bytes the volume already holds are kept, the
+// others walked in, and what the list no longer names walked out again.  The arguments and the result are mapOccupancy's, byte for byte; update (optional):
+// what the call did - the entries kept, added and removed, whether it started from nothing, the box of the new grid outside which no count changed.
+inline MapOccupancy updateOccupancy(qn_kf_store* store, const std::vector<int32_t>& ids, const std::vector<double>& poses16, const qn_occupancy_params* params = nullptr,
+                                    qn_occupancy_update* update = nullptr) {
+  if (poses16.size() != 16 * ids.size()) throw std::invalid_argument("[qn_map] updateOccupancy: 16 doubles per listed keyframe");
+  qn_occupancy_params p;
+  if (params) p = *params; else qn_occupancy_default_params(&p);
+  MapOccupancy out;
+  qn_occupancy_update u;
+  int rc = qn_kf_map_occupancy_update(store, ids.data(), poses16.data(), (uint32_t)ids.size(), &p, &out.stats, &u);
+  if (rc != QN_OK) throw std::runtime_error(std::string("[qn_map] qn_kf_map_occupancy_update: ") + qn_status_str(rc) + " " + qn_kf_last_error(store));
+  rc = qn_kf_map_occupancy_grid(store, &out.grid, nullptr, nullptr, nullptr);
+  if (rc != QN_OK) throw std::runtime_error(std::string("[qn_map] qn_kf_map_occupancy_grid: ") + qn_status_str(rc) + " " + qn_kf_last_error(store));
+  if (update) *update = u;
+  return out;
+}
+
 // the voxels of the latest mapOccupancy whose class bit is in class_mask (default: the occupied ones) as a cloud of voxel centres (minc + i + 0.5) * voxel, in
 // ascending linear index, intensity = hits (qn_kf_map_occupancy_list); misses (optional): their miss counts -> the number of voxels
 template <typename PointT>

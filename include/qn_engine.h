@@ -783,6 +783,44 @@ int  qn_kf_map_occupancy(qn_kf_store*, const int32_t* ids, const double* poses16
 int  qn_kf_map_occupancy_grid(qn_kf_store*, qn_occupancy_grid* info_out, uint32_t* hits_out, uint32_t* misses_out, uint8_t* class_out);
 int  qn_kf_map_occupancy_list(qn_kf_store*, uint32_t class_mask, uint32_t* n_out, int32_t* ijk_out, uint32_t* hits_out, uint32_t* misses_out);
 int  qn_kf_map_occupancy_slice(qn_kf_store*, int32_t iz_lo, int32_t iz_hi, uint8_t* occupancy_out /* W x H, y slow */);
+/* ---- the occupancy map updated in place (csrc/qn_mapoccupancy_update.inc, part of csrc/qn_staticmap.hip; numpy twin and specification: update() of
+ * qn_amd/mapoccupancy.py)
+ * qn_kf_map_occupancy starts from nothing.  A robot that asks for the volume at every tick has added one keyframe since the last call, or a loop closure has
+ * moved some poses; the counts are u32 sums behind one quantisation, so a contribution is taken out again by walking the same rays with -1 (mod 2^32), and the
+ * result is the same bytes whatever the order.
+ * qn_kf_map_occupancy_update brings the resident volume to this list.  The list, the parameters, the checks and the refusals are those of
+ *   qn_kf_map_occupancy.  Afterwards the live result equals, byte for byte, what qn_kf_map_occupancy leaves for the same list and parameters: *stats_out, the
+ *   grid info, every voxel's hits, misses and class, so every list and slice.  The grid is the tight box of the list's ray ends again: it also shrinks.  All
+ *   getters and qn_kf_map_distance / _route / _frontiers / _view_gain serve the result as they serve a rebuilt one, and a successful update ends the live results
+ *   of those four exactly as a successful qn_kf_map_occupancy does.
+ * Ledger: for the result it holds the store keeps one row per entry - the id, the 12 pose doubles the carving reads, the five record counts, the box of the
+ *   entry's ray ends in voxel coordinates (none without a ray).  A new list is matched against it as a multiset: an entry is kept when its id and the bytes
+ *   (memcmp) of its 12 doubles equal an unmatched row; the order of the list does not matter and repeated ids match as often as they occur.  A pose that
+ *   differs only in the sign of a zero counts as changed and is walked again.  Unmatched rows are removed - walked with -1 from the ledger's pose -, unmatched
+ *   entries are added; the caller never states what to remove, so no count can be driven below zero from outside.  Only a successful update leaves a ledger; a
+ *   successful qn_kf_map_occupancy drops it, and the next update then starts from an empty volume (rebuilt = 1), as it does when voxel, min_range, max_range or
+ *   shell differ from the ledger's.  When only min_hits or hit_weight differ the counts are kept and the classes formed again.
+ * Sequence: the diff on the host; the extent of the added entries only (their counts and boxes; one host read, none when nothing is added); the new box, the
+ *   union of the rows' boxes, where QN_ERR_CAPACITY (a ray end at 2^20 voxels, 2^15 a side, 2^27 voxels, 2^32 records) is decided with the previous result
+ *   intact, its ledger and the fields over it too; the removed rows' rays subtracted in the old grid; the counts moved into the new box when it differs (a
+ *   second pair of count buffers, kept for the next move); the added entries' rays; the classes of the whole grid and the sums (the second and last host read).
+ *   A HIP error after the first subtraction leaves no live result and no ledger.
+ * qn_occupancy_update (64 bytes): entries_kept, entries_added, entries_removed; rebuilt (1: no ledger to start from, or other ray parameters: every entry was
+ *   added to an empty volume); regridded (1: the box changed and the counts were moved); records_walked (the records of the added and the removed entries: what
+ *   the walks read); dirty_lo[3], dirty_hi[3] (the union of the boxes of the added and removed rows as indices of the NEW grid, clipped to it: every voxel of
+ *   the new grid whose hits or misses changed lies inside; lo = 0 > hi = -1 on every axis when it is empty); rays_added, rays_removed (u64).  Nothing in the
+ *   library consumes the dirty box yet.
+ * Cost on one MI355X (tools/gpu_map_occupancy_update_time.py, medians of 5; profiles/EXPERIMENTS.md), 500 keyframes x 60 000 records, 1 554 x 346 x 20
+ *   voxels, beside 203.6 ms for qn_kf_map_occupancy and 1.07 ms for qn_kf_map_frontiers in the same run: one keyframe added 1.41 ms, nothing changed 0.19 ms,
+ *   the last 50 poses moved 41.8 ms, every pose moved 327.6 ms (everything is walked twice), no ledger to start from 172.4 ms.                              */
+typedef struct qn_occupancy_update {
+  uint32_t entries_kept, entries_added, entries_removed;
+  uint32_t rebuilt, regridded, records_walked;
+  int32_t  dirty_lo[3], dirty_hi[3];
+  uint64_t rays_added, rays_removed;
+} qn_occupancy_update;                                                                                                       /* 64 bytes */
+int  qn_kf_map_occupancy_update(qn_kf_store*, const int32_t* ids, const double* poses16, uint32_t count, const qn_occupancy_params* params,
+                                qn_occupancy_stats* stats_out, qn_occupancy_update* update_out);
 /* ---- the occupancy map's Euclidean distance field (csrc/qn_mapdistance.inc, part of csrc/qn_staticmap.hip; numpy twin and specification: qn_amd/mapdistance.py)
  * What a planner asks of an occupancy map first: how far is this place from the nearest obstacle - for the collision check of a trajectory, an inflated
  * costmap, the clearance of a body of some height.  These calls run an exact Euclidean distance transform over the resident class bytes of the live

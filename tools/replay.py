@@ -355,7 +355,8 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
         drop_ground=False, map_clusters=False, cluster_tol=0.5, cluster_min=10, cluster_max=0xffffffff, drop_small_clusters=False,
         localize_every=0, localize_radius=35.0, localize_shift=0.5, localize_yaw=3.0, occupancy_3d=False, occ_voxel=0.3, occ_min_range=0.5,
         occ_max_range=60.0, occ_shell=1, occ_slice=None, occ_distance=False, occ_dist_max=16, occ_unknown_obstacle=False, robot_radius=None, occ_route=None,
-        route_from=None, route_min_d2=4, route_planar=False, occ_frontiers=False, frontier_min_size=8, occ_view_gain=False, view_range=20.0, view_beams=16, view_azimuth=300):
+        route_from=None, route_min_d2=4, route_planar=False, occ_frontiers=False, frontier_min_size=8, occ_view_gain=False, view_range=20.0, view_beams=16, view_azimuth=300,
+        occ_incremental=False):
     """sensor = "uniform": keyframe clouds sampled uniformly by area inside a disc (make_stream); "spinning": ray-cast spinning-LiDAR
     scans from the ground-truth poses of the same figure-8 (make_lidar_stream).  detector = "radius": the candidate is the closest older
     keyframe within `radius` of the corrected position (LC:34-56); "scancontext": the older keyframe nearest by Scan Context distance, kept
@@ -427,6 +428,11 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
     FIELDS x y z hits misses.  occ_slice = (z_lo, z_hi) in metres: also occupancy_slice.pgm / .yaml, the layers of those heights flattened to the grid a planner
     loads (occupied where any voxel is, else free where a ray passed, else unknown).  out["occupancy"]: rays, total_misses, width, height, depth, occupied, free,
     unknown, and slice_layers with occ_slice.
+    occ_incremental (with occupancy_3d; default False): the volume is kept live through the run instead of being built once at the end - after every loop-timer
+    tick it is brought to the current estimate of every keyframe's pose (KeyframeStore.map_occupancy_update on the GPU backend, mapoccupancy.update on the oracle
+    backend: the keyframes whose pose did not change are kept, the others walked out and in again), and once more with the final poses.  The files written and
+    out["occupancy"] are those of the one-shot run; out["occupancy"] also has updates, the number of calls, entries_listed, the sum of their list lengths, and
+    entries_walked, the entries they added plus those they removed.
     occ_distance (with occupancy_3d; default False): the exact Euclidean distance field of that volume (qn_amd/mapdistance.py: per voxel the squared distance in
     voxels to the nearest occupied voxel - with occ_unknown_obstacle to the nearest occupied or unknown one - up to occ_dist_max voxels), on the GPU backend by
     KeyframeStore.map_distance, on the oracle backend by the numpy twin.  out["distance"]: sites, reached, far, max_d2, sum_d2, site_mask, max_dist.
@@ -518,6 +524,8 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
         mapoccupancy.check_params(occ_params)                                                     # (raises ValueError on a parameter outside its range)
         if occ_slice is not None and not (len(occ_slice) == 2 and np.isfinite(occ_slice).all() and occ_slice[0] <= occ_slice[1]):
             raise ValueError("occ_slice must be two finite heights z_lo <= z_hi, not %r" % (occ_slice,))
+    if occ_incremental and not occupancy_3d:
+        raise ValueError("occ_incremental needs occupancy_3d (it keeps that volume live)")
     if (occ_distance or robot_radius is not None or occ_unknown_obstacle) and not (occupancy_3d and occ_distance):
         raise ValueError("occ_distance needs occupancy_3d, and occ_unknown_obstacle and robot_radius need occ_distance (the field is computed from its volume)")
     if occ_distance:
@@ -661,7 +669,21 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
         if todo:
             st = store.submap_describe(ctx, [ids[x] for x in todo], odom[:k + 1], submap_range, voxel, with_features=use_quatro)
             sub_hi.update({x: min(x + submap_range, k) for x, v in zip(todo, st) if v != engine.QN_ERR_CAPACITY})
+    occ_live = dict(updates=0, entries_listed=0, entries_walked=0, ledger=None, result=None, stats=None)
+
+    def occ_update():
+        """the live volume brought to the keyframes that exist, at their current estimate"""
+        n = len(corrected)
+        if backend == "gpu":
+            occ_live["stats"], up = store.map_occupancy_update(ids[:n], corrected, engine.OccupancyParams(*occ_params))
+            walked = up["entries_added"] + up["entries_removed"]
+        else:
+            occ_live["result"], up, occ_live["ledger"] = mapoccupancy.update(occ_live["ledger"], dict(enumerate(scans)), range(n), corrected, occ_params)
+            walked = up.entries_added + up.entries_removed
+        occ_live["updates"] += 1; occ_live["entries_listed"] += n; occ_live["entries_walked"] += walked
     for k in range(n_kf):
+        if occ_incremental and k and (k % loop_every == 0 if loop_every > 1 or catch_up else True):
+            occ_update()                                                                     # the tick of keyframe k - 1 is over: the volume follows what it left
         if backend == "gpu":
             ids.append(store.add(scans[k]) if scans is not None else cast_ids[k])
             if fgate:                                                                        # the keyframe's range images, once, on arrival
@@ -838,14 +860,16 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
     if save_dir:
         write_kitti_tum(save_dir, corrected, stamps)
         if occupancy_3d:
+            if occ_incremental:
+                occ_update()                                                                 # once more, with the final poses
             if backend == "gpu":
                 from qn_amd import engine
-                st = store.map_occupancy(ids, corrected, engine.OccupancyParams(*occ_params))
+                st = occ_live["stats"] if occ_incremental else store.map_occupancy(ids, corrected, engine.OccupancyParams(*occ_params))
                 info, hits, misses, cls = store.map_occupancy_grid()
                 res = dict(hits=hits, misses=misses, classes=cls, grid=mapoccupancy.OccupancyGrid(*(info[f] for f in mapoccupancy.OccupancyGrid._fields)),
                            slice=store.map_occupancy_slice)
             else:
-                res = mapoccupancy.classify(scans, corrected, occ_params)
+                res = dict(occ_live["result"]) if occ_incremental else mapoccupancy.classify(scans, corrected, occ_params)
                 st = res["stats"]._asdict()
             if occ_distance:
                 if backend == "gpu":
@@ -931,6 +955,8 @@ def run(n_kf=70, seed=7, use_quatro=False, radius=12.0, tdiff=15.0, voxel=0.3, s
             out["occupancy"] = {k: int(st[k]) for k in ("n_rays", "total_misses", "width", "height", "depth", "occupied", "free", "unknown")}
             if layers is not None:
                 out["occupancy"]["slice_layers"] = [int(layers[0]), int(layers[1])]
+            if occ_incremental:
+                out["occupancy"].update({k: occ_live[k] for k in ("updates", "entries_listed", "entries_walked")})
         if localize_every and save_map_leaf is None:
             store.build_map(ids, corrected, voxel)
             localize_stage()
@@ -1078,6 +1104,9 @@ if __name__ == "__main__":
     ap.add_argument("--localize-yaw", type=float, default=3.0, help="with --localize-every: and turned by this much [deg]")
     ap.add_argument("--occupancy-3d", action="store_true",
                     help="with --save-dir: also write occupied.pcd, the occupied voxels of the 3-D occupancy map carved by every keyframe's rays (x y z hits misses)")
+    ap.add_argument("--occ-incremental", action="store_true",
+                    help="with --occupancy-3d: keep the volume live through the run - updated in place at every loop-timer tick and once more with the final "
+                         "poses - instead of building it once at the end; the files are the same")
     ap.add_argument("--occ-voxel", type=float, default=0.3, help="with --occupancy-3d: the voxel edge [m]")
     ap.add_argument("--occ-min-range", type=float, default=0.5, help="with --occupancy-3d: records closer than this are no rays [m]")
     ap.add_argument("--occ-max-range", type=float, default=60.0, help="with --occupancy-3d: records farther than this are no rays [m]")
@@ -1124,6 +1153,8 @@ if __name__ == "__main__":
         ap.error("--occupancy-3d needs --save-dir")
     if a.occ_slice is not None and not a.occupancy_3d:
         ap.error("--occ-slice needs --occupancy-3d")
+    if a.occ_incremental and not a.occupancy_3d:
+        ap.error("--occ-incremental needs --occupancy-3d")
     if a.occ_distance and not a.occupancy_3d:
         ap.error("--occ-distance needs --occupancy-3d")
     if (a.occ_unknown_obstacle or a.robot_radius is not None) and not a.occ_distance:
@@ -1151,4 +1182,4 @@ if __name__ == "__main__":
         occ_max_range=a.occ_max_range, occ_shell=a.occ_shell, occ_slice=a.occ_slice, occ_distance=a.occ_distance, occ_dist_max=a.occ_dist_max,
         occ_unknown_obstacle=a.occ_unknown_obstacle, robot_radius=a.robot_radius, occ_route=a.occ_route, route_from=a.route_from, route_min_d2=a.route_min_d2,
         route_planar=a.route_planar, occ_frontiers=a.occ_frontiers, frontier_min_size=a.frontier_min_size, occ_view_gain=a.occ_view_gain, view_range=a.view_range,
-        view_beams=a.view_beams, view_azimuth=a.view_azimuth)
+        view_beams=a.view_beams, view_azimuth=a.view_azimuth, occ_incremental=a.occ_incremental)
