@@ -62,6 +62,8 @@ def lib():
         _lib.qn_ctx_stream.restype = C.c_void_p
         _lib.qn_ctx_stream.argtypes = [C.c_void_p]
         _lib.qn_ctx_destroy.argtypes = [C.c_void_p]
+        _lib.hipMemcpy.restype = C.c_int                 # the HIP runtime's, through the library that links it: the device read-backs of KeyframeStore
+        _lib.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
     return _lib
 
 
@@ -704,6 +706,47 @@ class MultiGpu:
 
 
 # ---------------------------------------------------------------------------------------- keyframe store / cloud assembly
+# The records below and KeyframeStore's wrappers share one set of idioms; the next unit's wrapper starts from them, not from a copy of the previous unit's:
+# a parameter record is a _Twinned Structure that names its twin once; a params= argument goes through _record; a result record becomes a dict through _as_dict.
+def _open_fields(cls):
+    """the (name, ctypes type) of a record's fields, in field order, without those whose names start with reserved or pad"""
+    return [(f, t) for f, t in cls._fields_ if not f.startswith(("reserved", "pad"))]
+
+
+def _as_dict(rec):
+    """a record as a dict of its open fields: numbers as Python numbers, arrays as tuples of them, nested records as dicts"""
+    def py(v):
+        return _as_dict(v) if isinstance(v, C.Structure) else tuple(py(x) for x in v) if isinstance(v, C.Array) else v
+    return {f: py(getattr(rec, f)) for f, _ in _open_fields(type(rec))}
+
+
+class _Twinned:
+    """mixin of a record with a numpy twin: TWIN = (the module of qn_amd, the name in it) says where the twin lives, once; the fields go across by name"""
+    TWIN = None
+
+    @classmethod
+    def _twin_type(cls):
+        import importlib
+        return getattr(importlib.import_module("." + cls.TWIN[0], __package__), cls.TWIN[1])
+
+    def twin(self):
+        """-> the twin with these values: a namedtuple twin's own fields (a stats twin has fewer than the record), else every open field"""
+        T = self._twin_type()
+        return T(**{f: getattr(self, f) for f in getattr(T, "_fields", [f for f, _ in _open_fields(type(self))])})
+
+    @classmethod
+    def from_twin(cls, p):
+        """-> the record of any object with the open fields as attributes, each coerced by the field's type: float() for a double, int() for an integer"""
+        return cls(**{f: (float if t is C.c_double else int)(getattr(p, f)) for f, t in _open_fields(cls)})
+
+
+def _record(cls, params):
+    """every params= argument: None -> the defaults, a cls -> that object, anything else (the twin) -> cls.from_twin(params)"""
+    if params is None:
+        return cls()
+    return params if isinstance(params, cls) else cls.from_twin(params)
+
+
 class SimSensor(C.Structure):
     """qn_sim_sensor"""
     _fields_ = [("n_beams", C.c_uint32), ("n_cols", C.c_uint32), ("cos_el", C.c_void_p), ("sin_el", C.c_void_p), ("cos_az", C.c_void_p),
@@ -729,8 +772,9 @@ class Overlap(C.Structure):
     _fields_ = [("a_to_b", OverlapDir), ("b_to_a", OverlapDir)]
 
 
-class RangeParams(C.Structure):
+class RangeParams(_Twinned, C.Structure):
     """qn_range_params (56 bytes): the range-image shape, field of view, blind radius, and the free-space check's window and tolerances"""
+    TWIN = ("freespace", "Params")
     _fields_ = [("n_rows", C.c_uint32), ("n_cols", C.c_uint32), ("el_lo", C.c_double), ("el_hi", C.c_double), ("min_range", C.c_double),
                 ("window_rows", C.c_uint32), ("window_cols", C.c_uint32), ("tol_abs", C.c_double), ("tol_rel", C.c_double)]
 
@@ -745,15 +789,6 @@ class RangeParams(C.Structure):
         from . import freespace
         return cls.from_twin(freespace.Params.for_sensor(sensor, **kw))
 
-    @classmethod
-    def from_twin(cls, p):
-        return cls(*[getattr(p, f) for f, _ in cls._fields_])
-
-    def twin(self):
-        """-> the freespace.Params with these values"""
-        from . import freespace
-        return freespace.Params(**{f: getattr(self, f) for f, _ in self._fields_})
-
 
 class FreespaceDir(C.Structure):
     """qn_freespace_dir (32 bytes): one direction of a pair's free-space record"""
@@ -765,47 +800,31 @@ class Freespace(C.Structure):
     _fields_ = [("q_in_c", FreespaceDir), ("c_in_q", FreespaceDir)]
 
 
-class StaticParams(C.Structure):
+class StaticParams(_Twinned, C.Structure):
     """qn_static_params (8 bytes): the rule of the static map - a record is removed iff seen_through >= min_see_through and seen_through > agree_weight * agree"""
+    TWIN = ("staticmap", "StaticParams")
     _fields_ = [("min_see_through", C.c_uint32), ("agree_weight", C.c_uint32)]
 
     def __init__(self, min_see_through=2, agree_weight=1):
         super().__init__(min_see_through, agree_weight)
 
-    @classmethod
-    def from_twin(cls, r):
-        return cls(int(r.min_see_through), int(r.agree_weight))
 
-    def twin(self):
-        """-> the staticmap.StaticParams with these values"""
-        from . import staticmap
-        return staticmap.StaticParams(int(self.min_see_through), int(self.agree_weight))
-
-
-class NormalParams(C.Structure):
+class NormalParams(_Twinned, C.Structure):
     """qn_normal_params (16 bytes): the neighbourhood radius of the map normals and the fewest neighbours (the point included) that make one"""
+    TWIN = ("mapnormals", "NormalParams")
     _fields_ = [("radius", C.c_double), ("min_neighbors", C.c_uint32), ("reserved", C.c_uint32)]
 
     def __init__(self, radius=0.6, min_neighbors=5):
         super().__init__(radius, min_neighbors, 0)
 
-    def twin(self):
-        """-> the mapnormals.NormalParams with these values"""
-        from . import mapnormals
-        return mapnormals.NormalParams(float(self.radius), int(self.min_neighbors))
 
-
-class OutlierParams(C.Structure):
+class OutlierParams(_Twinned, C.Structure):
     """qn_outlier_params (24 bytes): the neighbourhood radius, PCL's std_mul and the k nearest neighbours of the map's outlier filter"""
+    TWIN = ("mapoutliers", "OutlierParams")
     _fields_ = [("radius", C.c_double), ("std_mul", C.c_double), ("k", C.c_uint32), ("reserved", C.c_uint32)]
 
     def __init__(self, radius=1.0, std_mul=2.0, k=8):
         super().__init__(radius, std_mul, k, 0)
-
-    def twin(self):
-        """-> the mapoutliers.OutlierParams with these values"""
-        from . import mapoutliers
-        return mapoutliers.OutlierParams(float(self.radius), float(self.std_mul), int(self.k))
 
 
 class OutlierStats(C.Structure):
@@ -814,19 +833,15 @@ class OutlierStats(C.Structure):
                                                                                               ("mean_q", C.c_double), ("std_q", C.c_double), ("thr_q", C.c_double)]
 
 
-class GroundParams(C.Structure):
+class GroundParams(_Twinned, C.Structure):
     """qn_ground_params (40 bytes): the grid edge, the largest ground slope (rise over run), the ground tolerance, the clearance below which a point occupies
     its column, and the points a column needs to seed the ground.  The defaults are interface choices, not measurements."""
+    TWIN = ("mapground", "GroundParams")
     _fields_ = [("cell", C.c_double), ("max_slope", C.c_double), ("ground_tol", C.c_double), ("clearance", C.c_double), ("min_points", C.c_uint32),
                 ("reserved", C.c_uint32)]
 
     def __init__(self, cell=0.5, max_slope=0.3, ground_tol=0.2, clearance=2.0, min_points=1):
         super().__init__(cell, max_slope, ground_tol, clearance, min_points, 0)
-
-    def twin(self):
-        """-> the mapground.GroundParams with these values"""
-        from . import mapground
-        return mapground.GroundParams(float(self.cell), float(self.max_slope), float(self.ground_tol), float(self.clearance), int(self.min_points))
 
 
 class GroundStats(C.Structure):
@@ -846,20 +861,15 @@ QN_GROUND_NONE, QN_GROUND_GROUND, QN_GROUND_OBSTACLE, QN_GROUND_OVERHEAD, QN_GRO
 QN_GROUND_MAX_CELLS = 1 << 26
 
 
-class OccupancyParams(C.Structure):
+class OccupancyParams(_Twinned, C.Structure):
     """qn_occupancy_params (48 bytes): the voxel edge, the ranges between which a record is a ray, the voxels before a ray's end that are not carved, the hits a
     voxel needs to be occupied and the weight of a hit against a miss.  The defaults are interface choices, not measurements."""
+    TWIN = ("mapoccupancy", "OccupancyParams")
     _fields_ = [("voxel", C.c_double), ("min_range", C.c_double), ("max_range", C.c_double), ("shell", C.c_uint32), ("min_hits", C.c_uint32),
                 ("hit_weight", C.c_uint32), ("reserved", C.c_uint32 * 3)]
 
     def __init__(self, voxel=0.3, min_range=0.5, max_range=60.0, shell=1, min_hits=1, hit_weight=2):
         super().__init__(voxel, min_range, max_range, shell, min_hits, hit_weight)
-
-    def twin(self):
-        """-> the mapoccupancy.OccupancyParams with these values"""
-        from . import mapoccupancy
-        return mapoccupancy.OccupancyParams(float(self.voxel), float(self.min_range), float(self.max_range), int(self.shell), int(self.min_hits),
-                                            int(self.hit_weight))
 
 
 class OccupancyStats(C.Structure):
@@ -884,28 +894,20 @@ QN_OCC_UNKNOWN, QN_OCC_FREE, QN_OCC_OCCUPIED = range(3)
 QN_OCC_MAX_CELLS = 1 << 27
 
 
-class DistanceParams(C.Structure):
+class DistanceParams(_Twinned, C.Structure):
     """qn_distance_params (16 bytes): the classes that count as sites (bit 1 << class) and the largest distance, in voxels, the field resolves.  The defaults
     are interface choices, not measurements."""
+    TWIN = ("mapdistance", "DistanceParams")
     _fields_ = [("site_mask", C.c_uint32), ("max_dist", C.c_uint32), ("reserved", C.c_uint32 * 2)]
 
     def __init__(self, site_mask=1 << QN_OCC_OCCUPIED, max_dist=16):
         super().__init__(site_mask, max_dist)
 
-    def twin(self):
-        """-> the mapdistance.DistanceParams with these values"""
-        from . import mapdistance
-        return mapdistance.DistanceParams(int(self.site_mask), int(self.max_dist))
 
-
-class DistanceStats(C.Structure):
+class DistanceStats(_Twinned, C.Structure):
     """qn_distance_stats (32 bytes): every field is an integer the twin shares"""
+    TWIN = ("mapdistance", "DistanceStats")
     _fields_ = [("sites", C.c_uint32), ("reached", C.c_uint32), ("far", C.c_uint32), ("max_d2", C.c_uint32), ("sum_d2", C.c_uint64), ("reserved", C.c_uint32 * 2)]
-
-    def twin(self):
-        """-> the mapdistance.DistanceStats with these values"""
-        from . import mapdistance
-        return mapdistance.DistanceStats(int(self.sites), int(self.reached), int(self.far), int(self.max_d2), int(self.sum_d2))
 
 
 QN_DIST_FAR = 0xffff
@@ -913,30 +915,22 @@ QN_DIST_MAX_RADIUS = 255
 QN_DIST_OUTSIDE = 0xff
 
 
-class RouteParams(C.Structure):
+class RouteParams(_Twinned, C.Structure):
     """qn_route_params (32 bytes): the classes that are passable (bit 1 << class), the smallest d2 a passable voxel has (0: no test), the band of layers, and
     whether the field is the plane of columns.  The defaults are interface choices, not measurements."""
+    TWIN = ("maproute", "RouteParams")
     _fields_ = [("pass_mask", C.c_uint32), ("min_d2", C.c_uint32), ("iz_lo", C.c_int32), ("iz_hi", C.c_int32), ("planar", C.c_uint32), ("reserved", C.c_uint32 * 3)]
 
     def __init__(self, pass_mask=1 << QN_OCC_FREE, min_d2=4, iz_lo=0, iz_hi=0x7fffffff, planar=0):
         super().__init__(pass_mask, min_d2, iz_lo, iz_hi, planar)
 
-    def twin(self):
-        """-> the maproute.RouteParams with these values"""
-        from . import maproute
-        return maproute.RouteParams(int(self.pass_mask), int(self.min_d2), int(self.iz_lo), int(self.iz_hi), int(self.planar))
 
-
-class RouteStats(C.Structure):
+class RouteStats(_Twinned, C.Structure):
     """qn_route_stats (64 bytes): every field but rounds and tile_visits - diagnostics of the GPU schedule - is an integer the twin shares"""
+    TWIN = ("maproute", "RouteStats")
     _fields_ = [("passable", C.c_uint32), ("blocked", C.c_uint32), ("reached", C.c_uint32), ("unreached", C.c_uint32), ("goals_used", C.c_uint32),
                 ("goals_blocked", C.c_uint32), ("max_cost", C.c_uint32), ("reserved0", C.c_uint32), ("sum_cost", C.c_uint64), ("rounds", C.c_uint64),
                 ("tile_visits", C.c_uint64), ("reserved", C.c_uint32 * 2)]
-
-    def twin(self):
-        """-> the maproute.RouteStats with these values"""
-        from . import maproute
-        return maproute.RouteStats(*(int(getattr(self, f)) for f in maproute.RouteStats._fields))
 
 
 QN_ROUTE_BLOCKED = 0xfffffffe
@@ -945,30 +939,22 @@ QN_ROUTE_MAX_POINTS = 1 << 20
 QN_ROUTE_ROUNDS_PER_CHECK = 8
 
 
-class FrontierParams(C.Structure):
+class FrontierParams(_Twinned, C.Structure):
     """qn_frontier_params (32 bytes): the classes that are candidates and those that are unknown (bit 1 << class, no class in both), whether the space outside
     the grid is unknown, the smallest component that is a region, and the band of layers.  The defaults are interface choices, not measurements."""
+    TWIN = ("mapfrontier", "FrontierParams")
     _fields_ = [("free_mask", C.c_uint32), ("unknown_mask", C.c_uint32), ("edge_unknown", C.c_uint32), ("min_size", C.c_uint32), ("iz_lo", C.c_int32),
                 ("iz_hi", C.c_int32), ("reserved", C.c_uint32 * 2)]
 
     def __init__(self, free_mask=1 << QN_OCC_FREE, unknown_mask=1 << QN_OCC_UNKNOWN, edge_unknown=1, min_size=8, iz_lo=0, iz_hi=0x7fffffff):
         super().__init__(free_mask, unknown_mask, edge_unknown, min_size, iz_lo, iz_hi)
 
-    def twin(self):
-        """-> the mapfrontier.FrontierParams with these values"""
-        from . import mapfrontier
-        return mapfrontier.FrontierParams(int(self.free_mask), int(self.unknown_mask), int(self.edge_unknown), int(self.min_size), int(self.iz_lo), int(self.iz_hi))
 
-
-class FrontierStats(C.Structure):
+class FrontierStats(_Twinned, C.Structure):
     """qn_frontier_stats (48 bytes): every field but rounds - a diagnostic of the GPU schedule - is an integer the twin shares"""
+    TWIN = ("mapfrontier", "FrontierStats")
     _fields_ = [(f, C.c_uint32) for f in ("candidates", "frontier", "components", "regions", "too_small", "region_voxels", "rejected_voxels", "largest",
                                           "unknown_faces", "rounds")] + [("reserved", C.c_uint32 * 2)]
-
-    def twin(self):
-        """-> the mapfrontier.FrontierStats with these values"""
-        from . import mapfrontier
-        return mapfrontier.FrontierStats(*(int(getattr(self, f)) for f in mapfrontier.FrontierStats._fields))
 
 
 class FrontierInfo(C.Structure):
@@ -981,18 +967,14 @@ QN_FRONTIER_REJECTED = -1
 QN_FRONTIER_NONE = -2
 
 
-class ViewParams(C.Structure):
+class ViewParams(_Twinned, C.Structure):
     """qn_view_params (32 bytes): the classes whose voxels are gain and those that stop a ray (bit 1 << class, no class in both; stop_mask may be 0), the gain
     voxels a ray may pass through (0: no limit), and the band of layers in which a voxel is marked.  The defaults are interface choices, not measurements."""
+    TWIN = ("mapview", "ViewParams")
     _fields_ = [("gain_mask", C.c_uint32), ("stop_mask", C.c_uint32), ("max_through", C.c_uint32), ("iz_lo", C.c_int32), ("iz_hi", C.c_int32), ("reserved", C.c_uint32 * 3)]
 
     def __init__(self, gain_mask=1 << QN_OCC_UNKNOWN, stop_mask=1 << QN_OCC_OCCUPIED, max_through=0, iz_lo=0, iz_hi=0x7fffffff):
         super().__init__(gain_mask, stop_mask, max_through, iz_lo, iz_hi)
-
-    def twin(self):
-        """-> the mapview.ViewParams with these values"""
-        from . import mapview
-        return mapview.ViewParams(int(self.gain_mask), int(self.stop_mask), int(self.max_through), int(self.iz_lo), int(self.iz_hi))
 
 
 class ViewInfo(C.Structure):
@@ -1006,15 +988,11 @@ class ViewInfo(C.Structure):
         return np.frombuffer(bytes(self), mapview.VIEW_DTYPE).copy()
 
 
-class ViewStats(C.Structure):
+class ViewStats(_Twinned, C.Structure):
     """qn_view_stats (48 bytes): every field but passes - a diagnostic of the GPU schedule - is an integer the twin shares"""
+    TWIN = ("mapview", "ViewStats")
     _fields_ = [(f, C.c_uint32) for f in ("viewpoints", "outside", "rays", "covered", "max_cover", "passes")] + [("reserved", C.c_uint32 * 2), ("total_gain", C.c_uint64),
                                                                                                                ("steps", C.c_uint64)]
-
-    def twin(self):
-        """-> the mapview.ViewStats with these values"""
-        from . import mapview
-        return mapview.ViewStats(*(int(getattr(self, f)) for f in mapview.ViewStats._fields))
 
 
 QN_VIEW_OK = 0
@@ -1022,18 +1000,14 @@ QN_VIEW_OUTSIDE = 1
 QN_VIEW_MAX_OFFSET = 1 << 25
 
 
-class ClusterParams(C.Structure):
+class ClusterParams(_Twinned, C.Structure):
     """qn_cluster_params (24 bytes): the joining distance, the smallest and the largest component that is a cluster, and the ground classes that take part
     (0: every finite point).  The defaults are interface choices, not measurements."""
+    TWIN = ("mapclusters", "ClusterParams")
     _fields_ = [("tolerance", C.c_double), ("min_size", C.c_uint32), ("max_size", C.c_uint32), ("class_mask", C.c_uint32), ("reserved", C.c_uint32)]
 
     def __init__(self, tolerance=0.5, min_size=10, max_size=0xffffffff, class_mask=0):
         super().__init__(tolerance, min_size, max_size, class_mask, 0)
-
-    def twin(self):
-        """-> the mapclusters.ClusterParams with these values"""
-        from . import mapclusters
-        return mapclusters.ClusterParams(float(self.tolerance), int(self.min_size), int(self.max_size), int(self.class_mask))
 
 
 class ClusterStats(C.Structure):
@@ -1051,18 +1025,14 @@ QN_CLUSTER_REJECTED, QN_CLUSTER_NONE = -1, -2
 assert (C.sizeof(ClusterParams), C.sizeof(ClusterStats), C.sizeof(ClusterInfo)) == (24, 56, 56)             # the records of include/qn_engine.h
 
 
-class LocalizeParams(C.Structure):
+class LocalizeParams(_Twinned, C.Structure):
     """qn_localize_params (32 bytes): the crop radius around the guess, the scan's voxel leaf, the score threshold and the crop shape (QN_LOCALIZE_SPHERE /
     QN_LOCALIZE_CYLINDER); the defaults are config.yaml's radius, voxel and score."""
+    TWIN = ("maplocalize", "LocalizeParams")
     _fields_ = [("radius", C.c_double), ("leaf", C.c_double), ("score_thr", C.c_double), ("shape", C.c_uint32), ("reserved", C.c_uint32)]
 
     def __init__(self, radius=35.0, leaf=0.3, score_thr=1.5, shape=0):
         super().__init__(radius, leaf, score_thr, shape, 0)
-
-    def twin(self):
-        """-> the maplocalize.LocalizeParams with these values"""
-        from . import maplocalize
-        return maplocalize.LocalizeParams(float(self.radius), float(self.leaf), float(self.score_thr), int(self.shape))
 
 
 class LocalizeStats(C.Structure):
@@ -1135,6 +1105,74 @@ class KeyframeStore:
         if st != QN_OK:
             raise EngineError(st, self._l.qn_status_str(st).decode() + ": " + self._l.qn_kf_last_error(self.h).decode() + " / " + lib().qn_last_error(ctx.h).decode())
 
+    # ---- what the wrappers below share (everything a helper does not fit stays written out in its wrapper)
+    @staticmethod
+    def _ids_poses(ids, poses):
+        """the list build_map takes: ids (count,) int32 and one 4x4 f64 per id as (count, 16)"""
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        return ids, np.ascontiguousarray(poses, dtype=np.float64).reshape(len(ids), 16)
+
+    def _slot(self, call, *args, kept=None):
+        """a call that replaces the map slot and reports it through (ptr, n) outputs -> (device address, count), _map_n following.  kept: the failure statuses
+        that leave the slot as it was (None: all of them); any other failure empties it"""
+        ptr = C.c_void_p(); n = C.c_uint32()
+        st = call(self.h, *args, C.byref(ptr), C.byref(n))
+        if st != QN_OK and kept is not None and st not in kept:
+            self._map_n = 0
+        self._check(st)
+        self._map_n = n.value
+        return ptr.value, n.value
+
+    def _read_float4(self, ptr, n, who):
+        """the n float4 records at the device address ptr -> (n, 4) float32"""
+        out = np.zeros((n, 4), np.float32)
+        if n and self._l.hipMemcpy(out.ctypes.data, ptr, 16 * n, 2) != 0:
+            raise EngineError(QN_ERR_HIP, who + ": read-back failed")
+        return out
+
+    def _grid(self, call, n_arrays, params=None):
+        """the first half of a *_grid getter: the call without its n_arrays arrays -> (the occupancy grid's record, the call's leading arguments: the grid and,
+        where the call has one, the params record it fills)"""
+        g = OccupancyGrid()
+        head = [C.byref(g)] + ([] if params is None else [C.byref(params)])
+        self._check(call(self.h, *head, *[None] * n_arrays))
+        return g, head
+
+    def _volume(self, call, dtypes, params=None, planar=False):
+        """a *_grid getter: ask for the grid, allocate (at least one element), ask again -> (info, [params dict,] one (D, H, W) array per dtype); planar: the field
+        is one layer when the returned params say so"""
+        g, head = self._grid(call, len(dtypes), params)
+        W, H, D = int(g.width), int(g.height), int(g.depth)
+        if planar and params.planar:
+            D = 1 if W * H else 0
+        n = W * H * D
+        out = [np.zeros(max(n, 1), dt) for dt in dtypes]
+        self._check(call(self.h, *head, *[_p(a) for a in out]))
+        return (_as_dict(g),) + (() if params is None else (_as_dict(params),)) + tuple(a[:n].reshape(D, H, W) for a in out)
+
+    def _slice(self, g, call, iz_lo, iz_hi, dtype):
+        """a *_slice getter over the grid g of _grid: one value per column over the layers iz_lo .. iz_hi -> (H, W)"""
+        W, H = int(g.width), int(g.height)
+        out = np.zeros(max(W * H, 1), dtype)
+        self._check(call(self.h, C.c_int32(int(iz_lo)), C.c_int32(int(iz_hi)), _p(out)))
+        return out[:W * H].reshape(H, W)
+
+    def _count(self, call, n_arrays):
+        """the capacity probe of a list getter: the call with no room for its n_arrays arrays -> the rows it would write (QN_ERR_CAPACITY says that there are some)"""
+        cnt = C.c_uint32()
+        st = call(self.h, *[None] * n_arrays, C.c_uint32(0), C.byref(cnt))
+        if st != QN_ERR_CAPACITY:
+            self._check(st)
+        return int(cnt.value)
+
+    def _listed(self, call, *columns):
+        """a list getter: probe, allocate (at least one row), ask again -> one array per column (the shape of a row, dtype), cut to the rows written"""
+        n = self._count(call, len(columns))
+        out = [np.zeros((max(n, 1),) + tuple(shape), dt) for shape, dt in columns]
+        cnt = C.c_uint32()
+        self._check(call(self.h, *[_p(a) for a in out], C.c_uint32(max(n, 1)), C.byref(cnt)))
+        return [a[:cnt.value] for a in out]
+
     def add(self, xyz, intensity=None):
         """intensity (n,) given: qn_kf_add_xyzi, the keyframe carries it into build_map; otherwise qn_kf_add (intensity 0 in the map)."""
         kid = C.c_int32()
@@ -1190,7 +1228,7 @@ class KeyframeStore:
 
     def assemble(self, ids, poses, leaf, slot):
         """-> (device pointer of float4 points, count)"""
-        ids = np.ascontiguousarray(ids, dtype=np.int32); poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(len(ids), 16)
+        ids, poses = self._ids_poses(ids, poses)
         ptr = C.c_void_p(); n = C.c_uint32()
         self._check(self._l.qn_kf_assemble(self.h, _p(ids), _p(poses), C.c_uint32(len(ids)), C.c_double(leaf), C.c_int(slot), C.byref(ptr), C.byref(n)))
         return ptr.value, n.value
@@ -1203,11 +1241,8 @@ class KeyframeStore:
     def build_map(self, ids, poses, leaf):
         """qn_kf_build_map: the corrected global map (transform every listed keyframe, concatenate in `ids` order, voxel grid with
         intensity) into the store's own map slot -> number of map points."""
-        ids = np.ascontiguousarray(ids, dtype=np.int32); poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(len(ids), 16)
-        ptr = C.c_void_p(); n = C.c_uint32(); self._map_n = 0
-        self._check(self._l.qn_kf_build_map(self.h, _p(ids), _p(poses), C.c_uint32(len(ids)), C.c_double(leaf), C.byref(ptr), C.byref(n)))
-        self._map_n = n.value
-        return n.value
+        ids, poses = self._ids_poses(ids, poses)
+        return self._slot(self._l.qn_kf_build_map, _p(ids), _p(poses), C.c_uint32(len(ids)), C.c_double(leaf), kept=())[1]
 
     def download_map(self, n):
         """-> (n, 4) float32: x y z intensity of the latest build_map"""
@@ -1425,19 +1460,12 @@ class KeyframeStore:
         """qn_kf_verify_cloud: cloud `which` (QN_VERIFY_SRC / _DST / _COARSE / _FINAL) of pair `pair` of the latest verify_loop_pairs[_c2f] -> (n, 3) float32"""
         ptr = C.c_void_p(); n = C.c_uint32()
         self._check(self._l.qn_kf_verify_cloud(self.h, C.c_uint32(pair), C.c_int(which), C.byref(ptr), C.byref(n)))
-        out = np.zeros((n.value, 4), np.float32)
-        if n.value:
-            l = self._l; l.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]; l.hipMemcpy.restype = C.c_int
-            if l.hipMemcpy(out.ctypes.data, ptr, 16 * n.value, 2) != 0:
-                raise EngineError(QN_ERR_HIP, "verify_cloud: read-back failed")
-        return np.ascontiguousarray(out[:, :3])
+        return np.ascontiguousarray(self._read_float4(ptr, n.value, "verify_cloud")[:, :3])
 
     # ---- the two-way overlap of cloud pairs (qn_kf_overlap_batch / qn_kf_verify_overlap / qn_kf_overlap_points; numpy twin: qn_amd/overlap.py)
     @staticmethod
     def _overlap_records(out, status, n):
-        def one(d):
-            return dict(n=int(d.n), n_finite=int(d.n_finite), inliers=int(d.inliers), sum_d2=float(d.sum_d2))
-        return [dict(a_to_b=one(out[j].a_to_b), b_to_a=one(out[j].b_to_a), status=int(status[j])) for j in range(n)]
+        return [dict(_as_dict(out[j]), status=int(status[j])) for j in range(n)]
 
     def overlap_batch(self, pairs, radius):
         """qn_kf_overlap_batch: pairs = [(ptr_a, n_a, ptr_b, n_b), ...], device pointers (int addresses) of float4 records in one frame -> one dict per pair:
@@ -1483,9 +1511,7 @@ class KeyframeStore:
     def range_set_params(self, params=None, **kw):
         """qn_kf_range_set_params: a RangeParams (or a freespace.Params), or its fields as keywords (the rest default).  A change of the shape, the angles or
         min_range discards every image."""
-        p = RangeParams(**kw) if params is None else params
-        if not isinstance(p, RangeParams):
-            p = RangeParams.from_twin(p)
+        p = RangeParams(**kw) if params is None else _record(RangeParams, params)
         self._check(self._l.qn_kf_range_set_params(self.h, C.byref(p)))
 
     def range_params(self):
@@ -1519,8 +1545,7 @@ class KeyframeStore:
         out = (Freespace * max(n, 1))(); status = np.zeros(max(n, 1), np.int32)
         self._check(self._l.qn_kf_freespace_batch(self.h, _p(q) if n else None, _p(c) if n else None, _p(T) if n else None, C.c_uint32(n), out, _p(status)))
         self._freespace_n = [(int(out[j].q_in_c.n), int(out[j].c_in_q.n)) for j in range(n)]
-        d = lambda r: {f: int(getattr(r, f)) for f, _ in FreespaceDir._fields_ if f != "reserved"}
-        return [dict(q_in_c=d(out[j].q_in_c), c_in_q=d(out[j].c_in_q), status=int(status[j])) for j in range(n)]
+        return [dict(_as_dict(out[j]), status=int(status[j])) for j in range(n)]
 
     def freespace_points(self, pair_slot, direction):
         """qn_kf_freespace_points: the class byte of every record (freespace.DROPPED .. AGREE) of the latest freespace_batch for its pair `pair_slot`,
@@ -1550,9 +1575,7 @@ class KeyframeStore:
         off = np.ascontiguousarray(witnesses[0], dtype=np.uint32).reshape(-1); wit = np.ascontiguousarray(witnesses[1], dtype=np.uint32).reshape(-1)
         if len(off) != n + 1 or (n and int(off[-1]) > len(wit)):
             raise ValueError("static_classify: wit_off must be count + 1 offsets into wit")
-        p = StaticParams() if params is None else params
-        if not isinstance(p, StaticParams):
-            p = StaticParams.from_twin(p)
+        p = _record(StaticParams, params)
         removed = np.zeros(max(n, 1), np.uint32); status = np.zeros(max(n, 1), np.int32)
         self._check(self._l.qn_kf_static_classify(self.h, _p(ids) if n else None, _p(poses) if n else None, C.c_uint32(n), _p(off), _p(wit) if len(wit) else None,
                                                   C.byref(p), _p(removed), _p(status)))
@@ -1572,13 +1595,8 @@ class KeyframeStore:
     def build_map_static(self, leaf):
         """qn_kf_build_map_static: the static map of the latest static_classify - build_map of its list and poses without the removed records - into the
         store's map slot -> number of map points (download_map serves it).  May be called again with another leaf."""
-        ptr = C.c_void_p(); n = C.c_uint32()
-        st = self._l.qn_kf_build_map_static(self.h, C.c_double(leaf), C.byref(ptr), C.byref(n))
-        if st not in (QN_ERR_NOT_READY, QN_ERR_INVALID_ARG):         # a refused call leaves the map slot as it was
-            self._map_n = 0
-        self._check(st)
-        self._map_n = n.value
-        return n.value
+        refused = (QN_ERR_NOT_READY, QN_ERR_INVALID_ARG)             # a refused call leaves the map slot as it was
+        return self._slot(self._l.qn_kf_build_map_static, C.c_double(leaf), kept=refused)[1]
 
     # ---- normals and curvature of the map slot (qn_kf_map_normals / qn_kf_download_map_normals / qn_kf_map_moments; numpy twin: qn_amd/mapnormals.py)
     def map_normals(self, params=None, viewpoints=None):
@@ -1586,9 +1604,7 @@ class KeyframeStore:
         None: the defaults (0.6, 5).  viewpoints: (V, 3) f64 the normals are turned towards (the nearest one of each point; the corrected keyframe positions as
         a rule), None or empty: the largest component of each normal is made positive.  -> dict(normals (n, 3) f32, curvature (n,) f32, count (n,) uint32,
         view_idx (n,) int32, ptr (the device address of the n float4 records nx ny nz curvature)), equal to mapnormals.normals of the downloaded map."""
-        p = NormalParams() if params is None else params
-        if not isinstance(p, NormalParams):
-            p = NormalParams(float(p.radius), int(p.min_neighbors))
+        p = _record(NormalParams, params)
         v = np.zeros((0, 3)) if viewpoints is None else np.ascontiguousarray(np.asarray(viewpoints, dtype=np.float64).reshape(-1, 3))
         ptr = C.c_void_p(); n = C.c_uint32()
         self._check(self._l.qn_kf_map_normals(self.h, C.byref(p), _p(v) if len(v) else None, C.c_uint32(len(v)), C.byref(ptr), C.byref(n)))
@@ -1613,15 +1629,13 @@ class KeyframeStore:
         mapoutliers.OutlierParams); None: the defaults (1.0, 2.0, 8).  -> (stats, count (n,) uint32, mean_q (n,) uint32, removed (n,) uint8), equal to
         mapoutliers.classify of the downloaded map.  stats: a dict of the fields of qn_outlier_stats plus, in metres, mean, std and threshold (each the _q
         value times 2^-quant_exp).  The map slot is not touched; map_remove_outliers applies the result."""
-        p = OutlierParams() if params is None else params
-        if not isinstance(p, OutlierParams):
-            p = OutlierParams(float(p.radius), float(p.std_mul), int(p.k))
+        p = _record(OutlierParams, params)
         st = OutlierStats()
         self._check(self._l.qn_kf_map_outliers(self.h, C.byref(p), C.byref(st)))
         n = int(st.n)
         cnt = np.zeros(max(n, 1), np.uint32); mq = np.zeros(max(n, 1), np.uint32); rm = np.zeros(max(n, 1), np.uint8)
         self._check(self._l.qn_kf_map_outlier_points(self.h, _p(cnt), _p(mq), _p(rm)))
-        stats = {f: getattr(st, f) for f, _ in OutlierStats._fields_}
+        stats = _as_dict(st)
         unit = math.ldexp(1.0, -int(st.quant_exp))
         stats.update(mean=st.mean_q * unit, std=st.std_q * unit, threshold=st.thr_q * unit)
         return stats, cnt[:n], mq[:n], rm[:n]
@@ -1629,26 +1643,20 @@ class KeyframeStore:
     def map_remove_outliers(self):
         """qn_kf_map_remove_outliers: the records the latest map_outliers kept become the map slot, in order -> (ptr, n): the device address of the n float4
         records x y z intensity.  download_map and map_normals serve the filtered map; the classification and any map normals are stale afterwards."""
-        ptr = C.c_void_p(); n = C.c_uint32()
-        self._check(self._l.qn_kf_map_remove_outliers(self.h, C.byref(ptr), C.byref(n)))
-        self._map_n = n.value
-        return ptr.value, n.value
+        return self._slot(self._l.qn_kf_map_remove_outliers)
 
     # ---- the ground of the map slot and its occupancy grid (qn_kf_map_ground / _points / _grid / qn_kf_map_keep_classes; numpy twin: qn_amd/mapground.py)
     def map_ground(self, params=None):
         """qn_kf_map_ground on the map of the latest build or filter, then its per-point download.  params: a GroundParams (or a mapground.GroundParams); None:
         the defaults.  -> (stats, classes (n,) uint8, height_q (n,) int32), equal to mapground.classify of the downloaded map; stats: a dict of the fields of
         qn_ground_stats (rounds is the GPU's own).  The map slot is not touched; map_ground_grid serves the grid, map_keep_classes applies the classes."""
-        p = GroundParams() if params is None else params
-        if not isinstance(p, GroundParams):
-            p = GroundParams(float(p.cell), float(p.max_slope), float(p.ground_tol), float(p.clearance), int(p.min_points))
+        p = _record(GroundParams, params)
         st = GroundStats()
         self._check(self._l.qn_kf_map_ground(self.h, C.byref(p), C.byref(st)))
         n = int(st.n)
         cls = np.zeros(max(n, 1), np.uint8); hq = np.zeros(max(n, 1), np.int32)
         self._check(self._l.qn_kf_map_ground_points(self.h, _p(cls), _p(hq)))
-        stats = {f: getattr(st, f) for f, _ in GroundStats._fields_ if f != "reserved"}
-        return stats, cls[:n], hq[:n]
+        return _as_dict(st), cls[:n], hq[:n]
 
     def map_ground_grid(self):
         """qn_kf_map_ground_grid -> (info, ground_q (H, W) int32, occupancy (H, W) uint8) of the latest map_ground: info a dict of origin_x, origin_y, cell, width,
@@ -1658,60 +1666,40 @@ class KeyframeStore:
         W, H = int(g.width), int(g.height)
         gq = np.zeros(max(W * H, 1), np.int32); occ = np.zeros(max(W * H, 1), np.uint8)
         self._check(self._l.qn_kf_map_ground_grid(self.h, C.byref(g), _p(gq), _p(occ)))
-        info = {f: getattr(g, f) for f, _ in GroundGrid._fields_ if f != "reserved"}
-        return info, gq[:W * H].reshape(H, W), occ[:W * H].reshape(H, W)
+        return _as_dict(g), gq[:W * H].reshape(H, W), occ[:W * H].reshape(H, W)
 
     def map_keep_classes(self, mask):
         """qn_kf_map_keep_classes: the records of the latest map_ground whose class bit (1 << class) is set in mask become the map slot, in order -> (ptr, n):
         the device address of the n float4 records x y z intensity.  download_map, map_normals and map_outliers serve the kept map; the ground results, any
         outlier classification and any map normals are stale afterwards."""
-        ptr = C.c_void_p(); n = C.c_uint32()
-        self._check(self._l.qn_kf_map_keep_classes(self.h, C.c_uint32(int(mask) & 0xffffffff), C.byref(ptr), C.byref(n)))
-        self._map_n = n.value
-        return ptr.value, n.value
+        return self._slot(self._l.qn_kf_map_keep_classes, C.c_uint32(int(mask) & 0xffffffff))
 
     # ---- a 3-D occupancy map by ray carving (qn_kf_map_occupancy / _grid / _list / _slice; numpy twin: qn_amd/mapoccupancy.py)
     def map_occupancy(self, ids, poses, params=None):
         """qn_kf_map_occupancy over the list build_map takes: every record of every listed keyframe is a ray from the entry's sensor position to the world point.
         params: an OccupancyParams (or a mapoccupancy.OccupancyParams); None: the defaults.  -> stats, a dict of the fields of qn_occupancy_stats, equal to
         those of mapoccupancy.classify of the same keyframes.  The map slot is neither read nor touched; map_occupancy_grid / _list / _slice serve the volume."""
-        ids = np.ascontiguousarray(ids, dtype=np.int32); poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(len(ids), 16)
-        p = OccupancyParams() if params is None else params
-        if not isinstance(p, OccupancyParams):
-            p = OccupancyParams(float(p.voxel), float(p.min_range), float(p.max_range), int(p.shell), int(p.min_hits), int(p.hit_weight))
+        ids, poses = self._ids_poses(ids, poses)
+        p = _record(OccupancyParams, params)
         st = OccupancyStats()
         self._check(self._l.qn_kf_map_occupancy(self.h, _p(ids), _p(poses), C.c_uint32(len(ids)), C.byref(p), C.byref(st)))
-        return {f: int(getattr(st, f)) for f, _ in OccupancyStats._fields_ if f != "reserved"}
+        return _as_dict(st)
 
     def map_occupancy_update(self, ids, poses, params=None):
         """qn_kf_map_occupancy_update: the resident volume brought to this list in place - the entries whose id and pose bytes the volume already holds are
         kept, the others are walked in, and what the list no longer names is walked out again.  The arguments are map_occupancy's.  -> (stats, update): stats
         the dict map_occupancy returns for the same list, update a dict of the fields of qn_occupancy_update (dirty_lo, dirty_hi as tuples), equal to
         mapoccupancy.update's.  Afterwards every getter returns the bytes it returns after map_occupancy of the same list."""
-        ids = np.ascontiguousarray(ids, dtype=np.int32); poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(len(ids), 16)
-        p = OccupancyParams() if params is None else params
-        if not isinstance(p, OccupancyParams):
-            p = OccupancyParams(float(p.voxel), float(p.min_range), float(p.max_range), int(p.shell), int(p.min_hits), int(p.hit_weight))
+        ids, poses = self._ids_poses(ids, poses)
+        p = _record(OccupancyParams, params)
         st = OccupancyStats(); up = OccupancyUpdate()
         self._check(self._l.qn_kf_map_occupancy_update(self.h, _p(ids), _p(poses), C.c_uint32(len(ids)), C.byref(p), C.byref(st), C.byref(up)))
-        upd = {f: (tuple(int(v) for v in getattr(up, f)) if f.startswith("dirty") else int(getattr(up, f))) for f, _ in OccupancyUpdate._fields_}
-        return {f: int(getattr(st, f)) for f, _ in OccupancyStats._fields_ if f != "reserved"}, upd
-
-    @staticmethod
-    def _occupancy_info(g):
-        return dict(origin=tuple(float(v) for v in g.origin), voxel=float(g.voxel), width=int(g.width), height=int(g.height), depth=int(g.depth),
-                    minc=tuple(int(v) for v in g.minc))
+        return _as_dict(st), _as_dict(up)
 
     def map_occupancy_grid(self):
         """qn_kf_map_occupancy_grid -> (info, hits (D, H, W) uint32, misses (D, H, W) uint32, classes (D, H, W) uint8) of the latest map_occupancy: info a dict of
         origin, voxel, width, height, depth, minc; x the fastest axis, z the slowest; classes 0 unknown, 1 free, 2 occupied."""
-        g = OccupancyGrid()
-        self._check(self._l.qn_kf_map_occupancy_grid(self.h, C.byref(g), None, None, None))
-        W, H, D = int(g.width), int(g.height), int(g.depth)
-        n = W * H * D
-        hits = np.zeros(max(n, 1), np.uint32); misses = np.zeros(max(n, 1), np.uint32); cls = np.zeros(max(n, 1), np.uint8)
-        self._check(self._l.qn_kf_map_occupancy_grid(self.h, C.byref(g), _p(hits), _p(misses), _p(cls)))
-        return self._occupancy_info(g), hits[:n].reshape(D, H, W), misses[:n].reshape(D, H, W), cls[:n].reshape(D, H, W)
+        return self._volume(self._l.qn_kf_map_occupancy_grid, (np.uint32, np.uint32, np.uint8))
 
     def map_occupancy_list(self, mask=1 << QN_OCC_OCCUPIED):
         """qn_kf_map_occupancy_list -> (ijk (m, 3) int32 grid indices, hits (m,) uint32, misses (m,) uint32) of the voxels whose class bit (1 << class) is set in
@@ -1727,45 +1715,29 @@ class KeyframeStore:
     def map_occupancy_slice(self, iz_lo, iz_hi):
         """qn_kf_map_occupancy_slice -> (H, W) uint8: per column over the layers iz_lo .. iz_hi (inclusive, clipped to the grid) 2 if any voxel is occupied, else 1
         if any is free, else 0 - the values of map_ground_grid's occupancy, so mapground.to_pgm / map_yaml serve it"""
-        g = OccupancyGrid()
-        self._check(self._l.qn_kf_map_occupancy_grid(self.h, C.byref(g), None, None, None))
-        W, H = int(g.width), int(g.height)
-        out = np.zeros(max(W * H, 1), np.uint8)
-        self._check(self._l.qn_kf_map_occupancy_slice(self.h, C.c_int32(int(iz_lo)), C.c_int32(int(iz_hi)), _p(out)))
-        return out[:W * H].reshape(H, W)
+        g, _ = self._grid(self._l.qn_kf_map_occupancy_grid, 3)
+        return self._slice(g, self._l.qn_kf_map_occupancy_slice, iz_lo, iz_hi, np.uint8)
 
     # ---- the occupancy map's Euclidean distance field (qn_kf_map_distance / _grid / _slice / _query; numpy twin: qn_amd/mapdistance.py)
     def map_distance(self, params=None):
         """qn_kf_map_distance over the class bytes of the latest map_occupancy: per voxel the squared distance, in voxels, to the nearest voxel whose class bit
         is in site_mask, QN_DIST_FAR beyond max_dist.  params: a DistanceParams (or a mapdistance.DistanceParams); None: the defaults.  -> stats, a dict of the
         fields of qn_distance_stats, equal to those of mapdistance.transform of the downloaded classes.  map_distance_grid / _slice / _query serve the field."""
-        p = DistanceParams() if params is None else params
-        if not isinstance(p, DistanceParams):
-            p = DistanceParams(int(p.site_mask), int(p.max_dist))
+        p = _record(DistanceParams, params)
         st = DistanceStats()
         self._check(self._l.qn_kf_map_distance(self.h, C.byref(p), C.byref(st)))
-        return {f: int(getattr(st, f)) for f, _ in DistanceStats._fields_ if f != "reserved"}
+        return _as_dict(st)
 
     def map_distance_grid(self):
         """qn_kf_map_distance_grid -> (info, params, d2 (D, H, W) uint16) of the latest map_distance: info the occupancy grid's dict (map_occupancy_grid),
         params a dict of site_mask and max_dist"""
-        g = OccupancyGrid(); p = DistanceParams()
-        self._check(self._l.qn_kf_map_distance_grid(self.h, C.byref(g), C.byref(p), None))
-        W, H, D = int(g.width), int(g.height), int(g.depth)
-        n = W * H * D
-        d2 = np.zeros(max(n, 1), np.uint16)
-        self._check(self._l.qn_kf_map_distance_grid(self.h, C.byref(g), C.byref(p), _p(d2)))
-        return self._occupancy_info(g), dict(site_mask=int(p.site_mask), max_dist=int(p.max_dist)), d2[:n].reshape(D, H, W)
+        return self._volume(self._l.qn_kf_map_distance_grid, (np.uint16,), DistanceParams())
 
     def map_distance_slice(self, iz_lo, iz_hi):
         """qn_kf_map_distance_slice -> (H, W) uint16: per column the smallest d2 over the layers iz_lo .. iz_hi (inclusive, clipped to the grid), QN_DIST_FAR
         when the band misses the grid: the clearance of an upright body spanning those layers"""
-        g = OccupancyGrid(); p = DistanceParams()
-        self._check(self._l.qn_kf_map_distance_grid(self.h, C.byref(g), C.byref(p), None))
-        W, H = int(g.width), int(g.height)
-        out = np.zeros(max(W * H, 1), np.uint16)
-        self._check(self._l.qn_kf_map_distance_slice(self.h, C.c_int32(int(iz_lo)), C.c_int32(int(iz_hi)), _p(out)))
-        return out[:W * H].reshape(H, W)
+        g, _ = self._grid(self._l.qn_kf_map_distance_grid, 1, DistanceParams())
+        return self._slice(g, self._l.qn_kf_map_distance_slice, iz_lo, iz_hi, np.uint16)
 
     def map_distance_query(self, xyz):
         """qn_kf_map_distance_query: world points (n, 3) f64 -> (d2 (n,) uint16, class (n,) uint8) of the voxel each falls in; QN_DIST_FAR and QN_DIST_OUTSIDE
@@ -1782,26 +1754,16 @@ class KeyframeStore:
         nearest of the world points `goals` (n, 3) f64 through passable voxels, QN_ROUTE_BLOCKED where not passable, QN_ROUTE_UNREACHED where cut off.  params:
         a RouteParams (or a maproute.RouteParams); None: the defaults.  -> stats, a dict of the fields of qn_route_stats; all but rounds and tile_visits equal
         those of maproute.field of the downloaded classes and d2.  map_route_grid / _query / _paths serve the field."""
-        p = RouteParams() if params is None else params
-        if not isinstance(p, RouteParams):
-            p = RouteParams(*(int(v) for v in p))
+        p = _record(RouteParams, params)
         xyz = np.ascontiguousarray(goals, dtype=np.float64).reshape(-1, 3)
         st = RouteStats()
         self._check(self._l.qn_kf_map_route(self.h, _p(xyz), C.c_uint32(len(xyz)), C.byref(p), C.byref(st)))
-        return {f: int(getattr(st, f)) for f, _ in RouteStats._fields_ if not f.startswith("reserved")}
+        return _as_dict(st)
 
     def map_route_grid(self):
         """qn_kf_map_route_grid -> (info, params, cost (D, H, W) uint32, or (1, H, W) in planar mode) of the latest map_route: info the occupancy grid's dict,
         params a dict of the fields of qn_route_params"""
-        g = OccupancyGrid(); p = RouteParams()
-        self._check(self._l.qn_kf_map_route_grid(self.h, C.byref(g), C.byref(p), None))
-        W, H, D = int(g.width), int(g.height), int(g.depth)
-        if p.planar:
-            D = 1 if W * H else 0
-        n = W * H * D
-        cost = np.zeros(max(n, 1), np.uint32)
-        self._check(self._l.qn_kf_map_route_grid(self.h, C.byref(g), C.byref(p), _p(cost)))
-        return self._occupancy_info(g), p.twin()._asdict(), cost[:n].reshape(D, H, W)
+        return self._volume(self._l.qn_kf_map_route_grid, (np.uint32,), RouteParams(), planar=True)
 
     def map_route_query(self, xyz):
         """qn_kf_map_route_query: world points (n, 3) f64 -> the field's value (n,) uint32 at each; QN_ROUTE_BLOCKED for a point that is not finite or outside"""
@@ -1827,55 +1789,30 @@ class KeyframeStore:
         at least min_size voxels, numbered in ascending root.  params: a FrontierParams (or a mapfrontier.FrontierParams); None: the defaults.  -> stats, a dict
         of the fields of qn_frontier_stats; all but rounds equal those of mapfrontier.frontier of the downloaded classes.  map_frontier_grid / _regions /
         _list / _costs serve the result; neither map_distance nor map_route is needed, only map_frontier_costs reads the route field."""
-        p = FrontierParams() if params is None else params
-        if not isinstance(p, FrontierParams):
-            p = FrontierParams(*(int(v) for v in p))
+        p = _record(FrontierParams, params)
         st = FrontierStats()
         self._check(self._l.qn_kf_map_frontiers(self.h, C.byref(p), C.byref(st)))
-        return {f: int(getattr(st, f)) for f, _ in FrontierStats._fields_ if f != "reserved"}
+        return _as_dict(st)
 
     def map_frontier_grid(self):
         """qn_kf_map_frontier_grid -> (info, params, labels (D, H, W) int32) of the latest map_frontiers: info the occupancy grid's dict, params a dict of the
         fields of qn_frontier_params; a label is the region number, QN_FRONTIER_REJECTED or QN_FRONTIER_NONE"""
-        g = OccupancyGrid(); p = FrontierParams()
-        self._check(self._l.qn_kf_map_frontier_grid(self.h, C.byref(g), C.byref(p), None))
-        W, H, D = int(g.width), int(g.height), int(g.depth)
-        n = W * H * D
-        lab = np.zeros(max(n, 1), np.int32)
-        self._check(self._l.qn_kf_map_frontier_grid(self.h, C.byref(g), C.byref(p), _p(lab)))
-        return self._occupancy_info(g), p.twin()._asdict(), lab[:n].reshape(D, H, W)
+        return self._volume(self._l.qn_kf_map_frontier_grid, (np.int32,), FrontierParams())
 
     def map_frontier_regions(self):
         """qn_kf_map_frontier_regions -> the regions of the latest map_frontiers, a structured array of mapfrontier.INFO_DTYPE in region order"""
         from . import mapfrontier
-        cnt = C.c_uint32()
-        st = self._l.qn_kf_map_frontier_regions(self.h, None, C.c_uint32(0), C.byref(cnt))
-        if st != QN_ERR_CAPACITY:
-            self._check(st)
-        info = np.zeros(max(int(cnt.value), 1), mapfrontier.INFO_DTYPE)
-        self._check(self._l.qn_kf_map_frontier_regions(self.h, _p(info), C.c_uint32(len(info)), C.byref(cnt)))
-        return info[:cnt.value]
+        return self._listed(self._l.qn_kf_map_frontier_regions, ((), mapfrontier.INFO_DTYPE))[0]
 
     def map_frontier_list(self):
         """qn_kf_map_frontier_list -> (ijk (m, 3) int32 grid indices, label (m,) int32) of every frontier voxel of the latest map_frontiers, kept or rejected,
         in ascending linear index"""
-        cnt = C.c_uint32()
-        st = self._l.qn_kf_map_frontier_list(self.h, None, None, C.c_uint32(0), C.byref(cnt))
-        if st != QN_ERR_CAPACITY:
-            self._check(st)
-        m = int(cnt.value)
-        ijk = np.zeros((max(m, 1), 3), np.int32); lab = np.zeros(max(m, 1), np.int32)
-        self._check(self._l.qn_kf_map_frontier_list(self.h, _p(ijk), _p(lab), C.c_uint32(len(lab)), C.byref(cnt)))
-        return ijk[:m], lab[:m]
+        return tuple(self._listed(self._l.qn_kf_map_frontier_list, ((3,), np.int32), ((), np.int32)))
 
     def map_frontier_costs(self):
         """qn_kf_map_frontier_costs with the field of the latest map_route -> (cost (R,) uint32, ijk (R, 3) int32): per region the smallest cost below
         QN_ROUTE_BLOCKED over its voxels and the voxel attaining it (the smallest linear index on a tie); QN_ROUTE_UNREACHED and (0, 0, 0) without one"""
-        cnt = C.c_uint32()
-        st = self._l.qn_kf_map_frontier_regions(self.h, None, C.c_uint32(0), C.byref(cnt))
-        if st != QN_ERR_CAPACITY:
-            self._check(st)
-        R = int(cnt.value)
+        R = self._count(self._l.qn_kf_map_frontier_regions, 1)
         cost = np.zeros(max(R, 1), np.uint32); ijk = np.zeros((max(R, 1), 3), np.int32)
         self._check(self._l.qn_kf_map_frontier_costs(self.h, _p(cost), _p(ijk)))
         return cost[:R], ijk[:R]
@@ -1888,26 +1825,18 @@ class KeyframeStore:
         -> (info, a structured array of mapview.VIEW_DTYPE, one row per viewpoint; stats, a dict of the fields of qn_view_stats): all but passes equal those of
         mapview.gain of the downloaded classes.  map_view_grid serves the cover volume."""
         from . import mapview
-        p = ViewParams() if params is None else params
-        if not isinstance(p, ViewParams):
-            p = ViewParams(*(int(v) for v in p))
+        p = _record(ViewParams, params)
         xyz = np.ascontiguousarray(viewpoints, dtype=np.float64).reshape(-1, 3)
         off = np.ascontiguousarray(offsets, dtype=np.int32).reshape(-1, 3)
         info = np.zeros(max(len(xyz), 1), mapview.VIEW_DTYPE)
         st = ViewStats()
         self._check(self._l.qn_kf_map_view_gain(self.h, _p(xyz), C.c_uint32(len(xyz)), _p(off), C.c_uint32(len(off)), C.byref(p), _p(info), C.byref(st)))
-        return info[:len(xyz)], {f: int(getattr(st, f)) for f, _ in ViewStats._fields_ if f != "reserved"}
+        return info[:len(xyz)], _as_dict(st)
 
     def map_view_grid(self):
         """qn_kf_map_view_grid -> (info, params, cover (D, H, W) uint32) of the latest map_view_gain: info the occupancy grid's dict, params a dict of the fields
         of qn_view_params; cover[v] is the number of viewpoints that marked voxel v"""
-        g = OccupancyGrid(); p = ViewParams()
-        self._check(self._l.qn_kf_map_view_grid(self.h, C.byref(g), C.byref(p), None))
-        W, H, D = int(g.width), int(g.height), int(g.depth)
-        n = W * H * D
-        cover = np.zeros(max(n, 1), np.uint32)
-        self._check(self._l.qn_kf_map_view_grid(self.h, C.byref(g), C.byref(p), _p(cover)))
-        return self._occupancy_info(g), p.twin()._asdict(), cover[:n].reshape(D, H, W)
+        return self._volume(self._l.qn_kf_map_view_grid, (np.uint32,), ViewParams())
 
     # ---- the map slot's points clustered into objects (qn_kf_map_clusters / _cluster_points / _cluster_list / qn_kf_map_drop_rejected_clusters; numpy twin:
     # qn_amd/mapclusters.py)
@@ -1918,9 +1847,7 @@ class KeyframeStore:
         uint32, lo and hi (C, 3) float32, sum_q (C, 3) int64 and centroid (C, 3) float64 = sum_q / size * 2^-quant_exp.  The map slot is not touched;
         map_drop_rejected_clusters applies the result."""
         from . import mapclusters
-        p = ClusterParams() if params is None else params
-        if not isinstance(p, ClusterParams):
-            p = ClusterParams(float(p.tolerance), int(p.min_size), int(p.max_size), int(p.class_mask))
+        p = _record(ClusterParams, params)
         st = ClusterStats()
         self._check(self._l.qn_kf_map_clusters(self.h, C.byref(p), C.byref(st)))
         n = int(st.n)
@@ -1930,7 +1857,7 @@ class KeyframeStore:
         info = np.zeros(max(int(st.clusters), 1), mapclusters.INFO_DTYPE)
         self._check(self._l.qn_kf_map_cluster_list(self.h, _p(info), C.c_uint32(len(info)), C.byref(cnt)))
         info = info[:cnt.value]
-        stats = {f: getattr(st, f) for f, _ in ClusterStats._fields_ if f != "reserved"}
+        stats = _as_dict(st)
         clusters = {f: info[f].copy() for f in ("root", "size", "lo", "hi", "sum_q")}
         clusters["centroid"] = info["sum_q"].astype(np.float64) / info["size"].astype(np.float64)[:, None] * math.ldexp(1.0, -int(st.quant_exp))
         return stats, label[:n], root[:n], size[:n], clusters
@@ -1939,10 +1866,7 @@ class KeyframeStore:
         """qn_kf_map_drop_rejected_clusters: the map slot without the members of the components the latest map_clusters rejected, in order -> (ptr, n): the
         device address of the n float4 records x y z intensity.  Records that were not members stay.  Every result computed from the old slot is stale
         afterwards."""
-        ptr = C.c_void_p(); n = C.c_uint32()
-        self._check(self._l.qn_kf_map_drop_rejected_clusters(self.h, C.byref(ptr), C.byref(n)))
-        self._map_n = n.value
-        return ptr.value, n.value
+        return self._slot(self._l.qn_kf_map_drop_rejected_clusters)
 
     # ---- scans localised in the map slot (qn_kf_map_crop / _crop_get / qn_kf_map_localize[_c2f]; numpy twin of the crop: qn_amd/maplocalize.py)
     def map_crop(self, centres, radius, shape=0):
@@ -1958,23 +1882,17 @@ class KeyframeStore:
         """qn_kf_map_crop_get and the download of crop `crop` of the latest map_crop / map_localize -> dict(n, ptr, xyzi, idx)"""
         ptr = C.c_void_p(); n = C.c_uint32()
         self._check(self._l.qn_kf_map_crop_get(self.h, C.c_uint32(crop), C.byref(ptr), C.byref(n), None))
-        idx = np.zeros(max(n.value, 1), np.uint32); xyzi = np.zeros((n.value, 4), np.float32)
+        idx = np.zeros(max(n.value, 1), np.uint32)
         if n.value:
             self._check(self._l.qn_kf_map_crop_get(self.h, C.c_uint32(crop), C.byref(ptr), C.byref(n), _p(idx)))
-            l = self._l; l.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]; l.hipMemcpy.restype = C.c_int
-            if l.hipMemcpy(xyzi.ctypes.data, ptr, 16 * n.value, 2) != 0:
-                raise EngineError(QN_ERR_HIP, "map_crop_get: read-back failed")
-        return dict(n=int(n.value), ptr=ptr.value, xyzi=xyzi, idx=idx[:n.value].copy())
+        return dict(n=int(n.value), ptr=ptr.value, xyzi=self._read_float4(ptr, n.value, "map_crop_get"), idx=idx[:n.value].copy())
 
     def _localize_args(self, query, guesses, params):
         q = np.ascontiguousarray(np.atleast_1d(query), dtype=np.int32)
         g = np.ascontiguousarray(np.asarray(guesses, dtype=np.float64).reshape(-1, 16))
         if len(q) != len(g):
             raise ValueError("map_localize: %d queries but %d guesses" % (len(q), len(g)))
-        p = LocalizeParams() if params is None else params
-        if not isinstance(p, LocalizeParams):
-            p = LocalizeParams(float(p.radius), float(p.leaf), float(p.score_thr), int(p.shape))
-        return q, g, p, len(q)
+        return q, g, _record(LocalizeParams, params), len(q)
 
     def map_localize(self, ctx, query, guesses, params=None):
         """qn_kf_map_localize: pair j = keyframe query[j] (alone in its sensor frame, voxel grid at params.leaf) registered against the crop of the map slot
@@ -1985,8 +1903,7 @@ class KeyframeStore:
         results, valid, status, _, _ = _verify_out(n); st = LocalizeStats()
         rc = self._l.qn_kf_map_localize(self.h, ctx.h, C.byref(p), _p(q) if n else None, _p(g) if n else None, C.c_uint32(n), results, _p(valid), _p(status), C.byref(st))
         self._raise(rc, ctx)
-        stats = {f: int(getattr(st, f)) for f, _ in LocalizeStats._fields_ if f != "reserved"}
-        return _gicp_dicts(results, valid, status, n), stats
+        return _gicp_dicts(results, valid, status, n), _as_dict(st)
 
     def map_localize_c2f(self, ctx, query, guesses, params=None):
         """qn_kf_map_localize_c2f: the same clouds coarse to fine (Quatro -> transformPcd -> Nano-GICP); only the guess's translation is used, as the crop
@@ -1997,8 +1914,7 @@ class KeyframeStore:
         rc = self._l.qn_kf_map_localize_c2f(self.h, ctx.h, C.byref(p), _p(q) if n else None, _p(g) if n else None, C.c_uint32(n), results, _p(Tt), _p(Tq),
                                             _p(valid), _p(status), C.byref(st))
         self._raise(rc, ctx)
-        stats = {f: int(getattr(st, f)) for f, _ in LocalizeStats._fields_ if f != "reserved"}
-        return _c2f_dicts(results, Tt, Tq, valid, status, n), stats
+        return _c2f_dicts(results, Tt, Tq, valid, status, n), _as_dict(st)
 
     # ---- Scan Context loop candidates (qn_kf_sc_*; numpy twin: qn_amd/scancontext.py)
     def sc_set_params(self, params=None, **kw):

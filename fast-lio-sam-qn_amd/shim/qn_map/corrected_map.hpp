@@ -18,6 +18,7 @@
 #include <pcl/point_types.h>
 #include <Eigen/Core>
 #include "qn_engine.h"
+#include "detail.hpp"
 
 namespace qn_map {
 
@@ -26,7 +27,7 @@ class CorrectedMap {
  public:
   explicit CorrectedMap(int device = 0) {
     const int rc = qn_kf_store_create(device, &store_);
-    if (rc != QN_OK) throw std::runtime_error(std::string("[qn_map] qn_kf_store_create: ") + qn_status_str(rc));
+    if (rc != QN_OK) throw std::runtime_error(detail::why("qn_kf_store_create", rc, nullptr));
   }
   ~CorrectedMap() { qn_kf_store_destroy(store_); }
   CorrectedMap(const CorrectedMap&) = delete;
@@ -66,9 +67,7 @@ class CorrectedMap {
   }
 
  private:
-  void check(int rc, const char* what) {
-    if (rc != QN_OK) throw std::runtime_error(std::string("[qn_map] ") + what + ": " + qn_status_str(rc) + " " + qn_kf_last_error(store_));
-  }
+  void check(int rc, const char* what) { detail::check(store_, rc, what); }
   qn_kf_store* store_ = nullptr;
 };
 

@@ -10,6 +10,7 @@
 #include <string>
 #include <vector>
 #include "qn_engine.h"
+#include "detail.hpp"
 
 namespace qn_map {
 
@@ -20,7 +21,7 @@ inline std::vector<int> describeRangeImages(qn_kf_store* store, const std::vecto
   if (ids.empty()) return status;
   std::vector<int32_t> id32(ids.begin(), ids.end());
   const int rc = qn_kf_range_describe(store, id32.data(), (uint32_t)id32.size(), status.data());
-  if (rc != QN_OK) throw std::runtime_error(std::string("[qn_map] qn_kf_range_describe: ") + qn_status_str(rc) + " " + qn_kf_last_error(store));
+  detail::check(store, rc, "qn_kf_range_describe");
   return status;
 }
 
@@ -39,7 +40,7 @@ inline std::vector<FreespaceChecked> freespaceBatch(qn_kf_store* store, const st
   std::vector<qn_freespace> rec(q.size());
   std::vector<int> status(q.size());
   const int rc = qn_kf_freespace_batch(store, q.data(), c.data(), T16.data(), (uint32_t)q.size(), rec.data(), status.data());
-  if (rc != QN_OK) throw std::runtime_error(std::string("[qn_map] qn_kf_freespace_batch: ") + qn_status_str(rc) + " " + qn_kf_last_error(store));
+  detail::check(store, rc, "qn_kf_freespace_batch");
   for (size_t k = 0; k < q.size(); k++) out.push_back(FreespaceChecked{rec[k], status[k]});
   return out;
 }

@@ -11,6 +11,7 @@
 #include <vector>
 #include <Eigen/Core>
 #include "qn_engine.h"
+#include "detail.hpp"
 
 namespace qn_map {
 
@@ -57,7 +58,7 @@ inline std::vector<qn_pair_desc> loopSubmapPairs(qn_kf_store* store, const std::
   const uint32_t S = (uint32_t)candidates.size() + 1;
   std::vector<const float*> ptr(S); std::vector<uint32_t> n(S); std::vector<int> st(S);
   const int rc = qn_kf_assemble_batch(store, ids.data(), T.data(), seg_off.data(), S, leaf, ptr.data(), n.data(), st.data());
-  if (rc != QN_OK) throw std::runtime_error(std::string("[qn_map] qn_kf_assemble_batch: ") + qn_status_str(rc) + " " + qn_kf_last_error(store));
+  detail::check(store, rc, "qn_kf_assemble_batch");
   if (status) *status = st;
   std::vector<qn_pair_desc> pairs(candidates.size());
   for (size_t k = 0; k < candidates.size(); k++) pairs[k] = qn_pair_desc{ptr[0], n[0], ptr[k + 1], n[k + 1], 16u, 1};

@@ -10,6 +10,7 @@
 #include <string>
 #include <vector>
 #include "qn_engine.h"
+#include "detail.hpp"
 
 namespace qn_map {
 
@@ -29,21 +30,20 @@ struct MapClusters {
 
 // the clusters of the store's map slot (qn_kf_map_clusters); the slot is not touched.  params NULL: the defaults (tolerance 0.5, 10 .. 2^32 - 1 points, mask 0)
 inline MapClusters mapClusters(qn_kf_store* store, const qn_cluster_params* params) {
-  qn_cluster_params p;
-  if (params) p = *params; else qn_cluster_default_params(&p);
+  qn_cluster_params p = detail::params_or(params, qn_cluster_default_params);
   MapClusters out;
   int rc = qn_kf_map_clusters(store, &p, &out.stats);
-  if (rc != QN_OK) throw std::runtime_error(std::string("[qn_map] qn_kf_map_clusters: ") + qn_status_str(rc) + " " + qn_kf_last_error(store));
+  detail::check(store, rc, "qn_kf_map_clusters");
   const uint32_t n = out.stats.n, C = out.stats.clusters;
   out.label.resize(n); out.root.resize(n); out.size.resize(n);
   if (n) {
     rc = qn_kf_map_cluster_points(store, out.label.data(), out.root.data(), out.size.data());
-    if (rc != QN_OK) throw std::runtime_error(std::string("[qn_map] qn_kf_map_cluster_points: ") + qn_status_str(rc) + " " + qn_kf_last_error(store));
+    detail::check(store, rc, "qn_kf_map_cluster_points");
   }
   out.info.resize(C);
   uint32_t count = 0;
   rc = qn_kf_map_cluster_list(store, C ? out.info.data() : nullptr, C, &count);
-  if (rc != QN_OK || count != C) throw std::runtime_error(std::string("[qn_map] qn_kf_map_cluster_list: ") + qn_status_str(rc) + " " + qn_kf_last_error(store));
+  if (rc != QN_OK || count != C) throw std::runtime_error(detail::why("qn_kf_map_cluster_list", rc, store));
   out.clusters.resize(C);
   for (uint32_t c = 0; c < C; c++) {
     const qn_cluster_info& i = out.info[c];
@@ -58,7 +58,7 @@ inline MapClusters mapClusters(qn_kf_store* store, const qn_cluster_params* para
 inline uint32_t dropRejectedClusters(qn_kf_store* store, const float** d_xyzi = nullptr) {
   const float* d = nullptr; uint32_t n = 0;
   const int rc = qn_kf_map_drop_rejected_clusters(store, &d, &n);
-  if (rc != QN_OK) throw std::runtime_error(std::string("[qn_map] qn_kf_map_drop_rejected_clusters: ") + qn_status_str(rc) + " " + qn_kf_last_error(store));
+  detail::check(store, rc, "qn_kf_map_drop_rejected_clusters");
   if (d_xyzi) *d_xyzi = d;
   return n;
 }

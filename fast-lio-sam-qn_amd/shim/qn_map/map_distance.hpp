@@ -12,6 +12,7 @@
 #include <string>
 #include <vector>
 #include "qn_engine.h"
+#include "detail.hpp"
 
 namespace qn_map {
 
@@ -29,14 +30,13 @@ struct MapDistance {
 // the distance field of the latest mapOccupancy (qn_kf_map_distance).  params NULL: the defaults (sites: the occupied voxels, max_dist 16 voxels); unknown space
 // as an obstacle: site_mask = (1u << QN_OCC_OCCUPIED) | (1u << QN_OCC_UNKNOWN).  The field stays resident until the next mapDistance or mapOccupancy.
 inline MapDistance mapDistance(qn_kf_store* store, const qn_distance_params* params = nullptr) {
-  qn_distance_params p;
-  if (params) p = *params; else qn_distance_default_params(&p);
+  qn_distance_params p = detail::params_or(params, qn_distance_default_params);
   if (p.max_dist < 1 || p.max_dist > QN_DIST_MAX_RADIUS) throw std::invalid_argument("[qn_map] mapDistance: max_dist of 1 .. 255 voxels");
   MapDistance out;
   int rc = qn_kf_map_distance(store, &p, &out.stats);
-  if (rc != QN_OK) throw std::runtime_error(std::string("[qn_map] qn_kf_map_distance: ") + qn_status_str(rc) + " " + qn_kf_last_error(store));
+  detail::check(store, rc, "qn_kf_map_distance");
   rc = qn_kf_map_distance_grid(store, &out.grid, &out.params, nullptr);
-  if (rc != QN_OK) throw std::runtime_error(std::string("[qn_map] qn_kf_map_distance_grid: ") + qn_status_str(rc) + " " + qn_kf_last_error(store));
+  detail::check(store, rc, "qn_kf_map_distance_grid");
   return out;
 }
 
@@ -45,11 +45,11 @@ inline MapDistance mapDistance(qn_kf_store* store, const qn_distance_params* par
 inline std::vector<uint16_t> distanceSlice(qn_kf_store* store, int32_t iz_lo, int32_t iz_hi, qn_occupancy_grid* grid = nullptr) {
   qn_occupancy_grid g; qn_distance_params p;
   int rc = qn_kf_map_distance_grid(store, &g, &p, nullptr);
-  if (rc != QN_OK) throw std::runtime_error(std::string("[qn_map] qn_kf_map_distance_grid: ") + qn_status_str(rc) + " " + qn_kf_last_error(store));
+  detail::check(store, rc, "qn_kf_map_distance_grid");
   std::vector<uint16_t> d2((size_t)g.width * g.height);
   std::vector<uint16_t> pad(1);
   rc = qn_kf_map_distance_slice(store, iz_lo, iz_hi, d2.empty() ? pad.data() : d2.data());
-  if (rc != QN_OK) throw std::runtime_error(std::string("[qn_map] qn_kf_map_distance_slice: ") + qn_status_str(rc) + " " + qn_kf_last_error(store));
+  detail::check(store, rc, "qn_kf_map_distance_slice");
   if (grid) *grid = g;
   return d2;
 }
@@ -60,11 +60,11 @@ inline std::vector<double> distanceAt(qn_kf_store* store, const std::vector<doub
   if (xyz.empty() || xyz.size() % 3 != 0) throw std::invalid_argument("[qn_map] distanceAt: 3 doubles per point, at least one point");
   qn_occupancy_grid g; qn_distance_params p;
   int rc = qn_kf_map_distance_grid(store, &g, &p, nullptr);
-  if (rc != QN_OK) throw std::runtime_error(std::string("[qn_map] qn_kf_map_distance_grid: ") + qn_status_str(rc) + " " + qn_kf_last_error(store));
+  detail::check(store, rc, "qn_kf_map_distance_grid");
   const uint32_t n = (uint32_t)(xyz.size() / 3);
   std::vector<uint16_t> d2(n); std::vector<uint8_t> cls(n);
   rc = qn_kf_map_distance_query(store, xyz.data(), n, d2.data(), cls.data());
-  if (rc != QN_OK) throw std::runtime_error(std::string("[qn_map] qn_kf_map_distance_query: ") + qn_status_str(rc) + " " + qn_kf_last_error(store));
+  detail::check(store, rc, "qn_kf_map_distance_query");
   std::vector<double> out(n);
   for (uint32_t i = 0; i < n; i++) out[i] = d2[i] == QN_DIST_FAR ? std::numeric_limits<double>::infinity() : std::sqrt((double)d2[i]) * g.voxel;
   if (classes) classes->swap(cls);

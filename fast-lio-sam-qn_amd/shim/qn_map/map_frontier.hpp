@@ -13,6 +13,7 @@
 #include <string>
 #include <vector>
 #include "qn_engine.h"
+#include "detail.hpp"
 
 namespace qn_map {
 
@@ -44,16 +45,15 @@ struct FrontierCost {
 // the space outside the grid, min_size 8, every layer).  The result stays resident until the next mapFrontiers or mapOccupancy; mapDistance and mapRoute
 // do not touch it.
 inline MapFrontiers mapFrontiers(qn_kf_store* store, const qn_frontier_params* params = nullptr) {
-  qn_frontier_params p;
-  if (params) p = *params; else qn_frontier_default_params(&p);
+  qn_frontier_params p = detail::params_or(params, qn_frontier_default_params);
   if (p.iz_lo > p.iz_hi) throw std::invalid_argument("[qn_map] mapFrontiers: iz_lo <= iz_hi");
   if (p.min_size == 0) throw std::invalid_argument("[qn_map] mapFrontiers: min_size of at least 1");
   if (p.free_mask & p.unknown_mask) throw std::invalid_argument("[qn_map] mapFrontiers: free_mask and unknown_mask share a class");
   MapFrontiers out;
   int rc = qn_kf_map_frontiers(store, &p, &out.stats);
-  if (rc != QN_OK) throw std::runtime_error(std::string("[qn_map] qn_kf_map_frontiers: ") + qn_status_str(rc) + " " + qn_kf_last_error(store));
+  detail::check(store, rc, "qn_kf_map_frontiers");
   rc = qn_kf_map_frontier_grid(store, &out.grid, &out.params, nullptr);
-  if (rc != QN_OK) throw std::runtime_error(std::string("[qn_map] qn_kf_map_frontier_grid: ") + qn_status_str(rc) + " " + qn_kf_last_error(store));
+  detail::check(store, rc, "qn_kf_map_frontier_grid");
   return out;
 }
 
@@ -61,11 +61,11 @@ inline MapFrontiers mapFrontiers(qn_kf_store* store, const qn_frontier_params* p
 inline std::vector<qn_frontier_info> frontierRegions(qn_kf_store* store) {
   uint32_t n = 0;
   int rc = qn_kf_map_frontier_regions(store, nullptr, 0, &n);
-  if (rc != QN_OK && rc != QN_ERR_CAPACITY) throw std::runtime_error(std::string("[qn_map] qn_kf_map_frontier_regions: ") + qn_status_str(rc) + " " + qn_kf_last_error(store));
+  detail::check(store, rc, "qn_kf_map_frontier_regions", QN_ERR_CAPACITY);
   std::vector<qn_frontier_info> out(n);
   if (!n) return out;
   rc = qn_kf_map_frontier_regions(store, out.data(), n, &n);
-  if (rc != QN_OK) throw std::runtime_error(std::string("[qn_map] qn_kf_map_frontier_regions: ") + qn_status_str(rc) + " " + qn_kf_last_error(store));
+  detail::check(store, rc, "qn_kf_map_frontier_regions");
   return out;
 }
 
@@ -74,12 +74,12 @@ inline std::vector<qn_frontier_info> frontierRegions(qn_kf_store* store) {
 inline std::vector<std::array<int32_t, 3>> frontierVoxels(qn_kf_store* store, std::vector<int32_t>* labels = nullptr) {
   uint32_t n = 0;
   int rc = qn_kf_map_frontier_list(store, nullptr, nullptr, 0, &n);
-  if (rc != QN_OK && rc != QN_ERR_CAPACITY) throw std::runtime_error(std::string("[qn_map] qn_kf_map_frontier_list: ") + qn_status_str(rc) + " " + qn_kf_last_error(store));
+  detail::check(store, rc, "qn_kf_map_frontier_list", QN_ERR_CAPACITY);
   std::vector<std::array<int32_t, 3>> out(n);
   std::vector<int32_t> lab(n);
   if (n) {
     rc = qn_kf_map_frontier_list(store, &out[0][0], lab.data(), n, &n);
-    if (rc != QN_OK) throw std::runtime_error(std::string("[qn_map] qn_kf_map_frontier_list: ") + qn_status_str(rc) + " " + qn_kf_last_error(store));
+    detail::check(store, rc, "qn_kf_map_frontier_list");
   }
   if (labels) labels->swap(lab);
   return out;
@@ -89,11 +89,11 @@ inline std::vector<std::array<int32_t, 3>> frontierVoxels(qn_kf_store* store, st
 inline std::vector<FrontierCost> frontierCosts(qn_kf_store* store) {
   uint32_t n = 0;
   int rc = qn_kf_map_frontier_regions(store, nullptr, 0, &n);
-  if (rc != QN_OK && rc != QN_ERR_CAPACITY) throw std::runtime_error(std::string("[qn_map] qn_kf_map_frontier_regions: ") + qn_status_str(rc) + " " + qn_kf_last_error(store));
+  detail::check(store, rc, "qn_kf_map_frontier_regions", QN_ERR_CAPACITY);
   std::vector<uint32_t> cost(n ? n : 1);
   std::vector<int32_t> ijk(3 * (size_t)(n ? n : 1));
   rc = qn_kf_map_frontier_costs(store, cost.data(), ijk.data());
-  if (rc != QN_OK) throw std::runtime_error(std::string("[qn_map] qn_kf_map_frontier_costs: ") + qn_status_str(rc) + " " + qn_kf_last_error(store));
+  detail::check(store, rc, "qn_kf_map_frontier_costs");
   std::vector<FrontierCost> out(n);
   for (uint32_t k = 0; k < n; k++) { out[k].cost = cost[k]; out[k].voxel = {ijk[3 * (size_t)k], ijk[3 * (size_t)k + 1], ijk[3 * (size_t)k + 2]}; }
   return out;

@@ -11,6 +11,7 @@
 #include <string>
 #include <vector>
 #include "qn_engine.h"
+#include "detail.hpp"
 
 namespace qn_map {
 
@@ -31,16 +32,15 @@ struct OccupancyGrid {
 
 // the classes of the store's map slot (qn_kf_map_ground); the slot is not touched.  params NULL: the defaults (cell 0.5, slope 0.3, tolerance 0.2, clearance 2.0)
 inline MapGround mapGround(qn_kf_store* store, const qn_ground_params* params) {
-  qn_ground_params p;
-  if (params) p = *params; else qn_ground_default_params(&p);
+  qn_ground_params p = detail::params_or(params, qn_ground_default_params);
   MapGround out;
   int rc = qn_kf_map_ground(store, &p, &out.stats);
-  if (rc != QN_OK) throw std::runtime_error(std::string("[qn_map] qn_kf_map_ground: ") + qn_status_str(rc) + " " + qn_kf_last_error(store));
+  detail::check(store, rc, "qn_kf_map_ground");
   const uint32_t n = out.stats.n;
   out.classes.resize(n); out.height_q.resize(n);
   if (!n) return out;
   rc = qn_kf_map_ground_points(store, out.classes.data(), out.height_q.data());
-  if (rc != QN_OK) throw std::runtime_error(std::string("[qn_map] qn_kf_map_ground_points: ") + qn_status_str(rc) + " " + qn_kf_last_error(store));
+  detail::check(store, rc, "qn_kf_map_ground_points");
   return out;
 }
 
@@ -48,12 +48,12 @@ inline MapGround mapGround(qn_kf_store* store, const qn_ground_params* params) {
 inline OccupancyGrid occupancyGrid(qn_kf_store* store) {
   OccupancyGrid g;
   int rc = qn_kf_map_ground_grid(store, &g.info, nullptr, nullptr);
-  if (rc != QN_OK) throw std::runtime_error(std::string("[qn_map] qn_kf_map_ground_grid: ") + qn_status_str(rc) + " " + qn_kf_last_error(store));
+  detail::check(store, rc, "qn_kf_map_ground_grid");
   const size_t cells = (size_t)g.info.width * g.info.height;
   g.ground_q.resize(cells); g.occupancy.resize(cells);
   if (!cells) return g;
   rc = qn_kf_map_ground_grid(store, &g.info, g.ground_q.data(), g.occupancy.data());
-  if (rc != QN_OK) throw std::runtime_error(std::string("[qn_map] qn_kf_map_ground_grid: ") + qn_status_str(rc) + " " + qn_kf_last_error(store));
+  detail::check(store, rc, "qn_kf_map_ground_grid");
   return g;
 }
 
@@ -62,7 +62,7 @@ inline OccupancyGrid occupancyGrid(qn_kf_store* store) {
 inline uint32_t keepClasses(qn_kf_store* store, uint32_t class_mask, const float** d_xyzi = nullptr) {
   const float* d = nullptr; uint32_t n = 0;
   const int rc = qn_kf_map_keep_classes(store, class_mask, &d, &n);
-  if (rc != QN_OK) throw std::runtime_error(std::string("[qn_map] qn_kf_map_keep_classes: ") + qn_status_str(rc) + " " + qn_kf_last_error(store));
+  detail::check(store, rc, "qn_kf_map_keep_classes");
   if (d_xyzi) *d_xyzi = d;
   return n;
 }

@@ -11,6 +11,7 @@
 #include <string>
 #include <vector>
 #include "qn_engine.h"
+#include "detail.hpp"
 
 namespace qn_map {
 
@@ -29,14 +30,6 @@ struct MapLocalization {
 };
 
 namespace detail {
-inline std::string why(const char* call, int rc, qn_kf_store* store) {
-  return std::string("[qn_map] ") + call + ": " + qn_status_str(rc) + (store ? std::string(" ") + qn_kf_last_error(store) : std::string());
-}
-inline const qn_localize_params* params_or_default(const qn_localize_params* params, qn_localize_params* tmp) {
-  if (params) return params;
-  qn_localize_default_params(tmp);
-  return tmp;
-}
 inline void check_sizes(const std::vector<int32_t>& query, const std::vector<std::array<double, 16>>& guesses) {
   if (query.size() != guesses.size()) throw std::invalid_argument("[qn_map] localizeInMap: one guess per query");
 }
@@ -61,10 +54,10 @@ inline std::vector<MapCrop> cropMap(qn_kf_store* store, const std::vector<std::a
 inline std::vector<MapLocalization> localizeInMap(qn_kf_store* store, qn_ctx* ctx, const std::vector<int32_t>& query, const std::vector<std::array<double, 16>>& guesses,
                                                   const qn_localize_params* params = nullptr, qn_localize_stats* stats = nullptr) {
   detail::check_sizes(query, guesses);
-  qn_localize_params tmp;
+  const qn_localize_params p = detail::params_or(params, qn_localize_default_params);
   const size_t n = query.size();
   std::vector<qn_gicp_result> res(n + 1); std::vector<int> valid(n + 1, 0), status(n + 1, 0);
-  const int rc = qn_kf_map_localize(store, ctx, detail::params_or_default(params, &tmp), n ? query.data() : nullptr, n ? guesses[0].data() : nullptr, (uint32_t)n,
+  const int rc = qn_kf_map_localize(store, ctx, &p, n ? query.data() : nullptr, n ? guesses[0].data() : nullptr, (uint32_t)n,
                                     res.data(), valid.data(), status.data(), stats);
   if (rc != QN_OK) throw std::runtime_error(detail::why("qn_kf_map_localize", rc, store));
   std::vector<MapLocalization> out(n);
@@ -81,11 +74,11 @@ inline std::vector<MapLocalization> localizeInMapCoarseToFine(qn_kf_store* store
                                                               const std::vector<std::array<double, 16>>& guesses, const qn_localize_params* params = nullptr,
                                                               qn_localize_stats* stats = nullptr) {
   detail::check_sizes(query, guesses);
-  qn_localize_params tmp;
+  const qn_localize_params p = detail::params_or(params, qn_localize_default_params);
   const size_t n = query.size();
   std::vector<qn_gicp_result> res(n + 1); std::vector<int> valid(n + 1, 0), status(n + 1, 0);
   std::vector<double> Tt(16 * (n + 1)), Tq(16 * (n + 1));
-  const int rc = qn_kf_map_localize_c2f(store, ctx, detail::params_or_default(params, &tmp), n ? query.data() : nullptr, n ? guesses[0].data() : nullptr, (uint32_t)n,
+  const int rc = qn_kf_map_localize_c2f(store, ctx, &p, n ? query.data() : nullptr, n ? guesses[0].data() : nullptr, (uint32_t)n,
                                         res.data(), Tt.data(), Tq.data(), valid.data(), status.data(), stats);
   if (rc != QN_OK) throw std::runtime_error(detail::why("qn_kf_map_localize_c2f", rc, store));
   std::vector<MapLocalization> out(n);

@@ -11,6 +11,7 @@
 #include <string>
 #include <vector>
 #include "qn_engine.h"
+#include "detail.hpp"
 
 namespace qn_map {
 
@@ -32,14 +33,13 @@ struct MapWithNormals {
 // list the map was built from; params NULL: the defaults (radius 0.6, 5 neighbours)
 inline MapWithNormals mapNormals(qn_kf_store* store, const qn_normal_params* params, const std::vector<double>& poses16) {
   if (poses16.size() % 16) throw std::invalid_argument("[qn_map] mapNormals: 16 doubles per entry");
-  qn_normal_params p;
-  if (params) p = *params; else qn_normal_default_params(&p);
+  qn_normal_params p = detail::params_or(params, qn_normal_default_params);
   const uint32_t nv = (uint32_t)(poses16.size() / 16);
   std::vector<double> views(3 * (size_t)nv);
   for (uint32_t k = 0; k < nv; k++) { views[3 * k] = poses16[16 * k + 3]; views[3 * k + 1] = poses16[16 * k + 7]; views[3 * k + 2] = poses16[16 * k + 11]; }
   const float* d_normals = nullptr; uint32_t n = 0;
   int rc = qn_kf_map_normals(store, &p, nv ? views.data() : nullptr, nv, &d_normals, &n);
-  if (rc != QN_OK) throw std::runtime_error(std::string("[qn_map] qn_kf_map_normals: ") + qn_status_str(rc) + " " + qn_kf_last_error(store));
+  detail::check(store, rc, "qn_kf_map_normals");
   MapWithNormals out;
   out.points.assign(n, PointXYZINormal{});
   out.neighbors.resize(n); out.view.resize(n);
@@ -47,7 +47,7 @@ inline MapWithNormals mapNormals(qn_kf_store* store, const qn_normal_params* par
   std::vector<float> nrm(4 * (size_t)n);
   rc = qn_kf_download_map_normals(store, nrm.data(), out.neighbors.data(), out.view.data());
   if (rc == QN_OK) rc = qn_kf_download_map(store, out.points.data(), sizeof(PointXYZINormal), offsetof(PointXYZINormal, intensity));
-  if (rc != QN_OK) throw std::runtime_error(std::string("[qn_map] mapNormals download: ") + qn_status_str(rc) + " " + qn_kf_last_error(store));
+  detail::check(store, rc, "mapNormals download");
   for (uint32_t i = 0; i < n; i++) {
     PointXYZINormal& q = out.points[i];
     q.pad0 = 1.0f;

@@ -13,6 +13,7 @@
 #include <pcl/point_cloud.h>
 #include <pcl/point_types.h>
 #include "qn_engine.h"
+#include "detail.hpp"
 
 namespace qn_map {
 
@@ -28,13 +29,12 @@ struct MapOccupancy {
 // params NULL: the defaults (voxel 0.3, ranges 0.5 .. 60, shell 1, min_hits 1, hit_weight 2).  The map slot is neither read nor touched.
 inline MapOccupancy mapOccupancy(qn_kf_store* store, const std::vector<int32_t>& ids, const std::vector<double>& poses16, const qn_occupancy_params* params = nullptr) {
   if (poses16.size() != 16 * ids.size()) throw std::invalid_argument("[qn_map] mapOccupancy: 16 doubles per listed keyframe");
-  qn_occupancy_params p;
-  if (params) p = *params; else qn_occupancy_default_params(&p);
+  qn_occupancy_params p = detail::params_or(params, qn_occupancy_default_params);
   MapOccupancy out;
   int rc = qn_kf_map_occupancy(store, ids.data(), poses16.data(), (uint32_t)ids.size(), &p, &out.stats);
-  if (rc != QN_OK) throw std::runtime_error(std::string("[qn_map] qn_kf_map_occupancy: ") + qn_status_str(rc) + " " + qn_kf_last_error(store));
+  detail::check(store, rc, "qn_kf_map_occupancy");
   rc = qn_kf_map_occupancy_grid(store, &out.grid, nullptr, nullptr, nullptr);
-  if (rc != QN_OK) throw std::runtime_error(std::string("[qn_map] qn_kf_map_occupancy_grid: ") + qn_status_str(rc) + " " + qn_kf_last_error(store));
+  detail::check(store, rc, "qn_kf_map_occupancy_grid");
   return out;
 }
 
@@ -44,14 +44,13 @@ inline MapOccupancy mapOccupancy(qn_kf_store* store, const std::vector<int32_t>&
 inline MapOccupancy updateOccupancy(qn_kf_store* store, const std::vector<int32_t>& ids, const std::vector<double>& poses16, const qn_occupancy_params* params = nullptr,
                                     qn_occupancy_update* update = nullptr) {
   if (poses16.size() != 16 * ids.size()) throw std::invalid_argument("[qn_map] updateOccupancy: 16 doubles per listed keyframe");
-  qn_occupancy_params p;
-  if (params) p = *params; else qn_occupancy_default_params(&p);
+  qn_occupancy_params p = detail::params_or(params, qn_occupancy_default_params);
   MapOccupancy out;
   qn_occupancy_update u;
   int rc = qn_kf_map_occupancy_update(store, ids.data(), poses16.data(), (uint32_t)ids.size(), &p, &out.stats, &u);
-  if (rc != QN_OK) throw std::runtime_error(std::string("[qn_map] qn_kf_map_occupancy_update: ") + qn_status_str(rc) + " " + qn_kf_last_error(store));
+  detail::check(store, rc, "qn_kf_map_occupancy_update");
   rc = qn_kf_map_occupancy_grid(store, &out.grid, nullptr, nullptr, nullptr);
-  if (rc != QN_OK) throw std::runtime_error(std::string("[qn_map] qn_kf_map_occupancy_grid: ") + qn_status_str(rc) + " " + qn_kf_last_error(store));
+  detail::check(store, rc, "qn_kf_map_occupancy_grid");
   if (update) *update = u;
   return out;
 }
@@ -62,14 +61,14 @@ template <typename PointT>
 inline uint32_t occupiedVoxels(qn_kf_store* store, pcl::PointCloud<PointT>& out, uint32_t class_mask = 1u << QN_OCC_OCCUPIED, std::vector<uint32_t>* misses = nullptr) {
   qn_occupancy_grid g;
   int rc = qn_kf_map_occupancy_grid(store, &g, nullptr, nullptr, nullptr);
-  if (rc != QN_OK) throw std::runtime_error(std::string("[qn_map] qn_kf_map_occupancy_grid: ") + qn_status_str(rc) + " " + qn_kf_last_error(store));
+  detail::check(store, rc, "qn_kf_map_occupancy_grid");
   uint32_t n = 0;
   rc = qn_kf_map_occupancy_list(store, class_mask, &n, nullptr, nullptr, nullptr);
-  if (rc != QN_OK) throw std::runtime_error(std::string("[qn_map] qn_kf_map_occupancy_list: ") + qn_status_str(rc) + " " + qn_kf_last_error(store));
+  detail::check(store, rc, "qn_kf_map_occupancy_list");
   std::vector<int32_t> ijk(3 * (size_t)n); std::vector<uint32_t> hits(n), miss(n);
   if (n) {
     rc = qn_kf_map_occupancy_list(store, class_mask, &n, ijk.data(), hits.data(), miss.data());
-    if (rc != QN_OK) throw std::runtime_error(std::string("[qn_map] qn_kf_map_occupancy_list: ") + qn_status_str(rc) + " " + qn_kf_last_error(store));
+    detail::check(store, rc, "qn_kf_map_occupancy_list");
   }
   out.clear(); out.reserve(n);
   for (uint32_t k = 0; k < n; k++) {
@@ -89,11 +88,11 @@ inline uint32_t occupiedVoxels(qn_kf_store* store, pcl::PointCloud<PointT>& out,
 inline std::vector<uint8_t> occupancySlice(qn_kf_store* store, int32_t iz_lo, int32_t iz_hi, qn_occupancy_grid* grid = nullptr) {
   qn_occupancy_grid g;
   int rc = qn_kf_map_occupancy_grid(store, &g, nullptr, nullptr, nullptr);
-  if (rc != QN_OK) throw std::runtime_error(std::string("[qn_map] qn_kf_map_occupancy_grid: ") + qn_status_str(rc) + " " + qn_kf_last_error(store));
+  detail::check(store, rc, "qn_kf_map_occupancy_grid");
   std::vector<uint8_t> occ((size_t)g.width * g.height);
   std::vector<uint8_t> pad(1);
   rc = qn_kf_map_occupancy_slice(store, iz_lo, iz_hi, occ.empty() ? pad.data() : occ.data());
-  if (rc != QN_OK) throw std::runtime_error(std::string("[qn_map] qn_kf_map_occupancy_slice: ") + qn_status_str(rc) + " " + qn_kf_last_error(store));
+  detail::check(store, rc, "qn_kf_map_occupancy_slice");
   if (grid) *grid = g;
   return occ;
 }

@@ -10,6 +10,7 @@
 #include <string>
 #include <vector>
 #include "qn_engine.h"
+#include "detail.hpp"
 
 namespace qn_map {
 
@@ -24,16 +25,15 @@ struct MapOutliers {
 
 // the classification of the store's map slot (qn_kf_map_outliers); the slot is not touched.  params NULL: the defaults (radius 1.0, std_mul 2.0, k 8)
 inline MapOutliers mapOutliers(qn_kf_store* store, const qn_outlier_params* params) {
-  qn_outlier_params p;
-  if (params) p = *params; else qn_outlier_default_params(&p);
+  qn_outlier_params p = detail::params_or(params, qn_outlier_default_params);
   MapOutliers out;
   int rc = qn_kf_map_outliers(store, &p, &out.stats);
-  if (rc != QN_OK) throw std::runtime_error(std::string("[qn_map] qn_kf_map_outliers: ") + qn_status_str(rc) + " " + qn_kf_last_error(store));
+  detail::check(store, rc, "qn_kf_map_outliers");
   const uint32_t n = out.stats.n;
   out.neighbors.resize(n); out.mean_q.resize(n); out.removed.resize(n);
   if (!n) return out;
   rc = qn_kf_map_outlier_points(store, out.neighbors.data(), out.mean_q.data(), out.removed.data());
-  if (rc != QN_OK) throw std::runtime_error(std::string("[qn_map] qn_kf_map_outlier_points: ") + qn_status_str(rc) + " " + qn_kf_last_error(store));
+  detail::check(store, rc, "qn_kf_map_outlier_points");
   return out;
 }
 
@@ -41,7 +41,7 @@ inline MapOutliers mapOutliers(qn_kf_store* store, const qn_outlier_params* para
 inline uint32_t removeMapOutliers(qn_kf_store* store, const float** d_xyzi = nullptr) {
   const float* d = nullptr; uint32_t n = 0;
   const int rc = qn_kf_map_remove_outliers(store, &d, &n);
-  if (rc != QN_OK) throw std::runtime_error(std::string("[qn_map] qn_kf_map_remove_outliers: ") + qn_status_str(rc) + " " + qn_kf_last_error(store));
+  detail::check(store, rc, "qn_kf_map_remove_outliers");
   if (d_xyzi) *d_xyzi = d;
   return n;
 }

@@ -13,6 +13,7 @@
 #include <string>
 #include <vector>
 #include "qn_engine.h"
+#include "detail.hpp"
 
 namespace qn_map {
 
@@ -45,14 +46,13 @@ struct RoutePath {
 // the free voxels, min_d2 4, every layer, 3-D).  The field stays resident until the next mapRoute, mapDistance or mapOccupancy.
 inline MapRoute mapRoute(qn_kf_store* store, const std::vector<double>& goals, const qn_route_params* params = nullptr) {
   if (goals.empty() || goals.size() % 3 != 0) throw std::invalid_argument("[qn_map] mapRoute: 3 doubles per goal, at least one goal");
-  qn_route_params p;
-  if (params) p = *params; else qn_route_default_params(&p);
+  qn_route_params p = detail::params_or(params, qn_route_default_params);
   if (p.iz_lo > p.iz_hi) throw std::invalid_argument("[qn_map] mapRoute: iz_lo <= iz_hi");
   MapRoute out;
   int rc = qn_kf_map_route(store, goals.data(), (uint32_t)(goals.size() / 3), &p, &out.stats);
-  if (rc != QN_OK) throw std::runtime_error(std::string("[qn_map] qn_kf_map_route: ") + qn_status_str(rc) + " " + qn_kf_last_error(store));
+  detail::check(store, rc, "qn_kf_map_route");
   rc = qn_kf_map_route_grid(store, &out.grid, &out.params, nullptr);
-  if (rc != QN_OK) throw std::runtime_error(std::string("[qn_map] qn_kf_map_route_grid: ") + qn_status_str(rc) + " " + qn_kf_last_error(store));
+  detail::check(store, rc, "qn_kf_map_route_grid");
   return out;
 }
 
@@ -62,11 +62,11 @@ inline std::vector<double> routeCostAt(qn_kf_store* store, const std::vector<dou
   if (xyz.empty() || xyz.size() % 3 != 0) throw std::invalid_argument("[qn_map] routeCostAt: 3 doubles per point, at least one point");
   qn_occupancy_grid g; qn_route_params p;
   int rc = qn_kf_map_route_grid(store, &g, &p, nullptr);
-  if (rc != QN_OK) throw std::runtime_error(std::string("[qn_map] qn_kf_map_route_grid: ") + qn_status_str(rc) + " " + qn_kf_last_error(store));
+  detail::check(store, rc, "qn_kf_map_route_grid");
   const uint32_t n = (uint32_t)(xyz.size() / 3);
   std::vector<uint32_t> c(n);
   rc = qn_kf_map_route_query(store, xyz.data(), n, c.data());
-  if (rc != QN_OK) throw std::runtime_error(std::string("[qn_map] qn_kf_map_route_query: ") + qn_status_str(rc) + " " + qn_kf_last_error(store));
+  detail::check(store, rc, "qn_kf_map_route_query");
   std::vector<double> out(n);
   for (uint32_t i = 0; i < n; i++) out[i] = c[i] >= QN_ROUTE_BLOCKED ? std::numeric_limits<double>::infinity() : (double)c[i] / 3.0 * g.voxel;
   if (costs) costs->swap(c);
@@ -82,7 +82,7 @@ inline std::vector<RoutePath> routePath(qn_kf_store* store, const std::vector<do
   std::vector<uint32_t> len(n);
   std::vector<int32_t> ijk(3 * (size_t)max_len * n);
   const int rc = qn_kf_map_route_path(store, starts.data(), n, max_len, len.data(), ijk.data());
-  if (rc != QN_OK) throw std::runtime_error(std::string("[qn_map] qn_kf_map_route_path: ") + qn_status_str(rc) + " " + qn_kf_last_error(store));
+  detail::check(store, rc, "qn_kf_map_route_path");
   std::vector<RoutePath> out(n);
   for (uint32_t i = 0; i < n; i++) {
     out[i].len = len[i];

@@ -13,6 +13,7 @@
 #include <string>
 #include <vector>
 #include "qn_engine.h"
+#include "detail.hpp"
 
 namespace qn_map {
 
@@ -55,8 +56,7 @@ inline std::vector<int32_t> sensorRays(double voxel, double max_range, uint32_t 
 // mapOccupancy (qn_kf_map_view_gain).  params NULL: the defaults (gain: the unknown voxels, stop: the occupied ones, no limit on the voxels passed through,
 // every layer).  The result stays resident until the next mapViewGain or mapOccupancy; mapDistance, mapRoute and mapFrontiers do not touch it.
 inline MapViewGain mapViewGain(qn_kf_store* store, const std::vector<double>& xyz, const std::vector<int32_t>& rays, const qn_view_params* params = nullptr) {
-  qn_view_params p;
-  if (params) p = *params; else qn_view_default_params(&p);
+  qn_view_params p = detail::params_or(params, qn_view_default_params);
   if (xyz.empty() || xyz.size() % 3 != 0 || xyz.size() / 3 > (1u << 16)) throw std::invalid_argument("[qn_map] mapViewGain: three doubles per viewpoint, 1 .. 2^16 viewpoints");
   if (rays.empty() || rays.size() % 3 != 0 || rays.size() / 3 > (1u << 20)) throw std::invalid_argument("[qn_map] mapViewGain: three offsets per ray, 1 .. 2^20 rays");
   if (p.iz_lo > p.iz_hi) throw std::invalid_argument("[qn_map] mapViewGain: iz_lo <= iz_hi");
@@ -66,9 +66,9 @@ inline MapViewGain mapViewGain(qn_kf_store* store, const std::vector<double>& xy
   MapViewGain out;
   out.views.resize(xyz.size() / 3);
   int rc = qn_kf_map_view_gain(store, xyz.data(), (uint32_t)(xyz.size() / 3), rays.data(), (uint32_t)(rays.size() / 3), &p, out.views.data(), &out.stats);
-  if (rc != QN_OK) throw std::runtime_error(std::string("[qn_map] qn_kf_map_view_gain: ") + qn_status_str(rc) + " " + qn_kf_last_error(store));
+  detail::check(store, rc, "qn_kf_map_view_gain");
   rc = qn_kf_map_view_grid(store, &out.grid, &out.params, nullptr);
-  if (rc != QN_OK) throw std::runtime_error(std::string("[qn_map] qn_kf_map_view_grid: ") + qn_status_str(rc) + " " + qn_kf_last_error(store));
+  detail::check(store, rc, "qn_kf_map_view_grid");
   return out;
 }
 
@@ -76,11 +76,11 @@ inline MapViewGain mapViewGain(qn_kf_store* store, const std::vector<double>& xy
 inline std::vector<uint32_t> viewCover(qn_kf_store* store) {
   qn_occupancy_grid g; qn_view_params p;
   int rc = qn_kf_map_view_grid(store, &g, &p, nullptr);
-  if (rc != QN_OK) throw std::runtime_error(std::string("[qn_map] qn_kf_map_view_grid: ") + qn_status_str(rc) + " " + qn_kf_last_error(store));
+  detail::check(store, rc, "qn_kf_map_view_grid");
   std::vector<uint32_t> out((size_t)g.width * g.height * g.depth);
   if (out.empty()) return out;
   rc = qn_kf_map_view_grid(store, &g, &p, out.data());
-  if (rc != QN_OK) throw std::runtime_error(std::string("[qn_map] qn_kf_map_view_grid: ") + qn_status_str(rc) + " " + qn_kf_last_error(store));
+  detail::check(store, rc, "qn_kf_map_view_grid");
   return out;
 }
 

@@ -13,6 +13,7 @@
 #include <string>
 #include <vector>
 #include "qn_engine.h"
+#include "detail.hpp"
 
 namespace qn_map {
 
@@ -35,7 +36,7 @@ inline ScCandidates scanContextCandidates(qn_kf_store* store, const std::vector<
   std::vector<double> d((size_t)top_k);
   uint32_t n = 0;
   if (rc == QN_OK) rc = qn_kf_sc_query(store, &q, 1, stamps.data(), (uint32_t)stamps.size(), tdiff, (uint32_t)top_k, ids.data(), d.data(), shift.data(), &n);
-  if (rc != QN_OK) throw std::runtime_error(std::string("[qn_map] qn_kf_sc_query: ") + qn_status_str(rc) + " " + qn_kf_last_error(store));
+  detail::check(store, rc, "qn_kf_sc_query");
   ScCandidates out;
   const double pi = 3.14159265358979323846;
   for (uint32_t r = 0; r < n; r++) {
@@ -71,7 +72,7 @@ inline std::vector<ScVerified> verifyScanContextCandidates(qn_kf_store* store, q
   std::vector<int> valid(K), status(K);
   const int rc = qn_kf_verify_loop_candidates(store, ctx, query, ids.data(), c.yaw.data(), (uint32_t)K, poses16.data(), (uint32_t)(poses16.size() / 16),
                                               (uint32_t)submap_range, leaf, score_thr, r.data(), valid.data(), status.data());
-  if (rc != QN_OK) throw std::runtime_error(std::string("[qn_map] qn_kf_verify_loop_candidates: ") + qn_status_str(rc) + " " + qn_kf_last_error(store));
+  detail::check(store, rc, "qn_kf_verify_loop_candidates");
   for (size_t k = 0; k < K; k++) {
     ScVerified v{c.idx[k], valid[k] != 0, r[k].fitness, {}, status[k]};
     for (int i = 0; i < 16; i++) v.T[i] = (double)r[k].T[i];
@@ -108,7 +109,7 @@ inline std::vector<ScVerifiedC2f> verifyScanContextCandidatesCoarseToFine(qn_kf_
     rc = qn_kf_quatro_describe(store, ctx, all.data(), (uint32_t)all.size(), leaf, st.data());
     if (rc == QN_OK) rc = qn_kf_verify_loop_candidates_c2f(store, ctx, query, ids.data(), (uint32_t)K, score_thr, r.data(), Tt.data(), Tq.data(), valid.data(), status.data());
   }
-  if (rc != QN_OK) throw std::runtime_error(std::string("[qn_map] qn_kf_verify_loop_candidates_c2f: ") + qn_status_str(rc) + " " + qn_kf_last_error(store));
+  detail::check(store, rc, "qn_kf_verify_loop_candidates_c2f");
   for (size_t k = 0; k < K; k++) {
     ScVerifiedC2f v{c.idx[k], valid[k] != 0, r[k].fitness, {}, {}, status[k]};
     for (int i = 0; i < 16; i++) { v.T[i] = Tt[16 * k + i]; v.T_quatro[i] = Tq[16 * k + i]; }
@@ -139,7 +140,7 @@ inline ScPairs scanContextCandidatesMany(qn_kf_store* store, const std::vector<d
   std::vector<double> d(nq * k);
   std::vector<uint32_t> n(nq);
   if (rc == QN_OK) rc = qn_kf_sc_query(store, q.data(), (uint32_t)nq, stamps.data(), (uint32_t)stamps.size(), tdiff, (uint32_t)top_k, ids.data(), d.data(), shift.data(), n.data());
-  if (rc != QN_OK) throw std::runtime_error(std::string("[qn_map] qn_kf_sc_query: ") + qn_status_str(rc) + " " + qn_kf_last_error(store));
+  detail::check(store, rc, "qn_kf_sc_query");
   const double pi = 3.14159265358979323846;
   for (size_t i = 0; i < nq; i++)
     for (uint32_t r = 0; r < n[i]; r++) {
@@ -177,7 +178,7 @@ inline std::vector<ScVerifiedPair> verifyLoopPairs(qn_kf_store* store, qn_ctx* c
   std::vector<int> valid(K), status(K);
   const int rc = qn_kf_verify_loop_pairs(store, ctx, q.data(), ids.data(), c.yaw.data(), (uint32_t)K, poses16.data(), (uint32_t)(poses16.size() / 16),
                                          (uint32_t)submap_range, leaf, score_thr, r.data(), valid.data(), status.data());
-  if (rc != QN_OK) throw std::runtime_error(std::string("[qn_map] qn_kf_verify_loop_pairs: ") + qn_status_str(rc) + " " + qn_kf_last_error(store));
+  detail::check(store, rc, "qn_kf_verify_loop_pairs");
   for (size_t k = 0; k < K; k++) {
     ScVerifiedPair v{c.query[k], c.cand[k], valid[k] != 0, r[k].fitness, {}, {}, status[k]};
     for (int i = 0; i < 16; i++) { v.T[i] = (double)r[k].T[i]; v.T_quatro[i] = i % 5 == 0 ? 1.0 : 0.0; }
@@ -204,7 +205,7 @@ inline std::vector<ScVerifiedPair> verifyLoopPairsCoarseToFine(qn_kf_store* stor
     rc = qn_kf_quatro_describe(store, ctx, all.data(), (uint32_t)all.size(), leaf, st.data());
     if (rc == QN_OK) rc = qn_kf_verify_loop_pairs_c2f(store, ctx, q.data(), ids.data(), (uint32_t)K, score_thr, r.data(), Tt.data(), Tq.data(), valid.data(), status.data());
   }
-  if (rc != QN_OK) throw std::runtime_error(std::string("[qn_map] qn_kf_verify_loop_pairs_c2f: ") + qn_status_str(rc) + " " + qn_kf_last_error(store));
+  detail::check(store, rc, "qn_kf_verify_loop_pairs_c2f");
   for (size_t k = 0; k < K; k++) {
     ScVerifiedPair v{c.query[k], c.cand[k], valid[k] != 0, r[k].fitness, {}, {}, status[k]};
     for (int i = 0; i < 16; i++) { v.T[i] = Tt[16 * k + i]; v.T_quatro[i] = Tq[16 * k + i]; }
@@ -225,7 +226,7 @@ inline std::vector<int> describeLocalSubmaps(qn_kf_store* store, qn_ctx* ctx, co
   const std::vector<int32_t> id32(ids.begin(), ids.end());
   const int rc = qn_kf_submap_describe(store, ctx, id32.data(), (uint32_t)id32.size(), poses16.data(), (uint32_t)(poses16.size() / 16), (uint32_t)submap_range, leaf,
                                        with_features ? 1 : 0, st.data());
-  if (rc != QN_OK) throw std::runtime_error(std::string("[qn_map] qn_kf_submap_describe: ") + qn_status_str(rc) + " " + qn_kf_last_error(store));
+  detail::check(store, rc, "qn_kf_submap_describe");
   return st;
 }
 
@@ -240,7 +241,7 @@ inline std::vector<ScVerifiedPair> verifyLoopPairsSubmap(qn_kf_store* store, qn_
   std::vector<qn_gicp_result> r(K);
   std::vector<int> valid(K), status(K);
   const int rc = qn_kf_verify_loop_pairs_submap(store, ctx, q.data(), ids.data(), c.yaw.data(), (uint32_t)K, score_thr, r.data(), valid.data(), status.data());
-  if (rc != QN_OK) throw std::runtime_error(std::string("[qn_map] qn_kf_verify_loop_pairs_submap: ") + qn_status_str(rc) + " " + qn_kf_last_error(store));
+  detail::check(store, rc, "qn_kf_verify_loop_pairs_submap");
   for (size_t k = 0; k < K; k++) {
     ScVerifiedPair v{c.query[k], c.cand[k], valid[k] != 0, r[k].fitness, {}, {}, status[k]};
     for (int i = 0; i < 16; i++) { v.T[i] = (double)r[k].T[i]; v.T_quatro[i] = i % 5 == 0 ? 1.0 : 0.0; }
@@ -260,7 +261,7 @@ inline std::vector<ScVerifiedPair> verifyLoopPairsSubmapCoarseToFine(qn_kf_store
   std::vector<double> Tt(16 * K), Tq(16 * K);
   std::vector<int> valid(K), status(K);
   const int rc = qn_kf_verify_loop_pairs_submap_c2f(store, ctx, q.data(), ids.data(), (uint32_t)K, score_thr, r.data(), Tt.data(), Tq.data(), valid.data(), status.data());
-  if (rc != QN_OK) throw std::runtime_error(std::string("[qn_map] qn_kf_verify_loop_pairs_submap_c2f: ") + qn_status_str(rc) + " " + qn_kf_last_error(store));
+  detail::check(store, rc, "qn_kf_verify_loop_pairs_submap_c2f");
   for (size_t k = 0; k < K; k++) {
     ScVerifiedPair v{c.query[k], c.cand[k], valid[k] != 0, r[k].fitness, {}, {}, status[k]};
     for (int i = 0; i < 16; i++) { v.T[i] = Tt[16 * k + i]; v.T_quatro[i] = Tq[16 * k + i]; }
@@ -281,7 +282,7 @@ inline std::vector<VerifiedOverlap> verifyOverlap(qn_kf_store* store, size_t n_p
   std::vector<qn_overlap> rec(n_pairs);
   std::vector<int> status(n_pairs);
   const int rc = qn_kf_verify_overlap(store, nullptr, (uint32_t)n_pairs, radius, rec.data(), status.data());
-  if (rc != QN_OK) throw std::runtime_error(std::string("[qn_map] qn_kf_verify_overlap: ") + qn_status_str(rc) + " " + qn_kf_last_error(store));
+  detail::check(store, rc, "qn_kf_verify_overlap");
   for (size_t k = 0; k < n_pairs; k++) out.push_back(VerifiedOverlap{rec[k], status[k]});
   return out;
 }

@@ -13,6 +13,7 @@
 #include <utility>
 #include <vector>
 #include "qn_engine.h"
+#include "detail.hpp"
 
 namespace qn_map {
 
@@ -50,13 +51,12 @@ inline StaticClassified classifyStatic(qn_kf_store* store, const std::vector<int
   if (poses16.size() != 16 * ids.size() || w.off.size() != ids.size() + 1) throw std::invalid_argument("[qn_map] classifyStatic: 16 doubles and one witness range per entry");
   StaticClassified out;
   if (ids.empty()) return out;
-  qn_static_params p;
-  if (params) p = *params; else qn_static_default_params(&p);
+  qn_static_params p = detail::params_or(params, qn_static_default_params);
   std::vector<int32_t> id32(ids.begin(), ids.end());
   out.removed.resize(ids.size()); out.status.resize(ids.size());
   const int rc = qn_kf_static_classify(store, id32.data(), poses16.data(), (uint32_t)id32.size(), w.off.data(), w.wit.empty() ? nullptr : w.wit.data(), &p,
                                        out.removed.data(), out.status.data());
-  if (rc != QN_OK) throw std::runtime_error(std::string("[qn_map] qn_kf_static_classify: ") + qn_status_str(rc) + " " + qn_kf_last_error(store));
+  detail::check(store, rc, "qn_kf_static_classify");
   return out;
 }
 
@@ -65,7 +65,7 @@ inline uint32_t buildStaticMap(qn_kf_store* store, double leaf) {
   const float* d_map = nullptr; uint32_t n = 0;
   const int rc = qn_kf_build_map_static(store, leaf, &d_map, &n);
   if (rc == QN_ERR_EMPTY_CLOUD) return 0;
-  if (rc != QN_OK) throw std::runtime_error(std::string("[qn_map] qn_kf_build_map_static: ") + qn_status_str(rc) + " " + qn_kf_last_error(store));
+  detail::check(store, rc, "qn_kf_build_map_static");
   return n;
 }
 

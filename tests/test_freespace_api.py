@@ -9,6 +9,7 @@ import sys
 import numpy as np
 import pytest
 from qn_amd import engine, freespace as fs, synth
+from shim_build import build_shim
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMBOLS = ["qn_kf_range_set_params", "qn_kf_range_get_params", "qn_kf_range_describe", "qn_kf_range_get", "qn_kf_freespace_batch", "qn_kf_freespace_points"]
@@ -100,11 +101,6 @@ def test_the_three_kernels_have_no_scratch():
 
 
 def test_helper_compiles_against_the_standins_and_refuses_a_null_store(tmp_path):
-    from qn_amd import build
-    build.build()
-    out = str(tmp_path / "shim_freespace")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-I" + os.path.join(ROOT, "tests", "standins"), "-I" + os.path.join(ROOT, "fast-lio-sam-qn_amd", "shim"),
-                           "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "shim_freespace.cpp"),
-                           "-L" + os.path.join(ROOT, "fast-lio-sam-qn_amd"), "-lqn_engine", "-Wl,-rpath," + os.path.join(ROOT, "fast-lio-sam-qn_amd"), "-o", out])
+    out = build_shim("shim_freespace.cpp", tmp_path)
     txt = subprocess.check_output([out], text=True)
     assert "refused" in txt and "qn_kf_freespace_batch" in txt and "fraction 0.25" in txt

@@ -21,6 +21,7 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import test_gpu_sc_verify as scv                                                   # noqa: E402  (the street scene and its drifted poses)
+from shim_build import build_shim
 
 TOL_T, TOL_R = 0.05, math.radians(0.2)
 LEAF, RANGE, MAX_CORR, CAP, GCAP = 0.3, 5, 18.0, 60000, 200000
@@ -282,12 +283,8 @@ def test_a_single_query_call_leaves_no_record_of_its_own(street):
 
 
 def test_cpp_helpers_return_the_python_records(tmp_path):
-    from qn_amd import build, engine
-    build.build()
-    exe = str(tmp_path / "shim_loop_pairs")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-I" + os.path.join(ROOT, "tests", "standins"), "-I" + os.path.join(ROOT, "fast-lio-sam-qn_amd", "shim"),
-                           "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "shim_loop_pairs.cpp"),
-                           "-L" + os.path.join(ROOT, "fast-lio-sam-qn_amd"), "-lqn_engine", "-Wl,-rpath," + os.path.join(ROOT, "fast-lio-sam-qn_amd"), "-o", exe])
+    from qn_amd import engine
+    exe = build_shim("shim_loop_pairs.cpp", tmp_path)
     prims, poses = scv._street()
     sen = synth.SpinningLidar(n_beams=32, n_cols=720)
     clouds = [synth.lidar_scan(prims, sen, P, 100 + k)[:, :3] for k, P in enumerate(poses)]

@@ -314,9 +314,9 @@ def _fnv(chunks):
 
 
 def test_cpp_helper_gives_the_python_result(store, scans, tmp_path):
-    from test_map_clusters_api import build_shim
+    from shim_build import build_shim
     from qn_amd import engine
-    exe = build_shim(str(tmp_path / "shim_map_clusters"))
+    exe = build_shim("shim_map_clusters.cpp", tmp_path)
     ids, poses = scans[:2], POSES[:2]
     with open(tmp_path / "kf.bin", "wb") as f:
         for i in ids:

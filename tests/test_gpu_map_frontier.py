@@ -7,6 +7,7 @@ import pytest
 import frontier_cases as fc
 from test_map_route_twin import POSES, SEN
 from qn_amd import mapdistance as md, mapfrontier as mf, mapoccupancy as mo, maproute as mr, synth
+from shim_build import build_shim
 
 pytestmark = pytest.mark.gpu
 F = np.float32
@@ -230,10 +231,7 @@ def test_cpp_helper_gives_the_python_result(store, tmp_path):
     import subprocess
     from qn_amd import engine
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    exe = str(tmp_path / "shim_map_frontier")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-I" + os.path.join(root, "tests", "standins"), "-I" + os.path.join(root, "fast-lio-sam-qn_amd", "shim"),
-                           "-I" + os.path.join(root, "include"), os.path.join(root, "tests", "shim_map_frontier.cpp"),
-                           "-L" + os.path.join(root, "fast-lio-sam-qn_amd"), "-lqn_engine", "-Wl,-rpath," + os.path.join(root, "fast-lio-sam-qn_amd"), "-o", exe])
+    exe = build_shim("shim_map_frontier.cpp", tmp_path)
     prims = synth.Scene(np.random.default_rng(7), 120.0).primitives()
     ids = [int(i) for i in store.add_lidar_scans(prims, SEN, POSES[:2], [11, 12])]
     with open(tmp_path / "kf.bin", "wb") as f:

@@ -15,6 +15,7 @@ import sys
 import numpy as np
 import pytest
 from qn_amd import scancontext as sc, synth
+from shim_build import build_shim
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -181,12 +182,8 @@ def test_an_empty_candidate_submap_sits_beside_valid_ones():
 
 
 def test_cpp_helper_returns_the_python_records(tmp_path):
-    from qn_amd import build, engine
-    build.build()
-    exe = str(tmp_path / "shim_sc_verify")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-I" + os.path.join(ROOT, "tests", "standins"), "-I" + os.path.join(ROOT, "fast-lio-sam-qn_amd", "shim"),
-                           "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "shim_sc_verify.cpp"),
-                           "-L" + os.path.join(ROOT, "fast-lio-sam-qn_amd"), "-lqn_engine", "-Wl,-rpath," + os.path.join(ROOT, "fast-lio-sam-qn_amd"), "-o", exe])
+    from qn_amd import engine
+    exe = build_shim("shim_sc_verify.cpp", tmp_path)
     prims, poses = _street()
     sen = synth.SpinningLidar(n_beams=32, n_cols=720)
     clouds = [synth.lidar_scan(prims, sen, P, 100 + k)[:, :3] for k, P in enumerate(poses)]

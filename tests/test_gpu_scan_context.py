@@ -10,6 +10,7 @@ import sys
 import numpy as np
 import pytest
 from qn_amd import scancontext as sc, synth
+from shim_build import build_shim
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -260,12 +261,7 @@ def test_revisits_are_found_where_the_radius_search_finds_nothing():
 
 
 def test_cpp_helper_returns_the_python_candidates(tmp_path):
-    from qn_amd import build
-    build.build()
-    exe = str(tmp_path / "shim_scan_context")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-I" + os.path.join(ROOT, "tests", "standins"), "-I" + os.path.join(ROOT, "fast-lio-sam-qn_amd", "shim"),
-                           "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "shim_scan_context.cpp"),
-                           "-L" + os.path.join(ROOT, "fast-lio-sam-qn_amd"), "-lqn_engine", "-Wl,-rpath," + os.path.join(ROOT, "fast-lio-sam-qn_amd"), "-o", exe])
+    exe = build_shim("shim_scan_context.cpp", tmp_path)
     prims, poses = _street()
     sen = synth.SpinningLidar(n_beams=32, n_cols=720)
     clouds = [synth.lidar_scan(prims, sen, P, 100 + k)[:, :3] for k, P in enumerate(poses)]

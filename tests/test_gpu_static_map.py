@@ -11,6 +11,7 @@ import sys
 import numpy as np
 import pytest
 from qn_amd import freespace as fs, staticmap as sm, synth
+from shim_build import build_shim
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -255,12 +256,8 @@ def test_not_ready_before_a_classify(world):
 
 
 def test_cpp_helper_gives_the_python_result(world, tmp_path):
-    from qn_amd import build, engine
-    build.build()
-    exe = str(tmp_path / "shim_static_map")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-I" + os.path.join(ROOT, "tests", "standins"), "-I" + os.path.join(ROOT, "fast-lio-sam-qn_amd", "shim"),
-                           "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "shim_static_map.cpp"),
-                           "-L" + os.path.join(ROOT, "fast-lio-sam-qn_amd"), "-lqn_engine", "-Wl,-rpath," + os.path.join(ROOT, "fast-lio-sam-qn_amd"), "-o", exe])
+    from qn_amd import engine
+    exe = build_shim("shim_static_map.cpp", tmp_path)
     ids, poses = world["ids"][:6], world["poses"][:6]
     with open(tmp_path / "kf.bin", "wb") as f:
         for i in ids:

@@ -29,6 +29,7 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import test_gpu_sc_verify as scv                                                   # noqa: E402  (the street scene)
+from shim_build import build_shim
 
 LEAF, RANGE, MAX_CORR, CAP, THR = 0.3, 2, 18.0, 60000, 1.5
 N = 14                                                                             # keyframes of the street scene
@@ -448,12 +449,8 @@ def test_redescribe_and_release_drop_the_record_and_spare_the_scan_entries(stree
 
 # ------------------------------------------------------------------ 6. the layers above
 def test_cpp_helpers_return_the_python_records(tmp_path):
-    from qn_amd import build, engine
-    build.build()
-    exe = str(tmp_path / "shim_submap_verify")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-I" + os.path.join(ROOT, "tests", "standins"), "-I" + os.path.join(ROOT, "fast-lio-sam-qn_amd", "shim"),
-                           "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "shim_submap_verify.cpp"),
-                           "-L" + os.path.join(ROOT, "fast-lio-sam-qn_amd"), "-lqn_engine", "-Wl,-rpath," + os.path.join(ROOT, "fast-lio-sam-qn_amd"), "-o", exe])
+    from qn_amd import engine
+    exe = build_shim("shim_submap_verify.cpp", tmp_path)
     prims, poses = scv._street()
     sen = synth.SpinningLidar(n_beams=32, n_cols=720)
     clouds = [synth.lidar_scan(prims, sen, P, 100 + k)[:, :3] for k, P in enumerate(poses)]

@@ -5,6 +5,7 @@ import ctypes
 import itertools
 import os
 import subprocess
+from shim_build import build_shim
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LOOP_BIN = os.path.join(ROOT, "tests", "shim_loop_submaps")
@@ -93,19 +94,9 @@ def test_newest_keyframe_never_enters_a_submap_but_single_keyframe_cases_keep_it
     assert engine.loop_submap_ids(0, 0, 10, False, True, 1) == ([], [])
 
 
-def _compile(src_cpp, out, link=True):
-    cmd = ["g++", "-std=c++17", "-O2", "-Wall", "-I" + os.path.join(ROOT, "tests", "standins"), "-I" + os.path.join(ROOT, "fast-lio-sam-qn_amd", "shim"),
-           "-I" + os.path.join(ROOT, "include"), src_cpp]
-    if link:
-        cmd += ["-L" + os.path.join(ROOT, "fast-lio-sam-qn_amd"), "-lqn_engine", "-Wl,-rpath," + os.path.join(ROOT, "fast-lio-sam-qn_amd")]
-    subprocess.check_call(cmd + ["-o", out])
-    return out
-
-
 def build_loop_program():
-    from qn_amd import build
-    build.build()
-    return _compile(os.path.join(ROOT, "tests", "shim_loop_submaps.cpp"), LOOP_BIN)
+    assert build_shim("shim_loop_submaps.cpp", os.path.dirname(LOOP_BIN)) == LOOP_BIN
+    return LOOP_BIN
 
 
 def test_loop_submaps_helper_compiles_and_links():
@@ -119,7 +110,7 @@ def test_cpp_loop_submap_ids_restates_set_src_and_dst_cloud(tmp_path):
                     "int main(int c, char** v) { int a[6]; for (int k = 0; k < 6; k++) a[k] = std::atoi(v[k + 1]);\n"
                     "  const qn_map::SubmapIds r = qn_map::loopSubmapIds(a[0], a[1], a[2], a[3] != 0, a[4] != 0, a[5]);\n"
                     "  for (int i : r.src) std::printf(\"%d \", i); std::printf(\"|\"); for (int i : r.dst) std::printf(\" %d\", i); std::printf(\"\\n\"); return 0; }\n")
-    exe = _compile(str(prog), str(tmp_path / "ids"), link=False)
+    exe = build_shim(str(prog), tmp_path, link=False)
     cases = list(_cases())[:12]
     for (n, src, dst, r), (quatro, submap) in itertools.product(cases, FLAGS):
         out = subprocess.check_output([exe, str(src), str(dst), str(r), str(int(quatro)), str(int(submap)), str(n)], text=True)

@@ -3,8 +3,8 @@ pcl::VoxelGrid with intensity that the GPU tests compare against (checked here a
 (shim/qn_map/corrected_map.hpp) compiling against the stand-in pcl/Eigen headers.  No GPU needed."""
 import ctypes
 import os
-import subprocess
 import numpy as np
+from shim_build import build_shim
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MAP_BIN = os.path.join(ROOT, "tests", "shim_corrected_map")
@@ -78,12 +78,7 @@ def transform_xyzi(p4, T):
 
 
 def build_map_program():
-    from qn_amd import build
-    build.build()
-    cmd = ["g++", "-std=c++17", "-O2", "-I" + os.path.join(ROOT, "tests", "standins"), "-I" + os.path.join(ROOT, "fast-lio-sam-qn_amd", "shim"),
-           "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "shim_corrected_map.cpp"), "-L" + os.path.join(ROOT, "fast-lio-sam-qn_amd"),
-           "-lqn_engine", "-Wl,-rpath," + os.path.join(ROOT, "fast-lio-sam-qn_amd"), "-o", MAP_BIN]
-    subprocess.check_call(cmd)
+    assert build_shim("shim_corrected_map.cpp", os.path.dirname(MAP_BIN)) == MAP_BIN
     return MAP_BIN
 
 

@@ -2,8 +2,8 @@
 qn_kf_verify_loop_candidates_c2f): the C-ABI surface, the Python wrappers, and the C++ helper compiling against the stand-ins.  No GPU needed."""
 import ctypes
 import os
-import subprocess
 from qn_amd import engine
+from shim_build import build_shim
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMBOLS = ["qn_kf_quatro_describe", "qn_kf_quatro_cloud", "qn_kf_quatro_features", "qn_kf_verify_loop_candidates_c2f"]
@@ -33,10 +33,5 @@ def test_header_states_the_contract():
 
 
 def test_helper_compiles_against_the_standins(tmp_path):
-    from qn_amd import build
-    build.build()
-    out = str(tmp_path / "shim_kf_quatro")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-I" + os.path.join(ROOT, "tests", "standins"), "-I" + os.path.join(ROOT, "fast-lio-sam-qn_amd", "shim"),
-                           "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "shim_kf_quatro.cpp"),
-                           "-L" + os.path.join(ROOT, "fast-lio-sam-qn_amd"), "-lqn_engine", "-Wl,-rpath," + os.path.join(ROOT, "fast-lio-sam-qn_amd"), "-o", out])
+    out = build_shim("shim_kf_quatro.cpp", tmp_path)
     assert os.path.exists(out)

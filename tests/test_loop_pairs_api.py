@@ -4,10 +4,10 @@ No GPU needed."""
 import ctypes
 import os
 import re
-import subprocess
 import sys
 import numpy as np
 from qn_amd import engine
+from shim_build import build_shim
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMBOLS = ["qn_kf_verify_loop_pairs", "qn_kf_verify_loop_pairs_c2f", "qn_kf_verify_cloud"]
@@ -49,12 +49,7 @@ def test_python_wrappers_exist():
 
 
 def test_helpers_compile_against_the_standins(tmp_path):
-    from qn_amd import build
-    build.build()
-    out = str(tmp_path / "shim_loop_pairs")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-I" + os.path.join(ROOT, "tests", "standins"), "-I" + os.path.join(ROOT, "fast-lio-sam-qn_amd", "shim"),
-                           "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "shim_loop_pairs.cpp"),
-                           "-L" + os.path.join(ROOT, "fast-lio-sam-qn_amd"), "-lqn_engine", "-Wl,-rpath," + os.path.join(ROOT, "fast-lio-sam-qn_amd"), "-o", out])
+    out = build_shim("shim_loop_pairs.cpp", tmp_path)
     assert os.path.exists(out)
 
 

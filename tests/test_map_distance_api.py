@@ -8,6 +8,7 @@ import subprocess
 import sys
 import numpy as np
 from qn_amd import engine, mapdistance as md
+from shim_build import build_shim
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "fast-lio-sam-qn_amd", "csrc")
@@ -126,12 +127,7 @@ def test_no_floating_point_outside_the_query():
 
 
 def test_shim_program_compiles_and_prints_its_refusals(tmp_path):
-    from qn_amd import build
-    build.build()
-    exe = str(tmp_path / "shim_map_distance")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-I" + os.path.join(ROOT, "tests", "standins"), "-I" + os.path.join(ROOT, "fast-lio-sam-qn_amd", "shim"),
-                           "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "shim_map_distance.cpp"),
-                           "-L" + os.path.join(ROOT, "fast-lio-sam-qn_amd"), "-lqn_engine", "-Wl,-rpath," + os.path.join(ROOT, "fast-lio-sam-qn_amd"), "-o", exe])
+    exe = build_shim("shim_map_distance.cpp", tmp_path)
     txt = subprocess.check_output([exe], text=True)
     assert txt.count("refused") == 5 and "mapDistance: max_dist of 1 .. 255 voxels" in txt and "distanceAt: 3 doubles per point" in txt
     assert all(s in txt for s in ("qn_kf_map_distance:", "qn_kf_map_distance_grid:")) and "params 16 bytes, stats 32 bytes" in txt

@@ -9,6 +9,7 @@ import subprocess
 import sys
 import numpy as np
 from qn_amd import engine, mapfrontier as mf
+from shim_build import build_shim
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "fast-lio-sam-qn_amd", "csrc")
@@ -135,12 +136,7 @@ def test_the_kernels_have_no_scratch_and_no_spills():
 
 
 def test_shim_program_compiles_and_prints_its_refusals(tmp_path):
-    from qn_amd import build
-    build.build()
-    exe = str(tmp_path / "shim_map_frontier")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-I" + os.path.join(ROOT, "tests", "standins"), "-I" + os.path.join(ROOT, "fast-lio-sam-qn_amd", "shim"),
-                           "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "shim_map_frontier.cpp"),
-                           "-L" + os.path.join(ROOT, "fast-lio-sam-qn_amd"), "-lqn_engine", "-Wl,-rpath," + os.path.join(ROOT, "fast-lio-sam-qn_amd"), "-o", exe])
+    exe = build_shim("shim_map_frontier.cpp", tmp_path)
     txt = subprocess.check_output([exe], text=True)
     assert txt.count("refused") == 7 and "mapFrontiers: iz_lo <= iz_hi" in txt and "mapFrontiers: min_size of at least 1" in txt and "share a class" in txt
     assert all(s in txt for s in ("qn_kf_map_frontiers:", "qn_kf_map_frontier_regions:", "qn_kf_map_frontier_list:")) and "params 32 bytes, stats 48 bytes, info 64 bytes" in txt

@@ -9,6 +9,7 @@ import subprocess
 import sys
 import numpy as np
 from qn_amd import engine, maplocalize as ml
+from shim_build import build_shim
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMBOLS = ["qn_localize_default_params", "qn_kf_map_crop", "qn_kf_map_crop_get", "qn_kf_map_localize", "qn_kf_map_localize_c2f"]
@@ -103,16 +104,7 @@ def test_the_crop_kernels_have_no_scratch():
         assert all(int(l.split()[0]) == 0 and " spill   0 " in l for l in rows), rows
 
 
-def build_shim(out):
-    from qn_amd import build
-    build.build()
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-I" + os.path.join(ROOT, "tests", "standins"), "-I" + os.path.join(ROOT, "fast-lio-sam-qn_amd", "shim"),
-                           "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "shim_map_localize.cpp"),
-                           "-L" + os.path.join(ROOT, "fast-lio-sam-qn_amd"), "-lqn_engine", "-Wl,-rpath," + os.path.join(ROOT, "fast-lio-sam-qn_amd"), "-o", out])
-    return out
-
-
 def test_helper_compiles_against_the_standins_and_refuses_a_null_store(tmp_path):
-    txt = subprocess.check_output([build_shim(str(tmp_path / "shim_map_localize"))], text=True)
+    txt = subprocess.check_output([build_shim("shim_map_localize.cpp", tmp_path)], text=True)
     assert txt.count("refused") == 3 and "qn_kf_map_crop" in txt and "qn_kf_map_localize" in txt and "qn_kf_map_localize_c2f" in txt
     assert "params 32 bytes, stats 40 bytes" in txt

@@ -5,6 +5,7 @@ import os
 import subprocess
 import numpy as np
 from qn_amd import engine, mapnormals as mn
+from shim_build import build_shim
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMBOLS = ["qn_normal_default_params", "qn_kf_map_normals", "qn_kf_download_map_normals", "qn_kf_map_moments"]
@@ -54,15 +55,6 @@ def test_python_wrappers_exist():
         assert callable(getattr(engine.KeyframeStore, f))
 
 
-def build_shim(out):
-    from qn_amd import build
-    build.build()
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-I" + os.path.join(ROOT, "tests", "standins"), "-I" + os.path.join(ROOT, "fast-lio-sam-qn_amd", "shim"),
-                           "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "shim_map_normals.cpp"),
-                           "-L" + os.path.join(ROOT, "fast-lio-sam-qn_amd"), "-lqn_engine", "-Wl,-rpath," + os.path.join(ROOT, "fast-lio-sam-qn_amd"), "-o", out])
-    return out
-
-
 def test_helper_compiles_against_the_standins_and_refuses_a_null_store(tmp_path):
-    txt = subprocess.check_output([build_shim(str(tmp_path / "shim_map_normals"))], text=True)
+    txt = subprocess.check_output([build_shim("shim_map_normals.cpp", tmp_path)], text=True)
     assert txt.count("refused") == 1 and "qn_kf_map_normals" in txt and "record 48 bytes" in txt

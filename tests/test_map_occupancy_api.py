@@ -8,6 +8,7 @@ import subprocess
 import sys
 import numpy as np
 from qn_amd import engine, mapoccupancy as mo
+from shim_build import build_shim
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "fast-lio-sam-qn_amd", "csrc")
@@ -118,12 +119,7 @@ def test_no_floating_point_in_the_walk():
 
 
 def test_shim_program_compiles_and_refuses_a_null_store(tmp_path):
-    from qn_amd import build
-    build.build()
-    exe = str(tmp_path / "shim_map_occupancy")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-I" + os.path.join(ROOT, "tests", "standins"), "-I" + os.path.join(ROOT, "fast-lio-sam-qn_amd", "shim"),
-                           "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "shim_map_occupancy.cpp"),
-                           "-L" + os.path.join(ROOT, "fast-lio-sam-qn_amd"), "-lqn_engine", "-Wl,-rpath," + os.path.join(ROOT, "fast-lio-sam-qn_amd"), "-o", exe])
+    exe = build_shim("shim_map_occupancy.cpp", tmp_path)
     txt = subprocess.check_output([exe], text=True)
     assert txt.count("refused") == 4 and "mapOccupancy: 16 doubles per listed keyframe" in txt
     assert all(s in txt for s in ("qn_kf_map_occupancy:", "qn_kf_map_occupancy_grid:")) and "params 48 bytes, stats 64 bytes, grid 56 bytes" in txt

@@ -8,6 +8,7 @@ import sys
 import numpy as np
 import pytest
 from qn_amd import engine, mapoccupancy as mo
+from shim_build import build_shim
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "fast-lio-sam-qn_amd", "csrc")
@@ -22,12 +23,7 @@ def test_the_record_is_64_bytes_on_both_sides(tmp_path):
     h = open(os.path.join(ROOT, "include", "qn_engine.h")).read()
     body = h[h.index("typedef struct qn_occupancy_update {"):h.index("} qn_occupancy_update;")]
     assert re.findall(r"\b([a-z_]+)(?:\[3\])?[,;]", body) == [f for f, _ in U._fields_] and "/* 64 bytes */" in h[h.index("} qn_occupancy_update;"):][:200]
-    from qn_amd import build
-    build.build()
-    exe = str(tmp_path / "shim_map_occupancy_update")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-I" + os.path.join(ROOT, "tests", "standins"), "-I" + os.path.join(ROOT, "fast-lio-sam-qn_amd", "shim"),
-                           "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "shim_map_occupancy_update.cpp"),
-                           "-L" + os.path.join(ROOT, "fast-lio-sam-qn_amd"), "-lqn_engine", "-Wl,-rpath," + os.path.join(ROOT, "fast-lio-sam-qn_amd"), "-o", exe])
+    exe = build_shim("shim_map_occupancy_update.cpp", tmp_path)
     txt = subprocess.check_output([exe], text=True)
     assert txt.count("refused") == 2 and "updateOccupancy: 16 doubles per listed keyframe" in txt and "qn_kf_map_occupancy_update:" in txt and "update 64 bytes" in txt
     shim = open(os.path.join(ROOT, "fast-lio-sam-qn_amd", "shim", "qn_map", "map_occupancy.hpp")).read()

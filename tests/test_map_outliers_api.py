@@ -8,6 +8,7 @@ import subprocess
 import sys
 import numpy as np
 from qn_amd import engine, mapoutliers as mo
+from shim_build import build_shim
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMBOLS = ["qn_outlier_default_params", "qn_kf_map_outliers", "qn_kf_map_outlier_points", "qn_kf_map_remove_outliers"]
@@ -81,15 +82,6 @@ def test_the_selection_kernels_have_no_scratch():
         assert all(int(l.split()[0]) == 0 and " spill   0 " in l for l in rows), rows
 
 
-def build_shim(out):
-    from qn_amd import build
-    build.build()
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-I" + os.path.join(ROOT, "tests", "standins"), "-I" + os.path.join(ROOT, "fast-lio-sam-qn_amd", "shim"),
-                           "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "shim_map_outliers.cpp"),
-                           "-L" + os.path.join(ROOT, "fast-lio-sam-qn_amd"), "-lqn_engine", "-Wl,-rpath," + os.path.join(ROOT, "fast-lio-sam-qn_amd"), "-o", out])
-    return out
-
-
 def test_helper_compiles_against_the_standins_and_refuses_a_null_store(tmp_path):
-    txt = subprocess.check_output([build_shim(str(tmp_path / "shim_map_outliers"))], text=True)
+    txt = subprocess.check_output([build_shim("shim_map_outliers.cpp", tmp_path)], text=True)
     assert txt.count("refused") == 2 and "qn_kf_map_outliers" in txt and "qn_kf_map_remove_outliers" in txt and "params 24 bytes, stats 64 bytes" in txt

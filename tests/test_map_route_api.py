@@ -8,6 +8,7 @@ import subprocess
 import sys
 import numpy as np
 from qn_amd import engine, maproute as mr
+from shim_build import build_shim
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "fast-lio-sam-qn_amd", "csrc")
@@ -148,12 +149,7 @@ def test_no_floating_point_outside_the_quantisation():
 
 
 def test_shim_program_compiles_and_prints_its_refusals(tmp_path):
-    from qn_amd import build
-    build.build()
-    exe = str(tmp_path / "shim_map_route")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-I" + os.path.join(ROOT, "tests", "standins"), "-I" + os.path.join(ROOT, "fast-lio-sam-qn_amd", "shim"),
-                           "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "shim_map_route.cpp"),
-                           "-L" + os.path.join(ROOT, "fast-lio-sam-qn_amd"), "-lqn_engine", "-Wl,-rpath," + os.path.join(ROOT, "fast-lio-sam-qn_amd"), "-o", exe])
+    exe = build_shim("shim_map_route.cpp", tmp_path)
     txt = subprocess.check_output([exe], text=True)
     assert txt.count("refused") == 8 and "mapRoute: 3 doubles per goal" in txt and "routePath: max_len of at least 1" in txt and "mapRoute: iz_lo <= iz_hi" in txt
     assert all(s in txt for s in ("qn_kf_map_route:", "qn_kf_map_route_grid:", "qn_kf_map_route_path:")) and "params 32 bytes, stats 64 bytes" in txt

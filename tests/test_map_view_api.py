@@ -8,6 +8,7 @@ import subprocess
 import sys
 import numpy as np
 from qn_amd import engine, mapview as mv
+from shim_build import build_shim
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "fast-lio-sam-qn_amd", "csrc")
@@ -146,12 +147,7 @@ def test_the_kernels_have_no_scratch_and_no_spills():
 
 
 def test_shim_program_compiles_and_prints_its_refusals(tmp_path):
-    from qn_amd import build
-    build.build()
-    exe = str(tmp_path / "shim_map_view")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-I" + os.path.join(ROOT, "tests", "standins"), "-I" + os.path.join(ROOT, "fast-lio-sam-qn_amd", "shim"),
-                           "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "shim_map_view.cpp"),
-                           "-L" + os.path.join(ROOT, "fast-lio-sam-qn_amd"), "-lqn_engine", "-Wl,-rpath," + os.path.join(ROOT, "fast-lio-sam-qn_amd"), "-o", exe])
+    exe = build_shim("shim_map_view.cpp", tmp_path)
     txt = subprocess.check_output([exe], text=True)
     assert txt.count("refused") == 9 and "mapViewGain: iz_lo <= iz_hi" in txt and "share a class" in txt and "sensorRays: max_range / voxel beyond the offset limit" in txt
     assert "beyond QN_VIEW_MAX_OFFSET" in txt and txt.count("qn_kf_map_view_gain:") == 1 and txt.count("qn_kf_map_view_grid:") == 1

@@ -7,6 +7,7 @@ import sys
 import numpy as np
 import pytest
 from qn_amd import engine
+from shim_build import build_shim
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMBOLS = ["qn_kf_overlap_batch", "qn_kf_verify_overlap", "qn_kf_overlap_points"]
@@ -75,12 +76,7 @@ def test_null_and_bad_arguments_are_refused_without_a_device():
 
 
 def test_helper_compiles_against_the_standins_and_refuses_a_null_store(tmp_path):
-    from qn_amd import build
-    build.build()
-    out = str(tmp_path / "shim_overlap")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-I" + os.path.join(ROOT, "tests", "standins"), "-I" + os.path.join(ROOT, "fast-lio-sam-qn_amd", "shim"),
-                           "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "shim_overlap.cpp"),
-                           "-L" + os.path.join(ROOT, "fast-lio-sam-qn_amd"), "-lqn_engine", "-Wl,-rpath," + os.path.join(ROOT, "fast-lio-sam-qn_amd"), "-o", out])
+    out = build_shim("shim_overlap.cpp", tmp_path)
     txt = subprocess.check_output([out], text=True)
     assert "refused" in txt and "qn_kf_verify_overlap" in txt
 

@@ -3,10 +3,10 @@ zero distance for a scan against itself and against itself turned by whole secto
 query's admissibility / prefilter / order, the C-ABI declarations and the C++ helper compiling against the stand-ins.  No GPU needed."""
 import math
 import os
-import subprocess
 import numpy as np
 import pytest
 from qn_amd import scancontext as sc
+from shim_build import build_shim
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 P = sc.Params()                                    # 20 rings of 4 m, 60 sectors of 6 degrees, 80 m, lidar height 2
@@ -127,10 +127,5 @@ def test_engine_params_mirror_the_twin():
 
 
 def test_scan_context_helper_compiles_against_the_standins(tmp_path):
-    from qn_amd import build
-    build.build()
-    out = str(tmp_path / "shim_scan_context")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-I" + os.path.join(ROOT, "tests", "standins"), "-I" + os.path.join(ROOT, "fast-lio-sam-qn_amd", "shim"),
-                           "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "shim_scan_context.cpp"),
-                           "-L" + os.path.join(ROOT, "fast-lio-sam-qn_amd"), "-lqn_engine", "-Wl,-rpath," + os.path.join(ROOT, "fast-lio-sam-qn_amd"), "-o", out])
+    out = build_shim("shim_scan_context.cpp", tmp_path)
     assert os.path.exists(out)

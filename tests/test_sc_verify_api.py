@@ -4,10 +4,10 @@ sign of the seed against yaw_of_shift on a scan turned by whole sectors, and the
 import ctypes
 import math
 import os
-import subprocess
 import numpy as np
 import pytest
 from qn_amd import scancontext as sc
+from shim_build import build_shim
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMBOLS = ["qn_gicp_align_batch_guess", "qn_kf_verify_loop_candidates", "qn_kf_batch_count"]
@@ -96,10 +96,5 @@ def test_the_seed_from_the_shift_maps_the_query_onto_the_candidate(k):
 
 
 def test_verify_helper_compiles_against_the_standins(tmp_path):
-    from qn_amd import build
-    build.build()
-    out = str(tmp_path / "shim_sc_verify")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-I" + os.path.join(ROOT, "tests", "standins"), "-I" + os.path.join(ROOT, "fast-lio-sam-qn_amd", "shim"),
-                           "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "shim_sc_verify.cpp"),
-                           "-L" + os.path.join(ROOT, "fast-lio-sam-qn_amd"), "-lqn_engine", "-Wl,-rpath," + os.path.join(ROOT, "fast-lio-sam-qn_amd"), "-o", out])
+    out = build_shim("shim_sc_verify.cpp", tmp_path)
     assert os.path.exists(out)

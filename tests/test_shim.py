@@ -5,6 +5,7 @@ import os
 import subprocess
 import numpy as np
 import pytest
+from shim_build import build_shim
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BIN = os.path.join(ROOT, "tests", "shim_icp_alignment")
@@ -12,14 +13,8 @@ BIN2 = os.path.join(ROOT, "tests", "shim_coarse_to_fine")
 
 
 def build_shim_program():
-    from qn_amd import build
-    build.build()
     for name, out in (("shim_icp_alignment.cpp", BIN), ("shim_coarse_to_fine.cpp", BIN2)):
-        cmd = ["g++", "-std=c++17", "-O2", "-I" + os.path.join(ROOT, "tests", "standins"),
-               "-I" + os.path.join(ROOT, "fast-lio-sam-qn_amd", "shim"), "-I" + os.path.join(ROOT, "include"),
-               os.path.join(ROOT, "tests", name), "-L" + os.path.join(ROOT, "fast-lio-sam-qn_amd"),
-               "-lqn_engine", "-Wl,-rpath," + os.path.join(ROOT, "fast-lio-sam-qn_amd"), "-o", out]
-        subprocess.check_call(cmd)
+        assert build_shim(name, os.path.dirname(out)) == out
     return BIN
 
 

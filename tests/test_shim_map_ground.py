@@ -5,23 +5,15 @@ import subprocess
 import numpy as np
 import pytest
 from qn_amd import synth
+from shim_build import build_shim
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SEN = synth.SpinningLidar(n_beams=16, n_cols=300)
 POSES = [synth.sensor_pose(-6.0, 0.5, 0.1), synth.sensor_pose(0.0, -0.4, 0.3)]
 
 
-def build_shim(out):
-    from qn_amd import build
-    build.build()
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-I" + os.path.join(ROOT, "tests", "standins"), "-I" + os.path.join(ROOT, "fast-lio-sam-qn_amd", "shim"),
-                           "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "shim_map_ground.cpp"),
-                           "-L" + os.path.join(ROOT, "fast-lio-sam-qn_amd"), "-lqn_engine", "-Wl,-rpath," + os.path.join(ROOT, "fast-lio-sam-qn_amd"), "-o", out])
-    return out
-
-
 def test_helper_compiles_against_the_standins_and_refuses_a_null_store(tmp_path):
-    txt = subprocess.check_output([build_shim(str(tmp_path / "shim_map_ground"))], text=True)
+    txt = subprocess.check_output([build_shim("shim_map_ground.cpp", tmp_path)], text=True)
     assert txt.count("refused") == 3 and all(s in txt for s in ("qn_kf_map_ground:", "qn_kf_map_ground_grid:", "qn_kf_map_keep_classes:"))
     assert "params 40 bytes, stats 80 bytes, grid 40 bytes" in txt
 
@@ -37,7 +29,7 @@ def _fnv(chunks):
 @pytest.mark.gpu
 def test_cpp_helper_gives_the_python_result(tmp_path):
     from qn_amd import engine
-    exe = build_shim(str(tmp_path / "shim_map_ground"))
+    exe = build_shim("shim_map_ground.cpp", tmp_path)
     store = engine.KeyframeStore()
     try:
         prims = synth.Scene(np.random.default_rng(7), 120.0).primitives()

@@ -8,6 +8,7 @@ import sys
 import numpy as np
 import pytest
 from qn_amd import engine, staticmap as sm
+from shim_build import build_shim
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMBOLS = ["qn_static_default_params", "qn_kf_static_classify", "qn_kf_static_points", "qn_kf_build_map_static"]
@@ -105,11 +106,6 @@ def test_both_range_image_units_share_one_projection():
 
 
 def test_helper_compiles_against_the_standins_and_refuses_a_null_store(tmp_path):
-    from qn_amd import build
-    build.build()
-    out = str(tmp_path / "shim_static_map")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-I" + os.path.join(ROOT, "tests", "standins"), "-I" + os.path.join(ROOT, "fast-lio-sam-qn_amd", "shim"),
-                           "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "shim_static_map.cpp"),
-                           "-L" + os.path.join(ROOT, "fast-lio-sam-qn_amd"), "-lqn_engine", "-Wl,-rpath," + os.path.join(ROOT, "fast-lio-sam-qn_amd"), "-o", out])
+    out = build_shim("shim_static_map.cpp", tmp_path)
     txt = subprocess.check_output([out], text=True)
     assert "witnesses 1 4 0 1 3 2 1 2" in txt and txt.count("refused") == 2 and "qn_kf_static_classify" in txt and "qn_kf_build_map_static" in txt

@@ -8,6 +8,7 @@ import sys
 import numpy as np
 import pytest
 from qn_amd import engine
+from shim_build import build_shim
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMBOLS = ["qn_kf_submap_describe", "qn_kf_submap_cloud", "qn_kf_submap_features", "qn_kf_submap_release", "qn_kf_verify_loop_pairs_submap",
@@ -77,12 +78,7 @@ def test_null_arguments_are_refused_without_a_device():
 
 
 def test_helpers_compile_against_the_standins(tmp_path):
-    from qn_amd import build
-    build.build()
-    out = str(tmp_path / "shim_submap_verify")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-I" + os.path.join(ROOT, "tests", "standins"), "-I" + os.path.join(ROOT, "fast-lio-sam-qn_amd", "shim"),
-                           "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "shim_submap_verify.cpp"),
-                           "-L" + os.path.join(ROOT, "fast-lio-sam-qn_amd"), "-lqn_engine", "-Wl,-rpath," + os.path.join(ROOT, "fast-lio-sam-qn_amd"), "-o", out])
+    out = build_shim("shim_submap_verify.cpp", tmp_path)
     assert os.path.exists(out)
 
 
