@@ -15,8 +15,8 @@
 
 namespace {
 
-template <class F> void lanes_launch(const void* tab, dim3 grid, hipStream_t s, uint32_t shmem) {
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lanes<F>), grid, dim3(F::TB), shmem, s, (const LaneEntry<typename F::Args>*)tab);
+template <class F> void lanes_launch(const void* tab, dim3 grid, hipStream_t s) {
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lanes<F>), grid, dim3(F::TB), 0, s, (const LaneEntry<typename F::Args>*)tab);
 }
 template <class A> void lane_push(std::vector<LaneEntry<A>>& v, const A& a, uint32_t nbx) {
   LaneEntry<A> e; memset((void*)&e, 0, sizeof(e)); e.a = a; e.nbx = nbx; v.push_back(e);
@@ -24,15 +24,15 @@ template <class A> void lane_push(std::vector<LaneEntry<A>>& v, const A& a, uint
 
 struct LanePlan {                        // the launches of one segment and their argument tables
   qn_ctx* c; size_t off = 0; bool overflow = false; int flush_rc = QN_OK;
-  struct Item { void (*fn)(const void*, dim3, hipStream_t, uint32_t); size_t off; dim3 grid; int family; uint32_t shmem; };
+  struct Item { void (*fn)(const void*, dim3, hipStream_t); size_t off; dim3 grid; int family; };
   std::vector<Item> items;
   explicit LanePlan(qn_ctx* c_) : c(c_) {}
-  template <class F> void add(const std::vector<LaneEntry<typename F::Args>>& e, int family, uint32_t shmem = 0) {      // shmem: dynamic LDS the launch asks for on top of the kernel's own (an occupancy limiter: knob tick_lds_pad)      // family: the profiling family of qn_prof_get (hipEvents around the launch when profiling is on)
+  template <class F> void add(const std::vector<LaneEntry<typename F::Args>>& e, int family) {      // family: the profiling family of qn_prof_get (hipEvents around the launch when profiling is on)
     if (e.empty()) return;
     const size_t bytes = sizeof(LaneEntry<typename F::Args>) * e.size();
     const size_t a = reserve(bytes);
     if (a == SIZE_MAX) return;
-    put<F>(e, a, family, shmem);
+    put<F>(e, a, family);
   }
   // the same with `blob_bytes` bytes of data the entries point to (per-lane initial guesses) in front of the table, in ONE reservation: a flush of the arena can
   // never fall between the data and its launch.  fix(entries, device address of the blob) sets the entries' pointers once the place is known.
@@ -43,14 +43,14 @@ struct LanePlan {                        // the launches of one segment and thei
     if (a == SIZE_MAX) return;
     memcpy(c->args_h + a, blob, blob_bytes);
     fix(e, (const char*)(c->args_d + a));
-    put<F>(e, a + head, family, 0);
+    put<F>(e, a + head, family);
   }
-  template <class F> void put(const std::vector<LaneEntry<typename F::Args>>& e, size_t a, int family, uint32_t shmem) {
+  template <class F> void put(const std::vector<LaneEntry<typename F::Args>>& e, size_t a, int family) {
     const size_t bytes = sizeof(LaneEntry<typename F::Args>) * e.size();
     memcpy(c->args_h + a, e.data(), bytes);
     uint32_t gx = 0; for (const auto& x : e) gx = std::max(gx, x.nbx);
     gx = (gx + 7u) & ~7u;                                              // a multiple of 8: (linear workgroup id) mod 8 - the XCD - stays blockIdx.x mod 8 in every lane (xcd_block)
-    items.push_back(Item{&lanes_launch<F>, a, dim3(gx, (uint32_t)e.size()), family, shmem});
+    items.push_back(Item{&lanes_launch<F>, a, dim3(gx, (uint32_t)e.size()), family});
     off = a + bytes;
   }
   size_t reserve(size_t bytes) {                                       // the arena offset of `bytes` more (SIZE_MAX: overflow, reported by run())
@@ -70,7 +70,7 @@ struct LanePlan {                        // the launches of one segment and thei
     if (overflow) { if (flush_rc == QN_OK) c->last_error = "batch: argument arena too small for one launch's table"; return QN_ERR_HIP; }
     if (items.empty()) return QN_OK;
     HIPCHK(c, hipMemcpyAsync(c->args_d, c->args_h, off, hipMemcpyHostToDevice, c->stream));
-    for (const Item& it : items) { c->prof_begin(it.family, (int)it.grid.y); it.fn(c->args_d + it.off, it.grid, c->stream, it.shmem); c->prof_end(); }
+    for (const Item& it : items) { c->prof_begin(it.family, (int)it.grid.y); it.fn(c->args_d + it.off, it.grid, c->stream); c->prof_end(); }
     c->batch_launches += items.size();
     items.clear(); off = 0;
     HIPCHK(c, hipGetLastError());
@@ -114,8 +114,7 @@ int lane_set_cloud(qn_ctx* c, int which, const float* xyz, uint32_t n, uint32_t 
 bool batch_supported(const qn_ctx* c) {      // everything else takes the classic path, pair by pair (same results)
   const qn_gicp_params& p = c->params;
   const int maxit = p.force_iterations > 0 ? p.force_iterations : p.max_iterations;
-  return c->batch_lanes >= 2 && !c->lanes_failed && maxit > 0 && c->fused_ticks && c->fused_final && c->far_enabled && c->knn_hist && !c->verify_track && !c->clk_probe && !c->list_probe &&
-         c->tick_tb == 512 && c->tick_occ >= 4 && !c->dbg_counters;
+  return c->knob.batch_lanes >= 2 && !c->lanes_failed && maxit > 0 && c->knob.far_enabled && c->knob.knn_hist && !c->knob.verify_track && !c->clk_probe && !c->list_probe && !c->dbg_counters;
 }
 
 // the context's argument arena of the lane launches (pinned + device, 4 MB each), made on first use
@@ -129,11 +128,11 @@ int lane_args_arena(qn_ctx* c) {
 
 int batch_ensure_lanes(qn_ctx* c) {
   HIPCHK(c, hipSetDevice(c->device));
-  const int B = std::max(1, std::min(c->batch_lanes, 64));
+  const int B = std::max(1, std::min(c->knob.batch_lanes, 64));
   if (c->lanes.empty()) c->lanes.push_back(c);
   while ((int)c->lanes.size() < B) {
     qn_ctx* l = nullptr;
-    const int rc = (c->fail_lane_create > 0 && (int)c->lanes.size() >= c->fail_lane_create) ? QN_ERR_HIP : ctx_create(c->device, c->max_points, c->stream, &l);
+    const int rc = (c->knob.fail_lane_create > 0 && (int)c->lanes.size() >= c->knob.fail_lane_create) ? QN_ERR_HIP : ctx_create(c->device, c->max_points, c->stream, &l);
     if (rc != QN_OK) {      // (out of memory, typically: batch_lanes x a full max_points slab) - the lanes created so far are freed again, both entry points then take the one-pair path
       c->last_error = "batch: lane context creation failed (lanes need batch_lanes x the context's device memory)";
       while (c->lanes.size() > 1) { qn_ctx_destroy(c->lanes.back()); c->lanes.pop_back(); }
@@ -151,10 +150,7 @@ int batch_ensure_lanes(qn_ctx* c) {
     if (l == c) continue;
     if (l->params.k_correspondences != c->params.k_correspondences) l->cloud[0].has_cov = l->cloud[1].has_cov = false;
     l->params = c->params;
-    l->cell_override = c->cell_override; l->margin_nn = c->margin_nn; l->margin_nn_t0 = c->margin_nn_t0; l->margin_knn = c->margin_knn; l->big_blocks0 = c->big_blocks0; l->fb_blocks0 = c->fb_blocks0;
-    l->big_ratio = c->big_ratio; l->nn_rounds = c->nn_rounds; l->knn_rounds = c->knn_rounds; l->knn_trips = c->knn_trips; l->knn_mm = c->knn_mm; l->knn_single_all = c->knn_single_all; l->bbox_blocks = c->bbox_blocks; l->stable_cells = c->stable_cells;
-    l->unseeded_cap = c->unseeded_cap; l->track_from_tick = c->track_from_tick; l->fused_from_tick = c->fused_from_tick; l->ticks_per_chunk = c->ticks_per_chunk; l->far_chunk = c->far_chunk; l->far_group = c->far_group; l->far_ranked = c->far_ranked;
-    l->list_small = c->list_small; l->tick_ppt_min = c->tick_ppt_min; l->tick_rpb = c->tick_rpb; l->nn_lane = c->nn_lane;
+    l->lane = c->lane;
   }
   return QN_OK;
 }
@@ -183,7 +179,7 @@ int batch_register(qn_ctx* owner, const qn_pair_desc* pairs, const uint32_t* idx
   std::vector<LaneEntry<KnnHistArgs>> v_sel, v_lst; std::vector<LaneEntry<KnnSingleK::Args>> v_single; std::vector<LaneEntry<KnnCovArgs>> v_tail; std::vector<LaneEntry<CovFromIdxK::Args>> v_cov;
   auto push_grid = [&](const GridLaunch& G) {
     lane_push(v_pack, G.pack, G.pack_nb); lane_push(v_count, G.count, G.nb); lane_push(v_scan, G.scan, G.scan_nb); lane_push(v_scat, G.scat, G.nb);
-    if (G.stable) lane_push(v_stab, G.stab, G.nb);
+    lane_push(v_stab, G.stab, G.nb);
   };
   auto push_knn = [&](const KnnLaunch& K) {
     lane_push(v_sel, K.sel, K.sel_nb); lane_push(v_lst, K.lst, K.lst_nb); lane_push(v_single, K.single, K.single_nb); lane_push(v_tail, K.tail, K.tail_nb); lane_push(v_cov, K.cov, K.cov_nb);
@@ -195,11 +191,11 @@ int batch_register(qn_ctx* owner, const qn_pair_desc* pairs, const uint32_t* idx
     qn_gicp_result* out = &results[R.pair];
     valid[R.pair] = 0; memset(out, 0, sizeof(*out)); out->fitness = DBL_MAX;
     for (int i = 0; i < 4; i++) { out->T[5 * i] = 1.f; out->T64[5 * i] = 1.0; }
-    c->pair_pipeline = false; c->persist_batch_off = true; c->tgt_pending = false; c->tgt_on_stream2 = false;
+    c->knob.pair_pipeline = false; c->knob.persist_batch_off = true; c->tgt_pending = false; c->tgt_on_stream2 = false;
     const uint64_t key = ((uint64_t)pd.ns << 32) ^ ((uint64_t)pd.stride_bytes << 1) ^ (uint64_t)(pd.on_device ? 1 : 0);
     // the candidates of ONE query share their source cloud (qn_icp_alignment_same_source): a lane that still holds this source - same buffer within this call - keeps its grid and covariances
-    R.build_source = !(owner->batch_share_source && last_src[l] == pd.src && last_key[l] == key && pd.src != nullptr && c->cloud[0].has_grid && c->cloud[0].has_cov && c->cloud[0].n == pd.ns);
-    if (R.build_source && owner->batch_share_source && pd.src != nullptr && pd.ns > 0) {      // an earlier lane of this run with the same source buffer: borrow its preparation
+    R.build_source = !(owner->knob.batch_share_source && last_src[l] == pd.src && last_key[l] == key && pd.src != nullptr && c->cloud[0].has_grid && c->cloud[0].has_cov && c->cloud[0].n == pd.ns);
+    if (R.build_source && owner->knob.batch_share_source && pd.src != nullptr && pd.ns > 0) {      // an earlier lane of this run with the same source buffer: borrow its preparation
       for (uint32_t j = 0; j < l; j++) {
         const qn_pair_desc& pj = pairs[L[j].pair];
         if (L[j].active && L[j].alias < 0 && pj.src == pd.src && pj.ns == pd.ns && pj.stride_bytes == pd.stride_bytes && pj.on_device == pd.on_device) { R.alias = (int)j; break; }
@@ -224,10 +220,10 @@ int batch_register(qn_ctx* owner, const qn_pair_desc* pairs, const uint32_t* idx
   plan.add<PackBBoxK>(v_pack, QN_K_GRID_BUILD); plan.add<CellCountK>(v_count, QN_K_GRID_BUILD); plan.add<ScanLookbackK>(v_scan, QN_K_GRID_BUILD); plan.add<ScatterK>(v_scat, QN_K_GRID_BUILD); plan.add<StableCellsK>(v_stab, QN_K_GRID_BUILD);
   // (knn_mm 0: the VALU-scoring forms of both histogram passes)
   if (k <= 24) {
-    if (owner->knn_mm) { plan.add<KnnHistK<false, 32>>(v_sel, QN_K_KNN_SELECT, (uint32_t)owner->knn_lds_pad); plan.add<KnnHistK<true, 32>>(v_lst, QN_K_KNN_COV); }
-    else { plan.add<KnnHistK<false, 32, false>>(v_sel, QN_K_KNN_SELECT, (uint32_t)owner->knn_lds_pad); plan.add<KnnHistK<true, 32, false>>(v_lst, QN_K_KNN_COV); }
+    if (owner->lane.knn_mm) { plan.add<KnnHistK<false, 32>>(v_sel, QN_K_KNN_SELECT); plan.add<KnnHistK<true, 32>>(v_lst, QN_K_KNN_COV); }
+    else { plan.add<KnnHistK<false, 32, false>>(v_sel, QN_K_KNN_SELECT); plan.add<KnnHistK<true, 32, false>>(v_lst, QN_K_KNN_COV); }
   } else {
-    if (owner->knn_mm) { plan.add<KnnHistK<false, 48>>(v_sel, QN_K_KNN_SELECT); plan.add<KnnHistK<true, 48>>(v_lst, QN_K_KNN_COV); }
+    if (owner->lane.knn_mm) { plan.add<KnnHistK<false, 48>>(v_sel, QN_K_KNN_SELECT); plan.add<KnnHistK<true, 48>>(v_lst, QN_K_KNN_COV); }
     else { plan.add<KnnHistK<false, 48, false>>(v_sel, QN_K_KNN_SELECT); plan.add<KnnHistK<true, 48, false>>(v_lst, QN_K_KNN_COV); }
   }
   plan.add<KnnSingleK>(v_single, QN_K_KNN_COV);
@@ -237,7 +233,7 @@ int batch_register(qn_ctx* owner, const qn_pair_desc* pairs, const uint32_t* idx
   // ---- align() (loop_closure.cpp:124): gicp_align's batch-member form, every lane with its own chunk boundaries and far-query regime
   const int per_outer = p.optimizer == QN_OPT_LM ? 2 : 1;
   const int maxit = p.force_iterations > 0 ? p.force_iterations : p.max_iterations;
-  const int fixed_unseeded = std::max(1, std::min(owner->track_from_tick, owner->fused_from_tick)) * per_outer;
+  const int fixed_unseeded = fixed_unseeded_iterations(owner) * per_outer;
   const bool exact_ticks = p.force_iterations > 0 && p.optimizer == QN_OPT_GN;
   {
     std::vector<LaneEntry<InitStateK::Args>> v_init; std::vector<float> g16;
@@ -283,7 +279,7 @@ int batch_register(qn_ctx* owner, const qn_pair_desc* pairs, const uint32_t* idx
           qn_ctx* c = R.c;
           const int t = tick_no - R.chunk_start;
           c->count_far_now = R.first_chunk && (t / per_outer == (R.chunk - 1) / per_outer);      // far-query statistics: the chunk's last unseeded linearisation
-          const NnLaunch N = prep_nn(c, 0, c->sqd, false, tick_no / per_outer, 0);
+          const NnLaunch N = prep_nn(c, 0, c->sqd, 0);
           group = group && N.group; lane = lane && N.lane;
           lane_push(v_g, N.grid, N.grid_nb); lane_push(v_l, N.list, N.list_nb);
           const uint32_t nb = acc_blocks(c);
@@ -304,7 +300,7 @@ int batch_register(qn_ctx* owner, const qn_pair_desc* pairs, const uint32_t* idx
           if (a.far_mode == 1) { lane_push(v_f, far_args(c), (uint32_t)QN_FAR_BLOCKS); lane_push(v_r, far_reduce_args(c), 1u); }
           c->gen++; c->part_rows = -1;
         }
-        plan.add<TickK<512, 4, 0, false>>(v_t, QN_K_GN_TICK_FUSED, (uint32_t)owner->tick_lds_pad); plan.add<FarK>(v_f, QN_K_FAR); plan.add<FarReduceK>(v_r, QN_K_FAR);
+        plan.add<TickK<TICK_TB, 4, 0, false>>(v_t, QN_K_GN_TICK_FUSED); plan.add<FarK>(v_f, QN_K_FAR); plan.add<FarReduceK>(v_r, QN_K_FAR);
       }
     }
     // chunk ends of the lanes whose boundary this is: the statistics block only (forced Gauss-Newton runs that cannot be done yet), or the closing pass
@@ -321,14 +317,14 @@ int batch_register(qn_ctx* owner, const qn_pair_desc* pairs, const uint32_t* idx
           lane_push(v_fit, FinalizeFitK::Args{st_cur(c), c->result_host, c->far_stats, c->fit_psum, c->fit_pcnt, (int)tick_rows(c)}, 1u);
         }
       }
-      plan.add<FinalizeK>(v_fin, QN_K_SOLVE); plan.add<TickK<512, 4, 1, false>>(v_close, QN_K_FITNESS); plan.add<FinalizeFitK>(v_fit, QN_K_FITNESS);
+      plan.add<FinalizeK>(v_fin, QN_K_SOLVE); plan.add<TickK<TICK_TB, 4, 1, false>>(v_close, QN_K_FITNESS); plan.add<FinalizeFitK>(v_fit, QN_K_FITNESS);
     }
     const auto tt0 = std::chrono::steady_clock::now();
     int rc = plan.run();
     if (rc != QN_OK) return rc;
     const auto tt1 = std::chrono::steady_clock::now();
     HIPCHK(owner, hipStreamSynchronize(s));
-    if (owner->batch_trace) { const auto tt2 = std::chrono::steady_clock::now();
+    if (owner->knob.batch_trace) { const auto tt2 = std::chrono::steady_clock::now();
       fprintf(stderr, "qn batch %p: segment to tick %d  prep+enqueue %.0f us  sync %.0f us  (since call %.0f us)\n", (void*)owner, stop, std::chrono::duration<double, std::micro>(tt1 - tt0).count(),
               std::chrono::duration<double, std::micro>(tt2 - tt1).count(), std::chrono::duration<double, std::micro>(tt2 - t_call).count()); }
     for (LaneRun& R : L) {
@@ -345,8 +341,8 @@ int batch_register(qn_ctx* owner, const qn_pair_desc* pairs, const uint32_t* idx
       const qn::ResultBlock* rb = c->result_host;      // far queries: keep the refresh kernel in the chain only while ticks actually ask for refreshes
       if (R.first_chunk) c->far_mode = rb->far_queries * 16u > c->cloud[0].n ? 1 : 2;
       else c->far_mode = (c->far_mode == 1 ? rb->far_requests : rb->far_misses / (uint32_t)std::max(1, R.chunk)) > 256u ? 1 : 2;
-      if (!exact_ticks) R.chunk = R.first_chunk ? c->ticks_per_chunk : std::max(2 * per_outer, c->ticks_per_chunk / 2);
-      else R.chunk = c->far_mode == 1 ? std::min(R.ticks_left, c->far_chunk) : R.ticks_left;
+      if (!exact_ticks) R.chunk = R.first_chunk ? TICKS_PER_CHUNK : std::max(2 * per_outer, TICKS_PER_CHUNK / 2);
+      else R.chunk = c->far_mode == 1 ? std::min(R.ticks_left, FAR_CHUNK) : R.ticks_left;
       if (R.budget <= 0 || R.chunk <= 0) { c->last_error = "align: device state machine did not terminate"; owner->last_error = c->last_error; finish_lane(R, QN_ERR_HIP); continue; }
       R.first_chunk = false; R.chunk_start = stop; R.next = stop + R.chunk;
     }
@@ -374,17 +370,17 @@ extern "C" int qn_gicp_align_batch_guess(qn_ctx* c, const qn_pair_desc* pairs, c
   if (join_target(c) != QN_OK) return QN_ERR_HIP;
   int rc = batch_supported(c) ? batch_ensure_lanes(c) : QN_ERR_NOT_READY;
   if (rc != QN_OK) {                       // knobs that rule the lanes out, or no memory for them: the classic path, pair by pair, as a batch member (same results; what qn_icp_alignment_batch does too)
-    const bool sp = c->pair_pipeline, sb = c->persist_batch_off; c->pair_pipeline = false; c->persist_batch_off = true;
+    const bool sp = c->knob.pair_pipeline, sb = c->knob.persist_batch_off; c->knob.pair_pipeline = false; c->knob.persist_batch_off = true;
     for (uint32_t i = 0; i < n_pairs; i++) {
       const qn_pair_desc& p = pairs[i];
-      const bool same = c->batch_share_source && i > 0 && status[i - 1] == QN_OK && pairs[i - 1].src == p.src && pairs[i - 1].ns == p.ns && pairs[i - 1].stride_bytes == p.stride_bytes && pairs[i - 1].on_device == p.on_device;
-      status[i] = icp_alignment(c, p.src, p.ns, p.dst, p.nt, p.stride_bytes, score_thr, &results[i], &valid[i], p.on_device ? 1 : 0, same, false,
+      const bool same = c->knob.batch_share_source && i > 0 && status[i - 1] == QN_OK && pairs[i - 1].src == p.src && pairs[i - 1].ns == p.ns && pairs[i - 1].stride_bytes == p.stride_bytes && pairs[i - 1].on_device == p.on_device;
+      status[i] = icp_alignment(c, p.src, p.ns, p.dst, p.nt, p.stride_bytes, score_thr, &results[i], &valid[i], p.on_device ? 1 : 0, same,
                                 guesses16 ? guesses16 + 16 * (size_t)i : nullptr);
     }
-    c->pair_pipeline = sp; c->persist_batch_off = sb;
+    c->knob.pair_pipeline = sp; c->knob.persist_batch_off = sb;
     return QN_OK;
   }
-  const bool sp = c->pair_pipeline, sb = c->persist_batch_off;
+  const bool sp = c->knob.pair_pipeline, sb = c->knob.persist_batch_off;
   const uint32_t B = (uint32_t)c->lanes.size();
   std::vector<const float*> last_src(B, nullptr); std::vector<uint64_t> last_key(B, 0);      // (within THIS call: same pointer = same cloud)
   std::vector<uint32_t> idx(B);
@@ -393,7 +389,7 @@ extern "C" int qn_gicp_align_batch_guess(qn_ctx* c, const qn_pair_desc* pairs, c
     for (uint32_t l = 0; l < m; l++) idx[l] = base + l;
     rc = batch_register(c, pairs, idx.data(), m, score_thr, results, valid, status, last_src, last_key, guesses16);
   }
-  c->pair_pipeline = sp; c->persist_batch_off = sb;
+  c->knob.pair_pipeline = sp; c->knob.persist_batch_off = sb;
   if (rc != QN_OK) (void)hipStreamSynchronize(c->stream);
   return rc;
 }

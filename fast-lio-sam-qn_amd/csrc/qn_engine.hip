@@ -307,7 +307,7 @@ static int join_target(qn_ctx* c) {
 // device memory (GridView::dims, grid_resolve); the table-sized scan uses the grid of the largest table and leaves early.  What the host
 // needs to know - "the cloud held non-finite coordinates" - arrives with the pinned mirror at the next synchronisation (clouds_valid).
 // (arguments of the five launches for one cloud: the classic path launches them one by one, the batched path puts the entries of every cloud of a batch into ONE launch each)
-struct GridLaunch { PackBBoxK::Args pack; uint32_t pack_nb; CellCountK::Args count; ScanLookbackK::Args scan; uint32_t scan_nb; ScatterK::Args scat; StableCellsK::Args stab; bool stable; uint32_t nb; };
+struct GridLaunch { PackBBoxK::Args pack; uint32_t pack_nb; CellCountK::Args count; ScanLookbackK::Args scan; uint32_t scan_nb; ScatterK::Args scat; StableCellsK::Args stab; uint32_t nb; };
 static GridLaunch prep_grid(qn_ctx* c, CloudBuf& b, const char* dsrc, uint32_t stride, bool lanes = false) {
   const uint32_t n = b.n;
   GridView& g = b.grid;
@@ -318,12 +318,13 @@ static GridLaunch prep_grid(qn_ctx* c, CloudBuf& b, const char* dsrc, uint32_t s
   L.scan_nb = (c->max_cells + QN_BLOCK * QN_SCAN_ITEMS - 1) / (QN_BLOCK * QN_SCAN_ITEMS);
   if (((++c->build_epoch) & 0x3fffffffu) == 0u) ++c->build_epoch;     // (0 = the tag of the zero-initialised status words)
   // (a lone build wants few blocks - one contended ticket each; in a batched launch the clouds run side by side and the pack pass is bandwidth: all the slots)
-  L.pack_nb = std::min<uint32_t>(L.nb, (uint32_t)std::min(lanes ? QN_BBOX_MAX_BLOCKS : c->bbox_blocks, QN_BBOX_MAX_BLOCKS));
-  L.pack = PackBBoxK::Args{dsrc, stride, n, b.raw, c->bbox_acc, c->max_cells, c->cell_override, b.dims, b.dims_host};
+  constexpr int LONE_PACK_BLOCKS = 64;      // 128 blocks = 768 atomics on six words: 10.6 us per cloud; 32: 5 us
+  static_assert(LONE_PACK_BLOCKS <= QN_BBOX_MAX_BLOCKS, "the accumulator has one box per block");
+  L.pack_nb = std::min<uint32_t>(L.nb, (uint32_t)(lanes ? QN_BBOX_MAX_BLOCKS : LONE_PACK_BLOCKS));
+  L.pack = PackBBoxK::Args{dsrc, stride, n, b.raw, c->bbox_acc, c->max_cells, c->lane.cell_override, b.dims, b.dims_host};
   L.count = CellCountK::Args{b.raw, n, g, b.counts, b.cell_of_pt};
   L.scan = ScanLookbackK::Args{b.counts, b.dims, b.cell_start, c->scan_status, c->build_epoch, n};
-  L.stable = c->stable_cells;
-  L.scat = ScatterK::Args{b.raw, n, b.cell_of_pt, b.cell_start, b.counts, L.stable ? b.sorted_tmp : b.sorted};
+  L.scat = ScatterK::Args{b.raw, n, b.cell_of_pt, b.cell_start, b.counts, b.sorted_tmp};      // (k_stable_cells then puts every cell in a run-independent order)
   L.stab = StableCellsK::Args{b.sorted_tmp, n, b.cell_of_pt, b.cell_start, b.sorted};
   b.has_grid = true; b.has_cov = false; b.knn_tab = nullptr;
   return L;
@@ -338,7 +339,7 @@ static int build_grid(qn_ctx* c, CloudBuf& b, const char* dsrc, uint32_t stride)
     hipLaunchKernelGGL(k_cell_count, dim3(L.nb), dim3(QN_BLOCK), 0, s, L.count.pts, L.count.n, L.count.g, L.count.counts, L.count.cell_of_pt);
     hipLaunchKernelGGL(k_scan_lookback, dim3(L.scan_nb), dim3(QN_BLOCK), 0, s, L.scan.in, L.scan.dims, L.scan.out, L.scan.status, L.scan.epoch, L.scan.total);
     hipLaunchKernelGGL(k_scatter, dim3(L.nb), dim3(QN_BLOCK), 0, s, L.scat.pts, L.scat.n, L.scat.cell_of_pt, L.scat.cell_start, L.scat.counts, L.scat.sorted);
-    if (L.stable) hipLaunchKernelGGL(k_stable_cells, dim3(L.nb), dim3(QN_BLOCK), 0, s, L.stab.in, L.stab.n, L.stab.cell_of_pt, L.stab.cell_start, L.stab.out); }
+    hipLaunchKernelGGL(k_stable_cells, dim3(L.nb), dim3(QN_BLOCK), 0, s, L.stab.in, L.stab.n, L.stab.cell_of_pt, L.stab.cell_start, L.stab.out); }
   HIPCHK(c, hipGetLastError());
   return QN_OK;
 }
@@ -386,7 +387,7 @@ static int set_cloud(qn_ctx* c, int which, const float* xyz, uint32_t n, uint32_
   if (n > c->max_points) return QN_ERR_CAPACITY;
   HIPCHK(c, hipSetDevice(c->device));
   if (which == QN_SOURCE && join_target(c) != QN_OK) return QN_ERR_HIP;         // (a target still in flight reads the staging buffer)
-  c->tgt_on_stream2 = which == QN_TARGET ? (c->pair_pipeline && !c->prof_on && !c->no_pipe && c->cloud[0].has_grid && pair_pipeline_ready(c)) : c->tgt_on_stream2;
+  c->tgt_on_stream2 = which == QN_TARGET ? (c->knob.pair_pipeline && !c->prof_on && !c->no_pipe && c->cloud[0].has_grid && pair_pipeline_ready(c)) : c->tgt_on_stream2;
   TargetScope scope(c, which == QN_TARGET && c->tgt_on_stream2);
   hipStream_t s = c->stream;
   const char* dsrc = (const char*)xyz;
@@ -403,22 +404,23 @@ extern "C" int qn_gicp_set_target_device(qn_ctx* c, const float* xyz, uint32_t n
 // ------------------------------------------------------------------ calculateSource/TargetCovariances
 // the five launches of the histogram-selection path for one cloud (classic: one by one; batched: one entry per cloud in ONE launch each)
 struct KnnLaunch { KnnHistArgs sel; uint32_t sel_nb; KnnHistArgs lst; uint32_t lst_nb; KnnSingleK::Args single; uint32_t single_nb; KnnCovArgs tail; uint32_t tail_nb; CovFromIdxK::Args cov; uint32_t cov_nb; };
-static float knn_first_radius(const qn_ctx* c, const CloudBuf& b) {
+static float knn_first_radius(const CloudBuf& b) {
   // first radius in cells.  A cloud of <= 65536 points is ONE round of waves (16 queries each, 4096 resident): the kernel then lasts as long as
   // its slowest wave, and a wave that has to retry with a doubled radius is 3-4x slower - a wider first radius (fewer retries) wins there
   // (30k points: 174 -> 116 us); beyond that the retries hide behind the next round of waves and the smaller radius wins (100k: 100 vs 131 us);
   // at 10k points the wider radius measured slower again (few waves, each with more candidates): 2.5 only between 16k and 64k.
-  return -(c->margin_knn > 0.f ? c->margin_knn : (b.n > 16384u && b.n <= 65536u ? 2.5f : 2.0f));      // negative = in cells (the kernels know the cell edge, the host does not)
+  return -(b.n > 16384u && b.n <= 65536u ? 2.5f : 2.0f);      // negative = in cells (the kernels know the cell edge, the host does not)
 }
 // lanes: the launch carries many clouds (k_lanes) - the list passes, which serve a handful of leftovers per cloud with wave-stride loops, get small grids
 // (an empty block still costs the dispatcher ~4 ns: 2048 of them x 16 clouds were 140 us per launch)
 static KnnLaunch prep_knn(qn_ctx* c, CloudBuf& b, int k, int32_t* kidx, float* kd2, bool lanes = false) {
-  const float r0 = knn_first_radius(c, b);
+  const float r0 = knn_first_radius(b);
   uint32_t* genc = c->fb_count2 + 1;
   KnnLaunch L;
   L.sel_nb = (b.n + QN_KNN_BLOCK / 4 - 1) / (QN_KNN_BLOCK / 4);     // 16 queries per wave
-  if (lanes && c->knn_trips > 1) L.sel_nb = (L.sel_nb + (uint32_t)c->knn_trips - 1) / (uint32_t)c->knn_trips;      // batched launches: a wave serves several groups of 16 (its prologue - table entry, grid numbers - is a twentieth of a group's work)
-  L.sel = KnnHistArgs{b.grid, k, r0, c->knn_single_all ? -1 : c->knn_rounds, kidx, kd2, c->fb_list, c->fb_count2, c->big_list, genc};
+  if (lanes && c->lane.knn_trips > 1) L.sel_nb = (L.sel_nb + (uint32_t)c->lane.knn_trips - 1) / (uint32_t)c->lane.knn_trips;      // batched launches: a wave serves several groups of 16 (its prologue - table entry, grid numbers - is a twentieth of a group's work)
+  constexpr int KNN_ROUNDS = 2;      // rounds of the selection pass before a query goes to the list pass
+  L.sel = KnnHistArgs{b.grid, k, r0, KNN_ROUNDS, kidx, kd2, c->fb_list, c->fb_count2, c->big_list, genc};
   L.lst_nb = std::min<uint32_t>((b.n + 63) / 64, lanes ? 96 : 512) * (QN_BLOCK / QN_KNN_BLOCK);
   L.lst = KnnHistArgs{b.grid, k, r0, 64, kidx, kd2, c->fb_list, c->fb_count2, c->big_list, genc};
   // far / overflowing queries (isolated points, sparse far field): one per wave; its leftovers -> the sorted-list kernel (fb_list is free again)
@@ -433,21 +435,21 @@ static KnnLaunch prep_knn(qn_ctx* c, CloudBuf& b, int k, int32_t* kidx, float* k
 template <int KMAX>
 static void launch_knn_cov(qn_ctx* c, CloudBuf& b, int k, int32_t* kidx, float* kd2) {
   hipStream_t s = c->stream;
-  if (c->knn_hist) {                        // histogram selection (default); its leftovers -> hist list pass -> general sorted-list pass
+  if (c->knob.knn_hist) {                        // histogram selection (default); its leftovers -> hist list pass -> general sorted-list pass
     const KnnLaunch L = prep_knn(c, b, k, kidx, kd2);
     constexpr int HCAP = KMAX <= 24 ? 32 : 48;      // pass-2 list capacity: 32 keeps the selection kernel at 4 waves/SIMD
     { ProfScope sel(c, QN_K_KNN_SELECT);
-      if (!c->knn_mm) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_knn_hist<false, HCAP, false>), dim3(L.sel_nb), dim3(QN_KNN_BLOCK), 0, s, L.sel.g, L.sel.k, L.sel.r0, L.sel.max_rounds, L.sel.knn_idx, L.sel.knn_d2, L.sel.fb_list, L.sel.fb_count, L.sel.gen_list, L.sel.gen_count);
+      if (!c->lane.knn_mm) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_knn_hist<false, HCAP, false>), dim3(L.sel_nb), dim3(QN_KNN_BLOCK), 0, s, L.sel.g, L.sel.k, L.sel.r0, L.sel.max_rounds, L.sel.knn_idx, L.sel.knn_d2, L.sel.fb_list, L.sel.fb_count, L.sel.gen_list, L.sel.gen_count);
       else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_knn_hist<false, HCAP>), dim3(L.sel_nb), dim3(QN_KNN_BLOCK), 0, s, L.sel.g, L.sel.k, L.sel.r0, L.sel.max_rounds, L.sel.knn_idx, L.sel.knn_d2, L.sel.fb_list, L.sel.fb_count, L.sel.gen_list, L.sel.gen_count); }
     ProfScope ps(c, QN_K_KNN_COV);
-    if (!c->knn_mm) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_knn_hist<true, HCAP, false>), dim3(L.lst_nb), dim3(QN_KNN_BLOCK), 0, s, L.lst.g, L.lst.k, L.lst.r0, L.lst.max_rounds, L.lst.knn_idx, L.lst.knn_d2, L.lst.fb_list, L.lst.fb_count, L.lst.gen_list, L.lst.gen_count);
+    if (!c->lane.knn_mm) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_knn_hist<true, HCAP, false>), dim3(L.lst_nb), dim3(QN_KNN_BLOCK), 0, s, L.lst.g, L.lst.k, L.lst.r0, L.lst.max_rounds, L.lst.knn_idx, L.lst.knn_d2, L.lst.fb_list, L.lst.fb_count, L.lst.gen_list, L.lst.gen_count);
     else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_knn_hist<true, HCAP>), dim3(L.lst_nb), dim3(QN_KNN_BLOCK), 0, s, L.lst.g, L.lst.k, L.lst.r0, L.lst.max_rounds, L.lst.knn_idx, L.lst.knn_d2, L.lst.fb_list, L.lst.fb_count, L.lst.gen_list, L.lst.gen_count);
     hipLaunchKernelGGL(k_knn_single, dim3(L.single_nb), dim3(QN_BLOCK), 0, s, L.single.g, L.single.k, L.single.knn_idx, L.single.knn_d2, L.single.list, L.single.count, L.single.gen_list, L.single.gen_count);
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_knn_cov<KMAX, true, 4>), dim3(L.tail_nb), dim3(QN_BLOCK), 0, s, L.tail.g, L.tail.raw, L.tail.k, L.tail.r0, L.tail.max_rounds, L.tail.cov, L.tail.knn_idx, L.tail.knn_d2, L.tail.fb_list, L.tail.fb_count);
     hipLaunchKernelGGL(k_cov_from_idx, dim3(L.cov_nb), dim3(QN_BLOCK), 0, s, L.cov.raw, L.cov.sorted, L.cov.n, L.cov.k, L.cov.knn_idx, L.cov.nrm, L.cov.nrm_sorted, L.cov.rec, L.cov.list_counts);
     return;
   }
-  const float r0 = knn_first_radius(c, b);
+  const float r0 = knn_first_radius(b);
   ProfScope ps(c, QN_K_KNN_COV);
   {                                         // sorted-list sink, 16 queries per wave x 4 candidate sub-slots (knn_hist = 0)
     const uint32_t nb = (b.n + QN_BLOCK / 4 - 1) / (QN_BLOCK / 4);
@@ -485,90 +487,88 @@ static int compute_cov(qn_ctx* c, int which, int32_t* kidx, float* kd2) {
 extern "C" int qn_gicp_compute_covariances(qn_ctx* c, int which) { return compute_cov(c, which, c->knn_idx, nullptr); }
 
 // ------------------------------------------------------------------ align
-// seeded = true: the previous iteration's NN indices are valid -> temporal tracking kernel; false -> full grid search
-// tick = index of this NN pass within the align (list-pass grids shrink as the optimiser converges: the first search
-// leaves ~10-20 % of the queries to the list passes, the first tracked pass most of them after the big initial pose
-// step, later passes a handful - any grid is correct, the lists are walked wave-stride)
-// (arguments of the grid pass and the list pass of one exact 1-NN search; `seeded` searches replace the grid pass by k_nn_track)
+// One exact, unseeded 1-NN search (ball around the query): the grid pass and the list pass behind it.  The tracked regime has no launch of its own: it lives
+// inside k_tick.  Every such pass leaves thousands of queries to the lists (~10-20 % of them): the list grids below are sized for that - any grid is correct, the
+// lists are walked wave-stride.
+// (the search's tuned numbers; the measurements behind them: profiles/EXPERIMENTS.md, "Retired knobs")
+constexpr float NN_R0 = -1.f;                                        // first search radius: one cell (negative = in cells: the kernels know the cell edge, the host does not)
+constexpr float NN_BIG_RATIO = 2.5f;                                 // leftovers whose next radius exceeds NN_BIG_RATIO * r0 go one-per-wave
+constexpr int NN_BIG_BLOCKS = 4096; constexpr uint32_t NN_FB_BLOCKS = 512;      // grid of the list pass: one-far-query-per-wave blocks (idle blocks exit at once), wave-stride leftover blocks
 struct NnLaunch { NnSearchArgs grid; uint32_t grid_nb; NnSearchArgs list; uint32_t list_nb; bool group; bool lane; };      // lane: the first pass runs one query per lane (NnLaneK)
-static NnLaunch prep_nn(qn_ctx* c, int mode /*0 align, 1 fitness*/, float* sqd_out, bool seeded, int tick, int cond) {
+static NnLaunch prep_nn(qn_ctx* c, int mode /*0 align, 1 fitness*/, float* sqd_out, int cond) {
   CloudBuf &S = c->cloud[0], &T = c->cloud[1];
   const uint32_t nb = (S.n + QN_NN_BLOCK / 4 - 1) / (QN_NN_BLOCK / 4);   // grid passes: 16 queries per wave
   const uint32_t nb4 = (S.n + QN_BLOCK / 4 - 1) / (QN_BLOCK / 4);       // list passes: 4 waves per block
   const double thr2 = c->params.max_corr_dist * c->params.max_corr_dist;
   GicpState* st = st_cur(c);
   uint32_t* fbc = &st->fb_count; uint32_t* bgc = &st->big_count;
-  uint32_t* far_stats = (mode == 0 && !seeded && c->count_far_now) ? c->far_stats : nullptr;      // the LAST unseeded pass before the host's look (the clouds are best aligned then)
-  const bool wide = tick <= 2 || (mode == 0 && !seeded);                                              // every unseeded pass of an align leaves thousands of queries to the lists, whatever its index
-  int big_blocks = wide ? c->big_blocks0 : 1024;                                                      // waves with one far query each (idle blocks exit at once)
-  const uint32_t fbb = std::min<uint32_t>(nb4, wide ? (uint32_t)c->fb_blocks0 : 256u);                           // list pass: wave-stride over the leftovers
-  const float r0 = -(tick == 0 && mode == 0 && c->margin_nn_t0 > 0.f ? c->margin_nn_t0 : c->margin_nn);      // negative = in cells
-  const float big_ratio = c->big_ratio;
-  NnOpt opt; opt.clear_ref = (mode == 0 && !seeded && c->clear_far_now) ? c->far_cand_ref : nullptr; opt.cond = cond;
+  uint32_t* far_stats = (mode == 0 && c->count_far_now) ? c->far_stats : nullptr;      // the LAST unseeded pass before the host's look (the clouds are best aligned then)
+  int big_blocks = NN_BIG_BLOCKS;
+  const uint32_t fbb = std::min<uint32_t>(nb4, NN_FB_BLOCKS);
+  NnOpt opt; opt.clear_ref = (mode == 0 && c->clear_far_now) ? c->far_cand_ref : nullptr; opt.cond = cond;
   // far-list grouping (wave_search_far16): with several registrations in flight throughput counts and long far lists are shared (partial overlap: 1110 -> 1330
   // registrations/s; the aligned-scene headline is unchanged); a lone registration wants latency - its lists fit a few rounds of resident waves, one entry per
   // wave starts them all at once, and the leaner kernel keeps 6 blocks per CU (ms_per_align 0.552 against 0.570 / 0.609 with the grouped variant)
-  const bool batch = c->persist_batch_off;
-  opt.group = c->far_group >= 0 ? c->far_group : (batch ? 2048 : 0); opt.group_min = 0;      // (round 4, batched launches: 2048 - up to 16 neighbours per shared scan - measured +3 % over 4096; 8192 and up lose)
+  const bool batch = c->knob.persist_batch_off;
+  opt.group = c->lane.far_group >= 0 ? c->lane.far_group : (batch ? 2048 : 0); opt.group_min = 0;      // (round 4, batched launches: 2048 - up to 16 neighbours per shared scan - measured +3 % over 4096; 8192 and up lose)
   // (a grouped far list is served ceil(length / group) entries per wave: `group` waves are all it can use - same entry -> wave assignment, three quarters fewer empty blocks)
   if (mode == 0 && opt.group > 0) big_blocks = std::min(big_blocks, std::max(64, (opt.group + QN_BLOCK / 64 - 1) / (QN_BLOCK / 64)));
-  opt.probe = (mode == 0 && !seeded) ? c->list_probe : nullptr;
-  opt.fb_small = (mode == 0 && !c->persist_batch_off) ? (uint32_t)c->list_small : 0u;      // (a batch member keeps the 16-per-wave lists: fewer wave-instructions per query, +2 % throughput)
+  opt.probe = mode == 0 ? c->list_probe : nullptr;
+  constexpr uint32_t LIST_SMALL = 6000;      // lone registration: a 16-per-wave leftover list of at most this many entries is served one entry per wave (k_nn_search LIST)
+  opt.fb_small = (mode == 0 && !c->knob.persist_batch_off) ? LIST_SMALL : 0u;      // (a batch member keeps the 16-per-wave lists: fewer wave-instructions per query, +2 % throughput)
   NnOpt opt0; opt0.clear_ref = nullptr; opt0.cond = 0; opt0.group = 0; opt0.group_min = 0; opt0.probe = nullptr; opt0.fb_small = 0;
-  c->clear_far_now = mode == 0 && !seeded ? false : c->clear_far_now;
+  if (mode == 0) c->clear_far_now = false;
   const NnOpt& o = mode == 0 ? opt : opt0;
   NnLaunch L;
   // one query per lane for batch members (throughput: a quarter of the waves, a fifth of the instructions); a LONE registration keeps the cooperative pass - its 1563
   // one-per-lane waves are a single latency-bound round (48 us against 36-41)
-  L.lane = (c->nn_lane > 0 || (c->nn_lane < 0 && c->persist_batch_off)) && mode == 0 && !seeded;
+  L.lane = (c->lane.nn_lane > 0 || (c->lane.nn_lane < 0 && c->knob.persist_batch_off)) && mode == 0;
   L.grid_nb = L.lane ? (S.n + 255u) / 256u : nb; L.list_nb = fbb + (uint32_t)big_blocks; L.group = mode == 0 && opt.group > 0;
-  L.grid = NnSearchArgs{S.grid, T.grid, st, thr2, r0, mode == 0 ? c->nn_rounds : 1, c->corr, sqd_out, c->nn_idx, c->nn_ref, c->fb_list, fbc, c->big_list, bgc, 0, big_ratio, far_stats, o};
-  L.list = NnSearchArgs{S.grid, T.grid, st, thr2, r0, 64, c->corr, sqd_out, c->nn_idx, c->nn_ref, c->fb_list, fbc, c->big_list, bgc, big_blocks, big_ratio, far_stats, o};
+  // (max_rounds: ONE round of the grid pass before a query goes to the lists; the list pass runs until exact)
+  L.grid = NnSearchArgs{S.grid, T.grid, st, thr2, NN_R0, 1, c->corr, sqd_out, c->nn_idx, c->nn_ref, c->fb_list, fbc, c->big_list, bgc, 0, NN_BIG_RATIO, far_stats, o};
+  L.list = NnSearchArgs{S.grid, T.grid, st, thr2, NN_R0, 64, c->corr, sqd_out, c->nn_idx, c->nn_ref, c->fb_list, fbc, c->big_list, bgc, big_blocks, NN_BIG_RATIO, far_stats, o};
   return L;
 }
 #define QN_NN_ARGS(A) A.src, A.tgt, A.st, A.thr2, A.r0, A.max_rounds, A.corr, A.sqd, A.nn_idx, A.nn_ref, A.fb_list, A.fb_count, A.big_list, A.big_count, A.big_blocks, A.big_ratio, A.far_stats, A.opt
-static void enqueue_nn(qn_ctx* c, int mode /*0 align, 1 fitness*/, float* sqd_out, bool seeded, int tick = 0, int cond = 0) {
+static void enqueue_nn(qn_ctx* c, int mode /*0 align, 1 fitness*/, float* sqd_out, int cond = 0) {
   hipStream_t s = c->stream;
-  CloudBuf &S = c->cloud[0], &T = c->cloud[1];
-  const uint32_t nbt = (S.n + QN_BLOCK - 1) / QN_BLOCK;               // tracking: one query per lane
-  const NnLaunch L = prep_nn(c, mode, sqd_out, seeded, tick, cond);
+  const NnLaunch L = prep_nn(c, mode, sqd_out, cond);
   if (L.grid.opt.probe) (void)hipMemsetAsync(c->list_probe, 0, sizeof(unsigned long long) * 4 * 16384, s);
   const NnSearchArgs& G = L.grid; const NnSearchArgs& F = L.list;
   if (mode == 0) {
     { ProfScope ps(c, QN_K_NN_SEARCH);
-      if (seeded) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_nn_track<0>), dim3(nbt), dim3(QN_BLOCK), 0, s, S.grid, T.grid, T.raw, G.st, G.thr2, c->corr, sqd_out, c->nn_idx, c->nn_ref, c->fb_list, G.fb_count, c->big_list, G.big_count);
-      else if (L.lane) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_nn_lane<0>), dim3(L.grid_nb), dim3(256), 0, s, G);
+      if (L.lane) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_nn_lane<0>), dim3(L.grid_nb), dim3(256), 0, s, G);
       else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_nn_search<0, false, QN_NN_BLOCK>), dim3(L.grid_nb), dim3(QN_NN_BLOCK), 0, s, QN_NN_ARGS(G)); }
     { ProfScope ps(c, QN_K_NN_FALLBACK);
       if (L.group) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_nn_search<0, true, QN_BLOCK, true>), dim3(L.list_nb), dim3(QN_BLOCK), 0, s, QN_NN_ARGS(F));
       else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_nn_search<0, true, QN_BLOCK>), dim3(L.list_nb), dim3(QN_BLOCK), 0, s, QN_NN_ARGS(F)); }
   } else {
     ProfScope ps(c, QN_K_FITNESS);
-    if (seeded) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_nn_track<1>), dim3(nbt), dim3(QN_BLOCK), 0, s, S.grid, T.grid, T.raw, G.st, G.thr2, c->corr, sqd_out, c->nn_idx, c->nn_ref, c->fb_list, G.fb_count, c->big_list, G.big_count);
-    else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_nn_search<1, false, QN_NN_BLOCK>), dim3(L.grid_nb), dim3(QN_NN_BLOCK), 0, s, QN_NN_ARGS(G));
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_nn_search<1, false, QN_NN_BLOCK>), dim3(L.grid_nb), dim3(QN_NN_BLOCK), 0, s, QN_NN_ARGS(G));
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_nn_search<1, true, QN_BLOCK>), dim3(L.list_nb), dim3(QN_BLOCK), 0, s, QN_NN_ARGS(F));
   }
 }
 // debug knob "verify_track": a fresh, unseeded search of the current pose into scratch buffers, compared query by query with what
 // the tracked / bound-pruned pass just produced (tests/test_gpu_adversarial.py)
-static void enqueue_verify(qn_ctx* c, bool fused) {
+static void enqueue_verify(qn_ctx* c) {
   hipStream_t s = c->stream;
   CloudBuf &S = c->cloud[0], &T = c->cloud[1];
   const uint32_t nb = (S.n + QN_NN_BLOCK / 4 - 1) / (QN_NN_BLOCK / 4), nb4 = (S.n + QN_BLOCK / 4 - 1) / (QN_BLOCK / 4);
   const double thr2 = c->params.max_corr_dist * c->params.max_corr_dist;
   GicpState* st = st_cur(c);
   uint32_t* fbc = &st->fb_count; uint32_t* bgc = &st->big_count;
-  const float r0 = -c->margin_nn;
   hipLaunchKernelGGL(k_reset_lists, dim3(1), dim3(64), 0, s, st);
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_nn_search<0, false, QN_NN_BLOCK>), dim3(nb), dim3(QN_NN_BLOCK), 0, s, S.grid, T.grid, st, thr2, r0, c->nn_rounds, c->v_corr, c->v_sqd, c->v_nn_idx, c->v_nn_ref, c->fb_list, fbc, c->big_list, bgc, 0, c->big_ratio, (uint32_t*)nullptr, NnOpt{nullptr, 0, 0, 0, nullptr, 0});
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_nn_search<0, true, QN_BLOCK>), dim3(std::min<uint32_t>(nb4, 512) + 4096), dim3(QN_BLOCK), 0, s, S.grid, T.grid, st, thr2, r0, 64, c->v_corr, c->v_sqd, c->v_nn_idx, c->v_nn_ref, c->fb_list, fbc, c->big_list, bgc, 4096, c->big_ratio, (uint32_t*)nullptr, NnOpt{nullptr, 0, 0, 0, nullptr, 0});
-  hipLaunchKernelGGL(k_verify_nn, dim3((S.n + 255) / 256), dim3(256), 0, s, S.n, st, c->nn_idx, c->v_nn_idx, fused ? (const float*)nullptr : c->sqd, c->v_sqd, c->corr, c->v_corr, c->v_counters);
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_nn_search<0, false, QN_NN_BLOCK>), dim3(nb), dim3(QN_NN_BLOCK), 0, s, S.grid, T.grid, st, thr2, NN_R0, 1, c->v_corr, c->v_sqd, c->v_nn_idx, c->v_nn_ref, c->fb_list, fbc, c->big_list, bgc, 0, NN_BIG_RATIO, (uint32_t*)nullptr, NnOpt{nullptr, 0, 0, 0, nullptr, 0});
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_nn_search<0, true, QN_BLOCK>), dim3(std::min<uint32_t>(nb4, NN_FB_BLOCKS) + NN_BIG_BLOCKS), dim3(QN_BLOCK), 0, s, S.grid, T.grid, st, thr2, NN_R0, 64, c->v_corr, c->v_sqd, c->v_nn_idx, c->v_nn_ref, c->fb_list, fbc, c->big_list, bgc, NN_BIG_BLOCKS, NN_BIG_RATIO, (uint32_t*)nullptr, NnOpt{nullptr, 0, 0, 0, nullptr, 0});
+  hipLaunchKernelGGL(k_verify_nn, dim3((S.n + 255) / 256), dim3(256), 0, s, S.n, st, c->nn_idx, c->v_nn_idx, (const float*)nullptr, c->v_sqd, c->corr, c->v_corr, c->v_counters);
   hipLaunchKernelGGL(k_reset_lists, dim3(1), dim3(64), 0, s, st);
 }
 static uint32_t acc_blocks(const qn_ctx* c) { return std::min<uint32_t>((c->cloud[0].n + QN_BLOCK - 1) / QN_BLOCK, QN_ACC_MAX_BLOCKS); }
-static uint32_t tick_ppt(const qn_ctx* c) { return std::max<uint32_t>(c->tick_ppt_min, (c->cloud[0].n + c->tick_tb * QN_ACC_MAX_BLOCKS - 1) / (c->tick_tb * QN_ACC_MAX_BLOCKS)); }
-static uint32_t tick_rows(const qn_ctx* c) { const uint32_t per = c->tick_tb * tick_ppt(c); return (c->cloud[0].n + per - 1) / per; }      // partial rows of a tick: one per tick_tb x ppt source points
-static uint32_t tick_rpb(const qn_ctx* c) { return c->persist_batch_off ? std::max(1u, c->tick_rpb) : 1u; }      // rows a block forms: batch members take fewer, longer blocks (the rows - every bit downstream - are the same)
+constexpr uint32_t TICK_TB = 512;      // threads per block of k_tick and of k_solve (both run the same row reduction), and of the persistent kernel that takes over from them
+static_assert(TICK_TB == QN_PERSIST_TB, "k_align_persist reads the tracking records k_tick leaves: one block shape");
+static uint32_t tick_ppt(const qn_ctx* c) { return std::max<uint32_t>(1u, (c->cloud[0].n + TICK_TB * QN_ACC_MAX_BLOCKS - 1) / (TICK_TB * QN_ACC_MAX_BLOCKS)); }      // source points per lane
+static uint32_t tick_rows(const qn_ctx* c) { const uint32_t per = TICK_TB * tick_ppt(c); return (c->cloud[0].n + per - 1) / per; }      // partial rows of a tick: one per TICK_TB x ppt source points
+static uint32_t tick_rpb(const qn_ctx* c) { return c->knob.persist_batch_off ? std::max(1u, c->lane.tick_rpb) : 1u; }      // rows a block forms: batch members take fewer, longer blocks (the rows - every bit downstream - are the same)
 static uint32_t tick_blocks(const qn_ctx* c) { const uint32_t rpb = tick_rpb(c); return (tick_rows(c) + rpb - 1) / rpb; }
 // The controller step of a producer launch (controller_tail): generation g -> g + 1 inside the launch that wrote the rows.
 static TailArgs tail_args(qn_ctx* c, int enabled, int rows, const LookArgs* look = nullptr) {
@@ -600,8 +600,7 @@ static SolveArgs prep_solve(qn_ctx* c, int mode, int will_produce, const LookArg
 static void enqueue_solve(qn_ctx* c, int mode, int will_produce, const LookArgs* look = nullptr) {
   ProfScope ps(c, QN_K_SOLVE);
   const SolveArgs a = prep_solve(c, mode, will_produce, look);
-  if (c->tick_tb == 256) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_solve<256>), dim3(1), dim3(256), 0, c->stream, a.st_in, a.st_out, a.partials, a.rows, a.cfg, a.trace, a.mode, a.will_produce, a.look);
-  else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_solve<512>), dim3(1), dim3(512), 0, c->stream, a.st_in, a.st_out, a.partials, a.rows, a.cfg, a.trace, a.mode, a.will_produce, a.look);
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_solve<TICK_TB>), dim3(1), dim3(TICK_TB), 0, c->stream, a.st_in, a.st_out, a.partials, a.rows, a.cfg, a.trace, a.mode, a.will_produce, a.look);
 }
 // One "tick" of the device-side state machine = [controller step on the previous tick's partial rows] + [body under the new state].
 // Tracked regime: ONE kernel (k_tick: controller in the prologue of every block, tracked NN + accumulation, LM trial passes included).
@@ -612,7 +611,7 @@ static TickArgs tick_args(qn_ctx* c, int mode = 0) {
   a.src = S.grid; a.tgt = T.grid; a.part_out = part_cur(c);
   a.thr2 = c->params.max_corr_dist * c->params.max_corr_dist;
   a.nn_idx = c->nn_idx; a.nn_ref = c->nn_ref; a.nrm_s = c->nrm_s_sorted; a.tgt_rec = c->tgt_rec; a.ppt = tick_ppt(c); a.rpb = tick_rpb(c); a.rows = tick_rows(c);
-  a.far_mode = c->far_enabled ? c->far_mode : 0; a.tgt_raw = T.raw; a.cand = c->far_cand; a.cand_ref = c->far_cand_ref; a.cand_b = c->far_cand_b; a.far_req = c->far_req; a.far_stats = c->far_stats;
+  a.far_mode = c->knob.far_enabled ? c->far_mode : 0; a.tgt_raw = T.raw; a.cand = c->far_cand; a.cand_ref = c->far_cand_ref; a.cand_b = c->far_cand_b; a.far_req = c->far_req; a.far_stats = c->far_stats;
   a.tail = tail_args(c, (mode == 0 && a.far_mode != 1) ? 1 : 0, (int)tick_rows(c));
   a.aligned = c->aligned; a.fit_psum = c->fit_psum; a.fit_pcnt = c->fit_pcnt;
   a.clk = c->clk_probe ? c->clk_probe + 8 * (c->clk_n++ % 256) : nullptr; a.clk_blk = c->clk_probe ? c->clk_probe + 8 * 256 : nullptr;
@@ -622,7 +621,7 @@ static FarArgs far_args(qn_ctx* c) {         // k_far behind the tick that just 
   CloudBuf &S = c->cloud[0], &T = c->cloud[1];
   FarArgs f;
   f.src = S.grid; f.tgt = T.grid; f.st = st_cur(c); f.thr2 = c->params.max_corr_dist * c->params.max_corr_dist; f.nn_idx = c->nn_idx; f.nn_ref = c->nn_ref; f.nrm_s = c->nrm_s_sorted; f.tgt_rec = c->tgt_rec; f.tgt_raw = T.raw;
-  f.cand = c->far_cand; f.cand_ref = c->far_cand_ref; f.cand_b = c->far_cand_b; f.far_req = c->far_req; f.far_rows = c->far_rows; f.far_stats = c->far_stats; f.ranked_max = c->far_ranked ? (uint32_t)QN_FAR_WORDS : 0u;
+  f.cand = c->far_cand; f.cand_ref = c->far_cand_ref; f.cand_b = c->far_cand_b; f.far_req = c->far_req; f.far_rows = c->far_rows; f.far_stats = c->far_stats; f.ranked_max = c->lane.far_ranked ? (uint32_t)QN_FAR_WORDS : 0u;
   return f;
 }
 static FarReduceK::Args far_reduce_args(qn_ctx* c) {      // behind k_far: the side table -> one more row, then the controller step the tick left to it
@@ -631,12 +630,9 @@ static FarReduceK::Args far_reduce_args(qn_ctx* c) {      // behind k_far: the s
 static void enqueue_tick_fused(qn_ctx* c) {
   TickArgs a = tick_args(c);
   { ProfScope ps(c, QN_K_GN_TICK_FUSED);
-    const dim3 gr(tick_blocks(c)), bl(c->tick_tb);
-#define QN_TICK_LAUNCH(TB, OCC, PR) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tick<TB, OCC, 0, PR>), gr, bl, 0, c->stream, a)
-    if (a.clk) { if (c->tick_tb == 256) QN_TICK_LAUNCH(256, 4, true); else QN_TICK_LAUNCH(512, 4, true); }      // developer probe variant
-    else if (c->tick_tb == 256) { if (c->tick_occ >= 4) QN_TICK_LAUNCH(256, 4, false); else if (c->tick_occ == 3) QN_TICK_LAUNCH(256, 3, false); else QN_TICK_LAUNCH(256, 2, false); }
-    else { if (c->tick_occ >= 4) QN_TICK_LAUNCH(512, 4, false); else if (c->tick_occ == 3) QN_TICK_LAUNCH(512, 3, false); else QN_TICK_LAUNCH(512, 2, false); }
-#undef QN_TICK_LAUNCH
+    const dim3 gr(tick_blocks(c)), bl(TICK_TB);
+    if (a.clk) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tick<TICK_TB, 4, 0, true>), gr, bl, 0, c->stream, a);      // developer probe variant
+    else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tick<TICK_TB, 4, 0, false>), gr, bl, 0, c->stream, a);           // (4 waves per SIMD = 128 VGPRs: other streams' kernels keep half of the register file)
   }
   if (a.far_mode == 1) {                       // the tick's refresh requests, chip-wide, one query per wave; its row follows the tick's, then the controller step
     const FarArgs f = far_args(c);
@@ -644,34 +640,29 @@ static void enqueue_tick_fused(qn_ctx* c) {
       hipLaunchKernelGGL(k_far, dim3(QN_FAR_BLOCKS), dim3(QN_FAR_THREADS), 0, c->stream, f);
       hipLaunchKernelGGL(k_far_reduce, dim3(1), dim3(QN_FAR_BLOCKS), 0, c->stream, far_reduce_args(c)); }
   }
-  if (c->verify_track) enqueue_verify(c, true);         // (before the generation advances: st_cur is still the state - the pose - the tick's body used)
+  if (c->knob.verify_track) enqueue_verify(c);         // (before the generation advances: st_cur is still the state - the pose - the tick's body used)
   c->gen++; c->part_rows = -1;
 }
 // Unseeded regime (the first outer iterations, while the pose still moves by more than a few cells): controller launch, grid search +
 // list passes, accumulation.  `first`: the very first tick of an align has nothing to consume.
 static void enqueue_tick(qn_ctx* c, bool seeded, int tick_no, const LookArgs* look = nullptr) {
-  const int per_outer = c->params.optimizer == QN_OPT_LM ? 2 : 1, tick = tick_no / per_outer;      // tick = outer iteration (list-pass grid sizes)
-  if (tick_no < c->unseeded_until) seeded = false;
-  if (seeded && c->fused_ticks) { enqueue_tick_fused(c); return; }
-  enqueue_nn(c, 0, c->sqd, seeded, tick);
-  if (c->verify_track && seeded) enqueue_verify(c, false);
+  if (seeded && tick_no >= c->unseeded_until) { enqueue_tick_fused(c); return; }
+  enqueue_nn(c, 0, c->sqd);
   enqueue_accumulate(c, 0, true, look);                              // + the controller step (and, behind the chunk's last unseeded tick of a lone forced run, the hand-over decision)
 }
 // The closing pass of align(): the last controller step + (once the state machine is done) fitness sweep + output cloud in ONE launch
 // (k_tick<.., 1>) and the result block (k_finalize_fit).  `tracked`: the neighbours of the last tick seed the sweep; without them
-// (no iteration ran, or the fused path is switched off) the unfused sequence runs: controller, search + list pass, two reductions, transform.
+// (no iteration ran) the unfused sequence runs: search + list pass, two reductions, transform.
 static void enqueue_epilogue(qn_ctx* c, double max_range, bool tracked) {
-  if (tracked && c->fused_ticks && c->fused_final) {
+  if (tracked) {
     TickArgs a = tick_args(c, 1);
     { ProfScope ps(c, QN_K_FITNESS);
-      const dim3 gr(tick_blocks(c)), bl(c->tick_tb);
-      if (c->tick_tb == 256) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tick<256, 4, 1, false>), gr, bl, 0, c->stream, a);
-      else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tick<512, 4, 1, false>), gr, bl, 0, c->stream, a); }
+      hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tick<TICK_TB, 4, 1, false>), dim3(tick_blocks(c)), dim3(TICK_TB), 0, c->stream, a); }
     hipLaunchKernelGGL(k_finalize_fit, dim3(1), dim3(64), 0, c->stream, st_cur(c), c->result_host, c->far_stats, c->fit_psum, c->fit_pcnt, (int)tick_rows(c));
     return;
   }
   GicpState* st = st_cur(c);                                    // (already stepped by the controller tail of the chunk's last tick)
-  enqueue_nn(c, 1, c->sqd_fit, tracked, 1);
+  enqueue_nn(c, 1, c->sqd_fit);
   { ProfScope ps(c, QN_K_FITNESS);
     hipLaunchKernelGGL(k_fitness_partial, dim3(QN_FIT_BLOCKS), dim3(QN_BLOCK), 0, c->stream, c->sqd_fit, c->cloud[0].n, max_range, st, c->fit_psum, c->fit_pcnt, 1);
     hipLaunchKernelGGL(k_fitness_final, dim3(1), dim3(QN_FIT_BLOCKS), 0, c->stream, c->fit_psum, c->fit_pcnt, st, 1); }
@@ -688,8 +679,8 @@ static uint32_t persist_ppt(const qn_ctx* c) { const uint32_t cap = QN_PERSIST_T
 // (clouds beyond QN_PERSIST_TB x QN_PERSIST_MAX_BLOCKS points keep the chain: with more than one point per lane the persistent kernel's tracking records would live in memory, where
 //  its top-2 form - nn_ref.w bounds the THIRD-nearest point - is not what k_tick reads; persist_fits: the launch's nblk + 1 blocks are all resident on this device, measured at context creation)
 static bool persist_usable(const qn_ctx* c, bool alone) {
-  return c->persist && c->persist_fits && persist_ppt(c) == 1 && !c->persist_batch_off && alone && c->fused_ticks && c->fused_final && (!c->prof_on || c->prof_persist) && !c->verify_track && !c->clk_probe && c->tick_tb == QN_PERSIST_TB &&
-         (!c->far_enabled || c->far_mode == 2) && c->pg_rows != nullptr;
+  return c->knob.persist && c->persist_fits && persist_ppt(c) == 1 && !c->knob.persist_batch_off && alone && (!c->prof_on || c->knob.prof_persist) && !c->knob.verify_track && !c->clk_probe &&
+         (!c->knob.far_enabled || c->far_mode == 2) && c->pg_rows != nullptr;
 }
 // A persistent launch that gave up (bounded spins: the reducer or a worker waited longer than `persist_timeout` - another tenant holds CUs, a partitioned device ...) leaves
 // its row buffers in an unknown state and tracking records in its own top-2 form: re-arm the buffers; the caller then runs the whole align again on the k_tick chain
@@ -709,7 +700,7 @@ static int launch_persist(qn_ctx* c, uint32_t max_ticks, int cond = 0) {
   A.t = tick_args(c);                                                // (tail.st_in: the state the chain left, already stepped; tail.st_out: where the reducer leaves the final state)
   A.cond = cond; A.status_host = c->pg_status_host;
   A.t.ppt = persist_ppt(c); A.t.rpb = 1; A.t.rows = 0; A.t.clk = nullptr; A.t.clk_blk = nullptr;
-  A.t.far_mode = c->far_enabled ? 2 : 0;
+  A.t.far_mode = c->knob.far_enabled ? 2 : 0;
   const uint32_t per = QN_PERSIST_TB * A.t.ppt;
   A.nblk = (c->cloud[0].n + per - 1) / per;
   if (c->pg_epoch > 0xF0000000u) {                                   // epochs must never repeat within the life of the granule buffers
@@ -719,7 +710,7 @@ static int launch_persist(qn_ctx* c, uint32_t max_ticks, int cond = 0) {
   }
   A.rows_g = c->pg_rows; A.bc_g = c->pg_bc; A.fit_g = c->pg_fit; A.status = c->pg_status; A.result = c->result_host;
   A.epoch0 = c->pg_epoch; A.max_ticks = max_ticks; c->pg_epoch += max_ticks + 8;
-  A.timeout = c->persist_timeout;                                    // per spin, 100 MHz wall clock; default 0.25 s: three orders of magnitude above any legitimate wait
+  A.timeout = c->knob.persist_timeout;                                    // per spin, 100 MHz wall clock; default 0.25 s: three orders of magnitude above any legitimate wait
   c->pg_status_host[0] = 0xffffffffu; c->pg_status_host[1] = 0;      // (the reducer overwrites it when it leaves)
   { ProfScope ps(c, QN_K_ALIGN_PERSIST);
     A.clk = c->pg_clk;
@@ -736,9 +727,17 @@ static int launch_persist(qn_ctx* c, uint32_t max_ticks, int cond = 0) {
 // initial misalignment of a few degrees more than the bench's default turns one 25 us tick launch into 200-1800 us, and a launch ends with its slowest lane), while the dedicated
 // unseeded search costs the same whatever the step was.  Searches are exact in both regimes; the rule only decides which kernels run, and it reads nothing but the controller's own
 // step and the grids' numbers - the classic batch-member path (gicp_align) and the lanes (batch_register) take the same decision, so their records stay bit-identical.
+// up to UNSEEDED_CAP unseeded outer iterations per align: a tracked tick behind a step of metres re-searches every neighbourhood cooperatively inside the tick (100-1800 us
+// per 4-lane launch, and the launch ends with its slowest lane); the dedicated unseeded search does not care (round 6: an 8-pair call of the hardest re-pose variant 5.64 -> 3.2 ms)
+constexpr int UNSEEDED_CAP = 10;
+constexpr int TRACK_FROM_MAX = 3;        // the fixed schedule hands over to the tracked tick at outer iteration min(track_from_tick, 3): k_tick is the only tracked form
+static_assert(UNSEEDED_CAP > TRACK_FROM_MAX, "the adaptive extension needs room beyond the fixed schedule");
+static int fixed_unseeded_iterations(const qn_ctx* c) { return std::max(1, std::min(c->lane.track_from_tick, TRACK_FROM_MAX)); }
+constexpr int FAR_CHUNK = 2;             // tracked ticks of a forced run that keep the far-query refresh kernel behind them before the host looks again: the refresh regime is over after two ticks on the 80 %-overlap pairs
+constexpr int TICKS_PER_CHUNK = 8;       // unforced runs: ticks between two host looks (first chunk; half of it afterwards - convergence is usually near, ticks past it are wasted launches)
 static bool unseeded_goes_on(const qn_ctx* c, int tick_no, int per_outer, int ticks_left, bool lone = false) {      // lone: a registration on the adaptive lone path whose persistent launch declined on the second look (look_again)
-  if ((!c->persist_batch_off && !lone) || !c->far_enabled || !c->fused_ticks) return false;
-  if (tick_no != c->unseeded_until || tick_no + per_outer > c->unseeded_cap * per_outer || ticks_left < per_outer) return false;
+  if ((!c->knob.persist_batch_off && !lone) || !c->knob.far_enabled) return false;
+  if (tick_no != c->unseeded_until || tick_no + per_outer > UNSEEDED_CAP * per_outer || ticks_left < per_outer) return false;
   const qn::ResultBlock* rb = c->result_host;
   if (rb->phase == 2) return false;
   const GridDims& sg = *c->cloud[0].dims_host;                       // (valid: the stream has been synchronised since the grids were built)
@@ -791,15 +790,15 @@ static int gicp_align(qn_ctx* c, const float guess[16], qn_gicp_result* out, boo
   // streams fill the chip; measured best for throughput).
   // (only runs that are known to be long pay for the look - a forced iteration count: with the real stopping rule the reference's operating point converges in
   //  3-7 iterations, and the extra round trip cost it 0.03-0.07 ms; knob single_from_tick = 0: the fixed hand-over everywhere; an explicitly earlier one wins too)
-  const bool adaptive = (!c->persist_batch_off || (c->device_look && c->batch_look)) && c->fused_ticks && c->far_enabled && c->single_from_tick > 0 && p.force_iterations > 0 && p.optimizer == QN_OPT_GN && maxit >= 8 &&
-                        std::min(c->track_from_tick, c->fused_from_tick) > c->single_from_tick;
-  const int fixed_unseeded = std::max(1, std::min(c->track_from_tick, c->fused_from_tick)) * per_outer;
-  const int unseeded = adaptive ? std::max(1, std::min(fixed_unseeded / per_outer, c->single_from_tick)) * per_outer : fixed_unseeded;
+  const bool adaptive = !c->knob.persist_batch_off && c->knob.far_enabled && c->knob.single_from_tick > 0 && p.force_iterations > 0 && p.optimizer == QN_OPT_GN && maxit >= 8 &&
+                        fixed_unseeded_iterations(c) > c->knob.single_from_tick;
+  const int fixed_unseeded = fixed_unseeded_iterations(c) * per_outer;
+  const int unseeded = adaptive ? std::max(1, std::min(fixed_unseeded / per_outer, c->knob.single_from_tick)) * per_outer : fixed_unseeded;
   // The number of ticks is known in advance only for forced Gauss-Newton runs (one tick per iteration).  A forced LM run needs one more tick
   // per rejected trial step, so it is driven like an unforced one: chunks until the device reports `done`, bounded by `budget`.
   const bool exact_ticks = p.force_iterations > 0 && p.optimizer == QN_OPT_GN;
   int ticks_left = exact_ticks ? maxit : 1 << 30;
-  int chunk = c->far_enabled ? std::min(unseeded, ticks_left) : (exact_ticks ? ticks_left : c->ticks_per_chunk);
+  int chunk = c->knob.far_enabled ? std::min(unseeded, ticks_left) : (exact_ticks ? ticks_left : TICKS_PER_CHUNK);
   bool first_chunk = true;
   long budget = (long)maxit * (p.optimizer == QN_OPT_LM ? (p.lm_max_iterations + 1) : 1) + 2;
   c->result_host->phase = 0;
@@ -811,8 +810,8 @@ static int gicp_align(qn_ctx* c, const float guess[16], qn_gicp_result* out, boo
     // A registration that is alone on the GPU takes the look ON THE DEVICE (look_decide, at the end of that controller tail): the conditional third unseeded iteration and
     // the persistent launch are enqueued behind it and read its flags - no host round trip between the unseeded ticks and the tracked regime (it cost 15-30 us of a
     // 0.6 ms align).  If the flags say "not the persistent kernel" (many far neighbours: the k_far regime), that launch returns at once and the chain goes on from the host below.
-    const bool dev_look = look && c->device_look && chunk > 0;
-    const bool with_persist = dev_look && persist_usable(c, alone);   // (a batch member takes the same look - its third unseeded iteration is conditional too - and carries on with the chain)
+    const bool dev_look = look && c->knob.device_look && chunk > 0;
+    const bool with_persist = dev_look && persist_usable(c, alone);
     LookArgs la; memset(&la, 0, sizeof(la));
     if (dev_look) {
       la.out = c->result_host; la.far_stats = c->far_stats; la.sdims = c->cloud[0].dims; la.tdims = c->cloud[1].dims; la.enabled = 1;
@@ -827,9 +826,9 @@ static int gicp_align(qn_ctx* c, const float guess[16], qn_gicp_result* out, boo
     bool declined = false;
     if (dev_look) {
       c->unseeded_until = tick_no + 1;
-      enqueue_nn(c, 0, c->sqd, false, tick_no / per_outer, QN_LOOK_EXTRA);
+      enqueue_nn(c, 0, c->sqd, QN_LOOK_EXTRA);
       LookArgs la2 = la; la2.enabled = 2; la2.allow_extra = 0;      // the second look, at the tail of the extra iteration: the persistent launch goes ahead only if THAT step is small too (look_again)
-      enqueue_accumulate(c, QN_LOOK_EXTRA, true, c->unseeded_cap > fixed_unseeded / per_outer ? &la2 : nullptr);      // (flag not set: the launch hands the state on unchanged)
+      enqueue_accumulate(c, QN_LOOK_EXTRA, true, &la2);      // (flag not set: the launch hands the state on unchanged)
       if (with_persist && (rc = launch_persist(c, (uint32_t)(budget - chunk) + 2u, QN_LOOK_GO)) != QN_OK) return rc;
       HIPCHK(c, hipGetLastError());
       HIPCHK(c, hipStreamSynchronize(s));
@@ -863,13 +862,13 @@ static int gicp_align(qn_ctx* c, const float guess[16], qn_gicp_result* out, boo
       c->last_error = "align: closing pass did not complete"; return QN_ERR_HIP;
     }
     // far queries: keep the refresh kernel in the chain only while ticks actually ask for refreshes (a launch costs ~4 us per tick)
-    if (c->far_enabled) {
+    if (c->knob.far_enabled) {
       const qn::ResultBlock* rb = c->result_host;
       if (first_chunk) c->far_mode = rb->far_queries * 16u > c->cloud[0].n ? 1 : 2;      // more than ~6 % of the source has a far neighbour
       else c->far_mode = (c->far_mode == 1 ? rb->far_requests : rb->far_misses / (uint32_t)std::max(1, chunk)) > 256u ? 1 : 2;   // stray misses are cheaper inside k_tick
     }
-    if (!exact_ticks) chunk = first_chunk ? c->ticks_per_chunk : std::max(2 * per_outer, c->ticks_per_chunk / 2);   // convergence is usually near after the first chunks: ticks past it are wasted launches
-    else chunk = c->far_mode == 1 ? std::min(ticks_left, c->far_chunk) : ticks_left;      // the refresh regime is needed for the first few tracked ticks only: an empty k_far + k_far_reduce behind every later tick cost 14 us each (80 %-overlap pairs: 1384 -> 1429 registrations/s with 4 instead of 8)
+    if (!exact_ticks) chunk = first_chunk ? TICKS_PER_CHUNK : std::max(2 * per_outer, TICKS_PER_CHUNK / 2);   // convergence is usually near after the first chunks: ticks past it are wasted launches
+    else chunk = c->far_mode == 1 ? std::min(ticks_left, FAR_CHUNK) : ticks_left;      // the refresh regime is needed for the first few tracked ticks only: an empty k_far + k_far_reduce behind every later tick cost 14 us each (80 %-overlap pairs: 1384 -> 1429 registrations/s with 4 instead of 8)
     if (budget <= 0) { c->last_error = "align: device state machine did not terminate"; return QN_ERR_HIP; }
     if (first_chunk && (!adaptive || declined || extending) && unseeded_goes_on(c, tick_no, per_outer, ticks_left, adaptive)) {
       // a batch member - or a lone registration whose persistent launch declined on its second look - whose pose still moves by more than a fraction of a cell: one more
@@ -890,14 +889,11 @@ static int gicp_align(qn_ctx* c, const float guess[16], qn_gicp_result* out, boo
       extra = std::min(extra * per_outer, std::max(0, std::min(ticks_left - 1, per_outer)));
       if (!(moved == moved)) extra = 0;
       c->last_extra_unseeded = extra;
-      if (extra > 0 && c->unseeded_cap > fixed_unseeded / per_outer) {      // the extra iteration as a chunk of its own with a look behind it: the same decisions as the device route (look_again), one iteration per look
+      if (extra > 0) {      // the extra iteration as a chunk of its own with a look behind it: the same decisions as the device route (look_again), one iteration per look
         c->unseeded_until = tick_no + extra; chunk = extra; extending = true;
         continue;
       }
-      c->unseeded_until = tick_no + extra;
-      for (int t = 0; t < extra; t++) { enqueue_tick(c, seeded, tick_no); tick_no++; }
-      budget -= extra; ticks_left -= extra;
-      if (exact_ticks) chunk = c->far_mode == 1 ? std::min(ticks_left, c->far_chunk) : ticks_left;
+      c->unseeded_until = tick_no;
     }
     if (tick_no > 0 && persist_usable(c, alone)) {          // everything that is left - ticks, closing pass, result - in ONE persistent launch (first chunk end, or once the far-query refreshes have died down)
       if ((rc = launch_persist(c, (uint32_t)budget + 2u)) != QN_OK) return rc;
@@ -921,7 +917,7 @@ extern "C" int qn_gicp_fitness(qn_ctx* c, double max_range, double* score) {
   int rc = ready(c); if (rc != QN_OK) return rc;
   if (!score) return QN_ERR_INVALID_ARG;
   HIPCHK(c, hipSetDevice(c->device));
-  enqueue_nn(c, 1, c->sqd_fit, false);
+  enqueue_nn(c, 1, c->sqd_fit);
   hipLaunchKernelGGL(k_fitness_partial, dim3(QN_FIT_BLOCKS), dim3(QN_BLOCK), 0, c->stream, c->sqd_fit, c->cloud[0].n, max_range, st_cur(c), c->fit_psum, c->fit_pcnt, 1);
   hipLaunchKernelGGL(k_fitness_final, dim3(1), dim3(QN_FIT_BLOCKS), 0, c->stream, c->fit_psum, c->fit_pcnt, st_cur(c), 1);
   hipLaunchKernelGGL(k_finalize, dim3(1), dim3(64), 0, c->stream, st_cur(c), c->result_host, (uint32_t*)nullptr);
@@ -978,7 +974,7 @@ extern "C" int qn_gicp_get_lane_trace(qn_ctx* c, uint32_t lane, qn_iter_trace* o
 // 2 = source on the device as packed float4 (the coarse-aligned cloud of coarseToFineAlignment), target on the host,
 // 3 = like 2 with the target on the device too.
 static int icp_alignment(qn_ctx* c, const float* src, uint32_t ns, const float* dst, uint32_t nt, uint32_t stride, double thr,
-                         qn_gicp_result* out, int* valid, int where, bool reuse_source = false, bool target_ready = false, const float* guess = nullptr) {
+                         qn_gicp_result* out, int* valid, int where, bool reuse_source = false, const float* guess = nullptr) {
   if (!c || !out || !valid) return QN_ERR_INVALID_ARG;
   *valid = 0;
   memset(out, 0, sizeof(*out)); out->fitness = DBL_MAX;
@@ -987,20 +983,16 @@ static int icp_alignment(qn_ctx* c, const float* src, uint32_t ns, const float* 
   // reuse_source: the context still holds this source cloud's grid and covariances (the candidates of ONE loop-closure query share their
   // source; loop_closure.cpp:116-123 rebuilds it for every call because the reference only ever tries one candidate)
   const bool need_source = !(reuse_source && c->cloud[0].has_grid && c->cloud[0].has_cov && c->cloud[0].n == ns);
-  // target_ready: coarseToFineAlignment prepared the target (grid + covariances, :122-123) while Quatro's matching ran - it depends on nothing Quatro computes (coarse_to_fine)
-  const bool need_target = !(target_ready && c->cloud[1].has_grid && c->cloud[1].has_cov && c->cloud[1].n == nt);
   // tgt_early: the target's upload + grid build (second stream, own scratch) is ENQUEUED right behind the source's, before the source's k-NN launches: the host needs
   // ~50 us to submit those, and the second stream used to sit empty that long (lone registration: the target chain started 77 us into the call).  Same kernels, same data.
-  const bool early = c->tgt_early && need_source && need_target;
+  const bool early = c->knob.tgt_early && need_source;
   if (need_source) {
     if ((rc = set_cloud(c, QN_SOURCE, src, ns, where >= 2 ? 16 : stride, where != 0)) != QN_OK) return rc;   // :120
     if (early && (rc = set_cloud(c, QN_TARGET, dst, nt, stride, where == 1 || where == 3)) != QN_OK) return rc;     // :122, early
     if ((rc = qn_gicp_compute_covariances(c, QN_SOURCE)) != QN_OK) return rc;         // :121
   }
-  if (need_target) {
-    if (!early && (rc = set_cloud(c, QN_TARGET, dst, nt, stride, where == 1 || where == 3)) != QN_OK) return rc;     // :122 (on the second stream: see TargetScope)
-    if ((rc = qn_gicp_compute_covariances(c, QN_TARGET)) != QN_OK) return rc;         // :123
-  }
+  if (!early && (rc = set_cloud(c, QN_TARGET, dst, nt, stride, where == 1 || where == 3)) != QN_OK) return rc;     // :122 (on the second stream: see TargetScope)
+  if ((rc = qn_gicp_compute_covariances(c, QN_TARGET)) != QN_OK) return rc;         // :123
   if ((rc = qn_gicp_align(c, guess, out)) != QN_OK) return rc;                      // :124 (align(output, guess) when a guess is given), :127
   *valid = (out->converged && out->fitness < thr) ? 1 : 0;                          // :129
   return QN_OK;
@@ -1038,9 +1030,9 @@ extern "C" int qn_icp_alignment_batch(qn_ctx* const* ctxs, uint32_t n_ctx, const
   std::vector<char> saved_p(n_ctx);
   std::vector<char> use_lanes(n_ctx);
   for (uint32_t i = 0; i < n_ctx; i++) {
-    saved[i] = ctxs[i]->pair_pipeline; saved_p[i] = ctxs[i]->persist_batch_off;
+    saved[i] = ctxs[i]->knob.pair_pipeline; saved_p[i] = ctxs[i]->knob.persist_batch_off;
     use_lanes[i] = n_pairs > 1 && batch_supported(ctxs[i]) && batch_ensure_lanes(ctxs[i]) == QN_OK;
-    if (n_ctx > 1 || use_lanes[i]) { ctxs[i]->pair_pipeline = false; ctxs[i]->persist_batch_off = true; }
+    if (n_ctx > 1 || use_lanes[i]) { ctxs[i]->knob.pair_pipeline = false; ctxs[i]->knob.persist_batch_off = true; }
   }
   auto worker = [&](qn_ctx* c, bool lanes) {
     if (lanes) {
@@ -1059,7 +1051,7 @@ extern "C" int qn_icp_alignment_batch(qn_ctx* const* ctxs, uint32_t n_ctx, const
           if (rem > n_ctx * B) m = B;
           else {                                                        // the last round: what is left, in n_ctx equal shares (fixed by the first context that gets here)
             uint32_t q = final_share.load();
-            if (q == 0) { uint32_t want = std::min<uint32_t>(B, std::max<uint32_t>((uint32_t)std::max(1, ctxs[0]->batch_min_share), (rem + n_ctx - 1) / n_ctx)); if (final_share.compare_exchange_strong(q, want)) q = want; }
+            if (q == 0) { uint32_t want = std::min<uint32_t>(B, std::max<uint32_t>((uint32_t)std::max(1, ctxs[0]->knob.batch_min_share), (rem + n_ctx - 1) / n_ctx)); if (final_share.compare_exchange_strong(q, want)) q = want; }
             m = std::min(q, rem);
           }
           m = std::min(m, B);                                           // (the share was fixed by whichever context got there first, with ITS lane count: never more than this context's - ADVICE r5)
@@ -1077,13 +1069,13 @@ extern "C" int qn_icp_alignment_batch(qn_ctx* const* ctxs, uint32_t n_ctx, const
       const uint32_t i = next.fetch_add(1);
       if (i >= n_pairs) break;
       const qn_pair_desc& p = pairs[i];
-      const bool same = c->batch_share_source && last && last->src == p.src && last->ns == p.ns && last->stride_bytes == p.stride_bytes && last->on_device == p.on_device;
+      const bool same = c->knob.batch_share_source && last && last->src == p.src && last->ns == p.ns && last->stride_bytes == p.stride_bytes && last->on_device == p.on_device;
       status[i] = icp_alignment(c, p.src, p.ns, p.dst, p.nt, p.stride_bytes, thr, &results[i], &valid[i], p.on_device ? 1 : 0, same);
       last = status[i] == QN_OK ? &p : nullptr;
     }
   };
   qn::WorkerPool::instance().run(n_ctx, [&](uint32_t i) { worker(ctxs[i], use_lanes[i] != 0); });      // parked threads, not one std::thread per context per call (qn_pool.h)
-  for (uint32_t i = 0; i < n_ctx; i++) { ctxs[i]->pair_pipeline = saved[i] != 0; ctxs[i]->persist_batch_off = saved_p[i] != 0; }
+  for (uint32_t i = 0; i < n_ctx; i++) { ctxs[i]->knob.pair_pipeline = saved[i] != 0; ctxs[i]->knob.persist_batch_off = saved_p[i] != 0; }
   return QN_OK;
 }
 
@@ -1174,7 +1166,7 @@ extern "C" int qn_gicp_linearize(qn_ctx* c, const double T[16], double H[36], do
   hipStream_t s = c->stream;
   HIPCHK(c, hipMemcpyAsync(c->pose_tmp, T, sizeof(double) * 16, hipMemcpyHostToDevice, s));
   hipLaunchKernelGGL(k_set_pose, dim3(1), dim3(64), 0, s, st_cur(c), c->pose_tmp, 0, 0);
-  enqueue_nn(c, 0, c->sqd, false); enqueue_accumulate(c, 0, false); enqueue_solve(c, 1, 0);
+  enqueue_nn(c, 0, c->sqd); enqueue_accumulate(c, 0, false); enqueue_solve(c, 1, 0);
   GicpState* hs = (GicpState*)malloc(sizeof(GicpState));
   hipError_t e = hipMemcpyAsync(hs, st_cur(c), sizeof(GicpState), hipMemcpyDeviceToHost, s);
   if (e == hipSuccess && corr_out) e = hipMemcpyAsync(corr_out, c->corr, sizeof(int32_t) * c->cloud[0].n, hipMemcpyDeviceToHost, s);
@@ -1214,31 +1206,18 @@ extern "C" int qn_prof_get(qn_ctx* c, int fam, qn_kernel_stat* out) {
 extern "C" int qn_debug_set(qn_ctx* c, const char* key, double v) {
   if (!c || !key) return QN_ERR_INVALID_ARG;
   std::string k(key);
-  if (k == "cell") { c->cell_override = v; c->cloud[0].has_grid = c->cloud[1].has_grid = false; }
-  else if (k == "margin_nn") c->margin_nn = (float)v;
-  else if (k == "margin_nn_t0") c->margin_nn_t0 = (float)v;
-  else if (k == "big_blocks0") c->big_blocks0 = v < 64 ? 64 : (int)v;
-  else if (k == "fb_blocks0") c->fb_blocks0 = v < 64 ? 64 : (int)v;
-  else if (k == "margin_knn") c->margin_knn = (float)v;
-  else if (k == "knn_single_all") c->knn_single_all = v != 0;
-  else if (k == "bbox_blocks") c->bbox_blocks = std::max(1, (int)v);
-  else if (k == "device_look") c->device_look = v != 0;
-  else if (k == "far_group") c->far_group = (int)v;
-  else if (k == "c2f_overlap") c->c2f_overlap = v != 0;
-  else if (k == "quatro_fused") c->quatro_fused = v != 0;
-  else if (k == "tgt_early") c->tgt_early = v != 0;
-  else if (k == "c2f_lanes_fpfh") c->c2f_lanes_fpfh = v != 0;
-  else if (k == "normals_fg") c->normals_fg = (int)v;
-  else if (k == "fpfh_fg") c->fpfh_fg = (int)v;
-  else if (k == "list_small") c->list_small = std::max(0, (int)v);
-  else if (k == "far_chunk") c->far_chunk = std::max(1, (int)v);
-  else if (k == "far_ranked") c->far_ranked = v != 0;
-  else if (k == "batch_look") c->batch_look = v != 0;
-  else if (k == "unseeded_cap") c->unseeded_cap = (int)v;
-  else if (k == "pair_pipeline") c->pair_pipeline = v != 0;
-  else if (k == "persist") c->persist = v != 0;
-  else if (k == "persist_timeout") c->persist_timeout = v < 1 ? 1ull : (unsigned long long)v;      // 100 MHz ticks a spin of the persistent kernel may last (tests force a give-up with a tiny value)
-  else if (k == "prof_persist") c->prof_persist = v != 0;      // profiling (qn_prof_enable) normally times the k_tick chain; 1: let the persistent kernel run and time it as its own family
+  if (k == "cell") { c->lane.cell_override = v; c->cloud[0].has_grid = c->cloud[1].has_grid = false; }
+  else if (k == "device_look") c->knob.device_look = v != 0;
+  else if (k == "far_group") c->lane.far_group = (int)v;
+  else if (k == "tgt_early") c->knob.tgt_early = v != 0;
+  else if (k == "c2f_lanes_fpfh") c->knob.c2f_lanes_fpfh = v != 0;
+  else if (k == "normals_fg") c->feat.normals_fg = (int)v;
+  else if (k == "fpfh_fg") c->feat.fpfh_fg = (int)v;
+  else if (k == "far_ranked") c->lane.far_ranked = v != 0;
+  else if (k == "pair_pipeline") c->knob.pair_pipeline = v != 0;
+  else if (k == "persist") c->knob.persist = v != 0;
+  else if (k == "persist_timeout") c->knob.persist_timeout = v < 1 ? 1ull : (unsigned long long)v;      // 100 MHz ticks a spin of the persistent kernel may last (tests force a give-up with a tiny value)
+  else if (k == "prof_persist") c->knob.prof_persist = v != 0;      // profiling (qn_prof_enable) normally times the k_tick chain; 1: let the persistent kernel run and time it as its own family
   else if (k == "persist_probe") {                              // developer probe: wall-clock stamps inside k_align_persist (qn_debug_get_persist_clk)
     if (v != 0 && !c->pg_clk) { if (hipMalloc(&c->pg_clk, 8 * (64 * 16 + 16)) != hipSuccess) return QN_ERR_HIP; }
     if (c->pg_clk) (void)hipMemset(c->pg_clk, 0, 8 * (64 * 16 + 16));
@@ -1247,41 +1226,29 @@ extern "C" int qn_debug_set(qn_ctx* c, const char* key, double v) {
   else if (k == "batch_lanes") {                                 // candidate pairs per kernel launch of the batch entry points (qn_batch.inc); < 2: one pair at a time on this context's stream
     const int b = std::max(1, std::min((int)v, 64));
     if (b < (int)c->lanes.size()) { if (hipStreamSynchronize(c->stream) != hipSuccess) return QN_ERR_HIP; while ((int)c->lanes.size() > std::max(b, 1)) { qn_ctx* l = c->lanes.back(); c->lanes.pop_back(); if (l != c) qn_ctx_destroy(l); } }
-    c->batch_lanes = b; c->lanes_failed = false;
+    c->knob.batch_lanes = b; c->lanes_failed = false;
   }
-  else if (k == "fail_lane_create") c->fail_lane_create = (int)v;   // test knob: creating lane index >= v fails (the out-of-memory fallback of the batch entry points)
-  else if (k == "batch_share_source") c->batch_share_source = v != 0;      // batch entry points: pairs that name the same source buffer share its preparation (default on: the candidates of one query)
-  else if (k == "batch_trace") c->batch_trace = v != 0;           // developer: host timeline of every batched segment on stderr
-  else if (k == "batch_member") c->persist_batch_off = v != 0;      // this context registers beside others (qn_multi with in_flight > 1): no persistent launches
-  else if (k == "stable_cells") c->stable_cells = v != 0;
-  else if (k == "knn_hist") c->knn_hist = v != 0;
-  else if (k == "nn_rounds") c->nn_rounds = v < 1 ? 1 : (int)v;
-  else if (k == "nn_lane") c->nn_lane = v < 0 ? -1 : (v != 0 ? 1 : 0);                  // first (unseeded) 1-NN pass one query per lane (NnLaneK) instead of the cooperative 16-per-wave search
-  else if (k == "track_from_tick") c->track_from_tick = v < 1 ? 1 : (int)v;
-  else if (k == "single_from_tick") c->single_from_tick = v < 1 ? 1 : (int)v;
-  else if (k == "fused_from_tick") c->fused_from_tick = v < 1 ? 1 : (int)v;
-  else if (k == "knn_rounds") c->knn_rounds = v < 1 ? 1 : (int)v;
-  else if (k == "knn_trips") c->knn_trips = v < 1 ? 1 : (int)v;
-  else if (k == "knn_mm") c->knn_mm = v != 0;
-  else if (k == "fused_ticks") c->fused_ticks = v != 0;
-  else if (k == "big_ratio") c->big_ratio = (float)v;
-  else if (k == "margin_nn_cap") c->margin_nn_cap = (int)v;
-  else if (k == "margin_knn_cap") c->margin_knn_cap = (int)v;
+  else if (k == "fail_lane_create") c->knob.fail_lane_create = (int)v;   // test knob: creating lane index >= v fails (the out-of-memory fallback of the batch entry points)
+  else if (k == "batch_share_source") c->knob.batch_share_source = v != 0;      // batch entry points: pairs that name the same source buffer share its preparation (default on: the candidates of one query)
+  else if (k == "batch_trace") c->knob.batch_trace = v != 0;           // developer: host timeline of every batched segment on stderr
+  else if (k == "batch_member") c->knob.persist_batch_off = v != 0;      // this context registers beside others (qn_multi with in_flight > 1): no persistent launches
+  else if (k == "knn_hist") c->knob.knn_hist = v != 0;
+  else if (k == "nn_lane") c->lane.nn_lane = v < 0 ? -1 : (v != 0 ? 1 : 0);                  // first (unseeded) 1-NN pass one query per lane (NnLaneK) instead of the cooperative 16-per-wave search
+  else if (k == "track_from_tick") c->lane.track_from_tick = v < 1 ? 1 : (int)v;
+  else if (k == "single_from_tick") c->knob.single_from_tick = v < 1 ? 1 : (int)v;
+  else if (k == "knn_trips") c->lane.knn_trips = v < 1 ? 1 : (int)v;
+  else if (k == "knn_mm") c->lane.knn_mm = v != 0;
   else if (k == "dbg_counters") {
     if (v != 0 && !c->dbg_counters) { if (hipMalloc(&c->dbg_counters, 16 * sizeof(uint32_t)) != hipSuccess) return QN_ERR_HIP; }
     if (c->dbg_counters) (void)hipMemset(c->dbg_counters, 0, 16 * sizeof(uint32_t));
     if (v == 0) { (void)hipFree(c->dbg_counters); c->dbg_counters = nullptr; }
     for (int w = 0; w < 2; w++) c->cloud[w].grid.dbg = c->dbg_counters;
   }
-  else if (k == "ticks_per_chunk") c->ticks_per_chunk = std::max(1, (int)v);
-  else if (k == "tick_occ") c->tick_occ = (int)v;
-  else if (k == "far") c->far_enabled = v != 0;
-  else if (k == "fused_final") c->fused_final = v != 0;
-  else if (k == "feat_mfma") c->feat_mfma = v != 0;
-  else if (k == "feat_sample") c->feat_sample = (int)v;
-  else if (k == "feat_query_dedupe") c->feat_query_dedupe = v != 0;
-  else if (k == "feat_min_blocks") c->feat_min_blocks = (int)v;
-  else if (k == "feat_verify") { c->feat_verify = v != 0; if (c->q_mm_vcnt) (void)hipMemset(c->q_mm_vcnt, 0, 16); }
+  else if (k == "far") c->knob.far_enabled = v != 0;
+  else if (k == "feat_mfma") c->feat.mfma = v != 0;
+  else if (k == "feat_sample") c->feat.sample = (int)v;
+  else if (k == "feat_query_dedupe") c->feat.query_dedupe = v != 0;
+  else if (k == "feat_verify") { c->knob.feat_verify = v != 0; if (c->q_mm_vcnt) (void)hipMemset(c->q_mm_vcnt, 0, 16); }
   else if (k == "list_probe") {                                  // developer probe: wall-clock time of the one-per-wave entries of the LAST unseeded list pass (qn_debug_get_list_probe)
     if (v != 0 && !c->list_probe) { if (hipMalloc(&c->list_probe, sizeof(unsigned long long) * 4 * 16384) != hipSuccess) return QN_ERR_HIP; }
     if (v == 0 && c->list_probe) { (void)hipFree(c->list_probe); c->list_probe = nullptr; }
@@ -1291,12 +1258,8 @@ extern "C" int qn_debug_set(qn_ctx* c, const char* key, double v) {
     if (c->clk_probe) (void)hipMemset(c->clk_probe, 0, 8 * 8 * 256 + 8 * 12 * 1024);
     c->clk_n = 0; if (v == 0) { (void)hipFree(c->clk_probe); c->clk_probe = nullptr; }
   }
-  else if (k == "tick_tb") c->tick_tb = v >= 512 ? 512 : 256;
-  else if (k == "tick_ppt_min") c->tick_ppt_min = v < 1 ? 1u : (uint32_t)v;
-  else if (k == "tick_rpb") c->tick_rpb = v < 1 ? 1u : (uint32_t)v;
-  else if (k == "tick_lds_pad") c->tick_lds_pad = v < 0 ? 0 : (int)v;
-  else if (k == "knn_lds_pad") c->knn_lds_pad = v < 0 ? 0 : (int)v;
-  else if (k == "batch_min_share") c->batch_min_share = v < 1 ? 1 : (int)v;
+  else if (k == "tick_rpb") c->lane.tick_rpb = v < 1 ? 1u : (uint32_t)v;
+  else if (k == "batch_min_share") c->knob.batch_min_share = v < 1 ? 1 : (int)v;
   else if (k == "verify_track") {
     if (v != 0 && !c->v_counters) {
       const size_t n = c->max_points;
@@ -1304,7 +1267,7 @@ extern "C" int qn_debug_set(qn_ctx* c, const char* key, double v) {
           hipMalloc(&c->v_nn_ref, 16 * n) != hipSuccess || hipMalloc(&c->v_counters, 16) != hipSuccess) return QN_ERR_HIP;
     }
     if (c->v_counters) (void)hipMemset(c->v_counters, 0, 16);
-    c->verify_track = v != 0;
+    c->knob.verify_track = v != 0;
   }
   else return QN_ERR_INVALID_ARG;
   return QN_OK;
@@ -1574,7 +1537,7 @@ extern "C" int qn_debug_get(qn_ctx* c, const char* key, double* value) {
   if (k == "batch_launches") { *value = (double)c->batch_launches; return QN_OK; }      // kernel launches / pairs of the batched path so far (launches per registration = the ratio)
   if (k == "batch_pairs") { *value = (double)c->batch_pairs; return QN_OK; }
   if (k == "lanes_failed") { *value = c->lanes_failed ? 1.0 : 0.0; return QN_OK; }
-  if (k == "batch_lanes") { *value = (double)c->batch_lanes; return QN_OK; }      // aligns of this context that ran the persistent kernel
+  if (k == "batch_lanes") { *value = (double)c->knob.batch_lanes; return QN_OK; }      // aligns of this context that ran the persistent kernel
   if (k == "feat_fallbacks") { *value = c->feat_fallbacks; return QN_OK; }      // matrix-core feature searches repeated with the VALU kernel (survivor overflow)
   if (k == "feat_survivors") { *value = c->feat_survivors; return QN_OK; }      // survivors of the latest forward search (exactly re-evaluated pairs)
   return QN_ERR_INVALID_ARG;

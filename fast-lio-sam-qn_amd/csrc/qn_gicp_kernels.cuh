@@ -523,7 +523,7 @@ __device__ __forceinline__ uint32_t late(uint32_t v) { asm volatile("" : "+v"(v)
 template <int MODE>
 __device__ __forceinline__ void store_nn(unsigned long long key, uint32_t i, uint32_t t, double thr2, int32_t* __restrict__ corr, float* __restrict__ sqd, int32_t* __restrict__ nn_idx) {
   const float d2 = key_d2(key);
-  if (MODE == 0) nn_idx[t] = key != QN_INF_KEY ? (int32_t)key_idx(key) : -1;     // ungated NN: next iteration's search seed (k_nn_track); -1 = none (non-finite query): never a stale index
+  if (MODE == 0) nn_idx[t] = key != QN_INF_KEY ? (int32_t)key_idx(key) : -1;     // ungated NN: next iteration's search seed (tick_point); -1 = none (non-finite query): never a stale index
   if (MODE == 0) {
     const bool found = key != QN_INF_KEY;
     sqd[i] = found ? d2 : 0.f;
@@ -536,7 +536,7 @@ __device__ __forceinline__ void store_nn(unsigned long long key, uint32_t i, uin
 struct NnOpt { float4* clear_ref; int cond; int group, group_min; unsigned long long* probe; uint32_t fb_small; };       // fb_small: a 16-per-wave list of at most this many entries is served one entry per wave like the far list (0: never); probe: developer timing of the one-per-wave entries (knob list_probe): [4 w] = slowest entry << 32 | entries, [4 w + 1] = busy time of wave w (100 MHz ticks), [4 w + 2] = rounds << 48 | segments << 24 | candidates and [4 w + 3] = first radius | neighbour distance (f32 bits) of that slowest entry; group: far lists of at least group_min entries are served ceil(length / group) consecutive entries per wave, neighbours sharing a scan (0: one per wave); clear_ref: the first search of an align also resets the far-candidate references (one per query); cond: run only if this look flag is set
 // LIST = false: first search of an align (no seed): every source point, radius margin * cell, two rounds,
 // leftovers to fb_list.  LIST = true: the fb_list entries (leftovers of the first search, or the big-ball
-// queries of k_nn_track with their seed radius), 16 per wave, rounds until exact.
+// queries of a tracked pass with their seed radius), 16 per wave, rounds until exact.
 // In the LIST launch the last `big_blocks` blocks serve big_list instead, one query per wave (wave_search_single).
 // BLOCK = threads per block: the grid passes run one wave per block (finer refill of the CUs), the list passes four.
 struct NnSearchArgs { GridView src, tgt; const GicpState* st; double thr2; float r0; int max_rounds; int32_t* corr; float* sqd; int32_t* nn_idx; float4* nn_ref;
@@ -720,7 +720,7 @@ __device__ __forceinline__ void row_store(double* p, double v, const bool cohere
 }
 
 // ------------------------------------------------------------------ K4a'' first (unseeded) pass, one query per LANE
-// The unseeded passes of an align start with ONE round at radius r0 = one cell (margin_nn): the query's ball box is 3 x 3 x 3 cells, i.e. <= 9 (y, z) rows of <= 2
+// The unseeded passes of an align start with ONE round at radius r0 = one cell: the query's ball box is 3 x 3 x 3 cells, i.e. <= 9 (y, z) rows of <= 2
 // segments each (a row crosses a tile boundary at most once), ~40-60 candidates.  The cooperative search (wave_search: 16 queries per wave, cluster boxes, one dense
 // candidate stream staged through LDS) spends ~80 wave-instructions per query on that machinery; here every lane walks ITS OWN box - segment bounds of a whole
 // pass fetched in one go, candidates two at a time - for ~15-20 per query, four times fewer waves and no LDS.  Neighbouring lanes are neighbours in space (cell-sorted
@@ -752,7 +752,7 @@ struct NnLaneK {
     const int y0 = cell_coord(qy - r, tgt.oy, tgt.inv_cell, tgt.ny), y1 = cell_coord(qy + r, tgt.oy, tgt.inv_cell, tgt.ny);
     const int z0 = cell_coord(qz - r, tgt.oz, tgt.inv_cell, tgt.nz), z1 = cell_coord(qz + r, tgt.oz, tgt.inv_cell, tgt.nz);
     const int tx0 = x0 >> 3, ntr = (x1 >> 3) - tx0 + 1, nyr = y1 - y0 + 1, nzr = z1 - z0 + 1;
-    const bool scan = active && nyr <= 3 && nzr <= 3 && ntr <= 2;       // (a wider first radius - knob margin_nn - may not fit: such a query goes to the lists unscanned, with its radius)
+    const bool scan = active && nyr <= 3 && nzr <= 3 && ntr <= 2;       // (a wider first radius would not fit: such a query goes to the lists unscanned, with its radius)
     Best1 sink; sink.init();
     const float4* __restrict__ pts = tgt.pts; const uint32_t* __restrict__ cs = tgt.cell_start;
     // cell_key(x, y, z) = (tile << 7) | (z & 3) << 5 | (y & 3) << 3 | (x & 7) with tile = ((z >> 2) nty + (y >> 2)) ntx + (x >> 3): the z, y and x parts occupy disjoint bits and the
@@ -838,8 +838,7 @@ __global__ void __launch_bounds__(256, 6) k_nn_lane(NnSearchArgs a) { NnLaneK<MO
 // j0 is still the unique nearest neighbour and the scan is skipped - bit-identical result, no search.
 // As the optimiser converges delta -> 0 and almost every query takes this path.
 //
-// The optimiser ticks of the tracked regime use the same logic inside k_tick (qn_tick.cuh); this kernel serves the fitness pass
-// (MODE 1) and the unfused / verification path (MODE 0).
+// The logic lives inside k_tick (qn_tick.cuh, tick_point): the optimiser ticks and the closing pass of the tracked regime; there is no stand-alone tracking kernel.
 #define QN_TRACK_SEG 8
 // The pruning inequality  d(q, p_j0) + |q - q_ref| < d_other  evaluated in f32 with a margin that dominates every rounding
 // error involved.  Exact quantities: D0 = |q - p_j0|, DELTA = |q - q_ref|, B = the stored bound.  Computed: d0 (3 subtractions,
@@ -852,90 +851,6 @@ __global__ void __launch_bounds__(256, 6) k_nn_lane(NnSearchArgs a) { NnLaneK<MO
 // (strict inequality).  tests/test_gpu_adversarial.py exercises it on lattices and at +8 km offsets against a fresh search.
 __device__ __forceinline__ bool track_bound_holds(float d0, float delta, float bound) {
   return (sqrtf(d0) + delta) * 1.000004f < bound;
-}
-template <int MODE>
-__global__ void __launch_bounds__(QN_BLOCK, 6) k_nn_track(GridView src, GridView tgt, const float4* __restrict__ tgt_raw, const GicpState* __restrict__ st,
-                                                       double thr2, int32_t* __restrict__ corr, float* __restrict__ sqd, int32_t* __restrict__ nn_idx,
-                                                       float4* __restrict__ nn_ref, uint2* __restrict__ fb_list, uint32_t* __restrict__ fb_count,
-                                                       uint2* __restrict__ big_list, uint32_t* __restrict__ big_count) {
-  if (MODE == 0 && st->phase != 0) return;
-  if (MODE == 1 && st->phase != 2) return;
-  src = grid_resolve(src); tgt = grid_resolve(tgt);
-  float Tf[12];
-#pragma unroll
-  for (int j = 0; j < 12; j++) Tf[j] = (float)st->x0[j];
-  const uint32_t lblk = xcd_block(blockIdx.x, gridDim.x);          // XCD x tracks one contiguous eighth of the sorted queries
-  const uint32_t t = lblk * QN_BLOCK + threadIdx.x;
-  if (t >= src.n) return;
-  const float INF = __int_as_float(0x7f800000);
-  const float4 p = src.pts[t];
-  const uint32_t i = __float_as_uint(p.w);
-  float qx, qy, qz; xform_query<MODE>(Tf, p.x, p.y, p.z, qx, qy, qz);
-  unsigned long long best = QN_INF_KEY; float second = INF, d_unseen = INF;
-  bool rescanned = false, big = false, noseed = false;              // noseed: nn_idx = -1 after a non-finite pose, or an index from another target
-  float r = 0.f, delta = 0.f;
-  const bool finite_q = (qx - qx == 0.f) && (qy - qy == 0.f) && (qz - qz == 0.f);   // a non-finite query has no neighbour: corr = -1, like the first search
-  const uint32_t j0 = (uint32_t)nn_idx[t];
-  if (finite_q && j0 >= tgt.n) { noseed = true; big = true; r = tgt.cell; }
-  if (finite_q && !noseed) {
-    const float4 ref = nn_ref[t];
-    const float4 p0 = tgt_raw[j0];
-    const float d0 = sqdist(qx, qy, qz, p0.x, p0.y, p0.z);
-    best = pack_key(d0, j0);
-    delta = sqrtf(sqdist(qx, qy, qz, ref.x, ref.y, ref.z));
-    if (track_bound_holds(d0, delta, ref.w)) {                      // proven: j0 is still the unique NN
-      if (tgt.dbg && (threadIdx.x & 63) == 0) atomicAdd(&tgt.dbg[6], (uint32_t)__popcll(__ballot(1)));
-    } else {
-      r = sqrtf(d0) * 1.000001f + tgt.eps;
-      const int bx0 = cell_coord(qx - r, tgt.ox, tgt.inv_cell, tgt.nx), bx1 = cell_coord(qx + r, tgt.ox, tgt.inv_cell, tgt.nx);
-      const int by0 = cell_coord(qy - r, tgt.oy, tgt.inv_cell, tgt.ny), by1 = cell_coord(qy + r, tgt.oy, tgt.inv_cell, tgt.ny);
-      const int bz0 = cell_coord(qz - r, tgt.oz, tgt.inv_cell, tgt.nz), bz1 = cell_coord(qz + r, tgt.oz, tgt.inv_cell, tgt.nz);
-      const int tx0 = bx0 >> 3, ntr = (bx1 >> 3) - tx0 + 1, nyr = by1 - by0 + 1;
-      const int nseg = ntr * nyr * (bz1 - bz0 + 1);
-      if (!(d0 == d0) || nseg > QN_TRACK_SEG) big = true;           // big ball
-      else {
-        uint32_t s[QN_TRACK_SEG], e[QN_TRACK_SEG];
-#pragma unroll
-        for (int sg = 0; sg < QN_TRACK_SEG; sg++) {
-          s[sg] = 0; e[sg] = 0;
-          if (sg < nseg) {
-            int tt, rr; divmod_small(sg, ntr, rr, tt);
-            int qz_, ry_; divmod_small(rr, nyr, qz_, ry_);
-            const int ry = by0 + ry_, rz = bz0 + qz_, tx = tx0 + tt;
-            const int xa = max(bx0, tx << 3), xb = min(bx1, (tx << 3) + 7);
-            const uint32_t k0 = cell_key(tgt, xa, ry, rz);
-            s[sg] = tgt.cell_start[k0]; e[sg] = tgt.cell_start[k0 + (xb - xa) + 1];
-          }
-        }
-#pragma unroll
-        for (int sg = 0; sg < QN_TRACK_SEG; sg++) {
-          for (uint32_t u = s[sg]; u < e[sg]; u++) {
-            const float4 a = tgt.pts[u];
-            const float da = sqdist(qx, qy, qz, a.x, a.y, a.z);
-            const unsigned long long ka = pack_key(da, __float_as_uint(a.w));
-            if (ka < best) { second = key_d2(best); best = ka; }
-            else if (ka != best && da < second) second = da;
-          }
-        }
-        // distance to the faces of the scanned cell box that have unseen cells behind them
-        float d = INF;
-        if (bx0 > 0) d = fminf(d, qx - (tgt.ox + bx0 * tgt.cell));
-        if (bx1 < tgt.nx - 1) d = fminf(d, (tgt.ox + (bx1 + 1) * tgt.cell) - qx);
-        if (by0 > 0) d = fminf(d, qy - (tgt.oy + by0 * tgt.cell));
-        if (by1 < tgt.ny - 1) d = fminf(d, (tgt.oy + (by1 + 1) * tgt.cell) - qy);
-        if (bz0 > 0) d = fminf(d, qz - (tgt.oz + bz0 * tgt.cell));
-        if (bz1 < tgt.nz - 1) d = fminf(d, (tgt.oz + (bz1 + 1) * tgt.cell) - qz);
-        d_unseen = d - tgt.eps; rescanned = true;
-      }
-    }
-  }
-  // list passes, seeded with the bound.  tight seed (the query barely moved since it was scanned) AND far neighbour: one query per wave
-  const bool tight_far = r > 2.5f * tgt.cell && delta < 0.25f * r;
-  wave_append(big_list, big_count, big && tight_far, make_uint2(t, __float_as_uint(r)));
-  wave_append(fb_list, fb_count, big && !tight_far, make_uint2(t, __float_as_uint(noseed ? -r : r)));    // negative: unseeded, continue from |r|
-  if (big) return;
-  store_nn<MODE>(best, i, t, thr2, corr, sqd, nn_idx);
-  if (MODE == 0 && rescanned) nn_ref[t] = make_float4(qx, qy, qz, fminf(sqrtf(second), d_unseen));
 }
 
 // ------------------------------------------------------------------ verification of the tracked passes (debug knob "verify_track")

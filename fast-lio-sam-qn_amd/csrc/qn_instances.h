@@ -30,7 +30,6 @@ namespace qn {
 #define QN_NN_BLOCK 256        // threads per block of the grid-form 1-NN passes (16 queries per wave)
 #define QN_KNN_HIST_ARGS (GridView, int, float, int, int32_t*, float*, uint2*, uint32_t*, uint2*, uint32_t*)
 #define QN_NN_SEARCH_ARGS (GridView, GridView, const GicpState*, double, float, int, int32_t*, float*, int32_t*, float4*, uint2*, uint32_t*, uint2*, uint32_t*, int, float, uint32_t*, NnOpt)
-#define QN_NN_TRACK_ARGS (GridView, GridView, const float4*, const GicpState*, double, int32_t*, float*, int32_t*, float4*, uint2*, uint32_t*, uint2*, uint32_t*)
 
 QN_G1 __global__ void k_knn_hist<false, 32> QN_KNN_HIST_ARGS;
 QN_G1 __global__ void k_knn_hist<true, 32> QN_KNN_HIST_ARGS;
@@ -45,18 +44,9 @@ QN_G1 __global__ void k_nn_search<0, true, QN_BLOCK> QN_NN_SEARCH_ARGS;
 QN_G1 __global__ void k_nn_search<0, true, QN_BLOCK, true> QN_NN_SEARCH_ARGS;
 QN_G1 __global__ void k_nn_search<1, false, QN_NN_BLOCK> QN_NN_SEARCH_ARGS;
 QN_G1 __global__ void k_nn_search<1, true, QN_BLOCK> QN_NN_SEARCH_ARGS;
-QN_G1 __global__ void k_nn_track<0> QN_NN_TRACK_ARGS;
-QN_G1 __global__ void k_nn_track<1> QN_NN_TRACK_ARGS;
-QN_G1 __global__ void k_tick<256, 2, 0, false>(TickArgs);
-QN_G1 __global__ void k_tick<256, 3, 0, false>(TickArgs);
-QN_G1 __global__ void k_tick<256, 4, 0, false>(TickArgs);
-QN_G1 __global__ void k_tick<512, 2, 0, false>(TickArgs);
-QN_G1 __global__ void k_tick<512, 3, 0, false>(TickArgs);
 QN_G1 __global__ void k_tick<512, 4, 0, false>(TickArgs);
-QN_G1 __global__ void k_tick<256, 4, 1, false>(TickArgs);
 QN_G1 __global__ void k_tick<512, 4, 1, false>(TickArgs);
-QN_G1 __global__ void k_tick<256, 4, 0, true>(TickArgs);      // developer variants with device-clock stamps (knob clk_probe)
-QN_G1 __global__ void k_tick<512, 4, 0, true>(TickArgs);
+QN_G1 __global__ void k_tick<512, 4, 0, true>(TickArgs);      // developer variant with device-clock stamps (knob clk_probe)
 // batched launches (k_lanes: blockIdx.y = table entry = one candidate pair / one of its clouds)
 QN_G11 __global__ void k_lanes<KnnHistK<false, 32>>(const LaneEntry<KnnHistArgs>*);
 QN_G11 __global__ void k_lanes<KnnHistK<true, 32>>(const LaneEntry<KnnHistArgs>*);

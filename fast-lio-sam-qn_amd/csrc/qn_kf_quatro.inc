@@ -114,8 +114,8 @@ int kfq_rows(qn_kf_store* s, qn_ctx* c, KfqState* st, const float4* const* vp, c
     std::vector<LaneEntry<NormalsK<8>::Args>> v_nrm; std::vector<LaneEntry<SpfhK<8>::Args>> v_spfh; std::vector<LaneEntry<FpfhK<8>::Args>> v_fpfh; std::vector<LaneEntry<RowsToOriginalK::Args>> v_rows;
     // prep_grid on a CloudBuf of the slot's scratch, with the context's grid rules (max_cells, stable cells) and cell r_f / 2 - the bounding-box accumulator,
     // look-back status words and epoch are the slot's (swapped in around the call)
-    BBoxAcc* const save_acc = c->bbox_acc; unsigned long long* const save_status = c->scan_status; const uint32_t save_epoch = c->build_epoch; const double save_cell = c->cell_override;
-    c->cell_override = rf_d * 0.5;
+    BBoxAcc* const save_acc = c->bbox_acc; unsigned long long* const save_status = c->scan_status; const uint32_t save_epoch = c->build_epoch; const double save_cell = c->lane.cell_override;
+    c->lane.cell_override = rf_d * 0.5;
     char* p = st->pts.p;
     for (size_t j = chunks[ci].first; j < chunks[ci].second; j++) {
       const uint32_t i = live[j], n = vn[i], k = (uint32_t)(j - chunks[ci].first);
@@ -135,14 +135,14 @@ int kfq_rows(qn_kf_store* s, qn_ctx* c, KfqState* st, const float4* const* vp, c
       c->build_epoch = st->epoch - 1;                                               // (prep_grid tags the build with ++build_epoch)
       const GridLaunch G = prep_grid(c, b, (const char*)vp[i], 16, true);
       lane_push(v_pack, G.pack, G.pack_nb); lane_push(v_count, G.count, G.nb); lane_push(v_scan, G.scan, G.scan_nb); lane_push(v_scat, G.scat, G.nb);
-      if (G.stable) lane_push(v_stab, G.stab, G.nb);
+      lane_push(v_stab, G.stab, G.nb);
       const uint32_t nb = (n + QN_BLOCK - 1) / QN_BLOCK;
       lane_push(v_nrm, NormalsK<8>::Args{b.grid, rn, rn2, nrm}, nb * 8u);
       lane_push(v_spfh, SpfhK<8>::Args{b.grid, rf, rf2, nrm, spfh}, nb * 8u);
       lane_push(v_fpfh, FpfhK<8>::Args{b.grid, rf, rf2, nrm, spfh, fpfh_s}, nb * 8u);
       lane_push(v_rows, RowsToOriginalK::Args{b.sorted, n, fpfh_s, rows + QN_FROW * roff[i], QN_FROW, QN_FROW}, nb);
     }
-    c->bbox_acc = save_acc; c->scan_status = save_status; c->build_epoch = save_epoch; c->cell_override = save_cell;
+    c->bbox_acc = save_acc; c->scan_status = save_status; c->build_epoch = save_epoch; c->lane.cell_override = save_cell;
     plan.add<PackBBoxK>(v_pack, QN_K_GRID_BUILD); plan.add<CellCountK>(v_count, QN_K_GRID_BUILD); plan.add<ScanLookbackK>(v_scan, QN_K_GRID_BUILD); plan.add<ScatterK>(v_scat, QN_K_GRID_BUILD); plan.add<StableCellsK>(v_stab, QN_K_GRID_BUILD);
     plan.add<NormalsK<8>>(v_nrm, QN_K_FPFH_NORMALS); plan.add<SpfhK<8>>(v_spfh, QN_K_FPFH_SPFH); plan.add<FpfhK<8>>(v_fpfh, QN_K_FPFH_FPFH); plan.add<RowsToOriginalK>(v_rows, QN_K_FPFH_FPFH);
     if ((rc = plan.run()) != QN_OK) { (void)hipStreamSynchronize(c->stream); qn_kf_int_set_error(s, c->last_error.c_str()); return rc; }

@@ -410,9 +410,10 @@ static void launch_feat_nn_mm(qn_ctx* c, const float* Q, uint32_t nq_max, const 
     }
     per = (tiles + best - 1) / best; ny = (tiles + per - 1) / per;
   };
-  const uint32_t step = (uint32_t)std::max(1, std::min<int>(c->feat_sample, (int)nc_tiles));
+  const uint32_t step = (uint32_t)std::max(1, std::min<int>(c->feat.sample, (int)nc_tiles));
   uint32_t per1, ny1, per2, ny2;
-  split((nc_tiles + step - 1) / step, 512, per1, ny1); split(nc_tiles, (uint32_t)c->feat_min_blocks, per2, ny2);      // (the sampled pass is short: fewer, longer blocks - each loads its query fragments once)
+  constexpr uint32_t FULL_MIN_BLOCKS = 1536;      // smallest grid of the full pass: three rounds of the 512 blocks the chip holds
+  split((nc_tiles + step - 1) / step, 512, per1, ny1); split(nc_tiles, FULL_MIN_BLOCKS, per2, ny2);      // (the sampled pass is short: fewer, longer blocks - each loads its query fragments once)
   const uint32_t cap_spill = c->q_mm_cap / 3, cap_block = (c->q_mm_cap - cap_spill) / (bx * ny2);      // bx * ny2 <= 2048 + bx regions
   uint2* spill = c->q_mm_pairs + (size_t)cap_block * bx * ny2;
   hipLaunchKernelGGL((k_feat_mm<1>), dim3(bx, ny1), dim3(64 * QN_MM_WAVES), 0, s, (const qn_u4*)c->q_mm_q, nq_max, qlist ? qlist_n : (const uint32_t*)nullptr,
@@ -421,7 +422,7 @@ static void launch_feat_nn_mm(qn_ctx* c, const float* Q, uint32_t nq_max, const 
                      (const qn_u4*)c->q_mm_c, nc_tiles, per2, 1u, c->q_mm_L, (const float*)c->q_mm_qn, c->q_mm_pairs, c->q_mm_cnt, cap_block, spill, cap_spill);
   hipLaunchKernelGGL(k_feat_exact, dim3(bx * ny2 + 256), dim3(256), 0, s, (const uint2*)c->q_mm_pairs, (const uint32_t*)c->q_mm_cnt, cap_block, bx * ny2, (const uint2*)spill, cap_spill,
                      Q, qlist, C, nc, keys, mm_overflow);
-  if (c->feat_verify) {                                                      // developer check: the VALU search of the same queries, compared key by key
+  if (c->knob.feat_verify) {                                                      // developer check: the VALU search of the same queries, compared key by key
     if (!c->q_mm_vkeys) { (void)hipMalloc(&c->q_mm_vkeys, sizeof(unsigned long long) * c->max_points); (void)hipMalloc(&c->q_mm_vcnt, 16); (void)hipMemsetAsync(c->q_mm_vcnt, 0, 16, s); }
     hipLaunchKernelGGL(k_fill_u64, dim3((c->max_points + 255) / 256), dim3(256), 0, s, c->q_mm_vkeys, (uint32_t)c->max_points, QN_INF_KEY);
     hipLaunchKernelGGL(k_pair_rows, dim3((((nc + 1) / 2) * 34 + 255) / 256), dim3(256), 0, s, C, nc, (qn_v2f*)c->q_pair[cand_slot], c->q_pair_hash[cand_slot]);
@@ -447,8 +448,8 @@ static int quatro_match_enqueue(qn_ctx* c, uint32_t ns, uint32_t nt, const qn_qu
   QuatroTailOut* head = (QuatroTailOut*)c->q_host; QuatroCorr* recs = (QuatroCorr*)(head + 1);
   head->n_cand = 0; head->n_sel = 0; head->overflow = 0; head->pad = 0;
   if (join_target(c) != QN_OK) return QN_ERR_HIP;                            // the target's descriptors were made on the second stream
-  const bool mm = c->feat_mfma && !c->feat_mm_retry;
-  const bool fused = mm && c->quatro_fused && !(c->feat_query_dedupe && !c->feat_verify);      // the fused bookkeeping launches (round 5); knob quatro_fused = 0: the one-launch-per-step sequence
+  const bool mm = c->feat.mfma && !c->feat_mm_retry;
+  const bool fused = mm && !(c->feat.query_dedupe && !c->knob.feat_verify);      // the fused bookkeeping launches (round 5); without the matrix-core search, or with the query de-duplication: the one-launch-per-step sequence
   const uint32_t mm_table_n = c->q_mm_mask + 1u;
   if (fused) {      // ONE launch: counters, hit flags, both key arrays, both row-hash passes, and the matrix-core search's table / bounds / counters for the forward search
     ProfScope ps(c, QN_K_FEAT_MATCH);
@@ -467,7 +468,7 @@ static int quatro_match_enqueue(qn_ctx* c, uint32_t ns, uint32_t nt, const qn_qu
       if (!mm) hipLaunchKernelGGL(k_pair_rows, dim3((((nw + 1) / 2) * 34 + 255) / 256), dim3(256), 0, s, c->q_fpfh[w], nw, (qn_v2f*)c->q_pair[w], c->q_pair_hash[w]);
     } }
   }
-  if (mm && c->feat_query_dedupe && !c->feat_verify) {                       // every DISTINCT row of j -> nearest i, the other rows copy their representative's key (the developer check verifies every query: all of them are searched then)
+  if (mm && c->feat.query_dedupe && !c->knob.feat_verify) {                       // every DISTINCT row of j -> nearest i, the other rows copy their representative's key (the developer check verifies every query: all of them are searched then)
     { ProfScope ps(c, QN_K_FEAT_MATCH);
       (void)hipMemsetAsync(c->q_mm_table_q, 0xFF, sizeof(unsigned long long) * ((size_t)c->q_mm_mask + 1), s);
       hipLaunchKernelGGL(k_feat_dedupe, dim3((nj + 255) / 256), dim3(256), 0, s, (const float*)c->q_fpfh[J], nj, c->q_mm_table_q, c->q_mm_mask, &c->q_counts[2]);
@@ -515,7 +516,7 @@ static int quatro_match_enqueue(qn_ctx* c, uint32_t ns, uint32_t nt, const qn_qu
 static int quatro_match_collect(qn_ctx* c, uint32_t ns, uint32_t nt, const qn_quatro_params& p, bool want_mutual, qnq::TailResult& out) {
   const bool swapped = nt > ns;
   QuatroTailOut* head = (QuatroTailOut*)c->q_host; QuatroCorr* recs = (QuatroCorr*)(head + 1);
-  const bool mm = c->feat_mfma && !c->feat_mm_retry;
+  const bool mm = c->feat.mfma && !c->feat_mm_retry;
   c->prof_collect();
   { const int vrc = clouds_valid(c); if (vrc != QN_OK) return vrc; }
   if (mm && head->pad) {                                                     // survivor list overflow (pathological descriptor sets): the VALU search, same answer
@@ -556,11 +557,11 @@ static int quatro_features(qn_ctx* c, const float* src, uint32_t ns, const float
   int rc;
   if (!c->qparams_set) qn_quatro_default_params(&c->qparams), c->qparams_set = true;
   if ((rc = quatro_alloc(c)) != QN_OK) return rc;
-  const double save = c->cell_override;
-  c->cell_override = c->qparams.fpfh_radius * 0.5;
+  const double save = c->lane.cell_override;
+  c->lane.cell_override = c->qparams.fpfh_radius * 0.5;
   rc = set_cloud(c, QN_SOURCE, src, ns, stride, on_device);
   if (rc == QN_OK) rc = set_cloud(c, QN_TARGET, dst, nt, stride, on_device);     // on the second stream when the context has one (TargetScope, qn_engine.hip)
-  c->cell_override = save;
+  c->lane.cell_override = save;
   if (rc != QN_OK) return rc;
   if ((rc = quatro_fpfh(c, 0)) != QN_OK) return rc;
   // the target's descriptors follow its grid build on the second stream, concurrently with the source's on the first (the clouds are
@@ -575,10 +576,10 @@ static int quatro_features_target_only(qn_ctx* c, const float* dst, uint32_t nt,
   int rc;
   if (!c->qparams_set) qn_quatro_default_params(&c->qparams), c->qparams_set = true;
   if ((rc = quatro_alloc(c)) != QN_OK) return rc;
-  const double save = c->cell_override;
-  c->cell_override = c->qparams.fpfh_radius * 0.5;
+  const double save = c->lane.cell_override;
+  c->lane.cell_override = c->qparams.fpfh_radius * 0.5;
   rc = set_cloud(c, QN_TARGET, dst, nt, stride, on_device);
-  c->cell_override = save;
+  c->lane.cell_override = save;
   if (rc != QN_OK) return rc;
   return quatro_fpfh(c, 1);
 }
@@ -592,10 +593,10 @@ extern "C" int qn_fpfh(qn_ctx* c, const float* xyz, uint32_t n, uint32_t stride,
   int rc;
   if (!c->qparams_set) qn_quatro_default_params(&c->qparams), c->qparams_set = true;
   if ((rc = quatro_alloc(c)) != QN_OK) return rc;
-  const double save = c->cell_override;
-  c->cell_override = c->qparams.fpfh_radius * 0.5;
+  const double save = c->lane.cell_override;
+  c->lane.cell_override = c->qparams.fpfh_radius * 0.5;
   rc = set_cloud(c, QN_SOURCE, xyz, n, stride, false);
-  c->cell_override = save;
+  c->lane.cell_override = save;
   if (rc != QN_OK) return rc;
   if ((rc = quatro_fpfh(c, 0)) != QN_OK) return rc;
   std::vector<float> rows((size_t)n * QN_FROW);
@@ -765,31 +766,7 @@ static int coarse_to_fine(qn_ctx* c, const float* src, uint32_t ns, const float*
   for (int i = 0; i < 4; i++) { out->T[5 * i] = 1.f; out->T64[5 * i] = 1.0; }      // (a pair Quatro cannot register reports the identity, like the batched entry point - ADVICE r5: the two paths' records are the same bytes)
   for (int i = 0; i < 16; i++) T_total[i] = (i % 5 == 0) ? 1.0 : 0.0;
   double Tq[16]; int qvalid = 0;
-  // The fine stage's TARGET (setInputTarget + calculateTargetCovariances, :122-123 inside icpAlignment) depends on nothing Quatro computes: its grid build, k-NN and
-  // covariances are enqueued right behind Quatro's matching - on the second stream when the context has one, next to the matching; otherwise behind it, where the
-  // GPU would idle during the host solver - instead of after the solve.  Quatro's tail only reads the target's raw points and descriptor rows; the fine stage re-packs the same
-  // values into the same raw buffer and builds ITS grid (different cell edge) in the sorted / table buffers Quatro's FPFH kernels are done with (stream order).
-  bool target_ready = false;
-  int rc;
-  if (c->c2f_overlap && !c->prof_on && ns && nt) {
-    for (int i = 0; i < 16; i++) Tq[i] = (i % 5 == 0) ? 1.0 : 0.0;
-    HIPCHK(c, hipSetDevice(c->device));
-    const auto w0 = std::chrono::steady_clock::now();
-    if ((rc = quatro_features(c, src, ns, dst, nt, stride, on_device)) == QN_OK && (rc = quatro_match_enqueue(c, ns, nt, c->qparams)) == QN_OK) {
-      const auto w1 = std::chrono::steady_clock::now();
-      const bool tp = set_cloud(c, QN_TARGET, dst, nt, stride, on_device) == QN_OK && qn_gicp_compute_covariances(c, QN_TARGET) == QN_OK;
-      if (hipStreamSynchronize(c->stream) != hipSuccess) { c->last_error = "coarse-to-fine: stream synchronisation failed"; return QN_ERR_HIP; }
-      qnq::TailResult tr;
-      if ((rc = quatro_match_collect(c, ns, nt, c->qparams, false, tr)) == QN_OK) {
-        const auto w2 = std::chrono::steady_clock::now();
-        qnq::SolveOut so; qnq::solve(tr.S, tr.D, c->qparams, &so);
-        memcpy(Tq, so.T, sizeof(so.T)); qvalid = so.valid; target_ready = tp; c->q_last_scale = so.scale;
-        const auto w3 = std::chrono::steady_clock::now();
-        c->q_wall_ms[0] = std::chrono::duration<double, std::milli>(w1 - w0).count(); c->q_wall_ms[1] = std::chrono::duration<double, std::milli>(w2 - w1).count(); c->q_wall_ms[2] = std::chrono::duration<double, std::milli>(w3 - w2).count();
-      }
-    }
-  }
-  else rc = quatro_align_impl(c, src, ns, dst, nt, stride, on_device, Tq, &qvalid, nullptr, nullptr);   // :144
+  int rc = quatro_align_impl(c, src, ns, dst, nt, stride, on_device, Tq, &qvalid, nullptr, nullptr);   // :144
   if (T_quatro) memcpy(T_quatro, Tq, sizeof(Tq));
   if (rc != QN_OK) return rc;
   if (stage) *stage = 1;
@@ -799,7 +776,7 @@ static int coarse_to_fine(qn_ctx* c, const float* src, uint32_t ns, const float*
   HIPCHK(c, hipMemcpyAsync(c->q_T, Tq, sizeof(Tq), hipMemcpyHostToDevice, s));
   hipLaunchKernelGGL(k_transform_cloud_f64, dim3((ns + 255) / 256), dim3(256), 0, s, c->cloud[0].raw, ns, c->q_T, c->aligned);
   int gvalid = 0;
-  rc = icp_alignment(c, (const float*)c->aligned, ns, dst, nt, stride, score_thr, out, &gvalid, on_device ? 3 : 2, false, target_ready);   // :153 (the coarse-aligned source stays on the device)
+  rc = icp_alignment(c, (const float*)c->aligned, ns, dst, nt, stride, score_thr, out, &gvalid, on_device ? 3 : 2);   // :153 (the coarse-aligned source stays on the device)
   if (rc != QN_OK) return rc;
   if (stage) *stage = 2;
   *valid = gvalid;
@@ -889,14 +866,14 @@ int c2f_run(qn_ctx* owner, const qn_pair_desc* pairs, const uint32_t* idx, uint3
   // pairs on a stream that serialises them; the matching stage (K12 / K13) follows per lane.  MEASURED NEUTRAL TO SLIGHTLY SLOWER (qn_context.h, EXPERIMENTS.md round 5): with 3-8 contexts in
   // flight the small launches of one stream hide behind the other streams' kernels and the FPFH kernels themselves are issue-bound - so the default (knob c2f_lanes_fpfh = 0) is
   // that every lane launches its own, the one-pair path's calls; the lanes form stays as a tested variant (tests/test_gpu_c2f_batch.py).
-  const bool lanes_fpfh = owner->c2f_lanes_fpfh && owner->normals_fg <= 0 && owner->fpfh_fg <= 0;
+  const bool lanes_fpfh = owner->knob.c2f_lanes_fpfh && owner->feat.normals_fg <= 0 && owner->feat.fpfh_fg <= 0;
   LanePlan plan(owner);
   std::vector<LaneEntry<PackBBoxK::Args>> v_pack; std::vector<LaneEntry<CellCountK::Args>> v_count; std::vector<LaneEntry<ScanLookbackK::Args>> v_scan;
   std::vector<LaneEntry<ScatterK::Args>> v_scat; std::vector<LaneEntry<StableCellsK::Args>> v_stab;
   std::vector<LaneEntry<NormalsK<8>::Args>> v_nrm; std::vector<LaneEntry<SpfhK<8>::Args>> v_spfh; std::vector<LaneEntry<FpfhK<8>::Args>> v_fpfh; std::vector<LaneEntry<RowsToOriginalK::Args>> v_rows;
   auto push_grid = [&](const GridLaunch& G) {
     lane_push(v_pack, G.pack, G.pack_nb); lane_push(v_count, G.count, G.nb); lane_push(v_scan, G.scan, G.scan_nb); lane_push(v_scat, G.scat, G.nb);
-    if (G.stable) lane_push(v_stab, G.stab, G.nb);
+    lane_push(v_stab, G.stab, G.nb);
   };
   auto push_fpfh = [&](qn_ctx* c, int w) {      // quatro_fpfh(c, w) as table entries
     CloudBuf& b = c->cloud[w];
@@ -916,8 +893,8 @@ int c2f_run(qn_ctx* owner, const qn_pair_desc* pairs, const uint32_t* idx, uint3
     valid[q.pair] = 0; memset(out, 0, sizeof(*out)); out->fitness = DBL_MAX;
     for (int i = 0; i < 4; i++) { out->T[5 * i] = 1.f; out->T64[5 * i] = 1.0; }
     for (int i = 0; i < 16; i++) { q.Tq[i] = (i % 5 == 0) ? 1.0 : 0.0; T_total[16 * (size_t)q.pair + i] = q.Tq[i]; if (T_quatro) T_quatro[16 * (size_t)q.pair + i] = q.Tq[i]; }
-    if (c != owner) { c->qparams = owner->qparams; c->qparams_set = owner->qparams_set; c->feat_mfma = owner->feat_mfma; c->feat_sample = owner->feat_sample; c->feat_min_blocks = owner->feat_min_blocks; c->feat_query_dedupe = owner->feat_query_dedupe; c->normals_fg = owner->normals_fg; c->fpfh_fg = owner->fpfh_fg; c->quatro_fused = owner->quatro_fused; }
-    c->pair_pipeline = false; c->tgt_pending = false; c->tgt_on_stream2 = false;
+    if (c != owner) { c->qparams = owner->qparams; c->qparams_set = owner->qparams_set; c->feat = owner->feat; }
+    c->knob.pair_pipeline = false; c->tgt_pending = false; c->tgt_on_stream2 = false;
     if (pd.ns == 0 || pd.nt == 0) { q.rc = QN_ERR_EMPTY_CLOUD; continue; }
     if ((q.rc = c2f_alloc(owner, c)) != QN_OK) return q.rc;
     if ((q.rc = quatro_alloc(c)) != QN_OK) { owner->last_error = c->last_error; return q.rc; }      // (the lane's own buffers exist before any of them is swapped out)
@@ -931,7 +908,7 @@ int c2f_run(qn_ctx* owner, const qn_pair_desc* pairs, const uint32_t* idx, uint3
     }
     // the candidates of ONE query name the same source buffer: the first lane of the run that carries it prepares it (grid, normals, SPFH, FPFH), the others borrow
     // the result (read-only from here on: the matching reads raw points and descriptor rows, the row hashes written into the rows are the same for every borrower)
-    if (owner->batch_share_source && pd.src != nullptr) {
+    if (owner->knob.batch_share_source && pd.src != nullptr) {
       for (uint32_t j = 0; j < l; j++) {
         const qn_pair_desc& pj = pairs[S[j].pair];
         if ((S[j].enq || pending[j]) && S[j].alias < 0 && pj.src == pd.src && pj.ns == pd.ns && pj.stride_bytes == pd.stride_bytes && pj.on_device == pd.on_device) { q.alias = (int)j; break; }
@@ -948,12 +925,12 @@ int c2f_run(qn_ctx* owner, const qn_pair_desc* pairs, const uint32_t* idx, uint3
       continue;
     }
     // setInputCloud of both clouds as table entries (validation and upload as set_cloud; FPFH grid: cell = r_f / 2), the target with the second scratch set
-    const double save = c->cell_override;
-    c->cell_override = c->qparams.fpfh_radius * 0.5;
+    const double save = c->lane.cell_override;
+    c->lane.cell_override = c->qparams.fpfh_radius * 0.5;
     GridLaunch gs, gt; int rc = QN_OK;
     if (q.alias < 0) rc = lane_set_cloud(c, QN_SOURCE, pd.src, pd.ns, pd.stride_bytes, pd.on_device != 0, s, &gs);
     if (rc == QN_OK) { ScratchSwap sw(c); rc = lane_set_cloud(c, QN_TARGET, pd.dst, pd.nt, pd.stride_bytes, pd.on_device != 0, s, &gt); }
-    c->cell_override = save;
+    c->lane.cell_override = save;
     if (rc == QN_ERR_HIP) { owner->last_error = c->last_error; return rc; }
     q.rc = rc;
     if (rc != QN_OK) { if (q.alias < 0) { c->cloud[0].has_grid = false; c->cloud[0].n = 0; } c->cloud[1].has_grid = false; c->cloud[1].n = 0; q.alias = -1; continue; }
@@ -1040,7 +1017,7 @@ static int c2f_batch(qn_ctx* const* ctxs, uint32_t n_ctx, const qn_pair_desc* pa
     if (join_target(c) != QN_OK) { wrc[w] = QN_ERR_HIP; return; }
     if (!c->qparams_set) { qn_quatro_default_params(&c->qparams); c->qparams_set = true; }
     const bool lanes_ok = batch_supported(c) && batch_ensure_lanes(c) == QN_OK;
-    const bool sp = c->pair_pipeline, sb = c->persist_batch_off;
+    const bool sp = c->knob.pair_pipeline, sb = c->knob.persist_batch_off;
     if (!lanes_ok) {                                                              // (knobs that rule the lanes out: the one-pair path, pair by pair - same records)
       for (;;) {
         const uint32_t i = next.fetch_add(1);
@@ -1061,7 +1038,7 @@ static int c2f_batch(qn_ctx* const* ctxs, uint32_t n_ctx, const qn_pair_desc* pa
         if (rem > n_ctx * B) m = B;
         else {
           uint32_t q = final_share.load();
-          if (q == 0) { uint32_t want = std::min<uint32_t>(B, std::max<uint32_t>((uint32_t)std::max(1, ctxs[0]->batch_min_share), (rem + n_ctx - 1) / n_ctx)); if (final_share.compare_exchange_strong(q, want)) q = want; }
+          if (q == 0) { uint32_t want = std::min<uint32_t>(B, std::max<uint32_t>((uint32_t)std::max(1, ctxs[0]->knob.batch_min_share), (rem + n_ctx - 1) / n_ctx)); if (final_share.compare_exchange_strong(q, want)) q = want; }
           m = std::min(q, rem);
         }
         m = std::min(m, B);                                             // (never more pairs than THIS context has lanes: the share was fixed with the first context's lane count - ADVICE r5)
@@ -1072,7 +1049,7 @@ static int c2f_batch(qn_ctx* const* ctxs, uint32_t n_ctx, const qn_pair_desc* pa
       const int rc = c2f_run(c, pairs, idx.data(), m, score_thr, results, T_total, T_quatro, valid, status, cached, stage);
       if (rc != QN_OK) { (void)hipStreamSynchronize(c->stream); for (uint32_t l = 0; l < m; l++) { status[base + l] = rc; valid[base + l] = 0; } wrc[w] = rc; }
     }
-    c->pair_pipeline = sp; c->persist_batch_off = sb;
+    c->knob.pair_pipeline = sp; c->knob.persist_batch_off = sb;
   };
   qn::WorkerPool::instance().run(n_ctx, worker);
   return QN_OK;

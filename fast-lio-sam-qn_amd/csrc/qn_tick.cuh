@@ -230,7 +230,7 @@ struct Top2 { int32_t j1; float4 p1; };                                // j1 = -
 
 // One source point of a tick (the body of k_tick's loop; also the body of the persistent align kernel, qn_persist.cuh).
 //   lin = false   LM trial error: the cached correspondence rec0 at the trial pose xi, gate as at the linearisation;
-//   lin = true    tracked exact 1-NN at the pose x0 (k_nn_track's logic: bound pruning, in-lane rescan of <= QN_TRACK_SEG segments, far-query cache,
+//   lin = true    tracked exact 1-NN at the pose x0 (temporal tracking, qn_gicp_kernels.cuh: bound pruning, in-lane rescan of <= QN_TRACK_SEG segments, far-query cache,
 //                 cooperative big-ball search 16 queries at a time) and the correspondence's contribution to the 28 sums, or (MODE 1) its squared distance
 //                 and the transformed point of the output cloud.
 // sx0 / sxi: the f64 poses in LDS (fetched only where the sums are formed: the search and the accumulation are the two register-hungry parts, their live
@@ -256,7 +256,7 @@ __device__ __forceinline__ void tick_point(const TickArgs& a, const float (&Tf)[
     emit_point(have, false, first, sx0, sxi, sG, make_float4(p.x, p.y, p.z, 1.f), rec0.p, na, rec0.n, red, wrow);
     return;
   }
-  // ---- phase 0: tracked exact 1-NN (k_nn_track's logic: bound pruning, small in-lane rescan, cooperative big-ball search)
+  // ---- phase 0: tracked exact 1-NN (temporal tracking, qn_gicp_kernels.cuh: bound pruning, small in-lane rescan, cooperative big-ball search)
   float second = INF, d_unseen = INF, r = 0.f, delta = 0.f;
   bool rescanned = false, big = false;
   unsigned long long key2 = QN_INF_KEY; float third = INF;          // TOP2: the runner-up's key and the squared distance of the third-nearest, as far as this tick's scan knows them

@@ -1230,7 +1230,8 @@ int  qn_gicp_compute_error(qn_ctx*, const double T[16], double* err); /* cached 
 int  qn_prof_enable(qn_ctx*, int on);                /* records a hipEvent pair around every kernel family launch */
 int  qn_prof_reset(qn_ctx*);
 int  qn_prof_get(qn_ctx*, int kernel_family, qn_kernel_stat* out);
-/* developer knobs (cell size, margins, debug counters); not part of the reference surface */
+/* developer knobs (cell size, regime switches, probes, debug counters: the sub-structs LaneKnobs / FeatKnobs / OwnKnobs of csrc/qn_context.h list them); an unknown key is
+ * QN_ERR_INVALID_ARG.  Not part of the reference surface */
 int  qn_debug_set(qn_ctx*, const char* key, double value);
 int  qn_debug_get_counters(qn_ctx*, uint32_t out[16]);
 int  qn_debug_selftest(qn_ctx*, uint32_t n_waves, uint32_t seed, uint32_t* mismatches);      /* developer / tests: the device's wave-level search primitives against plain restatements (csrc/qn_selftest.cuh) */
@@ -1311,7 +1312,7 @@ int  qn_debug_linearize(qn_ctx*, int which, const double* in, uint32_t n, uint32
  * a non-finite coordinate, a radius that is not finite and > 0, max_rounds outside 1 .. 64, a KMAX other than the four, k outside 1 .. KMAX, a tile or box outside the grid, a tile-mode box not widened to
  * whole tiles, n or arg of 0 other than the grid's.  QN_ERR_NOT_READY: the context has no grid for that cloud; QN_ERR_EMPTY_CLOUD: the grid is empty (non-finite
  * cloud).  Non-finite queries are refused.  By grep for finite_q, the product callers that screen them before they search are k_nn_search's grouped list
- * pass (wave_search_far16), k_nn_track and k_tick; the queries of the k-NN kernels are the cloud's own points, finite because the grid build empties a cloud
+ * pass (wave_search_far16) and k_tick; the queries of the k-NN kernels are the cloud's own points, finite because the grid build empties a cloud
  * that holds another.  NOT screened: k_nn_search's first pass (wave_search<4>) and its one-entry-per-wave list pass (wave_search_single) hand a query over as
  * the pose made it and rely on the searches' own `r == r` exits - those exits are not reached through this entry point.  Nothing on a product path calls it. */
 #define QN_DEBUG_SEARCH_WHICH 13

@@ -1,4 +1,4 @@
-"""Adversarial inputs for the tracked / bound-pruned nearest-neighbour passes (k_nn_track, qn_gicp_kernels.cuh): every tracked pass of
+"""Adversarial inputs for the tracked / bound-pruned nearest-neighbour passes (the tracking of k_tick, qn_tick.cuh): every tracked pass of
 an align() is compared, ALL queries, with a fresh unseeded search of the same pose (debug knob "verify_track": indices and, where the
 pass stores them, the f32 squared distances bit for bit).  The pruning inequality  d(q, p_j0) + |q - q_ref| < d_other  carries a
 rounding margin (track_bound_holds); these cases sit where it could break:

@@ -42,7 +42,7 @@ def test_nn_exact_vs_bruteforce_on_sample(setup):
             j = D.argmin(1)
             assert np.array_equal(sqd[sel[a:a + 250]], D[np.arange(len(j)), j])
             assert np.array_equal(corr[sel[a:a + 250]], j)
-    # tracked passes: forced iterations run k_nn_track with bound pruning; the final fitness equals a fresh brute-force one on the sample
+    # tracked passes: forced iterations run the tracked ticks with bound pruning; the final fitness equals a fresh brute-force one on the sample
     g.setOptimizer("gn"); g.setForceIterations(8); g.setMaximumIterations(8)
     r = g.align(); Tf = np.array(r.T, dtype=np.float32).reshape(4, 4)
     al = g.alignedCloud()
